@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — ICP iterations/sec at |F|=|M|=16384, |R|=256 (BASELINE.json metric) on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config A|B|C] [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--config A|B|C] [--batch B] [--dump-outputs DIR]
 
 A "step" is one fixed-length registration pass of the hot path: starting from the identity transform,
 `iterations_per_step` (40 = the length of the reference's profiling run, include/ICP/algorithms.hpp:2482-2494; 10 at
@@ -805,6 +805,51 @@ def emit(full, out=None, err=None, extra_dirs=None):
     return text
 
 
+DUMP_LIMIT = 64 << 20                            # bytes of all --dump-outputs arrays together
+DUMP_SEED = 0x1C9D5EED                           # the fixed sample of points when the whole outputs would not fit
+
+
+def outputs_of(icp_amd, read, state, n, m):
+    """What a caller of the timed path receives after its last step, for each of its `n` registrations (read(i, mem), state(i)): the transform
+    T = [q (4) t (3) s], the rotation R and, per point of F, the distance and index of its correspondence and its weight.  float32 / float64
+    only: an index below 2^24 is exact in float32.  Larger than DUMP_LIMIT in all: the per-point arrays keep a fixed, seeded sample of the
+    points (the same for every registration), whose indices go in `point_index`."""
+    import numpy as np
+    per_point = 4 + 4 + (4 if m <= 1 << 24 else 8)
+    small = n * (8 + 9) * 4
+    idx = None
+    if small + n * m * per_point > DUMP_LIMIT:
+        k = max(1, (DUMP_LIMIT - small) // (n * per_point + 8))
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(m, size=k, replace=False))
+    pick = (lambda a: a) if idx is None else (lambda a: a[idx])
+    T, R, dist, nn_id, w = [], [], [], [], []
+    for i in range(n):
+        T.append(read(i, icp_amd.Memory.T))
+        R.append(np.array(state(i).R, np.float32).reshape(3, 3))
+        nn = read(i, icp_amd.Memory.NN_ID)
+        dist.append(pick(nn["dist"]))
+        nn_id.append(pick(nn["id"]).astype(np.float32 if m <= 1 << 24 else np.float64))
+        w.append(pick(read(i, icp_amd.Memory.W)))
+    out = {"T": np.stack(T), "R": np.stack(R), "nn_dist": np.stack(dist), "nn_id": np.stack(nn_id), "w": np.stack(w)}
+    if idx is not None:
+        out["point_index"] = idx.astype(np.float64)
+    return out
+
+
+def dump_outputs(directory, arrays, err=None):
+    """--dump-outputs: every array of `arrays` as directory/<name>.npy."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= DUMP_LIMIT, total
+    (err or sys.stderr).write("bench.py: outputs of the last timed step in %s (%s; %d bytes)\n" % (directory, ", ".join(sorted(arrays)), total))
+    return total
+
+
 def run_inprocess(icp_amd, args, n, batch, iters, steps, warmup):
     """--gpus N from a plain `python bench.py`: devices 0..N-1 (or ICP_BENCH_DEVICES, a comma list: self-test on a 1-GPU box)
     driven through icp_batch_*: registration i on slot i mod N, one host thread + stream per slot, no collective."""
@@ -828,6 +873,8 @@ def run_inprocess(icp_amd, args, n, batch, iters, steps, warmup):
         B.write(i, icp_amd.Memory.M, M)
     B.buildRBC()
     seconds, slot_ms = B.time_run_fixed_slots(iters, steps, warmup + 5)      # (+ 5 untimed passes per slot: the set-up's settle (), see there)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs_of(icp_amd, B.read, B.state, n * batch, m))
     B.close()
     per_gpu = [float(steps * iters * batch / (float(ms) * 1e-3)) for ms in slot_ms]
     return seconds, steps * iters * batch * n, per_gpu, devices
@@ -847,6 +894,9 @@ def main():
     ap.add_argument("--batch", type=int, default=0,
                     help="independent registrations per GPU sharing each launch; default: 1 on one GPU (the headline metric), "
                          "64 per GPU on several (BASELINE config 4)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (T, R, correspondences, weights of every registration; "
+                         "rank 0's under torch.distributed.run) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
 
     launch, world = resolve_launch(args.gpus, os.environ)
@@ -959,6 +1009,8 @@ def main():
         elapsed = time.perf_counter() - t0
         total_t, total_iters = aggregate(dist, elapsed, steps * iters * batch)
         per_gpu = gather_per_rank(dist, steps * iters * batch / elapsed)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, outputs_of(icp_amd, lambda i, mem: g.read(mem, batch_index=i), g.state, batch, m))
 
     # beside the metric (never part of `value`): latency of one whole registration = RBC construction + the iterations,
     # inputs resident, and the same with the two clouds uploaded from host memory first

@@ -118,3 +118,51 @@ def test_cpu_sweep_never_oversubscribes_the_share():
     assert bench.sweep_counts(8.0, 8) == [1, 8]
     assert bench.sweep_counts(96.0, 256) == [1, 8, 16, 64, 96]
     assert bench.sweep_counts(0.5, 4) == [1]
+
+
+def _fake_engine(n, m):
+    """read(i, mem) / state(i) of `n` registrations of `m` points with values that tell registration and point apart."""
+    import icp_amd
+    from types import SimpleNamespace
+
+    def read(i, mem):
+        if mem == icp_amd.Memory.T:
+            return np.arange(8, dtype=np.float32) + 100 * i
+        if mem == icp_amd.Memory.NN_ID:
+            nn = np.empty(m, icp_amd.DIST_ID)
+            nn["dist"] = np.arange(m, dtype=np.float32) + 0.5 + i
+            nn["id"] = (np.arange(m, dtype=np.uint32) * 7 + i) % m
+            return nn
+        if mem == icp_amd.Memory.W:
+            return np.full(m, 1.0 / (i + 1), np.float32)
+        raise AssertionError(mem)
+    return icp_amd, read, lambda i: SimpleNamespace(R=[float(i)] * 9)
+
+
+def test_dump_outputs_writes_what_the_caller_receives(tmp_path):
+    """--dump-outputs: T, R and the per-point correspondences and weights of every registration, float32 / float64 only, all points when
+    they fit (no `point_index`)."""
+    n, m = 3, 1000
+    icp_amd, read, state = _fake_engine(n, m)
+    out = bench.outputs_of(icp_amd, read, state, n, m)
+    total = bench.dump_outputs(str(tmp_path), out)
+    got = {p.stem: np.load(p) for p in tmp_path.iterdir()}
+    assert sorted(got) == ["R", "T", "nn_dist", "nn_id", "w"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()) and total == sum(a.nbytes for a in got.values())
+    assert got["T"].shape == (n, 8) and got["R"].shape == (n, 3, 3) and got["nn_dist"].shape == (n, m)
+    assert np.array_equal(got["T"][2], np.arange(8, dtype=np.float32) + 200) and np.all(got["R"][1] == 1.0)
+    assert np.array_equal(got["nn_id"][1], ((np.arange(m) * 7 + 1) % m).astype(np.float32))
+    assert np.all(got["w"][2] == np.float32(1.0 / 3))
+
+
+def test_dump_outputs_samples_the_same_points_when_too_large(tmp_path, monkeypatch):
+    """Outputs larger than DUMP_LIMIT: a fixed, seeded sample of the points (the same for every registration and every run), within the limit."""
+    n, m = 4, 5000
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 64 << 10)
+    icp_amd, read, state = _fake_engine(n, m)
+    a = bench.outputs_of(icp_amd, read, state, n, m)
+    b = bench.outputs_of(icp_amd, read, state, n, m)
+    idx = a["point_index"].astype(np.int64)
+    assert 0 < idx.size < m and np.array_equal(idx, np.unique(idx)) and np.array_equal(a["point_index"], b["point_index"])
+    assert np.array_equal(a["nn_dist"][3], np.arange(m, dtype=np.float32)[idx] + 3.5)
+    assert bench.dump_outputs(str(tmp_path), a) <= bench.DUMP_LIMIT

@@ -500,10 +500,13 @@ def test_oracle_bits_do_not_depend_on_the_thread_count(oracle, engine):
 
 
 def test_cpu_baseline_reports_a_thread_sweep(engine):
-    """bench.py's cpu_baseline: a bounded thread sweep, the best count as `value`, the host's core count beside it."""
+    """bench.py's cpu_baseline: a bounded thread sweep up to this process's CPU share (affinity and cgroup quota: a host's
+    cores beyond it only time-slice), the best count as `value`, the host's core count beside it."""
     import bench
     F, M = engine.synth_pair(64)
     r = bench.cpu_baseline(F, M, 4096, 64, True, budget_s=1.0)
     assert r["kind"] == "port" and r["host_cores"] == os.cpu_count() and r["unit"] == "iterations/s"
-    assert [x["threads"] for x in r["sweep"]] == sorted({t for t in (1, 8, 16, 64, os.cpu_count()) if t <= os.cpu_count()})
+    cap = max(1, min(os.cpu_count(), int(r["cpu_share"])))
+    assert r["cpu_share"] == bench.cpu_share() and cap <= len(os.sched_getaffinity(0))
+    assert [x["threads"] for x in r["sweep"]] == sorted({t for t in (1, 8, 16, 64, cap) if t <= cap})
     assert r["value"] == max(x["iterations_per_s"] for x in r["sweep"]) and r["cores"] in [x["threads"] for x in r["sweep"]]
