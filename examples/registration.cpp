@@ -5,10 +5,14 @@
 //   registration                          a synthetic pair (the data files of the reference are not distributed: .MISSING_LARGE_BLOBS)
 //   registration NAME                     data/NAME_1.bin, data/NAME_2.bin      (the reference's argument convention, :299-329)
 //   registration A B                      data/A.bin, data/B.bin — or A and B themselves when they name existing files
-//   ... [--out FILE] [--device N] [--reference-order] [--svd]
+//   ... [--out FILE] [--device N] [--reference-order] [--svd] [--reject-invalid] [--max-dist MM]
+//
+// --reject-invalid / --max-dist: correspondence rejection (icp_set_rejection: pairs with a pixel without depth at either end / pairs
+// farther apart than MM get weight 0).  Not the reference's behaviour; off by default.
 //
 // A cloud file is 640 x 480 points of 8 floats [x y z 1 r g b 1], little endian, row-major (src/kinect_frame_grabber.cpp:252-272).
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <string>
@@ -32,9 +36,11 @@ void read_cloud (const std::string &path, std::vector<icp_float8> &pc)
 std::string data_path (const std::string &name) { return exists (name) ? name : "../data/" + name + ".bin"; }
 
 template <cl_algo::ICP::ICPStepConfigT RC>
-int run (int device, icp::Mode mode, const std::vector<icp_float8> &pc1, const std::vector<icp_float8> &pc2, const std::string &out)
+int run (int device, icp::Mode mode, const std::vector<icp_float8> &pc1, const std::vector<icp_float8> &pc2, const std::string &out,
+         int reject_flags, float max_dist)
 {
     ICPReg<RC, cl_algo::ICP::ICPStepConfigW::WEIGHTED> app (device, mode);
+    if (reject_flags || max_dist > 0.f) app.setRejection (reject_flags, max_dist);
     app.init (pc1, pc2);
     app.registerPC ();                                        // buildRBC + run + transform + the reference's report
     auto &reg = app.registration ();
@@ -56,6 +62,7 @@ int main (int argc, char **argv)
     std::vector<std::string> names;
     std::string out;
     int device = 0; bool svd = false;
+    int reject_flags = 0; float max_dist = 0.f;
     icp::Mode mode = icp::Mode::FAST;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -63,6 +70,8 @@ int main (int argc, char **argv)
         else if (a == "--device" && i + 1 < argc) device = std::atoi (argv[++i]);
         else if (a == "--reference-order") mode = icp::Mode::REFERENCE_ORDER;
         else if (a == "--svd") svd = true;
+        else if (a == "--reject-invalid") reject_flags |= ICP_REJECT_INVALID;
+        else if (a == "--max-dist" && i + 1 < argc) max_dist = std::strtof (argv[++i], nullptr);
         else if (a.rfind ("--", 0) == 0) { std::fprintf (stderr, "unknown option %s\n", a.c_str ()); return 2; }
         else names.push_back (a);
     }
@@ -78,8 +87,8 @@ int main (int argc, char **argv)
         } else {
             read_cloud (data_path (names[0]), pc1); read_cloud (data_path (names[1]), pc2);
         }
-        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out)
-                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out);
+        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist)
+                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist);
     }
     catch (const std::exception &e)
     {

@@ -37,6 +37,14 @@ class ICPStepConfigW:            # include/ICP/algorithms.hpp:1560
     WEIGHTED = 1
 
 
+REJECT_INVALID = 1                # ICP_REJECT_INVALID (include/icp_amd.h): correspondence rejection of pairs with an invalid endpoint
+
+
+def _max_dist_arg(max_dist):
+    """max_dist of set_rejection -> the C argument (None: 0.0, no distance test); the library validates it."""
+    return 0.0 if max_dist is None else float(max_dist)
+
+
 class PowerMode:
     LITERAL = 0
     SQUARED = 1
@@ -121,6 +129,8 @@ def lib():
     sig("icp_set_scaling", i32, vp, f32)
     sig("icp_set_metric_scale", i32, vp, f32)
     sig("icp_get_metric_scale", i32, vp, C.POINTER(f32))
+    sig("icp_set_rejection", i32, vp, i32, f32)
+    sig("icp_get_rejection", i32, vp, C.POINTER(i32), C.POINTER(f32))
     sig("icp_get_max_iterations", i32, vp, C.POINTER(u32))
     sig("icp_set_max_iterations", i32, vp, u32)
     sig("icp_get_angle_threshold", i32, vp, C.POINTER(f64))
@@ -144,6 +154,7 @@ def lib():
     sig("icp_batch_destroy", i32, vp)
     sig("icp_batch_init", i32, vp, u32, u32, u32, f32, f32, u32, f64, f64)
     sig("icp_batch_set_modes", i32, vp, i32, i32)
+    sig("icp_batch_set_rejection", i32, vp, i32, f32)
     sig("icp_batch_write", i32, vp, u32, i32, vp)
     sig("icp_batch_build_rbc", i32, vp)
     sig("icp_batch_run", i32, vp)
@@ -596,6 +607,18 @@ class ICPStep:
         self._chk(self._L.icp_get_metric_scale(self._h, C.byref(v)))
         return v.value
 
+    def set_rejection(self, invalid=False, max_dist=None):
+        """Correspondence rejection (icp_set_rejection; not reference behaviour, off by default): pairs with an invalid endpoint (a
+        point at the origin) and / or pairs farther apart than `max_dist` (geometric, the cloud's units; None: no distance test) get
+        the weight 0.  The search itself is unchanged."""
+        self._chk(self._L.icp_set_rejection(self._h, REJECT_INVALID if invalid else 0, _max_dist_arg(max_dist)))
+
+    def rejection(self):
+        """(invalid, max_dist) as set: max_dist None when there is no distance test."""
+        fl, md = C.c_int32(), C.c_float()
+        self._chk(self._L.icp_get_rejection(self._h, C.byref(fl), C.byref(md)))
+        return bool(fl.value & REJECT_INVALID), (None if md.value == 0.0 or md.value == float("inf") else md.value)
+
     # -- extensions ------------------------------------------------------------------------
     def setPowerMode(self, mode):
         self._chk(self._L.icp_set_power_mode(self._h, mode))
@@ -915,6 +938,15 @@ class ICPBatch:
 
     def set_modes(self, reduce_mode, power_mode):
         self._chk(self._L.icp_batch_set_modes(self._b, reduce_mode, power_mode))
+
+    def set_rejection(self, invalid=False, max_dist=None):
+        """ICPStep.set_rejection on every registration (icp_batch_set_rejection)."""
+        self._chk(self._L.icp_batch_set_rejection(self._b, REJECT_INVALID if invalid else 0, _max_dist_arg(max_dist)))
+        self._rejection = (bool(invalid), None if max_dist in (None, 0, float("inf")) else float(np.float32(max_dist)))
+
+    def rejection(self):
+        """(invalid, max_dist) as last set on this batch."""
+        return getattr(self, "_rejection", (False, None))
 
     def write(self, i, mem, ptr):
         arr = np.ascontiguousarray(ptr, dtype=np.float32)

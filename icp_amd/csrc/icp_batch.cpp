@@ -348,6 +348,17 @@ int icp_batch_set_modes (icp_batch_handle b, int reduce_mode, int power_mode) tr
 }
 ICP_CATCH_ALL
 
+int icp_batch_set_rejection (icp_batch_handle b, int flags, float max_dist) try
+{
+    if (!b) return ICP_EINVAL;
+    for (icp_handle h : b->slots) {
+        int rc = icp_set_rejection (h, flags, max_dist);
+        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
+    }
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
 int icp_batch_build_rbc (icp_batch_handle b) try
 {
     if (!b || !b->inited) return b ? bfail (b, ICP_ESTATE, "icp_batch_init has not been called") : ICP_EINVAL;

@@ -205,11 +205,13 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     if (h->stream) HIPCHK (h, hipStreamSynchronize (h->stream));
     int rot = h->p.rot, weighted = h->p.weighted, pmode = h->p.power_mode, fused = h->p.fused, chain = h->p.chain;
     const float dist_scale = h->p.dist_scale;
+    const uint32_t reject = h->p.reject; const float reject_d2 = h->p.reject_d2, reject_max_dist = h->p.reject_max_dist;
     free_all (h);
     icp_params &p = h->p;
     p = icp_params {};
     p.rot = rot; p.weighted = weighted; p.power_mode = pmode; p.check = 0; p.fused = fused; p.chain = chain; p.emit = 1;
     p.dist_scale = dist_scale;
+    p.reject = reject; p.reject_d2 = reject_d2; p.reject_max_dist = reject_max_dist;
     p.m = m; p.nr = nr; p.batch = batch; p.side = side; p.nrx = nrx; p.nry = nry;
     p.a = a; p.c = c;
     {   // division-free cell lookups in the kernels (reps_grid guarantees a square grid that the representative grid tiles)
@@ -631,6 +633,32 @@ int icp_set_metric_scale (icp_handle h, float f_g) try
 }
 ICP_CATCH_ALL
 int icp_get_metric_scale (icp_handle h, float *f_g) try { api_guard guard_ (h); if (!h || !f_g) return ICP_EINVAL; *f_g = h->p.dist_scale; return ICP_OK; } ICP_CATCH_ALL
+// correspondence rejection (include/icp_amd.h): the weights of the pairs change, the search does not — the same route as the metric's scale
+// (graphs of the handle are updated in place with the new parameters)
+int icp_set_rejection (icp_handle h, int flags, float max_dist) try
+{
+    static_assert (ICP_REJECT_INVALID == 1 && !(ICP_REJECT_INVALID & ICP_REJECT_DIST_ON), "ks_epilogue tests bit 0");
+    api_guard guard_ (h);
+    if (flags & ~ICP_REJECT_INVALID) return fail (h, ICP_EINVAL, "icp_set_rejection: unknown flag bits");
+    if (!(max_dist >= 0.f)) return fail (h, ICP_EINVAL, "icp_set_rejection: max_dist must be >= 0 (0 or +inf: no distance test)");
+    if (!h) return fail (h, ICP_EINVAL, "icp_set_rejection: null handle");
+    { int rc = outputs_before_change (h); if (rc) return rc; }
+    const bool dist = max_dist > 0.f && !std::isinf (max_dist);
+    h->p.reject = (uint32_t) flags | (dist ? ICP_REJECT_DIST_ON : 0u);
+    h->p.reject_max_dist = max_dist;
+    h->p.reject_d2 = dist ? (float) ((double) max_dist * (double) max_dist) : 0.f;     // (the product of two floats is exact in double)
+    ++h->param_gen; return ICP_OK;
+}
+ICP_CATCH_ALL
+int icp_get_rejection (icp_handle h, int *flags, float *max_dist) try
+{
+    api_guard guard_ (h);
+    if (!h) return ICP_EINVAL;
+    if (flags) *flags = (int) (h->p.reject & ~ICP_REJECT_DIST_ON);
+    if (max_dist) *max_dist = h->p.reject_max_dist;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
 int icp_get_scaling (icp_handle h, float *c) try { api_guard guard_ (h); if (!h || !c) return ICP_EINVAL; *c = h->p.c; return ICP_OK; } ICP_CATCH_ALL
 int icp_set_scaling (icp_handle h, float c) try { api_guard guard_ (h); if (!h) return ICP_EINVAL; h->p.c = c; ++h->param_gen; return ICP_OK; } ICP_CATCH_ALL
 int icp_get_max_iterations (icp_handle h, uint32_t *n) try { api_guard guard_ (h); if (!h || !n) return ICP_EINVAL; *n = h->max_iterations; return ICP_OK; } ICP_CATCH_ALL

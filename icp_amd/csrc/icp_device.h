@@ -526,6 +526,21 @@ __device__ inline void icp_compose_pure (const float *Tprev, const float *Rprev,
     Tn[7] = sk * Tprev[7];
 }
 
+// An iteration that accepted no pair (correspondence rejection, sum W == 0) in place of the solver's result and the composition: S and
+// the means 0, the identity step Tk = [0,0,0,1 | 0,0,0,1], Rk = I, T and R as they were, bit for bit (icp_compose_pure would
+// renormalise q through R)
+__device__ __forceinline__ void icp_identity_step (const float *Tprev, const float *Rprev, float *S, float *means, float *Tk, float *Tn,
+                                                   float *Rn, float *Rk, int &iters)
+{
+#pragma unroll
+    for (int i = 0; i < 11; ++i) S[i] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { means[i] = 0.f; Tk[i] = (i == 3 || i == 7) ? 1.f : 0.f; Tn[i] = Tprev[i]; }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { Rn[i] = Rprev[i]; Rk[i] = (i % 4 == 0) ? 1.f : 0.f; }
+    iters = 0;
+}
+
 // ICP::check — src/ICP/algorithms.cpp:4824-4834 (predicate form: oracle check_converged)
 __device__ __forceinline__ int icp_check_converged (const float *Tk, double tan_half_thr, double trans_thr)
 {

@@ -102,7 +102,16 @@ struct icp_params {
     uint32_t *track_seq;         // number of the last registration of a tracked sequence that has finished (k_gate waits on it)
     uint32_t seq_value;          // this registration's number
     uint32_t no_state_reset;     // buildRBC leaves k / done alone (it runs ahead of the previous frame's end; the run's first launch resets them)
+    // correspondence rejection (icp_set_rejection; all zero = off, the reference's behaviour): a rejected pair keeps its correspondence
+    // and gets the weight +0 — its moment, mean and S terms are written as zeros —, REGULAR mode then divides by sum W like WEIGHTED
+    uint32_t reject;             // ICP_REJECT_* flags (bit 0: a pair with an invalid endpoint, a point at the origin) | ICP_REJECT_DIST_ON; 0: off
+    float reject_d2;             // ICP_REJECT_DIST_ON: max_dist^2 rounded to float (a pair is rejected when !(geo <= reject_d2))
+    float reject_max_dist;       // max_dist as it was set (icp_get_rejection)
 };
+#define ICP_REJECT_DIST_ON 0x80000000u   // icp_params::reject: the distance test is on (one scalar test of one word says whether anything is)
+
+// rejection on: the sum-W formulas in every mode, and a step of nothing accepted (sum W == 0) is the identity
+static __host__ __device__ __forceinline__ bool icp_rejecting (const icp_params &p) { return p.reject != 0u; }
 
 #define ICP_N_FULL(p, b) ((p).N + ((size_t) (p).batch + (b)) * (p).nr)
 
@@ -180,6 +189,8 @@ bool icp_dense (const icp_params &p);            // the dense search variant (se
 uint32_t icp_dense_tile (const icp_params &p);   // its LDS tile: 256 or 1024 representatives
 void icp_launch_owner_search (const icp_params &p, hipStream_t s);   // RBC construct, step 1 (k_search<.., OWNER>)
 void icp_launch_search_dense (const icp_params &p, hipStream_t s);          // icp_search_dense.hip: the dense variants (icp_dense (p))
+void icp_launch_search_rej (const icp_params &p, hipStream_t s);            // icp_search_rej.hip: every search with correspondence rejection on
+void icp_launch_chain_one_rej (const icp_params &p, hipStream_t s, uint32_t j, bool fresh, bool emit);
 void icp_launch_owner_search_dense (const icp_params &p, hipStream_t s);
 uint32_t icp_tbox_of (const icp_params &p);
 uint32_t icp_s2_wave_of (const icp_params &p);

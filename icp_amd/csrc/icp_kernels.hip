@@ -172,19 +172,24 @@ __global__ __launch_bounds__ (64) void k_means (const float4 *gPF, const float4 
     }
     float fx[8], fy[8], fz[8], qx[8], qy[8], qz[8];
     const float nf = (float) m;
+    // (correspondence rejection, a uniform branch: a pair of weight 0 contributes zeros written as such — never 0 * a non-finite point)
+    auto terms = [&] (auto rejecting) {
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        uint32_t e = g * 128u + l + 16u * k;
-        bool ok = (e & ~1u) < m;
-        if (weighted) {
-            float kk = (float) ((double) pf[k].w / sum_w);               // icp_kernels.cl:475
-            fx[k] = ok ? kk * pf[k].x : 0.f; fy[k] = ok ? kk * pf[k].y : 0.f; fz[k] = ok ? kk * pf[k].z : 0.f;
-            qx[k] = ok ? kk * pm[k].x : 0.f; qy[k] = ok ? kk * pm[k].y : 0.f; qz[k] = ok ? kk * pm[k].z : 0.f;
-        } else {                                                         // icp_kernels.cl:391
-            fx[k] = ok ? pf[k].x / nf : 0.f; fy[k] = ok ? pf[k].y / nf : 0.f; fz[k] = ok ? pf[k].z / nf : 0.f;
-            qx[k] = ok ? pm[k].x / nf : 0.f; qy[k] = ok ? pm[k].y / nf : 0.f; qz[k] = ok ? pm[k].z / nf : 0.f;
+        for (int k = 0; k < 8; ++k) {
+            uint32_t e = g * 128u + l + 16u * k;
+            bool ok = (e & ~1u) < m;
+            if (weighted) {
+                if constexpr (decltype (rejecting)::value) ok = ok && pf[k].w != 0.f;
+                float kk = (float) ((double) pf[k].w / sum_w);               // icp_kernels.cl:475
+                fx[k] = ok ? kk * pf[k].x : 0.f; fy[k] = ok ? kk * pf[k].y : 0.f; fz[k] = ok ? kk * pf[k].z : 0.f;
+                qx[k] = ok ? kk * pm[k].x : 0.f; qy[k] = ok ? kk * pm[k].y : 0.f; qz[k] = ok ? kk * pm[k].z : 0.f;
+            } else {                                                         // icp_kernels.cl:391
+                fx[k] = ok ? pf[k].x / nf : 0.f; fy[k] = ok ? pf[k].y / nf : 0.f; fz[k] = ok ? pf[k].z / nf : 0.f;
+                qx[k] = ok ? pm[k].x / nf : 0.f; qy[k] = ok ? pm[k].y / nf : 0.f; qz[k] = ok ? pm[k].z / nf : 0.f;
+            }
         }
-    }
+    };
+    if (icp_rejecting (p)) terms (std::true_type {}); else terms (std::false_type {});
     float4 mf, mm;
     mf.x = row_tree8 (fx); mf.y = row_tree8 (fy); mf.z = row_tree8 (fz); mf.w = 0.f;
     mm.x = row_tree8 (qx); mm.y = row_tree8 (qy); mm.z = row_tree8 (qz); mm.w = 0.f;
@@ -240,6 +245,7 @@ __global__ __launch_bounds__ (64) void k_sij (const float4 *gPF, const float4 *g
     }
 
     const float c = p.c;
+    const bool rejecting = icp_rejecting (p);        // (uniform) correspondence rejection: the weighted sums with w in {0, 1} in REGULAR mode too
     float A[11];
 #pragma unroll
     for (int k = 0; k < 11; ++k) A[k] = 0.f;
@@ -251,8 +257,10 @@ __global__ __launch_bounds__ (64) void k_sij (const float4 *gPF, const float4 *g
             float Fp[3] = { c * (pf[k].x - mf.x), c * (pf[k].y - mf.y), c * (pf[k].z - mf.z) };
             float ff = (Fp[0] * Fp[0] + Fp[1] * Fp[1]) + Fp[2] * Fp[2];
             float m2 = (Mp[0] * Mp[0] + Mp[1] * Mp[1]) + Mp[2] * Mp[2];
-            if (p.weighted) {
+            if (p.weighted || rejecting) {
                 float w = pf[k].w;
+                // (rejection: a pair of weight 0 adds a zero written as such)
+                if (rejecting && w == 0.f) { Mp[0] = Mp[1] = Mp[2] = 0.f; Fp[0] = Fp[1] = Fp[2] = 0.f; ff = 0.f; m2 = 0.f; }
 #pragma unroll
                 for (int a = 0; a < 3; ++a)
 #pragma unroll
@@ -312,13 +320,27 @@ __global__ __launch_bounds__ (192) void k_finalize (const float *gspart, icp_reg
     int iters = 0;
     if constexpr (ROT == 1) iters = icp_power_method_quad (S, means, Tk, p.power_mode, lane);
     else icp_svd_rotation (S, means, Rk, Tk);
+    // correspondence rejection with nothing accepted (sum W == 0): the identity step, S and the means 0, T unchanged (behind the solver,
+    // as in fused_finalize_block)
+    const bool none = icp_rejecting (p) && __builtin_amdgcn_readfirstlane ((int) (st->sum_w == 0.0)) != 0;
 
     if (lane == 0) {
         if (p.st_prev) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) p.st_prev[b].T[k] = st->T[k];
         }
-        icp_compose (st, Tk, Rk, ROT != 1);
+        if (none) {
+            float Tprev[8], Rprev[9], Tn[8], Rn[9];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) Tprev[k] = st->T[k];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) Rprev[k] = st->R[k];
+            icp_identity_step (Tprev, Rprev, S, means, Tk, Tn, Rn, Rk, iters);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { st->Tk[k] = Tk[k]; st->means[k] = means[k]; }
+#pragma unroll
+            for (int k = 0; k < 9; ++k) st->Rk[k] = Rk[k];
+        } else icp_compose (st, Tk, Rk, ROT != 1);
 #pragma unroll
         for (int k = 0; k < 11; ++k) st->S[k] = S[k];
         st->pm_iters = (uint32_t) iters;
@@ -332,7 +354,7 @@ __global__ __launch_bounds__ (192) void k_finalize (const float *gspart, icp_reg
 // (oracle orc_moments_fused / orc_moments_finish), then rotation, composition, convergence.
 // One block of 5 waves per registration: row k (of 20) reduces moment k.
 // ------------------------------------------------------------------------------------------
-template <int ROT>
+template <int ROT, bool REJ>       // REJ: correspondence rejection on (the ΣW == 0 step: fused_finalize_block)
 __global__ __launch_bounds__ (1024) void k_finalize_fused (const double *gmom, icp_reg_state *gst, uint32_t nb, uint32_t check, icp_params p)
 {
     // (the leading scalars: see k_search)
@@ -362,7 +384,7 @@ __global__ __launch_bounds__ (1024) void k_finalize_fused (const double *gmom, i
     // (host-driven checked runs: the new (k, done) is published by the NEXT search's prologue, not here — a store into host memory at the
     // end of this kernel is waited for by the kernel's end, and the next search by that: |F| = 65536, 18.7 -> 19.8 us per iteration)
     // A registration that converges here leaves its final state in host memory too, in front of the word's DONE | FINAL bits.
-    fused_finalize_block<128, 1024, ROT, true> (p, mom, nb, check, sv, a0, &s_fin, s_l1, s_t, gl1, st, ff_no_hook (), 0u,
+    fused_finalize_block<128, 1024, ROT, true, REJ> (p, mom, nb, check, sv, a0, &s_fin, s_l1, s_t, gl1, st, ff_no_hook (), 0u,
                                                 p.hmirror ? p.hmirror + b : nullptr, false, nullptr, p.hstate ? p.hstate + b : nullptr,
                                                 p.st_prev ? p.st_prev + b : nullptr);
 }
@@ -410,7 +432,7 @@ static __device__ __forceinline__ void seq_release (const icp_params &p, uint32_
     if (t == 0) __hip_atomic_store (p.track_seq, p.seq_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int ROT>
+template <int ROT, bool REJ>
 __global__ __launch_bounds__ (320) void k_chain_end (icp_params p)
 {
     const uint32_t b = blockIdx.x;
@@ -443,7 +465,7 @@ __global__ __launch_bounds__ (320) void k_chain_end (icp_params p)
         }
         return;
     }
-    fused_finalize_block<32, 320, ROT> (p, mom, p.nb, 0u, sv, a0, &s_fin, s_l1, s_t, nullptr, nullptr, ff_no_hook (), 1u,
+    fused_finalize_block<32, 320, ROT, false, REJ> (p, mom, p.nb, 0u, sv, a0, &s_fin, s_l1, s_t, nullptr, nullptr, ff_no_hook (), 1u,
                                         nullptr, false, nullptr, nullptr, p.st_prev ? p.st_prev + b : nullptr);
     fin_result_to_state (&s_fin, st, 0u);
     if (threadIdx.x < 64) {
@@ -511,16 +533,18 @@ void icp_launch_owner_search (const icp_params &p, hipStream_t s)
 
 void icp_launch_search (const icp_params &p, hipStream_t s)
 {
+    if (icp_rejecting (p)) { icp_launch_search_rej (p, s); return; }                         // (icp_search_rej.hip)
     if (icp_dense (p)) { icp_launch_search_dense (p, s); return; }                           // (icp_search_dense.hip)
-    if (p.fused) hipLaunchKernelGGL ((k_search<true, false, 2, 16>), dim3 (p.nb, p.batch), dim3 (1024), 0, s, KS_ARGS);
-    else hipLaunchKernelGGL ((k_search<false, false, 2, 16>), dim3 (2 * p.nwg, p.batch), dim3 (1024), 0, s, KS_ARGS);
+    ks_launch_latency<false> (p, s);
 }
 
 void icp_launch_means (const icp_params &p, hipStream_t s)
 {
-    if (p.weighted && p.nwp > 512) hipLaunchKernelGGL (k_sum_w, dim3 (1, p.batch), dim3 (64), 0, s, p);
+    // (correspondence rejection: the weighted formulas, w in {0, 1} in REGULAR mode)
+    const uint32_t weighted = (p.weighted || icp_rejecting (p)) ? 1u : 0u;
+    if (weighted && p.nwp > 512) hipLaunchKernelGGL (k_sum_w, dim3 (1, p.batch), dim3 (64), 0, s, p);
     hipLaunchKernelGGL (k_means, dim3 ((p.nwg + 3) / 4, p.batch), dim3 (64), 0, s, (const float4 *) p.PF, (const float4 *) p.PM, (const float *) p.wpart, p.st,
-                        p.m, p.nwp, (uint32_t) p.weighted, (uint32_t) p.check, p);
+                        p.m, p.nwp, weighted, (uint32_t) p.check, p);
 }
 
 void icp_launch_sij (const icp_params &p, hipStream_t s)
@@ -537,8 +561,10 @@ void icp_launch_finalize (const icp_params &p, hipStream_t s)
         const uint32_t ng = (p.nb + 127u) / 128u;
         if (ng > ICP_L1_MIN_GROUPS && p.ml1)
             hipLaunchKernelGGL (k_moment_level1, dim3 ((ICP_NMOM * ng + 15u) / 16u, p.batch), dim3 (256), 0, s, (const double *) p.mom, (const icp_reg_state *) p.st, p.ml1, p.nb, (uint32_t) p.check, p.ng_magic);
-        if (p.rot == 1) hipLaunchKernelGGL (k_finalize_fused<1>, dim3 (p.batch), dim3 (1024), 0, s, (const double *) p.mom, p.st, p.nb, (uint32_t) p.check, p);
-        else hipLaunchKernelGGL (k_finalize_fused<0>, dim3 (p.batch), dim3 (1024), 0, s, (const double *) p.mom, p.st, p.nb, (uint32_t) p.check, p);
+#define FF_LAUNCH(ROT_, REJ_) hipLaunchKernelGGL ((k_finalize_fused<ROT_, REJ_>), dim3 (p.batch), dim3 (1024), 0, s, (const double *) p.mom, p.st, p.nb, (uint32_t) p.check, p)
+        if (icp_rejecting (p)) { if (p.rot == 1) FF_LAUNCH (1, true); else FF_LAUNCH (0, true); }
+        else { if (p.rot == 1) FF_LAUNCH (1, false); else FF_LAUNCH (0, false); }
+#undef FF_LAUNCH
     } else {
         if (p.rot == 1) hipLaunchKernelGGL (k_finalize<1>, dim3 (p.batch), dim3 (192), 0, s, (const float *) p.spart, p.st, p.nsp, (uint32_t) p.check, p);
         else hipLaunchKernelGGL (k_finalize<0>, dim3 (p.batch), dim3 (192), 0, s, (const float *) p.spart, p.st, p.nsp, (uint32_t) p.check, p);
@@ -567,32 +593,20 @@ bool icp_chain_supported (const icp_params &p)
     return p.fused && p.nb <= 4096u && p.nr <= 1024u && (p.chain == 2 || (p.chain == 1 && !icp_dense (p)));
 }
 
-// launch j of a chain: reads state slot / moments buffer j & 1 and leaves the other (j = 0: reads the user-visible state, nothing to finalize yet)
-void icp_launch_chain_one (const icp_params &p0, hipStream_t s, uint32_t j, bool fresh, bool emit)
+// launch j of a chain (icp_search.h: ks_launch_chain_one)
+void icp_launch_chain_one (const icp_params &p, hipStream_t s, uint32_t j, bool fresh, bool emit)
 {
-    icp_params p = p0;
-    p.slot = j & 1u;
-    p.emit = emit ? 1 : 0;
-    const uint32_t first_flags = 2u | (fresh ? 16u : 0u);             // (fresh: the run starts from the identity, see k_search)
-    // (host-driven checked runs — p.hmirror set — take the HOSTRUN instantiation, fixed-length graphs the plain one)
-#define KS_CHAIN_LAUNCH(ROT_, HR_)                                                                                                              \
-    do {                                                                                                                                        \
-        if (j == 0) hipLaunchKernelGGL ((k_search<true, true, 2, 16, false, ROT_, 1024, false, false, HR_>), dim3 (p.nb, p.batch), dim3 (1024), 0, s, p.M, p.R, p.st,   \
-                                        (const double *) p.mom, p.m, p.nr, p.side, icp_tpr_magic (p.side), p.nb, KS_FLAGS (p) | first_flags, p);     \
-        else hipLaunchKernelGGL ((k_search<true, true, 2, 16, false, ROT_, 1024, false, false, HR_>), dim3 (p.nb, p.batch), dim3 (1024), 0, s, KS_CHAIN_ARGS);          \
-    } while (0)
-    const bool hostrun = p.hmirror != nullptr;
-    if (p.rot == 1) { if (hostrun) KS_CHAIN_LAUNCH (1, true); else KS_CHAIN_LAUNCH (1, false); }
-    else            { if (hostrun) KS_CHAIN_LAUNCH (0, true); else KS_CHAIN_LAUNCH (0, false); }
-#undef KS_CHAIN_LAUNCH
+    if (icp_rejecting (p)) icp_launch_chain_one_rej (p, s, j, fresh, emit);                  // (icp_search_rej.hip)
+    else ks_launch_chain_one<false> (p, s, j, fresh, emit);
 }
 
 void icp_launch_chain_end (const icp_params &p0, hipStream_t s, uint32_t launches)
 {
     icp_params p = p0;
     p.slot = launches & 1u;
-    if (p.rot == 1) hipLaunchKernelGGL (k_chain_end<1>, dim3 (p.batch), dim3 (320), 0, s, p);
-    else hipLaunchKernelGGL (k_chain_end<0>, dim3 (p.batch), dim3 (320), 0, s, p);
+    if (icp_rejecting (p)) { if (p.rot == 1) hipLaunchKernelGGL ((k_chain_end<1, true>), dim3 (p.batch), dim3 (320), 0, s, p); else hipLaunchKernelGGL ((k_chain_end<0, true>), dim3 (p.batch), dim3 (320), 0, s, p); }
+    else if (p.rot == 1) hipLaunchKernelGGL ((k_chain_end<1, false>), dim3 (p.batch), dim3 (320), 0, s, p);
+    else hipLaunchKernelGGL ((k_chain_end<0, false>), dim3 (p.batch), dim3 (320), 0, s, p);
 }
 
 void icp_launch_publish_state (const icp_params &p, hipStream_t s)

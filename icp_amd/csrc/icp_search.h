@@ -29,6 +29,10 @@
 // helpers
 // ------------------------------------------------------------------------------------------
 static __device__ __forceinline__ float sum4 (float4 v) { return ((v.x + v.y) + v.z) + v.w; }
+// bit 31 of a query's hand-in seed: the moving point is an invalid point of its frame (x = y = z = 0 before the transformation).  Stage 1
+// of the dense variants seeds such a query against the representatives at the origin (ks_seed_against_invalid); the finishing wave reads
+// it back for the correspondence rejection (ks_epilogue).  The pruning masks it off the seed's index.
+static __device__ __forceinline__ uint32_t ks_hole_bit (float4 mg) { return (mg.x == 0.f && mg.y == 0.f && mg.z == 0.f) ? 0x80000000u : 0u; }
 
 // ------------------------------------------------------------------------------------------
 // K1  search: transform (a3) + RBC one-shot search (a4) + weights and their first tree levels (a5)
@@ -427,7 +431,7 @@ static __device__ __forceinline__ void fused_moment_loads (const double *mom, ui
 // after (LEAN): called by every lane of the finishing wave with the new T, before the barrier that releases the block — the
 // chained search transforms and hands over its queries there, so that one barrier covers T's consumers.
 struct ff_no_hook { __device__ void operator() (const float *) const {} };
-template <int NG, int NT, int ROT, bool LEAN = false, typename AFTER = ff_no_hook>
+template <int NG, int NT, int ROT, bool LEAN = false, bool REJ = false, typename AFTER = ff_no_hook>
 static __device__ bool fused_finalize_block (const icp_params &p, const double *mom, uint32_t nb, uint32_t check, uint32_t sv,
                                              const double *a0, icp_fin_result *res, double (*s_l1)[NG], double *s_t,
                                              const double *gl1 = nullptr, icp_reg_state *direct = nullptr, AFTER after = AFTER (),
@@ -514,6 +518,9 @@ static __device__ bool fused_finalize_block (const icp_params &p, const double *
         if constexpr (ROT == 1) iters = icp_power_method_quad (S, means, Tk, p.power_mode, lane);
         else icp_svd_rotation (S, means, Rkin, Tk);
         FF_STAMP (12)
+        // correspondence rejection (REJ: the kernels of a handle with rejection on) with nothing accepted (sum W == 0): the step is the
+        // identity, means and S are 0, T stays as it is (the solver ran on NaN)
+        const bool none = REJ && __builtin_amdgcn_readfirstlane ((int) (sw == 0.0)) != 0;       // (wave-uniform)
 #ifdef ICP_DBG_STAMPS
         if (lane < 8 && p.dbg && ROT == 1) p.dbg[16 + lane] = icp_pm_stamps[lane];
 #endif
@@ -526,7 +533,8 @@ static __device__ bool fused_finalize_block (const icp_params &p, const double *
         if constexpr (LEAN) {
             // the composition on every lane (the same instructions as on one): T is then in registers where the hook wants it
             float Tn[8], Rn[9];
-            icp_compose_pure (Tprev, Rprev, Tk, Rkin, ROT != 1, Tn, Rn, Rk);
+            if (none) icp_identity_step (Tprev, Rprev, S, means, Tk, Tn, Rn, Rk, iters);
+            else icp_compose_pure (Tprev, Rprev, Tk, Rkin, ROT != 1, Tn, Rn, Rk);
             const uint32_t done = (p.check && icp_check_converged (Tk, p.tan_half_thr, p.trans_thr)) ? 1u : 0u;
             after (Tn);
             if (lane == 0) {
@@ -574,7 +582,8 @@ static __device__ bool fused_finalize_block (const icp_params &p, const double *
             }
         } else if (lane == 0) {
             float Tn[8], Rn[9];
-            icp_compose_pure (Tprev, Rprev, Tk, Rkin, ROT != 1, Tn, Rn, Rk);
+            if (none) icp_identity_step (Tprev, Rprev, S, means, Tk, Tn, Rn, Rk, iters);
+            else icp_compose_pure (Tprev, Rprev, Tk, Rkin, ROT != 1, Tn, Rn, Rk);
 #pragma unroll
             for (int k = 0; k < 8; ++k) { res->T[k] = Tn[k]; res->Tk[k] = Tk[k]; res->means[k] = means[k]; }
 #pragma unroll
@@ -897,8 +906,8 @@ static __device__ __forceinline__ void ks_stage2_lanes (const char *XQb, uint32_
 // moments (fused) or the first levels of the weight tree (reference order).  The LAST thing k_search does: every thread of the
 // block calls it (two block barriers inside), and its returns end the kernel.
 // ------------------------------------------------------------------------------------------
-template <bool FUSED, bool CHAIN, int MINW, int LPQ, bool OWNER, bool PRUNE>
-static __device__ __forceinline__ void ks_epilogue (const icp_params &p, float4 *s_qa, uint4 *s_qb, const uint32_t *s_slot, double (*s_mom)[64], float *s_w, const float4 *R4, const char *XQb,
+template <bool FUSED, bool CHAIN, int MINW, int LPQ, bool OWNER, bool PRUNE, bool REJ>
+static __device__ __forceinline__ void ks_epilogue (const icp_params &p, float4 *s_qa, uint4 *s_qb, const float4 *s_qc, const uint32_t *s_slot, double (*s_mom)[64], float *s_w, const float4 *R4, const char *XQb,
                                                     uint32_t b, uint32_t m, uint32_t nr, uint32_t check_flags, uint32_t tid, uint32_t lane, uint32_t slice, uint32_t tile_id,
                                                     uint32_t qe, uint32_t ss, uint32_t i, bool valid, uint32_t o, uint32_t n, uint32_t rstar, float dr, float dmin, uint32_t jmin,
                                                     float qx, float qy, float qz)
@@ -923,6 +932,7 @@ static __device__ __forceinline__ void ks_epilogue (const icp_params &p, float4 
         const float ex = qa.x, ey = qa.y, ez = qa.z, d = p.dist_scale * qa.w;
         const uint32_t ei = qb.w;
         float w = 0.f, f0 = 0.f, f1 = 0.f, f2 = 0.f;
+        bool acc = v;                // the pair contributes to the moments (rejection: an accepted pair)
         if (v) {
             uint32_t id;
             if (empty) {             // empty list: fall back to the representative itself
@@ -942,6 +952,17 @@ static __device__ __forceinline__ void ks_epilogue (const icp_params &p, float4 
                 f0 = wg.x; f1 = wg.z; f2 = wc.x; id = __float_as_uint (wc.z);
             }
             w = p.weighted ? 100.f / (100.f + d) : 1.f;                // icp_kernels.cl:232
+            if constexpr (REJ) {             // correspondence rejection (the REJ kernels): the pair keeps its record, its weight is +0
+                // (the moving point's own flag: bit 31 of its hand-in seed — the query wave's test of the untransformed point, see k_search)
+                bool rej = false;
+                if (p.reject & 1u)          // ICP_REJECT_INVALID
+                    rej = (__float_as_uint (s_qc[lane].w) >> 31) != 0u || (f0 == 0.f && f1 == 0.f && f2 == 0.f);
+                if (p.reject & ICP_REJECT_DIST_ON) {
+                    const float gx = ex - f0, gy = ey - f1, gz = ez - f2;
+                    rej = rej || !(((gx * gx + gy * gy) + gz * gz) <= p.reject_d2);     // NaN / inf distances: rejected
+                }
+                if (rej) { w = 0.f; acc = false; }
+            }
             // per-query outputs: uniform bases + 32-bit byte offsets (i < 2^20)
             icp_dist_id di; di.dist = d; di.id = id;
             // One-block-per-CU variants: the four output pointers are fetched from the kernel arguments HERE — an opaque copy of the
@@ -969,11 +990,11 @@ static __device__ __forceinline__ void ks_epilogue (const icp_params &p, float4 
             if (emit || PRUNE) *reinterpret_cast<uint32_t *> (o_rid + (ei << 2)) = qb.y;
         }
         if constexpr (FUSED) {
-            // the 18 moments of this pair in double (oracle orc_moments_fused); invalid queries contribute 0
+            // the 18 moments of this pair in double (oracle orc_moments_fused); invalid queries and rejected pairs contribute 0
             double W = (double) w;
-            double g0 = v ? (double) f0 : 0.0, g1 = v ? (double) f1 : 0.0, g2 = v ? (double) f2 : 0.0;
+            double g0 = acc ? (double) f0 : 0.0, g1 = acc ? (double) f1 : 0.0, g2 = acc ? (double) f2 : 0.0;
             double q0 = (double) ex, q1 = (double) ey, q2 = (double) ez;
-            if (!v) { W = 0.0; q0 = q1 = q2 = 0.0; }
+            if (!acc) { W = 0.0; q0 = q1 = q2 = 0.0; }
             double wq0 = W * q0, wq1 = W * q1, wq2 = W * q2;
             s_mom[0][eo] = W;
             s_mom[1][eo] = W * g0; s_mom[2][eo] = W * g1; s_mom[3][eo] = W * g2;
@@ -1002,7 +1023,7 @@ static __device__ __forceinline__ void ks_epilogue (const icp_params &p, float4 
             momw = (double *) (gf64) ks_params_from_kernarg ()->mom;
         }
         if (l == 0 && mrow < ICP_NMOM) momw[(((size_t) b * 2 + obuf) * ICP_NMOM + mrow) * p.nb + tile_id] = v;
-    } else if (slice == 0 && p.weighted) {
+    } else if (slice == 0 && (p.weighted || REJ)) {
         // tree levels d = 64 .. 2 restricted to this block's parity class (icp_kernels.cl:244-249):
         // element e of the class is position 2e + parity; levels pair e with e+32, e+16, .., e+1.
         const uint32_t l = lane & 15u;
@@ -1132,7 +1153,10 @@ static __device__ __forceinline__ void ks_fine_pass (const float4 *s_pair, uint3
 // converged registration to the user-visible state and to host memory, the transform each search used (p.st_prev).  Fixed-length graphs
 // (the metric's path) instantiate the kernel without any of it: what the publishing lane of block 0 carries in its prologue is on the
 // path the whole grid waits for (measured with everything decided at run time: 8.58 -> 8.73 us per dispatch).
-template <bool FUSED, bool CHAIN, int MINW, int LPQ, bool OWNER = false, int ROT = 1, int TILE = 1024, bool SINGLE = false, bool S2W = false, bool HOSTRUN = false>
+// REJ: correspondence rejection (icp_set_rejection) is on.  Those instantiations are made and launched by icp_search_rej.hip only (the
+// default kernels carry none of its code, and each translation unit keeps the kernel set it had).
+template <bool FUSED, bool CHAIN, int MINW, int LPQ, bool OWNER = false, int ROT = 1, int TILE = 1024, bool SINGLE = false, bool S2W = false, bool HOSTRUN = false,
+          bool REJ = false>
 __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (const float *gM, const float *gR, icp_reg_state *gst, const double *gmom,
                                                               uint32_t m, uint32_t nr, uint32_t side, uint32_t tpr_magic,
                                                               uint32_t nb, uint32_t check_flags, icp_params p)
@@ -1338,6 +1362,10 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
     if constexpr (!S2W) asm volatile ("" : "+v"(mgv), "+v"(mcv));     // (lanes = candidates, long lists: throughput-bound, measured 0.3 % slower with it)
     float4 mg = make_float4 (mgv.x, mgv.y, mgv.z, mgv.w), mc = make_float4 (mcv.x, mcv.y, mcv.z, mcv.w);
     if (iq >= m) { mg = make_float4 (0.f, 0.f, 0.f, 1.f); mc = mg; }
+    // (rejection: the query's hole bit for its hand-in seed — ks_hole_bit —, decided here: in the chained variant the hand-over sits behind
+    // the finalize, on the path every block of the grid waits for)
+    uint32_t hbit = 0u;
+    if constexpr (REJ && !OWNER) { hbit = ks_hole_bit (mg); if constexpr (CHAIN) asm volatile ("" : "+v"(hbit)); }
     const float4 *XQ4 = reinterpret_cast<const float4 *> (p.XQ + (size_t) b * m * 8);
     const char *XQb = reinterpret_cast<const char *> (XQ4);
     // the first tile of representatives goes to LDS now: nothing in it depends on T, and in the chained variant the
@@ -1377,9 +1405,9 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
                 float tx, ty, tz;
                 icp_transform_point (Tn, mg.x, mg.y, mg.z, tx, ty, tz);
                 s_qa[lane] = make_float4 (tx, ty, tz, __uint_as_float (iq));
-                s_qc[lane] = make_float4 (mc.x, mc.y, mc.z, __uint_as_float (seed));
+                s_qc[lane] = make_float4 (mc.x, mc.y, mc.z, __uint_as_float (seed | hbit));
             };
-            fused_finalize_block<32, 64 * LPQ, ROT, true> (p, gmom + (size_t) b * 2 * ICP_NMOM * nb, nb, 0u, sv, ma0, &s_fin, s_l1, s_t, nullptr,
+            fused_finalize_block<32, 64 * LPQ, ROT, true, REJ> (p, gmom + (size_t) b * 2 * ICP_NMOM * nb, nb, 0u, sv, ma0, &s_fin, s_l1, s_t, nullptr,
                                                            blockIdx.x == 0 ? sout : nullptr, hand_over, 1u,
                                                            (HOSTRUN && blockIdx.x == 0 && p.hmirror) ? p.hmirror + b : nullptr, HOSTRUN, HOSTRUN ? p.st + b : nullptr,
                                                            (HOSTRUN && p.hstate) ? p.hstate + b : nullptr, (HOSTRUN && p.st_prev) ? p.st_prev + b : nullptr);
@@ -1413,7 +1441,7 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
             }
         } else {
             s_qa[lane] = make_float4 (tx, ty, tz, __uint_as_float (iq));
-            s_qc[lane] = make_float4 (mc.x, mc.y, mc.z, __uint_as_float (seed));
+            s_qc[lane] = make_float4 (mc.x, mc.y, mc.z, __uint_as_float (seed | hbit));
         }
     }
     float qx = 0.f, qy = 0.f, qz = 0.f, qr = 0.f, qg = 0.f, qb = 0.f;
@@ -1676,7 +1704,7 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
     KS_STAMP (5)
     // ==================================================== EPILOGUE ====================================================
     // ---- epilogue (ks_epilogue): hand-off, finishing wave, outputs, block moments
-    ks_epilogue<FUSED, CHAIN, MINW, LPQ, OWNER, PRUNE> (p, s_qa, s_qb, s_slot, s_mom, s_w, R4, XQb, b, m, nr, check_flags, tid, lane, slice, tile_id, qe, ss, i, valid, o, n, rstar, dr, dmin, jmin,
+    ks_epilogue<FUSED, CHAIN, MINW, LPQ, OWNER, PRUNE, REJ> (p, s_qa, s_qb, s_qc, s_slot, s_mom, s_w, R4, XQb, b, m, nr, check_flags, tid, lane, slice, tile_id, qe, ss, i, valid, o, n, rstar, dr, dmin, jmin,
                                                         qx, qy, qz);
 }
 
@@ -1692,3 +1720,55 @@ static inline uint32_t icp_tpr_magic (uint32_t side)
 #define KS_FLAGS(p) ((uint32_t) ((p).check ? 1u : 0u) | ((p).emit ? 8u : 0u) | ((p).warm_seed ? 32u : 0u) | ((p).xcdmap ? 64u : 0u))
 #define KS_ARGS p.M, p.R, p.st, (const double *) p.mom, p.m, p.nr, p.side, icp_tpr_magic (p.side), p.nb, KS_FLAGS (p), p
 #define KS_CHAIN_ARGS p.M, p.R, p.cst + p.slot, (const double *) p.mom + (size_t) p.slot * ICP_NMOM * p.nb, p.m, p.nr, p.side, icp_tpr_magic (p.side), p.nb, KS_FLAGS (p), p
+
+// the launch of a search, the selection of the kernel (REJ = true: icp_search_rej.hip only; false: the latency variants and the chain
+// icp_kernels.hip, the dense ones icp_search_dense.hip)
+template <bool REJ>
+void ks_launch_dense (const icp_params &p, hipStream_t s)
+{
+    const bool t256 = icp_dense_tile (p) == 256u, multi = p.nr > 256u;
+    if (p.fused) {
+        if (p.s2wave && multi && t256) hipLaunchKernelGGL ((k_search<true, false, 4, 8, false, 1, 256, false, true, false, REJ>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_ARGS);
+        else if (p.s2wave && t256) hipLaunchKernelGGL ((k_search<true, false, 4, 8, false, 1, 256, true, true, false, REJ>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_ARGS);
+        else if (p.s2wave) hipLaunchKernelGGL ((k_search<true, false, 4, 8, false, 1, 1024, false, true, false, REJ>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_ARGS);
+        else if (multi && t256) hipLaunchKernelGGL ((k_search<true, false, 4, 8, false, 1, 256, false, false, false, REJ>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_ARGS);
+        else if (t256) hipLaunchKernelGGL ((k_search<true, false, 4, 8, false, 1, 256, true, false, false, REJ>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_ARGS);
+        else hipLaunchKernelGGL ((k_search<true, false, 4, 8, false, 1, 1024, false, false, false, REJ>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_ARGS);
+    } else {
+        // (the same tile choice as the fused variants: the tile boxes of a registration are built for one tile size, p.tbox)
+        if (p.s2wave && multi && t256) hipLaunchKernelGGL ((k_search<false, false, 4, 8, false, 1, 256, false, true, false, REJ>), dim3 (2 * p.nwg, p.batch), dim3 (512), 0, s, KS_ARGS);
+        else if (p.s2wave && t256) hipLaunchKernelGGL ((k_search<false, false, 4, 8, false, 1, 256, true, true, false, REJ>), dim3 (2 * p.nwg, p.batch), dim3 (512), 0, s, KS_ARGS);
+        else if (p.s2wave) hipLaunchKernelGGL ((k_search<false, false, 4, 8, false, 1, 1024, false, true, false, REJ>), dim3 (2 * p.nwg, p.batch), dim3 (512), 0, s, KS_ARGS);
+        else if (multi && t256) hipLaunchKernelGGL ((k_search<false, false, 4, 8, false, 1, 256, false, false, false, REJ>), dim3 (2 * p.nwg, p.batch), dim3 (512), 0, s, KS_ARGS);
+        else if (t256) hipLaunchKernelGGL ((k_search<false, false, 4, 8, false, 1, 256, true, false, false, REJ>), dim3 (2 * p.nwg, p.batch), dim3 (512), 0, s, KS_ARGS);
+        else hipLaunchKernelGGL ((k_search<false, false, 4, 8, false, 1, 1024, false, false, false, REJ>), dim3 (2 * p.nwg, p.batch), dim3 (512), 0, s, KS_ARGS);
+    }
+}
+
+template <bool REJ>
+void ks_launch_latency (const icp_params &p, hipStream_t s)
+{
+    if (p.fused) hipLaunchKernelGGL ((k_search<true, false, 2, 16, false, 1, 1024, false, false, false, REJ>), dim3 (p.nb, p.batch), dim3 (1024), 0, s, KS_ARGS);
+    else hipLaunchKernelGGL ((k_search<false, false, 2, 16, false, 1, 1024, false, false, false, REJ>), dim3 (2 * p.nwg, p.batch), dim3 (1024), 0, s, KS_ARGS);
+}
+
+// launch j of a chain: reads state slot / moments buffer j & 1 and leaves the other (j = 0: reads the user-visible state, nothing to finalize yet)
+template <bool REJ>
+void ks_launch_chain_one (const icp_params &p0, hipStream_t s, uint32_t j, bool fresh, bool emit)
+{
+    icp_params p = p0;
+    p.slot = j & 1u;
+    p.emit = emit ? 1 : 0;
+    const uint32_t first_flags = 2u | (fresh ? 16u : 0u);             // (fresh: the run starts from the identity, see k_search)
+    // (host-driven checked runs — p.hmirror set — take the HOSTRUN instantiation, fixed-length graphs the plain one)
+#define KS_CHAIN_LAUNCH(ROT_, HR_)                                                                                                              \
+    do {                                                                                                                                        \
+        if (j == 0) hipLaunchKernelGGL ((k_search<true, true, 2, 16, false, ROT_, 1024, false, false, HR_, REJ>), dim3 (p.nb, p.batch), dim3 (1024), 0, s, p.M, p.R, p.st, \
+                                        (const double *) p.mom, p.m, p.nr, p.side, icp_tpr_magic (p.side), p.nb, KS_FLAGS (p) | first_flags, p);     \
+        else hipLaunchKernelGGL ((k_search<true, true, 2, 16, false, ROT_, 1024, false, false, HR_, REJ>), dim3 (p.nb, p.batch), dim3 (1024), 0, s, KS_CHAIN_ARGS);     \
+    } while (0)
+    const bool hostrun = p.hmirror != nullptr;
+    if (p.rot == 1) { if (hostrun) KS_CHAIN_LAUNCH (1, true); else KS_CHAIN_LAUNCH (1, false); }
+    else            { if (hostrun) KS_CHAIN_LAUNCH (0, true); else KS_CHAIN_LAUNCH (0, false); }
+#undef KS_CHAIN_LAUNCH
+}

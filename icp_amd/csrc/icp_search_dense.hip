@@ -17,23 +17,4 @@ void icp_launch_owner_search_dense (const icp_params &p, hipStream_t s)
 #undef KS_OWNER_ARGS
 }
 
-void icp_launch_search_dense (const icp_params &p, hipStream_t s)
-{
-    const bool t256 = icp_dense_tile (p) == 256u, multi = p.nr > 256u;
-    if (p.fused) {
-        if (p.s2wave && multi && t256) hipLaunchKernelGGL ((k_search<true, false, 4, 8, false, 1, 256, false, true>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else if (p.s2wave && t256) hipLaunchKernelGGL ((k_search<true, false, 4, 8, false, 1, 256, true, true>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else if (p.s2wave) hipLaunchKernelGGL ((k_search<true, false, 4, 8, false, 1, 1024, false, true>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else if (multi && t256) hipLaunchKernelGGL ((k_search<true, false, 4, 8, false, 1, 256, false>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else if (t256) hipLaunchKernelGGL ((k_search<true, false, 4, 8, false, 1, 256, true>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else hipLaunchKernelGGL ((k_search<true, false, 4, 8>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_ARGS);
-    } else {
-        // (the same tile choice as the fused variants: the tile boxes of a registration are built for one tile size, p.tbox)
-        if (p.s2wave && multi && t256) hipLaunchKernelGGL ((k_search<false, false, 4, 8, false, 1, 256, false, true>), dim3 (2 * p.nwg, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else if (p.s2wave && t256) hipLaunchKernelGGL ((k_search<false, false, 4, 8, false, 1, 256, true, true>), dim3 (2 * p.nwg, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else if (p.s2wave) hipLaunchKernelGGL ((k_search<false, false, 4, 8, false, 1, 1024, false, true>), dim3 (2 * p.nwg, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else if (multi && t256) hipLaunchKernelGGL ((k_search<false, false, 4, 8, false, 1, 256, false>), dim3 (2 * p.nwg, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else if (t256) hipLaunchKernelGGL ((k_search<false, false, 4, 8, false, 1, 256, true>), dim3 (2 * p.nwg, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else hipLaunchKernelGGL ((k_search<false, false, 4, 8>), dim3 (2 * p.nwg, p.batch), dim3 (512), 0, s, KS_ARGS);
-    }
-}
+void icp_launch_search_dense (const icp_params &p, hipStream_t s) { ks_launch_dense<false> (p, s); }

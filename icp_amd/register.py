@@ -12,12 +12,15 @@ from .io import load_pc8d, save_pc8d
 
 
 def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, angle_threshold=0.001,
-                    translation_threshold=0.01, reduce_mode=ReduceMode.FUSED):
-    """Returns (T[8], k, latency_ms, transformed moving cloud)."""
+                    translation_threshold=0.01, reduce_mode=ReduceMode.FUSED, reject_invalid=False, max_dist=None):
+    """Returns (T[8], k, latency_ms, transformed moving cloud).  reject_invalid / max_dist: correspondence rejection
+    (ICPStep.set_rejection; not the reference's behaviour, off by default)."""
     reg = ICP(device)
     reg.init(16384, 256, a, c, max_iterations, angle_threshold, translation_threshold)   # src/ocl_icp_reg.cpp:81-88
     reg.setPowerMode(PowerMode.SQUARED)
     reg.setReduceMode(reduce_mode)
+    if reject_invalid or max_dist:
+        reg.set_rejection(reject_invalid, max_dist)
     reg.write_cloud(Memory.F, fixed)
     reg.write_cloud(Memory.M, moving)
     reg.buildRBC()
@@ -54,8 +57,13 @@ def main(argv=None):
     ap.add_argument("-o", "--output", help="write the transformed moving cloud (raw 640x480 float8)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("-a", "--alpha", type=float, default=2e2)
+    ap.add_argument("--reject-invalid", action="store_true",
+                    help="give pairs with an invalid endpoint (a pixel without depth) weight 0 (not reference behaviour)")
+    ap.add_argument("--max-dist", type=float, default=None,
+                    help="give pairs farther apart than this geometric distance (mm) weight 0 (not reference behaviour)")
     args = ap.parse_args(argv)
-    T, k, ms, out = register_clouds(load_pc8d(args.fixed), load_pc8d(args.moving), args.device, a=args.alpha)
+    T, k, ms, out = register_clouds(load_pc8d(args.fixed), load_pc8d(args.moving), args.device, a=args.alpha,
+                                    reject_invalid=args.reject_invalid, max_dist=args.max_dist)
     q, t, s = T[:4], T[4:7], T[7]
     sinth_2 = float(np.linalg.norm(q[:3]))
     angle = 180.0 / math.pi * 2 * math.atan2(sinth_2, float(q[3]))

@@ -592,6 +592,12 @@ namespace ICP
         float getScaling () { return c; }
         void setScaling (float _c) { check (icp_set_scaling (h, _c)); c = _c; }
 
+        /*! \brief Correspondence rejection (icp_set_rejection, include/icp_amd.h; not in the reference, off by default):
+         *         `flags` = ICP_REJECT_INVALID drops pairs with an invalid endpoint (a point at the origin), `max_dist` > 0 drops
+         *         pairs whose geometric distance exceeds it (the cloud's units; 0: no distance test).  Dropped pairs get weight 0. */
+        void setRejection (int flags, float max_dist = 0.f) { check (icp_set_rejection (h, flags, max_dist)); }
+        void getRejection (int &flags, float &max_dist) { check (icp_get_rejection (h, &flags, &max_dist)); }
+
         float *hPtrInF;  /*!< Staging buffer of the fixed set (reference: mapped H_IN_F). */
         float *hPtrInM;  /*!< Staging buffer of the moving set. */
         float *hPtrIOT;  /*!< Staging buffer of [q | t, s]. */

@@ -219,6 +219,26 @@ int icp_get_scaling (icp_handle h, float *c);
  * icp_set_alpha (h, a) + icp_set_metric_scale (h, 1 / (1 + a)).  Positive and finite. */
 int icp_set_metric_scale (icp_handle h, float f_g);
 int icp_get_metric_scale (icp_handle h, float *f_g);
+
+/* Correspondence rejection (not reference behaviour: the reference weights every pair, w = 100 / (100 + dist) or 1).  Opt-in;
+ * icp_set_rejection (h, 0, 0) — the default — changes nothing.  The search is not affected: a rejected pair keeps its
+ * correspondence (NN_ID, RID, PF / PM as before) and gets the weight +0 (the W output holds 0), and its moment, mean and S terms are
+ * exact zeros, written as such (a non-finite coordinate makes no NaN).  At the same T the correspondences are bit-identical to a
+ * run without rejection.
+ *   flags & ICP_REJECT_INVALID: reject a pair with an invalid endpoint — the moving point's untransformed x = y = z = 0 in M, or
+ *     the returned fixed point's x = y = z = 0 (a Kinect pixel without depth; in the empty-list fallback the representative).
+ *   max_dist > 0: reject a pair when !(geo <= max_dist^2), geo = (ex - f0)^2 + (ey - f1)^2 + (ez - f2)^2 in fp32, summed in this
+ *     order without contraction (e = the transformed moving point, f = its fixed point; max_dist^2 rounded to float).  A geometric
+ *     distance in the cloud's units (mm for Kinect data), not the photogeometric search metric; NaN / inf distances are rejected.
+ *     0 or +inf: no distance test.
+ * With rejection on, REGULAR mode uses the weighted formulas with w in {0, 1} (sum w x / sum w, not / n).  An iteration that
+ * accepts no pair (sum W == 0) is the identity step: Tk = [0,0,0,1 | 0,0,0,1], T unchanged, means and S 0 — ICP::run's
+ * convergence test then stops.  (Rejection off: sum W == 0 behaves as before.)
+ * Applies to every registration of the handle: single, batched (icp_init_batched) and tracked (icp_track_*); it survives icp_init.
+ * ICP_EINVAL: unknown flag bits, max_dist negative or NaN. */
+#define ICP_REJECT_INVALID 1
+int icp_set_rejection (icp_handle h, int flags, float max_dist);
+int icp_get_rejection (icp_handle h, int *flags, float *max_dist);
 int icp_set_scaling (icp_handle h, float c);
 int icp_get_max_iterations (icp_handle h, uint32_t *n);
 int icp_set_max_iterations (icp_handle h, uint32_t n);
@@ -402,6 +422,7 @@ int icp_batch_destroy (icp_batch_handle b);
 int icp_batch_init (icp_batch_handle b, uint32_t registrations, uint32_t m, uint32_t nr, float a, float c,
                     uint32_t max_iterations, double angle_threshold, double translation_threshold);
 int icp_batch_set_modes (icp_batch_handle b, int reduce_mode, int power_mode);
+int icp_batch_set_rejection (icp_batch_handle b, int flags, float max_dist);                /* icp_set_rejection on every slot */
 int icp_batch_write (icp_batch_handle b, uint32_t i, int mem, const void *host_ptr);       /* mem: F, M or T of registration i */
 int icp_batch_build_rbc (icp_batch_handle b);
 int icp_batch_run (icp_batch_handle b);                                                      /* ICP::run of every registration */

@@ -69,6 +69,10 @@ public:
         std::cout << "    Scale                 :    " << reg.s << std::endl;
     }
 
+    /*! \brief Correspondence rejection of the registration (ICPStep::setRejection; not in the reference's demo, off by default). */
+    void setRejection (int flags, float max_dist = 0.f) { reg.setRejection (flags, max_dist); }
+    void getRejection (int &flags, float &max_dist) { reg.getRejection (flags, max_dist); }
+
     /*! \brief The moving cloud after `registerPC ()` (the reference writes it into the GL vertex buffer). */
     const std::vector<icp_float8>& transformed () const { return moved; }
     /*! \brief The registration object itself: `k`, `q`, `t`, `s`, `R` as in the reference's `reg` member. */
