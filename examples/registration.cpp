@@ -5,10 +5,11 @@
 //   registration                          a synthetic pair (the data files of the reference are not distributed: .MISSING_LARGE_BLOBS)
 //   registration NAME                     data/NAME_1.bin, data/NAME_2.bin      (the reference's argument convention, :299-329)
 //   registration A B                      data/A.bin, data/B.bin — or A and B themselves when they name existing files
-//   ... [--out FILE] [--device N] [--reference-order] [--svd] [--reject-invalid] [--max-dist MM]
+//   ... [--out FILE] [--device N] [--reference-order] [--svd] [--reject-invalid] [--max-dist MM] [--trim FRACTION]
 //
 // --reject-invalid / --max-dist: correspondence rejection (icp_set_rejection: pairs with a pixel without depth at either end / pairs
-// farther apart than MM get weight 0).  Not the reference's behaviour; off by default.
+// farther apart than MM get weight 0).  --trim: trimmed ICP (icp_set_trimming: every iteration keeps the closest FRACTION in (0, 1] of the
+// pairs).  Not the reference's behaviour; off by default.
 //
 // A cloud file is 640 x 480 points of 8 floats [x y z 1 r g b 1], little endian, row-major (src/kinect_frame_grabber.cpp:252-272).
 #include <cstdio>
@@ -37,10 +38,11 @@ std::string data_path (const std::string &name) { return exists (name) ? name : 
 
 template <cl_algo::ICP::ICPStepConfigT RC>
 int run (int device, icp::Mode mode, const std::vector<icp_float8> &pc1, const std::vector<icp_float8> &pc2, const std::string &out,
-         int reject_flags, float max_dist)
+         int reject_flags, float max_dist, float trim)
 {
     ICPReg<RC, cl_algo::ICP::ICPStepConfigW::WEIGHTED> app (device, mode);
     if (reject_flags || max_dist > 0.f) app.setRejection (reject_flags, max_dist);
+    if (trim != 1.f) app.setTrimming (trim);
     app.init (pc1, pc2);
     app.registerPC ();                                        // buildRBC + run + transform + the reference's report
     auto &reg = app.registration ();
@@ -62,7 +64,7 @@ int main (int argc, char **argv)
     std::vector<std::string> names;
     std::string out;
     int device = 0; bool svd = false;
-    int reject_flags = 0; float max_dist = 0.f;
+    int reject_flags = 0; float max_dist = 0.f, trim = 1.f;
     icp::Mode mode = icp::Mode::FAST;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -72,6 +74,10 @@ int main (int argc, char **argv)
         else if (a == "--svd") svd = true;
         else if (a == "--reject-invalid") reject_flags |= ICP_REJECT_INVALID;
         else if (a == "--max-dist" && i + 1 < argc) max_dist = std::strtof (argv[++i], nullptr);
+        else if (a == "--trim" && i + 1 < argc) {
+            trim = std::strtof (argv[++i], nullptr);
+            if (!(trim > 0.f && trim <= 1.f)) { std::fprintf (stderr, "--trim: FRACTION must be in (0, 1]\n"); return 2; }
+        }
         else if (a.rfind ("--", 0) == 0) { std::fprintf (stderr, "unknown option %s\n", a.c_str ()); return 2; }
         else names.push_back (a);
     }
@@ -87,8 +93,8 @@ int main (int argc, char **argv)
         } else {
             read_cloud (data_path (names[0]), pc1); read_cloud (data_path (names[1]), pc2);
         }
-        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist)
-                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist);
+        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim)
+                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim);
     }
     catch (const std::exception &e)
     {

@@ -62,7 +62,7 @@ class TransformKind:             # ICPTransformConfig (include/ICP/algorithms.hp
 
 
 class Memory:                    # icp_mem in include/icp_amd.h
-    F, M, T, TK, MEANS, S, NN_ID, W, SUM_W, REPS, RBC_N, RBC_O, RBC_PERM, RBC_OWNER, RBC_XP, RID, R, RK, NN, QT = range(20)
+    F, M, T, TK, MEANS, S, NN_ID, W, SUM_W, REPS, RBC_N, RBC_O, RBC_PERM, RBC_OWNER, RBC_XP, RID, R, RK, NN, QT, TRIM = range(21)
     # reference spellings (ICPStep::Memory, include/ICP/algorithms.hpp:2241-2267)
     D_IN_F, D_IN_M, D_IO_T, H_IO_T = F, M, T, T
 
@@ -131,6 +131,8 @@ def lib():
     sig("icp_get_metric_scale", i32, vp, C.POINTER(f32))
     sig("icp_set_rejection", i32, vp, i32, f32)
     sig("icp_get_rejection", i32, vp, C.POINTER(i32), C.POINTER(f32))
+    sig("icp_set_trimming", i32, vp, f32)
+    sig("icp_get_trimming", i32, vp, C.POINTER(f32))
     sig("icp_get_max_iterations", i32, vp, C.POINTER(u32))
     sig("icp_set_max_iterations", i32, vp, u32)
     sig("icp_get_angle_threshold", i32, vp, C.POINTER(f64))
@@ -155,6 +157,7 @@ def lib():
     sig("icp_batch_init", i32, vp, u32, u32, u32, f32, f32, u32, f64, f64)
     sig("icp_batch_set_modes", i32, vp, i32, i32)
     sig("icp_batch_set_rejection", i32, vp, i32, f32)
+    sig("icp_batch_set_trimming", i32, vp, f32)
     sig("icp_batch_write", i32, vp, u32, i32, vp)
     sig("icp_batch_build_rbc", i32, vp)
     sig("icp_batch_run", i32, vp)
@@ -506,7 +509,7 @@ _MEM_DTYPE = {
     Memory.SUM_W: (np.float64, None), Memory.REPS: (np.float32, 8), Memory.RBC_N: (np.uint32, None),
     Memory.RBC_O: (np.uint32, None), Memory.RBC_PERM: (np.uint32, None), Memory.RBC_OWNER: (np.uint32, None),
     Memory.RID: (np.uint32, None), Memory.R: (np.float32, 3), Memory.RK: (np.float32, 3),
-    Memory.NN: (np.float32, 4), Memory.QT: (np.float32, 4),
+    Memory.NN: (np.float32, 4), Memory.QT: (np.float32, 4), Memory.TRIM: (np.uint32, None),
 }
 
 
@@ -618,6 +621,18 @@ class ICPStep:
         fl, md = C.c_int32(), C.c_float()
         self._chk(self._L.icp_get_rejection(self._h, C.byref(fl), C.byref(md)))
         return bool(fl.value & REJECT_INVALID), (None if md.value == 0.0 or md.value == float("inf") else md.value)
+
+    def set_trimming(self, keep=1.0):
+        """Trimmed ICP (icp_set_trimming; not reference behaviour, off by default): every iteration keeps the closest fraction
+        `keep` in (0, 1] of the pairs rejection leaves and gives the rest the weight 0; 1.0 switches it off.  read(Memory.TRIM) gives
+        the last iteration's (t bits, n, K, accepted).  Kinect data needs set_rejection(invalid=True) alongside it."""
+        self._chk(self._L.icp_set_trimming(self._h, float(keep)))
+
+    def trimming(self):
+        """The keep fraction as set (1.0: off)."""
+        v = C.c_float()
+        self._chk(self._L.icp_get_trimming(self._h, C.byref(v)))
+        return v.value
 
     # -- extensions ------------------------------------------------------------------------
     def setPowerMode(self, mode):
@@ -948,6 +963,15 @@ class ICPBatch:
         """(invalid, max_dist) as last set on this batch."""
         return getattr(self, "_rejection", (False, None))
 
+    def set_trimming(self, keep=1.0):
+        """ICPStep.set_trimming on every registration (icp_batch_set_trimming)."""
+        self._chk(self._L.icp_batch_set_trimming(self._b, float(keep)))
+        self._trimming = float(np.float32(keep))
+
+    def trimming(self):
+        """The keep fraction as last set on this batch (1.0: off)."""
+        return getattr(self, "_trimming", 1.0)
+
     def write(self, i, mem, ptr):
         arr = np.ascontiguousarray(ptr, dtype=np.float32)
         want = 8 if mem == Memory.T else self.m * 8
@@ -987,7 +1011,7 @@ class ICPBatch:
     def read(self, i, mem):
         dt, cols = _MEM_DTYPE[mem]
         sizes = {Memory.T: 32, Memory.TK: 32, Memory.MEANS: 32, Memory.S: 44, Memory.NN_ID: self.m * 8, Memory.R: 36, Memory.RK: 36,
-                 Memory.F: self.m * 32, Memory.M: self.m * 32, Memory.W: self.m * 4, Memory.RID: self.m * 4}
+                 Memory.F: self.m * 32, Memory.M: self.m * 32, Memory.W: self.m * 4, Memory.RID: self.m * 4, Memory.TRIM: 16}
         nbytes = sizes[mem]
         out = np.empty(nbytes // np.dtype(dt).itemsize, dt)
         self._chk(self._L.icp_batch_read(self._b, i, mem, _p(out), nbytes))

@@ -359,6 +359,18 @@ int icp_batch_set_rejection (icp_batch_handle b, int flags, float max_dist) try
 }
 ICP_CATCH_ALL
 
+int icp_batch_set_trimming (icp_batch_handle b, float keep_fraction) try
+{
+    if (!b) return ICP_EINVAL;
+    if (!(keep_fraction > 0.f && keep_fraction <= 1.f)) return bfail (b, ICP_EINVAL, "icp_batch_set_trimming: keep_fraction must be in (0, 1] (1: off)");
+    for (icp_handle h : b->slots) {
+        int rc = icp_set_trimming (h, keep_fraction);
+        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
+    }
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
 int icp_batch_build_rbc (icp_batch_handle b) try
 {
     if (!b || !b->inited) return b ? bfail (b, ICP_ESTATE, "icp_batch_init has not been called") : ICP_EINVAL;

@@ -205,13 +205,13 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     if (h->stream) HIPCHK (h, hipStreamSynchronize (h->stream));
     int rot = h->p.rot, weighted = h->p.weighted, pmode = h->p.power_mode, fused = h->p.fused, chain = h->p.chain;
     const float dist_scale = h->p.dist_scale;
-    const uint32_t reject = h->p.reject; const float reject_d2 = h->p.reject_d2, reject_max_dist = h->p.reject_max_dist;
+    const uint32_t reject = h->p.reject; const float reject_d2 = h->p.reject_d2, reject_max_dist = h->p.reject_max_dist, trim_keep = h->p.trim_keep;
     free_all (h);
     icp_params &p = h->p;
     p = icp_params {};
     p.rot = rot; p.weighted = weighted; p.power_mode = pmode; p.check = 0; p.fused = fused; p.chain = chain; p.emit = 1;
     p.dist_scale = dist_scale;
-    p.reject = reject; p.reject_d2 = reject_d2; p.reject_max_dist = reject_max_dist;
+    p.reject = reject; p.reject_d2 = reject_d2; p.reject_max_dist = reject_max_dist; p.trim_keep = trim_keep;
     p.m = m; p.nr = nr; p.batch = batch; p.side = side; p.nrx = nrx; p.nry = nry;
     p.a = a; p.c = c;
     {   // division-free cell lookups in the kernels (reps_grid guarantees a square grid that the representative grid tiles)
@@ -267,7 +267,9 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     if ((rc = dalloc (h, &p.mpart, B * 2 * p.nwg))) return rc;
     if ((rc = dalloc (h, &p.mscr, B * 2 * ((p.nwg + 127u) / 128u)))) return rc;
     if ((rc = dalloc (h, &p.spart, B * 11 * p.nsp * 8))) return rc;    // 8 sub-trees per work-group; padding stays 0.f
-    if ((rc = dalloc (h, &p.mom, B * 2 * 18 * p.nb))) return rc;
+    // (behind the moments: trimming's result, selection state, histograms and keys — icp_trim_area; zeroed: ICP_MEM_TRIM reads 0 until a
+    // trimmed iteration has run, and the histograms and counters start clear)
+    if ((rc = dalloc (h, &p.mom, B * 2 * 18 * p.nb + (icp_trim_words (batch, m) + 1u) / 2u))) return rc;
     if ((rc = dalloc (h, &p.ml1, B * 18 * ((p.nb + 127u) / 128u)))) return rc;
     if ((rc = dalloc (h, &p.cst, B * 2))) return rc;
     if ((rc = dalloc (h, &p.st, B))) return rc;
@@ -353,6 +355,7 @@ size_t icp_mem_size (icp_handle h, int mem)
         case ICP_MEM_RBC_N: case ICP_MEM_RBC_O: return (size_t) p.nr * 4;
         case ICP_MEM_R: case ICP_MEM_RK: return 36;
         case ICP_MEM_NN: case ICP_MEM_QT: return (size_t) p.m * 16;
+        case ICP_MEM_TRIM: return 16;
         default: return 0;
     }
 }
@@ -382,6 +385,7 @@ static int mem_ptr (icp_context *h, uint32_t b, int mem, const void **src)
         case ICP_MEM_NN: *src = p.PF + (size_t) b * p.m; break;
         case ICP_MEM_QT: *src = p.PM + (size_t) b * p.m; break;
         case ICP_MEM_W: *src = reinterpret_cast<const float *> (p.PF + (size_t) b * p.m) + 3; break;
+        case ICP_MEM_TRIM: *src = icp_trim_area (p) + 4u * b; break;
         default: return fail (h, ICP_EINVAL, "unknown icp_mem value");
     }
     return ICP_OK;
@@ -644,7 +648,7 @@ int icp_set_rejection (icp_handle h, int flags, float max_dist) try
     if (!h) return fail (h, ICP_EINVAL, "icp_set_rejection: null handle");
     { int rc = outputs_before_change (h); if (rc) return rc; }
     const bool dist = max_dist > 0.f && !std::isinf (max_dist);
-    h->p.reject = (uint32_t) flags | (dist ? ICP_REJECT_DIST_ON : 0u);
+    h->p.reject = (uint32_t) flags | (dist ? ICP_REJECT_DIST_ON : 0u) | (h->p.reject & ICP_REJECT_TRIM_ON);
     h->p.reject_max_dist = max_dist;
     h->p.reject_d2 = dist ? (float) ((double) max_dist * (double) max_dist) : 0.f;     // (the product of two floats is exact in double)
     ++h->param_gen; return ICP_OK;
@@ -654,8 +658,42 @@ int icp_get_rejection (icp_handle h, int *flags, float *max_dist) try
 {
     api_guard guard_ (h);
     if (!h) return ICP_EINVAL;
-    if (flags) *flags = (int) (h->p.reject & ~ICP_REJECT_DIST_ON);
+    if (flags) *flags = (int) (h->p.reject & ~(ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON));
     if (max_dist) *max_dist = h->p.reject_max_dist;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+// trimmed ICP (include/icp_amd.h, icp_trim.hip).  On <-> off changes which kernels run — the REJ search, select and apply, no chained form —:
+// the route of icp_set_reduce_mode (graphs captured anew).  A new fraction while trimming stays on is a parameter update.
+int icp_set_trimming (icp_handle h, float keep_fraction) try
+{
+    api_guard guard_ (h);
+    if (!(keep_fraction > 0.f && keep_fraction <= 1.f)) return fail (h, ICP_EINVAL, "icp_set_trimming: keep_fraction must be in (0, 1] (1: off)");
+    if (!h) return fail (h, ICP_EINVAL, "icp_set_trimming: null handle");
+    { int rc = outputs_before_change (h); if (rc) return rc; }
+    const bool on = keep_fraction < 1.f;
+    if (on == icp_trimming (h->p)) {
+        if (on) { h->p.trim_keep = keep_fraction; ++h->param_gen; }
+        return ICP_OK;
+    }
+    if (on) { h->p.reject |= ICP_REJECT_TRIM_ON; h->p.trim_keep = keep_fraction; }
+    else {
+        h->p.reject &= ~ICP_REJECT_TRIM_ON; h->p.trim_keep = 0.f;
+        if (h->inited) {                                                 // ICP_MEM_TRIM reads zeros while trimming is off
+            int rc = set_device (h); if (rc) return rc;
+            if ((rc = run_close_all (h))) return rc;
+            HIPCHK (h, hipMemsetAsync (icp_trim_area (h->p), 0, sizeof (uint32_t) * 4u * h->p.batch, h->stream));
+        }
+    }
+    drop_graphs (h);
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+int icp_get_trimming (icp_handle h, float *keep_fraction) try
+{
+    api_guard guard_ (h);
+    if (!h || !keep_fraction) return ICP_EINVAL;
+    *keep_fraction = icp_trimming (h->p) ? h->p.trim_keep : 1.f;
     return ICP_OK;
 }
 ICP_CATCH_ALL
@@ -920,6 +958,7 @@ int icp_launches_per_iteration (icp_handle h, uint32_t *n) try
     if ((rc = icp_run_form (h, &form))) return rc;
     // (fused, large sets: the first level of the moment tree is a launch of its own — icp_launch_finalize)
     *n = form != ICP_FORM_SEPARATE ? 1u : h->p.fused ? ((h->p.nb + 127u) / 128u > ICP_L1_MIN_GROUPS ? 3u : 2u) : 4u;
+    if (icp_trimming (h->p)) *n += icp_trim_launches (h->p);          // (select: one or three launches, apply: one)
     return ICP_OK;
 }
 ICP_CATCH_ALL
@@ -965,7 +1004,7 @@ int icp_debug_stamps (icp_handle h, unsigned long long *out, uint32_t nblocks) t
     note_enqueue (h); note_outputs_stored (h);
     if (e == hipSuccess) {
         if (icp_chain_supported (p)) icp_launch_chain (p, h->stream, 2);
-        else { icp_launch_search (p, h->stream); if (p.fused) icp_launch_finalize (p, h->stream); }
+        else { icp_launch_search_stage (p, h->stream); if (p.fused) icp_launch_finalize (p, h->stream); }
         e = hipGetLastError ();
     }
     if (e == hipSuccess) e = hipStreamSynchronize (h->stream);
@@ -990,7 +1029,7 @@ int icp_profile_run (icp_handle h, uint32_t iterations, float *out_ms, float *to
     // the stages as separate launches (the chained form has no stage boundaries to time), events around each
     for (uint32_t r = 0; r < iterations && e == hipSuccess; ++r) {
         hipEvent_t *x = &ev[(size_t) r * 5];
-        e = hipEventRecord (x[0], h->stream); icp_launch_search (p, h->stream);
+        e = hipEventRecord (x[0], h->stream); icp_launch_search_stage (p, h->stream);     // (trimming on: select and apply time with the search)
         if (e == hipSuccess) e = hipEventRecord (x[1], h->stream);
         if (!p.fused) icp_launch_means (p, h->stream);
         if (e == hipSuccess) e = hipEventRecord (x[2], h->stream);

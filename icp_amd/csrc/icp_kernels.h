@@ -107,11 +107,30 @@ struct icp_params {
     uint32_t reject;             // ICP_REJECT_* flags (bit 0: a pair with an invalid endpoint, a point at the origin) | ICP_REJECT_DIST_ON; 0: off
     float reject_d2;             // ICP_REJECT_DIST_ON: max_dist^2 rounded to float (a pair is rejected when !(geo <= reject_d2))
     float reject_max_dist;       // max_dist as it was set (icp_get_rejection)
+    // trimmed ICP (icp_set_trimming): with ICP_REJECT_TRIM_ON in `reject`, each iteration keeps the closest fraction trim_keep of the
+    // pairs rejection leaves (icp_trim.hip).  The field sits in the struct's tail padding: sizeof (icp_params) must not grow — every
+    // kernel takes the struct by value, and the hidden arguments (the grid's size) lie behind it in the argument segment.
+    float trim_keep;             // keep_fraction in (0, 1] while trimming is on; 0 while it is off
 };
 #define ICP_REJECT_DIST_ON 0x80000000u   // icp_params::reject: the distance test is on (one scalar test of one word says whether anything is)
+#define ICP_REJECT_TRIM_ON 0x40000000u   // icp_params::reject: trimming is on (the REJ kernels, plus select and apply: icp_launch_trim)
+static_assert (sizeof (icp_params) == 480, "icp_params grew: the hidden kernel arguments of every kernel would move");
 
 // rejection on: the sum-W formulas in every mode, and a step of nothing accepted (sum W == 0) is the identity
 static __host__ __device__ __forceinline__ bool icp_rejecting (const icp_params &p) { return p.reject != 0u; }
+static __host__ __device__ __forceinline__ bool icp_trimming (const icp_params &p) { return (p.reject & ICP_REJECT_TRIM_ON) != 0u; }
+
+// Trimming's device buffers lie behind the moment partials, in the same allocation (icp_params has no room for another pointer), as
+// uint32 words: [batch][4] the result of the last iteration (t bits, n, K, accepted: ICP_MEM_TRIM), [batch][4] the state of the
+// multi-block selection (prefix, rank left, count below, arrivals), [batch][2048] its histograms, and for sets beyond one workgroup's
+// selection [batch][m] the keys.
+#define ICP_TRIM_ONE_BLOCK_MAX 16384u    // up to this many pairs per registration: the selection is one workgroup's (k_trim_select)
+#define ICP_TRIM_BINS 2048u
+static inline size_t icp_trim_words (uint32_t batch, uint32_t m)
+{
+    return (size_t) batch * (8u + ICP_TRIM_BINS) + (m > ICP_TRIM_ONE_BLOCK_MAX ? (size_t) batch * m : 0u);
+}
+static inline uint32_t *icp_trim_area (const icp_params &p) { return reinterpret_cast<uint32_t *> (p.mom + (size_t) p.batch * 2 * 18 * p.nb); }
 
 #define ICP_N_FULL(p, b) ((p).N + ((size_t) (p).batch + (b)) * (p).nr)
 
@@ -174,6 +193,7 @@ static __device__ __forceinline__ uint32_t icp_other_kind_near (const unsigned l
 // launchers (icp_kernels.hip, icp_build.hip)
 void icp_launch_build_rbc (const icp_params &p, hipStream_t s);
 void icp_launch_search (const icp_params &p, hipStream_t s);
+void icp_launch_search_stage (const icp_params &p, hipStream_t s);    // the search of an iteration: with trimming on, + select and apply
 void icp_launch_means (const icp_params &p, hipStream_t s);
 void icp_launch_sij (const icp_params &p, hipStream_t s);
 void icp_launch_finalize (const icp_params &p, hipStream_t s);
@@ -191,6 +211,8 @@ void icp_launch_owner_search (const icp_params &p, hipStream_t s);   // RBC cons
 void icp_launch_search_dense (const icp_params &p, hipStream_t s);          // icp_search_dense.hip: the dense variants (icp_dense (p))
 void icp_launch_search_rej (const icp_params &p, hipStream_t s);            // icp_search_rej.hip: every search with correspondence rejection on
 void icp_launch_chain_one_rej (const icp_params &p, hipStream_t s, uint32_t j, bool fresh, bool emit);
+void icp_launch_trim (const icp_params &p, hipStream_t s);                   // icp_trim.hip: k_trim_select (one or three launches) + k_trim_apply
+uint32_t icp_trim_launches (const icp_params &p);                             // how many that is
 void icp_launch_owner_search_dense (const icp_params &p, hipStream_t s);
 uint32_t icp_tbox_of (const icp_params &p);
 uint32_t icp_s2_wave_of (const icp_params &p);

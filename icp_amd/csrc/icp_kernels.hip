@@ -573,10 +573,21 @@ void icp_launch_finalize (const icp_params &p, hipStream_t s)
 
 __global__ void k_nop (icp_params p) { if (p.m == 0xFFFFFFFFu) p.st->k = 0; }
 
-// diagnostic: any subset of the iteration's kernels (bit 0 search, 1 means, 2 sij, 3 finalize, 4 empty kernel)
+// The search of an iteration.  Trimming on (icp_trim.hip): the REJ search stores its per-query outputs every time — the selection reads
+// them —, then k_trim_select and k_trim_apply.
+void icp_launch_search_stage (const icp_params &p, hipStream_t s)
+{
+    if (!icp_trimming (p)) { icp_launch_search (p, s); return; }
+    icp_params q = p;
+    q.emit = 1;
+    icp_launch_search (q, s);
+    icp_launch_trim (q, s);
+}
+
+// diagnostic: any subset of the iteration's kernels (bit 0 search — with trimming on, select and apply too —, 1 means, 2 sij, 3 finalize, 4 empty kernel)
 void icp_launch_masked (const icp_params &p, hipStream_t s, unsigned mask)
 {
-    if (mask & 1u) icp_launch_search (p, s);
+    if (mask & 1u) icp_launch_search_stage (p, s);
     if ((mask & 2u) && !p.fused) icp_launch_means (p, s);
     if ((mask & 4u) && !p.fused) icp_launch_sij (p, s);
     if (mask & 8u) icp_launch_finalize (p, s);
@@ -590,7 +601,8 @@ void icp_launch_masked (const icp_params &p, hipStream_t s, unsigned mask)
 // removes outweighs every block re-deriving T), 2 always (sizes the second tree level of the prologue can hold).
 bool icp_chain_supported (const icp_params &p)
 {
-    return p.fused && p.nb <= 4096u && p.nr <= 1024u && (p.chain == 2 || (p.chain == 1 && !icp_dense (p)));
+    // (trimming: the selection sits between the search and the finalize, which the chained form folds into one launch)
+    return p.fused && !icp_trimming (p) && p.nb <= 4096u && p.nr <= 1024u && (p.chain == 2 || (p.chain == 1 && !icp_dense (p)));
 }
 
 // launch j of a chain (icp_search.h: ks_launch_chain_one)
@@ -624,7 +636,7 @@ void icp_launch_chain (const icp_params &p, hipStream_t s, uint32_t iterations, 
 
 void icp_launch_iteration (const icp_params &p, hipStream_t s)
 {
-    icp_launch_search (p, s);
+    icp_launch_search_stage (p, s);
     if (!p.fused) {
         icp_launch_means (p, s);
         icp_launch_sij (p, s);

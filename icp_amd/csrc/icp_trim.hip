@@ -1,0 +1,271 @@
+// icp_trim.hip — trimmed ICP (icp_set_trimming, include/icp_amd.h): every iteration keeps the closest fraction ξ of the pairs that
+// correspondence rejection leaves, and gives the rest the weight +0.
+//
+// An iteration with trimming on is: the REJ search (icp_search_rej.hip), which stores its per-query outputs; k_trim_select, which finds
+// per registration n (the candidates), K = ceil (ξ n) and t, the K-th smallest key; k_trim_apply, which zeroes the weights of the pairs
+// above t and rewrites the search blocks' partials in exactly the order the search wrote them; then the unchanged tail of the iteration
+// (k_finalize_fused<ROT, true>, or k_means / k_sij / k_finalize).  A trimmed pair is then exactly a rejected pair, and the oracle's
+// pieces with the trimmed rows zeroed give the same bits.  None of the existing kernels carries any of this code.
+//
+// The key of a pair is the bit pattern of its geo = (ex - f0)^2 + (ey - f1)^2 + (ez - f2)^2 in fp32, summed in that order (the
+// translation unit is built with -ffp-contract=off): a non-negative float orders as its bits do as uint32.  A pair that is no
+// candidate — weight 0, geo not finite, no query — gets the key ~0u, above every candidate's.
+//
+// The selection is a radix select on 11 / 11 / 10-bit digits: a histogram of the digit over the keys that match the digits picked so
+// far, then the bin that holds the remaining rank.  Up to ICP_TRIM_ONE_BLOCK_MAX pairs per registration one workgroup does all three
+// passes with the keys in registers and the histogram in LDS (grid.y = registration); beyond it every pass is a launch of many
+// workgroups whose LDS histograms are merged by device atomics, and the workgroup that arrives last picks the bin (k_trim_select_pass).
+// Both take the same t: the K-th smallest key is one number.
+#include "icp_search.h"
+
+namespace {
+
+constexpr uint32_t TRIM_NONE = 0xFFFFFFFFu;     // the key of a pair that is no candidate
+
+__device__ __forceinline__ uint32_t trim_key (float4 f, float4 q)
+{
+    if (f.w == 0.f) return TRIM_NONE;
+    const float gx = q.x - f.x, gy = q.y - f.y, gz = q.z - f.z;
+    const float geo = (gx * gx + gy * gy) + gz * gz;
+    return geo < __builtin_inff () ? __float_as_uint (geo) : TRIM_NONE;      // (NaN and +inf: no candidate)
+}
+
+// pass d of the select: the digit's shift and width, and the shift above which a key must match the prefix picked so far
+__device__ __forceinline__ uint32_t trim_shift (int d) { return d == 0 ? 21u : d == 1 ? 10u : 0u; }
+__device__ __forceinline__ bool trim_match (uint32_t key, uint32_t prefix, int d)
+{
+    return key != TRIM_NONE && (d == 0 || (key >> (trim_shift (d - 1))) == (prefix >> trim_shift (d - 1)));
+}
+__device__ __forceinline__ uint32_t trim_digit (uint32_t key, int d) { return (key >> trim_shift (d)) & (d == 2 ? 1023u : 2047u); }
+
+// K = ceil (ξ n) (ξ n is exact in double: a float times an integer below 2^21)
+__device__ __forceinline__ uint32_t trim_rank (float keep, uint32_t n)
+{
+    return min ((uint32_t) ceil ((double) keep * (double) n), n);
+}
+
+// Block-wide: the bin j of s_hist[0 .. 2048) where the cumulative count reaches kk (1 <= kk <= the total): s_pick = (j, count in the
+// bins below j, count of bin j).  Every thread of the block calls it; it ends behind a barrier.
+template <int NT>
+__device__ void trim_pick (const uint32_t *s_hist, uint32_t kk, uint32_t *s_wsum, uint32_t *s_pick)
+{
+    constexpr int PER = (int) ICP_TRIM_BINS / NT;
+    const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
+    uint32_t c[PER], sum = 0u;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) { c[k] = s_hist[t * PER + k]; sum += c[k]; }
+    uint32_t incl = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t u = __shfl_up (incl, d); if ((int) lane >= d) incl += u; }
+    if (lane == 63u) s_wsum[wv] = incl;
+    __syncthreads ();
+    uint32_t before = incl - sum;
+    for (uint32_t w = 0; w < wv; ++w) before += s_wsum[w];
+    if (before < kk && kk <= before + sum) {                 // (exactly one thread)
+        uint32_t run = before;
+        bool found = false;
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            if (!found && run + c[k] >= kk) { s_pick[0] = t * PER + k; s_pick[1] = run; s_pick[2] = c[k]; found = true; }
+            run += c[k];
+        }
+    }
+    __syncthreads ();
+}
+
+template <int NT>
+__device__ __forceinline__ uint32_t block_sum (uint32_t v, uint32_t *s_wsum)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor (v, d);
+    __syncthreads ();                                        // (s_wsum may still be read by a trim_pick before)
+    if ((threadIdx.x & 63u) == 0u) s_wsum[threadIdx.x >> 6] = v;
+    __syncthreads ();
+    uint32_t s = 0u;
+#pragma unroll
+    for (int w = 0; w < NT / 64; ++w) s += s_wsum[w];
+    __syncthreads ();
+    return s;
+}
+
+// ------------------------------------------------------------------------------------------
+// k_trim_select — one workgroup per registration (m <= ICP_TRIM_ONE_BLOCK_MAX): 16 keys per thread in registers, three passes
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__ (1024) void k_trim_select (icp_params p, uint32_t *area)
+{
+    constexpr int NT = 1024, KPT = (int) ICP_TRIM_ONE_BLOCK_MAX / NT;
+    __shared__ uint32_t s_hist[ICP_TRIM_BINS], s_wsum[NT / 64], s_pick[3];
+    const uint32_t b = blockIdx.y, t = threadIdx.x, m = p.m;
+    if (p.check && p.st[b].done) return;                     // (a converged registration: its last iteration's outputs stay)
+    const float4 *PF = p.PF + (size_t) b * m, *PM = p.PM + (size_t) b * m;
+    uint32_t key[KPT], cnt = 0u;
+#pragma unroll
+    for (int k = 0; k < KPT; ++k) {
+        const uint32_t i = t + (uint32_t) (NT * k);
+        key[k] = i < m ? trim_key (PF[i], PM[i]) : TRIM_NONE;
+        cnt += key[k] != TRIM_NONE ? 1u : 0u;
+    }
+    const uint32_t n = block_sum<NT> (cnt, s_wsum), K = trim_rank (p.trim_keep, n);
+    uint32_t *out = area + 4u * b;
+    if (n == 0u) {                                           // nothing to keep: k_trim_apply trims every pair
+        if (t == 0u) { out[0] = 0u; out[1] = 0u; out[2] = 0u; out[3] = 0u; }
+        return;
+    }
+    uint32_t prefix = 0u, kk = K, below = 0u, at = 0u;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        for (uint32_t j = t; j < ICP_TRIM_BINS; j += NT) s_hist[j] = 0u;
+        __syncthreads ();
+#pragma unroll
+        for (int k = 0; k < KPT; ++k)
+            if (trim_match (key[k], prefix, d)) atomicAdd (&s_hist[trim_digit (key[k], d)], 1u);
+        __syncthreads ();
+        trim_pick<NT> (s_hist, kk, s_wsum, s_pick);
+        const uint32_t j = s_pick[0], lo = s_pick[1];
+        at = s_pick[2];
+        prefix |= j << trim_shift (d); kk -= lo; below += lo;
+        __syncthreads ();                                    // (s_pick and s_hist are written again by the next pass)
+    }
+    if (t == 0u) { out[0] = prefix; out[1] = n; out[2] = K; out[3] = below + at; }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_trim_select_pass<D> — pass D of the selection of large sets: 2048 pairs per workgroup, grid (ceil (m / 2048), batch).  Pass 0
+// computes the keys and leaves them for passes 1 and 2.  The workgroups merge their histograms into the registration's by device
+// atomics; the one that arrives last picks the bin, leaves the state for the next pass and clears the histogram and the counter.
+// ------------------------------------------------------------------------------------------
+template <int D>
+__global__ __launch_bounds__ (256) void k_trim_select_pass (icp_params p, uint32_t *area)
+{
+    constexpr int NT = 256, KPT = 8;
+    __shared__ uint32_t s_hist[ICP_TRIM_BINS], s_wsum[NT / 64], s_pick[3];
+    __shared__ uint32_t s_last;
+    const uint32_t b = blockIdx.y, t = threadIdx.x, m = p.m, B = p.batch;
+    if (p.check && p.st[b].done) return;
+    uint32_t *out = area + 4u * b, *sel = area + 4u * B + 4u * b, *hist = area + 8u * B + (size_t) ICP_TRIM_BINS * b;
+    uint32_t *keys = area + (8u + ICP_TRIM_BINS) * (size_t) B + (size_t) b * m;
+    if (D > 0 && out[1] == 0u) return;                       // (no candidate: pass 0 has said so)
+    const uint32_t prefix = D > 0 ? sel[0] : 0u;
+    for (uint32_t j = t; j < ICP_TRIM_BINS; j += NT) s_hist[j] = 0u;
+    __syncthreads ();
+    const float4 *PF = p.PF + (size_t) b * m, *PM = p.PM + (size_t) b * m;
+    const uint32_t i0 = blockIdx.x * (uint32_t) (NT * KPT) + t;
+#pragma unroll
+    for (int k = 0; k < KPT; ++k) {
+        const uint32_t i = i0 + (uint32_t) (NT * k);
+        uint32_t key = TRIM_NONE;
+        if (i < m) {
+            if constexpr (D == 0) { key = trim_key (PF[i], PM[i]); keys[i] = key; }
+            else key = keys[i];
+        }
+        if (trim_match (key, prefix, D)) atomicAdd (&s_hist[trim_digit (key, D)], 1u);
+    }
+    __syncthreads ();
+    for (uint32_t j = t; j < ICP_TRIM_BINS; j += NT)
+        if (s_hist[j]) __hip_atomic_fetch_add (hist + j, s_hist[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __threadfence ();                                        // this thread's counts, before its arrival counts
+    __syncthreads ();                                        // (every wave's: the ticket below speaks for the whole workgroup)
+    if (t == 0u) s_last = __hip_atomic_fetch_add (sel + 3, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u ? 1u : 0u;
+    __syncthreads ();
+    if (!s_last) return;
+    __threadfence ();                                        // the others' counts
+    for (uint32_t j = t; j < ICP_TRIM_BINS; j += NT) {
+        s_hist[j] = __hip_atomic_load (hist + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store (hist + j, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (clear for the next pass)
+    }
+    if (t == 0u) __hip_atomic_store (sel + 3, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads ();
+    uint32_t kk, below, n = 0u, K = 0u;
+    if constexpr (D == 0) {
+        uint32_t c = 0u;
+        for (uint32_t j = t; j < ICP_TRIM_BINS; j += NT) c += s_hist[j];
+        n = block_sum<NT> (c, s_wsum); K = trim_rank (p.trim_keep, n);
+        if (n == 0u) {
+            if (t == 0u) { out[0] = 0u; out[1] = 0u; out[2] = 0u; out[3] = 0u; }
+            return;
+        }
+        kk = K; below = 0u;
+    } else { kk = sel[1]; below = sel[2]; }
+    trim_pick<NT> (s_hist, kk, s_wsum, s_pick);
+    if (t == 0u) {
+        const uint32_t j = s_pick[0], lo = s_pick[1];
+        sel[0] = prefix | (j << trim_shift (D)); sel[1] = kk - lo; sel[2] = below + lo;
+        if constexpr (D == 0) { out[1] = n; out[2] = K; }
+        if constexpr (D == 2) { out[0] = prefix | j; out[3] = below + lo + s_pick[2]; }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_trim_apply<FUSED> — one wave per block of the search, grid (nb | 2 nwg, batch).  Pair e of the block is the search's query e
+// (fused: fused_query_index of tile blockIdx.x; reference order: group blockIdx.x / 2, parity blockIdx.x & 1).  A trimmed pair's
+// weight becomes +0 in PF.w (the W output); then the block's partials are written again from PF / PM as ks_epilogue computes them:
+// the 18 double moments of its 64 pairs (an accepted pair's terms from the same floats, a trimmed pair's exact zeros) through the
+// same halving tree into p.mom's slot of the tile, or the weight partial (row_tree4) into p.wpart.
+// ------------------------------------------------------------------------------------------
+template <bool FUSED>
+__global__ __launch_bounds__ (64) void k_trim_apply (icp_params p, const uint32_t *area, uint32_t tpr_magic)
+{
+    __shared__ double s_mom[FUSED ? ICP_NMOM : 1][64];
+    __shared__ float s_w[64];
+    const uint32_t b = blockIdx.y, lane = threadIdx.x, m = p.m;
+    if (p.check && p.st[b].done) return;
+    const uint32_t t = area[4u * b], K = area[4u * b + 2u];
+    const uint32_t i = FUSED ? fused_query_index (m, p.side, tpr_magic, blockIdx.x, lane) : (blockIdx.x >> 1) * 128u + 2u * lane + (blockIdx.x & 1u);
+    const bool v = i < m;
+    float4 f = make_float4 (0.f, 0.f, 0.f, 0.f), q = f;
+    if (v) { f = p.PF[(size_t) b * m + i]; q = p.PM[(size_t) b * m + i]; }
+    const uint32_t key = v ? trim_key (f, q) : TRIM_NONE;
+    const bool acc = key != TRIM_NONE && K != 0u && key <= t;
+    if (v && f.w != 0.f && !acc) reinterpret_cast<float *> (p.PF + (size_t) b * m + i)[3] = 0.f;
+    if constexpr (FUSED) {
+        // (ks_epilogue's products, term for term)
+        double W = acc ? (double) f.w : 0.0;
+        double g0 = acc ? (double) f.x : 0.0, g1 = acc ? (double) f.y : 0.0, g2 = acc ? (double) f.z : 0.0;
+        double q0 = acc ? (double) q.x : 0.0, q1 = acc ? (double) q.y : 0.0, q2 = acc ? (double) q.z : 0.0;
+        double wq0 = W * q0, wq1 = W * q1, wq2 = W * q2;
+        s_mom[0][lane] = W;
+        s_mom[1][lane] = W * g0; s_mom[2][lane] = W * g1; s_mom[3][lane] = W * g2;
+        s_mom[4][lane] = wq0; s_mom[5][lane] = wq1; s_mom[6][lane] = wq2;
+        s_mom[7][lane] = wq0 * g0; s_mom[8][lane] = wq0 * g1; s_mom[9][lane] = wq0 * g2;
+        s_mom[10][lane] = wq1 * g0; s_mom[11][lane] = wq1 * g1; s_mom[12][lane] = wq1 * g2;
+        s_mom[13][lane] = wq2 * g0; s_mom[14][lane] = wq2 * g1; s_mom[15][lane] = wq2 * g2;
+        s_mom[16][lane] = W * ((g0 * g0 + g1 * g1) + g2 * g2);
+        s_mom[17][lane] = W * ((q0 * q0 + q1 * q1) + q2 * q2);
+        __syncthreads ();
+        // the search's halving tree over the 64 pairs, one 16-lane row per moment (four moments per round)
+        const uint32_t l = lane & 15u;
+        double *mom = p.mom + (size_t) b * 2 * ICP_NMOM * p.nb;
+#pragma unroll
+        for (uint32_t r = 0; r < (ICP_NMOM + 3u) / 4u; ++r) {
+            const uint32_t mrow = r * 4u + (lane >> 4), k = min (mrow, (uint32_t) ICP_NMOM - 1u);
+            double c0 = s_mom[k][l] + s_mom[k][l + 32], c1 = s_mom[k][l + 16] + s_mom[k][l + 48];
+            double s = row_tree_tail_d (c0 + c1);
+            if (l == 0 && mrow < ICP_NMOM) mom[(size_t) mrow * p.nb + blockIdx.x] = s;
+        }
+    } else {
+        s_w[lane] = acc ? f.w : 0.f;
+        __syncthreads ();
+        const uint32_t l = lane & 15u;
+        float a[4] = { s_w[l], s_w[l + 16], s_w[l + 32], s_w[l + 48] };
+        float s = row_tree4 (a);
+        if (lane == 0) p.wpart[(size_t) b * 2 * p.nwp + blockIdx.x] = s;
+    }
+}
+
+}  // namespace
+
+uint32_t icp_trim_launches (const icp_params &p) { return (p.m <= ICP_TRIM_ONE_BLOCK_MAX ? 1u : 3u) + 1u; }
+
+void icp_launch_trim (const icp_params &p, hipStream_t s)
+{
+    uint32_t *area = icp_trim_area (p);
+    if (p.m <= ICP_TRIM_ONE_BLOCK_MAX) hipLaunchKernelGGL (k_trim_select, dim3 (1, p.batch), dim3 (1024), 0, s, p, area);
+    else {
+        const dim3 grid ((p.m + 2047u) / 2048u, p.batch);
+        hipLaunchKernelGGL (k_trim_select_pass<0>, grid, dim3 (256), 0, s, p, area);
+        hipLaunchKernelGGL (k_trim_select_pass<1>, grid, dim3 (256), 0, s, p, area);
+        hipLaunchKernelGGL (k_trim_select_pass<2>, grid, dim3 (256), 0, s, p, area);
+    }
+    if (p.fused) hipLaunchKernelGGL (k_trim_apply<true>, dim3 (p.nb, p.batch), dim3 (64), 0, s, p, (const uint32_t *) area, icp_tpr_magic (p.side));
+    else hipLaunchKernelGGL (k_trim_apply<false>, dim3 (2 * p.nwg, p.batch), dim3 (64), 0, s, p, (const uint32_t *) area, icp_tpr_magic (p.side));
+}

@@ -12,15 +12,18 @@ from .io import load_pc8d, save_pc8d
 
 
 def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, angle_threshold=0.001,
-                    translation_threshold=0.01, reduce_mode=ReduceMode.FUSED, reject_invalid=False, max_dist=None):
+                    translation_threshold=0.01, reduce_mode=ReduceMode.FUSED, reject_invalid=False, max_dist=None, trim=1.0):
     """Returns (T[8], k, latency_ms, transformed moving cloud).  reject_invalid / max_dist: correspondence rejection
-    (ICPStep.set_rejection; not the reference's behaviour, off by default)."""
+    (ICPStep.set_rejection), trim: the fraction of pairs trimmed ICP keeps (ICPStep.set_trimming; 1.0: off); neither is the
+    reference's behaviour, both are off by default."""
     reg = ICP(device)
     reg.init(16384, 256, a, c, max_iterations, angle_threshold, translation_threshold)   # src/ocl_icp_reg.cpp:81-88
     reg.setPowerMode(PowerMode.SQUARED)
     reg.setReduceMode(reduce_mode)
     if reject_invalid or max_dist:
         reg.set_rejection(reject_invalid, max_dist)
+    if trim != 1.0:
+        reg.set_trimming(trim)
     reg.write_cloud(Memory.F, fixed)
     reg.write_cloud(Memory.M, moving)
     reg.buildRBC()
@@ -50,6 +53,13 @@ def track(frames, device=0, a=2e2, c=1e-6, warm_start=False, **kw):
     reg.close()
 
 
+def _fraction(s):
+    v = float(s)
+    if not 0.0 < v <= 1.0:
+        raise argparse.ArgumentTypeError("must be in (0, 1], got %s" % s)
+    return v
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("fixed")
@@ -61,9 +71,11 @@ def main(argv=None):
                     help="give pairs with an invalid endpoint (a pixel without depth) weight 0 (not reference behaviour)")
     ap.add_argument("--max-dist", type=float, default=None,
                     help="give pairs farther apart than this geometric distance (mm) weight 0 (not reference behaviour)")
+    ap.add_argument("--trim", type=_fraction, default=1.0, metavar="FRACTION",
+                    help="trimmed ICP: keep the closest FRACTION in (0, 1] of the pairs in every iteration (not reference behaviour)")
     args = ap.parse_args(argv)
     T, k, ms, out = register_clouds(load_pc8d(args.fixed), load_pc8d(args.moving), args.device, a=args.alpha,
-                                    reject_invalid=args.reject_invalid, max_dist=args.max_dist)
+                                    reject_invalid=args.reject_invalid, max_dist=args.max_dist, trim=args.trim)
     q, t, s = T[:4], T[4:7], T[7]
     sinth_2 = float(np.linalg.norm(q[:3]))
     angle = 180.0 / math.pi * 2 * math.atan2(sinth_2, float(q[3]))

@@ -598,6 +598,12 @@ namespace ICP
         void setRejection (int flags, float max_dist = 0.f) { check (icp_set_rejection (h, flags, max_dist)); }
         void getRejection (int &flags, float &max_dist) { check (icp_get_rejection (h, &flags, &max_dist)); }
 
+        /*! \brief Trimmed ICP (icp_set_trimming, include/icp_amd.h; not in the reference, off by default): every iteration keeps the
+         *         closest `keep_fraction` of the pairs rejection leaves and gives the rest weight 0 (1: off).  Kinect data needs
+         *         ICP_REJECT_INVALID alongside it. */
+        void setTrimming (float keep_fraction) { check (icp_set_trimming (h, keep_fraction)); }
+        float getTrimming () { float f = 1.f; check (icp_get_trimming (h, &f)); return f; }
+
         float *hPtrInF;  /*!< Staging buffer of the fixed set (reference: mapped H_IN_F). */
         float *hPtrInM;  /*!< Staging buffer of the moving set. */
         float *hPtrIOT;  /*!< Staging buffer of [q | t, s]. */

@@ -85,6 +85,7 @@ typedef enum {
     ICP_MEM_RK = 17,       /* out  float[9]     incremental rotation, row-major         */
     ICP_MEM_NN = 18,       /* out  m x float4   matched fixed xyz (+ weight in .w)      */
     ICP_MEM_QT = 19,       /* out  m x float4   transformed moving xyz (+ dist in .w)   */
+    ICP_MEM_TRIM = 20,     /* out  uint32[4]    trimming, last iteration: t (float bits), n, K, accepted (0 when off) */
     ICP_MEM_COUNT_
 } icp_mem;
 
@@ -239,6 +240,30 @@ int icp_get_metric_scale (icp_handle h, float *f_g);
 #define ICP_REJECT_INVALID 1
 int icp_set_rejection (icp_handle h, int flags, float max_dist);
 int icp_get_rejection (icp_handle h, int *flags, float *max_dist);
+
+/* Trimmed ICP (TrICP, Chetverikov et al.; not reference behaviour): in every iteration keep the closest fraction of the pairs and give
+ * the rest weight 0.  The rule:
+ *   - keep_fraction xi is in (0, 1].  xi = 1 is the default and means off: the same kernels, launches, graphs and bits as without it.
+ *   - Candidates are the pairs that survive icp_set_rejection's rules and have a weight != 0, and whose geo is finite.  geo is the
+ *     quantity the rejection rule defines: (ex - f0)^2 + (ey - f1)^2 + (ez - f2)^2 in fp32, summed in that order, with no contraction.
+ *     Let n be the number of candidates.
+ *   - K = (uint32_t) ceil ((double) xi * (double) n).
+ *   - t is the K-th smallest geo among the candidates, counting from 1.  geo is never negative, so its float bits order the same
+ *     way as uint32.
+ *   - Accepted pairs are the candidates with geo <= t.  All ties at t are kept, so the accepted count can be above K.  Every other
+ *     pair is trimmed.  A trimmed pair behaves exactly like a rejected one: its correspondence is kept, its weight is +0 (written to
+ *     the W and NN outputs), and its moment, mean and S terms are exact zeros.  As with rejection, REGULAR mode uses the sum-W
+ *     formulas with w in {0, 1}.
+ *   - If n == 0, nothing is accepted: the sum W == 0 identity step (T unchanged, ICP::run stops).
+ *   - Each registration of a batched handle (icp_init_batched) computes its own n, K and t.
+ * Trimming is applied after icp_set_rejection's rules.  Kinect data needs ICP_REJECT_INVALID alongside it: invalid <-> invalid pairs
+ * (pixels without depth in both frames) sit at geo = 0 and would be the first pairs kept.
+ * ICP_MEM_TRIM holds (t bits, n, K, accepted) of the last iteration per registration; zeros while trimming is off.  With trimming on
+ * the per-query outputs are stored by every iteration, and an iteration is the separate form (icp_run_form: the search, the
+ * selection, the pass that applies it, the usual tail — icp_launches_per_iteration counts them).  The setting applies to single,
+ * batched and tracked registrations and survives icp_init.  ICP_EINVAL: keep_fraction NaN, <= 0 or > 1. */
+int icp_set_trimming (icp_handle h, float keep_fraction);
+int icp_get_trimming (icp_handle h, float *keep_fraction);
 int icp_set_scaling (icp_handle h, float c);
 int icp_get_max_iterations (icp_handle h, uint32_t *n);
 int icp_set_max_iterations (icp_handle h, uint32_t n);
@@ -423,6 +448,7 @@ int icp_batch_init (icp_batch_handle b, uint32_t registrations, uint32_t m, uint
                     uint32_t max_iterations, double angle_threshold, double translation_threshold);
 int icp_batch_set_modes (icp_batch_handle b, int reduce_mode, int power_mode);
 int icp_batch_set_rejection (icp_batch_handle b, int flags, float max_dist);                /* icp_set_rejection on every slot */
+int icp_batch_set_trimming (icp_batch_handle b, float keep_fraction);                        /* icp_set_trimming on every slot */
 int icp_batch_write (icp_batch_handle b, uint32_t i, int mem, const void *host_ptr);       /* mem: F, M or T of registration i */
 int icp_batch_build_rbc (icp_batch_handle b);
 int icp_batch_run (icp_batch_handle b);                                                      /* ICP::run of every registration */
@@ -456,7 +482,8 @@ int icp_time_run_fixed_tail (icp_handle h, uint32_t iterations, uint32_t reps, i
  * (40 there) from the current state, no convergence test, with a per-step, per-stage table (the reference fills a
  * ProfilingInfo<40> per kernel class through the run (timer) overloads, e.g. :2359-2399).  The stages run as separate
  * launches with HIP events around each: out_ms[it * 4 + s], s = icp_stage; fused reductions have no means / Sij
- * stage (those entries read ~0: two events back to back).  *total_ms (may be NULL) = first event to last.  Blocking.
+ * stage (those entries read ~0: two events back to back); with trimming on (icp_set_trimming) the search stage includes the
+ * selection and the pass that applies it.  *total_ms (may be NULL) = first event to last.  Blocking.
  * (The graphs behind icp_run / icp_run_fixed fuse stages further — icp_launches_per_iteration — and are timed whole by
  * icp_time_run_fixed.) */
 typedef enum { ICP_STAGE_SEARCH = 0, ICP_STAGE_MEANS = 1, ICP_STAGE_SIJ = 2, ICP_STAGE_FINALIZE = 3, ICP_STAGE_COUNT_ = 4 } icp_stage;

@@ -72,6 +72,9 @@ public:
     /*! \brief Correspondence rejection of the registration (ICPStep::setRejection; not in the reference's demo, off by default). */
     void setRejection (int flags, float max_dist = 0.f) { reg.setRejection (flags, max_dist); }
     void getRejection (int &flags, float &max_dist) { reg.getRejection (flags, max_dist); }
+    /*! \brief Trimmed ICP of the registration (ICPStep::setTrimming; not in the reference's demo, off by default). */
+    void setTrimming (float keep_fraction) { reg.setTrimming (keep_fraction); }
+    float getTrimming () { return reg.getTrimming (); }
 
     /*! \brief The moving cloud after `registerPC ()` (the reference writes it into the GL vertex buffer). */
     const std::vector<icp_float8>& transformed () const { return moved; }
