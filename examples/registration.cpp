@@ -6,12 +6,15 @@
 //   registration NAME                     data/NAME_1.bin, data/NAME_2.bin      (the reference's argument convention, :299-329)
 //   registration A B                      data/A.bin, data/B.bin — or A and B themselves when they name existing files
 //   ... [--out FILE] [--device N] [--reference-order] [--svd] [--reject-invalid] [--max-dist MM] [--trim FRACTION]
+//       [--point-to-plane MU]
 //
 // --reject-invalid / --max-dist: correspondence rejection (icp_set_rejection: pairs with a pixel without depth at either end / pairs
 // farther apart than MM get weight 0).  --trim: trimmed ICP (icp_set_trimming: every iteration keeps the closest FRACTION in (0, 1] of the
-// pairs).  Not the reference's behaviour; off by default.
+// pairs).  --point-to-plane: point-to-plane ICP plus MU (>= 0) times the point-to-point error (icp_set_error_metric), the normals from the
+// fixed 128 x 128 landmark grid (ICP_NORMALS_GRID).  Not the reference's behaviour; off by default.
 //
 // A cloud file is 640 x 480 points of 8 floats [x y z 1 r g b 1], little endian, row-major (src/kinect_frame_grabber.cpp:252-272).
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -38,11 +41,12 @@ std::string data_path (const std::string &name) { return exists (name) ? name : 
 
 template <cl_algo::ICP::ICPStepConfigT RC>
 int run (int device, icp::Mode mode, const std::vector<icp_float8> &pc1, const std::vector<icp_float8> &pc2, const std::string &out,
-         int reject_flags, float max_dist, float trim)
+         int reject_flags, float max_dist, float trim, float p2pl_mu)
 {
     ICPReg<RC, cl_algo::ICP::ICPStepConfigW::WEIGHTED> app (device, mode);
     if (reject_flags || max_dist > 0.f) app.setRejection (reject_flags, max_dist);
     if (trim != 1.f) app.setTrimming (trim);
+    if (p2pl_mu >= 0.f) { app.setNormals (ICP_NORMALS_GRID, 128); app.setErrorMetric (ICP_METRIC_POINT_TO_PLANE, p2pl_mu); }
     app.init (pc1, pc2);
     app.registerPC ();                                        // buildRBC + run + transform + the reference's report
     auto &reg = app.registration ();
@@ -64,7 +68,7 @@ int main (int argc, char **argv)
     std::vector<std::string> names;
     std::string out;
     int device = 0; bool svd = false;
-    int reject_flags = 0; float max_dist = 0.f, trim = 1.f;
+    int reject_flags = 0; float max_dist = 0.f, trim = 1.f, p2pl_mu = -1.f;     // (p2pl_mu < 0: point-to-point)
     icp::Mode mode = icp::Mode::FAST;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -77,6 +81,10 @@ int main (int argc, char **argv)
         else if (a == "--trim" && i + 1 < argc) {
             trim = std::strtof (argv[++i], nullptr);
             if (!(trim > 0.f && trim <= 1.f)) { std::fprintf (stderr, "--trim: FRACTION must be in (0, 1]\n"); return 2; }
+        }
+        else if (a == "--point-to-plane" && i + 1 < argc) {
+            p2pl_mu = std::strtof (argv[++i], nullptr);
+            if (!(p2pl_mu >= 0.f && std::isfinite (p2pl_mu))) { std::fprintf (stderr, "--point-to-plane: MU must be finite and >= 0\n"); return 2; }
         }
         else if (a.rfind ("--", 0) == 0) { std::fprintf (stderr, "unknown option %s\n", a.c_str ()); return 2; }
         else names.push_back (a);
@@ -93,8 +101,8 @@ int main (int argc, char **argv)
         } else {
             read_cloud (data_path (names[0]), pc1); read_cloud (data_path (names[1]), pc2);
         }
-        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim)
-                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim);
+        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu)
+                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu);
     }
     catch (const std::exception &e)
     {

@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-__all__ = ["ICP", "ICPStep", "ICPError", "Memory", "ICPStepConfigT", "ICPStepConfigW",
+__all__ = ["ICP", "ICPStep", "ICPError", "Memory", "ErrorMetric", "Normals", "ICPStepConfigT", "ICPStepConfigW",
            "PowerMode", "ReduceMode", "TransformKind", "ICPBatch", "batch_partition", "power_method", "KernelObject", "kernel_lms", "kernel_reps", "kernel_weights", "kernel_mean", "kernel_devs", "kernel_s", "ReduceScan", "lib", "lib_path", "reduce", "scan", "ReduceConfig", "synth_pair", "synth_cloud_vga", "punch_holes", "HOLES_SCATTERED", "HOLES_CONTIGUOUS", "synth_pair_scene", "SCENE_CURVED", "SCENE_WALL", "device_count", "DIST_ID"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -40,6 +40,21 @@ class ICPStepConfigW:            # include/ICP/algorithms.hpp:1560
 REJECT_INVALID = 1                # ICP_REJECT_INVALID (include/icp_amd.h): correspondence rejection of pairs with an invalid endpoint
 
 
+class ErrorMetric:                # icp_set_error_metric (include/icp_amd.h)
+    POINT_TO_POINT = 0
+    POINT_TO_PLANE = 1
+
+
+class Normals:                    # icp_set_normals: where the fixed frame's point-to-plane normals come from
+    GIVEN = 0                     # written by the user (Memory.NORMALS_F)
+    GRID = 1                      # computed by buildRBC from F read as a row-major grid
+
+
+def _write_floats(mem, m):
+    """Floats a write of `mem` takes: T 8, NORMALS_F m x 4, F / M m x 8."""
+    return 8 if mem == Memory.T else m * 4 if mem == Memory.NORMALS_F else m * 8
+
+
 def _max_dist_arg(max_dist):
     """max_dist of set_rejection -> the C argument (None: 0.0, no distance test); the library validates it."""
     return 0.0 if max_dist is None else float(max_dist)
@@ -62,7 +77,8 @@ class TransformKind:             # ICPTransformConfig (include/ICP/algorithms.hp
 
 
 class Memory:                    # icp_mem in include/icp_amd.h
-    F, M, T, TK, MEANS, S, NN_ID, W, SUM_W, REPS, RBC_N, RBC_O, RBC_PERM, RBC_OWNER, RBC_XP, RID, R, RK, NN, QT, TRIM = range(21)
+    F, M, T, TK, MEANS, S, NN_ID, W, SUM_W, REPS, RBC_N, RBC_O, RBC_PERM, RBC_OWNER, RBC_XP, RID, R, RK, NN, QT, TRIM, \
+        NORMALS_F, PLANE_SYSTEM = range(23)
     # reference spellings (ICPStep::Memory, include/ICP/algorithms.hpp:2241-2267)
     D_IN_F, D_IN_M, D_IO_T, H_IO_T = F, M, T, T
 
@@ -133,6 +149,10 @@ def lib():
     sig("icp_get_rejection", i32, vp, C.POINTER(i32), C.POINTER(f32))
     sig("icp_set_trimming", i32, vp, f32)
     sig("icp_get_trimming", i32, vp, C.POINTER(f32))
+    sig("icp_set_error_metric", i32, vp, i32, f32)
+    sig("icp_get_error_metric", i32, vp, C.POINTER(i32), C.POINTER(f32))
+    sig("icp_set_normals", i32, vp, i32, u32)
+    sig("icp_get_normals", i32, vp, C.POINTER(i32), C.POINTER(u32))
     sig("icp_get_max_iterations", i32, vp, C.POINTER(u32))
     sig("icp_set_max_iterations", i32, vp, u32)
     sig("icp_get_angle_threshold", i32, vp, C.POINTER(f64))
@@ -158,6 +178,8 @@ def lib():
     sig("icp_batch_set_modes", i32, vp, i32, i32)
     sig("icp_batch_set_rejection", i32, vp, i32, f32)
     sig("icp_batch_set_trimming", i32, vp, f32)
+    sig("icp_batch_set_error_metric", i32, vp, i32, f32)
+    sig("icp_batch_set_normals", i32, vp, i32, u32)
     sig("icp_batch_write", i32, vp, u32, i32, vp)
     sig("icp_batch_build_rbc", i32, vp)
     sig("icp_batch_run", i32, vp)
@@ -510,6 +532,7 @@ _MEM_DTYPE = {
     Memory.RBC_O: (np.uint32, None), Memory.RBC_PERM: (np.uint32, None), Memory.RBC_OWNER: (np.uint32, None),
     Memory.RID: (np.uint32, None), Memory.R: (np.float32, 3), Memory.RK: (np.float32, 3),
     Memory.NN: (np.float32, 4), Memory.QT: (np.float32, 4), Memory.TRIM: (np.uint32, None),
+    Memory.NORMALS_F: (np.float32, 4), Memory.PLANE_SYSTEM: (np.float64, None),
 }
 
 
@@ -564,7 +587,7 @@ class ICPStep:
         arr = None
         if ptr is not None:
             arr = np.ascontiguousarray(ptr, dtype=np.float32)
-            want = 8 if mem == Memory.T else self.m * 8
+            want = _write_floats(mem, self.m)
             if arr.size != want:
                 raise ValueError("write(%d): expected %d floats, got %d" % (mem, want, arr.size))
         self._chk(self._L.icp_write_b(self._h, batch_index, mem, _p(arr) if arr is not None else None, int(block)))
@@ -633,6 +656,29 @@ class ICPStep:
         v = C.c_float()
         self._chk(self._L.icp_get_trimming(self._h, C.byref(v)))
         return v.value
+
+    def set_error_metric(self, metric=ErrorMetric.POINT_TO_POINT, point_weight=0.0):
+        """Point-to-plane ICP (icp_set_error_metric; not reference behaviour, off by default): each iteration minimises the
+        point-to-plane error plus `point_weight` (mu >= 0) times the point-to-point error, linearised, solved by LDL^T on the device.
+        The normals of the fixed frame come from set_normals.  read(Memory.PLANE_SYSTEM) gives the last system and its status."""
+        self._chk(self._L.icp_set_error_metric(self._h, int(metric), float(point_weight)))
+
+    def error_metric(self):
+        """(metric, point_weight) as set."""
+        m, w = C.c_int32(), C.c_float()
+        self._chk(self._L.icp_get_error_metric(self._h, C.byref(m), C.byref(w)))
+        return m.value, w.value
+
+    def set_normals(self, source=Normals.GIVEN, grid_width=0):
+        """Where the fixed frame's normals come from: Normals.GIVEN (write(Memory.NORMALS_F, m x 4 floats)) or Normals.GRID (buildRBC
+        computes them from F read as a row-major grid `grid_width` wide; m must be a multiple of it)."""
+        self._chk(self._L.icp_set_normals(self._h, int(source), int(grid_width)))
+
+    def normals(self):
+        """(source, grid_width) as set."""
+        s, w = C.c_int32(), C.c_uint32()
+        self._chk(self._L.icp_get_normals(self._h, C.byref(s), C.byref(w)))
+        return s.value, w.value
 
     # -- extensions ------------------------------------------------------------------------
     def setPowerMode(self, mode):
@@ -972,9 +1018,17 @@ class ICPBatch:
         """The keep fraction as last set on this batch (1.0: off)."""
         return getattr(self, "_trimming", 1.0)
 
+    def set_error_metric(self, metric=ErrorMetric.POINT_TO_POINT, point_weight=0.0):
+        """ICPStep.set_error_metric on every registration (icp_batch_set_error_metric)."""
+        self._chk(self._L.icp_batch_set_error_metric(self._b, int(metric), float(point_weight)))
+
+    def set_normals(self, source=Normals.GIVEN, grid_width=0):
+        """ICPStep.set_normals on every registration (icp_batch_set_normals)."""
+        self._chk(self._L.icp_batch_set_normals(self._b, int(source), int(grid_width)))
+
     def write(self, i, mem, ptr):
         arr = np.ascontiguousarray(ptr, dtype=np.float32)
-        want = 8 if mem == Memory.T else self.m * 8
+        want = _write_floats(mem, self.m)
         if arr.size != want:
             raise ValueError("write(%d): expected %d floats, got %d" % (mem, want, arr.size))
         self._chk(self._L.icp_batch_write(self._b, i, mem, _p(arr)))
@@ -1011,7 +1065,8 @@ class ICPBatch:
     def read(self, i, mem):
         dt, cols = _MEM_DTYPE[mem]
         sizes = {Memory.T: 32, Memory.TK: 32, Memory.MEANS: 32, Memory.S: 44, Memory.NN_ID: self.m * 8, Memory.R: 36, Memory.RK: 36,
-                 Memory.F: self.m * 32, Memory.M: self.m * 32, Memory.W: self.m * 4, Memory.RID: self.m * 4, Memory.TRIM: 16}
+                 Memory.F: self.m * 32, Memory.M: self.m * 32, Memory.W: self.m * 4, Memory.RID: self.m * 4, Memory.TRIM: 16,
+                 Memory.NN: self.m * 16, Memory.QT: self.m * 16, Memory.NORMALS_F: self.m * 16, Memory.PLANE_SYSTEM: 28 * 8}
         nbytes = sizes[mem]
         out = np.empty(nbytes // np.dtype(dt).itemsize, dt)
         self._chk(self._L.icp_batch_read(self._b, i, mem, _p(out), nbytes))

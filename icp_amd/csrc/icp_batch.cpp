@@ -371,6 +371,32 @@ int icp_batch_set_trimming (icp_batch_handle b, float keep_fraction) try
 }
 ICP_CATCH_ALL
 
+int icp_batch_set_error_metric (icp_batch_handle b, int metric, float point_weight) try
+{
+    if (!b) return ICP_EINVAL;
+    if (metric != ICP_METRIC_POINT_TO_POINT && metric != ICP_METRIC_POINT_TO_PLANE) return bfail (b, ICP_EINVAL, "icp_batch_set_error_metric: unknown metric");
+    if (!(point_weight >= 0.f && std::isfinite (point_weight))) return bfail (b, ICP_EINVAL, "icp_batch_set_error_metric: point_weight must be finite and >= 0");
+    for (icp_handle h : b->slots) {
+        int rc = icp_set_error_metric (h, metric, point_weight);
+        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
+    }
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
+int icp_batch_set_normals (icp_batch_handle b, int source, uint32_t grid_width) try
+{
+    if (!b) return ICP_EINVAL;
+    if (source != ICP_NORMALS_GIVEN && source != ICP_NORMALS_GRID) return bfail (b, ICP_EINVAL, "icp_batch_set_normals: unknown source");
+    if (source == ICP_NORMALS_GRID && grid_width == 0u) return bfail (b, ICP_EINVAL, "icp_batch_set_normals: ICP_NORMALS_GRID needs a grid width");
+    for (icp_handle h : b->slots) {
+        int rc = icp_set_normals (h, source, grid_width);
+        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
+    }
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
 int icp_batch_build_rbc (icp_batch_handle b) try
 {
     if (!b || !b->inited) return b ? bfail (b, ICP_ESTATE, "icp_batch_init has not been called") : ICP_EINVAL;

@@ -910,7 +910,16 @@ void icp_launch_transform_cloud_ex (int kind, const float *in, float *out, const
     else hipLaunchKernelGGL (k_transform_cloud_ex<2>, grid, block, 0, s, i4, o4, t, n);
 }
 
+static void build_rbc_lists (const icp_params &p, hipStream_t s);
+
+// buildRBC; with ICP_NORMALS_GRID (icp_set_normals) the fixed set's normals behind it (icp_p2pl.hip)
 void icp_launch_build_rbc (const icp_params &p, hipStream_t s)
+{
+    build_rbc_lists (p, s);
+    if (p.nrm_grid) icp_launch_normals_grid (p, s);
+}
+
+static void build_rbc_lists (const icp_params &p, hipStream_t s)
 {
     if (icp_build_lists (p)) {                       // two launches: the owner search (gathers the representatives itself, leaves the lists), the placement
         icp_launch_owner_search (p, s);

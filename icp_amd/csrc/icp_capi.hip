@@ -206,12 +206,14 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     int rot = h->p.rot, weighted = h->p.weighted, pmode = h->p.power_mode, fused = h->p.fused, chain = h->p.chain;
     const float dist_scale = h->p.dist_scale;
     const uint32_t reject = h->p.reject; const float reject_d2 = h->p.reject_d2, reject_max_dist = h->p.reject_max_dist, trim_keep = h->p.trim_keep;
+    const uint32_t metric = h->p.metric, nrm_grid = h->p.nrm_grid; const float p2pl_mu = h->p.p2pl_mu;
     free_all (h);
     icp_params &p = h->p;
     p = icp_params {};
     p.rot = rot; p.weighted = weighted; p.power_mode = pmode; p.check = 0; p.fused = fused; p.chain = chain; p.emit = 1;
     p.dist_scale = dist_scale;
     p.reject = reject; p.reject_d2 = reject_d2; p.reject_max_dist = reject_max_dist; p.trim_keep = trim_keep;
+    p.metric = metric; p.nrm_grid = nrm_grid; p.p2pl_mu = p2pl_mu;
     p.m = m; p.nr = nr; p.batch = batch; p.side = side; p.nrx = nrx; p.nry = nry;
     p.a = a; p.c = c;
     {   // division-free cell lookups in the kernels (reps_grid guarantees a square grid that the representative grid tiles)
@@ -245,7 +247,7 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     p.gtile = 0u;                                                    // 4 x 4 tile groups where the representative grid allows
     if (nrx % 4u == 0u && nry % 4u == 0u && !std::getenv ("ICP_AMD_STRIP_GROUPS")) { uint32_t lg = 0; while ((4u << lg) < nrx) ++lg; p.gtile = lg + 1u; }
     if ((rc = dalloc (h, &p.GB, B * 2 * (p.n16 + p.n1k)))) return rc;
-    if ((rc = dalloc (h, &p.XP, B * m * 8))) return rc;
+    if ((rc = dalloc (h, &p.XP, B * m * 12))) return rc;            // (behind the database: NORMALS_F, icp_normals_f; zeroed)
     if ((rc = dalloc (h, &p.XQ, B * m * 8))) return rc;
     if ((rc = dalloc (h, &p.OL, B * ICP_OL_STRIDE (nr)))) return rc;
     p.nlb = m / 16u + 2u;
@@ -269,7 +271,9 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     if ((rc = dalloc (h, &p.spart, B * 11 * p.nsp * 8))) return rc;    // 8 sub-trees per work-group; padding stays 0.f
     // (behind the moments: trimming's result, selection state, histograms and keys — icp_trim_area; zeroed: ICP_MEM_TRIM reads 0 until a
     // trimmed iteration has run, and the histograms and counters start clear)
-    if ((rc = dalloc (h, &p.mom, B * 2 * 18 * p.nb + (icp_trim_words (batch, m) + 1u) / 2u))) return rc;
+    // (behind those: the point-to-plane system and block partials — icp_p2pl_area; zeroed: ICP_MEM_PLANE_SYSTEM reads 0 until a
+    // point-to-plane iteration has run)
+    if ((rc = dalloc (h, &p.mom, B * 2 * 18 * p.nb + (icp_trim_words (batch, m) + 1u) / 2u + icp_p2pl_doubles (batch, m)))) return rc;
     if ((rc = dalloc (h, &p.ml1, B * 18 * ((p.nb + 127u) / 128u)))) return rc;
     if ((rc = dalloc (h, &p.cst, B * 2))) return rc;
     if ((rc = dalloc (h, &p.st, B))) return rc;
@@ -330,8 +334,17 @@ int icp_write_b (icp_handle h, uint32_t b, int mem, const void *host_ptr, int bl
             HIPCHK (h, hipGetLastError ());
             break;
         }
+        case ICP_MEM_NORMALS_F: {
+            // (point-to-plane normals, ICP_NORMALS_GIVEN: small and rare — a blocking copy from the caller's memory; the stream is
+            // ordered in front of it, so the iterations queued before this read the normals they were queued with)
+            if (!host_ptr) return fail (h, ICP_EINVAL, "icp_write: ICP_MEM_NORMALS_F needs a source");
+            note_inputs_change (h);
+            HIPCHK (h, hipStreamSynchronize (h->stream));
+            HIPCHK (h, hipMemcpy (icp_normals_f (h->p) + (size_t) b * h->p.m, host_ptr, (size_t) h->p.m * 16, hipMemcpyHostToDevice));
+            break;
+        }
         default:
-            return fail (h, ICP_EINVAL, "icp_write: mem must be ICP_MEM_F, ICP_MEM_M or ICP_MEM_T");
+            return fail (h, ICP_EINVAL, "icp_write: mem must be ICP_MEM_F, ICP_MEM_M, ICP_MEM_T or ICP_MEM_NORMALS_F");
     }
     if (block) HIPCHK (h, hipStreamSynchronize (h->stream));
     return ICP_OK;
@@ -356,6 +369,8 @@ size_t icp_mem_size (icp_handle h, int mem)
         case ICP_MEM_R: case ICP_MEM_RK: return 36;
         case ICP_MEM_NN: case ICP_MEM_QT: return (size_t) p.m * 16;
         case ICP_MEM_TRIM: return 16;
+        case ICP_MEM_NORMALS_F: return (size_t) p.m * 16;
+        case ICP_MEM_PLANE_SYSTEM: return ICP_P2PL_SYS * sizeof (double);
         default: return 0;
     }
 }
@@ -386,6 +401,8 @@ static int mem_ptr (icp_context *h, uint32_t b, int mem, const void **src)
         case ICP_MEM_QT: *src = p.PM + (size_t) b * p.m; break;
         case ICP_MEM_W: *src = reinterpret_cast<const float *> (p.PF + (size_t) b * p.m) + 3; break;
         case ICP_MEM_TRIM: *src = icp_trim_area (p) + 4u * b; break;
+        case ICP_MEM_NORMALS_F: *src = icp_normals_f (p) + (size_t) b * p.m; break;
+        case ICP_MEM_PLANE_SYSTEM: *src = icp_p2pl_area (p) + (size_t) ICP_P2PL_SYS * b; break;
         default: return fail (h, ICP_EINVAL, "unknown icp_mem value");
     }
     return ICP_OK;
@@ -449,6 +466,8 @@ int icp_build_rbc (icp_handle h) try
     api_guard guard_ (h);
     int rc = need (h, false); if (rc) return rc;
     if ((rc = set_device (h))) return rc;
+    if (h->p.nrm_grid && h->p.m % h->p.nrm_grid)
+        return fail (h, ICP_ESTATE, "icp_build_rbc: ICP_NORMALS_GRID: m is not a multiple of the grid width");
     note_inputs_change (h);
     // The two (latency-bound sizes) to six launches of the construction are enqueued as they are: a graph of so few nodes costs more
     // at its head and tail than it saves between them — same box, back to back, graph against plain launches: A 22.3 -> 13.6 us,
@@ -694,6 +713,64 @@ int icp_get_trimming (icp_handle h, float *keep_fraction) try
     api_guard guard_ (h);
     if (!h || !keep_fraction) return ICP_EINVAL;
     *keep_fraction = icp_trimming (h->p) ? h->p.trim_keep : 1.f;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+// point-to-plane (include/icp_amd.h, icp_p2pl.hip).  On <-> off changes which kernels run — the moments and the 6 x 6 finalize, no
+// chained form —: the route of icp_set_reduce_mode (graphs captured anew).  A new mu while the metric stays on is a parameter update.
+int icp_set_error_metric (icp_handle h, int metric, float point_weight) try
+{
+    api_guard guard_ (h);
+    if (metric != ICP_METRIC_POINT_TO_POINT && metric != ICP_METRIC_POINT_TO_PLANE) return fail (h, ICP_EINVAL, "icp_set_error_metric: unknown metric");
+    if (!(point_weight >= 0.f && std::isfinite (point_weight))) return fail (h, ICP_EINVAL, "icp_set_error_metric: point_weight must be finite and >= 0");
+    if (!h) return fail (h, ICP_EINVAL, "icp_set_error_metric: null handle");
+    { int rc = outputs_before_change (h); if (rc) return rc; }
+    const bool on = metric == ICP_METRIC_POINT_TO_PLANE;
+    if (on == icp_p2pl (h->p)) {
+        if (on) { h->p.p2pl_mu = point_weight; ++h->param_gen; }
+        return ICP_OK;
+    }
+    if (on) { h->p.metric = (uint32_t) metric; h->p.p2pl_mu = point_weight; }
+    else {
+        h->p.metric = 0u; h->p.p2pl_mu = 0.f;
+        if (h->inited) {                                                 // ICP_MEM_PLANE_SYSTEM reads zeros while the metric is off
+            int rc = set_device (h); if (rc) return rc;
+            if ((rc = run_close_all (h))) return rc;
+            HIPCHK (h, hipMemsetAsync (icp_p2pl_area (h->p), 0, sizeof (double) * ICP_P2PL_SYS * h->p.batch, h->stream));
+        }
+    }
+    drop_graphs (h);
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+int icp_get_error_metric (icp_handle h, int *metric, float *point_weight) try
+{
+    api_guard guard_ (h);
+    if (!h) return ICP_EINVAL;
+    if (metric) *metric = (int) h->p.metric;
+    if (point_weight) *point_weight = h->p.p2pl_mu;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+// The source of the normals changes what buildRBC launches (k_normals_grid behind it): the build graph goes with the others.
+int icp_set_normals (icp_handle h, int source, uint32_t grid_width) try
+{
+    api_guard guard_ (h);
+    if (source != ICP_NORMALS_GIVEN && source != ICP_NORMALS_GRID) return fail (h, ICP_EINVAL, "icp_set_normals: unknown source");
+    if (source == ICP_NORMALS_GRID && grid_width == 0u) return fail (h, ICP_EINVAL, "icp_set_normals: ICP_NORMALS_GRID needs a grid width");
+    if (!h) return fail (h, ICP_EINVAL, "icp_set_normals: null handle");
+    const uint32_t w = source == ICP_NORMALS_GRID ? grid_width : 0u;
+    if (w && h->inited && h->p.m % w) return fail (h, ICP_ESTATE, "icp_set_normals: m is not a multiple of the grid width");
+    if (w != h->p.nrm_grid) { h->p.nrm_grid = w; drop_graphs (h); }
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+int icp_get_normals (icp_handle h, int *source, uint32_t *grid_width) try
+{
+    api_guard guard_ (h);
+    if (!h) return ICP_EINVAL;
+    if (source) *source = h->p.nrm_grid ? ICP_NORMALS_GRID : ICP_NORMALS_GIVEN;
+    if (grid_width) *grid_width = h->p.nrm_grid;
     return ICP_OK;
 }
 ICP_CATCH_ALL
@@ -959,6 +1036,7 @@ int icp_launches_per_iteration (icp_handle h, uint32_t *n) try
     // (fused, large sets: the first level of the moment tree is a launch of its own — icp_launch_finalize)
     *n = form != ICP_FORM_SEPARATE ? 1u : h->p.fused ? ((h->p.nb + 127u) / 128u > ICP_L1_MIN_GROUPS ? 3u : 2u) : 4u;
     if (icp_trimming (h->p)) *n += icp_trim_launches (h->p);          // (select: one or three launches, apply: one)
+    if (icp_p2pl (h->p)) *n = 1u + (icp_trimming (h->p) ? icp_trim_launches (h->p) : 0u) + ICP_P2PL_LAUNCHES;   // (search, moments, finalize)
     return ICP_OK;
 }
 ICP_CATCH_ALL

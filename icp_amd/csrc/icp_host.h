@@ -251,8 +251,8 @@ int run_begin (icp_context *h, run_ctl &r, hipStream_t stream, const icp_params 
     r.stream = stream;
     r.t[0] = now_s ();
     r.p = p; r.p.check = 1;
-    // (reference-order kernels read the outputs themselves, and so does the selection of trimming: always stored)
-    r.p.emit = (h->outputs_lazy && p.fused && !icp_trimming (p)) ? 0 : 1;
+    // (reference-order kernels read the outputs themselves, and so do the selection of trimming and the point-to-plane moments: always stored)
+    r.p.emit = (h->outputs_lazy && p.fused && !icp_trimming (p) && !icp_p2pl (p)) ? 0 : 1;
     h->outputs_stale = r.p.emit == 0; h->outputs_lost = false;
     if (++h->epoch == 0u) h->epoch = 1u;
     r.p.epoch = h->epoch; r.p.hmirror = mirror; r.p.hstate = hstate;    // (fine-grained host allocations: the host pointer is the device pointer)

@@ -59,6 +59,8 @@ struct icp_params {
     uint32_t warm_seed;          // diagnostics (ICP_AMD_WARM_SEED=1): a registration's first search is seeded with p.rid as it stands (the previous
                                  // registration's answer) instead of the query's own grid cell
     uint32_t s2wave;             // stage 2 of the dense search with lanes = candidates (lists of >= ICP_S2_WAVE_MIN candidates on average: see k_search)
+    uint32_t nrm_grid;           // point-to-plane normals (icp_set_normals): the grid width of ICP_NORMALS_GRID (buildRBC computes them), 0: ICP_NORMALS_GIVEN
+                                 // (this and the next two p2pl fields fill alignment holes: no other field moves — see the static_assert below)
     float *XP;                   // [batch][m][8]  permuted database (RBCConstruct D_OUT_X_P)
     float *XQ;                   // [batch][m][8]  same, lane 3 = original index bits (search copy)
     float4 *OL;                  // [batch][ICP_OL_STRIDE (nr)]  the representatives at the origin (invalid points), ascending: [0].x = their number (bits),
@@ -69,6 +71,7 @@ struct icp_params {
     float4 *LB;                  // [batch][3 * nlb]  6-D bounding boxes of the list chunks (16 consecutive positions of one list, chunk c >= 1 of list r at
                                  // index (O[r] >> 4) + c: k_list_boxes) as [lo.x lo.y lo.z lo.r | lo.g lo.b hi.x hi.y | hi.z hi.r hi.g hi.b]
     uint32_t nlb;                // m / 16 + 2 boxes per registration
+    uint32_t metric;             // ICP_METRIC_POINT_TO_POINT (0, the default) or ICP_METRIC_POINT_TO_PLANE (icp_set_error_metric; icp_p2pl.hip)
     uint32_t *rep_src, *owner, *N, *O, *perm, *chunk_hist;   // [batch][...]; N: [2][batch][nr] — [0] the length of a list AS THE SEARCH SCANS IT (k_search reads
                                  // p.N: a long list without the tail members that repeat an earlier member bit for bit, k_list_boxes), [1] = ICP_N_FULL: the list's
                                  // length N of the construction (RBCConstruct's output, ICP_MEM_RBC_N); the two differ for long lists with duplicates only
@@ -86,6 +89,7 @@ struct icp_params {
     double *ml1;                 // [batch][18][ceil(nb/128)]  fused mode, large sets: first tree level of the moments (k_moment_level1)
     icp_reg_state *cst;          // [batch][2]  chained fused mode: state slots, launch j reads slot j&1 and writes the other
     uint32_t slot;               // chained fused mode: slot this launch reads
+    float p2pl_mu;               // point-to-plane: the share mu of the point-to-point term
     icp_reg_state *st;           // [batch]
     icp_reg_state *st_prev;      // [batch]  .T = the transform the last executed search used (stored by every finalize; everything else stays zero):
                                  // icp_launch_search on it reproduces that iteration's per-query outputs (checked runs do not store them on the way)
@@ -131,6 +135,22 @@ static inline size_t icp_trim_words (uint32_t batch, uint32_t m)
     return (size_t) batch * (8u + ICP_TRIM_BINS) + (m > ICP_TRIM_ONE_BLOCK_MAX ? (size_t) batch * m : 0u);
 }
 static inline uint32_t *icp_trim_area (const icp_params &p) { return reinterpret_cast<uint32_t *> (p.mom + (size_t) p.batch * 2 * 18 * p.nb); }
+
+// Point-to-plane ICP (icp_set_error_metric, icp_p2pl.hip).  NORMALS_F lies behind the permuted database XP, in the same allocation: it
+// belongs to the fixed frame as the RBC does, and a tracked handle's second RBC set (icp_track.hip) carries a second one with it.  The
+// solve's buffers lie behind trimming's, in the moments' allocation: [batch][28] ICP_MEM_PLANE_SYSTEM (A's upper triangle, b, status),
+// then [batch][27][icp_p2pl_nblk] the block partials of k_p2pl_moments.
+#define ICP_P2PL_BLOCK 256u      // pairs per block of the first tree level
+#define ICP_P2PL_TERMS 27u       // 21 upper-triangle terms of A, then the 6 of b
+#define ICP_P2PL_SYS 28u         // doubles of ICP_MEM_PLANE_SYSTEM per registration
+static __host__ __device__ __forceinline__ bool icp_p2pl (const icp_params &p) { return p.metric != 0u; }
+static __host__ __device__ __forceinline__ uint32_t icp_p2pl_nblk (uint32_t m) { return (m + ICP_P2PL_BLOCK - 1u) / ICP_P2PL_BLOCK; }
+static inline size_t icp_p2pl_doubles (uint32_t batch, uint32_t m) { return (size_t) batch * (ICP_P2PL_SYS + ICP_P2PL_TERMS * icp_p2pl_nblk (m)); }
+static __host__ __device__ __forceinline__ float4 *icp_normals_f (const icp_params &p) { return reinterpret_cast<float4 *> (p.XP + (size_t) p.batch * p.m * 8); }
+static inline double *icp_p2pl_area (const icp_params &p)
+{
+    return p.mom + (size_t) p.batch * 2 * 18 * p.nb + (icp_trim_words (p.batch, p.m) + 1u) / 2u;
+}
 
 #define ICP_N_FULL(p, b) ((p).N + ((size_t) (p).batch + (b)) * (p).nr)
 
@@ -213,6 +233,9 @@ void icp_launch_search_rej (const icp_params &p, hipStream_t s);            // i
 void icp_launch_chain_one_rej (const icp_params &p, hipStream_t s, uint32_t j, bool fresh, bool emit);
 void icp_launch_trim (const icp_params &p, hipStream_t s);                   // icp_trim.hip: k_trim_select (one or three launches) + k_trim_apply
 uint32_t icp_trim_launches (const icp_params &p);                             // how many that is
+void icp_launch_p2pl_solve (const icp_params &p, hipStream_t s);             // icp_p2pl.hip: k_p2pl_moments + k_p2pl_finalize (point-to-plane)
+void icp_launch_normals_grid (const icp_params &p, hipStream_t s);           // icp_p2pl.hip: k_normals_grid (ICP_NORMALS_GRID, behind buildRBC)
+#define ICP_P2PL_LAUNCHES 2u                                                  // launches of icp_launch_p2pl_solve
 void icp_launch_owner_search_dense (const icp_params &p, hipStream_t s);
 uint32_t icp_tbox_of (const icp_params &p);
 uint32_t icp_s2_wave_of (const icp_params &p);

@@ -540,6 +540,7 @@ void icp_launch_search (const icp_params &p, hipStream_t s)
 
 void icp_launch_means (const icp_params &p, hipStream_t s)
 {
+    if (icp_p2pl (p)) return;                                        // (point-to-plane: no means, no S — icp_p2pl.hip)
     // (correspondence rejection: the weighted formulas, w in {0, 1} in REGULAR mode)
     const uint32_t weighted = (p.weighted || icp_rejecting (p)) ? 1u : 0u;
     if (weighted && p.nwp > 512) hipLaunchKernelGGL (k_sum_w, dim3 (1, p.batch), dim3 (64), 0, s, p);
@@ -549,6 +550,7 @@ void icp_launch_means (const icp_params &p, hipStream_t s)
 
 void icp_launch_sij (const icp_params &p, hipStream_t s)
 {
+    if (icp_p2pl (p)) return;
     if (p.nwg > 128) hipLaunchKernelGGL (k_gmean, dim3 (1, p.batch), dim3 (1024), 0, s, p);
     hipLaunchKernelGGL (k_sij, dim3 (((p.G + 511) / 512) * 8, p.batch), dim3 (64), 0, s, (const float4 *) p.PF, (const float4 *) p.PM, (const float4 *) p.mpart, p.st,
                         p.m, p.G, p.nwg, (uint32_t) p.check, p);
@@ -556,6 +558,8 @@ void icp_launch_sij (const icp_params &p, hipStream_t s)
 
 void icp_launch_finalize (const icp_params &p, hipStream_t s)
 {
+    // point-to-plane (icp_p2pl.hip): the 6 x 6 system and its solve in place of the moments and the rotation solver
+    if (icp_p2pl (p)) { icp_launch_p2pl_solve (p, s); return; }
     // the rotation solver is a template parameter (p.rot: 1 power method, else SVD)
     if (p.fused) {
         const uint32_t ng = (p.nb + 127u) / 128u;
@@ -574,14 +578,17 @@ void icp_launch_finalize (const icp_params &p, hipStream_t s)
 __global__ void k_nop (icp_params p) { if (p.m == 0xFFFFFFFFu) p.st->k = 0; }
 
 // The search of an iteration.  Trimming on (icp_trim.hip): the REJ search stores its per-query outputs every time — the selection reads
-// them —, then k_trim_select and k_trim_apply.
+// them —, then k_trim_select and k_trim_apply.  Point-to-plane on (icp_p2pl.hip): the outputs are stored every time too — the moments
+// read them —, and the search takes its reference-order form whatever the reduce mode: the same per-query outputs, and its prologue
+// publishes every iteration's (k, done) to a host-driven run (the fused form leaves a converged registration's word to the fused finalize).
 void icp_launch_search_stage (const icp_params &p, hipStream_t s)
 {
-    if (!icp_trimming (p)) { icp_launch_search (p, s); return; }
+    if (!icp_trimming (p) && !icp_p2pl (p)) { icp_launch_search (p, s); return; }
     icp_params q = p;
     q.emit = 1;
+    if (icp_p2pl (p)) q.fused = 0;
     icp_launch_search (q, s);
-    icp_launch_trim (q, s);
+    if (icp_trimming (p)) icp_launch_trim (q, s);
 }
 
 // diagnostic: any subset of the iteration's kernels (bit 0 search — with trimming on, select and apply too —, 1 means, 2 sij, 3 finalize, 4 empty kernel)
@@ -602,7 +609,8 @@ void icp_launch_masked (const icp_params &p, hipStream_t s, unsigned mask)
 bool icp_chain_supported (const icp_params &p)
 {
     // (trimming: the selection sits between the search and the finalize, which the chained form folds into one launch)
-    return p.fused && !icp_trimming (p) && p.nb <= 4096u && p.nr <= 1024u && (p.chain == 2 || (p.chain == 1 && !icp_dense (p)));
+    // (point-to-plane: its own finalize, no chained form)
+    return p.fused && !icp_trimming (p) && !icp_p2pl (p) && p.nb <= 4096u && p.nr <= 1024u && (p.chain == 2 || (p.chain == 1 && !icp_dense (p)));
 }
 
 // launch j of a chain (icp_search.h: ks_launch_chain_one)

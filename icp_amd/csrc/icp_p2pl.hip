@@ -1,0 +1,287 @@
+// icp_p2pl.hip — point-to-plane ICP (icp_set_error_metric, icp_set_normals: include/icp_amd.h states the rule).
+//
+// An iteration with the metric on is: the search stage (icp_launch_search_stage), which stores PF (matched fixed xyz, weight) and PM
+// (transformed moving xyz) every time — rejection and trimming have put their zeros into PF.w already —; k_p2pl_moments, the 27 terms
+// of the linearised 6 x 6 system per pair in double and their tree over blocks of ICP_P2PL_BLOCK pairs; k_p2pl_finalize, one workgroup
+// per registration: the tree over the block partials, LDL^T in one lane, the increment composed with icp_compose's arithmetic and checked with
+// icp_check_converged.  k_normals_grid computes NORMALS_F from F behind buildRBC (ICP_NORMALS_GRID).  None of the existing kernels
+// carries any of this code; the translation unit is built with -ffp-contract=off like every other, so each expression below is evaluated
+// exactly in the order it is written.
+#include "icp_kernels.h"
+
+namespace {
+
+// a grid point takes part in a difference when its xyz is finite and not the origin (a Kinect pixel without depth)
+__device__ __forceinline__ bool nrm_valid (float3 v)
+{
+    return isfinite (v.x) && isfinite (v.y) && isfinite (v.z) && !(v.x == 0.f && v.y == 0.f && v.z == 0.f);
+}
+
+__device__ __forceinline__ float3 nrm_sub (float3 a, float3 b) { return make_float3 (a.x - b.x, a.y - b.y, a.z - b.z); }
+
+// the difference along one grid axis: central if both neighbours are valid, else one-sided against the centre (the next neighbour first)
+__device__ __forceinline__ bool nrm_diff (float3 prev, bool has_prev, float3 c, float3 next, bool has_next, float3 &d)
+{
+    const bool vp = has_prev && nrm_valid (prev), vn = has_next && nrm_valid (next);
+    if (vp && vn) d = nrm_sub (next, prev);
+    else if (vn) d = nrm_sub (next, c);
+    else if (vp) d = nrm_sub (c, prev);
+    return vp || vn;
+}
+
+}  // namespace
+
+// NORMALS_F of the fixed set, read as a row-major grid p.nrm_grid wide (m % width == 0: icp_build_rbc checks it).  One thread per point,
+// grid.y = registration.  fp32, no contraction:
+//   c = dh x dv,  n = c / sqrtf ((c.x^2 + c.y^2) + c.z^2),  n = -n if (n.x C.x + n.y C.y) + n.z C.z > 0 (faces the sensor at the origin),
+//   n = 0 when the centre is invalid, a difference is missing, or the length is not > 0 and finite.
+__global__ __launch_bounds__ (256) void k_normals_grid (icp_params p, float4 *nrm)
+{
+    const uint32_t b = blockIdx.y, i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= p.m) return;
+    const uint32_t W = p.nrm_grid, x = i % W, y = i / W, H = p.m / W;
+    const float *F = p.F + (size_t) b * p.m * 8;
+    auto at = [&] (uint32_t j) { const float *r = F + (size_t) j * 8; return make_float3 (r[0], r[1], r[2]); };
+    const float3 c = at (i);
+    float4 n = make_float4 (0.f, 0.f, 0.f, 0.f);
+    float3 dh = make_float3 (0.f, 0.f, 0.f), dv = dh;
+    const float3 zero = dh;
+    // (i + 1 < m, y + 1 < H: no read beyond the set even if the width did not divide m — the host refuses that, ICP_ESTATE)
+    const bool hasl = x > 0u, hasr = x + 1u < W && i + 1u < p.m, hasu = y > 0u, hasd = y + 1u < H;
+    if (nrm_valid (c) &&
+        nrm_diff (hasl ? at (i - 1u) : zero, hasl, c, hasr ? at (i + 1u) : zero, hasr, dh) &&
+        nrm_diff (hasu ? at (i - W) : zero, hasu, c, hasd ? at (i + W) : zero, hasd, dv)) {
+        const float cx = dh.y * dv.z - dh.z * dv.y, cy = dh.z * dv.x - dh.x * dv.z, cz = dh.x * dv.y - dh.y * dv.x;
+        const float len = sqrtf ((cx * cx + cy * cy) + cz * cz);
+        if (len > 0.f && len < __builtin_inff ()) {
+            float nx = cx / len, ny = cy / len, nz = cz / len;
+            if ((nx * c.x + ny * c.y) + nz * c.z > 0.f) { nx = -nx; ny = -ny; nz = -nz; }
+            n = make_float4 (nx, ny, nz, 0.f);
+        }
+    }
+    nrm[(size_t) b * p.m + i] = n;
+}
+
+// The 27 terms of pair i in double (include/icp_amd.h; tests/p2pl_ref.py restates them), w = PF.w, P = PM.xyz, Q = PF.xyz, N =
+// NORMALS_F[NN_ID.id] (a non-finite normal counts as zero), all converted from float first:
+//   c = P x N: (py nz - pz ny, pz nx - px nz, px ny - py nx)       J = (c, N)
+//   d = Q - P (componentwise)     r = (dx nx + dy ny) + dz nz      pp = (px px + py py) + pz pz
+//   G = [[pp I - P P^T, [P]x], [-[P]x, I]]: G00 = pp - px px, G01 = -(px py), G02 = -(px pz), G11 = pp - py py, G12 = -(py pz),
+//       G22 = pp - pz pz; G03 = 0, G04 = -pz, G05 = py, G13 = pz, G14 = 0, G15 = -px, G23 = -py, G24 = px, G25 = 0;
+//       G33 = G44 = G55 = 1, G34 = G35 = G45 = 0
+//   g = (P x Q, d): P x Q = (py qz - pz qy, pz qx - px qz, px qy - py qx)
+//   term (a, b), a <= b, row-major:  w (J_a J_b + mu G_ab)         term 21 + a:  w (J_a r + mu g_a)
+// w == 0 (no query, rejected, trimmed) selects exact zeros.  Then the halving tree over the block's ICP_P2PL_BLOCK pairs,
+// x[i] += x[i + h] for h = 128 .. 1 (lanes: h = 32 .. 1 pair lane i with lane i + h, the same additions).
+__global__ __launch_bounds__ (256) void k_p2pl_moments (icp_params p, const float4 *nrm, double *part, uint32_t nblk)
+{
+    const uint32_t b = blockIdx.y, tid = threadIdx.x, i = blockIdx.x * ICP_P2PL_BLOCK + tid;
+    const size_t o = (size_t) b * p.m;
+    const uint32_t ic = min (i, p.m - 1u);
+    const float4 f = p.PF[o + ic], q = p.PM[o + ic];
+    const uint32_t id = p.nn_id[o + ic].id;
+    // (a converged registration: asked behind the pair's loads — in front of them the flag's round trip would come first)
+    if (p.check && p.st[b].done) return;                 // (block-uniform)
+    double v[ICP_P2PL_TERMS];
+#pragma unroll
+    for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) v[t] = 0.0;
+    if (i < p.m) {
+        if (f.w != 0.f) {
+            float4 nf = id < p.m ? nrm[o + id] : make_float4 (0.f, 0.f, 0.f, 0.f);
+            if (!(isfinite (nf.x) && isfinite (nf.y) && isfinite (nf.z))) nf = make_float4 (0.f, 0.f, 0.f, 0.f);
+            const double w = (double) f.w, mu = (double) p.p2pl_mu;
+            const double px = (double) q.x, py = (double) q.y, pz = (double) q.z;
+            const double qx = (double) f.x, qy = (double) f.y, qz = (double) f.z;
+            const double nx = (double) nf.x, ny = (double) nf.y, nz = (double) nf.z;
+            const double J[6] = { py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz };
+            const double dx = qx - px, dy = qy - py, dz = qz - pz;
+            const double r = (dx * nx + dy * ny) + dz * nz;
+            const double pp = (px * px + py * py) + pz * pz;
+            const double G[21] = { pp - px * px, -(px * py), -(px * pz), 0.0, -pz, py,
+                                   pp - py * py, -(py * pz), pz, 0.0, -px,
+                                   pp - pz * pz, -py, px, 0.0,
+                                   1.0, 0.0, 0.0,
+                                   1.0, 0.0,
+                                   1.0 };
+            const double g[6] = { py * qz - pz * qy, pz * qx - px * qz, px * qy - py * qx, dx, dy, dz };
+            int t = 0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int c = a; c < 6; ++c, ++t) v[t] = w * (J[a] * J[c] + mu * G[t]);
+#pragma unroll
+            for (int a = 0; a < 6; ++a) v[21 + a] = w * (J[a] * r + mu * g[a]);
+        }
+    }
+    __shared__ double s[ICP_P2PL_TERMS][128];
+    if (tid >= 128u) {
+#pragma unroll
+        for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) s[t][tid - 128u] = v[t];
+    }
+    __syncthreads ();
+    if (tid < 128u) {
+#pragma unroll
+        for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) v[t] = v[t] + s[t][tid];
+    }
+    __syncthreads ();
+    if (tid >= 64u && tid < 128u) {
+#pragma unroll
+        for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) s[t][tid - 64u] = v[t];
+    }
+    __syncthreads ();
+    if (tid >= 64u) return;
+#pragma unroll
+    for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) {
+        double x = v[t] + s[t][tid];
+#pragma unroll
+        for (int h = 32; h >= 1; h >>= 1) x = x + __shfl_down (x, (unsigned) h, 64);
+        v[t] = x;
+    }
+    if (tid == 0u) {
+#pragma unroll
+        for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) part[((size_t) b * ICP_P2PL_TERMS + t) * nblk + blockIdx.x] = v[t];
+    }
+}
+
+#define P2PL_LDS 4096u           // doubles of the finalize's tree buffer (nblk <= 4096: m <= 2^20)
+
+// One workgroup per registration: the halving tree over the block partials zero-padded to P = 2^ceil(log2 nblk), as many terms at a time
+// as the LDS buffer holds; then lane 0: LDL^T, the increment, the composition and the check.
+__global__ __launch_bounds__ (256) void k_p2pl_finalize (icp_params p, const double *part, double *sys, uint32_t nblk, uint32_t P)
+{
+    const uint32_t b = blockIdx.x, tid = threadIdx.x;
+    icp_reg_state *st = p.st + b;
+    __shared__ double s[P2PL_LDS];
+    __shared__ double s_sum[ICP_P2PL_TERMS];
+    const uint32_t lgP = 31u - (uint32_t) __builtin_clz (P), tc = min (ICP_P2PL_TERMS, P2PL_LDS / P);
+    const double *pb = part + (size_t) b * ICP_P2PL_TERMS * nblk;
+    // the transform before the step, in lane 0's registers from the start (the composition then waits for no load)
+    float Tprev[8], Rprev[9];
+    if (tid == 0u) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) Tprev[k] = st->T[k];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Rprev[k] = st->R[k];
+    }
+    for (uint32_t t0 = 0; t0 < ICP_P2PL_TERMS; t0 += tc) {
+        const uint32_t nt = min (tc, ICP_P2PL_TERMS - t0), n = nt << lgP;
+        // (every load of the pass in flight at once: at most P2PL_LDS / 256 per lane)
+        double x[P2PL_LDS / 256u];
+#pragma unroll
+        for (uint32_t u = 0; u < P2PL_LDS / 256u; ++u) {
+            const uint32_t j = tid + 256u * u, t = j >> lgP, i = j & (P - 1u);
+            x[u] = (j < n && i < nblk) ? pb[(size_t) (t0 + t) * nblk + i] : 0.0;
+        }
+        // (a converged registration: asked behind the first loads)
+        if (t0 == 0u && p.check && st->done) return;     // (block-uniform)
+#pragma unroll
+        for (uint32_t u = 0; u < P2PL_LDS / 256u; ++u) {
+            const uint32_t j = tid + 256u * u;
+            if (j < n) s[j] = x[u];
+        }
+        __syncthreads ();
+        for (uint32_t lh = lgP; lh-- > 0u;) {
+            const uint32_t h = 1u << lh;
+            for (uint32_t j = tid; j < (nt << lh); j += 256u) {
+                const uint32_t t = j >> lh, i = j & (h - 1u);
+                s[(t << lgP) + i] = s[(t << lgP) + i] + s[(t << lgP) + i + h];
+            }
+            __syncthreads ();
+        }
+        if (tid < nt) s_sum[t0 + tid] = s[tid << lgP];
+        __syncthreads ();
+    }
+    if (tid != 0u) return;
+
+    // A (symmetric, from the upper triangle) and b
+    double A[6][6], bb[6];
+    {
+        int t = 0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int c = a; c < 6; ++c, ++t) { A[a][c] = s_sum[t]; A[c][a] = s_sum[t]; }
+#pragma unroll
+        for (int a = 0; a < 6; ++a) bb[a] = s_sum[21 + a];
+    }
+    // LDL^T, column by column:  e_jk = L_jk d_k;  d_j = A_jj - e_j0 L_j0 - .. - e_j(j-1) L_j(j-1)  (subtracted in order k = 0, 1, ..);
+    // L_ij = (A_ij - L_i0 e_j0 - .. - L_i(j-1) e_j(j-1)) / d_j for i > j.  A pivot that is not finite or d_j <= 1e-12 A_jj: singular.
+    double L[6][6], E[6][6], d[6];
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double v = A[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) v = v - E[j][k] * L[j][k];
+        d[j] = v;
+        if (!isfinite (v) || v <= 1e-12 * A[j][j]) ok = false;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double u = A[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) u = u - L[i][k] * E[j][k];
+            L[i][j] = u / v;
+            E[i][j] = L[i][j] * v;
+        }
+    }
+    // L y = b (y_i = b_i - L_i0 y_0 - .. in order), z = y / d, L^T x = z (x_i = z_i - L_(i+1)i x_(i+1) - .. - L_5i x_5, ascending k)
+    double y[6], x[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double u = bb[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) u = u - L[i][k] * y[k];
+        y[i] = u;
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double u = y[i] / d[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) u = u - L[k][i] * x[k];
+        x[i] = u;
+    }
+
+    double *sb = sys + (size_t) b * ICP_P2PL_SYS;
+#pragma unroll
+    for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) sb[t] = s_sum[t];
+    sb[ICP_P2PL_TERMS] = ok ? 1.0 : 0.0;
+
+    if (p.st_prev) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) p.st_prev[b].T[k] = Tprev[k];
+    }
+    float Tk[8], Tn[8], Rn[9], Rk[9];
+    if (ok) {
+        // qk = (w/2, 1) / |(w/2, 1)| in double, rounded to float; tk = (float) tau; sk = 1
+        const double hx = x[0] * 0.5, hy = x[1] * 0.5, hz = x[2] * 0.5;
+        const double inv = 1.0 / sqrt (((hx * hx + hy * hy) + hz * hz) + 1.0);
+        Tk[0] = (float) (hx * inv); Tk[1] = (float) (hy * inv); Tk[2] = (float) (hz * inv); Tk[3] = (float) inv;
+        Tk[4] = (float) x[3]; Tk[5] = (float) x[4]; Tk[6] = (float) x[5]; Tk[7] = 1.f;
+        icp_compose_pure (Tprev, Rprev, Tk, nullptr, 0, Tn, Rn, Rk);            // (icp_compose's arithmetic, registers in and out)
+    } else {
+        float S[11], means[8];
+        int iters = 0;
+        icp_identity_step (Tprev, Rprev, S, means, Tk, Tn, Rn, Rk, iters);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { st->T[k] = Tn[k]; st->Tk[k] = Tk[k]; }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { st->R[k] = Rn[k]; st->Rk[k] = Rk[k]; }
+    st->pm_iters = 0u;
+    st->k = st->k + 1u;
+    if (p.check && icp_check_converged (Tk, p.tan_half_thr, p.trans_thr)) st->done = 1u;
+}
+
+void icp_launch_p2pl_solve (const icp_params &p, hipStream_t s)
+{
+    const uint32_t nblk = icp_p2pl_nblk (p.m);
+    uint32_t P = 1u; while (P < nblk) P <<= 1;
+    double *sys = icp_p2pl_area (p), *part = sys + (size_t) p.batch * ICP_P2PL_SYS;
+    hipLaunchKernelGGL (k_p2pl_moments, dim3 (nblk, p.batch), dim3 (ICP_P2PL_BLOCK), 0, s, p, (const float4 *) icp_normals_f (p), part, nblk);
+    hipLaunchKernelGGL (k_p2pl_finalize, dim3 (p.batch), dim3 (256), 0, s, p, (const double *) part, sys, nblk, P);
+}
+
+void icp_launch_normals_grid (const icp_params &p, hipStream_t s)
+{
+    hipLaunchKernelGGL (k_normals_grid, dim3 ((p.m + 255u) / 256u, p.batch), dim3 (256), 0, s, p, icp_normals_f (p));
+}

@@ -50,7 +50,7 @@ static int track_prepare (icp_context *h)
             return e == hipSuccess ? ICP_OK : fail (h, ICP_ENOMEM, std::string ("tracking (second RBC set): ") + hipGetErrorString (e));
         };
         int rc;
-        if (!b.R && ((rc = al ((void **) &b.R, (size_t) p.nr * 32)) || (rc = al ((void **) &b.GB, (size_t) 2 * (p.n16 + p.n1k) * 16)) || (rc = al ((void **) &b.LB, (size_t) 3 * p.nlb * 16)) || (rc = al ((void **) &b.OL, (size_t) ICP_OL_STRIDE (p.nr) * 16)) || (rc = al ((void **) &b.XP, (size_t) p.m * 32)) ||
+        if (!b.R && ((rc = al ((void **) &b.R, (size_t) p.nr * 32)) || (rc = al ((void **) &b.GB, (size_t) 2 * (p.n16 + p.n1k) * 16)) || (rc = al ((void **) &b.LB, (size_t) 3 * p.nlb * 16)) || (rc = al ((void **) &b.OL, (size_t) ICP_OL_STRIDE (p.nr) * 16)) || (rc = al ((void **) &b.XP, (size_t) p.m * 48)) ||
             (rc = al ((void **) &b.XQ, (size_t) p.m * 32)) || (rc = al ((void **) &b.rep_src, (size_t) p.nr * 4)) || (rc = al ((void **) &b.owner, (size_t) p.m * 4)) ||
             (rc = al ((void **) &b.N, (size_t) 2 * p.batch * p.nr * 4)) || (rc = al ((void **) &b.O, (size_t) p.nr * 4)) || (rc = al ((void **) &b.perm, (size_t) p.m * 4)) ||
             (rc = al ((void **) &b.chunk_hist, (size_t) p.nchunk * p.nr * 4)) || (rc = al ((void **) &b.blist, (size_t) p.nb * 64 * 8)) ||
@@ -330,6 +330,12 @@ static int track_submit (icp_context *h, const void *cloud, int warm_start, bool
     int rc = need (h, false, true); if (rc) return rc;
     if ((rc = keeper_error (h))) return rc;
     if (!cloud) return fail (h, ICP_EINVAL, "null pointer");
+    // (point-to-plane: each frame's normals come from its own landmarks, which only buildRBC can give it — ICP_NORMALS_GRID)
+    if (icp_p2pl (h->p) && !h->p.nrm_grid)
+        return fail (h, ICP_ESTATE, "icp_track_submit: point-to-plane tracking needs ICP_NORMALS_GRID (icp_set_normals)");
+    // (a frame's buildRBC is enqueued from here, not through icp_build_rbc: the grid width is checked here as icp_build_rbc checks it)
+    if (h->p.nrm_grid && h->p.m % h->p.nrm_grid)
+        return fail (h, ICP_ESTATE, "icp_track_submit: ICP_NORMALS_GRID: m is not a multiple of the grid width");
     if ((rc = set_device (h))) return rc;
     if ((rc = track_prepare (h))) return rc;                            // (everything that can fail for lack of memory comes first)
     if (h->track_submitted - h->track_collected >= ICP_TRACK_RING)

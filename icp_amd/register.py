@@ -7,15 +7,17 @@ import time
 
 import numpy as np
 
-from . import ICP, Memory, PowerMode, ReduceMode
+from . import ICP, ErrorMetric, Memory, Normals, PowerMode, ReduceMode
 from .io import load_pc8d, save_pc8d
 
 
 def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, angle_threshold=0.001,
-                    translation_threshold=0.01, reduce_mode=ReduceMode.FUSED, reject_invalid=False, max_dist=None, trim=1.0):
+                    translation_threshold=0.01, reduce_mode=ReduceMode.FUSED, reject_invalid=False, max_dist=None, trim=1.0,
+                    point_to_plane=None):
     """Returns (T[8], k, latency_ms, transformed moving cloud).  reject_invalid / max_dist: correspondence rejection
-    (ICPStep.set_rejection), trim: the fraction of pairs trimmed ICP keeps (ICPStep.set_trimming; 1.0: off); neither is the
-    reference's behaviour, both are off by default."""
+    (ICPStep.set_rejection), trim: the fraction of pairs trimmed ICP keeps (ICPStep.set_trimming; 1.0: off), point_to_plane: mu of
+    point-to-plane ICP with the fixed frame's normals from its 128 x 128 landmark grid (ICPStep.set_error_metric; None: off); none
+    is the reference's behaviour, all are off by default."""
     reg = ICP(device)
     reg.init(16384, 256, a, c, max_iterations, angle_threshold, translation_threshold)   # src/ocl_icp_reg.cpp:81-88
     reg.setPowerMode(PowerMode.SQUARED)
@@ -24,6 +26,9 @@ def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, a
         reg.set_rejection(reject_invalid, max_dist)
     if trim != 1.0:
         reg.set_trimming(trim)
+    if point_to_plane is not None:
+        reg.set_normals(Normals.GRID, 128)                     # (640 x 480 clouds -> 128 x 128 landmarks, row-major)
+        reg.set_error_metric(ErrorMetric.POINT_TO_PLANE, point_to_plane)
     reg.write_cloud(Memory.F, fixed)
     reg.write_cloud(Memory.M, moving)
     reg.buildRBC()
@@ -60,6 +65,13 @@ def _fraction(s):
     return v
 
 
+def _point_weight(s):
+    v = float(s)
+    if not (v >= 0.0 and math.isfinite(v)):
+        raise argparse.ArgumentTypeError("must be finite and >= 0, got %s" % s)
+    return v
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("fixed")
@@ -73,9 +85,13 @@ def main(argv=None):
                     help="give pairs farther apart than this geometric distance (mm) weight 0 (not reference behaviour)")
     ap.add_argument("--trim", type=_fraction, default=1.0, metavar="FRACTION",
                     help="trimmed ICP: keep the closest FRACTION in (0, 1] of the pairs in every iteration (not reference behaviour)")
+    ap.add_argument("--point-to-plane", type=_point_weight, default=None, metavar="MU",
+                    help="point-to-plane ICP plus MU (>= 0) times the point-to-point error, normals from the fixed landmark grid "
+                         "(not reference behaviour)")
     args = ap.parse_args(argv)
     T, k, ms, out = register_clouds(load_pc8d(args.fixed), load_pc8d(args.moving), args.device, a=args.alpha,
-                                    reject_invalid=args.reject_invalid, max_dist=args.max_dist, trim=args.trim)
+                                    reject_invalid=args.reject_invalid, max_dist=args.max_dist, trim=args.trim,
+                                    point_to_plane=args.point_to_plane)
     q, t, s = T[:4], T[4:7], T[7]
     sinth_2 = float(np.linalg.norm(q[:3]))
     angle = 180.0 / math.pi * 2 * math.atan2(sinth_2, float(q[3]))

@@ -604,6 +604,15 @@ namespace ICP
         void setTrimming (float keep_fraction) { check (icp_set_trimming (h, keep_fraction)); }
         float getTrimming () { float f = 1.f; check (icp_get_trimming (h, &f)); return f; }
 
+        /*! \brief Point-to-plane ICP (icp_set_error_metric, include/icp_amd.h; not in the reference, off by default): metric
+         *         ICP_METRIC_POINT_TO_PLANE minimises the point-to-plane error plus point_weight (mu >= 0) times the point-to-point
+         *         error, linearised and solved on the device; ICP_METRIC_POINT_TO_POINT is the reference's iteration. */
+        void setErrorMetric (int metric, float point_weight = 0.f) { check (icp_set_error_metric (h, metric, point_weight)); }
+        void getErrorMetric (int &metric, float &point_weight) { check (icp_get_error_metric (h, &metric, &point_weight)); }
+        /*! \brief The fixed frame's normals (icp_set_normals): ICP_NORMALS_GIVEN (written as ICP_MEM_NORMALS_F) or ICP_NORMALS_GRID
+         *         (computed by buildRBC from F read as a row-major grid grid_width wide). */
+        void setNormals (int source, uint32_t grid_width = 0) { check (icp_set_normals (h, source, grid_width)); }
+
         float *hPtrInF;  /*!< Staging buffer of the fixed set (reference: mapped H_IN_F). */
         float *hPtrInM;  /*!< Staging buffer of the moving set. */
         float *hPtrIOT;  /*!< Staging buffer of [q | t, s]. */

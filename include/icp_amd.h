@@ -86,6 +86,8 @@ typedef enum {
     ICP_MEM_NN = 18,       /* out  m x float4   matched fixed xyz (+ weight in .w)      */
     ICP_MEM_QT = 19,       /* out  m x float4   transformed moving xyz (+ dist in .w)   */
     ICP_MEM_TRIM = 20,     /* out  uint32[4]    trimming, last iteration: t (float bits), n, K, accepted (0 when off) */
+    ICP_MEM_NORMALS_F = 21,/* io   m x float4   normals of the fixed landmarks [nx ny nz 0] (point-to-plane) */
+    ICP_MEM_PLANE_SYSTEM = 22, /* out double[28] point-to-plane: A's upper triangle (21), b (6), status (0 while off) */
     ICP_MEM_COUNT_
 } icp_mem;
 
@@ -122,8 +124,9 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
 /* ---- data movement ------------------------------------------------------------------------ */
 
 /* ICPStep::write (mem, ptr, block, events, event) — include/ICP/algorithms.hpp:2273,
- * src/ICP/algorithms.cpp:4596-4622.  mem in {ICP_MEM_F, ICP_MEM_M, ICP_MEM_T}.  Host -> pinned
- * staging -> device on the handle's stream; block != 0 waits for completion. */
+ * src/ICP/algorithms.cpp:4596-4622.  mem in {ICP_MEM_F, ICP_MEM_M, ICP_MEM_T}, or ICP_MEM_NORMALS_F (m x float4, the
+ * point-to-plane normals of ICP_NORMALS_GIVEN).  Host -> pinned staging -> device on the handle's stream; block != 0 waits for
+ * completion. */
 int icp_write (icp_handle h, int mem, const void *host_ptr, int block);
 int icp_write_b (icp_handle h, uint32_t batch_index, int mem, const void *host_ptr, int block);
 
@@ -264,6 +267,56 @@ int icp_get_rejection (icp_handle h, int *flags, float *max_dist);
  * batched and tracked registrations and survives icp_init.  ICP_EINVAL: keep_fraction NaN, <= 0 or > 1. */
 int icp_set_trimming (icp_handle h, float keep_fraction);
 int icp_get_trimming (icp_handle h, float *keep_fraction);
+
+/* Point-to-plane ICP with a share of point-to-point (not reference behaviour; off by default).  The rule:
+ *   - metric is ICP_METRIC_POINT_TO_POINT (the default: the same kernels, launches, graphs and bits as without it) or
+ *     ICP_METRIC_POINT_TO_PLANE.  point_weight mu is finite and >= 0.
+ *   - With point-to-plane on, each iteration minimises, linearised about the current transform (x = (omega, tau)),
+ *         E = sum_i w_i [ ((P_i + omega x P_i + tau - Q_i) . N_i)^2 + mu |P_i + omega x P_i + tau - Q_i|^2 ]
+ *     P = the transformed moving point the search used (ICP_MEM_QT xyz), Q = its matched fixed point (ICP_MEM_NN xyz), N = the normal
+ *     of that fixed point (ICP_MEM_NORMALS_F[id], id = ICP_MEM_NN_ID.id; a non-finite normal counts as zero), w = the weight the
+ *     search stores (ICP_MEM_W: 100 / (100 + dist) in WEIGHTED mode, 1 in REGULAR mode, 0 for a pair rejection or trimming removed).
+ *   - Per pair, in double from the float inputs, with J = (P x N, N), r = (Q - P) . N and [P]x the cross-product matrix:
+ *         A_i = J J^T + mu [[ |P|^2 I - P P^T, [P]x ], [ -[P]x, I ]]      b_i = J r + mu (P x Q, Q - P)
+ *     21 upper-triangle terms (row-major) and 6, each w (J_a J_b + mu G_ab) and w (J_a r + mu g_a); every expression is evaluated in
+ *     the order icp_p2pl.hip writes it down, with no contraction.  A pair with w == 0 contributes exact zeros (selected,
+ *     not multiplied: a NaN coordinate makes no NaN).
+ *   - The 27 sums: a halving tree x[i] += x[i + h] inside blocks of 256 consecutive pairs, then a halving tree over the block partials
+ *     zero-padded to a power of two.  No atomics; the result does not depend on the launch shape.
+ *   - A x = b is solved by LDL^T in double.  If a pivot d_j is not finite or d_j <= 1e-12 A_jj, the iteration is the identity step:
+ *     Tk = [0,0,0,1 | 0,0,0,1], Rk = I, T unchanged, and ICP::run's convergence test stops the run.  Otherwise
+ *     qk = (omega / 2, 1) normalised in double by 1 / sqrt of its squared length and rounded to float, tk = (float) tau, sk = 1,
+ *     composed as every other step (R = Rk R, Rk from qk) and checked with the same convergence test.
+ *   - rot, the power mode and the reduce mode do not affect a point-to-plane iteration; power_iterations is 0; ICP_MEM_MEANS, S and
+ *     SUM_W are not written.  The per-query outputs are stored by every iteration, and the form is the separate one (icp_run_form).
+ *   - ICP_MEM_PLANE_SYSTEM holds, per registration, A's upper triangle row-major (21), b (6) and the status (1 solved, 0 identity
+ *     step) of the last point-to-plane iteration; it reads zeros while the metric is off.
+ * Rejection and trimming apply as in point-to-point: their zeros are the weights.  A new mu while the metric stays on is a parameter
+ * update; switching the metric captures the run graphs anew.  The setting survives icp_init and applies to single, batched and
+ * tracked registrations (tracking needs ICP_NORMALS_GRID: icp_track_submit returns ICP_ESTATE with ICP_NORMALS_GIVEN).
+ * ICP_EINVAL: an unknown metric, mu negative, NaN or infinite. */
+#define ICP_METRIC_POINT_TO_POINT 0
+#define ICP_METRIC_POINT_TO_PLANE 1
+int icp_set_error_metric (icp_handle h, int metric, float point_weight);
+int icp_get_error_metric (icp_handle h, int *metric, float *point_weight);
+
+/* Where the fixed frame's normals come from (point-to-plane):
+ *   ICP_NORMALS_GIVEN (the default): the user writes ICP_MEM_NORMALS_F (m x float4 [nx ny nz 0] per registration, indexed like F);
+ *     it is used as given and starts as zeros.  grid_width is ignored (pass 0).
+ *   ICP_NORMALS_GRID: icp_build_rbc computes ICP_MEM_NORMALS_F from F, read as a row-major grid grid_width wide, in fp32 with no
+ *     contraction.  A point is valid when its xyz is finite and not (0,0,0).  The horizontal difference is P(x+1) - P(x-1) if both
+ *     neighbours are valid, else P(x+1) - P(x) if the right one is, else P(x) - P(x-1) if the left one is, else there is none; the
+ *     vertical difference follows the same rule with y.  c = dh x dv, n = c / sqrtf ((c.x^2 + c.y^2) + c.z^2), flipped to -n if
+ *     (n.x C.x + n.y C.y) + n.z C.z > 0 (it faces the sensor at the origin).  n = 0 when the centre C is invalid, a difference is
+ *     missing, or the length is not > 0 and finite.  The normals belong to the fixed frame as the RBC does: batched and tracked
+ *     runs need no extra call.
+ * m % grid_width must be 0: checked here on an initialised handle, and by icp_build_rbc and icp_track_submit / icp_track_next, which
+ * build the RBC (ICP_ESTATE).  The setting survives icp_init.
+ * ICP_EINVAL: an unknown source, or grid_width 0 with ICP_NORMALS_GRID. */
+#define ICP_NORMALS_GIVEN 0
+#define ICP_NORMALS_GRID 1
+int icp_set_normals (icp_handle h, int source, uint32_t grid_width);
+int icp_get_normals (icp_handle h, int *source, uint32_t *grid_width);
 int icp_set_scaling (icp_handle h, float c);
 int icp_get_max_iterations (icp_handle h, uint32_t *n);
 int icp_set_max_iterations (icp_handle h, uint32_t n);
@@ -449,7 +502,9 @@ int icp_batch_init (icp_batch_handle b, uint32_t registrations, uint32_t m, uint
 int icp_batch_set_modes (icp_batch_handle b, int reduce_mode, int power_mode);
 int icp_batch_set_rejection (icp_batch_handle b, int flags, float max_dist);                /* icp_set_rejection on every slot */
 int icp_batch_set_trimming (icp_batch_handle b, float keep_fraction);                        /* icp_set_trimming on every slot */
-int icp_batch_write (icp_batch_handle b, uint32_t i, int mem, const void *host_ptr);       /* mem: F, M or T of registration i */
+int icp_batch_set_error_metric (icp_batch_handle b, int metric, float point_weight);         /* icp_set_error_metric on every slot */
+int icp_batch_set_normals (icp_batch_handle b, int source, uint32_t grid_width);             /* icp_set_normals on every slot */
+int icp_batch_write (icp_batch_handle b, uint32_t i, int mem, const void *host_ptr);       /* mem: F, M, T or NORMALS_F of registration i */
 int icp_batch_build_rbc (icp_batch_handle b);
 int icp_batch_run (icp_batch_handle b);                                                      /* ICP::run of every registration */
 int icp_batch_run_fixed (icp_batch_handle b, uint32_t iterations, int from_identity);

@@ -75,6 +75,10 @@ public:
     /*! \brief Trimmed ICP of the registration (ICPStep::setTrimming; not in the reference's demo, off by default). */
     void setTrimming (float keep_fraction) { reg.setTrimming (keep_fraction); }
     float getTrimming () { return reg.getTrimming (); }
+    /*! \brief Point-to-plane ICP of the registration (ICPStep::setErrorMetric / setNormals; not in the reference's demo, off by default). */
+    void setErrorMetric (int metric, float point_weight = 0.f) { reg.setErrorMetric (metric, point_weight); }
+    void getErrorMetric (int &metric, float &point_weight) { reg.getErrorMetric (metric, point_weight); }
+    void setNormals (int source, uint32_t grid_width = 0) { reg.setNormals (source, grid_width); }
 
     /*! \brief The moving cloud after `registerPC ()` (the reference writes it into the GL vertex buffer). */
     const std::vector<icp_float8>& transformed () const { return moved; }
