@@ -6,12 +6,14 @@
 //   registration NAME                     data/NAME_1.bin, data/NAME_2.bin      (the reference's argument convention, :299-329)
 //   registration A B                      data/A.bin, data/B.bin — or A and B themselves when they name existing files
 //   ... [--out FILE] [--device N] [--reference-order] [--svd] [--reject-invalid] [--max-dist MM] [--trim FRACTION]
-//       [--point-to-plane MU]
+//       [--point-to-plane MU] [--colored KAPPA]
 //
 // --reject-invalid / --max-dist: correspondence rejection (icp_set_rejection: pairs with a pixel without depth at either end / pairs
 // farther apart than MM get weight 0).  --trim: trimmed ICP (icp_set_trimming: every iteration keeps the closest FRACTION in (0, 1] of the
 // pairs).  --point-to-plane: point-to-plane ICP plus MU (>= 0) times the point-to-point error (icp_set_error_metric), the normals from the
-// fixed 128 x 128 landmark grid (ICP_NORMALS_GRID).  Not the reference's behaviour; off by default.
+// fixed 128 x 128 landmark grid (ICP_NORMALS_GRID).  --colored: colored ICP (ICP_METRIC_COLORED): point-to-plane plus KAPPA (>= 0) times
+// the photometric term (icp_set_color_weight), grid normals and intensity gradients; MU of --point-to-plane when given, else 0.
+// Not the reference's behaviour; off by default.
 //
 // A cloud file is 640 x 480 points of 8 floats [x y z 1 r g b 1], little endian, row-major (src/kinect_frame_grabber.cpp:252-272).
 #include <cmath>
@@ -41,12 +43,16 @@ std::string data_path (const std::string &name) { return exists (name) ? name : 
 
 template <cl_algo::ICP::ICPStepConfigT RC>
 int run (int device, icp::Mode mode, const std::vector<icp_float8> &pc1, const std::vector<icp_float8> &pc2, const std::string &out,
-         int reject_flags, float max_dist, float trim, float p2pl_mu)
+         int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa)
 {
     ICPReg<RC, cl_algo::ICP::ICPStepConfigW::WEIGHTED> app (device, mode);
     if (reject_flags || max_dist > 0.f) app.setRejection (reject_flags, max_dist);
     if (trim != 1.f) app.setTrimming (trim);
-    if (p2pl_mu >= 0.f) { app.setNormals (ICP_NORMALS_GRID, 128); app.setErrorMetric (ICP_METRIC_POINT_TO_PLANE, p2pl_mu); }
+    if (kappa >= 0.f) {
+        app.setNormals (ICP_NORMALS_GRID, 128); app.setColorWeight (kappa);
+        app.setErrorMetric (ICP_METRIC_COLORED, p2pl_mu >= 0.f ? p2pl_mu : 0.f);
+    }
+    else if (p2pl_mu >= 0.f) { app.setNormals (ICP_NORMALS_GRID, 128); app.setErrorMetric (ICP_METRIC_POINT_TO_PLANE, p2pl_mu); }
     app.init (pc1, pc2);
     app.registerPC ();                                        // buildRBC + run + transform + the reference's report
     auto &reg = app.registration ();
@@ -68,7 +74,7 @@ int main (int argc, char **argv)
     std::vector<std::string> names;
     std::string out;
     int device = 0; bool svd = false;
-    int reject_flags = 0; float max_dist = 0.f, trim = 1.f, p2pl_mu = -1.f;     // (p2pl_mu < 0: point-to-point)
+    int reject_flags = 0; float max_dist = 0.f, trim = 1.f, p2pl_mu = -1.f, kappa = -1.f;     // (p2pl_mu < 0: point-to-point; kappa < 0: not colored)
     icp::Mode mode = icp::Mode::FAST;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -86,6 +92,10 @@ int main (int argc, char **argv)
             p2pl_mu = std::strtof (argv[++i], nullptr);
             if (!(p2pl_mu >= 0.f && std::isfinite (p2pl_mu))) { std::fprintf (stderr, "--point-to-plane: MU must be finite and >= 0\n"); return 2; }
         }
+        else if (a == "--colored" && i + 1 < argc) {
+            kappa = std::strtof (argv[++i], nullptr);
+            if (!(kappa >= 0.f && std::isfinite (kappa))) { std::fprintf (stderr, "--colored: KAPPA must be finite and >= 0\n"); return 2; }
+        }
         else if (a.rfind ("--", 0) == 0) { std::fprintf (stderr, "unknown option %s\n", a.c_str ()); return 2; }
         else names.push_back (a);
     }
@@ -101,8 +111,8 @@ int main (int argc, char **argv)
         } else {
             read_cloud (data_path (names[0]), pc1); read_cloud (data_path (names[1]), pc2);
         }
-        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu)
-                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu);
+        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa)
+                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa);
     }
     catch (const std::exception &e)
     {

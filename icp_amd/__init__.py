@@ -43,6 +43,7 @@ REJECT_INVALID = 1                # ICP_REJECT_INVALID (include/icp_amd.h): corr
 class ErrorMetric:                # icp_set_error_metric (include/icp_amd.h)
     POINT_TO_POINT = 0
     POINT_TO_PLANE = 1
+    COLORED = 2                   # point-to-plane plus kappa times a photometric term (set_color_weight)
 
 
 class Normals:                    # icp_set_normals: where the fixed frame's point-to-plane normals come from
@@ -51,8 +52,8 @@ class Normals:                    # icp_set_normals: where the fixed frame's poi
 
 
 def _write_floats(mem, m):
-    """Floats a write of `mem` takes: T 8, NORMALS_F m x 4, F / M m x 8."""
-    return 8 if mem == Memory.T else m * 4 if mem == Memory.NORMALS_F else m * 8
+    """Floats a write of `mem` takes: T 8, NORMALS_F / COLOR_GRAD_F m x 4, F / M m x 8."""
+    return 8 if mem == Memory.T else m * 4 if mem in (Memory.NORMALS_F, Memory.COLOR_GRAD_F) else m * 8
 
 
 def _max_dist_arg(max_dist):
@@ -78,7 +79,7 @@ class TransformKind:             # ICPTransformConfig (include/ICP/algorithms.hp
 
 class Memory:                    # icp_mem in include/icp_amd.h
     F, M, T, TK, MEANS, S, NN_ID, W, SUM_W, REPS, RBC_N, RBC_O, RBC_PERM, RBC_OWNER, RBC_XP, RID, R, RK, NN, QT, TRIM, \
-        NORMALS_F, PLANE_SYSTEM = range(23)
+        NORMALS_F, PLANE_SYSTEM, COLOR_GRAD_F = range(24)
     # reference spellings (ICPStep::Memory, include/ICP/algorithms.hpp:2241-2267)
     D_IN_F, D_IN_M, D_IO_T, H_IO_T = F, M, T, T
 
@@ -153,6 +154,8 @@ def lib():
     sig("icp_get_error_metric", i32, vp, C.POINTER(i32), C.POINTER(f32))
     sig("icp_set_normals", i32, vp, i32, u32)
     sig("icp_get_normals", i32, vp, C.POINTER(i32), C.POINTER(u32))
+    sig("icp_set_color_weight", i32, vp, f32)
+    sig("icp_get_color_weight", i32, vp, C.POINTER(f32))
     sig("icp_get_max_iterations", i32, vp, C.POINTER(u32))
     sig("icp_set_max_iterations", i32, vp, u32)
     sig("icp_get_angle_threshold", i32, vp, C.POINTER(f64))
@@ -180,6 +183,7 @@ def lib():
     sig("icp_batch_set_trimming", i32, vp, f32)
     sig("icp_batch_set_error_metric", i32, vp, i32, f32)
     sig("icp_batch_set_normals", i32, vp, i32, u32)
+    sig("icp_batch_set_color_weight", i32, vp, f32)
     sig("icp_batch_write", i32, vp, u32, i32, vp)
     sig("icp_batch_build_rbc", i32, vp)
     sig("icp_batch_run", i32, vp)
@@ -532,7 +536,7 @@ _MEM_DTYPE = {
     Memory.RBC_O: (np.uint32, None), Memory.RBC_PERM: (np.uint32, None), Memory.RBC_OWNER: (np.uint32, None),
     Memory.RID: (np.uint32, None), Memory.R: (np.float32, 3), Memory.RK: (np.float32, 3),
     Memory.NN: (np.float32, 4), Memory.QT: (np.float32, 4), Memory.TRIM: (np.uint32, None),
-    Memory.NORMALS_F: (np.float32, 4), Memory.PLANE_SYSTEM: (np.float64, None),
+    Memory.NORMALS_F: (np.float32, 4), Memory.PLANE_SYSTEM: (np.float64, None), Memory.COLOR_GRAD_F: (np.float32, 4),
 }
 
 
@@ -679,6 +683,18 @@ class ICPStep:
         s, w = C.c_int32(), C.c_uint32()
         self._chk(self._L.icp_get_normals(self._h, C.byref(s), C.byref(w)))
         return s.value, w.value
+
+    def set_color_weight(self, kappa):
+        """Colored ICP's photometric weight kappa (icp_set_color_weight; finite, >= 0, default 0, mm^2 per intensity^2): used with
+        set_error_metric(ErrorMetric.COLORED, mu).  The fixed frame's intensity gradients are Memory.COLOR_GRAD_F (m x 4 floats
+        [gx gy gz C]): computed by buildRBC with Normals.GRID, written by the user with Normals.GIVEN."""
+        self._chk(self._L.icp_set_color_weight(self._h, float(kappa)))
+
+    def color_weight(self):
+        """kappa as set."""
+        v = C.c_float()
+        self._chk(self._L.icp_get_color_weight(self._h, C.byref(v)))
+        return v.value
 
     # -- extensions ------------------------------------------------------------------------
     def setPowerMode(self, mode):
@@ -1026,6 +1042,10 @@ class ICPBatch:
         """ICPStep.set_normals on every registration (icp_batch_set_normals)."""
         self._chk(self._L.icp_batch_set_normals(self._b, int(source), int(grid_width)))
 
+    def set_color_weight(self, kappa):
+        """ICPStep.set_color_weight on every registration (icp_batch_set_color_weight)."""
+        self._chk(self._L.icp_batch_set_color_weight(self._b, float(kappa)))
+
     def write(self, i, mem, ptr):
         arr = np.ascontiguousarray(ptr, dtype=np.float32)
         want = _write_floats(mem, self.m)
@@ -1066,7 +1086,8 @@ class ICPBatch:
         dt, cols = _MEM_DTYPE[mem]
         sizes = {Memory.T: 32, Memory.TK: 32, Memory.MEANS: 32, Memory.S: 44, Memory.NN_ID: self.m * 8, Memory.R: 36, Memory.RK: 36,
                  Memory.F: self.m * 32, Memory.M: self.m * 32, Memory.W: self.m * 4, Memory.RID: self.m * 4, Memory.TRIM: 16,
-                 Memory.NN: self.m * 16, Memory.QT: self.m * 16, Memory.NORMALS_F: self.m * 16, Memory.PLANE_SYSTEM: 28 * 8}
+                 Memory.NN: self.m * 16, Memory.QT: self.m * 16, Memory.NORMALS_F: self.m * 16, Memory.PLANE_SYSTEM: 28 * 8,
+                 Memory.COLOR_GRAD_F: self.m * 16}
         nbytes = sizes[mem]
         out = np.empty(nbytes // np.dtype(dt).itemsize, dt)
         self._chk(self._L.icp_batch_read(self._b, i, mem, _p(out), nbytes))

@@ -374,10 +374,23 @@ ICP_CATCH_ALL
 int icp_batch_set_error_metric (icp_batch_handle b, int metric, float point_weight) try
 {
     if (!b) return ICP_EINVAL;
-    if (metric != ICP_METRIC_POINT_TO_POINT && metric != ICP_METRIC_POINT_TO_PLANE) return bfail (b, ICP_EINVAL, "icp_batch_set_error_metric: unknown metric");
+    if (metric != ICP_METRIC_POINT_TO_POINT && metric != ICP_METRIC_POINT_TO_PLANE && metric != ICP_METRIC_COLORED)
+        return bfail (b, ICP_EINVAL, "icp_batch_set_error_metric: unknown metric");
     if (!(point_weight >= 0.f && std::isfinite (point_weight))) return bfail (b, ICP_EINVAL, "icp_batch_set_error_metric: point_weight must be finite and >= 0");
     for (icp_handle h : b->slots) {
         int rc = icp_set_error_metric (h, metric, point_weight);
+        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
+    }
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
+int icp_batch_set_color_weight (icp_batch_handle b, float kappa) try
+{
+    if (!b) return ICP_EINVAL;
+    if (!(kappa >= 0.f && std::isfinite (kappa))) return bfail (b, ICP_EINVAL, "icp_batch_set_color_weight: kappa must be finite and >= 0");
+    for (icp_handle h : b->slots) {
+        int rc = icp_set_color_weight (h, kappa);
         if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
     }
     return ICP_OK;

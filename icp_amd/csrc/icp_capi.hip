@@ -181,6 +181,14 @@ int icp_destroy (icp_handle h) try
 }
 ICP_CATCH_ALL
 
+// colored ICP's kappa -> its device word (icp_color_kappa), in stream order behind whatever the handle's stream holds
+static int write_color_kappa (icp_context *h)
+{
+    uint32_t bits; std::memcpy (&bits, &h->color_kappa, sizeof bits);
+    HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (icp_color_kappa (h->p)), (int) bits, 1, h->stream));
+    return ICP_OK;
+}
+
 int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, float a, float c,
                       uint32_t max_iterations, double angle_threshold, double translation_threshold) try
 {
@@ -247,7 +255,7 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     p.gtile = 0u;                                                    // 4 x 4 tile groups where the representative grid allows
     if (nrx % 4u == 0u && nry % 4u == 0u && !std::getenv ("ICP_AMD_STRIP_GROUPS")) { uint32_t lg = 0; while ((4u << lg) < nrx) ++lg; p.gtile = lg + 1u; }
     if ((rc = dalloc (h, &p.GB, B * 2 * (p.n16 + p.n1k)))) return rc;
-    if ((rc = dalloc (h, &p.XP, B * m * 12))) return rc;            // (behind the database: NORMALS_F, icp_normals_f; zeroed)
+    if ((rc = dalloc (h, &p.XP, B * m * 16))) return rc;            // (behind the database: NORMALS_F, icp_normals_f, then COLOR_GRAD_F; zeroed)
     if ((rc = dalloc (h, &p.XQ, B * m * 8))) return rc;
     if ((rc = dalloc (h, &p.OL, B * ICP_OL_STRIDE (nr)))) return rc;
     p.nlb = m / 16u + 2u;
@@ -272,8 +280,9 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     // (behind the moments: trimming's result, selection state, histograms and keys — icp_trim_area; zeroed: ICP_MEM_TRIM reads 0 until a
     // trimmed iteration has run, and the histograms and counters start clear)
     // (behind those: the point-to-plane system and block partials — icp_p2pl_area; zeroed: ICP_MEM_PLANE_SYSTEM reads 0 until a
-    // point-to-plane iteration has run)
-    if ((rc = dalloc (h, &p.mom, B * 2 * 18 * p.nb + (icp_trim_words (batch, m) + 1u) / 2u + icp_p2pl_doubles (batch, m)))) return rc;
+    // point-to-plane iteration has run) and the word of colored ICP's kappa (icp_color_kappa, written below)
+    if ((rc = dalloc (h, &p.mom, B * 2 * 18 * p.nb + (icp_trim_words (batch, m) + 1u) / 2u + icp_p2pl_doubles (batch, m) + 1u))) return rc;
+    if ((rc = write_color_kappa (h))) return rc;
     if ((rc = dalloc (h, &p.ml1, B * 18 * ((p.nb + 127u) / 128u)))) return rc;
     if ((rc = dalloc (h, &p.cst, B * 2))) return rc;
     if ((rc = dalloc (h, &p.st, B))) return rc;
@@ -343,8 +352,16 @@ int icp_write_b (icp_handle h, uint32_t b, int mem, const void *host_ptr, int bl
             HIPCHK (h, hipMemcpy (icp_normals_f (h->p) + (size_t) b * h->p.m, host_ptr, (size_t) h->p.m * 16, hipMemcpyHostToDevice));
             break;
         }
+        case ICP_MEM_COLOR_GRAD_F: {
+            // (colored ICP's intensity gradients, ICP_NORMALS_GIVEN: as ICP_MEM_NORMALS_F)
+            if (!host_ptr) return fail (h, ICP_EINVAL, "icp_write: ICP_MEM_COLOR_GRAD_F needs a source");
+            note_inputs_change (h);
+            HIPCHK (h, hipStreamSynchronize (h->stream));
+            HIPCHK (h, hipMemcpy (icp_color_grad_f (h->p) + (size_t) b * h->p.m, host_ptr, (size_t) h->p.m * 16, hipMemcpyHostToDevice));
+            break;
+        }
         default:
-            return fail (h, ICP_EINVAL, "icp_write: mem must be ICP_MEM_F, ICP_MEM_M, ICP_MEM_T or ICP_MEM_NORMALS_F");
+            return fail (h, ICP_EINVAL, "icp_write: mem must be ICP_MEM_F, ICP_MEM_M, ICP_MEM_T, ICP_MEM_NORMALS_F or ICP_MEM_COLOR_GRAD_F");
     }
     if (block) HIPCHK (h, hipStreamSynchronize (h->stream));
     return ICP_OK;
@@ -369,7 +386,7 @@ size_t icp_mem_size (icp_handle h, int mem)
         case ICP_MEM_R: case ICP_MEM_RK: return 36;
         case ICP_MEM_NN: case ICP_MEM_QT: return (size_t) p.m * 16;
         case ICP_MEM_TRIM: return 16;
-        case ICP_MEM_NORMALS_F: return (size_t) p.m * 16;
+        case ICP_MEM_NORMALS_F: case ICP_MEM_COLOR_GRAD_F: return (size_t) p.m * 16;
         case ICP_MEM_PLANE_SYSTEM: return ICP_P2PL_SYS * sizeof (double);
         default: return 0;
     }
@@ -402,6 +419,7 @@ static int mem_ptr (icp_context *h, uint32_t b, int mem, const void **src)
         case ICP_MEM_W: *src = reinterpret_cast<const float *> (p.PF + (size_t) b * p.m) + 3; break;
         case ICP_MEM_TRIM: *src = icp_trim_area (p) + 4u * b; break;
         case ICP_MEM_NORMALS_F: *src = icp_normals_f (p) + (size_t) b * p.m; break;
+        case ICP_MEM_COLOR_GRAD_F: *src = icp_color_grad_f (p) + (size_t) b * p.m; break;
         case ICP_MEM_PLANE_SYSTEM: *src = icp_p2pl_area (p) + (size_t) ICP_P2PL_SYS * b; break;
         default: return fail (h, ICP_EINVAL, "unknown icp_mem value");
     }
@@ -718,19 +736,24 @@ int icp_get_trimming (icp_handle h, float *keep_fraction) try
 ICP_CATCH_ALL
 // point-to-plane (include/icp_amd.h, icp_p2pl.hip).  On <-> off changes which kernels run — the moments and the 6 x 6 finalize, no
 // chained form —: the route of icp_set_reduce_mode (graphs captured anew).  A new mu while the metric stays on is a parameter update.
+// Colored ICP (icp_color.hip) is point-to-plane with other moments: POINT_TO_PLANE <-> COLORED changes the kernels too (same route).
 int icp_set_error_metric (icp_handle h, int metric, float point_weight) try
 {
     api_guard guard_ (h);
-    if (metric != ICP_METRIC_POINT_TO_POINT && metric != ICP_METRIC_POINT_TO_PLANE) return fail (h, ICP_EINVAL, "icp_set_error_metric: unknown metric");
+    if (metric != ICP_METRIC_POINT_TO_POINT && metric != ICP_METRIC_POINT_TO_PLANE && metric != ICP_METRIC_COLORED)
+        return fail (h, ICP_EINVAL, "icp_set_error_metric: unknown metric");
     if (!(point_weight >= 0.f && std::isfinite (point_weight))) return fail (h, ICP_EINVAL, "icp_set_error_metric: point_weight must be finite and >= 0");
     if (!h) return fail (h, ICP_EINVAL, "icp_set_error_metric: null handle");
     { int rc = outputs_before_change (h); if (rc) return rc; }
-    const bool on = metric == ICP_METRIC_POINT_TO_PLANE;
-    if (on == icp_p2pl (h->p)) {
-        if (on) { h->p.p2pl_mu = point_weight; ++h->param_gen; }
+    if ((uint32_t) metric == h->p.metric) {
+        if (metric != ICP_METRIC_POINT_TO_POINT) { h->p.p2pl_mu = point_weight; ++h->param_gen; }
         return ICP_OK;
     }
-    if (on) { h->p.metric = (uint32_t) metric; h->p.p2pl_mu = point_weight; }
+    if (metric != ICP_METRIC_POINT_TO_POINT) {
+        h->p.metric = (uint32_t) metric; h->p.p2pl_mu = point_weight;
+        // (grid normals: the last buildRBC computed no intensity gradients — the next run needs a new one, as after a new F)
+        if (metric == ICP_METRIC_COLORED && h->p.nrm_grid) h->built = false;
+    }
     else {
         h->p.metric = 0u; h->p.p2pl_mu = 0.f;
         if (h->inited) {                                                 // ICP_MEM_PLANE_SYSTEM reads zeros while the metric is off
@@ -740,6 +763,32 @@ int icp_set_error_metric (icp_handle h, int metric, float point_weight) try
         }
     }
     drop_graphs (h);
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+// kappa lives in a device word the moments read (icp_color_kappa), not in the captured arguments: a new kappa touches no graph.  The
+// word is written in stream order once the open runs have ended, and the stream is drained so that work later enqueued on any of the
+// handle's streams reads the new value.
+int icp_set_color_weight (icp_handle h, float kappa) try
+{
+    api_guard guard_ (h);
+    if (!(kappa >= 0.f && std::isfinite (kappa))) return fail (h, ICP_EINVAL, "icp_set_color_weight: kappa must be finite and >= 0");
+    if (!h) return fail (h, ICP_EINVAL, "icp_set_color_weight: null handle");
+    h->color_kappa = kappa;
+    if (h->inited) {
+        int rc = set_device (h); if (rc) return rc;
+        if ((rc = run_close_all (h))) return rc;
+        if ((rc = write_color_kappa (h))) return rc;
+        HIPCHK (h, hipStreamSynchronize (h->stream));
+    }
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+int icp_get_color_weight (icp_handle h, float *kappa) try
+{
+    api_guard guard_ (h);
+    if (!h || !kappa) return ICP_EINVAL;
+    *kappa = h->color_kappa;
     return ICP_OK;
 }
 ICP_CATCH_ALL

@@ -71,7 +71,7 @@ struct icp_params {
     float4 *LB;                  // [batch][3 * nlb]  6-D bounding boxes of the list chunks (16 consecutive positions of one list, chunk c >= 1 of list r at
                                  // index (O[r] >> 4) + c: k_list_boxes) as [lo.x lo.y lo.z lo.r | lo.g lo.b hi.x hi.y | hi.z hi.r hi.g hi.b]
     uint32_t nlb;                // m / 16 + 2 boxes per registration
-    uint32_t metric;             // ICP_METRIC_POINT_TO_POINT (0, the default) or ICP_METRIC_POINT_TO_PLANE (icp_set_error_metric; icp_p2pl.hip)
+    uint32_t metric;             // ICP_METRIC_POINT_TO_POINT (0, the default), ICP_METRIC_POINT_TO_PLANE (icp_p2pl.hip) or ICP_METRIC_COLORED (icp_color.hip)
     uint32_t *rep_src, *owner, *N, *O, *perm, *chunk_hist;   // [batch][...]; N: [2][batch][nr] — [0] the length of a list AS THE SEARCH SCANS IT (k_search reads
                                  // p.N: a long list without the tail members that repeat an earlier member bit for bit, k_list_boxes), [1] = ICP_N_FULL: the list's
                                  // length N of the construction (RBCConstruct's output, ICP_MEM_RBC_N); the two differ for long lists with duplicates only
@@ -151,6 +151,15 @@ static inline double *icp_p2pl_area (const icp_params &p)
 {
     return p.mom + (size_t) p.batch * 2 * 18 * p.nb + (icp_trim_words (p.batch, p.m) + 1u) / 2u;
 }
+
+// Colored ICP (ICP_METRIC_COLORED, icp_color.hip): the point-to-plane system with a photometric term.  COLOR_GRAD_F ([gx gy gz C] per
+// fixed point) lies behind NORMALS_F in the XP allocation (B m 16 floats in all), so each RBC set carries its own as it does its normals.
+// The weight kappa has no room in icp_params: it is a device word behind the point-to-plane buffers in the moments' allocation
+// (icp_color_kappa; icp_set_color_weight writes it in stream order), which the run graphs read instead of capturing it.
+#define ICP_METRIC_COLORED_ 2u
+static __host__ __device__ __forceinline__ bool icp_colored (const icp_params &p) { return p.metric == ICP_METRIC_COLORED_; }
+static __host__ __device__ __forceinline__ float4 *icp_color_grad_f (const icp_params &p) { return reinterpret_cast<float4 *> (p.XP + (size_t) p.batch * p.m * 12); }
+static inline float *icp_color_kappa (const icp_params &p) { return reinterpret_cast<float *> (icp_p2pl_area (p) + icp_p2pl_doubles (p.batch, p.m)); }
 
 #define ICP_N_FULL(p, b) ((p).N + ((size_t) (p).batch + (b)) * (p).nr)
 
@@ -235,7 +244,9 @@ void icp_launch_trim (const icp_params &p, hipStream_t s);                   // 
 uint32_t icp_trim_launches (const icp_params &p);                             // how many that is
 void icp_launch_p2pl_solve (const icp_params &p, hipStream_t s);             // icp_p2pl.hip: k_p2pl_moments + k_p2pl_finalize (point-to-plane)
 void icp_launch_normals_grid (const icp_params &p, hipStream_t s);           // icp_p2pl.hip: k_normals_grid (ICP_NORMALS_GRID, behind buildRBC)
-#define ICP_P2PL_LAUNCHES 2u                                                  // launches of icp_launch_p2pl_solve
+#define ICP_P2PL_LAUNCHES 2u                                                  // launches of icp_launch_p2pl_solve (colored: the same count)
+void icp_launch_color_moments (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);   // icp_color.hip: k_color_moments
+void icp_launch_color_grad_grid (const icp_params &p, hipStream_t s);      // icp_color.hip: k_color_grad_grid (colored + ICP_NORMALS_GRID)
 void icp_launch_owner_search_dense (const icp_params &p, hipStream_t s);
 uint32_t icp_tbox_of (const icp_params &p);
 uint32_t icp_s2_wave_of (const icp_params &p);

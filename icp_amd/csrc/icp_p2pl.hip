@@ -277,11 +277,14 @@ void icp_launch_p2pl_solve (const icp_params &p, hipStream_t s)
     const uint32_t nblk = icp_p2pl_nblk (p.m);
     uint32_t P = 1u; while (P < nblk) P <<= 1;
     double *sys = icp_p2pl_area (p), *part = sys + (size_t) p.batch * ICP_P2PL_SYS;
-    hipLaunchKernelGGL (k_p2pl_moments, dim3 (nblk, p.batch), dim3 (ICP_P2PL_BLOCK), 0, s, p, (const float4 *) icp_normals_f (p), part, nblk);
+    // (colored ICP: its moments write the same partials, icp_color.hip; the finalize is this one)
+    if (icp_colored (p)) icp_launch_color_moments (p, s, part, nblk);
+    else hipLaunchKernelGGL (k_p2pl_moments, dim3 (nblk, p.batch), dim3 (ICP_P2PL_BLOCK), 0, s, p, (const float4 *) icp_normals_f (p), part, nblk);
     hipLaunchKernelGGL (k_p2pl_finalize, dim3 (p.batch), dim3 (256), 0, s, p, (const double *) part, sys, nblk, P);
 }
 
 void icp_launch_normals_grid (const icp_params &p, hipStream_t s)
 {
     hipLaunchKernelGGL (k_normals_grid, dim3 ((p.m + 255u) / 256u, p.batch), dim3 (256), 0, s, p, icp_normals_f (p));
+    if (icp_colored (p)) icp_launch_color_grad_grid (p, s);          // (the intensity gradients need the normals just computed)
 }

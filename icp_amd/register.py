@@ -13,11 +13,12 @@ from .io import load_pc8d, save_pc8d
 
 def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, angle_threshold=0.001,
                     translation_threshold=0.01, reduce_mode=ReduceMode.FUSED, reject_invalid=False, max_dist=None, trim=1.0,
-                    point_to_plane=None):
+                    point_to_plane=None, colored=None):
     """Returns (T[8], k, latency_ms, transformed moving cloud).  reject_invalid / max_dist: correspondence rejection
     (ICPStep.set_rejection), trim: the fraction of pairs trimmed ICP keeps (ICPStep.set_trimming; 1.0: off), point_to_plane: mu of
-    point-to-plane ICP with the fixed frame's normals from its 128 x 128 landmark grid (ICPStep.set_error_metric; None: off); none
-    is the reference's behaviour, all are off by default."""
+    point-to-plane ICP with the fixed frame's normals from its 128 x 128 landmark grid (ICPStep.set_error_metric; None: off),
+    colored: kappa of colored ICP, with grid normals and intensity gradients and mu = point_to_plane or 0 (ICPStep.set_color_weight;
+    None: off); none is the reference's behaviour, all are off by default."""
     reg = ICP(device)
     reg.init(16384, 256, a, c, max_iterations, angle_threshold, translation_threshold)   # src/ocl_icp_reg.cpp:81-88
     reg.setPowerMode(PowerMode.SQUARED)
@@ -26,7 +27,11 @@ def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, a
         reg.set_rejection(reject_invalid, max_dist)
     if trim != 1.0:
         reg.set_trimming(trim)
-    if point_to_plane is not None:
+    if colored is not None:
+        reg.set_normals(Normals.GRID, 128)
+        reg.set_color_weight(colored)
+        reg.set_error_metric(ErrorMetric.COLORED, 0.0 if point_to_plane is None else point_to_plane)
+    elif point_to_plane is not None:
         reg.set_normals(Normals.GRID, 128)                     # (640 x 480 clouds -> 128 x 128 landmarks, row-major)
         reg.set_error_metric(ErrorMetric.POINT_TO_PLANE, point_to_plane)
     reg.write_cloud(Memory.F, fixed)
@@ -88,10 +93,13 @@ def main(argv=None):
     ap.add_argument("--point-to-plane", type=_point_weight, default=None, metavar="MU",
                     help="point-to-plane ICP plus MU (>= 0) times the point-to-point error, normals from the fixed landmark grid "
                          "(not reference behaviour)")
+    ap.add_argument("--colored", type=_point_weight, default=None, metavar="KAPPA",
+                    help="colored ICP: point-to-plane plus KAPPA (>= 0) times the photometric term, normals and intensity gradients "
+                         "from the fixed landmark grid; MU of --point-to-plane when given, else 0 (not reference behaviour)")
     args = ap.parse_args(argv)
     T, k, ms, out = register_clouds(load_pc8d(args.fixed), load_pc8d(args.moving), args.device, a=args.alpha,
                                     reject_invalid=args.reject_invalid, max_dist=args.max_dist, trim=args.trim,
-                                    point_to_plane=args.point_to_plane)
+                                    point_to_plane=args.point_to_plane, colored=args.colored)
     q, t, s = T[:4], T[4:7], T[7]
     sinth_2 = float(np.linalg.norm(q[:3]))
     angle = 180.0 / math.pi * 2 * math.atan2(sinth_2, float(q[3]))

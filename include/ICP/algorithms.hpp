@@ -42,6 +42,9 @@ namespace icp
      *  Final [q | t, s] of the two agree within 1e-5 relative (|q| = 1, scene scale for t, s itself). */
     enum class Mode : uint8_t { FAST, REFERENCE_ORDER };
 
+    /*! \brief The objective of an iteration (setErrorMetric; include/icp_amd.h): the values of ICP_METRIC_*, usable as int. */
+    struct ErrorMetric { enum : int { POINT_TO_POINT = ICP_METRIC_POINT_TO_POINT, POINT_TO_PLANE = ICP_METRIC_POINT_TO_PLANE, COLORED = ICP_METRIC_COLORED }; };
+
     struct Vector3f
     {
         float v[3] = { 0.f, 0.f, 0.f };
@@ -612,6 +615,10 @@ namespace ICP
         /*! \brief The fixed frame's normals (icp_set_normals): ICP_NORMALS_GIVEN (written as ICP_MEM_NORMALS_F) or ICP_NORMALS_GRID
          *         (computed by buildRBC from F read as a row-major grid grid_width wide). */
         void setNormals (int source, uint32_t grid_width = 0) { check (icp_set_normals (h, source, grid_width)); }
+        /*! \brief Colored ICP's photometric weight kappa (icp_set_color_weight; finite, >= 0, default 0): used with
+         *         setErrorMetric (ICP_METRIC_COLORED, mu), the fixed frame's intensity gradients as ICP_MEM_COLOR_GRAD_F. */
+        void setColorWeight (float kappa) { check (icp_set_color_weight (h, kappa)); }
+        float getColorWeight () { float k = 0.f; check (icp_get_color_weight (h, &k)); return k; }
 
         float *hPtrInF;  /*!< Staging buffer of the fixed set (reference: mapped H_IN_F). */
         float *hPtrInM;  /*!< Staging buffer of the moving set. */

@@ -88,6 +88,7 @@ typedef enum {
     ICP_MEM_TRIM = 20,     /* out  uint32[4]    trimming, last iteration: t (float bits), n, K, accepted (0 when off) */
     ICP_MEM_NORMALS_F = 21,/* io   m x float4   normals of the fixed landmarks [nx ny nz 0] (point-to-plane) */
     ICP_MEM_PLANE_SYSTEM = 22, /* out double[28] point-to-plane: A's upper triangle (21), b (6), status (0 while off) */
+    ICP_MEM_COLOR_GRAD_F = 23, /* io m x float4  colored ICP: intensity gradients of the fixed landmarks [gx gy gz C] */
     ICP_MEM_COUNT_
 } icp_mem;
 
@@ -124,8 +125,8 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
 /* ---- data movement ------------------------------------------------------------------------ */
 
 /* ICPStep::write (mem, ptr, block, events, event) — include/ICP/algorithms.hpp:2273,
- * src/ICP/algorithms.cpp:4596-4622.  mem in {ICP_MEM_F, ICP_MEM_M, ICP_MEM_T}, or ICP_MEM_NORMALS_F (m x float4, the
- * point-to-plane normals of ICP_NORMALS_GIVEN).  Host -> pinned staging -> device on the handle's stream; block != 0 waits for
+ * src/ICP/algorithms.cpp:4596-4622.  mem in {ICP_MEM_F, ICP_MEM_M, ICP_MEM_T}, or ICP_MEM_NORMALS_F / ICP_MEM_COLOR_GRAD_F (m x
+ * float4, the point-to-plane normals and colored ICP's gradients of ICP_NORMALS_GIVEN).  Host -> pinned staging -> device on the handle's stream; block != 0 waits for
  * completion. */
 int icp_write (icp_handle h, int mem, const void *host_ptr, int block);
 int icp_write_b (icp_handle h, uint32_t batch_index, int mem, const void *host_ptr, int block);
@@ -294,11 +295,43 @@ int icp_get_trimming (icp_handle h, float *keep_fraction);
  * Rejection and trimming apply as in point-to-point: their zeros are the weights.  A new mu while the metric stays on is a parameter
  * update; switching the metric captures the run graphs anew.  The setting survives icp_init and applies to single, batched and
  * tracked registrations (tracking needs ICP_NORMALS_GRID: icp_track_submit returns ICP_ESTATE with ICP_NORMALS_GIVEN).
- * ICP_EINVAL: an unknown metric, mu negative, NaN or infinite. */
+ * ICP_EINVAL: an unknown metric, mu negative, NaN or infinite.  ICP_METRIC_COLORED (below) is point-to-plane with a photometric term. */
 #define ICP_METRIC_POINT_TO_POINT 0
 #define ICP_METRIC_POINT_TO_PLANE 1
+#define ICP_METRIC_COLORED 2
 int icp_set_error_metric (icp_handle h, int metric, float point_weight);
 int icp_get_error_metric (icp_handle h, int *metric, float *point_weight);
+
+/* Colored ICP (Park, Zhou, Koltun 2017; not reference behaviour; off by default): ICP_METRIC_COLORED is point-to-plane (the rule
+ * above, every part of it: mu, weights, trees, LDL^T, identity step, composition, PLANE_SYSTEM, the separate form) plus kappa times a
+ * linearised photometric residual per pair.  The rule:
+ *   - kappa (icp_set_color_weight) is finite and >= 0, default 0, in mm^2 per intensity^2; it survives icp_init.  A new kappa is a
+ *     parameter update (no graph is captured anew); POINT_TO_PLANE <-> COLORED changes the kernels (graphs captured anew).
+ *   - Intensity: C = ((r + g) + b) / 3 in fp32, from a landmark's rgb (floats 4..6).
+ *   - ICP_MEM_COLOR_GRAD_F, m x float4 [gx gy gz C] per registration, indexed like F: the intensity gradient at each fixed point in its
+ *     tangent plane, and its intensity.  ICP_NORMALS_GIVEN: the user writes it (icp_write, as ICP_MEM_NORMALS_F); it starts as zeros.
+ *     ICP_NORMALS_GRID with the colored metric: icp_build_rbc computes it behind the normals, for a valid centre p (finite, not the
+ *     origin) with normal n != 0, from the valid points p' of its 3 x 3 grid window in row-major order (the centre excluded), in double
+ *     from the float inputs:
+ *         v = p' - p, vn = (vx nx + vy ny) + vz nz, u = v - vn n (componentwise: vx - vn nx, ..), dC = C(p') - C(p);
+ *         from zeros, in window order: A_ab = A_ab + u_a u_b (A00 A01 A02 A11 A12 A22), b_a = b_a + u_a dC;  K = their number;
+ *         then with kn = (K nx, K ny, K nz): A_ab = A_ab + kn_a kn_b  (min sum (u . g - dC)^2 + (K n . g)^2);
+ *     solved by LDL^T with the 6 x 6 solve's order and pivot test, rounded to float once.  g = 0 when K < 3, the centre is invalid,
+ *     n = 0 or a pivot fails; C = C(p) always.  The gradients belong to the RBC set as the normals do (tracked frames get their own).
+ *     Switching a handle with ICP_NORMALS_GRID to the colored metric leaves it without gradients: icp_run and the other runs return
+ *     ICP_ESTATE until icp_build_rbc has run again.
+ *   - Per pair, with point-to-plane's P, Q, N, w, J, r, G, g and in double from the float inputs: (d, C_Q) = COLOR_GRAD_F[id] (a
+ *     non-finite d counts as zero), C_P = the intensity of the moving landmark M[i] (query order), and
+ *         dn = (dx nx + dy ny) + dz nz,  t = d - dn N (componentwise: dx - dn nx, ..)         (d in Q's tangent plane)
+ *         J_C = (P x t, t) = (py tz - pz ty, pz tx - px tz, px ty - py tx, tx, ty, tz)
+ *         e = P - Q,  r_C = C_P - (C_Q + ((tx ex + ty ey) + tz ez))
+ *         term (a, b), a <= b:  w ((J_a J_b + mu G_ab) + kappa (J_Ca J_Cb))     term 21 + a:  w ((J_a r + mu g_a) + kappa (J_Ca r_C))
+ *     so that J_C . x = r_C is the photometric match after the step, as J . x = r is the geometric one.  w == 0 selects exact zeros.
+ *     kappa = 0 gives point-to-plane's values (a -0 may become +0).
+ *   - Tracking needs ICP_NORMALS_GRID, as point-to-plane does; each frame's gradients come from its own buildRBC.
+ * ICP_EINVAL: kappa negative, NaN or infinite. */
+int icp_set_color_weight (icp_handle h, float kappa);
+int icp_get_color_weight (icp_handle h, float *kappa);
 
 /* Where the fixed frame's normals come from (point-to-plane):
  *   ICP_NORMALS_GIVEN (the default): the user writes ICP_MEM_NORMALS_F (m x float4 [nx ny nz 0] per registration, indexed like F);
@@ -504,7 +537,8 @@ int icp_batch_set_rejection (icp_batch_handle b, int flags, float max_dist);    
 int icp_batch_set_trimming (icp_batch_handle b, float keep_fraction);                        /* icp_set_trimming on every slot */
 int icp_batch_set_error_metric (icp_batch_handle b, int metric, float point_weight);         /* icp_set_error_metric on every slot */
 int icp_batch_set_normals (icp_batch_handle b, int source, uint32_t grid_width);             /* icp_set_normals on every slot */
-int icp_batch_write (icp_batch_handle b, uint32_t i, int mem, const void *host_ptr);       /* mem: F, M, T or NORMALS_F of registration i */
+int icp_batch_set_color_weight (icp_batch_handle b, float kappa);                            /* icp_set_color_weight on every slot */
+int icp_batch_write (icp_batch_handle b, uint32_t i, int mem, const void *host_ptr);       /* mem: F, M, T, NORMALS_F or COLOR_GRAD_F of registration i */
 int icp_batch_build_rbc (icp_batch_handle b);
 int icp_batch_run (icp_batch_handle b);                                                      /* ICP::run of every registration */
 int icp_batch_run_fixed (icp_batch_handle b, uint32_t iterations, int from_identity);

@@ -79,6 +79,9 @@ public:
     void setErrorMetric (int metric, float point_weight = 0.f) { reg.setErrorMetric (metric, point_weight); }
     void getErrorMetric (int &metric, float &point_weight) { reg.getErrorMetric (metric, point_weight); }
     void setNormals (int source, uint32_t grid_width = 0) { reg.setNormals (source, grid_width); }
+    /*! \brief Colored ICP of the registration (ICPStep::setColorWeight with setErrorMetric (ICP_METRIC_COLORED, mu)). */
+    void setColorWeight (float kappa) { reg.setColorWeight (kappa); }
+    float getColorWeight () { return reg.getColorWeight (); }
 
     /*! \brief The moving cloud after `registerPC ()` (the reference writes it into the GL vertex buffer). */
     const std::vector<icp_float8>& transformed () const { return moved; }

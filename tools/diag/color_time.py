@@ -1,0 +1,79 @@
+"""Diagnostic (not a test): microseconds per iteration of colored ICP (ICP_METRIC_COLORED) against point-to-plane and the default
+point-to-point iteration at A (16384 / 256), B (65536 / 1024) and A x 64, through the fixed-length run graphs bench.py times; and
+buildRBC back to back without normals, with grid normals (point-to-plane) and with grid normals and intensity gradients (colored).
+
+    python tools/diag/color_time.py [--only-colored] [--reps N]
+
+Prints one line per configuration and one JSON line at the end.  Under `rocprofv3 --kernel-trace --stats` (--only-colored) the
+per-kernel table shows the search, k_color_moments, k_p2pl_finalize, k_normals_grid and k_color_grad_grid."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+import icp_amd  # noqa: E402
+
+CONFIGS = {"A": (128, 256, 1), "B": (256, 1024, 1), "Ax64": (128, 256, 64)}
+METRICS = {"p2p": icp_amd.ErrorMetric.POINT_TO_POINT, "p2pl": icp_amd.ErrorMetric.POINT_TO_PLANE, "colored": icp_amd.ErrorMetric.COLORED}
+
+
+def make(side, nr, batch, metric):
+    g = icp_amd.ICP(0)
+    g.init(side * side, nr, 2e2, 1e-6, batch=batch)
+    g.setPowerMode(icp_amd.PowerMode.SQUARED)
+    if metric != icp_amd.ErrorMetric.POINT_TO_POINT:
+        g.set_normals(icp_amd.Normals.GRID, side)
+        g.set_color_weight(1000.0)
+        g.set_error_metric(metric, 0.05)
+    for b in range(batch):
+        F, M, _ = icp_amd.synth_pair_scene(side, icp_amd.SCENE_WALL, seed=0x1C9D5EED + b)
+        g.write(icp_amd.Memory.F, F, batch_index=b)
+        g.write(icp_amd.Memory.M, M, batch_index=b)
+    g.buildRBC()
+    return g
+
+
+def per_iteration_us(g, iterations, reps):
+    g.time_run_fixed(iterations, 2, True)                   # (warm-up: graph capture, clocks)
+    best = min(g.time_run_fixed(iterations, reps, True) for _ in range(3))
+    return best * 1e3 / (iterations * reps)
+
+
+def build_us(g, n=200):
+    g.buildRBC(); g.sync()
+    best = float("inf")
+    for _ in range(3):
+        t0 = time.perf_counter()
+        for _ in range(n):
+            g.buildRBC()
+        g.sync()
+        best = min(best, (time.perf_counter() - t0) / n * 1e6)
+    return best
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--only-colored", action="store_true")
+    ap.add_argument("--reps", type=int, default=20)
+    args = ap.parse_args()
+    out = {}
+    for name, (side, nr, batch) in CONFIGS.items():
+        for mname, metric in METRICS.items():
+            if args.only_colored and mname != "colored":
+                continue
+            g = make(side, nr, batch, metric)
+            us = per_iteration_us(g, 20, args.reps)
+            bus = build_us(g)
+            form, launches = g.run_form(), g.launches_per_iteration()
+            g.close()
+            out["%s_%s" % (name, mname)] = round(us, 3)
+            out["%s_%s_build" % (name, mname)] = round(bus, 3)
+            print("%-5s %-8s %8.3f us/iteration  (form %d, %d launches per iteration)   buildRBC %8.2f us"
+                  % (name, mname, us, form, launches, bus))
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
