@@ -1,0 +1,355 @@
+"""The opt-in paths of the iteration (point-to-plane, colored, trimming, rejection) at the sizes where their kernels branch.
+
+The bit-for-bit modules of each path run at a few sizes only; this one takes their checks, unchanged, to the shapes they miss:
+  - point-to-plane / colored: m below one block of 256 (nblk = 1: the finalize's tree has no level), a partly filled last block
+    (the clamp and the i < m guard of the moments), block counts that are no power of two (the finalize's zero padding), P > 256 (the
+    finalize's multi-pass tree: 8, 4, 2, 1 terms per pass) up to m = 2^20, batches with such block counts;
+  - trimming: the multi-workgroup select (m > 16384) with a partly filled last workgroup, just above the one-workgroup limit, batched
+    (each registration its own histogram, arrival counter and keys) and in runs whose registrations stop at different iterations;
+  - rejection and trimming at sides that are not a multiple of 8 (fused mode's linear 64-query blocks) and in the dense layouts.
+Every check is teacher-forced: the restatement (tests/p2pl_ref.py, tests/colored_ref.py) or the oracle's pieces are fed the engine's own
+correspondences of the step.  The point-to-plane steps are also compared with numpy's least-squares solution of their own system."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import test_gpu_colored_icp as col                              # noqa: E402
+import test_gpu_point_to_plane as p2pl                          # noqa: E402
+import test_gpu_trimming as trim                                # noqa: E402
+from test_gpu_parity import A, C_, assert_bits, set_modes       # noqa: E402
+from test_gpu_rejection import _holes, _t0, check_one_step, make_handle as rej_handle, oracle_search, pick_max_dist   # noqa: E402
+from test_plane_system_float64 import unpack                    # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+POWER = 1
+REGULAR, WEIGHTED = 0, 1
+EPS32 = float(np.finfo(np.float32).eps)
+EPS64 = float(np.finfo(np.float64).eps)
+
+
+def check_lstsq(engine, g, b=0):
+    """The step of registration b against numpy's least-squares solution of the engine's own system A x = b, at float32 rounding:
+    omega from TK's quaternion (2 qk / qk.w), tau from TK[4:7].  Compared in the variables scaled by sqrt(diag A) (the scale in which
+    LDL^T's error is bounded by the scaled condition number).  Returns False for an identity step (nothing to compare)."""
+    s = g.read(engine.Memory.PLANE_SYSTEM, b)
+    if s[27] != 1.0:
+        return False
+    Am, bv = unpack(s[:27])
+    d = 1.0 / np.sqrt(np.diag(Am))
+    As = Am * np.outer(d, d)
+    ys = np.linalg.lstsq(As, bv * d, rcond=None)[0]
+    Tk = g.read(engine.Memory.TK, b).astype(np.float64)
+    x = np.concatenate([2.0 * Tk[:3] / Tk[3], Tk[4:7]])
+    ye = x / d
+    tol = 8 * EPS32 + 100 * np.linalg.cond(As) * EPS64
+    for part, what in ((slice(0, 3), "omega"), (slice(3, 6), "tau")):
+        err = np.linalg.norm(ye[part] - ys[part])
+        assert err <= tol * np.linalg.norm(ys), (what, b, ye, ys, tol)
+    return True
+
+
+# ---- 1. point-to-plane and colored at the finalize's shapes -------------------------------------------------------------------
+
+# (side, nr): m, nblk = ceil (m / 256), P = nblk padded to a power of two
+#   (6, 4) 36 and (14, 4) 196: nblk = 1, no tree level in the finalize;  (30, 4) 900: a partly filled last block, nblk = 4;
+#   (96, 64) 9216: nblk = 36 padded to 64;  (150, 4) 22500: a partly filled last block, nblk = 88;  (320, 256) 102400: P = 512, the
+#   multi-pass tree (8 terms per pass);  (512, 1024) 2^18: P = 1024;  (1000, 64) 10^6: a partly filled last block, nblk = 3907 padded to
+#   4096, 27 passes of one term;  (1024, 4096) 2^20 (config C): nblk = 4096, the largest m icp_init accepts.
+PLANE_SHAPES = [(6, 4), (14, 4), (30, 4), (96, 64), (150, 4), (320, 256), (512, 1024), (1000, 64), (1024, 4096)]
+
+
+@pytest.mark.parametrize("side,nr", PLANE_SHAPES)
+def test_point_to_plane_steps(engine, side, nr):
+    F, M = engine.synth_pair(side, seed=0x9A1E + side)
+    g = p2pl.make(engine, side, nr, mu=0.05)
+    p2pl.load(engine, g, F, M)
+    g.buildRBC()
+    for _ in range(2):
+        s = p2pl.check_step(engine, g, 0.05)
+        assert s[27] == 1.0
+        assert check_lstsq(engine, g)
+    g.close()
+
+
+@pytest.mark.parametrize("side,nr", [(30, 4), (150, 4), (1000, 64)])
+def test_point_to_plane_messy_grid(engine, side, nr):
+    """Holes, NaN / inf and zero points in F (grid normals of zero around them), REGULAR weights."""
+    seed = 0xBAD + side
+    F = p2pl._messy_grid(engine, side, seed)
+    M = engine.synth_pair(side, seed=seed)[1]
+    g = p2pl.make(engine, side, nr, weighted=REGULAR, mu=0.05, fused=False)
+    p2pl.load(engine, g, F, M)
+    g.buildRBC()
+    assert np.count_nonzero(g.read(engine.Memory.NORMALS_F)[:, :3].any(axis=1)) < side * side * 0.9
+    for _ in range(2):
+        p2pl.check_step(engine, g, 0.05)
+        check_lstsq(engine, g)
+    g.close()
+
+
+@pytest.mark.parametrize("side,nr", [(6, 4), (30, 4), (150, 4), (320, 256), (1024, 4096)])
+def test_colored_steps(engine, side, nr):
+    F, M, _ = engine.synth_pair_scene(side, engine.SCENE_WALL, seed=0xC01 + side)
+    g = col.make(engine, side, nr, mu=0.05, kappa=1000.0)
+    col.load(engine, g, F, M)
+    g.buildRBC()
+    for _ in range(2):
+        s = col.check_step(engine, g, 0.05, 1000.0)
+        assert s[27] == 1.0
+        assert check_lstsq(engine, g)
+    g.close()
+
+
+def test_point_to_plane_batch3_at_P512(engine):
+    """Three registrations of 102400 (nblk = 400 each, P = 512): each checked on its own and against a single handle."""
+    side, nr, n = 320, 256, 3
+    pairs = [engine.synth_pair(side, seed=0x7A00 + i, rot_deg=1.0 + 1.5 * i) for i in range(n)]
+    g = p2pl.make(engine, side, nr, batch=n, mu=0.05)
+    for b, (F, M) in enumerate(pairs):
+        p2pl.load(engine, g, F, M, b)
+    g.buildRBC()
+    Mem = engine.Memory
+    for _ in range(2):
+        T0 = [(g.read(Mem.T, b).copy(), g.read(Mem.R, b).ravel().copy()) for b in range(n)]
+        g.step()
+        for b in range(n):
+            p2pl.check_last(engine, g, 0.05, T0[b][0], T0[b][1], b)
+            assert check_lstsq(engine, g, b)
+    systems = [g.read(Mem.PLANE_SYSTEM, b).copy() for b in range(n)]
+    assert not np.array_equal(systems[0], systems[1]) and not np.array_equal(systems[1], systems[2])
+    for b in range(n):
+        h = p2pl.make(engine, side, nr, mu=0.05)
+        p2pl.load(engine, h, *pairs[b])
+        h.buildRBC()
+        h.step(); h.step()
+        assert_bits(g.read(Mem.T, b), h.read(Mem.T), "T of registration %d" % b)
+        assert_bits(g.read(Mem.PLANE_SYSTEM, b), h.read(Mem.PLANE_SYSTEM), "system of registration %d" % b)
+        assert np.array_equal(g.read(Mem.NN_ID, b)["id"], h.read(Mem.NN_ID)["id"]), b
+        h.close()
+    g.close()
+
+
+@pytest.mark.parametrize("metric", [p2pl.P2PL, col.COLORED])
+def test_run_batch2_at_a_partial_block(engine, metric):
+    """ICP::run on two registrations of 22500 (nblk = 88, the last block partly filled) against single handles: k, T, the system."""
+    side, nr = 150, 4
+    if metric == col.COLORED:
+        pairs = [engine.synth_pair_scene(side, engine.SCENE_WALL, seed=0x7B00 + i, rot_deg=1.0 + 2.0 * i)[:2] for i in range(2)]
+        mk = lambda batch=1: col.make(engine, side, nr, mu=0.05, kappa=1000.0, batch=batch)
+    else:
+        pairs = [engine.synth_pair(side, seed=0x7B00 + i, rot_deg=1.0 + 2.0 * i) for i in range(2)]
+        mk = lambda batch=1: p2pl.make(engine, side, nr, mu=0.05, batch=batch)
+    g = mk(2)
+    for b, (F, M) in enumerate(pairs):
+        p2pl.load(engine, g, F, M, b)
+    g.buildRBC()
+    g.run()
+    Mem = engine.Memory
+    for b, (F, M) in enumerate(pairs):
+        h = mk()
+        p2pl.load(engine, h, F, M)
+        h.buildRBC()
+        k = h.run()
+        assert 1 < k <= 40, k
+        assert g.state(b).k == k, (b, g.state(b).k, k)
+        assert_bits(g.read(Mem.T, b), h.read(Mem.T), "T of registration %d" % b)
+        assert_bits(g.read(Mem.PLANE_SYSTEM, b), h.read(Mem.PLANE_SYSTEM), "system of registration %d" % b)
+        h.close()
+    g.close()
+
+
+# ---- 2. trimming's multi-workgroup select ----------------------------------------------------------------------------------------
+
+# m > ICP_TRIM_ONE_BLOCK_MAX (16384): the select in three multi-workgroup passes of 2048 pairs per workgroup.  (130, 4) 16900: just
+# above the one-workgroup limit, 516 pairs in the last workgroup;  (150, 4) 22500: a side that is no multiple of 8 (fused mode's linear
+# 64-query blocks in k_trim_apply), 2020 in the last workgroup;  (200, 64) 40000: the tiled order, 1088 in the last workgroup.
+TRIM_SHAPES = [(130, 4), (150, 4), (200, 64)]
+TRIM_MODES = [(True, WEIGHTED), (False, REGULAR)]
+
+
+@pytest.mark.parametrize("side,nr", TRIM_SHAPES)
+@pytest.mark.parametrize("fused,weighted", TRIM_MODES)
+def test_trim_one_step_large_select(engine, oracle, side, nr, fused, weighted):
+    F, M = _holes(engine, side, 0x7E1 + side)
+    T = _t0()
+    g = trim.make_handle(engine, side * side, nr, fused, weighted, POWER, fused, True, 0.75)
+    trim.one_step(engine, g, F, M, T)
+    _, t = trim.check_step(engine, oracle, g, F, M, T, side, fused, weighted, POWER, fused, True, 0.75)
+    n, K = int(t[1]), int(t[2])
+    assert n > side * side // 3 and K <= t[3] < n, t
+    g.close()
+
+
+def _varied_pairs(engine, side, n, seed):
+    """n pairs with different motions and hole patterns (blobs 30 %, scattered 10 %, blobs 10 %, ..)."""
+    from icp_amd import workloads as W
+    names = ["blobs30", "scattered10", "blobs10"]
+    out = []
+    for b in range(n):
+        pattern, fraction, keep = W.HOLES[names[b % 3]]
+        F, M = engine.synth_pair(side, seed=seed + 17 * b, rot_deg=0.5 + 1.75 * b, t=(25.0 - 9 * b, -10.0 + 4 * b, 15.0 - 5 * b))
+        F = engine.punch_holes(F, side, side, pattern, fraction, keep, seed=seed + 17 * b + 101)
+        M = engine.punch_holes(M, side, side, pattern, fraction, keep, seed=seed + 17 * b + 202)
+        out.append((F, M))
+    return out
+
+
+@pytest.mark.parametrize("side,nr", [(150, 4), (200, 64)])
+@pytest.mark.parametrize("fused,weighted", TRIM_MODES)
+def test_trim_batch3_large_select(engine, oracle, side, nr, fused, weighted):
+    """Three registrations in one handle, each with its own histogram, arrival counter and keys: every one checked."""
+    n = 3
+    pairs = _varied_pairs(engine, side, n, 0x7E2 + side)
+    T = _t0()
+    g = trim.make_handle(engine, side * side, nr, fused, weighted, POWER, fused, True, 0.75, batch=n)
+    for b, (F, M) in enumerate(pairs):
+        g.write(engine.Memory.F, F, batch_index=b); g.write(engine.Memory.M, M, batch_index=b)
+    g.buildRBC()
+    for b in range(n):
+        g.write(engine.Memory.T, T, batch_index=b, block=True)
+    g.step()
+    ts = set()
+    for b, (F, M) in enumerate(pairs):
+        _, t = trim.check_step(engine, oracle, g, F, M, T, side, fused, weighted, POWER, fused, True, 0.75, b=b)
+        ts.add((int(t[0]), int(t[1])))
+    assert len(ts) == n, ts
+    g.close()
+
+
+@pytest.mark.parametrize("fused", [True, False])
+def test_trim_batch3_run_against_single_handles(engine, fused):
+    """ICP::run on three registrations of 22500 that stop at different iterations (converged ones skip the select's passes): each
+    one's k, T and ICP_MEM_TRIM equal a single handle's.  Registration 0 registers a frame to itself (it converges at once); the
+    other two have motions and holes of their own."""
+    side, nr, n = 150, 4, 3
+    pairs = _varied_pairs(engine, side, n, 0x7E3)
+    pairs[0] = (pairs[0][0], pairs[0][0].copy())
+
+    def handle(batch):
+        g = engine.ICP(0)
+        g.init(side * side, nr, A, C_, angle_threshold=0.01, translation_threshold=0.05, batch=batch)
+        set_modes(engine, g, power_fast=fused, fused=fused)
+        g.set_rejection(True, None)
+        g.set_trimming(0.75)
+        return g
+
+    g = handle(n)
+    for b, (F, M) in enumerate(pairs):
+        g.write(engine.Memory.F, F, batch_index=b); g.write(engine.Memory.M, M, batch_index=b)
+    g.buildRBC()
+    g.run()
+    ks = []
+    for b, (F, M) in enumerate(pairs):
+        h = handle(1)
+        h.write(engine.Memory.F, F); h.write(engine.Memory.M, M)
+        h.buildRBC()
+        k = h.run()
+        ks.append(k)
+        assert g.state(b).k == k, (b, g.state(b).k, k)
+        assert_bits(g.read(engine.Memory.T, b), h.read(engine.Memory.T), "T of registration %d" % b)
+        assert np.array_equal(g.read(engine.Memory.TRIM, b), h.read(engine.Memory.TRIM)), b
+        h.close()
+    assert len(set(ks)) > 1 and min(ks) < 40, ks
+    g.close()
+
+
+@pytest.mark.parametrize("fused", [True, False])
+def test_point_to_plane_with_trimming_large_select(engine, fused):
+    """The select of 22500 pairs feeds the plane moments: the accepted set by the rule, then the system by the restatement."""
+    side, nr = 150, 4
+    F, M = _holes(engine, side, 0x7E4)
+    g = p2pl.make(engine, side, nr, mu=0.05, fused=fused)
+    g.set_rejection(True, None)
+    g.set_trimming(0.75)
+    p2pl.load(engine, g, F, M)
+    g.buildRBC()
+    Mem = engine.Memory
+    for _ in range(2):
+        p2pl.check_step(engine, g, 0.05)
+        PF, PM, nn_id = g.read(Mem.NN), g.read(Mem.QT), g.read(Mem.NN_ID)
+        W0 = trim.weights_before_trim(nn_id, M, PF, PM, True, True)
+        acc, t = trim.trim_rule(PF, PM, W0, 0.75)
+        assert np.array_equal(g.read(Mem.TRIM), t), (g.read(Mem.TRIM), t)
+        assert_bits(PF[acc, 3], W0[acc], "accepted weights")
+        assert np.all(PF[~acc, 3].view(np.uint32) == 0), "a trimmed or rejected pair's weight is +0"
+        assert t[3] < t[1]
+        check_lstsq(engine, g)
+    g.close()
+
+
+# ---- 3. rejection and trimming at tiny and odd sides, and in the dense layouts ------------------------------------------------------
+
+TINY = [(2, 1), (2, 4), (4, 2), (8, 64), (10, 4), (14, 4), (30, 4)]
+
+
+def _tiny_pair(engine, side):
+    """synth_pair with invalid points planted by hand: the first moving point, and about one in seven points of either set beyond it."""
+    F, M = engine.synth_pair(side, seed=0x71 + side)
+    m = side * side
+    M[0, :3] = 0.0
+    F[m - 1, :3] = 0.0
+    F[np.arange(3, m - 1, 7), :3] = 0.0
+    M[np.arange(5, m, 7), :3] = 0.0
+    return F, M
+
+
+@pytest.mark.parametrize("side,nr", TINY)
+@pytest.mark.parametrize("fused", [True, False])
+def test_rejection_tiny_and_odd(engine, oracle, side, nr, fused):
+    F, M = _tiny_pair(engine, side)
+    T = _t0()
+    g = rej_handle(engine, side * side, nr, fused, WEIGHTED, POWER, fused, True, 1.0)
+    g.write(engine.Memory.F, F); g.write(engine.Memory.M, M)
+    g.buildRBC()
+    g.write(engine.Memory.T, T, block=True)
+    for _ in range(2):
+        T = g.read(engine.Memory.T).copy()
+        md = pick_max_dist(oracle, F, M, T, nr, frac=0.3)             # (a cap that rejects some valid pair at this step's T)
+        g.set_rejection(True, md)
+        g.step()
+        rej = check_one_step(engine, oracle, g, F, M, T, side, nr, fused, WEIGHTED, POWER, fused, True, md)
+        invalid = (M[:, :3] == 0).all(1) | (g.read(engine.Memory.NN)[:, :3] == 0).all(1)
+        assert invalid.any() and (rej & ~invalid).any(), "both rules reject some pair"
+    g.close()
+
+
+@pytest.mark.parametrize("side,nr", TINY)
+@pytest.mark.parametrize("fused", [True, False])
+def test_trimming_tiny_and_odd(engine, oracle, side, nr, fused):
+    F, M = _tiny_pair(engine, side)
+    T = _t0()
+    g = trim.make_handle(engine, side * side, nr, fused, WEIGHTED, POWER, fused, True, 0.5)
+    trim.one_step(engine, g, F, M, T)
+    for it in range(2):
+        if it:
+            T = g.read(engine.Memory.T).copy()
+            g.step()
+        acc, t = trim.check_step(engine, oracle, g, F, M, T, side, fused, WEIGHTED, POWER, fused, True, 0.5,
+                                 oracle_search(oracle, F, M, T, nr))
+        assert 0 < t[3] < t[1], t                                      # (some pair trimmed, some kept)
+    g.close()
+
+
+@pytest.mark.parametrize("side,nr,batch", [(256, 256, 1), (128, 64, 3)])
+@pytest.mark.parametrize("fused", [True, False])
+def test_rejection_dense_layouts(engine, oracle, side, nr, batch, fused):
+    """The stage-2 layouts with lanes as candidates (dense, and dense by batch): their REJ variants."""
+    pairs = [_holes(engine, side, 0x7E5 + 11 * b, "blobs30" if b % 2 == 0 else "scattered10") for b in range(batch)]
+    T = _t0()
+    md = pick_max_dist(oracle, pairs[0][0], pairs[0][1], T, nr)
+    g = rej_handle(engine, side * side, nr, fused, WEIGHTED, POWER, fused, True, md, batch=batch)
+    if fused:
+        assert g.search_layout() == (1, 256, 1)
+    for b, (F, M) in enumerate(pairs):
+        g.write(engine.Memory.F, F, batch_index=b); g.write(engine.Memory.M, M, batch_index=b)
+    g.buildRBC()
+    for b in range(batch):
+        g.write(engine.Memory.T, T, batch_index=b, block=True)
+    g.step()
+    for b, (F, M) in enumerate(pairs):
+        check_one_step(engine, oracle, g, F, M, T, side, nr, fused, WEIGHTED, POWER, fused, True, md, b=b)
+    g.close()
