@@ -255,7 +255,7 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     p.gtile = 0u;                                                    // 4 x 4 tile groups where the representative grid allows
     if (nrx % 4u == 0u && nry % 4u == 0u && !std::getenv ("ICP_AMD_STRIP_GROUPS")) { uint32_t lg = 0; while ((4u << lg) < nrx) ++lg; p.gtile = lg + 1u; }
     if ((rc = dalloc (h, &p.GB, B * 2 * (p.n16 + p.n1k)))) return rc;
-    if ((rc = dalloc (h, &p.XP, B * m * 16))) return rc;            // (behind the database: NORMALS_F, icp_normals_f, then COLOR_GRAD_F; zeroed)
+    if ((rc = dalloc (h, &p.XP, icp_xp_layout_of (batch, m).total))) return rc;    // (behind the database: NORMALS_F, then COLOR_GRAD_F; zeroed)
     if ((rc = dalloc (h, &p.XQ, B * m * 8))) return rc;
     if ((rc = dalloc (h, &p.OL, B * ICP_OL_STRIDE (nr)))) return rc;
     p.nlb = m / 16u + 2u;
@@ -277,11 +277,9 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     if ((rc = dalloc (h, &p.mpart, B * 2 * p.nwg))) return rc;
     if ((rc = dalloc (h, &p.mscr, B * 2 * ((p.nwg + 127u) / 128u)))) return rc;
     if ((rc = dalloc (h, &p.spart, B * 11 * p.nsp * 8))) return rc;    // 8 sub-trees per work-group; padding stays 0.f
-    // (behind the moments: trimming's result, selection state, histograms and keys — icp_trim_area; zeroed: ICP_MEM_TRIM reads 0 until a
-    // trimmed iteration has run, and the histograms and counters start clear)
-    // (behind those: the point-to-plane system and block partials — icp_p2pl_area; zeroed: ICP_MEM_PLANE_SYSTEM reads 0 until a
-    // point-to-plane iteration has run) and the word of colored ICP's kappa (icp_color_kappa, written below)
-    if ((rc = dalloc (h, &p.mom, B * 2 * 18 * p.nb + (icp_trim_words (batch, m) + 1u) / 2u + icp_p2pl_doubles (batch, m) + 1u))) return rc;
+    // (behind the moments, icp_mom_layout: trimming's words, the plane system and its block partials, the word of kappa (written below);
+    // zeroed: ICP_MEM_TRIM and ICP_MEM_PLANE_SYSTEM read 0 until an iteration has written them, and the histograms and counters start clear)
+    if ((rc = dalloc (h, &p.mom, icp_mom_layout_of (batch, m, p.nb).total))) return rc;
     if ((rc = write_color_kappa (h))) return rc;
     if ((rc = dalloc (h, &p.ml1, B * 18 * ((p.nb + 127u) / 128u)))) return rc;
     if ((rc = dalloc (h, &p.cst, B * 2))) return rc;
@@ -736,7 +734,7 @@ int icp_get_trimming (icp_handle h, float *keep_fraction) try
 ICP_CATCH_ALL
 // point-to-plane (include/icp_amd.h, icp_p2pl.hip).  On <-> off changes which kernels run — the moments and the 6 x 6 finalize, no
 // chained form —: the route of icp_set_reduce_mode (graphs captured anew).  A new mu while the metric stays on is a parameter update.
-// Colored ICP (icp_color.hip) is point-to-plane with other moments: POINT_TO_PLANE <-> COLORED changes the kernels too (same route).
+// Colored ICP is point-to-plane with other moments: POINT_TO_PLANE <-> COLORED changes the kernels too (same route).
 int icp_set_error_metric (icp_handle h, int metric, float point_weight) try
 {
     api_guard guard_ (h);

@@ -71,7 +71,7 @@ struct icp_params {
     float4 *LB;                  // [batch][3 * nlb]  6-D bounding boxes of the list chunks (16 consecutive positions of one list, chunk c >= 1 of list r at
                                  // index (O[r] >> 4) + c: k_list_boxes) as [lo.x lo.y lo.z lo.r | lo.g lo.b hi.x hi.y | hi.z hi.r hi.g hi.b]
     uint32_t nlb;                // m / 16 + 2 boxes per registration
-    uint32_t metric;             // ICP_METRIC_POINT_TO_POINT (0, the default), ICP_METRIC_POINT_TO_PLANE (icp_p2pl.hip) or ICP_METRIC_COLORED (icp_color.hip)
+    uint32_t metric;             // ICP_METRIC_POINT_TO_POINT (0, the default), ICP_METRIC_POINT_TO_PLANE or ICP_METRIC_COLORED (icp_p2pl.hip)
     uint32_t *rep_src, *owner, *N, *O, *perm, *chunk_hist;   // [batch][...]; N: [2][batch][nr] — [0] the length of a list AS THE SEARCH SCANS IT (k_search reads
                                  // p.N: a long list without the tail members that repeat an earlier member bit for bit, k_list_boxes), [1] = ICP_N_FULL: the list's
                                  // length N of the construction (RBCConstruct's output, ICP_MEM_RBC_N); the two differ for long lists with duplicates only
@@ -124,42 +124,69 @@ static_assert (sizeof (icp_params) == 480, "icp_params grew: the hidden kernel a
 static __host__ __device__ __forceinline__ bool icp_rejecting (const icp_params &p) { return p.reject != 0u; }
 static __host__ __device__ __forceinline__ bool icp_trimming (const icp_params &p) { return (p.reject & ICP_REJECT_TRIM_ON) != 0u; }
 
-// Trimming's device buffers lie behind the moment partials, in the same allocation (icp_params has no room for another pointer), as
-// uint32 words: [batch][4] the result of the last iteration (t bits, n, K, accepted: ICP_MEM_TRIM), [batch][4] the state of the
-// multi-block selection (prefix, rank left, count below, arrivals), [batch][2048] its histograms, and for sets beyond one workgroup's
-// selection [batch][m] the keys.
+// Trimming's buffers (icp_trim.hip) are uint32 words: [batch][4] the result of the last iteration (t bits, n, K, accepted: ICP_MEM_TRIM),
+// [batch][4] the state of the multi-block selection (prefix, rank left, count below, arrivals), [batch][2048] its histograms, and for
+// sets beyond one workgroup's selection [batch][m] the keys.
 #define ICP_TRIM_ONE_BLOCK_MAX 16384u    // up to this many pairs per registration: the selection is one workgroup's (k_trim_select)
 #define ICP_TRIM_BINS 2048u
-static inline size_t icp_trim_words (uint32_t batch, uint32_t m)
-{
-    return (size_t) batch * (8u + ICP_TRIM_BINS) + (m > ICP_TRIM_ONE_BLOCK_MAX ? (size_t) batch * m : 0u);
-}
-static inline uint32_t *icp_trim_area (const icp_params &p) { return reinterpret_cast<uint32_t *> (p.mom + (size_t) p.batch * 2 * 18 * p.nb); }
 
-// Point-to-plane ICP (icp_set_error_metric, icp_p2pl.hip).  NORMALS_F lies behind the permuted database XP, in the same allocation: it
-// belongs to the fixed frame as the RBC does, and a tracked handle's second RBC set (icp_track.hip) carries a second one with it.  The
-// solve's buffers lie behind trimming's, in the moments' allocation: [batch][28] ICP_MEM_PLANE_SYSTEM (A's upper triangle, b, status),
-// then [batch][27][icp_p2pl_nblk] the block partials of k_p2pl_moments.
+// The plane system (icp_set_error_metric, icp_p2pl.hip): point-to-plane ICP and colored ICP (ICP_METRIC_COLORED), the point-to-plane
+// system with a photometric term.  [batch][28] ICP_MEM_PLANE_SYSTEM (A's upper triangle, b, status), [batch][27][icp_p2pl_nblk] the
+// block partials of k_plane_moments.
 #define ICP_P2PL_BLOCK 256u      // pairs per block of the first tree level
 #define ICP_P2PL_TERMS 27u       // 21 upper-triangle terms of A, then the 6 of b
 #define ICP_P2PL_SYS 28u         // doubles of ICP_MEM_PLANE_SYSTEM per registration
-static __host__ __device__ __forceinline__ bool icp_p2pl (const icp_params &p) { return p.metric != 0u; }
-static __host__ __device__ __forceinline__ uint32_t icp_p2pl_nblk (uint32_t m) { return (m + ICP_P2PL_BLOCK - 1u) / ICP_P2PL_BLOCK; }
-static inline size_t icp_p2pl_doubles (uint32_t batch, uint32_t m) { return (size_t) batch * (ICP_P2PL_SYS + ICP_P2PL_TERMS * icp_p2pl_nblk (m)); }
-static __host__ __device__ __forceinline__ float4 *icp_normals_f (const icp_params &p) { return reinterpret_cast<float4 *> (p.XP + (size_t) p.batch * p.m * 8); }
-static inline double *icp_p2pl_area (const icp_params &p)
-{
-    return p.mom + (size_t) p.batch * 2 * 18 * p.nb + (icp_trim_words (p.batch, p.m) + 1u) / 2u;
-}
-
-// Colored ICP (ICP_METRIC_COLORED, icp_color.hip): the point-to-plane system with a photometric term.  COLOR_GRAD_F ([gx gy gz C] per
-// fixed point) lies behind NORMALS_F in the XP allocation (B m 16 floats in all), so each RBC set carries its own as it does its normals.
-// The weight kappa has no room in icp_params: it is a device word behind the point-to-plane buffers in the moments' allocation
-// (icp_color_kappa; icp_set_color_weight writes it in stream order), which the run graphs read instead of capturing it.
 #define ICP_METRIC_COLORED_ 2u
+static __host__ __device__ __forceinline__ bool icp_p2pl (const icp_params &p) { return p.metric != 0u; }
 static __host__ __device__ __forceinline__ bool icp_colored (const icp_params &p) { return p.metric == ICP_METRIC_COLORED_; }
-static __host__ __device__ __forceinline__ float4 *icp_color_grad_f (const icp_params &p) { return reinterpret_cast<float4 *> (p.XP + (size_t) p.batch * p.m * 12); }
-static inline float *icp_color_kappa (const icp_params &p) { return reinterpret_cast<float *> (icp_p2pl_area (p) + icp_p2pl_doubles (p.batch, p.m)); }
+static __host__ __device__ __forceinline__ uint32_t icp_p2pl_nblk (uint32_t m) { return (m + ICP_P2PL_BLOCK - 1u) / ICP_P2PL_BLOCK; }
+
+// The moments' allocation p.mom, offsets in doubles.  icp_params has no room for more pointers, so everything the opt-in paths keep per
+// iteration lies behind the fused mode's moment partials: trimming's words, the plane system and its block partials, and colored ICP's
+// weight kappa, a device word (icp_set_color_weight writes it in stream order) that the run graphs read instead of capturing it.
+struct icp_mom_layout {
+    size_t trim;                 // trimming's uint32 words (icp_trim_area)
+    size_t sys;                  // [batch][ICP_P2PL_SYS] ICP_MEM_PLANE_SYSTEM (icp_p2pl_area)
+    size_t part;                 // [batch][ICP_P2PL_TERMS][icp_p2pl_nblk] the plane system's block partials (icp_p2pl_part)
+    size_t kappa;                // the float word of kappa (icp_color_kappa)
+    size_t total;
+};
+static inline icp_mom_layout icp_mom_layout_of (uint32_t batch, uint32_t m, uint32_t nb)
+{
+    const size_t B = batch, trim_words = B * (8u + ICP_TRIM_BINS) + (m > ICP_TRIM_ONE_BLOCK_MAX ? B * m : 0u);
+    icp_mom_layout l;
+    l.trim = B * 2 * 18 * nb;                            // behind [batch][2][18][nb], the fused mode's moment partials
+    l.sys = l.trim + (trim_words + 1u) / 2u;
+    l.part = l.sys + B * ICP_P2PL_SYS;
+    l.kappa = l.part + B * ICP_P2PL_TERMS * icp_p2pl_nblk (m);
+    l.total = l.kappa + 1u;
+    return l;
+}
+static inline icp_mom_layout icp_mom_layout_of (const icp_params &p) { return icp_mom_layout_of (p.batch, p.m, p.nb); }
+static inline uint32_t *icp_trim_area (const icp_params &p) { return reinterpret_cast<uint32_t *> (p.mom + icp_mom_layout_of (p).trim); }
+static inline double *icp_p2pl_area (const icp_params &p) { return p.mom + icp_mom_layout_of (p).sys; }
+static inline double *icp_p2pl_part (const icp_params &p) { return p.mom + icp_mom_layout_of (p).part; }
+static inline float *icp_color_kappa (const icp_params &p) { return reinterpret_cast<float *> (p.mom + icp_mom_layout_of (p).kappa); }
+
+// The XP allocation of one RBC set, offsets in floats: [batch][m][8] the permuted database, then [batch][m] float4 NORMALS_F and
+// [batch][m] float4 COLOR_GRAD_F ([gx gy gz C] per fixed point).  The normals and gradients belong to the fixed frame as the RBC does,
+// so a tracked handle's second RBC set (icp_track.hip) carries its own with it.
+struct icp_xp_layout {
+    size_t normals, color_grad, total;
+};
+static __host__ __device__ __forceinline__ icp_xp_layout icp_xp_layout_of (uint32_t batch, uint32_t m)
+{
+    const size_t n = (size_t) batch * m;
+    return { n * 8, n * 12, n * 16 };
+}
+static __host__ __device__ __forceinline__ float4 *icp_normals_f (const icp_params &p)
+{
+    return reinterpret_cast<float4 *> (p.XP + icp_xp_layout_of (p.batch, p.m).normals);
+}
+static __host__ __device__ __forceinline__ float4 *icp_color_grad_f (const icp_params &p)
+{
+    return reinterpret_cast<float4 *> (p.XP + icp_xp_layout_of (p.batch, p.m).color_grad);
+}
 
 #define ICP_N_FULL(p, b) ((p).N + ((size_t) (p).batch + (b)) * (p).nr)
 
@@ -242,11 +269,9 @@ void icp_launch_search_rej (const icp_params &p, hipStream_t s);            // i
 void icp_launch_chain_one_rej (const icp_params &p, hipStream_t s, uint32_t j, bool fresh, bool emit);
 void icp_launch_trim (const icp_params &p, hipStream_t s);                   // icp_trim.hip: k_trim_select (one or three launches) + k_trim_apply
 uint32_t icp_trim_launches (const icp_params &p);                             // how many that is
-void icp_launch_p2pl_solve (const icp_params &p, hipStream_t s);             // icp_p2pl.hip: k_p2pl_moments + k_p2pl_finalize (point-to-plane)
-void icp_launch_normals_grid (const icp_params &p, hipStream_t s);           // icp_p2pl.hip: k_normals_grid (ICP_NORMALS_GRID, behind buildRBC)
-#define ICP_P2PL_LAUNCHES 2u                                                  // launches of icp_launch_p2pl_solve (colored: the same count)
-void icp_launch_color_moments (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);   // icp_color.hip: k_color_moments
-void icp_launch_color_grad_grid (const icp_params &p, hipStream_t s);      // icp_color.hip: k_color_grad_grid (colored + ICP_NORMALS_GRID)
+void icp_launch_p2pl_solve (const icp_params &p, hipStream_t s);             // icp_p2pl.hip: k_plane_moments<colored?> + k_p2pl_finalize
+void icp_launch_normals_grid (const icp_params &p, hipStream_t s);           // icp_p2pl.hip: k_normals_grid (+ colored: k_color_grad_grid), behind buildRBC
+#define ICP_P2PL_LAUNCHES 2u                                                  // launches of icp_launch_p2pl_solve
 void icp_launch_owner_search_dense (const icp_params &p, hipStream_t s);
 uint32_t icp_tbox_of (const icp_params &p);
 uint32_t icp_s2_wave_of (const icp_params &p);

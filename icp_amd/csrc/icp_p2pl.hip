@@ -1,32 +1,78 @@
-// icp_p2pl.hip — point-to-plane ICP (icp_set_error_metric, icp_set_normals: include/icp_amd.h states the rule).
+// icp_p2pl.hip — the plane system: point-to-plane ICP (icp_set_error_metric, icp_set_normals) and colored ICP (ICP_METRIC_COLORED,
+// icp_set_color_weight; Park, Zhou, Koltun 2017).  include/icp_amd.h states both rules.
 //
-// An iteration with the metric on is: the search stage (icp_launch_search_stage), which stores PF (matched fixed xyz, weight) and PM
-// (transformed moving xyz) every time — rejection and trimming have put their zeros into PF.w already —; k_p2pl_moments, the 27 terms
-// of the linearised 6 x 6 system per pair in double and their tree over blocks of ICP_P2PL_BLOCK pairs; k_p2pl_finalize, one workgroup
-// per registration: the tree over the block partials, LDL^T in one lane, the increment composed with icp_compose's arithmetic and checked with
-// icp_check_converged.  k_normals_grid computes NORMALS_F from F behind buildRBC (ICP_NORMALS_GRID).  None of the existing kernels
-// carries any of this code; the translation unit is built with -ffp-contract=off like every other, so each expression below is evaluated
-// exactly in the order it is written.
+// An iteration with either metric on is: the search stage (icp_launch_search_stage), which stores PF (matched fixed xyz, weight) and PM
+// (transformed moving xyz) every time — rejection and trimming have put their zeros into PF.w already —; k_plane_moments<COLORED>, the
+// 27 terms of the linearised 6 x 6 system per pair in double (colored: plus kappa times a photometric term) and their tree over blocks
+// of ICP_P2PL_BLOCK pairs; k_p2pl_finalize, one workgroup per registration: the tree over the block partials, LDL^T in one lane, the
+// increment composed with icp_compose's arithmetic and checked with icp_check_converged.  k_normals_grid computes NORMALS_F from F
+// behind buildRBC (ICP_NORMALS_GRID), and with the colored metric k_color_grad_grid computes COLOR_GRAD_F behind it.  None of the
+// point-to-point kernels carries any of this code; the translation unit is built with -ffp-contract=off like every other, so each
+// expression below is evaluated exactly in the order it is written.
 #include "icp_kernels.h"
 
 namespace {
 
-// a grid point takes part in a difference when its xyz is finite and not the origin (a Kinect pixel without depth)
-__device__ __forceinline__ bool nrm_valid (float3 v)
+// a grid point takes part in a difference or a gradient when its xyz is finite and not the origin (a Kinect pixel without depth)
+__device__ __forceinline__ bool grid_valid (float x, float y, float z)
 {
-    return isfinite (v.x) && isfinite (v.y) && isfinite (v.z) && !(v.x == 0.f && v.y == 0.f && v.z == 0.f);
+    return isfinite (x) && isfinite (y) && isfinite (z) && !(x == 0.f && y == 0.f && z == 0.f);
 }
+
+// the intensity of a landmark [x y z 1 r g b 1], fp32
+__device__ __forceinline__ float intensity (float r, float g, float b) { return ((r + g) + b) / 3.f; }
 
 __device__ __forceinline__ float3 nrm_sub (float3 a, float3 b) { return make_float3 (a.x - b.x, a.y - b.y, a.z - b.z); }
 
 // the difference along one grid axis: central if both neighbours are valid, else one-sided against the centre (the next neighbour first)
 __device__ __forceinline__ bool nrm_diff (float3 prev, bool has_prev, float3 c, float3 next, bool has_next, float3 &d)
 {
-    const bool vp = has_prev && nrm_valid (prev), vn = has_next && nrm_valid (next);
+    const bool vp = has_prev && grid_valid (prev.x, prev.y, prev.z), vn = has_next && grid_valid (next.x, next.y, next.z);
     if (vp && vn) d = nrm_sub (next, prev);
     else if (vn) d = nrm_sub (next, c);
     else if (vp) d = nrm_sub (c, prev);
     return vp || vn;
+}
+
+// A x = bb for a symmetric N x N A by LDL^T, column by column:  e_jk = L_jk d_k;  d_j = A_jj - e_j0 L_j0 - .. - e_j(j-1) L_j(j-1)
+// (subtracted in order k = 0, 1, ..);  L_ij = (A_ij - L_i0 e_j0 - .. - L_i(j-1) e_j(j-1)) / d_j for i > j.  Then L y = bb (y_i = bb_i -
+// L_i0 y_0 - .. in order), z = y / d, L^T x = z (x_i = z_i - L_(i+1)i x_(i+1) - .. - L_(N-1)i x_(N-1), ascending k).  ok = false
+// (singular) when a pivot is not finite or d_j <= 1e-12 A_jj; x is computed either way.
+template <int N>
+__device__ __forceinline__ void ldlt_solve (const double (&A)[N][N], const double (&bb)[N], double (&x)[N], bool &ok)
+{
+    double L[N][N], E[N][N], d[N], y[N];
+    ok = true;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        double v = A[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) v = v - E[j][k] * L[j][k];
+        d[j] = v;
+        if (!isfinite (v) || v <= 1e-12 * A[j][j]) ok = false;
+#pragma unroll
+        for (int i = j + 1; i < N; ++i) {
+            double u = A[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) u = u - L[i][k] * E[j][k];
+            L[i][j] = u / v;
+            E[i][j] = L[i][j] * v;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        double u = bb[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) u = u - L[i][k] * y[k];
+        y[i] = u;
+    }
+#pragma unroll
+    for (int i = N - 1; i >= 0; --i) {
+        double u = y[i] / d[i];
+#pragma unroll
+        for (int k = i + 1; k < N; ++k) u = u - L[k][i] * x[k];
+        x[i] = u;
+    }
 }
 
 }  // namespace
@@ -48,7 +94,7 @@ __global__ __launch_bounds__ (256) void k_normals_grid (icp_params p, float4 *nr
     const float3 zero = dh;
     // (i + 1 < m, y + 1 < H: no read beyond the set even if the width did not divide m — the host refuses that, ICP_ESTATE)
     const bool hasl = x > 0u, hasr = x + 1u < W && i + 1u < p.m, hasu = y > 0u, hasd = y + 1u < H;
-    if (nrm_valid (c) &&
+    if (grid_valid (c.x, c.y, c.z) &&
         nrm_diff (hasl ? at (i - 1u) : zero, hasl, c, hasr ? at (i + 1u) : zero, hasr, dh) &&
         nrm_diff (hasu ? at (i - W) : zero, hasu, c, hasd ? at (i + W) : zero, hasd, dv)) {
         const float cx = dh.y * dv.z - dh.z * dv.y, cy = dh.z * dv.x - dh.x * dv.z, cz = dh.x * dv.y - dh.y * dv.x;
@@ -62,8 +108,66 @@ __global__ __launch_bounds__ (256) void k_normals_grid (icp_params p, float4 *nr
     nrm[(size_t) b * p.m + i] = n;
 }
 
-// The 27 terms of pair i in double (include/icp_amd.h; tests/p2pl_ref.py restates them), w = PF.w, P = PM.xyz, Q = PF.xyz, N =
-// NORMALS_F[NN_ID.id] (a non-finite normal counts as zero), all converted from float first:
+// COLOR_GRAD_F of the fixed set, F read as a row-major grid p.nrm_grid wide (m % width == 0: the host checks it), n = NORMALS_F just
+// computed.  One thread per point, grid.y = registration.  For a valid centre p with n != 0, over the valid points p' of the 3 x 3
+// window (row-major, the centre excluded), in double from the float inputs:
+//   v = p' - p,  vn = (vx nx + vy ny) + vz nz,  u = v - vn n (componentwise: vx - vn nx, ..),  dC = C(p') - C(p),
+//   A_ab = A_ab + u_a u_b  (A00, A01, A02, A11, A12, A22),   b_a = b_a + u_a dC,   K = K + 1      (window order, from zeros)
+// then with k = K, kn = (k nx, k ny, k nz):  A_ab = A_ab + kn_a kn_b;  ldlt_solve<3>, x rounded to float once.  g = 0 when K < 3, the
+// centre is invalid, n = 0 or a pivot fails; .w = C(p) always.
+__global__ __launch_bounds__ (256) void k_color_grad_grid (icp_params p, const float4 *nrm, float4 *grad)
+{
+    const uint32_t b = blockIdx.y, i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= p.m) return;
+    const uint32_t W = p.nrm_grid, x = i % W, y = i / W, H = p.m / W;
+    const float *F = p.F + (size_t) b * p.m * 8;
+    const float *c = F + (size_t) i * 8;
+    const float cx = c[0], cy = c[1], cz = c[2], Cc = intensity (c[4], c[5], c[6]);
+    const float4 n = nrm[(size_t) b * p.m + i];
+    float4 out = make_float4 (0.f, 0.f, 0.f, Cc);
+    if (grid_valid (cx, cy, cz) && !(n.x == 0.f && n.y == 0.f && n.z == 0.f)) {
+        const double nx = (double) n.x, ny = (double) n.y, nz = (double) n.z;
+        const double px = (double) cx, py = (double) cy, pz = (double) cz, pc = (double) Cc;
+        double A00 = 0.0, A01 = 0.0, A02 = 0.0, A11 = 0.0, A12 = 0.0, A22 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0;
+        uint32_t K = 0u;
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                if (dx == 0 && dy == 0) continue;
+                const int xx = (int) x + dx, yy = (int) y + dy;
+                if (xx < 0 || xx >= (int) W || yy < 0 || yy >= (int) H) continue;
+                const uint32_t j = (uint32_t) yy * W + (uint32_t) xx;
+                if (j >= p.m) continue;                      // (no read beyond the set even if the width did not divide m)
+                const float *q = F + (size_t) j * 8;
+                const float qx = q[0], qy = q[1], qz = q[2];
+                if (!grid_valid (qx, qy, qz)) continue;
+                const double vx = (double) qx - px, vy = (double) qy - py, vz = (double) qz - pz;
+                const double vn = (vx * nx + vy * ny) + vz * nz;
+                const double ux = vx - vn * nx, uy = vy - vn * ny, uz = vz - vn * nz;
+                const double dC = (double) intensity (q[4], q[5], q[6]) - pc;
+                A00 = A00 + ux * ux; A01 = A01 + ux * uy; A02 = A02 + ux * uz;
+                A11 = A11 + uy * uy; A12 = A12 + uy * uz; A22 = A22 + uz * uz;
+                b0 = b0 + ux * dC; b1 = b1 + uy * dC; b2 = b2 + uz * dC;
+                ++K;
+            }
+        }
+        if (K >= 3u) {
+            const double k = (double) K, kx = k * nx, ky = k * ny, kz = k * nz;
+            A00 = A00 + kx * kx; A01 = A01 + kx * ky; A02 = A02 + kx * kz;
+            A11 = A11 + ky * ky; A12 = A12 + ky * kz; A22 = A22 + kz * kz;
+            const double A[3][3] = { { A00, A01, A02 }, { A01, A11, A12 }, { A02, A12, A22 } }, bb[3] = { b0, b1, b2 };
+            double xv[3];
+            bool ok;
+            ldlt_solve (A, bb, xv, ok);
+            if (ok) { out.x = (float) xv[0]; out.y = (float) xv[1]; out.z = (float) xv[2]; }
+        }
+    }
+    grad[(size_t) b * p.m + i] = out;
+}
+
+// The 27 terms of pair i in double (include/icp_amd.h; tests/p2pl_ref.py and tests/colored_ref.py restate them), w = PF.w, P = PM.xyz,
+// Q = PF.xyz, N = NORMALS_F[NN_ID.id] (a non-finite normal counts as zero), all converted from float first:
 //   c = P x N: (py nz - pz ny, pz nx - px nz, px ny - py nx)       J = (c, N)
 //   d = Q - P (componentwise)     r = (dx nx + dy ny) + dz nz      pp = (px px + py py) + pz pz
 //   G = [[pp I - P P^T, [P]x], [-[P]x, I]]: G00 = pp - px px, G01 = -(px py), G02 = -(px pz), G11 = pp - py py, G12 = -(py pz),
@@ -71,15 +175,26 @@ __global__ __launch_bounds__ (256) void k_normals_grid (icp_params p, float4 *nr
 //       G33 = G44 = G55 = 1, G34 = G35 = G45 = 0
 //   g = (P x Q, d): P x Q = (py qz - pz qy, pz qx - px qz, px qy - py qx)
 //   term (a, b), a <= b, row-major:  w (J_a J_b + mu G_ab)         term 21 + a:  w (J_a r + mu g_a)
+// COLORED adds the photometric terms: (d, C_Q) = grad[NN_ID.id] (COLOR_GRAD_F; a non-finite d counts as zero), C_P = the intensity of
+// M[i] (fp32), kappa = *kappa_word (icp_color_kappa):
+//   dn = (dx nx + dy ny) + dz nz,  t = d - dn N (componentwise: dx - dn nx, ..)          (the gradient in Q's tangent plane)
+//   J_C = (P x t, t): (py tz - pz ty, pz tx - px tz, px ty - py tx, tx, ty, tz)
+//   e = P - Q (componentwise),  r_C = C_P - (C_Q + ((tx ex + ty ey) + tz ez))
+//   term (a, b), a <= b:  w ((J_a J_b + mu G_ab) + kappa (J_Ca J_Cb))        term 21 + a:  w ((J_a r + mu g_a) + kappa (J_Ca r_C))
 // w == 0 (no query, rejected, trimmed) selects exact zeros.  Then the halving tree over the block's ICP_P2PL_BLOCK pairs,
 // x[i] += x[i + h] for h = 128 .. 1 (lanes: h = 32 .. 1 pair lane i with lane i + h, the same additions).
-__global__ __launch_bounds__ (256) void k_p2pl_moments (icp_params p, const float4 *nrm, double *part, uint32_t nblk)
+template <bool COLORED>
+__global__ __launch_bounds__ (256) void k_plane_moments (icp_params p, const float4 *nrm, double *part, uint32_t nblk, const float4 *grad,
+                                                         const float *kappa_word)
 {
     const uint32_t b = blockIdx.y, tid = threadIdx.x, i = blockIdx.x * ICP_P2PL_BLOCK + tid;
     const size_t o = (size_t) b * p.m;
     const uint32_t ic = min (i, p.m - 1u);
     const float4 f = p.PF[o + ic], q = p.PM[o + ic];
     const uint32_t id = p.nn_id[o + ic].id;
+    // (colored: (r, g, b, 1) of the moving landmark, and kappa)
+    const float4 mc = COLORED ? *reinterpret_cast<const float4 *> (p.M + (o + ic) * 8 + 4) : make_float4 (0.f, 0.f, 0.f, 0.f);
+    const float kap = COLORED ? *kappa_word : 0.f;
     // (a converged registration: asked behind the pair's loads — in front of them the flag's round trip would come first)
     if (p.check && p.st[b].done) return;                 // (block-uniform)
     double v[ICP_P2PL_TERMS];
@@ -104,13 +219,34 @@ __global__ __launch_bounds__ (256) void k_p2pl_moments (icp_params p, const floa
                                    1.0, 0.0,
                                    1.0 };
             const double g[6] = { py * qz - pz * qy, pz * qx - px * qz, px * qy - py * qx, dx, dy, dz };
+            double kappa = 0.0, JC[6] = {}, rc = 0.0;
+            if constexpr (COLORED) {
+                float4 gf = id < p.m ? grad[o + id] : make_float4 (0.f, 0.f, 0.f, 0.f);
+                if (!(isfinite (gf.x) && isfinite (gf.y) && isfinite (gf.z))) { gf.x = 0.f; gf.y = 0.f; gf.z = 0.f; }
+                kappa = (double) kap;
+                const double gx = (double) gf.x, gy = (double) gf.y, gz = (double) gf.z, cq = (double) gf.w;
+                const double cp = (double) intensity (mc.x, mc.y, mc.z);
+                const double dn = (gx * nx + gy * ny) + gz * nz;
+                const double tx = gx - dn * nx, ty = gy - dn * ny, tz = gz - dn * nz;
+                JC[0] = py * tz - pz * ty; JC[1] = pz * tx - px * tz; JC[2] = px * ty - py * tx; JC[3] = tx; JC[4] = ty; JC[5] = tz;
+                const double ex = px - qx, ey = py - qy, ez = pz - qz;
+                rc = cp - (cq + ((tx * ex + ty * ey) + tz * ez));
+            }
             int t = 0;
 #pragma unroll
             for (int a = 0; a < 6; ++a)
 #pragma unroll
-                for (int c = a; c < 6; ++c, ++t) v[t] = w * (J[a] * J[c] + mu * G[t]);
+                for (int c = a; c < 6; ++c, ++t) {
+                    double x = J[a] * J[c] + mu * G[t];
+                    if constexpr (COLORED) x = x + kappa * (JC[a] * JC[c]);
+                    v[t] = w * x;
+                }
 #pragma unroll
-            for (int a = 0; a < 6; ++a) v[21 + a] = w * (J[a] * r + mu * g[a]);
+            for (int a = 0; a < 6; ++a) {
+                double x = J[a] * r + mu * g[a];
+                if constexpr (COLORED) x = x + kappa * (JC[a] * rc);
+                v[21 + a] = w * x;
+            }
         }
     }
     __shared__ double s[ICP_P2PL_TERMS][128];
@@ -146,7 +282,7 @@ __global__ __launch_bounds__ (256) void k_p2pl_moments (icp_params p, const floa
 #define P2PL_LDS 4096u           // doubles of the finalize's tree buffer (nblk <= 4096: m <= 2^20)
 
 // One workgroup per registration: the halving tree over the block partials zero-padded to P = 2^ceil(log2 nblk), as many terms at a time
-// as the LDS buffer holds; then lane 0: LDL^T, the increment, the composition and the check.
+// as the LDS buffer holds; then lane 0: ldlt_solve<6>, the increment, the composition and the check.
 __global__ __launch_bounds__ (256) void k_p2pl_finalize (icp_params p, const double *part, double *sys, uint32_t nblk, uint32_t P)
 {
     const uint32_t b = blockIdx.x, tid = threadIdx.x;
@@ -204,42 +340,9 @@ __global__ __launch_bounds__ (256) void k_p2pl_finalize (icp_params p, const dou
 #pragma unroll
         for (int a = 0; a < 6; ++a) bb[a] = s_sum[21 + a];
     }
-    // LDL^T, column by column:  e_jk = L_jk d_k;  d_j = A_jj - e_j0 L_j0 - .. - e_j(j-1) L_j(j-1)  (subtracted in order k = 0, 1, ..);
-    // L_ij = (A_ij - L_i0 e_j0 - .. - L_i(j-1) e_j(j-1)) / d_j for i > j.  A pivot that is not finite or d_j <= 1e-12 A_jj: singular.
-    double L[6][6], E[6][6], d[6];
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double v = A[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) v = v - E[j][k] * L[j][k];
-        d[j] = v;
-        if (!isfinite (v) || v <= 1e-12 * A[j][j]) ok = false;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double u = A[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) u = u - L[i][k] * E[j][k];
-            L[i][j] = u / v;
-            E[i][j] = L[i][j] * v;
-        }
-    }
-    // L y = b (y_i = b_i - L_i0 y_0 - .. in order), z = y / d, L^T x = z (x_i = z_i - L_(i+1)i x_(i+1) - .. - L_5i x_5, ascending k)
-    double y[6], x[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double u = bb[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) u = u - L[i][k] * y[k];
-        y[i] = u;
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double u = y[i] / d[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) u = u - L[k][i] * x[k];
-        x[i] = u;
-    }
+    double x[6];
+    bool ok;
+    ldlt_solve (A, bb, x, ok);
 
     double *sb = sys + (size_t) b * ICP_P2PL_SYS;
 #pragma unroll
@@ -276,15 +379,18 @@ void icp_launch_p2pl_solve (const icp_params &p, hipStream_t s)
 {
     const uint32_t nblk = icp_p2pl_nblk (p.m);
     uint32_t P = 1u; while (P < nblk) P <<= 1;
-    double *sys = icp_p2pl_area (p), *part = sys + (size_t) p.batch * ICP_P2PL_SYS;
-    // (colored ICP: its moments write the same partials, icp_color.hip; the finalize is this one)
-    if (icp_colored (p)) icp_launch_color_moments (p, s, part, nblk);
-    else hipLaunchKernelGGL (k_p2pl_moments, dim3 (nblk, p.batch), dim3 (ICP_P2PL_BLOCK), 0, s, p, (const float4 *) icp_normals_f (p), part, nblk);
+    double *sys = icp_p2pl_area (p), *part = icp_p2pl_part (p);
+    const float4 *nrm = icp_normals_f (p), *grad = icp_color_grad_f (p);
+    const float *kappa = icp_color_kappa (p);
+    if (icp_colored (p)) hipLaunchKernelGGL (k_plane_moments<true>, dim3 (nblk, p.batch), dim3 (ICP_P2PL_BLOCK), 0, s, p, nrm, part, nblk, grad, kappa);
+    else hipLaunchKernelGGL (k_plane_moments<false>, dim3 (nblk, p.batch), dim3 (ICP_P2PL_BLOCK), 0, s, p, nrm, part, nblk, grad, kappa);
     hipLaunchKernelGGL (k_p2pl_finalize, dim3 (p.batch), dim3 (256), 0, s, p, (const double *) part, sys, nblk, P);
 }
 
 void icp_launch_normals_grid (const icp_params &p, hipStream_t s)
 {
-    hipLaunchKernelGGL (k_normals_grid, dim3 ((p.m + 255u) / 256u, p.batch), dim3 (256), 0, s, p, icp_normals_f (p));
-    if (icp_colored (p)) icp_launch_color_grad_grid (p, s);          // (the intensity gradients need the normals just computed)
+    const dim3 grid ((p.m + 255u) / 256u, p.batch);
+    hipLaunchKernelGGL (k_normals_grid, grid, dim3 (256), 0, s, p, icp_normals_f (p));
+    // (the intensity gradients need the normals just computed)
+    if (icp_colored (p)) hipLaunchKernelGGL (k_color_grad_grid, grid, dim3 (256), 0, s, p, (const float4 *) icp_normals_f (p), icp_color_grad_f (p));
 }

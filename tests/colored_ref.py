@@ -1,6 +1,6 @@
 """Colored ICP restated in numpy (the rule of include/icp_amd.h: ICP_METRIC_COLORED, icp_set_color_weight).
 
-Every function follows the engine's expression order so that the results are bit for bit those of icp_color.hip:
+Every function follows the engine's expression order so that the results are bit for bit those of icp_p2pl.hip:
   - intensity:  C = ((r + g) + b) / 3 in float32;
   - grid_gradients:  COLOR_GRAD_F of ICP_NORMALS_GRID, the 3 x 3 least squares in float64 and its LDL^T, rounded to float32 once;
   - photometric:  d in Q's tangent plane, J_C and r_C of a pair in float64;

@@ -1,7 +1,7 @@
 """Colored ICP without a device: argument validation of the C-ABI, the enum values, the header as C, the C++ facade's and ICPReg's
-setters, both command lines, the compiler's resources of the new kernels, and two independent checks of the numpy restatement
-(tests/colored_ref.py): grid gradients of a linear intensity ramp on a tilted plane, and J_C against a finite difference of r_C.
-(tests/test_gpu_colored_icp.py checks the engine against the restatement.)"""
+setters, both command lines, and two independent checks of the numpy restatement (tests/colored_ref.py): grid gradients of a linear
+intensity ramp on a tilted plane, and J_C against a finite difference of r_C.  (tests/test_gpu_colored_icp.py checks the engine
+against the restatement; tests/test_point_to_plane_cpu.py checks the compiler's resources of the plane kernels, colored ones included.)"""
 import ctypes as C
 import math
 import os
@@ -14,7 +14,6 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import colored_ref as cref                                 # noqa: E402
 import p2pl_ref as ref                                      # noqa: E402
-from kernel_resources import kernel_resources               # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -112,14 +111,6 @@ def test_example_command_line_accepts_the_option():
     for bad in ("-1", "nan", "inf"):
         r = subprocess.run([exe, "--colored", bad], capture_output=True, text=True, cwd=ROOT)
         assert r.returncode == 2 and "--colored: KAPPA must be finite and >= 0" in r.stderr, (bad, r.stderr)
-
-
-def test_color_kernels_have_zero_scratch():
-    res = dict(kernel_resources("icp_amd/csrc/icp_color.hip"))
-    names = sorted(res)
-    assert names == ["k_color_grad_grid", "k_color_moments"], names
-    for n in names:
-        assert res[n]["scratch"] == 0 and res[n]["dynamic_stack"] == "False", (n, res[n])
 
 
 # ---- (a) grid gradients of a linear intensity ramp on a tilted plane

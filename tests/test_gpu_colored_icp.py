@@ -3,6 +3,7 @@
 Every iteration is checked teacher-forced, as tests/test_gpu_point_to_plane.py does for point-to-plane: the restatement takes the
 engine's own search outputs of that iteration (NN, QT, NN_ID), its NORMALS_F, COLOR_GRAD_F and moving landmarks and the transform
 before the step, and must give the same PLANE_SYSTEM, T, R, TK and RK bits."""
+import functools
 import os
 import sys
 
@@ -12,32 +13,14 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import colored_ref as cref                                      # noqa: E402
 import p2pl_ref as ref                                          # noqa: E402
+import test_gpu_point_to_plane as p2pl                          # noqa: E402
 from test_gpu_parity import A, C_, assert_bits                  # noqa: E402
+from test_gpu_point_to_plane import (COLORED, GIVEN, GRID, P2P, P2PL, REGULAR, SIZES, WEIGHTED, _errors,   # noqa: E402
+                                     _messy_grid, _register, load)
 
 pytestmark = pytest.mark.gpu
 
-POWER, EIGEN = 1, 0
-REGULAR, WEIGHTED = 0, 1
-P2P, P2PL, COLORED = 0, 1, 2
-GIVEN, GRID = 0, 1
-SIZES = {"small": (32, 64), "A": (128, 256), "B": (256, 1024)}
-
-
-def make(engine, side, nr, weighted=WEIGHTED, rot=POWER, mu=0.05, kappa=1000.0, normals=GRID, fused=True, power_fast=True, batch=1,
-         max_iterations=40):
-    g = engine.ICP(0, rot, weighted)
-    g.init(side * side, nr, A, C_, max_iterations, batch=batch)
-    g.setPowerMode(engine.PowerMode.SQUARED if power_fast else engine.PowerMode.LITERAL)
-    g.setReduceMode(engine.ReduceMode.FUSED if fused else engine.ReduceMode.REFERENCE_ORDER)
-    g.set_normals(normals, side if normals == GRID else 0)
-    g.set_color_weight(kappa)
-    g.set_error_metric(COLORED, mu)
-    return g
-
-
-def load(engine, g, F, M, b=0):
-    g.write(engine.Memory.F, F, batch_index=b)
-    g.write(engine.Memory.M, M, batch_index=b)
+make = functools.partial(p2pl.make, metric=COLORED)          # (kappa 1000 unless given)
 
 
 def check_step(engine, g, mu, kappa, b=0):
@@ -60,19 +43,6 @@ def check_last(engine, g, mu, kappa, T0, R0, b=0):
     assert_bits(g.read(Mem.RK, b).ravel(), Rk, "RK (registration %d)" % b)
     assert g.state(b).power_iterations == 0
     return system
-
-
-def _messy_grid(engine, side, seed):
-    F, _ = engine.synth_pair(side, seed=seed)
-    F = engine.punch_holes(F, side, side, engine.HOLES_CONTIGUOUS, 0.15, True, seed=seed)
-    F = engine.punch_holes(F, side, side, engine.HOLES_SCATTERED, 0.05, True, seed=seed + 1)
-    rng = np.random.default_rng(seed)
-    idx = rng.choice(side * side, 40, replace=False)
-    F[idx[:10], 0] = np.nan
-    F[idx[10:20], 1] = np.inf
-    F[idx[20:30], 2] = -np.inf
-    F[idx[30:], :3] = 0.0
-    return F
 
 
 def grads_of(F, width):
@@ -444,27 +414,6 @@ def test_kappa_zero_is_point_to_plane(engine):
 
 
 # ---- 6. accuracy
-
-def _errors(engine, T, T_true):
-    from icp_amd import workloads as W
-    return W.rotation_error_deg(T, T_true), float(np.linalg.norm(T[4:7].astype(np.float64) - T_true[4:7]))
-
-
-def _register(engine, F, M, metric, mu=0.0, kappa=0.0):
-    g = engine.ICP(0)
-    g.init(F.shape[0], 256, A, C_)
-    if metric != P2P:
-        g.set_normals(GRID, int(round(np.sqrt(F.shape[0]))))
-        g.set_color_weight(kappa)
-        g.set_error_metric(metric, mu)
-    load(engine, g, F, M)
-    g.buildRBC()
-    k = g.run()
-    T = g.read(engine.Memory.T).copy()
-    conv = g.state().converged
-    g.close()
-    return T, k, conv
-
 
 KAPPAS = (0.0, 1e2, 1e3, 1e4)
 

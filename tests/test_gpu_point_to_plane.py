@@ -2,7 +2,9 @@
 
 Every iteration is checked teacher-forced: the restatement takes the engine's own search outputs of that iteration (NN, QT, NN_ID —
 stored every iteration with the metric on) and its transform before the step, and must give the same PLANE_SYSTEM, T, R, TK and RK
-bits.  The search itself is the unchanged one (tests/test_gpu_parity.py checks it against the oracle)."""
+bits.  The search itself is the unchanged one (tests/test_gpu_parity.py checks it against the oracle).
+
+make, load, _messy_grid, _errors and _register serve tests/test_gpu_colored_icp.py too (make and _register take the metric)."""
 import os
 import sys
 
@@ -17,20 +19,23 @@ pytestmark = pytest.mark.gpu
 
 POWER, EIGEN = 1, 0
 REGULAR, WEIGHTED = 0, 1
-P2PL, P2P = 1, 0
+P2P, P2PL, COLORED = 0, 1, 2
 GIVEN, GRID = 0, 1
 SIZES = {"small": (32, 64), "A": (128, 256), "B": (256, 1024)}
 IDENTITY8 = np.array([0, 0, 0, 1, 0, 0, 0, 1], np.float32)
 
 
 def make(engine, side, nr, weighted=WEIGHTED, rot=POWER, mu=0.05, normals=GRID, fused=True, power_fast=True, batch=1,
-         max_iterations=40):
+         max_iterations=40, metric=P2PL, kappa=1000.0):
+    """A handle with a plane metric on: P2PL, or COLORED with the weight kappa."""
     g = engine.ICP(0, rot, weighted)
     g.init(side * side, nr, A, C_, max_iterations, batch=batch)
     g.setPowerMode(engine.PowerMode.SQUARED if power_fast else engine.PowerMode.LITERAL)
     g.setReduceMode(engine.ReduceMode.FUSED if fused else engine.ReduceMode.REFERENCE_ORDER)
     g.set_normals(normals, side if normals == GRID else 0)
-    g.set_error_metric(P2PL, mu)
+    if metric == COLORED:
+        g.set_color_weight(kappa)
+    g.set_error_metric(metric, mu)
     return g
 
 
@@ -469,12 +474,14 @@ def _errors(engine, T, T_true):
     return W.rotation_error_deg(T, T_true), float(np.linalg.norm(T[4:7].astype(np.float64) - T_true[4:7]))
 
 
-def _register(engine, F, M, p2pl, mu=0.0):
+def _register(engine, F, M, metric, mu=0.0, kappa=0.0):
     g = engine.ICP(0)
     g.init(F.shape[0], 256, A, C_)
-    if p2pl:
+    if metric != P2P:
         g.set_normals(GRID, int(round(np.sqrt(F.shape[0]))))
-        g.set_error_metric(P2PL, mu)
+        if metric == COLORED:
+            g.set_color_weight(kappa)
+        g.set_error_metric(metric, mu)
     load(engine, g, F, M)
     g.buildRBC()
     k = g.run()
@@ -488,8 +495,8 @@ def test_accuracy_curved_scene(engine):
     """Scene 0, mu = 0 converges.  Measured on an MI355X: point-to-point 0.1251 deg / 8.810 mm in 36 iterations (the half-cell sampling
     offset of the moving frame), point-to-plane 0.0051 deg / 0.121 mm in 8; the bounds are more than twice the measured values."""
     F, M, T_true = engine.synth_pair_scene(128, engine.SCENE_CURVED)
-    Tp, kp, _ = _register(engine, F, M, False)
-    T, k, conv = _register(engine, F, M, True, 0.0)
+    Tp, kp, _ = _register(engine, F, M, P2P)
+    T, k, conv = _register(engine, F, M, P2PL, 0.0)
     (rp, tp), (r, t) = _errors(engine, Tp, T_true), _errors(engine, T, T_true)
     print("curved scene: point-to-point %.4f deg %.3f mm k=%d | point-to-plane mu=0 %.4f deg %.3f mm k=%d"
           % (rp, tp, kp, r, t, k))
@@ -503,12 +510,12 @@ def test_accuracy_wall_scene(engine):
     mu = 0 0.066 deg / 0.13 mm (k = 6: the wall's millimetre of roughness is geometry both frames share), mu = 1 0.053 deg / 8.14 mm.
     (With the scene's default motion, 3 degrees and 31 mm, no variant gets there in 40 iterations: DESIGN.md.)"""
     F, M, T_true = engine.synth_pair_scene(128, engine.SCENE_WALL, rot_deg=1.0, t=(8.0, -4.0, 5.0))
-    Tp, kp, _ = _register(engine, F, M, False)
+    Tp, kp, _ = _register(engine, F, M, P2P)
     (rp, tp) = _errors(engine, Tp, T_true)
     line = "wall scene: point-to-point %.4f deg %.3f mm k=%d" % (rp, tp, kp)
     res = {}
     for mu in (0.0, 0.05, 1.0):
-        T, k, conv = _register(engine, F, M, True, mu)
+        T, k, conv = _register(engine, F, M, P2PL, mu)
         res[mu] = _errors(engine, T, T_true) + (k, conv)
         line += " | point-to-plane mu=%g %.4f deg %.3f mm k=%d" % (mu, res[mu][0], res[mu][1], k)
     print(line)

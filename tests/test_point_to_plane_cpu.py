@@ -1,6 +1,6 @@
 """Point-to-plane ICP without a device: argument validation of the C-ABI, the header as C, the C++ facade's and ICPReg's setters,
-both command lines, the numpy restatement's solver and grid normals (tests/p2pl_ref.py), and the compiler's resources of the new
-kernels.  (tests/test_gpu_point_to_plane.py checks the engine against the restatement.)"""
+both command lines, the numpy restatement's solver and grid normals (tests/p2pl_ref.py), and the compiler's resources of the plane
+kernels (point-to-plane and colored).  (tests/test_gpu_point_to_plane.py checks the engine against the restatement.)"""
 import ctypes as C
 import os
 import subprocess
@@ -181,9 +181,10 @@ def test_grid_normals_of_a_tilted_plane():
     assert (ref.grid_normals(F[:side], side) == 0).all()
 
 
-def test_p2pl_kernels_have_zero_scratch():
+def test_plane_kernels_have_zero_scratch():
+    """The point-to-plane and colored kernels (one translation unit)."""
     res = dict(kernel_resources("icp_amd/csrc/icp_p2pl.hip"))
     names = sorted(res)
-    assert names == ["k_normals_grid", "k_p2pl_finalize", "k_p2pl_moments"], names
+    assert names == ["k_color_grad_grid", "k_normals_grid", "k_p2pl_finalize", "k_plane_moments<false>", "k_plane_moments<true>"], names
     for n in names:
         assert res[n]["scratch"] == 0 and res[n]["dynamic_stack"] == "False", (n, res[n])

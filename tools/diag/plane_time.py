@@ -1,11 +1,12 @@
-"""Diagnostic (not a test): microseconds per iteration of colored ICP (ICP_METRIC_COLORED) against point-to-plane and the default
-point-to-point iteration at A (16384 / 256), B (65536 / 1024) and A x 64, through the fixed-length run graphs bench.py times; and
-buildRBC back to back without normals, with grid normals (point-to-plane) and with grid normals and intensity gradients (colored).
+"""Diagnostic (not a test): microseconds per iteration of the plane metrics, colored ICP (ICP_METRIC_COLORED) and point-to-plane,
+against the default point-to-point iteration at A (16384 / 256), B (65536 / 1024) and A x 64, through the fixed-length run graphs
+bench.py times; and buildRBC back to back without normals, with grid normals (point-to-plane) and with grid normals and intensity
+gradients (colored).
 
-    python tools/diag/color_time.py [--only-colored] [--reps N]
+    python tools/diag/plane_time.py [--only {p2p,p2pl,colored}] [--reps N]
 
-Prints one line per configuration and one JSON line at the end.  Under `rocprofv3 --kernel-trace --stats` (--only-colored) the
-per-kernel table shows the search, k_color_moments, k_p2pl_finalize, k_normals_grid and k_color_grad_grid."""
+Prints one line per configuration and one JSON line at the end.  Under `rocprofv3 --kernel-trace --stats` (--only p2pl or colored)
+the per-kernel table shows the search, k_plane_moments, k_p2pl_finalize, k_normals_grid and (colored) k_color_grad_grid."""
 import argparse
 import json
 import os
@@ -55,13 +56,13 @@ def build_us(g, n=200):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
-    ap.add_argument("--only-colored", action="store_true")
+    ap.add_argument("--only", choices=sorted(METRICS), help="time this metric only")
     ap.add_argument("--reps", type=int, default=20)
     args = ap.parse_args()
     out = {}
     for name, (side, nr, batch) in CONFIGS.items():
         for mname, metric in METRICS.items():
-            if args.only_colored and mname != "colored":
+            if args.only and mname != args.only:
                 continue
             g = make(side, nr, batch, metric)
             us = per_iteration_us(g, 20, args.reps)
