@@ -309,6 +309,13 @@ class ReduceScan:
         self._chk(self._L.icp_rs_read(self._r, _p(out)))
         return out
 
+    def device_ptr(self, output=True):
+        """Device address of the input buffer (output=False) or of the output buffer every run writes (output=True):
+        the facade's get(D_IN / D_OUT), fixed for the object's lifetime."""
+        p = C.c_void_p()
+        self._chk(self._L.icp_rs_device_ptr(self._r, int(bool(output)), C.byref(p)))
+        return p.value
+
     def time(self, reps=100):
         us = C.c_float()
         self._chk(self._L.icp_rs_time(self._r, reps, C.byref(us)))

@@ -3,7 +3,8 @@
 // host src/ICP/algorithms.cpp:131-322) and Scan<INCLUSIVE|EXCLUSIVE,int> (kernels/scan_kernels.cl:67, 188, 296;
 // host :403-600).  Row-wise over a rows x cols array (cols a multiple of 4, as the reference requires).
 // SUM follows reduce_sum_f's tree exactly (oracle orc_reduce_sum_f): bit-identical sums; MIN/MAX and the
-// integer scans are exact in any order.
+// integer scans are exact in any order.  MIN has the reference's fmin semantics: NaN loses to any number, and a row
+// is NaN only when all of it is.
 #include "../../include/icp_amd.h"
 #include "icp_cguard.h"
 #include "icp_device.h"
@@ -31,6 +32,10 @@ __global__ __launch_bounds__ (64) void k_rs_sum_level (const float *in, uint32_t
     if (l == 0 && g < wgp) out[(size_t) row * wgp + g] = v;
 }
 
+// MAX over unsigned ints: the larger.  MIN over floats: fmin (kernels/reduce_kernels.cl:89-101), spelled as a select
+// so that NaN never survives a number in any of the three combine stages (a NaN v takes x; a NaN x never wins x < v)
+template <typename T, bool MAXOP> __device__ __forceinline__ T rs_pick (T x, T v) { return MAXOP ? (x > v ? x : v) : ((v != v || x < v) ? x : v); }
+
 template <typename T, bool MAXOP>
 __global__ __launch_bounds__ (256) void k_rs_minmax (const T *in, uint32_t cols, T *out)
 {
@@ -38,12 +43,12 @@ __global__ __launch_bounds__ (256) void k_rs_minmax (const T *in, uint32_t cols,
     const uint32_t row = blockIdx.x, t = threadIdx.x;
     const T *src = in + (size_t) row * cols;
     T v = src[min (t, cols - 1u)];
-    for (uint32_t c = t; c < cols; c += 256u) { T x = src[c]; v = MAXOP ? (x > v ? x : v) : (x < v ? x : v); }
-    for (int d = 32; d > 0; d >>= 1) { T x = __shfl_xor (v, d); v = MAXOP ? (x > v ? x : v) : (x < v ? x : v); }
+    for (uint32_t c = t; c < cols; c += 256u) v = rs_pick<T, MAXOP> (src[c], v);
+    for (int d = 32; d > 0; d >>= 1) v = rs_pick<T, MAXOP> (__shfl_xor (v, d), v);
     if ((t & 63u) == 0) s[t >> 6] = v;
     __syncthreads ();
     if (t == 0) {
-        for (int k = 1; k < 4; ++k) { T x = s[k]; v = MAXOP ? (x > v ? x : v) : (x < v ? x : v); }
+        for (int k = 1; k < 4; ++k) v = rs_pick<T, MAXOP> (s[k], v);
         out[row] = v;
     }
 }
@@ -85,8 +90,8 @@ struct icp_rs_context {
     uint32_t cols = 0, rows = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    void *din = nullptr, *dout = nullptr, *dtmp = nullptr;
-    const void *result = nullptr;                // where the last run left the rows results (SUM: ping-pong buffers)
+    void *din = nullptr, *dout = nullptr, *dtmp = nullptr;   // dout holds every run's result (SUM: dtmp is the other ping-pong buffer)
+    uint32_t levels = 0;                         // SUM: reduce_sum_f passes per run
     size_t out_bytes = 0;
 };
 
@@ -136,8 +141,12 @@ int icp_rs_create (icp_rs_handle *out, int device, int kind, uint32_t cols, uint
         r->out_bytes = (size_t) rows * 4;
         if (ok) RSCHK (hipMalloc (&r->dout, (size_t) rows * wgp0 * 4));
         if (ok) RSCHK (hipMalloc (&r->dtmp, (size_t) rows * wgp0 * 4));
+        for (uint32_t c = cols;; ) {                 // the passes rs_enqueue makes (algorithms.cpp:140-142)
+            const uint32_t wg = (c + 511u) / 512u, wgp = (wg != 1 && (wg % 4)) ? wg + 4 - wg % 4 : wg;
+            ++r->levels; c = wgp;
+            if (wgp == 1) break;
+        }
     }
-    r->result = r->dout;
     if (!ok) { icp_rs_destroy (r); return rs_fail (ICP_EHIP, err); }
     *out = r;
     return ICP_OK;
@@ -160,8 +169,10 @@ static int rs_enqueue (icp_rs_context *r)
 {
     const uint32_t cols = r->cols, rows = r->rows;
     if (r->kind == ICP_RS_SUM_F) {
+        // the first pass writes dtmp when the pass count is even, so that the last one always writes dout: the output
+        // pointer (icp_rs_device_ptr) is one buffer for the object's lifetime
         const float *cur = static_cast<const float *> (r->din);
-        float *a = static_cast<float *> (r->dout), *b = static_cast<float *> (r->dtmp);
+        float *a = static_cast<float *> (r->levels % 2 ? r->dout : r->dtmp), *b = static_cast<float *> (r->levels % 2 ? r->dtmp : r->dout);
         uint32_t c = cols;
         for (;;) {
             uint32_t wg = (c + 511u) / 512u, wgp = (wg != 1 && (wg % 4)) ? wg + 4 - wg % 4 : wg;   // algorithms.cpp:140-142
@@ -170,7 +181,6 @@ static int rs_enqueue (icp_rs_context *r)
             float *t = a; a = b; b = t;
             if (wgp == 1) break;
         }
-        r->result = cur;
     } else if (r->kind == ICP_RS_MIN_F)
         hipLaunchKernelGGL ((k_rs_minmax<float, false>), dim3 (rows), dim3 (256), 0, r->stream, static_cast<const float *> (r->din), cols, static_cast<float *> (r->dout));
     else if (r->kind == ICP_RS_MAX_UI)
@@ -194,7 +204,7 @@ int icp_rs_read (icp_rs_handle r, void *host_out) try
     if (!r || !host_out) return ICP_EINVAL;
     bool ok = true; std::string err;
     RSCHK (hipSetDevice (r->device));
-    if (ok) RSCHK (hipMemcpyAsync (host_out, r->result, r->out_bytes, hipMemcpyDeviceToHost, r->stream));
+    if (ok) RSCHK (hipMemcpyAsync (host_out, r->dout, r->out_bytes, hipMemcpyDeviceToHost, r->stream));
     if (ok) RSCHK (hipStreamSynchronize (r->stream));
     return ok ? ICP_OK : rs_fail (ICP_EHIP, err);
 }
@@ -203,7 +213,7 @@ ICP_CATCH_ALL
 int icp_rs_device_ptr (icp_rs_handle r, int output, void **dptr) try
 {
     if (!r || !dptr) return ICP_EINVAL;
-    *dptr = output ? const_cast<void *> (r->result) : r->din;
+    *dptr = output ? r->dout : r->din;
     return ICP_OK;
 }
 ICP_CATCH_ALL

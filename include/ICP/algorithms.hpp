@@ -136,7 +136,8 @@ namespace ICP
             chk (icp_rs_create (&h, env.device, kind, _cols, _rows));
             cols = _cols; rows = _rows; in.assign ((size_t) cols * rows, T ()); out.assign (rows, T ());
         }
-        /*! \brief Device buffer (reference: cl::Memory& get (Memory)): D_IN, or D_OUT = the result of the last run. */
+        /*! \brief Device buffer (reference: cl::Memory& get (Memory)): D_IN, or D_OUT, where every run leaves its result;
+         *         both stay the same from init to the next init, so they can be wired before the first run. */
         void* get (Memory mem) { void *p = nullptr; chk (icp_rs_device_ptr (h, mem == Memory::D_OUT || mem == Memory::D_RED ? 1 : 0, &p)); return p; }
         /*! \brief Host -> device (ptr == nullptr: the staging buffer hPtrIn () as it stands). */
         void write (Memory = Memory::D_IN, void *ptr = nullptr, bool = false)

@@ -516,7 +516,7 @@ int icp_rs_create (icp_rs_handle *r, int device, int kind, uint32_t cols, uint32
 int icp_rs_write (icp_rs_handle r, const void *host_in);            /* cols x rows elements (4 bytes each) */
 int icp_rs_run (icp_rs_handle r);                                   /* enqueue only */
 int icp_rs_read (icp_rs_handle r, void *host_out);                  /* rows results (reduce) / cols x rows (scan); blocking */
-int icp_rs_device_ptr (icp_rs_handle r, int output, void **dptr);   /* 0: input buffer, 1: result of the last run */
+int icp_rs_device_ptr (icp_rs_handle r, int output, void **dptr);   /* 0: input buffer, 1: output buffer (every run's result); both fixed from create to destroy */
 int icp_rs_time (icp_rs_handle r, uint32_t reps, float *us_per_run);
 int icp_rs_destroy (icp_rs_handle r);
 
