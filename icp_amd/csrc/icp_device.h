@@ -146,6 +146,7 @@ __device__ __forceinline__ void icp_transform_point (const float *T, float px, f
 // All 64 lanes must be active.  Returns the loop-trip count; Tk is valid in every lane.
 // ------------------------------------------------------------------------------------------
 #define ICP_PM_SQUARINGS 10
+#define ICP_PM_EXTRA_SQUARINGS 20
 typedef float icp_f4 __attribute__ ((ext_vector_type (4)));
 
 // value of lane k of the quad, in every lane of the quad: one DPP quad broadcast (no SGPR round trip, no hazards)
@@ -178,15 +179,48 @@ __device__ __forceinline__ void pmq_rescale (float *Brow)
     // (oracle rescale16; max is exact in any order: the quad's rows are combined with two DPP steps)
     // (four instructions, written out: fmaxf / fabsf compile to a canonicalising v_max per operand and a DPP move per step —
     // twelve instructions on the one wave the whole grid waits for; v_max3 / v_max return the non-NaN operand as fmaxf does, the
-    // entries are results of arithmetic (no signalling NaNs).  s_nop 1: DPP operand hazard, opaque to the compiler's hazard pass.)
+    // entries are results of arithmetic (no signalling NaNs).  Nothing inside the string is padded by the compiler's hazard pass:
+    // s_nop 4 first — in pmq_square the operands are the D registers of the v_mfma_f32_4x4x1 that has just written them, and a
+    // VALU read of an MFMA's D needs wait states (the compiler puts s_nop 3 before a plain C++ reader; one more for margin);
+    // s_nop 1 twice: the DPP operand hazard.)
     float mx;
-    asm ("v_max3_f32 %0, |%1|, |%2|, |%3|\n\tv_max_f32_e64 %0, %0, |%4|\n\ts_nop 1\n\t"
+    asm ("s_nop 4\n\tv_max3_f32 %0, |%1|, |%2|, |%3|\n\tv_max_f32_e64 %0, %0, |%4|\n\ts_nop 1\n\t"
          "v_max_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\ts_nop 1\n\t"
          "v_max_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1"
          : "=&v"(mx) : "v"(Brow[0]), "v"(Brow[1]), "v"(Brow[2]), "v"(Brow[3]));
     const uint32_t e = (__float_as_uint (mx) >> 23) & 0xFFu;
     const float sc = (e == 0u || e >= 254u) ? 1.f : __uint_as_float ((254u - e) << 23);    // zero / subnormal / inf / nan: leave
     Brow[0] = Brow[0] * sc; Brow[1] = Brow[1] * sc; Brow[2] = Brow[2] * sc; Brow[3] = Brow[3] * sc;
+}
+
+// squaring s of B (one row per lane): four v_mfma_f32_4x4x1 steps, the exact rescale after every fifth (oracle square16)
+__device__ __forceinline__ void pmq_square (float *Brow, const int s)
+{
+    icp_f4 acc = { 0.f, 0.f, 0.f, 0.f };
+    acc = __builtin_amdgcn_mfma_f32_4x4x1f32 (Brow[0], Brow[0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_4x4x1f32 (Brow[1], Brow[1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_4x4x1f32 (Brow[2], Brow[2], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_4x4x1f32 (Brow[3], Brow[3], acc, 0, 0, 0);
+    Brow[0] = acc[0]; Brow[1] = acc[1]; Brow[2] = acc[2]; Brow[3] = acc[3];
+    if (s % 5 == 4) pmq_rescale (Brow);                  // max|entry| < 2 after a rescale, < 2^94 five squarings later
+}
+
+// fast exit on the unnormalised pair (oracle fast_exit_converged): |u x v|^2 over the six index pairs against 2^-44 (u.u)(v.v); u.u and
+// u.v (the sign of the eigenvalue) for the caller.  Lane i holds the pairs (i, i+1) and (i, i+2) (indices mod 4; (3,0) and (2,0), (3,1)
+// are the negatives of (0,3), (0,2), (1,3): the same squares); summed in the oracle's order 01, 02, 03, 12, 13, 23.  Wave-uniform.
+__device__ __forceinline__ bool pmq_fast_exit (float u, float v, float &uu, float &uv)
+{
+    const float u1 = icp_dpp<0x39> (u), v1 = icp_dpp<0x39> (v);      // quad_perm [1,2,3,0]: component i + 1
+    const float u2 = icp_dpp<0x4E> (u), v2 = icp_dpp<0x4E> (v);      // quad_perm [2,3,0,1]: component i + 2
+    const float ta = u * v1 - u1 * v, tb = u * v2 - u2 * v;
+    const float a1 = ta * ta, a2 = tb * tb;
+    float c2 = 0.f;
+    c2 = c2 + pmq_q<0> (a1); c2 = c2 + pmq_q<0> (a2); c2 = c2 + pmq_q<3> (a1);
+    c2 = c2 + pmq_q<1> (a1); c2 = c2 + pmq_q<1> (a2); c2 = c2 + pmq_q<2> (a1);
+    uu = pmq_seq4 (u * u);
+    const float vv = pmq_seq4 (v * v);
+    uv = pmq_seq4 (u * v);
+    return !__ballot (c2 > 0x1p-44f * (uu * vv));
 }
 
 #ifdef ICP_DBG_STAMPS
@@ -230,43 +264,33 @@ __device__ inline int icp_power_method_quad (const float *S, const float *means,
         Tk[7] = sk;
     };
     PM_STAMP (0)
-    bool shifted = false;
+    bool shifted = false, extended = false;
     if (squared_start) {
         // oracle power_fast: B = N^1024, u = B 1, x = normalize (u), xn = normalize (N u) (two independent chains),
         // loop on squared step lengths, division-free sign test, no extra pass after the loop
+        bool extend = false;
         for (;;) {
             float Brow[4] = { Nrow[0], Nrow[1], Nrow[2], Nrow[3] };
             pmq_rescale (Brow);
-            for (int s = 0; s < ICP_PM_SQUARINGS; ++s) {
-                icp_f4 acc = { 0.f, 0.f, 0.f, 0.f };
-                acc = __builtin_amdgcn_mfma_f32_4x4x1f32 (Brow[0], Brow[0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_4x4x1f32 (Brow[1], Brow[1], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_4x4x1f32 (Brow[2], Brow[2], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_4x4x1f32 (Brow[3], Brow[3], acc, 0, 0, 0);
-                Brow[0] = acc[0]; Brow[1] = acc[1]; Brow[2] = acc[2]; Brow[3] = acc[3];
-                if (s % 5 == 4) pmq_rescale (Brow);              // max|entry| < 2 after a rescale, < 2^94 five squarings later
+            for (int s = 0; s < ICP_PM_SQUARINGS; ++s) pmq_square (Brow, s);
+            if (__builtin_expect (__ballot (extend), 0)) {
+                // the extra squarings (see the end of the fast-exit block) — N is what it was in the pass before, so are these ten.
+                // A loop, not unrolled: once per solve at most, on rare inputs.  (A scalar branch: `extend` is the same in every lane.)
+                extend = false;
+#pragma nounroll
+                for (int s = ICP_PM_SQUARINGS; s < ICP_PM_SQUARINGS + ICP_PM_EXTRA_SQUARINGS; ++s) pmq_square (Brow, s);
             }
             PM_STAMP (1)
-            const float u = pmq_matvec (Brow, 1.f);
-            const float v = pmq_matvec (Nrow, u);
+            float u = pmq_matvec (Brow, 1.f);
+            float v = pmq_matvec (Nrow, u);
             xn = pmq_normalize (v);
             ++iters;
-            // fast exit on the unnormalised pair (oracle power_fast): |u x v|^2 over the six index pairs against
-            // 2^-44 (u.u)(v.v), sign of the eigenvalue from u.v — decided while the normalisation above is still under way.
-            // Lane i holds the pairs (i, i+1) and (i, i+2) (indices mod 4; (3,0) and (2,0), (3,1) are the negatives of
-            // (0,3), (0,2), (1,3): the same squares); summed in the oracle's order 01, 02, 03, 12, 13, 23.
+            // fast exit on the unnormalised pair (pmq_fast_exit), decided while the normalisation above is still under way
             {
-                const float u1 = icp_dpp<0x39> (u), v1 = icp_dpp<0x39> (v);      // quad_perm [1,2,3,0]: component i + 1
-                const float u2 = icp_dpp<0x4E> (u), v2 = icp_dpp<0x4E> (v);      // quad_perm [2,3,0,1]: component i + 2
-                const float ta = u * v1 - u1 * v, tb = u * v2 - u2 * v;
-                const float a1 = ta * ta, a2 = tb * tb;
-                float c2 = 0.f;
-                c2 = c2 + pmq_q<0> (a1); c2 = c2 + pmq_q<0> (a2); c2 = c2 + pmq_q<3> (a1);
-                c2 = c2 + pmq_q<1> (a1); c2 = c2 + pmq_q<1> (a2); c2 = c2 + pmq_q<2> (a1);
-                const float uu = pmq_seq4 (u * u), vv = pmq_seq4 (v * v), uv = pmq_seq4 (u * v);
+                float uu, uv;
                 // (scalar branches: every quad holds the same values; as per-lane compares the compiler builds divergent control flow around the
                 // one path every iteration of every ordinary scene takes)
-                if (__builtin_expect (!__ballot (c2 > 0x1p-44f * (uu * vv)), 1)) {
+                if (__builtin_expect (pmq_fast_exit (u, v, uu, uv), 1)) {
                     if (__ballot (uv < 0.f)) {
                         const float lambda = uv / uu;
 #pragma unroll
@@ -287,6 +311,12 @@ __device__ inline int icp_power_method_quad (const float *S, const float *means,
                         for (int k = 0; k < 4; ++k) Nrow[k] = (i == (uint32_t) k) ? Nrow[k] + sigma : Nrow[k];
                         continue;
                     }
+                } else if (!extended) {
+                    // the shifted matrix still fails the fast exit: a small gap without the planar +-lambda pairing (a rod-like set), made
+                    // smaller by the shift — once per solve, the next pass squares B 20 times more than this one (N^(2^30); oracle
+                    // power_fast)
+                    extended = extend = true;
+                    continue;
                 }
             }
             x = pmq_normalize (u);
@@ -425,6 +455,45 @@ template <int P, int Q> __device__ __forceinline__ void icp_svd_rotate_pair (flo
         V[i * 3 + P] = cs * vp - sn * vq; V[i * 3 + Q] = sn * vp + cs * vq;
     }
 }
+// A zero singular value leaves its column of U at 0 (oracle svd_complete_u): U completed to an orthonormal basis of det +1 — one zero
+// column: the cross product of the other two, in cyclic order; two: the Gram-Schmidt of the first coordinate axis with the smallest |u_m|
+// against the third column u, and u x that; three: the identity.  Written with selects and compile-time indices: branches that store
+// to different columns are merged by the compiler into one store at a computed index, which puts U in scratch memory.
+__device__ __forceinline__ void icp_svd_complete_u (float *U, const float *sig)
+{
+    const bool z[3] = { sig[0] == 0.f, sig[1] == 0.f, sig[2] == 0.f };
+    const int nz = (int) z[0] + (int) z[1] + (int) z[2];
+    float c[9];                                                         // one zero column: the cross products, column j in c[3 j ..]
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int a = (j + 1) % 3, b = (j + 2) % 3;
+        c[3 * j]     = U[3 + a] * U[6 + b] - U[6 + a] * U[3 + b];
+        c[3 * j + 1] = U[6 + a] * U[b]     - U[a]     * U[6 + b];
+        c[3 * j + 2] = U[a]     * U[3 + b] - U[3 + a] * U[b];
+    }
+    // two zero columns: u the other one
+    const float u0 = !z[0] ? U[0] : !z[1] ? U[1] : U[2];
+    const float u1 = !z[0] ? U[3] : !z[1] ? U[4] : U[5];
+    const float u2 = !z[0] ? U[6] : !z[1] ? U[7] : U[8];
+    const bool ge1 = fabsf (u1) < fabsf (u0);
+    const bool m2 = fabsf (u2) < fabsf (ge1 ? u1 : u0), m1 = ge1 && !m2, m0 = !ge1 && !m2;
+    const float um = m2 ? u2 : m1 ? u1 : u0;
+    float w0 = (m0 ? 1.f : 0.f) - um * u0, w1 = (m1 ? 1.f : 0.f) - um * u1, w2 = (m2 ? 1.f : 0.f) - um * u2;
+    const float wn = sqrtf ((w0 * w0 + w1 * w1) + w2 * w2);
+    w0 = w0 / wn; w1 = w1 / wn; w2 = w2 / wn;
+    const float x0 = u1 * w2 - u2 * w1, x1 = u2 * w0 - u0 * w2, x2 = u0 * w1 - u1 * w0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        // column j: the cross product (one zero), w if it follows u cyclically else u x w (two zeros), e_j (three)
+        const bool after_u = !z[(j + 2) % 3];
+        const float n0 = nz == 3 ? (j == 0 ? 1.f : 0.f) : nz == 1 ? c[3 * j]     : after_u ? w0 : x0;
+        const float n1 = nz == 3 ? (j == 1 ? 1.f : 0.f) : nz == 1 ? c[3 * j + 1] : after_u ? w1 : x1;
+        const float n2 = nz == 3 ? (j == 2 ? 1.f : 0.f) : nz == 1 ? c[3 * j + 2] : after_u ? w2 : x2;
+        U[j]     = z[j] ? n0 : U[j];
+        U[3 + j] = z[j] ? n1 : U[3 + j];
+        U[6 + j] = z[j] ? n2 : U[6 + j];
+    }
+}
 __device__ inline void icp_svd_rotation (const float *S11, const float *means, float *Rk, float *Tk)
 {
     float A[9], V[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 };
@@ -444,6 +513,7 @@ __device__ inline void icp_svd_rotation (const float *S11, const float *means, f
 #pragma unroll
         for (int i = 0; i < 3; ++i) U[i * 3 + j] = sig[j] > 0.f ? A[i * 3 + j] / sig[j] : 0.f;
     }
+    if (sig[0] == 0.f || sig[1] == 0.f || sig[2] == 0.f) icp_svd_complete_u (U, sig);     // (S of rank < 3 only)
     int smin = 0; float sminv = sig[0];                                // first smallest singular value
     if (sig[1] < sminv) { smin = 1; sminv = sig[1]; }
     if (sig[2] < sminv) { smin = 2; sminv = sig[2]; }

@@ -536,6 +536,38 @@ static void rescale16 (float *B)
 }
 
 #define PM_SQUARINGS 10
+#define PM_EXTRA_SQUARINGS 20
+
+/* squarings s0 .. s1-1 of B: C = B B as a k-ordered fmaf chain (what v_mfma_f32_4x4x1 evaluates: one rounding per step), an exact
+ * power-of-two rescale after every fifth */
+static void square16 (float *B, int s0, int s1)
+{
+    float C[16];
+    for (int s = s0; s < s1; ++s) {
+        for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j) {
+                float acc = 0.f;
+                for (int k = 0; k < 4; ++k) acc = fmaf (B[i * 4 + k], B[k * 4 + j], acc);
+                C[i * 4 + j] = acc;
+            }
+        memcpy (B, C, sizeof C);
+        if (s % 5 == 4) rescale16 (B);          /* max|entry| < 2 after a rescale, < 2^94 five squarings later */
+    }
+}
+
+/* The squared start's fast-exit test on the unnormalised pair (u, v = N u): |u x v|^2 = sum over the six index pairs of
+ * (u_i v_j - u_j v_i)^2 (Lagrange's identity: no cancellation between large terms) against 2^-44 (u.u)(v.v), i.e. sin^2 of the angle
+ * between two successive iterates against the square of one ulp of a unit vector.  False on NaN. */
+static int fast_exit_converged (const float *u, const float *v)
+{
+    float c2 = 0.f, t;
+    t = u[0] * v[1] - u[1] * v[0]; c2 += t * t;  t = u[0] * v[2] - u[2] * v[0]; c2 += t * t;
+    t = u[0] * v[3] - u[3] * v[0]; c2 += t * t;  t = u[1] * v[2] - u[2] * v[1]; c2 += t * t;
+    t = u[1] * v[3] - u[3] * v[1]; c2 += t * t;  t = u[2] * v[3] - u[3] * v[2]; c2 += t * t;
+    float uu = 0.f, vv = 0.f;
+    for (int k = 0; k < 4; ++k) { uu += u[k] * u[k]; vv += v[k] * v[k]; }
+    return !(c2 > 0x1p-44f * (uu * vv));
+}
 
 /* The reference's power method, literally (icp_kernels.cl:977-1054). */
 static int power_literal (const float *S, const float *means, float *Tk)
@@ -580,22 +612,16 @@ static int power_fast (const float *S, const float *means, float *Tk)
     float N[16]; build_N (S, N);
     float x[4], xn[4], u[4];
     const float ones[4] = { 1.f, 1.f, 1.f, 1.f };
-    int iters = 0, shifted = 0;
+    int iters = 0, shifted = 0, extended = 0, extend = 0;
     for (;;) {
-        float B[16], C[16]; memcpy (B, N, sizeof B); rescale16 (B);
-        for (int s = 0; s < PM_SQUARINGS; ++s) {
-            /* C = B B as a k-ordered fmaf chain (what v_mfma_f32_4x4x1 evaluates: one rounding per step) */
-            for (int i = 0; i < 4; ++i)
-                for (int j = 0; j < 4; ++j) {
-                    float acc = 0.f;
-                    for (int k = 0; k < 4; ++k) acc = fmaf (B[i * 4 + k], B[k * 4 + j], acc);
-                    C[i * 4 + j] = acc;
-                }
-            memcpy (B, C, sizeof B);
-            if (s % 5 == 4) rescale16 (B);          /* max|entry| < 2 after a rescale, < 2^94 five squarings later */
+        float B[16]; memcpy (B, N, sizeof B); rescale16 (B);
+        square16 (B, 0, PM_SQUARINGS);
+        if (extend) {                                /* the extra squarings (see the end of the fast-exit block) */
+            extend = 0;
+            square16 (B, PM_SQUARINGS, PM_SQUARINGS + PM_EXTRA_SQUARINGS);
         }
-        prod4 (B, ones, u);
-        float v[4]; prod4 (N, u, v);
+        float v[4];
+        prod4 (B, ones, u); prod4 (N, u, v);
         ++iters;
         /* Fast exit, decided on the unnormalised pair (u, v = N u) — nothing on the way to the result waits for it:
          * |u x v|^2 = sum over the six index pairs of (u_i v_j - u_j v_i)^2 (Lagrange's identity: no cancellation between
@@ -604,13 +630,9 @@ static int power_fast (const float *S, const float *means, float *Tk)
          * NaN like the loop's own test below.  Converged and positive: the result is normalize (N u), what the general
          * path below ends with in this case. */
         {
-            float c2 = 0.f, t;
-            t = u[0] * v[1] - u[1] * v[0]; c2 += t * t;  t = u[0] * v[2] - u[2] * v[0]; c2 += t * t;
-            t = u[0] * v[3] - u[3] * v[0]; c2 += t * t;  t = u[1] * v[2] - u[2] * v[1]; c2 += t * t;
-            t = u[1] * v[3] - u[3] * v[1]; c2 += t * t;  t = u[2] * v[3] - u[3] * v[2]; c2 += t * t;
-            float uu = 0.f, vv = 0.f, uv = 0.f;
-            for (int k = 0; k < 4; ++k) { uu += u[k] * u[k]; vv += v[k] * v[k]; uv += u[k] * v[k]; }
-            if (!(c2 > 0x1p-44f * (uu * vv))) {
+            float uu = 0.f, uv = 0.f;
+            for (int k = 0; k < 4; ++k) { uu += u[k] * u[k]; uv += u[k] * v[k]; }
+            if (fast_exit_converged (u, v)) {
                 if (uv < 0.f) {                              /* negative dominant eigenvalue: shift by it (:1024-1037), start over */
                     const float lambda = uv / uu;
                     N[0] -= lambda; N[5] -= lambda; N[10] -= lambda; N[15] -= lambda;
@@ -636,6 +658,12 @@ static int power_fast (const float *S, const float *means, float *Tk)
                     N[0] += sigma; N[5] += sigma; N[10] += sigma; N[15] += sigma;
                     continue;
                 }
+            } else if (!extended) {
+                /* The shifted matrix still fails the test: a small gap between N's two top eigenvalues without the planar +-lambda
+                 * pairing (a thin, rod-like point set), which the shift has made smaller still.  Once per solve, the next pass (on the
+                 * same N) squares on to N^(2^(PM_SQUARINGS + PM_EXTRA_SQUARINGS)), the same squarings and rescale cadence. */
+                extended = extend = 1;
+                continue;
             }
         }
         memcpy (x, u, sizeof x); normalize4 (x);
@@ -715,6 +743,37 @@ static float dot3c (const float *a, int sa, const float *b, int sb)
 /* a12  EIGEN branch — src/ICP/algorithms.cpp:3867-3909: JacobiSVD of S, Rk = V U^T with    */
 /*      det fix.  Restated as a one-sided (Hestenes) Jacobi SVD in fp32 (Eigen un-vendored). */
 /* ======================================================================================= */
+/* A zero singular value (S of rank 2 or less: an exactly planar or collinear set, or no pairs) leaves its column of U at 0, and
+ * V U^T would not be a rotation.  U is completed to an orthonormal basis of det +1, as JacobiSVD's full U is: one zero column is the
+ * cross product of the other two (cyclic order), two are the Gram-Schmidt of the coordinate axis least aligned with the third and
+ * the cross product of the two, three are the identity.  The det fix then applies as for a full-rank S. */
+static void svd_complete_u (float *U, const float *sig)
+{
+    const int z0 = sig[0] == 0.f, z1 = sig[1] == 0.f, z2 = sig[2] == 0.f;
+    if (z0 + z1 + z2 == 3) {
+        for (int i = 0; i < 9; ++i) U[i] = (i % 4 == 0) ? 1.f : 0.f;
+    } else if (z0 + z1 + z2 == 1) {
+        const int j = z0 ? 0 : z1 ? 1 : 2, a = (j + 1) % 3, b = (j + 2) % 3;
+        U[j]     = U[3 + a] * U[6 + b] - U[6 + a] * U[3 + b];
+        U[3 + j] = U[6 + a] * U[b]     - U[a]     * U[6 + b];
+        U[6 + j] = U[a]     * U[3 + b] - U[3 + a] * U[b];
+    } else {
+        const int k = !z0 ? 0 : !z1 ? 1 : 2, a = (k + 1) % 3, b = (k + 2) % 3;
+        const float u0 = U[k], u1 = U[3 + k], u2 = U[6 + k];
+        int m = 0;                                        /* the first coordinate axis with the smallest |u_m| */
+        if (fabsf (u1) < fabsf (u0)) m = 1;
+        if (fabsf (u2) < fabsf (m ? u1 : u0)) m = 2;
+        const float um = m == 0 ? u0 : m == 1 ? u1 : u2;
+        float w0 = (m == 0 ? 1.f : 0.f) - um * u0, w1 = (m == 1 ? 1.f : 0.f) - um * u1, w2 = (m == 2 ? 1.f : 0.f) - um * u2;
+        const float wn = sqrtf ((w0 * w0 + w1 * w1) + w2 * w2);
+        w0 = w0 / wn; w1 = w1 / wn; w2 = w2 / wn;
+        U[a] = w0; U[3 + a] = w1; U[6 + a] = w2;
+        U[b]     = u1 * w2 - u2 * w1;                     /* u_k x w */
+        U[3 + b] = u2 * w0 - u0 * w2;
+        U[6 + b] = u0 * w1 - u1 * w0;
+    }
+}
+
 void orc_svd_rotation (const float *S11, const float *means, float *Rk, float *Tk)
 {
     /* Eigen maps S row-major: S(a,b) = S11[3a+b], a = moving component, b = fixed component */
@@ -750,6 +809,7 @@ void orc_svd_rotation (const float *S11, const float *means, float *Rk, float *T
         sig[j] = sqrtf ((A[j] * A[j] + A[3 + j] * A[3 + j]) + A[6 + j] * A[6 + j]);
         for (int i = 0; i < 3; ++i) U[i * 3 + j] = sig[j] > 0.f ? A[i * 3 + j] / sig[j] : 0.f;
     }
+    if (sig[0] == 0.f || sig[1] == 0.f || sig[2] == 0.f) svd_complete_u (U, sig);
     /* smallest singular value last matters only for the det fix: find its column */
     int smin = 0; for (int j = 1; j < 3; ++j) if (sig[j] < sig[smin]) smin = j;
     /* Rk = V * U^T */
