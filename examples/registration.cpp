@@ -6,13 +6,14 @@
 //   registration NAME                     data/NAME_1.bin, data/NAME_2.bin      (the reference's argument convention, :299-329)
 //   registration A B                      data/A.bin, data/B.bin — or A and B themselves when they name existing files
 //   ... [--out FILE] [--device N] [--reference-order] [--svd] [--reject-invalid] [--max-dist MM] [--trim FRACTION]
-//       [--point-to-plane MU] [--colored KAPPA]
+//       [--point-to-plane MU] [--colored KAPPA] [--robust KIND:SCALE]
 //
 // --reject-invalid / --max-dist: correspondence rejection (icp_set_rejection: pairs with a pixel without depth at either end / pairs
 // farther apart than MM get weight 0).  --trim: trimmed ICP (icp_set_trimming: every iteration keeps the closest FRACTION in (0, 1] of the
 // pairs).  --point-to-plane: point-to-plane ICP plus MU (>= 0) times the point-to-point error (icp_set_error_metric), the normals from the
 // fixed 128 x 128 landmark grid (ICP_NORMALS_GRID).  --colored: colored ICP (ICP_METRIC_COLORED): point-to-plane plus KAPPA (>= 0) times
 // the photometric term (icp_set_color_weight), grid normals and intensity gradients; MU of --point-to-plane when given, else 0.
+// --robust: a robust loss (icp_set_robust_loss) of KIND huber, cauchy or tukey with the scale SCALE (> 0, mm), e.g. tukey:50.
 // Not the reference's behaviour; off by default.
 //
 // A cloud file is 640 x 480 points of 8 floats [x y z 1 r g b 1], little endian, row-major (src/kinect_frame_grabber.cpp:252-272).
@@ -43,11 +44,12 @@ std::string data_path (const std::string &name) { return exists (name) ? name : 
 
 template <cl_algo::ICP::ICPStepConfigT RC>
 int run (int device, icp::Mode mode, const std::vector<icp_float8> &pc1, const std::vector<icp_float8> &pc2, const std::string &out,
-         int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa)
+         int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa, icp::RobustLoss robust)
 {
     ICPReg<RC, cl_algo::ICP::ICPStepConfigW::WEIGHTED> app (device, mode);
     if (reject_flags || max_dist > 0.f) app.setRejection (reject_flags, max_dist);
     if (trim != 1.f) app.setTrimming (trim);
+    if (robust.loss != icp::RobustLoss::NONE) app.setRobustLoss (robust);
     if (kappa >= 0.f) {
         app.setNormals (ICP_NORMALS_GRID, 128); app.setColorWeight (kappa);
         app.setErrorMetric (ICP_METRIC_COLORED, p2pl_mu >= 0.f ? p2pl_mu : 0.f);
@@ -75,6 +77,7 @@ int main (int argc, char **argv)
     std::string out;
     int device = 0; bool svd = false;
     int reject_flags = 0; float max_dist = 0.f, trim = 1.f, p2pl_mu = -1.f, kappa = -1.f;     // (p2pl_mu < 0: point-to-point; kappa < 0: not colored)
+    icp::RobustLoss robust;
     icp::Mode mode = icp::Mode::FAST;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -96,6 +99,17 @@ int main (int argc, char **argv)
             kappa = std::strtof (argv[++i], nullptr);
             if (!(kappa >= 0.f && std::isfinite (kappa))) { std::fprintf (stderr, "--colored: KAPPA must be finite and >= 0\n"); return 2; }
         }
+        else if (a == "--robust" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            const size_t c = v.find (':');
+            const std::string kind = v.substr (0, c);
+            robust.loss = kind == "huber" ? icp::RobustLoss::HUBER : kind == "cauchy" ? icp::RobustLoss::CAUCHY : kind == "tukey" ? icp::RobustLoss::TUKEY : -1;
+            char *end = nullptr;
+            robust.scale = c == std::string::npos ? 0.f : std::strtof (v.c_str () + c + 1, &end);
+            if (robust.loss < 0 || c == std::string::npos || end == v.c_str () + c + 1 || *end || !(robust.scale > 0.f && std::isfinite (robust.scale))) {
+                std::fprintf (stderr, "--robust: KIND:SCALE with KIND huber, cauchy or tukey and SCALE finite and > 0\n"); return 2;
+            }
+        }
         else if (a.rfind ("--", 0) == 0) { std::fprintf (stderr, "unknown option %s\n", a.c_str ()); return 2; }
         else names.push_back (a);
     }
@@ -111,8 +125,8 @@ int main (int argc, char **argv)
         } else {
             read_cloud (data_path (names[0]), pc1); read_cloud (data_path (names[1]), pc2);
         }
-        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa)
-                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa);
+        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust)
+                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust);
     }
     catch (const std::exception &e)
     {

@@ -46,6 +46,14 @@ class ErrorMetric:                # icp_set_error_metric (include/icp_amd.h)
     COLORED = 2                   # point-to-plane plus kappa times a photometric term (set_color_weight)
 
 
+class RobustLoss:                # icp_set_robust_loss (include/icp_amd.h): the IRLS weight omega (u) of u = s^2 / k^2
+    NONE = 0                      # off (the default)
+    HUBER = 1                     # u <= 1 ? 1 : 1 / sqrt (u)
+    CAUCHY = 2                    # 1 / (1 + u)
+    TUKEY = 3                     # u < 1 ? (1 - u)^2 : 0
+    NAMES = {"none": NONE, "huber": HUBER, "cauchy": CAUCHY, "tukey": TUKEY}
+
+
 class Normals:                    # icp_set_normals: where the fixed frame's point-to-plane normals come from
     GIVEN = 0                     # written by the user (Memory.NORMALS_F)
     GRID = 1                      # computed by buildRBC from F read as a row-major grid
@@ -150,6 +158,8 @@ def lib():
     sig("icp_get_rejection", i32, vp, C.POINTER(i32), C.POINTER(f32))
     sig("icp_set_trimming", i32, vp, f32)
     sig("icp_get_trimming", i32, vp, C.POINTER(f32))
+    sig("icp_set_robust_loss", i32, vp, i32, f32)
+    sig("icp_get_robust_loss", i32, vp, C.POINTER(i32), C.POINTER(f32))
     sig("icp_set_error_metric", i32, vp, i32, f32)
     sig("icp_get_error_metric", i32, vp, C.POINTER(i32), C.POINTER(f32))
     sig("icp_set_normals", i32, vp, i32, u32)
@@ -181,6 +191,7 @@ def lib():
     sig("icp_batch_set_modes", i32, vp, i32, i32)
     sig("icp_batch_set_rejection", i32, vp, i32, f32)
     sig("icp_batch_set_trimming", i32, vp, f32)
+    sig("icp_batch_set_robust_loss", i32, vp, i32, f32)
     sig("icp_batch_set_error_metric", i32, vp, i32, f32)
     sig("icp_batch_set_normals", i32, vp, i32, u32)
     sig("icp_batch_set_color_weight", i32, vp, f32)
@@ -668,6 +679,18 @@ class ICPStep:
         self._chk(self._L.icp_get_trimming(self._h, C.byref(v)))
         return v.value
 
+    def set_robust_loss(self, loss=RobustLoss.NONE, scale=0.0):
+        """Robust loss (icp_set_robust_loss; not reference behaviour, off by default): every pair's weight is multiplied by the
+        loss's IRLS weight omega (s^2 / scale^2) of its own residual s, for every error metric.  `scale` k (finite, > 0, the cloud's
+        units) is ignored with RobustLoss.NONE.  Point-to-point: read(Memory.W) gives the weights after it."""
+        self._chk(self._L.icp_set_robust_loss(self._h, int(loss), float(scale)))
+
+    def robust_loss(self):
+        """(loss, scale) as set ((0, 0.0): off)."""
+        l, k = C.c_int32(), C.c_float()
+        self._chk(self._L.icp_get_robust_loss(self._h, C.byref(l), C.byref(k)))
+        return l.value, k.value
+
     def set_error_metric(self, metric=ErrorMetric.POINT_TO_POINT, point_weight=0.0):
         """Point-to-plane ICP (icp_set_error_metric; not reference behaviour, off by default): each iteration minimises the
         point-to-plane error plus `point_weight` (mu >= 0) times the point-to-point error, linearised, solved by LDL^T on the device.
@@ -1040,6 +1063,10 @@ class ICPBatch:
     def trimming(self):
         """The keep fraction as last set on this batch (1.0: off)."""
         return getattr(self, "_trimming", 1.0)
+
+    def set_robust_loss(self, loss=RobustLoss.NONE, scale=0.0):
+        """ICPStep.set_robust_loss on every registration (icp_batch_set_robust_loss)."""
+        self._chk(self._L.icp_batch_set_robust_loss(self._b, int(loss), float(scale)))
 
     def set_error_metric(self, metric=ErrorMetric.POINT_TO_POINT, point_weight=0.0):
         """ICPStep.set_error_metric on every registration (icp_batch_set_error_metric)."""

@@ -371,6 +371,22 @@ int icp_batch_set_trimming (icp_batch_handle b, float keep_fraction) try
 }
 ICP_CATCH_ALL
 
+int icp_batch_set_robust_loss (icp_batch_handle b, int loss, float scale) try
+{
+    // (the arguments first, as icp_set_robust_loss does: with b == NULL the message is icp_batch_last_error (NULL)'s)
+    if (loss != ICP_ROBUST_NONE && loss != ICP_ROBUST_HUBER && loss != ICP_ROBUST_CAUCHY && loss != ICP_ROBUST_TUKEY)
+        return bfail (b, ICP_EINVAL, "icp_batch_set_robust_loss: unknown loss");
+    if (loss != ICP_ROBUST_NONE && !(scale > 0.f && std::isfinite (scale)))
+        return bfail (b, ICP_EINVAL, "icp_batch_set_robust_loss: scale must be finite and > 0");
+    if (!b) return bfail (b, ICP_EINVAL, "icp_batch_set_robust_loss: null handle");
+    for (icp_handle h : b->slots) {
+        int rc = icp_set_robust_loss (h, loss, scale);
+        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
+    }
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
 int icp_batch_set_error_metric (icp_batch_handle b, int metric, float point_weight) try
 {
     if (!b) return ICP_EINVAL;

@@ -189,6 +189,14 @@ static int write_color_kappa (icp_context *h)
     return ICP_OK;
 }
 
+// the robust loss's scale k -> its device word (icp_robust_scale), in stream order like kappa's (0 while the loss is off)
+static int write_robust_scale (icp_context *h)
+{
+    uint32_t bits; std::memcpy (&bits, &h->robust_scale, sizeof bits);
+    HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (icp_robust_scale (h->p)), (int) bits, 1, h->stream));
+    return ICP_OK;
+}
+
 int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, float a, float c,
                       uint32_t max_iterations, double angle_threshold, double translation_threshold) try
 {
@@ -277,10 +285,12 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     if ((rc = dalloc (h, &p.mpart, B * 2 * p.nwg))) return rc;
     if ((rc = dalloc (h, &p.mscr, B * 2 * ((p.nwg + 127u) / 128u)))) return rc;
     if ((rc = dalloc (h, &p.spart, B * 11 * p.nsp * 8))) return rc;    // 8 sub-trees per work-group; padding stays 0.f
-    // (behind the moments, icp_mom_layout: trimming's words, the plane system and its block partials, the word of kappa (written below);
+    // (behind the moments, icp_mom_layout: trimming's words, the plane system and its block partials, the words of kappa and of the
+    // robust loss's scale (written below);
     // zeroed: ICP_MEM_TRIM and ICP_MEM_PLANE_SYSTEM read 0 until an iteration has written them, and the histograms and counters start clear)
     if ((rc = dalloc (h, &p.mom, icp_mom_layout_of (batch, m, p.nb).total))) return rc;
     if ((rc = write_color_kappa (h))) return rc;
+    if ((rc = write_robust_scale (h))) return rc;
     if ((rc = dalloc (h, &p.ml1, B * 18 * ((p.nb + 127u) / 128u)))) return rc;
     if ((rc = dalloc (h, &p.cst, B * 2))) return rc;
     if ((rc = dalloc (h, &p.st, B))) return rc;
@@ -683,7 +693,7 @@ int icp_set_rejection (icp_handle h, int flags, float max_dist) try
     if (!h) return fail (h, ICP_EINVAL, "icp_set_rejection: null handle");
     { int rc = outputs_before_change (h); if (rc) return rc; }
     const bool dist = max_dist > 0.f && !std::isinf (max_dist);
-    h->p.reject = (uint32_t) flags | (dist ? ICP_REJECT_DIST_ON : 0u) | (h->p.reject & ICP_REJECT_TRIM_ON);
+    h->p.reject = (uint32_t) flags | (dist ? ICP_REJECT_DIST_ON : 0u) | (h->p.reject & (ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK));
     h->p.reject_max_dist = max_dist;
     h->p.reject_d2 = dist ? (float) ((double) max_dist * (double) max_dist) : 0.f;     // (the product of two floats is exact in double)
     ++h->param_gen; return ICP_OK;
@@ -693,7 +703,7 @@ int icp_get_rejection (icp_handle h, int *flags, float *max_dist) try
 {
     api_guard guard_ (h);
     if (!h) return ICP_EINVAL;
-    if (flags) *flags = (int) (h->p.reject & ~(ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON));
+    if (flags) *flags = (int) (h->p.reject & ~(ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK));
     if (max_dist) *max_dist = h->p.reject_max_dist;
     return ICP_OK;
 }
@@ -729,6 +739,44 @@ int icp_get_trimming (icp_handle h, float *keep_fraction) try
     api_guard guard_ (h);
     if (!h || !keep_fraction) return ICP_EINVAL;
     *keep_fraction = icp_trimming (h->p) ? h->p.trim_keep : 1.f;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+// robust loss (include/icp_amd.h; icp_trim.hip, icp_p2pl.hip).  On <-> off and a new kind change which kernels run — point-to-point: the
+// REJ search and the apply pass, no chained form; the plane metrics: other moments —: the route of icp_set_trimming (graphs captured
+// anew).  A new scale while the loss stays on goes to its device word, as kappa does (icp_set_color_weight): no graph is touched.
+int icp_set_robust_loss (icp_handle h, int loss, float scale) try
+{
+    api_guard guard_ (h);
+    static_assert (ICP_ROBUST_TUKEY << ICP_REJECT_ROBUST_SHIFT == ICP_REJECT_ROBUST_MASK, "the loss's kind fills the mask's two bits");
+    static_assert (!(ICP_REJECT_ROBUST_MASK & (ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_INVALID)), "the loss's bits are its own");
+    if (loss != ICP_ROBUST_NONE && loss != ICP_ROBUST_HUBER && loss != ICP_ROBUST_CAUCHY && loss != ICP_ROBUST_TUKEY)
+        return fail (h, ICP_EINVAL, "icp_set_robust_loss: unknown loss");
+    if (loss != ICP_ROBUST_NONE && !(scale > 0.f && std::isfinite (scale)))
+        return fail (h, ICP_EINVAL, "icp_set_robust_loss: scale must be finite and > 0");
+    if (!h) return fail (h, ICP_EINVAL, "icp_set_robust_loss: null handle");
+    { int rc = outputs_before_change (h); if (rc) return rc; }
+    const uint32_t kind = (uint32_t) loss;
+    const float k = loss != ICP_ROBUST_NONE ? scale : 0.f;
+    const bool reroute = kind != icp_robust (h->p);
+    h->robust_scale = k;
+    h->p.reject = (h->p.reject & ~ICP_REJECT_ROBUST_MASK) | (kind << ICP_REJECT_ROBUST_SHIFT);
+    if (h->inited) {
+        int rc = set_device (h); if (rc) return rc;
+        if ((rc = run_close_all (h))) return rc;
+        if ((rc = write_robust_scale (h))) return rc;
+        HIPCHK (h, hipStreamSynchronize (h->stream));
+    }
+    if (reroute) drop_graphs (h);
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+int icp_get_robust_loss (icp_handle h, int *loss, float *scale) try
+{
+    api_guard guard_ (h);
+    if (!h) return ICP_EINVAL;
+    if (loss) *loss = (int) icp_robust (h->p);
+    if (scale) *scale = h->robust_scale;
     return ICP_OK;
 }
 ICP_CATCH_ALL
@@ -1082,8 +1130,8 @@ int icp_launches_per_iteration (icp_handle h, uint32_t *n) try
     if ((rc = icp_run_form (h, &form))) return rc;
     // (fused, large sets: the first level of the moment tree is a launch of its own — icp_launch_finalize)
     *n = form != ICP_FORM_SEPARATE ? 1u : h->p.fused ? ((h->p.nb + 127u) / 128u > ICP_L1_MIN_GROUPS ? 3u : 2u) : 4u;
-    if (icp_trimming (h->p)) *n += icp_trim_launches (h->p);          // (select: one or three launches, apply: one)
-    if (icp_p2pl (h->p)) *n = 1u + (icp_trimming (h->p) ? icp_trim_launches (h->p) : 0u) + ICP_P2PL_LAUNCHES;   // (search, moments, finalize)
+    if (icp_apply_pass (h->p)) *n += icp_trim_launches (h->p);        // (trimming's select: one or three launches; apply: one)
+    if (icp_p2pl (h->p)) *n = 1u + (icp_apply_pass (h->p) ? icp_trim_launches (h->p) : 0u) + ICP_P2PL_LAUNCHES;   // (search, moments, finalize)
     return ICP_OK;
 }
 ICP_CATCH_ALL

@@ -112,6 +112,7 @@ struct icp_context {
     double stat_t[6] = { 0, 0, 0, 0, 0, 0 };     // its host timeline (run_ctl::t) + the moment its FINAL bit was seen
     double stat_launch_max_us = 0.0; uint64_t stat_launch_slow = 0, stat_launch_total = 0;   // launch calls of all checked runs since icp_init
     float color_kappa = 0.f;                     // colored ICP's kappa (icp_set_color_weight; survives icp_init): its device word is icp_color_kappa
+    float robust_scale = 0.f;                    // the robust loss's scale k (icp_set_robust_loss; 0 while off; survives icp_init): its device word is icp_robust_scale
     uint64_t graph_clock = 0, param_gen = 0;     // LRU stamp of the graph cache; generation of the parameters the cached graphs were captured with
     float *dTin = nullptr;                       // device scratch for write(T)
     float *dCloud = nullptr, *dCloudOut = nullptr; uint32_t cloud_cap = 0;
@@ -252,8 +253,8 @@ int run_begin (icp_context *h, run_ctl &r, hipStream_t stream, const icp_params 
     r.stream = stream;
     r.t[0] = now_s ();
     r.p = p; r.p.check = 1;
-    // (reference-order kernels read the outputs themselves, and so do the selection of trimming and the point-to-plane moments: always stored)
-    r.p.emit = (h->outputs_lazy && p.fused && !icp_trimming (p) && !icp_p2pl (p)) ? 0 : 1;
+    // (reference-order kernels read the outputs themselves, and so do trimming's selection, the apply pass and the point-to-plane moments: always stored)
+    r.p.emit = (h->outputs_lazy && p.fused && !icp_apply_pass (p) && !icp_p2pl (p)) ? 0 : 1;
     h->outputs_stale = r.p.emit == 0; h->outputs_lost = false;
     if (++h->epoch == 0u) h->epoch = 1u;
     r.p.epoch = h->epoch; r.p.hmirror = mirror; r.p.hstate = hstate;    // (fine-grained host allocations: the host pointer is the device pointer)

@@ -118,11 +118,29 @@ struct icp_params {
 };
 #define ICP_REJECT_DIST_ON 0x80000000u   // icp_params::reject: the distance test is on (one scalar test of one word says whether anything is)
 #define ICP_REJECT_TRIM_ON 0x40000000u   // icp_params::reject: trimming is on (the REJ kernels, plus select and apply: icp_launch_trim)
+#define ICP_REJECT_ROBUST_SHIFT 28u
+#define ICP_REJECT_ROBUST_MASK 0x30000000u   // icp_params::reject: the robust loss (icp_set_robust_loss): ICP_ROBUST_* << 28, 0: off
 static_assert (sizeof (icp_params) == 480, "icp_params grew: the hidden kernel arguments of every kernel would move");
 
 // rejection on: the sum-W formulas in every mode, and a step of nothing accepted (sum W == 0) is the identity
 static __host__ __device__ __forceinline__ bool icp_rejecting (const icp_params &p) { return p.reject != 0u; }
 static __host__ __device__ __forceinline__ bool icp_trimming (const icp_params &p) { return (p.reject & ICP_REJECT_TRIM_ON) != 0u; }
+// the robust loss's kind (ICP_ROBUST_HUBER 1, CAUCHY 2, TUKEY 3; 0: off).  Its scale k is a device word (icp_robust_scale).
+static __host__ __device__ __forceinline__ uint32_t icp_robust (const icp_params &p) { return (p.reject & ICP_REJECT_ROBUST_MASK) >> ICP_REJECT_ROBUST_SHIFT; }
+// The robust loss's IRLS weight omega (u) of u = s^2 / k^2 (include/icp_amd.h), in double, each expression in the order written; NaN: 0
+static __host__ __device__ __forceinline__ double icp_robust_omega (uint32_t loss, double u)
+{
+    if (u != u) return 0.0;
+    if (loss == 1u) return u <= 1.0 ? 1.0 : 1.0 / sqrt (u);            // Huber
+    if (loss == 2u) return 1.0 / (1.0 + u);                             // Cauchy
+    return u < 1.0 ? (1.0 - u) * (1.0 - u) : 0.0;                        // Tukey
+}
+// An apply pass (k_trim_apply) rewrites the weights behind the search: trimming, or a robust loss on point-to-point (the plane metrics
+// weigh their pairs in k_plane_moments).  The route of every such iteration: per-query outputs stored every time, no chained form.
+static __host__ __device__ __forceinline__ bool icp_apply_pass (const icp_params &p)
+{
+    return icp_trimming (p) || (icp_robust (p) != 0u && p.metric == 0u);
+}
 
 // Trimming's buffers (icp_trim.hip) are uint32 words: [batch][4] the result of the last iteration (t bits, n, K, accepted: ICP_MEM_TRIM),
 // [batch][4] the state of the multi-block selection (prefix, rank left, count below, arrivals), [batch][2048] its histograms, and for
@@ -143,15 +161,17 @@ static __host__ __device__ __forceinline__ uint32_t icp_p2pl_nblk (uint32_t m) {
 
 // The moments' allocation p.mom, offsets in doubles.  icp_params has no room for more pointers, so everything the opt-in paths keep per
 // iteration lies behind the fused mode's moment partials: trimming's words, the plane system and its block partials, and colored ICP's
-// weight kappa, a device word (icp_set_color_weight writes it in stream order) that the run graphs read instead of capturing it.
+// weight kappa and the robust loss's scale k, device words (icp_set_color_weight and icp_set_robust_loss write them in stream order) that
+// the run graphs read instead of capturing them.
 struct icp_mom_layout {
     size_t trim;                 // trimming's uint32 words (icp_trim_area)
     size_t sys;                  // [batch][ICP_P2PL_SYS] ICP_MEM_PLANE_SYSTEM (icp_p2pl_area)
     size_t part;                 // [batch][ICP_P2PL_TERMS][icp_p2pl_nblk] the plane system's block partials (icp_p2pl_part)
     size_t kappa;                // the float word of kappa (icp_color_kappa)
+    size_t robust;               // the float word of the robust loss's scale k (icp_robust_scale)
     size_t total;
 };
-static inline icp_mom_layout icp_mom_layout_of (uint32_t batch, uint32_t m, uint32_t nb)
+static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (uint32_t batch, uint32_t m, uint32_t nb)
 {
     const size_t B = batch, trim_words = B * (8u + ICP_TRIM_BINS) + (m > ICP_TRIM_ONE_BLOCK_MAX ? B * m : 0u);
     icp_mom_layout l;
@@ -159,14 +179,17 @@ static inline icp_mom_layout icp_mom_layout_of (uint32_t batch, uint32_t m, uint
     l.sys = l.trim + (trim_words + 1u) / 2u;
     l.part = l.sys + B * ICP_P2PL_SYS;
     l.kappa = l.part + B * ICP_P2PL_TERMS * icp_p2pl_nblk (m);
-    l.total = l.kappa + 1u;
+    l.robust = l.kappa + 1u;
+    l.total = l.robust + 1u;
     return l;
 }
-static inline icp_mom_layout icp_mom_layout_of (const icp_params &p) { return icp_mom_layout_of (p.batch, p.m, p.nb); }
+static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (const icp_params &p) { return icp_mom_layout_of (p.batch, p.m, p.nb); }
 static inline uint32_t *icp_trim_area (const icp_params &p) { return reinterpret_cast<uint32_t *> (p.mom + icp_mom_layout_of (p).trim); }
 static inline double *icp_p2pl_area (const icp_params &p) { return p.mom + icp_mom_layout_of (p).sys; }
 static inline double *icp_p2pl_part (const icp_params &p) { return p.mom + icp_mom_layout_of (p).part; }
 static inline float *icp_color_kappa (const icp_params &p) { return reinterpret_cast<float *> (p.mom + icp_mom_layout_of (p).kappa); }
+// (also on the device: the robust kernels find the word from their icp_params, the loss-off kernels take no argument for it)
+static __host__ __device__ inline float *icp_robust_scale (const icp_params &p) { return reinterpret_cast<float *> (p.mom + icp_mom_layout_of (p).robust); }
 
 // The XP allocation of one RBC set, offsets in floats: [batch][m][8] the permuted database, then [batch][m] float4 NORMALS_F and
 // [batch][m] float4 COLOR_GRAD_F ([gx gy gz C] per fixed point).  The normals and gradients belong to the fixed frame as the RBC does,
@@ -269,6 +292,8 @@ void icp_launch_search_rej (const icp_params &p, hipStream_t s);            // i
 void icp_launch_chain_one_rej (const icp_params &p, hipStream_t s, uint32_t j, bool fresh, bool emit);
 void icp_launch_trim (const icp_params &p, hipStream_t s);                   // icp_trim.hip: k_trim_select (one or three launches) + k_trim_apply
 uint32_t icp_trim_launches (const icp_params &p);                             // how many that is
+void icp_launch_robust_apply (const icp_params &p, hipStream_t s);            // icp_robust.hip: k_trim_apply<fused, true> (a point-to-point robust loss)
+void icp_launch_plane_moments_robust (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);   // icp_robust.hip: k_plane_moments<colored, true>
 void icp_launch_p2pl_solve (const icp_params &p, hipStream_t s);             // icp_p2pl.hip: k_plane_moments<colored?> + k_p2pl_finalize
 void icp_launch_normals_grid (const icp_params &p, hipStream_t s);           // icp_p2pl.hip: k_normals_grid (+ colored: k_color_grad_grid), behind buildRBC
 #define ICP_P2PL_LAUNCHES 2u                                                  // launches of icp_launch_p2pl_solve

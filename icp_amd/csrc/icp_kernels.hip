@@ -578,20 +578,21 @@ void icp_launch_finalize (const icp_params &p, hipStream_t s)
 __global__ void k_nop (icp_params p) { if (p.m == 0xFFFFFFFFu) p.st->k = 0; }
 
 // The search of an iteration.  Trimming on (icp_trim.hip): the REJ search stores its per-query outputs every time — the selection reads
-// them —, then k_trim_select and k_trim_apply.  Point-to-plane on (icp_p2pl.hip): the outputs are stored every time too — the moments
+// them —, then k_trim_select and k_trim_apply.  A robust loss on point-to-point takes the same route (icp_apply_pass): k_trim_apply
+// weighs every pair, behind the selection if trimming is on too.  Point-to-plane on (icp_p2pl.hip): the outputs are stored every time too — the moments
 // read them —, and the search takes its reference-order form whatever the reduce mode: the same per-query outputs, and its prologue
 // publishes every iteration's (k, done) to a host-driven run (the fused form leaves a converged registration's word to the fused finalize).
 void icp_launch_search_stage (const icp_params &p, hipStream_t s)
 {
-    if (!icp_trimming (p) && !icp_p2pl (p)) { icp_launch_search (p, s); return; }
+    if (!icp_apply_pass (p) && !icp_p2pl (p)) { icp_launch_search (p, s); return; }
     icp_params q = p;
     q.emit = 1;
     if (icp_p2pl (p)) q.fused = 0;
     icp_launch_search (q, s);
-    if (icp_trimming (p)) icp_launch_trim (q, s);
+    if (icp_apply_pass (p)) icp_launch_trim (q, s);
 }
 
-// diagnostic: any subset of the iteration's kernels (bit 0 search — with trimming on, select and apply too —, 1 means, 2 sij, 3 finalize, 4 empty kernel)
+// diagnostic: any subset of the iteration's kernels (bit 0 search — with trimming or a point-to-point loss on, select and apply too —, 1 means, 2 sij, 3 finalize, 4 empty kernel)
 void icp_launch_masked (const icp_params &p, hipStream_t s, unsigned mask)
 {
     if (mask & 1u) icp_launch_search_stage (p, s);
@@ -608,9 +609,9 @@ void icp_launch_masked (const icp_params &p, hipStream_t s, unsigned mask)
 // removes outweighs every block re-deriving T), 2 always (sizes the second tree level of the prologue can hold).
 bool icp_chain_supported (const icp_params &p)
 {
-    // (trimming: the selection sits between the search and the finalize, which the chained form folds into one launch)
+    // (trimming, a point-to-point robust loss: the apply pass sits between the search and the finalize, which the chained form folds into one launch)
     // (point-to-plane: its own finalize, no chained form)
-    return p.fused && !icp_trimming (p) && !icp_p2pl (p) && p.nb <= 4096u && p.nr <= 1024u && (p.chain == 2 || (p.chain == 1 && !icp_dense (p)));
+    return p.fused && !icp_apply_pass (p) && !icp_p2pl (p) && p.nb <= 4096u && p.nr <= 1024u && (p.chain == 2 || (p.chain == 1 && !icp_dense (p)));
 }
 
 // launch j of a chain (icp_search.h: ks_launch_chain_one)

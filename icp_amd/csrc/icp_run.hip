@@ -286,8 +286,9 @@ int materialize_outputs (icp_context *h, int mem)
     if (!h->outputs_stale) return ICP_OK;
     icp_params q = h->p;
     q.st = q.st_prev; q.check = 0; q.emit = 1; q.hmirror = nullptr; q.hstate = nullptr;
-    // (with trimming on the outputs are never left to this — run_begin stores them every iteration, icp_set_trimming materialises before
-    // it switches —: the trim stage here is defensive, so that the weights read back are the trimmed ones whatever path gets here)
+    // (with an apply pass — trimming, a point-to-point robust loss: icp_apply_pass — the outputs are never left to this: run_begin stores
+    // them every iteration, and the setters materialise before they switch.  The stage here is defensive, so that the weights read back
+    // are the applied ones whatever path gets here)
     icp_launch_search_stage (q, h->stream);
     HIPCHK (h, hipGetLastError ());
     h->outputs_stale = false;

@@ -7,28 +7,16 @@
 // (k_finalize_fused<ROT, true>, or k_means / k_sij / k_finalize).  A trimmed pair is then exactly a rejected pair, and the oracle's
 // pieces with the trimmed rows zeroed give the same bits.  None of the existing kernels carries any of this code.
 //
-// The key of a pair is the bit pattern of its geo = (ex - f0)^2 + (ey - f1)^2 + (ez - f2)^2 in fp32, summed in that order (the
-// translation unit is built with -ffp-contract=off): a non-negative float orders as its bits do as uint32.  A pair that is no
-// candidate — weight 0, geo not finite, no query — gets the key ~0u, above every candidate's.
+// The key of a pair and the apply pass are in icp_trim_apply.h (a point-to-point robust loss instantiates the pass in icp_robust.hip).
 //
 // The selection is a radix select on 11 / 11 / 10-bit digits: a histogram of the digit over the keys that match the digits picked so
 // far, then the bin that holds the remaining rank.  Up to ICP_TRIM_ONE_BLOCK_MAX pairs per registration one workgroup does all three
 // passes with the keys in registers and the histogram in LDS (grid.y = registration); beyond it every pass is a launch of many
 // workgroups whose LDS histograms are merged by device atomics, and the workgroup that arrives last picks the bin (k_trim_select_pass).
 // Both take the same t: the K-th smallest key is one number.
-#include "icp_search.h"
+#include "icp_trim_apply.h"             // (TRIM_NONE, trim_key)
 
 namespace {
-
-constexpr uint32_t TRIM_NONE = 0xFFFFFFFFu;     // the key of a pair that is no candidate
-
-__device__ __forceinline__ uint32_t trim_key (float4 f, float4 q)
-{
-    if (f.w == 0.f) return TRIM_NONE;
-    const float gx = q.x - f.x, gy = q.y - f.y, gz = q.z - f.z;
-    const float geo = (gx * gx + gy * gy) + gz * gz;
-    return geo < __builtin_inff () ? __float_as_uint (geo) : TRIM_NONE;      // (NaN and +inf: no candidate)
-}
 
 // pass d of the select: the digit's shift and width, and the shift above which a key must match the prefix picked so far
 __device__ __forceinline__ uint32_t trim_shift (int d) { return d == 0 ? 21u : d == 1 ? 10u : 0u; }
@@ -195,77 +183,30 @@ __global__ __launch_bounds__ (256) void k_trim_select_pass (icp_params p, uint32
     }
 }
 
-// ------------------------------------------------------------------------------------------
-// k_trim_apply<FUSED> — one wave per block of the search, grid (nb | 2 nwg, batch).  Pair e of the block is the search's query e
-// (fused: fused_query_index of tile blockIdx.x; reference order: group blockIdx.x / 2, parity blockIdx.x & 1).  A trimmed pair's
-// weight becomes +0 in PF.w (the W output); then the block's partials are written again from PF / PM as ks_epilogue computes them:
-// the 18 double moments of its 64 pairs (an accepted pair's terms from the same floats, a trimmed pair's exact zeros) through the
-// same halving tree into p.mom's slot of the tile, or the weight partial (row_tree4) into p.wpart.
-// ------------------------------------------------------------------------------------------
-template <bool FUSED>
-__global__ __launch_bounds__ (64) void k_trim_apply (icp_params p, const uint32_t *area, uint32_t tpr_magic)
-{
-    __shared__ double s_mom[FUSED ? ICP_NMOM : 1][64];
-    __shared__ float s_w[64];
-    const uint32_t b = blockIdx.y, lane = threadIdx.x, m = p.m;
-    if (p.check && p.st[b].done) return;
-    const uint32_t t = area[4u * b], K = area[4u * b + 2u];
-    const uint32_t i = FUSED ? fused_query_index (m, p.side, tpr_magic, blockIdx.x, lane) : (blockIdx.x >> 1) * 128u + 2u * lane + (blockIdx.x & 1u);
-    const bool v = i < m;
-    float4 f = make_float4 (0.f, 0.f, 0.f, 0.f), q = f;
-    if (v) { f = p.PF[(size_t) b * m + i]; q = p.PM[(size_t) b * m + i]; }
-    const uint32_t key = v ? trim_key (f, q) : TRIM_NONE;
-    const bool acc = key != TRIM_NONE && K != 0u && key <= t;
-    if (v && f.w != 0.f && !acc) reinterpret_cast<float *> (p.PF + (size_t) b * m + i)[3] = 0.f;
-    if constexpr (FUSED) {
-        // (ks_epilogue's products, term for term)
-        double W = acc ? (double) f.w : 0.0;
-        double g0 = acc ? (double) f.x : 0.0, g1 = acc ? (double) f.y : 0.0, g2 = acc ? (double) f.z : 0.0;
-        double q0 = acc ? (double) q.x : 0.0, q1 = acc ? (double) q.y : 0.0, q2 = acc ? (double) q.z : 0.0;
-        double wq0 = W * q0, wq1 = W * q1, wq2 = W * q2;
-        s_mom[0][lane] = W;
-        s_mom[1][lane] = W * g0; s_mom[2][lane] = W * g1; s_mom[3][lane] = W * g2;
-        s_mom[4][lane] = wq0; s_mom[5][lane] = wq1; s_mom[6][lane] = wq2;
-        s_mom[7][lane] = wq0 * g0; s_mom[8][lane] = wq0 * g1; s_mom[9][lane] = wq0 * g2;
-        s_mom[10][lane] = wq1 * g0; s_mom[11][lane] = wq1 * g1; s_mom[12][lane] = wq1 * g2;
-        s_mom[13][lane] = wq2 * g0; s_mom[14][lane] = wq2 * g1; s_mom[15][lane] = wq2 * g2;
-        s_mom[16][lane] = W * ((g0 * g0 + g1 * g1) + g2 * g2);
-        s_mom[17][lane] = W * ((q0 * q0 + q1 * q1) + q2 * q2);
-        __syncthreads ();
-        // the search's halving tree over the 64 pairs, one 16-lane row per moment (four moments per round)
-        const uint32_t l = lane & 15u;
-        double *mom = p.mom + (size_t) b * 2 * ICP_NMOM * p.nb;
-#pragma unroll
-        for (uint32_t r = 0; r < (ICP_NMOM + 3u) / 4u; ++r) {
-            const uint32_t mrow = r * 4u + (lane >> 4), k = min (mrow, (uint32_t) ICP_NMOM - 1u);
-            double c0 = s_mom[k][l] + s_mom[k][l + 32], c1 = s_mom[k][l + 16] + s_mom[k][l + 48];
-            double s = row_tree_tail_d (c0 + c1);
-            if (l == 0 && mrow < ICP_NMOM) mom[(size_t) mrow * p.nb + blockIdx.x] = s;
-        }
-    } else {
-        s_w[lane] = acc ? f.w : 0.f;
-        __syncthreads ();
-        const uint32_t l = lane & 15u;
-        float a[4] = { s_w[l], s_w[l + 16], s_w[l + 32], s_w[l + 48] };
-        float s = row_tree4 (a);
-        if (lane == 0) p.wpart[(size_t) b * 2 * p.nwp + blockIdx.x] = s;
-    }
-}
+#define ICP_APPLY_NAME k_trim_apply
+#define ICP_APPLY_ROBUST false
+#include "icp_trim_apply.inc"
 
 }  // namespace
 
-uint32_t icp_trim_launches (const icp_params &p) { return (p.m <= ICP_TRIM_ONE_BLOCK_MAX ? 1u : 3u) + 1u; }
+uint32_t icp_trim_launches (const icp_params &p)
+{
+    return (icp_trimming (p) ? (p.m <= ICP_TRIM_ONE_BLOCK_MAX ? 1u : 3u) : 0u) + 1u;
+}
 
 void icp_launch_trim (const icp_params &p, hipStream_t s)
 {
     uint32_t *area = icp_trim_area (p);
-    if (p.m <= ICP_TRIM_ONE_BLOCK_MAX) hipLaunchKernelGGL (k_trim_select, dim3 (1, p.batch), dim3 (1024), 0, s, p, area);
+    if (!icp_trimming (p)) {}
+    else if (p.m <= ICP_TRIM_ONE_BLOCK_MAX) hipLaunchKernelGGL (k_trim_select, dim3 (1, p.batch), dim3 (1024), 0, s, p, area);
     else {
         const dim3 grid ((p.m + 2047u) / 2048u, p.batch);
         hipLaunchKernelGGL (k_trim_select_pass<0>, grid, dim3 (256), 0, s, p, area);
         hipLaunchKernelGGL (k_trim_select_pass<1>, grid, dim3 (256), 0, s, p, area);
         hipLaunchKernelGGL (k_trim_select_pass<2>, grid, dim3 (256), 0, s, p, area);
     }
+    // (a robust loss on the plane metrics weighs its pairs in k_plane_moments: the apply pass is trimming's alone there)
+    if (icp_robust (p) != 0u && !icp_p2pl (p)) { icp_launch_robust_apply (p, s); return; }
     if (p.fused) hipLaunchKernelGGL (k_trim_apply<true>, dim3 (p.nb, p.batch), dim3 (64), 0, s, p, (const uint32_t *) area, icp_tpr_magic (p.side));
     else hipLaunchKernelGGL (k_trim_apply<false>, dim3 (2 * p.nwg, p.batch), dim3 (64), 0, s, p, (const uint32_t *) area, icp_tpr_magic (p.side));
 }

@@ -7,18 +7,19 @@ import time
 
 import numpy as np
 
-from . import ICP, ErrorMetric, Memory, Normals, PowerMode, ReduceMode
+from . import ICP, ErrorMetric, Memory, Normals, PowerMode, ReduceMode, RobustLoss
 from .io import load_pc8d, save_pc8d
 
 
 def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, angle_threshold=0.001,
                     translation_threshold=0.01, reduce_mode=ReduceMode.FUSED, reject_invalid=False, max_dist=None, trim=1.0,
-                    point_to_plane=None, colored=None):
+                    point_to_plane=None, colored=None, robust=None):
     """Returns (T[8], k, latency_ms, transformed moving cloud).  reject_invalid / max_dist: correspondence rejection
     (ICPStep.set_rejection), trim: the fraction of pairs trimmed ICP keeps (ICPStep.set_trimming; 1.0: off), point_to_plane: mu of
     point-to-plane ICP with the fixed frame's normals from its 128 x 128 landmark grid (ICPStep.set_error_metric; None: off),
     colored: kappa of colored ICP, with grid normals and intensity gradients and mu = point_to_plane or 0 (ICPStep.set_color_weight;
-    None: off); none is the reference's behaviour, all are off by default."""
+    None: off), robust: (RobustLoss kind, scale) of a robust loss (ICPStep.set_robust_loss; None: off); none is the reference's
+    behaviour, all are off by default."""
     reg = ICP(device)
     reg.init(16384, 256, a, c, max_iterations, angle_threshold, translation_threshold)   # src/ocl_icp_reg.cpp:81-88
     reg.setPowerMode(PowerMode.SQUARED)
@@ -27,6 +28,8 @@ def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, a
         reg.set_rejection(reject_invalid, max_dist)
     if trim != 1.0:
         reg.set_trimming(trim)
+    if robust is not None:
+        reg.set_robust_loss(*robust)
     if colored is not None:
         reg.set_normals(Normals.GRID, 128)
         reg.set_color_weight(colored)
@@ -77,6 +80,20 @@ def _point_weight(s):
     return v
 
 
+def _robust(s):
+    """KIND:SCALE, e.g. tukey:50 -> (RobustLoss kind, scale); KIND is huber, cauchy or tukey, SCALE finite and > 0."""
+    kind, sep, scale = s.partition(":")
+    if kind.lower() not in ("huber", "cauchy", "tukey") or not sep:
+        raise argparse.ArgumentTypeError("must be KIND:SCALE with KIND huber, cauchy or tukey, got %s" % s)
+    try:
+        v = float(scale)
+    except ValueError:
+        raise argparse.ArgumentTypeError("SCALE must be a number, got %s" % s)
+    if not (v > 0.0 and math.isfinite(v)):
+        raise argparse.ArgumentTypeError("SCALE must be finite and > 0, got %s" % s)
+    return RobustLoss.NAMES[kind.lower()], v
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("fixed")
@@ -96,10 +113,13 @@ def main(argv=None):
     ap.add_argument("--colored", type=_point_weight, default=None, metavar="KAPPA",
                     help="colored ICP: point-to-plane plus KAPPA (>= 0) times the photometric term, normals and intensity gradients "
                          "from the fixed landmark grid; MU of --point-to-plane when given, else 0 (not reference behaviour)")
+    ap.add_argument("--robust", type=_robust, default=None, metavar="KIND:SCALE",
+                    help="robust loss: huber, cauchy or tukey with the scale SCALE (> 0, mm), e.g. tukey:50; every pair is "
+                         "down-weighted by its own residual (not reference behaviour)")
     args = ap.parse_args(argv)
     T, k, ms, out = register_clouds(load_pc8d(args.fixed), load_pc8d(args.moving), args.device, a=args.alpha,
                                     reject_invalid=args.reject_invalid, max_dist=args.max_dist, trim=args.trim,
-                                    point_to_plane=args.point_to_plane, colored=args.colored)
+                                    point_to_plane=args.point_to_plane, colored=args.colored, robust=args.robust)
     q, t, s = T[:4], T[4:7], T[7]
     sinth_2 = float(np.linalg.norm(q[:3]))
     angle = 180.0 / math.pi * 2 * math.atan2(sinth_2, float(q[3]))

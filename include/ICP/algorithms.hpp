@@ -45,6 +45,15 @@ namespace icp
     /*! \brief The objective of an iteration (setErrorMetric; include/icp_amd.h): the values of ICP_METRIC_*, usable as int. */
     struct ErrorMetric { enum : int { POINT_TO_POINT = ICP_METRIC_POINT_TO_POINT, POINT_TO_PLANE = ICP_METRIC_POINT_TO_PLANE, COLORED = ICP_METRIC_COLORED }; };
 
+    /*! \brief A robust loss and its scale (setRobustLoss; include/icp_amd.h): `loss` one of the values of ICP_ROBUST_*, `scale` k in the
+     *         cloud's units (finite, > 0 with a loss on; ignored and read back as 0 with NONE). */
+    struct RobustLoss
+    {
+        enum : int { NONE = ICP_ROBUST_NONE, HUBER = ICP_ROBUST_HUBER, CAUCHY = ICP_ROBUST_CAUCHY, TUKEY = ICP_ROBUST_TUKEY };
+        int loss = NONE;
+        float scale = 0.f;
+    };
+
     struct Vector3f
     {
         float v[3] = { 0.f, 0.f, 0.f };
@@ -607,6 +616,12 @@ namespace ICP
          *         ICP_REJECT_INVALID alongside it. */
         void setTrimming (float keep_fraction) { check (icp_set_trimming (h, keep_fraction)); }
         float getTrimming () { float f = 1.f; check (icp_get_trimming (h, &f)); return f; }
+
+        /*! \brief Robust loss (icp_set_robust_loss, include/icp_amd.h; not in the reference, off by default): every pair's weight is
+         *         multiplied by the loss's IRLS weight of its own residual, for every error metric.  ICP_ROBUST_NONE: off. */
+        void setRobustLoss (int loss, float scale = 0.f) { check (icp_set_robust_loss (h, loss, scale)); }
+        void setRobustLoss (const icp::RobustLoss &r) { setRobustLoss (r.loss, r.scale); }
+        icp::RobustLoss getRobustLoss () { icp::RobustLoss r; check (icp_get_robust_loss (h, &r.loss, &r.scale)); return r; }
 
         /*! \brief Point-to-plane ICP (icp_set_error_metric, include/icp_amd.h; not in the reference, off by default): metric
          *         ICP_METRIC_POINT_TO_PLANE minimises the point-to-plane error plus point_weight (mu >= 0) times the point-to-point

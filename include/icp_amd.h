@@ -333,6 +333,43 @@ int icp_get_error_metric (icp_handle h, int *metric, float *point_weight);
 int icp_set_color_weight (icp_handle h, float kappa);
 int icp_get_color_weight (icp_handle h, float *kappa);
 
+/* Robust loss (an M-estimator as iteratively reweighted least squares; not reference behaviour; off by default): every pair is
+ * down-weighted by the size of its own residual, for every error metric.  The rule:
+ *   - loss = ICP_ROBUST_NONE (the default) is off: the same kernels, launches, graphs and bits as without it; the scale is ignored and
+ *     icp_get_robust_loss returns (0, 0.f).  For any other loss the scale k is finite and > 0, in the cloud's units (mm for Kinect data).
+ *   - The weight of a residual of squared size s2 is omega (u), in double: k2 = (double) k * (double) k, u = s2 / k2, and
+ *         HUBER   u <= 1.0 ? 1.0 : 1.0 / sqrt (u)             (rho (s) = s^2 / 2 for s <= k, k s - k^2 / 2 beyond)
+ *         CAUCHY  1.0 / (1.0 + u)                             (rho (s) = (k^2 / 2) log (1 + s^2 / k^2))
+ *         TUKEY   u < 1.0 ? (1.0 - u) * (1.0 - u) : 0.0       (rho (s) = (k^2 / 6) (1 - (1 - s^2 / k^2)^3) for s <= k, k^2 / 6 beyond)
+ *     omega = rho'(s) / s; omega = 0 when u is NaN (u = +inf gives 0 by each formula).  Every expression in the order written, with no
+ *     contraction.
+ *   - Point-to-point: s2 = (double) geo, the rejection rule's fp32 quantity.  The loss acts after rejection and trimming: every pair
+ *     they leave with w != 0 gets W' = (float) ((double) w * omega (u)), and ICP_MEM_W holds W'.  A pair whose W' is 0 is exactly a
+ *     rejected pair (its correspondence kept, its moment, mean and S terms exact zeros).  As with rejection, REGULAR mode uses the
+ *     sum-W formulas, and an iteration with sum W == 0 is the identity step (ICP::run stops).  The per-query outputs are stored by
+ *     every iteration, and an iteration is the separate form: the search, trimming's selection (when trimming is on too), the pass
+ *     that applies the weights, the usual tail (icp_run_form, icp_launches_per_iteration).
+ *   - Point-to-plane and colored, with the point-to-plane rule's r, d, mu and the colored rule's kappa and r_C:
+ *         sG2 = r * r + mu * ((dx * dx + dy * dy) + dz * dz),  wG = omega (sG2 / k2)        (point-to-plane with its point-to-point share)
+ *         sC2 = kappa * (r_C * r_C),                         wC = omega (sC2 / k2)        (colored: sqrt (kappa) r_C is in the cloud's units)
+ *         term (a, b):  w * ((wG * (J_a J_b + mu G_ab)) + (kappa * wC) * (J_Ca J_Cb))
+ *         term 21 + a:  w * ((wG * (J_a r + mu g_a)) + (kappa * wC) * (J_Ca r_C))
+ *     point-to-plane without the photometric part: w * (wG * (J_a J_b + mu G_ab)) and w * (wG * (J_a r + mu g_a)).  wG == 0 selects an
+ *     exact zero for the geometric part and wC == 0 for the photometric part (selections, not products: a non-finite residual makes
+ *     no NaN); w == 0 still selects zeros for the whole pair.  ICP_MEM_W keeps the search's weight (with rejection's and trimming's
+ *     zeros); the factors show only in ICP_MEM_PLANE_SYSTEM.  omega = 1 gives the loss-off system (up to the sign of a zero).
+ *   - Turning the loss on or off, or changing its kind, captures the graphs anew (as icp_set_trimming does).  A new scale while the loss
+ *     stays on is a parameter update: it takes effect in already captured run graphs, as kappa does.
+ *   - The setting applies to single, batched (icp_init_batched), icp_batch_* and tracked (icp_track_*) registrations and survives
+ *     icp_init.
+ * ICP_EINVAL: an unknown loss, or a scale that is not finite and > 0 with a loss on. */
+#define ICP_ROBUST_NONE 0
+#define ICP_ROBUST_HUBER 1
+#define ICP_ROBUST_CAUCHY 2
+#define ICP_ROBUST_TUKEY 3
+int icp_set_robust_loss (icp_handle h, int loss, float scale);
+int icp_get_robust_loss (icp_handle h, int *loss, float *scale);
+
 /* Where the fixed frame's normals come from (point-to-plane):
  *   ICP_NORMALS_GIVEN (the default): the user writes ICP_MEM_NORMALS_F (m x float4 [nx ny nz 0] per registration, indexed like F);
  *     it is used as given and starts as zeros.  grid_width is ignored (pass 0).
@@ -535,6 +572,7 @@ int icp_batch_init (icp_batch_handle b, uint32_t registrations, uint32_t m, uint
 int icp_batch_set_modes (icp_batch_handle b, int reduce_mode, int power_mode);
 int icp_batch_set_rejection (icp_batch_handle b, int flags, float max_dist);                /* icp_set_rejection on every slot */
 int icp_batch_set_trimming (icp_batch_handle b, float keep_fraction);                        /* icp_set_trimming on every slot */
+int icp_batch_set_robust_loss (icp_batch_handle b, int loss, float scale);                   /* icp_set_robust_loss on every slot */
 int icp_batch_set_error_metric (icp_batch_handle b, int metric, float point_weight);         /* icp_set_error_metric on every slot */
 int icp_batch_set_normals (icp_batch_handle b, int source, uint32_t grid_width);             /* icp_set_normals on every slot */
 int icp_batch_set_color_weight (icp_batch_handle b, float kappa);                            /* icp_set_color_weight on every slot */

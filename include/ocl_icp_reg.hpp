@@ -75,6 +75,10 @@ public:
     /*! \brief Trimmed ICP of the registration (ICPStep::setTrimming; not in the reference's demo, off by default). */
     void setTrimming (float keep_fraction) { reg.setTrimming (keep_fraction); }
     float getTrimming () { return reg.getTrimming (); }
+    /*! \brief Robust loss of the registration (ICPStep::setRobustLoss; not in the reference's demo, off by default). */
+    void setRobustLoss (int loss, float scale = 0.f) { reg.setRobustLoss (loss, scale); }
+    void setRobustLoss (const icp::RobustLoss &r) { reg.setRobustLoss (r); }
+    icp::RobustLoss getRobustLoss () { return reg.getRobustLoss (); }
     /*! \brief Point-to-plane ICP of the registration (ICPStep::setErrorMetric / setNormals; not in the reference's demo, off by default). */
     void setErrorMetric (int metric, float point_weight = 0.f) { reg.setErrorMetric (metric, point_weight); }
     void getErrorMetric (int &metric, float &point_weight) { reg.getErrorMetric (metric, point_weight); }
