@@ -48,11 +48,16 @@ class Float64ICP:
         self.a, self.c, self.weighted, self.fg = float(a), float(c), bool(weighted), float(dist_scale)
         self.R, self.t, self.s = np.eye(3), np.zeros(3), 1.0
 
-    def step(self, ids):
+    def step(self, ids, weights=None):
+        """weights: given per-pair weights (a robust loss's W', rejection's zeros) instead of the ones derived from the distances; a
+        pair of weight 0 takes no part, whatever its points hold."""
         ids = np.asarray(ids, np.int64)
         tM = self.s * (self.M[:, :3] @ self.R.T) + self.t
         NN = self.F[ids, :3]
-        if self.weighted:
+        if weights is not None:
+            w = np.asarray(weights, np.float64)
+            tM, NN = np.where(w[:, None] != 0, tM, 0.0), np.where(w[:, None] != 0, NN, 0.0)
+        elif self.weighted:
             geo = ((tM - NN) ** 2).sum(1)
             pho = ((self.M[:, 4:7] - self.F[ids, 4:7]) ** 2).sum(1)
             w = 100.0 / (100.0 + self.fg * (geo + self.a * pho))
@@ -68,6 +73,11 @@ class Float64ICP:
         tk = mf - sk * (Rk @ mm)
         self.R, self.t, self.s = Rk @ self.R, sk * (Rk @ self.t) + tk, sk * self.s
         return Rk, tk, sk
+
+    def set_T(self, T):
+        """Start from the engine's [q | t, s]."""
+        T = np.asarray(T, np.float64)
+        self.R, self.t, self.s = quat_to_rot(T[:4] / np.linalg.norm(T[:4])), T[4:7].copy(), float(T[7])
 
     @property
     def T(self):

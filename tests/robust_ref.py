@@ -166,3 +166,53 @@ def plane_step(PF, PM, ids, normals, mu, loss, scale, T, R, grads=None, M=None, 
     Tk = p2pl.increment(x)
     Tn, Rn, Rk = p2pl.compose(T, R, Tk)
     return system, Tn, Rn, Tk, Rk
+
+
+# ---- the edge scene: pairs whose u = s2 / k2 is known to the bit ----------------------------------------------------------------------
+
+IDENTITY_T = np.array([0, 0, 0, 1, 0, 0, 0, 1], F32)
+EDGE_CLASSES = ("zero", "at_k", "below_k", "above_k", "half_k", "two_k", "subnormal_geo", "far")
+
+
+def edge_offsets(k):
+    """The eight z offsets of the edge scene for the scale k (fp32): 0, k, one ulp below and above k, k / 2, 2 k, 1e-20 (its square is
+    a float subnormal) and 192 (a far outlier); named by EDGE_CLASSES."""
+    k = F32(k)
+    return np.array([0.0, k, np.nextafter(k, F32(0)), np.nextafter(k, F32(np.inf)), k / F32(2), F32(2) * k, F32(1e-20), 192.0], F32)
+
+
+def edge_scene(side, template, offsets):
+    """(F, M, class of every point): F a flat grid x = 64 (col + 1), y = 64 (row + 1), z = 0 of one colour (the other words as in
+    `template`, m x 8), M = F with z = offsets[i % len (offsets)].  Under the identity transform geo of pair i is fp32 (offset^2) exactly
+    and every query's nearest neighbour is its own index (the grid step, 64, is far above every offset's share)."""
+    m = side * side
+    F = np.array(template, F32).reshape(m, 8).copy()
+    i = np.arange(m)
+    F[:, 0] = 64.0 * (i % side + 1)
+    F[:, 1] = 64.0 * (i // side + 1)
+    F[:, 2] = 0.0
+    F[:, 4:7] = 0.5
+    cls = i % len(offsets)
+    M = F.copy()
+    M[:, 2] = np.asarray(offsets, F32)[cls]
+    return F, M, cls
+
+
+def edge_geo(offsets):
+    """geo of each class in fp32: (0 * 0 + 0 * 0) + o * o."""
+    o = np.asarray(offsets, F32)
+    return (o * o).astype(F32)
+
+
+def intensity_channel(target):
+    """A float32 r with ((r + 0) + 0) / 3 == target in fp32 (colored_ref.intensity of the colour (r, 0, 0)), searched among the floats
+    next to 3 * target; None when there is none."""
+    target = F32(target)
+    r = F32(3) * target
+    lo = hi = r
+    for _ in range(8):
+        for c in (lo, hi):
+            if F32(c) / F32(3) == target:
+                return F32(c)
+        lo, hi = np.nextafter(lo, F32(-np.inf)), np.nextafter(hi, F32(np.inf))
+    return None

@@ -353,3 +353,202 @@ def test_rejection_dense_layouts(engine, oracle, side, nr, batch, fused):
     for b, (F, M) in enumerate(pairs):
         check_one_step(engine, oracle, g, F, M, T, side, nr, fused, WEIGHTED, POWER, fused, True, md, b=b)
     g.close()
+
+
+# ---- 4. the robust loss at the sizes where its kernels branch ---------------------------------------------------------------------
+#
+# tests/test_gpu_robust_loss.py runs every check at side 128 with 256 representatives.  Here its checks, unchanged, reach: m < 64 and
+# one partly filled block of the apply pass, fused mode's linear 64-query blocks (a side that is no multiple of 8) also beyond 16384
+# pairs, the dense search layouts (single, batched, masked, several representative tiles), the loss behind trimming's three-pass
+# select, m = 2^20 (k_moment_level1 in front of the finalize); for the plane metrics the clamp ic = min (i, m - 1) with a partly filled
+# last block and the finalize's padded multi-pass tree; and batches whose registrations stop at different iterations (both robust
+# kernels return for a registration that is done).
+
+import robust_ref as rref                                        # noqa: E402
+import test_gpu_robust_loss as rl                                # noqa: E402
+
+ROBUST_DENSE = [(256, 256, 1), (128, 64, 3), (256, 1024, 1), (192, 2048, 1)]
+
+
+def _robust_p2p_step(engine, oracle, pairs, side, nr, fused, loss, invalid=True, keep=1.0):
+    """One step from _t0 () of a handle with len (pairs) registrations, every registration by check_p2p.  Returns the handle and W'."""
+    T, n = _t0(), len(pairs)
+    g = rl.p2p_handle(engine, side * side, nr, fused, WEIGHTED, POWER, fused, loss, rl.SCALE[loss], invalid=invalid, keep=keep, batch=n)
+    for b, (F, M) in enumerate(pairs):
+        g.write(engine.Memory.F, F, batch_index=b); g.write(engine.Memory.M, M, batch_index=b)
+    g.buildRBC()
+    for b in range(n):
+        g.write(engine.Memory.T, T, batch_index=b, block=True)
+    g.step()
+    Ws = [rl.check_p2p_or_identity(oracle, g, engine, M, T, side, fused, WEIGHTED, POWER, fused, invalid=invalid, keep=keep, loss=loss,
+                                   scale=rl.SCALE[loss], b=b)[0] for b, (F, M) in enumerate(pairs)]
+    return g, Ws
+
+
+@pytest.mark.parametrize("loss", rl.LOSSES)
+@pytest.mark.parametrize("side,nr", TINY + [(150, 4)])
+@pytest.mark.parametrize("fused", [True, False])
+def test_robust_p2p_tiny_and_odd(engine, oracle, side, nr, fused, loss):
+    """m < 64, one partly filled block, linear 64-query blocks (also at m = 22500), with invalid points planted by hand.  Below side
+    30 the grid is so coarse that every residual is beyond Tukey's 30 mm: those cases are the identity step (nothing accepted)."""
+    g, (W,) = _robust_p2p_step(engine, oracle, [_tiny_pair(engine, side)], side, nr, fused, loss)
+    assert np.count_nonzero(W == 0) > 0                                # (the planted invalid pairs at least)
+    g.close()
+
+
+@pytest.mark.parametrize("loss", rl.LOSSES)
+@pytest.mark.parametrize("side,nr,batch", ROBUST_DENSE)
+@pytest.mark.parametrize("fused", [True, False])
+def test_robust_p2p_dense_layouts(engine, oracle, side, nr, batch, fused, loss):
+    """The dense search layouts in front of the apply pass: single, batched, masked (|R| = 1024), several representative tiles."""
+    pairs = [_holes(engine, side, 0x7E6 + 11 * b, "blobs30" if b % 2 == 0 else "scattered10") for b in range(batch)]
+    g, Ws = _robust_p2p_step(engine, oracle, pairs, side, nr, fused, loss)
+    if fused:
+        assert g.search_layout()[0] == 1, g.search_layout()           # (a dense layout)
+    for W in Ws:
+        assert 0 < np.count_nonzero(W) < W.size
+    g.close()
+
+
+@pytest.mark.parametrize("loss", rl.LOSSES)
+@pytest.mark.parametrize("side,nr", TRIM_SHAPES)
+@pytest.mark.parametrize("fused", [True, False])
+def test_robust_p2p_behind_the_large_select(engine, oracle, side, nr, fused, loss):
+    """keep = 0.8 at m > 16384: the loss weighs what the three-pass select accepts."""
+    g, (W,) = _robust_p2p_step(engine, oracle, [_holes(engine, side, 0x7E7 + side)], side, nr, fused, loss, keep=0.8)
+    t = g.read(engine.Memory.TRIM)
+    assert 0 < t[2] <= t[3] < t[1] and np.count_nonzero(W) <= t[3], t
+    g.close()
+
+
+def test_robust_p2p_at_2_pow_20(engine, oracle):
+    """m = 2^20 (config C), fused, Cauchy, one step: 16384 tiles, k_moment_level1 in front of the finalize."""
+    side, nr = 1024, 4096
+    F, M = engine.synth_pair(side, seed=0x9A1E + side)
+    g, (W,) = _robust_p2p_step(engine, oracle, [(F, M)], side, nr, True, rref.CAUCHY, invalid=False)
+    assert np.count_nonzero(W) == side * side
+    g.close()
+
+
+def _robust_plane_steps(engine, g, metric, loss, Ms, steps=2):
+    """`steps` steps of a loaded handle: every registration by check_plane, and by check_lstsq where its status word is 1."""
+    Mem = engine.Memory
+    for _ in range(steps):
+        T0 = [(g.read(Mem.T, b).copy(), g.read(Mem.R, b).ravel().copy()) for b in range(len(Ms))]
+        g.step()
+        for b, M in enumerate(Ms):
+            s = rl.check_plane(engine, g, metric, loss, rl.SCALE[loss], T0[b][0], T0[b][1], M=M, b=b)
+            assert check_lstsq(engine, g, b) == (s[27] == 1.0)
+            assert np.isfinite(s).all() and s[:27].any()
+
+
+# (every loss up to 102400 pairs; the two cases of about 10^6 pairs with one loss each, for the suite's time)
+ROBUST_PLANE_CASES = [(side, nr, loss) for side, nr in PLANE_SHAPES[:6] for loss in rl.LOSSES] + [(1000, 64, rref.TUKEY),
+                                                                                                  (1024, 4096, rref.CAUCHY)]
+
+
+@pytest.mark.parametrize("side,nr,loss", ROBUST_PLANE_CASES)
+def test_robust_point_to_plane_steps(engine, side, nr, loss):
+    F, M = engine.synth_pair(side, seed=0x9A1E + side)
+    g = rl.plane_handle(engine, side, nr, rl.P2PL, loss, rl.SCALE[loss])
+    p2pl.load(engine, g, F, M)
+    g.buildRBC()
+    _robust_plane_steps(engine, g, rl.P2PL, loss, [M])
+    g.close()
+
+
+@pytest.mark.parametrize("loss", rl.LOSSES)
+@pytest.mark.parametrize("side,nr", [(6, 4), (150, 4), (320, 256)])
+def test_robust_colored_steps(engine, side, nr, loss):
+    F, M, _ = engine.synth_pair_scene(side, engine.SCENE_WALL, seed=0xC01 + side)
+    g = rl.plane_handle(engine, side, nr, rl.COLORED, loss, rl.SCALE[loss])
+    p2pl.load(engine, g, F, M)
+    g.buildRBC()
+    _robust_plane_steps(engine, g, rl.COLORED, loss, [M])
+    g.close()
+
+
+def test_robust_point_to_plane_batch3_at_P512(engine):
+    """Three registrations of 102400 with Tukey on: each by the restatement and against a single handle."""
+    side, nr, n, loss = 320, 256, 3, rref.TUKEY
+    pairs = [engine.synth_pair(side, seed=0x7A00 + i, rot_deg=1.0 + 1.5 * i) for i in range(n)]
+    g = rl.plane_handle(engine, side, nr, rl.P2PL, loss, rl.SCALE[loss], batch=n)
+    for b, (F, M) in enumerate(pairs):
+        p2pl.load(engine, g, F, M, b)
+    g.buildRBC()
+    _robust_plane_steps(engine, g, rl.P2PL, loss, [M for _, M in pairs])
+    Mem = engine.Memory
+    for b in range(n):
+        h = rl.plane_handle(engine, side, nr, rl.P2PL, loss, rl.SCALE[loss])
+        p2pl.load(engine, h, *pairs[b])
+        h.buildRBC()
+        h.step(); h.step()
+        assert_bits(g.read(Mem.T, b), h.read(Mem.T), "T of registration %d" % b)
+        assert_bits(g.read(Mem.PLANE_SYSTEM, b), h.read(Mem.PLANE_SYSTEM), "system of registration %d" % b)
+        h.close()
+    g.close()
+
+
+@pytest.mark.parametrize("metric", [rl.P2PL, rl.COLORED])
+def test_robust_run_batch2_at_a_partial_block(engine, metric):
+    """ICP::run with Cauchy on, two registrations of 22500 against single handles: k, T, the system."""
+    side, nr, loss = 150, 4, rref.CAUCHY
+    if metric == rl.COLORED:
+        pairs = [engine.synth_pair_scene(side, engine.SCENE_WALL, seed=0x7B00 + i, rot_deg=1.0 + 2.0 * i)[:2] for i in range(2)]
+    else:
+        pairs = [engine.synth_pair(side, seed=0x7B00 + i, rot_deg=1.0 + 2.0 * i) for i in range(2)]
+    mk = lambda batch=1: rl.plane_handle(engine, side, nr, metric, loss, rl.SCALE[loss], batch=batch)
+    g = mk(2)
+    for b, (F, M) in enumerate(pairs):
+        p2pl.load(engine, g, F, M, b)
+    g.buildRBC()
+    g.run()
+    Mem = engine.Memory
+    for b, (F, M) in enumerate(pairs):
+        h = mk()
+        p2pl.load(engine, h, F, M)
+        h.buildRBC()
+        k = h.run()
+        assert 1 < k <= 40, k
+        assert g.state(b).k == k, (b, g.state(b).k, k)
+        assert_bits(g.read(Mem.T, b), h.read(Mem.T), "T of registration %d" % b)
+        assert_bits(g.read(Mem.PLANE_SYSTEM, b), h.read(Mem.PLANE_SYSTEM), "system of registration %d" % b)
+        h.close()
+    g.close()
+
+
+@pytest.mark.parametrize("side,nr", [(64, 64), (128, 64)])
+@pytest.mark.parametrize("fused", [True, False])
+def test_robust_p2p_batch3_runs_end_at_different_iterations(engine, side, nr, fused):
+    """ICP::run with Cauchy on, three registrations whose pairs start 0.5, 3 and 6 degrees apart, against three single handles: a
+    registration that is done is skipped by the apply pass while the others go on."""
+    n, loss = 3, rref.CAUCHY
+    pairs = [engine.synth_pair(side, seed=0x7C00 + i, rot_deg=(0.5, 3.0, 6.0)[i]) for i in range(n)]
+
+    def handle(batch):
+        g = engine.ICP(0)
+        g.init(side * side, nr, A, C_, angle_threshold=0.01, translation_threshold=0.05, batch=batch)
+        set_modes(engine, g, power_fast=fused, fused=fused)
+        g.set_robust_loss(loss, rl.SCALE[loss])
+        return g
+
+    Mem = engine.Memory
+    g = handle(n)
+    for b, (F, M) in enumerate(pairs):
+        g.write(Mem.F, F, batch_index=b); g.write(Mem.M, M, batch_index=b)
+    g.buildRBC()
+    g.run()
+    ks = []
+    for b, (F, M) in enumerate(pairs):
+        h = handle(1)
+        h.write(Mem.F, F); h.write(Mem.M, M)
+        h.buildRBC()
+        ks.append(h.run())
+        assert g.state(b).k == ks[-1], (b, g.state(b).k, ks)
+        assert_bits(g.read(Mem.T, b), h.read(Mem.T), "T of registration %d" % b)
+        assert_bits(g.read(Mem.W, b), h.read(Mem.W), "W' of registration %d" % b)
+        assert_bits(g.read(Mem.SUM_W, b), h.read(Mem.SUM_W), "sum W of registration %d" % b)
+        assert np.array_equal(g.read(Mem.NN_ID, b)["id"], h.read(Mem.NN_ID)["id"]), b
+        h.close()
+    assert len(set(ks)) > 1 and min(ks) < 40, ks
+    g.close()

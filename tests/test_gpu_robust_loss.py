@@ -76,6 +76,23 @@ def check_p2p(oracle, g, engine, M, T, side, fused, weighted, rot, power_fast, i
     return W
 
 
+def check_p2p_or_identity(oracle, g, engine, M, T, side, fused, weighted, rot, power_fast, invalid=False, max_dist=None, keep=1.0,
+                          loss=ref.CAUCHY, scale=12.0, b=0):
+    """check_p2p, or — when the restatement's sum W is 0 — the header's identity step: W' all +0, sum W, means and S zero, T as it
+    was, Tk the identity.  Returns (W', whether nothing was accepted)."""
+    Mem = engine.Memory
+    W, sw, _, _, _ = p2p_expected(oracle, g, engine, M, T, side, fused, weighted, rot, power_fast, invalid, max_dist, keep, loss, scale, b)
+    if sw != 0:
+        return check_p2p(oracle, g, engine, M, T, side, fused, weighted, rot, power_fast, invalid, max_dist, keep, loss, scale, b), False
+    gW = g.read(Mem.W, batch_index=b)
+    assert_bits(gW, W, "W'")
+    assert (np.ascontiguousarray(gW).view(np.uint32) == 0).all() and g.read(Mem.SUM_W, batch_index=b)[0] == 0
+    assert (g.read(Mem.MEANS, batch_index=b) == 0).all() and (g.read(Mem.S, batch_index=b) == 0).all()
+    assert_bits(g.read(Mem.T, batch_index=b), T, "T behind a step that accepts nothing")
+    assert_bits(g.read(Mem.TK, batch_index=b), np.array([0, 0, 0, 1, 0, 0, 0, 1], np.float32), "Tk behind a step that accepts nothing")
+    return W, True
+
+
 def p2p_handle(engine, m, nr, fused, weighted, rot, power_fast, loss, scale, invalid=False, max_dist=None, keep=1.0, batch=1, it=40):
     g = engine.ICP(0, rot, weighted)
     g.init(m, nr, A, C_, it, batch=batch)

@@ -31,7 +31,7 @@ def test_setter_refuses_unknown_losses_and_bad_scales_with_a_message(L):
         for k in BAD_SCALES:
             assert L.icp_set_robust_loss(None, loss, k) == 1, (loss, k)
             assert "scale" in L.icp_last_error(None).decode(), (loss, k)
-    for loss, k in ((0, float("nan")), (0, -5.0), (2, 30.0), (3, 1e-30)):   # valid (NONE ignores the scale): only the null handle is refused
+    for loss, k in ((0, float("nan")), (0, -5.0), (2, 30.0), (3, 1e-30), (1, 1e-45), (2, 3e38)):   # valid (NONE ignores the scale; a subnormal scale is > 0): only the null handle is refused
         assert L.icp_set_robust_loss(None, loss, k) == 1
         assert "null handle" in L.icp_last_error(None).decode()
     l, k = C.c_int32(), C.c_float()
@@ -140,3 +140,69 @@ def test_omega_edges():
         assert w[0] == 1.0 and w[1] == 0.0 and w[2] == 0.0, (loss, w)
     assert ref.omega(ref.HUBER, 1.0) == 1.0 and ref.omega(ref.HUBER, 4.0) == 0.5
     assert ref.omega(ref.TUKEY, 1.0) == 0.0 and ref.omega(ref.CAUCHY, 1.0) == 0.5
+
+
+# ---- helpers of tests/test_gpu_robust_edges.py
+
+@pytest.mark.parametrize("side,nr", [(128, 256), (30, 4)])
+def test_edge_scene_is_exact_on_the_oracle(engine, oracle, side, nr):
+    """The identity transform reproduces M bit for bit, every query keeps its own index, geo of each class is fp32 (offset^2), and
+    u = geo / k^2 is 1 exactly for the class lifted by k = 8 and below 1 for k = 7.3 (fp32 geo below the double k^2)."""
+    template = engine.synth_pair(side)[0]
+    for k in (8.0, 7.3):
+        offsets = ref.edge_offsets(k)
+        F, M, cls = ref.edge_scene(side, template, offsets)
+        tM = oracle.transform_q(M, ref.IDENTITY_T)
+        assert np.array_equal(tM.view(np.uint32), M.view(np.uint32))
+        o = oracle.OracleICP(side * side, nr, 2e2, 1e-6, threads=8)
+        o.write_f(F); o.write_m(M)
+        o.build_rbc()
+        o.step()
+        assert np.array_equal(o.nn_id["id"], np.arange(side * side))
+        geo = ref.geo(F[o.nn_id["id"]], tM)
+        assert np.array_equal(geo.view(np.uint32), ref.edge_geo(offsets)[cls].view(np.uint32))
+        u = geo.astype(np.float64) / ref.k2(k)
+        at, below, above = (u[cls == c] for c in (1, 2, 3))
+        assert at.size >= side * side // 10
+        if k == 8.0:
+            assert (at == 1.0).all() and (below == 1.0 - 2.0 ** -23).all() and (above > 1.0).all()
+            assert (u[cls == 0] == 0).all() and (geo[cls == 6] < np.finfo(np.float32).tiny).all() and (geo[cls == 6] > 0).all()
+            assert ref.omega(ref.TUKEY, at).max() == 0 and ref.omega(ref.TUKEY, below).min() > 0
+        else:
+            assert (at < 1.0).all() and ref.omega(ref.TUKEY, at).min() > 0
+            # (k^2 in float instead of double would put the class at u == 1)
+            assert (geo[cls == 1] == np.float32(k) * np.float32(k)).all()
+
+
+def test_intensity_channel_hits_its_target():
+    import colored_ref
+    for t in (4.0, np.nextafter(np.float32(4), np.float32(0)), np.nextafter(np.float32(4), np.float32(8)), 0.0, 2.0, 12.0):
+        r = ref.intensity_channel(t)
+        assert r is not None, t
+        X = np.zeros((1, 8), np.float32)
+        X[0, 4] = r
+        assert colored_ref.intensity(X)[0] == np.float32(t), (t, r)
+
+
+def test_float64_step_takes_given_weights(engine):
+    """Float64ICP.step (weights=): the derived weights handed back give the same step; a pair of weight 0 takes no part, whatever its
+    points hold."""
+    import float64_ref as f64
+    F, M = engine.synth_pair(16)
+    ids = np.arange(256)
+    a = f64.Float64ICP(F, M, 2e2, 1e-6)
+    tM = M[:, :3].astype(np.float64)
+    NN = F[:, :3].astype(np.float64)
+    w = 100.0 / (100.0 + ((tM - NN) ** 2).sum(1) + 2e2 * ((M[:, 4:7].astype(np.float64) - F[:, 4:7]) ** 2).sum(1))
+    Rk, tk, sk = a.step(ids)
+    b = f64.Float64ICP(F, M, 2e2, 1e-6)
+    Rk2, tk2, sk2 = b.step(ids, weights=w)
+    assert np.array_equal(Rk, Rk2) and np.array_equal(tk, tk2) and sk == sk2
+    w0 = w.copy(); w0[::5] = 0.0
+    Mbad = M.copy(); Mbad[::5, :3] = np.nan
+    c, d = f64.Float64ICP(F, M, 2e2, 1e-6), f64.Float64ICP(F, Mbad, 2e2, 1e-6)
+    r1, r2 = c.step(ids, weights=w0), d.step(ids, weights=w0)
+    assert all(np.array_equal(x, y) for x, y in zip(r1, r2)) and np.isfinite(r2[1]).all()
+    T = np.array([0.01, 0.02, 0.03, 0.9993, 4.0, -3.0, 2.0, 1.0])
+    c.set_T(T)
+    assert np.allclose(c.T[:4], T[:4] / np.linalg.norm(T[:4])) and np.array_equal(c.T[4:], T[4:])
