@@ -60,8 +60,8 @@ class Normals:                    # icp_set_normals: where the fixed frame's poi
 
 
 def _write_floats(mem, m):
-    """Floats a write of `mem` takes: T 8, NORMALS_F / COLOR_GRAD_F m x 4, F / M m x 8."""
-    return 8 if mem == Memory.T else m * 4 if mem in (Memory.NORMALS_F, Memory.COLOR_GRAD_F) else m * 8
+    """Floats a write of `mem` takes: T 8, NORMALS_F / COLOR_GRAD_F / NORMALS_M m x 4, F / M m x 8."""
+    return 8 if mem == Memory.T else m * 4 if mem in (Memory.NORMALS_F, Memory.COLOR_GRAD_F, Memory.NORMALS_M) else m * 8
 
 
 def _max_dist_arg(max_dist):
@@ -87,7 +87,7 @@ class TransformKind:             # ICPTransformConfig (include/ICP/algorithms.hp
 
 class Memory:                    # icp_mem in include/icp_amd.h
     F, M, T, TK, MEANS, S, NN_ID, W, SUM_W, REPS, RBC_N, RBC_O, RBC_PERM, RBC_OWNER, RBC_XP, RID, R, RK, NN, QT, TRIM, \
-        NORMALS_F, PLANE_SYSTEM, COLOR_GRAD_F = range(24)
+        NORMALS_F, PLANE_SYSTEM, COLOR_GRAD_F, NORMALS_M = range(25)
     # reference spellings (ICPStep::Memory, include/ICP/algorithms.hpp:2241-2267)
     D_IN_F, D_IN_M, D_IO_T, H_IO_T = F, M, T, T
 
@@ -166,6 +166,8 @@ def lib():
     sig("icp_get_normals", i32, vp, C.POINTER(i32), C.POINTER(u32))
     sig("icp_set_color_weight", i32, vp, f32)
     sig("icp_get_color_weight", i32, vp, C.POINTER(f32))
+    sig("icp_set_plane_to_plane", i32, vp, f32)
+    sig("icp_get_plane_to_plane", i32, vp, C.POINTER(f32))
     sig("icp_get_max_iterations", i32, vp, C.POINTER(u32))
     sig("icp_set_max_iterations", i32, vp, u32)
     sig("icp_get_angle_threshold", i32, vp, C.POINTER(f64))
@@ -195,6 +197,7 @@ def lib():
     sig("icp_batch_set_error_metric", i32, vp, i32, f32)
     sig("icp_batch_set_normals", i32, vp, i32, u32)
     sig("icp_batch_set_color_weight", i32, vp, f32)
+    sig("icp_batch_set_plane_to_plane", i32, vp, f32)
     sig("icp_batch_write", i32, vp, u32, i32, vp)
     sig("icp_batch_build_rbc", i32, vp)
     sig("icp_batch_run", i32, vp)
@@ -555,6 +558,7 @@ _MEM_DTYPE = {
     Memory.RID: (np.uint32, None), Memory.R: (np.float32, 3), Memory.RK: (np.float32, 3),
     Memory.NN: (np.float32, 4), Memory.QT: (np.float32, 4), Memory.TRIM: (np.uint32, None),
     Memory.NORMALS_F: (np.float32, 4), Memory.PLANE_SYSTEM: (np.float64, None), Memory.COLOR_GRAD_F: (np.float32, 4),
+    Memory.NORMALS_M: (np.float32, 4),
 }
 
 
@@ -724,6 +728,19 @@ class ICPStep:
         """kappa as set."""
         v = C.c_float()
         self._chk(self._L.icp_get_color_weight(self._h, C.byref(v)))
+        return v.value
+
+    def set_plane_to_plane(self, epsilon):
+        """Generalized ICP (icp_set_plane_to_plane; not reference behaviour): with ErrorMetric.POINT_TO_PLANE every pair's residual is
+        weighed by (C_Q + C_P)^-1, the covariances R diag(epsilon, 1, 1) R^T of the two frames' normals.  epsilon in (0, 1]; 0 (the
+        default) is off.  The moving frame's normals are Memory.NORMALS_M (m x 4 floats): computed from M with Normals.GRID (by
+        buildRBC and every later write of M), written by the user with Normals.GIVEN."""
+        self._chk(self._L.icp_set_plane_to_plane(self._h, float(epsilon)))
+
+    def plane_to_plane(self):
+        """epsilon as set (0: off)."""
+        v = C.c_float()
+        self._chk(self._L.icp_get_plane_to_plane(self._h, C.byref(v)))
         return v.value
 
     # -- extensions ------------------------------------------------------------------------
@@ -1080,6 +1097,10 @@ class ICPBatch:
         """ICPStep.set_color_weight on every registration (icp_batch_set_color_weight)."""
         self._chk(self._L.icp_batch_set_color_weight(self._b, float(kappa)))
 
+    def set_plane_to_plane(self, epsilon):
+        """ICPStep.set_plane_to_plane on every registration (icp_batch_set_plane_to_plane)."""
+        self._chk(self._L.icp_batch_set_plane_to_plane(self._b, float(epsilon)))
+
     def write(self, i, mem, ptr):
         arr = np.ascontiguousarray(ptr, dtype=np.float32)
         want = _write_floats(mem, self.m)
@@ -1121,7 +1142,7 @@ class ICPBatch:
         sizes = {Memory.T: 32, Memory.TK: 32, Memory.MEANS: 32, Memory.S: 44, Memory.NN_ID: self.m * 8, Memory.R: 36, Memory.RK: 36,
                  Memory.F: self.m * 32, Memory.M: self.m * 32, Memory.W: self.m * 4, Memory.RID: self.m * 4, Memory.TRIM: 16,
                  Memory.NN: self.m * 16, Memory.QT: self.m * 16, Memory.NORMALS_F: self.m * 16, Memory.PLANE_SYSTEM: 28 * 8,
-                 Memory.COLOR_GRAD_F: self.m * 16}
+                 Memory.COLOR_GRAD_F: self.m * 16, Memory.NORMALS_M: self.m * 16}
         nbytes = sizes[mem]
         out = np.empty(nbytes // np.dtype(dt).itemsize, dt)
         self._chk(self._L.icp_batch_read(self._b, i, mem, _p(out), nbytes))

@@ -413,6 +413,19 @@ int icp_batch_set_color_weight (icp_batch_handle b, float kappa) try
 }
 ICP_CATCH_ALL
 
+int icp_batch_set_plane_to_plane (icp_batch_handle b, float epsilon) try
+{
+    // (the argument first, as icp_set_plane_to_plane does: with b == NULL the message is icp_batch_last_error (NULL)'s)
+    if (!(epsilon >= 0.f && epsilon <= 1.f)) return bfail (b, ICP_EINVAL, "icp_batch_set_plane_to_plane: epsilon must be in [0, 1] (0: off)");
+    if (!b) return bfail (b, ICP_EINVAL, "icp_batch_set_plane_to_plane: null handle");
+    for (icp_handle h : b->slots) {
+        int rc = icp_set_plane_to_plane (h, epsilon);
+        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
+    }
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
 int icp_batch_set_normals (icp_batch_handle b, int source, uint32_t grid_width) try
 {
     if (!b) return ICP_EINVAL;

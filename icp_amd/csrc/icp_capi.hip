@@ -197,6 +197,21 @@ static int write_robust_scale (icp_context *h)
     return ICP_OK;
 }
 
+// plane-to-plane's epsilon -> its device word (icp_gicp_eps), in stream order like kappa's (0 while it is off)
+static int write_gicp_eps (icp_context *h)
+{
+    uint32_t bits; std::memcpy (&bits, &h->gicp_eps, sizeof bits);
+    HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (icp_gicp_eps (h->p)), (int) bits, 1, h->stream));
+    return ICP_OK;
+}
+
+// plane-to-plane with ICP_NORMALS_GRID: the moving normals of registrations b0 .. b0 + nb - 1 follow a new M, in stream order behind its copy
+// (a width that does not divide m: nothing — icp_build_rbc refuses the handle anyway)
+static void normals_m_follow (icp_context *h, uint32_t b0, uint32_t nb)
+{
+    if (h->p.gicp && h->p.nrm_grid && h->p.m % h->p.nrm_grid == 0u) icp_launch_normals_m (h->p, h->stream, b0, nb);
+}
+
 int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, float a, float c,
                       uint32_t max_iterations, double angle_threshold, double translation_threshold) try
 {
@@ -222,14 +237,14 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     int rot = h->p.rot, weighted = h->p.weighted, pmode = h->p.power_mode, fused = h->p.fused, chain = h->p.chain;
     const float dist_scale = h->p.dist_scale;
     const uint32_t reject = h->p.reject; const float reject_d2 = h->p.reject_d2, reject_max_dist = h->p.reject_max_dist, trim_keep = h->p.trim_keep;
-    const uint32_t metric = h->p.metric, nrm_grid = h->p.nrm_grid; const float p2pl_mu = h->p.p2pl_mu;
+    const uint32_t metric = h->p.metric, nrm_grid = h->p.nrm_grid, gicp = h->p.gicp; const float p2pl_mu = h->p.p2pl_mu;
     free_all (h);
     icp_params &p = h->p;
     p = icp_params {};
     p.rot = rot; p.weighted = weighted; p.power_mode = pmode; p.check = 0; p.fused = fused; p.chain = chain; p.emit = 1;
     p.dist_scale = dist_scale;
     p.reject = reject; p.reject_d2 = reject_d2; p.reject_max_dist = reject_max_dist; p.trim_keep = trim_keep;
-    p.metric = metric; p.nrm_grid = nrm_grid; p.p2pl_mu = p2pl_mu;
+    p.metric = metric; p.nrm_grid = nrm_grid; p.p2pl_mu = p2pl_mu; p.gicp = gicp;
     p.m = m; p.nr = nr; p.batch = batch; p.side = side; p.nrx = nrx; p.nry = nry;
     p.a = a; p.c = c;
     {   // division-free cell lookups in the kernels (reps_grid guarantees a square grid that the representative grid tiles)
@@ -263,7 +278,7 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     p.gtile = 0u;                                                    // 4 x 4 tile groups where the representative grid allows
     if (nrx % 4u == 0u && nry % 4u == 0u && !std::getenv ("ICP_AMD_STRIP_GROUPS")) { uint32_t lg = 0; while ((4u << lg) < nrx) ++lg; p.gtile = lg + 1u; }
     if ((rc = dalloc (h, &p.GB, B * 2 * (p.n16 + p.n1k)))) return rc;
-    if ((rc = dalloc (h, &p.XP, icp_xp_layout_of (batch, m).total))) return rc;    // (behind the database: NORMALS_F, then COLOR_GRAD_F; zeroed)
+    if ((rc = dalloc (h, &p.XP, icp_xp_layout_of (batch, m).total))) return rc;    // (behind the database: NORMALS_F, COLOR_GRAD_F, NORMALS_M; zeroed)
     if ((rc = dalloc (h, &p.XQ, B * m * 8))) return rc;
     if ((rc = dalloc (h, &p.OL, B * ICP_OL_STRIDE (nr)))) return rc;
     p.nlb = m / 16u + 2u;
@@ -291,6 +306,7 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     if ((rc = dalloc (h, &p.mom, icp_mom_layout_of (batch, m, p.nb).total))) return rc;
     if ((rc = write_color_kappa (h))) return rc;
     if ((rc = write_robust_scale (h))) return rc;
+    if ((rc = write_gicp_eps (h))) return rc;
     if ((rc = dalloc (h, &p.ml1, B * 18 * ((p.nb + 127u) / 128u)))) return rc;
     if ((rc = dalloc (h, &p.cst, B * 2))) return rc;
     if ((rc = dalloc (h, &p.st, B))) return rc;
@@ -339,6 +355,7 @@ int icp_write_b (icp_handle h, uint32_t b, int mem, const void *host_ptr, int bl
             if (host_ptr) std::memcpy (stage, host_ptr, fm);           // algorithms.cpp:4604-4606
             HIPCHK (h, hipMemcpyAsync (dst, stage, fm, hipMemcpyHostToDevice, h->stream));
             HIPCHK (h, hipEventRecord (ev, h->stream));
+            if (mem == ICP_MEM_M) { normals_m_follow (h, b, 1u); HIPCHK (h, hipGetLastError ()); }
             break;
         }
         case ICP_MEM_T: {
@@ -368,8 +385,16 @@ int icp_write_b (icp_handle h, uint32_t b, int mem, const void *host_ptr, int bl
             HIPCHK (h, hipMemcpy (icp_color_grad_f (h->p) + (size_t) b * h->p.m, host_ptr, (size_t) h->p.m * 16, hipMemcpyHostToDevice));
             break;
         }
+        case ICP_MEM_NORMALS_M: {
+            // (plane-to-plane's moving normals, ICP_NORMALS_GIVEN: as ICP_MEM_NORMALS_F)
+            if (!host_ptr) return fail (h, ICP_EINVAL, "icp_write: ICP_MEM_NORMALS_M needs a source");
+            note_inputs_change (h);
+            HIPCHK (h, hipStreamSynchronize (h->stream));
+            HIPCHK (h, hipMemcpy (icp_normals_m (h->p) + (size_t) b * h->p.m, host_ptr, (size_t) h->p.m * 16, hipMemcpyHostToDevice));
+            break;
+        }
         default:
-            return fail (h, ICP_EINVAL, "icp_write: mem must be ICP_MEM_F, ICP_MEM_M, ICP_MEM_T, ICP_MEM_NORMALS_F or ICP_MEM_COLOR_GRAD_F");
+            return fail (h, ICP_EINVAL, "icp_write: mem must be ICP_MEM_F, ICP_MEM_M, ICP_MEM_T, ICP_MEM_NORMALS_F, ICP_MEM_COLOR_GRAD_F or ICP_MEM_NORMALS_M");
     }
     if (block) HIPCHK (h, hipStreamSynchronize (h->stream));
     return ICP_OK;
@@ -394,7 +419,7 @@ size_t icp_mem_size (icp_handle h, int mem)
         case ICP_MEM_R: case ICP_MEM_RK: return 36;
         case ICP_MEM_NN: case ICP_MEM_QT: return (size_t) p.m * 16;
         case ICP_MEM_TRIM: return 16;
-        case ICP_MEM_NORMALS_F: case ICP_MEM_COLOR_GRAD_F: return (size_t) p.m * 16;
+        case ICP_MEM_NORMALS_F: case ICP_MEM_COLOR_GRAD_F: case ICP_MEM_NORMALS_M: return (size_t) p.m * 16;
         case ICP_MEM_PLANE_SYSTEM: return ICP_P2PL_SYS * sizeof (double);
         default: return 0;
     }
@@ -428,6 +453,7 @@ static int mem_ptr (icp_context *h, uint32_t b, int mem, const void **src)
         case ICP_MEM_TRIM: *src = icp_trim_area (p) + 4u * b; break;
         case ICP_MEM_NORMALS_F: *src = icp_normals_f (p) + (size_t) b * p.m; break;
         case ICP_MEM_COLOR_GRAD_F: *src = icp_color_grad_f (p) + (size_t) b * p.m; break;
+        case ICP_MEM_NORMALS_M: *src = icp_normals_m (p) + (size_t) b * p.m; break;
         case ICP_MEM_PLANE_SYSTEM: *src = icp_p2pl_area (p) + (size_t) ICP_P2PL_SYS * b; break;
         default: return fail (h, ICP_EINVAL, "unknown icp_mem value");
     }
@@ -780,6 +806,40 @@ int icp_get_robust_loss (icp_handle h, int *loss, float *scale) try
     return ICP_OK;
 }
 ICP_CATCH_ALL
+// plane-to-plane (include/icp_amd.h, icp_gicp.hip).  On <-> off changes which moments kernel a point-to-plane iteration runs and what
+// buildRBC launches: the route of icp_set_trimming (graphs captured anew).  A new epsilon while it stays on goes to its device word, as
+// kappa does (icp_set_color_weight): no graph is touched.
+int icp_set_plane_to_plane (icp_handle h, float epsilon) try
+{
+    api_guard guard_ (h);
+    if (!(epsilon >= 0.f && epsilon <= 1.f)) return fail (h, ICP_EINVAL, "icp_set_plane_to_plane: epsilon must be in [0, 1] (0: off)");
+    if (!h) return fail (h, ICP_EINVAL, "icp_set_plane_to_plane: null handle");
+    { int rc = outputs_before_change (h); if (rc) return rc; }
+    const uint32_t on = epsilon > 0.f ? 1u : 0u;
+    h->gicp_eps = epsilon;
+    if (h->inited) {
+        int rc = set_device (h); if (rc) return rc;
+        if ((rc = run_close_all (h))) return rc;
+        if ((rc = write_gicp_eps (h))) return rc;
+        HIPCHK (h, hipStreamSynchronize (h->stream));
+    }
+    if (on != h->p.gicp) {
+        h->p.gicp = on;
+        // (grid normals: the last buildRBC computed no moving normals — the next run needs a new one, as after a new F)
+        if (on && h->p.nrm_grid) h->built = false;
+        drop_graphs (h);
+    }
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+int icp_get_plane_to_plane (icp_handle h, float *epsilon) try
+{
+    api_guard guard_ (h);
+    if (!h || !epsilon) return ICP_EINVAL;
+    *epsilon = h->gicp_eps;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
 // point-to-plane (include/icp_amd.h, icp_p2pl.hip).  On <-> off changes which kernels run — the moments and the 6 x 6 finalize, no
 // chained form —: the route of icp_set_reduce_mode (graphs captured anew).  A new mu while the metric stays on is a parameter update.
 // Colored ICP is point-to-plane with other moments: POINT_TO_PLANE <-> COLORED changes the kernels too (same route).
@@ -960,6 +1020,7 @@ int icp_write_cloud (icp_handle h, int which, const void *cloud, int block) try
     note_inputs_change (h);
     HIPCHK (h, hipMemcpyAsync (h->dCloud, cloud, (size_t) n * 32, hipMemcpyHostToDevice, h->stream));
     icp_launch_get_lms (h->dCloud, which == ICP_MEM_F ? h->dF : h->dM, h->stream);
+    if (which == ICP_MEM_M) normals_m_follow (h, 0u, 1u);
     HIPCHK (h, hipGetLastError ());
     HIPCHK (h, hipStreamSynchronize (h->stream));   // the source is pageable host memory
     (void) block;

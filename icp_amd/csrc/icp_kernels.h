@@ -99,6 +99,8 @@ struct icp_params {
     unsigned long long *hmirror; // [batch]  ICP_MIRROR_WORD (epoch, done, k) stored by the lane that publishes a registration's state
     icp_reg_state *hstate;       // [batch]  the final state of a run, stored by its end kernel in front of the word's FINAL bit
     uint32_t epoch;              // tag of the run the words belong to (a word of another epoch is stale)
+    uint32_t gicp;               // plane-to-plane (icp_set_plane_to_plane): 1 while epsilon > 0, whatever the metric (icp_gicp: in effect).  It fills
+                                 // the alignment hole behind `epoch`: no other field moves.  epsilon itself is a device word (icp_gicp_eps)
     // tracking with frames gated on the device (icp_capi.hip: track_submit): consecutive frames alternate between two streams, so the
     // launches of a frame that has converged and the next frame's run concurrently
     uint32_t *run_flag;          // [batch]  epoch of the run that has converged: its remaining launches leave at once and WRITE NOTHING (one flag per
@@ -157,18 +159,21 @@ static __host__ __device__ __forceinline__ bool icp_apply_pass (const icp_params
 #define ICP_METRIC_COLORED_ 2u
 static __host__ __device__ __forceinline__ bool icp_p2pl (const icp_params &p) { return p.metric != 0u; }
 static __host__ __device__ __forceinline__ bool icp_colored (const icp_params &p) { return p.metric == ICP_METRIC_COLORED_; }
+// plane-to-plane in effect: switched on, and the metric is point-to-plane (icp_gicp.hip has the moments then)
+static __host__ __device__ __forceinline__ bool icp_gicp (const icp_params &p) { return p.gicp != 0u && p.metric == 1u; }
 static __host__ __device__ __forceinline__ uint32_t icp_p2pl_nblk (uint32_t m) { return (m + ICP_P2PL_BLOCK - 1u) / ICP_P2PL_BLOCK; }
 
 // The moments' allocation p.mom, offsets in doubles.  icp_params has no room for more pointers, so everything the opt-in paths keep per
 // iteration lies behind the fused mode's moment partials: trimming's words, the plane system and its block partials, and colored ICP's
-// weight kappa and the robust loss's scale k, device words (icp_set_color_weight and icp_set_robust_loss write them in stream order) that
-// the run graphs read instead of capturing them.
+// weight kappa, the robust loss's scale k and plane-to-plane's epsilon, device words (icp_set_color_weight, icp_set_robust_loss and
+// icp_set_plane_to_plane write them in stream order) that the run graphs read instead of capturing them.
 struct icp_mom_layout {
     size_t trim;                 // trimming's uint32 words (icp_trim_area)
     size_t sys;                  // [batch][ICP_P2PL_SYS] ICP_MEM_PLANE_SYSTEM (icp_p2pl_area)
     size_t part;                 // [batch][ICP_P2PL_TERMS][icp_p2pl_nblk] the plane system's block partials (icp_p2pl_part)
     size_t kappa;                // the float word of kappa (icp_color_kappa)
     size_t robust;               // the float word of the robust loss's scale k (icp_robust_scale)
+    size_t gicp;                 // the float word of plane-to-plane's epsilon (icp_gicp_eps)
     size_t total;
 };
 static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (uint32_t batch, uint32_t m, uint32_t nb)
@@ -180,7 +185,8 @@ static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (uint32_t bat
     l.part = l.sys + B * ICP_P2PL_SYS;
     l.kappa = l.part + B * ICP_P2PL_TERMS * icp_p2pl_nblk (m);
     l.robust = l.kappa + 1u;
-    l.total = l.robust + 1u;
+    l.gicp = l.robust + 1u;
+    l.total = l.gicp + 1u;
     return l;
 }
 static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (const icp_params &p) { return icp_mom_layout_of (p.batch, p.m, p.nb); }
@@ -190,17 +196,19 @@ static inline double *icp_p2pl_part (const icp_params &p) { return p.mom + icp_m
 static inline float *icp_color_kappa (const icp_params &p) { return reinterpret_cast<float *> (p.mom + icp_mom_layout_of (p).kappa); }
 // (also on the device: the robust kernels find the word from their icp_params, the loss-off kernels take no argument for it)
 static __host__ __device__ inline float *icp_robust_scale (const icp_params &p) { return reinterpret_cast<float *> (p.mom + icp_mom_layout_of (p).robust); }
+static __host__ __device__ inline float *icp_gicp_eps (const icp_params &p) { return reinterpret_cast<float *> (p.mom + icp_mom_layout_of (p).gicp); }
 
 // The XP allocation of one RBC set, offsets in floats: [batch][m][8] the permuted database, then [batch][m] float4 NORMALS_F and
 // [batch][m] float4 COLOR_GRAD_F ([gx gy gz C] per fixed point).  The normals and gradients belong to the fixed frame as the RBC does,
-// so a tracked handle's second RBC set (icp_track.hip) carries its own with it.
+// so a tracked handle's second RBC set (icp_track.hip) carries its own with it.  Behind them [batch][m] float4 NORMALS_M, the moving
+// frame's normals of plane-to-plane (icp_params has no room for a pointer of their own; tracking does not combine with them).
 struct icp_xp_layout {
-    size_t normals, color_grad, total;
+    size_t normals, color_grad, normals_m, total;
 };
 static __host__ __device__ __forceinline__ icp_xp_layout icp_xp_layout_of (uint32_t batch, uint32_t m)
 {
     const size_t n = (size_t) batch * m;
-    return { n * 8, n * 12, n * 16 };
+    return { n * 8, n * 12, n * 16, n * 20 };
 }
 static __host__ __device__ __forceinline__ float4 *icp_normals_f (const icp_params &p)
 {
@@ -209,6 +217,10 @@ static __host__ __device__ __forceinline__ float4 *icp_normals_f (const icp_para
 static __host__ __device__ __forceinline__ float4 *icp_color_grad_f (const icp_params &p)
 {
     return reinterpret_cast<float4 *> (p.XP + icp_xp_layout_of (p.batch, p.m).color_grad);
+}
+static __host__ __device__ __forceinline__ float4 *icp_normals_m (const icp_params &p)
+{
+    return reinterpret_cast<float4 *> (p.XP + icp_xp_layout_of (p.batch, p.m).normals_m);
 }
 
 #define ICP_N_FULL(p, b) ((p).N + ((size_t) (p).batch + (b)) * (p).nr)
@@ -295,7 +307,9 @@ uint32_t icp_trim_launches (const icp_params &p);                             //
 void icp_launch_robust_apply (const icp_params &p, hipStream_t s);            // icp_robust.hip: k_trim_apply<fused, true> (a point-to-point robust loss)
 void icp_launch_plane_moments_robust (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);   // icp_robust.hip: k_plane_moments<colored, true>
 void icp_launch_p2pl_solve (const icp_params &p, hipStream_t s);             // icp_p2pl.hip: k_plane_moments<colored?> + k_p2pl_finalize
-void icp_launch_normals_grid (const icp_params &p, hipStream_t s);           // icp_p2pl.hip: k_normals_grid (+ colored: k_color_grad_grid), behind buildRBC
+void icp_launch_normals_grid (const icp_params &p, hipStream_t s);           // icp_p2pl.hip: k_normals_grid (+ colored: k_color_grad_grid; plane-to-plane: + NORMALS_M), behind buildRBC
+void icp_launch_normals_m (const icp_params &p, hipStream_t s, uint32_t b0, uint32_t nb);   // icp_p2pl.hip: k_normals_grid pointed at M, registrations b0 .. b0 + nb - 1
+void icp_launch_gicp_moments (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);          // icp_gicp.hip: k_gicp_moments / k_gicp_moments_robust
 #define ICP_P2PL_LAUNCHES 2u                                                  // launches of icp_launch_p2pl_solve
 void icp_launch_owner_search_dense (const icp_params &p, hipStream_t s);
 uint32_t icp_tbox_of (const icp_params &p);

@@ -7,7 +7,7 @@
 // weighed by the loss's omega of its residual) and their tree over blocks
 // of ICP_P2PL_BLOCK pairs; k_p2pl_finalize, one workgroup per registration: the tree over the block partials, LDL^T in one lane, the
 // increment composed with icp_compose's arithmetic and checked with icp_check_converged.  k_normals_grid computes NORMALS_F from F
-// behind buildRBC (ICP_NORMALS_GRID), and with the colored metric k_color_grad_grid computes COLOR_GRAD_F behind it.  None of the
+// behind buildRBC (ICP_NORMALS_GRID; with plane-to-plane on, whose moments are icp_gicp.hip's, also NORMALS_M from M), and with the colored metric k_color_grad_grid computes COLOR_GRAD_F behind it.  None of the
 // point-to-point kernels carries any of this code; the translation unit is built with -ffp-contract=off like every other, so each
 // expression below is evaluated exactly in the order it is written.
 #include "icp_plane_moments.h"          // (intensity)
@@ -76,16 +76,17 @@ __device__ __forceinline__ void ldlt_solve (const double (&A)[N][N], const doubl
 
 }  // namespace
 
-// NORMALS_F of the fixed set, read as a row-major grid p.nrm_grid wide (m % width == 0: icp_build_rbc checks it).  One thread per point,
-// grid.y = registration.  fp32, no contraction:
+// NORMALS_F of the fixed set (src = F), read as a row-major grid p.nrm_grid wide (m % width == 0: icp_build_rbc checks it); with
+// plane-to-plane on also NORMALS_M of the moving set (src = M).  One thread per point, grid.y = registration counted from src and nrm.
+// fp32, no contraction:
 //   c = dh x dv,  n = c / sqrtf ((c.x^2 + c.y^2) + c.z^2),  n = -n if (n.x C.x + n.y C.y) + n.z C.z > 0 (faces the sensor at the origin),
 //   n = 0 when the centre is invalid, a difference is missing, or the length is not > 0 and finite.
-__global__ __launch_bounds__ (256) void k_normals_grid (icp_params p, float4 *nrm)
+__global__ __launch_bounds__ (256) void k_normals_grid (icp_params p, const float *src, float4 *nrm)
 {
     const uint32_t b = blockIdx.y, i = blockIdx.x * 256u + threadIdx.x;
     if (i >= p.m) return;
     const uint32_t W = p.nrm_grid, x = i % W, y = i / W, H = p.m / W;
-    const float *F = p.F + (size_t) b * p.m * 8;
+    const float *F = src + (size_t) b * p.m * 8;
     auto at = [&] (uint32_t j) { const float *r = F + (size_t) j * 8; return make_float3 (r[0], r[1], r[2]); };
     const float3 c = at (i);
     float4 n = make_float4 (0.f, 0.f, 0.f, 0.f);
@@ -273,7 +274,8 @@ void icp_launch_p2pl_solve (const icp_params &p, hipStream_t s)
     const float4 *nrm = icp_normals_f (p), *grad = icp_color_grad_f (p);
     const float *kappa = icp_color_kappa (p);
     const dim3 grid (nblk, p.batch);
-    if (icp_robust (p)) icp_launch_plane_moments_robust (p, s, part, nblk);        // (icp_robust.hip)
+    if (icp_gicp (p)) icp_launch_gicp_moments (p, s, part, nblk);                  // (icp_gicp.hip: plane-to-plane, with or without a robust loss)
+    else if (icp_robust (p)) icp_launch_plane_moments_robust (p, s, part, nblk);   // (icp_robust.hip)
     else if (icp_colored (p)) hipLaunchKernelGGL (k_plane_moments<true>, grid, dim3 (ICP_P2PL_BLOCK), 0, s, p, nrm, part, nblk, grad, kappa);
     else hipLaunchKernelGGL (k_plane_moments<false>, grid, dim3 (ICP_P2PL_BLOCK), 0, s, p, nrm, part, nblk, grad, kappa);
     hipLaunchKernelGGL (k_p2pl_finalize, dim3 (p.batch), dim3 (256), 0, s, p, (const double *) part, sys, nblk, P);
@@ -282,7 +284,15 @@ void icp_launch_p2pl_solve (const icp_params &p, hipStream_t s)
 void icp_launch_normals_grid (const icp_params &p, hipStream_t s)
 {
     const dim3 grid ((p.m + 255u) / 256u, p.batch);
-    hipLaunchKernelGGL (k_normals_grid, grid, dim3 (256), 0, s, p, icp_normals_f (p));
+    hipLaunchKernelGGL (k_normals_grid, grid, dim3 (256), 0, s, p, p.F, icp_normals_f (p));
     // (the intensity gradients need the normals just computed)
     if (icp_colored (p)) hipLaunchKernelGGL (k_color_grad_grid, grid, dim3 (256), 0, s, p, (const float4 *) icp_normals_f (p), icp_color_grad_f (p));
+    if (p.gicp) icp_launch_normals_m (p, s, 0u, p.batch);
+}
+
+// plane-to-plane with ICP_NORMALS_GRID: NORMALS_M of registrations b0 .. b0 + nb - 1 from M, by the same kernel
+void icp_launch_normals_m (const icp_params &p, hipStream_t s, uint32_t b0, uint32_t nb)
+{
+    const dim3 grid ((p.m + 255u) / 256u, nb);
+    hipLaunchKernelGGL (k_normals_grid, grid, dim3 (256), 0, s, p, p.M + (size_t) b0 * p.m * 8, icp_normals_m (p) + (size_t) b0 * p.m);
 }

@@ -22,6 +22,8 @@ int need (icp_context *h, bool built, bool keep_run)
     if (!h) return ICP_EINVAL;
     if (!h->inited) return fail (h, ICP_ESTATE, "icp_init has not been called");
     if (built && !h->built) return fail (h, ICP_ESTATE, "icp_build_rbc has not been called");
+    if (built && h->p.gicp && icp_colored (h->p))
+        return fail (h, ICP_ESTATE, "icp_set_plane_to_plane does not combine with ICP_METRIC_COLORED (icp_set_error_metric): switch one of them off");
     if (!keep_run && (h->run.active || h->run2.active || h->stream2_dirty)) {
         if (hipSetDevice (h->device) != hipSuccess) return fail (h, ICP_EHIP, "hipSetDevice");
         int rc = run_close_all (h); if (rc) return rc;

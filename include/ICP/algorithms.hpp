@@ -525,7 +525,8 @@ namespace ICP
     {
     public:
         /*! \brief reference include/ICP/algorithms.hpp:2241-2267 */
-        enum class Memory : uint8_t { H_IN_F, H_IN_M, H_IO_T, D_IN_F, D_IN_M, D_IO_T };
+        enum class Memory : uint8_t { H_IN_F, H_IN_M, H_IO_T, D_IN_F, D_IN_M, D_IO_T,
+                                      NORMALS_M /*!< not in the reference: the moving frame's normals of setPlaneToPlane (m x float4, written from `ptr`) */ };
 
         ICPStep (icp::Env _env, icp::Mode _mode = icp::Mode::FAST) : env (_env), h (nullptr), a (1e2f), c (1e-6f), m (0), nr (0)
         {
@@ -562,6 +563,7 @@ namespace ICP
         /*! \brief reference include/ICP/algorithms.hpp:2273, src/ICP/algorithms.cpp:4596-4622 */
         void write (Memory mem = Memory::D_IN_F, void *ptr = nullptr, bool block = false)
         {
+            if (mem == Memory::NORMALS_M) { check (icp_write (h, ICP_MEM_NORMALS_M, ptr, block ? 1 : 0)); return; }     // (no staging buffer: straight from ptr)
             if (!(staging == Staging::I || staging == Staging::IO)) return;
             int which; float *stage; size_t n = (size_t) m * 8;
             switch (mem)
@@ -635,6 +637,12 @@ namespace ICP
          *         setErrorMetric (ICP_METRIC_COLORED, mu), the fixed frame's intensity gradients as ICP_MEM_COLOR_GRAD_F. */
         void setColorWeight (float kappa) { check (icp_set_color_weight (h, kappa)); }
         float getColorWeight () { float k = 0.f; check (icp_get_color_weight (h, &k)); return k; }
+        /*! \brief Generalized ICP (icp_set_plane_to_plane, include/icp_amd.h; not in the reference, off by default): with
+         *         setErrorMetric (ICP_METRIC_POINT_TO_PLANE, mu) every pair's residual is weighed by (C_Q + C_P)^-1, the covariances
+         *         R diag (epsilon, 1, 1) R^T of the two frames' normals.  epsilon in (0, 1]; 0: off.  The moving frame's normals are
+         *         Memory::NORMALS_M: computed from M with ICP_NORMALS_GRID, written by the user with ICP_NORMALS_GIVEN. */
+        void setPlaneToPlane (float epsilon) { check (icp_set_plane_to_plane (h, epsilon)); }
+        float getPlaneToPlane () { float e = 0.f; check (icp_get_plane_to_plane (h, &e)); return e; }
 
         float *hPtrInF;  /*!< Staging buffer of the fixed set (reference: mapped H_IN_F). */
         float *hPtrInM;  /*!< Staging buffer of the moving set. */

@@ -89,6 +89,7 @@ typedef enum {
     ICP_MEM_NORMALS_F = 21,/* io   m x float4   normals of the fixed landmarks [nx ny nz 0] (point-to-plane) */
     ICP_MEM_PLANE_SYSTEM = 22, /* out double[28] point-to-plane: A's upper triangle (21), b (6), status (0 while off) */
     ICP_MEM_COLOR_GRAD_F = 23, /* io m x float4  colored ICP: intensity gradients of the fixed landmarks [gx gy gz C] */
+    ICP_MEM_NORMALS_M = 24,    /* io m x float4  normals of the moving landmarks [nx ny nz 0], indexed like M (plane-to-plane) */
     ICP_MEM_COUNT_
 } icp_mem;
 
@@ -125,8 +126,8 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
 /* ---- data movement ------------------------------------------------------------------------ */
 
 /* ICPStep::write (mem, ptr, block, events, event) — include/ICP/algorithms.hpp:2273,
- * src/ICP/algorithms.cpp:4596-4622.  mem in {ICP_MEM_F, ICP_MEM_M, ICP_MEM_T}, or ICP_MEM_NORMALS_F / ICP_MEM_COLOR_GRAD_F (m x
- * float4, the point-to-plane normals and colored ICP's gradients of ICP_NORMALS_GIVEN).  Host -> pinned staging -> device on the handle's stream; block != 0 waits for
+ * src/ICP/algorithms.cpp:4596-4622.  mem in {ICP_MEM_F, ICP_MEM_M, ICP_MEM_T}, or ICP_MEM_NORMALS_F / ICP_MEM_COLOR_GRAD_F /
+ * ICP_MEM_NORMALS_M (m x float4, the point-to-plane normals, colored ICP's gradients and plane-to-plane's moving normals of ICP_NORMALS_GIVEN).  Host -> pinned staging -> device on the handle's stream; block != 0 waits for
  * completion. */
 int icp_write (icp_handle h, int mem, const void *host_ptr, int block);
 int icp_write_b (icp_handle h, uint32_t batch_index, int mem, const void *host_ptr, int block);
@@ -370,6 +371,51 @@ int icp_get_color_weight (icp_handle h, float *kappa);
 int icp_set_robust_loss (icp_handle h, int loss, float scale);
 int icp_get_robust_loss (icp_handle h, int *loss, float *scale);
 
+/* Generalized ICP (Segal, Haehnel, Thrun 2009: "plane-to-plane"; not reference behaviour; off by default): point-to-plane with the
+ * 3-vector residual of every pair weighed by (C_Q + C_P)^-1, the sum of the two frames' local covariances.  The rule:
+ *   - epsilon == 0 (the default) is off: the same kernels, launches, graphs and bits as without it, for every metric.  0 < epsilon <= 1
+ *     turns it on; it takes effect while the metric is ICP_METRIC_POINT_TO_PLANE.  ICP_METRIC_POINT_TO_POINT ignores it, as it ignores
+ *     mu.  With ICP_METRIC_COLORED every run, step and batched run returns ICP_ESTATE (the combination is not provided).
+ *   - ICP_MEM_NORMALS_M, m x float4 [nx ny nz 0] per registration, indexed like M: the moving frame's normals, in the moving frame.  It
+ *     starts as zeros.  ICP_NORMALS_GIVEN: the user writes it (icp_write, as ICP_MEM_NORMALS_F); it is used as given.
+ *     ICP_NORMALS_GRID with plane-to-plane on: computed from M by exactly the grid rule of ICP_MEM_NORMALS_F (icp_set_normals), by
+ *     icp_build_rbc behind the fixed normals, and again by every later icp_write / icp_write_b / icp_write_cloud / icp_batch_write of
+ *     ICP_MEM_M.  Switching plane-to-plane on with ICP_NORMALS_GRID leaves the handle without moving normals: icp_run and the other runs
+ *     return ICP_ESTATE until icp_build_rbc has run again (as with colored ICP's gradients).  With plane-to-plane off, nothing computes
+ *     or reads the buffer.
+ *   - Per pair, with point-to-plane's P, Q, w, d = Q - P, G and g, in double from the float inputs, every expression in the order
+ *     written, with no contraction:
+ *         N_Q = NORMALS_F[id],  N_M = NORMALS_M[i] (query order); a non-finite normal counts as zero.
+ *         R = the registration's cumulative rotation before the step (ICP_MEM_R, the floats this iteration's search used);
+ *         N_P = R N_M, each component (R_a0 nx + R_a1 ny) + R_a2 nz.
+ *         Covariance of a normal n:  nn = (nx nx + ny ny) + nz nz.  If nn > 0 and finite: k = (1.0 - (double) epsilon) / nn and
+ *         C_ab = delta_ab - k (n_a n_b) (C01 = 0.0 - k (nx ny), ..); otherwise C = I.  (R diag (epsilon, 1, 1) R^T for a unit normal; an
+ *         absent normal makes that side isotropic.)
+ *         S = C_Q + C_P, componentwise, upper triangle (s00 s01 s02 s11 s12 s22).
+ *         c00 = s11 s22 - s12 s12, c01 = s02 s12 - s01 s22, c02 = s01 s12 - s02 s11, c11 = s00 s22 - s02 s02, c12 = s01 s02 - s00 s12,
+ *         c22 = s00 s11 - s01 s01;  det = (s00 c00 + s01 c01) + s02 c02;  M_ab = c_ab / det (symmetric).  A pair whose det is not
+ *         finite or not > 0 contributes exact zeros.
+ *         H = [-[P]x | I], columns h0 = (0, -pz, py), h1 = (pz, 0, -px), h2 = (-py, px, 0), h3 .. h5 the unit vectors;  u_a = M h_a.
+ *         term (a, b), a <= b, row-major:  w (h_a . u_b + mu G_ab)        term 21 + a:  w (u_a . d + mu g_a)
+ *     The products with the structural zeros and ones of h_a are dropped, everywhere alike:
+ *         u_0r = M_r1 (-pz) + M_r2 py,   u_1r = M_r0 pz + M_r2 (-px),   u_2r = M_r0 (-py) + M_r1 px,   u_(3+c)r = M_rc      (r = 0, 1, 2)
+ *         h_0 . u_b = (-pz) u_b1 + py u_b2,   h_1 . u_b = pz u_b0 + (-px) u_b2,   h_2 . u_b = (-py) u_b0 + px u_b1,   h_(3+c) . u_b = u_bc
+ *         u_a . d = (u_a0 dx + u_a1 dy) + u_a2 dz
+ *     So each iteration minimises sum_i w_i [ e^T (C_Q + C_P)^-1 e + mu |e|^2 ], e = Q - (P + omega x P + tau).  w == 0 selects exact
+ *     zeros for the pair.  epsilon = 1 makes M = I / 2 for every pair.
+ *   - Robust loss: u_d = M d, each component (M_r0 dx + M_r1 dy) + M_r2 dz;  sG2 = ((u_d0 dx + u_d1 dy) + u_d2 dz) + mu ((dx dx +
+ *     dy dy) + dz dz),  wG = omega (sG2 / k2);  the terms are w (wG (h_a . u_b + mu G_ab)) and w (wG (u_a . d + mu g_a)), wG == 0
+ *     selecting an exact zero, as in the point-to-plane rule.
+ *   - Everything behind the 27 terms is point-to-plane's: the two trees, LDL^T with its pivot test, the identity step, qk, tk, sk = 1,
+ *     the composition, the convergence test, ICP_MEM_PLANE_SYSTEM, the separate form, the per-query outputs stored by every iteration.
+ *     Rejection and trimming act through w.
+ *   - Turning it on or off captures the run graphs anew.  A new epsilon while it stays on is a parameter update: it takes effect in
+ *     already captured run graphs, as kappa does.  The setting survives icp_init and applies to single, batched (icp_init_batched) and
+ *     icp_batch_* registrations.  Tracking is not provided: icp_track_submit and icp_track_next return ICP_ESTATE while it is on.
+ * ICP_EINVAL: epsilon negative, NaN, infinite or above 1. */
+int icp_set_plane_to_plane (icp_handle h, float epsilon);
+int icp_get_plane_to_plane (icp_handle h, float *epsilon);
+
 /* Where the fixed frame's normals come from (point-to-plane):
  *   ICP_NORMALS_GIVEN (the default): the user writes ICP_MEM_NORMALS_F (m x float4 [nx ny nz 0] per registration, indexed like F);
  *     it is used as given and starts as zeros.  grid_width is ignored (pass 0).
@@ -576,7 +622,8 @@ int icp_batch_set_robust_loss (icp_batch_handle b, int loss, float scale);      
 int icp_batch_set_error_metric (icp_batch_handle b, int metric, float point_weight);         /* icp_set_error_metric on every slot */
 int icp_batch_set_normals (icp_batch_handle b, int source, uint32_t grid_width);             /* icp_set_normals on every slot */
 int icp_batch_set_color_weight (icp_batch_handle b, float kappa);                            /* icp_set_color_weight on every slot */
-int icp_batch_write (icp_batch_handle b, uint32_t i, int mem, const void *host_ptr);       /* mem: F, M, T, NORMALS_F or COLOR_GRAD_F of registration i */
+int icp_batch_set_plane_to_plane (icp_batch_handle b, float epsilon);                        /* icp_set_plane_to_plane on every slot */
+int icp_batch_write (icp_batch_handle b, uint32_t i, int mem, const void *host_ptr);       /* mem: F, M, T, NORMALS_F, COLOR_GRAD_F or NORMALS_M of registration i */
 int icp_batch_build_rbc (icp_batch_handle b);
 int icp_batch_run (icp_batch_handle b);                                                      /* ICP::run of every registration */
 int icp_batch_run_fixed (icp_batch_handle b, uint32_t iterations, int from_identity);

@@ -85,6 +85,8 @@ public:
     void setNormals (int source, uint32_t grid_width = 0) { reg.setNormals (source, grid_width); }
     /*! \brief Colored ICP of the registration (ICPStep::setColorWeight with setErrorMetric (ICP_METRIC_COLORED, mu)). */
     void setColorWeight (float kappa) { reg.setColorWeight (kappa); }
+    /*! \brief Generalized ICP of the registration (ICPStep::setPlaneToPlane with setErrorMetric (ICP_METRIC_POINT_TO_PLANE, mu)). */
+    void setPlaneToPlane (float epsilon) { reg.setPlaneToPlane (epsilon); }
     float getColorWeight () { return reg.getColorWeight (); }
 
     /*! \brief The moving cloud after `registerPC ()` (the reference writes it into the GL vertex buffer). */
