@@ -6,7 +6,7 @@
 //   registration NAME                     data/NAME_1.bin, data/NAME_2.bin      (the reference's argument convention, :299-329)
 //   registration A B                      data/A.bin, data/B.bin — or A and B themselves when they name existing files
 //   ... [--out FILE] [--device N] [--reference-order] [--svd] [--reject-invalid] [--max-dist MM] [--trim FRACTION]
-//       [--point-to-plane MU] [--colored KAPPA] [--robust KIND:SCALE] [--plane-to-plane EPS]
+//       [--point-to-plane MU] [--colored KAPPA] [--robust KIND:SCALE] [--plane-to-plane EPS] [--symmetric]
 //
 // --reject-invalid / --max-dist: correspondence rejection (icp_set_rejection: pairs with a pixel without depth at either end / pairs
 // farther apart than MM get weight 0).  --trim: trimmed ICP (icp_set_trimming: every iteration keeps the closest FRACTION in (0, 1] of the
@@ -16,6 +16,8 @@
 // --robust: a robust loss (icp_set_robust_loss) of KIND huber, cauchy or tukey with the scale SCALE (> 0, mm), e.g. tukey:50.
 // --plane-to-plane: Generalized ICP (icp_set_plane_to_plane) with the covariance parameter EPS in (0, 1], e.g. 0.001: point-to-plane with
 // every pair weighed by both frames' grid normals; implies --point-to-plane 0 when no MU is given.
+// --symmetric: symmetric ICP (icp_set_symmetric; Rusinkiewicz 2019): point-to-plane along the mean of both frames' grid normals, the
+// rotation split between the frames; implies --point-to-plane 0 when no MU is given.
 // Not the reference's behaviour; off by default.
 //
 // A cloud file is 640 x 480 points of 8 floats [x y z 1 r g b 1], little endian, row-major (src/kinect_frame_grabber.cpp:252-272).
@@ -46,13 +48,14 @@ std::string data_path (const std::string &name) { return exists (name) ? name : 
 
 template <cl_algo::ICP::ICPStepConfigT RC>
 int run (int device, icp::Mode mode, const std::vector<icp_float8> &pc1, const std::vector<icp_float8> &pc2, const std::string &out,
-         int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa, icp::RobustLoss robust, float gicp_eps)
+         int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa, icp::RobustLoss robust, float gicp_eps, bool symmetric)
 {
     ICPReg<RC, cl_algo::ICP::ICPStepConfigW::WEIGHTED> app (device, mode);
     if (reject_flags || max_dist > 0.f) app.setRejection (reject_flags, max_dist);
     if (trim != 1.f) app.setTrimming (trim);
     if (robust.loss != icp::RobustLoss::NONE) app.setRobustLoss (robust);
     if (gicp_eps > 0.f) app.setPlaneToPlane (gicp_eps);
+    if (symmetric) app.setSymmetric (true);
     if (kappa >= 0.f) {
         app.setNormals (ICP_NORMALS_GRID, 128); app.setColorWeight (kappa);
         app.setErrorMetric (ICP_METRIC_COLORED, p2pl_mu >= 0.f ? p2pl_mu : 0.f);
@@ -78,7 +81,7 @@ int main (int argc, char **argv)
 {
     std::vector<std::string> names;
     std::string out;
-    int device = 0; bool svd = false;
+    int device = 0; bool svd = false, symmetric = false;
     int reject_flags = 0; float max_dist = 0.f, trim = 1.f, p2pl_mu = -1.f, kappa = -1.f, gicp_eps = 0.f;     // (p2pl_mu < 0: point-to-point; kappa < 0: not colored; gicp_eps 0: off)
     icp::RobustLoss robust;
     icp::Mode mode = icp::Mode::FAST;
@@ -106,6 +109,7 @@ int main (int argc, char **argv)
             gicp_eps = std::strtof (argv[++i], nullptr);
             if (!(gicp_eps > 0.f && gicp_eps <= 1.f)) { std::fprintf (stderr, "--plane-to-plane: EPS must be in (0, 1]\n"); return 2; }
         }
+        else if (a == "--symmetric") symmetric = true;
         else if (a == "--robust" && i + 1 < argc) {
             const std::string v = argv[++i];
             const size_t c = v.find (':');
@@ -120,7 +124,7 @@ int main (int argc, char **argv)
         else if (a.rfind ("--", 0) == 0) { std::fprintf (stderr, "unknown option %s\n", a.c_str ()); return 2; }
         else names.push_back (a);
     }
-    if (gicp_eps > 0.f && p2pl_mu < 0.f) p2pl_mu = 0.f;                  // (plane-to-plane acts in the point-to-plane metric)
+    if ((gicp_eps > 0.f || symmetric) && p2pl_mu < 0.f) p2pl_mu = 0.f;   // (plane-to-plane and symmetric act in the point-to-plane metric)
     try
     {
         std::vector<icp_float8> pc1, pc2;
@@ -133,8 +137,8 @@ int main (int argc, char **argv)
         } else {
             read_cloud (data_path (names[0]), pc1); read_cloud (data_path (names[1]), pc2);
         }
-        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps)
-                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps);
+        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric)
+                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric);
     }
     catch (const std::exception &e)
     {

@@ -168,6 +168,8 @@ def lib():
     sig("icp_get_color_weight", i32, vp, C.POINTER(f32))
     sig("icp_set_plane_to_plane", i32, vp, f32)
     sig("icp_get_plane_to_plane", i32, vp, C.POINTER(f32))
+    sig("icp_set_symmetric", i32, vp, i32)
+    sig("icp_get_symmetric", i32, vp, C.POINTER(i32))
     sig("icp_get_max_iterations", i32, vp, C.POINTER(u32))
     sig("icp_set_max_iterations", i32, vp, u32)
     sig("icp_get_angle_threshold", i32, vp, C.POINTER(f64))
@@ -198,6 +200,7 @@ def lib():
     sig("icp_batch_set_normals", i32, vp, i32, u32)
     sig("icp_batch_set_color_weight", i32, vp, f32)
     sig("icp_batch_set_plane_to_plane", i32, vp, f32)
+    sig("icp_batch_set_symmetric", i32, vp, i32)
     sig("icp_batch_write", i32, vp, u32, i32, vp)
     sig("icp_batch_build_rbc", i32, vp)
     sig("icp_batch_run", i32, vp)
@@ -743,6 +746,19 @@ class ICPStep:
         self._chk(self._L.icp_get_plane_to_plane(self._h, C.byref(v)))
         return v.value
 
+    def set_symmetric(self, on=True):
+        """Symmetric ICP (icp_set_symmetric; Rusinkiewicz 2019; not reference behaviour): with ErrorMetric.POINT_TO_PLANE every pair's
+        residual is taken along the mean of the two frames' normals and the rotation is split evenly between the frames.  The moving
+        frame's normals are Memory.NORMALS_M, as for set_plane_to_plane (with which, as with ErrorMetric.COLORED, it does not
+        combine): computed from M with Normals.GRID (by buildRBC and every later write of M), written by the user with Normals.GIVEN."""
+        self._chk(self._L.icp_set_symmetric(self._h, int(bool(on))))
+
+    def symmetric(self):
+        """Whether the symmetric objective is switched on."""
+        v = C.c_int32()
+        self._chk(self._L.icp_get_symmetric(self._h, C.byref(v)))
+        return bool(v.value)
+
     # -- extensions ------------------------------------------------------------------------
     def setPowerMode(self, mode):
         self._chk(self._L.icp_set_power_mode(self._h, mode))
@@ -1100,6 +1116,10 @@ class ICPBatch:
     def set_plane_to_plane(self, epsilon):
         """ICPStep.set_plane_to_plane on every registration (icp_batch_set_plane_to_plane)."""
         self._chk(self._L.icp_batch_set_plane_to_plane(self._b, float(epsilon)))
+
+    def set_symmetric(self, on=True):
+        """ICPStep.set_symmetric on every registration (icp_batch_set_symmetric)."""
+        self._chk(self._L.icp_batch_set_symmetric(self._b, int(bool(on))))
 
     def write(self, i, mem, ptr):
         arr = np.ascontiguousarray(ptr, dtype=np.float32)

@@ -426,6 +426,19 @@ int icp_batch_set_plane_to_plane (icp_batch_handle b, float epsilon) try
 }
 ICP_CATCH_ALL
 
+int icp_batch_set_symmetric (icp_batch_handle b, int on) try
+{
+    // (the argument first, as icp_set_symmetric does)
+    if (on != 0 && on != 1) return bfail (b, ICP_EINVAL, "icp_batch_set_symmetric: on must be 0 or 1");
+    if (!b) return bfail (b, ICP_EINVAL, "icp_batch_set_symmetric: null handle");
+    for (icp_handle h : b->slots) {
+        int rc = icp_set_symmetric (h, on);
+        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
+    }
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
 int icp_batch_set_normals (icp_batch_handle b, int source, uint32_t grid_width) try
 {
     if (!b) return ICP_EINVAL;

@@ -205,7 +205,7 @@ static int write_gicp_eps (icp_context *h)
     return ICP_OK;
 }
 
-// plane-to-plane with ICP_NORMALS_GRID: the moving normals of registrations b0 .. b0 + nb - 1 follow a new M, in stream order behind its copy
+// plane-to-plane or symmetric with ICP_NORMALS_GRID: the moving normals of registrations b0 .. b0 + nb - 1 follow a new M, in stream order behind its copy
 // (a width that does not divide m: nothing — icp_build_rbc refuses the handle anyway)
 static void normals_m_follow (icp_context *h, uint32_t b0, uint32_t nb)
 {
@@ -806,6 +806,18 @@ int icp_get_robust_loss (icp_handle h, int *loss, float *scale) try
     return ICP_OK;
 }
 ICP_CATCH_ALL
+// The two settings that need the moving frame's normals, plane-to-plane and symmetric, share one word of icp_params (p.gicp: 1, 2); the
+// handle keeps what the user set apart (gicp_eps, symmetric), so that need () can name both when they are on together.  A changed word
+// changes which moments kernel a point-to-plane iteration runs and what buildRBC launches: graphs captured anew.
+static void moving_normals_word (icp_context *h)
+{
+    const uint32_t word = h->gicp_eps > 0.f ? 1u : h->symmetric ? ICP_MOVING_NORMALS_SYM : 0u;
+    if (word == h->p.gicp) return;
+    // (grid normals: the last buildRBC computed no moving normals — the next run needs a new one, as after a new F)
+    if (!h->p.gicp && h->p.nrm_grid) h->built = false;
+    h->p.gicp = word;
+    drop_graphs (h);
+}
 // plane-to-plane (include/icp_amd.h, icp_gicp.hip).  On <-> off changes which moments kernel a point-to-plane iteration runs and what
 // buildRBC launches: the route of icp_set_trimming (graphs captured anew).  A new epsilon while it stays on goes to its device word, as
 // kappa does (icp_set_color_weight): no graph is touched.
@@ -815,7 +827,6 @@ int icp_set_plane_to_plane (icp_handle h, float epsilon) try
     if (!(epsilon >= 0.f && epsilon <= 1.f)) return fail (h, ICP_EINVAL, "icp_set_plane_to_plane: epsilon must be in [0, 1] (0: off)");
     if (!h) return fail (h, ICP_EINVAL, "icp_set_plane_to_plane: null handle");
     { int rc = outputs_before_change (h); if (rc) return rc; }
-    const uint32_t on = epsilon > 0.f ? 1u : 0u;
     h->gicp_eps = epsilon;
     if (h->inited) {
         int rc = set_device (h); if (rc) return rc;
@@ -823,12 +834,7 @@ int icp_set_plane_to_plane (icp_handle h, float epsilon) try
         if ((rc = write_gicp_eps (h))) return rc;
         HIPCHK (h, hipStreamSynchronize (h->stream));
     }
-    if (on != h->p.gicp) {
-        h->p.gicp = on;
-        // (grid normals: the last buildRBC computed no moving normals — the next run needs a new one, as after a new F)
-        if (on && h->p.nrm_grid) h->built = false;
-        drop_graphs (h);
-    }
+    moving_normals_word (h);
     return ICP_OK;
 }
 ICP_CATCH_ALL
@@ -837,6 +843,30 @@ int icp_get_plane_to_plane (icp_handle h, float *epsilon) try
     api_guard guard_ (h);
     if (!h || !epsilon) return ICP_EINVAL;
     *epsilon = h->gicp_eps;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+// the symmetric objective (include/icp_amd.h, icp_symmetric.hip): the route of icp_set_plane_to_plane, without a device word
+int icp_set_symmetric (icp_handle h, int on) try
+{
+    api_guard guard_ (h);
+    if (on != 0 && on != 1) return fail (h, ICP_EINVAL, "icp_set_symmetric: on must be 0 or 1");
+    if (!h) return fail (h, ICP_EINVAL, "icp_set_symmetric: null handle");
+    { int rc = outputs_before_change (h); if (rc) return rc; }
+    h->symmetric = on != 0;
+    if (h->inited) {
+        int rc = set_device (h); if (rc) return rc;
+        if ((rc = run_close_all (h))) return rc;
+    }
+    moving_normals_word (h);
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+int icp_get_symmetric (icp_handle h, int *on) try
+{
+    api_guard guard_ (h);
+    if (!h || !on) return ICP_EINVAL;
+    *on = h->symmetric ? 1 : 0;
     return ICP_OK;
 }
 ICP_CATCH_ALL

@@ -113,6 +113,7 @@ struct icp_context {
     double stat_launch_max_us = 0.0; uint64_t stat_launch_slow = 0, stat_launch_total = 0;   // launch calls of all checked runs since icp_init
     float color_kappa = 0.f;                     // colored ICP's kappa (icp_set_color_weight; survives icp_init): its device word is icp_color_kappa
     float robust_scale = 0.f;                    // the robust loss's scale k (icp_set_robust_loss; 0 while off; survives icp_init): its device word is icp_robust_scale
+    bool symmetric = false;                      // the symmetric objective (icp_set_symmetric; survives icp_init): with gicp_eps it decides p.gicp
     float gicp_eps = 0.f;                        // plane-to-plane's epsilon (icp_set_plane_to_plane; 0 while off; survives icp_init): its device word is icp_gicp_eps
     uint64_t graph_clock = 0, param_gen = 0;     // LRU stamp of the graph cache; generation of the parameters the cached graphs were captured with
     float *dTin = nullptr;                       // device scratch for write(T)

@@ -99,8 +99,10 @@ struct icp_params {
     unsigned long long *hmirror; // [batch]  ICP_MIRROR_WORD (epoch, done, k) stored by the lane that publishes a registration's state
     icp_reg_state *hstate;       // [batch]  the final state of a run, stored by its end kernel in front of the word's FINAL bit
     uint32_t epoch;              // tag of the run the words belong to (a word of another epoch is stale)
-    uint32_t gicp;               // plane-to-plane (icp_set_plane_to_plane): 1 while epsilon > 0, whatever the metric (icp_gicp: in effect).  It fills
-                                 // the alignment hole behind `epoch`: no other field moves.  epsilon itself is a device word (icp_gicp_eps)
+    uint32_t gicp;               // a metric that needs the moving frame's normals, whatever the metric word: 1 plane-to-plane (icp_set_plane_to_plane,
+                                 // epsilon > 0; icp_gicp: in effect), 2 symmetric (icp_set_symmetric; icp_sym: in effect), 0 neither.  With both
+                                 // switched on it is 1 and every run is refused (icp_run.hip: need).  It fills the alignment hole behind `epoch`:
+                                 // no other field moves.  epsilon itself is a device word (icp_gicp_eps)
     // tracking with frames gated on the device (icp_capi.hip: track_submit): consecutive frames alternate between two streams, so the
     // launches of a frame that has converged and the next frame's run concurrently
     uint32_t *run_flag;          // [batch]  epoch of the run that has converged: its remaining launches leave at once and WRITE NOTHING (one flag per
@@ -160,7 +162,11 @@ static __host__ __device__ __forceinline__ bool icp_apply_pass (const icp_params
 static __host__ __device__ __forceinline__ bool icp_p2pl (const icp_params &p) { return p.metric != 0u; }
 static __host__ __device__ __forceinline__ bool icp_colored (const icp_params &p) { return p.metric == ICP_METRIC_COLORED_; }
 // plane-to-plane in effect: switched on, and the metric is point-to-plane (icp_gicp.hip has the moments then)
-static __host__ __device__ __forceinline__ bool icp_gicp (const icp_params &p) { return p.gicp != 0u && p.metric == 1u; }
+static __host__ __device__ __forceinline__ bool icp_gicp (const icp_params &p) { return p.gicp == 1u && p.metric == 1u; }
+// the symmetric objective in effect: switched on, and the metric is point-to-plane (icp_symmetric.hip has the moments then, and
+// k_p2pl_finalize takes the symmetric increment)
+#define ICP_MOVING_NORMALS_SYM 2u
+static __host__ __device__ __forceinline__ bool icp_sym (const icp_params &p) { return p.gicp == ICP_MOVING_NORMALS_SYM && p.metric == 1u; }
 static __host__ __device__ __forceinline__ uint32_t icp_p2pl_nblk (uint32_t m) { return (m + ICP_P2PL_BLOCK - 1u) / ICP_P2PL_BLOCK; }
 
 // The moments' allocation p.mom, offsets in doubles.  icp_params has no room for more pointers, so everything the opt-in paths keep per
@@ -201,7 +207,7 @@ static __host__ __device__ inline float *icp_gicp_eps (const icp_params &p) { re
 // The XP allocation of one RBC set, offsets in floats: [batch][m][8] the permuted database, then [batch][m] float4 NORMALS_F and
 // [batch][m] float4 COLOR_GRAD_F ([gx gy gz C] per fixed point).  The normals and gradients belong to the fixed frame as the RBC does,
 // so a tracked handle's second RBC set (icp_track.hip) carries its own with it.  Behind them [batch][m] float4 NORMALS_M, the moving
-// frame's normals of plane-to-plane (icp_params has no room for a pointer of their own; tracking does not combine with them).
+// frame's normals of plane-to-plane and the symmetric objective (icp_params has no room for a pointer of their own; tracking does not combine with them).
 struct icp_xp_layout {
     size_t normals, color_grad, normals_m, total;
 };
@@ -307,9 +313,10 @@ uint32_t icp_trim_launches (const icp_params &p);                             //
 void icp_launch_robust_apply (const icp_params &p, hipStream_t s);            // icp_robust.hip: k_trim_apply<fused, true> (a point-to-point robust loss)
 void icp_launch_plane_moments_robust (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);   // icp_robust.hip: k_plane_moments<colored, true>
 void icp_launch_p2pl_solve (const icp_params &p, hipStream_t s);             // icp_p2pl.hip: k_plane_moments<colored?> + k_p2pl_finalize
-void icp_launch_normals_grid (const icp_params &p, hipStream_t s);           // icp_p2pl.hip: k_normals_grid (+ colored: k_color_grad_grid; plane-to-plane: + NORMALS_M), behind buildRBC
+void icp_launch_normals_grid (const icp_params &p, hipStream_t s);           // icp_p2pl.hip: k_normals_grid (+ colored: k_color_grad_grid; plane-to-plane, symmetric: + NORMALS_M), behind buildRBC
 void icp_launch_normals_m (const icp_params &p, hipStream_t s, uint32_t b0, uint32_t nb);   // icp_p2pl.hip: k_normals_grid pointed at M, registrations b0 .. b0 + nb - 1
 void icp_launch_gicp_moments (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);          // icp_gicp.hip: k_gicp_moments / k_gicp_moments_robust
+void icp_launch_sym_moments (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);           // icp_symmetric.hip: k_sym_moments<robust?>
 #define ICP_P2PL_LAUNCHES 2u                                                  // launches of icp_launch_p2pl_solve
 void icp_launch_owner_search_dense (const icp_params &p, hipStream_t s);
 uint32_t icp_tbox_of (const icp_params &p);

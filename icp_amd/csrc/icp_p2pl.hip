@@ -7,7 +7,8 @@
 // weighed by the loss's omega of its residual) and their tree over blocks
 // of ICP_P2PL_BLOCK pairs; k_p2pl_finalize, one workgroup per registration: the tree over the block partials, LDL^T in one lane, the
 // increment composed with icp_compose's arithmetic and checked with icp_check_converged.  k_normals_grid computes NORMALS_F from F
-// behind buildRBC (ICP_NORMALS_GRID; with plane-to-plane on, whose moments are icp_gicp.hip's, also NORMALS_M from M), and with the colored metric k_color_grad_grid computes COLOR_GRAD_F behind it.  None of the
+// behind buildRBC (ICP_NORMALS_GRID; with plane-to-plane or the symmetric objective on, whose moments are icp_gicp.hip's and
+// icp_symmetric.hip's, also NORMALS_M from M), and with the colored metric k_color_grad_grid computes COLOR_GRAD_F behind it.  None of the
 // point-to-point kernels carries any of this code; the translation unit is built with -ffp-contract=off like every other, so each
 // expression below is evaluated exactly in the order it is written.
 #include "icp_plane_moments.h"          // (intensity)
@@ -77,7 +78,7 @@ __device__ __forceinline__ void ldlt_solve (const double (&A)[N][N], const doubl
 }  // namespace
 
 // NORMALS_F of the fixed set (src = F), read as a row-major grid p.nrm_grid wide (m % width == 0: icp_build_rbc checks it); with
-// plane-to-plane on also NORMALS_M of the moving set (src = M).  One thread per point, grid.y = registration counted from src and nrm.
+// plane-to-plane or the symmetric objective on also NORMALS_M of the moving set (src = M).  One thread per point, grid.y = registration counted from src and nrm.
 // fp32, no contraction:
 //   c = dh x dv,  n = c / sqrtf ((c.x^2 + c.y^2) + c.z^2),  n = -n if (n.x C.x + n.y C.y) + n.z C.z > 0 (faces the sensor at the origin),
 //   n = 0 when the centre is invalid, a difference is missing, or the length is not > 0 and finite.
@@ -173,7 +174,8 @@ __global__ __launch_bounds__ (256) void k_color_grad_grid (icp_params p, const f
 #define P2PL_LDS 4096u           // doubles of the finalize's tree buffer (nblk <= 4096: m <= 2^20)
 
 // One workgroup per registration: the halving tree over the block partials zero-padded to P = 2^ceil(log2 nblk), as many terms at a time
-// as the LDS buffer holds; then lane 0: ldlt_solve<6>, the increment, the composition and the check.
+// as the LDS buffer holds; then lane 0: ldlt_solve<6>, the increment (point-to-plane's, or the symmetric objective's while icp_sym (p)),
+// the composition and the check.
 __global__ __launch_bounds__ (256) void k_p2pl_finalize (icp_params p, const double *part, double *sys, uint32_t nblk, uint32_t P)
 {
     const uint32_t b = blockIdx.x, tid = threadIdx.x;
@@ -246,11 +248,29 @@ __global__ __launch_bounds__ (256) void k_p2pl_finalize (icp_params p, const dou
     }
     float Tk[8], Tn[8], Rn[9], Rk[9];
     if (ok) {
-        // qk = (w/2, 1) / |(w/2, 1)| in double, rounded to float; tk = (float) tau; sk = 1
-        const double hx = x[0] * 0.5, hy = x[1] * 0.5, hz = x[2] * 0.5;
-        const double inv = 1.0 / sqrt (((hx * hx + hy * hy) + hz * hz) + 1.0);
-        Tk[0] = (float) (hx * inv); Tk[1] = (float) (hy * inv); Tk[2] = (float) (hz * inv); Tk[3] = (float) inv;
-        Tk[4] = (float) x[3]; Tk[5] = (float) x[4]; Tk[6] = (float) x[5]; Tk[7] = 1.f;
+        if (icp_sym (p)) {
+            // the symmetric objective (icp_set_symmetric): x = (a, t) with half the rotation applied to each frame, the step Rot o Trans o Rot.
+            // qk = (a, 1) / |(a, 1)|: the rotation by 2 theta about a, tan theta = |a|;  tk = R_a (cos theta t), R_a the rotation by theta,
+            // by Rodrigues' formula with c = cos theta: c2 t + c2 (a x t) + a ((a . t) c3 / (1 + c));  sk = 1
+            const double ax = x[0], ay = x[1], az = x[2], tx = x[3], ty = x[4], tz = x[5];
+            const double aa = (ax * ax + ay * ay) + az * az;
+            const double c = 1.0 / sqrt (aa + 1.0);
+            Tk[0] = (float) (ax * c); Tk[1] = (float) (ay * c); Tk[2] = (float) (az * c); Tk[3] = (float) c;
+            const double ux = ay * tz - az * ty, uy = az * tx - ax * tz, uz = ax * ty - ay * tx;
+            const double at = (ax * tx + ay * ty) + az * tz;
+            const double c2 = c * c;
+            const double k3 = (c2 * c) / (1.0 + c);
+            Tk[4] = (float) ((c2 * tx + c2 * ux) + ax * (at * k3));
+            Tk[5] = (float) ((c2 * ty + c2 * uy) + ay * (at * k3));
+            Tk[6] = (float) ((c2 * tz + c2 * uz) + az * (at * k3));
+            Tk[7] = 1.f;
+        } else {
+            // qk = (w/2, 1) / |(w/2, 1)| in double, rounded to float; tk = (float) tau; sk = 1
+            const double hx = x[0] * 0.5, hy = x[1] * 0.5, hz = x[2] * 0.5;
+            const double inv = 1.0 / sqrt (((hx * hx + hy * hy) + hz * hz) + 1.0);
+            Tk[0] = (float) (hx * inv); Tk[1] = (float) (hy * inv); Tk[2] = (float) (hz * inv); Tk[3] = (float) inv;
+            Tk[4] = (float) x[3]; Tk[5] = (float) x[4]; Tk[6] = (float) x[5]; Tk[7] = 1.f;
+        }
         icp_compose_pure (Tprev, Rprev, Tk, nullptr, 0, Tn, Rn, Rk);            // (icp_compose's arithmetic, registers in and out)
     } else {
         float S[11], means[8];
@@ -275,6 +295,7 @@ void icp_launch_p2pl_solve (const icp_params &p, hipStream_t s)
     const float *kappa = icp_color_kappa (p);
     const dim3 grid (nblk, p.batch);
     if (icp_gicp (p)) icp_launch_gicp_moments (p, s, part, nblk);                  // (icp_gicp.hip: plane-to-plane, with or without a robust loss)
+    else if (icp_sym (p)) icp_launch_sym_moments (p, s, part, nblk);               // (icp_symmetric.hip: the symmetric objective, likewise)
     else if (icp_robust (p)) icp_launch_plane_moments_robust (p, s, part, nblk);   // (icp_robust.hip)
     else if (icp_colored (p)) hipLaunchKernelGGL (k_plane_moments<true>, grid, dim3 (ICP_P2PL_BLOCK), 0, s, p, nrm, part, nblk, grad, kappa);
     else hipLaunchKernelGGL (k_plane_moments<false>, grid, dim3 (ICP_P2PL_BLOCK), 0, s, p, nrm, part, nblk, grad, kappa);
@@ -290,7 +311,7 @@ void icp_launch_normals_grid (const icp_params &p, hipStream_t s)
     if (p.gicp) icp_launch_normals_m (p, s, 0u, p.batch);
 }
 
-// plane-to-plane with ICP_NORMALS_GRID: NORMALS_M of registrations b0 .. b0 + nb - 1 from M, by the same kernel
+// plane-to-plane or symmetric with ICP_NORMALS_GRID: NORMALS_M of registrations b0 .. b0 + nb - 1 from M, by the same kernel
 void icp_launch_normals_m (const icp_params &p, hipStream_t s, uint32_t b0, uint32_t nb)
 {
     const dim3 grid ((p.m + 255u) / 256u, nb);

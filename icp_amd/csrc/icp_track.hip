@@ -330,7 +330,8 @@ static int track_submit (icp_context *h, const void *cloud, int warm_start, bool
     int rc = need (h, false, true); if (rc) return rc;
     if ((rc = keeper_error (h))) return rc;
     if (!cloud) return fail (h, ICP_EINVAL, "null pointer");
-    if (h->p.gicp) return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while plane-to-plane is on (icp_set_plane_to_plane)");
+    if (h->gicp_eps > 0.f) return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while plane-to-plane is on (icp_set_plane_to_plane)");
+    if (h->symmetric) return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while the symmetric objective is on (icp_set_symmetric)");
     // (point-to-plane: each frame's normals come from its own landmarks, which only buildRBC can give it — ICP_NORMALS_GRID)
     if (icp_p2pl (h->p) && !h->p.nrm_grid)
         return fail (h, ICP_ESTATE, "icp_track_submit: point-to-plane tracking needs ICP_NORMALS_GRID (icp_set_normals)");

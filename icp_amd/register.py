@@ -13,13 +13,14 @@ from .io import load_pc8d, save_pc8d
 
 def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, angle_threshold=0.001,
                     translation_threshold=0.01, reduce_mode=ReduceMode.FUSED, reject_invalid=False, max_dist=None, trim=1.0,
-                    point_to_plane=None, colored=None, robust=None, plane_to_plane=None):
+                    point_to_plane=None, colored=None, robust=None, plane_to_plane=None, symmetric=False):
     """Returns (T[8], k, latency_ms, transformed moving cloud).  reject_invalid / max_dist: correspondence rejection
     (ICPStep.set_rejection), trim: the fraction of pairs trimmed ICP keeps (ICPStep.set_trimming; 1.0: off), point_to_plane: mu of
     point-to-plane ICP with the fixed frame's normals from its 128 x 128 landmark grid (ICPStep.set_error_metric; None: off),
     colored: kappa of colored ICP, with grid normals and intensity gradients and mu = point_to_plane or 0 (ICPStep.set_color_weight;
     None: off), robust: (RobustLoss kind, scale) of a robust loss (ICPStep.set_robust_loss; None: off), plane_to_plane: epsilon of
-    Generalized ICP, with both frames' grid normals and mu = point_to_plane or 0 (ICPStep.set_plane_to_plane; None: off); none is the
+    Generalized ICP, with both frames' grid normals and mu = point_to_plane or 0 (ICPStep.set_plane_to_plane; None: off), symmetric:
+    the symmetric objective, with both frames' grid normals and mu = point_to_plane or 0 (ICPStep.set_symmetric); none is the
     reference's behaviour, all are off by default."""
     reg = ICP(device)
     reg.init(16384, 256, a, c, max_iterations, angle_threshold, translation_threshold)   # src/ocl_icp_reg.cpp:81-88
@@ -35,6 +36,10 @@ def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, a
         reg.set_plane_to_plane(plane_to_plane)
         if point_to_plane is None:
             point_to_plane = 0.0                               # (plane-to-plane acts in the point-to-plane metric)
+    if symmetric:
+        reg.set_symmetric(True)
+        if point_to_plane is None:
+            point_to_plane = 0.0                               # (the symmetric objective acts in the point-to-plane metric)
     if colored is not None:
         reg.set_normals(Normals.GRID, 128)
         reg.set_color_weight(colored)
@@ -131,11 +136,14 @@ def main(argv=None):
     ap.add_argument("--plane-to-plane", type=_epsilon, default=None, metavar="EPS",
                     help="Generalized ICP: point-to-plane with every pair weighed by both frames' grid normals, covariance parameter "
                          "EPS in (0, 1], e.g. 0.001; implies --point-to-plane 0 when no MU is given (not reference behaviour)")
+    ap.add_argument("--symmetric", action="store_true",
+                    help="symmetric ICP (Rusinkiewicz 2019): point-to-plane along the mean of both frames' grid normals, the rotation "
+                         "split between the frames; implies --point-to-plane 0 when no MU is given (not reference behaviour)")
     args = ap.parse_args(argv)
     T, k, ms, out = register_clouds(load_pc8d(args.fixed), load_pc8d(args.moving), args.device, a=args.alpha,
                                     reject_invalid=args.reject_invalid, max_dist=args.max_dist, trim=args.trim,
                                     point_to_plane=args.point_to_plane, colored=args.colored, robust=args.robust,
-                                    plane_to_plane=args.plane_to_plane)
+                                    plane_to_plane=args.plane_to_plane, symmetric=args.symmetric)
     q, t, s = T[:4], T[4:7], T[7]
     sinth_2 = float(np.linalg.norm(q[:3]))
     angle = 180.0 / math.pi * 2 * math.atan2(sinth_2, float(q[3]))

@@ -526,7 +526,7 @@ namespace ICP
     public:
         /*! \brief reference include/ICP/algorithms.hpp:2241-2267 */
         enum class Memory : uint8_t { H_IN_F, H_IN_M, H_IO_T, D_IN_F, D_IN_M, D_IO_T,
-                                      NORMALS_M /*!< not in the reference: the moving frame's normals of setPlaneToPlane (m x float4, written from `ptr`) */ };
+                                      NORMALS_M /*!< not in the reference: the moving frame's normals of setPlaneToPlane and setSymmetric (m x float4, written from `ptr`) */ };
 
         ICPStep (icp::Env _env, icp::Mode _mode = icp::Mode::FAST) : env (_env), h (nullptr), a (1e2f), c (1e-6f), m (0), nr (0)
         {
@@ -643,6 +643,12 @@ namespace ICP
          *         Memory::NORMALS_M: computed from M with ICP_NORMALS_GRID, written by the user with ICP_NORMALS_GIVEN. */
         void setPlaneToPlane (float epsilon) { check (icp_set_plane_to_plane (h, epsilon)); }
         float getPlaneToPlane () { float e = 0.f; check (icp_get_plane_to_plane (h, &e)); return e; }
+        /*! \brief Symmetric ICP (icp_set_symmetric, include/icp_amd.h; Rusinkiewicz 2019; not in the reference, off by default): with
+         *         setErrorMetric (ICP_METRIC_POINT_TO_PLANE, mu) every pair's residual is taken along the mean of the two frames' normals
+         *         and the rotation is split evenly between the frames.  The moving frame's normals are Memory::NORMALS_M, as for
+         *         setPlaneToPlane, with which it does not combine. */
+        void setSymmetric (bool on = true) { check (icp_set_symmetric (h, on ? 1 : 0)); }
+        bool getSymmetric () { int on = 0; check (icp_get_symmetric (h, &on)); return on != 0; }
 
         float *hPtrInF;  /*!< Staging buffer of the fixed set (reference: mapped H_IN_F). */
         float *hPtrInM;  /*!< Staging buffer of the moving set. */

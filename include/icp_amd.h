@@ -89,7 +89,7 @@ typedef enum {
     ICP_MEM_NORMALS_F = 21,/* io   m x float4   normals of the fixed landmarks [nx ny nz 0] (point-to-plane) */
     ICP_MEM_PLANE_SYSTEM = 22, /* out double[28] point-to-plane: A's upper triangle (21), b (6), status (0 while off) */
     ICP_MEM_COLOR_GRAD_F = 23, /* io m x float4  colored ICP: intensity gradients of the fixed landmarks [gx gy gz C] */
-    ICP_MEM_NORMALS_M = 24,    /* io m x float4  normals of the moving landmarks [nx ny nz 0], indexed like M (plane-to-plane) */
+    ICP_MEM_NORMALS_M = 24,    /* io m x float4  normals of the moving landmarks [nx ny nz 0], indexed like M (plane-to-plane, symmetric) */
     ICP_MEM_COUNT_
 } icp_mem;
 
@@ -416,6 +416,56 @@ int icp_get_robust_loss (icp_handle h, int *loss, float *scale);
 int icp_set_plane_to_plane (icp_handle h, float epsilon);
 int icp_get_plane_to_plane (icp_handle h, float *epsilon);
 
+/* Symmetric ICP (Rusinkiewicz 2019, "A Symmetric Objective Function for ICP"; not reference behaviour; off by default): point-to-plane
+ * with the residual of every pair taken along the mean of the two frames' normals and the rotation split evenly between the frames,
+ *     sum_i w_i [ (P_i - Q_i) . (n_P,i + n_Q,i) ]^2,
+ * which is zero whenever a pair lies on a common circular arc or quadratic patch, not only on a common plane.  The rule:
+ *   - on == 0 (the default) is off: the same kernels, launches, graphs and bits as without it, for every metric.  on == 1 turns it on;
+ *     it takes effect while the metric is ICP_METRIC_POINT_TO_PLANE.  ICP_METRIC_POINT_TO_POINT ignores it, as it ignores mu.  With
+ *     ICP_METRIC_COLORED, or with plane-to-plane (icp_set_plane_to_plane) on at the same time under a plane metric, every step, run,
+ *     fixed run and batched run returns ICP_ESTATE with a message that names both settings (the combinations are not provided).
+ *   - ICP_MEM_NORMALS_M follows exactly plane-to-plane's rules.  ICP_NORMALS_GIVEN: the user writes it; it is used as written.
+ *     ICP_NORMALS_GRID with the setting on: computed from M by the grid rule of ICP_MEM_NORMALS_F, by icp_build_rbc behind the fixed
+ *     normals, and again by every later icp_write / icp_write_b / icp_write_cloud / icp_batch_write of ICP_MEM_M.  Switching the setting
+ *     on with ICP_NORMALS_GRID (plane-to-plane off) leaves the handle without moving normals: icp_run and the other runs return
+ *     ICP_ESTATE until icp_build_rbc has run again.  While both this setting and plane-to-plane are off, nothing computes or reads the
+ *     buffer.
+ *   - Per pair, in double from the float inputs, every expression in the order written, with no contraction; w = PF.w, P = PM.xyz,
+ *     Q = PF.xyz as in the point-to-plane rule:
+ *         N_Q = NORMALS_F[id],  N_M = NORMALS_M[i] (query order); a non-finite normal counts as zero.
+ *         R = the registration's cumulative rotation before the step (ICP_MEM_R, the floats this iteration's search used);
+ *         N_P = R N_M, each component (R_a0 mx + R_a1 my) + R_a2 mz.
+ *         o = (nqx npx + nqy npy) + nqz npz.  If o < 0, N_P is negated componentwise: the two normals point the same way.
+ *         n = 0.5 (N_Q + N_P), componentwise (nqx + npx) * 0.5: the mean normal, so that mu and a robust scale k keep the meaning they
+ *         have under point-to-plane.  A pair with one absent normal counts a quarter; a pair with none contributes its mu share only.
+ *         s = P + Q,  d = Q - P, componentwise.
+ *         c = s x n = (sy nz - sz ny, sz nx - sx nz, sx ny - sy nx);  J = (c, n).
+ *         r = (dx nx + dy ny) + dz nz;  ss = (sx sx + sy sy) + sz sz.
+ *         G = point-to-plane's G with s in P's place: G00 = ss - sx sx, G01 = -(sx sy), G02 = -(sx sz), G11 = ss - sy sy,
+ *         G12 = -(sy sz), G22 = ss - sz sz, G04 = -sz, G05 = sy, G13 = sz, G15 = -sx, G23 = -sy, G24 = sx; the unit block and the zeros
+ *         as there.
+ *         g = (s x d, d) = (sy dz - sz dy, sz dx - sx dz, sx dy - sy dx, dx, dy, dz).
+ *         term (a, b), a <= b, row-major:  w (J_a J_b + mu G_ab)        term 21 + a:  w (J_a r + mu g_a)
+ *     w == 0 selects exact zeros for the pair.
+ *   - Robust loss: sG2 = r r + mu ((dx dx + dy dy) + dz dz),  wG = omega (sG2 / k2);  the terms are w (wG (J_a J_b + mu G_ab)) and
+ *     w (wG (J_a r + mu g_a)), wG == 0 selecting an exact zero, as in the point-to-plane rule.
+ *   - The block tree, the partial layout, the second tree, LDL^T with its pivot test, the identity step on a singular system and
+ *     ICP_MEM_PLANE_SYSTEM are point-to-plane's, unchanged.  Rejection and trimming act through w.
+ *   - The increment differs.  The solution x = (a, t) is Rusinkiewicz's: half the rotation is applied to each frame, the step is
+ *     Rot o Trans o Rot.  In double:
+ *         aa = (ax ax + ay ay) + az az;   c = 1.0 / sqrt (aa + 1.0);   qk = ((float) (ax c), (float) (ay c), (float) (az c), (float) c)
+ *         u = a x t = (ay tz - az ty, az tx - ax tz, ax ty - ay tx);   at = (ax tx + ay ty) + az tz
+ *         c2 = c c;   k3 = (c2 c) / (1.0 + c)
+ *         tk_x = (float) ((c2 tx + c2 ux) + ax (at k3)), likewise y and z;   sk = 1
+ *     So qk is the rotation by 2 theta about a with tan theta = |a|, and tk = R_a (cos theta t) with R_a the rotation by theta.  The
+ *     composition and the convergence test follow as they are.
+ *   - Turning it on or off captures the run graphs anew.  The setting survives icp_init and applies to single, batched
+ *     (icp_init_batched) and icp_batch_* registrations.  Tracking is not provided: icp_track_submit and icp_track_next return ICP_ESTATE
+ *     while it is on.
+ * ICP_EINVAL: a null handle, or `on` other than 0 / 1. */
+int icp_set_symmetric (icp_handle h, int on);
+int icp_get_symmetric (icp_handle h, int *on);
+
 /* Where the fixed frame's normals come from (point-to-plane):
  *   ICP_NORMALS_GIVEN (the default): the user writes ICP_MEM_NORMALS_F (m x float4 [nx ny nz 0] per registration, indexed like F);
  *     it is used as given and starts as zeros.  grid_width is ignored (pass 0).
@@ -623,6 +673,7 @@ int icp_batch_set_error_metric (icp_batch_handle b, int metric, float point_weig
 int icp_batch_set_normals (icp_batch_handle b, int source, uint32_t grid_width);             /* icp_set_normals on every slot */
 int icp_batch_set_color_weight (icp_batch_handle b, float kappa);                            /* icp_set_color_weight on every slot */
 int icp_batch_set_plane_to_plane (icp_batch_handle b, float epsilon);                        /* icp_set_plane_to_plane on every slot */
+int icp_batch_set_symmetric (icp_batch_handle b, int on);                                    /* icp_set_symmetric on every slot */
 int icp_batch_write (icp_batch_handle b, uint32_t i, int mem, const void *host_ptr);       /* mem: F, M, T, NORMALS_F, COLOR_GRAD_F or NORMALS_M of registration i */
 int icp_batch_build_rbc (icp_batch_handle b);
 int icp_batch_run (icp_batch_handle b);                                                      /* ICP::run of every registration */

@@ -87,6 +87,8 @@ public:
     void setColorWeight (float kappa) { reg.setColorWeight (kappa); }
     /*! \brief Generalized ICP of the registration (ICPStep::setPlaneToPlane with setErrorMetric (ICP_METRIC_POINT_TO_PLANE, mu)). */
     void setPlaneToPlane (float epsilon) { reg.setPlaneToPlane (epsilon); }
+    /*! \brief Symmetric ICP of the registration (ICPStep::setSymmetric with setErrorMetric (ICP_METRIC_POINT_TO_PLANE, mu)). */
+    void setSymmetric (bool on = true) { reg.setSymmetric (on); }
     float getColorWeight () { return reg.getColorWeight (); }
 
     /*! \brief The moving cloud after `registerPC ()` (the reference writes it into the GL vertex buffer). */

@@ -1,16 +1,17 @@
 """Diagnostic (not a test): microseconds per iteration of the plane metrics, colored ICP (ICP_METRIC_COLORED), point-to-plane and
-plane-to-plane (gicp: point-to-plane with icp_set_plane_to_plane 0.001, both frames' grid normals),
+plane-to-plane (gicp: point-to-plane with icp_set_plane_to_plane 0.001, both frames' grid normals) and symmetric (sym: point-to-plane
+with icp_set_symmetric, both frames' grid normals),
 against the default point-to-point iteration at A (16384 / 256), B (65536 / 1024) and A x 64, through the fixed-length run graphs
 bench.py times; and buildRBC back to back without normals, with grid normals (point-to-plane) and with grid normals and intensity
 gradients (colored).
 
-    python tools/diag/plane_time.py [--only {p2p,p2pl,colored,gicp}] [--reps N] [--robust KIND:SCALE]
+    python tools/diag/plane_time.py [--only {p2p,p2pl,colored,gicp,sym}] [--reps N] [--robust KIND:SCALE]
 
 --robust (e.g. cauchy:20) times every configuration with that robust loss on (icp_set_robust_loss) as well as without it.
 
 Prints one line per configuration and one JSON line at the end.  Under `rocprofv3 --kernel-trace --stats` (--only p2pl or colored)
 the per-kernel table shows the search, k_plane_moments, k_p2pl_finalize, k_normals_grid and (colored) k_color_grad_grid; --only gicp shows
-k_gicp_moments in k_plane_moments' place."""
+k_gicp_moments, --only sym k_sym_moments, in k_plane_moments' place."""
 import argparse
 import json
 import os
@@ -22,11 +23,11 @@ import icp_amd  # noqa: E402
 
 CONFIGS = {"A": (128, 256, 1), "B": (256, 1024, 1), "Ax64": (128, 256, 64)}
 METRICS = {"p2p": icp_amd.ErrorMetric.POINT_TO_POINT, "p2pl": icp_amd.ErrorMetric.POINT_TO_PLANE, "colored": icp_amd.ErrorMetric.COLORED,
-           "gicp": icp_amd.ErrorMetric.POINT_TO_PLANE}
+           "gicp": icp_amd.ErrorMetric.POINT_TO_PLANE, "sym": icp_amd.ErrorMetric.POINT_TO_PLANE}
 GICP_EPS = 1e-3
 
 
-def make(side, nr, batch, metric, robust=None, gicp=False):
+def make(side, nr, batch, metric, robust=None, gicp=False, sym=False):
     g = icp_amd.ICP(0)
     g.init(side * side, nr, 2e2, 1e-6, batch=batch)
     g.setPowerMode(icp_amd.PowerMode.SQUARED)
@@ -36,6 +37,8 @@ def make(side, nr, batch, metric, robust=None, gicp=False):
         g.set_error_metric(metric, 0.05)
     if gicp:
         g.set_plane_to_plane(GICP_EPS)
+    if sym:
+        g.set_symmetric(True)
     if robust:
         g.set_robust_loss(*robust)
     for b in range(batch):
@@ -80,7 +83,7 @@ def main():
             if args.only and mname != args.only:
                 continue
             for tag, rb in (("", None), ("_robust", robust)) if robust else (("", None),):
-                g = make(side, nr, batch, metric, rb, mname == "gicp")
+                g = make(side, nr, batch, metric, rb, mname == "gicp", mname == "sym")
                 us = per_iteration_us(g, 20, args.reps)
                 bus = build_us(g)
                 form, launches = g.run_form(), g.launches_per_iteration()
