@@ -6,7 +6,7 @@
 //   registration NAME                     data/NAME_1.bin, data/NAME_2.bin      (the reference's argument convention, :299-329)
 //   registration A B                      data/A.bin, data/B.bin — or A and B themselves when they name existing files
 //   ... [--out FILE] [--device N] [--reference-order] [--svd] [--reject-invalid] [--max-dist MM] [--trim FRACTION]
-//       [--point-to-plane MU] [--colored KAPPA] [--robust KIND:SCALE] [--plane-to-plane EPS] [--symmetric]
+//       [--point-to-plane MU] [--colored KAPPA] [--robust KIND:SCALE] [--plane-to-plane EPS] [--symmetric] [--one-to-one]
 //
 // --reject-invalid / --max-dist: correspondence rejection (icp_set_rejection: pairs with a pixel without depth at either end / pairs
 // farther apart than MM get weight 0).  --trim: trimmed ICP (icp_set_trimming: every iteration keeps the closest FRACTION in (0, 1] of the
@@ -18,6 +18,7 @@
 // every pair weighed by both frames' grid normals; implies --point-to-plane 0 when no MU is given.
 // --symmetric: symmetric ICP (icp_set_symmetric; Rusinkiewicz 2019): point-to-plane along the mean of both frames' grid normals, the
 // rotation split between the frames; implies --point-to-plane 0 when no MU is given.
+// --one-to-one: one-to-one correspondences (icp_set_unique): of the pairs that share a fixed point only the closest keeps its weight.
 // Not the reference's behaviour; off by default.
 //
 // A cloud file is 640 x 480 points of 8 floats [x y z 1 r g b 1], little endian, row-major (src/kinect_frame_grabber.cpp:252-272).
@@ -48,10 +49,11 @@ std::string data_path (const std::string &name) { return exists (name) ? name : 
 
 template <cl_algo::ICP::ICPStepConfigT RC>
 int run (int device, icp::Mode mode, const std::vector<icp_float8> &pc1, const std::vector<icp_float8> &pc2, const std::string &out,
-         int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa, icp::RobustLoss robust, float gicp_eps, bool symmetric)
+         int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa, icp::RobustLoss robust, float gicp_eps, bool symmetric, bool one_to_one)
 {
     ICPReg<RC, cl_algo::ICP::ICPStepConfigW::WEIGHTED> app (device, mode);
     if (reject_flags || max_dist > 0.f) app.setRejection (reject_flags, max_dist);
+    if (one_to_one) app.setUnique (true);
     if (trim != 1.f) app.setTrimming (trim);
     if (robust.loss != icp::RobustLoss::NONE) app.setRobustLoss (robust);
     if (gicp_eps > 0.f) app.setPlaneToPlane (gicp_eps);
@@ -81,7 +83,7 @@ int main (int argc, char **argv)
 {
     std::vector<std::string> names;
     std::string out;
-    int device = 0; bool svd = false, symmetric = false;
+    int device = 0; bool svd = false, symmetric = false, one_to_one = false;
     int reject_flags = 0; float max_dist = 0.f, trim = 1.f, p2pl_mu = -1.f, kappa = -1.f, gicp_eps = 0.f;     // (p2pl_mu < 0: point-to-point; kappa < 0: not colored; gicp_eps 0: off)
     icp::RobustLoss robust;
     icp::Mode mode = icp::Mode::FAST;
@@ -110,6 +112,7 @@ int main (int argc, char **argv)
             if (!(gicp_eps > 0.f && gicp_eps <= 1.f)) { std::fprintf (stderr, "--plane-to-plane: EPS must be in (0, 1]\n"); return 2; }
         }
         else if (a == "--symmetric") symmetric = true;
+        else if (a == "--one-to-one") one_to_one = true;
         else if (a == "--robust" && i + 1 < argc) {
             const std::string v = argv[++i];
             const size_t c = v.find (':');
@@ -137,8 +140,8 @@ int main (int argc, char **argv)
         } else {
             read_cloud (data_path (names[0]), pc1); read_cloud (data_path (names[1]), pc2);
         }
-        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric)
-                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric);
+        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one)
+                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one);
     }
     catch (const std::exception &e)
     {

@@ -87,7 +87,7 @@ class TransformKind:             # ICPTransformConfig (include/ICP/algorithms.hp
 
 class Memory:                    # icp_mem in include/icp_amd.h
     F, M, T, TK, MEANS, S, NN_ID, W, SUM_W, REPS, RBC_N, RBC_O, RBC_PERM, RBC_OWNER, RBC_XP, RID, R, RK, NN, QT, TRIM, \
-        NORMALS_F, PLANE_SYSTEM, COLOR_GRAD_F, NORMALS_M = range(25)
+        NORMALS_F, PLANE_SYSTEM, COLOR_GRAD_F, NORMALS_M, UNIQUE = range(26)
     # reference spellings (ICPStep::Memory, include/ICP/algorithms.hpp:2241-2267)
     D_IN_F, D_IN_M, D_IO_T, H_IO_T = F, M, T, T
 
@@ -158,6 +158,8 @@ def lib():
     sig("icp_get_rejection", i32, vp, C.POINTER(i32), C.POINTER(f32))
     sig("icp_set_trimming", i32, vp, f32)
     sig("icp_get_trimming", i32, vp, C.POINTER(f32))
+    sig("icp_set_unique", i32, vp, i32)
+    sig("icp_get_unique", i32, vp, C.POINTER(i32))
     sig("icp_set_robust_loss", i32, vp, i32, f32)
     sig("icp_get_robust_loss", i32, vp, C.POINTER(i32), C.POINTER(f32))
     sig("icp_set_error_metric", i32, vp, i32, f32)
@@ -195,6 +197,7 @@ def lib():
     sig("icp_batch_set_modes", i32, vp, i32, i32)
     sig("icp_batch_set_rejection", i32, vp, i32, f32)
     sig("icp_batch_set_trimming", i32, vp, f32)
+    sig("icp_batch_set_unique", i32, vp, i32)
     sig("icp_batch_set_robust_loss", i32, vp, i32, f32)
     sig("icp_batch_set_error_metric", i32, vp, i32, f32)
     sig("icp_batch_set_normals", i32, vp, i32, u32)
@@ -561,7 +564,7 @@ _MEM_DTYPE = {
     Memory.RID: (np.uint32, None), Memory.R: (np.float32, 3), Memory.RK: (np.float32, 3),
     Memory.NN: (np.float32, 4), Memory.QT: (np.float32, 4), Memory.TRIM: (np.uint32, None),
     Memory.NORMALS_F: (np.float32, 4), Memory.PLANE_SYSTEM: (np.float64, None), Memory.COLOR_GRAD_F: (np.float32, 4),
-    Memory.NORMALS_M: (np.float32, 4),
+    Memory.NORMALS_M: (np.float32, 4), Memory.UNIQUE: (np.uint32, None),
 }
 
 
@@ -685,6 +688,18 @@ class ICPStep:
         v = C.c_float()
         self._chk(self._L.icp_get_trimming(self._h, C.byref(v)))
         return v.value
+
+    def set_unique(self, on=True):
+        """One-to-one correspondences (icp_set_unique; not reference behaviour, off by default): of the pairs that share a fixed
+        point only the closest keeps its weight (ties: the lowest query index), the others get the weight 0.  It acts after
+        rejection and before trimming and the robust loss.  read(Memory.UNIQUE) gives the last iteration's (candidates, winners)."""
+        self._chk(self._L.icp_set_unique(self._h, int(on)))
+
+    def unique(self):
+        """Whether one-to-one correspondences are on."""
+        v = C.c_int32()
+        self._chk(self._L.icp_get_unique(self._h, C.byref(v)))
+        return bool(v.value)
 
     def set_robust_loss(self, loss=RobustLoss.NONE, scale=0.0):
         """Robust loss (icp_set_robust_loss; not reference behaviour, off by default): every pair's weight is multiplied by the
@@ -1097,6 +1112,15 @@ class ICPBatch:
         """The keep fraction as last set on this batch (1.0: off)."""
         return getattr(self, "_trimming", 1.0)
 
+    def set_unique(self, on=True):
+        """ICPStep.set_unique on every registration (icp_batch_set_unique)."""
+        self._chk(self._L.icp_batch_set_unique(self._b, int(on)))
+        self._unique = bool(on)
+
+    def unique(self):
+        """Whether one-to-one correspondences were last switched on for this batch."""
+        return getattr(self, "_unique", False)
+
     def set_robust_loss(self, loss=RobustLoss.NONE, scale=0.0):
         """ICPStep.set_robust_loss on every registration (icp_batch_set_robust_loss)."""
         self._chk(self._L.icp_batch_set_robust_loss(self._b, int(loss), float(scale)))
@@ -1160,7 +1184,7 @@ class ICPBatch:
     def read(self, i, mem):
         dt, cols = _MEM_DTYPE[mem]
         sizes = {Memory.T: 32, Memory.TK: 32, Memory.MEANS: 32, Memory.S: 44, Memory.NN_ID: self.m * 8, Memory.R: 36, Memory.RK: 36,
-                 Memory.F: self.m * 32, Memory.M: self.m * 32, Memory.W: self.m * 4, Memory.RID: self.m * 4, Memory.TRIM: 16,
+                 Memory.F: self.m * 32, Memory.M: self.m * 32, Memory.W: self.m * 4, Memory.RID: self.m * 4, Memory.TRIM: 16, Memory.UNIQUE: 8,
                  Memory.NN: self.m * 16, Memory.QT: self.m * 16, Memory.NORMALS_F: self.m * 16, Memory.PLANE_SYSTEM: 28 * 8,
                  Memory.COLOR_GRAD_F: self.m * 16, Memory.NORMALS_M: self.m * 16}
         nbytes = sizes[mem]

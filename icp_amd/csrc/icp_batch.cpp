@@ -371,6 +371,18 @@ int icp_batch_set_trimming (icp_batch_handle b, float keep_fraction) try
 }
 ICP_CATCH_ALL
 
+int icp_batch_set_unique (icp_batch_handle b, int on) try
+{
+    if (!b) return ICP_EINVAL;
+    if (on != 0 && on != 1) return bfail (b, ICP_EINVAL, "icp_batch_set_unique: on must be 0 or 1");
+    for (icp_handle h : b->slots) {
+        int rc = icp_set_unique (h, on);
+        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
+    }
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
 int icp_batch_set_robust_loss (icp_batch_handle b, int loss, float scale) try
 {
     // (the arguments first, as icp_set_robust_loss does: with b == NULL the message is icp_batch_last_error (NULL)'s)

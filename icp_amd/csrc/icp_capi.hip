@@ -307,6 +307,8 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     if ((rc = write_color_kappa (h))) return rc;
     if ((rc = write_robust_scale (h))) return rc;
     if ((rc = write_gicp_eps (h))) return rc;
+    // (one-to-one correspondences: the claim table reads all-ones between iterations — icp_unique.hip)
+    HIPCHK (h, hipMemsetAsync (icp_unique_claims (p), 0xFF, sizeof (unsigned long long) * B * m, h->stream));
     if ((rc = dalloc (h, &p.ml1, B * 18 * ((p.nb + 127u) / 128u)))) return rc;
     if ((rc = dalloc (h, &p.cst, B * 2))) return rc;
     if ((rc = dalloc (h, &p.st, B))) return rc;
@@ -419,6 +421,7 @@ size_t icp_mem_size (icp_handle h, int mem)
         case ICP_MEM_R: case ICP_MEM_RK: return 36;
         case ICP_MEM_NN: case ICP_MEM_QT: return (size_t) p.m * 16;
         case ICP_MEM_TRIM: return 16;
+        case ICP_MEM_UNIQUE: return 8;
         case ICP_MEM_NORMALS_F: case ICP_MEM_COLOR_GRAD_F: case ICP_MEM_NORMALS_M: return (size_t) p.m * 16;
         case ICP_MEM_PLANE_SYSTEM: return ICP_P2PL_SYS * sizeof (double);
         default: return 0;
@@ -451,6 +454,7 @@ static int mem_ptr (icp_context *h, uint32_t b, int mem, const void **src)
         case ICP_MEM_QT: *src = p.PM + (size_t) b * p.m; break;
         case ICP_MEM_W: *src = reinterpret_cast<const float *> (p.PF + (size_t) b * p.m) + 3; break;
         case ICP_MEM_TRIM: *src = icp_trim_area (p) + 4u * b; break;
+        case ICP_MEM_UNIQUE: *src = icp_unique_area (p) + 4u * b + 1u; break;
         case ICP_MEM_NORMALS_F: *src = icp_normals_f (p) + (size_t) b * p.m; break;
         case ICP_MEM_COLOR_GRAD_F: *src = icp_color_grad_f (p) + (size_t) b * p.m; break;
         case ICP_MEM_NORMALS_M: *src = icp_normals_m (p) + (size_t) b * p.m; break;
@@ -719,7 +723,7 @@ int icp_set_rejection (icp_handle h, int flags, float max_dist) try
     if (!h) return fail (h, ICP_EINVAL, "icp_set_rejection: null handle");
     { int rc = outputs_before_change (h); if (rc) return rc; }
     const bool dist = max_dist > 0.f && !std::isinf (max_dist);
-    h->p.reject = (uint32_t) flags | (dist ? ICP_REJECT_DIST_ON : 0u) | (h->p.reject & (ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK));
+    h->p.reject = (uint32_t) flags | (dist ? ICP_REJECT_DIST_ON : 0u) | (h->p.reject & (ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON));
     h->p.reject_max_dist = max_dist;
     h->p.reject_d2 = dist ? (float) ((double) max_dist * (double) max_dist) : 0.f;     // (the product of two floats is exact in double)
     ++h->param_gen; return ICP_OK;
@@ -729,7 +733,7 @@ int icp_get_rejection (icp_handle h, int *flags, float *max_dist) try
 {
     api_guard guard_ (h);
     if (!h) return ICP_EINVAL;
-    if (flags) *flags = (int) (h->p.reject & ~(ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK));
+    if (flags) *flags = (int) (h->p.reject & ~(ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON));
     if (max_dist) *max_dist = h->p.reject_max_dist;
     return ICP_OK;
 }
@@ -765,6 +769,37 @@ int icp_get_trimming (icp_handle h, float *keep_fraction) try
     api_guard guard_ (h);
     if (!h || !keep_fraction) return ICP_EINVAL;
     *keep_fraction = icp_trimming (h->p) ? h->p.trim_keep : 1.f;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+// one-to-one correspondences (include/icp_amd.h, icp_unique.hip).  On <-> off changes which kernels run — the REJ search, claim and
+// resolve, on point-to-point the apply pass, no chained form —: the route of icp_set_trimming (graphs captured anew).
+int icp_set_unique (icp_handle h, int on) try
+{
+    static_assert (!(ICP_REJECT_UNIQUE_ON & (ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_INVALID)), "the rule's bit is its own");
+    api_guard guard_ (h);
+    if (on != 0 && on != 1) return fail (h, ICP_EINVAL, "icp_set_unique: on must be 0 or 1");
+    if (!h) return fail (h, ICP_EINVAL, "icp_set_unique: null handle");
+    { int rc = outputs_before_change (h); if (rc) return rc; }
+    if ((on != 0) == icp_unique (h->p)) return ICP_OK;
+    if (on) h->p.reject |= ICP_REJECT_UNIQUE_ON;
+    else {
+        h->p.reject &= ~ICP_REJECT_UNIQUE_ON;
+        if (h->inited) {                                                 // ICP_MEM_UNIQUE reads zeros while the rule is off
+            int rc = set_device (h); if (rc) return rc;
+            if ((rc = run_close_all (h))) return rc;
+            HIPCHK (h, hipMemsetAsync (icp_unique_area (h->p), 0, sizeof (uint32_t) * 4u * h->p.batch, h->stream));
+        }
+    }
+    drop_graphs (h);
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+int icp_get_unique (icp_handle h, int *on) try
+{
+    api_guard guard_ (h);
+    if (!h || !on) return ICP_EINVAL;
+    *on = icp_unique (h->p) ? 1 : 0;
     return ICP_OK;
 }
 ICP_CATCH_ALL
@@ -1223,6 +1258,7 @@ int icp_launches_per_iteration (icp_handle h, uint32_t *n) try
     *n = form != ICP_FORM_SEPARATE ? 1u : h->p.fused ? ((h->p.nb + 127u) / 128u > ICP_L1_MIN_GROUPS ? 3u : 2u) : 4u;
     if (icp_apply_pass (h->p)) *n += icp_trim_launches (h->p);        // (trimming's select: one or three launches; apply: one)
     if (icp_p2pl (h->p)) *n = 1u + (icp_apply_pass (h->p) ? icp_trim_launches (h->p) : 0u) + ICP_P2PL_LAUNCHES;   // (search, moments, finalize)
+    if (icp_unique (h->p)) *n += ICP_UNIQUE_LAUNCHES;                 // (one-to-one correspondences: claim and resolve, behind the search)
     return ICP_OK;
 }
 ICP_CATCH_ALL

@@ -124,11 +124,14 @@ struct icp_params {
 #define ICP_REJECT_TRIM_ON 0x40000000u   // icp_params::reject: trimming is on (the REJ kernels, plus select and apply: icp_launch_trim)
 #define ICP_REJECT_ROBUST_SHIFT 28u
 #define ICP_REJECT_ROBUST_MASK 0x30000000u   // icp_params::reject: the robust loss (icp_set_robust_loss): ICP_ROBUST_* << 28, 0: off
+#define ICP_REJECT_UNIQUE_ON 0x08000000u   // icp_params::reject: one-to-one correspondences are on (icp_set_unique: the REJ kernels, plus claim and resolve: icp_launch_unique)
 static_assert (sizeof (icp_params) == 480, "icp_params grew: the hidden kernel arguments of every kernel would move");
 
 // rejection on: the sum-W formulas in every mode, and a step of nothing accepted (sum W == 0) is the identity
 static __host__ __device__ __forceinline__ bool icp_rejecting (const icp_params &p) { return p.reject != 0u; }
 static __host__ __device__ __forceinline__ bool icp_trimming (const icp_params &p) { return (p.reject & ICP_REJECT_TRIM_ON) != 0u; }
+// one-to-one correspondences (icp_unique.hip): of the candidates that share a fixed point only the closest keeps its weight
+static __host__ __device__ __forceinline__ bool icp_unique (const icp_params &p) { return (p.reject & ICP_REJECT_UNIQUE_ON) != 0u; }
 // the robust loss's kind (ICP_ROBUST_HUBER 1, CAUCHY 2, TUKEY 3; 0: off).  Its scale k is a device word (icp_robust_scale).
 static __host__ __device__ __forceinline__ uint32_t icp_robust (const icp_params &p) { return (p.reject & ICP_REJECT_ROBUST_MASK) >> ICP_REJECT_ROBUST_SHIFT; }
 // The robust loss's IRLS weight omega (u) of u = s^2 / k^2 (include/icp_amd.h), in double, each expression in the order written; NaN: 0
@@ -140,10 +143,12 @@ static __host__ __device__ __forceinline__ double icp_robust_omega (uint32_t los
     return u < 1.0 ? (1.0 - u) * (1.0 - u) : 0.0;                        // Tukey
 }
 // An apply pass (k_trim_apply) rewrites the weights behind the search: trimming, or a robust loss on point-to-point (the plane metrics
-// weigh their pairs in k_plane_moments).  The route of every such iteration: per-query outputs stored every time, no chained form.
+// weigh their pairs in k_plane_moments).  One-to-one correspondences on point-to-point need it too: the resolve pass has zeroed weights
+// behind the search's partials, and the pass writes the partials again (the plane metrics read w in k_plane_moments: no pass for them).
+// The route of every such iteration: per-query outputs stored every time, no chained form.
 static __host__ __device__ __forceinline__ bool icp_apply_pass (const icp_params &p)
 {
-    return icp_trimming (p) || (icp_robust (p) != 0u && p.metric == 0u);
+    return icp_trimming (p) || ((icp_robust (p) != 0u || icp_unique (p)) && p.metric == 0u);
 }
 
 // Trimming's buffers (icp_trim.hip) are uint32 words: [batch][4] the result of the last iteration (t bits, n, K, accepted: ICP_MEM_TRIM),
@@ -180,6 +185,7 @@ struct icp_mom_layout {
     size_t kappa;                // the float word of kappa (icp_color_kappa)
     size_t robust;               // the float word of the robust loss's scale k (icp_robust_scale)
     size_t gicp;                 // the float word of plane-to-plane's epsilon (icp_gicp_eps)
+    size_t uniq;                 // one-to-one correspondences: [batch][4] uint32 result words (icp_unique_area), [batch][m] uint64 claim table (icp_unique_claims)
     size_t total;
 };
 static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (uint32_t batch, uint32_t m, uint32_t nb)
@@ -192,7 +198,8 @@ static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (uint32_t bat
     l.kappa = l.part + B * ICP_P2PL_TERMS * icp_p2pl_nblk (m);
     l.robust = l.kappa + 1u;
     l.gicp = l.robust + 1u;
-    l.total = l.gicp + 1u;
+    l.uniq = l.gicp + 1u;
+    l.total = l.uniq + 2u * B + B * m;
     return l;
 }
 static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (const icp_params &p) { return icp_mom_layout_of (p.batch, p.m, p.nb); }
@@ -203,6 +210,14 @@ static inline float *icp_color_kappa (const icp_params &p) { return reinterpret_
 // (also on the device: the robust kernels find the word from their icp_params, the loss-off kernels take no argument for it)
 static __host__ __device__ inline float *icp_robust_scale (const icp_params &p) { return reinterpret_cast<float *> (p.mom + icp_mom_layout_of (p).robust); }
 static __host__ __device__ inline float *icp_gicp_eps (const icp_params &p) { return reinterpret_cast<float *> (p.mom + icp_mom_layout_of (p).gicp); }
+// One-to-one correspondences (icp_unique.hip).  The result words of a registration are laid out as k_trim_apply reads trimming's:
+// (0xFFFFFFFE, n, winners, winners) — a threshold above every candidate's key and a K that is 0 only when nothing is left —, so that
+// the apply pass behind the resolve pass is trimming's own kernel pointed at these words; ICP_MEM_UNIQUE is words 1 and 2.
+static inline uint32_t *icp_unique_area (const icp_params &p) { return reinterpret_cast<uint32_t *> (p.mom + icp_mom_layout_of (p).uniq); }
+static inline unsigned long long *icp_unique_claims (const icp_params &p)
+{
+    return reinterpret_cast<unsigned long long *> (p.mom + icp_mom_layout_of (p).uniq + 2u * (size_t) p.batch);
+}
 
 // The XP allocation of one RBC set, offsets in floats: [batch][m][8] the permuted database, then [batch][m] float4 NORMALS_F and
 // [batch][m] float4 COLOR_GRAD_F ([gx gy gz C] per fixed point).  The normals and gradients belong to the fixed frame as the RBC does,
@@ -310,6 +325,8 @@ void icp_launch_search_rej (const icp_params &p, hipStream_t s);            // i
 void icp_launch_chain_one_rej (const icp_params &p, hipStream_t s, uint32_t j, bool fresh, bool emit);
 void icp_launch_trim (const icp_params &p, hipStream_t s);                   // icp_trim.hip: k_trim_select (one or three launches) + k_trim_apply
 uint32_t icp_trim_launches (const icp_params &p);                             // how many that is
+void icp_launch_unique (const icp_params &p, hipStream_t s);                 // icp_unique.hip: k_unique_claim + k_unique_resolve
+#define ICP_UNIQUE_LAUNCHES 2u                                                // launches of icp_launch_unique
 void icp_launch_robust_apply (const icp_params &p, hipStream_t s);            // icp_robust.hip: k_trim_apply<fused, true> (a point-to-point robust loss)
 void icp_launch_plane_moments_robust (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);   // icp_robust.hip: k_plane_moments<colored, true>
 void icp_launch_p2pl_solve (const icp_params &p, hipStream_t s);             // icp_p2pl.hip: k_plane_moments<colored?> + k_p2pl_finalize

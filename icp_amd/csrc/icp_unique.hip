@@ -1,0 +1,100 @@
+// icp_unique.hip — one-to-one correspondences (icp_set_unique, include/icp_amd.h): of the candidate pairs that share a fixed point only
+// the closest keeps its weight; every other gets the weight +0 and is then exactly a rejected pair.
+//
+// An iteration with the rule on is: the REJ search (icp_search_rej.hip), which stores its per-query outputs; k_unique_claim, in which
+// every candidate pair i takes an unsigned 64-bit minimum of its key (bits (geo_i) << 32 | i) into claim[b][id_i]; k_unique_resolve, in
+// which pair i is the winner of its fixed point when claim[b][id_i] == key_i, a loser's weight becomes +0 in PF.w, and the
+// registration's (candidates, winners) are counted; then trimming's selection (when trimming is on too: its candidates are the winners)
+// and the apply pass (icp_trim_apply.inc), which writes the search blocks' partials again from PF / PM — point-to-point only: the plane
+// metrics read w in k_plane_moments —; then the unchanged tail of the iteration.  None of the existing kernels carries any of this code.
+//
+// Determinism: the winner is the minimum of integers that are all different (the query index is part of the key), and an integer minimum
+// does not depend on the order of arrival.  Nothing else decides a value: the counts are integer sums.
+//
+// The claim table is ONE table of m words per registration that reads all-ones between iterations.  A slot that was claimed has exactly
+// one winner, and the winner — having compared — stores all-ones back into its slot in the resolve pass; a loser of that slot that reads
+// it afterwards sees all-ones in place of the winner's key, and neither equals its own key (a candidate's geo is finite: its key's high
+// word is below 0x7F800000), so it is a loser either way.  The two passes are launched together (icp_launch_unique) and both leave a
+// registration alone under the same test (p.check && st.done, which only a finalize behind them changes), so a claim pass without its
+// resolve pass does not exist: a converged registration's table is not touched and stays clean, and the first iteration after
+// icp_init (which fills the table with 0xFF), buildRBC, reset_transform or a new graph finds it as the last resolve pass left it.  No
+// memset, no extra launch, no second table.
+//
+// The result words of a registration, [batch][4] uint32 (icp_unique_area): (0xFFFFFFFE, n, winners, 0).  k_unique_claim's first thread
+// resets them, k_unique_resolve's blocks add their counts.  They are laid out as k_trim_apply reads trimming's words (t at 0, K at 2): a
+// threshold that every candidate passes and a K that is 0 only when no pair is left, so the apply pass of the rule alone is trimming's
+// own kernel pointed at these words.  ICP_MEM_UNIQUE is words 1 and 2.
+#include "icp_trim_apply.h"             // (TRIM_NONE, trim_key)
+
+namespace {
+
+constexpr uint32_t UNIQUE_BLOCK = 256u;
+constexpr unsigned long long UNIQUE_FREE = ~0ull;       // a slot nobody has claimed
+
+// the claim key of pair i, and the slot it claims (candidate: key != UNIQUE_FREE)
+__device__ __forceinline__ unsigned long long unique_key (const icp_params &p, uint32_t b, uint32_t i, uint32_t *id)
+{
+    const size_t e = (size_t) b * p.m + i;
+    const uint32_t k = trim_key (p.PF[e], p.PM[e]);
+    *id = p.nn_id[e].id;
+    // (an id is an index into F; a word that is not would be no claim, never a store outside the table)
+    return (k != TRIM_NONE && *id < p.m) ? ((unsigned long long) k << 32) | i : UNIQUE_FREE;
+}
+
+// ------------------------------------------------------------------------------------------
+// k_unique_claim — one thread per pair, grid (ceil (m / 256), batch)
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__ (UNIQUE_BLOCK) void k_unique_claim (icp_params p, unsigned long long *claims, uint32_t *area)
+{
+    const uint32_t b = blockIdx.y, i = blockIdx.x * UNIQUE_BLOCK + threadIdx.x;
+    if (p.check && p.st[b].done) return;                     // (a converged registration: its last iteration's outputs stay)
+    if (i == 0u) { uint32_t *out = area + 4u * b; out[0] = 0xFFFFFFFEu; out[1] = 0u; out[2] = 0u; out[3] = 0u; }
+    if (i >= p.m) return;
+    uint32_t id;
+    const unsigned long long key = unique_key (p, b, i, &id);
+    if (key != UNIQUE_FREE) __hip_atomic_fetch_min (claims + (size_t) b * p.m + id, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ------------------------------------------------------------------------------------------
+// k_unique_resolve — one thread per pair, same grid
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__ (UNIQUE_BLOCK) void k_unique_resolve (icp_params p, unsigned long long *claims, uint32_t *area)
+{
+    __shared__ uint32_t s_n[UNIQUE_BLOCK / 64u], s_win[UNIQUE_BLOCK / 64u];
+    const uint32_t b = blockIdx.y, t = threadIdx.x, i = blockIdx.x * UNIQUE_BLOCK + t;
+    if (p.check && p.st[b].done) return;
+    bool cand = false, win = false;
+    if (i < p.m) {
+        uint32_t id;
+        const unsigned long long key = unique_key (p, b, i, &id);
+        cand = key != UNIQUE_FREE;
+        if (cand) {
+            unsigned long long *slot = claims + (size_t) b * p.m + id;
+            win = __hip_atomic_load (slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == key;
+            if (win) __hip_atomic_store (slot, UNIQUE_FREE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // (clean for the next iteration)
+            else reinterpret_cast<float *> (p.PF + (size_t) b * p.m + i)[3] = 0.f;
+        }
+    }
+    const uint32_t n = (uint32_t) __popcll (__ballot (cand)), w = (uint32_t) __popcll (__ballot (win));
+    if ((t & 63u) == 0u) { s_n[t >> 6] = n; s_win[t >> 6] = w; }
+    __syncthreads ();
+    if (t == 0u) {
+        uint32_t sn = 0u, sw = 0u;
+#pragma unroll
+        for (uint32_t v = 0; v < UNIQUE_BLOCK / 64u; ++v) { sn += s_n[v]; sw += s_win[v]; }
+        uint32_t *out = area + 4u * b;
+        if (sn) __hip_atomic_fetch_add (out + 1, sn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (sw) __hip_atomic_fetch_add (out + 2, sw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+}  // namespace
+
+void icp_launch_unique (const icp_params &p, hipStream_t s)
+{
+    const dim3 grid ((p.m + UNIQUE_BLOCK - 1u) / UNIQUE_BLOCK, p.batch);
+    unsigned long long *claims = icp_unique_claims (p);
+    uint32_t *area = icp_unique_area (p);
+    hipLaunchKernelGGL (k_unique_claim, grid, dim3 (UNIQUE_BLOCK), 0, s, p, claims, area);
+    hipLaunchKernelGGL (k_unique_resolve, grid, dim3 (UNIQUE_BLOCK), 0, s, p, claims, area);
+}

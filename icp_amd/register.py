@@ -13,21 +13,24 @@ from .io import load_pc8d, save_pc8d
 
 def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, angle_threshold=0.001,
                     translation_threshold=0.01, reduce_mode=ReduceMode.FUSED, reject_invalid=False, max_dist=None, trim=1.0,
-                    point_to_plane=None, colored=None, robust=None, plane_to_plane=None, symmetric=False):
+                    point_to_plane=None, colored=None, robust=None, plane_to_plane=None, symmetric=False, one_to_one=False):
     """Returns (T[8], k, latency_ms, transformed moving cloud).  reject_invalid / max_dist: correspondence rejection
     (ICPStep.set_rejection), trim: the fraction of pairs trimmed ICP keeps (ICPStep.set_trimming; 1.0: off), point_to_plane: mu of
     point-to-plane ICP with the fixed frame's normals from its 128 x 128 landmark grid (ICPStep.set_error_metric; None: off),
     colored: kappa of colored ICP, with grid normals and intensity gradients and mu = point_to_plane or 0 (ICPStep.set_color_weight;
     None: off), robust: (RobustLoss kind, scale) of a robust loss (ICPStep.set_robust_loss; None: off), plane_to_plane: epsilon of
     Generalized ICP, with both frames' grid normals and mu = point_to_plane or 0 (ICPStep.set_plane_to_plane; None: off), symmetric:
-    the symmetric objective, with both frames' grid normals and mu = point_to_plane or 0 (ICPStep.set_symmetric); none is the
-    reference's behaviour, all are off by default."""
+    the symmetric objective, with both frames' grid normals and mu = point_to_plane or 0 (ICPStep.set_symmetric), one_to_one: of the
+    pairs that share a fixed point only the closest keeps its weight (ICPStep.set_unique); none is the reference's behaviour, all are
+    off by default."""
     reg = ICP(device)
     reg.init(16384, 256, a, c, max_iterations, angle_threshold, translation_threshold)   # src/ocl_icp_reg.cpp:81-88
     reg.setPowerMode(PowerMode.SQUARED)
     reg.setReduceMode(reduce_mode)
     if reject_invalid or max_dist:
         reg.set_rejection(reject_invalid, max_dist)
+    if one_to_one:
+        reg.set_unique(True)
     if trim != 1.0:
         reg.set_trimming(trim)
     if robust is not None:
@@ -124,6 +127,9 @@ def main(argv=None):
                     help="give pairs farther apart than this geometric distance (mm) weight 0 (not reference behaviour)")
     ap.add_argument("--trim", type=_fraction, default=1.0, metavar="FRACTION",
                     help="trimmed ICP: keep the closest FRACTION in (0, 1] of the pairs in every iteration (not reference behaviour)")
+    ap.add_argument("--one-to-one", action="store_true",
+                    help="one-to-one correspondences: of the pairs that share a fixed point only the closest keeps its weight, "
+                         "before trimming (not reference behaviour)")
     ap.add_argument("--point-to-plane", type=_point_weight, default=None, metavar="MU",
                     help="point-to-plane ICP plus MU (>= 0) times the point-to-point error, normals from the fixed landmark grid "
                          "(not reference behaviour)")
@@ -143,7 +149,7 @@ def main(argv=None):
     T, k, ms, out = register_clouds(load_pc8d(args.fixed), load_pc8d(args.moving), args.device, a=args.alpha,
                                     reject_invalid=args.reject_invalid, max_dist=args.max_dist, trim=args.trim,
                                     point_to_plane=args.point_to_plane, colored=args.colored, robust=args.robust,
-                                    plane_to_plane=args.plane_to_plane, symmetric=args.symmetric)
+                                    plane_to_plane=args.plane_to_plane, symmetric=args.symmetric, one_to_one=args.one_to_one)
     q, t, s = T[:4], T[4:7], T[7]
     sinth_2 = float(np.linalg.norm(q[:3]))
     angle = 180.0 / math.pi * 2 * math.atan2(sinth_2, float(q[3]))

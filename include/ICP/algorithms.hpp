@@ -619,6 +619,12 @@ namespace ICP
         void setTrimming (float keep_fraction) { check (icp_set_trimming (h, keep_fraction)); }
         float getTrimming () { float f = 1.f; check (icp_get_trimming (h, &f)); return f; }
 
+        /*! \brief One-to-one correspondences (icp_set_unique, include/icp_amd.h; not in the reference, off by default): of the pairs
+         *         that share a fixed point only the closest keeps its weight, the others get weight 0.  It acts after rejection and
+         *         before trimming and the robust loss. */
+        void setUnique (bool on) { check (icp_set_unique (h, on ? 1 : 0)); }
+        bool getUnique () { int on = 0; check (icp_get_unique (h, &on)); return on != 0; }
+
         /*! \brief Robust loss (icp_set_robust_loss, include/icp_amd.h; not in the reference, off by default): every pair's weight is
          *         multiplied by the loss's IRLS weight of its own residual, for every error metric.  ICP_ROBUST_NONE: off. */
         void setRobustLoss (int loss, float scale = 0.f) { check (icp_set_robust_loss (h, loss, scale)); }

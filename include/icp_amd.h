@@ -90,6 +90,7 @@ typedef enum {
     ICP_MEM_PLANE_SYSTEM = 22, /* out double[28] point-to-plane: A's upper triangle (21), b (6), status (0 while off) */
     ICP_MEM_COLOR_GRAD_F = 23, /* io m x float4  colored ICP: intensity gradients of the fixed landmarks [gx gy gz C] */
     ICP_MEM_NORMALS_M = 24,    /* io m x float4  normals of the moving landmarks [nx ny nz 0], indexed like M (plane-to-plane, symmetric) */
+    ICP_MEM_UNIQUE = 25,       /* out uint32[2]   one-to-one correspondences, last iteration: candidates n, winners (0 when off) */
     ICP_MEM_COUNT_
 } icp_mem;
 
@@ -269,6 +270,39 @@ int icp_get_rejection (icp_handle h, int *flags, float *max_dist);
  * batched and tracked registrations and survives icp_init.  ICP_EINVAL: keep_fraction NaN, <= 0 or > 1. */
 int icp_set_trimming (icp_handle h, float keep_fraction);
 int icp_get_trimming (icp_handle h, float *keep_fraction);
+
+/* One-to-one correspondences (PCL: CorrespondenceRejectorOneToOne; not reference behaviour): the search gives every moving point a
+ * fixed point, and nothing stops many moving points from sharing one.  With the rule on, of the pairs that share a fixed point only
+ * the closest keeps its weight.  The rule:
+ *   - on is 0 or 1.  0 is the default and means off: the same kernels, launches, graphs and bits as without it.
+ *   - Candidates are the pairs that survive icp_set_rejection's rules and have a weight != 0, and whose geo is finite.  geo is the
+ *     quantity the rejection rule defines: (ex - f0)^2 + (ey - f1)^2 + (ez - f2)^2 in fp32, summed in that order, with no contraction.
+ *   - For a fixed index j, take the candidates i with ICP_MEM_NN_ID[i].id == j.  The winner is the one with the smallest 64-bit key
+ *     ((uint64_t) bits (geo_i) << 32) | i: the closest pair wins, a tie goes to the lowest query index.  geo is never negative, so its
+ *     float bits order as the values do.
+ *   - Every other candidate of j behaves exactly like a rejected pair: its correspondence is kept (NN_ID, RID and the NN / QT xyz stay
+ *     as they are), its weight is +0 (written to the W and NN outputs), and its moment, mean and S terms — for a plane metric its
+ *     plane-system terms — are exact zeros.  A pair that is no candidate neither claims a fixed point nor changes.  As with rejection,
+ *     REGULAR mode uses the sum-W formulas with w in {0, 1}.
+ *   - No winner at all: the sum W == 0 identity step (T unchanged, ICP::run stops).
+ *   - Each registration of a batched handle (icp_init_batched) resolves its own claims.
+ * The rule acts after icp_set_rejection's rules and before trimming and the robust loss: trimming's candidates, and its n, are the
+ * pairs this rule leaves (with both on, ICP_MEM_TRIM's n equals the winner count).  The search is untouched: at the same T the ids,
+ * distances and RID are bit-identical to a run with the rule off.  The winner is an integer minimum, so the result does not depend on
+ * the order in which the device gets to the pairs.
+ * ICP_MEM_UNIQUE holds (n, winners) of the last iteration per registration; zeros while the rule is off.  With the rule on the
+ * per-query outputs are stored by every iteration, and an iteration is the separate form (icp_run_form is ICP_FORM_SEPARATE, there is
+ * no chained launch).  icp_launches_per_iteration counts what the rule adds behind the search:
+ *   - point-to-point: 3 launches — the claim pass, the resolve pass, and the pass that writes the search's partials again from the
+ *     weights (the apply pass of trimming and of a point-to-point robust loss; with either of them on it runs anyway, and the rule
+ *     adds 2);
+ *   - the plane metrics (point-to-plane, colored, plane-to-plane, symmetric): 2 launches — the claim pass and the resolve pass; their
+ *     moments read the weights themselves.
+ * Turning the rule on or off captures the graphs anew (as icp_set_trimming does).  The setting applies to single, batched and tracked
+ * registrations, to every error metric, both reduce modes and both rotation solvers, and survives icp_init.  icp_profile_run counts
+ * its passes into the search stage.  ICP_EINVAL: on outside {0, 1}. */
+int icp_set_unique (icp_handle h, int on);
+int icp_get_unique (icp_handle h, int *on);
 
 /* Point-to-plane ICP with a share of point-to-point (not reference behaviour; off by default).  The rule:
  *   - metric is ICP_METRIC_POINT_TO_POINT (the default: the same kernels, launches, graphs and bits as without it) or
@@ -668,6 +702,7 @@ int icp_batch_init (icp_batch_handle b, uint32_t registrations, uint32_t m, uint
 int icp_batch_set_modes (icp_batch_handle b, int reduce_mode, int power_mode);
 int icp_batch_set_rejection (icp_batch_handle b, int flags, float max_dist);                /* icp_set_rejection on every slot */
 int icp_batch_set_trimming (icp_batch_handle b, float keep_fraction);                        /* icp_set_trimming on every slot */
+int icp_batch_set_unique (icp_batch_handle b, int on);                                       /* icp_set_unique on every slot */
 int icp_batch_set_robust_loss (icp_batch_handle b, int loss, float scale);                   /* icp_set_robust_loss on every slot */
 int icp_batch_set_error_metric (icp_batch_handle b, int metric, float point_weight);         /* icp_set_error_metric on every slot */
 int icp_batch_set_normals (icp_batch_handle b, int source, uint32_t grid_width);             /* icp_set_normals on every slot */

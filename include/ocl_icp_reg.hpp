@@ -75,6 +75,9 @@ public:
     /*! \brief Trimmed ICP of the registration (ICPStep::setTrimming; not in the reference's demo, off by default). */
     void setTrimming (float keep_fraction) { reg.setTrimming (keep_fraction); }
     float getTrimming () { return reg.getTrimming (); }
+    /*! \brief One-to-one correspondences of the registration (ICPStep::setUnique; not in the reference's demo, off by default). */
+    void setUnique (bool on) { reg.setUnique (on); }
+    bool getUnique () { return reg.getUnique (); }
     /*! \brief Robust loss of the registration (ICPStep::setRobustLoss; not in the reference's demo, off by default). */
     void setRobustLoss (int loss, float scale = 0.f) { reg.setRobustLoss (loss, scale); }
     void setRobustLoss (const icp::RobustLoss &r) { reg.setRobustLoss (r); }
