@@ -5,10 +5,10 @@
 // point-to-point kernels carry none of this code.  Built with -ffp-contract=off like every other translation unit: each expression
 // below is evaluated exactly in the order it is written; tests/gicp_ref.py restates them.
 //
-// The 27 terms of pair i in double, w = PF.w, P = PM.xyz, Q = PF.xyz, N_Q = NORMALS_F[NN_ID.id], N_M = NORMALS_M[i] (a non-finite
-// normal counts as zero), R = p.st[b].R (the cumulative rotation the search of this iteration used), eps = *icp_gicp_eps (p), all
-// converted from float first:
-//   N_P = R N_M: (R_a0 nx + R_a1 ny) + R_a2 nz
+// What is this kernel's own, per pair in double (icp_plane_moments.h states the terms, G, g, the loss and the tree), N_Q =
+// NORMALS_F[NN_ID.id], N_M = NORMALS_M[i], R = p.st[b].R (the cumulative rotation the search of this iteration used), eps =
+// *icp_gicp_eps (p):
+//   N_P = R N_M (plane_rot_normal)
 //   cov (n): nn = (nx nx + ny ny) + nz nz;  nn > 0 and finite: k = (1.0 - eps) / nn, C_ab = delta_ab - k (n_a n_b);  else C = I
 //   S = C_Q + C_P (s00 s01 s02 s11 s12 s22);  cofactors c00 = s11 s22 - s12 s12, c01 = s02 s12 - s01 s22, c02 = s01 s12 - s02 s11,
 //   c11 = s00 s22 - s02 s02, c12 = s01 s02 - s00 s12, c22 = s00 s11 - s01 s01;  det = (s00 c00 + s01 c01) + s02 c02;  M_ab = c_ab / det;
@@ -17,12 +17,9 @@
 //   of h's structural zeros and ones dropped:
 //     u_0r = M_r1 (-pz) + M_r2 py,  u_1r = M_r0 pz + M_r2 (-px),  u_2r = M_r0 (-py) + M_r1 px,  u_(3+c)r = M_rc
 //     h_0 . u_b = (-pz) u_b1 + py u_b2,  h_1 . u_b = pz u_b0 + (-px) u_b2,  h_2 . u_b = (-py) u_b0 + px u_b1,  h_(3+c) . u_b = u_bc
-//   d = Q - P,  G and g as in icp_plane_moments.inc
-//   term (a, b), a <= b, row-major:  w (h_a . u_b + mu G_ab)        term 21 + a:  w (((u_a0 dx + u_a1 dy) + u_a2 dz) + mu g_a)
-// ROBUST: u_d = M d ((M_r0 dx + M_r1 dy) + M_r2 dz), sG2 = ((u_d0 dx + u_d1 dy) + u_d2 dz) + mu ((dx dx + dy dy) + dz dz),
-// wG = omega (sG2 / k2); the terms are w (wG (..)), wG == 0 selecting an exact zero.  w == 0 selects exact zeros for the pair.
-// Then the halving tree over the block's ICP_P2PL_BLOCK pairs, exactly k_plane_moments'.
-#include "icp_kernels.h"
+//   the products: q_t = h_a . u_b (a <= b, row-major),  q_(21 + a) = (u_a0 dx + u_a1 dy) + u_a2 dz;   G and g about A = P with B = Q
+// ROBUST: u_d = M d ((M_r0 dx + M_r1 dy) + M_r2 dz), sG2 = ((u_d0 dx + u_d1 dy) + u_d2 dz) + mu ((dx dx + dy dy) + dz dz).
+#include "icp_plane_moments.h"
 
 namespace {
 
@@ -60,105 +57,51 @@ __global__ __launch_bounds__ (256) void k_gicp_moments (icp_params p, const floa
     double v[ICP_P2PL_TERMS];
 #pragma unroll
     for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) v[t] = 0.0;
-    if (i < p.m) {
-        if (f.w != 0.f) {
-            float4 nf = id < p.m ? nrm[o + id] : make_float4 (0.f, 0.f, 0.f, 0.f), nm = nmf;
-            if (!(isfinite (nf.x) && isfinite (nf.y) && isfinite (nf.z))) nf = make_float4 (0.f, 0.f, 0.f, 0.f);
-            if (!(isfinite (nm.x) && isfinite (nm.y) && isfinite (nm.z))) nm = make_float4 (0.f, 0.f, 0.f, 0.f);
-            const double w = (double) f.w, mu = (double) p.p2pl_mu, eps = (double) epsf;
-            const double px = (double) q.x, py = (double) q.y, pz = (double) q.z;
-            const double qx = (double) f.x, qy = (double) f.y, qz = (double) f.z;
-            const double mx = (double) nm.x, my = (double) nm.y, mz = (double) nm.z;
-            double CQ[6], CP[6];
-            gicp_cov ((double) nf.x, (double) nf.y, (double) nf.z, eps, CQ);
-            gicp_cov (((double) Rf[0] * mx + (double) Rf[1] * my) + (double) Rf[2] * mz,
-                      ((double) Rf[3] * mx + (double) Rf[4] * my) + (double) Rf[5] * mz,
-                      ((double) Rf[6] * mx + (double) Rf[7] * my) + (double) Rf[8] * mz, eps, CP);
-            const double s00 = CQ[0] + CP[0], s01 = CQ[1] + CP[1], s02 = CQ[2] + CP[2], s11 = CQ[3] + CP[3], s12 = CQ[4] + CP[4], s22 = CQ[5] + CP[5];
-            const double c00 = s11 * s22 - s12 * s12, c01 = s02 * s12 - s01 * s22, c02 = s01 * s12 - s02 * s11;
-            const double c11 = s00 * s22 - s02 * s02, c12 = s01 * s02 - s00 * s12, c22 = s00 * s11 - s01 * s01;
-            const double det = (s00 * c00 + s01 * c01) + s02 * c02;
-            if (det > 0.0 && isfinite (det)) {
-                // M, symmetric, by rows
-                const double M[3][3] = { { c00 / det, c01 / det, c02 / det }, { c01 / det, c11 / det, c12 / det }, { c02 / det, c12 / det, c22 / det } };
-                const double npx = -px, npy = -py, npz = -pz;
-                double u[6][3];
+    if (i < p.m && f.w != 0.f) {
+        const float4 nf = plane_finite_or_zero (id < p.m ? nrm[o + id] : make_float4 (0.f, 0.f, 0.f, 0.f)), nm = plane_finite_or_zero (nmf);
+        const double w = (double) f.w, mu = (double) p.p2pl_mu, eps = (double) epsf;
+        const double px = (double) q.x, py = (double) q.y, pz = (double) q.z;
+        const double qx = (double) f.x, qy = (double) f.y, qz = (double) f.z;
+        double np[3], CQ[6], CP[6];
+        plane_rot_normal (Rf, nm, np);
+        gicp_cov ((double) nf.x, (double) nf.y, (double) nf.z, eps, CQ);
+        gicp_cov (np[0], np[1], np[2], eps, CP);
+        const double s00 = CQ[0] + CP[0], s01 = CQ[1] + CP[1], s02 = CQ[2] + CP[2], s11 = CQ[3] + CP[3], s12 = CQ[4] + CP[4], s22 = CQ[5] + CP[5];
+        const double c00 = s11 * s22 - s12 * s12, c01 = s02 * s12 - s01 * s22, c02 = s01 * s12 - s02 * s11;
+        const double c11 = s00 * s22 - s02 * s02, c12 = s01 * s02 - s00 * s12, c22 = s00 * s11 - s01 * s01;
+        const double det = (s00 * c00 + s01 * c01) + s02 * c02;
+        if (det > 0.0 && isfinite (det)) {
+            // M, symmetric, by rows
+            const double M[3][3] = { { c00 / det, c01 / det, c02 / det }, { c01 / det, c11 / det, c12 / det }, { c02 / det, c12 / det, c22 / det } };
+            const double npx = -px, npy = -py, npz = -pz;
+            double u[6][3];
 #pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    u[0][r] = M[r][1] * npz + M[r][2] * py;
-                    u[1][r] = M[r][0] * pz + M[r][2] * npx;
-                    u[2][r] = M[r][0] * npy + M[r][1] * px;
-                    u[3][r] = M[r][0]; u[4][r] = M[r][1]; u[5][r] = M[r][2];
-                }
-                const double dx = qx - px, dy = qy - py, dz = qz - pz;
-                const double pp = (px * px + py * py) + pz * pz;
-                const double G[21] = { pp - px * px, -(px * py), -(px * pz), 0.0, -pz, py,
-                                       pp - py * py, -(py * pz), pz, 0.0, -px,
-                                       pp - pz * pz, -py, px, 0.0,
-                                       1.0, 0.0, 0.0,
-                                       1.0, 0.0,
-                                       1.0 };
-                const double g[6] = { py * qz - pz * qy, pz * qx - px * qz, px * qy - py * qx, dx, dy, dz };
-                [[maybe_unused]] double wG = 1.0;
-                if constexpr (ROBUST) {
-                    const double k = (double) *icp_robust_scale (p), k2 = k * k;
-                    const double ud0 = (M[0][0] * dx + M[0][1] * dy) + M[0][2] * dz;
-                    const double ud1 = (M[1][0] * dx + M[1][1] * dy) + M[1][2] * dz;
-                    const double ud2 = (M[2][0] * dx + M[2][1] * dy) + M[2][2] * dz;
-                    const double sG2 = ((ud0 * dx + ud1 * dy) + ud2 * dz) + mu * ((dx * dx + dy * dy) + dz * dz);
-                    wG = icp_robust_omega (icp_robust (p), sG2 / k2);
-                }
-                int t = 0;
-#pragma unroll
-                for (int a = 0; a < 6; ++a)
-#pragma unroll
-                    for (int c = a; c < 6; ++c, ++t) {
-                        // h_a . u_c
-                        const double hu = a == 0 ? npz * u[c][1] + py * u[c][2]
-                                        : a == 1 ? pz * u[c][0] + npx * u[c][2]
-                                        : a == 2 ? npy * u[c][0] + px * u[c][1]
-                                        : u[c][a - 3];
-                        const double x = hu + mu * G[t];
-                        if constexpr (ROBUST) v[t] = w * (wG != 0.0 ? wG * x : 0.0);
-                        else v[t] = w * x;
-                    }
-#pragma unroll
-                for (int a = 0; a < 6; ++a) {
-                    const double x = ((u[a][0] * dx + u[a][1] * dy) + u[a][2] * dz) + mu * g[a];
-                    if constexpr (ROBUST) v[21 + a] = w * (wG != 0.0 ? wG * x : 0.0);
-                    else v[21 + a] = w * x;
-                }
+            for (int r = 0; r < 3; ++r) {
+                u[0][r] = M[r][1] * npz + M[r][2] * py;
+                u[1][r] = M[r][0] * pz + M[r][2] * npx;
+                u[2][r] = M[r][0] * npy + M[r][1] * px;
+                u[3][r] = M[r][0]; u[4][r] = M[r][1]; u[5][r] = M[r][2];
             }
+            const double dx = qx - px, dy = qy - py, dz = qz - pz;
+            const plane_share S = plane_point_share (px, py, pz, qx, qy, qz, dx, dy, dz);
+            double wG = 1.0;
+            if constexpr (ROBUST) {
+                const double ud0 = (M[0][0] * dx + M[0][1] * dy) + M[0][2] * dz;
+                const double ud1 = (M[1][0] * dx + M[1][1] * dy) + M[1][2] * dz;
+                const double ud2 = (M[2][0] * dx + M[2][1] * dy) + M[2][2] * dz;
+                wG = plane_loss_of (p).omega (((ud0 * dx + ud1 * dy) + ud2 * dz) + mu * ((dx * dx + dy * dy) + dz * dz));
+            }
+            // h_a . u_c, and u_a . d for the residual's column
+            plane_emit<ROBUST> (v, w, mu, wG, S, [&] (int a, int c) __attribute__ ((always_inline)) {
+                return c == 6 ? (u[a][0] * dx + u[a][1] * dy) + u[a][2] * dz
+                     : a == 0 ? npz * u[c][1] + py * u[c][2]
+                     : a == 1 ? pz * u[c][0] + npx * u[c][2]
+                     : a == 2 ? npy * u[c][0] + px * u[c][1]
+                     : u[c][a - 3];
+            });
         }
     }
-    __shared__ double s[ICP_P2PL_TERMS][128];
-    if (tid >= 128u) {
-#pragma unroll
-        for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) s[t][tid - 128u] = v[t];
-    }
-    __syncthreads ();
-    if (tid < 128u) {
-#pragma unroll
-        for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) v[t] = v[t] + s[t][tid];
-    }
-    __syncthreads ();
-    if (tid >= 64u && tid < 128u) {
-#pragma unroll
-        for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) s[t][tid - 64u] = v[t];
-    }
-    __syncthreads ();
-    if (tid >= 64u) return;
-#pragma unroll
-    for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) {
-        double x = v[t] + s[t][tid];
-#pragma unroll
-        for (int h = 32; h >= 1; h >>= 1) x = x + __shfl_down (x, (unsigned) h, 64);
-        v[t] = x;
-    }
-    if (tid == 0u) {
-#pragma unroll
-        for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) part[((size_t) b * ICP_P2PL_TERMS + t) * nblk + blockIdx.x] = v[t];
-    }
+    plane_block_tree (v, part, nblk, b);
 }
 
 void icp_launch_gicp_moments (const icp_params &p, hipStream_t s, double *part, uint32_t nblk)

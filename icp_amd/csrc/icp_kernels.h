@@ -327,12 +327,12 @@ void icp_launch_trim (const icp_params &p, hipStream_t s);                   // 
 uint32_t icp_trim_launches (const icp_params &p);                             // how many that is
 void icp_launch_unique (const icp_params &p, hipStream_t s);                 // icp_unique.hip: k_unique_claim + k_unique_resolve
 #define ICP_UNIQUE_LAUNCHES 2u                                                // launches of icp_launch_unique
-void icp_launch_robust_apply (const icp_params &p, hipStream_t s);            // icp_robust.hip: k_trim_apply<fused, true> (a point-to-point robust loss)
-void icp_launch_plane_moments_robust (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);   // icp_robust.hip: k_plane_moments<colored, true>
+void icp_launch_robust_apply (const icp_params &p, hipStream_t s);            // icp_robust.hip: k_trim_apply_robust<fused?> (a point-to-point robust loss)
+void icp_launch_plane_moments_robust (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);   // icp_robust.hip: k_plane_moments_robust<colored?>
 void icp_launch_p2pl_solve (const icp_params &p, hipStream_t s);             // icp_p2pl.hip: k_plane_moments<colored?> + k_p2pl_finalize
 void icp_launch_normals_grid (const icp_params &p, hipStream_t s);           // icp_p2pl.hip: k_normals_grid (+ colored: k_color_grad_grid; plane-to-plane, symmetric: + NORMALS_M), behind buildRBC
 void icp_launch_normals_m (const icp_params &p, hipStream_t s, uint32_t b0, uint32_t nb);   // icp_p2pl.hip: k_normals_grid pointed at M, registrations b0 .. b0 + nb - 1
-void icp_launch_gicp_moments (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);          // icp_gicp.hip: k_gicp_moments / k_gicp_moments_robust
+void icp_launch_gicp_moments (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);          // icp_gicp.hip: k_gicp_moments<robust?>
 void icp_launch_sym_moments (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);           // icp_symmetric.hip: k_sym_moments<robust?>
 #define ICP_P2PL_LAUNCHES 2u                                                  // launches of icp_launch_p2pl_solve
 void icp_launch_owner_search_dense (const icp_params &p, hipStream_t s);

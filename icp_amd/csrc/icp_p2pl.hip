@@ -2,7 +2,7 @@
 // icp_set_color_weight; Park, Zhou, Koltun 2017).  include/icp_amd.h states both rules.
 //
 // An iteration with either metric on is: the search stage (icp_launch_search_stage), which stores PF (matched fixed xyz, weight) and PM
-// (transformed moving xyz) every time — rejection and trimming have put their zeros into PF.w already —; k_plane_moments<COLORED> (icp_plane_moments.inc), the
+// (transformed moving xyz) every time — rejection and trimming have put their zeros into PF.w already —; k_plane_moments<COLORED> (icp_plane_moments.h), the
 // 27 terms of the linearised 6 x 6 system per pair in double (colored: plus kappa times a photometric term; a robust loss: each part
 // weighed by the loss's omega of its residual) and their tree over blocks
 // of ICP_P2PL_BLOCK pairs; k_p2pl_finalize, one workgroup per registration: the tree over the block partials, LDL^T in one lane, the
@@ -11,7 +11,7 @@
 // icp_symmetric.hip's, also NORMALS_M from M), and with the colored metric k_color_grad_grid computes COLOR_GRAD_F behind it.  None of the
 // point-to-point kernels carries any of this code; the translation unit is built with -ffp-contract=off like every other, so each
 // expression below is evaluated exactly in the order it is written.
-#include "icp_plane_moments.h"          // (intensity)
+#include "icp_plane_moments.h"          // (plane_moments, intensity)
 
 namespace {
 
@@ -167,9 +167,13 @@ __global__ __launch_bounds__ (256) void k_color_grad_grid (icp_params p, const f
     grad[(size_t) b * p.m + i] = out;
 }
 
-#define ICP_MOMENTS_NAME k_plane_moments
-#define ICP_MOMENTS_ROBUST false
-#include "icp_plane_moments.inc"
+// the 27 terms per pair and their block tree with the loss off (icp_plane_moments.h)
+template <bool COLORED>
+__global__ __launch_bounds__ (256) void k_plane_moments (icp_params p, const float4 *nrm, double *part, uint32_t nblk, const float4 *grad,
+                                                         const float *kappa_word)
+{
+    plane_moments<COLORED, false> (p, nrm, part, nblk, grad, kappa_word);
+}
 
 #define P2PL_LDS 4096u           // doubles of the finalize's tree buffer (nblk <= 4096: m <= 2^20)
 

@@ -14,7 +14,7 @@
 // passes with the keys in registers and the histogram in LDS (grid.y = registration); beyond it every pass is a launch of many
 // workgroups whose LDS histograms are merged by device atomics, and the workgroup that arrives last picks the bin (k_trim_select_pass).
 // Both take the same t: the K-th smallest key is one number.
-#include "icp_trim_apply.h"             // (TRIM_NONE, trim_key)
+#include "icp_trim_apply.h"             // (TRIM_NONE, trim_key, trim_apply)
 
 namespace {
 
@@ -183,9 +183,12 @@ __global__ __launch_bounds__ (256) void k_trim_select_pass (icp_params p, uint32
     }
 }
 
-#define ICP_APPLY_NAME k_trim_apply
-#define ICP_APPLY_ROBUST false
-#include "icp_trim_apply.inc"
+// the apply pass with the loss off (icp_trim_apply.h)
+template <bool FUSED>
+__global__ __launch_bounds__ (64) void k_trim_apply (icp_params p, const uint32_t *area, uint32_t tpr_magic)
+{
+    trim_apply<FUSED, false> (p, area, tpr_magic);
+}
 
 }  // namespace
 

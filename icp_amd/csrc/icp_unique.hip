@@ -5,7 +5,7 @@
 // every candidate pair i takes an unsigned 64-bit minimum of its key (bits (geo_i) << 32 | i) into claim[b][id_i]; k_unique_resolve, in
 // which pair i is the winner of its fixed point when claim[b][id_i] == key_i, a loser's weight becomes +0 in PF.w, and the
 // registration's (candidates, winners) are counted; then trimming's selection (when trimming is on too: its candidates are the winners)
-// and the apply pass (icp_trim_apply.inc), which writes the search blocks' partials again from PF / PM — point-to-point only: the plane
+// and the apply pass (icp_trim_apply.h), which writes the search blocks' partials again from PF / PM — point-to-point only: the plane
 // metrics read w in k_plane_moments —; then the unchanged tail of the iteration.  None of the existing kernels carries any of this code.
 //
 // Determinism: the winner is the minimum of integers that are all different (the query index is part of the key), and an integer minimum

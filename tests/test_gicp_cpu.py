@@ -24,6 +24,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gicp_ref as gref                                     # noqa: E402
 import p2pl_ref as ref                                      # noqa: E402
+from kernel_resources import kernel_resources               # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
@@ -311,3 +312,12 @@ def test_a_pair_on_two_planes_weighs_the_normal_direction(eps):
     assert eps / 2 <= ratio <= 2 * eps, (ratio, eps)
     assert abs(along_normal - 16.0 / (2 * float(F32(eps)))) <= 1e-4 * along_normal
     assert abs(along_tangent - 16.0 / 2) <= 1e-4 * along_tangent
+
+
+def test_gicp_kernels_have_zero_scratch():
+    """The plane-to-plane moments (loss off, loss on): the unit's complete kernel list, no scratch, no dynamic stack."""
+    res = dict(kernel_resources("icp_amd/csrc/icp_gicp.hip"))
+    names = sorted(res)
+    assert names == ["k_gicp_moments<false>", "k_gicp_moments<true>"], names
+    for n in names:
+        assert res[n]["scratch"] == 0 and res[n]["dynamic_stack"] == "False", (n, res[n])

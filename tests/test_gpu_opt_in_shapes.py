@@ -362,10 +362,14 @@ def test_rejection_dense_layouts(engine, oracle, side, nr, batch, fused):
 # pairs, the dense search layouts (single, batched, masked, several representative tiles), the loss behind trimming's three-pass
 # select, m = 2^20 (k_moment_level1 in front of the finalize); for the plane metrics the clamp ic = min (i, m - 1) with a partly filled
 # last block and the finalize's padded multi-pass tree; and batches whose registrations stop at different iterations (both robust
-# kernels return for a registration that is done).
+# kernels return for a registration that is done).  Plane-to-plane and the symmetric objective take the pair's guard i < m, the clamp,
+# the loss's weight and the block tree from the same header as the kernels above (icp_plane_moments.h): they are taken, loss off and
+# on, to m < 256, to a partly filled last block and to a batch whose registrations stop at different iterations.
 
 import robust_ref as rref                                        # noqa: E402
+import test_gpu_gicp as gicp                                     # noqa: E402
 import test_gpu_robust_loss as rl                                # noqa: E402
+import test_gpu_symmetric as sym                                 # noqa: E402
 
 ROBUST_DENSE = [(256, 256, 1), (128, 64, 3), (256, 1024, 1), (192, 2048, 1)]
 
@@ -551,4 +555,71 @@ def test_robust_p2p_batch3_runs_end_at_different_iterations(engine, side, nr, fu
         assert np.array_equal(g.read(Mem.NN_ID, b)["id"], h.read(Mem.NN_ID)["id"]), b
         h.close()
     assert len(set(ks)) > 1 and min(ks) < 40, ks
+    g.close()
+
+
+# (side, nr): m = 36 and 196, one partly filled block (nblk = 1); 900, nblk = 4 with 132 pairs in the last block
+SHARED_BODY_SHAPES = PLANE_SHAPES[:3]
+GICP_EPS = 1e-3
+
+
+def _two_normals_handle(engine, metric, side, nr, loss, batch=1):
+    """A plane-to-plane ("gicp") or symmetric ("sym") handle, mu = 0.05, with the loss on when one is given; and its step check."""
+    if metric == "gicp":
+        g = gicp.make(engine, side, nr, mu=0.05, eps=GICP_EPS, batch=batch)
+        check = lambda T0, R0, k0, b: gicp.check_last(engine, g, 0.05, GICP_EPS, T0, R0, k0, b, loss, rl.SCALE.get(loss))
+    else:
+        g = sym.make(engine, side, nr, mu=0.05, batch=batch)
+        check = lambda T0, R0, k0, b: sym.check_last(engine, g, 0.05, T0, R0, k0, b, loss, rl.SCALE.get(loss))
+    if loss is not None:
+        g.set_robust_loss(loss, rl.SCALE[loss])
+    return g, check
+
+
+@pytest.mark.parametrize("loss", [None, rref.CAUCHY, rref.TUKEY])
+@pytest.mark.parametrize("side,nr", SHARED_BODY_SHAPES)
+@pytest.mark.parametrize("metric", ["gicp", "sym"])
+def test_two_normals_metrics_below_and_across_a_block(engine, metric, side, nr, loss):
+    """Two steps, each against the metric's restatement (tests/gicp_ref.py, tests/sym_ref.py) fed the engine's own outputs."""
+    F, M = engine.synth_pair(side, seed=0x9A1E + side)
+    g, check = _two_normals_handle(engine, metric, side, nr, loss)
+    gicp.load(engine, g, F, M)
+    g.buildRBC()
+    for _ in range(2):
+        T0, R0, k0 = gicp.before(engine, g)
+        g.step()
+        s = check(T0, R0, k0, 0)
+        assert np.isfinite(s).all()
+        if loss != rref.TUKEY:                                      # (Tukey at these coarse grids may accept nothing: the identity step)
+            assert s[27] == 1.0 and s[:27].any()
+    g.close()
+
+
+@pytest.mark.parametrize("loss", [None, rref.CAUCHY])
+@pytest.mark.parametrize("metric", ["gicp", "sym"])
+def test_two_normals_metrics_run_batch2_at_a_partial_block(engine, metric, loss):
+    """ICP::run on two registrations of 2500 (nblk = 10, 196 pairs in the last block) against single handles: k, T, the system.  The
+    two stop at different iterations by construction, whatever the metric and the loss: registration 0 moves a set onto itself (M = F:
+    every d = Q - P is zero, so the right-hand side b is six exact zeros, x = 0, the step is the identity and the run ends at k = 1),
+    registration 1 starts 4 degrees away and cannot end there.  From iteration 2 on the moments return for registration 0."""
+    side, nr = 50, 4
+    F0 = engine.synth_pair(side, seed=0x7D00)[0]
+    pairs = [(F0, F0.copy()), engine.synth_pair(side, seed=0x7D01, rot_deg=4.0)]
+    g, _ = _two_normals_handle(engine, metric, side, nr, loss, batch=2)
+    for b, (F, M) in enumerate(pairs):
+        gicp.load(engine, g, F, M, b)
+    g.buildRBC()
+    g.run()
+    Mem = engine.Memory
+    ks = []
+    for b, (F, M) in enumerate(pairs):
+        h, _ = _two_normals_handle(engine, metric, side, nr, loss)
+        gicp.load(engine, h, F, M)
+        h.buildRBC()
+        ks.append(h.run())
+        assert g.state(b).k == ks[-1], (b, g.state(b).k, ks)
+        assert_bits(g.read(Mem.T, b), h.read(Mem.T), "T of registration %d" % b)
+        assert_bits(g.read(Mem.PLANE_SYSTEM, b), h.read(Mem.PLANE_SYSTEM), "system of registration %d" % b)
+        h.close()
+    assert ks[0] == 1 and 1 < ks[1] <= 40, ks
     g.close()

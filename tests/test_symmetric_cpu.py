@@ -14,6 +14,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import sym_ref as sref                                      # noqa: E402
 import p2pl_ref as ref                                      # noqa: E402
+from kernel_resources import kernel_resources               # noqa: E402
 import robust_ref                                           # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -385,3 +386,12 @@ def test_zero_normals_give_the_mu_share_and_zero_weights_the_identity_step():
     system, T, Rn, Tk, Rk = sref.step(PF0, PM, ids, NF, NM, mu, T0, R0)
     assert (system == 0).all() and system[27] == 0.0
     assert np.array_equal(T, T0) and np.array_equal(Tk, ref.IDENTITY_TK)
+
+
+def test_sym_kernels_have_zero_scratch():
+    """The symmetric moments (loss off, loss on): the unit's complete kernel list, no scratch, no dynamic stack."""
+    res = dict(kernel_resources("icp_amd/csrc/icp_symmetric.hip"))
+    names = sorted(res)
+    assert names == ["k_sym_moments<false>", "k_sym_moments<true>"], names
+    for n in names:
+        assert res[n]["scratch"] == 0 and res[n]["dynamic_stack"] == "False", (n, res[n])
