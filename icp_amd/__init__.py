@@ -87,7 +87,7 @@ class TransformKind:             # ICPTransformConfig (include/ICP/algorithms.hp
 
 class Memory:                    # icp_mem in include/icp_amd.h
     F, M, T, TK, MEANS, S, NN_ID, W, SUM_W, REPS, RBC_N, RBC_O, RBC_PERM, RBC_OWNER, RBC_XP, RID, R, RK, NN, QT, TRIM, \
-        NORMALS_F, PLANE_SYSTEM, COLOR_GRAD_F, NORMALS_M, UNIQUE = range(26)
+        NORMALS_F, PLANE_SYSTEM, COLOR_GRAD_F, NORMALS_M, UNIQUE, PAIR_FILTER = range(27)
     # reference spellings (ICPStep::Memory, include/ICP/algorithms.hpp:2241-2267)
     D_IN_F, D_IN_M, D_IO_T, H_IO_T = F, M, T, T
 
@@ -160,6 +160,10 @@ def lib():
     sig("icp_get_trimming", i32, vp, C.POINTER(f32))
     sig("icp_set_unique", i32, vp, i32)
     sig("icp_get_unique", i32, vp, C.POINTER(i32))
+    sig("icp_set_normal_rejection", i32, vp, i32, f32)
+    sig("icp_get_normal_rejection", i32, vp, C.POINTER(i32), C.POINTER(f32))
+    sig("icp_set_boundary_rejection", i32, vp, u32)
+    sig("icp_get_boundary_rejection", i32, vp, C.POINTER(u32))
     sig("icp_set_robust_loss", i32, vp, i32, f32)
     sig("icp_get_robust_loss", i32, vp, C.POINTER(i32), C.POINTER(f32))
     sig("icp_set_error_metric", i32, vp, i32, f32)
@@ -198,6 +202,8 @@ def lib():
     sig("icp_batch_set_rejection", i32, vp, i32, f32)
     sig("icp_batch_set_trimming", i32, vp, f32)
     sig("icp_batch_set_unique", i32, vp, i32)
+    sig("icp_batch_set_normal_rejection", i32, vp, i32, f32)
+    sig("icp_batch_set_boundary_rejection", i32, vp, u32)
     sig("icp_batch_set_robust_loss", i32, vp, i32, f32)
     sig("icp_batch_set_error_metric", i32, vp, i32, f32)
     sig("icp_batch_set_normals", i32, vp, i32, u32)
@@ -564,7 +570,7 @@ _MEM_DTYPE = {
     Memory.RID: (np.uint32, None), Memory.R: (np.float32, 3), Memory.RK: (np.float32, 3),
     Memory.NN: (np.float32, 4), Memory.QT: (np.float32, 4), Memory.TRIM: (np.uint32, None),
     Memory.NORMALS_F: (np.float32, 4), Memory.PLANE_SYSTEM: (np.float64, None), Memory.COLOR_GRAD_F: (np.float32, 4),
-    Memory.NORMALS_M: (np.float32, 4), Memory.UNIQUE: (np.uint32, None),
+    Memory.NORMALS_M: (np.float32, 4), Memory.UNIQUE: (np.uint32, None), Memory.PAIR_FILTER: (np.uint32, None),
 }
 
 
@@ -700,6 +706,33 @@ class ICPStep:
         v = C.c_int32()
         self._chk(self._L.icp_get_unique(self._h, C.byref(v)))
         return bool(v.value)
+
+    def set_normal_rejection(self, min_cos=None):
+        """Rejection by normal compatibility (icp_set_normal_rejection; not reference behaviour, off by default): a pair whose
+        fixed normal and rotated moving normal enclose an angle with a cosine below `min_cos` (in [-1, 1]) gets the weight 0; a pair
+        without both normals too.  None: off.  It needs NORMALS_F and NORMALS_M (set_normals), under every metric, and acts before
+        one-to-one correspondences, trimming and the robust loss.  read(Memory.PAIR_FILTER) gives the last iteration's
+        (n, at_boundary, incompatible, accepted)."""
+        on = min_cos is not None
+        self._chk(self._L.icp_set_normal_rejection(self._h, int(on), float(min_cos) if on else 0.0))
+
+    def normal_rejection(self):
+        """The cosine threshold of normal rejection, None while it is off."""
+        on, c = C.c_int32(), C.c_float()
+        self._chk(self._L.icp_get_normal_rejection(self._h, C.byref(on), C.byref(c)))
+        return c.value if on.value else None
+
+    def set_boundary_rejection(self, grid_width=None):
+        """Rejection at the fixed grid's boundary (icp_set_boundary_rejection; not reference behaviour, off by default): F is read as
+        a row-major grid `grid_width` wide, and a pair whose fixed point lies on the grid's rim, is invalid or has an invalid grid
+        neighbour gets the weight 0.  None or 0: off."""
+        self._chk(self._L.icp_set_boundary_rejection(self._h, int(grid_width or 0)))
+
+    def boundary_rejection(self):
+        """The grid width of boundary rejection, None while it is off."""
+        w = C.c_uint32()
+        self._chk(self._L.icp_get_boundary_rejection(self._h, C.byref(w)))
+        return w.value or None
 
     def set_robust_loss(self, loss=RobustLoss.NONE, scale=0.0):
         """Robust loss (icp_set_robust_loss; not reference behaviour, off by default): every pair's weight is multiplied by the
@@ -1121,6 +1154,25 @@ class ICPBatch:
         """Whether one-to-one correspondences were last switched on for this batch."""
         return getattr(self, "_unique", False)
 
+    def set_normal_rejection(self, min_cos=None):
+        """ICPStep.set_normal_rejection on every registration (icp_batch_set_normal_rejection)."""
+        on = min_cos is not None
+        self._chk(self._L.icp_batch_set_normal_rejection(self._b, int(on), float(min_cos) if on else 0.0))
+        self._normal_rejection = float(min_cos) if on else None
+
+    def normal_rejection(self):
+        """The cosine threshold as last set on this batch (None: off)."""
+        return getattr(self, "_normal_rejection", None)
+
+    def set_boundary_rejection(self, grid_width=None):
+        """ICPStep.set_boundary_rejection on every registration (icp_batch_set_boundary_rejection)."""
+        self._chk(self._L.icp_batch_set_boundary_rejection(self._b, int(grid_width or 0)))
+        self._boundary_rejection = int(grid_width or 0) or None
+
+    def boundary_rejection(self):
+        """The grid width as last set on this batch (None: off)."""
+        return getattr(self, "_boundary_rejection", None)
+
     def set_robust_loss(self, loss=RobustLoss.NONE, scale=0.0):
         """ICPStep.set_robust_loss on every registration (icp_batch_set_robust_loss)."""
         self._chk(self._L.icp_batch_set_robust_loss(self._b, int(loss), float(scale)))
@@ -1184,7 +1236,7 @@ class ICPBatch:
     def read(self, i, mem):
         dt, cols = _MEM_DTYPE[mem]
         sizes = {Memory.T: 32, Memory.TK: 32, Memory.MEANS: 32, Memory.S: 44, Memory.NN_ID: self.m * 8, Memory.R: 36, Memory.RK: 36,
-                 Memory.F: self.m * 32, Memory.M: self.m * 32, Memory.W: self.m * 4, Memory.RID: self.m * 4, Memory.TRIM: 16, Memory.UNIQUE: 8,
+                 Memory.F: self.m * 32, Memory.M: self.m * 32, Memory.W: self.m * 4, Memory.RID: self.m * 4, Memory.TRIM: 16, Memory.UNIQUE: 8, Memory.PAIR_FILTER: 16,
                  Memory.NN: self.m * 16, Memory.QT: self.m * 16, Memory.NORMALS_F: self.m * 16, Memory.PLANE_SYSTEM: 28 * 8,
                  Memory.COLOR_GRAD_F: self.m * 16, Memory.NORMALS_M: self.m * 16}
         nbytes = sizes[mem]

@@ -383,6 +383,30 @@ int icp_batch_set_unique (icp_batch_handle b, int on) try
 }
 ICP_CATCH_ALL
 
+int icp_batch_set_normal_rejection (icp_batch_handle b, int on, float min_cos) try
+{
+    if (!b) return ICP_EINVAL;
+    if (on != 0 && on != 1) return bfail (b, ICP_EINVAL, "icp_batch_set_normal_rejection: on must be 0 or 1");
+    if (!(min_cos >= -1.f && min_cos <= 1.f)) return bfail (b, ICP_EINVAL, "icp_batch_set_normal_rejection: min_cos must be in [-1, 1]");
+    for (icp_handle h : b->slots) {
+        int rc = icp_set_normal_rejection (h, on, min_cos);
+        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
+    }
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
+int icp_batch_set_boundary_rejection (icp_batch_handle b, uint32_t grid_width) try
+{
+    if (!b) return ICP_EINVAL;
+    for (icp_handle h : b->slots) {
+        int rc = icp_set_boundary_rejection (h, grid_width);
+        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
+    }
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
 int icp_batch_set_robust_loss (icp_batch_handle b, int loss, float scale) try
 {
     // (the arguments first, as icp_set_robust_loss does: with b == NULL the message is icp_batch_last_error (NULL)'s)

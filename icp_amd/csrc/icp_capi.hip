@@ -205,11 +205,21 @@ static int write_gicp_eps (icp_context *h)
     return ICP_OK;
 }
 
-// plane-to-plane or symmetric with ICP_NORMALS_GRID: the moving normals of registrations b0 .. b0 + nb - 1 follow a new M, in stream order behind its copy
+// the pair filter's settings -> their device words (icp_pair_filter_settings: min_cos, the grid width), in stream order like kappa's
+static int write_pair_filter_settings (icp_context *h)
+{
+    uint32_t bits; std::memcpy (&bits, &h->normal_min_cos, sizeof bits);
+    uint32_t *w = icp_pair_filter_settings (h->p);
+    HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (w), (int) bits, 1, h->stream));
+    HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (w + 1), (int) h->boundary_gw, 1, h->stream));
+    return ICP_OK;
+}
+
+// plane-to-plane, symmetric or normal rejection with ICP_NORMALS_GRID: the moving normals of registrations b0 .. b0 + nb - 1 follow a new M, in stream order behind its copy
 // (a width that does not divide m: nothing — icp_build_rbc refuses the handle anyway)
 static void normals_m_follow (icp_context *h, uint32_t b0, uint32_t nb)
 {
-    if (h->p.gicp && h->p.nrm_grid && h->p.m % h->p.nrm_grid == 0u) icp_launch_normals_m (h->p, h->stream, b0, nb);
+    if (icp_moving_normals (h->p) && h->p.nrm_grid && h->p.m % h->p.nrm_grid == 0u) icp_launch_normals_m (h->p, h->stream, b0, nb);
 }
 
 int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, float a, float c,
@@ -307,6 +317,7 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     if ((rc = write_color_kappa (h))) return rc;
     if ((rc = write_robust_scale (h))) return rc;
     if ((rc = write_gicp_eps (h))) return rc;
+    if ((rc = write_pair_filter_settings (h))) return rc;
     // (one-to-one correspondences: the claim table reads all-ones between iterations — icp_unique.hip)
     HIPCHK (h, hipMemsetAsync (icp_unique_claims (p), 0xFF, sizeof (unsigned long long) * B * m, h->stream));
     if ((rc = dalloc (h, &p.ml1, B * 18 * ((p.nb + 127u) / 128u)))) return rc;
@@ -422,6 +433,7 @@ size_t icp_mem_size (icp_handle h, int mem)
         case ICP_MEM_NN: case ICP_MEM_QT: return (size_t) p.m * 16;
         case ICP_MEM_TRIM: return 16;
         case ICP_MEM_UNIQUE: return 8;
+        case ICP_MEM_PAIR_FILTER: return 16;
         case ICP_MEM_NORMALS_F: case ICP_MEM_COLOR_GRAD_F: case ICP_MEM_NORMALS_M: return (size_t) p.m * 16;
         case ICP_MEM_PLANE_SYSTEM: return ICP_P2PL_SYS * sizeof (double);
         default: return 0;
@@ -455,6 +467,7 @@ static int mem_ptr (icp_context *h, uint32_t b, int mem, const void **src)
         case ICP_MEM_W: *src = reinterpret_cast<const float *> (p.PF + (size_t) b * p.m) + 3; break;
         case ICP_MEM_TRIM: *src = icp_trim_area (p) + 4u * b; break;
         case ICP_MEM_UNIQUE: *src = icp_unique_area (p) + 4u * b + 1u; break;
+        case ICP_MEM_PAIR_FILTER: *src = icp_pair_filter_area (p) + 4u * b; break;
         case ICP_MEM_NORMALS_F: *src = icp_normals_f (p) + (size_t) b * p.m; break;
         case ICP_MEM_COLOR_GRAD_F: *src = icp_color_grad_f (p) + (size_t) b * p.m; break;
         case ICP_MEM_NORMALS_M: *src = icp_normals_m (p) + (size_t) b * p.m; break;
@@ -524,6 +537,8 @@ int icp_build_rbc (icp_handle h) try
     if ((rc = set_device (h))) return rc;
     if (h->p.nrm_grid && h->p.m % h->p.nrm_grid)
         return fail (h, ICP_ESTATE, "icp_build_rbc: ICP_NORMALS_GRID: m is not a multiple of the grid width");
+    if (h->boundary_gw && h->p.m % h->boundary_gw)
+        return fail (h, ICP_ESTATE, "icp_build_rbc: icp_set_boundary_rejection: m is not a multiple of the grid width");
     note_inputs_change (h);
     // The two (latency-bound sizes) to six launches of the construction are enqueued as they are: a graph of so few nodes costs more
     // at its head and tail than it saves between them — same box, back to back, graph against plain launches: A 22.3 -> 13.6 us,
@@ -723,7 +738,7 @@ int icp_set_rejection (icp_handle h, int flags, float max_dist) try
     if (!h) return fail (h, ICP_EINVAL, "icp_set_rejection: null handle");
     { int rc = outputs_before_change (h); if (rc) return rc; }
     const bool dist = max_dist > 0.f && !std::isinf (max_dist);
-    h->p.reject = (uint32_t) flags | (dist ? ICP_REJECT_DIST_ON : 0u) | (h->p.reject & (ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON));
+    h->p.reject = (uint32_t) flags | (dist ? ICP_REJECT_DIST_ON : 0u) | (h->p.reject & (ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON | ICP_REJECT_FILTER_MASK));
     h->p.reject_max_dist = max_dist;
     h->p.reject_d2 = dist ? (float) ((double) max_dist * (double) max_dist) : 0.f;     // (the product of two floats is exact in double)
     ++h->param_gen; return ICP_OK;
@@ -733,7 +748,7 @@ int icp_get_rejection (icp_handle h, int *flags, float *max_dist) try
 {
     api_guard guard_ (h);
     if (!h) return ICP_EINVAL;
-    if (flags) *flags = (int) (h->p.reject & ~(ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON));
+    if (flags) *flags = (int) (h->p.reject & ~(ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON | ICP_REJECT_FILTER_MASK));
     if (max_dist) *max_dist = h->p.reject_max_dist;
     return ICP_OK;
 }
@@ -803,6 +818,79 @@ int icp_get_unique (icp_handle h, int *on) try
     return ICP_OK;
 }
 ICP_CATCH_ALL
+// boundary and normal rejection (include/icp_amd.h, icp_pair_filter.hip).  A rule on <-> off changes which kernels run — the REJ search,
+// k_pair_filter, on point-to-point the apply pass, no chained form —: the route of icp_set_trimming (graphs captured anew; a new width
+// too).  A new min_cos while the normal rule stays on goes to its device word, as kappa does (icp_set_color_weight): no graph is touched.
+static int pair_filter_switched (icp_context *h)
+{
+    if (h->inited) {
+        int rc = set_device (h); if (rc) return rc;
+        if ((rc = run_close_all (h))) return rc;
+        if ((rc = write_pair_filter_settings (h))) return rc;
+        if (!icp_pair_filter (h->p))                                     // ICP_MEM_PAIR_FILTER reads zeros while both rules are off
+            HIPCHK (h, hipMemsetAsync (icp_pair_filter_area (h->p), 0, sizeof (uint32_t) * 8u * h->p.batch, h->stream));
+        HIPCHK (h, hipStreamSynchronize (h->stream));
+    }
+    drop_graphs (h);
+    return ICP_OK;
+}
+int icp_set_normal_rejection (icp_handle h, int on, float min_cos) try
+{
+    static_assert (!(ICP_REJECT_FILTER_MASK & (ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON | ICP_REJECT_INVALID)), "the rules' bits are their own");
+    api_guard guard_ (h);
+    if (on != 0 && on != 1) return fail (h, ICP_EINVAL, "icp_set_normal_rejection: on must be 0 or 1");
+    if (!(min_cos >= -1.f && min_cos <= 1.f)) return fail (h, ICP_EINVAL, "icp_set_normal_rejection: min_cos must be in [-1, 1]");
+    if (!h) return fail (h, ICP_EINVAL, "icp_set_normal_rejection: null handle");
+    { int rc = outputs_before_change (h); if (rc) return rc; }
+    const bool was = (h->p.reject & ICP_REJECT_NORMAL_ON) != 0u;
+    h->normal_min_cos = on ? min_cos : 0.f;
+    if ((on != 0) == was) {
+        if (on && h->inited) {                                           // (a new threshold: the device word alone)
+            int rc = set_device (h); if (rc) return rc;
+            if ((rc = run_close_all (h))) return rc;
+            if ((rc = write_pair_filter_settings (h))) return rc;
+            HIPCHK (h, hipStreamSynchronize (h->stream));
+        }
+        return ICP_OK;
+    }
+    if (on) {
+        // (grid normals: the last buildRBC computed no moving normals — the next run needs a new one, as after a new F)
+        if (!icp_moving_normals (h->p) && h->p.nrm_grid) h->built = false;
+        h->p.reject |= ICP_REJECT_NORMAL_ON;
+    }
+    else h->p.reject &= ~ICP_REJECT_NORMAL_ON;
+    return pair_filter_switched (h);
+}
+ICP_CATCH_ALL
+int icp_get_normal_rejection (icp_handle h, int *on, float *min_cos) try
+{
+    api_guard guard_ (h);
+    if (!h) return ICP_EINVAL;
+    if (on) *on = (h->p.reject & ICP_REJECT_NORMAL_ON) ? 1 : 0;
+    if (min_cos) *min_cos = h->normal_min_cos;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+int icp_set_boundary_rejection (icp_handle h, uint32_t grid_width) try
+{
+    api_guard guard_ (h);
+    if (!h) return fail (h, ICP_EINVAL, "icp_set_boundary_rejection: null handle");
+    if (grid_width && h->inited && h->p.m % grid_width) return fail (h, ICP_ESTATE, "icp_set_boundary_rejection: m is not a multiple of the grid width");
+    { int rc = outputs_before_change (h); if (rc) return rc; }
+    if (grid_width == h->boundary_gw) return ICP_OK;
+    h->boundary_gw = grid_width;
+    if (grid_width) h->p.reject |= ICP_REJECT_BOUNDARY_ON; else h->p.reject &= ~ICP_REJECT_BOUNDARY_ON;
+    return pair_filter_switched (h);
+}
+ICP_CATCH_ALL
+int icp_get_boundary_rejection (icp_handle h, uint32_t *grid_width) try
+{
+    api_guard guard_ (h);
+    if (!h || !grid_width) return ICP_EINVAL;
+    *grid_width = h->boundary_gw;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
 // robust loss (include/icp_amd.h; icp_trim.hip, icp_p2pl.hip).  On <-> off and a new kind change which kernels run — point-to-point: the
 // REJ search and the apply pass, no chained form; the plane metrics: other moments —: the route of icp_set_trimming (graphs captured
 // anew).  A new scale while the loss stays on goes to its device word, as kappa does (icp_set_color_weight): no graph is touched.
@@ -849,7 +937,7 @@ static void moving_normals_word (icp_context *h)
     const uint32_t word = h->gicp_eps > 0.f ? 1u : h->symmetric ? ICP_MOVING_NORMALS_SYM : 0u;
     if (word == h->p.gicp) return;
     // (grid normals: the last buildRBC computed no moving normals — the next run needs a new one, as after a new F)
-    if (!h->p.gicp && h->p.nrm_grid) h->built = false;
+    if (!icp_moving_normals (h->p) && h->p.nrm_grid) h->built = false;
     h->p.gicp = word;
     drop_graphs (h);
 }
@@ -1259,6 +1347,7 @@ int icp_launches_per_iteration (icp_handle h, uint32_t *n) try
     if (icp_apply_pass (h->p)) *n += icp_trim_launches (h->p);        // (trimming's select: one or three launches; apply: one)
     if (icp_p2pl (h->p)) *n = 1u + (icp_apply_pass (h->p) ? icp_trim_launches (h->p) : 0u) + ICP_P2PL_LAUNCHES;   // (search, moments, finalize)
     if (icp_unique (h->p)) *n += ICP_UNIQUE_LAUNCHES;                 // (one-to-one correspondences: claim and resolve, behind the search)
+    if (icp_pair_filter (h->p)) *n += ICP_PAIR_FILTER_LAUNCHES;       // (boundary and normal rejection: one pass behind the search)
     return ICP_OK;
 }
 ICP_CATCH_ALL
@@ -1329,7 +1418,7 @@ int icp_profile_run (icp_handle h, uint32_t iterations, float *out_ms, float *to
     // the stages as separate launches (the chained form has no stage boundaries to time), events around each
     for (uint32_t r = 0; r < iterations && e == hipSuccess; ++r) {
         hipEvent_t *x = &ev[(size_t) r * 5];
-        e = hipEventRecord (x[0], h->stream); icp_launch_search_stage (p, h->stream);     // (trimming on: select and apply time with the search)
+        e = hipEventRecord (x[0], h->stream); icp_launch_search_stage (p, h->stream);     // (trimming, one-to-one, the pair filter on: their passes time with the search)
         if (e == hipSuccess) e = hipEventRecord (x[1], h->stream);
         if (!p.fused) icp_launch_means (p, h->stream);
         if (e == hipSuccess) e = hipEventRecord (x[2], h->stream);

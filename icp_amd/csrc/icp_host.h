@@ -115,6 +115,8 @@ struct icp_context {
     float robust_scale = 0.f;                    // the robust loss's scale k (icp_set_robust_loss; 0 while off; survives icp_init): its device word is icp_robust_scale
     bool symmetric = false;                      // the symmetric objective (icp_set_symmetric; survives icp_init): with gicp_eps it decides p.gicp
     float gicp_eps = 0.f;                        // plane-to-plane's epsilon (icp_set_plane_to_plane; 0 while off; survives icp_init): its device word is icp_gicp_eps
+    float normal_min_cos = 0.f;                  // normal rejection's threshold (icp_set_normal_rejection; 0 while off; survives icp_init): its device word is icp_pair_filter_settings [0]
+    uint32_t boundary_gw = 0;                    // boundary rejection's grid width (icp_set_boundary_rejection; 0: off; survives icp_init): its device word is icp_pair_filter_settings [1]
     uint64_t graph_clock = 0, param_gen = 0;     // LRU stamp of the graph cache; generation of the parameters the cached graphs were captured with
     float *dTin = nullptr;                       // device scratch for write(T)
     float *dCloud = nullptr, *dCloudOut = nullptr; uint32_t cloud_cap = 0;

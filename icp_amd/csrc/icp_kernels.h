@@ -125,6 +125,9 @@ struct icp_params {
 #define ICP_REJECT_ROBUST_SHIFT 28u
 #define ICP_REJECT_ROBUST_MASK 0x30000000u   // icp_params::reject: the robust loss (icp_set_robust_loss): ICP_ROBUST_* << 28, 0: off
 #define ICP_REJECT_UNIQUE_ON 0x08000000u   // icp_params::reject: one-to-one correspondences are on (icp_set_unique: the REJ kernels, plus claim and resolve: icp_launch_unique)
+#define ICP_REJECT_BOUNDARY_ON 0x04000000u   // icp_params::reject: boundary rejection is on (icp_set_boundary_rejection: the REJ kernels, plus k_pair_filter: icp_launch_pair_filter)
+#define ICP_REJECT_NORMAL_ON 0x02000000u   // icp_params::reject: rejection by normal compatibility is on (icp_set_normal_rejection: likewise; the moving frame's normals are needed)
+#define ICP_REJECT_FILTER_MASK (ICP_REJECT_BOUNDARY_ON | ICP_REJECT_NORMAL_ON)
 static_assert (sizeof (icp_params) == 480, "icp_params grew: the hidden kernel arguments of every kernel would move");
 
 // rejection on: the sum-W formulas in every mode, and a step of nothing accepted (sum W == 0) is the identity
@@ -132,6 +135,10 @@ static __host__ __device__ __forceinline__ bool icp_rejecting (const icp_params 
 static __host__ __device__ __forceinline__ bool icp_trimming (const icp_params &p) { return (p.reject & ICP_REJECT_TRIM_ON) != 0u; }
 // one-to-one correspondences (icp_unique.hip): of the candidates that share a fixed point only the closest keeps its weight
 static __host__ __device__ __forceinline__ bool icp_unique (const icp_params &p) { return (p.reject & ICP_REJECT_UNIQUE_ON) != 0u; }
+// the pair filter (icp_pair_filter.hip): rejection at the fixed grid's boundary and / or by normal compatibility, one pass behind the search
+static __host__ __device__ __forceinline__ bool icp_pair_filter (const icp_params &p) { return (p.reject & ICP_REJECT_FILTER_MASK) != 0u; }
+// the moving frame's normals are needed: by a metric (p.gicp: plane-to-plane, symmetric) or by normal rejection, whatever the metric
+static __host__ __device__ __forceinline__ bool icp_moving_normals (const icp_params &p) { return p.gicp != 0u || (p.reject & ICP_REJECT_NORMAL_ON) != 0u; }
 // the robust loss's kind (ICP_ROBUST_HUBER 1, CAUCHY 2, TUKEY 3; 0: off).  Its scale k is a device word (icp_robust_scale).
 static __host__ __device__ __forceinline__ uint32_t icp_robust (const icp_params &p) { return (p.reject & ICP_REJECT_ROBUST_MASK) >> ICP_REJECT_ROBUST_SHIFT; }
 // The robust loss's IRLS weight omega (u) of u = s^2 / k^2 (include/icp_amd.h), in double, each expression in the order written; NaN: 0
@@ -144,11 +151,12 @@ static __host__ __device__ __forceinline__ double icp_robust_omega (uint32_t los
 }
 // An apply pass (k_trim_apply) rewrites the weights behind the search: trimming, or a robust loss on point-to-point (the plane metrics
 // weigh their pairs in k_plane_moments).  One-to-one correspondences on point-to-point need it too: the resolve pass has zeroed weights
-// behind the search's partials, and the pass writes the partials again (the plane metrics read w in k_plane_moments: no pass for them).
+// behind the search's partials, and the pass writes the partials again (the plane metrics read w in k_plane_moments: no pass for them);
+// the pair filter (icp_pair_filter.hip) zeroes weights the same way.
 // The route of every such iteration: per-query outputs stored every time, no chained form.
 static __host__ __device__ __forceinline__ bool icp_apply_pass (const icp_params &p)
 {
-    return icp_trimming (p) || ((icp_robust (p) != 0u || icp_unique (p)) && p.metric == 0u);
+    return icp_trimming (p) || ((icp_robust (p) != 0u || icp_unique (p) || icp_pair_filter (p)) && p.metric == 0u);
 }
 
 // Trimming's buffers (icp_trim.hip) are uint32 words: [batch][4] the result of the last iteration (t bits, n, K, accepted: ICP_MEM_TRIM),
@@ -186,6 +194,8 @@ struct icp_mom_layout {
     size_t robust;               // the float word of the robust loss's scale k (icp_robust_scale)
     size_t gicp;                 // the float word of plane-to-plane's epsilon (icp_gicp_eps)
     size_t uniq;                 // one-to-one correspondences: [batch][4] uint32 result words (icp_unique_area), [batch][m] uint64 claim table (icp_unique_claims)
+    size_t filt;                 // the pair filter's uint32 words (icp_pair_filter_area): [batch][4] ICP_MEM_PAIR_FILTER, [batch][4] the words of its apply pass,
+                                 // [batch][8] the blocks' running counts and their arrival counter, then min_cos (float) and the boundary rule's grid width
     size_t total;
 };
 static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (uint32_t batch, uint32_t m, uint32_t nb)
@@ -199,7 +209,8 @@ static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (uint32_t bat
     l.robust = l.kappa + 1u;
     l.gicp = l.robust + 1u;
     l.uniq = l.gicp + 1u;
-    l.total = l.uniq + 2u * B + B * m;
+    l.filt = l.uniq + 2u * B + B * m;
+    l.total = l.filt + 8u * B + 1u;
     return l;
 }
 static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (const icp_params &p) { return icp_mom_layout_of (p.batch, p.m, p.nb); }
@@ -218,6 +229,14 @@ static inline unsigned long long *icp_unique_claims (const icp_params &p)
 {
     return reinterpret_cast<unsigned long long *> (p.mom + icp_mom_layout_of (p).uniq + 2u * (size_t) p.batch);
 }
+// The pair filter (icp_pair_filter.hip), uint32 words: [batch][4] the result of the last iteration (n, at_boundary, incompatible, accepted:
+// ICP_MEM_PAIR_FILTER); [batch][4] the same laid out as k_trim_apply reads trimming's words, (0xFFFFFFFE, n, accepted, 0), for the apply
+// pass of the filter alone (icp_pair_filter_apply_area); [batch][8] the running counts of an iteration's blocks and their arrival counter,
+// zero between launches; then the two settings the kernel reads instead of capturing them: min_cos (float) and the grid width.
+static inline uint32_t *icp_pair_filter_area (const icp_params &p) { return reinterpret_cast<uint32_t *> (p.mom + icp_mom_layout_of (p).filt); }
+static inline uint32_t *icp_pair_filter_apply_area (const icp_params &p) { return icp_pair_filter_area (p) + 4u * (size_t) p.batch; }
+static inline uint32_t *icp_pair_filter_counts (const icp_params &p) { return icp_pair_filter_area (p) + 8u * (size_t) p.batch; }
+static inline uint32_t *icp_pair_filter_settings (const icp_params &p) { return icp_pair_filter_area (p) + 16u * (size_t) p.batch; }
 
 // The XP allocation of one RBC set, offsets in floats: [batch][m][8] the permuted database, then [batch][m] float4 NORMALS_F and
 // [batch][m] float4 COLOR_GRAD_F ([gx gy gz C] per fixed point).  The normals and gradients belong to the fixed frame as the RBC does,
@@ -327,10 +346,12 @@ void icp_launch_trim (const icp_params &p, hipStream_t s);                   // 
 uint32_t icp_trim_launches (const icp_params &p);                             // how many that is
 void icp_launch_unique (const icp_params &p, hipStream_t s);                 // icp_unique.hip: k_unique_claim + k_unique_resolve
 #define ICP_UNIQUE_LAUNCHES 2u                                                // launches of icp_launch_unique
+void icp_launch_pair_filter (const icp_params &p, hipStream_t s);            // icp_pair_filter.hip: k_pair_filter (boundary and / or normal rejection), behind the search
+#define ICP_PAIR_FILTER_LAUNCHES 1u                                           // launches of icp_launch_pair_filter
 void icp_launch_robust_apply (const icp_params &p, hipStream_t s);            // icp_robust.hip: k_trim_apply_robust<fused?> (a point-to-point robust loss)
 void icp_launch_plane_moments_robust (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);   // icp_robust.hip: k_plane_moments_robust<colored?>
 void icp_launch_p2pl_solve (const icp_params &p, hipStream_t s);             // icp_p2pl.hip: k_plane_moments<colored?> + k_p2pl_finalize
-void icp_launch_normals_grid (const icp_params &p, hipStream_t s);           // icp_p2pl.hip: k_normals_grid (+ colored: k_color_grad_grid; plane-to-plane, symmetric: + NORMALS_M), behind buildRBC
+void icp_launch_normals_grid (const icp_params &p, hipStream_t s);           // icp_p2pl.hip: k_normals_grid (+ colored: k_color_grad_grid; plane-to-plane, symmetric, normal rejection: + NORMALS_M), behind buildRBC
 void icp_launch_normals_m (const icp_params &p, hipStream_t s, uint32_t b0, uint32_t nb);   // icp_p2pl.hip: k_normals_grid pointed at M, registrations b0 .. b0 + nb - 1
 void icp_launch_gicp_moments (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);          // icp_gicp.hip: k_gicp_moments<robust?>
 void icp_launch_sym_moments (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);           // icp_symmetric.hip: k_sym_moments<robust?>

@@ -584,6 +584,7 @@ __global__ void k_nop (icp_params p) { if (p.m == 0xFFFFFFFFu) p.st->k = 0; }
 // publishes every iteration's (k, done) to a host-driven run (the fused form leaves a converged registration's word to the fused finalize).
 // One-to-one correspondences on (icp_unique.hip): k_unique_claim and k_unique_resolve right behind the search, so that trimming's
 // candidates are the winners; on point-to-point the apply pass follows whatever else is on (icp_apply_pass).
+// Boundary or normal rejection on (icp_pair_filter.hip): k_pair_filter in front of them, so that a pair it rejects claims no fixed point.
 void icp_launch_search_stage (const icp_params &p, hipStream_t s)
 {
     if (!icp_apply_pass (p) && !icp_p2pl (p)) { icp_launch_search (p, s); return; }
@@ -591,6 +592,7 @@ void icp_launch_search_stage (const icp_params &p, hipStream_t s)
     q.emit = 1;
     if (icp_p2pl (p)) q.fused = 0;
     icp_launch_search (q, s);
+    if (icp_pair_filter (p)) icp_launch_pair_filter (q, s);        // (icp_pair_filter.hip: boundary and normal rejection, in front of everything else that reads the weights)
     if (icp_unique (p)) icp_launch_unique (q, s);                  // (icp_unique.hip: in front of trimming's selection and of every apply pass)
     if (icp_apply_pass (p)) icp_launch_trim (q, s);
 }
@@ -612,7 +614,7 @@ void icp_launch_masked (const icp_params &p, hipStream_t s, unsigned mask)
 // removes outweighs every block re-deriving T), 2 always (sizes the second tree level of the prologue can hold).
 bool icp_chain_supported (const icp_params &p)
 {
-    // (trimming, a point-to-point robust loss, one-to-one correspondences on point-to-point: the apply pass sits between the search and the finalize, which the chained form folds into one launch)
+    // (trimming, a point-to-point robust loss, one-to-one correspondences or the pair filter on point-to-point: the apply pass sits between the search and the finalize, which the chained form folds into one launch)
     // (point-to-plane: its own finalize, no chained form)
     return p.fused && !icp_apply_pass (p) && !icp_p2pl (p) && p.nb <= 4096u && p.nr <= 1024u && (p.chain == 2 || (p.chain == 1 && !icp_dense (p)));
 }

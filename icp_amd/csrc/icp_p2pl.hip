@@ -312,10 +312,10 @@ void icp_launch_normals_grid (const icp_params &p, hipStream_t s)
     hipLaunchKernelGGL (k_normals_grid, grid, dim3 (256), 0, s, p, p.F, icp_normals_f (p));
     // (the intensity gradients need the normals just computed)
     if (icp_colored (p)) hipLaunchKernelGGL (k_color_grad_grid, grid, dim3 (256), 0, s, p, (const float4 *) icp_normals_f (p), icp_color_grad_f (p));
-    if (p.gicp) icp_launch_normals_m (p, s, 0u, p.batch);
+    if (icp_moving_normals (p)) icp_launch_normals_m (p, s, 0u, p.batch);
 }
 
-// plane-to-plane or symmetric with ICP_NORMALS_GRID: NORMALS_M of registrations b0 .. b0 + nb - 1 from M, by the same kernel
+// plane-to-plane, symmetric or normal rejection with ICP_NORMALS_GRID: NORMALS_M of registrations b0 .. b0 + nb - 1 from M, by the same kernel
 void icp_launch_normals_m (const icp_params &p, hipStream_t s, uint32_t b0, uint32_t nb)
 {
     const dim3 grid ((p.m + 255u) / 256u, nb);

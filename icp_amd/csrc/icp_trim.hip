@@ -211,7 +211,8 @@ void icp_launch_trim (const icp_params &p, hipStream_t s)
     // (a robust loss on the plane metrics weighs its pairs in k_plane_moments: the apply pass is trimming's alone there)
     if (icp_robust (p) != 0u && !icp_p2pl (p)) { icp_launch_robust_apply (p, s); return; }
     // (one-to-one correspondences alone: the resolve pass has left words that accept every candidate — icp_unique_area)
-    if (!icp_trimming (p)) area = icp_unique_area (p);
+    // (the pair filter alone — icp_pair_filter.hip — has left such words too: icp_pair_filter_apply_area)
+    if (!icp_trimming (p)) area = icp_unique (p) ? icp_unique_area (p) : icp_pair_filter_apply_area (p);
     if (p.fused) hipLaunchKernelGGL (k_trim_apply<true>, dim3 (p.nb, p.batch), dim3 (64), 0, s, p, (const uint32_t *) area, icp_tpr_magic (p.side));
     else hipLaunchKernelGGL (k_trim_apply<false>, dim3 (2 * p.nwg, p.batch), dim3 (64), 0, s, p, (const uint32_t *) area, icp_tpr_magic (p.side));
 }

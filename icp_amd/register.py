@@ -13,7 +13,8 @@ from .io import load_pc8d, save_pc8d
 
 def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, angle_threshold=0.001,
                     translation_threshold=0.01, reduce_mode=ReduceMode.FUSED, reject_invalid=False, max_dist=None, trim=1.0,
-                    point_to_plane=None, colored=None, robust=None, plane_to_plane=None, symmetric=False, one_to_one=False):
+                    point_to_plane=None, colored=None, robust=None, plane_to_plane=None, symmetric=False, one_to_one=False,
+                    normal_angle=None, reject_boundary=False):
     """Returns (T[8], k, latency_ms, transformed moving cloud).  reject_invalid / max_dist: correspondence rejection
     (ICPStep.set_rejection), trim: the fraction of pairs trimmed ICP keeps (ICPStep.set_trimming; 1.0: off), point_to_plane: mu of
     point-to-plane ICP with the fixed frame's normals from its 128 x 128 landmark grid (ICPStep.set_error_metric; None: off),
@@ -21,14 +22,21 @@ def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, a
     None: off), robust: (RobustLoss kind, scale) of a robust loss (ICPStep.set_robust_loss; None: off), plane_to_plane: epsilon of
     Generalized ICP, with both frames' grid normals and mu = point_to_plane or 0 (ICPStep.set_plane_to_plane; None: off), symmetric:
     the symmetric objective, with both frames' grid normals and mu = point_to_plane or 0 (ICPStep.set_symmetric), one_to_one: of the
-    pairs that share a fixed point only the closest keeps its weight (ICPStep.set_unique); none is the reference's behaviour, all are
-    off by default."""
+    pairs that share a fixed point only the closest keeps its weight (ICPStep.set_unique), normal_angle: the largest angle in degrees
+    between the two normals of a pair, with both frames' grid normals (ICPStep.set_normal_rejection with its cosine; None: off),
+    reject_boundary: pairs whose fixed point lies at the boundary of the 128 wide landmark grid get weight 0
+    (ICPStep.set_boundary_rejection); none is the reference's behaviour, all are off by default."""
     reg = ICP(device)
     reg.init(16384, 256, a, c, max_iterations, angle_threshold, translation_threshold)   # src/ocl_icp_reg.cpp:81-88
     reg.setPowerMode(PowerMode.SQUARED)
     reg.setReduceMode(reduce_mode)
     if reject_invalid or max_dist:
         reg.set_rejection(reject_invalid, max_dist)
+    if reject_boundary:
+        reg.set_boundary_rejection(128)                        # (640 x 480 clouds -> 128 x 128 landmarks, row-major)
+    if normal_angle is not None:
+        reg.set_normals(Normals.GRID, 128)
+        reg.set_normal_rejection(normal_cosine(normal_angle))
     if one_to_one:
         reg.set_unique(True)
     if trim != 1.0:
@@ -100,6 +108,18 @@ def _epsilon(s):
     return v
 
 
+def normal_cosine(degrees):
+    """The min_cos of ICPStep.set_normal_rejection for a largest angle in degrees (the engine's rule takes the cosine)."""
+    return min(1.0, max(-1.0, math.cos(math.radians(float(degrees)))))
+
+
+def _angle(s):
+    v = float(s)
+    if not 0.0 <= v <= 180.0:
+        raise argparse.ArgumentTypeError("must be an angle in [0, 180] degrees, got %s" % s)
+    return v
+
+
 def _robust(s):
     """KIND:SCALE, e.g. tukey:50 -> (RobustLoss kind, scale); KIND is huber, cauchy or tukey, SCALE finite and > 0."""
     kind, sep, scale = s.partition(":")
@@ -130,6 +150,12 @@ def main(argv=None):
     ap.add_argument("--one-to-one", action="store_true",
                     help="one-to-one correspondences: of the pairs that share a fixed point only the closest keeps its weight, "
                          "before trimming (not reference behaviour)")
+    ap.add_argument("--normal-angle", type=_angle, default=None, metavar="DEG",
+                    help="give pairs whose two surface normals differ by more than DEG degrees weight 0, normals from both landmark "
+                         "grids (not reference behaviour)")
+    ap.add_argument("--reject-boundary", action="store_true",
+                    help="give pairs whose fixed point lies on the rim of the fixed landmark grid or beside a depth hole weight 0 "
+                         "(not reference behaviour)")
     ap.add_argument("--point-to-plane", type=_point_weight, default=None, metavar="MU",
                     help="point-to-plane ICP plus MU (>= 0) times the point-to-point error, normals from the fixed landmark grid "
                          "(not reference behaviour)")
@@ -149,7 +175,8 @@ def main(argv=None):
     T, k, ms, out = register_clouds(load_pc8d(args.fixed), load_pc8d(args.moving), args.device, a=args.alpha,
                                     reject_invalid=args.reject_invalid, max_dist=args.max_dist, trim=args.trim,
                                     point_to_plane=args.point_to_plane, colored=args.colored, robust=args.robust,
-                                    plane_to_plane=args.plane_to_plane, symmetric=args.symmetric, one_to_one=args.one_to_one)
+                                    plane_to_plane=args.plane_to_plane, symmetric=args.symmetric, one_to_one=args.one_to_one,
+                                    normal_angle=args.normal_angle, reject_boundary=args.reject_boundary)
     q, t, s = T[:4], T[4:7], T[7]
     sinth_2 = float(np.linalg.norm(q[:3]))
     angle = 180.0 / math.pi * 2 * math.atan2(sinth_2, float(q[3]))

@@ -625,6 +625,18 @@ namespace ICP
         void setUnique (bool on) { check (icp_set_unique (h, on ? 1 : 0)); }
         bool getUnique () { int on = 0; check (icp_get_unique (h, &on)); return on != 0; }
 
+        /*! \brief Rejection by normal compatibility (icp_set_normal_rejection, include/icp_amd.h; not in the reference, off by
+         *         default): a pair whose two normals enclose an angle with a cosine below min_cos gets weight 0.  It needs both frames'
+         *         normals (setNormals) and acts before one-to-one correspondences, trimming and the robust loss. */
+        void setNormalRejection (bool on, float min_cos = 0.f) { check (icp_set_normal_rejection (h, on ? 1 : 0, on ? min_cos : 0.f)); }
+        bool getNormalRejection (float *min_cos = nullptr) { int on = 0; float c = 0.f; check (icp_get_normal_rejection (h, &on, &c)); if (min_cos) *min_cos = c; return on != 0; }
+
+        /*! \brief Rejection at the fixed grid's boundary (icp_set_boundary_rejection, include/icp_amd.h; not in the reference, off by
+         *         default): a pair whose fixed point lies on the rim of the grid_width wide fixed grid, is invalid or has an invalid
+         *         grid neighbour gets weight 0.  0: off. */
+        void setBoundaryRejection (uint32_t grid_width) { check (icp_set_boundary_rejection (h, grid_width)); }
+        uint32_t getBoundaryRejection () { uint32_t w = 0; check (icp_get_boundary_rejection (h, &w)); return w; }
+
         /*! \brief Robust loss (icp_set_robust_loss, include/icp_amd.h; not in the reference, off by default): every pair's weight is
          *         multiplied by the loss's IRLS weight of its own residual, for every error metric.  ICP_ROBUST_NONE: off. */
         void setRobustLoss (int loss, float scale = 0.f) { check (icp_set_robust_loss (h, loss, scale)); }

@@ -91,6 +91,7 @@ typedef enum {
     ICP_MEM_COLOR_GRAD_F = 23, /* io m x float4  colored ICP: intensity gradients of the fixed landmarks [gx gy gz C] */
     ICP_MEM_NORMALS_M = 24,    /* io m x float4  normals of the moving landmarks [nx ny nz 0], indexed like M (plane-to-plane, symmetric) */
     ICP_MEM_UNIQUE = 25,       /* out uint32[2]   one-to-one correspondences, last iteration: candidates n, winners (0 when off) */
+    ICP_MEM_PAIR_FILTER = 26,  /* out uint32[4]   boundary / normal rejection, last iteration: n, at_boundary, incompatible, accepted (0 when off) */
     ICP_MEM_COUNT_
 } icp_mem;
 
@@ -303,6 +304,58 @@ int icp_get_trimming (icp_handle h, float *keep_fraction);
  * its passes into the search stage.  ICP_EINVAL: on outside {0, 1}. */
 int icp_set_unique (icp_handle h, int on);
 int icp_get_unique (icp_handle h, int *on);
+
+/* Rejection by normal compatibility (PCL: CorrespondenceRejectorSurfaceNormal) and at the fixed grid's boundary (PCL:
+ * CorrespondenceRejectorBoundaryPoints; Turk & Levoy; both in Rusinkiewicz & Levoy, "Efficient Variants of ICP"; not reference
+ * behaviour).  Two independent settings, both off by default; with both off: the same kernels, launches, graphs and bits as without
+ * them.  The common rule:
+ *   - Candidates are the pairs that survive icp_set_rejection's rules and have a weight != 0 and an ICP_MEM_NN_ID id < m.
+ *   - A candidate that a rule rejects behaves exactly like a rejected pair: its correspondence is kept (NN_ID, RID and the NN / QT xyz
+ *     stay as they are), its weight is +0 (written to the W and NN outputs), and its moment, mean and S terms — for a plane metric its
+ *     plane-system terms — are exact zeros.  As with rejection, REGULAR mode uses the sum-W formulas.  No pair accepted: the
+ *     sum W == 0 identity step (T unchanged, ICP::run stops).
+ *   - The rules act after icp_set_rejection's rules and before one-to-one correspondences, trimming and the robust loss: a rejected
+ *     pair claims no fixed point (with icp_set_unique on, ICP_MEM_UNIQUE's n equals `accepted` below), and is none of trimming's n.
+ *   - The boundary test comes first and a pair is counted once: ICP_MEM_PAIR_FILTER holds (n, at_boundary, incompatible, accepted) of
+ *     the last iteration per registration, n = at_boundary + incompatible + accepted; zeros while both rules are off.
+ *   - The search is untouched: at the same T the ids, distances and RID are bit-identical to a run with the rules off.  The counts are
+ *     integer sums and nothing else is accumulated: the result does not depend on the order in which the device gets to the pairs.
+ * The boundary rule, icp_set_boundary_rejection (h, grid_width) with grid_width gw > 0 (0: off):
+ *   - F is read as a row-major grid gw wide, rows = m / gw.  m % gw == 0 is required and checked as icp_set_normals checks its width:
+ *     ICP_ESTATE from this call on an initialised handle, and from icp_build_rbc and the icp_track_* calls that build the RBC.
+ *   - A point of F is valid as in the icp_set_normals rule: xyz finite and not (0, 0, 0).
+ *   - With x = id % gw, y = id / gw the fixed point id is a boundary point when x == 0, x == gw - 1, y == 0 or y == rows - 1, when the
+ *     point itself is invalid, or when any of its 8 grid neighbours in F is invalid.  F is the registration's fixed set in its original
+ *     order, the one id indexes.  A depth jump between valid neighbours is no boundary.
+ *   - A candidate whose fixed point is a boundary point is rejected.  The mask is evaluated from F in every iteration; nothing is kept
+ *     per fixed frame, so a tracked frame needs nothing more than its landmarks.
+ * The normal rule, icp_set_normal_rejection (h, 1, min_cos); min_cos is the cosine of the largest accepted angle, finite, in [-1, 1]:
+ *   - Per pair in double from the float inputs, every expression in the order written, with no contraction: N_Q =
+ *     ICP_MEM_NORMALS_F[id], N_M = ICP_MEM_NORMALS_M[i] in query order (a non-finite normal counts as zero); R the cumulative
+ *     rotation this iteration's search used, as in the plane-to-plane rule; N_P = R N_M, each component (R_a0 mx + R_a1 my) + R_a2 mz;
+ *     qq = (qx qx + qy qy) + qz qz, pp likewise from N_P, o = (qx px + qy py) + qz pz.
+ *   - The pair is compatible iff qq > 0 && pp > 0 && o >= (double) min_cos * sqrt (qq * pp); every other candidate is rejected.  A
+ *     pair with an absent normal cannot be shown compatible; a NaN or an infinity makes the comparison false.
+ *   - The setting makes the handle need the moving frame's normals under every metric, point-to-point included, and
+ *     ICP_MEM_NORMALS_M follows plane-to-plane's rules: ICP_NORMALS_GIVEN: used as written; ICP_NORMALS_GRID: computed by
+ *     icp_build_rbc behind the fixed normals and again by every later write of M — switching the rule on with ICP_NORMALS_GRID
+ *     makes runs return ICP_ESTATE until icp_build_rbc has run again.
+ *   - It combines with every metric.  Tracking is not provided (as for plane-to-plane): icp_track_submit / icp_track_next return
+ *     ICP_ESTATE.
+ * With a rule on the per-query outputs are stored by every iteration, and an iteration is the separate form (icp_run_form is
+ * ICP_FORM_SEPARATE, there is no chained launch).  icp_launches_per_iteration counts what the rules add behind the search:
+ *   - point-to-point: 2 launches — the pass, and the pass that writes the search's partials again from the weights (the apply pass of
+ *     trimming, one-to-one correspondences and a point-to-point robust loss; with any of them on it runs anyway, and the rules add 1);
+ *   - the plane metrics: 1 launch; their moments read the weights themselves.
+ * Switching a rule on or off, or a new width, captures the graphs anew (as icp_set_trimming does); a new min_cos while the normal rule
+ * stays on is a parameter update that captured run graphs see.  The settings apply to single and batched registrations, the boundary
+ * rule to tracked ones too, to both reduce modes and both rotation solvers, and survive icp_init.  icp_profile_run counts the pass
+ * into the search stage.  ICP_EINVAL: on outside {0, 1}, min_cos NaN or outside [-1, 1].  icp_get_normal_rejection gives (0, 0.f)
+ * while the rule is off. */
+int icp_set_normal_rejection (icp_handle h, int on, float min_cos);
+int icp_get_normal_rejection (icp_handle h, int *on, float *min_cos);
+int icp_set_boundary_rejection (icp_handle h, uint32_t grid_width);
+int icp_get_boundary_rejection (icp_handle h, uint32_t *grid_width);
 
 /* Point-to-plane ICP with a share of point-to-point (not reference behaviour; off by default).  The rule:
  *   - metric is ICP_METRIC_POINT_TO_POINT (the default: the same kernels, launches, graphs and bits as without it) or
@@ -703,6 +756,8 @@ int icp_batch_set_modes (icp_batch_handle b, int reduce_mode, int power_mode);
 int icp_batch_set_rejection (icp_batch_handle b, int flags, float max_dist);                /* icp_set_rejection on every slot */
 int icp_batch_set_trimming (icp_batch_handle b, float keep_fraction);                        /* icp_set_trimming on every slot */
 int icp_batch_set_unique (icp_batch_handle b, int on);                                       /* icp_set_unique on every slot */
+int icp_batch_set_normal_rejection (icp_batch_handle b, int on, float min_cos);              /* icp_set_normal_rejection on every slot */
+int icp_batch_set_boundary_rejection (icp_batch_handle b, uint32_t grid_width);              /* icp_set_boundary_rejection on every slot */
 int icp_batch_set_robust_loss (icp_batch_handle b, int loss, float scale);                   /* icp_set_robust_loss on every slot */
 int icp_batch_set_error_metric (icp_batch_handle b, int metric, float point_weight);         /* icp_set_error_metric on every slot */
 int icp_batch_set_normals (icp_batch_handle b, int source, uint32_t grid_width);             /* icp_set_normals on every slot */

@@ -78,6 +78,9 @@ public:
     /*! \brief One-to-one correspondences of the registration (ICPStep::setUnique; not in the reference's demo, off by default). */
     void setUnique (bool on) { reg.setUnique (on); }
     bool getUnique () { return reg.getUnique (); }
+    /*! \brief Normal and boundary rejection of the registration (ICPStep::setNormalRejection, setBoundaryRejection; off by default). */
+    void setNormalRejection (bool on, float min_cos = 0.f) { reg.setNormalRejection (on, min_cos); }
+    void setBoundaryRejection (uint32_t grid_width) { reg.setBoundaryRejection (grid_width); }
     /*! \brief Robust loss of the registration (ICPStep::setRobustLoss; not in the reference's demo, off by default). */
     void setRobustLoss (int loss, float scale = 0.f) { reg.setRobustLoss (loss, scale); }
     void setRobustLoss (const icp::RobustLoss &r) { reg.setRobustLoss (r); }
