@@ -200,6 +200,19 @@ int for_each_slot (icp_batch_context *b, Fn &&fn)
     return ICP_OK;
 }
 
+// The batch setters: the single-handle setter applied to every slot's handle.  It validates the arguments and words the message (the
+// first slot's handle reports); a batch setter checks for itself only where the tests pin a message with its own name.
+template <typename... P, typename... A>
+int set_all (icp_batch_context *b, int (*set) (icp_handle, P...), A... args)
+{
+    if (!b) return ICP_EINVAL;
+    for (icp_handle h : b->slots) {
+        int rc = set (h, args...);
+        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
+    }
+    return ICP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -339,152 +352,59 @@ ICP_CATCH_ALL
 
 int icp_batch_set_modes (icp_batch_handle b, int reduce_mode, int power_mode) try
 {
-    if (!b) return ICP_EINVAL;
-    for (icp_handle h : b->slots) {
-        int rc = icp_set_reduce_mode (h, reduce_mode); if (rc == ICP_OK) rc = icp_set_power_mode (h, power_mode);
-        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
-    }
-    return ICP_OK;
+    int rc = set_all (b, icp_set_reduce_mode, reduce_mode);
+    return rc ? rc : set_all (b, icp_set_power_mode, power_mode);
 }
 ICP_CATCH_ALL
 
-int icp_batch_set_rejection (icp_batch_handle b, int flags, float max_dist) try
-{
-    if (!b) return ICP_EINVAL;
-    for (icp_handle h : b->slots) {
-        int rc = icp_set_rejection (h, flags, max_dist);
-        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
-    }
-    return ICP_OK;
-}
-ICP_CATCH_ALL
+int icp_batch_set_rejection (icp_batch_handle b, int flags, float max_dist) try { return set_all (b, icp_set_rejection, flags, max_dist); } ICP_CATCH_ALL
+int icp_batch_set_trimming (icp_batch_handle b, float keep_fraction) try { return set_all (b, icp_set_trimming, keep_fraction); } ICP_CATCH_ALL
+int icp_batch_set_unique (icp_batch_handle b, int on) try { return set_all (b, icp_set_unique, on); } ICP_CATCH_ALL
+int icp_batch_set_normal_rejection (icp_batch_handle b, int on, float min_cos) try { return set_all (b, icp_set_normal_rejection, on, min_cos); } ICP_CATCH_ALL
+int icp_batch_set_boundary_rejection (icp_batch_handle b, uint32_t grid_width) try { return set_all (b, icp_set_boundary_rejection, grid_width); } ICP_CATCH_ALL
+int icp_batch_set_error_metric (icp_batch_handle b, int metric, float point_weight) try { return set_all (b, icp_set_error_metric, metric, point_weight); } ICP_CATCH_ALL
 
-int icp_batch_set_trimming (icp_batch_handle b, float keep_fraction) try
-{
-    if (!b) return ICP_EINVAL;
-    if (!(keep_fraction > 0.f && keep_fraction <= 1.f)) return bfail (b, ICP_EINVAL, "icp_batch_set_trimming: keep_fraction must be in (0, 1] (1: off)");
-    for (icp_handle h : b->slots) {
-        int rc = icp_set_trimming (h, keep_fraction);
-        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
-    }
-    return ICP_OK;
-}
-ICP_CATCH_ALL
-
-int icp_batch_set_unique (icp_batch_handle b, int on) try
-{
-    if (!b) return ICP_EINVAL;
-    if (on != 0 && on != 1) return bfail (b, ICP_EINVAL, "icp_batch_set_unique: on must be 0 or 1");
-    for (icp_handle h : b->slots) {
-        int rc = icp_set_unique (h, on);
-        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
-    }
-    return ICP_OK;
-}
-ICP_CATCH_ALL
-
-int icp_batch_set_normal_rejection (icp_batch_handle b, int on, float min_cos) try
-{
-    if (!b) return ICP_EINVAL;
-    if (on != 0 && on != 1) return bfail (b, ICP_EINVAL, "icp_batch_set_normal_rejection: on must be 0 or 1");
-    if (!(min_cos >= -1.f && min_cos <= 1.f)) return bfail (b, ICP_EINVAL, "icp_batch_set_normal_rejection: min_cos must be in [-1, 1]");
-    for (icp_handle h : b->slots) {
-        int rc = icp_set_normal_rejection (h, on, min_cos);
-        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
-    }
-    return ICP_OK;
-}
-ICP_CATCH_ALL
-
-int icp_batch_set_boundary_rejection (icp_batch_handle b, uint32_t grid_width) try
-{
-    if (!b) return ICP_EINVAL;
-    for (icp_handle h : b->slots) {
-        int rc = icp_set_boundary_rejection (h, grid_width);
-        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
-    }
-    return ICP_OK;
-}
-ICP_CATCH_ALL
-
-int icp_batch_set_robust_loss (icp_batch_handle b, int loss, float scale) try
-{
-    // (the arguments first, as icp_set_robust_loss does: with b == NULL the message is icp_batch_last_error (NULL)'s)
-    if (loss != ICP_ROBUST_NONE && loss != ICP_ROBUST_HUBER && loss != ICP_ROBUST_CAUCHY && loss != ICP_ROBUST_TUKEY)
-        return bfail (b, ICP_EINVAL, "icp_batch_set_robust_loss: unknown loss");
-    if (loss != ICP_ROBUST_NONE && !(scale > 0.f && std::isfinite (scale)))
-        return bfail (b, ICP_EINVAL, "icp_batch_set_robust_loss: scale must be finite and > 0");
-    if (!b) return bfail (b, ICP_EINVAL, "icp_batch_set_robust_loss: null handle");
-    for (icp_handle h : b->slots) {
-        int rc = icp_set_robust_loss (h, loss, scale);
-        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
-    }
-    return ICP_OK;
-}
-ICP_CATCH_ALL
-
-int icp_batch_set_error_metric (icp_batch_handle b, int metric, float point_weight) try
-{
-    if (!b) return ICP_EINVAL;
-    if (metric != ICP_METRIC_POINT_TO_POINT && metric != ICP_METRIC_POINT_TO_PLANE && metric != ICP_METRIC_COLORED)
-        return bfail (b, ICP_EINVAL, "icp_batch_set_error_metric: unknown metric");
-    if (!(point_weight >= 0.f && std::isfinite (point_weight))) return bfail (b, ICP_EINVAL, "icp_batch_set_error_metric: point_weight must be finite and >= 0");
-    for (icp_handle h : b->slots) {
-        int rc = icp_set_error_metric (h, metric, point_weight);
-        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
-    }
-    return ICP_OK;
-}
-ICP_CATCH_ALL
-
+// (these two word a refused argument with their own name, behind the handle check)
 int icp_batch_set_color_weight (icp_batch_handle b, float kappa) try
 {
-    if (!b) return ICP_EINVAL;
-    if (!(kappa >= 0.f && std::isfinite (kappa))) return bfail (b, ICP_EINVAL, "icp_batch_set_color_weight: kappa must be finite and >= 0");
-    for (icp_handle h : b->slots) {
-        int rc = icp_set_color_weight (h, kappa);
-        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
-    }
-    return ICP_OK;
-}
-ICP_CATCH_ALL
-
-int icp_batch_set_plane_to_plane (icp_batch_handle b, float epsilon) try
-{
-    // (the argument first, as icp_set_plane_to_plane does: with b == NULL the message is icp_batch_last_error (NULL)'s)
-    if (!(epsilon >= 0.f && epsilon <= 1.f)) return bfail (b, ICP_EINVAL, "icp_batch_set_plane_to_plane: epsilon must be in [0, 1] (0: off)");
-    if (!b) return bfail (b, ICP_EINVAL, "icp_batch_set_plane_to_plane: null handle");
-    for (icp_handle h : b->slots) {
-        int rc = icp_set_plane_to_plane (h, epsilon);
-        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
-    }
-    return ICP_OK;
-}
-ICP_CATCH_ALL
-
-int icp_batch_set_symmetric (icp_batch_handle b, int on) try
-{
-    // (the argument first, as icp_set_symmetric does)
-    if (on != 0 && on != 1) return bfail (b, ICP_EINVAL, "icp_batch_set_symmetric: on must be 0 or 1");
-    if (!b) return bfail (b, ICP_EINVAL, "icp_batch_set_symmetric: null handle");
-    for (icp_handle h : b->slots) {
-        int rc = icp_set_symmetric (h, on);
-        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
-    }
-    return ICP_OK;
+    if (b && !(kappa >= 0.f && std::isfinite (kappa))) return bfail (b, ICP_EINVAL, "icp_batch_set_color_weight: kappa must be finite and >= 0");
+    return set_all (b, icp_set_color_weight, kappa);
 }
 ICP_CATCH_ALL
 
 int icp_batch_set_normals (icp_batch_handle b, int source, uint32_t grid_width) try
 {
-    if (!b) return ICP_EINVAL;
-    if (source != ICP_NORMALS_GIVEN && source != ICP_NORMALS_GRID) return bfail (b, ICP_EINVAL, "icp_batch_set_normals: unknown source");
-    if (source == ICP_NORMALS_GRID && grid_width == 0u) return bfail (b, ICP_EINVAL, "icp_batch_set_normals: ICP_NORMALS_GRID needs a grid width");
-    for (icp_handle h : b->slots) {
-        int rc = icp_set_normals (h, source, grid_width);
-        if (rc != ICP_OK) return bfail (b, rc, icp_last_error (h));
-    }
-    return ICP_OK;
+    if (b && source != ICP_NORMALS_GIVEN && source != ICP_NORMALS_GRID) return bfail (b, ICP_EINVAL, "icp_batch_set_normals: unknown source");
+    if (b && source == ICP_NORMALS_GRID && grid_width == 0u) return bfail (b, ICP_EINVAL, "icp_batch_set_normals: ICP_NORMALS_GRID needs a grid width");
+    return set_all (b, icp_set_normals, source, grid_width);
+}
+ICP_CATCH_ALL
+
+// (the arguments first, as the single-handle setters do: with b == NULL the message is icp_batch_last_error (NULL)'s)
+int icp_batch_set_robust_loss (icp_batch_handle b, int loss, float scale) try
+{
+    if (loss != ICP_ROBUST_NONE && loss != ICP_ROBUST_HUBER && loss != ICP_ROBUST_CAUCHY && loss != ICP_ROBUST_TUKEY)
+        return bfail (b, ICP_EINVAL, "icp_batch_set_robust_loss: unknown loss");
+    if (loss != ICP_ROBUST_NONE && !(scale > 0.f && std::isfinite (scale)))
+        return bfail (b, ICP_EINVAL, "icp_batch_set_robust_loss: scale must be finite and > 0");
+    if (!b) return bfail (b, ICP_EINVAL, "icp_batch_set_robust_loss: null handle");
+    return set_all (b, icp_set_robust_loss, loss, scale);
+}
+ICP_CATCH_ALL
+
+int icp_batch_set_plane_to_plane (icp_batch_handle b, float epsilon) try
+{
+    if (!(epsilon >= 0.f && epsilon <= 1.f)) return bfail (b, ICP_EINVAL, "icp_batch_set_plane_to_plane: epsilon must be in [0, 1] (0: off)");
+    if (!b) return bfail (b, ICP_EINVAL, "icp_batch_set_plane_to_plane: null handle");
+    return set_all (b, icp_set_plane_to_plane, epsilon);
+}
+ICP_CATCH_ALL
+
+int icp_batch_set_symmetric (icp_batch_handle b, int on) try
+{
+    if (on != 0 && on != 1) return bfail (b, ICP_EINVAL, "icp_batch_set_symmetric: on must be 0 or 1");
+    if (!b) return bfail (b, ICP_EINVAL, "icp_batch_set_symmetric: null handle");
+    return set_all (b, icp_set_symmetric, on);
 }
 ICP_CATCH_ALL
 

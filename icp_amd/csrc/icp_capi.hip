@@ -68,6 +68,89 @@ int outputs_before_change (icp_context *h)
     return materialize_outputs (h, ICP_MEM_NN_ID);
 }
 
+// The fields of icp_params that follow from what the user set.  The ONLY place that packs the bits of `reject` or decides the word
+// `gicp`: icp_create and icp_init_batched start from it, commit () brings p up to date behind every setter.
+uint32_t moving_normals_word (const icp_options &o)    // plane-to-plane and symmetric share p.gicp; both on: 1, and need () refuses the run
+{
+    return o.gicp_eps > 0.f ? 1u : o.symmetric ? ICP_MOVING_NORMALS_SYM : 0u;
+}
+constexpr int reject_user_flags = ICP_REJECT_INVALID;    // the bits of `reject` that icp_set_rejection takes from the caller as they are
+void derive_params (const icp_options &o, icp_params &p)
+{
+    constexpr uint64_t sum = (uint64_t) ICP_REJECT_INVALID + ICP_REJECT_DIST_ON + ICP_REJECT_TRIM_ON + ICP_REJECT_ROBUST_MASK + ICP_REJECT_UNIQUE_ON + ICP_REJECT_FILTER_MASK;
+    static_assert (sum == (ICP_REJECT_INVALID | ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON | ICP_REJECT_FILTER_MASK),
+                   "every rule's bits in icp_params::reject are its own");
+    static_assert (ICP_REJECT_INVALID == 1, "ks_epilogue tests bit 0");
+    static_assert (ICP_ROBUST_TUKEY << ICP_REJECT_ROBUST_SHIFT == ICP_REJECT_ROBUST_MASK, "the loss's kind fills the mask's two bits");
+    static_assert (ICP_REJECT_BOUNDARY_ON + ICP_REJECT_NORMAL_ON == ICP_REJECT_FILTER_MASK, "the pair filter's two rules, a bit each");
+    const bool dist = o.reject_max_dist > 0.f && !std::isinf (o.reject_max_dist), trim = o.trim_keep < 1.f;
+    p.rot = o.rot; p.weighted = o.weighted; p.power_mode = o.power_mode; p.fused = o.reduce_mode; p.chain = o.chain;
+    p.dist_scale = o.metric_scale;
+    p.reject = (uint32_t) o.reject_flags | (dist ? ICP_REJECT_DIST_ON : 0u) | (trim ? ICP_REJECT_TRIM_ON : 0u)
+             | ((uint32_t) o.robust << ICP_REJECT_ROBUST_SHIFT) | (o.unique ? ICP_REJECT_UNIQUE_ON : 0u)
+             | (o.boundary_gw ? ICP_REJECT_BOUNDARY_ON : 0u) | (o.normal_on ? ICP_REJECT_NORMAL_ON : 0u);
+    p.reject_max_dist = o.reject_max_dist;
+    p.reject_d2 = dist ? (float) ((double) o.reject_max_dist * (double) o.reject_max_dist) : 0.f;     // (the product of two floats is exact in double)
+    p.trim_keep = trim ? o.trim_keep : 0.f;
+    p.metric = (uint32_t) o.metric; p.p2pl_mu = o.p2pl_mu;
+    p.gicp = moving_normals_word (o);
+    p.nrm_grid = o.nrm_grid;
+}
+
+// The settings the kernels read from device words instead of captured arguments (a new value touches no graph): which value of the
+// record goes where.  write_words writes the chosen ones (OPT_WORDS: all) in stream order behind whatever the handle's stream holds.
+enum : unsigned { OPT_W_KAPPA = 1u, OPT_W_ROBUST = 2u, OPT_W_EPS = 4u, OPT_W_MIN_COS = 8u, OPT_W_GRID = 16u, OPT_WORDS = 31u };
+int write_words (icp_context *h, unsigned which)
+{
+    const icp_options &o = h->opt;
+    auto bits = [] (float f) { uint32_t u; std::memcpy (&u, &f, sizeof u); return u; };
+    uint32_t *const filter = icp_pair_filter_settings (h->p);
+    const struct { unsigned flag; uint32_t value; void *word; } words[] = {
+        { OPT_W_KAPPA, bits (o.color_kappa), icp_color_kappa (h->p) },
+        { OPT_W_ROBUST, bits (o.robust_scale), icp_robust_scale (h->p) },
+        { OPT_W_EPS, bits (o.gicp_eps), icp_gicp_eps (h->p) },
+        { OPT_W_MIN_COS, bits (o.normal_min_cos), filter },
+        { OPT_W_GRID, o.boundary_gw, filter + 1 },
+    };
+    for (const auto &w : words)
+        if (which & w.flag) HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (w.word), (int) w.value, 1, h->stream));
+    return ICP_OK;
+}
+
+// The one route behind every setter, once it has updated the record.  `what` is what the setter alone knows: which device words it
+// changed (OPT_W_*), and whether the change is a parameter update (OPT_PARAMS: cached graphs are updated in place when next used), a
+// change of route (OPT_ROUTE: other kernels run, graphs are captured anew), or neither.  What follows from the parameters is found
+// by comparing them, old against new: the result area of a feature that went off is cleared (ICP_MEM_TRIM, ICP_MEM_UNIQUE,
+// ICP_MEM_PAIR_FILTER, ICP_MEM_PLANE_SYSTEM read zeros while it is off), and with grid normals a handle that now needs something its
+// last buildRBC did not compute — the moving normals, the intensity gradients — needs a new buildRBC, as after a new F.
+// Device work in a fixed order: the open runs end, words, clears, then the stream is drained, so that work later enqueued on any of
+// the handle's streams sees them.  OPT_QUIESCE: the open runs end although nothing is written.
+enum : unsigned { OPT_PARAMS = 32u, OPT_ROUTE = 64u, OPT_QUIESCE = 128u };
+int commit (icp_context *h, unsigned what)
+{
+    const icp_params was = h->p;
+    icp_params &p = h->p;
+    derive_params (h->opt, p);
+    if (p.nrm_grid && ((icp_moving_normals (p) && !icp_moving_normals (was)) || (icp_colored (p) && !icp_colored (was)))) h->built = false;
+    const bool off[] = { icp_trimming (was) && !icp_trimming (p), icp_unique (was) && !icp_unique (p),
+                         icp_pair_filter (was) && !icp_pair_filter (p), icp_p2pl (was) && !icp_p2pl (p) };
+    const bool clears = off[0] || off[1] || off[2] || off[3];
+    if (h->inited && ((what & (OPT_WORDS | OPT_QUIESCE)) || clears)) {
+        int rc = set_device (h); if (rc) return rc;
+        if ((rc = run_close_all (h))) return rc;
+        if ((rc = write_words (h, what & OPT_WORDS))) return rc;
+        const struct { void *area; size_t bytes; } areas[] = {
+            { icp_trim_area (p), sizeof (uint32_t) * 4u }, { icp_unique_area (p), sizeof (uint32_t) * 4u },
+            { icp_pair_filter_area (p), sizeof (uint32_t) * 8u }, { icp_p2pl_area (p), sizeof (double) * ICP_P2PL_SYS },
+        };
+        for (int i = 0; i < 4; ++i) if (off[i]) HIPCHK (h, hipMemsetAsync (areas[i].area, 0, areas[i].bytes * p.batch, h->stream));
+        if ((what & OPT_WORDS) || clears) HIPCHK (h, hipStreamSynchronize (h->stream));
+    }
+    if (what & OPT_ROUTE) drop_graphs (h);
+    else if (what & OPT_PARAMS) ++h->param_gen;
+    return ICP_OK;
+}
+
 // landmark-grid / representative-grid validation — src/ICP/algorithms.cpp:842-854 generalised (oracle: orc_reps_grid)
 bool reps_grid (uint32_t m, uint32_t nr, uint32_t *nrx, uint32_t *nry, uint32_t *side)
 {
@@ -80,6 +163,33 @@ bool reps_grid (uint32_t m, uint32_t nr, uint32_t *nrx, uint32_t *nry, uint32_t 
     if (g % x || g % y) return false;
     *nrx = x; *nry = y; *side = g;
     return true;
+}
+
+// the device the caller names exists and is a gfx950; who: the caller's message prefix
+int gfx950_device (int device, const std::string &who)
+{
+    int count = 0;
+    if (hipGetDeviceCount (&count) != hipSuccess || count <= 0)
+        return fail (nullptr, ICP_ENODEVICE, who + ": no HIP device visible (the engine has no CPU fallback)");
+    if (device < 0 || device >= count) return fail (nullptr, ICP_EINVAL, who + ": device ordinal out of range");
+    hipDeviceProp_t prop;
+    hipError_t e = hipGetDeviceProperties (&prop, device);
+    if (e != hipSuccess) return fail (nullptr, ICP_EHIP, std::string ("hipGetDeviceProperties: ") + hipGetErrorString (e));
+    if (std::strncmp (prop.gcnArchName, "gfx950", 6) != 0)
+        return fail (nullptr, ICP_ENODEVICE, who + ": device is " + prop.gcnArchName + ", kernels are built for gfx950 only");
+    return ICP_OK;
+}
+
+// the cloud scratch (dCloud, dCloudOut) holds n points of 32 bytes
+int cloud_reserve (icp_context *h, uint32_t n)
+{
+    if (h->cloud_cap >= n) return ICP_OK;
+    if (h->dCloud) (void) hipFree (h->dCloud);
+    if (h->dCloudOut) (void) hipFree (h->dCloudOut);
+    h->dCloud = h->dCloudOut = nullptr; h->cloud_cap = 0;
+    for (float **q : { &h->dCloud, &h->dCloudOut }) HIPCHK (h, hipMalloc ((void **) q, (size_t) n * 32));
+    h->cloud_cap = n;
+    return ICP_OK;
 }
 
 }  // namespace
@@ -118,30 +228,22 @@ int icp_create (icp_handle *out, int device, int rot, int weighted) try
     *out = nullptr;
     if ((rot != ICP_ROT_EIGEN && rot != ICP_ROT_POWER_METHOD) || (weighted != 0 && weighted != 1))
         return fail (nullptr, ICP_EINVAL, "icp_create: rot must be 0|1 and weighted 0|1");
-    int count = 0;
-    hipError_t e = hipGetDeviceCount (&count);
-    if (e != hipSuccess || count <= 0)
-        return fail (nullptr, ICP_ENODEVICE, "icp_create: no HIP device visible (the engine has no CPU fallback)");
-    if (device < 0 || device >= count) return fail (nullptr, ICP_EINVAL, "icp_create: device ordinal out of range");
-    hipDeviceProp_t prop;
-    e = hipGetDeviceProperties (&prop, device);
-    if (e != hipSuccess) return fail (nullptr, ICP_EHIP, std::string ("hipGetDeviceProperties: ") + hipGetErrorString (e));
-    if (std::strncmp (prop.gcnArchName, "gfx950", 6) != 0)
-        return fail (nullptr, ICP_ENODEVICE, std::string ("icp_create: device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
+    { int rc = gfx950_device (device, "icp_create"); if (rc) return rc; }
     icp_context *h = new icp_context ();
     h->device = device;
     // Default modes = the benchmarked path: single-pass double moments + squared power start.
     // ICP_AMD_MODE=reference (read here) starts the handle in the reference-order / literal modes instead, whose
     // intermediates restate the reference's arithmetic order; icp_set_reduce_mode / icp_set_power_mode switch later.
-    h->p.rot = rot; h->p.weighted = weighted; h->p.power_mode = ICP_POWER_SQUARED; h->p.fused = ICP_REDUCE_FUSED;
-    h->p.dist_scale = 1.f;
-    { const char *e = std::getenv ("ICP_AMD_MODE"); if (e && (e[0] == 'r' || e[0] == 'R')) { h->p.power_mode = ICP_POWER_LITERAL; h->p.fused = ICP_REDUCE_REFERENCE_ORDER; } }
-    { const char *e = std::getenv ("ICP_AMD_CHAIN"); h->p.chain = !e ? 1 : (e[0] == '1') ? 2 : (e[0] == '0') ? 0 : 1; }   // see icp_chain_supported
+    icp_options &o = h->opt;
+    o.rot = rot; o.weighted = weighted;
+    { const char *e = std::getenv ("ICP_AMD_MODE"); if (e && (e[0] == 'r' || e[0] == 'R')) { o.power_mode = ICP_POWER_LITERAL; o.reduce_mode = ICP_REDUCE_REFERENCE_ORDER; } }
+    { const char *e = std::getenv ("ICP_AMD_CHAIN"); o.chain = !e ? 1 : (e[0] == '1') ? 2 : (e[0] == '0') ? 0 : 1; }   // see icp_chain_supported
+    derive_params (o, h->p);
     { const char *e = std::getenv ("ICP_AMD_RUN_ADAPTIVE"); if (e && e[0] == '0') h->run_adaptive = 0; }                  // see run_ctl
     { const char *e = std::getenv ("ICP_AMD_TRACK_GATE"); if (e && e[0] == '0') h->track_gate = 0; }
     { const char *e = std::getenv ("ICP_AMD_OUTPUTS"); if (e && (e[0] == 'e' || e[0] == 'E')) h->outputs_lazy = 0; }
     { const char *e = std::getenv ("ICP_AMD_RUN_DEPTH"); if (e) { const int d = std::atoi (e); if (d >= 1 && d <= 64) h->run_depth = (uint32_t) d; } }
-    e = hipSetDevice (device);
+    hipError_t e = hipSetDevice (device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags (&h->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipStreamCreateWithFlags (&h->copy_stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreate (&h->ev0);
@@ -181,40 +283,6 @@ int icp_destroy (icp_handle h) try
 }
 ICP_CATCH_ALL
 
-// colored ICP's kappa -> its device word (icp_color_kappa), in stream order behind whatever the handle's stream holds
-static int write_color_kappa (icp_context *h)
-{
-    uint32_t bits; std::memcpy (&bits, &h->color_kappa, sizeof bits);
-    HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (icp_color_kappa (h->p)), (int) bits, 1, h->stream));
-    return ICP_OK;
-}
-
-// the robust loss's scale k -> its device word (icp_robust_scale), in stream order like kappa's (0 while the loss is off)
-static int write_robust_scale (icp_context *h)
-{
-    uint32_t bits; std::memcpy (&bits, &h->robust_scale, sizeof bits);
-    HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (icp_robust_scale (h->p)), (int) bits, 1, h->stream));
-    return ICP_OK;
-}
-
-// plane-to-plane's epsilon -> its device word (icp_gicp_eps), in stream order like kappa's (0 while it is off)
-static int write_gicp_eps (icp_context *h)
-{
-    uint32_t bits; std::memcpy (&bits, &h->gicp_eps, sizeof bits);
-    HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (icp_gicp_eps (h->p)), (int) bits, 1, h->stream));
-    return ICP_OK;
-}
-
-// the pair filter's settings -> their device words (icp_pair_filter_settings: min_cos, the grid width), in stream order like kappa's
-static int write_pair_filter_settings (icp_context *h)
-{
-    uint32_t bits; std::memcpy (&bits, &h->normal_min_cos, sizeof bits);
-    uint32_t *w = icp_pair_filter_settings (h->p);
-    HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (w), (int) bits, 1, h->stream));
-    HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (w + 1), (int) h->boundary_gw, 1, h->stream));
-    return ICP_OK;
-}
-
 // plane-to-plane, symmetric or normal rejection with ICP_NORMALS_GRID: the moving normals of registrations b0 .. b0 + nb - 1 follow a new M, in stream order behind its copy
 // (a width that does not divide m: nothing — icp_build_rbc refuses the handle anyway)
 static void normals_m_follow (icp_context *h, uint32_t b0, uint32_t nb)
@@ -244,17 +312,11 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     if (h->copy_stream) HIPCHK (h, hipStreamSynchronize (h->copy_stream));
     if (h->stream2) HIPCHK (h, hipStreamSynchronize (h->stream2));
     if (h->stream) HIPCHK (h, hipStreamSynchronize (h->stream));
-    int rot = h->p.rot, weighted = h->p.weighted, pmode = h->p.power_mode, fused = h->p.fused, chain = h->p.chain;
-    const float dist_scale = h->p.dist_scale;
-    const uint32_t reject = h->p.reject; const float reject_d2 = h->p.reject_d2, reject_max_dist = h->p.reject_max_dist, trim_keep = h->p.trim_keep;
-    const uint32_t metric = h->p.metric, nrm_grid = h->p.nrm_grid, gicp = h->p.gicp; const float p2pl_mu = h->p.p2pl_mu;
     free_all (h);
     icp_params &p = h->p;
     p = icp_params {};
-    p.rot = rot; p.weighted = weighted; p.power_mode = pmode; p.check = 0; p.fused = fused; p.chain = chain; p.emit = 1;
-    p.dist_scale = dist_scale;
-    p.reject = reject; p.reject_d2 = reject_d2; p.reject_max_dist = reject_max_dist; p.trim_keep = trim_keep;
-    p.metric = metric; p.nrm_grid = nrm_grid; p.p2pl_mu = p2pl_mu; p.gicp = gicp;
+    derive_params (h->opt, p);
+    p.check = 0; p.emit = 1;
     p.m = m; p.nr = nr; p.batch = batch; p.side = side; p.nrx = nrx; p.nry = nry;
     p.a = a; p.c = c;
     {   // division-free cell lookups in the kernels (reps_grid guarantees a square grid that the representative grid tiles)
@@ -310,14 +372,10 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     if ((rc = dalloc (h, &p.mpart, B * 2 * p.nwg))) return rc;
     if ((rc = dalloc (h, &p.mscr, B * 2 * ((p.nwg + 127u) / 128u)))) return rc;
     if ((rc = dalloc (h, &p.spart, B * 11 * p.nsp * 8))) return rc;    // 8 sub-trees per work-group; padding stays 0.f
-    // (behind the moments, icp_mom_layout: trimming's words, the plane system and its block partials, the words of kappa and of the
-    // robust loss's scale (written below);
-    // zeroed: ICP_MEM_TRIM and ICP_MEM_PLANE_SYSTEM read 0 until an iteration has written them, and the histograms and counters start clear)
+    // (behind the moments, icp_mom_layout: trimming's words, the plane system and its block partials, the device words of the
+    // settings (written below); zeroed: ICP_MEM_TRIM and ICP_MEM_PLANE_SYSTEM read 0 until an iteration has written them, and the histograms and counters start clear)
     if ((rc = dalloc (h, &p.mom, icp_mom_layout_of (batch, m, p.nb).total))) return rc;
-    if ((rc = write_color_kappa (h))) return rc;
-    if ((rc = write_robust_scale (h))) return rc;
-    if ((rc = write_gicp_eps (h))) return rc;
-    if ((rc = write_pair_filter_settings (h))) return rc;
+    if ((rc = write_words (h, OPT_WORDS))) return rc;
     // (one-to-one correspondences: the claim table reads all-ones between iterations — icp_unique.hip)
     HIPCHK (h, hipMemsetAsync (icp_unique_claims (p), 0xFF, sizeof (unsigned long long) * B * m, h->stream));
     if ((rc = dalloc (h, &p.ml1, B * 18 * ((p.nb + 127u) / 128u)))) return rc;
@@ -347,6 +405,46 @@ int icp_init (icp_handle h, uint32_t m, uint32_t nr, float a, float c, uint32_t 
     return icp_init_batched (h, 1, m, nr, a, c, max_iterations, angle_threshold, translation_threshold);
 }
 ICP_CATCH_ALL
+
+// A memory object of registration b: where it lives on the device, its full size (0: no such object) and, where icp_write takes it as a
+// plain copy of m x 16 bytes from the caller's memory, its name (else nullptr).  icp_mem_size, icp_read, icp_device_ptr and icp_write go by it.
+struct mem_desc { const void *ptr; size_t bytes; const char *plain_write; };
+static mem_desc mem_of (const icp_context *h, uint32_t b, int mem)
+{
+    const icp_params &p = h->p;
+    const size_t m = p.m, nr = p.nr;
+    const char *st = reinterpret_cast<const char *> (p.st + b);
+    switch (mem) {
+        case ICP_MEM_F: return { h->dF + b * m * 8, m * 32, nullptr };
+        case ICP_MEM_M: return { h->dM + b * m * 8, m * 32, nullptr };
+        case ICP_MEM_RBC_XP: return { p.XP + b * m * 8, m * 32, nullptr };
+        case ICP_MEM_T: return { st + offsetof (icp_reg_state, T), 32, nullptr };
+        case ICP_MEM_TK: return { st + offsetof (icp_reg_state, Tk), 32, nullptr };
+        case ICP_MEM_MEANS: return { st + offsetof (icp_reg_state, means), 32, nullptr };
+        case ICP_MEM_S: return { st + offsetof (icp_reg_state, S), 44, nullptr };
+        case ICP_MEM_SUM_W: return { st + offsetof (icp_reg_state, sum_w), 8, nullptr };
+        case ICP_MEM_R: return { st + offsetof (icp_reg_state, R), 36, nullptr };
+        case ICP_MEM_RK: return { st + offsetof (icp_reg_state, Rk), 36, nullptr };
+        case ICP_MEM_NN_ID: return { p.nn_id + b * m, m * 8, nullptr };
+        case ICP_MEM_RBC_PERM: return { p.perm + b * m, m * 4, nullptr };
+        case ICP_MEM_RBC_OWNER: return { p.owner + b * m, m * 4, nullptr };
+        case ICP_MEM_RID: return { p.rid + b * m, m * 4, nullptr };
+        case ICP_MEM_REPS: return { p.R + b * nr * 8, nr * 32, nullptr };
+        case ICP_MEM_RBC_N: return { ICP_N_FULL (p, b), nr * 4, nullptr };
+        case ICP_MEM_RBC_O: return { p.O + b * nr, nr * 4, nullptr };
+        case ICP_MEM_NN: return { p.PF + b * m, m * 16, nullptr };
+        case ICP_MEM_QT: return { p.PM + b * m, m * 16, nullptr };
+        case ICP_MEM_W: return { reinterpret_cast<const float *> (p.PF + b * m) + 3, m * 4, nullptr };    // (the .w lane of the matched points: a strided read)
+        case ICP_MEM_TRIM: return { icp_trim_area (p) + 4u * b, 16, nullptr };
+        case ICP_MEM_UNIQUE: return { icp_unique_area (p) + 4u * b + 1u, 8, nullptr };
+        case ICP_MEM_PAIR_FILTER: return { icp_pair_filter_area (p) + 4u * b, 16, nullptr };
+        case ICP_MEM_NORMALS_F: return { icp_normals_f (p) + b * m, m * 16, "ICP_MEM_NORMALS_F" };
+        case ICP_MEM_COLOR_GRAD_F: return { icp_color_grad_f (p) + b * m, m * 16, "ICP_MEM_COLOR_GRAD_F" };
+        case ICP_MEM_NORMALS_M: return { icp_normals_m (p) + b * m, m * 16, "ICP_MEM_NORMALS_M" };
+        case ICP_MEM_PLANE_SYSTEM: return { icp_p2pl_area (p) + (size_t) ICP_P2PL_SYS * b, ICP_P2PL_SYS * sizeof (double), nullptr };
+        default: return { nullptr, 0, nullptr };
+    }
+}
 
 int icp_write_b (icp_handle h, uint32_t b, int mem, const void *host_ptr, int block) try
 {
@@ -381,33 +479,17 @@ int icp_write_b (icp_handle h, uint32_t b, int mem, const void *host_ptr, int bl
             HIPCHK (h, hipGetLastError ());
             break;
         }
-        case ICP_MEM_NORMALS_F: {
-            // (point-to-plane normals, ICP_NORMALS_GIVEN: small and rare — a blocking copy from the caller's memory; the stream is
-            // ordered in front of it, so the iterations queued before this read the normals they were queued with)
-            if (!host_ptr) return fail (h, ICP_EINVAL, "icp_write: ICP_MEM_NORMALS_F needs a source");
+        default: {
+            // (the fixed normals, colored ICP's intensity gradients, the moving normals, ICP_NORMALS_GIVEN: small and rare — a blocking copy
+            // from the caller's memory; the stream is ordered in front of it, so the iterations queued before this read what they were queued with)
+            const mem_desc d = mem_of (h, b, mem);
+            if (!d.plain_write)
+                return fail (h, ICP_EINVAL, "icp_write: mem must be ICP_MEM_F, ICP_MEM_M, ICP_MEM_T, ICP_MEM_NORMALS_F, ICP_MEM_COLOR_GRAD_F or ICP_MEM_NORMALS_M");
+            if (!host_ptr) return fail (h, ICP_EINVAL, std::string ("icp_write: ") + d.plain_write + " needs a source");
             note_inputs_change (h);
             HIPCHK (h, hipStreamSynchronize (h->stream));
-            HIPCHK (h, hipMemcpy (icp_normals_f (h->p) + (size_t) b * h->p.m, host_ptr, (size_t) h->p.m * 16, hipMemcpyHostToDevice));
-            break;
+            HIPCHK (h, hipMemcpy (const_cast<void *> (d.ptr), host_ptr, d.bytes, hipMemcpyHostToDevice));
         }
-        case ICP_MEM_COLOR_GRAD_F: {
-            // (colored ICP's intensity gradients, ICP_NORMALS_GIVEN: as ICP_MEM_NORMALS_F)
-            if (!host_ptr) return fail (h, ICP_EINVAL, "icp_write: ICP_MEM_COLOR_GRAD_F needs a source");
-            note_inputs_change (h);
-            HIPCHK (h, hipStreamSynchronize (h->stream));
-            HIPCHK (h, hipMemcpy (icp_color_grad_f (h->p) + (size_t) b * h->p.m, host_ptr, (size_t) h->p.m * 16, hipMemcpyHostToDevice));
-            break;
-        }
-        case ICP_MEM_NORMALS_M: {
-            // (plane-to-plane's moving normals, ICP_NORMALS_GIVEN: as ICP_MEM_NORMALS_F)
-            if (!host_ptr) return fail (h, ICP_EINVAL, "icp_write: ICP_MEM_NORMALS_M needs a source");
-            note_inputs_change (h);
-            HIPCHK (h, hipStreamSynchronize (h->stream));
-            HIPCHK (h, hipMemcpy (icp_normals_m (h->p) + (size_t) b * h->p.m, host_ptr, (size_t) h->p.m * 16, hipMemcpyHostToDevice));
-            break;
-        }
-        default:
-            return fail (h, ICP_EINVAL, "icp_write: mem must be ICP_MEM_F, ICP_MEM_M, ICP_MEM_T, ICP_MEM_NORMALS_F, ICP_MEM_COLOR_GRAD_F or ICP_MEM_NORMALS_M");
     }
     if (block) HIPCHK (h, hipStreamSynchronize (h->stream));
     return ICP_OK;
@@ -416,66 +498,7 @@ ICP_CATCH_ALL
 
 int icp_write (icp_handle h, int mem, const void *host_ptr, int block) try { api_guard guard_ (h); return icp_write_b (h, 0, mem, host_ptr, block); } ICP_CATCH_ALL
 
-size_t icp_mem_size (icp_handle h, int mem)
-{
-    if (!h || !h->inited) return 0;
-    const icp_params &p = h->p;
-    switch (mem) {
-        case ICP_MEM_F: case ICP_MEM_M: case ICP_MEM_RBC_XP: return (size_t) p.m * 32;
-        case ICP_MEM_T: case ICP_MEM_TK: case ICP_MEM_MEANS: return 32;
-        case ICP_MEM_S: return 44;
-        case ICP_MEM_NN_ID: return (size_t) p.m * 8;
-        case ICP_MEM_W: case ICP_MEM_RBC_PERM: case ICP_MEM_RBC_OWNER: case ICP_MEM_RID: return (size_t) p.m * 4;
-        case ICP_MEM_SUM_W: return 8;
-        case ICP_MEM_REPS: return (size_t) p.nr * 32;
-        case ICP_MEM_RBC_N: case ICP_MEM_RBC_O: return (size_t) p.nr * 4;
-        case ICP_MEM_R: case ICP_MEM_RK: return 36;
-        case ICP_MEM_NN: case ICP_MEM_QT: return (size_t) p.m * 16;
-        case ICP_MEM_TRIM: return 16;
-        case ICP_MEM_UNIQUE: return 8;
-        case ICP_MEM_PAIR_FILTER: return 16;
-        case ICP_MEM_NORMALS_F: case ICP_MEM_COLOR_GRAD_F: case ICP_MEM_NORMALS_M: return (size_t) p.m * 16;
-        case ICP_MEM_PLANE_SYSTEM: return ICP_P2PL_SYS * sizeof (double);
-        default: return 0;
-    }
-}
-
-static int mem_ptr (icp_context *h, uint32_t b, int mem, const void **src)
-{
-    const icp_params &p = h->p;
-    const char *st = reinterpret_cast<const char *> (p.st + b);
-    switch (mem) {
-        case ICP_MEM_F: *src = h->dF + (size_t) b * p.m * 8; break;
-        case ICP_MEM_M: *src = h->dM + (size_t) b * p.m * 8; break;
-        case ICP_MEM_RBC_XP: *src = p.XP + (size_t) b * p.m * 8; break;
-        case ICP_MEM_T: *src = st + offsetof (icp_reg_state, T); break;
-        case ICP_MEM_TK: *src = st + offsetof (icp_reg_state, Tk); break;
-        case ICP_MEM_MEANS: *src = st + offsetof (icp_reg_state, means); break;
-        case ICP_MEM_S: *src = st + offsetof (icp_reg_state, S); break;
-        case ICP_MEM_SUM_W: *src = st + offsetof (icp_reg_state, sum_w); break;
-        case ICP_MEM_R: *src = st + offsetof (icp_reg_state, R); break;
-        case ICP_MEM_RK: *src = st + offsetof (icp_reg_state, Rk); break;
-        case ICP_MEM_NN_ID: *src = p.nn_id + (size_t) b * p.m; break;
-        case ICP_MEM_RBC_PERM: *src = p.perm + (size_t) b * p.m; break;
-        case ICP_MEM_RBC_OWNER: *src = p.owner + (size_t) b * p.m; break;
-        case ICP_MEM_RID: *src = p.rid + (size_t) b * p.m; break;
-        case ICP_MEM_REPS: *src = p.R + (size_t) b * p.nr * 8; break;
-        case ICP_MEM_RBC_N: *src = ICP_N_FULL (p, b); break;
-        case ICP_MEM_RBC_O: *src = p.O + (size_t) b * p.nr; break;
-        case ICP_MEM_NN: *src = p.PF + (size_t) b * p.m; break;
-        case ICP_MEM_QT: *src = p.PM + (size_t) b * p.m; break;
-        case ICP_MEM_W: *src = reinterpret_cast<const float *> (p.PF + (size_t) b * p.m) + 3; break;
-        case ICP_MEM_TRIM: *src = icp_trim_area (p) + 4u * b; break;
-        case ICP_MEM_UNIQUE: *src = icp_unique_area (p) + 4u * b + 1u; break;
-        case ICP_MEM_PAIR_FILTER: *src = icp_pair_filter_area (p) + 4u * b; break;
-        case ICP_MEM_NORMALS_F: *src = icp_normals_f (p) + (size_t) b * p.m; break;
-        case ICP_MEM_COLOR_GRAD_F: *src = icp_color_grad_f (p) + (size_t) b * p.m; break;
-        case ICP_MEM_NORMALS_M: *src = icp_normals_m (p) + (size_t) b * p.m; break;
-        case ICP_MEM_PLANE_SYSTEM: *src = icp_p2pl_area (p) + (size_t) ICP_P2PL_SYS * b; break;
-        default: return fail (h, ICP_EINVAL, "unknown icp_mem value");
-    }
-    return ICP_OK;
-}
+size_t icp_mem_size (icp_handle h, int mem) { return h && h->inited ? mem_of (h, 0, mem).bytes : 0; }
 
 int icp_read_b (icp_handle h, uint32_t b, int mem, void *host_dst, size_t bytes) try
 {
@@ -483,12 +506,11 @@ int icp_read_b (icp_handle h, uint32_t b, int mem, void *host_dst, size_t bytes)
     int rc = need (h, false); if (rc) return rc;
     if (!host_dst) return fail (h, ICP_EINVAL, "icp_read: null destination");
     if (b >= h->p.batch) return fail (h, ICP_EINVAL, "batch index out of range");
-    size_t full = icp_mem_size (h, mem);
-    if (full == 0) return fail (h, ICP_EINVAL, "unknown icp_mem value");
-    if (bytes > full) return fail (h, ICP_EINVAL, "icp_read: more bytes requested than the object holds");
+    const mem_desc d = mem_of (h, b, mem);
+    if (!d.bytes) return fail (h, ICP_EINVAL, "unknown icp_mem value");
+    if (bytes > d.bytes) return fail (h, ICP_EINVAL, "icp_read: more bytes requested than the object holds");
     if ((rc = set_device (h))) return rc;
-    const void *src = nullptr;
-    if ((rc = mem_ptr (h, b, mem, &src))) return rc;
+    const void *src = d.ptr;
     if ((rc = materialize_outputs (h, mem))) return rc;
     if (mem == ICP_MEM_W) {                        // weights live in the .w lane of the matched points
         size_t rows = bytes / 4;
@@ -507,11 +529,11 @@ int icp_device_ptr (icp_handle h, int mem, void **dptr) try
     api_guard guard_ (h);
     int rc = need (h, false); if (rc) return rc;
     if (!dptr) return fail (h, ICP_EINVAL, "null pointer");
-    const void *src = nullptr;
-    if ((rc = mem_ptr (h, 0, mem, &src))) return rc;
+    const mem_desc d = mem_of (h, 0, mem);
+    if (!d.bytes) return fail (h, ICP_EINVAL, "unknown icp_mem value");
     if ((rc = set_device (h))) return rc;
     if ((rc = materialize_outputs (h, mem))) return rc;
-    *dptr = const_cast<void *> (src);
+    *dptr = const_cast<void *> (d.ptr);
     return ICP_OK;
 }
 ICP_CATCH_ALL
@@ -537,7 +559,7 @@ int icp_build_rbc (icp_handle h) try
     if ((rc = set_device (h))) return rc;
     if (h->p.nrm_grid && h->p.m % h->p.nrm_grid)
         return fail (h, ICP_ESTATE, "icp_build_rbc: ICP_NORMALS_GRID: m is not a multiple of the grid width");
-    if (h->boundary_gw && h->p.m % h->boundary_gw)
+    if (h->opt.boundary_gw && h->p.m % h->opt.boundary_gw)
         return fail (h, ICP_ESTATE, "icp_build_rbc: icp_set_boundary_rejection: m is not a multiple of the grid width");
     note_inputs_change (h);
     // The two (latency-bound sizes) to six launches of the construction are enqueued as they are: a graph of so few nodes costs more
@@ -723,151 +745,97 @@ int icp_set_metric_scale (icp_handle h, float f_g) try
     if (!h) return ICP_EINVAL;
     if (!(f_g > 0.f) || !std::isfinite (f_g)) return fail (h, ICP_EINVAL, "the metric scale must be positive and finite");
     { int rc = outputs_before_change (h); if (rc) return rc; }
-    h->p.dist_scale = f_g; ++h->param_gen; return ICP_OK;
+    h->opt.metric_scale = f_g;
+    return commit (h, OPT_PARAMS);
 }
 ICP_CATCH_ALL
-int icp_get_metric_scale (icp_handle h, float *f_g) try { api_guard guard_ (h); if (!h || !f_g) return ICP_EINVAL; *f_g = h->p.dist_scale; return ICP_OK; } ICP_CATCH_ALL
-// correspondence rejection (include/icp_amd.h): the weights of the pairs change, the search does not — the same route as the metric's scale
-// (graphs of the handle are updated in place with the new parameters)
+int icp_get_metric_scale (icp_handle h, float *f_g) try { api_guard guard_ (h); if (!h || !f_g) return ICP_EINVAL; *f_g = h->opt.metric_scale; return ICP_OK; } ICP_CATCH_ALL
+// The opt-in settings (include/icp_amd.h).  Each setter validates its arguments, reproduces lazy outputs where the change would alter
+// them (outputs_before_change), updates the record (icp_options) and commits.
+// correspondence rejection: the weights of the pairs change, the search does not — a parameter update, as the metric's scale
 int icp_set_rejection (icp_handle h, int flags, float max_dist) try
 {
-    static_assert (ICP_REJECT_INVALID == 1 && !(ICP_REJECT_INVALID & ICP_REJECT_DIST_ON), "ks_epilogue tests bit 0");
     api_guard guard_ (h);
-    if (flags & ~ICP_REJECT_INVALID) return fail (h, ICP_EINVAL, "icp_set_rejection: unknown flag bits");
+    if (flags & ~reject_user_flags) return fail (h, ICP_EINVAL, "icp_set_rejection: unknown flag bits");
     if (!(max_dist >= 0.f)) return fail (h, ICP_EINVAL, "icp_set_rejection: max_dist must be >= 0 (0 or +inf: no distance test)");
     if (!h) return fail (h, ICP_EINVAL, "icp_set_rejection: null handle");
     { int rc = outputs_before_change (h); if (rc) return rc; }
-    const bool dist = max_dist > 0.f && !std::isinf (max_dist);
-    h->p.reject = (uint32_t) flags | (dist ? ICP_REJECT_DIST_ON : 0u) | (h->p.reject & (ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON | ICP_REJECT_FILTER_MASK));
-    h->p.reject_max_dist = max_dist;
-    h->p.reject_d2 = dist ? (float) ((double) max_dist * (double) max_dist) : 0.f;     // (the product of two floats is exact in double)
-    ++h->param_gen; return ICP_OK;
+    h->opt.reject_flags = flags; h->opt.reject_max_dist = max_dist;
+    return commit (h, OPT_PARAMS);
 }
 ICP_CATCH_ALL
 int icp_get_rejection (icp_handle h, int *flags, float *max_dist) try
 {
     api_guard guard_ (h);
     if (!h) return ICP_EINVAL;
-    if (flags) *flags = (int) (h->p.reject & ~(ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON | ICP_REJECT_FILTER_MASK));
-    if (max_dist) *max_dist = h->p.reject_max_dist;
+    if (flags) *flags = h->opt.reject_flags;
+    if (max_dist) *max_dist = h->opt.reject_max_dist;
     return ICP_OK;
 }
 ICP_CATCH_ALL
-// trimmed ICP (include/icp_amd.h, icp_trim.hip).  On <-> off changes which kernels run — the REJ search, select and apply, no chained form —:
-// the route of icp_set_reduce_mode (graphs captured anew).  A new fraction while trimming stays on is a parameter update.
+// trimmed ICP (icp_trim.hip).  On <-> off changes which kernels run — the REJ search, select and apply, no chained form —: a change of
+// route.  A new fraction while trimming stays on is a parameter update.
 int icp_set_trimming (icp_handle h, float keep_fraction) try
 {
     api_guard guard_ (h);
     if (!(keep_fraction > 0.f && keep_fraction <= 1.f)) return fail (h, ICP_EINVAL, "icp_set_trimming: keep_fraction must be in (0, 1] (1: off)");
     if (!h) return fail (h, ICP_EINVAL, "icp_set_trimming: null handle");
     { int rc = outputs_before_change (h); if (rc) return rc; }
-    const bool on = keep_fraction < 1.f;
-    if (on == icp_trimming (h->p)) {
-        if (on) { h->p.trim_keep = keep_fraction; ++h->param_gen; }
-        return ICP_OK;
-    }
-    if (on) { h->p.reject |= ICP_REJECT_TRIM_ON; h->p.trim_keep = keep_fraction; }
-    else {
-        h->p.reject &= ~ICP_REJECT_TRIM_ON; h->p.trim_keep = 0.f;
-        if (h->inited) {                                                 // ICP_MEM_TRIM reads zeros while trimming is off
-            int rc = set_device (h); if (rc) return rc;
-            if ((rc = run_close_all (h))) return rc;
-            HIPCHK (h, hipMemsetAsync (icp_trim_area (h->p), 0, sizeof (uint32_t) * 4u * h->p.batch, h->stream));
-        }
-    }
-    drop_graphs (h);
-    return ICP_OK;
+    const bool was = h->opt.trim_keep < 1.f, on = keep_fraction < 1.f;
+    h->opt.trim_keep = keep_fraction;
+    return commit (h, on != was ? OPT_ROUTE : on ? OPT_PARAMS : 0u);
 }
 ICP_CATCH_ALL
 int icp_get_trimming (icp_handle h, float *keep_fraction) try
 {
     api_guard guard_ (h);
     if (!h || !keep_fraction) return ICP_EINVAL;
-    *keep_fraction = icp_trimming (h->p) ? h->p.trim_keep : 1.f;
+    *keep_fraction = h->opt.trim_keep;
     return ICP_OK;
 }
 ICP_CATCH_ALL
-// one-to-one correspondences (include/icp_amd.h, icp_unique.hip).  On <-> off changes which kernels run — the REJ search, claim and
-// resolve, on point-to-point the apply pass, no chained form —: the route of icp_set_trimming (graphs captured anew).
+// one-to-one correspondences (icp_unique.hip).  On <-> off changes which kernels run — the REJ search, claim and resolve, on
+// point-to-point the apply pass, no chained form —: a change of route.
 int icp_set_unique (icp_handle h, int on) try
 {
-    static_assert (!(ICP_REJECT_UNIQUE_ON & (ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_INVALID)), "the rule's bit is its own");
     api_guard guard_ (h);
     if (on != 0 && on != 1) return fail (h, ICP_EINVAL, "icp_set_unique: on must be 0 or 1");
     if (!h) return fail (h, ICP_EINVAL, "icp_set_unique: null handle");
     { int rc = outputs_before_change (h); if (rc) return rc; }
-    if ((on != 0) == icp_unique (h->p)) return ICP_OK;
-    if (on) h->p.reject |= ICP_REJECT_UNIQUE_ON;
-    else {
-        h->p.reject &= ~ICP_REJECT_UNIQUE_ON;
-        if (h->inited) {                                                 // ICP_MEM_UNIQUE reads zeros while the rule is off
-            int rc = set_device (h); if (rc) return rc;
-            if ((rc = run_close_all (h))) return rc;
-            HIPCHK (h, hipMemsetAsync (icp_unique_area (h->p), 0, sizeof (uint32_t) * 4u * h->p.batch, h->stream));
-        }
-    }
-    drop_graphs (h);
-    return ICP_OK;
+    const bool was = h->opt.unique;
+    h->opt.unique = on != 0;
+    return commit (h, h->opt.unique != was ? OPT_ROUTE : 0u);
 }
 ICP_CATCH_ALL
 int icp_get_unique (icp_handle h, int *on) try
 {
     api_guard guard_ (h);
     if (!h || !on) return ICP_EINVAL;
-    *on = icp_unique (h->p) ? 1 : 0;
+    *on = h->opt.unique ? 1 : 0;
     return ICP_OK;
 }
 ICP_CATCH_ALL
-// boundary and normal rejection (include/icp_amd.h, icp_pair_filter.hip).  A rule on <-> off changes which kernels run — the REJ search,
-// k_pair_filter, on point-to-point the apply pass, no chained form —: the route of icp_set_trimming (graphs captured anew; a new width
-// too).  A new min_cos while the normal rule stays on goes to its device word, as kappa does (icp_set_color_weight): no graph is touched.
-static int pair_filter_switched (icp_context *h)
-{
-    if (h->inited) {
-        int rc = set_device (h); if (rc) return rc;
-        if ((rc = run_close_all (h))) return rc;
-        if ((rc = write_pair_filter_settings (h))) return rc;
-        if (!icp_pair_filter (h->p))                                     // ICP_MEM_PAIR_FILTER reads zeros while both rules are off
-            HIPCHK (h, hipMemsetAsync (icp_pair_filter_area (h->p), 0, sizeof (uint32_t) * 8u * h->p.batch, h->stream));
-        HIPCHK (h, hipStreamSynchronize (h->stream));
-    }
-    drop_graphs (h);
-    return ICP_OK;
-}
+// boundary and normal rejection (icp_pair_filter.hip).  A rule on <-> off changes which kernels run — the REJ search, k_pair_filter, on
+// point-to-point the apply pass, no chained form —: a change of route (a new width too).  A new min_cos while the normal rule stays on
+// goes to its device word alone: no graph is touched.
 int icp_set_normal_rejection (icp_handle h, int on, float min_cos) try
 {
-    static_assert (!(ICP_REJECT_FILTER_MASK & (ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON | ICP_REJECT_INVALID)), "the rules' bits are their own");
     api_guard guard_ (h);
     if (on != 0 && on != 1) return fail (h, ICP_EINVAL, "icp_set_normal_rejection: on must be 0 or 1");
     if (!(min_cos >= -1.f && min_cos <= 1.f)) return fail (h, ICP_EINVAL, "icp_set_normal_rejection: min_cos must be in [-1, 1]");
     if (!h) return fail (h, ICP_EINVAL, "icp_set_normal_rejection: null handle");
     { int rc = outputs_before_change (h); if (rc) return rc; }
-    const bool was = (h->p.reject & ICP_REJECT_NORMAL_ON) != 0u;
-    h->normal_min_cos = on ? min_cos : 0.f;
-    if ((on != 0) == was) {
-        if (on && h->inited) {                                           // (a new threshold: the device word alone)
-            int rc = set_device (h); if (rc) return rc;
-            if ((rc = run_close_all (h))) return rc;
-            if ((rc = write_pair_filter_settings (h))) return rc;
-            HIPCHK (h, hipStreamSynchronize (h->stream));
-        }
-        return ICP_OK;
-    }
-    if (on) {
-        // (grid normals: the last buildRBC computed no moving normals — the next run needs a new one, as after a new F)
-        if (!icp_moving_normals (h->p) && h->p.nrm_grid) h->built = false;
-        h->p.reject |= ICP_REJECT_NORMAL_ON;
-    }
-    else h->p.reject &= ~ICP_REJECT_NORMAL_ON;
-    return pair_filter_switched (h);
+    const bool was = h->opt.normal_on;
+    h->opt.normal_on = on != 0; h->opt.normal_min_cos = on ? min_cos : 0.f;
+    return commit (h, h->opt.normal_on != was ? OPT_ROUTE | OPT_W_MIN_COS : on ? OPT_W_MIN_COS : 0u);
 }
 ICP_CATCH_ALL
 int icp_get_normal_rejection (icp_handle h, int *on, float *min_cos) try
 {
     api_guard guard_ (h);
     if (!h) return ICP_EINVAL;
-    if (on) *on = (h->p.reject & ICP_REJECT_NORMAL_ON) ? 1 : 0;
-    if (min_cos) *min_cos = h->normal_min_cos;
+    if (on) *on = h->opt.normal_on ? 1 : 0;
+    if (min_cos) *min_cos = h->opt.normal_min_cos;
     return ICP_OK;
 }
 ICP_CATCH_ALL
@@ -877,125 +845,90 @@ int icp_set_boundary_rejection (icp_handle h, uint32_t grid_width) try
     if (!h) return fail (h, ICP_EINVAL, "icp_set_boundary_rejection: null handle");
     if (grid_width && h->inited && h->p.m % grid_width) return fail (h, ICP_ESTATE, "icp_set_boundary_rejection: m is not a multiple of the grid width");
     { int rc = outputs_before_change (h); if (rc) return rc; }
-    if (grid_width == h->boundary_gw) return ICP_OK;
-    h->boundary_gw = grid_width;
-    if (grid_width) h->p.reject |= ICP_REJECT_BOUNDARY_ON; else h->p.reject &= ~ICP_REJECT_BOUNDARY_ON;
-    return pair_filter_switched (h);
+    if (grid_width == h->opt.boundary_gw) return ICP_OK;
+    h->opt.boundary_gw = grid_width;
+    return commit (h, OPT_ROUTE | OPT_W_GRID);
 }
 ICP_CATCH_ALL
 int icp_get_boundary_rejection (icp_handle h, uint32_t *grid_width) try
 {
     api_guard guard_ (h);
     if (!h || !grid_width) return ICP_EINVAL;
-    *grid_width = h->boundary_gw;
+    *grid_width = h->opt.boundary_gw;
     return ICP_OK;
 }
 ICP_CATCH_ALL
-// robust loss (include/icp_amd.h; icp_trim.hip, icp_p2pl.hip).  On <-> off and a new kind change which kernels run — point-to-point: the
-// REJ search and the apply pass, no chained form; the plane metrics: other moments —: the route of icp_set_trimming (graphs captured
-// anew).  A new scale while the loss stays on goes to its device word, as kappa does (icp_set_color_weight): no graph is touched.
+// robust loss (icp_trim.hip, icp_p2pl.hip).  On <-> off and a new kind change which kernels run — point-to-point: the REJ search and
+// the apply pass, no chained form; the plane metrics: other moments —: a change of route.  A new scale while the loss stays on goes to
+// its device word alone: no graph is touched.
 int icp_set_robust_loss (icp_handle h, int loss, float scale) try
 {
     api_guard guard_ (h);
-    static_assert (ICP_ROBUST_TUKEY << ICP_REJECT_ROBUST_SHIFT == ICP_REJECT_ROBUST_MASK, "the loss's kind fills the mask's two bits");
-    static_assert (!(ICP_REJECT_ROBUST_MASK & (ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_INVALID)), "the loss's bits are its own");
     if (loss != ICP_ROBUST_NONE && loss != ICP_ROBUST_HUBER && loss != ICP_ROBUST_CAUCHY && loss != ICP_ROBUST_TUKEY)
         return fail (h, ICP_EINVAL, "icp_set_robust_loss: unknown loss");
     if (loss != ICP_ROBUST_NONE && !(scale > 0.f && std::isfinite (scale)))
         return fail (h, ICP_EINVAL, "icp_set_robust_loss: scale must be finite and > 0");
     if (!h) return fail (h, ICP_EINVAL, "icp_set_robust_loss: null handle");
     { int rc = outputs_before_change (h); if (rc) return rc; }
-    const uint32_t kind = (uint32_t) loss;
-    const float k = loss != ICP_ROBUST_NONE ? scale : 0.f;
-    const bool reroute = kind != icp_robust (h->p);
-    h->robust_scale = k;
-    h->p.reject = (h->p.reject & ~ICP_REJECT_ROBUST_MASK) | (kind << ICP_REJECT_ROBUST_SHIFT);
-    if (h->inited) {
-        int rc = set_device (h); if (rc) return rc;
-        if ((rc = run_close_all (h))) return rc;
-        if ((rc = write_robust_scale (h))) return rc;
-        HIPCHK (h, hipStreamSynchronize (h->stream));
-    }
-    if (reroute) drop_graphs (h);
-    return ICP_OK;
+    const int was = h->opt.robust;
+    h->opt.robust = loss; h->opt.robust_scale = loss != ICP_ROBUST_NONE ? scale : 0.f;
+    return commit (h, OPT_W_ROBUST | (loss != was ? OPT_ROUTE : 0u));
 }
 ICP_CATCH_ALL
 int icp_get_robust_loss (icp_handle h, int *loss, float *scale) try
 {
     api_guard guard_ (h);
     if (!h) return ICP_EINVAL;
-    if (loss) *loss = (int) icp_robust (h->p);
-    if (scale) *scale = h->robust_scale;
+    if (loss) *loss = h->opt.robust;
+    if (scale) *scale = h->opt.robust_scale;
     return ICP_OK;
 }
 ICP_CATCH_ALL
-// The two settings that need the moving frame's normals, plane-to-plane and symmetric, share one word of icp_params (p.gicp: 1, 2); the
-// handle keeps what the user set apart (gicp_eps, symmetric), so that need () can name both when they are on together.  A changed word
-// changes which moments kernel a point-to-plane iteration runs and what buildRBC launches: graphs captured anew.
-static void moving_normals_word (icp_context *h)
-{
-    const uint32_t word = h->gicp_eps > 0.f ? 1u : h->symmetric ? ICP_MOVING_NORMALS_SYM : 0u;
-    if (word == h->p.gicp) return;
-    // (grid normals: the last buildRBC computed no moving normals — the next run needs a new one, as after a new F)
-    if (!icp_moving_normals (h->p) && h->p.nrm_grid) h->built = false;
-    h->p.gicp = word;
-    drop_graphs (h);
-}
-// plane-to-plane (include/icp_amd.h, icp_gicp.hip).  On <-> off changes which moments kernel a point-to-plane iteration runs and what
-// buildRBC launches: the route of icp_set_trimming (graphs captured anew).  A new epsilon while it stays on goes to its device word, as
-// kappa does (icp_set_color_weight): no graph is touched.
+// The two settings that need the moving frame's normals, plane-to-plane (icp_gicp.hip) and symmetric (icp_symmetric.hip), share one
+// word of icp_params (moving_normals_word); the record keeps them apart, so that need () can name both when they are on together.  A
+// changed word changes which moments kernel a point-to-plane iteration runs and what buildRBC launches: a change of route.  A new
+// epsilon while plane-to-plane stays on goes to its device word alone: no graph is touched.
 int icp_set_plane_to_plane (icp_handle h, float epsilon) try
 {
     api_guard guard_ (h);
     if (!(epsilon >= 0.f && epsilon <= 1.f)) return fail (h, ICP_EINVAL, "icp_set_plane_to_plane: epsilon must be in [0, 1] (0: off)");
     if (!h) return fail (h, ICP_EINVAL, "icp_set_plane_to_plane: null handle");
     { int rc = outputs_before_change (h); if (rc) return rc; }
-    h->gicp_eps = epsilon;
-    if (h->inited) {
-        int rc = set_device (h); if (rc) return rc;
-        if ((rc = run_close_all (h))) return rc;
-        if ((rc = write_gicp_eps (h))) return rc;
-        HIPCHK (h, hipStreamSynchronize (h->stream));
-    }
-    moving_normals_word (h);
-    return ICP_OK;
+    const uint32_t was = moving_normals_word (h->opt);
+    h->opt.gicp_eps = epsilon;
+    return commit (h, OPT_W_EPS | (moving_normals_word (h->opt) != was ? OPT_ROUTE : 0u));
 }
 ICP_CATCH_ALL
 int icp_get_plane_to_plane (icp_handle h, float *epsilon) try
 {
     api_guard guard_ (h);
     if (!h || !epsilon) return ICP_EINVAL;
-    *epsilon = h->gicp_eps;
+    *epsilon = h->opt.gicp_eps;
     return ICP_OK;
 }
 ICP_CATCH_ALL
-// the symmetric objective (include/icp_amd.h, icp_symmetric.hip): the route of icp_set_plane_to_plane, without a device word
 int icp_set_symmetric (icp_handle h, int on) try
 {
     api_guard guard_ (h);
     if (on != 0 && on != 1) return fail (h, ICP_EINVAL, "icp_set_symmetric: on must be 0 or 1");
     if (!h) return fail (h, ICP_EINVAL, "icp_set_symmetric: null handle");
     { int rc = outputs_before_change (h); if (rc) return rc; }
-    h->symmetric = on != 0;
-    if (h->inited) {
-        int rc = set_device (h); if (rc) return rc;
-        if ((rc = run_close_all (h))) return rc;
-    }
-    moving_normals_word (h);
-    return ICP_OK;
+    const uint32_t was = moving_normals_word (h->opt);
+    h->opt.symmetric = on != 0;
+    return commit (h, OPT_QUIESCE | (moving_normals_word (h->opt) != was ? OPT_ROUTE : 0u));
 }
 ICP_CATCH_ALL
 int icp_get_symmetric (icp_handle h, int *on) try
 {
     api_guard guard_ (h);
     if (!h || !on) return ICP_EINVAL;
-    *on = h->symmetric ? 1 : 0;
+    *on = h->opt.symmetric ? 1 : 0;
     return ICP_OK;
 }
 ICP_CATCH_ALL
-// point-to-plane (include/icp_amd.h, icp_p2pl.hip).  On <-> off changes which kernels run — the moments and the 6 x 6 finalize, no
-// chained form —: the route of icp_set_reduce_mode (graphs captured anew).  A new mu while the metric stays on is a parameter update.
-// Colored ICP is point-to-plane with other moments: POINT_TO_PLANE <-> COLORED changes the kernels too (same route).
+// point-to-plane (icp_p2pl.hip).  On <-> off changes which kernels run — the moments and the 6 x 6 finalize, no chained form —: a
+// change of route.  A new mu while the metric stays on is a parameter update.  Colored ICP is point-to-plane with other moments:
+// POINT_TO_PLANE <-> COLORED changes the kernels too.
 int icp_set_error_metric (icp_handle h, int metric, float point_weight) try
 {
     api_guard guard_ (h);
@@ -1004,59 +937,36 @@ int icp_set_error_metric (icp_handle h, int metric, float point_weight) try
     if (!(point_weight >= 0.f && std::isfinite (point_weight))) return fail (h, ICP_EINVAL, "icp_set_error_metric: point_weight must be finite and >= 0");
     if (!h) return fail (h, ICP_EINVAL, "icp_set_error_metric: null handle");
     { int rc = outputs_before_change (h); if (rc) return rc; }
-    if ((uint32_t) metric == h->p.metric) {
-        if (metric != ICP_METRIC_POINT_TO_POINT) { h->p.p2pl_mu = point_weight; ++h->param_gen; }
-        return ICP_OK;
-    }
-    if (metric != ICP_METRIC_POINT_TO_POINT) {
-        h->p.metric = (uint32_t) metric; h->p.p2pl_mu = point_weight;
-        // (grid normals: the last buildRBC computed no intensity gradients — the next run needs a new one, as after a new F)
-        if (metric == ICP_METRIC_COLORED && h->p.nrm_grid) h->built = false;
-    }
-    else {
-        h->p.metric = 0u; h->p.p2pl_mu = 0.f;
-        if (h->inited) {                                                 // ICP_MEM_PLANE_SYSTEM reads zeros while the metric is off
-            int rc = set_device (h); if (rc) return rc;
-            if ((rc = run_close_all (h))) return rc;
-            HIPCHK (h, hipMemsetAsync (icp_p2pl_area (h->p), 0, sizeof (double) * ICP_P2PL_SYS * h->p.batch, h->stream));
-        }
-    }
-    drop_graphs (h);
-    return ICP_OK;
-}
-ICP_CATCH_ALL
-// kappa lives in a device word the moments read (icp_color_kappa), not in the captured arguments: a new kappa touches no graph.  The
-// word is written in stream order once the open runs have ended, and the stream is drained so that work later enqueued on any of the
-// handle's streams reads the new value.
-int icp_set_color_weight (icp_handle h, float kappa) try
-{
-    api_guard guard_ (h);
-    if (!(kappa >= 0.f && std::isfinite (kappa))) return fail (h, ICP_EINVAL, "icp_set_color_weight: kappa must be finite and >= 0");
-    if (!h) return fail (h, ICP_EINVAL, "icp_set_color_weight: null handle");
-    h->color_kappa = kappa;
-    if (h->inited) {
-        int rc = set_device (h); if (rc) return rc;
-        if ((rc = run_close_all (h))) return rc;
-        if ((rc = write_color_kappa (h))) return rc;
-        HIPCHK (h, hipStreamSynchronize (h->stream));
-    }
-    return ICP_OK;
-}
-ICP_CATCH_ALL
-int icp_get_color_weight (icp_handle h, float *kappa) try
-{
-    api_guard guard_ (h);
-    if (!h || !kappa) return ICP_EINVAL;
-    *kappa = h->color_kappa;
-    return ICP_OK;
+    const int was = h->opt.metric;
+    h->opt.metric = metric; h->opt.p2pl_mu = metric != ICP_METRIC_POINT_TO_POINT ? point_weight : 0.f;
+    return commit (h, metric != was ? OPT_ROUTE : metric != ICP_METRIC_POINT_TO_POINT ? OPT_PARAMS : 0u);
 }
 ICP_CATCH_ALL
 int icp_get_error_metric (icp_handle h, int *metric, float *point_weight) try
 {
     api_guard guard_ (h);
     if (!h) return ICP_EINVAL;
-    if (metric) *metric = (int) h->p.metric;
-    if (point_weight) *point_weight = h->p.p2pl_mu;
+    if (metric) *metric = h->opt.metric;
+    if (point_weight) *point_weight = h->opt.p2pl_mu;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+// kappa lives in a device word the moments read (icp_color_kappa), not in the captured arguments: a new kappa touches no graph, and no
+// search would give other outputs for it (no outputs_before_change).
+int icp_set_color_weight (icp_handle h, float kappa) try
+{
+    api_guard guard_ (h);
+    if (!(kappa >= 0.f && std::isfinite (kappa))) return fail (h, ICP_EINVAL, "icp_set_color_weight: kappa must be finite and >= 0");
+    if (!h) return fail (h, ICP_EINVAL, "icp_set_color_weight: null handle");
+    h->opt.color_kappa = kappa;
+    return commit (h, OPT_W_KAPPA);
+}
+ICP_CATCH_ALL
+int icp_get_color_weight (icp_handle h, float *kappa) try
+{
+    api_guard guard_ (h);
+    if (!h || !kappa) return ICP_EINVAL;
+    *kappa = h->opt.color_kappa;
     return ICP_OK;
 }
 ICP_CATCH_ALL
@@ -1069,16 +979,17 @@ int icp_set_normals (icp_handle h, int source, uint32_t grid_width) try
     if (!h) return fail (h, ICP_EINVAL, "icp_set_normals: null handle");
     const uint32_t w = source == ICP_NORMALS_GRID ? grid_width : 0u;
     if (w && h->inited && h->p.m % w) return fail (h, ICP_ESTATE, "icp_set_normals: m is not a multiple of the grid width");
-    if (w != h->p.nrm_grid) { h->p.nrm_grid = w; drop_graphs (h); }
-    return ICP_OK;
+    if (w == h->opt.nrm_grid) return ICP_OK;
+    h->opt.nrm_grid = w;
+    return commit (h, OPT_ROUTE);
 }
 ICP_CATCH_ALL
 int icp_get_normals (icp_handle h, int *source, uint32_t *grid_width) try
 {
     api_guard guard_ (h);
     if (!h) return ICP_EINVAL;
-    if (source) *source = h->p.nrm_grid ? ICP_NORMALS_GRID : ICP_NORMALS_GIVEN;
-    if (grid_width) *grid_width = h->p.nrm_grid;
+    if (source) *source = h->opt.nrm_grid ? ICP_NORMALS_GRID : ICP_NORMALS_GIVEN;
+    if (grid_width) *grid_width = h->opt.nrm_grid;
     return ICP_OK;
 }
 ICP_CATCH_ALL
@@ -1114,7 +1025,8 @@ int icp_set_power_mode (icp_handle h, int mode) try
     api_guard guard_ (h);
     if (!h) return ICP_EINVAL;
     if (mode != ICP_POWER_LITERAL && mode != ICP_POWER_SQUARED) return fail (h, ICP_EINVAL, "unknown power mode");
-    h->p.power_mode = mode; ++h->param_gen; return ICP_OK;
+    h->opt.power_mode = mode;
+    return commit (h, OPT_PARAMS);
 }
 ICP_CATCH_ALL
 
@@ -1124,7 +1036,8 @@ int icp_set_reduce_mode (icp_handle h, int mode) try
     if (!h) return ICP_EINVAL;
     if (mode != ICP_REDUCE_REFERENCE_ORDER && mode != ICP_REDUCE_FUSED) return fail (h, ICP_EINVAL, "unknown reduce mode");
     { int rc = outputs_before_change (h); if (rc) return rc; }
-    h->p.fused = mode; drop_graphs (h); return ICP_OK;
+    h->opt.reduce_mode = mode;
+    return commit (h, OPT_ROUTE);
 }
 ICP_CATCH_ALL
 
@@ -1162,14 +1075,7 @@ int icp_write_cloud (icp_handle h, int which, const void *cloud, int block) try
     if (!cloud) return fail (h, ICP_EINVAL, "null pointer");
     if ((rc = set_device (h))) return rc;
     const uint32_t n = 640u * 480u;
-    if (h->cloud_cap < n) {
-        if (h->dCloud) (void) hipFree (h->dCloud);
-        if (h->dCloudOut) (void) hipFree (h->dCloudOut);
-        h->dCloud = h->dCloudOut = nullptr; h->cloud_cap = 0;
-        HIPCHK (h, hipMalloc ((void **) &h->dCloud, (size_t) n * 32));
-        HIPCHK (h, hipMalloc ((void **) &h->dCloudOut, (size_t) n * 32));
-        h->cloud_cap = n;
-    }
+    if ((rc = cloud_reserve (h, n))) return rc;
     note_inputs_change (h);
     HIPCHK (h, hipMemcpyAsync (h->dCloud, cloud, (size_t) n * 32, hipMemcpyHostToDevice, h->stream));
     icp_launch_get_lms (h->dCloud, which == ICP_MEM_F ? h->dF : h->dM, h->stream);
@@ -1187,14 +1093,7 @@ int icp_transform_cloud (icp_handle h, const void *host_in, void *host_out, uint
     int rc = need (h, false); if (rc) return rc;
     if (!host_in || !host_out || n == 0) return fail (h, ICP_EINVAL, "bad arguments");
     if ((rc = set_device (h))) return rc;
-    if (h->cloud_cap < n) {
-        if (h->dCloud) (void) hipFree (h->dCloud);
-        if (h->dCloudOut) (void) hipFree (h->dCloudOut);
-        h->dCloud = h->dCloudOut = nullptr; h->cloud_cap = 0;
-        HIPCHK (h, hipMalloc ((void **) &h->dCloud, (size_t) n * 32));
-        HIPCHK (h, hipMalloc ((void **) &h->dCloudOut, (size_t) n * 32));
-        h->cloud_cap = n;
-    }
+    if ((rc = cloud_reserve (h, n))) return rc;
     HIPCHK (h, hipMemcpyAsync (h->dCloud, host_in, (size_t) n * 32, hipMemcpyHostToDevice, h->stream));
     icp_launch_transform_cloud (h->dCloud, h->dCloudOut, h->p.st, n, h->stream);
     HIPCHK (h, hipGetLastError ());
@@ -1213,14 +1112,7 @@ int icp_transform_cloud_ex (icp_handle h, int kind, const float *T, const void *
         return fail (h, ICP_EINVAL, "icp_transform_cloud_ex: unknown transformation kind");
     if (!T || !host_in || !host_out || n == 0) return fail (h, ICP_EINVAL, "bad arguments");
     int rc = set_device (h); if (rc) return rc;
-    if (h->cloud_cap < n) {
-        if (h->dCloud) (void) hipFree (h->dCloud);
-        if (h->dCloudOut) (void) hipFree (h->dCloudOut);
-        h->dCloud = h->dCloudOut = nullptr; h->cloud_cap = 0;
-        HIPCHK (h, hipMalloc ((void **) &h->dCloud, (size_t) n * 32));
-        HIPCHK (h, hipMalloc ((void **) &h->dCloudOut, (size_t) n * 32));
-        h->cloud_cap = n;
-    }
+    if ((rc = cloud_reserve (h, n))) return rc;
     HIPCHK (h, hipMemcpyAsync (h->dCloud, host_in, (size_t) n * 32, hipMemcpyHostToDevice, h->stream));
     icp_launch_transform_cloud_ex (kind, h->dCloud, h->dCloudOut, T, n, h->stream);
     HIPCHK (h, hipGetLastError ());
@@ -1235,14 +1127,7 @@ int icp_power_method (int device, int rot, int power_mode, const float *S11, con
     if (!S11 || !means8 || !Tk8) return fail (nullptr, ICP_EINVAL, "icp_power_method: null pointer");
     if ((rot != ICP_ROT_EIGEN && rot != ICP_ROT_POWER_METHOD) || (power_mode != ICP_POWER_LITERAL && power_mode != ICP_POWER_SQUARED))
         return fail (nullptr, ICP_EINVAL, "icp_power_method: rot must be 0|1 and power_mode 0|1");
-    int count = 0;
-    if (hipGetDeviceCount (&count) != hipSuccess || count <= 0)
-        return fail (nullptr, ICP_ENODEVICE, "icp_power_method: no HIP device visible (the engine has no CPU fallback)");
-    if (device < 0 || device >= count) return fail (nullptr, ICP_EINVAL, "icp_power_method: device ordinal out of range");
-    hipDeviceProp_t prop;
-    HIPCHK (nullptr, hipGetDeviceProperties (&prop, device));
-    if (std::strncmp (prop.gcnArchName, "gfx950", 6) != 0)
-        return fail (nullptr, ICP_ENODEVICE, std::string ("icp_power_method: device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
+    { int rc = gfx950_device (device, "icp_power_method"); if (rc) return rc; }
     HIPCHK (nullptr, hipSetDevice (device));
     float *d = nullptr;
     HIPCHK (nullptr, hipMalloc ((void **) &d, (19 + 18) * sizeof (float)));

@@ -72,6 +72,26 @@ constexpr int ICP_KEEPER_ABORTED = -77;          // internal: run_finish on the 
 
 inline double now_s () { return std::chrono::duration<double> (std::chrono::steady_clock::now ().time_since_epoch ()).count (); }
 
+// What the user set: every value icp_create or a setter stores that outlives icp_init, as it was given — the getters read this record and
+// nothing else.  The fields of icp_params that depend on it come from derive_params (icp_capi.hip), the device words of the float
+// settings from write_words; a setter updates the record and hands the consequences to commit.
+struct icp_options {
+    int rot = ICP_ROT_POWER_METHOD, weighted = 1, power_mode = ICP_POWER_SQUARED, reduce_mode = ICP_REDUCE_FUSED;
+    int chain = 1;                               // ICP_AMD_CHAIN: 0 never, 1 automatic, 2 always (icp_chain_supported)
+    float metric_scale = 1.f;                    // icp_set_metric_scale
+    int reject_flags = 0; float reject_max_dist = 0.f;      // icp_set_rejection
+    float trim_keep = 1.f;                       // icp_set_trimming (1: off)
+    bool unique = false;                         // icp_set_unique
+    bool normal_on = false; float normal_min_cos = 0.f;     // icp_set_normal_rejection (0 while off); device word icp_pair_filter_settings [0]
+    uint32_t boundary_gw = 0;                    // icp_set_boundary_rejection (0: off); device word icp_pair_filter_settings [1]
+    int robust = ICP_ROBUST_NONE; float robust_scale = 0.f; // icp_set_robust_loss (0 while off); device word icp_robust_scale
+    int metric = ICP_METRIC_POINT_TO_POINT; float p2pl_mu = 0.f;   // icp_set_error_metric (0 on point-to-point)
+    float color_kappa = 0.f;                     // icp_set_color_weight; device word icp_color_kappa
+    float gicp_eps = 0.f;                        // icp_set_plane_to_plane (0: off); device word icp_gicp_eps
+    bool symmetric = false;                      // icp_set_symmetric
+    uint32_t nrm_grid = 0;                       // icp_set_normals: the grid width of ICP_NORMALS_GRID, 0: ICP_NORMALS_GIVEN
+};
+
 }  // namespace icp_host
 
 struct icp_context {
@@ -111,12 +131,7 @@ struct icp_context {
     uint32_t stat_launches = 0, stat_k = 0, stat_dead = 0;   // last finished checked run: iteration launches enqueued, final k, launches past the last live one
     double stat_t[6] = { 0, 0, 0, 0, 0, 0 };     // its host timeline (run_ctl::t) + the moment its FINAL bit was seen
     double stat_launch_max_us = 0.0; uint64_t stat_launch_slow = 0, stat_launch_total = 0;   // launch calls of all checked runs since icp_init
-    float color_kappa = 0.f;                     // colored ICP's kappa (icp_set_color_weight; survives icp_init): its device word is icp_color_kappa
-    float robust_scale = 0.f;                    // the robust loss's scale k (icp_set_robust_loss; 0 while off; survives icp_init): its device word is icp_robust_scale
-    bool symmetric = false;                      // the symmetric objective (icp_set_symmetric; survives icp_init): with gicp_eps it decides p.gicp
-    float gicp_eps = 0.f;                        // plane-to-plane's epsilon (icp_set_plane_to_plane; 0 while off; survives icp_init): its device word is icp_gicp_eps
-    float normal_min_cos = 0.f;                  // normal rejection's threshold (icp_set_normal_rejection; 0 while off; survives icp_init): its device word is icp_pair_filter_settings [0]
-    uint32_t boundary_gw = 0;                    // boundary rejection's grid width (icp_set_boundary_rejection; 0: off; survives icp_init): its device word is icp_pair_filter_settings [1]
+    icp_host::icp_options opt;                   // what the user set (survives icp_init; p's dependent fields are derived from it)
     uint64_t graph_clock = 0, param_gen = 0;     // LRU stamp of the graph cache; generation of the parameters the cached graphs were captured with
     float *dTin = nullptr;                       // device scratch for write(T)
     float *dCloud = nullptr, *dCloudOut = nullptr; uint32_t cloud_cap = 0;

@@ -22,11 +22,11 @@ int need (icp_context *h, bool built, bool keep_run)
     if (!h) return ICP_EINVAL;
     if (!h->inited) return fail (h, ICP_ESTATE, "icp_init has not been called");
     if (built && !h->built) return fail (h, ICP_ESTATE, "icp_build_rbc has not been called");
-    if (built && h->gicp_eps > 0.f && icp_colored (h->p))
+    if (built && h->opt.gicp_eps > 0.f && icp_colored (h->p))
         return fail (h, ICP_ESTATE, "icp_set_plane_to_plane does not combine with ICP_METRIC_COLORED (icp_set_error_metric): switch one of them off");
-    if (built && h->symmetric && icp_colored (h->p))
+    if (built && h->opt.symmetric && icp_colored (h->p))
         return fail (h, ICP_ESTATE, "icp_set_symmetric does not combine with ICP_METRIC_COLORED (icp_set_error_metric): switch one of them off");
-    if (built && h->symmetric && h->gicp_eps > 0.f && icp_p2pl (h->p))          // (point-to-point ignores both)
+    if (built && h->opt.symmetric && h->opt.gicp_eps > 0.f && icp_p2pl (h->p))          // (point-to-point ignores both)
         return fail (h, ICP_ESTATE, "icp_set_symmetric does not combine with icp_set_plane_to_plane: switch one of them off");
     if (!keep_run && (h->run.active || h->run2.active || h->stream2_dirty)) {
         if (hipSetDevice (h->device) != hipSuccess) return fail (h, ICP_EHIP, "hipSetDevice");

@@ -330,9 +330,9 @@ static int track_submit (icp_context *h, const void *cloud, int warm_start, bool
     int rc = need (h, false, true); if (rc) return rc;
     if ((rc = keeper_error (h))) return rc;
     if (!cloud) return fail (h, ICP_EINVAL, "null pointer");
-    if (h->gicp_eps > 0.f) return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while plane-to-plane is on (icp_set_plane_to_plane)");
-    if (h->symmetric) return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while the symmetric objective is on (icp_set_symmetric)");
-    if (h->p.reject & ICP_REJECT_NORMAL_ON)
+    if (h->opt.gicp_eps > 0.f) return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while plane-to-plane is on (icp_set_plane_to_plane)");
+    if (h->opt.symmetric) return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while the symmetric objective is on (icp_set_symmetric)");
+    if (h->opt.normal_on)
         return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while normal rejection is on (icp_set_normal_rejection)");
     // (point-to-plane: each frame's normals come from its own landmarks, which only buildRBC can give it — ICP_NORMALS_GRID)
     if (icp_p2pl (h->p) && !h->p.nrm_grid)
@@ -340,7 +340,7 @@ static int track_submit (icp_context *h, const void *cloud, int warm_start, bool
     // (a frame's buildRBC is enqueued from here, not through icp_build_rbc: the grid width is checked here as icp_build_rbc checks it)
     if (h->p.nrm_grid && h->p.m % h->p.nrm_grid)
         return fail (h, ICP_ESTATE, "icp_track_submit: ICP_NORMALS_GRID: m is not a multiple of the grid width");
-    if (h->boundary_gw && h->p.m % h->boundary_gw)
+    if (h->opt.boundary_gw && h->p.m % h->opt.boundary_gw)
         return fail (h, ICP_ESTATE, "icp_track_submit: icp_set_boundary_rejection: m is not a multiple of the grid width");
     if ((rc = set_device (h))) return rc;
     if ((rc = track_prepare (h))) return rc;                            // (everything that can fail for lack of memory comes first)

@@ -791,3 +791,84 @@ def test_the_rules_cope_with_partial_overlap(engine, fused):
     assert 1 < res["on"][0] <= 40, res
     assert res["on"][1] < ROT_BOUND < res["off"][1], res
     assert res["on"][2] < TRANS_BOUND < res["off"][2], res
+
+
+# ---- 9. every option at once survives icp_init
+
+def _set_every_option(engine, g, moving):
+    """Every setting a setter stores, at a value that is not its default and that a float holds exactly."""
+    g.setPowerMode(engine.PowerMode.LITERAL); g.setReduceMode(engine.ReduceMode.REFERENCE_ORDER)
+    g.setMetricScale(2.0)
+    g.set_normals(engine.Normals.GRID, 16)
+    g.set_error_metric(engine.ErrorMetric.POINT_TO_PLANE, 0.0625)
+    g.set_color_weight(250.0)
+    g.set_robust_loss(engine.RobustLoss.HUBER, 32.0)
+    g.set_rejection(True, 512.0)
+    g.set_trimming(0.75)
+    g.set_unique(True)
+    g.set_boundary_rejection(16)
+    g.set_normal_rejection(0.25)
+    if moving == "plane_to_plane":
+        g.set_plane_to_plane(0.125)
+    else:
+        g.set_symmetric(True)
+
+
+def _every_getter(g):
+    return (g.getMetricScale(), g.normals(), g.error_metric(), g.color_weight(), g.robust_loss(), g.rejection(), g.trimming(), g.unique(),
+            g.boundary_rejection(), g.normal_rejection(), g.plane_to_plane(), g.symmetric())
+
+
+_RESULT_WORDS = ("TRIM", "UNIQUE", "PAIR_FILTER", "PLANE_SYSTEM")
+
+
+def _run_and_read(engine, g, F, M):
+    """T and the per-registration result words after a run of three iterations from the identity."""
+    g.write(engine.Memory.F, F); g.write(engine.Memory.M, M)
+    g.buildRBC()
+    g.run_fixed(3)
+    out = {"T": g.read(engine.Memory.T).copy()}
+    for name in _RESULT_WORDS:
+        out[name] = g.read(getattr(engine.Memory, name)).copy()
+    return out
+
+
+def _switch_off_and_expect_zeros(engine, g):
+    g.set_trimming(1.0); g.set_unique(False); g.set_normal_rejection(None); g.set_boundary_rejection(None)
+    g.set_error_metric(engine.ErrorMetric.POINT_TO_POINT)
+    for name in _RESULT_WORDS:
+        assert np.all(g.read(getattr(engine.Memory, name)).view(np.uint32) == 0), "%s reads zeros while its feature is off" % name
+
+
+@pytest.mark.parametrize("moving", ["plane_to_plane", "symmetric"])
+def test_every_option_survives_icp_init(engine, moving):
+    """The union of the per-feature "survives icp_init" cases.  A handle gets every option BEFORE its first icp_init and is then
+    initialised three times in a row — m = 256, |R| = 16; m = 1024, |R| = 64; m = 256 again — with no setter called in between.  After
+    each icp_init every getter returns what was set, and a run of three iterations gives the bits of T, ICP_MEM_TRIM, ICP_MEM_UNIQUE,
+    ICP_MEM_PAIR_FILTER and ICP_MEM_PLANE_SYSTEM of a fresh handle that got the same options AFTER its icp_init.  Switching the features
+    off must leave their result areas reading zeros: checked on each shape's fresh handle, and on the handle under test once its
+    third icp_init has been checked (switching them off earlier would leave the later calls of icp_init nothing to keep).
+    (The grid width 16 is the landmark grid's at m = 256; at m = 1024 it divides m and reads the 32 x 32 grid as 64 rows of 16: the normals
+    and the rim are then not the surface's, which the comparison does not need.)"""
+    want = (2.0, (engine.Normals.GRID, 16), (engine.ErrorMetric.POINT_TO_PLANE, 0.0625), 250.0, (engine.RobustLoss.HUBER, 32.0),
+            (True, 512.0), 0.75, True, 16, 0.25, 0.125 if moving == "plane_to_plane" else 0.0, moving == "symmetric")
+    g = engine.ICP(0)
+    _set_every_option(engine, g, moving)
+    assert _every_getter(g) == want
+    for side, nr in ((16, 16), (32, 64), (16, 16)):
+        F, M = engine.synth_pair(side)
+        g.init(side * side, nr, A, C_)
+        assert _every_getter(g) == want, (side, _every_getter(g))
+        got = _run_and_read(engine, g, F, M)
+        fresh = engine.ICP(0)
+        fresh.init(side * side, nr, A, C_)
+        _set_every_option(engine, fresh, moving)
+        ref = _run_and_read(engine, fresh, F, M)
+        print("m = %d:" % (side * side), {k: v.tolist() for k, v in ref.items() if k != "PLANE_SYSTEM"}, "system status", ref["PLANE_SYSTEM"][27])
+        assert ref["PAIR_FILTER"][0] > 0 and ref["UNIQUE"][0] > 0 and ref["TRIM"][1] > 0, "the rules had candidates to work on"
+        for name in ("T",) + _RESULT_WORDS:
+            assert_bits(got[name], ref[name], "%s at m = %d against a handle set up after icp_init" % (name, side * side))
+        _switch_off_and_expect_zeros(engine, fresh)
+        fresh.close()
+    _switch_off_and_expect_zeros(engine, g)
+    g.close()
