@@ -140,8 +140,8 @@ int commit (icp_context *h, unsigned what)
         if ((rc = run_close_all (h))) return rc;
         if ((rc = write_words (h, what & OPT_WORDS))) return rc;
         const struct { void *area; size_t bytes; } areas[] = {
-            { icp_trim_area (p), sizeof (uint32_t) * 4u }, { icp_unique_area (p), sizeof (uint32_t) * 4u },
-            { icp_pair_filter_area (p), sizeof (uint32_t) * 8u }, { icp_p2pl_area (p), sizeof (double) * ICP_P2PL_SYS },
+            { icp_trim_area (p), sizeof (uint32_t) * 4u }, { icp_unique_area (p), sizeof (uint32_t) * 2u },
+            { icp_pair_filter_area (p), sizeof (uint32_t) * 4u }, { icp_p2pl_area (p), sizeof (double) * ICP_P2PL_SYS },
         };
         for (int i = 0; i < 4; ++i) if (off[i]) HIPCHK (h, hipMemsetAsync (areas[i].area, 0, areas[i].bytes * p.batch, h->stream));
         if ((what & OPT_WORDS) || clears) HIPCHK (h, hipStreamSynchronize (h->stream));
@@ -237,7 +237,7 @@ int icp_create (icp_handle *out, int device, int rot, int weighted) try
     icp_options &o = h->opt;
     o.rot = rot; o.weighted = weighted;
     { const char *e = std::getenv ("ICP_AMD_MODE"); if (e && (e[0] == 'r' || e[0] == 'R')) { o.power_mode = ICP_POWER_LITERAL; o.reduce_mode = ICP_REDUCE_REFERENCE_ORDER; } }
-    { const char *e = std::getenv ("ICP_AMD_CHAIN"); o.chain = !e ? 1 : (e[0] == '1') ? 2 : (e[0] == '0') ? 0 : 1; }   // see icp_chain_supported
+    { const char *e = std::getenv ("ICP_AMD_CHAIN"); o.chain = !e ? 1 : (e[0] == '1') ? 2 : (e[0] == '0') ? 0 : 1; }   // see icp_route_of
     derive_params (o, h->p);
     { const char *e = std::getenv ("ICP_AMD_RUN_ADAPTIVE"); if (e && e[0] == '0') h->run_adaptive = 0; }                  // see run_ctl
     { const char *e = std::getenv ("ICP_AMD_TRACK_GATE"); if (e && e[0] == '0') h->track_gate = 0; }
@@ -436,7 +436,7 @@ static mem_desc mem_of (const icp_context *h, uint32_t b, int mem)
         case ICP_MEM_QT: return { p.PM + b * m, m * 16, nullptr };
         case ICP_MEM_W: return { reinterpret_cast<const float *> (p.PF + b * m) + 3, m * 4, nullptr };    // (the .w lane of the matched points: a strided read)
         case ICP_MEM_TRIM: return { icp_trim_area (p) + 4u * b, 16, nullptr };
-        case ICP_MEM_UNIQUE: return { icp_unique_area (p) + 4u * b + 1u, 8, nullptr };
+        case ICP_MEM_UNIQUE: return { icp_unique_area (p) + 2u * b, 8, nullptr };
         case ICP_MEM_PAIR_FILTER: return { icp_pair_filter_area (p) + 4u * b, 16, nullptr };
         case ICP_MEM_NORMALS_F: return { icp_normals_f (p) + b * m, m * 16, "ICP_MEM_NORMALS_F" };
         case ICP_MEM_COLOR_GRAD_F: return { icp_color_grad_f (p) + b * m, m * 16, "ICP_MEM_COLOR_GRAD_F" };
@@ -1205,8 +1205,7 @@ int icp_run_form (icp_handle h, int *form) try
     api_guard guard_ (h);
     int rc = need (h, false); if (rc) return rc;
     if (!form) return fail (h, ICP_EINVAL, "null output");
-    if (icp_chain_supported (h->p)) *form = ICP_FORM_CHAINED;
-    else *form = ICP_FORM_SEPARATE;
+    *form = icp_route_of (h->p).chained ? ICP_FORM_CHAINED : ICP_FORM_SEPARATE;
     return ICP_OK;
 }
 ICP_CATCH_ALL
@@ -1225,14 +1224,7 @@ int icp_launches_per_iteration (icp_handle h, uint32_t *n) try
     api_guard guard_ (h);
     int rc = need (h, false); if (rc) return rc;
     if (!n) return fail (h, ICP_EINVAL, "null output");
-    int form = ICP_FORM_SEPARATE;
-    if ((rc = icp_run_form (h, &form))) return rc;
-    // (fused, large sets: the first level of the moment tree is a launch of its own — icp_launch_finalize)
-    *n = form != ICP_FORM_SEPARATE ? 1u : h->p.fused ? ((h->p.nb + 127u) / 128u > ICP_L1_MIN_GROUPS ? 3u : 2u) : 4u;
-    if (icp_apply_pass (h->p)) *n += icp_trim_launches (h->p);        // (trimming's select: one or three launches; apply: one)
-    if (icp_p2pl (h->p)) *n = 1u + (icp_apply_pass (h->p) ? icp_trim_launches (h->p) : 0u) + ICP_P2PL_LAUNCHES;   // (search, moments, finalize)
-    if (icp_unique (h->p)) *n += ICP_UNIQUE_LAUNCHES;                 // (one-to-one correspondences: claim and resolve, behind the search)
-    if (icp_pair_filter (h->p)) *n += ICP_PAIR_FILTER_LAUNCHES;       // (boundary and normal rejection: one pass behind the search)
+    *n = icp_route_of (h->p).launches;
     return ICP_OK;
 }
 ICP_CATCH_ALL
@@ -1277,8 +1269,8 @@ int icp_debug_stamps (icp_handle h, unsigned long long *out, uint32_t nblocks) t
     icp_params p = h->p; p.check = 0; p.dbg = d; p.hmirror = nullptr; p.hstate = nullptr;
     note_enqueue (h); note_outputs_stored (h);
     if (e == hipSuccess) {
-        if (icp_chain_supported (p)) icp_launch_chain (p, h->stream, 2);
-        else { icp_launch_search_stage (p, h->stream); if (p.fused) icp_launch_finalize (p, h->stream); }
+        if (icp_route_of (p).chained) icp_launch_chain (p, h->stream, 2);
+        else icp_launch_masked (p, h->stream, p.fused ? 1u | 8u : 1u);
         e = hipGetLastError ();
     }
     if (e == hipSuccess) e = hipStreamSynchronize (h->stream);
@@ -1303,14 +1295,11 @@ int icp_profile_run (icp_handle h, uint32_t iterations, float *out_ms, float *to
     // the stages as separate launches (the chained form has no stage boundaries to time), events around each
     for (uint32_t r = 0; r < iterations && e == hipSuccess; ++r) {
         hipEvent_t *x = &ev[(size_t) r * 5];
-        e = hipEventRecord (x[0], h->stream); icp_launch_search_stage (p, h->stream);     // (trimming, one-to-one, the pair filter on: their passes time with the search)
-        if (e == hipSuccess) e = hipEventRecord (x[1], h->stream);
-        if (!p.fused) icp_launch_means (p, h->stream);
-        if (e == hipSuccess) e = hipEventRecord (x[2], h->stream);
-        if (!p.fused) icp_launch_sij (p, h->stream);
-        if (e == hipSuccess) e = hipEventRecord (x[3], h->stream);
-        icp_launch_finalize (p, h->stream);
-        if (e == hipSuccess) e = hipEventRecord (x[4], h->stream);
+        e = hipEventRecord (x[0], h->stream);                                             // (trimming, one-to-one, the pair filter on: their passes time with the search)
+        for (int k = 0; k < 4; ++k) {
+            icp_launch_masked (p, h->stream, 1u << k);
+            if (e == hipSuccess) e = hipEventRecord (x[k + 1], h->stream);
+        }
     }
     if (e == hipSuccess) e = hipGetLastError ();
     if (e == hipSuccess) e = hipStreamSynchronize (h->stream);

@@ -77,7 +77,7 @@ inline double now_s () { return std::chrono::duration<double> (std::chrono::stea
 // settings from write_words; a setter updates the record and hands the consequences to commit.
 struct icp_options {
     int rot = ICP_ROT_POWER_METHOD, weighted = 1, power_mode = ICP_POWER_SQUARED, reduce_mode = ICP_REDUCE_FUSED;
-    int chain = 1;                               // ICP_AMD_CHAIN: 0 never, 1 automatic, 2 always (icp_chain_supported)
+    int chain = 1;                               // ICP_AMD_CHAIN: 0 never, 1 automatic, 2 always (icp_route_of)
     float metric_scale = 1.f;                    // icp_set_metric_scale
     int reject_flags = 0; float reject_max_dist = 0.f;      // icp_set_rejection
     float trim_keep = 1.f;                       // icp_set_trimming (1: off)
@@ -272,15 +272,16 @@ int run_begin (icp_context *h, run_ctl &r, hipStream_t stream, const icp_params 
     r.stream = stream;
     r.t[0] = now_s ();
     r.p = p; r.p.check = 1;
-    // (reference-order kernels read the outputs themselves, and so do trimming's selection, the apply pass and the point-to-plane moments: always stored)
-    r.p.emit = (h->outputs_lazy && p.fused && !icp_apply_pass (p) && !icp_p2pl (p)) ? 0 : 1;
+    const icp_route route = icp_route_of (p);
+    // (reference-order kernels read the outputs themselves, and so does whatever makes the route store them: always stored)
+    r.p.emit = (h->outputs_lazy && p.fused && !route.stored) ? 0 : 1;
     h->outputs_stale = r.p.emit == 0; h->outputs_lost = false;
     if (++h->epoch == 0u) h->epoch = 1u;
     r.p.epoch = h->epoch; r.p.hmirror = mirror; r.p.hstate = hstate;    // (fine-grained host allocations: the host pointer is the device pointer)
     r.mirror = mirror; r.track_slot = track_slot;
     for (uint32_t b = 0; b < p.batch; ++b) mirror[b] = 0ull;
     std::atomic_thread_fence (std::memory_order_seq_cst);
-    r.chained = icp_chain_supported (r.p); r.fresh = fresh;
+    r.chained = route.chained; r.fresh = fresh;
     r.k0 = (fresh || with_build || h->k_base < 0) ? 0u : (uint32_t) h->k_base;      // (a fresh run and a rebuilt RBC start the count at 0)
     r.maxit = h->max_iterations; r.depth = h->run_depth ? h->run_depth : 1u;
     if (other && other->active) (void) run_pump (h, *other);

@@ -121,7 +121,7 @@ struct icp_params {
     float trim_keep;             // keep_fraction in (0, 1] while trimming is on; 0 while it is off
 };
 #define ICP_REJECT_DIST_ON 0x80000000u   // icp_params::reject: the distance test is on (one scalar test of one word says whether anything is)
-#define ICP_REJECT_TRIM_ON 0x40000000u   // icp_params::reject: trimming is on (the REJ kernels, plus select and apply: icp_launch_trim)
+#define ICP_REJECT_TRIM_ON 0x40000000u   // icp_params::reject: trimming is on (the REJ kernels, plus the selection and the apply pass: icp_route_of)
 #define ICP_REJECT_ROBUST_SHIFT 28u
 #define ICP_REJECT_ROBUST_MASK 0x30000000u   // icp_params::reject: the robust loss (icp_set_robust_loss): ICP_ROBUST_* << 28, 0: off
 #define ICP_REJECT_UNIQUE_ON 0x08000000u   // icp_params::reject: one-to-one correspondences are on (icp_set_unique: the REJ kernels, plus claim and resolve: icp_launch_unique)
@@ -149,16 +149,6 @@ static __host__ __device__ __forceinline__ double icp_robust_omega (uint32_t los
     if (loss == 2u) return 1.0 / (1.0 + u);                             // Cauchy
     return u < 1.0 ? (1.0 - u) * (1.0 - u) : 0.0;                        // Tukey
 }
-// An apply pass (k_trim_apply) rewrites the weights behind the search: trimming, or a robust loss on point-to-point (the plane metrics
-// weigh their pairs in k_plane_moments).  One-to-one correspondences on point-to-point need it too: the resolve pass has zeroed weights
-// behind the search's partials, and the pass writes the partials again (the plane metrics read w in k_plane_moments: no pass for them);
-// the pair filter (icp_pair_filter.hip) zeroes weights the same way.
-// The route of every such iteration: per-query outputs stored every time, no chained form.
-static __host__ __device__ __forceinline__ bool icp_apply_pass (const icp_params &p)
-{
-    return icp_trimming (p) || ((icp_robust (p) != 0u || icp_unique (p) || icp_pair_filter (p)) && p.metric == 0u);
-}
-
 // Trimming's buffers (icp_trim.hip) are uint32 words: [batch][4] the result of the last iteration (t bits, n, K, accepted: ICP_MEM_TRIM),
 // [batch][4] the state of the multi-block selection (prefix, rank left, count below, arrivals), [batch][2048] its histograms, and for
 // sets beyond one workgroup's selection [batch][m] the keys.
@@ -193,9 +183,9 @@ struct icp_mom_layout {
     size_t kappa;                // the float word of kappa (icp_color_kappa)
     size_t robust;               // the float word of the robust loss's scale k (icp_robust_scale)
     size_t gicp;                 // the float word of plane-to-plane's epsilon (icp_gicp_eps)
-    size_t uniq;                 // one-to-one correspondences: [batch][4] uint32 result words (icp_unique_area), [batch][m] uint64 claim table (icp_unique_claims)
-    size_t filt;                 // the pair filter's uint32 words (icp_pair_filter_area): [batch][4] ICP_MEM_PAIR_FILTER, [batch][4] the words of its apply pass,
-                                 // [batch][8] the blocks' running counts and their arrival counter, then min_cos (float) and the boundary rule's grid width
+    size_t uniq;                 // one-to-one correspondences: [batch][2] uint32 result words (icp_unique_area), [batch][m] uint64 claim table (icp_unique_claims)
+    size_t filt;                 // the pair filter's uint32 words (icp_pair_filter_area): [batch][4] ICP_MEM_PAIR_FILTER, [batch][8] the blocks' running
+                                 // counts and their arrival counter, then min_cos (float) and the boundary rule's grid width
     size_t total;
 };
 static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (uint32_t batch, uint32_t m, uint32_t nb)
@@ -209,8 +199,8 @@ static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (uint32_t bat
     l.robust = l.kappa + 1u;
     l.gicp = l.robust + 1u;
     l.uniq = l.gicp + 1u;
-    l.filt = l.uniq + 2u * B + B * m;
-    l.total = l.filt + 8u * B + 1u;
+    l.filt = l.uniq + B + B * m;
+    l.total = l.filt + 6u * B + 1u;
     return l;
 }
 static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (const icp_params &p) { return icp_mom_layout_of (p.batch, p.m, p.nb); }
@@ -221,22 +211,18 @@ static inline float *icp_color_kappa (const icp_params &p) { return reinterpret_
 // (also on the device: the robust kernels find the word from their icp_params, the loss-off kernels take no argument for it)
 static __host__ __device__ inline float *icp_robust_scale (const icp_params &p) { return reinterpret_cast<float *> (p.mom + icp_mom_layout_of (p).robust); }
 static __host__ __device__ inline float *icp_gicp_eps (const icp_params &p) { return reinterpret_cast<float *> (p.mom + icp_mom_layout_of (p).gicp); }
-// One-to-one correspondences (icp_unique.hip).  The result words of a registration are laid out as k_trim_apply reads trimming's:
-// (0xFFFFFFFE, n, winners, winners) — a threshold above every candidate's key and a K that is 0 only when nothing is left —, so that
-// the apply pass behind the resolve pass is trimming's own kernel pointed at these words; ICP_MEM_UNIQUE is words 1 and 2.
+// One-to-one correspondences (icp_unique.hip): the result words of a registration are (n, winners), ICP_MEM_UNIQUE as it is read.
 static inline uint32_t *icp_unique_area (const icp_params &p) { return reinterpret_cast<uint32_t *> (p.mom + icp_mom_layout_of (p).uniq); }
 static inline unsigned long long *icp_unique_claims (const icp_params &p)
 {
-    return reinterpret_cast<unsigned long long *> (p.mom + icp_mom_layout_of (p).uniq + 2u * (size_t) p.batch);
+    return reinterpret_cast<unsigned long long *> (p.mom + icp_mom_layout_of (p).uniq + (size_t) p.batch);
 }
 // The pair filter (icp_pair_filter.hip), uint32 words: [batch][4] the result of the last iteration (n, at_boundary, incompatible, accepted:
-// ICP_MEM_PAIR_FILTER); [batch][4] the same laid out as k_trim_apply reads trimming's words, (0xFFFFFFFE, n, accepted, 0), for the apply
-// pass of the filter alone (icp_pair_filter_apply_area); [batch][8] the running counts of an iteration's blocks and their arrival counter,
-// zero between launches; then the two settings the kernel reads instead of capturing them: min_cos (float) and the grid width.
+// ICP_MEM_PAIR_FILTER); [batch][8] the running counts of an iteration's blocks and their arrival counter, zero between launches; then
+// the two settings the kernel reads instead of capturing them: min_cos (float) and the grid width.
 static inline uint32_t *icp_pair_filter_area (const icp_params &p) { return reinterpret_cast<uint32_t *> (p.mom + icp_mom_layout_of (p).filt); }
-static inline uint32_t *icp_pair_filter_apply_area (const icp_params &p) { return icp_pair_filter_area (p) + 4u * (size_t) p.batch; }
-static inline uint32_t *icp_pair_filter_counts (const icp_params &p) { return icp_pair_filter_area (p) + 8u * (size_t) p.batch; }
-static inline uint32_t *icp_pair_filter_settings (const icp_params &p) { return icp_pair_filter_area (p) + 16u * (size_t) p.batch; }
+static inline uint32_t *icp_pair_filter_counts (const icp_params &p) { return icp_pair_filter_area (p) + 4u * (size_t) p.batch; }
+static inline uint32_t *icp_pair_filter_settings (const icp_params &p) { return icp_pair_filter_area (p) + 12u * (size_t) p.batch; }
 
 // The XP allocation of one RBC set, offsets in floats: [batch][m][8] the permuted database, then [batch][m] float4 NORMALS_F and
 // [batch][m] float4 COLOR_GRAD_F ([gx gy gz C] per fixed point).  The normals and gradients belong to the fixed frame as the RBC does,
@@ -321,20 +307,35 @@ static __device__ __forceinline__ uint32_t icp_other_kind_near (const unsigned l
     return fallback;
 }
 
+// The route of an iteration: what icp_launch_iteration enqueues for these parameters, and how the run graphs and the host-driven runs
+// execute it.  icp_route_of (icp_kernels.hip) is the one place that decides it; the launchers, the run code (icp_run.hip, icp_host.h),
+// icp_run_form and icp_launches_per_iteration read the record.
+enum icp_apply_kind { ICP_APPLY_NONE = 0, ICP_APPLY_PLAIN, ICP_APPLY_ROBUST };    // k_trim_apply<fused?> / k_trim_apply_robust<fused?>
+enum icp_tail_kind { ICP_TAIL_FUSED = 0, ICP_TAIL_FUSED_L1, ICP_TAIL_REFERENCE, ICP_TAIL_PLANE };
+struct icp_route {
+    bool chained;                // runs take one launch per iteration (icp_launch_chain): no pass below is on, and the tail is what the
+                                 // diagnostics that time an iteration stage by stage enqueue (icp_launch_masked)
+    bool stored;                 // the search stores its per-query outputs every iteration: a pass or the plane moments read them
+    bool ref_search;             // the search in its reference-order form whatever p.fused (the plane metrics)
+    bool filter;                 // k_pair_filter
+    bool unique;                 // k_unique_claim + k_unique_resolve
+    uint32_t select;             // trimming's selection: 0, 1 (k_trim_select) or 3 launches (k_trim_select_pass<0 .. 2>)
+    icp_apply_kind apply;        // the pass that writes the search's partials again from the weights
+    icp_tail_kind tail;          // k_finalize_fused / k_moment_level1 + k_finalize_fused / k_means, k_sij, k_finalize / k_plane_moments, k_p2pl_finalize
+    uint32_t launches;           // what icp_launches_per_iteration reports
+};
+icp_route icp_route_of (const icp_params &p);
+
 // launchers (icp_kernels.hip, icp_build.hip)
 void icp_launch_build_rbc (const icp_params &p, hipStream_t s);
 void icp_launch_search (const icp_params &p, hipStream_t s);
-void icp_launch_search_stage (const icp_params &p, hipStream_t s);    // the search of an iteration: with trimming on, + select and apply
-void icp_launch_means (const icp_params &p, hipStream_t s);
-void icp_launch_sij (const icp_params &p, hipStream_t s);
-void icp_launch_finalize (const icp_params &p, hipStream_t s);
 void icp_launch_iteration (const icp_params &p, hipStream_t s);
+// any subset of an iteration's stages (bit 0 the search with the passes behind it, 1 means, 2 sij, 3 finalize; 4: an empty kernel)
 void icp_launch_masked (const icp_params &p, hipStream_t s, unsigned mask);
 void icp_launch_chain (const icp_params &p, hipStream_t s, uint32_t iterations, bool fresh = false);
 void icp_launch_chain_one (const icp_params &p, hipStream_t s, uint32_t j, bool fresh, bool emit);   // launch j of a chain (j = 0: reads the user-visible state)
 void icp_launch_chain_end (const icp_params &p, hipStream_t s, uint32_t launches);                  // after `launches` chained launches: the last moments -> p.st (and p.hstate)
 void icp_launch_publish_state (const icp_params &p, hipStream_t s);                                  // separate launches: p.st -> p.hstate + the FINAL bit
-bool icp_chain_supported (const icp_params &p);
 bool icp_build_lists (const icp_params &p);      // buildRBC = owner search + k_place_lists (2 launches)
 bool icp_dense (const icp_params &p);            // the dense search variant (several blocks per CU, stage-1 pruning)
 uint32_t icp_dense_tile (const icp_params &p);   // its LDS tile: 256 or 1024 representatives
@@ -342,12 +343,10 @@ void icp_launch_owner_search (const icp_params &p, hipStream_t s);   // RBC cons
 void icp_launch_search_dense (const icp_params &p, hipStream_t s);          // icp_search_dense.hip: the dense variants (icp_dense (p))
 void icp_launch_search_rej (const icp_params &p, hipStream_t s);            // icp_search_rej.hip: every search with correspondence rejection on
 void icp_launch_chain_one_rej (const icp_params &p, hipStream_t s, uint32_t j, bool fresh, bool emit);
-void icp_launch_trim (const icp_params &p, hipStream_t s);                   // icp_trim.hip: k_trim_select (one or three launches) + k_trim_apply
-uint32_t icp_trim_launches (const icp_params &p);                             // how many that is
+void icp_launch_trim_select (const icp_params &p, hipStream_t s, uint32_t launches);   // icp_trim.hip: k_trim_select (1) or k_trim_select_pass<0 .. 2> (3: icp_route::select)
+void icp_launch_trim_apply (const icp_params &p, hipStream_t s);             // icp_trim.hip: k_trim_apply<fused?>
 void icp_launch_unique (const icp_params &p, hipStream_t s);                 // icp_unique.hip: k_unique_claim + k_unique_resolve
-#define ICP_UNIQUE_LAUNCHES 2u                                                // launches of icp_launch_unique
 void icp_launch_pair_filter (const icp_params &p, hipStream_t s);            // icp_pair_filter.hip: k_pair_filter (boundary and / or normal rejection), behind the search
-#define ICP_PAIR_FILTER_LAUNCHES 1u                                           // launches of icp_launch_pair_filter
 void icp_launch_robust_apply (const icp_params &p, hipStream_t s);            // icp_robust.hip: k_trim_apply_robust<fused?> (a point-to-point robust loss)
 void icp_launch_plane_moments_robust (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);   // icp_robust.hip: k_plane_moments_robust<colored?>
 void icp_launch_p2pl_solve (const icp_params &p, hipStream_t s);             // icp_p2pl.hip: k_plane_moments<colored?> + k_p2pl_finalize
@@ -355,7 +354,6 @@ void icp_launch_normals_grid (const icp_params &p, hipStream_t s);           // 
 void icp_launch_normals_m (const icp_params &p, hipStream_t s, uint32_t b0, uint32_t nb);   // icp_p2pl.hip: k_normals_grid pointed at M, registrations b0 .. b0 + nb - 1
 void icp_launch_gicp_moments (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);          // icp_gicp.hip: k_gicp_moments<robust?>
 void icp_launch_sym_moments (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);           // icp_symmetric.hip: k_sym_moments<robust?>
-#define ICP_P2PL_LAUNCHES 2u                                                  // launches of icp_launch_p2pl_solve
 void icp_launch_owner_search_dense (const icp_params &p, hipStream_t s);
 uint32_t icp_tbox_of (const icp_params &p);
 uint32_t icp_s2_wave_of (const icp_params &p);

@@ -21,6 +21,10 @@
 // latency-bound sizes; k_reps_and_boxes, k_search<.., OWNER>, k_chunk_hist, k_count_offsets (or k_count, k_offsets beyond 1024
 // representatives), k_place otherwise.
 //
+// The opt-in passes between the search and the tail (the pair filter, one-to-one correspondences, trimming, the robust loss) and
+// the plane metrics' tail live in translation units of their own; which of them an iteration enqueues, in which order, and how
+// many launches that is, is decided by icp_route_of below and nowhere else.
+//
 // Every reduction follows the canonical tree of DESIGN.md §3, so results are bit-identical to
 // oracle/icp_oracle.c.  blockIdx.y is the registration index of a batch.
 #include "icp_search.h"
@@ -538,9 +542,46 @@ void icp_launch_search (const icp_params &p, hipStream_t s)
     ks_launch_latency<false> (p, s);
 }
 
-void icp_launch_means (const icp_params &p, hipStream_t s)
+// ------------------------------------------------------------------------------------------
+// The route of an iteration (icp_route, icp_kernels.h): the one place that decides what an iteration enqueues and counts it, each
+// launch beside the decision that causes it.
+//   - Trimming (icp_trim.hip): the selection and an apply pass behind the search, under every metric.  Point-to-point with the pair
+//     filter, one-to-one correspondences or a robust loss on: an apply pass too — the filter and the resolve pass have zeroed weights
+//     behind the search's partials, the loss weighs every pair in its instantiation of the pass.  The plane metrics read the weights,
+//     and carry the loss, in their moments: no pass for them unless trimming is on.
+//   - The order: k_pair_filter first (a pair it rejects claims no fixed point), claim and resolve in front of trimming's selection (its
+//     candidates are the winners), the apply pass last.
+//   - Whatever reads the per-query outputs between the search and the tail — a pass, the plane moments — has them stored every
+//     iteration and rules the chained form out (it folds the finalize into the next search).  The plane metrics (icp_p2pl.hip) take the
+//     search in its reference-order form whatever the reduce mode: the same outputs, and its prologue publishes every iteration's
+//     (k, done) to a host-driven run (the fused form leaves a converged registration's word to the fused finalize).
+//   - The chained form (fused mode): p.chain = 0 never, 1 automatic (latency-bound sizes: the launch boundary it removes outweighs every
+//     block re-deriving T), 2 always (sizes the second tree level of the prologue can hold: 32 groups).
+// The count follows include/icp_amd.h: trimming's selection passes and k_moment_level1 count; the small second-level launches of the
+// reference-order reductions (k_sum_w beyond 65536 pairs, k_gmean beyond 16384) do not.
+// ------------------------------------------------------------------------------------------
+icp_route icp_route_of (const icp_params &p)
 {
-    if (icp_p2pl (p)) return;                                        // (point-to-plane: no means, no S — icp_p2pl.hip)
+    const bool plane = icp_p2pl (p), p2p_loss = !plane && icp_robust (p) != 0u;
+    icp_route r {};
+    r.launches = 1u;                                                              // the search
+    r.filter = icp_pair_filter (p);                                               r.launches += r.filter ? 1u : 0u;
+    r.unique = icp_unique (p);                                                    r.launches += r.unique ? 2u : 0u;
+    r.select = !icp_trimming (p) ? 0u : p.m <= ICP_TRIM_ONE_BLOCK_MAX ? 1u : 3u;  r.launches += r.select;
+    const bool pass = r.select || p2p_loss || (!plane && (r.filter || r.unique));
+    r.apply = !pass ? ICP_APPLY_NONE : p2p_loss ? ICP_APPLY_ROBUST : ICP_APPLY_PLAIN;   r.launches += pass ? 1u : 0u;
+    const bool level1 = (p.nb + 127u) / 128u > ICP_L1_MIN_GROUPS && p.ml1;        // (as k_finalize_fused decides where its first level comes from)
+    r.tail = plane ? ICP_TAIL_PLANE : !p.fused ? ICP_TAIL_REFERENCE : level1 ? ICP_TAIL_FUSED_L1 : ICP_TAIL_FUSED;
+    r.launches += r.tail == ICP_TAIL_REFERENCE ? 3u : r.tail == ICP_TAIL_FUSED ? 1u : 2u;
+    r.ref_search = plane;
+    r.stored = plane || r.apply != ICP_APPLY_NONE;
+    r.chained = p.fused && !r.stored && p.nb <= 4096u && p.nr <= 1024u && (p.chain == 2 || (p.chain == 1 && !icp_dense (p)));
+    if (r.chained) r.launches = 1u;
+    return r;
+}
+
+static void launch_means (const icp_params &p, hipStream_t s)
+{
     // (correspondence rejection: the weighted formulas, w in {0, 1} in REGULAR mode)
     const uint32_t weighted = (p.weighted || icp_rejecting (p)) ? 1u : 0u;
     if (weighted && p.nwp > 512) hipLaunchKernelGGL (k_sum_w, dim3 (1, p.batch), dim3 (64), 0, s, p);
@@ -548,76 +589,62 @@ void icp_launch_means (const icp_params &p, hipStream_t s)
                         p.m, p.nwp, weighted, (uint32_t) p.check, p);
 }
 
-void icp_launch_sij (const icp_params &p, hipStream_t s)
+static void launch_sij (const icp_params &p, hipStream_t s)
 {
-    if (icp_p2pl (p)) return;
     if (p.nwg > 128) hipLaunchKernelGGL (k_gmean, dim3 (1, p.batch), dim3 (1024), 0, s, p);
     hipLaunchKernelGGL (k_sij, dim3 (((p.G + 511) / 512) * 8, p.batch), dim3 (64), 0, s, (const float4 *) p.PF, (const float4 *) p.PM, (const float4 *) p.mpart, p.st,
                         p.m, p.G, p.nwg, (uint32_t) p.check, p);
 }
 
-void icp_launch_finalize (const icp_params &p, hipStream_t s)
+static void launch_finalize (const icp_params &p, hipStream_t s, icp_tail_kind tail)
 {
-    // point-to-plane (icp_p2pl.hip): the 6 x 6 system and its solve in place of the moments and the rotation solver
-    if (icp_p2pl (p)) { icp_launch_p2pl_solve (p, s); return; }
+    // the plane metrics (icp_p2pl.hip): the 6 x 6 system and its solve in place of the moments and the rotation solver
+    if (tail == ICP_TAIL_PLANE) { icp_launch_p2pl_solve (p, s); return; }
     // the rotation solver is a template parameter (p.rot: 1 power method, else SVD)
-    if (p.fused) {
-        const uint32_t ng = (p.nb + 127u) / 128u;
-        if (ng > ICP_L1_MIN_GROUPS && p.ml1)
-            hipLaunchKernelGGL (k_moment_level1, dim3 ((ICP_NMOM * ng + 15u) / 16u, p.batch), dim3 (256), 0, s, (const double *) p.mom, (const icp_reg_state *) p.st, p.ml1, p.nb, (uint32_t) p.check, p.ng_magic);
-#define FF_LAUNCH(ROT_, REJ_) hipLaunchKernelGGL ((k_finalize_fused<ROT_, REJ_>), dim3 (p.batch), dim3 (1024), 0, s, (const double *) p.mom, p.st, p.nb, (uint32_t) p.check, p)
-        if (icp_rejecting (p)) { if (p.rot == 1) FF_LAUNCH (1, true); else FF_LAUNCH (0, true); }
-        else { if (p.rot == 1) FF_LAUNCH (1, false); else FF_LAUNCH (0, false); }
-#undef FF_LAUNCH
-    } else {
+    if (tail == ICP_TAIL_REFERENCE) {
         if (p.rot == 1) hipLaunchKernelGGL (k_finalize<1>, dim3 (p.batch), dim3 (192), 0, s, (const float *) p.spart, p.st, p.nsp, (uint32_t) p.check, p);
         else hipLaunchKernelGGL (k_finalize<0>, dim3 (p.batch), dim3 (192), 0, s, (const float *) p.spart, p.st, p.nsp, (uint32_t) p.check, p);
+        return;
     }
+    const uint32_t ng = (p.nb + 127u) / 128u;
+    if (tail == ICP_TAIL_FUSED_L1)
+        hipLaunchKernelGGL (k_moment_level1, dim3 ((ICP_NMOM * ng + 15u) / 16u, p.batch), dim3 (256), 0, s, (const double *) p.mom, (const icp_reg_state *) p.st, p.ml1, p.nb, (uint32_t) p.check, p.ng_magic);
+#define FF_LAUNCH(ROT_, REJ_) hipLaunchKernelGGL ((k_finalize_fused<ROT_, REJ_>), dim3 (p.batch), dim3 (1024), 0, s, (const double *) p.mom, p.st, p.nb, (uint32_t) p.check, p)
+    if (icp_rejecting (p)) { if (p.rot == 1) FF_LAUNCH (1, true); else FF_LAUNCH (0, true); }
+    else { if (p.rot == 1) FF_LAUNCH (1, false); else FF_LAUNCH (0, false); }
+#undef FF_LAUNCH
 }
 
 __global__ void k_nop (icp_params p) { if (p.m == 0xFFFFFFFFu) p.st->k = 0; }
 
-// The search of an iteration.  Trimming on (icp_trim.hip): the REJ search stores its per-query outputs every time — the selection reads
-// them —, then k_trim_select and k_trim_apply.  A robust loss on point-to-point takes the same route (icp_apply_pass): k_trim_apply
-// weighs every pair, behind the selection if trimming is on too.  Point-to-plane on (icp_p2pl.hip): the outputs are stored every time too — the moments
-// read them —, and the search takes its reference-order form whatever the reduce mode: the same per-query outputs, and its prologue
-// publishes every iteration's (k, done) to a host-driven run (the fused form leaves a converged registration's word to the fused finalize).
-// One-to-one correspondences on (icp_unique.hip): k_unique_claim and k_unique_resolve right behind the search, so that trimming's
-// candidates are the winners; on point-to-point the apply pass follows whatever else is on (icp_apply_pass).
-// Boundary or normal rejection on (icp_pair_filter.hip): k_pair_filter in front of them, so that a pair it rejects claims no fixed point.
-void icp_launch_search_stage (const icp_params &p, hipStream_t s)
+// the search of an iteration and the passes behind it, as the route says
+static void launch_search_stage (const icp_params &p, hipStream_t s, const icp_route &r)
 {
-    if (!icp_apply_pass (p) && !icp_p2pl (p)) { icp_launch_search (p, s); return; }
+    if (!r.stored) { icp_launch_search (p, s); return; }
     icp_params q = p;
     q.emit = 1;
-    if (icp_p2pl (p)) q.fused = 0;
+    if (r.ref_search) q.fused = 0;
     icp_launch_search (q, s);
-    if (icp_pair_filter (p)) icp_launch_pair_filter (q, s);        // (icp_pair_filter.hip: boundary and normal rejection, in front of everything else that reads the weights)
-    if (icp_unique (p)) icp_launch_unique (q, s);                  // (icp_unique.hip: in front of trimming's selection and of every apply pass)
-    if (icp_apply_pass (p)) icp_launch_trim (q, s);
+    if (r.filter) icp_launch_pair_filter (q, s);
+    if (r.unique) icp_launch_unique (q, s);
+    if (r.select) icp_launch_trim_select (q, s, r.select);
+    if (r.apply == ICP_APPLY_ROBUST) icp_launch_robust_apply (q, s);
+    else if (r.apply == ICP_APPLY_PLAIN) icp_launch_trim_apply (q, s);
 }
 
-// diagnostic: any subset of the iteration's kernels (bit 0 search — with trimming or a point-to-point loss on, select and apply too —, 1 means, 2 sij, 3 finalize, 4 empty kernel)
+// An iteration stage by stage, the only spelling of it: icp_launch_iteration is every stage, the diagnostics (icp_time_masked,
+// icp_profile_run, icp_debug_stamps) take subsets (bit 0 the search with the passes behind it, 1 means, 2 sij, 3 finalize, 4 an empty kernel)
 void icp_launch_masked (const icp_params &p, hipStream_t s, unsigned mask)
 {
-    if (mask & 1u) icp_launch_search_stage (p, s);
-    if ((mask & 2u) && !p.fused) icp_launch_means (p, s);
-    if ((mask & 4u) && !p.fused) icp_launch_sij (p, s);
-    if (mask & 8u) icp_launch_finalize (p, s);
+    const icp_route r = icp_route_of (p);
+    if (mask & 1u) launch_search_stage (p, s, r);
+    if ((mask & 2u) && r.tail == ICP_TAIL_REFERENCE) launch_means (p, s);
+    if ((mask & 4u) && r.tail == ICP_TAIL_REFERENCE) launch_sij (p, s);
+    if (mask & 8u) launch_finalize (p, s, r.tail);
     if (mask & 16u) hipLaunchKernelGGL (k_nop, dim3 (256, p.batch), dim3 (64), 0, s, p);
 }
 
-// chained fused run: begin, one launch per iteration, end (icp_chain_supported: second tree level fits 32 groups)
-// Measured at |F|=|M|=16384: the replicated prologue (every block fetching the 36 KB of fresh moment partials)
-// costs more than the launch boundary it removes (15.7 vs 14.9 us per iteration), so the chain is opt-in.
-// One launch per iteration (fused mode): p.chain = 0 never, 1 automatic (latency-bound sizes: the launch boundary it
-// removes outweighs every block re-deriving T), 2 always (sizes the second tree level of the prologue can hold).
-bool icp_chain_supported (const icp_params &p)
-{
-    // (trimming, a point-to-point robust loss, one-to-one correspondences or the pair filter on point-to-point: the apply pass sits between the search and the finalize, which the chained form folds into one launch)
-    // (point-to-plane: its own finalize, no chained form)
-    return p.fused && !icp_apply_pass (p) && !icp_p2pl (p) && p.nb <= 4096u && p.nr <= 1024u && (p.chain == 2 || (p.chain == 1 && !icp_dense (p)));
-}
+void icp_launch_iteration (const icp_params &p, hipStream_t s) { icp_launch_masked (p, s, 15u); }
 
 // launch j of a chain (icp_search.h: ks_launch_chain_one)
 void icp_launch_chain_one (const icp_params &p, hipStream_t s, uint32_t j, bool fresh, bool emit)
@@ -646,14 +673,4 @@ void icp_launch_chain (const icp_params &p, hipStream_t s, uint32_t iterations, 
     for (uint32_t j = 0; j < iterations; ++j)                       // (with checks on, any iteration may be the last executed: every launch emits)
         icp_launch_chain_one (p, s, j, fresh, p.check || j + 1 == iterations);
     icp_launch_chain_end (p, s, iterations);
-}
-
-void icp_launch_iteration (const icp_params &p, hipStream_t s)
-{
-    icp_launch_search_stage (p, s);
-    if (!p.fused) {
-        icp_launch_means (p, s);
-        icp_launch_sij (p, s);
-    }
-    icp_launch_finalize (p, s);
 }

@@ -1,7 +1,7 @@
 // icp_p2pl.hip — the plane system: point-to-plane ICP (icp_set_error_metric, icp_set_normals) and colored ICP (ICP_METRIC_COLORED,
 // icp_set_color_weight; Park, Zhou, Koltun 2017).  include/icp_amd.h states both rules.
 //
-// An iteration with either metric on is: the search stage (icp_launch_search_stage), which stores PF (matched fixed xyz, weight) and PM
+// An iteration with either metric on is: the search stage (icp_route_of, icp_kernels.hip), which stores PF (matched fixed xyz, weight) and PM
 // (transformed moving xyz) every time — rejection and trimming have put their zeros into PF.w already —; k_plane_moments<COLORED> (icp_plane_moments.h), the
 // 27 terms of the linearised 6 x 6 system per pair in double (colored: plus kappa times a photometric term; a robust loss: each part
 // weighed by the loss's omega of its residual) and their tree over blocks

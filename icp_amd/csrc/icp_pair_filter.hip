@@ -1,5 +1,5 @@
 // icp_pair_filter.hip — rejection at the fixed grid's boundary (icp_set_boundary_rejection) and by normal compatibility
-// (icp_set_normal_rejection), include/icp_amd.h: one pass, k_pair_filter, right behind the REJ search (icp_launch_search_stage) and in
+// (icp_set_normal_rejection), include/icp_amd.h: one pass, k_pair_filter, right behind the REJ search (icp_route_of, icp_kernels.hip) and in
 // front of one-to-one correspondences, trimming's selection and every apply pass.  A candidate pair (weight != 0, id < m) that a rule
 // rejects gets the weight +0 in PF.w and is then exactly a rejected pair: the passes behind this one see no candidate in it, the apply
 // pass (icp_trim_apply.h; point-to-point) writes the search blocks' partials again from the weights, and the plane metrics read w in
@@ -19,9 +19,9 @@
 // Counting: the boundary test comes first, a pair is counted once, n = at_boundary + incompatible + accepted.  The blocks of a
 // registration add their integer counts to four running words and then take a ticket; the block that draws the last ticket — every
 // other block's counts are in by then (release / acquire on the ticket, agent scope) — moves the sums into the result words
-// (n, at_boundary, incompatible, accepted: ICP_MEM_PAIR_FILTER) and into the words of the apply pass (0xFFFFFFFE, n, accepted, 0: a
-// threshold every candidate passes and a K that is 0 only when nothing is left — icp_launch_trim), and leaves the running words and
-// the ticket counter zero for the next launch.  Integer sums: nothing depends on the order in which the device gets to the pairs.
+// (n, at_boundary, incompatible, accepted: ICP_MEM_PAIR_FILTER), and leaves the running words and the ticket counter zero for the
+// next launch.  Integer sums: nothing depends on the order in which the device gets to the pairs.  Nothing else reads the words: the
+// apply pass behind the filter accepts every pair that still has a weight (icp_trim_apply.h).
 #include "icp_plane_moments.h"          // (plane_finite_or_zero, plane_rot_normal)
 
 namespace {
@@ -50,14 +50,15 @@ __device__ __forceinline__ bool filter_at_boundary (const float *F, uint32_t id,
 }
 
 // ------------------------------------------------------------------------------------------
-// k_pair_filter — one thread per pair, grid (ceil (m / 256), batch)
+// k_pair_filter — one thread per pair, grid (ceil (m / 256), batch).  result, counts, settings: icp_pair_filter_area / _counts /
+// _settings (icp_kernels.h)
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__ (FILTER_BLOCK) void k_pair_filter (icp_params p, const float4 *nrm, const float4 *nrm_m, uint32_t *area)
+__global__ __launch_bounds__ (FILTER_BLOCK) void k_pair_filter (icp_params p, const float4 *nrm, const float4 *nrm_m, uint32_t *result, uint32_t *counts,
+                                                                const uint32_t *settings)
 {
     __shared__ uint32_t s_cnt[FILTER_BLOCK / 64u][4];
     const uint32_t b = blockIdx.y, t = threadIdx.x, i = blockIdx.x * FILTER_BLOCK + t;
     if (p.check && p.st[b].done) return;                     // (a converged registration: its last iteration's outputs and counts stay)
-    const uint32_t *settings = area + 16u * (size_t) p.batch;
     const float min_cos = __uint_as_float (settings[0]);
     const uint32_t gw = settings[1];
     const bool by_boundary = (p.reject & ICP_REJECT_BOUNDARY_ON) != 0u && gw != 0u, by_normal = (p.reject & ICP_REJECT_NORMAL_ON) != 0u;
@@ -91,7 +92,7 @@ __global__ __launch_bounds__ (FILTER_BLOCK) void k_pair_filter (icp_params p, co
         uint32_t sn = 0u, sb = 0u, si = 0u;
 #pragma unroll
         for (uint32_t v = 0; v < FILTER_BLOCK / 64u; ++v) { sn += s_cnt[v][0]; sb += s_cnt[v][1]; si += s_cnt[v][2]; }
-        uint32_t *run = area + 8u * (size_t) p.batch + 8u * b;
+        uint32_t *run = counts + 8u * b;
         if (sn) __hip_atomic_fetch_add (run + 0, sn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (sb) __hip_atomic_fetch_add (run + 1, sb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (si) __hip_atomic_fetch_add (run + 2, si, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -101,10 +102,8 @@ __global__ __launch_bounds__ (FILTER_BLOCK) void k_pair_filter (icp_params p, co
             const uint32_t nb = __hip_atomic_exchange (run + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const uint32_t ni = __hip_atomic_exchange (run + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store (run + 4, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t acc = n - nb - ni;
-            uint32_t *out = area + 4u * b, *apply = area + 4u * (size_t) p.batch + 4u * b;
-            out[0] = n; out[1] = nb; out[2] = ni; out[3] = acc;
-            apply[0] = 0xFFFFFFFEu; apply[1] = n; apply[2] = acc; apply[3] = 0u;
+            uint32_t *out = result + 4u * b;
+            out[0] = n; out[1] = nb; out[2] = ni; out[3] = n - nb - ni;
         }
     }
 }
@@ -115,5 +114,5 @@ void icp_launch_pair_filter (const icp_params &p, hipStream_t s)
 {
     const dim3 grid ((p.m + FILTER_BLOCK - 1u) / FILTER_BLOCK, p.batch);
     hipLaunchKernelGGL (k_pair_filter, grid, dim3 (FILTER_BLOCK), 0, s, p, (const float4 *) icp_normals_f (p), (const float4 *) icp_normals_m (p),
-                        icp_pair_filter_area (p));
+                        icp_pair_filter_area (p), icp_pair_filter_counts (p), icp_pair_filter_settings (p));
 }

@@ -49,24 +49,31 @@ int set_device (icp_context *h)
 // nodes' arguments; instantiating anew costs milliseconds) — same topology by construction, re-instantiated only if the update is refused.
 // fresh: the graph starts the registration from the identity transform (icp_reset_transform + the run as one graph; the
 // chained form folds the reset into its first launch).  with_build: buildRBC in front of the run.
+// A fixed-length run enqueued on the handle's stream, captured into a graph (get_graph) or as it stands (launch_run's diagnostic
+// branch): the build, the reset of a fresh run, the chain or the loop of iterations — the per-query outputs stored by the last one only,
+// or by every one when any may be the last executed (checks on) —, and for checked runs the states' copy to the pinned mirror.
+static hipError_t enqueue_fixed_run (icp_context *h, uint32_t iterations, int check, bool fresh, bool with_build)
+{
+    icp_params p = h->p;
+    p.check = check; p.hmirror = nullptr; p.hstate = nullptr;
+    if (with_build) icp_launch_build_rbc (p, h->stream);
+    if (icp_route_of (p).chained) icp_launch_chain (p, h->stream, iterations, fresh);     // one launch per iteration; the first folds the reset in
+    else {
+        if (fresh) icp_launch_reset_state (p, h->stream, 1);
+        for (uint32_t k = 0; k < iterations; ++k) {
+            p.emit = (check || k + 1 == iterations) ? 1 : 0;
+            icp_launch_iteration (p, h->stream);
+        }
+    }
+    return check ? hipMemcpyAsync (h->hState, p.st, sizeof (icp_reg_state) * p.batch, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
+}
+
 int get_graph (icp_context *h, uint32_t iterations, int check, hipGraphExec_t *out, bool fresh, bool with_build)
 {
     uint64_t key = ((uint64_t) iterations << 3) | (uint64_t) (check ? 4 : 0) | (uint64_t) h->parity | ((uint64_t) (fresh ? 1 : 0) << 62) | ((uint64_t) (with_build ? 1 : 0) << 61);
     auto it = h->graphs.find (key);
     if (it != h->graphs.end () && it->second.gen == h->param_gen) { it->second.used = ++h->graph_clock; *out = it->second.exec; return ICP_OK; }
-    icp_params p = h->p;
-    p.check = check; p.hmirror = nullptr; p.hstate = nullptr;
-    auto launches = [&] {
-        if (with_build) icp_launch_build_rbc (p, h->stream);
-        if (fresh && !icp_chain_supported (p)) icp_launch_reset_state (p, h->stream, 1);
-        if (icp_chain_supported (p)) icp_launch_chain (p, h->stream, iterations, fresh);   // one launch per iteration
-        else for (uint32_t k = 0; k < iterations; ++k) {
-            p.emit = (check || k + 1 == iterations) ? 1 : 0;            // (with checks on, any iteration may be the last executed)
-            icp_launch_iteration (p, h->stream);
-        }
-        // checked graphs: the states travel to the pinned mirror as the last node of the graph
-        if (check) (void) hipMemcpyAsync (h->hState, p.st, sizeof (icp_reg_state) * p.batch, hipMemcpyDeviceToHost, h->stream);
-    };
+    auto launches = [&] { (void) enqueue_fixed_run (h, iterations, check, fresh, with_build); };   // (capture_graph reports what failed)
     if (it != h->graphs.end ()) {                                       // stale parameters: update the executable graph in place
         graph_entry ng;
         int rc = capture_graph (h, launches, &ng, false);
@@ -238,26 +245,17 @@ int run_close_all (icp_context *h)
 // Launches the graph of a run.
 int launch_run (icp_context *h, uint32_t iterations, int check, bool fresh, bool with_build)
 {
-    {   // diagnostic (ICP_AMD_RUN_GRAPH=0): the same launches enqueued one by one instead of as a cached graph
-        static const char *e = std::getenv ("ICP_AMD_RUN_GRAPH");
-        if (e && e[0] == '0') {
-            icp_params p = h->p; p.check = check; p.hmirror = nullptr; p.hstate = nullptr;
-            if (with_build) icp_launch_build_rbc (p, h->stream);
-            if (fresh && !icp_chain_supported (p)) icp_launch_reset_state (p, h->stream, 1);
-            if (icp_chain_supported (p)) icp_launch_chain (p, h->stream, iterations, fresh);
-            else for (uint32_t k = 0; k < iterations; ++k) { p.emit = (check || k + 1 == iterations) ? 1 : 0; icp_launch_iteration (p, h->stream); }
-            if (check) HIPCHK (h, hipMemcpyAsync (h->hState, p.st, sizeof (icp_reg_state) * p.batch, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK (h, hipGetLastError ());
-            h->hstate_fresh = check != 0; h->hstate_here = false;
-            h->k_base = check ? -1 : (fresh || with_build) ? (long long) iterations : (h->k_base >= 0 ? h->k_base + iterations : -1);
-            note_outputs_stored (h);
-            return ICP_OK;
-        }
+    // diagnostic (ICP_AMD_RUN_GRAPH=0): the same launches enqueued one by one instead of as a cached graph
+    static const char *e = std::getenv ("ICP_AMD_RUN_GRAPH");
+    if (e && e[0] == '0') {
+        HIPCHK (h, enqueue_fixed_run (h, iterations, check, fresh, with_build));
+        HIPCHK (h, hipGetLastError ());
+    } else {
+        hipGraphExec_t exec;
+        int rc = get_graph (h, iterations, check, &exec, fresh, with_build);
+        if (rc) return rc;
+        HIPCHK (h, hipGraphLaunch (exec, h->stream));
     }
-    hipGraphExec_t exec;
-    int rc = get_graph (h, iterations, check, &exec, fresh, with_build);
-    if (rc) return rc;
-    HIPCHK (h, hipGraphLaunch (exec, h->stream));
     h->hstate_fresh = check != 0; h->hstate_here = false;
     h->k_base = check ? -1 : (fresh || with_build) ? (long long) iterations : (h->k_base >= 0 ? h->k_base + iterations : -1);
     note_outputs_stored (h);
@@ -292,10 +290,10 @@ int materialize_outputs (icp_context *h, int mem)
     if (!h->outputs_stale) return ICP_OK;
     icp_params q = h->p;
     q.st = q.st_prev; q.check = 0; q.emit = 1; q.hmirror = nullptr; q.hstate = nullptr;
-    // (with an apply pass — trimming, a point-to-point robust loss: icp_apply_pass — the outputs are never left to this: run_begin stores
-    // them every iteration, and the setters materialise before they switch.  The stage here is defensive, so that the weights read back
-    // are the applied ones whatever path gets here)
-    icp_launch_search_stage (q, h->stream);
+    // (a route that stores the outputs — icp_route::stored — never leaves them to this: run_begin stores them every iteration, and the
+    // setters materialise before they switch.  The whole search stage here is defensive, so that the weights read back are the applied
+    // ones whatever path gets here)
+    icp_launch_masked (q, h->stream, 1u);
     HIPCHK (h, hipGetLastError ());
     h->outputs_stale = false;
     return ICP_OK;

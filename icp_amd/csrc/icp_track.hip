@@ -353,7 +353,7 @@ static int track_submit (icp_context *h, const void *cloud, int warm_start, bool
     // gated: registration f lives in run slot f & 1 on stream f & 1; its predecessor (f - 1) in the other slot, possibly still open
     // (the release of the sequence word lives in the chained kernel: other forms — reference-order reductions, |R| > 1024 — stay host-ordered)
     // (and the blocking icp_track_next has nothing to overlap: it stays on one stream and spares itself the gate)
-    const bool gated = !blocking && h->run_adaptive && h->track_gate && h->rbc2_ready && icp_chain_supported (h->p);
+    const bool gated = !blocking && h->run_adaptive && h->track_gate && h->rbc2_ready && icp_route_of (h->p).chained;
     if (gated != h->track_last_gated) {                                 // the form changes in mid-sequence (a mode was switched): start from a drained device
         if ((rc = run_close_all (h))) return rc;
         if (h->stream2) HIPCHK (h, hipStreamSynchronize (h->stream2));
@@ -525,7 +525,7 @@ int icp_track_form (icp_handle h, int *gated) try
     if (!gated) return fail (h, ICP_EINVAL, "null output");
     if ((rc = set_device (h))) return rc;
     if (h->run_adaptive && h->track_gate && h->p.m == 16384u && h->p.batch == 1u && h->ownF && h->ownM && (rc = track_prepare (h))) return rc;   // (runs the probe)
-    *gated = (h->run_adaptive && h->track_gate && h->rbc2_ready && icp_chain_supported (h->p)) ? 1 : 0;
+    *gated = (h->run_adaptive && h->track_gate && h->rbc2_ready && icp_route_of (h->p).chained) ? 1 : 0;
     return ICP_OK;
 }
 ICP_CATCH_ALL

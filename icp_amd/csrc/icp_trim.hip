@@ -1,13 +1,16 @@
 // icp_trim.hip — trimmed ICP (icp_set_trimming, include/icp_amd.h): every iteration keeps the closest fraction ξ of the pairs that
 // correspondence rejection leaves, and gives the rest the weight +0.
 //
-// An iteration with trimming on is: the REJ search (icp_search_rej.hip), which stores its per-query outputs; k_trim_select, which finds
-// per registration n (the candidates), K = ceil (ξ n) and t, the K-th smallest key; k_trim_apply, which zeroes the weights of the pairs
-// above t and rewrites the search blocks' partials in exactly the order the search wrote them; then the unchanged tail of the iteration
+// An iteration with trimming on is (icp_route_of, icp_kernels.hip): the REJ search (icp_search_rej.hip), which stores its per-query
+// outputs; the selection (icp_launch_trim_select: k_trim_select), which finds per registration n (the candidates), K = ceil (ξ n) and t,
+// the K-th smallest key; the apply pass (icp_launch_trim_apply: k_trim_apply), which zeroes the weights of the pairs above t and rewrites
+// the search blocks' partials in exactly the order the search wrote them; then the unchanged tail of the iteration
 // (k_finalize_fused<ROT, true>, or k_means / k_sij / k_finalize).  A trimmed pair is then exactly a rejected pair, and the oracle's
 // pieces with the trimmed rows zeroed give the same bits.  None of the existing kernels carries any of this code.
 //
 // The key of a pair and the apply pass are in icp_trim_apply.h (a point-to-point robust loss instantiates the pass in icp_robust.hip).
+// The pass also runs with trimming off, behind the pair filter or one-to-one correspondences on point-to-point: it then accepts every
+// candidate they left and reads none of trimming's words.
 //
 // The selection is a radix select on 11 / 11 / 10-bit digits: a histogram of the digit over the keys that match the digits picked so
 // far, then the bin that holds the remaining rank.  Up to ICP_TRIM_ONE_BLOCK_MAX pairs per registration one workgroup does all three
@@ -192,27 +195,20 @@ __global__ __launch_bounds__ (64) void k_trim_apply (icp_params p, const uint32_
 
 }  // namespace
 
-uint32_t icp_trim_launches (const icp_params &p)
-{
-    return (icp_trimming (p) ? (p.m <= ICP_TRIM_ONE_BLOCK_MAX ? 1u : 3u) : 0u) + 1u;
-}
-
-void icp_launch_trim (const icp_params &p, hipStream_t s)
+// the selection: one workgroup's up to ICP_TRIM_ONE_BLOCK_MAX pairs per registration, three multi-workgroup passes beyond (launches: icp_route::select)
+void icp_launch_trim_select (const icp_params &p, hipStream_t s, uint32_t launches)
 {
     uint32_t *area = icp_trim_area (p);
-    if (!icp_trimming (p)) {}
-    else if (p.m <= ICP_TRIM_ONE_BLOCK_MAX) hipLaunchKernelGGL (k_trim_select, dim3 (1, p.batch), dim3 (1024), 0, s, p, area);
-    else {
-        const dim3 grid ((p.m + 2047u) / 2048u, p.batch);
-        hipLaunchKernelGGL (k_trim_select_pass<0>, grid, dim3 (256), 0, s, p, area);
-        hipLaunchKernelGGL (k_trim_select_pass<1>, grid, dim3 (256), 0, s, p, area);
-        hipLaunchKernelGGL (k_trim_select_pass<2>, grid, dim3 (256), 0, s, p, area);
-    }
-    // (a robust loss on the plane metrics weighs its pairs in k_plane_moments: the apply pass is trimming's alone there)
-    if (icp_robust (p) != 0u && !icp_p2pl (p)) { icp_launch_robust_apply (p, s); return; }
-    // (one-to-one correspondences alone: the resolve pass has left words that accept every candidate — icp_unique_area)
-    // (the pair filter alone — icp_pair_filter.hip — has left such words too: icp_pair_filter_apply_area)
-    if (!icp_trimming (p)) area = icp_unique (p) ? icp_unique_area (p) : icp_pair_filter_apply_area (p);
-    if (p.fused) hipLaunchKernelGGL (k_trim_apply<true>, dim3 (p.nb, p.batch), dim3 (64), 0, s, p, (const uint32_t *) area, icp_tpr_magic (p.side));
-    else hipLaunchKernelGGL (k_trim_apply<false>, dim3 (2 * p.nwg, p.batch), dim3 (64), 0, s, p, (const uint32_t *) area, icp_tpr_magic (p.side));
+    if (launches == 1u) { hipLaunchKernelGGL (k_trim_select, dim3 (1, p.batch), dim3 (1024), 0, s, p, area); return; }
+    const dim3 grid ((p.m + 2047u) / 2048u, p.batch);
+    hipLaunchKernelGGL (k_trim_select_pass<0>, grid, dim3 (256), 0, s, p, area);
+    hipLaunchKernelGGL (k_trim_select_pass<1>, grid, dim3 (256), 0, s, p, area);
+    hipLaunchKernelGGL (k_trim_select_pass<2>, grid, dim3 (256), 0, s, p, area);
+}
+
+void icp_launch_trim_apply (const icp_params &p, hipStream_t s)
+{
+    const uint32_t *area = icp_trim_area (p);
+    if (p.fused) hipLaunchKernelGGL (k_trim_apply<true>, dim3 (p.nb, p.batch), dim3 (64), 0, s, p, area, icp_tpr_magic (p.side));
+    else hipLaunchKernelGGL (k_trim_apply<false>, dim3 (2 * p.nwg, p.batch), dim3 (64), 0, s, p, area, icp_tpr_magic (p.side));
 }

@@ -1,7 +1,11 @@
 // icp_trim_apply.h — the pass that rewrites the weights behind the search (include/icp_amd.h: trimming, the robust loss) and the key of
 // a pair.  The pass is trim_apply<FUSED, ROBUST> below, one body behind two __global__ names: k_trim_apply<FUSED> in icp_trim.hip
-// (ROBUST false: trimming alone, or one-to-one correspondences alone) and k_trim_apply_robust<FUSED> in icp_robust.hip (true: a
+// (ROBUST false: trimming, the pair filter, one-to-one correspondences) and k_trim_apply_robust<FUSED> in icp_robust.hip (true: a
 // point-to-point robust loss), so that each translation unit keeps its own kernel list.
+//
+// One acceptance rule for both: a pair is accepted iff it is a candidate and, with trimming on, among the K closest (key <= t, K != 0).
+// icp_trimming (p) is a uniform test of the kernel argument p.reject; trimming's words (area = icp_trim_area (p), always) are read under
+// it only.  With trimming off the pass accepts every candidate the passes in front of it left: nobody forges words for it.
 //
 // The key of a pair is the bit pattern of its geo = (ex - f0)^2 + (ey - f1)^2 + (ez - f2)^2 in fp32, summed in that order (the
 // translation units are built with -ffp-contract=off): a non-negative float orders as its bits do as uint32.  A pair that is no
@@ -25,8 +29,8 @@ __device__ __forceinline__ uint32_t trim_key (float4 f, float4 q)
 // trim_apply<FUSED, ROBUST> — one wave per block of the search, grid (nb | 2 nwg, batch), launch bounds 64.  Pair e of the block is the
 // search's query e (fused: fused_query_index of tile blockIdx.x; reference order: group blockIdx.x / 2, parity blockIdx.x & 1).  A
 // trimmed pair's weight becomes +0 in PF.w (the W output).  ROBUST (a point-to-point robust loss, icp_set_robust_loss): an accepted
-// pair's weight becomes W' = (float) ((double) w * omega (geo / k^2)), k = *icp_robust_scale (p) — with trimming off every candidate is
-// accepted —, and a W' of 0 makes it a rejected pair.  Then the block's partials are written again from PF / PM as ks_epilogue
+// pair's weight becomes W' = (float) ((double) w * omega (geo / k^2)), k = *icp_robust_scale (p), and a W' of 0 makes it a rejected
+// pair.  Then the block's partials are written again from PF / PM as ks_epilogue
 // computes them: the 18 double moments of its 64 pairs (an accepted pair's terms from the same floats, a trimmed pair's exact zeros)
 // through the same halving tree into p.mom's slot of the tile, or the weight partial (row_tree4) into p.wpart.
 // ------------------------------------------------------------------------------------------
@@ -37,15 +41,15 @@ __device__ __forceinline__ void trim_apply (icp_params p, const uint32_t *area, 
     __shared__ float s_w[64];
     const uint32_t b = blockIdx.y, lane = threadIdx.x, m = p.m;
     if (p.check && p.st[b].done) return;
-    const uint32_t t = area[4u * b], K = area[4u * b + 2u];
     const uint32_t i = FUSED ? fused_query_index (m, p.side, tpr_magic, blockIdx.x, lane) : (blockIdx.x >> 1) * 128u + 2u * lane + (blockIdx.x & 1u);
     const bool v = i < m;
     float4 f = make_float4 (0.f, 0.f, 0.f, 0.f), q = f;
     if (v) { f = p.PF[(size_t) b * m + i]; q = p.PM[(size_t) b * m + i]; }
     const uint32_t key = v ? trim_key (f, q) : TRIM_NONE;
-    bool acc = key != TRIM_NONE && K != 0u && key <= t;
+    // acc = key != TRIM_NONE && (!icp_trimming (p) || (K != 0u && key <= t)), trimming's words read under the uniform test only
+    bool acc = key != TRIM_NONE;
+    if (icp_trimming (p)) { const uint32_t t = area[4u * b], K = area[4u * b + 2u]; acc = acc && K != 0u && key <= t; }
     if constexpr (ROBUST) {
-        if (!icp_trimming (p)) acc = key != TRIM_NONE;           // (trimming off: every candidate; its words are not read)
         const double k = (double) *icp_robust_scale (p), k2 = k * k, u = (double) __uint_as_float (key) / k2;
         const float wr = acc ? (float) ((double) f.w * icp_robust_omega (icp_robust (p), u)) : 0.f;
         if (v && f.w != 0.f) reinterpret_cast<float *> (p.PF + (size_t) b * m + i)[3] = wr;

@@ -6,7 +6,8 @@
 // which pair i is the winner of its fixed point when claim[b][id_i] == key_i, a loser's weight becomes +0 in PF.w, and the
 // registration's (candidates, winners) are counted; then trimming's selection (when trimming is on too: its candidates are the winners)
 // and the apply pass (icp_trim_apply.h), which writes the search blocks' partials again from PF / PM — point-to-point only: the plane
-// metrics read w in k_plane_moments —; then the unchanged tail of the iteration.  None of the existing kernels carries any of this code.
+// metrics read w in k_plane_moments —; then the unchanged tail of the iteration (the order: icp_route_of, icp_kernels.hip).  None of the
+// existing kernels carries any of this code.
 //
 // Determinism: the winner is the minimum of integers that are all different (the query index is part of the key), and an integer minimum
 // does not depend on the order of arrival.  Nothing else decides a value: the counts are integer sums.
@@ -20,10 +21,9 @@
 // icp_init (which fills the table with 0xFF), buildRBC, reset_transform or a new graph finds it as the last resolve pass left it.  No
 // memset, no extra launch, no second table.
 //
-// The result words of a registration, [batch][4] uint32 (icp_unique_area): (0xFFFFFFFE, n, winners, 0).  k_unique_claim's first thread
-// resets them, k_unique_resolve's blocks add their counts.  They are laid out as k_trim_apply reads trimming's words (t at 0, K at 2): a
-// threshold that every candidate passes and a K that is 0 only when no pair is left, so the apply pass of the rule alone is trimming's
-// own kernel pointed at these words.  ICP_MEM_UNIQUE is words 1 and 2.
+// The result words of a registration, [batch][2] uint32 (icp_unique_area): (n, winners), ICP_MEM_UNIQUE as it is read.  k_unique_claim's
+// first thread resets them, k_unique_resolve's blocks add their counts.  Nothing else reads them: the apply pass behind the rule
+// accepts every pair that still has a weight (icp_trim_apply.h).
 #include "icp_trim_apply.h"             // (TRIM_NONE, trim_key)
 
 namespace {
@@ -48,7 +48,7 @@ __global__ __launch_bounds__ (UNIQUE_BLOCK) void k_unique_claim (icp_params p, u
 {
     const uint32_t b = blockIdx.y, i = blockIdx.x * UNIQUE_BLOCK + threadIdx.x;
     if (p.check && p.st[b].done) return;                     // (a converged registration: its last iteration's outputs stay)
-    if (i == 0u) { uint32_t *out = area + 4u * b; out[0] = 0xFFFFFFFEu; out[1] = 0u; out[2] = 0u; out[3] = 0u; }
+    if (i == 0u) { uint32_t *out = area + 2u * b; out[0] = 0u; out[1] = 0u; }
     if (i >= p.m) return;
     uint32_t id;
     const unsigned long long key = unique_key (p, b, i, &id);
@@ -82,9 +82,9 @@ __global__ __launch_bounds__ (UNIQUE_BLOCK) void k_unique_resolve (icp_params p,
         uint32_t sn = 0u, sw = 0u;
 #pragma unroll
         for (uint32_t v = 0; v < UNIQUE_BLOCK / 64u; ++v) { sn += s_n[v]; sw += s_win[v]; }
-        uint32_t *out = area + 4u * b;
-        if (sn) __hip_atomic_fetch_add (out + 1, sn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (sw) __hip_atomic_fetch_add (out + 2, sw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        uint32_t *out = area + 2u * b;
+        if (sn) __hip_atomic_fetch_add (out + 0, sn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (sw) __hip_atomic_fetch_add (out + 1, sw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 

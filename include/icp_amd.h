@@ -808,7 +808,9 @@ int icp_time_kernels (icp_handle h, uint32_t reps, float *out_ms4);
 
 /* Kernel launches per iteration of the graphs behind icp_run / icp_run_fixed with the current modes and sizes:
  * 4 (reference-order reductions), 2 (fused: search + finalize; 3 beyond |F| = 16384, where the first level of the
- * moment tree is a launch of its own) or 1 (fused, latency-bound sizes: chained, see icp_run_form). */
+ * moment tree is a launch of its own) or 1 (fused, latency-bound sizes: chained, see icp_run_form).  The small second-level
+ * launches of the reference-order reductions (the sum of the weights beyond 65536 pairs, the global means beyond 16384) are not
+ * counted: the "4" holds at every size. */
 int icp_launches_per_iteration (icp_handle h, uint32_t *n);
 
 /* How icp_run / icp_run_fixed execute with the current modes and sizes:

@@ -7,6 +7,8 @@ The bit-for-bit modules of each path run at a few sizes only; this one takes the
   - trimming: the multi-workgroup select (m > 16384) with a partly filled last workgroup, just above the one-workgroup limit, batched
     (each registration its own histogram, arrival counter and keys) and in runs whose registrations stop at different iterations;
   - rejection and trimming at sides that are not a multiple of 8 (fused mode's linear 64-query blocks) and in the dense layouts.
+  - the route of an iteration (form and launch count) for every combination of the opt-in passes, and the apply pass that accepts
+    every candidate (one-to-one and the boundary rule without trimming) at partly filled blocks.
 Every check is teacher-forced: the restatement (tests/p2pl_ref.py, tests/colored_ref.py) or the oracle's pieces are fed the engine's own
 correspondences of the step.  The point-to-plane steps are also compared with numpy's least-squares solution of their own system."""
 import os
@@ -622,4 +624,106 @@ def test_two_normals_metrics_run_batch2_at_a_partial_block(engine, metric, loss)
         assert_bits(g.read(Mem.PLANE_SYSTEM, b), h.read(Mem.PLANE_SYSTEM), "system of registration %d" % b)
         h.close()
     assert ks[0] == 1 and 1 < ks[1] <= 40, ks
+    g.close()
+
+
+# ---- 5. the route of an iteration: form and launch count of every combination of the opt-in passes ----------------------------------
+#
+# Only icp_init and setters: no iteration runs.  The literals follow include/icp_amd.h (icp_launches_per_iteration, icp_run_form and
+# the paragraphs of the setters).  Point-to-point: the tail — 4 launches in reference order; fused 2, or 3 where the first level of the
+# moment tree is a launch of its own (more than 256 blocks of 64 pairs: m = 22500 has 352), or 1 chained launch when no pass is on —
+# plus 1 for the pair filter, 2 for one-to-one (claim, resolve), trimming's selection (1 launch up to 16384 pairs, 3 beyond) and 1
+# apply pass as soon as any of the four is on (the loss adds nothing else).  The plane metrics, whatever the reduce mode: search,
+# moments, finalize = 3, plus 1 for the pair filter, 2 for one-to-one, the selection and its apply pass for trimming, nothing for the
+# loss (the moments weigh the pairs).  The second-level launches of the reference-order reductions (beyond 65536 / 16384 pairs) do
+# not count.  Index = bit 0 the pair filter (the boundary rule), bit 1 one-to-one, bit 2 trimming, bit 3 the robust loss.
+ROUTE_LAUNCHES = {
+    ("p2p", True, 30): [1, 4, 5, 6, 4, 5, 6, 7, 3, 4, 5, 6, 4, 5, 6, 7],
+    ("p2p", True, 150): [1, 5, 6, 7, 7, 8, 9, 10, 4, 5, 6, 7, 7, 8, 9, 10],
+    ("p2p", False, 30): [4, 6, 7, 8, 6, 7, 8, 9, 5, 6, 7, 8, 6, 7, 8, 9],
+    ("p2p", False, 150): [4, 6, 7, 8, 8, 9, 10, 11, 5, 6, 7, 8, 8, 9, 10, 11],
+    ("plane", True, 30): [3, 4, 5, 6, 5, 6, 7, 8, 3, 4, 5, 6, 5, 6, 7, 8],
+    ("plane", True, 150): [3, 4, 5, 6, 7, 8, 9, 10, 3, 4, 5, 6, 7, 8, 9, 10],
+}
+ROUTE_LAUNCHES["plane", False, 30] = ROUTE_LAUNCHES["plane", True, 30]
+ROUTE_LAUNCHES["plane", False, 150] = ROUTE_LAUNCHES["plane", True, 150]
+FORM_SEPARATE, FORM_CHAINED = 0, 1
+
+
+@pytest.mark.parametrize("mask", range(16))
+@pytest.mark.parametrize("side", [30, 150])
+@pytest.mark.parametrize("fused", [True, False])
+@pytest.mark.parametrize("metric", ["p2p", "plane"])
+def test_route_table(engine, metric, fused, side, mask):
+    g = engine.ICP(0)
+    g.init(side * side, 4, A, C_)
+    set_modes(engine, g, power_fast=fused, fused=fused)
+    if metric == "plane":
+        g.set_normals(1, side)                               # Normals.GRID: no data needed
+        g.set_error_metric(engine.ErrorMetric.POINT_TO_PLANE, 0.05)
+    if mask & 1:
+        g.set_boundary_rejection(side)
+    if mask & 2:
+        g.set_unique(True)
+    if mask & 4:
+        g.set_trimming(0.75)
+    if mask & 8:
+        g.set_robust_loss(rref.CAUCHY, rl.SCALE[rref.CAUCHY])
+    chained = metric == "p2p" and fused and mask == 0
+    got = (g.run_form(), g.launches_per_iteration())
+    g.close()
+    assert got == (FORM_CHAINED if chained else FORM_SEPARATE, ROUTE_LAUNCHES[metric, fused, side][mask]), got
+
+
+# ---- 6. the apply pass that accepts every candidate, at the edges of its blocks ----------------------------------------------------
+#
+# One-to-one correspondences alone, the boundary rule alone (grid width = side) and both, with trimming and the loss off: the apply
+# pass keeps every pair the passes in front of it left.  (6, 4): m = 36, one partly filled block of 64 pairs; (30, 4): m = 900, the
+# last block of 64 (fused) and the last group of 128 (reference order) partly filled.  The modules' own checks, bit for bit, and
+# ICP_MEM_UNIQUE / ICP_MEM_PAIR_FILTER against the restatements' counts.
+
+import test_gpu_pair_filter as pf                                # noqa: E402
+import test_gpu_unique as uq                                     # noqa: E402
+import unique_ref                                                # noqa: E402
+
+
+@pytest.mark.parametrize("case", ["unique", "boundary", "both"])
+@pytest.mark.parametrize("side,nr", [(6, 4), (30, 4)])
+@pytest.mark.parametrize("fused", [True, False])
+def test_accept_all_apply_pass_at_block_edges(engine, oracle, fused, side, nr, case):
+    Mem = engine.Memory
+    unique, boundary = case != "boundary", case != "unique"
+    F, M = engine.synth_pair(side)
+    T = _t0()
+    g = pf.make_handle(engine, side, nr, fused, WEIGHTED, POWER, fused, False, boundary, None)
+    if unique:
+        g.set_unique(True)
+    assert g.trimming() == 1.0 and g.robust_loss()[0] == 0
+    R0 = pf.one_step(engine, g, F, M, T)
+    want = oracle_search(oracle, F, M, T, nr)
+    if case == "unique":
+        _, counts = uq.check_step(engine, oracle, g, F, M, T, side, fused, WEIGHTED, POWER, fused, False, want)
+        assert counts[0] == side * side and 0 < counts[1] <= counts[0], counts
+    elif case == "boundary":
+        counts, _ = pf.check_step(engine, oracle, g, F, M, T, R0, side, fused, WEIGHTED, POWER, fused, False, side, None, want)
+        assert counts[0] == side * side and counts[1] > 0 and counts[2] == 0 and counts[3] > 0, counts
+    else:
+        nn_id = g.read(Mem.NN_ID)
+        assert np.array_equal(nn_id["id"], want[0]["id"])
+        _, counts, W0, (_, _, acc) = pf.numpy_rule(engine, g, F, M, R0, True, False, side, None)
+        assert np.array_equal(g.read(Mem.PAIR_FILTER), counts) and counts[1] > 0 and counts[3] > 0, (g.read(Mem.PAIR_FILTER), counts)
+        win, _, ucounts = unique_ref.unique_rule(nn_id["id"], g.read(Mem.NN), g.read(Mem.QT), np.where(acc, W0, np.float32(0)).astype(np.float32))
+        got = g.read(Mem.UNIQUE)
+        assert np.array_equal(got, ucounts) and got[0] == counts[3] and 0 < got[1] <= got[0], (got, ucounts, counts)
+        W, sw, means, S, Tk = trim.expected_pieces(oracle, F, M, T, nn_id, side, fused, True, POWER, fused, ~win)
+        gW = g.read(Mem.W)
+        assert_bits(gW, W, "weights")
+        assert np.all(np.ascontiguousarray(gW[~win]).view(np.uint32) == 0) and np.all(gW[win] != 0)
+        assert_bits(g.read(Mem.SUM_W), np.array([sw]), "sum of weights")
+        assert_bits(g.read(Mem.MEANS), means, "means")
+        assert_bits(g.read(Mem.S), S, "S")
+        gTk = g.read(Mem.TK)
+        nan = np.isnan(Tk)
+        assert np.array_equal(np.isnan(gTk), nan), ("Tk", gTk, Tk)
+        assert_bits(gTk[~nan], Tk[~nan], "Tk")
     g.close()
