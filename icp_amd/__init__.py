@@ -479,6 +479,10 @@ class KernelObject:
     def run(self):
         _kchk(self._L.icp_ko_run(self._k))
 
+    def set_scaling(self, c):
+        """ICPS::setScaling: the factor c of the next run()."""
+        _kchk(self._L.icp_ko_set_scaling(self._k, c))
+
 
 def device_count():
     n = C.c_int(0)
