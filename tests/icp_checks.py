@@ -1,0 +1,631 @@
+"""Step checks shared by the GPU test modules — TEST INFRASTRUCTURE (a plain module: pytest collects nothing from it).
+
+pytest rewrites `assert` only in the modules it collects, so every assert here carries its own message.
+
+1. basics: constants, the bit-for-bit comparison, scenes and the numpy rules several features share;
+2. the reference-order / fused parity checks against a whole OracleICP (parity_make, check_rbc, parity_check_step);
+3. the weight-rule family (rejection, trimming, one-to-one, the pair filter, the robust loss on point-to-point): a feature's numpy rule
+   names the rows that weigh nothing (`zero`), check_pieces compares the step with the oracle's pieces fed those rows zeroed;
+4. the plane family (point-to-plane, colored, plane-to-plane, symmetric, their robust forms): a `restate` callable wraps the metric's
+   float64 restatement, check_last compares the last iteration with it."""
+import functools
+
+import numpy as np
+
+import colored_ref
+import gicp_ref
+import p2pl_ref
+import pair_filter_ref
+import robust_ref
+import sym_ref
+import unique_ref
+
+# ---- 1. basics --------------------------------------------------------------------------------------------------------------------
+
+A, C_ = 2e2, 1e-6
+POWER, EIGEN = 1, 0
+REGULAR, WEIGHTED = 0, 1
+P2P, P2PL, COLORED = 0, 1, 2
+GIVEN, GRID = 0, 1
+MODES = [(POWER, False), (POWER, True), (EIGEN, False)]
+IDENTITY = np.array([0, 0, 0, 1, 0, 0, 0, 1], np.float32)
+IDENTITY.flags.writeable = False
+SIZES = {"small": (32, 64), "A": (128, 256), "B": (256, 1024)}
+STEP_SIZES = [(128, 256), (50, 4), (256, 1024)]                  # m = 16384; 2500 (no multiple of 256); 65536 with nr = 1024
+LOSSES = [robust_ref.HUBER, robust_ref.CAUCHY, robust_ref.TUKEY]
+SCALE = {robust_ref.HUBER: 8.0, robust_ref.CAUCHY: 12.0, robust_ref.TUKEY: 30.0}     # (mm: each cuts into the residuals of the scenes)
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.float64:
+        return a.view(np.uint64)
+    return a.view(np.uint32)
+
+
+def assert_bits(got, want, what):
+    got = np.ascontiguousarray(got)
+    want = np.ascontiguousarray(want)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    bad = np.nonzero(bits(got).reshape(-1) != bits(want).reshape(-1))[0]
+    assert bad.size == 0, "%s: %d of %d words differ, first at %d: got %r want %r" % (
+        what, bad.size, got.size, bad[0], got.reshape(-1)[bad[0]], want.reshape(-1)[bad[0]])
+
+
+def assert_bits_nan(got, want, what):
+    """Bit for bit, except that a NaN of `want` asks for a NaN only (a degenerate S — one accepted pair — leaves the solver's NaN:
+    payload bits are no part of the rule)."""
+    nan = np.isnan(want)
+    assert np.array_equal(np.isnan(got), nan), "%s: the NaN masks differ: got %r want %r" % (what, got, want)
+    assert_bits(got[~nan], want[~nan], what)
+
+
+def set_modes(engine, g, power_fast=False, fused=False):
+    """Explicit modes (the handle's defaults are the benchmarked ones: squared + fused)."""
+    g.setPowerMode(engine.PowerMode.SQUARED if power_fast else engine.PowerMode.LITERAL)
+    g.setReduceMode(engine.ReduceMode.FUSED if fused else engine.ReduceMode.REFERENCE_ORDER)
+
+
+def _t0():
+    """A non-identity starting transform: 1 degree about a skew axis, a few mm."""
+    ax = np.array([0.3, 0.9, 0.1]) / np.linalg.norm([0.3, 0.9, 0.1])
+    h = np.deg2rad(1.0) / 2
+    return np.array([*(np.sin(h) * ax), np.cos(h), 4.0, -3.0, 2.0, 1.0], np.float32)
+
+
+def holes_pair(engine, side, seed, name="blobs30"):
+    """Scene level: the benchmark pair with the invalid points of case `name` in both frames."""
+    from icp_amd import workloads as W
+    return W.holes_pair(engine, name, side, seed=seed)
+
+
+def punch_cloud(engine, X, side, seed):
+    """Cloud level: contiguous (15 %) and scattered (5 %) holes in one set."""
+    X = engine.punch_holes(X, side, side, engine.HOLES_CONTIGUOUS, 0.15, True, seed=seed)
+    return engine.punch_holes(X, side, side, engine.HOLES_SCATTERED, 0.05, True, seed=seed + 1)
+
+
+def messy_grid(engine, side, seed):
+    """A fixed set with holes, NaN / inf coordinates and points at the origin."""
+    F, _ = engine.synth_pair(side, seed=seed)
+    F = punch_cloud(engine, F, side, seed)
+    rng = np.random.default_rng(seed)
+    idx = rng.choice(side * side, 40, replace=False)
+    F[idx[:10], 0] = np.nan
+    F[idx[10:20], 1] = np.inf
+    F[idx[20:30], 2] = -np.inf
+    F[idx[30:], :3] = 0.0
+    return F
+
+
+def _partial_overlap(engine):
+    """synth_pair_scene(128) with a frame-to-frame motion (1 degree, (8, -4, 5) mm) and the last quarter of M's rows moved 150 mm
+    towards the camera: a surface F has no counterpart for."""
+    F, M, T_true = engine.synth_pair_scene(128, rot_deg=1.0, t=(8.0, -4.0, 5.0))
+    M = M.copy()
+    M[np.arange(128 * 128) >= 96 * 128, 2] -= 150.0
+    return F, M, T_true
+
+
+def _outlier_scene(engine):
+    """The curved scene with about 20 % of the moving landmarks gross outliers: a contiguous band of 26 grid rows pulled 300 mm toward
+    the sensor (an occluder only the moving frame sees)."""
+    F, M, T_true = engine.synth_pair_scene(128, engine.SCENE_CURVED)
+    M = M.copy()
+    rows = slice(50 * 128, 76 * 128)
+    z = M[rows, 2].astype(np.float64)
+    f = np.where(z > 0, (z - 300.0) / z, 1.0).astype(np.float32)
+    M[rows, :3] *= f[:, None]
+    return F, M, T_true
+
+
+def _errors(T, T_true):
+    """(rotation error in degrees, translation error in mm) of T against T_true."""
+    from icp_amd import workloads as W
+    return W.rotation_error_deg(T, T_true), float(np.linalg.norm(T[4:7].astype(np.float64) - T_true[4:7].astype(np.float64)))
+
+
+def register(engine, F, M, metric, mu=0.0, kappa=0.0):
+    """(T, k, converged) of a free run of a fresh handle with the metric on."""
+    g = engine.ICP(0)
+    g.init(F.shape[0], 256, A, C_)
+    if metric != P2P:
+        g.set_normals(GRID, int(round(np.sqrt(F.shape[0]))))
+        if metric == COLORED:
+            g.set_color_weight(kappa)
+        g.set_error_metric(metric, mu)
+    load(engine, g, F, M)
+    g.buildRBC()
+    k = g.run()
+    T = g.read(engine.Memory.T).copy()
+    conv = g.state().converged
+    g.close()
+    return T, k, conv
+
+
+def geo_of(PF, PM):
+    g = (PM[:, :3] - PF[:, :3]).astype(np.float32)
+    return (g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2]
+
+
+def rejected_set(M, PF, PM, invalid, max_dist):
+    """The rule of include/icp_amd.h in numpy: M = the moving set (untransformed), PF / PM = (matched fixed xyz, w) / (transformed
+    moving xyz, dist) per query."""
+    rej = np.zeros(M.shape[0], bool)
+    if invalid:
+        rej |= (M[:, :3] == 0).all(axis=1) | (PF[:, :3] == 0).all(axis=1)
+    if max_dist:
+        d2 = np.float32(max_dist) * np.float32(max_dist)
+        rej |= ~(geo_of(PF, PM) <= d2)
+    return rej
+
+
+def trim_rule(PF, PM, W0, keep):
+    """(accepted mask, [t bits, n, K, accepted]) by the rule: candidates are the pairs of weight != 0 (W0: after rejection, before
+    trimming) with a finite geo; K = ceil (keep n); t = the K-th smallest geo; accepted: candidates with geo <= t."""
+    geo = geo_of(PF, PM)
+    cand = (W0 != 0) & np.isfinite(geo)
+    n = int(np.count_nonzero(cand))
+    if n == 0:
+        return np.zeros(PF.shape[0], bool), np.zeros(4, np.uint32)
+    K = min(int(np.ceil(np.float64(np.float32(keep)) * n)), n)
+    t = np.sort(geo[cand])[K - 1]
+    acc = cand & (geo <= t)
+    return acc, np.array([t.view(np.uint32), n, K, np.count_nonzero(acc)], np.uint32)
+
+
+def search_weights(nn_id, weighted):
+    """The weights of the search's distances: 100 / (100 + dist), or ones in REGULAR mode."""
+    dist = nn_id["dist"].astype(np.float32)
+    return (np.float32(100.0) / (np.float32(100.0) + dist)).astype(np.float32) if weighted else np.ones_like(dist)
+
+
+def weights_before_trim(nn_id, M, PF, PM, weighted, invalid, max_dist=None):
+    W0 = search_weights(nn_id, weighted)
+    W0[rejected_set(M, PF, PM, invalid, max_dist)] = 0.0
+    return W0
+
+
+def oracle_search(oracle, F, M, T, nr):
+    o = oracle.OracleICP(F.shape[0], nr, A, C_, threads=8)
+    o.write_f(F); o.write_m(M); o.build_rbc(); o.write_t(T)
+    o.step()
+    return o.nn_id, o.rid
+
+
+def pick_max_dist(oracle, F, M, T, nr, frac=0.12):
+    """A distance that rejects about `frac` of the pairs whose endpoints are both valid, at T."""
+    nn_id, _ = oracle_search(oracle, F, M, T, nr)
+    tM = oracle.transform_q(M, T)
+    NN = F[nn_id["id"]]
+    ok = ~((M[:, :3] == 0).all(axis=1) | (NN[:, :3] == 0).all(axis=1))
+    g = (tM[:, :3] - NN[:, :3]).astype(np.float64)
+    geo = (g * g).sum(axis=1)[ok]
+    return float(np.sqrt(np.quantile(geo, 1.0 - frac)))
+
+
+@functools.lru_cache(maxsize=None)
+def _scene(side, nr, name):
+    import icp_amd as engine
+    from oracle import oracle
+    F, M = engine.synth_pair(side) if name == "clean" else holes_pair(engine, side, 0x1C9D5EED)
+    T = _t0()
+    nn_id, rid = oracle_search(oracle, F, M, T, nr)
+    for a in (F, M, T, nn_id, rid):
+        a.flags.writeable = False
+    return F, M, T, name == "holes", (nn_id, rid)
+
+
+def scene(engine, oracle, side, nr, name):
+    """(F, M, T, invalid flag, the oracle's (nn_id, rid) at T) of the "clean" pair or the blobs30 "holes" pair, read-only: built and
+    searched once per session.  (engine and oracle are the session's fixtures: asking for them builds both libraries first.)"""
+    return _scene(side, nr, name)
+
+
+def scenes_A(engine, oracle):
+    """name -> scene at side 128 with 256 representatives."""
+    return {name: scene(engine, oracle, 128, 256, name) for name in ("clean", "holes")}
+
+
+# ---- 2. parity against a whole OracleICP --------------------------------------------------------------------------------------
+
+def parity_make(engine, oracle, side, nr, rot=1, weighted=1, power_fast=False, zero_fraction=0.0, seed=0x1C9D5EED,
+                max_iterations=40, fused=False):
+    m = side * side
+    F, M = engine.synth_pair(side, seed=seed, zero_fraction=zero_fraction)
+    g = engine.ICP(0, rot, weighted)
+    g.init(m, nr, A, C_, max_iterations=max_iterations)
+    set_modes(engine, g, power_fast, fused)
+    g.write(engine.Memory.F, F)
+    g.write(engine.Memory.M, M)
+    o = oracle.OracleICP(m, nr, A, C_, rot=rot, weighted=weighted, power_fast=power_fast, threads=8,
+                         max_iterations=max_iterations, fused=fused)
+    o.write_f(F)
+    o.write_m(M)
+    return g, o, F, M
+
+
+def check_rbc(engine, g, o):
+    Mem = engine.Memory
+    assert_bits(g.read(Mem.REPS), o.reps, "representatives")
+    assert np.array_equal(g.read(Mem.RBC_OWNER), o.rbc_owner), "owner"
+    assert np.array_equal(g.read(Mem.RBC_N), o.rbc_N), "N"
+    assert np.array_equal(g.read(Mem.RBC_O), o.rbc_O), "O"
+    assert np.array_equal(g.read(Mem.RBC_PERM), o.rbc_perm), "perm"
+
+
+def parity_check_step(engine, g, o, weighted=True):
+    Mem = engine.Memory
+    assert np.array_equal(g.read(Mem.RID), o.rid), "nearest representative"
+    gn, on = g.read(Mem.NN_ID), o.nn_id
+    assert np.array_equal(gn["id"], on["id"]), "correspondence ids: %d differ" % np.count_nonzero(gn["id"] != on["id"])
+    assert_bits(gn["dist"], on["dist"], "correspondence distances")
+    if weighted:
+        assert_bits(g.read(Mem.W), o.W, "weights")
+        assert_bits(g.read(Mem.SUM_W), np.array([o.sum_w]), "sum of weights")
+    assert_bits(g.read(Mem.MEANS), o.means, "means")
+    assert_bits(g.read(Mem.S), o.S, "S")
+    assert_bits(g.read(Mem.TK), o.Tk, "Tk")
+    assert_bits(g.read(Mem.RK).reshape(3, 3), o.Rk, "Rk")
+    assert_bits(g.read(Mem.R).reshape(3, 3), o.R, "R")
+    assert_bits(g.read(Mem.T), o.T, "T")
+
+
+# ---- 3. the weight-rule family ------------------------------------------------------------------------------------------------
+
+def make_handle(engine, m, nr, fused, weighted, rot, power_fast, batch=1, max_iterations=40, rejection=None, boundary=None,
+                normal_rejection=None, unique=None, trimming=None, robust_loss=None):
+    """A point-to-point handle with explicit modes.  The options are applied in this order, each only when given (not None):
+    rejection = (invalid, max_dist); boundary = grid width; normal_rejection = (grid width of the GRID normals, min_cos);
+    unique = flag; trimming = keep; robust_loss = (loss, scale)."""
+    g = engine.ICP(0, rot, weighted)
+    g.init(m, nr, A, C_, max_iterations, batch=batch)
+    set_modes(engine, g, power_fast, fused)
+    if rejection is not None:
+        g.set_rejection(*rejection)
+    if boundary is not None:
+        g.set_boundary_rejection(boundary)
+    if normal_rejection is not None:
+        g.set_normals(GRID, normal_rejection[0])
+        g.set_normal_rejection(normal_rejection[1])
+    if unique is not None:
+        g.set_unique(unique)
+    if trimming is not None:
+        g.set_trimming(trimming)
+    if robust_loss is not None:
+        g.set_robust_loss(*robust_loss)
+    return g
+
+
+def only_invalid(invalid):
+    """make_handle's rejection option for "the invalid-point rule when the scene has holes, else untouched"."""
+    return (True, None) if invalid else None
+
+
+def one_step(engine, g, F, M, T):
+    """Load the pair, build, start at T, step.  Returns R as the step's search used it."""
+    g.write(engine.Memory.F, F); g.write(engine.Memory.M, M)
+    g.buildRBC()
+    g.write(engine.Memory.T, T, block=True)
+    R0 = g.read(engine.Memory.R).ravel().copy()
+    g.step()
+    return R0
+
+
+def step_batch(engine, g, pairs, T):
+    """one_step for a handle of len (pairs) registrations, all from T."""
+    for b, (F, M) in enumerate(pairs):
+        g.write(engine.Memory.F, F, batch_index=b); g.write(engine.Memory.M, M, batch_index=b)
+    g.buildRBC()
+    for b in range(len(pairs)):
+        g.write(engine.Memory.T, T, batch_index=b, block=True)
+    g.step()
+
+
+def correspondences(engine, g, want=None, b=0):
+    """The nn_id the rules and the oracle's pieces are fed: the oracle's (want = its (nn_id, rid); check_pieces compares the engine's
+    with it) or, without one, the engine's own."""
+    return want[0] if want is not None else g.read(engine.Memory.NN_ID, batch_index=b)
+
+
+def expected_pieces(oracle, F, M, T, nn_id, side, fused, weighted, rot, power_fast, zero, weights=None):
+    """(W, sum_w, means, S, Tk) of one step at T from the oracle's pieces with the rows `zero` (trimmed, rejected, ..) zeroed.
+    weights: arbitrary weights W' in place of the search's (the robust loss; in reference order sum W is then
+    robust_ref.sum_w_reference, orc_weights' tree over arbitrary weights)."""
+    tM = oracle.transform_q(M, T)
+    NNz, tMz = np.ascontiguousarray(F[nn_id["id"]]), tM.copy()
+    NNz[zero] = 0.0
+    tMz[zero] = 0.0
+    if fused or weights is not None:
+        W = search_weights(nn_id, weighted) if weights is None else weights
+        if weights is None:
+            W[zero] = 0.0
+    if fused:
+        sw, means, S = oracle.moments_fused(NNz, tMz, W, side, C_)
+    else:
+        if weights is None:
+            D = nn_id.copy()
+            if not weighted:
+                D["dist"] = 0.0                      # 100 / (100 + 0) = 1: the weights of REGULAR mode, w in {0, 1}
+            D["dist"][zero] = np.inf                 # 100 / (100 + inf) = +0
+            W, sw = oracle.weights(D)
+        else:
+            sw = robust_ref.sum_w_reference(W)
+        means = oracle.mean_weighted(NNz, tMz, W, sw)
+        DF, DM = oracle.devs(NNz, tMz, means)
+        S = oracle.sij(DM, DF, W, C_)
+    if rot == POWER:
+        Tk, _ = oracle.power_method(S, means, fast=power_fast)
+    else:
+        _, Tk = oracle.svd_rotation(S, means)
+    return W, sw, means, S, Tk
+
+
+def check_search(engine, g, want, b=0):
+    """The engine's correspondences, distances and nearest representatives against the oracle's (nn_id, rid)."""
+    Mem = engine.Memory
+    nn_id, rid = want
+    gn = g.read(Mem.NN_ID, batch_index=b)
+    assert np.array_equal(gn["id"], nn_id["id"]), "correspondence ids: %d differ" % np.count_nonzero(gn["id"] != nn_id["id"])
+    assert_bits(gn["dist"], nn_id["dist"], "correspondence distances")
+    assert np.array_equal(g.read(Mem.RID, batch_index=b), rid), "nearest representative"
+
+
+def check_pieces(engine, oracle, g, F, M, T, side, fused, weighted, rot, power_fast, zero, want=None, b=0, weights=None):
+    """The engine's step from T (already taken): the search against the oracle's (want = its (nn_id, rid) at T; None: the engine's own
+    correspondences feed the oracle's pieces), then W, sum W, means, S and Tk bit for bit against expected_pieces with the rows `zero`
+    zeroed, and "a row in zero has the weight +0".  Returns the expected W."""
+    Mem = engine.Memory
+    if want is not None:
+        check_search(engine, g, want, b)
+    nn_id = correspondences(engine, g, want, b)
+    W, sw, means, S, Tk = expected_pieces(oracle, F, M, T, nn_id, side, fused, weighted, rot, power_fast, zero, weights)
+    gW = g.read(Mem.W, batch_index=b)
+    assert_bits(gW, W, "weights")
+    nonzero = np.count_nonzero(np.ascontiguousarray(gW[zero]).view(np.uint32))
+    assert nonzero == 0, "a trimmed, rejected or losing pair's weight is +0: %d are not" % nonzero
+    assert_bits(g.read(Mem.SUM_W, batch_index=b), np.array([sw]), "sum of weights")
+    assert_bits(g.read(Mem.MEANS, batch_index=b), means, "means")
+    assert_bits(g.read(Mem.S, batch_index=b), S, "S")
+    assert_bits_nan(g.read(Mem.TK, batch_index=b), Tk, "Tk")
+    return W
+
+
+def assert_words(engine, g, mem, counts, b=0):
+    """A feature's result words (ICP_MEM_TRIM, ICP_MEM_UNIQUE, ICP_MEM_PAIR_FILTER) against the numpy rule's."""
+    got = g.read(getattr(engine.Memory, mem), batch_index=b)
+    assert np.array_equal(got, counts), "ICP_MEM_%s: got %r want %r" % (mem, got, counts)
+    return got
+
+
+def check_rejection_step(engine, oracle, g, F, M, T, side, nr, fused, weighted, rot, power_fast, invalid, max_dist, b=0):
+    """Rejection: the rejected set of the oracle's search equals the one of the engine's own outputs; then the pieces."""
+    Mem = engine.Memory
+    want = oracle_search(oracle, F, M, T, nr)
+    check_search(engine, g, want, b)
+    NN, tM = F[want[0]["id"]], oracle.transform_q(M, T)
+    rej = rejected_set(M, NN[:, :4], tM[:, :4], invalid, max_dist)
+    PF, PM = g.read(Mem.NN, batch_index=b), g.read(Mem.QT, batch_index=b)
+    assert np.array_equal(rejected_set(M, PF, PM, invalid, max_dist), rej), "rejected set"
+    assert rej.any() and not rej.all(), "rejected set: %d of %d" % (np.count_nonzero(rej), rej.size)
+    check_pieces(engine, oracle, g, F, M, T, side, fused, weighted, rot, power_fast, rej, want, b)
+    return rej
+
+
+def check_trim_step(engine, oracle, g, F, M, T, side, fused, weighted, rot, power_fast, invalid, keep, want=None, b=0):
+    """Trimming: ICP_MEM_TRIM against trim_rule on the engine's own NN / QT, then the pieces.  Returns (accepted, the words)."""
+    Mem = engine.Memory
+    nn_id = correspondences(engine, g, want, b)
+    PF, PM = g.read(Mem.NN, batch_index=b), g.read(Mem.QT, batch_index=b)
+    acc, trim = trim_rule(PF, PM, weights_before_trim(nn_id, M, PF, PM, weighted, invalid), keep)
+    assert_words(engine, g, "TRIM", trim, b)
+    check_pieces(engine, oracle, g, F, M, T, side, fused, weighted, rot, power_fast, ~acc, want, b)
+    return acc, trim
+
+
+def unique_rule_of(engine, g, M, weighted, invalid, b=0, nn_id=None):
+    """(winner mask, rows that weigh nothing, [n, winners], weights before the rule) from the engine's outputs of registration b."""
+    Mem = engine.Memory
+    if nn_id is None:
+        nn_id = g.read(Mem.NN_ID, batch_index=b)
+    PF, PM = g.read(Mem.NN, batch_index=b), g.read(Mem.QT, batch_index=b)
+    W0 = weights_before_trim(nn_id, M, PF, PM, weighted, invalid)
+    win, cand, counts = unique_ref.unique_rule(nn_id["id"], PF, PM, W0)
+    return win, (W0 == 0) | (cand & ~win), counts, W0
+
+
+def check_unique_step(engine, oracle, g, F, M, T, side, fused, weighted, rot, power_fast, invalid, want=None, b=0):
+    """One-to-one: ICP_MEM_UNIQUE, the pieces, and "a winner keeps its weight".  Returns (winners, counts)."""
+    win, zero, counts, _ = unique_rule_of(engine, g, M, weighted, invalid, b, correspondences(engine, g, want, b))
+    assert_words(engine, g, "UNIQUE", counts, b)
+    check_pieces(engine, oracle, g, F, M, T, side, fused, weighted, rot, power_fast, zero, want, b)
+    lost = np.count_nonzero(g.read(engine.Memory.W, batch_index=b)[win] == 0)
+    assert lost == 0, "a winner keeps its weight: %d do not" % lost
+    return win, counts
+
+
+def pair_filter_rule_of(engine, g, F, M, R0, weighted, invalid, gw, min_cos, b=0, nn_id=None):
+    """(rows that weigh nothing, counts, weights before the rules, (at_boundary, incompatible, accepted))."""
+    Mem = engine.Memory
+    if nn_id is None:
+        nn_id = g.read(Mem.NN_ID, batch_index=b)
+    PF, PM = g.read(Mem.NN, batch_index=b), g.read(Mem.QT, batch_index=b)
+    W0 = weights_before_trim(nn_id, M, PF, PM, weighted, invalid)
+    NF = NM = None
+    if min_cos is not None:
+        NF, NM = g.read(Mem.NORMALS_F, batch_index=b), g.read(Mem.NORMALS_M, batch_index=b)
+    bnd, inc, acc, counts = pair_filter_ref.pair_filter(nn_id["id"], W0, F, gw, NF, NM, R0, min_cos)
+    return ~acc, counts, W0, (bnd, inc, acc)
+
+
+def check_pair_filter_step(engine, oracle, g, F, M, T, R0, side, fused, weighted, rot, power_fast, invalid, gw, min_cos, want=None, b=0):
+    """The pair filter: ICP_MEM_PAIR_FILTER, the pieces, "an accepted pair keeps its weight" and the NN output's weights."""
+    Mem = engine.Memory
+    zero, counts, W0, masks = pair_filter_rule_of(engine, g, F, M, R0, weighted, invalid, gw, min_cos, b, correspondences(engine, g, want, b))
+    got = g.read(Mem.PAIR_FILTER, batch_index=b)
+    print("ICP_MEM_PAIR_FILTER", got.tolist(), "numpy", counts.tolist())
+    assert_words(engine, g, "PAIR_FILTER", counts, b)
+    assert got[0] == got[1] + got[2] + got[3], "ICP_MEM_PAIR_FILTER: n is not the sum of its parts: %r" % got
+    W = check_pieces(engine, oracle, g, F, M, T, side, fused, weighted, rot, power_fast, zero, want, b)
+    lost = np.count_nonzero(g.read(Mem.W, batch_index=b)[masks[2]] == 0)
+    assert lost == 0, "an accepted pair keeps its weight: %d do not" % lost
+    assert_bits(g.read(Mem.NN, batch_index=b)[:, 3], W, "the NN output's weights")
+    return counts, masks
+
+
+# the robust loss on point-to-point: the weights W' come from numpy (robust_ref.p2p_weights on the engine's own NN / QT after rejection
+# and trimming), and the pieces are fed W' with the rows of W' == 0 zeroed
+
+def p2p_expected(oracle, g, engine, M, T, side, fused, weighted, rot, power_fast, invalid, max_dist, keep, loss, scale, b=0):
+    """(W', sum W, means, S, Tk) of the step the engine took from T, from its own outputs."""
+    Mem = engine.Memory
+    nn_id = g.read(Mem.NN_ID, batch_index=b)
+    W = _robust_weights(engine, g, nn_id, M, weighted, invalid, max_dist, keep, loss, scale, b)
+    return expected_pieces(oracle, g.read(Mem.F, batch_index=b), M, T, nn_id, side, fused, weighted, rot, power_fast, W == 0, W)
+
+
+def _robust_weights(engine, g, nn_id, M, weighted, invalid, max_dist, keep, loss, scale, b):
+    Mem = engine.Memory
+    PF, PM = g.read(Mem.NN, batch_index=b), g.read(Mem.QT, batch_index=b)
+    W0 = weights_before_trim(nn_id, M, PF, PM, weighted, invalid, max_dist)
+    if keep < 1.0:
+        acc, _ = trim_rule(PF, PM, W0, keep)
+        W0[~acc] = 0.0
+    return robust_ref.p2p_weights(W0, PF, PM, loss, scale)
+
+
+def check_p2p(oracle, g, engine, M, T, side, fused, weighted, rot, power_fast, invalid=False, max_dist=None, keep=1.0,
+              loss=robust_ref.CAUCHY, scale=12.0, b=0):
+    Mem = engine.Memory
+    W = _robust_weights(engine, g, g.read(Mem.NN_ID, batch_index=b), M, weighted, invalid, max_dist, keep, loss, scale, b)
+    return check_pieces(engine, oracle, g, g.read(Mem.F, batch_index=b), M, T, side, fused, weighted, rot, power_fast, W == 0, None, b, W)
+
+
+def check_p2p_or_identity(oracle, g, engine, M, T, side, fused, weighted, rot, power_fast, invalid=False, max_dist=None, keep=1.0,
+                          loss=robust_ref.CAUCHY, scale=12.0, b=0):
+    """check_p2p, or — when the restatement's sum W is 0 — the header's identity step: W' all +0, sum W, means and S zero, T as it
+    was, Tk the identity.  Returns (W', whether nothing was accepted)."""
+    Mem = engine.Memory
+    W, sw, _, _, _ = p2p_expected(oracle, g, engine, M, T, side, fused, weighted, rot, power_fast, invalid, max_dist, keep, loss, scale, b)
+    if sw != 0:
+        return check_p2p(oracle, g, engine, M, T, side, fused, weighted, rot, power_fast, invalid, max_dist, keep, loss, scale, b), False
+    gW = g.read(Mem.W, batch_index=b)
+    assert_bits(gW, W, "W'")
+    assert (np.ascontiguousarray(gW).view(np.uint32) == 0).all() and g.read(Mem.SUM_W, batch_index=b)[0] == 0, "W' and sum W are +0"
+    assert (g.read(Mem.MEANS, batch_index=b) == 0).all() and (g.read(Mem.S, batch_index=b) == 0).all(), "means and S are zero"
+    assert_bits(g.read(Mem.T, batch_index=b), T, "T behind a step that accepts nothing")
+    assert_bits(g.read(Mem.TK, batch_index=b), IDENTITY, "Tk behind a step that accepts nothing")
+    return W, True
+
+
+def p2p_handle(engine, m, nr, fused, weighted, rot, power_fast, loss, scale, invalid=False, max_dist=None, keep=1.0, batch=1, it=40):
+    return make_handle(engine, m, nr, fused, weighted, rot, power_fast, batch, it,
+                       rejection=(invalid, max_dist) if invalid or max_dist else None, trimming=keep if keep < 1.0 else None,
+                       robust_loss=(loss, scale))
+
+
+# ---- 4. the plane family ----------------------------------------------------------------------------------------------------------
+
+def make_plane(engine, side, nr, weighted=WEIGHTED, mu=0.05, normals=GRID, batch=1, max_iterations=40, rot=POWER, fused=None,
+               power_fast=None, metric=P2PL, kappa=None, plane_to_plane=None, symmetric=None, trimming=None, robust_loss=None):
+    """A handle with a plane metric on.  The options are applied in this order, each only when given: fused / power_fast (either one
+    given sets both modes; the other then defaults to the handle's own default, on); the normals; kappa (COLORED: 1000 unless given);
+    the metric with mu; plane_to_plane = epsilon; symmetric = flag; trimming = keep; robust_loss = (loss, scale)."""
+    g = engine.ICP(0, rot, weighted)
+    g.init(side * side, nr, A, C_, max_iterations, batch=batch)
+    if fused is not None or power_fast is not None:
+        set_modes(engine, g, power_fast is None or power_fast, fused is None or fused)
+    g.set_normals(normals, side if normals == GRID else 0)
+    if metric == COLORED:
+        g.set_color_weight(1000.0 if kappa is None else kappa)
+    g.set_error_metric(metric, mu)
+    if plane_to_plane is not None:
+        g.set_plane_to_plane(plane_to_plane)
+    if symmetric is not None:
+        g.set_symmetric(symmetric)
+    if trimming is not None:
+        g.set_trimming(trimming)
+    if robust_loss is not None:
+        g.set_robust_loss(*robust_loss)
+    return g
+
+
+def load(engine, g, F, M, b=0):
+    g.write(engine.Memory.F, F, batch_index=b)
+    g.write(engine.Memory.M, M, batch_index=b)
+
+
+def before(engine, g, b=0):
+    Mem = engine.Memory
+    return g.read(Mem.T, b).copy(), g.read(Mem.R, b).ravel().copy(), g.state(b).k
+
+
+# restate (read, PF, PM, ids, T0, R0) -> (system, T, R, Tk, Rk): read (name) is the engine's table ICP_MEM_<name> of the registration
+
+def restate_p2pl(mu, normals=None):
+    return lambda read, PF, PM, ids, T0, R0: p2pl_ref.step(PF, PM, ids, read("NORMALS_F") if normals is None else normals, mu, T0, R0)
+
+
+def restate_colored(mu, kappa):
+    return lambda read, PF, PM, ids, T0, R0: colored_ref.step(PF, PM, ids, read("NORMALS_F"), read("COLOR_GRAD_F"),
+                                                              read("M").reshape(-1, 8), mu, kappa, T0, R0)
+
+
+def restate_gicp(mu, eps, loss=None, scale=None):
+    return lambda read, PF, PM, ids, T0, R0: gicp_ref.step(PF, PM, ids, read("NORMALS_F"), read("NORMALS_M"), mu, eps, T0, R0, loss, scale)
+
+
+def restate_symmetric(mu, loss=None, scale=None):
+    return lambda read, PF, PM, ids, T0, R0: sym_ref.step(PF, PM, ids, read("NORMALS_F"), read("NORMALS_M"), mu, T0, R0, loss, scale)
+
+
+def restate_robust(metric, loss, scale, mu=0.05, kappa=1e3, M=None):
+    return lambda read, PF, PM, ids, T0, R0: robust_ref.plane_step(PF, PM, ids, read("NORMALS_F"), mu, loss, scale, T0, R0,
+                                                                   read("COLOR_GRAD_F") if metric == COLORED else None, M, kappa)
+
+
+def check_last(engine, g, restate, T0, R0, k0, b=0, steps=1):
+    """The last iteration of registration b against the restatement fed the device's own outputs and the state (T0, R0, k0) before the
+    `steps` iterations (k0 None: the caller does not know it, k is not compared).  Returns the system."""
+    Mem = engine.Memory
+    PF, PM, ids = g.read(Mem.NN, b), g.read(Mem.QT, b), g.read(Mem.NN_ID, b)["id"]
+    system, T, R, Tk, Rk = restate(lambda name: g.read(getattr(Mem, name), b), PF, PM, ids, T0, R0)
+    assert_bits(g.read(Mem.PLANE_SYSTEM, b), system, "PLANE_SYSTEM (registration %d)" % b)
+    assert_bits(g.read(Mem.T, b), T, "T (registration %d)" % b)
+    assert_bits(g.read(Mem.R, b).ravel(), R, "R (registration %d)" % b)
+    assert_bits(g.read(Mem.TK, b), Tk, "TK (registration %d)" % b)
+    assert_bits(g.read(Mem.RK, b).ravel(), Rk, "RK (registration %d)" % b)
+    st = g.state(b)
+    if k0 is not None:
+        assert st.k == k0 + steps, "k (registration %d): got %d want %d" % (b, st.k, k0 + steps)
+    assert st.power_iterations == 0, "power_iterations (registration %d): %d" % (b, st.power_iterations)
+    return system
+
+
+def check_step(engine, g, restate, b=0):
+    """One step of handle g (all registrations), checked for registration b against the restatement.  Returns the system."""
+    T0, R0, k0 = before(engine, g, b)
+    g.step()
+    return check_last(engine, g, restate, T0, R0, k0, b)
+
+
+def check_fixed_run(engine, g, n, restate):
+    """A fixed run of n iterations: its last iteration against the restatement, from the state n - 1 steps leave (stepped on the same
+    handle, whose steps are checked one by one elsewhere)."""
+    g.reset_transform(); g.buildRBC()
+    for _ in range(n - 1):
+        g.step()
+    T0, R0, _ = before(engine, g)
+    g.reset_transform(); g.buildRBC()
+    g.run_fixed(n)
+    return check_last(engine, g, restate, T0, R0, 0, 0, steps=n)
+
+
+def plane_handle(engine, side, nr, metric, loss, scale, mu=0.05, kappa=1e3, normals=GRID, fused=True, batch=1, it=40, keep=1.0):
+    """A robust plane handle: the default rotation and weighting, the squared power start."""
+    return make_plane(engine, side, nr, WEIGHTED, mu, normals, batch, it, fused=fused, power_fast=True, metric=metric, kappa=kappa,
+                      trimming=keep if keep < 1.0 else None, robust_loss=(loss, scale))
+
+
+def check_plane(engine, g, metric, loss, scale, T0, R0, mu=0.05, kappa=1e3, M=None, b=0):
+    return check_last(engine, g, restate_robust(metric, loss, scale, mu, kappa, M), T0, R0, None, b)

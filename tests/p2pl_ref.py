@@ -260,3 +260,14 @@ def step(PF, PM, ids, normals, mu, T, R):
     Tk = increment(x)
     Tn, Rn, Rk = compose(T, R, Tk)
     return system, Tn, Rn, Tk, Rk
+
+
+UPPER = [(a, c) for a in range(6) for c in range(a, 6)]          # the 21 upper-triangle terms of a system, row-major
+
+
+def unpack(s):
+    """(A 6 x 6, b 6) of a 27-term system."""
+    A = np.zeros((6, 6))
+    for t, (a, c) in enumerate(UPPER):
+        A[a, c] = A[c, a] = s[t]
+    return A, np.asarray(s[21:27], np.float64)

@@ -215,3 +215,23 @@ def literal_applies(case):
     """Where the reference's literal loop (icp_kernels.cl:1012-1041) can work: a dominant positive eigenvalue, a clear gap and a first
     component it can divide by (:1024)."""
     return (case.unique and case.lam[0] >= 1.5 * abs(case.lam[3]) and case.gap >= 0.1 and abs(case.q[0]) >= 0.05)
+
+
+def planar_case(seed, tilt=0.3):
+    """S[11], means[8] of an exactly planar pair: points on a tilted plane, the moving set rotated by 7 degrees about the plane's normal
+    (S of rank 2: Horn's N has the eigenvalue pairs +-(s1 + s2), +-(s1 - s2))."""
+    rng = np.random.default_rng(seed)
+    uv = rng.uniform(-1, 1, (400, 2)) * np.array([300.0, 200.0])
+    e1 = np.array([1.0, 0.0, tilt]); e1 /= np.linalg.norm(e1)
+    e2 = np.cross(np.array([0.2, 1.0, 0.1]), e1); e2 /= np.linalg.norm(e2)
+    n = np.cross(e1, e2)
+    f = uv[:, :1] * e1 + uv[:, 1:] * e2
+    th = np.radians(7.0)
+    K = np.array([[0, -n[2], n[1]], [n[2], 0, -n[0]], [-n[1], n[0], 0]])
+    R = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
+    q = f @ R.T                                            # moving = R fixed: the solver must find R^T
+    c = 1e-3
+    S9 = (c * q).T @ (c * f)                               # S_ab = sum m_a f_b
+    S = np.concatenate([S9.ravel(), [((c * f) ** 2).sum(), ((c * q) ** 2).sum()]]).astype(np.float32)
+    means = np.zeros(8, np.float32)
+    return S, means, R.T

@@ -13,36 +13,17 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import colored_ref as cref                                      # noqa: E402
 import p2pl_ref as ref                                          # noqa: E402
-import test_gpu_point_to_plane as p2pl                          # noqa: E402
-from test_gpu_parity import A, C_, assert_bits                  # noqa: E402
-from test_gpu_point_to_plane import (COLORED, GIVEN, GRID, P2P, P2PL, REGULAR, SIZES, WEIGHTED, _errors,   # noqa: E402
-                                     _messy_grid, _register, load)
+from icp_checks import (A, C_, COLORED, GIVEN, GRID, P2P, P2PL, REGULAR, SIZES, WEIGHTED, assert_bits, check_last, load,  # noqa: E402
+                        make_plane, messy_grid as _messy_grid, register as _register, restate_colored, _errors)
+import icp_checks      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-make = functools.partial(p2pl.make, metric=COLORED)          # (kappa 1000 unless given)
+make = functools.partial(make_plane, metric=COLORED)         # (kappa 1000 unless given)
 
 
 def check_step(engine, g, mu, kappa, b=0):
-    Mem = engine.Memory
-    T0, R0 = g.read(Mem.T, b).copy(), g.read(Mem.R, b).ravel().copy()
-    g.step()
-    return check_last(engine, g, mu, kappa, T0, R0, b)
-
-
-def check_last(engine, g, mu, kappa, T0, R0, b=0):
-    """The last step of registration b against the restatement, from the engine's own inputs of that step.  Returns the system."""
-    Mem = engine.Memory
-    PF, PM, ids = g.read(Mem.NN, b), g.read(Mem.QT, b), g.read(Mem.NN_ID, b)["id"]
-    N, Gd, M = g.read(Mem.NORMALS_F, b), g.read(Mem.COLOR_GRAD_F, b), g.read(Mem.M, b).reshape(-1, 8)
-    system, T, R, Tk, Rk = cref.step(PF, PM, ids, N, Gd, M, mu, kappa, T0, R0)
-    assert_bits(g.read(Mem.PLANE_SYSTEM, b), system, "PLANE_SYSTEM (registration %d)" % b)
-    assert_bits(g.read(Mem.T, b), T, "T (registration %d)" % b)
-    assert_bits(g.read(Mem.R, b).ravel(), R, "R (registration %d)" % b)
-    assert_bits(g.read(Mem.TK, b), Tk, "TK (registration %d)" % b)
-    assert_bits(g.read(Mem.RK, b).ravel(), Rk, "RK (registration %d)" % b)
-    assert g.state(b).power_iterations == 0
-    return system
+    return icp_checks.check_step(engine, g, restate_colored(mu, kappa), b)
 
 
 def grads_of(F, width):
@@ -172,7 +153,7 @@ def test_batch_of_64_at_A(engine):
     T0 = [(g.read(engine.Memory.T, b).copy(), g.read(engine.Memory.R, b).ravel().copy()) for b in range(n)]
     g.step()
     for b in range(n):
-        check_last(engine, g, 0.05, 1000.0, T0[b][0], T0[b][1], b)
+        check_last(engine, g, restate_colored(0.05, 1000.0), T0[b][0], T0[b][1], None, b)
     for b in (0, 17, 63):
         h = make(engine, side, nr)
         load(engine, h, *pairs[b])
@@ -421,12 +402,12 @@ KAPPAS = (0.0, 1e2, 1e3, 1e4)
 def _sweep(engine, F, M, T_true):
     res = {}
     T, k, c = _register(engine, F, M, P2P)
-    res["p2p"] = _errors(engine, T, T_true) + (k, c)
+    res["p2p"] = _errors(T, T_true) + (k, c)
     T, k, c = _register(engine, F, M, P2PL, 0.05)
-    res["p2pl"] = _errors(engine, T, T_true) + (k, c)
+    res["p2pl"] = _errors(T, T_true) + (k, c)
     for kappa in KAPPAS:
         T, k, c = _register(engine, F, M, COLORED, 0.05, kappa)
-        res[kappa] = _errors(engine, T, T_true) + (k, c)
+        res[kappa] = _errors(T, T_true) + (k, c)
     print(" | ".join("%s %.4f deg %.3f mm k=%d" % (("colored kappa=%g" % n) if not isinstance(n, str) else n, *v[:3])
                      for n, v in res.items()))
     return res

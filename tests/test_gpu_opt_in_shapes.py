@@ -18,17 +18,18 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import test_gpu_colored_icp as col                              # noqa: E402
-import test_gpu_point_to_plane as p2pl                          # noqa: E402
-import test_gpu_trimming as trim                                # noqa: E402
-from test_gpu_parity import A, C_, assert_bits, set_modes       # noqa: E402
-from test_gpu_rejection import _holes, _t0, check_one_step, make_handle as rej_handle, oracle_search, pick_max_dist   # noqa: E402
-from test_plane_system_float64 import unpack                    # noqa: E402
+import p2pl_ref                                                  # noqa: E402
+import robust_ref as rref                                        # noqa: E402
+import unique_ref                                                # noqa: E402
+from icp_checks import (A, C_, COLORED, LOSSES, P2PL, POWER, REGULAR, SCALE, WEIGHTED, assert_bits, before, check_last,  # noqa: E402
+                        check_p2p_or_identity, check_pair_filter_step, check_pieces, check_plane, check_rejection_step, check_step,
+                        check_trim_step, check_unique_step, holes_pair as _holes, load, make_handle, make_plane,
+                        messy_grid, one_step, oracle_search, p2p_handle, pair_filter_rule_of, pick_max_dist, plane_handle,
+                        restate_colored, restate_gicp, restate_p2pl, restate_symmetric, set_modes, trim_rule,
+                        weights_before_trim, step_batch, _t0)
 
 pytestmark = pytest.mark.gpu
 
-POWER = 1
-REGULAR, WEIGHTED = 0, 1
 EPS32 = float(np.finfo(np.float32).eps)
 EPS64 = float(np.finfo(np.float64).eps)
 
@@ -40,7 +41,7 @@ def check_lstsq(engine, g, b=0):
     s = g.read(engine.Memory.PLANE_SYSTEM, b)
     if s[27] != 1.0:
         return False
-    Am, bv = unpack(s[:27])
+    Am, bv = p2pl_ref.unpack(s[:27])
     d = 1.0 / np.sqrt(np.diag(Am))
     As = Am * np.outer(d, d)
     ys = np.linalg.lstsq(As, bv * d, rcond=None)[0]
@@ -67,11 +68,11 @@ PLANE_SHAPES = [(6, 4), (14, 4), (30, 4), (96, 64), (150, 4), (320, 256), (512, 
 @pytest.mark.parametrize("side,nr", PLANE_SHAPES)
 def test_point_to_plane_steps(engine, side, nr):
     F, M = engine.synth_pair(side, seed=0x9A1E + side)
-    g = p2pl.make(engine, side, nr, mu=0.05)
-    p2pl.load(engine, g, F, M)
+    g = make_plane(engine, side, nr, mu=0.05)
+    load(engine, g, F, M)
     g.buildRBC()
     for _ in range(2):
-        s = p2pl.check_step(engine, g, 0.05)
+        s = check_step(engine, g, restate_p2pl(0.05))
         assert s[27] == 1.0
         assert check_lstsq(engine, g)
     g.close()
@@ -81,14 +82,14 @@ def test_point_to_plane_steps(engine, side, nr):
 def test_point_to_plane_messy_grid(engine, side, nr):
     """Holes, NaN / inf and zero points in F (grid normals of zero around them), REGULAR weights."""
     seed = 0xBAD + side
-    F = p2pl._messy_grid(engine, side, seed)
+    F = messy_grid(engine, side, seed)
     M = engine.synth_pair(side, seed=seed)[1]
-    g = p2pl.make(engine, side, nr, weighted=REGULAR, mu=0.05, fused=False)
-    p2pl.load(engine, g, F, M)
+    g = make_plane(engine, side, nr, weighted=REGULAR, mu=0.05, fused=False)
+    load(engine, g, F, M)
     g.buildRBC()
     assert np.count_nonzero(g.read(engine.Memory.NORMALS_F)[:, :3].any(axis=1)) < side * side * 0.9
     for _ in range(2):
-        p2pl.check_step(engine, g, 0.05)
+        check_step(engine, g, restate_p2pl(0.05))
         check_lstsq(engine, g)
     g.close()
 
@@ -96,11 +97,11 @@ def test_point_to_plane_messy_grid(engine, side, nr):
 @pytest.mark.parametrize("side,nr", [(6, 4), (30, 4), (150, 4), (320, 256), (1024, 4096)])
 def test_colored_steps(engine, side, nr):
     F, M, _ = engine.synth_pair_scene(side, engine.SCENE_WALL, seed=0xC01 + side)
-    g = col.make(engine, side, nr, mu=0.05, kappa=1000.0)
-    col.load(engine, g, F, M)
+    g = make_plane(engine, side, nr, mu=0.05, metric=COLORED, kappa=1000.0)
+    load(engine, g, F, M)
     g.buildRBC()
     for _ in range(2):
-        s = col.check_step(engine, g, 0.05, 1000.0)
+        s = check_step(engine, g, restate_colored(0.05, 1000.0))
         assert s[27] == 1.0
         assert check_lstsq(engine, g)
     g.close()
@@ -110,22 +111,22 @@ def test_point_to_plane_batch3_at_P512(engine):
     """Three registrations of 102400 (nblk = 400 each, P = 512): each checked on its own and against a single handle."""
     side, nr, n = 320, 256, 3
     pairs = [engine.synth_pair(side, seed=0x7A00 + i, rot_deg=1.0 + 1.5 * i) for i in range(n)]
-    g = p2pl.make(engine, side, nr, batch=n, mu=0.05)
+    g = make_plane(engine, side, nr, batch=n, mu=0.05)
     for b, (F, M) in enumerate(pairs):
-        p2pl.load(engine, g, F, M, b)
+        load(engine, g, F, M, b)
     g.buildRBC()
     Mem = engine.Memory
     for _ in range(2):
         T0 = [(g.read(Mem.T, b).copy(), g.read(Mem.R, b).ravel().copy()) for b in range(n)]
         g.step()
         for b in range(n):
-            p2pl.check_last(engine, g, 0.05, T0[b][0], T0[b][1], b)
+            check_last(engine, g, restate_p2pl(0.05), T0[b][0], T0[b][1], None, b)
             assert check_lstsq(engine, g, b)
     systems = [g.read(Mem.PLANE_SYSTEM, b).copy() for b in range(n)]
     assert not np.array_equal(systems[0], systems[1]) and not np.array_equal(systems[1], systems[2])
     for b in range(n):
-        h = p2pl.make(engine, side, nr, mu=0.05)
-        p2pl.load(engine, h, *pairs[b])
+        h = make_plane(engine, side, nr, mu=0.05)
+        load(engine, h, *pairs[b])
         h.buildRBC()
         h.step(); h.step()
         assert_bits(g.read(Mem.T, b), h.read(Mem.T), "T of registration %d" % b)
@@ -135,25 +136,25 @@ def test_point_to_plane_batch3_at_P512(engine):
     g.close()
 
 
-@pytest.mark.parametrize("metric", [p2pl.P2PL, col.COLORED])
+@pytest.mark.parametrize("metric", [P2PL, COLORED])
 def test_run_batch2_at_a_partial_block(engine, metric):
     """ICP::run on two registrations of 22500 (nblk = 88, the last block partly filled) against single handles: k, T, the system."""
     side, nr = 150, 4
-    if metric == col.COLORED:
+    if metric == COLORED:
         pairs = [engine.synth_pair_scene(side, engine.SCENE_WALL, seed=0x7B00 + i, rot_deg=1.0 + 2.0 * i)[:2] for i in range(2)]
-        mk = lambda batch=1: col.make(engine, side, nr, mu=0.05, kappa=1000.0, batch=batch)
+        mk = lambda batch=1: make_plane(engine, side, nr, mu=0.05, metric=COLORED, kappa=1000.0, batch=batch)
     else:
         pairs = [engine.synth_pair(side, seed=0x7B00 + i, rot_deg=1.0 + 2.0 * i) for i in range(2)]
-        mk = lambda batch=1: p2pl.make(engine, side, nr, mu=0.05, batch=batch)
+        mk = lambda batch=1: make_plane(engine, side, nr, mu=0.05, batch=batch)
     g = mk(2)
     for b, (F, M) in enumerate(pairs):
-        p2pl.load(engine, g, F, M, b)
+        load(engine, g, F, M, b)
     g.buildRBC()
     g.run()
     Mem = engine.Memory
     for b, (F, M) in enumerate(pairs):
         h = mk()
-        p2pl.load(engine, h, F, M)
+        load(engine, h, F, M)
         h.buildRBC()
         k = h.run()
         assert 1 < k <= 40, k
@@ -178,9 +179,9 @@ TRIM_MODES = [(True, WEIGHTED), (False, REGULAR)]
 def test_trim_one_step_large_select(engine, oracle, side, nr, fused, weighted):
     F, M = _holes(engine, side, 0x7E1 + side)
     T = _t0()
-    g = trim.make_handle(engine, side * side, nr, fused, weighted, POWER, fused, True, 0.75)
-    trim.one_step(engine, g, F, M, T)
-    _, t = trim.check_step(engine, oracle, g, F, M, T, side, fused, weighted, POWER, fused, True, 0.75)
+    g = make_handle(engine, side * side, nr, fused, weighted, POWER, fused, rejection=(True, None), trimming=0.75)
+    one_step(engine, g, F, M, T)
+    _, t = check_trim_step(engine, oracle, g, F, M, T, side, fused, weighted, POWER, fused, True, 0.75)
     n, K = int(t[1]), int(t[2])
     assert n > side * side // 3 and K <= t[3] < n, t
     g.close()
@@ -207,16 +208,11 @@ def test_trim_batch3_large_select(engine, oracle, side, nr, fused, weighted):
     n = 3
     pairs = _varied_pairs(engine, side, n, 0x7E2 + side)
     T = _t0()
-    g = trim.make_handle(engine, side * side, nr, fused, weighted, POWER, fused, True, 0.75, batch=n)
-    for b, (F, M) in enumerate(pairs):
-        g.write(engine.Memory.F, F, batch_index=b); g.write(engine.Memory.M, M, batch_index=b)
-    g.buildRBC()
-    for b in range(n):
-        g.write(engine.Memory.T, T, batch_index=b, block=True)
-    g.step()
+    g = make_handle(engine, side * side, nr, fused, weighted, POWER, fused, n, rejection=(True, None), trimming=0.75)
+    step_batch(engine, g, pairs, T)
     ts = set()
     for b, (F, M) in enumerate(pairs):
-        _, t = trim.check_step(engine, oracle, g, F, M, T, side, fused, weighted, POWER, fused, True, 0.75, b=b)
+        _, t = check_trim_step(engine, oracle, g, F, M, T, side, fused, weighted, POWER, fused, True, 0.75, b=b)
         ts.add((int(t[0]), int(t[1])))
     assert len(ts) == n, ts
     g.close()
@@ -264,17 +260,17 @@ def test_point_to_plane_with_trimming_large_select(engine, fused):
     """The select of 22500 pairs feeds the plane moments: the accepted set by the rule, then the system by the restatement."""
     side, nr = 150, 4
     F, M = _holes(engine, side, 0x7E4)
-    g = p2pl.make(engine, side, nr, mu=0.05, fused=fused)
+    g = make_plane(engine, side, nr, mu=0.05, fused=fused)
     g.set_rejection(True, None)
     g.set_trimming(0.75)
-    p2pl.load(engine, g, F, M)
+    load(engine, g, F, M)
     g.buildRBC()
     Mem = engine.Memory
     for _ in range(2):
-        p2pl.check_step(engine, g, 0.05)
+        check_step(engine, g, restate_p2pl(0.05))
         PF, PM, nn_id = g.read(Mem.NN), g.read(Mem.QT), g.read(Mem.NN_ID)
-        W0 = trim.weights_before_trim(nn_id, M, PF, PM, True, True)
-        acc, t = trim.trim_rule(PF, PM, W0, 0.75)
+        W0 = weights_before_trim(nn_id, M, PF, PM, True, True)
+        acc, t = trim_rule(PF, PM, W0, 0.75)
         assert np.array_equal(g.read(Mem.TRIM), t), (g.read(Mem.TRIM), t)
         assert_bits(PF[acc, 3], W0[acc], "accepted weights")
         assert np.all(PF[~acc, 3].view(np.uint32) == 0), "a trimmed or rejected pair's weight is +0"
@@ -304,7 +300,7 @@ def _tiny_pair(engine, side):
 def test_rejection_tiny_and_odd(engine, oracle, side, nr, fused):
     F, M = _tiny_pair(engine, side)
     T = _t0()
-    g = rej_handle(engine, side * side, nr, fused, WEIGHTED, POWER, fused, True, 1.0)
+    g = make_handle(engine, side * side, nr, fused, WEIGHTED, POWER, fused, rejection=(True, 1.0))
     g.write(engine.Memory.F, F); g.write(engine.Memory.M, M)
     g.buildRBC()
     g.write(engine.Memory.T, T, block=True)
@@ -313,7 +309,7 @@ def test_rejection_tiny_and_odd(engine, oracle, side, nr, fused):
         md = pick_max_dist(oracle, F, M, T, nr, frac=0.3)             # (a cap that rejects some valid pair at this step's T)
         g.set_rejection(True, md)
         g.step()
-        rej = check_one_step(engine, oracle, g, F, M, T, side, nr, fused, WEIGHTED, POWER, fused, True, md)
+        rej = check_rejection_step(engine, oracle, g, F, M, T, side, nr, fused, WEIGHTED, POWER, fused, True, md)
         invalid = (M[:, :3] == 0).all(1) | (g.read(engine.Memory.NN)[:, :3] == 0).all(1)
         assert invalid.any() and (rej & ~invalid).any(), "both rules reject some pair"
     g.close()
@@ -324,13 +320,13 @@ def test_rejection_tiny_and_odd(engine, oracle, side, nr, fused):
 def test_trimming_tiny_and_odd(engine, oracle, side, nr, fused):
     F, M = _tiny_pair(engine, side)
     T = _t0()
-    g = trim.make_handle(engine, side * side, nr, fused, WEIGHTED, POWER, fused, True, 0.5)
-    trim.one_step(engine, g, F, M, T)
+    g = make_handle(engine, side * side, nr, fused, WEIGHTED, POWER, fused, rejection=(True, None), trimming=0.5)
+    one_step(engine, g, F, M, T)
     for it in range(2):
         if it:
             T = g.read(engine.Memory.T).copy()
             g.step()
-        acc, t = trim.check_step(engine, oracle, g, F, M, T, side, fused, WEIGHTED, POWER, fused, True, 0.5,
+        acc, t = check_trim_step(engine, oracle, g, F, M, T, side, fused, WEIGHTED, POWER, fused, True, 0.5,
                                  oracle_search(oracle, F, M, T, nr))
         assert 0 < t[3] < t[1], t                                      # (some pair trimmed, some kept)
     g.close()
@@ -343,17 +339,12 @@ def test_rejection_dense_layouts(engine, oracle, side, nr, batch, fused):
     pairs = [_holes(engine, side, 0x7E5 + 11 * b, "blobs30" if b % 2 == 0 else "scattered10") for b in range(batch)]
     T = _t0()
     md = pick_max_dist(oracle, pairs[0][0], pairs[0][1], T, nr)
-    g = rej_handle(engine, side * side, nr, fused, WEIGHTED, POWER, fused, True, md, batch=batch)
+    g = make_handle(engine, side * side, nr, fused, WEIGHTED, POWER, fused, batch, rejection=(True, md))
     if fused:
         assert g.search_layout() == (1, 256, 1)
+    step_batch(engine, g, pairs, T)
     for b, (F, M) in enumerate(pairs):
-        g.write(engine.Memory.F, F, batch_index=b); g.write(engine.Memory.M, M, batch_index=b)
-    g.buildRBC()
-    for b in range(batch):
-        g.write(engine.Memory.T, T, batch_index=b, block=True)
-    g.step()
-    for b, (F, M) in enumerate(pairs):
-        check_one_step(engine, oracle, g, F, M, T, side, nr, fused, WEIGHTED, POWER, fused, True, md, b=b)
+        check_rejection_step(engine, oracle, g, F, M, T, side, nr, fused, WEIGHTED, POWER, fused, True, md, b=b)
     g.close()
 
 
@@ -368,30 +359,20 @@ def test_rejection_dense_layouts(engine, oracle, side, nr, batch, fused):
 # the loss's weight and the block tree from the same header as the kernels above (icp_plane_moments.h): they are taken, loss off and
 # on, to m < 256, to a partly filled last block and to a batch whose registrations stop at different iterations.
 
-import robust_ref as rref                                        # noqa: E402
-import test_gpu_gicp as gicp                                     # noqa: E402
-import test_gpu_robust_loss as rl                                # noqa: E402
-import test_gpu_symmetric as sym                                 # noqa: E402
-
 ROBUST_DENSE = [(256, 256, 1), (128, 64, 3), (256, 1024, 1), (192, 2048, 1)]
 
 
 def _robust_p2p_step(engine, oracle, pairs, side, nr, fused, loss, invalid=True, keep=1.0):
     """One step from _t0 () of a handle with len (pairs) registrations, every registration by check_p2p.  Returns the handle and W'."""
     T, n = _t0(), len(pairs)
-    g = rl.p2p_handle(engine, side * side, nr, fused, WEIGHTED, POWER, fused, loss, rl.SCALE[loss], invalid=invalid, keep=keep, batch=n)
-    for b, (F, M) in enumerate(pairs):
-        g.write(engine.Memory.F, F, batch_index=b); g.write(engine.Memory.M, M, batch_index=b)
-    g.buildRBC()
-    for b in range(n):
-        g.write(engine.Memory.T, T, batch_index=b, block=True)
-    g.step()
-    Ws = [rl.check_p2p_or_identity(oracle, g, engine, M, T, side, fused, WEIGHTED, POWER, fused, invalid=invalid, keep=keep, loss=loss,
-                                   scale=rl.SCALE[loss], b=b)[0] for b, (F, M) in enumerate(pairs)]
+    g = p2p_handle(engine, side * side, nr, fused, WEIGHTED, POWER, fused, loss, SCALE[loss], invalid=invalid, keep=keep, batch=n)
+    step_batch(engine, g, pairs, T)
+    Ws = [check_p2p_or_identity(oracle, g, engine, M, T, side, fused, WEIGHTED, POWER, fused, invalid=invalid, keep=keep, loss=loss,
+                                   scale=SCALE[loss], b=b)[0] for b, (F, M) in enumerate(pairs)]
     return g, Ws
 
 
-@pytest.mark.parametrize("loss", rl.LOSSES)
+@pytest.mark.parametrize("loss", LOSSES)
 @pytest.mark.parametrize("side,nr", TINY + [(150, 4)])
 @pytest.mark.parametrize("fused", [True, False])
 def test_robust_p2p_tiny_and_odd(engine, oracle, side, nr, fused, loss):
@@ -402,7 +383,7 @@ def test_robust_p2p_tiny_and_odd(engine, oracle, side, nr, fused, loss):
     g.close()
 
 
-@pytest.mark.parametrize("loss", rl.LOSSES)
+@pytest.mark.parametrize("loss", LOSSES)
 @pytest.mark.parametrize("side,nr,batch", ROBUST_DENSE)
 @pytest.mark.parametrize("fused", [True, False])
 def test_robust_p2p_dense_layouts(engine, oracle, side, nr, batch, fused, loss):
@@ -416,7 +397,7 @@ def test_robust_p2p_dense_layouts(engine, oracle, side, nr, batch, fused, loss):
     g.close()
 
 
-@pytest.mark.parametrize("loss", rl.LOSSES)
+@pytest.mark.parametrize("loss", LOSSES)
 @pytest.mark.parametrize("side,nr", TRIM_SHAPES)
 @pytest.mark.parametrize("fused", [True, False])
 def test_robust_p2p_behind_the_large_select(engine, oracle, side, nr, fused, loss):
@@ -443,34 +424,34 @@ def _robust_plane_steps(engine, g, metric, loss, Ms, steps=2):
         T0 = [(g.read(Mem.T, b).copy(), g.read(Mem.R, b).ravel().copy()) for b in range(len(Ms))]
         g.step()
         for b, M in enumerate(Ms):
-            s = rl.check_plane(engine, g, metric, loss, rl.SCALE[loss], T0[b][0], T0[b][1], M=M, b=b)
+            s = check_plane(engine, g, metric, loss, SCALE[loss], T0[b][0], T0[b][1], M=M, b=b)
             assert check_lstsq(engine, g, b) == (s[27] == 1.0)
             assert np.isfinite(s).all() and s[:27].any()
 
 
 # (every loss up to 102400 pairs; the two cases of about 10^6 pairs with one loss each, for the suite's time)
-ROBUST_PLANE_CASES = [(side, nr, loss) for side, nr in PLANE_SHAPES[:6] for loss in rl.LOSSES] + [(1000, 64, rref.TUKEY),
+ROBUST_PLANE_CASES = [(side, nr, loss) for side, nr in PLANE_SHAPES[:6] for loss in LOSSES] + [(1000, 64, rref.TUKEY),
                                                                                                   (1024, 4096, rref.CAUCHY)]
 
 
 @pytest.mark.parametrize("side,nr,loss", ROBUST_PLANE_CASES)
 def test_robust_point_to_plane_steps(engine, side, nr, loss):
     F, M = engine.synth_pair(side, seed=0x9A1E + side)
-    g = rl.plane_handle(engine, side, nr, rl.P2PL, loss, rl.SCALE[loss])
-    p2pl.load(engine, g, F, M)
+    g = plane_handle(engine, side, nr, P2PL, loss, SCALE[loss])
+    load(engine, g, F, M)
     g.buildRBC()
-    _robust_plane_steps(engine, g, rl.P2PL, loss, [M])
+    _robust_plane_steps(engine, g, P2PL, loss, [M])
     g.close()
 
 
-@pytest.mark.parametrize("loss", rl.LOSSES)
+@pytest.mark.parametrize("loss", LOSSES)
 @pytest.mark.parametrize("side,nr", [(6, 4), (150, 4), (320, 256)])
 def test_robust_colored_steps(engine, side, nr, loss):
     F, M, _ = engine.synth_pair_scene(side, engine.SCENE_WALL, seed=0xC01 + side)
-    g = rl.plane_handle(engine, side, nr, rl.COLORED, loss, rl.SCALE[loss])
-    p2pl.load(engine, g, F, M)
+    g = plane_handle(engine, side, nr, COLORED, loss, SCALE[loss])
+    load(engine, g, F, M)
     g.buildRBC()
-    _robust_plane_steps(engine, g, rl.COLORED, loss, [M])
+    _robust_plane_steps(engine, g, COLORED, loss, [M])
     g.close()
 
 
@@ -478,15 +459,15 @@ def test_robust_point_to_plane_batch3_at_P512(engine):
     """Three registrations of 102400 with Tukey on: each by the restatement and against a single handle."""
     side, nr, n, loss = 320, 256, 3, rref.TUKEY
     pairs = [engine.synth_pair(side, seed=0x7A00 + i, rot_deg=1.0 + 1.5 * i) for i in range(n)]
-    g = rl.plane_handle(engine, side, nr, rl.P2PL, loss, rl.SCALE[loss], batch=n)
+    g = plane_handle(engine, side, nr, P2PL, loss, SCALE[loss], batch=n)
     for b, (F, M) in enumerate(pairs):
-        p2pl.load(engine, g, F, M, b)
+        load(engine, g, F, M, b)
     g.buildRBC()
-    _robust_plane_steps(engine, g, rl.P2PL, loss, [M for _, M in pairs])
+    _robust_plane_steps(engine, g, P2PL, loss, [M for _, M in pairs])
     Mem = engine.Memory
     for b in range(n):
-        h = rl.plane_handle(engine, side, nr, rl.P2PL, loss, rl.SCALE[loss])
-        p2pl.load(engine, h, *pairs[b])
+        h = plane_handle(engine, side, nr, P2PL, loss, SCALE[loss])
+        load(engine, h, *pairs[b])
         h.buildRBC()
         h.step(); h.step()
         assert_bits(g.read(Mem.T, b), h.read(Mem.T), "T of registration %d" % b)
@@ -495,24 +476,24 @@ def test_robust_point_to_plane_batch3_at_P512(engine):
     g.close()
 
 
-@pytest.mark.parametrize("metric", [rl.P2PL, rl.COLORED])
+@pytest.mark.parametrize("metric", [P2PL, COLORED])
 def test_robust_run_batch2_at_a_partial_block(engine, metric):
     """ICP::run with Cauchy on, two registrations of 22500 against single handles: k, T, the system."""
     side, nr, loss = 150, 4, rref.CAUCHY
-    if metric == rl.COLORED:
+    if metric == COLORED:
         pairs = [engine.synth_pair_scene(side, engine.SCENE_WALL, seed=0x7B00 + i, rot_deg=1.0 + 2.0 * i)[:2] for i in range(2)]
     else:
         pairs = [engine.synth_pair(side, seed=0x7B00 + i, rot_deg=1.0 + 2.0 * i) for i in range(2)]
-    mk = lambda batch=1: rl.plane_handle(engine, side, nr, metric, loss, rl.SCALE[loss], batch=batch)
+    mk = lambda batch=1: plane_handle(engine, side, nr, metric, loss, SCALE[loss], batch=batch)
     g = mk(2)
     for b, (F, M) in enumerate(pairs):
-        p2pl.load(engine, g, F, M, b)
+        load(engine, g, F, M, b)
     g.buildRBC()
     g.run()
     Mem = engine.Memory
     for b, (F, M) in enumerate(pairs):
         h = mk()
-        p2pl.load(engine, h, F, M)
+        load(engine, h, F, M)
         h.buildRBC()
         k = h.run()
         assert 1 < k <= 40, k
@@ -535,7 +516,7 @@ def test_robust_p2p_batch3_runs_end_at_different_iterations(engine, side, nr, fu
         g = engine.ICP(0)
         g.init(side * side, nr, A, C_, angle_threshold=0.01, translation_threshold=0.05, batch=batch)
         set_modes(engine, g, power_fast=fused, fused=fused)
-        g.set_robust_loss(loss, rl.SCALE[loss])
+        g.set_robust_loss(loss, SCALE[loss])
         return g
 
     Mem = engine.Memory
@@ -568,13 +549,14 @@ GICP_EPS = 1e-3
 def _two_normals_handle(engine, metric, side, nr, loss, batch=1):
     """A plane-to-plane ("gicp") or symmetric ("sym") handle, mu = 0.05, with the loss on when one is given; and its step check."""
     if metric == "gicp":
-        g = gicp.make(engine, side, nr, mu=0.05, eps=GICP_EPS, batch=batch)
-        check = lambda T0, R0, k0, b: gicp.check_last(engine, g, 0.05, GICP_EPS, T0, R0, k0, b, loss, rl.SCALE.get(loss))
+        g = make_plane(engine, side, nr, mu=0.05, batch=batch, plane_to_plane=GICP_EPS)
+        restate = restate_gicp(0.05, GICP_EPS, loss, SCALE.get(loss))
     else:
-        g = sym.make(engine, side, nr, mu=0.05, batch=batch)
-        check = lambda T0, R0, k0, b: sym.check_last(engine, g, 0.05, T0, R0, k0, b, loss, rl.SCALE.get(loss))
+        g = make_plane(engine, side, nr, mu=0.05, batch=batch, symmetric=True)
+        restate = restate_symmetric(0.05, loss, SCALE.get(loss))
+    check = lambda T0, R0, k0, b: check_last(engine, g, restate, T0, R0, k0, b)
     if loss is not None:
-        g.set_robust_loss(loss, rl.SCALE[loss])
+        g.set_robust_loss(loss, SCALE[loss])
     return g, check
 
 
@@ -585,10 +567,10 @@ def test_two_normals_metrics_below_and_across_a_block(engine, metric, side, nr, 
     """Two steps, each against the metric's restatement (tests/gicp_ref.py, tests/sym_ref.py) fed the engine's own outputs."""
     F, M = engine.synth_pair(side, seed=0x9A1E + side)
     g, check = _two_normals_handle(engine, metric, side, nr, loss)
-    gicp.load(engine, g, F, M)
+    load(engine, g, F, M)
     g.buildRBC()
     for _ in range(2):
-        T0, R0, k0 = gicp.before(engine, g)
+        T0, R0, k0 = before(engine, g)
         g.step()
         s = check(T0, R0, k0, 0)
         assert np.isfinite(s).all()
@@ -609,14 +591,14 @@ def test_two_normals_metrics_run_batch2_at_a_partial_block(engine, metric, loss)
     pairs = [(F0, F0.copy()), engine.synth_pair(side, seed=0x7D01, rot_deg=4.0)]
     g, _ = _two_normals_handle(engine, metric, side, nr, loss, batch=2)
     for b, (F, M) in enumerate(pairs):
-        gicp.load(engine, g, F, M, b)
+        load(engine, g, F, M, b)
     g.buildRBC()
     g.run()
     Mem = engine.Memory
     ks = []
     for b, (F, M) in enumerate(pairs):
         h, _ = _two_normals_handle(engine, metric, side, nr, loss)
-        gicp.load(engine, h, F, M)
+        load(engine, h, F, M)
         h.buildRBC()
         ks.append(h.run())
         assert g.state(b).k == ks[-1], (b, g.state(b).k, ks)
@@ -668,7 +650,7 @@ def test_route_table(engine, metric, fused, side, mask):
     if mask & 4:
         g.set_trimming(0.75)
     if mask & 8:
-        g.set_robust_loss(rref.CAUCHY, rl.SCALE[rref.CAUCHY])
+        g.set_robust_loss(rref.CAUCHY, SCALE[rref.CAUCHY])
     chained = metric == "p2p" and fused and mask == 0
     got = (g.run_form(), g.launches_per_iteration())
     g.close()
@@ -682,10 +664,6 @@ def test_route_table(engine, metric, fused, side, mask):
 # last block of 64 (fused) and the last group of 128 (reference order) partly filled.  The modules' own checks, bit for bit, and
 # ICP_MEM_UNIQUE / ICP_MEM_PAIR_FILTER against the restatements' counts.
 
-import test_gpu_pair_filter as pf                                # noqa: E402
-import test_gpu_unique as uq                                     # noqa: E402
-import unique_ref                                                # noqa: E402
-
 
 @pytest.mark.parametrize("case", ["unique", "boundary", "both"])
 @pytest.mark.parametrize("side,nr", [(6, 4), (30, 4)])
@@ -695,35 +673,26 @@ def test_accept_all_apply_pass_at_block_edges(engine, oracle, fused, side, nr, c
     unique, boundary = case != "boundary", case != "unique"
     F, M = engine.synth_pair(side)
     T = _t0()
-    g = pf.make_handle(engine, side, nr, fused, WEIGHTED, POWER, fused, False, boundary, None)
+    g = make_handle(engine, side * side, nr, fused, WEIGHTED, POWER, fused, boundary=side if boundary else None)
     if unique:
         g.set_unique(True)
     assert g.trimming() == 1.0 and g.robust_loss()[0] == 0
-    R0 = pf.one_step(engine, g, F, M, T)
+    R0 = one_step(engine, g, F, M, T)
     want = oracle_search(oracle, F, M, T, nr)
     if case == "unique":
-        _, counts = uq.check_step(engine, oracle, g, F, M, T, side, fused, WEIGHTED, POWER, fused, False, want)
+        _, counts = check_unique_step(engine, oracle, g, F, M, T, side, fused, WEIGHTED, POWER, fused, False, want)
         assert counts[0] == side * side and 0 < counts[1] <= counts[0], counts
     elif case == "boundary":
-        counts, _ = pf.check_step(engine, oracle, g, F, M, T, R0, side, fused, WEIGHTED, POWER, fused, False, side, None, want)
+        counts, _ = check_pair_filter_step(engine, oracle, g, F, M, T, R0, side, fused, WEIGHTED, POWER, fused, False, side, None, want)
         assert counts[0] == side * side and counts[1] > 0 and counts[2] == 0 and counts[3] > 0, counts
     else:
         nn_id = g.read(Mem.NN_ID)
         assert np.array_equal(nn_id["id"], want[0]["id"])
-        _, counts, W0, (_, _, acc) = pf.numpy_rule(engine, g, F, M, R0, True, False, side, None)
+        _, counts, W0, (_, _, acc) = pair_filter_rule_of(engine, g, F, M, R0, True, False, side, None)
         assert np.array_equal(g.read(Mem.PAIR_FILTER), counts) and counts[1] > 0 and counts[3] > 0, (g.read(Mem.PAIR_FILTER), counts)
         win, _, ucounts = unique_ref.unique_rule(nn_id["id"], g.read(Mem.NN), g.read(Mem.QT), np.where(acc, W0, np.float32(0)).astype(np.float32))
         got = g.read(Mem.UNIQUE)
         assert np.array_equal(got, ucounts) and got[0] == counts[3] and 0 < got[1] <= got[0], (got, ucounts, counts)
-        W, sw, means, S, Tk = trim.expected_pieces(oracle, F, M, T, nn_id, side, fused, True, POWER, fused, ~win)
-        gW = g.read(Mem.W)
-        assert_bits(gW, W, "weights")
-        assert np.all(np.ascontiguousarray(gW[~win]).view(np.uint32) == 0) and np.all(gW[win] != 0)
-        assert_bits(g.read(Mem.SUM_W), np.array([sw]), "sum of weights")
-        assert_bits(g.read(Mem.MEANS), means, "means")
-        assert_bits(g.read(Mem.S), S, "S")
-        gTk = g.read(Mem.TK)
-        nan = np.isnan(Tk)
-        assert np.array_equal(np.isnan(gTk), nan), ("Tk", gTk, Tk)
-        assert_bits(gTk[~nan], Tk[~nan], "Tk")
+        check_pieces(engine, oracle, g, F, M, T, side, fused, True, POWER, fused, ~win)
+        assert np.all(g.read(Mem.W)[win] != 0)
     g.close()

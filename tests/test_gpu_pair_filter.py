@@ -20,15 +20,14 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import p2pl_ref                                                 # noqa: E402
 import pair_filter_ref as ref                                   # noqa: E402
 import robust_ref                                               # noqa: E402
-from test_gpu_parity import A, C_, assert_bits, set_modes      # noqa: E402
-from test_gpu_rejection import _holes, _t0, oracle_search, IDENTITY      # noqa: E402
-from test_gpu_trimming import expected_pieces, trim_rule, weights_before_trim, _partial_overlap      # noqa: E402
+import icp_checks      # noqa: E402
+from icp_checks import (A, C_, IDENTITY, MODES, POWER, EIGEN, REGULAR, WEIGHTED, assert_bits,  # noqa: E402
+                        check_pair_filter_step as check_step, expected_pieces, holes_pair as _holes, one_step, oracle_search,
+                        only_invalid, pair_filter_rule_of as numpy_rule, set_modes, trim_rule,
+                        _partial_overlap, _t0)
 
 pytestmark = pytest.mark.gpu
 
-POWER, EIGEN = 1, 0
-REGULAR, WEIGHTED = 0, 1
-MODES = [(POWER, False), (POWER, True), (EIGEN, False)]
 MIN_COS = 0.95
 RULES = {"boundary": (True, None), "normal": (False, MIN_COS), "both": (True, MIN_COS)}
 # (n, at_boundary, incompatible, accepted) of the numpy rule on the CPU oracle's correspondences at _t0 (), side 128, |R| = 256
@@ -40,85 +39,15 @@ ADDED_P2P, ADDED_PLANE = 2, 1
 
 
 def make_handle(engine, side, nr, fused, weighted, rot, power_fast, invalid, boundary, min_cos, batch=1, gw=None):
-    g = engine.ICP(0, rot, weighted)
-    g.init(side * side, nr, A, C_, batch=batch)
-    set_modes(engine, g, power_fast, fused)
-    if invalid:
-        g.set_rejection(True, None)
-    if boundary:
-        g.set_boundary_rejection(gw or side)
-    if min_cos is not None:
-        g.set_normals(1, gw or side)                     # Normals.GRID
-        g.set_normal_rejection(min_cos)
-    return g
-
-
-def one_step(engine, g, F, M, T):
-    """Returns R as the step's search used it."""
-    g.write(engine.Memory.F, F); g.write(engine.Memory.M, M)
-    g.buildRBC()
-    g.write(engine.Memory.T, T, block=True)
-    R0 = g.read(engine.Memory.R).ravel().copy()
-    g.step()
-    return R0
-
-
-def numpy_rule(engine, g, F, M, R0, weighted, invalid, gw, min_cos, b=0, nn_id=None):
-    """(rows that weigh nothing, counts, weights before the rules, (at_boundary, incompatible, accepted))."""
-    Mem = engine.Memory
-    if nn_id is None:
-        nn_id = g.read(Mem.NN_ID, batch_index=b)
-    PF, PM = g.read(Mem.NN, batch_index=b), g.read(Mem.QT, batch_index=b)
-    W0 = weights_before_trim(nn_id, M, PF, PM, weighted, invalid)
-    NF = NM = None
-    if min_cos is not None:
-        NF, NM = g.read(Mem.NORMALS_F, batch_index=b), g.read(Mem.NORMALS_M, batch_index=b)
-    bnd, inc, acc, counts = ref.pair_filter(nn_id["id"], W0, F, gw, NF, NM, R0, min_cos)
-    return ~acc, counts, W0, (bnd, inc, acc)
-
-
-def check_step(engine, oracle, g, F, M, T, R0, side, fused, weighted, rot, power_fast, invalid, gw, min_cos, want=None, b=0):
-    """The engine's step from T (already taken): the search against the oracle's, ICP_MEM_PAIR_FILTER, W, sum W, means, S, Tk."""
-    Mem = engine.Memory
-    gn = g.read(Mem.NN_ID, batch_index=b)
-    if want is not None:
-        nn_id, rid = want
-        assert np.array_equal(gn["id"], nn_id["id"]), "correspondence ids: %d differ" % np.count_nonzero(gn["id"] != nn_id["id"])
-        assert_bits(gn["dist"], nn_id["dist"], "correspondence distances")
-        assert np.array_equal(g.read(Mem.RID, batch_index=b), rid), "nearest representative"
-    else:
-        nn_id = gn
-    zero, counts, W0, masks = numpy_rule(engine, g, F, M, R0, weighted, invalid, gw, min_cos, b, nn_id)
-    got = g.read(Mem.PAIR_FILTER, batch_index=b)
-    print("ICP_MEM_PAIR_FILTER", got.tolist(), "numpy", counts.tolist())
-    assert np.array_equal(got, counts), ("ICP_MEM_PAIR_FILTER", got, counts)
-    assert got[0] == got[1] + got[2] + got[3]
-    W, sw, means, S, Tk = expected_pieces(oracle, F, M, T, nn_id, side, fused, weighted, rot, power_fast, zero)
-    gW = g.read(Mem.W, batch_index=b)
-    assert_bits(gW, W, "weights")
-    assert np.all(np.ascontiguousarray(gW[zero]).view(np.uint32) == 0), "a rejected pair's weight is +0"
-    assert np.all(gW[masks[2]] != 0), "an accepted pair keeps its weight"
-    assert_bits(g.read(Mem.NN, batch_index=b)[:, 3], W, "the NN output's weights")
-    assert_bits(g.read(Mem.SUM_W, batch_index=b), np.array([sw]), "sum of weights")
-    assert_bits(g.read(Mem.MEANS, batch_index=b), means, "means")
-    assert_bits(g.read(Mem.S, batch_index=b), S, "S")
-    gTk = g.read(Mem.TK, batch_index=b)
-    nan = np.isnan(Tk)
-    assert np.array_equal(np.isnan(gTk), nan), ("Tk", gTk, Tk)
-    assert_bits(gTk[~nan], Tk[~nan], "Tk")
-    return counts, masks
+    return icp_checks.make_handle(engine, side * side, nr, fused, weighted, rot, power_fast, batch, rejection=only_invalid(invalid),
+                                  boundary=(gw or side) if boundary else None,
+                                  normal_rejection=(gw or side, min_cos) if min_cos is not None else None)
 
 
 @pytest.fixture(scope="module")
 def scenes_A(engine, oracle):
     """name -> (F, M, T, invalid flag, the oracle's (nn_id, rid) at T): a clean pair and a blobs30 holes pair."""
-    side, nr = 128, 256
-    T = _t0()
-    out = {}
-    for name in ("clean", "holes"):
-        F, M = engine.synth_pair(side) if name == "clean" else _holes(engine, side, 0x1C9D5EED)
-        out[name] = (F, M, T, name == "holes", oracle_search(oracle, F, M, T, nr))
-    return out
+    return icp_checks.scenes_A(engine, oracle)
 
 
 # ---- 0. arguments and getters

@@ -10,74 +10,11 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rotation_cases      # noqa: E402
+from icp_checks import (A, C_, assert_bits, check_rbc, parity_check_step as check_step, parity_make as make,  # noqa: E402
+                        set_modes)
 
 pytestmark = pytest.mark.gpu
-
-A, C_ = 2e2, 1e-6
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.float64:
-        return a.view(np.uint64)
-    return a.view(np.uint32)
-
-
-def assert_bits(got, want, what):
-    got = np.ascontiguousarray(got)
-    want = np.ascontiguousarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = np.nonzero(bits(got).reshape(-1) != bits(want).reshape(-1))[0]
-    assert bad.size == 0, "%s: %d of %d words differ, first at %d: got %r want %r" % (
-        what, bad.size, got.size, bad[0], got.reshape(-1)[bad[0]], want.reshape(-1)[bad[0]])
-
-
-def set_modes(engine, g, power_fast=False, fused=False):
-    """Explicit modes (the handle's defaults are the benchmarked ones: squared + fused)."""
-    g.setPowerMode(engine.PowerMode.SQUARED if power_fast else engine.PowerMode.LITERAL)
-    g.setReduceMode(engine.ReduceMode.FUSED if fused else engine.ReduceMode.REFERENCE_ORDER)
-
-
-def make(engine, oracle, side, nr, rot=1, weighted=1, power_fast=False, zero_fraction=0.0, seed=0x1C9D5EED,
-         max_iterations=40, fused=False):
-    m = side * side
-    F, M = engine.synth_pair(side, seed=seed, zero_fraction=zero_fraction)
-    g = engine.ICP(0, rot, weighted)
-    g.init(m, nr, A, C_, max_iterations=max_iterations)
-    set_modes(engine, g, power_fast, fused)
-    g.write(engine.Memory.F, F)
-    g.write(engine.Memory.M, M)
-    o = oracle.OracleICP(m, nr, A, C_, rot=rot, weighted=weighted, power_fast=power_fast, threads=8,
-                         max_iterations=max_iterations, fused=fused)
-    o.write_f(F)
-    o.write_m(M)
-    return g, o, F, M
-
-
-def check_rbc(engine, g, o):
-    Mem = engine.Memory
-    assert_bits(g.read(Mem.REPS), o.reps, "representatives")
-    assert np.array_equal(g.read(Mem.RBC_OWNER), o.rbc_owner), "owner"
-    assert np.array_equal(g.read(Mem.RBC_N), o.rbc_N), "N"
-    assert np.array_equal(g.read(Mem.RBC_O), o.rbc_O), "O"
-    assert np.array_equal(g.read(Mem.RBC_PERM), o.rbc_perm), "perm"
-
-
-def check_step(engine, g, o, weighted=True):
-    Mem = engine.Memory
-    assert np.array_equal(g.read(Mem.RID), o.rid), "nearest representative"
-    gn, on = g.read(Mem.NN_ID), o.nn_id
-    assert np.array_equal(gn["id"], on["id"]), "correspondence ids: %d differ" % np.count_nonzero(gn["id"] != on["id"])
-    assert_bits(gn["dist"], on["dist"], "correspondence distances")
-    if weighted:
-        assert_bits(g.read(Mem.W), o.W, "weights")
-        assert_bits(g.read(Mem.SUM_W), np.array([o.sum_w]), "sum of weights")
-    assert_bits(g.read(Mem.MEANS), o.means, "means")
-    assert_bits(g.read(Mem.S), o.S, "S")
-    assert_bits(g.read(Mem.TK), o.Tk, "Tk")
-    assert_bits(g.read(Mem.RK).reshape(3, 3), o.Rk, "Rk")
-    assert_bits(g.read(Mem.R).reshape(3, 3), o.R, "R")
-    assert_bits(g.read(Mem.T), o.T, "T")
 
 
 @pytest.mark.parametrize("side,nr", [(128, 256), (32, 16), (64, 64), (30, 4), (6, 4), (16, 256), (192, 2048), (96, 1024)])
@@ -1024,8 +961,7 @@ def test_reference_kat_through_the_hip_rotation_solvers(engine, oracle):
 def test_planar_scene_through_the_hip_rotation_solvers(engine, oracle, seed):
     """Coplanar points (the reference's wall scene at the solver, tests/test_oracle_golden.py::test_squared_power_method_on_a_planar_scene):
     the device's squared start takes the norm shift exactly as the oracle does — same bits, two passes — and the literal loop its 1000 trips."""
-    from test_oracle_golden import _planar_case
-    S, means, Rt = _planar_case(seed)
+    S, means, Rt = rotation_cases.planar_case(seed)
     Tq, Rq, itq = engine.power_method(S, means, mode=engine.PowerMode.SQUARED)
     Tl, Rl, itl = engine.power_method(S, means, mode=engine.PowerMode.LITERAL)
     oq, oq_it = oracle.power_method(S, means, fast=True)

@@ -2,9 +2,7 @@
 
 Every iteration is checked teacher-forced: the restatement takes the engine's own search outputs of that iteration (NN, QT, NN_ID —
 stored every iteration with the metric on) and its transform before the step, and must give the same PLANE_SYSTEM, T, R, TK and RK
-bits.  The search itself is the unchanged one (tests/test_gpu_parity.py checks it against the oracle).
-
-make, load, _messy_grid, _errors and _register serve tests/test_gpu_colored_icp.py too (make and _register take the metric)."""
+bits.  The search itself is the unchanged one (tests/test_gpu_parity.py checks it against the oracle)."""
 import os
 import sys
 
@@ -13,57 +11,17 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import p2pl_ref as ref                                          # noqa: E402
-from test_gpu_parity import A, C_, assert_bits                  # noqa: E402
+from icp_checks import (A, C_, EIGEN, GIVEN, GRID, IDENTITY as IDENTITY8, P2P, P2PL, POWER, REGULAR, SIZES, WEIGHTED,  # noqa: E402
+                        assert_bits, check_last, load, make_plane as make, messy_grid as _messy_grid, register as _register,
+                        restate_p2pl, _errors)
+import icp_checks      # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-POWER, EIGEN = 1, 0
-REGULAR, WEIGHTED = 0, 1
-P2P, P2PL, COLORED = 0, 1, 2
-GIVEN, GRID = 0, 1
-SIZES = {"small": (32, 64), "A": (128, 256), "B": (256, 1024)}
-IDENTITY8 = np.array([0, 0, 0, 1, 0, 0, 0, 1], np.float32)
-
-
-def make(engine, side, nr, weighted=WEIGHTED, rot=POWER, mu=0.05, normals=GRID, fused=True, power_fast=True, batch=1,
-         max_iterations=40, metric=P2PL, kappa=1000.0):
-    """A handle with a plane metric on: P2PL, or COLORED with the weight kappa."""
-    g = engine.ICP(0, rot, weighted)
-    g.init(side * side, nr, A, C_, max_iterations, batch=batch)
-    g.setPowerMode(engine.PowerMode.SQUARED if power_fast else engine.PowerMode.LITERAL)
-    g.setReduceMode(engine.ReduceMode.FUSED if fused else engine.ReduceMode.REFERENCE_ORDER)
-    g.set_normals(normals, side if normals == GRID else 0)
-    if metric == COLORED:
-        g.set_color_weight(kappa)
-    g.set_error_metric(metric, mu)
-    return g
-
-
-def load(engine, g, F, M, b=0):
-    g.write(engine.Memory.F, F, batch_index=b)
-    g.write(engine.Memory.M, M, batch_index=b)
 
 
 def check_step(engine, g, mu, b=0, normals=None):
     """One step of handle g (all registrations), checked for registration b against the restatement.  Returns the system."""
-    Mem = engine.Memory
-    T0, R0 = g.read(Mem.T, b).copy(), g.read(Mem.R, b).ravel().copy()
-    g.step()
-    return check_last(engine, g, mu, T0, R0, b, normals)
-
-
-def check_last(engine, g, mu, T0, R0, b=0, normals=None):
-    Mem = engine.Memory
-    PF, PM, ids = g.read(Mem.NN, b), g.read(Mem.QT, b), g.read(Mem.NN_ID, b)["id"]
-    N = g.read(Mem.NORMALS_F, b) if normals is None else normals
-    system, T, R, Tk, Rk = ref.step(PF, PM, ids, N, mu, T0, R0)
-    assert_bits(g.read(Mem.PLANE_SYSTEM, b), system, "PLANE_SYSTEM (registration %d)" % b)
-    assert_bits(g.read(Mem.T, b), T, "T (registration %d)" % b)
-    assert_bits(g.read(Mem.R, b).ravel(), R, "R (registration %d)" % b)
-    assert_bits(g.read(Mem.TK, b), Tk, "TK (registration %d)" % b)
-    assert_bits(g.read(Mem.RK, b).ravel(), Rk, "RK (registration %d)" % b)
-    assert g.state(b).power_iterations == 0
-    return system
+    return icp_checks.check_step(engine, g, restate_p2pl(mu, normals), b)
 
 
 # ---- 0. the composition restatement against the engine's own point-to-point steps
@@ -87,19 +45,6 @@ def test_composition_restatement_matches_point_to_point_steps(engine):
 
 
 # ---- 1. grid normals
-
-def _messy_grid(engine, side, seed):
-    F, _ = engine.synth_pair(side, seed=seed)
-    F = engine.punch_holes(F, side, side, engine.HOLES_CONTIGUOUS, 0.15, True, seed=seed)
-    F = engine.punch_holes(F, side, side, engine.HOLES_SCATTERED, 0.05, True, seed=seed + 1)
-    rng = np.random.default_rng(seed)
-    idx = rng.choice(side * side, 40, replace=False)
-    F[idx[:10], 0] = np.nan
-    F[idx[10:20], 1] = np.inf
-    F[idx[20:30], 2] = -np.inf
-    F[idx[30:], :3] = 0.0
-    return F
-
 
 @pytest.mark.parametrize("side,nr", [(32, 64), (128, 256), (256, 1024)])
 def test_grid_normals(engine, side, nr):
@@ -246,7 +191,7 @@ def test_batch_of_64_at_A(engine):
     T0 = [(g.read(engine.Memory.T, b).copy(), g.read(engine.Memory.R, b).ravel().copy()) for b in range(n)]
     g.step()
     for b in range(n):
-        check_last(engine, g, 0.05, T0[b][0], T0[b][1], b)
+        check_last(engine, g, restate_p2pl(0.05), T0[b][0], T0[b][1], None, b)
     # a few registrations against single handles
     for b in (0, 17, 63):
         h = make(engine, side, nr, mu=0.05)
@@ -469,35 +414,13 @@ def test_switching_back_is_point_to_point(engine, fused):
 
 # ---- 7. accuracy
 
-def _errors(engine, T, T_true):
-    from icp_amd import workloads as W
-    return W.rotation_error_deg(T, T_true), float(np.linalg.norm(T[4:7].astype(np.float64) - T_true[4:7]))
-
-
-def _register(engine, F, M, metric, mu=0.0, kappa=0.0):
-    g = engine.ICP(0)
-    g.init(F.shape[0], 256, A, C_)
-    if metric != P2P:
-        g.set_normals(GRID, int(round(np.sqrt(F.shape[0]))))
-        if metric == COLORED:
-            g.set_color_weight(kappa)
-        g.set_error_metric(metric, mu)
-    load(engine, g, F, M)
-    g.buildRBC()
-    k = g.run()
-    T = g.read(engine.Memory.T).copy()
-    conv = g.state().converged
-    g.close()
-    return T, k, conv
-
-
 def test_accuracy_curved_scene(engine):
     """Scene 0, mu = 0 converges.  Measured on an MI355X: point-to-point 0.1251 deg / 8.810 mm in 36 iterations (the half-cell sampling
     offset of the moving frame), point-to-plane 0.0051 deg / 0.121 mm in 8; the bounds are more than twice the measured values."""
     F, M, T_true = engine.synth_pair_scene(128, engine.SCENE_CURVED)
     Tp, kp, _ = _register(engine, F, M, P2P)
     T, k, conv = _register(engine, F, M, P2PL, 0.0)
-    (rp, tp), (r, t) = _errors(engine, Tp, T_true), _errors(engine, T, T_true)
+    (rp, tp), (r, t) = _errors(Tp, T_true), _errors(T, T_true)
     print("curved scene: point-to-point %.4f deg %.3f mm k=%d | point-to-plane mu=0 %.4f deg %.3f mm k=%d"
           % (rp, tp, kp, r, t, k))
     assert conv == 1 and k <= 20, k
@@ -511,12 +434,12 @@ def test_accuracy_wall_scene(engine):
     (With the scene's default motion, 3 degrees and 31 mm, no variant gets there in 40 iterations: DESIGN.md.)"""
     F, M, T_true = engine.synth_pair_scene(128, engine.SCENE_WALL, rot_deg=1.0, t=(8.0, -4.0, 5.0))
     Tp, kp, _ = _register(engine, F, M, P2P)
-    (rp, tp) = _errors(engine, Tp, T_true)
+    (rp, tp) = _errors(Tp, T_true)
     line = "wall scene: point-to-point %.4f deg %.3f mm k=%d" % (rp, tp, kp)
     res = {}
     for mu in (0.0, 0.05, 1.0):
         T, k, conv = _register(engine, F, M, P2PL, mu)
-        res[mu] = _errors(engine, T, T_true) + (k, conv)
+        res[mu] = _errors(T, T_true) + (k, conv)
         line += " | point-to-plane mu=%g %.4f deg %.3f mm k=%d" % (mu, res[mu][0], res[mu][1], k)
     print(line)
     r, t, k, conv = res[0.05]

@@ -11,116 +11,15 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_gpu_parity import A, C_, assert_bits, set_modes      # noqa: E402
+from icp_checks import (A, C_, IDENTITY, POWER, EIGEN, REGULAR, WEIGHTED, assert_bits, check_rejection_step as check_one_step,  # noqa: E402
+                        holes_pair as _holes, pick_max_dist, set_modes, step_batch, _t0)
+import icp_checks      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-POWER, EIGEN = 1, 0
-REGULAR, WEIGHTED = 0, 1
-IDENTITY = np.array([0, 0, 0, 1, 0, 0, 0, 1], np.float32)
-
-
-def _t0():
-    """A non-identity starting transform: 1 degree about a skew axis, a few mm."""
-    ax = np.array([0.3, 0.9, 0.1]) / np.linalg.norm([0.3, 0.9, 0.1])
-    h = np.deg2rad(1.0) / 2
-    return np.array([*(np.sin(h) * ax), np.cos(h), 4.0, -3.0, 2.0, 1.0], np.float32)
-
-
-def _holes(engine, side, seed, name="blobs30"):
-    from icp_amd import workloads as W
-    return W.holes_pair(engine, name, side, seed=seed)
-
-
-def rejected_set(M, PF, PM, invalid, max_dist):
-    """The rule of include/icp_amd.h in numpy: M = the moving set (untransformed), PF / PM = (matched fixed xyz, w) / (transformed
-    moving xyz, dist) per query."""
-    rej = np.zeros(M.shape[0], bool)
-    if invalid:
-        rej |= (M[:, :3] == 0).all(axis=1) | (PF[:, :3] == 0).all(axis=1)
-    if max_dist:
-        d2 = np.float32(max_dist) * np.float32(max_dist)
-        g = (PM[:, :3] - PF[:, :3]).astype(np.float32)
-        geo = (g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2]
-        rej |= ~(geo <= d2)
-    return rej
-
-
-def expected_pieces(oracle, F, M, T, nn_id, side, fused, weighted, rot, power_fast, invalid, max_dist):
-    """(rejected, W, sum_w, means, S, Tk) of one step at T from the oracle's pieces with the rejected rows zeroed."""
-    tM = oracle.transform_q(M, T)
-    NN = np.ascontiguousarray(F[nn_id["id"]])
-    rej = rejected_set(M, NN[:, :4], tM[:, :4], invalid, max_dist)
-    NNz, tMz = NN.copy(), tM.copy()
-    NNz[rej] = 0.0
-    tMz[rej] = 0.0
-    dist = nn_id["dist"].astype(np.float32)
-    if fused:
-        W = (np.float32(100.0) / (np.float32(100.0) + dist)).astype(np.float32) if weighted else np.ones_like(dist)
-        W[rej] = 0.0
-        sw, means, S = oracle.moments_fused(NNz, tMz, W, side, C_)
-    else:
-        D = nn_id.copy()
-        if not weighted:
-            D["dist"] = 0.0                          # 100 / (100 + 0) = 1: the weights of REGULAR mode, w in {0, 1}
-        D["dist"][rej] = np.inf                      # 100 / (100 + inf) = +0
-        W, sw = oracle.weights(D)
-        means = oracle.mean_weighted(NNz, tMz, W, sw)
-        DF, DM = oracle.devs(NNz, tMz, means)
-        S = oracle.sij(DM, DF, W, C_)
-    if rot == POWER:
-        Tk, _ = oracle.power_method(S, means, fast=power_fast)
-    else:
-        _, Tk = oracle.svd_rotation(S, means)
-    return rej, W, sw, means, S, Tk
-
-
-def oracle_search(oracle, F, M, T, nr):
-    o = oracle.OracleICP(F.shape[0], nr, A, C_, threads=8)
-    o.write_f(F); o.write_m(M); o.build_rbc(); o.write_t(T)
-    o.step()
-    return o.nn_id, o.rid
-
-
-def check_one_step(engine, oracle, g, F, M, T, side, nr, fused, weighted, rot, power_fast, invalid, max_dist, b=0):
-    """The engine's step from T (already taken) against the oracle: search, rejected set, W, sum W, means, S, Tk."""
-    Mem = engine.Memory
-    nn_id, rid = oracle_search(oracle, F, M, T, nr)
-    gn = g.read(Mem.NN_ID, batch_index=b)
-    assert np.array_equal(gn["id"], nn_id["id"]), "correspondence ids: %d differ" % np.count_nonzero(gn["id"] != nn_id["id"])
-    assert_bits(gn["dist"], nn_id["dist"], "correspondence distances")
-    assert np.array_equal(g.read(Mem.RID, batch_index=b), rid), "nearest representative"
-    rej, W, sw, means, S, Tk = expected_pieces(oracle, F, M, T, nn_id, side, fused, weighted, rot, power_fast, invalid, max_dist)
-    PF, PM = g.read(Mem.NN, batch_index=b), g.read(Mem.QT, batch_index=b)
-    assert np.array_equal(rejected_set(M, PF, PM, invalid, max_dist), rej), "rejected set"
-    assert rej.any() and not rej.all()
-    gW = g.read(Mem.W, batch_index=b)
-    assert_bits(gW, W, "weights")
-    assert np.all(gW[rej].view(np.uint32) == 0), "a rejected pair's weight is +0"
-    assert_bits(g.read(Mem.SUM_W, batch_index=b), np.array([sw]), "sum of weights")
-    assert_bits(g.read(Mem.MEANS, batch_index=b), means, "means")
-    assert_bits(g.read(Mem.S, batch_index=b), S, "S")
-    assert_bits(g.read(Mem.TK, batch_index=b), Tk, "Tk")
-    return rej
-
-
-def pick_max_dist(oracle, F, M, T, nr, frac=0.12):
-    """A distance that rejects about `frac` of the pairs whose endpoints are both valid, at T."""
-    nn_id, _ = oracle_search(oracle, F, M, T, nr)
-    tM = oracle.transform_q(M, T)
-    NN = F[nn_id["id"]]
-    ok = ~((M[:, :3] == 0).all(axis=1) | (NN[:, :3] == 0).all(axis=1))
-    g = (tM[:, :3] - NN[:, :3]).astype(np.float64)
-    geo = (g * g).sum(axis=1)[ok]
-    return float(np.sqrt(np.quantile(geo, 1.0 - frac)))
-
 
 def make_handle(engine, m, nr, fused, weighted, rot, power_fast, invalid, max_dist, batch=1):
-    g = engine.ICP(0, rot, weighted)
-    g.init(m, nr, A, C_, batch=batch)
-    set_modes(engine, g, power_fast, fused)
-    g.set_rejection(invalid, max_dist)
-    return g
+    return icp_checks.make_handle(engine, m, nr, fused, weighted, rot, power_fast, batch, rejection=(invalid, max_dist))
 
 
 KINDS = [("invalid", True, False), ("distance", False, True), ("both", True, True)]
@@ -241,12 +140,7 @@ def test_one_step_batch64(engine, oracle, fused):
     T = _t0()
     md = pick_max_dist(oracle, pairs[0][0], pairs[0][1], T, nr)
     g = make_handle(engine, side * side, nr, fused, WEIGHTED, POWER, fused, True, md, batch=B)
-    for b, (F, M) in enumerate(pairs):
-        g.write(engine.Memory.F, F, batch_index=b); g.write(engine.Memory.M, M, batch_index=b)
-    g.buildRBC()
-    for b in range(B):
-        g.write(engine.Memory.T, T, batch_index=b, block=True)
-    g.step()
+    step_batch(engine, g, pairs, T)
     for b in W.CHECKED:
         F, M = pairs[b]
         check_one_step(engine, oracle, g, F, M, T, side, nr, fused, WEIGHTED, POWER, fused, True, md, b=b)

@@ -17,10 +17,8 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import float64_ref as f64                                        # noqa: E402
 import robust_ref as ref                                         # noqa: E402
-from test_gpu_parity import A, C_, assert_bits                  # noqa: E402
-from test_gpu_rejection import _t0                               # noqa: E402
-from test_gpu_robust_loss import (COLORED, GIVEN, GRID, LOSSES, P2PL, POWER, REGULAR, WEIGHTED, _outlier_scene, check_p2p, check_p2p_or_identity, check_plane,  # noqa: E402
-                                  one_step, p2p_expected, p2p_handle, plane_handle)
+from icp_checks import (A, C_, COLORED, GIVEN, LOSSES, P2PL, POWER, REGULAR, SCALE, WEIGHTED, assert_bits, check_p2p,  # noqa: E402
+                        check_p2p_or_identity, check_plane, one_step, p2p_expected, p2p_handle, plane_handle, _outlier_scene, _t0)
 
 pytestmark = pytest.mark.gpu
 
@@ -320,7 +318,6 @@ def test_p2p_step_against_float64(engine, oracle, which, fused, loss):
     starts next to the solution, so |t_k| is 0.8 .. 2 mm while t_k = mean_f - s_k R_k mean_m is a difference of centroids about
     1800 mm from the origin: fp32 rounding of the transformed points and of R_k leaves about 1e-4 mm, a 1e-7 share of the centroids
     but a 1e-4 share of this t_k.  The bound for |dt| / |t_k| is therefore twice the oracle's largest measured distance, 2.7e-4."""
-    from test_gpu_robust_loss import SCALE
     F, M = engine.synth_pair(128) if which == "clean" else _outlier_scene(engine)[:2]
     T = _t0()
     Mem = engine.Memory

@@ -12,104 +12,13 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import robust_ref as ref                                        # noqa: E402
-from test_gpu_parity import A, C_, assert_bits, set_modes      # noqa: E402
-from test_gpu_rejection import _holes, _t0, rejected_set       # noqa: E402
-from test_gpu_trimming import trim_rule                         # noqa: E402
+from icp_checks import (A, C_, COLORED, EIGEN, GIVEN, GRID, LOSSES, P2P, P2PL, POWER, REGULAR, SCALE, WEIGHTED, assert_bits,  # noqa: E402
+                        check_p2p, check_plane, holes_pair as _holes, one_step, p2p_handle, plane_handle, _outlier_scene, step_batch, _t0)
 
 pytestmark = pytest.mark.gpu
 
-POWER, EIGEN = 1, 0
-REGULAR, WEIGHTED = 0, 1
-P2P, P2PL, COLORED = 0, 1, 2
-GIVEN, GRID = 0, 1
-LOSSES = [ref.HUBER, ref.CAUCHY, ref.TUKEY]
-SCALE = {ref.HUBER: 8.0, ref.CAUCHY: 12.0, ref.TUKEY: 30.0}     # (mm: each cuts into the residuals of the scenes below)
-
 
 # ---- point-to-point
-
-def p2p_expected(oracle, g, engine, M, T, side, fused, weighted, rot, power_fast, invalid, max_dist, keep, loss, scale, b=0):
-    """(W', sum W, means, S, Tk) of the step the engine took from T, from its own outputs."""
-    Mem = engine.Memory
-    nn_id = g.read(Mem.NN_ID, batch_index=b)
-    PF, PM = g.read(Mem.NN, batch_index=b), g.read(Mem.QT, batch_index=b)
-    dist = nn_id["dist"].astype(np.float32)
-    W0 = (np.float32(100.0) / (np.float32(100.0) + dist)).astype(np.float32) if weighted else np.ones_like(dist)
-    W0[rejected_set(M, PF, PM, invalid, max_dist)] = 0.0
-    if keep < 1.0:
-        acc, _ = trim_rule(PF, PM, W0, keep)
-        W0[~acc] = 0.0
-    W = ref.p2p_weights(W0, PF, PM, loss, scale)
-    zero = W == 0
-    F = g.read(Mem.F, batch_index=b)
-    tM = oracle.transform_q(M, T)
-    NNz, tMz = np.ascontiguousarray(F[nn_id["id"]]), tM.copy()
-    NNz[zero] = 0.0
-    tMz[zero] = 0.0
-    if fused:
-        sw, means, S = oracle.moments_fused(NNz, tMz, W, side, C_)
-    else:
-        sw = ref.sum_w_reference(W)
-        means = oracle.mean_weighted(NNz, tMz, W, sw)
-        DF, DM = oracle.devs(NNz, tMz, means)
-        S = oracle.sij(DM, DF, W, C_)
-    if rot == POWER:
-        Tk, _ = oracle.power_method(S, means, fast=power_fast)
-    else:
-        _, Tk = oracle.svd_rotation(S, means)
-    return W, sw, means, S, Tk
-
-
-def check_p2p(oracle, g, engine, M, T, side, fused, weighted, rot, power_fast, invalid=False, max_dist=None, keep=1.0,
-              loss=ref.CAUCHY, scale=12.0, b=0):
-    Mem = engine.Memory
-    W, sw, means, S, Tk = p2p_expected(oracle, g, engine, M, T, side, fused, weighted, rot, power_fast, invalid, max_dist, keep, loss,
-                                       scale, b)
-    assert_bits(g.read(Mem.W, batch_index=b), W, "W'")
-    assert_bits(g.read(Mem.SUM_W, batch_index=b), np.array([sw]), "sum of weights")
-    assert_bits(g.read(Mem.MEANS, batch_index=b), means, "means")
-    assert_bits(g.read(Mem.S, batch_index=b), S, "S")
-    gTk = g.read(Mem.TK, batch_index=b)
-    nan = np.isnan(Tk)
-    assert np.array_equal(np.isnan(gTk), nan), ("Tk", gTk, Tk)
-    assert_bits(gTk[~nan], Tk[~nan], "Tk")
-    return W
-
-
-def check_p2p_or_identity(oracle, g, engine, M, T, side, fused, weighted, rot, power_fast, invalid=False, max_dist=None, keep=1.0,
-                          loss=ref.CAUCHY, scale=12.0, b=0):
-    """check_p2p, or — when the restatement's sum W is 0 — the header's identity step: W' all +0, sum W, means and S zero, T as it
-    was, Tk the identity.  Returns (W', whether nothing was accepted)."""
-    Mem = engine.Memory
-    W, sw, _, _, _ = p2p_expected(oracle, g, engine, M, T, side, fused, weighted, rot, power_fast, invalid, max_dist, keep, loss, scale, b)
-    if sw != 0:
-        return check_p2p(oracle, g, engine, M, T, side, fused, weighted, rot, power_fast, invalid, max_dist, keep, loss, scale, b), False
-    gW = g.read(Mem.W, batch_index=b)
-    assert_bits(gW, W, "W'")
-    assert (np.ascontiguousarray(gW).view(np.uint32) == 0).all() and g.read(Mem.SUM_W, batch_index=b)[0] == 0
-    assert (g.read(Mem.MEANS, batch_index=b) == 0).all() and (g.read(Mem.S, batch_index=b) == 0).all()
-    assert_bits(g.read(Mem.T, batch_index=b), T, "T behind a step that accepts nothing")
-    assert_bits(g.read(Mem.TK, batch_index=b), np.array([0, 0, 0, 1, 0, 0, 0, 1], np.float32), "Tk behind a step that accepts nothing")
-    return W, True
-
-
-def p2p_handle(engine, m, nr, fused, weighted, rot, power_fast, loss, scale, invalid=False, max_dist=None, keep=1.0, batch=1, it=40):
-    g = engine.ICP(0, rot, weighted)
-    g.init(m, nr, A, C_, it, batch=batch)
-    set_modes(engine, g, power_fast, fused)
-    if invalid or max_dist:
-        g.set_rejection(invalid, max_dist)
-    if keep < 1.0:
-        g.set_trimming(keep)
-    g.set_robust_loss(loss, scale)
-    return g
-
-
-def one_step(engine, g, F, M, T):
-    g.write(engine.Memory.F, F); g.write(engine.Memory.M, M)
-    g.buildRBC()
-    g.write(engine.Memory.T, T, block=True)
-    g.step()
 
 
 @pytest.fixture(scope="module")
@@ -158,12 +67,7 @@ def test_p2p_batch(engine, oracle, fused):
     pairs = [_holes(engine, side, 0x2000 + b, "blobs30" if b % 2 else "scattered10") for b in range(B)]
     T = _t0()
     g = p2p_handle(engine, side * side, 256, fused, WEIGHTED, POWER, fused, loss, SCALE[loss], invalid=True, batch=B)
-    for b, (F, M) in enumerate(pairs):
-        g.write(engine.Memory.F, F, batch_index=b); g.write(engine.Memory.M, M, batch_index=b)
-    g.buildRBC()
-    for b in range(B):
-        g.write(engine.Memory.T, T, batch_index=b, block=True)
-    g.step()
+    step_batch(engine, g, pairs, T)
     for b, (F, M) in enumerate(pairs):
         check_p2p(oracle, g, engine, M, T, side, fused, WEIGHTED, POWER, fused, invalid=True, loss=loss, scale=SCALE[loss], b=b)
     g.close()
@@ -213,34 +117,6 @@ def test_tukey_below_every_residual_is_the_identity_step(engine, scenes, metric)
 
 
 # ---- plane metrics
-
-def plane_handle(engine, side, nr, metric, loss, scale, mu=0.05, kappa=1e3, normals=GRID, fused=True, batch=1, it=40, keep=1.0):
-    g = engine.ICP(0)
-    g.init(side * side, nr, A, C_, it, batch=batch)
-    g.setPowerMode(engine.PowerMode.SQUARED)
-    g.setReduceMode(engine.ReduceMode.FUSED if fused else engine.ReduceMode.REFERENCE_ORDER)
-    g.set_normals(normals, side if normals == GRID else 0)
-    if metric == COLORED:
-        g.set_color_weight(kappa)
-    g.set_error_metric(metric, mu)
-    if keep < 1.0:
-        g.set_trimming(keep)
-    g.set_robust_loss(loss, scale)
-    return g
-
-
-def check_plane(engine, g, metric, loss, scale, T0, R0, mu=0.05, kappa=1e3, M=None, b=0):
-    Mem = engine.Memory
-    PF, PM, ids = g.read(Mem.NN, b), g.read(Mem.QT, b), g.read(Mem.NN_ID, b)["id"]
-    N = g.read(Mem.NORMALS_F, b)
-    grads = g.read(Mem.COLOR_GRAD_F, b) if metric == COLORED else None
-    system, T, R, Tk, Rk = ref.plane_step(PF, PM, ids, N, mu, loss, scale, T0, R0, grads, M, kappa)
-    assert_bits(g.read(Mem.PLANE_SYSTEM, b), system, "PLANE_SYSTEM")
-    assert_bits(g.read(Mem.T, b), T, "T")
-    assert_bits(g.read(Mem.TK, b), Tk, "TK")
-    assert_bits(g.read(Mem.RK, b).ravel(), Rk, "RK")
-    return system
-
 
 @pytest.mark.parametrize("keep", [1.0, 0.8])
 @pytest.mark.parametrize("loss", LOSSES)
@@ -449,18 +325,6 @@ def test_tracking_equals_fresh_handles(engine, oracle, metric):
 
 
 # ---- accuracy
-
-def _outlier_scene(engine):
-    """The curved scene with about 20 % of the moving landmarks gross outliers: a contiguous band of 26 grid rows pulled 300 mm toward
-    the sensor (an occluder only the moving frame sees)."""
-    F, M, T_true = engine.synth_pair_scene(128, engine.SCENE_CURVED)
-    M = M.copy()
-    rows = slice(50 * 128, 76 * 128)
-    z = M[rows, 2].astype(np.float64)
-    f = np.where(z > 0, (z - 300.0) / z, 1.0).astype(np.float32)
-    M[rows, :3] *= f[:, None]
-    return F, M, T_true
-
 
 def _register(engine, F, M, metric, loss, scale):
     from icp_amd import workloads as W

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_gpu_parity import A, C_, assert_bits, check_rbc, check_step, set_modes      # noqa: E402
+from icp_checks import A, C_, assert_bits, check_rbc, parity_check_step as check_step, set_modes      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 

@@ -12,78 +12,26 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import sym_ref as sref                                          # noqa: E402
 import p2pl_ref as ref                                          # noqa: E402
 import robust_ref                                               # noqa: E402
-from test_gpu_parity import A, C_, assert_bits                  # noqa: E402
+from icp_checks import (A, C_, COLORED, GIVEN, GRID, IDENTITY as IDENTITY8, P2PL, POWER, REGULAR, STEP_SIZES as SIZES, WEIGHTED,  # noqa: E402
+                        assert_bits, load, make_plane, punch_cloud as _holes, restate_symmetric, _errors)
+import icp_checks      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-POWER = 1
-REGULAR, WEIGHTED = 0, 1
-P2P, P2PL, COLORED = 0, 1, 2
-GIVEN, GRID = 0, 1
 ESTATE = 4
-IDENTITY8 = np.array([0, 0, 0, 1, 0, 0, 0, 1], np.float32)
-SIZES = [(128, 256), (50, 4), (256, 1024)]                       # m = 16384; 2500 (no multiple of 256); 65536 with nr = 1024
-
 
 def make(engine, side, nr, weighted=WEIGHTED, mu=0.05, sym=True, normals=GRID, batch=1, max_iterations=40):
-    g = engine.ICP(0, POWER, weighted)
-    g.init(side * side, nr, A, C_, max_iterations, batch=batch)
-    g.set_normals(normals, side if normals == GRID else 0)
-    g.set_error_metric(P2PL, mu)
-    g.set_symmetric(sym)
-    return g
-
-
-def load(engine, g, F, M, b=0):
-    g.write(engine.Memory.F, F, batch_index=b)
-    g.write(engine.Memory.M, M, batch_index=b)
-
-
-def before(engine, g, b=0):
-    Mem = engine.Memory
-    return g.read(Mem.T, b).copy(), g.read(Mem.R, b).ravel().copy(), g.state(b).k
-
-
-def check_last(engine, g, mu, T0, R0, k0, b=0, loss=None, scale=None, steps=1):
-    """The last iteration of registration b against the restatement fed the device's own outputs and the state before that iteration."""
-    Mem = engine.Memory
-    PF, PM, ids = g.read(Mem.NN, b), g.read(Mem.QT, b), g.read(Mem.NN_ID, b)["id"]
-    NF, NM = g.read(Mem.NORMALS_F, b), g.read(Mem.NORMALS_M, b)
-    system, T, R, Tk, Rk = sref.step(PF, PM, ids, NF, NM, mu, T0, R0, loss, scale)
-    assert_bits(g.read(Mem.PLANE_SYSTEM, b), system, "PLANE_SYSTEM (registration %d)" % b)
-    assert_bits(g.read(Mem.T, b), T, "T (registration %d)" % b)
-    assert_bits(g.read(Mem.R, b).ravel(), R, "R (registration %d)" % b)
-    assert_bits(g.read(Mem.TK, b), Tk, "TK (registration %d)" % b)
-    assert_bits(g.read(Mem.RK, b).ravel(), Rk, "RK (registration %d)" % b)
-    st = g.state(b)
-    assert st.k == k0 + steps and st.power_iterations == 0
-    return system
+    return make_plane(engine, side, nr, weighted, mu, normals, batch, max_iterations, symmetric=sym)
 
 
 def check_step(engine, g, mu, b=0, loss=None, scale=None):
-    T0, R0, k0 = before(engine, g, b)
-    g.step()
-    return check_last(engine, g, mu, T0, R0, k0, b, loss, scale)
+    return icp_checks.check_step(engine, g, restate_symmetric(mu, loss, scale), b)
 
 
 def check_fixed_run(engine, g, n, mu, loss=None, scale=None):
-    """A fixed run of n iterations: its last iteration against the restatement, from the state n - 1 steps leave (stepped on the same
-    handle, whose steps are checked one by one elsewhere)."""
-    g.reset_transform(); g.buildRBC()
-    for _ in range(n - 1):
-        g.step()
-    T0, R0, k0 = before(engine, g)
-    g.reset_transform(); g.buildRBC()
-    g.run_fixed(n)
-    return check_last(engine, g, mu, T0, R0, 0, 0, loss, scale, steps=n)
-
-
-def _holes(engine, X, side, seed):
-    X = engine.punch_holes(X, side, side, engine.HOLES_CONTIGUOUS, 0.15, True, seed=seed)
-    return engine.punch_holes(X, side, side, engine.HOLES_SCATTERED, 0.05, True, seed=seed + 1)
+    return icp_checks.check_fixed_run(engine, g, n, restate_symmetric(mu, loss, scale))
 
 
 # ---- 1. steps and fixed runs, bit for bit
@@ -396,11 +344,6 @@ def test_refusals(engine):
 
 
 # ---- 6. convergence, the one free-running check
-
-def _errors(T, T_true):
-    from icp_amd import workloads as W
-    return W.rotation_error_deg(T, T_true), float(np.linalg.norm(T[4:7].astype(np.float64) - T_true[4:7].astype(np.float64)))
-
 
 def test_convergence_against_point_to_plane(engine):
     """Scene 0 at side 128 with the benchmark's motion, 20 % contiguous holes in both frames and ICP_REJECT_INVALID (the pair of

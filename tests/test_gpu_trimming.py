@@ -11,129 +11,22 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_gpu_parity import A, C_, assert_bits, set_modes      # noqa: E402
-from test_gpu_rejection import _holes, _t0, oracle_search, rejected_set, IDENTITY      # noqa: E402
+import icp_checks      # noqa: E402
+from icp_checks import (A, C_, IDENTITY, MODES, POWER, EIGEN, REGULAR, WEIGHTED, assert_bits, check_trim_step as check_step,  # noqa: E402
+                        holes_pair as _holes, one_step, oracle_search, only_invalid, set_modes, trim_rule, weights_before_trim,
+                        _partial_overlap, step_batch, _t0)
 
 pytestmark = pytest.mark.gpu
 
-POWER, EIGEN = 1, 0
-REGULAR, WEIGHTED = 0, 1
-MODES = [(POWER, False), (POWER, True), (EIGEN, False)]
-
-
-def trim_rule(PF, PM, W0, keep):
-    """(accepted mask, [t bits, n, K, accepted]) by the rule: candidates are the pairs of weight != 0 (W0: after rejection, before
-    trimming) with a finite geo; K = ceil (keep n); t = the K-th smallest geo; accepted: candidates with geo <= t."""
-    g = (PM[:, :3] - PF[:, :3]).astype(np.float32)
-    geo = (g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2]
-    cand = (W0 != 0) & np.isfinite(geo)
-    n = int(np.count_nonzero(cand))
-    if n == 0:
-        return np.zeros(PF.shape[0], bool), np.zeros(4, np.uint32)
-    K = min(int(np.ceil(np.float64(np.float32(keep)) * n)), n)
-    t = np.sort(geo[cand])[K - 1]
-    acc = cand & (geo <= t)
-    return acc, np.array([t.view(np.uint32), n, K, np.count_nonzero(acc)], np.uint32)
-
-
-def weights_before_trim(nn_id, M, PF, PM, weighted, invalid):
-    dist = nn_id["dist"].astype(np.float32)
-    W0 = (np.float32(100.0) / (np.float32(100.0) + dist)).astype(np.float32) if weighted else np.ones_like(dist)
-    W0[rejected_set(M, PF, PM, invalid, None)] = 0.0
-    return W0
-
-
-def expected_pieces(oracle, F, M, T, nn_id, side, fused, weighted, rot, power_fast, zero):
-    """(W, sum_w, means, S, Tk) of one step at T from the oracle's pieces with the rows `zero` (trimmed or rejected) zeroed."""
-    tM = oracle.transform_q(M, T)
-    NN = np.ascontiguousarray(F[nn_id["id"]])
-    NNz, tMz = NN.copy(), tM.copy()
-    NNz[zero] = 0.0
-    tMz[zero] = 0.0
-    dist = nn_id["dist"].astype(np.float32)
-    if fused:
-        W = (np.float32(100.0) / (np.float32(100.0) + dist)).astype(np.float32) if weighted else np.ones_like(dist)
-        W[zero] = 0.0
-        sw, means, S = oracle.moments_fused(NNz, tMz, W, side, C_)
-    else:
-        D = nn_id.copy()
-        if not weighted:
-            D["dist"] = 0.0
-        D["dist"][zero] = np.inf
-        W, sw = oracle.weights(D)
-        means = oracle.mean_weighted(NNz, tMz, W, sw)
-        DF, DM = oracle.devs(NNz, tMz, means)
-        S = oracle.sij(DM, DF, W, C_)
-    if rot == POWER:
-        Tk, _ = oracle.power_method(S, means, fast=power_fast)
-    else:
-        _, Tk = oracle.svd_rotation(S, means)
-    return W, sw, means, S, Tk
-
-
-def check_step(engine, oracle, g, F, M, T, side, fused, weighted, rot, power_fast, invalid, keep, want=None, b=0):
-    """The engine's step from T (already taken): trimmed set, ICP_MEM_TRIM, W, sum W, means, S, Tk bit for bit.  want: the oracle's
-    (nn_id, rid) at T (None: the engine's own correspondences feed the oracle's pieces)."""
-    Mem = engine.Memory
-    gn = g.read(Mem.NN_ID, batch_index=b)
-    if want is not None:
-        nn_id, rid = want
-        assert np.array_equal(gn["id"], nn_id["id"]), "correspondence ids: %d differ" % np.count_nonzero(gn["id"] != nn_id["id"])
-        assert_bits(gn["dist"], nn_id["dist"], "correspondence distances")
-        assert np.array_equal(g.read(Mem.RID, batch_index=b), rid), "nearest representative"
-    else:
-        nn_id = gn
-    PF, PM = g.read(Mem.NN, batch_index=b), g.read(Mem.QT, batch_index=b)
-    acc, trim = trim_rule(PF, PM, weights_before_trim(nn_id, M, PF, PM, weighted, invalid), keep)
-    got = g.read(Mem.TRIM, batch_index=b)
-    assert np.array_equal(got, trim), ("ICP_MEM_TRIM", got, trim)
-    W, sw, means, S, Tk = expected_pieces(oracle, F, M, T, nn_id, side, fused, weighted, rot, power_fast, ~acc)
-    gW = g.read(Mem.W, batch_index=b)
-    assert_bits(gW, W, "weights")
-    assert np.all(gW[~acc].view(np.uint32) == 0), "a trimmed pair's weight is +0"
-    assert_bits(g.read(Mem.SUM_W, batch_index=b), np.array([sw]), "sum of weights")
-    assert_bits(g.read(Mem.MEANS, batch_index=b), means, "means")
-    assert_bits(g.read(Mem.S, batch_index=b), S, "S")
-    gTk = g.read(Mem.TK, batch_index=b)
-    nan = np.isnan(Tk)
-    if nan.any():                # (a degenerate S — one accepted pair — leaves the solver's NaN: payload bits are no part of the rule)
-        assert np.array_equal(np.isnan(gTk), nan), ("Tk", gTk, Tk)
-        assert_bits(gTk[~nan], Tk[~nan], "Tk")
-    else:
-        assert_bits(gTk, Tk, "Tk")
-    return acc, trim
-
 
 def make_handle(engine, m, nr, fused, weighted, rot, power_fast, invalid, keep, batch=1):
-    g = engine.ICP(0, rot, weighted)
-    g.init(m, nr, A, C_, batch=batch)
-    set_modes(engine, g, power_fast, fused)
-    if invalid:
-        g.set_rejection(True, None)
-    g.set_trimming(keep)
-    return g
-
-
-def one_step(engine, g, F, M, T, b=None):
-    g.write(engine.Memory.F, F); g.write(engine.Memory.M, M)
-    g.buildRBC()
-    g.write(engine.Memory.T, T, block=True)
-    g.step()
+    return icp_checks.make_handle(engine, m, nr, fused, weighted, rot, power_fast, batch, rejection=only_invalid(invalid), trimming=keep)
 
 
 @pytest.fixture(scope="module")
 def scenes_A(engine, oracle):
     """name -> (F, M, T, invalid flag, the oracle's (nn_id, rid) at T): a clean pair and a blobs30 holes pair."""
-    side, nr = 128, 256
-    T = _t0()
-    out = {}
-    for name in ("clean", "holes"):
-        if name == "clean":
-            F, M = engine.synth_pair(side)
-        else:
-            F, M = _holes(engine, side, 0x1C9D5EED)
-        out[name] = (F, M, T, name == "holes", oracle_search(oracle, F, M, T, nr))
-    return out
+    return icp_checks.scenes_A(engine, oracle)
 
 
 # ---- 1. one step at A, every mode, clean and with holes
@@ -194,12 +87,7 @@ def test_one_step_batch64(engine, oracle, fused):
         pairs.append((F, M))
     T = _t0()
     g = make_handle(engine, side * side, nr, fused, WEIGHTED, POWER, fused, True, 0.7, batch=B)
-    for b, (F, M) in enumerate(pairs):
-        g.write(engine.Memory.F, F, batch_index=b); g.write(engine.Memory.M, M, batch_index=b)
-    g.buildRBC()
-    for b in range(B):
-        g.write(engine.Memory.T, T, batch_index=b, block=True)
-    g.step()
+    step_batch(engine, g, pairs, T)
     ts = set()
     for b in range(B):
         F, M = pairs[b]
@@ -424,15 +312,6 @@ def test_form_and_launch_count(engine):
 
 
 # ---- 5. what it is for: partial overlap
-
-def _partial_overlap(engine):
-    """synth_pair_scene(128) with a frame-to-frame motion (1 degree, (8, -4, 5) mm) and the last quarter of M's rows moved 150 mm
-    towards the camera: a surface F has no counterpart for."""
-    F, M, T_true = engine.synth_pair_scene(128, rot_deg=1.0, t=(8.0, -4.0, 5.0))
-    M = M.copy()
-    M[np.arange(128 * 128) >= 96 * 128, 2] -= 150.0
-    return F, M, T_true
-
 
 @pytest.mark.parametrize("fused", [True, False])
 def test_trimming_copes_with_partial_overlap(engine, fused):

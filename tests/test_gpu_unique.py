@@ -15,89 +15,27 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import p2pl_ref                                                 # noqa: E402
 import robust_ref                                               # noqa: E402
 import unique_ref as ref                                        # noqa: E402
-from test_gpu_parity import A, C_, assert_bits, set_modes      # noqa: E402
-from test_gpu_rejection import _holes, _t0, oracle_search, IDENTITY      # noqa: E402
-from test_gpu_trimming import expected_pieces, trim_rule, weights_before_trim, _partial_overlap      # noqa: E402
+import icp_checks      # noqa: E402
+from icp_checks import (A, C_, IDENTITY, MODES, POWER, EIGEN, REGULAR, WEIGHTED, assert_bits, check_unique_step as check_step,  # noqa: E402
+                        expected_pieces, holes_pair as _holes, one_step, oracle_search, only_invalid, set_modes, trim_rule,
+                        unique_rule_of as numpy_rule, _partial_overlap, step_batch, _t0)
 
 pytestmark = pytest.mark.gpu
 
-POWER, EIGEN = 1, 0
-REGULAR, WEIGHTED = 0, 1
-MODES = [(POWER, False), (POWER, True), (EIGEN, False)]
 # What the header documents for icp_launches_per_iteration: the rule adds claim + resolve + the apply pass on point-to-point, claim +
 # resolve on the plane metrics.
 ADDED_P2P, ADDED_PLANE = 3, 2
 
 
-def numpy_rule(engine, g, M, weighted, invalid, b=0, nn_id=None):
-    """(winner mask, rows that weigh nothing, [n, winners], weights before the rule) from the engine's outputs of registration b."""
-    Mem = engine.Memory
-    if nn_id is None:
-        nn_id = g.read(Mem.NN_ID, batch_index=b)
-    PF, PM = g.read(Mem.NN, batch_index=b), g.read(Mem.QT, batch_index=b)
-    W0 = weights_before_trim(nn_id, M, PF, PM, weighted, invalid)
-    win, cand, counts = ref.unique_rule(nn_id["id"], PF, PM, W0)
-    return win, (W0 == 0) | (cand & ~win), counts, W0
-
-
-def check_step(engine, oracle, g, F, M, T, side, fused, weighted, rot, power_fast, invalid, want=None, b=0):
-    """The engine's step from T (already taken): the search against the oracle's (want = its (nn_id, rid) at T; None: the engine's own
-    correspondences feed the oracle's pieces), ICP_MEM_UNIQUE, W, sum W, means, S, Tk bit for bit.  Returns (winners, counts)."""
-    Mem = engine.Memory
-    gn = g.read(Mem.NN_ID, batch_index=b)
-    if want is not None:
-        nn_id, rid = want
-        assert np.array_equal(gn["id"], nn_id["id"]), "correspondence ids: %d differ" % np.count_nonzero(gn["id"] != nn_id["id"])
-        assert_bits(gn["dist"], nn_id["dist"], "correspondence distances")
-        assert np.array_equal(g.read(Mem.RID, batch_index=b), rid), "nearest representative"
-    else:
-        nn_id = gn
-    win, zero, counts, _ = numpy_rule(engine, g, M, weighted, invalid, b, nn_id)
-    got = g.read(Mem.UNIQUE, batch_index=b)
-    assert np.array_equal(got, counts), ("ICP_MEM_UNIQUE", got, counts)
-    W, sw, means, S, Tk = expected_pieces(oracle, F, M, T, nn_id, side, fused, weighted, rot, power_fast, zero)
-    gW = g.read(Mem.W, batch_index=b)
-    assert_bits(gW, W, "weights")
-    assert np.all(np.ascontiguousarray(gW[zero]).view(np.uint32) == 0), "a loser's weight is +0"
-    assert np.all(gW[win] != 0), "a winner keeps its weight"
-    assert_bits(g.read(Mem.SUM_W, batch_index=b), np.array([sw]), "sum of weights")
-    assert_bits(g.read(Mem.MEANS, batch_index=b), means, "means")
-    assert_bits(g.read(Mem.S, batch_index=b), S, "S")
-    gTk = g.read(Mem.TK, batch_index=b)
-    nan = np.isnan(Tk)
-    assert np.array_equal(np.isnan(gTk), nan), ("Tk", gTk, Tk)
-    assert_bits(gTk[~nan], Tk[~nan], "Tk")
-    return win, counts
-
-
 def make_handle(engine, m, nr, fused, weighted, rot, power_fast, invalid, batch=1, unique=True):
-    g = engine.ICP(0, rot, weighted)
-    g.init(m, nr, A, C_, batch=batch)
-    set_modes(engine, g, power_fast, fused)
-    if invalid:
-        g.set_rejection(True, None)
-    if unique:
-        g.set_unique(True)
-    return g
-
-
-def one_step(engine, g, F, M, T):
-    g.write(engine.Memory.F, F); g.write(engine.Memory.M, M)
-    g.buildRBC()
-    g.write(engine.Memory.T, T, block=True)
-    g.step()
+    return icp_checks.make_handle(engine, m, nr, fused, weighted, rot, power_fast, batch, rejection=only_invalid(invalid),
+                                  unique=True if unique else None)
 
 
 @pytest.fixture(scope="module")
 def scenes_A(engine, oracle):
     """name -> (F, M, T, invalid flag, the oracle's (nn_id, rid) at T): a clean pair and a blobs30 holes pair."""
-    side, nr = 128, 256
-    T = _t0()
-    out = {}
-    for name in ("clean", "holes"):
-        F, M = engine.synth_pair(side) if name == "clean" else _holes(engine, side, 0x1C9D5EED)
-        out[name] = (F, M, T, name == "holes", oracle_search(oracle, F, M, T, nr))
-    return out
+    return icp_checks.scenes_A(engine, oracle)
 
 
 # ---- 0. arguments
@@ -189,12 +127,7 @@ def test_one_step_batch3(engine, oracle, fused):
     pairs = [W.pair(engine, 0), _holes(engine, side, W.BASE_SEED + 3, "blobs30"), _holes(engine, side, W.BASE_SEED + 6, "scattered10")]
     T = _t0()
     g = make_handle(engine, side * side, nr, fused, WEIGHTED, POWER, fused, True, batch=B)
-    for b, (F, M) in enumerate(pairs):
-        g.write(engine.Memory.F, F, batch_index=b); g.write(engine.Memory.M, M, batch_index=b)
-    g.buildRBC()
-    for b in range(B):
-        g.write(engine.Memory.T, T, batch_index=b, block=True)
-    g.step()
+    step_batch(engine, g, pairs, T)
     seen = set()
     for b, (F, M) in enumerate(pairs):
         _, counts = check_step(engine, oracle, g, F, M, T, side, fused, WEIGHTED, POWER, fused, True, oracle_search(oracle, F, M, T, nr), b=b)

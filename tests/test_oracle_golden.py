@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+from rotation_cases import planar_case
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 KAT = json.load(open(os.path.join(HERE, "golden", "reference_kat.json")))
 EPS = np.finfo(np.float32).eps
@@ -426,33 +428,13 @@ def test_wall_scene_needs_the_photometric_term(oracle, engine):
     assert not conv and k == W.WALL_MAX_ITERATIONS and err > 3 * res["wall_a2e2"][2] and s < 0.97
 
 
-def _planar_case(seed, tilt=0.3):
-    """S[11], means[8] of an exactly planar pair: points on a tilted plane, the moving set rotated by 7 degrees about the plane's normal
-    (S of rank 2: Horn's N has the eigenvalue pairs +-(s1 + s2), +-(s1 - s2))."""
-    rng = np.random.default_rng(seed)
-    uv = rng.uniform(-1, 1, (400, 2)) * np.array([300.0, 200.0])
-    e1 = np.array([1.0, 0.0, tilt]); e1 /= np.linalg.norm(e1)
-    e2 = np.cross(np.array([0.2, 1.0, 0.1]), e1); e2 /= np.linalg.norm(e2)
-    n = np.cross(e1, e2)
-    f = uv[:, :1] * e1 + uv[:, 1:] * e2
-    th = np.radians(7.0)
-    K = np.array([[0, -n[2], n[1]], [n[2], 0, -n[0]], [-n[1], n[0], 0]])
-    R = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
-    q = f @ R.T                                            # moving = R fixed: the solver must find R^T
-    c = 1e-3
-    S9 = (c * q).T @ (c * f)                               # S_ab = sum m_a f_b
-    S = np.concatenate([S9.ravel(), [((c * f) ** 2).sum(), ((c * q) ** 2).sum()]]).astype(np.float32)
-    means = np.zeros(8, np.float32)
-    return S, means, R.T
-
-
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_squared_power_method_on_a_planar_scene(oracle, seed):
     """The reference's kg_pc8d_wall case (data/README.md:11-16) at the solver: for coplanar points Horn's matrix has eigenvalues in
     +- pairs, which no power method separates (the literal loop spends all its 1000 trips: kernels/icp_kernels.cl:1012-1022); the
     squared start shifts the matrix by its largest absolute row sum once when its first pass does not converge and finds the rotation
     in two passes.  Ordinary scenes never take that branch (every other fixture is unchanged)."""
-    S, means, Rt = _planar_case(seed)
+    S, means, Rt = planar_case(seed)
     Tq, itq = oracle.power_method(S, means, fast=True)
     assert itq == 2                                        # the first pass does not converge (+- pairs), the shifted one does
     assert np.abs(oracle.quat_to_rot(Tq[:4]) - Rt).max() < 1e-6

@@ -18,17 +18,10 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import colored_ref as cref                                      # noqa: E402
 import p2pl_ref as ref                                          # noqa: E402
+from p2pl_ref import unpack                                     # noqa: E402
 
 F32 = np.float32
 UPPER = [(a, c) for a in range(6) for c in range(a, 6)]          # the 21 upper-triangle terms, row-major
-
-
-def unpack(s):
-    """(A 6 x 6, b 6) of a 27-term system."""
-    A = np.zeros((6, 6))
-    for t, (a, c) in enumerate(UPPER):
-        A[a, c] = A[c, a] = s[t]
-    return A, np.asarray(s[21:27], np.float64)
 
 
 def lstsq_of_system(s):
