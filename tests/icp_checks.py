@@ -8,6 +8,7 @@ pytest rewrites `assert` only in the modules it collects, so every assert here c
    names the rows that weigh nothing (`zero`), check_pieces compares the step with the oracle's pieces fed those rows zeroed;
 4. the plane family (point-to-plane, colored, plane-to-plane, symmetric, their robust forms): a `restate` callable wraps the metric's
    float64 restatement, check_last compares the last iteration with it."""
+import collections
 import functools
 
 import numpy as np
@@ -584,11 +585,15 @@ def restate_robust(metric, loss, scale, mu=0.05, kappa=1e3, M=None):
                                                                    read("COLOR_GRAD_F") if metric == COLORED else None, M, kappa)
 
 
-def check_last(engine, g, restate, T0, R0, k0, b=0, steps=1):
+def check_last(engine, g, restate, T0, R0, k0, b=0, steps=1, weights=None):
     """The last iteration of registration b against the restatement fed the device's own outputs and the state (T0, R0, k0) before the
-    `steps` iterations (k0 None: the caller does not know it, k is not compared).  Returns the system."""
+    `steps` iterations (k0 None: the caller does not know it, k is not compared).  weights: a numpy rule's weights, fed in place of
+    the device's own weight column.  Returns the system."""
     Mem = engine.Memory
     PF, PM, ids = g.read(Mem.NN, b), g.read(Mem.QT, b), g.read(Mem.NN_ID, b)["id"]
+    if weights is not None:
+        PF = PF.copy()
+        PF[:, 3] = weights
     system, T, R, Tk, Rk = restate(lambda name: g.read(getattr(Mem, name), b), PF, PM, ids, T0, R0)
     assert_bits(g.read(Mem.PLANE_SYSTEM, b), system, "PLANE_SYSTEM (registration %d)" % b)
     assert_bits(g.read(Mem.T, b), T, "T (registration %d)" % b)
@@ -629,3 +634,249 @@ def plane_handle(engine, side, nr, metric, loss, scale, mu=0.05, kappa=1e3, norm
 
 def check_plane(engine, g, metric, loss, scale, T0, R0, mu=0.05, kappa=1e3, M=None, b=0):
     return check_last(engine, g, restate_robust(metric, loss, scale, mu, kappa, M), T0, R0, None, b)
+
+
+# ---- 5. the route of an iteration: every opt-in pass composed, in icp_route_of's order -------------------------------------------
+#
+# The search's weights (invalid points and the maximum distance rejected), then the pair filter, one-to-one, trimming and — on
+# point-to-point — the robust loss, each fed what the stage before left.  The rules are the single ones above and in the *_ref modules.
+
+RouteOptions = collections.namedtuple("RouteOptions", "weighted invalid max_dist gw min_cos unique keep loss scale")
+RouteOptions.__doc__ = """What composed_rule needs of a handle's options.  Off is: gw None (the boundary rule), min_cos None (the
+normal rule), unique False, keep None (trimming), loss None."""
+RouteResult = collections.namedtuple("RouteResult", "W0 filter unique trim words W_before_loss W")
+RouteResult.__doc__ = """W0: the weights behind the search's rejection;  filter: (at_boundary, incompatible, accepted);  unique:
+(winners, candidates);  trim: the accepted mask — a stage that is off has None there —;  words: name -> what ICP_MEM_<name> reports
+(PAIR_FILTER, UNIQUE, TRIM; None while the stage is off);  W_before_loss: the weights the plane moments read;  W: W'."""
+
+
+def route_options(mask, max_dist, min_cos, side, keep=0.75, loss=robust_ref.CAUCHY, scale=None, weighted=True, invalid=True):
+    """The options of mask (bit 0 the pair filter — the boundary rule at the grid width `side` and the normal rule at min_cos —, bit 1
+    one-to-one, bit 2 trimming, bit 3 the robust loss) over rejection by invalid points and max_dist."""
+    return RouteOptions(weighted, invalid, max_dist, side if mask & 1 else None, min_cos if mask & 1 else None, bool(mask & 2),
+                        keep if mask & 4 else None, loss if mask & 8 else None, (SCALE[loss] if scale is None else scale) if mask & 8 else None)
+
+
+def composed_rule(nn_id, PF, PM, F, M, R0, NF, NM, o, plane=False):
+    """The weights of an iteration with the passes of `o` (a RouteOptions) on, by the single rules in the route's order.  NF / NM: the
+    two normal tables (read only when the normal rule is on).  plane: a plane metric — the loss is the moments' business, W is
+    W_before_loss.  A stage that is off passes its input through and reports no words."""
+    ids = nn_id["id"]
+    W0 = weights_before_trim(nn_id, M, PF, PM, o.weighted, o.invalid, o.max_dist)
+    W, words = W0.copy(), {"PAIR_FILTER": None, "UNIQUE": None, "TRIM": None}
+    flt = unq = trm = None
+    if o.gw or o.min_cos is not None:
+        bnd, inc, acc, words["PAIR_FILTER"] = pair_filter_ref.pair_filter(ids, W, F, o.gw, NF, NM, R0, o.min_cos)
+        flt = (bnd, inc, acc)
+        W = np.where(acc, W, np.float32(0)).astype(np.float32)
+    if o.unique:
+        win, cand, words["UNIQUE"] = unique_ref.unique_rule(ids, PF, PM, W)
+        unq = (win, cand)
+        W = unique_ref.weights_after(W, win, cand)
+    if o.keep is not None:
+        trm, words["TRIM"] = trim_rule(PF, PM, W, o.keep)
+        W = np.where(trm, W, np.float32(0)).astype(np.float32)
+    Wl = W if plane or o.loss is None else robust_ref.p2p_weights(W, PF, PM, o.loss, o.scale)
+    return RouteResult(W0, flt, unq, trm, words, W, Wl)
+
+
+def stage_shares(r, o):
+    """name -> (candidates, removed, kept) of every stage of the result r that is on; for the loss `removed` counts the candidates
+    whose weight is neither their input weight nor zero."""
+    out = {}
+    if r.words["PAIR_FILTER"] is not None:
+        n, b, i, a = (int(x) for x in r.words["PAIR_FILTER"])
+        if o.gw:
+            out["boundary"] = (n, b, n - b)
+        if o.min_cos is not None:
+            out["normal"] = (n, i, n - i)
+        out["filter"] = (n, b + i, a)
+    if r.words["UNIQUE"] is not None:
+        n, w = (int(x) for x in r.words["UNIQUE"])
+        out["unique"] = (n, n - w, w)
+    if r.words["TRIM"] is not None:
+        n, a = int(r.words["TRIM"][1]), int(r.words["TRIM"][3])
+        out["trim"] = (n, n - a, a)
+    if o.loss is not None and r.W is not r.W_before_loss:
+        cand = r.W_before_loss != 0
+        out["loss"] = (int(np.count_nonzero(cand)), int(np.count_nonzero(cand & (r.W != r.W_before_loss) & (r.W != 0))),
+                       int(np.count_nonzero(cand & (r.W != 0))))
+    return out
+
+
+def assert_every_stage_bites(r, o, what):
+    """Every stage that is on removes (the loss: re-weighs) at least 2 % of its own candidates and keeps at least half of them; the
+    search's rejection rejects some pair by either of its rules.  Returns stage_shares."""
+    shares = stage_shares(r, o)
+    for name, (n, removed, kept) in shares.items():
+        assert n > 0 and 50 * removed >= n and 2 * kept >= n, "%s: stage %s has %d candidates, removes %d, keeps %d" % (what, name, n, removed, kept)
+    m = r.W0.shape[0]
+    assert 0 < np.count_nonzero(r.W0 == 0) < m // 2, "%s: the search rejects %d of %d" % (what, np.count_nonzero(r.W0 == 0), m)
+    return shares
+
+
+def pick_min_cos(oracle, F, M, T, nr, width, frac=0.1):
+    """A threshold the normal rule rejects about `frac` of its candidates with, at T: that quantile of the cosines between the grid
+    normals (p2pl_ref.grid_normals, `width` wide) of the reference's pairs that have both normals and no boundary point."""
+    nn_id, _ = oracle_search(oracle, F, M, T, nr)
+    ids = nn_id["id"]
+    NF, NM = p2pl_ref.grid_normals(F, width), p2pl_ref.grid_normals(M, width)
+    cos = pair_filter_ref.cosines(NF[ids], NM, oracle.quat_to_rot(T[:4]))
+    ok = np.isfinite(cos) & ~pair_filter_ref.boundary_mask(F, width)[ids] & ~(M[:, :3] == 0).all(axis=1)
+    return float(np.float32(np.quantile(cos[ok], frac)))
+
+
+def pick_scale(oracle, F, M, T, nr, max_dist, frac=0.9):
+    """A loss scale the residuals of about `frac` of the pairs that survive the search's rejection (at T) stay below."""
+    nn_id, _ = oracle_search(oracle, F, M, T, nr)
+    PF, PM = F[nn_id["id"]], oracle.transform_q(M, T)
+    geo = geo_of(PF, PM)[~rejected_set(M, PF, PM, True, max_dist)]
+    return float(np.float32(np.sqrt(np.quantile(geo.astype(np.float64), frac))))
+
+
+# The scenes of the composed checks.  The benchmark pair at _t0 () matches far fewer than half of its queries one to one (its frames lie
+# 25 mm and more apart, and the 8-d metric follows the colour: 29 % winners at side 128, 27 % at side 150), so one-to-one could not
+# keep half of its candidates there.  These pairs are the same synthetic frames moved by about what _t0 () undoes, with 10 % of either
+# frame punched out in blobs of its own: at _t0 () most queries have a fixed point to themselves, some share one, and every stage has
+# pairs to remove and to keep.  name -> (side, |R|, seed, rotation in degrees, translation in mm).
+ROUTE_SCENES = {"30": (30, 4, 0x20C7E, 1.0, (4.0, -3.0, 2.0)), "150": (150, 4, 0x20C7F, 1.0, (4.0, -3.0, 2.0)),
+                "A": (128, 256, 0x20C80, 1.0, (4.0, -3.0, 2.0)), "batch0": (128, 64, 0x20C81, 1.0, (4.0, -3.0, 2.0)),
+                "batch1": (128, 64, 0x20C82, 1.2, (6.0, -2.0, 3.0)), "batch2": (128, 64, 0x20C83, 0.8, (3.0, -4.0, 1.0))}
+ROUTE_BATCH = ("batch0", "batch1", "batch2")                     # one handle, one set of options: batch0's, proven on each of the three
+ROUTE_KEEP = 0.75
+RouteScene = collections.namedtuple("RouteScene", "side nr F M T want R0 PF PM NF NM max_dist min_cos scale")
+
+
+@functools.lru_cache(maxsize=None)
+def route_scene(name):
+    """The scene `name` of ROUTE_SCENES, read-only, from the engine's host-side generators and the oracle alone: the pair, T = _t0 (),
+    the oracle's (nn_id, rid) and R at T, PF = F[ids], PM = the transformed moving set, the grid normals of both frames, and the
+    options chosen on the reference's pairs: max_dist rejects 12 % of the valid pairs (pick_max_dist), min_cos 10 % of the normal
+    rule's candidates (pick_min_cos); the scales are SCALE's but Tukey's, which 90 % of the surviving residuals stay below
+    (pick_scale: SCALE's 30 mm is beyond most residuals of the 30 x 30 grid).  keep is ROUTE_KEEP."""
+    import icp_amd as engine
+    from oracle import oracle
+    side, nr, seed, rot_deg, t = ROUTE_SCENES[name]
+    F, M = engine.synth_pair(side, seed=seed, rot_deg=rot_deg, t=t)
+    F = engine.punch_holes(F, side, side, engine.HOLES_CONTIGUOUS, 0.10, True, seed=seed + 101)
+    M = engine.punch_holes(M, side, side, engine.HOLES_CONTIGUOUS, 0.10, True, seed=seed + 202)
+    T = _t0()
+    want = oracle_search(oracle, F, M, T, nr)
+    if name in ROUTE_BATCH[1:]:
+        max_dist, min_cos, scale = route_scene(ROUTE_BATCH[0])[-3:]
+    else:
+        max_dist, min_cos = float(np.float32(pick_max_dist(oracle, F, M, T, nr))), pick_min_cos(oracle, F, M, T, nr, side)
+        scale = dict(SCALE)
+        scale[robust_ref.TUKEY] = pick_scale(oracle, F, M, T, nr, max_dist)
+    s = RouteScene(side, nr, F, M, T, want, oracle.quat_to_rot(T[:4]).ravel(), np.ascontiguousarray(F[want[0]["id"]]),
+                   oracle.transform_q(M, T), p2pl_ref.grid_normals(F, side), p2pl_ref.grid_normals(M, side), max_dist, min_cos, scale)
+    for a in s[2:5] + want + s[6:11]:
+        a.flags.writeable = False
+    return s
+
+
+def route_scene_options(s, mask, loss=robust_ref.CAUCHY):
+    return route_options(mask, s.max_dist, s.min_cos, s.side, ROUTE_KEEP, loss, s.scale[loss])
+
+
+@functools.lru_cache(maxsize=None)
+def route_proof(name, mask, loss=robust_ref.CAUCHY, plane=False):
+    """(RouteResult, stage shares) of composed_rule on the scene's reference pairs at _t0 (), every stage proven to bite."""
+    s = route_scene(name)
+    o = route_scene_options(s, mask, loss)
+    r = composed_rule(s.want[0], s.PF, s.PM, s.F, s.M, s.R0, s.NF, s.NM, o, plane)
+    return r, assert_every_stage_bites(r, o, "scene %s, mask %d, loss %d" % (name, mask, loss))
+
+
+ROUTE_WORDS = {"PAIR_FILTER": 4, "UNIQUE": 2, "TRIM": 4}
+ROUTE_METRICS = ("p2pl", "colored", "gicp", "sym")
+GICP_EPS = 1e-3
+
+
+def route_handle(engine, side, nr, o, metric="p2p", fused=None, batch=1, it=40):
+    """A handle with the options o on.  metric "p2p": explicit modes, fused + the squared power start or reference order + the
+    literal one; a plane metric of ROUTE_METRICS (mu = 0.05, kappa = 1000, epsilon = GICP_EPS): the handle's default modes."""
+    loss = (o.loss, o.scale) if o.loss is not None else None
+    if metric == "p2p":
+        return make_handle(engine, side * side, nr, fused, o.weighted, POWER, fused, batch, it, rejection=(o.invalid, o.max_dist),
+                           boundary=o.gw, normal_rejection=(side, o.min_cos) if o.min_cos is not None else None,
+                           unique=True if o.unique else None, trimming=o.keep, robust_loss=loss)
+    g = make_plane(engine, side, nr, WEIGHTED if o.weighted else REGULAR, batch=batch, max_iterations=it,
+                   metric=COLORED if metric == "colored" else P2PL, plane_to_plane=GICP_EPS if metric == "gicp" else None,
+                   symmetric=True if metric == "sym" else None, trimming=o.keep, robust_loss=loss)
+    g.set_rejection(o.invalid, o.max_dist)
+    if o.gw:
+        g.set_boundary_rejection(o.gw)
+    if o.min_cos is not None:
+        g.set_normal_rejection(o.min_cos)
+    if o.unique:
+        g.set_unique(True)
+    return g
+
+
+def route_restate(metric, o, M):
+    """The plane metric's restatement, with the loss of o when it has one."""
+    if metric == "gicp":
+        return restate_gicp(0.05, GICP_EPS, o.loss, o.scale)
+    if metric == "sym":
+        return restate_symmetric(0.05, o.loss, o.scale)
+    if o.loss is not None:
+        return restate_robust(COLORED if metric == "colored" else P2PL, o.loss, o.scale, M=M)
+    return restate_colored(0.05, 1000.0) if metric == "colored" else restate_p2pl(0.05)
+
+
+def _route_rule(engine, g, F, M, NF, NM, R0, want, o, plane, b, proof, what):
+    """The search against the oracle's, the normal tables against the grid normals, then composed_rule on the engine's NN / QT: the
+    three result words against the rule's (zeros while a stage is off) and against `proof`'s (a RouteResult from the reference's pairs:
+    the first step's), every stage biting by the proof's conditions; without a proof every stage still removes some pair and keeps half."""
+    Mem = engine.Memory
+    check_search(engine, g, want, b)
+    if plane or o.min_cos is not None:
+        assert_bits(g.read(Mem.NORMALS_F, b), NF, "NORMALS_F against the grid normals (%s)" % what)
+    if o.min_cos is not None:
+        assert_bits(g.read(Mem.NORMALS_M, b), NM, "NORMALS_M against the grid normals (%s)" % what)
+    PF, PM = g.read(Mem.NN, b), g.read(Mem.QT, b)
+    r = composed_rule(want[0], PF, PM, F, M, R0, NF, NM, o, plane)
+    for name, n in ROUTE_WORDS.items():
+        words = r.words[name] if r.words[name] is not None else np.zeros(n, np.uint32)
+        got = assert_words(engine, g, name, words, b)
+        if proof is not None:
+            proven = proof.words[name] if proof.words[name] is not None else np.zeros(n, np.uint32)
+            assert np.array_equal(got, proven), "%s: ICP_MEM_%s %r, from the reference's pairs %r" % (what, name, got, proven)
+    if proof is not None:                                         # (the proven step: the words just compared are the proof's)
+        shares = assert_every_stage_bites(r, o, what)
+    else:                                                         # (a later step, at a T no proof covers: the passes still have work)
+        shares = stage_shares(r, o)
+        for name in ("filter", "unique", "trim", "loss"):
+            n, removed, kept = shares.get(name, (1, 1, 1))
+            assert removed > 0 and 2 * kept >= n, "%s: stage %s has %d candidates, removes %d, keeps %d" % (what, name, n, removed, kept)
+    print(what, "shares", shares)
+    return r, PF, PM
+
+
+def check_route_step(engine, oracle, g, F, M, NF, NM, T, R0, want, o, fused, b=0, proof=None, what=""):
+    """A point-to-point step from (T, R0), already taken, with the passes of o on: _route_rule, then ICP_MEM_W against W', sum W,
+    means, S and Tk by check_pieces, "an accepted pair keeps its weight" (under the loss: the loss's weight of its search weight) and
+    the NN output's weights.  Returns the RouteResult."""
+    Mem = engine.Memory
+    r, PF, PM = _route_rule(engine, g, F, M, NF, NM, R0, want, o, False, b, proof, what)
+    side = int(round(np.sqrt(F.shape[0])))
+    check_pieces(engine, oracle, g, F, M, T, side, fused, o.weighted, POWER, fused, r.W == 0, want, b, r.W if o.loss is not None else None)
+    gW = g.read(Mem.W, b)
+    assert_bits(gW, r.W, "W' (%s)" % what)
+    acc = r.W_before_loss != 0
+    alone = r.W0 if o.loss is None else robust_ref.p2p_weights(r.W0, PF, PM, o.loss, o.scale)
+    assert_bits(gW[acc], alone[acc], "an accepted pair keeps its weight (%s)" % what)
+    assert_bits(PF[:, 3], gW, "the NN output's weights (%s)" % what)
+    return r
+
+
+def check_route_plane_step(engine, g, F, M, NF, NM, T0, R0, k0, want, o, restate, b=0, proof=None, what=""):
+    """A plane metric's step from (T0, R0, k0), already taken: _route_rule, the NN output's weights and ICP_MEM_W against the composed
+    weights before the loss, then check_last with the restatement fed the rule's weights.  Returns the RouteResult."""
+    Mem = engine.Memory
+    r, PF, _ = _route_rule(engine, g, F, M, NF, NM, R0, want, o, True, b, proof, what)
+    assert_bits(PF[:, 3], r.W_before_loss, "the NN output's weights (%s)" % what)
+    assert_bits(g.read(Mem.W, b), r.W_before_loss, "ICP_MEM_W (%s)" % what)
+    check_last(engine, g, restate, T0, R0, k0, b, weights=r.W_before_loss)
+    return r
