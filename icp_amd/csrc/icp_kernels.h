@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "icp_device.h"
+#include "icp_search_select.h"
 
 // fused finalize: beyond this many 128-block groups (|F| > 16384) the first level of the moment tree gets a kernel of its own
 // (k_moment_level1: the block moments come from all over the chip; one CU fetching 147 KB of them at |F| = 65536 costs more than

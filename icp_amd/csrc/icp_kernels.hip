@@ -498,11 +498,8 @@ bool icp_dense (const icp_params &p)
     return (size_t) p.batch * p.nb > 512u || p.nr >= ICP_S1_REJECT_MIN_NR;
 }
 
-// LDS tile of the dense search variant: 256 representatives (21 KB of LDS, 8 waves per SIMD) where a tile holds whole rows of
-// 4 x 4 pruning groups (representative grid at most 64 wide: |R| <= 4096), else 1024.
-// (Several 256-tiles with a block vote per tile measured slower than the 1024-tile — B 16.6 -> 17.5 us, C 417 -> 520 us —: the
-// MASKED form of k_search decides a block's tile set in one pre-pass instead.)
-uint32_t icp_dense_tile (const icp_params &p) { return (p.nr <= 256u || p.nrx <= 64u) ? 256u : 1024u; }
+// LDS tile of the dense search variant: 256 or 1024 representatives (the rule and its reasons: icp_search_select.h)
+uint32_t icp_dense_tile (const icp_params &p) { return icp_dense_tile_rule (p.nr, p.nrx); }
 // Stage 2 with lanes = candidates pays where the lists are long (its 64-lane reduction per query is a fixed cost; lists of 64 are
 // one trip either way): from ICP_S2_WAVE_MIN candidates per list on average.  ICP_AMD_S2WAVE=0/1 forces it (diagnostics).
 #ifndef ICP_S2_WAVE_MIN
@@ -532,7 +529,7 @@ bool icp_build_lists (const icp_params &p) { return !icp_dense (p) && p.nr < 102
 void icp_launch_owner_search (const icp_params &p, hipStream_t s)
 {
     if (icp_dense (p)) { icp_launch_owner_search_dense (p, s); return; }                     // (icp_search_dense.hip)
-    hipLaunchKernelGGL ((k_search<true, false, 2, 16, true>), dim3 (p.nb, p.batch), dim3 (1024), 0, s, p.F, p.R, p.st, (const double *) p.mom, p.m, p.nr, p.side, icp_tpr_magic (p.side), p.nb, 0u, p);
+    hipLaunchKernelGGL (ks_owner<KS_OWNER_LATENCY>, dim3 (p.nb, p.batch), dim3 (1024), 0, s, KS_OWNER_ARGS);
 }
 
 void icp_launch_search (const icp_params &p, hipStream_t s)

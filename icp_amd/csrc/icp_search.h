@@ -1,14 +1,15 @@
 // icp_search.h — the search kernel template and the device helpers it shares with the finalize kernels (trees over the block partials,
-// the finalize of a block: moments -> T).  Included by the two translation units that instantiate k_search:
+// the finalize of a block: moments -> T).  Included by the three translation units that instantiate k_search:
 //   icp_kernels.hip        the latency variants (one 1024-thread block per CU: a single small registration; chained form; the owner
 //                          search with per-block lists) + every other per-iteration kernel
 //   icp_search_dense.hip   the dense variants (512-thread blocks, several per CU, exact stage-1 pruning, 256- / 1024-representative tiles,
 //                          both list-scan forms) + the dense owner search
-// so that the two families compile side by side and a change to one family's launch code does not rebuild the other.
+//   icp_search_rej.hip     every variant with correspondence rejection on (REJ = true)
+// so that the families compile side by side and a change to one family's launch code does not rebuild the others.
 //
-// Map of this file (round 5: k_search split into its phases; what a phase needs from the others is in its parameter list):
-//   helpers                      sums, group minima (DPP), KS_CAND / KS_CAND_IF (one list candidate against the lane's query), ks_tile_of_block,
-//                                fused_query_index, cell_rep_of
+// Map of this file (what a phase needs from the others is in its parameter list):
+//   helpers                      sums, group minima (DPP), KS_CAND / KS_CAND_IF (one list candidate against the lane's query), KS_PAIR (one pair of
+//                                representatives in LDS against it: the unpruned stage-1 scan), ks_tile_of_block, fused_query_index, cell_rep_of
 //   ks_seed_against_invalid, ks_origin_list, ks_origin_section    a frame's invalid points (representatives at the origin): the seed of a
 //                                query whose cell's representative is of the other kind; their list, scanned behind the tiles
 //   fused_moment_* / fused_finalize_block / fin_result_to_state      the finalize of a block: 18 double moments -> T (shared with icp_kernels.hip)
@@ -16,12 +17,20 @@
 //   ks_stage2_lanes<LPQ>         stage 2, a query's lanes scan its list; exact chunk-box pruning beyond the first 128 positions of long lists
 //   ks_epilogue<...>             hand-off to the finishing wave, winner record, weights, per-query outputs, block moments / weight tree
 //   ks_owner_lists_tail          RBC construct of the latency-bound sizes: what the owner search leaves for k_place_lists
+//   ks_rep_to_lds, ks_box_bound  a representative -> the pair-interleaved LDS tile (every staging site, the NaN pad slot); the point-to-box bound
 //   ks_coarse_pass / ks_fine_pass  stage 1 over one LDS tile of representatives: group-box tests, then the groups some query of the wave needs
 //                                (free functions with plain scalar parameters: with the query passed as a struct the 64-register variants spilled)
+//   ks_winner_list               the winner's list header (offset, size): from LDS where its tile's headers are staged, else from memory
 //   k_search<...>                the kernel: PROLOGUE (every independent load issued before the first wait; chained form: the previous
 //                                iteration's finalize), the STAGE 1 drivers (MASKED: tile set decided once; else a tile loop; the origin list),
-//                                then the calls above
-//   host side                    icp_tpr_magic, KS_FLAGS, KS_ARGS
+//                                then the calls above.  (The drivers, the seed bound and the query hand-in read stay in its body: as functions
+//                                or lambdas each compiled to other instructions than before — tools/diag/isa_diff.py.)
+//   host side                    icp_tpr_magic, KS_FLAGS, KS_*ARGS, the named instantiations (ks_latency, ks_dense, ks_chained, ks_owner) and the
+//                                launchers over them; which dense kernel runs: icp_search_select.h
+// Four compile-time A/B switches decided long ago are gone, folded to the value every build had (their names: DESIGN.md §5): the MASKED
+// home tile's mode -> 1, staged in the prologue (profiles/r03_home_tile_ab.txt); the origin list -> on (off: wrong results on frames with
+// invalid points; profiles/r05_holes_*.txt); the stage-1 seed -> on (PRUNE is MINW == 4; docs/HISTORY.md); the XCD map -> on
+// (ks_tile_of_block's bands; docs/HISTORY.md: 9.61 -> 9.42 us at A).
 #pragma once
 #include "icp_kernels.h"
 
@@ -52,14 +61,8 @@ static __device__ __forceinline__ uint32_t ks_hole_bit (float4 mg) { return (mg.
 #ifndef ICP_S2_UNCOND
 #define ICP_S2_UNCOND 128u           // stage 2 (a query's lanes scan its list): positions of a list scanned unconditionally; beyond them chunk boxes first
 #endif
-#ifndef ICP_S1_ORIGIN_LIST
-#define ICP_S1_ORIGIN_LIST 1         // dense variants: the representatives at the origin are scanned as a list of their own (0: A/B builds without it — wrong results on frames with invalid points)
-#endif
 #ifndef ICP_OL_STAGED_MIN
 #define ICP_OL_STAGED_MIN 32u         // the list of the representatives at the origin: up to this length (one trip of a query's lanes) read per wave, not staged per block
-#endif
-#ifndef ICP_S1_SEED
-#define ICP_S1_SEED 1                // stage 1: prune with the distance to the previous search's nearest representative
 #endif
 #ifndef ICP_S1_REJECT_MIN_NR
 #define ICP_S1_REJECT_MIN_NR 1024u   // stage 1: exact early rejection from this many representatives on
@@ -85,13 +88,11 @@ static __device__ __forceinline__ const icp_params *ks_params_from_kernarg ()
     asm volatile ("" : "+s"(a_));                // (opaque: the scalar loads through it stay where the caller is, they do not join the ones at the kernel's top)
     return (const icp_params *) (const icp_params __attribute__ ((address_space (4))) *) a_;
 }
-// MASKED search, home tile (see k_search): 1 = staged into LDS in the prologue (seed from LDS); 2 = loads issued in the prologue, LDS
-// write after the tile masks (seed from global: the tile's round trip overlaps the seed's); 3 = no home tile (only its list offsets).
-// Same box, alternating, us per iteration of fresh 40-iteration runs at |F| = 65536 / 10-iteration runs at 2^20 (profiles/
-// r03_home_tile_ab.txt): without the home tile 18.62 / 263.8, mode 1 17.90 / 258.8, mode 2 18.18 / 258.7, mode 3 18.79 / 261.6.
-#ifndef ICP_HOME_MODE
-#define ICP_HOME_MODE 1
-#endif
+// MASKED search, home tile (see k_search): staged into LDS in the prologue, the seed read from LDS.  Measured against it and not kept (the
+// former modes 2 and 3 of a compile-time switch): the loads issued in the prologue and the LDS write after the tile masks (seed from
+// global: the tile's round trip overlaps the seed's); no home tile, only its list offsets.  Same box, alternating, us per iteration of
+// fresh 40-iteration runs at |F| = 65536 / 10-iteration runs at 2^20 (profiles/r03_home_tile_ab.txt): without the home tile
+// 18.62 / 263.8, staged in the prologue 17.90 / 258.8, written after the masks 18.18 / 258.7, list offsets only 18.79 / 261.6.
 
 #ifdef ICP_DBG_STAMPS
 #define KS_STAMP(k)                                                                                       \
@@ -308,6 +309,22 @@ static __device__ __forceinline__ void ks_origin_section (float4 *s_pair, uint32
         if (d_ < best2 && (LIVE)) { best2 = d_; bj = (J); }                                           \
     }
 
+// pair P of a tile in LDS (3 float4 from s_pair[P3]; representatives R0, R0 + 1) against the lane's query (float2v pairs vqx .. vqb, va = (a, a)),
+// both halves in packed instructions: the unpruned stage-1 scan.  A lane's pairs ascend and an update needs a strict '<', so each lane keeps
+// its lowest index among equal distances.  (A macro like KS_CAND: as a function or a lambda the loops around it compiled to other instructions.)
+#define KS_PAIR(P3, R0)                                                                                                                  \
+    {                                                                                                                                    \
+        float4 A = s_pair[P3], B = s_pair[(P3) + 1], C = s_pair[(P3) + 2];                                                                \
+        float2v x = { A.x, A.y }, y = { A.z, A.w }, z = { B.x, B.y }, r = { B.z, B.w }, g = { C.x, C.y }, bb = { C.z, C.w };              \
+        float2v dx = vqx - x, dy = vqy - y, dz = vqz - z, dr = vqr - r, dg = vqg - g, db = vqb - bb;                                      \
+        float2v geo = __builtin_elementwise_fma (dz, dz, __builtin_elementwise_fma (dy, dy, dx * dx));                                    \
+        float2v pho = __builtin_elementwise_fma (db, db, __builtin_elementwise_fma (dg, dg, dr * dr));                                    \
+        float2v d = __builtin_elementwise_fma (va, pho, geo);                                                                             \
+        const uint32_t r0 = (R0);                                                                                                         \
+        if (d.x < best) { best = d.x; bid = r0; }                                                                                         \
+        if (d.y < best) { best = d.y; bid = r0 + 1u; }                                                                                    \
+    }
+
 #define ICP_NMOM 18
 
 #ifdef ICP_DBG_STAMPS
@@ -331,11 +348,7 @@ static __device__ __forceinline__ void ks_origin_section (float4 *s_pair, uint32
 // (Speed only: nothing depends on the placement actually being round-robin.)
 static __device__ __forceinline__ uint32_t ks_tile_of_block (uint32_t bx, uint32_t nbx)
 {
-#ifdef ICP_NO_XCD_MAP
-    return bx;
-#else
     return (nbx & 7u) == 0u ? (bx & 7u) * (nbx >> 3) + (bx >> 3) : bx;
-#endif
 }
 
 // fused mode: query index of local element e of block b (CPU twin: orc_fused_query).  8 x 8 tiles of the
@@ -925,7 +938,7 @@ static __device__ __forceinline__ void ks_epilogue (const icp_params &p, float4 
     if (slice == 0u) {
         const float4 qa = s_qa[lane]; const uint4 qb = s_qb[lane];
         // (dense variants: the queries were handed over with a frame's invalid ones last — s_slot: the place in the tile of the query at this position)
-        const uint32_t eo = (PRUNE && ICP_S1_ORIGIN_LIST) ? s_slot[lane] : lane;
+        const uint32_t eo = PRUNE ? s_slot[lane] : lane;
         const bool v = (qb.z & 1u) != 0u, empty = (qb.z & 2u) != 0u;
         // the search ran on geo + a pho (a positive common factor changes neither the argmin nor the ties, and the pruning
         // bound d >= geo stays as it is); the distance reported and fed to the weights carries the metric's absolute scale
@@ -1068,6 +1081,24 @@ static __device__ __forceinline__ void ks_owner_lists_tail (const icp_params &p,
 // stage 1 (nearest representative) — the two passes over one tile of representatives in LDS; their drivers (which tiles, in which order,
 // behind which barriers: MASKED / the tile loop) are in k_search.
 // ------------------------------------------------------------------------------------------
+// one representative (g = [x y z .], c = [r g b .]) -> slot k of a pair-interleaved tile buffer (tile = its first float): pair k >> 1 =
+// 3 float4 [x0 x1 y0 y1] [z0 z1 r0 r1] [g0 g1 b0 b1], half k & 1
+static __device__ __forceinline__ void ks_rep_to_lds (float *tile, uint32_t k, float4 g, float4 c)
+{
+    float *dst = tile + (k >> 1) * 12u + (k & 1u);
+    dst[0] = g.x; dst[2] = g.y; dst[4] = g.z; dst[6] = c.x; dst[8] = c.y; dst[10] = c.z;
+}
+
+// geometric lower bound of a query's distance to every point inside the box (lo, hi): the metric's own operations on the per-axis
+// distances to the box; every operation is monotone under round-to-nearest, so bound <= geo <= d for every member (a > 0)
+static __device__ __forceinline__ float ks_box_bound (float4 lo, float4 hi, float qx, float qy, float qz)
+{
+    const float ex = fmaxf (fmaxf (lo.x - qx, qx - hi.x), 0.f);
+    const float ey = fmaxf (fmaxf (lo.y - qy, qy - hi.y), 0.f);
+    const float ez = fmaxf (fmaxf (lo.z - qz, qz - hi.z), 0.f);
+    return __builtin_fmaf (ez, ez, __builtin_fmaf (ey, ey, ex * ex));
+}
+
 // coarse pass of the pruning over the groups of the tile in LDS (box[box0 ..]: the tile's (lo, hi) pairs): bit t of the result = this lane's
 // t-th group (ss, ss + LPQ, ..) may hold a representative nearer than `lim`.  The lower bound applies the metric's own operations to the
 // per-axis distances to the group's bounding box; every operation is monotone under round-to-nearest, so bound <= geo <= d for every
@@ -1078,12 +1109,7 @@ static __device__ __forceinline__ uint32_t ks_coarse_pass (const float4 *s_box, 
     const uint32_t ngt = (((tn_ + 1u) >> 1) + KS_SPLIT - 1u) / KS_SPLIT;
     uint32_t cm = 0u;
     auto test = [&] (uint32_t t, uint32_t g) {
-        const float4 lo = s_box[box0 + 2 * g], hi = s_box[box0 + 2 * g + 1];
-        const float ex = fmaxf (fmaxf (lo.x - qx, qx - hi.x), 0.f);
-        const float ey = fmaxf (fmaxf (lo.y - qy, qy - hi.y), 0.f);
-        const float ez = fmaxf (fmaxf (lo.z - qz, qz - hi.z), 0.f);
-        const float bound = __builtin_fmaf (ez, ez, __builtin_fmaf (ey, ey, ex * ex));
-        if (bound < lim_) cm |= 1u << t;
+        if (ks_box_bound (s_box[box0 + 2 * g], s_box[box0 + 2 * g + 1], qx, qy, qz) < lim_) cm |= 1u << t;
     };
     if constexpr (TILE == 256) {                     // at most two trips per lane: not unrolled (the 64-register budget of this variant)
 #pragma unroll 1
@@ -1134,6 +1160,20 @@ static __device__ __forceinline__ void ks_fine_pass (const float4 *s_pair, uint3
             }
         }
     }
+}
+
+// list offset / size of the winner rstar.  From LDS where its tile's headers are staged — one tile (always the case for the MINW == 2
+// variants, see icp_launch_search); MASKED: the home tile's (buffer 1 is never overwritten: a winner there, the usual case, costs no
+// dependent global load) —, else from global memory.  (The opaque use keeps the compiler from merging the two sources into flat loads.)
+template <int MINW, bool MASKED, uint32_t KT>
+static __device__ __forceinline__ uint2 ks_winner_list (const uint2 *s_on, const uint32_t *gO, const uint32_t *gN, uint32_t rstar, uint32_t nr, uint32_t ht)
+{
+    uint32_t o, n;
+    if (MINW == 2 || (MASKED ? rstar / KT == ht : nr <= KT)) {
+        const uint2 on = s_on[rstar - (MASKED ? ht * KT : 0u)]; o = on.x; n = on.y;
+        if constexpr (MINW != 2) asm volatile ("" : "+v"(o), "+v"(n));
+    } else { o = gO[rstar]; n = gN[rstar]; }
+    return make_uint2 (o, n);
 }
 
 // CHAIN (fused mode only): launch j reads state slot j&1 and the moments buffer j&1, turns the previous
@@ -1204,7 +1244,7 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
     __shared__ uint4 s_qb[64];                       //   (winner position or representative, representative, flags, query index)
     // dense variants: the query wave hands a frame's invalid queries over BEHIND the valid ones (see there); the finishing wave puts a query's
     // moment products back at the slot of its place in the block's tile: the sums keep their order
-    __shared__ uint32_t s_slot[(ICP_S1_SEED && ICP_S1_ORIGIN_LIST && MINW == 4) ? 64 : 1];      // the tile slot of the query handed over at position p
+    __shared__ uint32_t s_slot[MINW == 4 ? 64 : 1];      // the tile slot of the query handed over at position p
     __shared__ double s_mom[FUSED ? ICP_NMOM : 1][64];
     __shared__ icp_fin_result s_fin;
     __shared__ double s_l1[CHAIN ? ICP_NMOM : 1][CHAIN ? 32 : 1];
@@ -1291,7 +1331,7 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
         const uint32_t i0 = (uint32_t) __builtin_amdgcn_readfirstlane ((int) min (FUSED ? fused_query_index (m, side, tpr_magic, tile_id, 0u) : (blockIdx.x >> 1) * 128u + (blockIdx.x & 1u), m - 1u));
         const uint32_t cell = p.side_magic ? cell_rep_of (p, i0) : 0u;
         ht = min (cell, nr - 1u) / KT; tnH = min (KT, nr - ht * KT);
-        if (ICP_HOME_MODE != 3 && tid < tnH) { rg[0] = R4[2 * (size_t) (ht * KT + tid)]; rc[0] = R4[2 * (size_t) (ht * KT + tid) + 1]; }
+        if (tid < tnH) { rg[0] = R4[2 * (size_t) (ht * KT + tid)]; rc[0] = R4[2 * (size_t) (ht * KT + tid) + 1]; }
     }
     // (list offsets / sizes: their base pointers come with the second batch of kernel arguments)
     const uint32_t *gO = p.O + (size_t) b * nr, *gN = p.N + (size_t) b * nr;
@@ -1310,7 +1350,7 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
     // Pruning pays where stage 1 is throughput-bound: the dense variant (MINW == 4: several blocks per CU, or a
     // large representative set — see icp_launch_search); a single small registration is latency-bound and keeps
     // the branch-free loop (compile-time: the pruning code costs 0.25 us there even when it is switched off).
-    constexpr bool PRUNE = ICP_S1_SEED && MINW == 4;
+    constexpr bool PRUNE = MINW == 4;
     const bool prune = PRUNE && p.a > 0.f;
     const uint32_t gt_lg1 = p.gtile;                 // 0: strip groups; 1 + log2 (nrx / 4): 4 x 4 tile groups (k_rep_boxes)
     // A registration's FIRST search (k == 0: ICP::buildRBC / a reset came before it) has no previous search of its own: whatever
@@ -1320,7 +1360,7 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
     // check_flags bit 5 (ICP_AMD_WARM_SEED=1, diagnostics): always the previous search's answer.
     uint32_t seed = 0u, seed_cell = 0xFFFFFFFFu;
     if (qwave && prune && p.side_magic) seed_cell = cell_rep_of (p, ic);     // the representative sampled from the point's own cell
-    if constexpr (OWNER) seed = (seed_cell == 0xFFFFFFFFu ? 0u : seed_cell) | ((PRUNE && ICP_S1_ORIGIN_LIST) ? 0x40000000u : 0u);      // (bit 30: a seed from the grid cell — ks_seed_against_invalid)
+    if constexpr (OWNER) seed = (seed_cell == 0xFFFFFFFFu ? 0u : seed_cell) | (PRUNE ? 0x40000000u : 0u);      // (bit 30: a seed from the grid cell — ks_seed_against_invalid)
     else if (qwave && prune) {
         seed = p.rid[(size_t) b * m + ic];           // (selected against seed_cell below, once the state has arrived)
         if ((check_flags & 32u) || seed_cell == 0xFFFFFFFFu) seed_cell = 0xFFFFFFFFu;
@@ -1331,12 +1371,12 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
     float4 boxv = make_float4 (0.f, 0.f, 0.f, 0.f);
     if (!MASKED && prune && tid < nbox0) boxv = GBt[tid];
     const uint32_t nboxH = 2u * ((tnH + 2u * KS_SPLIT - 1u) / (2u * KS_SPLIT));
-    if (MASKED && ICP_HOME_MODE != 3 && prune && tid < nboxH) boxv = GBt[2u * (ht * KT / (2u * KS_SPLIT)) + tid];
+    if (MASKED && prune && tid < nboxH) boxv = GBt[2u * (ht * KT / (2u * KS_SPLIT)) + tid];
     float T[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) T[k] = state_lane_f (sv, ICP_ST_DW (T) + k);
     if constexpr (PRUNE && !OWNER) {
-        if (seed_cell != 0xFFFFFFFFu && __builtin_amdgcn_readlane ((int) sv, (int) ICP_ST_DW (k)) == 0) seed = seed_cell | (ICP_S1_ORIGIN_LIST ? 0x40000000u : 0u);    // first search of a registration (bit 30: a seed from the grid cell)
+        if (seed_cell != 0xFFFFFFFFu && __builtin_amdgcn_readlane ((int) sv, (int) ICP_ST_DW (k)) == 0) seed = seed_cell | 0x40000000u;    // first search of a registration (bit 30: a seed from the grid cell)
     }
     icp_reg_state *sout = CHAIN ? p.cst + (size_t) b * 2 + (p.slot ^ 1u) : st;
     if constexpr (!OWNER && !CHAIN) {
@@ -1374,25 +1414,21 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
     for (int u = 0; u < 2; ++u) {
         uint32_t k = tid + (uint32_t) u * 64u * KS_SPLIT;
         if (!MASKED && k < tn0) {
-            float *dst = s_pairf + (k >> 1) * 12u + (k & 1u);
-            dst[0] = rg[u].x; dst[2] = rg[u].y; dst[4] = rg[u].z; dst[6] = rc[u].x; dst[8] = rc[u].y; dst[10] = rc[u].z;
+            ks_rep_to_lds (s_pairf, k, rg[u], rc[u]);
             if constexpr (!OWNER && !MASKED) s_on[k] = ron[u];
         }
     }
     if (!MASKED && prune && tid < nbox0) s_box[tid] = boxv;
     auto home_to_lds = [&] () {                      // the home tile -> buffer 1
-        if (tid < tnH) {
-            float *dst = s_pairf + PB * 4u + (tid >> 1) * 12u + (tid & 1u);
-            dst[0] = rg[0].x; dst[2] = rg[0].y; dst[4] = rg[0].z; dst[6] = rc[0].x; dst[8] = rc[0].y; dst[10] = rc[0].z;
-        }
+        if (tid < tnH) ks_rep_to_lds (s_pairf + PB * 4u, tid, rg[0], rc[0]);
         if (prune && tid < nboxH) s_box[BB + tid] = boxv;
     };
     if constexpr (MASKED) {
-        if (ICP_HOME_MODE == 1) home_to_lds ();
+        home_to_lds ();
         if constexpr (!OWNER) { if (tid < tnH) s_on[tid] = ron[0]; }
     }
     if (MASKED && tid == 0) s_tmask = 0u;
-    if (PRUNE && ICP_S1_ORIGIN_LIST && tid == 0) s_ovote = 0u;
+    if (PRUNE && tid == 0) s_ovote = 0u;
     if constexpr (MINW == 4 && !SINGLE) {            // the boxes of all tiles: a tile is tested before it is staged (stage 1 below)
         if (prune && nr > KT && tid < 2u * p.n1k) s_tbox[tid] = p.GB[(size_t) b * 2 * (p.n16 + p.n1k) + 2u * p.n16 + tid];
     }
@@ -1421,7 +1457,7 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
     if (qwave && !handed) {
         float tx = mg.x, ty = mg.y, tz = mg.z;
         if constexpr (!OWNER) icp_transform_point (T, mg.x, mg.y, mg.z, tx, ty, tz);
-        if constexpr (PRUNE && ICP_S1_ORIGIN_LIST) {
+        if constexpr (PRUNE) {
             // Dense variants.  A query that is an invalid point of its frame (at the origin before the transformation) is flagged — bit 31 of
             // the seed: ks_seed_against_invalid — and handed over BEHIND the block's valid queries (a stable partition of the 64: the valid
             // ones stay neighbours).  Scattered over the block's waves such queries made nearly every wave walk the list of the
@@ -1459,7 +1495,7 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
         __syncthreads ();                            // the queries (s_qa / s_qc), the tile boxes, s_tmask = 0
         {
             const float4 a4 = s_qa[qe], c4 = s_qc[qe];
-            if constexpr (PRUNE && ICP_S1_ORIGIN_LIST) { if (prune) n_origin = (uint32_t) __builtin_amdgcn_readfirstlane ((int) __float_as_uint (s_tbox[1].w)); }
+            if constexpr (PRUNE) { if (prune) n_origin = (uint32_t) __builtin_amdgcn_readfirstlane ((int) __float_as_uint (s_tbox[1].w)); }
             qx = a4.x; qy = a4.y; qz = a4.z; i = __float_as_uint (a4.w); valid = i < m;
             qr = c4.x; qg = c4.y; qb = c4.z; seed = __float_as_uint (c4.w);
         }
@@ -1470,7 +1506,7 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
             const uint32_t sfl = seed >> 30;             // (bit 1: an invalid point of its frame, bit 0: a seed from the grid cell — ks_seed_against_invalid)
             seed = min (seed & 0x3FFFFFFFu, nr - 1u);
             float sx, sy, sz, sr, sg, sb;
-            if (ICP_HOME_MODE == 1 && seed / KT == ht) {
+            if (seed / KT == ht) {
                 const float *sp = s_pairf + PB * 4u + ((seed - ht * KT) >> 1) * 12u + (seed & 1u);
                 sx = sp[0]; sy = sp[2]; sz = sp[4]; sr = sp[6]; sg = sp[8]; sb = sp[10];
                 // (keeps the compiler from merging this with the global path below into flat loads)
@@ -1479,7 +1515,7 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
                 const float4 g = R4[2 * (size_t) seed], c = R4[2 * (size_t) seed + 1];
                 sx = g.x; sy = g.y; sz = g.z; sr = c.x; sg = c.y; sb = c.z;
             }
-            if constexpr (ICP_S1_ORIGIN_LIST) ks_seed_against_invalid (sfl, s_tbox + 1, nr, b, R4, seed, sx, sy, sz, sr, sg, sb);
+            ks_seed_against_invalid (sfl, s_tbox + 1, nr, b, R4, seed, sx, sy, sz, sr, sg, sb);
             const float b0 = icp_metric8 (qx, qy, qz, qr, qg, qb, sx, sy, sz, sr, sg, sb, alpha);
             if (b0 >= 0.f && b0 < __builtin_inff ()) s1_lim = __uint_as_float (__float_as_uint (b0) + 1u);     // next float up
             // tiles this query can find a nearer representative in: lane ss tests the tiles ss, ss + LPQ, ..; OR over the lanes
@@ -1488,11 +1524,7 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
             // 64-register variants then spilled — or read again from LDS behind it: |F| = 65536 18.19 -> 18.09 us, 2^20 274.7 -> 273.2)
 #pragma unroll 1
             for (uint32_t t = ss; t < ntile; t += KS_SPLIT) {
-                const float4 lo = s_tbox[2u * t], hi = s_tbox[2u * t + 1u];
-                const float ex = fmaxf (fmaxf (lo.x - qx, qx - hi.x), 0.f);
-                const float ey = fmaxf (fmaxf (lo.y - qy, qy - hi.y), 0.f);
-                const float ez = fmaxf (fmaxf (lo.z - qz, qz - hi.z), 0.f);
-                if (__builtin_fmaf (ez, ez, __builtin_fmaf (ey, ey, ex * ex)) < s1_lim) tm |= 1u << t;
+                if (ks_box_bound (s_tbox[2u * t], s_tbox[2u * t + 1u], qx, qy, qz) < s1_lim) tm |= 1u << t;
             }
             tm |= (uint32_t) __builtin_amdgcn_update_dpp (0, (int) tm, 0xB1, 0xF, 0xF, true);      // quad_perm [1,0,3,2]
             tm |= (uint32_t) __builtin_amdgcn_update_dpp (0, (int) tm, 0x4E, 0xF, 0xF, true);      // quad_perm [2,3,0,1]
@@ -1505,7 +1537,6 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
                  (uint32_t) __builtin_amdgcn_readlane ((int) wm, 32) | (uint32_t) __builtin_amdgcn_readlane ((int) wm, 48);
             if (lane == 0) atomicOr (&s_tmask, wm);
         }
-        if (ICP_HOME_MODE == 2) home_to_lds ();
         __syncthreads ();
         KS_STAMP (10)
         uint32_t bm = s_tmask;                       // block-uniform
@@ -1514,7 +1545,7 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
             const uint32_t tl = (uint32_t) __builtin_ctz (bm);
             bm &= bm - 1u;
             const uint32_t t0 = tl * KT, tn = min (KT, nr - t0), npair = (tn + 1u) >> 1;
-            const uint32_t hb = (ICP_HOME_MODE != 3 && tl == ht) ? 1u : 0u;    // the home tile is there already: no fetch, no barrier
+            const uint32_t hb = tl == ht ? 1u : 0u;    // the home tile is there already: no fetch, no barrier
             if (!hb) {
                 if (used0) __syncthreads ();         // every wave is done with the previous tile of buffer 0
                 used0 = true;
@@ -1522,11 +1553,7 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
                     const uint32_t nbx = 2u * ((tn + 2u * KS_SPLIT - 1u) / (2u * KS_SPLIT));
                     if (tid < nbx) s_box[tid] = GBt[2u * (t0 / (2u * KS_SPLIT)) + tid];
                 }
-                if (tid < tn) {
-                    const float4 g = R4[2 * (size_t) (t0 + tid)], c = R4[2 * (size_t) (t0 + tid) + 1];
-                    float *dst = s_pairf + (tid >> 1) * 12u + (tid & 1u);
-                    dst[0] = g.x; dst[2] = g.y; dst[4] = g.z; dst[6] = c.x; dst[8] = c.y; dst[10] = c.z;
-                }
+                if (tid < tn) ks_rep_to_lds (s_pairf, tid, R4[2 * (size_t) (t0 + tid)], R4[2 * (size_t) (t0 + tid) + 1]);
                 __syncthreads ();
             }
             if (prune) {
@@ -1538,17 +1565,7 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
             } else {
                 const float2v vqx = { qx, qx }, vqy = { qy, qy }, vqz = { qz, qz }, vqr = { qr, qr }, vqg = { qg, qg }, vqb = { qb, qb };
                 const float2v va = { alpha, alpha };
-                for (uint32_t P = ss; P < npair; P += KS_SPLIT) {
-                    float4 A = s_pair[hb * PB + 3 * P], B = s_pair[hb * PB + 3 * P + 1], C = s_pair[hb * PB + 3 * P + 2];
-                    float2v x = { A.x, A.y }, y = { A.z, A.w }, z = { B.x, B.y }, r = { B.z, B.w }, g = { C.x, C.y }, bb = { C.z, C.w };
-                    float2v dx = vqx - x, dy = vqy - y, dz = vqz - z, dr = vqr - r, dg = vqg - g, db = vqb - bb;
-                    float2v geo = __builtin_elementwise_fma (dz, dz, __builtin_elementwise_fma (dy, dy, dx * dx));
-                    float2v pho = __builtin_elementwise_fma (db, db, __builtin_elementwise_fma (dg, dg, dr * dr));
-                    float2v d = __builtin_elementwise_fma (va, pho, geo);
-                    const uint32_t r0 = t0 + 2u * P;
-                    if (d.x < best) { best = d.x; bid = r0; }
-                    if (d.y < best) { best = d.y; bid = r0 + 1u; }
-                }
+                for (uint32_t P = ss; P < npair; P += KS_SPLIT) KS_PAIR (hb * PB + 3 * P, t0 + 2u * P)      // (not unrolled by hand: as the compiler leaves it)
             }
         }
     } else
@@ -1560,11 +1577,7 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
         // block's 64 neighbouring queries need one, seldom two, of the four tiles)
         auto tile_near = [&] (float lim_) -> bool {
             if (SINGLE || nr <= KT) return true;
-            const float4 lo = s_tbox[2u * (t0 / ICP_TBOX)], hi = s_tbox[2u * (t0 / ICP_TBOX) + 1u];     // (staged in the prologue)
-            const float ex = fmaxf (fmaxf (lo.x - qx, qx - hi.x), 0.f);
-            const float ey = fmaxf (fmaxf (lo.y - qy, qy - hi.y), 0.f);
-            const float ez = fmaxf (fmaxf (lo.z - qz, qz - hi.z), 0.f);
-            return __builtin_fmaf (ez, ez, __builtin_fmaf (ey, ey, ex * ex)) < lim_;
+            return ks_box_bound (s_tbox[2u * (t0 / ICP_TBOX)], s_tbox[2u * (t0 / ICP_TBOX) + 1u], qx, qy, qz) < lim_;     // (staged in the prologue)
         };
         if (t0) {                                    // further tiles (nr > KT)
             __syncthreads ();
@@ -1578,23 +1591,20 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
                 if (!__syncthreads_or (cmask != 0u)) continue;
             }
             for (uint32_t k = tid; k < tn; k += 64 * KS_SPLIT) {
-                float4 g = R4[2 * (size_t) (t0 + k)], c = R4[2 * (size_t) (t0 + k) + 1];
-                float *dst = s_pairf + (k >> 1) * 12u + (k & 1u);
-                dst[0] = g.x; dst[2] = g.y; dst[4] = g.z; dst[6] = c.x; dst[8] = c.y; dst[10] = c.z;
+                ks_rep_to_lds (s_pairf, k, R4[2 * (size_t) (t0 + k)], R4[2 * (size_t) (t0 + k) + 1]);
                 if constexpr (!OWNER) s_on[k] = make_uint2 (gO[t0 + k], gN[t0 + k]);
             }
         }
         if ((tn & 1u) && tid == 0) {                 // odd tile (nr == 1): the pad slot never wins (NaN distance)
-            float *dst = s_pairf + (tn >> 1) * 12u + 1u;
             const float qnan = __builtin_nanf ("");
-            dst[0] = qnan; dst[2] = qnan; dst[4] = qnan; dst[6] = qnan; dst[8] = qnan; dst[10] = qnan;
+            ks_rep_to_lds (s_pairf, tn, make_float4 (qnan, qnan, qnan, qnan), make_float4 (qnan, qnan, qnan, qnan));
         }
         // (chained variant, queries handed over inside the finalize: its closing barrier already stands behind every LDS write of
         // the prologue — representatives, list headers, boxes, queries —; a second one here would only be waited for)
         if (!(CHAIN && handed && t0 == 0u && !(tn & 1u))) __syncthreads ();
         if (t0 == 0) {                               // the query prepared by the query wave
             const float4 a4 = s_qa[qe], c4 = s_qc[qe];
-            if constexpr (PRUNE && ICP_S1_ORIGIN_LIST) { if (prune) n_origin = (uint32_t) __builtin_amdgcn_readfirstlane ((int) __float_as_uint ((!SINGLE && nr > KT) ? s_tbox[1].w : s_box[1].w)); }
+            if constexpr (PRUNE) { if (prune) n_origin = (uint32_t) __builtin_amdgcn_readfirstlane ((int) __float_as_uint ((!SINGLE && nr > KT) ? s_tbox[1].w : s_box[1].w)); }
             qx = a4.x; qy = a4.y; qz = a4.z; i = __float_as_uint (a4.w); valid = i < m;
             qr = c4.x; qg = c4.y; qb = c4.z; seed = __float_as_uint (c4.w);
         }
@@ -1625,7 +1635,7 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
                 const float4 g = R4[2 * (size_t) seed], c = R4[2 * (size_t) seed + 1];
                 sx = g.x; sy = g.y; sz = g.z; sr = c.x; sg = c.y; sb = c.z;
             }
-            if constexpr (ICP_S1_ORIGIN_LIST && MINW == 4)
+            if constexpr (MINW == 4)
                 ks_seed_against_invalid (sfl, (!SINGLE && nr > KT) ? s_tbox + 1 : s_box + 1, nr, b, R4, seed, sx, sy, sz, sr, sg, sb);
             const float b0 = icp_metric8 (qx, qy, qz, qr, qg, qb, sx, sy, sz, sr, sg, sb, alpha);
             if (b0 >= 0.f && b0 < __builtin_inff ()) lim = __uint_as_float (__float_as_uint (b0) + 1u);     // next float up
@@ -1639,21 +1649,11 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
             s1_lim = fminf (lim, ks_grp_min_f<KS_SPLIT> (best));
         } else {
 #pragma unroll 8
-            for (uint32_t P = ss; P < npair; P += KS_SPLIT) {
-                float4 A = s_pair[3 * P], B = s_pair[3 * P + 1], C = s_pair[3 * P + 2];
-                float2v x = { A.x, A.y }, y = { A.z, A.w }, z = { B.x, B.y }, r = { B.z, B.w }, g = { C.x, C.y }, bb = { C.z, C.w };
-                float2v dx = vqx - x, dy = vqy - y, dz = vqz - z, dr = vqr - r, dg = vqg - g, db = vqb - bb;
-                float2v geo = __builtin_elementwise_fma (dz, dz, __builtin_elementwise_fma (dy, dy, dx * dx));
-                float2v pho = __builtin_elementwise_fma (db, db, __builtin_elementwise_fma (dg, dg, dr * dr));
-                float2v d = __builtin_elementwise_fma (va, pho, geo);
-                const uint32_t r0 = t0 + 2u * P;
-                if (d.x < best) { best = d.x; bid = r0; }
-                if (d.y < best) { best = d.y; bid = r0 + 1u; }
-            }
+            for (uint32_t P = ss; P < npair; P += KS_SPLIT) KS_PAIR (3 * P, t0 + 2u * P)
         }
     }
     KS_STAMP (14)
-    if constexpr (PRUNE && ICP_S1_ORIGIN_LIST) {
+    if constexpr (PRUNE) {
         // the representatives at the origin (invalid points): kept out of the boxes above, scanned here by the queries that are near the origin
         // Their number rides in a spare lane of the box array the block has staged in LDS anyway (hi.w of group box 0 / of tile box 0:
         // k_reps_and_boxes): one LDS read here.  (Loaded from global memory in the prologue — by a vector load, or by a scalar one with its
@@ -1680,18 +1680,8 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
     }
     KS_KEEP (dr, rstar)
     KS_STAMP (3)
-    // list offset / size of the winner.  One tile (always the case for the MINW == 2 variants, see icp_launch_search):
-    // from LDS; the compile-time split keeps the compiler from merging the two sources into flat loads.
-    uint32_t o, n;
-    if constexpr (MINW == 2) { const uint2 on = s_on[rstar]; o = on.x; n = on.y; }
-    else if constexpr (MASKED) {
-        // the home tile's (offset, size) pairs are in LDS (buffer 1 is never overwritten): a winner there — the usual case — costs
-        // no dependent global load
-        if (rstar / KT == ht) { const uint2 on = s_on[rstar - ht * KT]; o = on.x; n = on.y; asm volatile ("" : "+v"(o), "+v"(n)); }
-        else { o = gO[rstar]; n = gN[rstar]; }
-    }
-    else if (nr <= KT) { const uint2 on = s_on[rstar]; o = on.x; n = on.y; asm volatile ("" : "+v"(o), "+v"(n)); }
-    else { o = gO[rstar]; n = gN[rstar]; }
+    const uint2 on = ks_winner_list<MINW, MASKED, KT> (s_on, gO, gN, rstar, nr, ht);
+    const uint32_t o = on.x, n = on.y;
 
     // ==================================================== STAGE 2 =====================================================
     // ---- stage 2: the list of that representative (ks_stage2_lanes / ks_stage2_wave)
@@ -1710,7 +1700,7 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
 
 
 // ------------------------------------------------------------------------------------------
-// host side, shared by the two translation units' launchers
+// host side, shared by the three translation units' launchers
 // ------------------------------------------------------------------------------------------
 static inline uint32_t icp_tpr_magic (uint32_t side)
 {   // floor (2^32 / tpr) + 1 for tpr = side / 8 tiles per row (tpr == 1: one block, b == 0, any value works)
@@ -1718,38 +1708,50 @@ static inline uint32_t icp_tpr_magic (uint32_t side)
     return tpr ? (uint32_t) ((1ull << 32) / tpr + 1ull) : 0u;
 }
 #define KS_FLAGS(p) ((uint32_t) ((p).check ? 1u : 0u) | ((p).emit ? 8u : 0u) | ((p).warm_seed ? 32u : 0u) | ((p).xcdmap ? 64u : 0u))
+// k_search's arguments (k_search_args): of a search; of launch j > 0 of a chain (state slot / moments buffer p.slot); of the owner search
 #define KS_ARGS p.M, p.R, p.st, (const double *) p.mom, p.m, p.nr, p.side, icp_tpr_magic (p.side), p.nb, KS_FLAGS (p), p
 #define KS_CHAIN_ARGS p.M, p.R, p.cst + p.slot, (const double *) p.mom + (size_t) p.slot * ICP_NMOM * p.nb, p.m, p.nr, p.side, icp_tpr_magic (p.side), p.nb, KS_FLAGS (p), p
+#define KS_OWNER_ARGS p.F, p.R, p.st, (const double *) p.mom, p.m, p.nr, p.side, icp_tpr_magic (p.side), p.nb, 0u, p
+
+// The instantiations by family.  k_search keeps its positional template list (profiles, docs/HISTORY.md and the diagnostics name the
+// variants by it); a launch names its kernel through one of these, which fix what the family never varies: ks_latency (one 1024-thread
+// block per CU), ks_dense (512-thread blocks, pruning; tile 256 — SINGLE, or MASKED = not SINGLE — or 1024), ks_chained (the chained form
+// of the latency variant), ks_owner (the owner search of buildRBC: stage 1 only).  REJ remains the translation unit's choice.
+typedef void (*ks_kernel) (const float *, const float *, icp_reg_state *, const double *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, icp_params);
+template <bool FUSED, bool REJ> constexpr ks_kernel ks_latency = k_search<FUSED, false, 2, 16, false, 1, 1024, false, false, false, REJ>;
+template <bool FUSED, int TILE, bool SINGLE, bool S2W, bool REJ> constexpr ks_kernel ks_dense = k_search<FUSED, false, 4, 8, false, 1, TILE, SINGLE, S2W, false, REJ>;
+template <int ROT, bool HOSTRUN, bool REJ> constexpr ks_kernel ks_chained = k_search<true, true, 2, 16, false, ROT, 1024, false, false, HOSTRUN, REJ>;
+enum ks_owner_form { KS_OWNER_LATENCY, KS_OWNER_DENSE_1024, KS_OWNER_DENSE_256_SINGLE, KS_OWNER_DENSE_256_MASKED };
+template <ks_owner_form F> constexpr ks_kernel ks_owner =
+    k_search<true, false, F == KS_OWNER_LATENCY ? 2 : 4, F == KS_OWNER_LATENCY ? 16 : 8, true, 1, (F == KS_OWNER_DENSE_256_SINGLE || F == KS_OWNER_DENSE_256_MASKED) ? 256 : 1024,
+             F == KS_OWNER_DENSE_256_SINGLE>;
 
 // the launch of a search, the selection of the kernel (REJ = true: icp_search_rej.hip only; false: the latency variants and the chain
 // icp_kernels.hip, the dense ones icp_search_dense.hip)
+// Dense: ks_dense_select (icp_search_select.h) decides the form once — tile = icp_dense_tile (p); SINGLE iff tile == 256 and nr <= 256;
+// MASKED iff tile == 256 and nr > 256 (the SINGLE = false instantiation); at tile 1024 SINGLE is always false; S2W iff p.s2wave — and
+// the fused and the reference-order grid share the dispatch: fused (nb, batch), reference order (2 * nwg, batch); 512 threads.
+// (The reference-order variants take the same tile as the fused ones: the tile boxes of a registration are built for one tile size, p.tbox.)
+template <bool FUSED, bool REJ>
+static inline ks_kernel ks_dense_kernel (const ks_dense_form &f)
+{
+    if (f.masked) return f.s2w ? ks_dense<FUSED, 256, false, true, REJ> : ks_dense<FUSED, 256, false, false, REJ>;
+    if (f.single) return f.s2w ? ks_dense<FUSED, 256, true, true, REJ> : ks_dense<FUSED, 256, true, false, REJ>;
+    return f.s2w ? ks_dense<FUSED, 1024, false, true, REJ> : ks_dense<FUSED, 1024, false, false, REJ>;
+}
 template <bool REJ>
 void ks_launch_dense (const icp_params &p, hipStream_t s)
 {
-    const bool t256 = icp_dense_tile (p) == 256u, multi = p.nr > 256u;
-    if (p.fused) {
-        if (p.s2wave && multi && t256) hipLaunchKernelGGL ((k_search<true, false, 4, 8, false, 1, 256, false, true, false, REJ>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else if (p.s2wave && t256) hipLaunchKernelGGL ((k_search<true, false, 4, 8, false, 1, 256, true, true, false, REJ>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else if (p.s2wave) hipLaunchKernelGGL ((k_search<true, false, 4, 8, false, 1, 1024, false, true, false, REJ>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else if (multi && t256) hipLaunchKernelGGL ((k_search<true, false, 4, 8, false, 1, 256, false, false, false, REJ>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else if (t256) hipLaunchKernelGGL ((k_search<true, false, 4, 8, false, 1, 256, true, false, false, REJ>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else hipLaunchKernelGGL ((k_search<true, false, 4, 8, false, 1, 1024, false, false, false, REJ>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_ARGS);
-    } else {
-        // (the same tile choice as the fused variants: the tile boxes of a registration are built for one tile size, p.tbox)
-        if (p.s2wave && multi && t256) hipLaunchKernelGGL ((k_search<false, false, 4, 8, false, 1, 256, false, true, false, REJ>), dim3 (2 * p.nwg, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else if (p.s2wave && t256) hipLaunchKernelGGL ((k_search<false, false, 4, 8, false, 1, 256, true, true, false, REJ>), dim3 (2 * p.nwg, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else if (p.s2wave) hipLaunchKernelGGL ((k_search<false, false, 4, 8, false, 1, 1024, false, true, false, REJ>), dim3 (2 * p.nwg, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else if (multi && t256) hipLaunchKernelGGL ((k_search<false, false, 4, 8, false, 1, 256, false, false, false, REJ>), dim3 (2 * p.nwg, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else if (t256) hipLaunchKernelGGL ((k_search<false, false, 4, 8, false, 1, 256, true, false, false, REJ>), dim3 (2 * p.nwg, p.batch), dim3 (512), 0, s, KS_ARGS);
-        else hipLaunchKernelGGL ((k_search<false, false, 4, 8, false, 1, 1024, false, false, false, REJ>), dim3 (2 * p.nwg, p.batch), dim3 (512), 0, s, KS_ARGS);
-    }
+    const ks_dense_form f = ks_dense_select (p.nr, p.nrx, p.s2wave);
+    const ks_kernel k = p.fused ? ks_dense_kernel<true, REJ> (f) : ks_dense_kernel<false, REJ> (f);
+    hipLaunchKernelGGL (k, dim3 (ks_dense_grid_x (p.fused, p.nb, p.nwg), p.batch), dim3 (KS_DENSE_THREADS), 0, s, KS_ARGS);
 }
 
 template <bool REJ>
 void ks_launch_latency (const icp_params &p, hipStream_t s)
 {
-    if (p.fused) hipLaunchKernelGGL ((k_search<true, false, 2, 16, false, 1, 1024, false, false, false, REJ>), dim3 (p.nb, p.batch), dim3 (1024), 0, s, KS_ARGS);
-    else hipLaunchKernelGGL ((k_search<false, false, 2, 16, false, 1, 1024, false, false, false, REJ>), dim3 (2 * p.nwg, p.batch), dim3 (1024), 0, s, KS_ARGS);
+    if (p.fused) hipLaunchKernelGGL ((ks_latency<true, REJ>), dim3 (p.nb, p.batch), dim3 (1024), 0, s, KS_ARGS);
+    else hipLaunchKernelGGL ((ks_latency<false, REJ>), dim3 (2 * p.nwg, p.batch), dim3 (1024), 0, s, KS_ARGS);
 }
 
 // launch j of a chain: reads state slot / moments buffer j & 1 and leaves the other (j = 0: reads the user-visible state, nothing to finalize yet)
@@ -1761,14 +1763,8 @@ void ks_launch_chain_one (const icp_params &p0, hipStream_t s, uint32_t j, bool 
     p.emit = emit ? 1 : 0;
     const uint32_t first_flags = 2u | (fresh ? 16u : 0u);             // (fresh: the run starts from the identity, see k_search)
     // (host-driven checked runs — p.hmirror set — take the HOSTRUN instantiation, fixed-length graphs the plain one)
-#define KS_CHAIN_LAUNCH(ROT_, HR_)                                                                                                              \
-    do {                                                                                                                                        \
-        if (j == 0) hipLaunchKernelGGL ((k_search<true, true, 2, 16, false, ROT_, 1024, false, false, HR_, REJ>), dim3 (p.nb, p.batch), dim3 (1024), 0, s, p.M, p.R, p.st, \
-                                        (const double *) p.mom, p.m, p.nr, p.side, icp_tpr_magic (p.side), p.nb, KS_FLAGS (p) | first_flags, p);     \
-        else hipLaunchKernelGGL ((k_search<true, true, 2, 16, false, ROT_, 1024, false, false, HR_, REJ>), dim3 (p.nb, p.batch), dim3 (1024), 0, s, KS_CHAIN_ARGS);     \
-    } while (0)
     const bool hostrun = p.hmirror != nullptr;
-    if (p.rot == 1) { if (hostrun) KS_CHAIN_LAUNCH (1, true); else KS_CHAIN_LAUNCH (1, false); }
-    else            { if (hostrun) KS_CHAIN_LAUNCH (0, true); else KS_CHAIN_LAUNCH (0, false); }
-#undef KS_CHAIN_LAUNCH
+    const ks_kernel k = p.rot == 1 ? (hostrun ? ks_chained<1, true, REJ> : ks_chained<1, false, REJ>) : (hostrun ? ks_chained<0, true, REJ> : ks_chained<0, false, REJ>);
+    if (j == 0) hipLaunchKernelGGL (k, dim3 (p.nb, p.batch), dim3 (1024), 0, s, p.M, p.R, p.st, (const double *) p.mom, p.m, p.nr, p.side, icp_tpr_magic (p.side), p.nb, KS_FLAGS (p) | first_flags, p);
+    else hipLaunchKernelGGL (k, dim3 (p.nb, p.batch), dim3 (1024), 0, s, KS_CHAIN_ARGS);
 }

@@ -10,11 +10,9 @@
 // 256-tile: icp_dense_tile)
 void icp_launch_owner_search_dense (const icp_params &p, hipStream_t s)
 {
-#define KS_OWNER_ARGS p.F, p.R, p.st, (const double *) p.mom, p.m, p.nr, p.side, icp_tpr_magic (p.side), p.nb, 0u, p
-    if (p.nr > 256u && icp_dense_tile (p) == 256u) hipLaunchKernelGGL ((k_search<true, false, 4, 8, true, 1, 256, false>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_OWNER_ARGS);
-    else if (icp_dense_tile (p) == 256u) hipLaunchKernelGGL ((k_search<true, false, 4, 8, true, 1, 256, true>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_OWNER_ARGS);
-    else hipLaunchKernelGGL ((k_search<true, false, 4, 8, true>), dim3 (p.nb, p.batch), dim3 (512), 0, s, KS_OWNER_ARGS);
-#undef KS_OWNER_ARGS
+    const ks_dense_form f = ks_dense_select (p.nr, p.nrx, 0u);
+    const ks_kernel k = f.masked ? ks_owner<KS_OWNER_DENSE_256_MASKED> : f.single ? ks_owner<KS_OWNER_DENSE_256_SINGLE> : ks_owner<KS_OWNER_DENSE_1024>;
+    hipLaunchKernelGGL (k, dim3 (p.nb, p.batch), dim3 (KS_DENSE_THREADS), 0, s, KS_OWNER_ARGS);
 }
 
 void icp_launch_search_dense (const icp_params &p, hipStream_t s) { ks_launch_dense<false> (p, s); }

@@ -761,6 +761,11 @@ def test_stage1_pruning_exact_fused_multi_tile(engine, oracle, side, nr, zero_fr
     (256, 256, 1, False, 0.05, (1, 256, 1)),        # reference-order reductions
     (128, 64, 3, True, 0.0, (1, 256, 1)),           # dense by batch
     (256, 1024, 1, True, 0.0, (1, 256, 0)),         # lists of 64: the lanes of a query scan (the other form)
+    (64, 64, 9, True, 0.0, (1, 256, 0)),            # one 256-tile with the lanes form (dense by batch, lists of 64)
+    (256, 8192, 1, True, 0.0, (1, 1024, 0)),        # the 1024-tile (representative grid 128 wide) with the lanes form (lists of 8)
+    (256, 512, 1, False, 0.1, (1, 256, 1)),         # several 256-tiles in reference order
+    (256, 8192, 1, False, 0.0, (1, 1024, 0)),       # the 1024-tile in reference order, lanes form
+    (1024, 8192, 1, False, 0.0, (1, 1024, 1)),      # the 1024-tile in reference order, lanes = candidates (lists of 128 need 2^20 points)
 ])
 def test_stage2_lanes_as_candidates(engine, oracle, side, nr, batch, fused, zero_fraction, layout):
     """Dense search, long lists (>= 128 candidates on average): stage 2 runs with lanes = candidates — a wave loads a list once
@@ -783,7 +788,7 @@ def test_stage2_lanes_as_candidates(engine, oracle, side, nr, batch, fused, zero
         o.build_rbc()
         oracles.append(o)
     g.buildRBC()
-    for it in range(4):
+    for it in range(4 if m < (1 << 20) else 1):      # (2^20 points: one step, like the fused 1024-tile test below)
         g.step()
         for b, o in enumerate(oracles):
             o.step()

@@ -22,10 +22,11 @@ def demangle(names):
     return out.stdout.split("\n")[:len(names)] if out.returncode == 0 else names
 
 
-def kernel_resources(source="icp_amd/csrc/icp_kernels.hip", extra_flags=()):
-    """{demangled kernel name: {vgprs, sgprs, scratch, occupancy, lds, ...}} for one translation unit."""
-    cmd = [HIPCC] + FLAGS + list(extra_flags) + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, source), "-o", os.devnull]
-    p = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
+def kernel_resources(source="icp_amd/csrc/icp_kernels.hip", extra_flags=(), root=None):
+    """{demangled kernel name: {vgprs, sgprs, scratch, occupancy, lds, ...}} for one translation unit (root: another tree than this one)."""
+    root = root or ROOT
+    cmd = [HIPCC] + FLAGS + list(extra_flags) + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(root, source), "-o", os.devnull]
+    p = subprocess.run(cmd, capture_output=True, text=True, cwd=root)
     if p.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + p.stderr[-4000:])
     recs, cur = [], None
@@ -46,10 +47,11 @@ def kernel_resources(source="icp_amd/csrc/icp_kernels.hip", extra_flags=()):
     return {re.sub(r"\(.*$", "", n.replace("(anonymous namespace)::", "")).replace("void ", ""): r for n, r in zip(names, recs)}
 
 
-def kernel_isa(source="icp_amd/csrc/icp_kernels.hip", extra_flags=()):
-    """{mangled kernel name: [instruction lines]} of one translation unit's device code (hipcc -S --cuda-device-only)."""
-    p = subprocess.run([HIPCC] + FLAGS + list(extra_flags) + ["-S", "--cuda-device-only", "-o", "-", os.path.join(ROOT, source)],
-                       capture_output=True, text=True, cwd=ROOT)
+def kernel_isa(source="icp_amd/csrc/icp_kernels.hip", extra_flags=(), root=None):
+    """{mangled kernel name: [instruction lines]} of one translation unit's device code (hipcc -S --cuda-device-only; root: another tree than this one)."""
+    root = root or ROOT
+    p = subprocess.run([HIPCC] + FLAGS + list(extra_flags) + ["-S", "--cuda-device-only", "-o", "-", os.path.join(root, source)],
+                       capture_output=True, text=True, cwd=root)
     if p.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + p.stderr[-4000:])
     out, cur = {}, None
