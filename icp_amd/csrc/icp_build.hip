@@ -8,6 +8,11 @@
 // ------------------------------------------------------------------------------------------
 // state
 // ------------------------------------------------------------------------------------------
+// what ICP::buildRBC restarts (src/ICP/algorithms.cpp:4796)
+static __device__ __forceinline__ void state_restart (icp_reg_state *st) { st->k = 0; st->done = 0; st->pm_iters = 0; }
+// the cumulative rotation re-derived from the quaternion of T
+static __device__ __forceinline__ void state_rotation_from (icp_reg_state *st, const float *T) { float R[9]; icp_quat_to_rot (T, R); for (int i = 0; i < 9; ++i) st->R[i] = R[i]; }
+
 __global__ void k_reset_state (icp_params p, int reset_T)
 {
     uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -22,18 +27,17 @@ __global__ void k_reset_state (icp_params p, int reset_T)
         for (int i = 0; i < 8; ++i) st->means[i] = 0.f;
         st->sum_w = 0.0;
     }
-    st->k = 0; st->done = 0; st->pm_iters = 0;       // ICP::buildRBC — :4796
+    state_restart (st);
 }
 
 // write (D_IO_T): T is replaced and the cumulative rotation re-derived from it
 __global__ void k_set_T (icp_reg_state *st, const float *T8, int reset_k)
 {
     if (threadIdx.x != 0) return;
-    if (reset_k) { st->k = 0; st->done = 0; st->pm_iters = 0; }      // (tracking: what buildRBC would have reset, see icp_params::no_state_reset)
+    if (reset_k) state_restart (st);                 // (tracking: what buildRBC would have reset, see icp_params::no_state_reset)
     float T[8]; for (int i = 0; i < 8; ++i) T[i] = T8[i];
     for (int i = 0; i < 8; ++i) st->T[i] = T[i];
-    float R[9]; icp_quat_to_rot (T, R);
-    for (int i = 0; i < 9; ++i) st->R[i] = R[i];
+    state_rotation_from (st, T);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -117,6 +121,61 @@ __global__ __launch_bounds__ (256) void k_transform_cloud_ex (const float4 *in, 
 // buildRBC
 // ------------------------------------------------------------------------------------------
 
+// ---- the steps the construction's kernels share, one spelling each ----
+// inclusive scan over the wave's lanes
+static __device__ __forceinline__ uint32_t wave_scan_incl (uint32_t v, uint32_t lane)
+{
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) { const uint32_t t = __shfl_up (v, d); if (lane >= d) v += t; }
+    return v;
+}
+// exclusive scan of `part` over the block's threads (exclusiveScan_i, kernels/scan_kernels.cl:188): wave scans, then the totals of the
+// earlier waves through s_wave (one word per wave).  Holds a barrier: every thread of the block calls it.
+static __device__ __forceinline__ uint32_t block_scan_excl (uint32_t part, uint32_t lane, uint32_t wave, uint32_t *s_wave)
+{
+    const uint32_t inc = wave_scan_incl (part, lane);
+    if (lane == 63u) s_wave[wave] = inc;
+    __syncthreads ();
+    uint32_t run = inc - part;
+    for (uint32_t w = 0; w < wave; ++w) run += s_wave[w];
+    return run;
+}
+// K-component min / max over rows of W lanes (min / max are exact in any order)
+template <int K, int W>
+static __device__ __forceinline__ void row_minmax (float (&lo)[K], float (&hi)[K])
+{
+#pragma unroll
+    for (int d = W / 2; d > 0; d >>= 1)
+#pragma unroll
+        for (int k = 0; k < K; ++k) { lo[k] = fminf (lo[k], __shfl_xor (lo[k], d, W)); hi[k] = fmaxf (hi[k], __shfl_xor (hi[k], d, W)); }
+}
+// a box takes a point in (fminf / fmaxf skip NaN coordinates)
+static __device__ __forceinline__ void box_add (float (&lo)[3], float (&hi)[3], float x, float y, float z)
+{
+    lo[0] = fminf (lo[0], x); lo[1] = fminf (lo[1], y); lo[2] = fminf (lo[2], z);
+    hi[0] = fmaxf (hi[0], x); hi[1] = fmaxf (hi[1], y); hi[2] = fmaxf (hi[2], z);
+}
+// ... unless it is at the origin: an invalid point of its frame (or a slot beyond the set, read as zeros) stays out of the geometry boxes, listed in p.OL (ks_origin_list)
+static __device__ __forceinline__ void box_add_off_origin (float (&lo)[3], float (&hi)[3], const float4 &v)
+{
+    const float inf = __builtin_inff ();
+    const bool in = !(v.x == 0.f && v.y == 0.f && v.z == 0.f);
+    lo[0] = fminf (lo[0], in ? v.x : inf); lo[1] = fminf (lo[1], in ? v.y : inf); lo[2] = fminf (lo[2], in ? v.z : inf);
+    hi[0] = fmaxf (hi[0], in ? v.x : -inf); hi[1] = fmaxf (hi[1], in ? v.y : -inf); hi[2] = fmaxf (hi[2], in ? v.z : -inf);
+}
+// The placement record of fixed point i (geometry g, colour c) at position pos of registration b: perm, X_P, and the search copy laid out for packed
+// fp32 math, [x r y g | z b id 0] — (geometry, colour) pairs side by side, the unused homogeneous lane carries the original index (saves the perm[] round trip)
+static __device__ __forceinline__ void place_record (const icp_params &p, uint32_t b, uint32_t pos, uint32_t i, const float4 &g, const float4 &c)
+{
+    float4 *X4 = reinterpret_cast<float4 *> (p.XP + (size_t) b * p.m * 8);
+    float4 *Q4 = reinterpret_cast<float4 *> (p.XQ + (size_t) b * p.m * 8);
+    p.perm[(size_t) b * p.m + pos] = i;
+    X4[2 * (size_t) pos] = g;
+    X4[2 * (size_t) pos + 1] = c;
+    Q4[2 * (size_t) pos] = make_float4 (g.x, c.x, g.y, c.y);
+    Q4[2 * (size_t) pos + 1] = make_float4 (g.z, c.z, __uint_as_float (i), 0.f);
+}
+
 #define ICP_ORIGIN_SOLO 16u       // k_reps_and_boxes: up to this many blocks of 64 representatives, one wave lists those at the origin by itself
 
 // the end of the list of the representatives at the origin (k_reps_and_boxes): colour boxes of its chunks, its length where the search reads it
@@ -138,13 +197,9 @@ static __device__ __forceinline__ void origin_list_close (const icp_params &p, u
         for (uint32_t e = lane; e < run; e += 64u) {
             const float4 v = OL[1u + e];
             s_ent[e] = v;
-            lo[0] = fminf (lo[0], v.x); lo[1] = fminf (lo[1], v.y); lo[2] = fminf (lo[2], v.z);
-            hi[0] = fmaxf (hi[0], v.x); hi[1] = fmaxf (hi[1], v.y); hi[2] = fmaxf (hi[2], v.z);
+            box_add (lo, hi, v.x, v.y, v.z);
         }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { lo[k] = fminf (lo[k], __shfl_xor (lo[k], d)); hi[k] = fmaxf (hi[k], __shfl_xor (hi[k], d)); }
+        row_minmax<3, 64> (lo, hi);
         float sc[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) sc[k] = hi[k] > lo[k] ? 32.f / (hi[k] - lo[k]) : 0.f;
@@ -215,16 +270,13 @@ static __device__ __forceinline__ void origin_list_close (const icp_params &p, u
         float4 *BX = OL + 1u + p.nr;
         const uint32_t n_oc = (run + 7u) >> 3;
         for (uint32_t c = lane; c < n_oc; c += 64u) {
-            float4 lo = make_float4 (inf, inf, inf, 0.f), hi = make_float4 (-inf, -inf, -inf, 0.f);
+            float lo[3] = { inf, inf, inf }, hi[3] = { -inf, -inf, -inf };
             float4 v[8];                                                  // (the chunk's eight entries in flight; past the list's end: its last entry once more)
 #pragma unroll
             for (uint32_t e = 0; e < 8u; ++e) v[e] = OL[1u + min (8u * c + e, run - 1u)];
 #pragma unroll
-            for (uint32_t e = 0; e < 8u; ++e) {
-                lo.x = fminf (lo.x, v[e].x); lo.y = fminf (lo.y, v[e].y); lo.z = fminf (lo.z, v[e].z);
-                hi.x = fmaxf (hi.x, v[e].x); hi.y = fmaxf (hi.y, v[e].y); hi.z = fmaxf (hi.z, v[e].z);
-            }
-            BX[2u * c] = lo; BX[2u * c + 1u] = hi;
+            for (uint32_t e = 0; e < 8u; ++e) box_add (lo, hi, v[e].x, v[e].y, v[e].z);
+            BX[2u * c] = make_float4 (lo[0], lo[1], lo[2], 0.f); BX[2u * c + 1u] = make_float4 (hi[0], hi[1], hi[2], 0.f);
         }
     }
     if (lane == 0) {
@@ -291,9 +343,7 @@ __global__ __launch_bounds__ (64) void k_reps_and_boxes (icp_params p, uint32_t 
         for (uint32_t i0 = 0; i0 < nbr; i0 += 64u) {                  // 64 ballots at a time: lane l holds ballot i0 + l and the number of entries in front of it
             const unsigned long long mk = i0 + lane < nbr ? __hip_atomic_load (MK + i0 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
             const uint32_t cnt = (uint32_t) __builtin_popcountll (mk);
-            uint32_t incl = cnt;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up (incl, d); if ((int) lane >= d) incl += t; }
+            const uint32_t incl = wave_scan_incl (cnt, lane);
             const uint32_t before = run + incl - cnt, mlo = (uint32_t) mk, mhi = (uint32_t) (mk >> 32);
             if (__ballot (mk != 0ull)) {
                 for (uint32_t u0 = 0; u0 < 64u; u0 += 8u) {           // eight ballots' colour loads in flight
@@ -320,7 +370,7 @@ __global__ __launch_bounds__ (64) void k_reps_and_boxes (icp_params p, uint32_t 
     } else if (blockIdx.x < nbr + nbg) {
         const uint32_t g = (blockIdx.x - nbr) * 64u + lane;
         if (g >= p.n16) return;
-        float4 lo = make_float4 (inf, inf, inf, 0.f), hi = make_float4 (-inf, -inf, -inf, 0.f);
+        float lo[3] = { inf, inf, inf }, hi[3] = { -inf, -inf, -inf };
         const bool tiled = p.gtile != 0u;
         const uint32_t lg = p.gtile - 1u, ty = tiled ? g >> lg : 0u, tx = tiled ? g & ((1u << lg) - 1u) : 0u;
         float4 v[16];                                                 // (all sixteen loads in flight, then the selects: a loop with an early
@@ -331,16 +381,11 @@ __global__ __launch_bounds__ (64) void k_reps_and_boxes (icp_params p, uint32_t 
             if (r < p.nr) v[e] = F4[2 * (size_t) src_of (r)];
         }
 #pragma unroll
-        for (uint32_t e = 0; e < 16u; ++e) {
-            // an invalid point (at the origin; so reads a slot beyond the set): kept out of the box, listed in p.OL (k_search: ks_origin_list)
-            const bool in = !(v[e].x == 0.f && v[e].y == 0.f && v[e].z == 0.f);
-            lo.x = fminf (lo.x, in ? v[e].x : inf); lo.y = fminf (lo.y, in ? v[e].y : inf); lo.z = fminf (lo.z, in ? v[e].z : inf);
-            hi.x = fmaxf (hi.x, in ? v[e].x : -inf); hi.y = fmaxf (hi.y, in ? v[e].y : -inf); hi.z = fmaxf (hi.z, in ? v[e].z : -inf);
-        }
+        for (uint32_t e = 0; e < 16u; ++e) box_add_off_origin (lo, hi, v[e]);
         float4 *GB = p.GB + (size_t) b * 2 * (p.n16 + p.n1k);
-        GB[2 * g] = lo;
+        GB[2 * g] = make_float4 (lo[0], lo[1], lo[2], 0.f);
         float *hi3 = reinterpret_cast<float *> (GB + 2 * g + 1);          // (hi.w of group box 0 belongs to the block that lists the representatives at the origin)
-        hi3[0] = hi.x; hi3[1] = hi.y; hi3[2] = hi.z;
+        hi3[0] = hi[0]; hi3[1] = hi[1]; hi3[2] = hi[2];
     } else if (nbr <= ICP_ORIGIN_SOLO && blockIdx.x == gridDim.x - 1u) {
         // (small sets) the representatives at the origin: one wave, a ballot and a running offset per 64 representatives, all geometry
         // loads in flight at once; the colour is fetched by the lanes that list an entry
@@ -379,16 +424,9 @@ __global__ __launch_bounds__ (64) void k_reps_and_boxes (icp_params p, uint32_t 
                 if (r < r_end) v[u] = F4[2 * (size_t) src_of (r)];
             }
 #pragma unroll
-            for (uint32_t u = 0; u < 16u; ++u) {
-                const bool in = !(v[u].x == 0.f && v[u].y == 0.f && v[u].z == 0.f);
-                lo[0] = fminf (lo[0], in ? v[u].x : inf); lo[1] = fminf (lo[1], in ? v[u].y : inf); lo[2] = fminf (lo[2], in ? v[u].z : inf);
-                hi[0] = fmaxf (hi[0], in ? v[u].x : -inf); hi[1] = fmaxf (hi[1], in ? v[u].y : -inf); hi[2] = fmaxf (hi[2], in ? v[u].z : -inf);
-            }
+            for (uint32_t u = 0; u < 16u; ++u) box_add_off_origin (lo, hi, v[u]);
         }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { lo[k] = fminf (lo[k], __shfl_xor (lo[k], d)); hi[k] = fmaxf (hi[k], __shfl_xor (hi[k], d)); }
+        row_minmax<3, 64> (lo, hi);
         if (lane == 0) {
             float4 *GB = p.GB + (size_t) b * 2 * (p.n16 + p.n1k) + 2u * p.n16;
             GB[2 * tile] = make_float4 (lo[0], lo[1], lo[2], 0.f);
@@ -464,14 +502,7 @@ __global__ __launch_bounds__ (1024) void k_offsets (icp_params p)
     const uint32_t per = (p.nr + 1023u) / 1024u, lo = t * per, hi = min (lo + per, p.nr);
     uint32_t part = 0;
     for (uint32_t r = lo; r < hi; ++r) part += N[r];
-    uint32_t inc = part;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) { const uint32_t v = __shfl_up (inc, d); if (lane >= d) inc += v; }
-    if (lane == 63u) s_wave[wave] = inc;
-    __syncthreads ();
-    uint32_t base = 0;
-    for (uint32_t w = 0; w < wave; ++w) base += s_wave[w];
-    uint32_t run = base + inc - part;
+    uint32_t run = block_scan_excl (part, lane, wave, s_wave);
     for (uint32_t r = lo; r < hi; ++r) { O[r] = run; run += N[r]; }
 }
 
@@ -494,14 +525,8 @@ __global__ __launch_bounds__ (1024) void k_count_offsets (icp_params p)
         }
         p.N[(size_t) b * p.nr + r] = run; ICP_N_FULL (p, b)[r] = run;
     }
-    uint32_t inc = run;                              // exclusive scan over r (exclusiveScan_i, kernels/scan_kernels.cl:188)
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) { const uint32_t v = __shfl_up (inc, d); if (lane >= d) inc += v; }
-    if (lane == 63u) s_wave[wave] = inc;
-    __syncthreads ();
-    uint32_t base = 0;
-    for (uint32_t w = 0; w < wave; ++w) base += s_wave[w];
-    if (r < p.nr) p.O[(size_t) b * p.nr + r] = base + inc - run;
+    const uint32_t before = block_scan_excl (run, lane, wave, s_wave);      // exclusive scan over r
+    if (r < p.nr) p.O[(size_t) b * p.nr + r] = before;
 }
 
 // step 5: stable placement: position = O[owner] + #{j < i : owner[j] == owner[i]}; perm, X_P and the search copy.
@@ -539,20 +564,12 @@ __global__ __launch_bounds__ (1024) void k_place (icp_params p)
             rank += (v.x == own) ? v.y : 0u;
         }
     }
-    if (chunk == 0u && t == 0u && !p.no_state_reset) { icp_reg_state *st = p.st + b; st->k = 0; st->done = 0; st->pm_iters = 0; }     // ICP::buildRBC (:4796)
+    if (chunk == 0u && t == 0u && !p.no_state_reset) state_restart (p.st + b);
     if (valid) {
         const uint32_t pos = base + rank;
         const float4 *F4 = reinterpret_cast<const float4 *> (p.F + (size_t) b * p.m * 8);
-        float4 *X4 = reinterpret_cast<float4 *> (p.XP + (size_t) b * p.m * 8);
-        p.perm[(size_t) b * p.m + pos] = i;
-        float4 g = F4[2 * (size_t) i], c = F4[2 * (size_t) i + 1];
-        X4[2 * (size_t) pos] = g;
-        X4[2 * (size_t) pos + 1] = c;
-        // search copy, laid out for packed fp32 math: [x r y g | z b id 0] — (geometry, colour) pairs side by side, and
-        // the unused homogeneous lane carries the original index (saves the perm[] round trip)
-        float4 *Q4 = reinterpret_cast<float4 *> (p.XQ + (size_t) b * p.m * 8);
-        Q4[2 * (size_t) pos] = make_float4 (g.x, c.x, g.y, c.y);
-        Q4[2 * (size_t) pos + 1] = make_float4 (g.z, c.z, __uint_as_float (i), 0.f);
+        const float4 g = F4[2 * (size_t) i], c = F4[2 * (size_t) i + 1];      // (loaded here: a reference to F itself would be read again behind every store)
+        place_record (p, b, pos, i, g, c);
     }
 }
 
@@ -572,10 +589,7 @@ static __device__ __forceinline__ void list_boxes_of (const icp_params &p, uint3
 #pragma unroll
             for (int k = 0; k < 6; ++k) if (lo[k] != lo[k]) { lo[k] = inf; hi[k] = -inf; }    // NaN: out of the box
         }
-#pragma unroll
-        for (int d = 8; d > 0; d >>= 1)
-#pragma unroll
-            for (int k = 0; k < 6; ++k) { lo[k] = fminf (lo[k], __shfl_xor (lo[k], d, 16)); hi[k] = fmaxf (hi[k], __shfl_xor (hi[k], d, 16)); }
+        row_minmax<6, 16> (lo, hi);
         if (l == 0) {
             float4 *dst = LB + 3 * (size_t) ((o >> 4) + c);
             dst[0] = make_float4 (lo[0], lo[1], lo[2], lo[3]);
@@ -669,20 +683,14 @@ __global__ __launch_bounds__ (256) void k_place_lists (icp_params p)
     const uint32_t per = (p.nr + 255u) / 256u, lo = min (t * per, p.nr), hi = min (lo + per, p.nr);
     uint32_t part = 0u;
     for (uint32_t r = lo; r < hi; ++r) part += s_total[r];
-    uint32_t inc = part;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) { const uint32_t v = __shfl_up (inc, d); if (lane >= d) inc += v; }
-    if (lane == 63u) s_wave[wave] = inc;
-    __syncthreads ();
-    uint32_t run = inc - part;
-    for (uint32_t w = 0; w < wave; ++w) run += s_wave[w];
+    uint32_t run = block_scan_excl (part, lane, wave, s_wave);
     for (uint32_t r = lo; r < hi; ++r) {
         const uint32_t n = s_total[r];
         if (c == 0u) { p.N[(size_t) b * p.nr + r] = n; ICP_N_FULL (p, b)[r] = n; p.O[(size_t) b * p.nr + r] = run; }
         s_before[r] += run;                          // position of the chunk's first point of list r
         run += n;
     }
-    if (c == 0u && t == 0u && !p.no_state_reset) { icp_reg_state *st = p.st + b; st->k = 0; st->done = 0; st->pm_iters = 0; }
+    if (c == 0u && t == 0u && !p.no_state_reset) state_restart (p.st + b);
     __syncthreads ();
     if (valid) {
         uint32_t pos = s_before[own] + rk;
@@ -690,13 +698,7 @@ __global__ __launch_bounds__ (256) void k_place_lists (icp_params p)
             const uint32_t n = s_n[w];
             for (uint32_t e = 0; e < n; ++e) { const uint2 v = s_list[w][e]; pos += (v.x == own) ? v.y : 0u; }
         }
-        float4 *X4 = reinterpret_cast<float4 *> (p.XP + (size_t) b * p.m * 8);
-        float4 *Q4 = reinterpret_cast<float4 *> (p.XQ + (size_t) b * p.m * 8);
-        p.perm[(size_t) b * p.m + pos] = i;
-        X4[2 * (size_t) pos] = g;
-        X4[2 * (size_t) pos + 1] = cc;
-        Q4[2 * (size_t) pos] = make_float4 (g.x, cc.x, g.y, cc.y);                      // search copy: see k_place
-        Q4[2 * (size_t) pos + 1] = make_float4 (g.z, cc.z, __uint_as_float (i), 0.f);
+        place_record (p, b, pos, i, g, cc);
     }
 }
 
@@ -760,9 +762,7 @@ __global__ __launch_bounds__ (256) void k_list_boxes (icp_params p)
             if (!as_prev && !as_first) keep |= 1u << e;
         }
         const uint32_t cnt = (uint32_t) __builtin_popcount (keep);
-        uint32_t inc = cnt;
-#pragma unroll
-        for (uint32_t d = 1; d < 64u; d <<= 1) { const uint32_t v = __shfl_up (inc, d); if (lane >= d) inc += v; }
+        const uint32_t inc = wave_scan_incl (cnt, lane);     // (the block step stays in this kernel's own text: its barriers also order s_prev, and it needs the total)
         __syncthreads ();                            // (every read of this pass is done; s_prev / s_cnt of the previous pass have been used)
         if (lane == 63u) s_cnt[wave] = inc;
         const uint32_t last = min (s + 256u * E, n) - 1u;       // the pass's last position: the next pass's predecessor
@@ -866,10 +866,9 @@ __global__ __launch_bounds__ (64) void k_gate (const uint32_t *seq, uint32_t wan
         return;
     }
     if (warm) {
-        warm->k = 0; warm->done = 0; warm->pm_iters = 0;
+        state_restart (warm);
         float T[4]; for (int i = 0; i < 4; ++i) T[i] = warm->T[i];
-        float R[9]; icp_quat_to_rot (T, R);
-        for (int i = 0; i < 9; ++i) warm->R[i] = R[i];
+        state_rotation_from (warm, T);
     }
 }
 
@@ -910,15 +909,6 @@ void icp_launch_transform_cloud_ex (int kind, const float *in, float *out, const
     else hipLaunchKernelGGL (k_transform_cloud_ex<2>, grid, block, 0, s, i4, o4, t, n);
 }
 
-static void build_rbc_lists (const icp_params &p, hipStream_t s);
-
-// buildRBC; with ICP_NORMALS_GRID (icp_set_normals) the fixed set's normals behind it (icp_p2pl.hip)
-void icp_launch_build_rbc (const icp_params &p, hipStream_t s)
-{
-    build_rbc_lists (p, s);
-    if (p.nrm_grid) icp_launch_normals_grid (p, s);
-}
-
 static void build_rbc_lists (const icp_params &p, hipStream_t s)
 {
     if (icp_build_lists (p)) {                       // two launches: the owner search (gathers the representatives itself, leaves the lists), the placement
@@ -948,4 +938,11 @@ static void build_rbc_lists (const icp_params &p, hipStream_t s)
     }
     hipLaunchKernelGGL (k_place, dim3 (p.nchunk, p.batch), dim3 (1024), 0, s, p);
     hipLaunchKernelGGL (k_list_boxes, dim3 (p.nr, p.batch), dim3 (256), 0, s, p);
+}
+
+// buildRBC; with ICP_NORMALS_GRID (icp_set_normals) the fixed set's normals behind it (icp_p2pl.hip)
+void icp_launch_build_rbc (const icp_params &p, hipStream_t s)
+{
+    build_rbc_lists (p, s);
+    if (p.nrm_grid) icp_launch_normals_grid (p, s);
 }

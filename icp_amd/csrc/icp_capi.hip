@@ -44,12 +44,9 @@ void free_all (icp_context *h)
     h->lm[0] = h->lm[1] = h->lm[2] = nullptr;
     if (h->hTrack) (void) hipHostFree (h->hTrack);
     h->hTrack = nullptr;
-    {   // (whatever track_prepare got to: a failed stream probe leaves the buffers allocated and rbc2_ready false)
-        icp_context::rbc_set &q = h->rbc[1];
-        void *ptrs[] = { q.R, q.GB, q.OL, q.LB, q.XP, q.XQ, q.rep_src, q.owner, q.N, q.O, q.perm, q.chunk_hist, q.blist, q.bn, q.brank };
-        for (void *x : ptrs) if (x) (void) hipFree (x);
-    }
-    h->rbc[0] = h->rbc[1] = icp_context::rbc_set {}; h->rbc2_ready = false;
+    // (whatever track_prepare got to: a failed stream probe leaves the buffers allocated and rbc2_ready false)
+    (void) icp_rbc_for_each (h->rbc[1], h->p, [] (const char *, void **q, size_t) { if (*q) (void) hipFree (*q); return 0; });
+    h->rbc[0] = h->rbc[1] = icp_rbc_set {}; h->rbc2_ready = false;
     if (h->dSeq) (void) hipFree (h->dSeq);
     if (h->dRunFlag) (void) hipFree (h->dRunFlag);
     if (h->hGateFlag) (void) hipHostFree (h->hGateFlag);
@@ -340,30 +337,19 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     if ((rc = dalloc (h, &F, B * m * 8))) return rc;
     if ((rc = dalloc (h, &M, B * m * 8))) return rc;
     h->dF = F; h->dM = M; p.F = F; p.M = M; h->lm[0] = F; h->lm[1] = M;
-    if ((rc = dalloc (h, &p.R, B * nr * 8))) return rc;
     p.n16 = (nr + 15u) / 16u;
-    p.nb = (m + 63u) / 64u;
     p.tbox = icp_tbox_of (p); p.n1k = (nr + p.tbox - 1u) / p.tbox;
     p.s2wave = icp_s2_wave_of (p);
     { const char *e = std::getenv ("ICP_AMD_XCDMAP"); p.xcdmap = e ? (e[0] == '1') : (B == 1u); }
     { const char *e = std::getenv ("ICP_AMD_WARM_SEED"); p.warm_seed = (e && e[0] == '1') ? 1u : 0u; }
     p.gtile = 0u;                                                    // 4 x 4 tile groups where the representative grid allows
     if (nrx % 4u == 0u && nry % 4u == 0u && !std::getenv ("ICP_AMD_STRIP_GROUPS")) { uint32_t lg = 0; while ((4u << lg) < nrx) ++lg; p.gtile = lg + 1u; }
-    if ((rc = dalloc (h, &p.GB, B * 2 * (p.n16 + p.n1k)))) return rc;
-    if ((rc = dalloc (h, &p.XP, icp_xp_layout_of (batch, m).total))) return rc;    // (behind the database: NORMALS_F, COLOR_GRAD_F, NORMALS_M; zeroed)
-    if ((rc = dalloc (h, &p.XQ, B * m * 8))) return rc;
-    if ((rc = dalloc (h, &p.OL, B * ICP_OL_STRIDE (nr)))) return rc;
     p.nlb = m / 16u + 2u;
-    if ((rc = dalloc (h, &p.LB, B * 3 * p.nlb))) return rc;
-    if ((rc = dalloc (h, &p.rep_src, B * nr))) return rc;
-    if ((rc = dalloc (h, &p.owner, B * m))) return rc;
-    if ((rc = dalloc (h, &p.N, 2 * B * nr))) return rc;         // (the search's view of the lengths, then the lengths: ICP_N_FULL)
-    if ((rc = dalloc (h, &p.O, B * nr))) return rc;
-    if ((rc = dalloc (h, &p.perm, B * m))) return rc;
-    if ((rc = dalloc (h, &p.chunk_hist, B * p.nchunk * nr))) return rc;
-    if ((rc = dalloc (h, &p.blist, B * p.nb * 64))) return rc;
-    if ((rc = dalloc (h, &p.bn, B * p.nb))) return rc;
-    if ((rc = dalloc (h, &p.brank, B * m))) return rc;
+    {   // the RBC set (icp_rbc_set.h), zeroed: XP's tail reads 0 until something has written it
+        icp_rbc_set s;
+        if ((rc = icp_rbc_for_each (s, p, [&] (const char *, void **q, size_t bytes) { return dalloc (h, reinterpret_cast<char **> (q), bytes); }))) return rc;
+        icp_rbc_into (p, s);
+    }
     if ((rc = dalloc (h, &p.rid, B * m))) return rc;
     if ((rc = dalloc (h, &p.nn_id, B * m))) return rc;
     if ((rc = dalloc (h, &p.PF, B * m))) return rc;
@@ -562,32 +548,10 @@ int icp_build_rbc (icp_handle h) try
     if (h->opt.boundary_gw && h->p.m % h->opt.boundary_gw)
         return fail (h, ICP_ESTATE, "icp_build_rbc: icp_set_boundary_rejection: m is not a multiple of the grid width");
     note_inputs_change (h);
-    // The two (latency-bound sizes) to six launches of the construction are enqueued as they are: a graph of so few nodes costs more
-    // at its head and tail than it saves between them — same box, back to back, graph against plain launches: A 22.3 -> 13.6 us,
-    // B 46.9 -> 39.8, C 193 -> 185, A x 64 115 -> 106 us (ICP_AMD_BUILD_GRAPH=1 brings the cached graph back for the comparison).
-    {
-        static const char *e = std::getenv ("ICP_AMD_BUILD_GRAPH");
-        const bool direct = !(e && e[0] == '1');
-        if (direct) {
-            note_enqueue (h);
-            icp_launch_build_rbc (h->p, h->stream);
-            HIPCHK (h, hipGetLastError ());
-            h->built = true; h->k_base = 0;                                 // (ICP::buildRBC resets k, :4796)
-            return ICP_OK;
-        }
-    }
-    // the five or six launches of the construction as one cached graph (key: all ones; dropped with the others when a
-    // parameter or a buffer changes)
-    const uint64_t key = ~0ull - h->parity;
-    auto it = h->graphs.find (key);
-    if (it == h->graphs.end ()) {
-        graph_entry ge;
-        if ((rc = capture_graph (h, [&] { icp_launch_build_rbc (h->p, h->stream); }, &ge))) return rc;     // (the placement kernel also sets k = 0: ICP::buildRBC, :4796)
-        it = h->graphs.emplace (key, ge).first;
-    }
     note_enqueue (h);
-    HIPCHK (h, hipGraphLaunch (it->second.exec, h->stream));
-    h->built = true; h->k_base = 0;
+    icp_launch_build_rbc (h->p, h->stream);          // (plain launches: docs/HISTORY.md has the comparison with a cached graph)
+    HIPCHK (h, hipGetLastError ());
+    h->built = true; h->k_base = 0;                                 // (ICP::buildRBC resets k, :4796)
     return ICP_OK;
 }
 ICP_CATCH_ALL

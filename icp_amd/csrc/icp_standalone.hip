@@ -153,13 +153,6 @@ __global__ void k_sa_sij (const float4 *DM, const float4 *DF, const float *W, ui
 }
 
 // ICPLMs / ICPReps
-__global__ void k_sa_get_lms (const float4 *cloud, float4 *lms)
-{
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= 16384u * 2u) return;
-    const uint32_t lm = t >> 1, half = t & 1u, gX = lm & 127u, gY = lm >> 7;
-    lms[t] = cloud[((size_t) (48u + gY * 3u + 1u) * 640u + 64u + 4u * gX + 1u) * 2u + half];      // kernels/icp_kernels.cl:63-76
-}
 __global__ void k_sa_get_reps (const float4 *F, float4 *R, icp_params p)
 {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -373,7 +366,7 @@ int icp_ko_run (icp_ko_handle k) try
     const uint32_t n = k->n;
     switch (k->kind) {
         case ICP_KO_LMS:
-            hipLaunchKernelGGL (k_sa_get_lms, dim3 (128), dim3 (256), 0, 0, (const float4 *) k->slot[0], (float4 *) k->slot[1]);
+            icp_launch_get_lms ((const float *) k->slot[0], (float *) k->slot[1], 0);      // (k_get_lms, icp_build.hip)
             break;
         case ICP_KO_REPS:
             hipLaunchKernelGGL (k_sa_get_reps, dim3 ((k->aux + 255u) / 256u), dim3 (256), 0, 0, (const float4 *) k->slot[0], (float4 *) k->slot[1], k->p);

@@ -41,24 +41,18 @@ static int track_prepare (icp_context *h)
         // the other stream, may converge while launches of this one are still queued; the frame after that is behind them on this stream)
         if (!h->dRunFlag) { HIPCHK (h, hipMalloc ((void **) &h->dRunFlag, 2 * sizeof (uint32_t))); HIPCHK (h, hipMemset (h->dRunFlag, 0, 2 * sizeof (uint32_t))); }
         if (!h->hGateFlag) { HIPCHK (h, hipHostMalloc ((void **) &h->hGateFlag, sizeof (uint32_t), hipHostMallocMapped | hipHostMallocCoherent)); *h->hGateFlag = 0u; }
-        icp_context::rbc_set &a = h->rbc[0], &b = h->rbc[1];
-        a.R = p.R; a.GB = p.GB; a.OL = p.OL; a.LB = p.LB; a.XP = p.XP; a.XQ = p.XQ; a.rep_src = p.rep_src; a.owner = p.owner; a.N = p.N; a.O = p.O; a.perm = p.perm;
-        a.chunk_hist = p.chunk_hist; a.blist = p.blist; a.bn = p.bn; a.brank = p.brank;
-        auto al = [&] (void **q, size_t bytes) -> int {
-            hipError_t e = hipMalloc (q, bytes ? bytes : 1);
-            if (e == hipSuccess) e = hipMemset (*q, 0, bytes ? bytes : 1);
-            return e == hipSuccess ? ICP_OK : fail (h, ICP_ENOMEM, std::string ("tracking (second RBC set): ") + hipGetErrorString (e));
-        };
-        int rc;
-        if (!b.R && ((rc = al ((void **) &b.R, (size_t) p.nr * 32)) || (rc = al ((void **) &b.GB, (size_t) 2 * (p.n16 + p.n1k) * 16)) || (rc = al ((void **) &b.LB, (size_t) 3 * p.nlb * 16)) || (rc = al ((void **) &b.OL, (size_t) ICP_OL_STRIDE (p.nr) * 16)) || (rc = al ((void **) &b.XP, icp_xp_layout_of (p.batch, p.m).total * sizeof (float))) ||
-            (rc = al ((void **) &b.XQ, (size_t) p.m * 32)) || (rc = al ((void **) &b.rep_src, (size_t) p.nr * 4)) || (rc = al ((void **) &b.owner, (size_t) p.m * 4)) ||
-            (rc = al ((void **) &b.N, (size_t) 2 * p.batch * p.nr * 4)) || (rc = al ((void **) &b.O, (size_t) p.nr * 4)) || (rc = al ((void **) &b.perm, (size_t) p.m * 4)) ||
-            (rc = al ((void **) &b.chunk_hist, (size_t) p.nchunk * p.nr * 4)) || (rc = al ((void **) &b.blist, (size_t) p.nb * 64 * 8)) ||
-            (rc = al ((void **) &b.bn, (size_t) p.nb * 4)) || (rc = al ((void **) &b.brank, (size_t) p.m)))) {
-            void *ptrs[] = { b.R, b.GB, b.OL, b.LB, b.XP, b.XQ, b.rep_src, b.owner, b.N, b.O, b.perm, b.chunk_hist, b.blist, b.bn, b.brank };
-            for (void *x : ptrs) if (x) (void) hipFree (x);
-            b = icp_context::rbc_set {};
-            return rc;
+        h->rbc[0] = icp_rbc_of (p);
+        if (!h->rbc[1].R) {                          // (all or nothing: a set that could not be completed is freed again)
+            const int rc = icp_rbc_for_each (h->rbc[1], p, [&] (const char *, void **q, size_t bytes) -> int {
+                hipError_t e = hipMalloc (q, bytes ? bytes : 1);
+                if (e == hipSuccess) e = hipMemset (*q, 0, bytes ? bytes : 1);
+                return e == hipSuccess ? ICP_OK : fail (h, ICP_ENOMEM, std::string ("tracking (second RBC set): ") + hipGetErrorString (e));
+            });
+            if (rc) {
+                (void) icp_rbc_for_each (h->rbc[1], p, [] (const char *, void **q, size_t) { if (*q) (void) hipFree (*q); return 0; });
+                h->rbc[1] = icp_rbc_set {};
+                return rc;
+            }
         }
         // Do the two streams really run side by side?  HIP spreads streams over a few hardware queues; two streams that share one are served in
         // order, and a gate would then hold back the very launches it is waiting for.  One probe at set-up: a short-lived gate on stream2
@@ -74,12 +68,6 @@ static int track_prepare (icp_context *h)
         h->rbc2_ready = true;
     }
     return ICP_OK;
-}
-
-static void rbc_into (icp_params &p, const icp_context::rbc_set &q)
-{
-    p.R = q.R; p.GB = q.GB; p.OL = q.OL; p.LB = q.LB; p.XP = q.XP; p.XQ = q.XQ; p.rep_src = q.rep_src; p.owner = q.owner; p.N = q.N; p.O = q.O; p.perm = q.perm;
-    p.chunk_hist = q.chunk_hist; p.blist = q.blist; p.bn = q.bn; p.brank = q.brank;
 }
 
 // the iteration counts of the last two registrations the host knows the outcome of (a run that was decided because all max_iterations
@@ -435,7 +423,7 @@ static int track_submit (icp_context *h, const void *cloud, int warm_start, bool
     note_inputs_change (h);
     float *newM = h->lm[buf], *newF = h->lm[(f + 2u) % 3u];             // (f - 1) mod 3: the previous frame's landmarks (first frame: a buffer that is not M)
     icp_params p = h->p; p.M = newM; p.F = newF; p.seq_value = (uint32_t) f;
-    if (gated) rbc_into (p, h->rbc[f & 1u]);
+    if (gated) icp_rbc_into (p, h->rbc[f & 1u]);
     if (f > 0u) {
         note_enqueue (h);
         // warm start: from the previous hop's transform, as by write (D_IO_T) — the first registration of a sequence has no previous hop
@@ -509,7 +497,7 @@ static int track_submit (icp_context *h, const void *cloud, int warm_start, bool
     if (g_tp.on) { g_tp.t[6] += now_s () - tp_first; ++g_tp.n; }
     // everything that can fail is behind us: the handle now points at this frame's buffers
     h->dM = newM; h->p.M = newM; h->dF = newF; h->p.F = newF;
-    if (gated && f > 0u) rbc_into (h->p, h->rbc[f & 1u]);
+    if (gated && f > 0u) icp_rbc_into (h->p, h->rbc[f & 1u]);
     h->parity = 1u + buf;                                               // graphs hold the pointers: one cached set per rotation step (0: the buffers of icp_init)
     h->built = f > 0u;
     h->track_submitted = f + 1u;

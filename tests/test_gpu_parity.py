@@ -28,6 +28,36 @@ def test_build_rbc(engine, oracle, side, nr):
     g.close()
 
 
+@pytest.mark.parametrize("side,nr,batch", [(30, 4, 40), (50, 4, 13)])
+def test_build_rbc_batched(engine, oracle, side, nr, batch):
+    """The dense construction (k_reps_and_boxes, k_chunk_hist, k_count_offsets, k_place) over a batch whose sets end in a ragged chunk
+    of 1024: m = 900 (one partly filled chunk, 40 x 15 = 600 blocks of 64) and m = 2500 (three chunks, the last one ragged, 13 x 40 = 520
+    blocks) — the smallest batches beyond the 512 blocks up to which the construction takes its two-launch form.  Registration by
+    registration what test_build_rbc asserts for one."""
+    Mem = engine.Memory
+    m = side * side
+    g = engine.ICP(0)
+    g.init(m, nr, A, C_, batch=batch)
+    set_modes(engine, g)
+    Fs = []
+    for b in range(batch):
+        F, M = engine.synth_pair(side, seed=0x1C9D5EED + b)
+        g.write(Mem.F, F, batch_index=b); g.write(Mem.M, M, batch_index=b)
+        Fs.append(F)
+    g.buildRBC()
+    for b, F in enumerate(Fs):
+        o = oracle.OracleICP(m, nr, A, C_, threads=1)
+        o.write_f(F); o.write_m(F)
+        o.build_rbc()
+        assert_bits(g.read(Mem.REPS, batch_index=b), o.reps, "representatives of registration %d" % b)
+        assert np.array_equal(g.read(Mem.RBC_OWNER, batch_index=b), o.rbc_owner), ("owner", b)
+        assert np.array_equal(g.read(Mem.RBC_N, batch_index=b), o.rbc_N), ("N", b)
+        assert np.array_equal(g.read(Mem.RBC_O, batch_index=b), o.rbc_O), ("O", b)
+        assert np.array_equal(g.read(Mem.RBC_PERM, batch_index=b), o.rbc_perm), ("perm", b)
+        assert_bits(g.read(Mem.RBC_XP, batch_index=b), F[o.rbc_perm], "permuted database of registration %d" % b)
+    g.close()
+
+
 @pytest.mark.parametrize("side,nr", [(128, 256), (32, 16), (30, 4), (6, 4)])
 def test_steps_bit_exact(engine, oracle, side, nr):
     """config 2 (kg-like pair, power method, weighted) and small / ragged sizes: 4 free-running steps."""

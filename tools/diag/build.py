@@ -1,4 +1,4 @@
-"""Diagnostic (not a test): steady-state RBC construction time (cached graph), config A / B / C."""
+"""Diagnostic (not a test): steady-state RBC construction time (plain launches), config A / B / C."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import icp_amd

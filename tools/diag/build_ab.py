@@ -1,4 +1,4 @@
-"""Diagnostic (not a test): buildRBC time (cached graph, back to back) at the BASELINE sizes.  usage: ICP_AMD_LIB=... [CASE=blobs30] python tools/diag/build_ab.py"""
+"""Diagnostic (not a test): buildRBC time (plain launches, back to back) at the BASELINE sizes.  usage: ICP_AMD_LIB=... [CASE=blobs30] python tools/diag/build_ab.py"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import icp_amd
