@@ -7,6 +7,7 @@
 //   registration A B                      data/A.bin, data/B.bin — or A and B themselves when they name existing files
 //   ... [--out FILE] [--device N] [--reference-order] [--svd] [--reject-invalid] [--max-dist MM] [--trim FRACTION]
 //       [--point-to-plane MU] [--colored KAPPA] [--robust KIND:SCALE] [--plane-to-plane EPS] [--symmetric] [--one-to-one]
+//       [--evaluate MAXDIST]
 //
 // --reject-invalid / --max-dist: correspondence rejection (icp_set_rejection: pairs with a pixel without depth at either end / pairs
 // farther apart than MM get weight 0).  --trim: trimmed ICP (icp_set_trimming: every iteration keeps the closest FRACTION in (0, 1] of the
@@ -19,6 +20,8 @@
 // --symmetric: symmetric ICP (icp_set_symmetric; Rusinkiewicz 2019): point-to-plane along the mean of both frames' grid normals, the
 // rotation split between the frames; implies --point-to-plane 0 when no MU is given.
 // --one-to-one: one-to-one correspondences (icp_set_unique): of the pairs that share a fixed point only the closest keeps its weight.
+// --evaluate: after the run, the registration's quality at the final transform (icp_evaluate): fitness, inlier RMSE and the inlier
+// count for pairs no farther apart than MAXDIST mm (0: no distance test).
 // Not the reference's behaviour; off by default.
 //
 // A cloud file is 640 x 480 points of 8 floats [x y z 1 r g b 1], little endian, row-major (src/kinect_frame_grabber.cpp:252-272).
@@ -49,7 +52,8 @@ std::string data_path (const std::string &name) { return exists (name) ? name : 
 
 template <cl_algo::ICP::ICPStepConfigT RC>
 int run (int device, icp::Mode mode, const std::vector<icp_float8> &pc1, const std::vector<icp_float8> &pc2, const std::string &out,
-         int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa, icp::RobustLoss robust, float gicp_eps, bool symmetric, bool one_to_one)
+         int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa, icp::RobustLoss robust, float gicp_eps, bool symmetric, bool one_to_one,
+         float evaluate)
 {
     ICPReg<RC, cl_algo::ICP::ICPStepConfigW::WEIGHTED> app (device, mode);
     if (reject_flags || max_dist > 0.f) app.setRejection (reject_flags, max_dist);
@@ -68,6 +72,10 @@ int run (int device, icp::Mode mode, const std::vector<icp_float8> &pc1, const s
     auto &reg = app.registration ();
     std::printf ("\n    q = (%.9g, %.9g, %.9g, %.9g)   t = (%.9g, %.9g, %.9g)   s = %.9g   k = %u\n",
                  reg.q.x (), reg.q.y (), reg.q.z (), reg.q.w (), reg.t (0), reg.t (1), reg.t (2), reg.s, reg.k);
+    if (evaluate >= 0.f) {
+        const icp_quality_t q = reg.evaluate (evaluate);
+        std::printf ("    fitness = %.6f   inlier RMSE = %.6f mm   inliers = %u of %u\n", q.fitness, q.inlier_rmse, q.n_inliers, q.n_moving);
+    }
     if (!out.empty ()) {
         std::ofstream f (out, std::ios::binary);
         f.write (reinterpret_cast<const char *> (app.transformed ().data ()), (std::streamsize) (kPoints * sizeof (icp_float8)));
@@ -84,7 +92,7 @@ int main (int argc, char **argv)
     std::vector<std::string> names;
     std::string out;
     int device = 0; bool svd = false, symmetric = false, one_to_one = false;
-    int reject_flags = 0; float max_dist = 0.f, trim = 1.f, p2pl_mu = -1.f, kappa = -1.f, gicp_eps = 0.f;     // (p2pl_mu < 0: point-to-point; kappa < 0: not colored; gicp_eps 0: off)
+    int reject_flags = 0; float max_dist = 0.f, trim = 1.f, p2pl_mu = -1.f, kappa = -1.f, gicp_eps = 0.f, evaluate = -1.f;     // (p2pl_mu < 0: point-to-point; kappa < 0: not colored; gicp_eps 0: off; evaluate < 0: no quality report)
     icp::RobustLoss robust;
     icp::Mode mode = icp::Mode::FAST;
     for (int i = 1; i < argc; ++i) {
@@ -110,6 +118,10 @@ int main (int argc, char **argv)
         else if (a == "--plane-to-plane" && i + 1 < argc) {
             gicp_eps = std::strtof (argv[++i], nullptr);
             if (!(gicp_eps > 0.f && gicp_eps <= 1.f)) { std::fprintf (stderr, "--plane-to-plane: EPS must be in (0, 1]\n"); return 2; }
+        }
+        else if (a == "--evaluate" && i + 1 < argc) {
+            evaluate = std::strtof (argv[++i], nullptr);
+            if (!(evaluate >= 0.f)) { std::fprintf (stderr, "--evaluate: MAXDIST must be >= 0\n"); return 2; }
         }
         else if (a == "--symmetric") symmetric = true;
         else if (a == "--one-to-one") one_to_one = true;
@@ -140,8 +152,8 @@ int main (int argc, char **argv)
         } else {
             read_cloud (data_path (names[0]), pc1); read_cloud (data_path (names[1]), pc2);
         }
-        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one)
-                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one);
+        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, evaluate)
+                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, evaluate);
     }
     catch (const std::exception &e)
     {

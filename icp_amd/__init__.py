@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-__all__ = ["ICP", "ICPStep", "ICPError", "Memory", "ErrorMetric", "Normals", "ICPStepConfigT", "ICPStepConfigW",
+__all__ = ["ICP", "ICPStep", "ICPError", "Memory", "Quality", "ErrorMetric", "Normals", "ICPStepConfigT", "ICPStepConfigW",
            "PowerMode", "ReduceMode", "TransformKind", "ICPBatch", "batch_partition", "power_method", "KernelObject", "kernel_lms", "kernel_reps", "kernel_weights", "kernel_mean", "kernel_devs", "kernel_s", "ReduceScan", "lib", "lib_path", "reduce", "scan", "ReduceConfig", "synth_pair", "synth_cloud_vga", "punch_holes", "HOLES_SCATTERED", "HOLES_CONTIGUOUS", "synth_pair_scene", "SCENE_CURVED", "SCENE_WALL", "device_count", "DIST_ID"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -97,6 +97,16 @@ class _State(C.Structure):
                 ("Rk", C.c_float * 9), ("qk", C.c_float * 4), ("tk", C.c_float * 3), ("sk", C.c_float),
                 ("k", C.c_uint32), ("converged", C.c_uint32), ("power_iterations", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class Quality(C.Structure):
+    """icp_quality_t (include/icp_amd.h): fitness, inlier RMSE, the sum of the inliers' squared distances, the 6 x 6 information matrix
+    (row-major, rotation first), and the counts (n = m, counted moving points, inliers)."""
+    _fields_ = [("fitness", C.c_double), ("inlier_rmse", C.c_double), ("sum_geo", C.c_double), ("information", C.c_double * 36),
+                ("n", C.c_uint32), ("n_moving", C.c_uint32), ("n_inliers", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def information_matrix(self):
+        return np.array(self.information, np.float64).reshape(6, 6)
 
 
 _lib = None
@@ -186,6 +196,8 @@ def lib():
     sig("icp_set_reduce_mode", i32, vp, i32)
     sig("icp_state", i32, vp, C.POINTER(_State))
     sig("icp_state_b", i32, vp, u32, C.POINTER(_State))
+    sig("icp_evaluate", i32, vp, f32, C.POINTER(Quality), u32)
+    sig("icp_batch_evaluate", i32, vp, u32, f32, C.POINTER(Quality))
     sig("icp_write_cloud", i32, vp, i32, vp, i32)
     sig("icp_transform_cloud", i32, vp, vp, vp, u32)
     sig("icp_transform_cloud_ex", i32, vp, i32, vp, vp, vp, u32)
@@ -993,6 +1005,15 @@ class ICPStep:
         self._chk(self._L.icp_state_b(self._h, batch_index, C.byref(st)))
         return st
 
+    def evaluate(self, max_dist=0.0, count=None):
+        """Registration quality at the current transform (icp_evaluate; blocking): a list of Quality records, one per registration
+        0 .. count - 1 (count None: the whole batch).  max_dist: the largest distance of an inlier pair, in the cloud's units (None, 0
+        or inf: no distance test).  The handle's options have no influence, and the call disturbs nothing an iteration reads or writes."""
+        n = self.batch if count is None else int(count)
+        out = (Quality * max(n, 1))()
+        self._chk(self._L.icp_evaluate(self._h, _max_dist_arg(max_dist), out, n))
+        return list(out)[:n]
+
     def _vec(self, name, shape=None):
         a = np.array(getattr(self.state(), name), dtype=np.float32)
         return a.reshape(shape) if shape else a
@@ -1236,6 +1257,12 @@ class ICPBatch:
         st = _State()
         self._chk(self._L.icp_batch_state(self._b, i, C.byref(st)))
         return st
+
+    def evaluate(self, i, max_dist=0.0):
+        """ICPStep.evaluate of registration i: its Quality record (icp_batch_evaluate)."""
+        q = Quality()
+        self._chk(self._L.icp_batch_evaluate(self._b, i, _max_dist_arg(max_dist), C.byref(q)))
+        return q
 
     def read(self, i, mem):
         dt, cols = _MEM_DTYPE[mem]

@@ -350,6 +350,18 @@ int icp_batch_state (icp_batch_handle b, uint32_t i, icp_state_t *out) try
 }
 ICP_CATCH_ALL
 
+// icp_evaluate of registration i's slot (one launch set serves the slot's registrations), the record of registration i
+int icp_batch_evaluate (icp_batch_handle b, uint32_t i, float max_dist, icp_quality_t *out) try
+{
+    BATCH_SLOT (b, i)
+    if (!out) return bfail (b, ICP_EINVAL, "icp_batch_evaluate: null output");
+    std::vector<icp_quality_t> q (idx_ + 1u);
+    BATCH_CALL (b, icp_evaluate (h_, max_dist, q.data (), idx_ + 1u));
+    *out = q[idx_];
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
 int icp_batch_set_modes (icp_batch_handle b, int reduce_mode, int power_mode) try
 {
     int rc = set_all (b, icp_set_reduce_mode, reduce_mode);

@@ -32,6 +32,7 @@ void free_all (icp_context *h)
     if (h->dCloudOut) (void) hipFree (h->dCloudOut);
     h->hF = h->hM = h->hT = nullptr; h->dCloud = h->dCloudOut = nullptr; h->cloud_cap = 0;
     h->dF = h->dM = nullptr; h->ownF = h->ownM = true;
+    h->quality = icp_context::quality_buffers {};                 // (they were among dev_allocs)
     for (int k = 0; k < 2; ++k) {
         if (h->hBand[k]) (void) hipHostFree (h->hBand[k]);
         if (h->hFrame[k]) (void) hipHostFree (h->hFrame[k]);
@@ -1029,6 +1030,65 @@ int icp_state_b (icp_handle h, uint32_t b, icp_state_t *out) try
 ICP_CATCH_ALL
 
 int icp_state (icp_handle h, icp_state_t *out) try { api_guard guard_ (h); return icp_state_b (h, 0, out); } ICP_CATCH_ALL
+
+// Registration quality (include/icp_amd.h; icp_quality.hip): one search at the registrations' current state into the evaluation's own
+// buffers, the pair kernel, the second level, one copy of the result words.  The search is the plain one of the handle's layout in its
+// reference-order form with every opt-in rule off and REGULAR weights — the same correspondences and points bit for bit, and a form
+// that writes nothing but its per-query outputs: no moment partials (the fused form's), no weight partials (the WEIGHTED ones).  The
+// state, the flags of the lazy outputs, the graphs and the pinned mirror are not touched.
+int icp_evaluate (icp_handle h, float max_dist, icp_quality_t *out, uint32_t count) try
+{
+    api_guard guard_ (h);
+    if (!h) return ICP_EINVAL;
+    if (!out) return fail (h, ICP_EINVAL, "icp_evaluate: null output");
+    if (count == 0) return fail (h, ICP_EINVAL, "icp_evaluate: count must be at least 1");
+    if (!(max_dist >= 0.f)) return fail (h, ICP_EINVAL, "icp_evaluate: max_dist must be >= 0 (0 or +inf: no distance test)");
+    int rc = need (h, false); if (rc) return rc;         // (brings an open checked run to its end, as icp_read does)
+    if (count > h->p.batch) return fail (h, ICP_EINVAL, "icp_evaluate: count is above the handle's batch");
+    if (h->track_submitted) return fail (h, ICP_ESTATE, "icp_evaluate: the handle has tracked frames (the quality of tracked frames is not provided): icp_init or icp_track_reset first");
+    if (!h->built) return fail (h, ICP_ESTATE, "icp_build_rbc has not been called");
+    const icp_params &p = h->p;
+    const size_t B = p.batch, n = B * p.m, nblk = icp_p2pl_nblk (p.m);
+    if ((rc = set_device (h))) return rc;
+    icp_context::quality_buffers &Q = h->quality;
+    // (first use; each buffer on its own: a call that ran out of memory half way leaves what it got to the next one)
+    if (!Q.nn_id && (rc = dalloc (h, &Q.nn_id, n))) return rc;
+    if (!Q.PF && (rc = dalloc (h, &Q.PF, n))) return rc;
+    if (!Q.PM && (rc = dalloc (h, &Q.PM, n))) return rc;
+    if (!Q.rid && (rc = dalloc (h, &Q.rid, n))) return rc;
+    if (!Q.part && (rc = dalloc (h, &Q.part, B * ICP_QUALITY_TERMS * nblk))) return rc;
+    if (!Q.cnt && (rc = dalloc (h, &Q.cnt, B * 2 * nblk))) return rc;
+    if (!Q.res && (rc = dalloc (h, &Q.res, B * ICP_QUALITY_RES))) return rc;
+    icp_params q = p;
+    q.check = 0; q.emit = 1; q.fused = 0; q.weighted = 0; q.hmirror = nullptr; q.hstate = nullptr; q.dbg = nullptr;
+    q.reject = 0u; q.reject_d2 = 0.f; q.reject_max_dist = 0.f; q.trim_keep = 0.f; q.metric = ICP_METRIC_POINT_TO_POINT; q.p2pl_mu = 0.f; q.gicp = 0u;
+    q.nn_id = Q.nn_id; q.PF = Q.PF; q.PM = Q.PM; q.rid = Q.rid;
+    // (the dense search seeds its pruning with the nearest representatives of the search before it and leaves its own: the seeds are the
+    // iterations', the answers stay here)
+    if (icp_dense (q)) HIPCHK (h, hipMemcpyAsync (Q.rid, p.rid, n * sizeof (uint32_t), hipMemcpyDeviceToDevice, h->stream));
+    icp_launch_search (q, h->stream);
+    const bool dist_on = max_dist > 0.f && !std::isinf (max_dist);
+    icp_launch_quality (Q.PF, Q.PM, p.M, p.m, p.batch, dist_on, dist_on ? (float) ((double) max_dist * (double) max_dist) : 0.f, Q.part, Q.cnt, Q.res, h->stream);
+    HIPCHK (h, hipGetLastError ());
+    std::vector<double> res (B * ICP_QUALITY_RES);
+    HIPCHK (h, hipMemcpyAsync (res.data (), Q.res, res.size () * sizeof (double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK (h, hipStreamSynchronize (h->stream));
+    for (uint32_t b = 0; b < count; ++b) {
+        const double *r = res.data () + (size_t) b * ICP_QUALITY_RES;
+        icp_quality_t &o = out[b];
+        uint32_t c[2];
+        std::memcpy (c, r + ICP_QUALITY_TERMS, sizeof c);
+        o.n = p.m; o.n_moving = c[0]; o.n_inliers = c[1]; o.reserved = 0u;
+        o.sum_geo = r[21];
+        o.fitness = c[0] ? (double) c[1] / (double) c[0] : 0.0;
+        o.inlier_rmse = c[1] ? std::sqrt (r[21] / (double) c[1]) : 0.0;
+        int t = 0;
+        for (int a = 0; a < 6; ++a)
+            for (int cc = a; cc < 6; ++cc, ++t) { o.information[a * 6 + cc] = r[t]; o.information[cc * 6 + a] = r[t]; }
+    }
+    return ICP_OK;
+}
+ICP_CATCH_ALL
 
 int icp_write_cloud (icp_handle h, int which, const void *cloud, int block) try
 {

@@ -135,6 +135,13 @@ struct icp_context {
     icp_host::icp_options opt;                   // what the user set (survives icp_init; p's dependent fields are derived from it)
     uint64_t graph_clock = 0, param_gen = 0;     // LRU stamp of the graph cache; generation of the parameters the cached graphs were captured with
     float *dTin = nullptr;                       // device scratch for write(T)
+    // icp_evaluate's own buffers (allocated at its first use, freed with the others by icp_init): the per-query outputs of its search
+    // [batch][m] each, the block partials and counts of k_quality_pairs, the result words of k_quality_finish.  Nothing else reads or
+    // writes them: the outputs, partials and state of the iterations stay as they are.
+    struct quality_buffers {
+        icp_dist_id *nn_id = nullptr; float4 *PF = nullptr, *PM = nullptr; uint32_t *rid = nullptr;
+        double *part = nullptr; uint32_t *cnt = nullptr; double *res = nullptr;
+    } quality;
     float *dCloud = nullptr, *dCloudOut = nullptr; uint32_t cloud_cap = 0;
     std::map<uint64_t, icp_host::graph_entry> graphs;      // key: iterations << 3 | check << 2 | parity (+ fresh, + kind: see get_graph)
     uint32_t parity = 0;                         // tracking: which landmark buffers are the fixed / moving set (graphs hold pointers): frame f -> f mod 3

@@ -173,6 +173,12 @@ static __host__ __device__ __forceinline__ bool icp_gicp (const icp_params &p) {
 static __host__ __device__ __forceinline__ bool icp_sym (const icp_params &p) { return p.gicp == ICP_MOVING_NORMALS_SYM && p.metric == 1u; }
 static __host__ __device__ __forceinline__ uint32_t icp_p2pl_nblk (uint32_t m) { return (m + ICP_P2PL_BLOCK - 1u) / ICP_P2PL_BLOCK; }
 
+// Registration quality (icp_evaluate, icp_quality.hip): the 21 upper-triangle terms of the information matrix, then the sum of geo, by the
+// plane system's two trees over blocks of ICP_P2PL_BLOCK pairs.  Per registration the result is ICP_QUALITY_RES doubles: the 22 sums,
+// then one double's room for the two counts (n_moving, n_inliers: uint32) and one of padding.
+#define ICP_QUALITY_TERMS 22u
+#define ICP_QUALITY_RES 24u
+
 // The moments' allocation p.mom, offsets in doubles.  icp_params has no room for more pointers, so everything the opt-in paths keep per
 // iteration lies behind the fused mode's moment partials: trimming's words, the plane system and its block partials, and colored ICP's
 // weight kappa, the robust loss's scale k and plane-to-plane's epsilon, device words (icp_set_color_weight, icp_set_robust_loss and
@@ -356,6 +362,10 @@ void icp_launch_normals_m (const icp_params &p, hipStream_t s, uint32_t b0, uint
 void icp_launch_gicp_moments (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);          // icp_gicp.hip: k_gicp_moments<robust?>
 void icp_launch_sym_moments (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);           // icp_symmetric.hip: k_sym_moments<robust?>
 void icp_launch_owner_search_dense (const icp_params &p, hipStream_t s);
+// icp_quality.hip: k_quality_pairs + k_quality_finish over the pairs a search has left in PF / PM (its own buffers: icp_evaluate), M the
+// moving sets [batch][m][8]; part [batch][ICP_QUALITY_TERMS][icp_p2pl_nblk (m)], cnt [batch][2][icp_p2pl_nblk (m)], res [batch][ICP_QUALITY_RES]
+void icp_launch_quality (const float4 *PF, const float4 *PM, const float *M, uint32_t m, uint32_t batch, bool dist_on, float d2, double *part, uint32_t *cnt,
+                         double *res, hipStream_t s);
 uint32_t icp_tbox_of (const icp_params &p);
 uint32_t icp_s2_wave_of (const icp_params &p);
 void icp_search_layout_of (const icp_params &p, int *dense, int *tile, int *stage2);   // what icp_launch_search selects          // 1: the dense search scans the lists with lanes = candidates (long lists)

@@ -2,6 +2,7 @@
 // k_plane_moments<COLORED> (icp_p2pl.hip) and k_plane_moments_robust<COLORED> (icp_robust.hip), which are plane_moments<COLORED, ROBUST>
 // below behind a __global__ name each; k_gicp_moments<ROBUST> (icp_gicp.hip) and k_sym_moments<ROBUST> (icp_symmetric.hip), which keep
 // what is their own and take the rest from here.  Also the intensity of a landmark, which k_color_grad_grid (icp_p2pl.hip) uses too.
+// k_quality_pairs (icp_quality.hip: icp_evaluate) takes G from plane_point_share and the tree, over its 22 terms, from plane_block_tree.
 // Every translation unit is built with -ffp-contract=off: each expression below is evaluated exactly in the order it is written;
 // tests/p2pl_ref.py, colored_ref.py, robust_ref.py, gicp_ref.py and sym_ref.py restate them.
 //
@@ -109,29 +110,31 @@ __device__ __forceinline__ void plane_emit (double (&v)[ICP_P2PL_TERMS], double 
     }
 }
 
-// The halving tree over the block's 256 pairs and the store of its 27 partials of registration b.  Every thread of the block calls it.
-__device__ __forceinline__ void plane_block_tree (double (&v)[ICP_P2PL_TERMS], double *part, uint32_t nblk, uint32_t b)
+// The halving tree over the block's 256 pairs and the store of its N partials of registration b (N = ICP_P2PL_TERMS for the plane
+// system, ICP_QUALITY_TERMS for icp_quality.hip).  Every thread of the block calls it.
+template <uint32_t N>
+__device__ __forceinline__ void plane_block_tree (double (&v)[N], double *part, uint32_t nblk, uint32_t b)
 {
     const uint32_t tid = threadIdx.x;
-    __shared__ double s[ICP_P2PL_TERMS][128];
+    __shared__ double s[N][128];
     if (tid >= 128u) {
 #pragma unroll
-        for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) s[t][tid - 128u] = v[t];
+        for (int t = 0; t < (int) N; ++t) s[t][tid - 128u] = v[t];
     }
     __syncthreads ();
     if (tid < 128u) {
 #pragma unroll
-        for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) v[t] = v[t] + s[t][tid];
+        for (int t = 0; t < (int) N; ++t) v[t] = v[t] + s[t][tid];
     }
     __syncthreads ();
     if (tid >= 64u && tid < 128u) {
 #pragma unroll
-        for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) s[t][tid - 64u] = v[t];
+        for (int t = 0; t < (int) N; ++t) s[t][tid - 64u] = v[t];
     }
     __syncthreads ();
     if (tid >= 64u) return;
 #pragma unroll
-    for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) {
+    for (int t = 0; t < (int) N; ++t) {
         double x = v[t] + s[t][tid];
 #pragma unroll
         for (int h = 32; h >= 1; h >>= 1) x = x + __shfl_down (x, (unsigned) h, 64);
@@ -139,7 +142,7 @@ __device__ __forceinline__ void plane_block_tree (double (&v)[ICP_P2PL_TERMS], d
     }
     if (tid == 0u) {
 #pragma unroll
-        for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) part[((size_t) b * ICP_P2PL_TERMS + t) * nblk + blockIdx.x] = v[t];
+        for (int t = 0; t < (int) N; ++t) part[((size_t) b * N + t) * nblk + blockIdx.x] = v[t];
     }
 }
 

@@ -2,6 +2,7 @@
 does (src/ocl_icp_reg.cpp:165-210) without the GL window: landmarks (getLMs), buildRBC, ICP::run, full-cloud
 transform of the moving cloud, and the same printout."""
 import argparse
+import inspect
 import math
 import time
 
@@ -26,6 +27,21 @@ def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, a
     between the two normals of a pair, with both frames' grid normals (ICPStep.set_normal_rejection with its cosine; None: off),
     reject_boundary: pairs whose fixed point lies at the boundary of the 128 wide landmark grid get weight 0
     (ICPStep.set_boundary_rejection); none is the reference's behaviour, all are off by default."""
+    return _register(None, **locals())[:4]
+
+
+def register_and_evaluate(fixed, moving, evaluate, **options):
+    """register_clouds (its options) with the registration's quality at the final transform: returns (T[8], k, latency_ms,
+    transformed moving cloud, Quality record) — fitness, inlier RMSE, information matrix and counts for pairs no farther apart than
+    `evaluate` mm (ICPStep.evaluate; 0 or None: no distance test)."""
+    bound = inspect.signature(register_clouds).bind(fixed, moving, **options)
+    bound.apply_defaults()
+    return _register(0.0 if evaluate is None else evaluate, **bound.arguments)
+
+
+def _register(evaluate, fixed, moving, device, a, c, max_iterations, angle_threshold, translation_threshold, reduce_mode, reject_invalid,
+              max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one, normal_angle, reject_boundary):
+    """(T[8], k, latency_ms, transformed moving cloud, Quality record or None): register_clouds' options; evaluate None: no evaluation."""
     reg = ICP(device)
     reg.init(16384, 256, a, c, max_iterations, angle_threshold, translation_threshold)   # src/ocl_icp_reg.cpp:81-88
     reg.setPowerMode(PowerMode.SQUARED)
@@ -66,9 +82,10 @@ def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, a
     k = reg.run()
     ms = (time.perf_counter() - t0) * 1e3
     T = reg.read(Memory.T)
+    quality = reg.evaluate(evaluate)[0] if evaluate is not None else None
     out = reg.transform_cloud(moving)
     reg.close()
-    return T, k, ms, out
+    return T, k, ms, out, quality
 
 
 def track(frames, device=0, a=2e2, c=1e-6, warm_start=False, **kw):
@@ -171,12 +188,19 @@ def main(argv=None):
     ap.add_argument("--symmetric", action="store_true",
                     help="symmetric ICP (Rusinkiewicz 2019): point-to-plane along the mean of both frames' grid normals, the rotation "
                          "split between the frames; implies --point-to-plane 0 when no MU is given (not reference behaviour)")
+    ap.add_argument("--evaluate", type=_point_weight, default=None, metavar="MAXDIST",
+                    help="after the run print the registration's fitness, inlier RMSE and inlier count at the final transform, for "
+                         "pairs no farther apart than MAXDIST mm (0: no distance test)")
     args = ap.parse_args(argv)
-    T, k, ms, out = register_clouds(load_pc8d(args.fixed), load_pc8d(args.moving), args.device, a=args.alpha,
-                                    reject_invalid=args.reject_invalid, max_dist=args.max_dist, trim=args.trim,
-                                    point_to_plane=args.point_to_plane, colored=args.colored, robust=args.robust,
-                                    plane_to_plane=args.plane_to_plane, symmetric=args.symmetric, one_to_one=args.one_to_one,
-                                    normal_angle=args.normal_angle, reject_boundary=args.reject_boundary)
+    fixed, moving = load_pc8d(args.fixed), load_pc8d(args.moving)
+    options = dict(device=args.device, a=args.alpha, reject_invalid=args.reject_invalid, max_dist=args.max_dist, trim=args.trim,
+                   point_to_plane=args.point_to_plane, colored=args.colored, robust=args.robust, plane_to_plane=args.plane_to_plane,
+                   symmetric=args.symmetric, one_to_one=args.one_to_one, normal_angle=args.normal_angle,
+                   reject_boundary=args.reject_boundary)
+    if args.evaluate is None:
+        (T, k, ms, out), quality = register_clouds(fixed, moving, **options), None
+    else:
+        T, k, ms, out, quality = register_and_evaluate(fixed, moving, args.evaluate, **options)
     q, t, s = T[:4], T[4:7], T[7]
     sinth_2 = float(np.linalg.norm(q[:3]))
     angle = 180.0 / math.pi * 2 * math.atan2(sinth_2, float(q[3]))
@@ -188,6 +212,10 @@ def main(argv=None):
     print("    Rotation axis         :    %s" % np.array2string(axis, precision=6))
     print("    Translation vector    :    %s" % np.array2string(t, precision=4))
     print("    Scale                 :    %g" % s)
+    if quality is not None:
+        print("    Fitness               :    %.6f" % quality.fitness)
+        print("    Inlier RMSE           :    %.6f mm" % quality.inlier_rmse)
+        print("    Inliers               :    %d of %d" % (quality.n_inliers, quality.n_moving))
     if args.output:
         save_pc8d(args.output, out)
 

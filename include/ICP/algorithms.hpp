@@ -764,6 +764,17 @@ namespace ICP
             return info.total ();
         }
 
+        /*! \brief Registration quality at the current transform (icp_evaluate, include/icp_amd.h): fitness, inlier RMSE and the
+         *         6 x 6 information matrix for pairs no farther apart than `max_dist` (0: no distance test).  Blocking; the handle's
+         *         options have no influence and nothing an iteration reads or writes is disturbed.  Open3D: evaluate_registration,
+         *         GetInformationMatrixFromPointClouds; PCL: getFitnessScore. */
+        icp_quality_t evaluate (float max_dist = 0.f)
+        {
+            icp_quality_t q;
+            this->check (icp_evaluate (this->h, max_dist, &q, 1));
+            return q;
+        }
+
         unsigned int getMaxIterations () { return max_iterations; }
         void setMaxIterations (unsigned int n) { this->check (icp_set_max_iterations (this->h, n)); max_iterations = n; }
         double getAngleThreshold () { return angle_threshold; }

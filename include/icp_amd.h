@@ -584,6 +584,47 @@ int icp_set_reduce_mode (icp_handle h, int mode);     /* icp_reduce_mode */
 int icp_state (icp_handle h, icp_state_t *out);
 int icp_state_b (icp_handle h, uint32_t batch_index, icp_state_t *out);
 
+/* Registration quality (Open3D: evaluate_registration and GetInformationMatrixFromPointClouds; PCL: getFitnessScore; not reference
+ * behaviour): what tells a caller whether the clouds overlap at the transform a run ended with — `converged` only says that the last
+ * increment was small.  Nothing runs unless the call is made: without it every kernel, launch, graph and bit is as before.  The rule:
+ *   - icp_evaluate measures registration b of a handle at its current cumulative transform: the state after the last executed
+ *     iteration, the one icp_state_b reports (after icp_write (ICP_MEM_T): that transform).  Its inputs are the handle's F, M, RBC and
+ *     alpha, and max_dist.
+ *   - One search of M against the RBC with that state: the same kernel family, layout and bits as an iteration's search would produce
+ *     at this T.  For every query i it gives e, the transformed moving point (what ICP_MEM_QT would hold), f, the returned fixed point
+ *     (what ICP_MEM_NN would hold), and the id.
+ *   - The handle's rejection, boundary and normal rules, one-to-one, trimming, robust loss, error metric and weighting have no
+ *     influence: quality is a property of (F, M, alpha, T, max_dist).
+ *   - geo_i = (ex - f0)^2 + (ey - f1)^2 + (ez - f2)^2 in fp32, summed in this order, with no contraction: the rejection rule's quantity.
+ *   - A moving point counts when M[i]'s own xyz is finite and not (0, 0, 0); n_moving is the number of such points.
+ *   - A pair is an inlier when its moving point counts, f is not (0, 0, 0), geo is finite and geo <= (float) ((double) max_dist *
+ *     max_dist); with max_dist 0 or +inf the last test is dropped.  n_inliers is their number.  Both counts are integer sums on the
+ *     device: independent of order.
+ *   - 22 sums in double on the device: sum_geo = sum (double) geo_i over the inliers, and the 21 upper-triangle terms, row-major, of
+ *     sum G (Q_i) over the inliers, Q = f converted to double, G the matrix of the point-to-plane rule about the point Q:
+ *     [[qq I - Q Q^T, [Q]x], [-[Q]x, I]], qq = (qx qx + qy qy) + qz qz — Open3D's G^T G with the rows (0, z, -y, 1, 0, 0),
+ *     (-z, 0, x, 0, 1, 0), (y, -x, 0, 0, 0, 1); rotation first, then translation, as in ICP_MEM_PLANE_SYSTEM.  A pair that is no inlier
+ *     contributes exact zeros (selected, not multiplied: a NaN coordinate makes no NaN).
+ *   - Both trees are the plane system's: a halving tree x[i] += x[i + h] inside blocks of 256 consecutive pairs, then a halving tree
+ *     over the block partials zero-padded to a power of two.  No atomics on the doubles; the result does not depend on the launch shape.
+ *   - On the host, in double: fitness = n_inliers / n_moving (0 when n_moving == 0), inlier_rmse = sqrt (sum_geo / n_inliers) (0 when
+ *     there is none), information[36] the symmetric 6 x 6, row-major.  n is m.
+ * The call blocks.  It first brings an open checked run to its end, as icp_read does.  One launch set — the search, the pair pass, a
+ * one-block pass per registration — serves all registrations of a batched handle; out receives the records of registrations
+ * 0 .. count - 1.  It disturbs nothing: the search writes into buffers of the evaluation's own (allocated at the first call), so the
+ * five per-query outputs of the last iteration, lazy outputs still to be reproduced, the registration state, the partials a later
+ * launch consumes and the cached graphs are as they were, and icp_step / icp_run behind it give the bits they would have given.
+ * Cost: the device work is one search plus one small pass; a blocking call — three launches, the copy of the result words, the wait —
+ * measured 40 us at |F| = 16384 beside a search stage of 9.0 us in the same run (icp_time_kernels).
+ * ICP_EINVAL: out NULL, count 0 or above the batch, max_dist negative or NaN.  ICP_ESTATE: before icp_build_rbc, and on a handle
+ * that has tracked a frame since icp_init / icp_track_reset — the quality of tracked frames is not provided.
+ * icp_batch_evaluate: the record of registration i of an icp_batch_* object (one icp_evaluate on its slot). */
+typedef struct {
+    double fitness, inlier_rmse, sum_geo, information[36];
+    uint32_t n, n_moving, n_inliers, reserved;
+} icp_quality_t;
+int icp_evaluate (icp_handle h, float max_dist, icp_quality_t *out, uint32_t count);
+
 /* ---- adjacent steps -------------------------------------------------------------- */
 
 /* ICPLMs: getLMs — kernels/icp_kernels.cl:63-76, src/ICP/algorithms.cpp:621-785.
@@ -770,6 +811,7 @@ int icp_batch_run (icp_batch_handle b);                                         
 int icp_batch_run_fixed (icp_batch_handle b, uint32_t iterations, int from_identity);
 int icp_batch_state (icp_batch_handle b, uint32_t i, icp_state_t *out);
 int icp_batch_read (icp_batch_handle b, uint32_t i, int mem, void *host_dst, size_t bytes);
+int icp_batch_evaluate (icp_batch_handle b, uint32_t i, float max_dist, icp_quality_t *out);   /* icp_evaluate: the record of registration i */
 int icp_batch_size (icp_batch_handle b, uint32_t *registrations, uint32_t *n_slots);
 /* wall-clock seconds of `reps` fixed-length passes (from the identity) on all slots at once = max over devices */
 int icp_batch_time_run_fixed (icp_batch_handle b, uint32_t iterations, uint32_t reps, double *seconds);
