@@ -7,7 +7,7 @@
 //   registration A B                      data/A.bin, data/B.bin — or A and B themselves when they name existing files
 //   ... [--out FILE] [--device N] [--reference-order] [--svd] [--reject-invalid] [--max-dist MM] [--trim FRACTION]
 //       [--point-to-plane MU] [--colored KAPPA] [--robust KIND:SCALE] [--plane-to-plane EPS] [--symmetric] [--one-to-one]
-//       [--evaluate MAXDIST]
+//       [--evaluate MAXDIST] [--pyramid LEVELS[:MAXDZ]]
 //
 // --reject-invalid / --max-dist: correspondence rejection (icp_set_rejection: pairs with a pixel without depth at either end / pairs
 // farther apart than MM get weight 0).  --trim: trimmed ICP (icp_set_trimming: every iteration keeps the closest FRACTION in (0, 1] of the
@@ -22,6 +22,9 @@
 // --one-to-one: one-to-one correspondences (icp_set_unique): of the pairs that share a fixed point only the closest keeps its weight.
 // --evaluate: after the run, the registration's quality at the final transform (icp_evaluate): fitness, inlier RMSE and the inlier
 // count for pairs no farther apart than MAXDIST mm (0: no distance test).
+// --pyramid: coarse-to-fine registration (icp_pyramid_*): LEVELS landmark grids 128, 64, 32, .. wide with 256, 64, 64, .. representatives,
+// coarsest first, each level made of 2 x 2 means of the one below it (points within MAXDZ mm in z of the block's first valid point,
+// doubling per level; default 0: no band); the other options apply to every level, with the level's own grid width.
 // Not the reference's behaviour; off by default.
 //
 // A cloud file is 640 x 480 points of 8 floats [x y z 1 r g b 1], little endian, row-major (src/kinect_frame_grabber.cpp:252-272).
@@ -85,6 +88,57 @@ int run (int device, icp::Mode mode, const std::vector<icp_float8> &pc1, const s
     return 0;
 }
 
+void check_level (icp_handle h, int rc) { if (rc != ICP_OK) throw std::runtime_error (std::string ("level: ") + icp_last_error (h)); }
+
+// the same registration through cl_algo::ICP::ICPPyramid: the options on every level's handle, the level's own grid width
+template <cl_algo::ICP::ICPStepConfigT RC>
+int run_pyramid (int device, icp::Mode mode, unsigned levels, float max_dz, const std::vector<icp_float8> &pc1, const std::vector<icp_float8> &pc2, const std::string &out,
+                 int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa, icp::RobustLoss robust, float gicp_eps, bool symmetric, bool one_to_one,
+                 float evaluate)
+{
+    cl_algo::ICP::ICPPyramid<RC, cl_algo::ICP::ICPStepConfigW::WEIGHTED> pyr (icp::Env (device), mode);
+    std::vector<uint32_t> nr (levels, 64u); nr[0] = 256u;
+    pyr.init (16384, nr, 2e2f, 1e-6f);                       // (the demo's parameters: src/ocl_icp_reg.cpp:82-88)
+    pyr.setReduction (ICP_PYRAMID_MEAN, max_dz);
+    for (unsigned l = 0; l < levels; ++l) {
+        icp_handle h = pyr.level (l);
+        const uint32_t gw = 128u >> l;
+        if (reject_flags || max_dist > 0.f) check_level (h, icp_set_rejection (h, reject_flags, max_dist));
+        if (one_to_one) check_level (h, icp_set_unique (h, 1));
+        if (trim != 1.f) check_level (h, icp_set_trimming (h, trim));
+        if (robust.loss != icp::RobustLoss::NONE) check_level (h, icp_set_robust_loss (h, robust.loss, robust.scale));
+        if (gicp_eps > 0.f) check_level (h, icp_set_plane_to_plane (h, gicp_eps));
+        if (symmetric) check_level (h, icp_set_symmetric (h, 1));
+        if (kappa >= 0.f) {
+            check_level (h, icp_set_normals (h, ICP_NORMALS_GRID, gw)); check_level (h, icp_set_color_weight (h, kappa));
+            check_level (h, icp_set_error_metric (h, ICP_METRIC_COLORED, p2pl_mu >= 0.f ? p2pl_mu : 0.f));
+        }
+        else if (p2pl_mu >= 0.f) { check_level (h, icp_set_normals (h, ICP_NORMALS_GRID, gw)); check_level (h, icp_set_error_metric (h, ICP_METRIC_POINT_TO_PLANE, p2pl_mu)); }
+    }
+    pyr.writeCloud (ICP_MEM_F, pc1.data ());
+    pyr.writeCloud (ICP_MEM_M, pc2.data ());
+    pyr.buildRBC ();
+    pyr.sync ();
+    pyr.run ();
+    std::printf ("\n    q = (%.9g, %.9g, %.9g, %.9g)   t = (%.9g, %.9g, %.9g)   s = %.9g   k =",
+                 pyr.q.x (), pyr.q.y (), pyr.q.z (), pyr.q.w (), pyr.t (0), pyr.t (1), pyr.t (2), pyr.s);
+    for (unsigned l = 0; l < levels; ++l) std::printf (" %u", pyr.k[l]);
+    std::printf ("   (per level, finest first)\n");
+    if (evaluate >= 0.f) {
+        const icp_quality_t q = pyr.evaluate (evaluate);
+        std::printf ("    fitness = %.6f   inlier RMSE = %.6f mm   inliers = %u of %u\n", q.fitness, q.inlier_rmse, q.n_inliers, q.n_moving);
+    }
+    if (!out.empty ()) {
+        std::vector<icp_float8> moved (kPoints);
+        check_level (pyr.level (0), icp_transform_cloud (pyr.level (0), pc2.data (), moved.data (), (uint32_t) kPoints));
+        std::ofstream f (out, std::ios::binary);
+        f.write (reinterpret_cast<const char *> (moved.data ()), (std::streamsize) (kPoints * sizeof (icp_float8)));
+        if (!f) throw std::runtime_error ("cannot write " + out);
+        std::printf ("    transformed cloud     :    %s\n", out.c_str ());
+    }
+    return 0;
+}
+
 }  // namespace
 
 int main (int argc, char **argv)
@@ -94,6 +148,7 @@ int main (int argc, char **argv)
     int device = 0; bool svd = false, symmetric = false, one_to_one = false;
     int reject_flags = 0; float max_dist = 0.f, trim = 1.f, p2pl_mu = -1.f, kappa = -1.f, gicp_eps = 0.f, evaluate = -1.f;     // (p2pl_mu < 0: point-to-point; kappa < 0: not colored; gicp_eps 0: off; evaluate < 0: no quality report)
     icp::RobustLoss robust;
+    unsigned pyramid_levels = 0; float pyramid_dz = 0.f;       // (0 levels: one level, no pyramid object)
     icp::Mode mode = icp::Mode::FAST;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -122,6 +177,19 @@ int main (int argc, char **argv)
         else if (a == "--evaluate" && i + 1 < argc) {
             evaluate = std::strtof (argv[++i], nullptr);
             if (!(evaluate >= 0.f)) { std::fprintf (stderr, "--evaluate: MAXDIST must be >= 0\n"); return 2; }
+        }
+        else if (a == "--pyramid" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            const size_t c = v.find (':');
+            char *end = nullptr;
+            const long n = std::strtol (v.c_str (), &end, 10);
+            const bool levels_ok = end != v.c_str () && (*end == 0 || *end == ':') && n >= 1 && n <= ICP_PYRAMID_MAX_LEVELS;
+            char *dend = nullptr;
+            pyramid_dz = c == std::string::npos ? 0.f : std::strtof (v.c_str () + c + 1, &dend);
+            if (!levels_ok || (c != std::string::npos && (dend == v.c_str () + c + 1 || *dend)) || !(pyramid_dz >= 0.f && std::isfinite (pyramid_dz))) {
+                std::fprintf (stderr, "--pyramid: LEVELS[:MAXDZ] with LEVELS in [1, 5] and MAXDZ finite and >= 0\n"); return 2;
+            }
+            pyramid_levels = (unsigned) n;
         }
         else if (a == "--symmetric") symmetric = true;
         else if (a == "--one-to-one") one_to_one = true;
@@ -152,6 +220,9 @@ int main (int argc, char **argv)
         } else {
             read_cloud (data_path (names[0]), pc1); read_cloud (data_path (names[1]), pc2);
         }
+        if (pyramid_levels)
+            return svd ? run_pyramid<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pyramid_levels, pyramid_dz, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, evaluate)
+                       : run_pyramid<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pyramid_levels, pyramid_dz, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, evaluate);
         return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, evaluate)
                    : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, evaluate);
     }

@@ -233,6 +233,23 @@ def lib():
     sig("icp_batch_time_run_fixed_slots", i32, vp, u32, u32, u32, C.POINTER(f64), vp)
     sig("icp_batch_partition", i32, u32, u32, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32))
     sig("icp_batch_last_error", C.c_char_p, vp)
+    sig("icp_pyramid_create", i32, C.POINTER(vp), i32, i32, i32)
+    sig("icp_pyramid_destroy", i32, vp)
+    sig("icp_pyramid_init", i32, vp, u32, u32, C.POINTER(u32), f32, f32, C.POINTER(u32), f64, f64)
+    sig("icp_pyramid_set_reduction", i32, vp, i32, f32)
+    sig("icp_pyramid_get_reduction", i32, vp, C.POINTER(i32), C.POINTER(f32))
+    sig("icp_pyramid_levels", i32, vp, C.POINTER(u32))
+    sig("icp_pyramid_level", i32, vp, u32, C.POINTER(vp))
+    sig("icp_pyramid_write", i32, vp, i32, vp, i32)
+    sig("icp_pyramid_write_cloud", i32, vp, i32, vp, i32)
+    sig("icp_pyramid_reset_transform", i32, vp)
+    sig("icp_pyramid_build_rbc", i32, vp)
+    sig("icp_pyramid_run", i32, vp, C.POINTER(u32))
+    sig("icp_pyramid_run_fixed", i32, vp, C.POINTER(u32))
+    sig("icp_pyramid_sync", i32, vp)
+    sig("icp_pyramid_pending", i32, vp, C.POINTER(i32))
+    sig("icp_pyramid_time_build", i32, vp, i32, u32, C.POINTER(f32))
+    sig("icp_pyramid_last_error", C.c_char_p, vp)
     sig("icp_time_run_fixed", i32, vp, u32, u32, i32, C.POINTER(f32))
     sig("icp_time_run_fixed_tail", i32, vp, u32, u32, i32, C.POINTER(f32), C.POINTER(u32))
     sig("icp_reset_transform", i32, vp)
@@ -1274,3 +1291,164 @@ class ICPBatch:
         out = np.empty(nbytes // np.dtype(dt).itemsize, dt)
         self._chk(self._L.icp_batch_read(self._b, i, mem, _p(out), nbytes))
         return out.reshape(-1, cols) if cols else out
+
+
+class PyramidReduction:          # icp_pyramid_set_reduction (include/icp_amd.h)
+    MEAN, PICK = 0, 1
+
+
+PYRAMID_MAX_LEVELS = 5            # ICP_PYRAMID_MAX_LEVELS
+
+
+class _PyramidLevel(ICP):
+    """The borrowed handle of a pyramid level as an ICP object: every setter, getter, read, state() and evaluate() of ICP; it never
+    destroys the handle (close() only lets go of it).  Not for init, writes of F / M, adoption or tracking (include/icp_amd.h)."""
+
+    def __init__(self, handle, m, nr, max_iterations, angle_threshold, translation_threshold):
+        self._L = lib()
+        self._h = handle
+        self.m, self.nr, self.batch = m, nr, 1
+        self._max_it, self._ang, self._tra = max_iterations, angle_threshold, translation_threshold
+
+    def close(self):
+        self._h = None
+
+    def _refuse(self, what):
+        raise ICPError(4, "%s would take the pyramid's levels apart: use ICPPyramid (include/icp_amd.h, icp_pyramid_level)" % what)
+
+    def init(self, *args, **kwargs):
+        self._refuse("init of a level")
+
+    def write(self, mem=Memory.D_IN_F, ptr=None, block=False, batch_index=0):
+        if mem in (Memory.F, Memory.M):
+            self._refuse("a write of F or M into a level")
+        super().write(mem, ptr, block, batch_index)
+
+    def write_cloud(self, which, cloud):
+        self._refuse("write_cloud into a level")
+
+    def track_next(self, *args, **kwargs):
+        self._refuse("tracking on a level")
+
+    track_submit = track_collect = track_staging = track_register = track_unregister = track_pipelined = track_reset = track_next
+
+
+class ICPPyramid:
+    """Coarse-to-fine registration (icp_pyramid_*, include/icp_amd.h): one engine handle per level on one device, the levels of F and M
+    built on the device from level 0 by one launch, T handed from each level to the next finer one on the device.  The result is level
+    0's: level(0).read(Memory.T), level(0).state(), level(0).evaluate()."""
+
+    def __init__(self, device=0, CR=ICPStepConfigT.POWER_METHOD, CW=ICPStepConfigW.WEIGHTED):
+        self._L = lib()
+        self._p = C.c_void_p()
+        rc = self._L.icp_pyramid_create(C.byref(self._p), device, CR, CW)
+        if rc:
+            msg = self._L.icp_pyramid_last_error(None).decode()
+            self._p = None
+            raise ICPError(rc, msg)
+        self.levels = self.m = self.side = 0
+        self._levels = []
+
+    def _chk(self, rc):
+        if rc:
+            raise ICPError(rc, self._L.icp_pyramid_last_error(self._p).decode())
+
+    def close(self):
+        if getattr(self, "_p", None):
+            for lv in self._levels:
+                lv.close()
+            self._levels = []
+            self._L.icp_pyramid_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def init(self, m, nr, a=1e2, c=1e-6, max_iterations=40, angle_threshold=0.001, translation_threshold=0.01):
+        """nr: one count per level, finest first (its length is the number of levels); max_iterations: one number for all levels or
+        one per level."""
+        nr = [int(v) for v in nr]
+        levels = len(nr)
+        its = [int(max_iterations)] * levels if np.isscalar(max_iterations) else [int(v) for v in max_iterations]
+        if len(its) != levels:
+            raise ValueError("max_iterations: expected %d entries, got %d" % (levels, len(its)))
+        for lv in self._levels:
+            lv.close()
+        self._levels = []
+        self.levels = 0
+        self._chk(self._L.icp_pyramid_init(self._p, levels, m, (C.c_uint32 * max(levels, 1))(*nr), a, c,
+                                           (C.c_uint32 * max(levels, 1))(*its), angle_threshold, translation_threshold))
+        self.levels, self.m, self.side = levels, m, int(round(m ** 0.5))
+        for l in range(levels):
+            h = C.c_void_p()
+            self._chk(self._L.icp_pyramid_level(self._p, l, C.byref(h)))
+            self._levels.append(_PyramidLevel(h, (self.side >> l) ** 2, nr[l], its[l], angle_threshold, translation_threshold))
+
+    def level(self, l):
+        """The ICP object over the borrowed handle of level l (0: the finest)."""
+        if not 0 <= l < self.levels:
+            h = C.c_void_p()
+            self._chk(self._L.icp_pyramid_level(self._p, l if l >= 0 else 0xFFFFFFFF, C.byref(h)))
+        return self._levels[l]
+
+    def set_reduction(self, kind=PyramidReduction.MEAN, max_dz=0.0):
+        """How a level is made from the one below it: MEAN (of the valid points of each 2 x 2 block within max_dz * 2^(l-1) of the first
+        valid one in z; 0 or inf: no band) or PICK (the block's first point).  Takes effect at the next write."""
+        self._chk(self._L.icp_pyramid_set_reduction(self._p, kind, max_dz))
+
+    def reduction(self):
+        k, z = C.c_int(), C.c_float()
+        self._chk(self._L.icp_pyramid_get_reduction(self._p, C.byref(k), C.byref(z)))
+        return k.value, z.value
+
+    def write(self, mem, ptr=None, block=False):
+        arr = None
+        if ptr is not None:
+            arr = np.ascontiguousarray(ptr, dtype=np.float32)
+            want = _write_floats(mem, self.m)
+            if arr.size != want:
+                raise ValueError("write(%d): expected %d floats, got %d" % (mem, want, arr.size))
+        self._chk(self._L.icp_pyramid_write(self._p, mem, _p(arr) if arr is not None else None, int(block)))
+
+    def write_cloud(self, which, cloud, block=False):
+        arr = np.ascontiguousarray(cloud, dtype=np.float32)
+        if arr.size != 640 * 480 * 8:
+            raise ValueError("write_cloud: expected a 640 x 480 x 8 cloud")
+        self._chk(self._L.icp_pyramid_write_cloud(self._p, which, _p(arr), int(block)))
+
+    def buildRBC(self):
+        self._chk(self._L.icp_pyramid_build_rbc(self._p))
+
+    def run(self):
+        """A checked run per level, coarsest first (blocking); returns the iteration counts, finest first."""
+        k = (C.c_uint32 * PYRAMID_MAX_LEVELS)()
+        self._chk(self._L.icp_pyramid_run(self._p, k))
+        return [int(v) for v in k[:self.levels]]
+
+    def run_fixed(self, iterations):
+        """Exactly iterations[l] steps per level (finest first); enqueue only — sync() waits."""
+        its = [int(v) for v in iterations]
+        if len(its) != self.levels:
+            raise ValueError("run_fixed: expected %d counts, got %d" % (self.levels, len(its)))
+        self._chk(self._L.icp_pyramid_run_fixed(self._p, (C.c_uint32 * max(len(its), 1))(*its)))
+
+    def reset_transform(self):
+        self._chk(self._L.icp_pyramid_reset_transform(self._p))
+
+    def sync(self):
+        self._chk(self._L.icp_pyramid_sync(self._p))
+
+    def pending(self):
+        """True while what the last run_fixed enqueued is still in flight (a query, not a wait)."""
+        v = C.c_int()
+        self._chk(self._L.icp_pyramid_pending(self._p, C.byref(v)))
+        return bool(v.value)
+
+    def time_build(self, mem=Memory.F, reps=20):
+        """Mean ms of the construction launch of F or M alone (HIP events around it)."""
+        ms = C.c_float()
+        self._chk(self._L.icp_pyramid_time_build(self._p, mem, reps, C.byref(ms)))
+        return ms.value

@@ -192,6 +192,15 @@ int cloud_reserve (icp_context *h, uint32_t n)
 
 }  // namespace
 
+// plane-to-plane, symmetric or normal rejection with ICP_NORMALS_GRID: the moving normals of registrations b0 .. b0 + nb - 1 follow a new M, in stream order behind its copy
+// (a width that does not divide m: nothing — icp_build_rbc refuses the handle anyway)
+namespace icp_host {
+void normals_m_follow (icp_context *h, uint32_t b0, uint32_t nb)
+{
+    if (icp_moving_normals (h->p) && h->p.nrm_grid && h->p.m % h->p.nrm_grid == 0u) icp_launch_normals_m (h->p, h->stream, b0, nb);
+}
+}  // namespace icp_host
+
 extern "C" {
 
 const char *icp_version (void) { return "icp_amd 0.1 (gfx950)"; }
@@ -280,13 +289,6 @@ int icp_destroy (icp_handle h) try
     return ICP_OK;
 }
 ICP_CATCH_ALL
-
-// plane-to-plane, symmetric or normal rejection with ICP_NORMALS_GRID: the moving normals of registrations b0 .. b0 + nb - 1 follow a new M, in stream order behind its copy
-// (a width that does not divide m: nothing — icp_build_rbc refuses the handle anyway)
-static void normals_m_follow (icp_context *h, uint32_t b0, uint32_t nb)
-{
-    if (icp_moving_normals (h->p) && h->p.nrm_grid && h->p.m % h->p.nrm_grid == 0u) icp_launch_normals_m (h->p, h->stream, b0, nb);
-}
 
 int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, float a, float c,
                       uint32_t max_iterations, double angle_threshold, double translation_threshold) try

@@ -237,6 +237,9 @@ void note_enqueue (icp_context *h);
 void note_inputs_change (icp_context *h);
 void note_outputs_stored (icp_context *h);
 int materialize_outputs (icp_context *h, int mem);
+// ---- icp_capi.hip ---------------------------------------------------------------------------------------------------------------
+// what every write of M does behind its copy (icp_write, icp_write_cloud, icp_pyramid_write): with ICP_NORMALS_GRID the moving normals follow
+void normals_m_follow (icp_context *h, uint32_t b0, uint32_t nb);
 
 // Captures the launches `launches ()` enqueues on the handle's stream into a graph (instantiate: also into an executable one).
 // Whatever fails, the stream has left capture mode and nothing is leaked when this returns.

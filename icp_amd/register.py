@@ -8,14 +8,14 @@ import time
 
 import numpy as np
 
-from . import ICP, ErrorMetric, Memory, Normals, PowerMode, ReduceMode, RobustLoss
+from . import ICP, ErrorMetric, ICPPyramid, Memory, Normals, PowerMode, PyramidReduction, ReduceMode, RobustLoss
 from .io import load_pc8d, save_pc8d
 
 
 def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, angle_threshold=0.001,
                     translation_threshold=0.01, reduce_mode=ReduceMode.FUSED, reject_invalid=False, max_dist=None, trim=1.0,
                     point_to_plane=None, colored=None, robust=None, plane_to_plane=None, symmetric=False, one_to_one=False,
-                    normal_angle=None, reject_boundary=False):
+                    normal_angle=None, reject_boundary=False, pyramid=None):
     """Returns (T[8], k, latency_ms, transformed moving cloud).  reject_invalid / max_dist: correspondence rejection
     (ICPStep.set_rejection), trim: the fraction of pairs trimmed ICP keeps (ICPStep.set_trimming; 1.0: off), point_to_plane: mu of
     point-to-plane ICP with the fixed frame's normals from its 128 x 128 landmark grid (ICPStep.set_error_metric; None: off),
@@ -26,7 +26,10 @@ def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, a
     pairs that share a fixed point only the closest keeps its weight (ICPStep.set_unique), normal_angle: the largest angle in degrees
     between the two normals of a pair, with both frames' grid normals (ICPStep.set_normal_rejection with its cosine; None: off),
     reject_boundary: pairs whose fixed point lies at the boundary of the 128 wide landmark grid get weight 0
-    (ICPStep.set_boundary_rejection); none is the reference's behaviour, all are off by default."""
+    (ICPStep.set_boundary_rejection); pyramid: (levels, max_dz) of a coarse-to-fine registration (ICPPyramid: 128, 64, 32, .. wide
+    levels with 256, 64, 64, .. representatives, 2 x 2 means within a z band of max_dz mm, 0: no band; every option above applies to
+    every level with the level's own grid width; k is then the list of the levels' counts, finest first; None: one level); none is
+    the reference's behaviour, all are off by default."""
     return _register(None, **locals())[:4]
 
 
@@ -39,19 +42,23 @@ def register_and_evaluate(fixed, moving, evaluate, **options):
     return _register(0.0 if evaluate is None else evaluate, **bound.arguments)
 
 
-def _register(evaluate, fixed, moving, device, a, c, max_iterations, angle_threshold, translation_threshold, reduce_mode, reject_invalid,
-              max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one, normal_angle, reject_boundary):
-    """(T[8], k, latency_ms, transformed moving cloud, Quality record or None): register_clouds' options; evaluate None: no evaluation."""
-    reg = ICP(device)
-    reg.init(16384, 256, a, c, max_iterations, angle_threshold, translation_threshold)   # src/ocl_icp_reg.cpp:81-88
+def pyramid_nr(levels):
+    """Representatives per level of the 128 wide landmark grid, finest first: 256, 64, 64, .."""
+    return [256] + [64] * (levels - 1)
+
+
+def _apply_options(reg, side, reduce_mode, reject_invalid, max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric,
+                   one_to_one, normal_angle, reject_boundary):
+    """register_clouds' options on one handle whose landmark grid is `side` wide (640 x 480 clouds -> 128 x 128 landmarks, row-major;
+    a pyramid level l: 128 >> l)."""
     reg.setPowerMode(PowerMode.SQUARED)
     reg.setReduceMode(reduce_mode)
     if reject_invalid or max_dist:
         reg.set_rejection(reject_invalid, max_dist)
     if reject_boundary:
-        reg.set_boundary_rejection(128)                        # (640 x 480 clouds -> 128 x 128 landmarks, row-major)
+        reg.set_boundary_rejection(side)
     if normal_angle is not None:
-        reg.set_normals(Normals.GRID, 128)
+        reg.set_normals(Normals.GRID, side)
         reg.set_normal_rejection(normal_cosine(normal_angle))
     if one_to_one:
         reg.set_unique(True)
@@ -68,12 +75,32 @@ def _register(evaluate, fixed, moving, device, a, c, max_iterations, angle_thres
         if point_to_plane is None:
             point_to_plane = 0.0                               # (the symmetric objective acts in the point-to-plane metric)
     if colored is not None:
-        reg.set_normals(Normals.GRID, 128)
+        reg.set_normals(Normals.GRID, side)
         reg.set_color_weight(colored)
         reg.set_error_metric(ErrorMetric.COLORED, 0.0 if point_to_plane is None else point_to_plane)
     elif point_to_plane is not None:
-        reg.set_normals(Normals.GRID, 128)                     # (640 x 480 clouds -> 128 x 128 landmarks, row-major)
+        reg.set_normals(Normals.GRID, side)
         reg.set_error_metric(ErrorMetric.POINT_TO_PLANE, point_to_plane)
+
+
+def _register(evaluate, fixed, moving, device, a, c, max_iterations, angle_threshold, translation_threshold, reduce_mode, reject_invalid,
+              max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one, normal_angle, reject_boundary,
+              pyramid=None):
+    """(T[8], k, latency_ms, transformed moving cloud, Quality record or None): register_clouds' options; evaluate None: no evaluation."""
+    options = (reduce_mode, reject_invalid, max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one,
+               normal_angle, reject_boundary)
+    if pyramid is not None:
+        levels, max_dz = pyramid
+        reg = ICPPyramid(device)
+        reg.init(16384, pyramid_nr(levels), a, c, max_iterations, angle_threshold, translation_threshold)
+        reg.set_reduction(PyramidReduction.MEAN, max_dz)
+        for l in range(levels):
+            _apply_options(reg.level(l), 128 >> l, *options)
+        result = reg.level(0)
+    else:
+        reg = result = ICP(device)
+        reg.init(16384, 256, a, c, max_iterations, angle_threshold, translation_threshold)   # src/ocl_icp_reg.cpp:81-88
+        _apply_options(reg, 128, *options)
     reg.write_cloud(Memory.F, fixed)
     reg.write_cloud(Memory.M, moving)
     reg.buildRBC()
@@ -81,9 +108,9 @@ def _register(evaluate, fixed, moving, device, a, c, max_iterations, angle_thres
     t0 = time.perf_counter()
     k = reg.run()
     ms = (time.perf_counter() - t0) * 1e3
-    T = reg.read(Memory.T)
-    quality = reg.evaluate(evaluate)[0] if evaluate is not None else None
-    out = reg.transform_cloud(moving)
+    T = result.read(Memory.T)
+    quality = result.evaluate(evaluate)[0] if evaluate is not None else None
+    out = result.transform_cloud(moving)
     reg.close()
     return T, k, ms, out, quality
 
@@ -151,6 +178,18 @@ def _robust(s):
     return RobustLoss.NAMES[kind.lower()], v
 
 
+def _pyramid(s):
+    """LEVELS[:MAXDZ], e.g. 3 or 3:24 -> (levels, max_dz); LEVELS in [1, 5], MAXDZ finite and >= 0 (mm; 0: no band)."""
+    levels, sep, dz = s.partition(":")
+    try:
+        n, v = int(levels), float(dz) if sep else 0.0
+    except ValueError:
+        raise argparse.ArgumentTypeError("must be LEVELS[:MAXDZ], got %s" % s)
+    if not 1 <= n <= 5 or not (v >= 0.0 and math.isfinite(v)):
+        raise argparse.ArgumentTypeError("LEVELS must be in [1, 5] and MAXDZ finite and >= 0, got %s" % s)
+    return n, v
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("fixed")
@@ -191,12 +230,16 @@ def main(argv=None):
     ap.add_argument("--evaluate", type=_point_weight, default=None, metavar="MAXDIST",
                     help="after the run print the registration's fitness, inlier RMSE and inlier count at the final transform, for "
                          "pairs no farther apart than MAXDIST mm (0: no distance test)")
+    ap.add_argument("--pyramid", type=_pyramid, default=None, metavar="LEVELS[:MAXDZ]",
+                    help="coarse-to-fine: register on LEVELS landmark grids (128, 64, 32, .. wide; 256, 64, 64, .. representatives), "
+                         "coarsest first, each level made of 2 x 2 means of the one below it (points within MAXDZ mm in z, doubling "
+                         "per level; default 0: no band); the other options apply to every level (not reference behaviour)")
     args = ap.parse_args(argv)
     fixed, moving = load_pc8d(args.fixed), load_pc8d(args.moving)
     options = dict(device=args.device, a=args.alpha, reject_invalid=args.reject_invalid, max_dist=args.max_dist, trim=args.trim,
                    point_to_plane=args.point_to_plane, colored=args.colored, robust=args.robust, plane_to_plane=args.plane_to_plane,
                    symmetric=args.symmetric, one_to_one=args.one_to_one, normal_angle=args.normal_angle,
-                   reject_boundary=args.reject_boundary)
+                   reject_boundary=args.reject_boundary, pyramid=args.pyramid)
     if args.evaluate is None:
         (T, k, ms, out), quality = register_clouds(fixed, moving, **options), None
     else:
@@ -206,7 +249,7 @@ def main(argv=None):
     angle = 180.0 / math.pi * 2 * math.atan2(sinth_2, float(q[3]))
     axis = q[:3] / sinth_2 if sinth_2 else np.zeros(3)
     print("\n================\n")                                     # src/ocl_icp_reg.cpp:199-206
-    print("    Iterations            :    %d" % k)
+    print("    Iterations            :    %s" % (k if args.pyramid is None else " + ".join("%d" % v for v in k) + "  (per level, finest first)"))
     print("    Latency               :    %.3f ms" % ms)
     print("    Rotation angle        :    %g degrees" % angle)
     print("    Rotation axis         :    %s" % np.array2string(axis, precision=6))

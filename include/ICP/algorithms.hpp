@@ -824,6 +824,83 @@ namespace ICP
         bool warm_start;   /*!< start every registration from the previous hop's transform instead of the identity */
         bool registered;   /*!< the last collected frame had a predecessor */
     };
+
+    /*! \brief Coarse-to-fine registration (icp_pyramid_*, include/icp_amd.h; Open3D: multi_scale_icp): one engine handle per level
+     *         on one device, the levels of F and M built on the device from level 0 (`side >> l` points a side, 2 x 2 means or
+     *         picks), the coarsest level run first and every finer one started from the transform of the level above it — the
+     *         hand-over happens on the device.  `run` is blocking and leaves level 0's `R q t s` and every level's count in `k`
+     *         (finest first); `runFixed` only enqueues.  `level (l)` is the borrowed C handle of a level for the per-level setters
+     *         (icp_set_error_metric, icp_set_normals with the level's own grid width `side >> l`, ..), icp_read and icp_evaluate;
+     *         it must not be initialised, destroyed or written F / M through.  The reference has no such class.
+     */
+    template <ICPStepConfigT CR, ICPStepConfigW CW>
+    class ICPPyramid
+    {
+    public:
+        ICPPyramid (icp::Env _env, icp::Mode _mode = icp::Mode::FAST) : s (1.f), p (nullptr), mode (_mode)
+        {
+            static_assert (CR != ICPStepConfigT::JACOBI, "JACOBI is a \\todo in the reference as well");
+            int rc = icp_pyramid_create (&p, _env.device, CR == ICPStepConfigT::POWER_METHOD ? ICP_ROT_POWER_METHOD : ICP_ROT_EIGEN,
+                                         CW == ICPStepConfigW::WEIGHTED ? ICP_W_WEIGHTED : ICP_W_REGULAR);
+            if (rc != ICP_OK) throw std::runtime_error (std::string ("ICPPyramid: ") + icp_pyramid_last_error (nullptr));
+        }
+        ICPPyramid (const ICPPyramid&) = delete;
+        ICPPyramid& operator= (const ICPPyramid&) = delete;
+        ~ICPPyramid () { if (p) icp_pyramid_destroy (p); }
+
+        /*! \brief `_nr` and `_max_iterations` hold one entry per level, finest first; `_nr.size ()` is the number of levels. */
+        void init (unsigned int _m, const std::vector<uint32_t> &_nr, float _a = 1e2f, float _c = 1e-6f, const std::vector<uint32_t> &_max_iterations = {},
+                   double _angle_threshold = 0.001, double _translation_threshold = 0.01)
+        {
+            std::vector<uint32_t> its = _max_iterations.empty () ? std::vector<uint32_t> (_nr.size (), 40u) : _max_iterations;
+            if (its.size () != _nr.size ()) throw std::runtime_error ("ICPPyramid::init: one max_iterations entry per level");
+            check (icp_pyramid_init (p, (uint32_t) _nr.size (), _m, _nr.data (), _a, _c, its.data (), _angle_threshold, _translation_threshold));
+            k.assign (_nr.size (), 0u);
+            for (uint32_t l = 0; l < _nr.size (); ++l) {
+                icp_handle h = level (l);
+                checkLevel (h, icp_set_reduce_mode (h, mode == icp::Mode::FAST ? ICP_REDUCE_FUSED : ICP_REDUCE_REFERENCE_ORDER));
+                checkLevel (h, icp_set_power_mode (h, mode == icp::Mode::FAST ? ICP_POWER_SQUARED : ICP_POWER_LITERAL));
+            }
+        }
+        unsigned int levels () { uint32_t n = 0; check (icp_pyramid_levels (p, &n)); return n; }
+        icp_handle level (unsigned int l) { icp_handle h = nullptr; check (icp_pyramid_level (p, l, &h)); return h; }
+        /*! \brief ICP_PYRAMID_MEAN (max_dz: the z band of a block at the first transition, doubling per level; 0: none) or ICP_PYRAMID_PICK. */
+        void setReduction (int kind, float max_dz = 0.f) { check (icp_pyramid_set_reduction (p, kind, max_dz)); }
+        void getReduction (int &kind, float &max_dz) { check (icp_pyramid_get_reduction (p, &kind, &max_dz)); }
+        /*! \brief mem: ICP_MEM_F / ICP_MEM_M (level 0's points; the coarser levels follow on the device) or ICP_MEM_T (the coarsest level's start). */
+        void write (int mem, const void *ptr, bool block = false) { check (icp_pyramid_write (p, mem, ptr, block ? 1 : 0)); }
+        void writeCloud (int which, const void *cloud_640x480x8, bool block = false) { check (icp_pyramid_write_cloud (p, which, cloud_640x480x8, block ? 1 : 0)); }
+        void buildRBC () { check (icp_pyramid_build_rbc (p)); }
+        void resetTransform () { check (icp_pyramid_reset_transform (p)); }
+        void run () { check (icp_pyramid_run (p, k.data ())); pull (); }
+        void runFixed (const std::vector<uint32_t> &iterations)
+        {
+            if (iterations.size () != k.size ()) throw std::runtime_error ("ICPPyramid::runFixed: one count per level");
+            check (icp_pyramid_run_fixed (p, iterations.data ()));
+        }
+        void sync () { check (icp_pyramid_sync (p)); }
+        /*! \brief Level 0's state into `R q t s` and every level's count into `k` (blocking; `run` does it itself). */
+        void pull ()
+        {
+            for (uint32_t l = 0; l < k.size (); ++l) {
+                icp_handle h = level (l);
+                icp_state_t st; checkLevel (h, icp_state (h, &st));
+                k[l] = st.k;
+                if (l == 0) { std::memcpy (R.m, st.R, sizeof st.R); std::memcpy (q.c, st.q, sizeof st.q); std::memcpy (t.v, st.t, sizeof st.t); s = st.s; }
+            }
+        }
+        icp_quality_t evaluate (float max_dist = 0.f) { icp_handle h = level (0); icp_quality_t r; checkLevel (h, icp_evaluate (h, max_dist, &r, 1)); return r; }
+        icp_pyramid_handle handle () { return p; }
+
+        std::vector<uint32_t> k;                                             /*!< iterations every level executed in the last run, finest first */
+        icp::Matrix3f R;  icp::Quaternionf q;  icp::Vector3f t;  float s;    /*!< level 0's result */
+
+    private:
+        void check (int rc) { if (rc != ICP_OK) throw std::runtime_error (std::string ("ICPPyramid: ") + icp_pyramid_last_error (p)); }
+        void checkLevel (icp_handle h, int rc) { if (rc != ICP_OK) throw std::runtime_error (std::string ("ICPPyramid: ") + icp_last_error (h)); }
+        icp_pyramid_handle p;
+        icp::Mode mode;
+    };
 }
 }
 

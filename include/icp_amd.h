@@ -825,6 +825,87 @@ int icp_batch_partition (uint32_t registrations, uint32_t n_slots, uint32_t i, u
 int icp_batch_slot_cpus (icp_batch_handle b, uint32_t slot, char *out, size_t cap);
 const char *icp_batch_last_error (icp_batch_handle b);   /* b may be NULL: error of the last failed create */
 
+/* ---- coarse-to-fine registration (Open3D: multi_scale_icp; KinectFusion's three-level pyramid; not reference behaviour) ------------
+ * An icp_pyramid_* object owns one ordinary engine handle per level, all on one device, and keeps them consistent: the levels of F and
+ * M are built on the device from level 0, the coarsest level runs first, and every finer level starts from the transform the level
+ * above it ended with.  Nothing else changes: every level runs the kernels, launches and graphs a plain handle of its shape runs.
+ * The rule:
+ *   Levels
+ *   - Level 0 is the finest: m points, a row-major side x side grid, as icp_init requires.  Level l has side_l = side >> l and
+ *     m_l = side_l^2.  levels is in [1, ICP_PYRAMID_MAX_LEVELS]; side % (1 << (levels - 1)) == 0 is required.
+ *   - Every (m_l, nr[l]) must pass icp_init's own checks — in particular side_l must be even —, else icp_pyramid_init returns
+ *     ICP_EINVAL with a message that names the level.
+ *   - a, c and the two thresholds are common to all levels; nr[] and max_iterations[] are per level, finest first.
+ *   - One registration per level (batch 1).  Batched pyramids and tracked frames are not provided.
+ *   Reduction from level l - 1 to level l, applied to F and to M alike
+ *   - Per output point (x, y) the block is the four points (2x, 2y), (2x+1, 2y), (2x, 2y+1), (2x+1, 2y+1) of level l - 1, in that
+ *     (row-major) order.  A point is valid as in the icp_set_normals rule: xyz finite and not (0, 0, 0).
+ *   - ICP_PYRAMID_PICK: the output is the eight floats of block element 0, copied bit for bit.
+ *   - ICP_PYRAMID_MEAN (the default): the reference point is the first valid point of the block in block order.  Included are the valid
+ *     points with fabsf (z - z_ref) <= band_l in fp32, band_l = max_dz * (float) (1u << (l - 1)): the grid spacing doubles per level,
+ *     and so does the band.  max_dz == 0 (the default) or +inf: no band test.  With n included points, for each of x, y, z, r, g, b:
+ *     s = the first included point's value, then s = s + next in block order; the output is s / (float) n — fp32, no contraction, an
+ *     IEEE divide.  Floats 3 and 7 are written as 1.0f.  A block without a valid point gives the eight floats of element 0, bit for
+ *     bit: an invalid pixel stays invalid and keeps its colour.
+ *   - Levels are derived recursively: level l from level l - 1, never from level 0 directly.  No atomics; the result does not depend
+ *     on the launch shape.
+ *   Hand-over of T
+ *   - Before level l - 1 runs, its T becomes level l's final T, with the effect of icp_write (ICP_MEM_T) of those eight floats: the
+ *     rotation state is re-derived.  The source is the coarser handle's device state: no host copy, no host wait; the two levels'
+ *     streams are ordered by events, both ways: the finer level waits for the coarser level's run, and whatever writes the coarser
+ *     level's state next (a further run, icp_pyramid_reset_transform, icp_pyramid_write (ICP_MEM_T)) waits for the read.  No
+ *     icp_pyramid_sync is needed between icp_pyramid_run_fixed and the next call.
+ *   Iteration counts
+ *   - In every pyramid run each level's count starts at 0, as after icp_build_rbc; afterwards icp_state (level l).k is what that level
+ *     executed in this run.
+ * The result is level 0's: icp_read (h0, ICP_MEM_T), icp_state (h0), icp_evaluate (h0, ..) with h0 from icp_pyramid_level (p, 0, &h0).
+ * The coarsest level starts from its own current T: the identity after icp_pyramid_init and icp_pyramid_reset_transform, what
+ * icp_pyramid_write (ICP_MEM_T) gave it, or — in a second run without either — where its last run ended.
+ *
+ * icp_pyramid_level hands out the BORROWED handle of a level.  Allowed on it: every setter and getter (modes, metric, normals,
+ * rejection, trimming, robust loss, ..; they survive icp_pyramid_init as they survive icp_init), icp_read, icp_state, icp_evaluate,
+ * icp_device_ptr, icp_transform_cloud, icp_sync and the diagnostics.  The grid widths of icp_set_normals and icp_set_boundary_rejection are per level
+ * (side_l): the caller sets them level by level.  NOT allowed, because they would take the levels apart: icp_init*, icp_destroy,
+ * icp_write / icp_write_cloud of F or M, icp_adopt_device_buffer and icp_track_*.
+ *
+ * icp_pyramid_write       ICP_MEM_F / ICP_MEM_M: the staged upload into level 0 (icp_write), then ONE launch that writes all coarser
+ *                         levels into the level handles' own device buffers; every level handle sees that write as it sees an icp_write
+ *                         of the same object (lazy outputs are gone; with ICP_NORMALS_GRID the moving normals follow a new M).
+ *                         Non-blocking unless `block`: the levels' streams wait on an event, not the host.  ICP_MEM_T: the coarsest
+ *                         level's start.
+ * icp_pyramid_write_cloud icp_write_cloud into level 0 (m must be 16384), then the same launch.
+ * icp_pyramid_set_reduction  survives icp_pyramid_init and takes effect at the next write.  ICP_EINVAL: an unknown kind, max_dz negative or NaN.
+ * icp_pyramid_run         a checked icp_run per level, coarsest to finest, the hand-over in front of each finer level; blocking.
+ *                         k (may be NULL) receives `levels` counts, finest first.
+ * icp_pyramid_run_fixed   exactly iterations[l] steps per level.  Enqueue only: fixed runs, event, hand-over, next level.
+ * icp_pyramid_pending     diagnostic: 1 while what the last icp_pyramid_run_fixed enqueued is still in flight (a query, not a wait).
+ * icp_pyramid_time_build  measurement: the construction launch of `mem` alone, `reps` times, HIP events around each; mean ms.
+ * ICP_ESTATE: a run before icp_pyramid_build_rbc; before icp_pyramid_init every call but create, destroy, the reduction's setter and
+ * getter and icp_pyramid_levels (which gives 0). */
+#define ICP_PYRAMID_MAX_LEVELS 5
+#define ICP_PYRAMID_MEAN 0
+#define ICP_PYRAMID_PICK 1
+typedef struct icp_pyramid_context *icp_pyramid_handle;
+int icp_pyramid_create (icp_pyramid_handle *p, int device, int rot, int weighted);
+int icp_pyramid_destroy (icp_pyramid_handle p);
+int icp_pyramid_init (icp_pyramid_handle p, uint32_t levels, uint32_t m, const uint32_t *nr, float a, float c,
+                      const uint32_t *max_iterations, double angle_threshold, double translation_threshold);
+int icp_pyramid_set_reduction (icp_pyramid_handle p, int kind, float max_dz);
+int icp_pyramid_get_reduction (icp_pyramid_handle p, int *kind, float *max_dz);
+int icp_pyramid_levels (icp_pyramid_handle p, uint32_t *levels);
+int icp_pyramid_level (icp_pyramid_handle p, uint32_t l, icp_handle *h);
+int icp_pyramid_write (icp_pyramid_handle p, int mem, const void *host_ptr, int block);
+int icp_pyramid_write_cloud (icp_pyramid_handle p, int which, const void *host_cloud_640x480x8, int block);
+int icp_pyramid_reset_transform (icp_pyramid_handle p);                    /* coarsest T <- identity */
+int icp_pyramid_build_rbc (icp_pyramid_handle p);                          /* icp_build_rbc of every level */
+int icp_pyramid_run (icp_pyramid_handle p, uint32_t *k);
+int icp_pyramid_run_fixed (icp_pyramid_handle p, const uint32_t *iterations);
+int icp_pyramid_sync (icp_pyramid_handle p);
+/* diagnostics and measurement (as icp_time_*: not part of a registration) */
+int icp_pyramid_pending (icp_pyramid_handle p, int *pending);
+int icp_pyramid_time_build (icp_pyramid_handle p, int mem, uint32_t reps, float *ms_per_launch);
+const char *icp_pyramid_last_error (icp_pyramid_handle p);   /* p may be NULL: error of the last failed create */
+
 /* ---- measurement (bench.py, HIP events on the handle's stream) --------------------------------- */
 
 /* Times `reps` back-to-back icp_run_fixed(iterations) passes with hipEvents recorded on the
