@@ -1214,7 +1214,10 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
     // every query tests the boxes of all tiles against its seed bound, the block ORs the answers — and only those tiles
     // are staged and scanned, in ascending order, without a vote per tile.
     constexpr bool MASKED = (TILE == 256) && !SINGLE && (MINW == 4);
-    if constexpr (SINGLE) __builtin_assume (nr <= KT);
+    // (CHAIN: icp_route_of takes the chained route for |R| <= 1024 only — one tile, like SINGLE: the tile loop folds to its one trip, A 8.75 ->
+    // 8.54 us per iteration, profiles/bounds_ab.txt)
+    constexpr bool ONE_TILE = SINGLE || CHAIN;
+    if constexpr (ONE_TILE) __builtin_assume (nr <= KT);
     if constexpr (MASKED) __builtin_assume (nr > KT && nr <= 32u * KT);
     const uint32_t b = blockIdx.y, check = check_flags & 1u;
     icp_reg_state *st = (CHAIN && !(check_flags & 2u)) ? gst + (size_t) b * 2 : gst + b;
@@ -1576,7 +1579,7 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
         // 64 group tests, and a tile no query of the block is near is neither tested further nor staged (at |R| = 4096 a
         // block's 64 neighbouring queries need one, seldom two, of the four tiles)
         auto tile_near = [&] (float lim_) -> bool {
-            if (SINGLE || nr <= KT) return true;
+            if (ONE_TILE || nr <= KT) return true;
             return ks_box_bound (s_tbox[2u * (t0 / ICP_TBOX)], s_tbox[2u * (t0 / ICP_TBOX) + 1u], qx, qy, qz) < lim_;     // (staged in the prologue)
         };
         if (t0) {                                    // further tiles (nr > KT)
