@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-__all__ = ["ICP", "ICPStep", "ICPError", "Memory", "Quality", "ErrorMetric", "Normals", "ICPStepConfigT", "ICPStepConfigW",
+__all__ = ["ICP", "ICPStep", "ICPError", "Memory", "Quality", "Pairs", "PAIR", "ErrorMetric", "Normals", "ICPStepConfigT", "ICPStepConfigW",
            "PowerMode", "ReduceMode", "TransformKind", "ICPBatch", "batch_partition", "power_method", "KernelObject", "kernel_lms", "kernel_reps", "kernel_weights", "kernel_mean", "kernel_devs", "kernel_s", "ReduceScan", "lib", "lib_path", "reduce", "scan", "ReduceConfig", "synth_pair", "synth_cloud_vga", "punch_holes", "HOLES_SCATTERED", "HOLES_CONTIGUOUS", "synth_pair_scene", "SCENE_CURVED", "SCENE_WALL", "device_count", "DIST_ID"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -109,6 +109,19 @@ class Quality(C.Structure):
         return np.array(self.information, np.float64).reshape(6, 6)
 
 
+class Pairs:                     # icp_correspondences (include/icp_amd.h): which pairs the set holds
+    EVALUATED = 0                 # the inliers of icp_evaluate's rule at the same max_dist (the handle's opt-in rules have no influence)
+    LAST_ITERATION = 1            # the pairs the solver used in the last executed iteration: ICP_MEM_W != 0
+
+
+PAIR = np.dtype([("moving", "<u4"), ("fixed", "<u4"), ("geo", "<f4"), ("weight", "<f4")])       # icp_pair_t
+
+
+class _Pair(C.Structure):
+    """icp_pair_t (include/icp_amd.h): one member pair of a correspondence set, 16 bytes."""
+    _fields_ = [("moving", C.c_uint32), ("fixed", C.c_uint32), ("geo", C.c_float), ("weight", C.c_float)]
+
+
 _lib = None
 
 
@@ -198,6 +211,10 @@ def lib():
     sig("icp_state_b", i32, vp, u32, C.POINTER(_State))
     sig("icp_evaluate", i32, vp, f32, C.POINTER(Quality), u32)
     sig("icp_batch_evaluate", i32, vp, u32, f32, C.POINTER(Quality))
+    sig("icp_correspondences", i32, vp, i32, f32, C.POINTER(u32), u32)
+    sig("icp_correspondences_read", i32, vp, u32, vp, u32, C.POINTER(u32))
+    sig("icp_correspondences_device_ptr", i32, vp, u32, C.POINTER(vp), C.POINTER(vp))
+    sig("icp_batch_correspondences", i32, vp, u32, i32, f32, vp, u32, C.POINTER(u32))
     sig("icp_write_cloud", i32, vp, i32, vp, i32)
     sig("icp_transform_cloud", i32, vp, vp, vp, u32)
     sig("icp_transform_cloud_ex", i32, vp, i32, vp, vp, vp, u32)
@@ -1031,6 +1048,26 @@ class ICPStep:
         self._chk(self._L.icp_evaluate(self._h, _max_dist_arg(max_dist), out, n))
         return list(out)[:n]
 
+    def correspondences(self, source=Pairs.EVALUATED, max_dist=0.0, batch_index=0):
+        """The correspondence set of registration batch_index (icp_correspondences + icp_correspondences_read; blocking): a structured
+        array of dtype PAIR (moving, fixed, geo, weight), one record per member pair in ascending query index.  Pairs.EVALUATED: the
+        inliers of evaluate() at the same max_dist; Pairs.LAST_ITERATION: the pairs with a weight != 0 in the last executed iteration
+        (max_dist must be 0).  One launch set computes the sets of the whole batch; the others stay readable (correspondences_read)."""
+        counts = (C.c_uint32 * self.batch)()
+        self._chk(self._L.icp_correspondences(self._h, source, _max_dist_arg(max_dist), counts, self.batch))
+        return self.correspondences_read(batch_index)
+
+    def correspondences_read(self, batch_index=0):
+        """The set of registration batch_index as the last correspondences() computed it (icp_correspondences_read)."""
+        n = C.c_uint32()
+        rc = self._L.icp_correspondences_read(self._h, batch_index, None, 0, C.byref(n))
+        if rc and not (rc == 1 and n.value):               # (ICP_EINVAL with a count: the set is there and needs room)
+            self._chk(rc)
+        out = np.empty(n.value, PAIR)
+        if n.value:
+            self._chk(self._L.icp_correspondences_read(self._h, batch_index, _p(out), n.value, C.byref(n)))
+        return out
+
     def _vec(self, name, shape=None):
         a = np.array(getattr(self.state(), name), dtype=np.float32)
         return a.reshape(shape) if shape else a
@@ -1281,6 +1318,13 @@ class ICPBatch:
         self._chk(self._L.icp_batch_evaluate(self._b, i, _max_dist_arg(max_dist), C.byref(q)))
         return q
 
+    def correspondences(self, i, source=Pairs.EVALUATED, max_dist=0.0):
+        """ICPStep.correspondences of registration i (icp_batch_correspondences): its set as a structured array of dtype PAIR."""
+        n = C.c_uint32()
+        out = np.empty(self.m, PAIR)                       # (a set has at most m members)
+        self._chk(self._L.icp_batch_correspondences(self._b, i, source, _max_dist_arg(max_dist), _p(out), self.m, C.byref(n)))
+        return out[:n.value].copy()
+
     def read(self, i, mem):
         dt, cols = _MEM_DTYPE[mem]
         sizes = {Memory.T: 32, Memory.TK: 32, Memory.MEANS: 32, Memory.S: 44, Memory.NN_ID: self.m * 8, Memory.R: 36, Memory.RK: 36,
@@ -1301,7 +1345,7 @@ PYRAMID_MAX_LEVELS = 5            # ICP_PYRAMID_MAX_LEVELS
 
 
 class _PyramidLevel(ICP):
-    """The borrowed handle of a pyramid level as an ICP object: every setter, getter, read, state() and evaluate() of ICP; it never
+    """The borrowed handle of a pyramid level as an ICP object: every setter, getter, read, state(), evaluate() and correspondences() of ICP; it never
     destroys the handle (close() only lets go of it).  Not for init, writes of F / M, adoption or tracking (include/icp_amd.h)."""
 
     def __init__(self, handle, m, nr, max_iterations, angle_threshold, translation_threshold):
@@ -1336,7 +1380,7 @@ class _PyramidLevel(ICP):
 class ICPPyramid:
     """Coarse-to-fine registration (icp_pyramid_*, include/icp_amd.h): one engine handle per level on one device, the levels of F and M
     built on the device from level 0 by one launch, T handed from each level to the next finer one on the device.  The result is level
-    0's: level(0).read(Memory.T), level(0).state(), level(0).evaluate()."""
+    0's: level(0).read(Memory.T), level(0).state(), level(0).evaluate(), level(0).correspondences()."""
 
     def __init__(self, device=0, CR=ICPStepConfigT.POWER_METHOD, CW=ICPStepConfigW.WEIGHTED):
         self._L = lib()

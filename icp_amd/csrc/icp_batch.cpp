@@ -362,6 +362,18 @@ int icp_batch_evaluate (icp_batch_handle b, uint32_t i, float max_dist, icp_qual
 }
 ICP_CATCH_ALL
 
+// icp_correspondences on registration i's slot (one launch set serves the slot's registrations), then the records of registration i
+int icp_batch_correspondences (icp_batch_handle b, uint32_t i, int source, float max_dist,
+                               icp_pair_t *host_dst, uint32_t capacity, uint32_t *n) try
+{
+    BATCH_SLOT (b, i)
+    std::vector<uint32_t> c (idx_ + 1u);
+    BATCH_CALL (b, icp_correspondences (h_, source, max_dist, c.data (), idx_ + 1u));
+    BATCH_CALL (b, icp_correspondences_read (h_, idx_, host_dst, capacity, n));
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
 int icp_batch_set_modes (icp_batch_handle b, int reduce_mode, int power_mode) try
 {
     int rc = set_all (b, icp_set_reduce_mode, reduce_mode);

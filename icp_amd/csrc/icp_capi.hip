@@ -33,6 +33,7 @@ void free_all (icp_context *h)
     h->hF = h->hM = h->hT = nullptr; h->dCloud = h->dCloudOut = nullptr; h->cloud_cap = 0;
     h->dF = h->dM = nullptr; h->ownF = h->ownM = true;
     h->quality = icp_context::quality_buffers {};                 // (they were among dev_allocs)
+    h->pairs = icp_context::pairs_buffers {};
     for (int k = 0; k < 2; ++k) {
         if (h->hBand[k]) (void) hipHostFree (h->hBand[k]);
         if (h->hFrame[k]) (void) hipHostFree (h->hFrame[k]);
@@ -1033,34 +1034,35 @@ ICP_CATCH_ALL
 
 int icp_state (icp_handle h, icp_state_t *out) try { api_guard guard_ (h); return icp_state_b (h, 0, out); } ICP_CATCH_ALL
 
-// Registration quality (include/icp_amd.h; icp_quality.hip): one search at the registrations' current state into the evaluation's own
-// buffers, the pair kernel, the second level, one copy of the result words.  The search is the plain one of the handle's layout in its
-// reference-order form with every opt-in rule off and REGULAR weights — the same correspondences and points bit for bit, and a form
-// that writes nothing but its per-query outputs: no moment partials (the fused form's), no weight partials (the WEIGHTED ones).  The
-// state, the flags of the lazy outputs, the graphs and the pinned mirror are not touched.
-int icp_evaluate (icp_handle h, float max_dist, icp_quality_t *out, uint32_t count) try
+// What icp_evaluate and icp_correspondences ask of the handle before they touch the device (`who`: the call's name for the messages).
+// need () brings an open checked run to its end, as icp_read does.
+static int evaluation_ready (icp_context *h, const char *who, uint32_t count)
 {
-    api_guard guard_ (h);
-    if (!h) return ICP_EINVAL;
-    if (!out) return fail (h, ICP_EINVAL, "icp_evaluate: null output");
-    if (count == 0) return fail (h, ICP_EINVAL, "icp_evaluate: count must be at least 1");
-    if (!(max_dist >= 0.f)) return fail (h, ICP_EINVAL, "icp_evaluate: max_dist must be >= 0 (0 or +inf: no distance test)");
-    int rc = need (h, false); if (rc) return rc;         // (brings an open checked run to its end, as icp_read does)
-    if (count > h->p.batch) return fail (h, ICP_EINVAL, "icp_evaluate: count is above the handle's batch");
-    if (h->track_submitted) return fail (h, ICP_ESTATE, "icp_evaluate: the handle has tracked frames (the quality of tracked frames is not provided): icp_init or icp_track_reset first");
+    const std::string w (who);
+    if (count == 0) return fail (h, ICP_EINVAL, w + ": count must be at least 1");
+    int rc = need (h, false); if (rc) return rc;
+    if (count > h->p.batch) return fail (h, ICP_EINVAL, w + ": count is above the handle's batch");
+    if (h->track_submitted) return fail (h, ICP_ESTATE, w + ": the handle has tracked frames (the quality of tracked frames is not provided): icp_init or icp_track_reset first");
     if (!h->built) return fail (h, ICP_ESTATE, "icp_build_rbc has not been called");
+    return set_device (h);
+}
+
+// The search into the evaluation's own buffers, shared by icp_evaluate and icp_correspondences (ICP_PAIRS_EVALUATED): the plain search of
+// the handle's layout in its reference-order form with every opt-in rule off and REGULAR weights — the same correspondences and points
+// bit for bit as an iteration's search at this state, and a form that writes nothing but its per-query outputs: no moment partials (the
+// fused form's), no weight partials (the WEIGHTED ones).  The state, the flags of the lazy outputs, the graphs and the pinned mirror are
+// not touched.
+static int evaluation_search (icp_context *h)
+{
     const icp_params &p = h->p;
-    const size_t B = p.batch, n = B * p.m, nblk = icp_p2pl_nblk (p.m);
-    if ((rc = set_device (h))) return rc;
+    const size_t n = (size_t) p.batch * p.m;
     icp_context::quality_buffers &Q = h->quality;
+    int rc;
     // (first use; each buffer on its own: a call that ran out of memory half way leaves what it got to the next one)
     if (!Q.nn_id && (rc = dalloc (h, &Q.nn_id, n))) return rc;
     if (!Q.PF && (rc = dalloc (h, &Q.PF, n))) return rc;
     if (!Q.PM && (rc = dalloc (h, &Q.PM, n))) return rc;
     if (!Q.rid && (rc = dalloc (h, &Q.rid, n))) return rc;
-    if (!Q.part && (rc = dalloc (h, &Q.part, B * ICP_QUALITY_TERMS * nblk))) return rc;
-    if (!Q.cnt && (rc = dalloc (h, &Q.cnt, B * 2 * nblk))) return rc;
-    if (!Q.res && (rc = dalloc (h, &Q.res, B * ICP_QUALITY_RES))) return rc;
     icp_params q = p;
     q.check = 0; q.emit = 1; q.fused = 0; q.weighted = 0; q.hmirror = nullptr; q.hstate = nullptr; q.dbg = nullptr;
     q.reject = 0u; q.reject_d2 = 0.f; q.reject_max_dist = 0.f; q.trim_keep = 0.f; q.metric = ICP_METRIC_POINT_TO_POINT; q.p2pl_mu = 0.f; q.gicp = 0u;
@@ -1069,6 +1071,25 @@ int icp_evaluate (icp_handle h, float max_dist, icp_quality_t *out, uint32_t cou
     // iterations', the answers stay here)
     if (icp_dense (q)) HIPCHK (h, hipMemcpyAsync (Q.rid, p.rid, n * sizeof (uint32_t), hipMemcpyDeviceToDevice, h->stream));
     icp_launch_search (q, h->stream);
+    return ICP_OK;
+}
+
+// Registration quality (include/icp_amd.h; icp_quality.hip): one search at the registrations' current state into the evaluation's own
+// buffers (evaluation_search), the pair kernel, the second level, one copy of the result words.
+int icp_evaluate (icp_handle h, float max_dist, icp_quality_t *out, uint32_t count) try
+{
+    api_guard guard_ (h);
+    if (!h) return ICP_EINVAL;
+    if (!out) return fail (h, ICP_EINVAL, "icp_evaluate: null output");
+    if (!(max_dist >= 0.f)) return fail (h, ICP_EINVAL, "icp_evaluate: max_dist must be >= 0 (0 or +inf: no distance test)");
+    int rc = evaluation_ready (h, "icp_evaluate", count); if (rc) return rc;
+    const icp_params &p = h->p;
+    const size_t B = p.batch, nblk = icp_p2pl_nblk (p.m);
+    icp_context::quality_buffers &Q = h->quality;
+    if ((rc = evaluation_search (h))) return rc;
+    if (!Q.part && (rc = dalloc (h, &Q.part, B * ICP_QUALITY_TERMS * nblk))) return rc;
+    if (!Q.cnt && (rc = dalloc (h, &Q.cnt, B * 2 * nblk))) return rc;
+    if (!Q.res && (rc = dalloc (h, &Q.res, B * ICP_QUALITY_RES))) return rc;
     const bool dist_on = max_dist > 0.f && !std::isinf (max_dist);
     icp_launch_quality (Q.PF, Q.PM, p.M, p.m, p.batch, dist_on, dist_on ? (float) ((double) max_dist * (double) max_dist) : 0.f, Q.part, Q.cnt, Q.res, h->stream);
     HIPCHK (h, hipGetLastError ());
@@ -1088,6 +1109,78 @@ int icp_evaluate (icp_handle h, float max_dist, icp_quality_t *out, uint32_t cou
         for (int a = 0; a < 6; ++a)
             for (int cc = a; cc < 6; ++cc, ++t) { o.information[a * 6 + cc] = r[t]; o.information[cc * 6 + a] = r[t]; }
     }
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
+// The correspondence set (include/icp_amd.h; icp_pairs.hip).  ICP_PAIRS_EVALUATED: evaluation_search, then the two passes over the
+// evaluation's buffers — icp_evaluate's launch count.  ICP_PAIRS_LAST_ITERATION: the two passes over the per-query outputs as icp_read
+// would deliver them (lazy outputs are reproduced first: materialize_outputs).  One copy of the count words, the wait.
+int icp_correspondences (icp_handle h, int source, float max_dist, uint32_t *counts, uint32_t count) try
+{
+    api_guard guard_ (h);
+    if (!h) return ICP_EINVAL;
+    if (source != ICP_PAIRS_EVALUATED && source != ICP_PAIRS_LAST_ITERATION) return fail (h, ICP_EINVAL, "icp_correspondences: unknown source");
+    if (!counts) return fail (h, ICP_EINVAL, "icp_correspondences: null counts");
+    if (!(max_dist >= 0.f)) return fail (h, ICP_EINVAL, "icp_correspondences: max_dist must be >= 0 (0 or +inf: no distance test)");
+    if (source == ICP_PAIRS_LAST_ITERATION && max_dist != 0.f)
+        return fail (h, ICP_EINVAL, "icp_correspondences: ICP_PAIRS_LAST_ITERATION takes the pairs the iteration used: max_dist must be 0");
+    int rc = evaluation_ready (h, "icp_correspondences", count); if (rc) return rc;
+    const icp_params &p = h->p;
+    const size_t B = p.batch;
+    icp_context::pairs_buffers &P = h->pairs;
+    static_assert (sizeof (icp_pair_t) == sizeof (uint4) && sizeof (icp_pair_t) == 16, "a record is one 16-byte store");
+    if (source == ICP_PAIRS_LAST_ITERATION && (rc = materialize_outputs (h, ICP_MEM_W))) return rc;
+    // (first use; each buffer on its own, as the evaluation's)
+    if (!P.blk && (rc = dalloc (h, &P.blk, B * icp_p2pl_nblk (p.m)))) return rc;
+    if (!P.rec && (rc = dalloc (h, &P.rec, B * p.m))) return rc;
+    if (!P.count && (rc = dalloc (h, &P.count, B))) return rc;
+    P.valid = false;
+    if (source == ICP_PAIRS_EVALUATED) {
+        if ((rc = evaluation_search (h))) return rc;
+        const icp_context::quality_buffers &Q = h->quality;
+        const bool dist_on = max_dist > 0.f && !std::isinf (max_dist);
+        icp_launch_pairs (source, Q.PF, Q.PM, p.M, Q.nn_id, p.m, p.batch, dist_on, dist_on ? (float) ((double) max_dist * (double) max_dist) : 0.f, P.blk, P.rec, P.count, h->stream);
+    } else
+        icp_launch_pairs (source, p.PF, p.PM, nullptr, p.nn_id, p.m, p.batch, false, 0.f, P.blk, P.rec, P.count, h->stream);
+    HIPCHK (h, hipGetLastError ());
+    P.n.assign (B, 0u);
+    HIPCHK (h, hipMemcpyAsync (P.n.data (), P.count, B * sizeof (uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK (h, hipStreamSynchronize (h->stream));
+    for (uint32_t b = 0; b < count; ++b) counts[b] = P.n[b];
+    P.valid = true;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
+int icp_correspondences_read (icp_handle h, uint32_t b, icp_pair_t *host_dst, uint32_t capacity, uint32_t *n) try
+{
+    api_guard guard_ (h);
+    int rc = need (h, false); if (rc) return rc;
+    if (b >= h->p.batch) return fail (h, ICP_EINVAL, "batch index out of range");
+    const icp_context::pairs_buffers &P = h->pairs;
+    if (!P.valid) return fail (h, ICP_ESTATE, "icp_correspondences_read: no set has been computed since icp_init: icp_correspondences first");
+    const uint32_t c = P.n[b];
+    if (n) *n = c;
+    if (capacity < c) return fail (h, ICP_EINVAL, "icp_correspondences_read: the set holds more records than `capacity`");
+    if (c == 0u) return ICP_OK;
+    if (!host_dst) return fail (h, ICP_EINVAL, "icp_correspondences_read: null destination");
+    if ((rc = set_device (h))) return rc;
+    HIPCHK (h, hipMemcpyAsync (host_dst, P.rec + (size_t) b * h->p.m, (size_t) c * sizeof (icp_pair_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK (h, hipStreamSynchronize (h->stream));
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
+int icp_correspondences_device_ptr (icp_handle h, uint32_t b, void **pairs, void **count_word) try
+{
+    api_guard guard_ (h);
+    int rc = need (h, false); if (rc) return rc;
+    if (b >= h->p.batch) return fail (h, ICP_EINVAL, "batch index out of range");
+    const icp_context::pairs_buffers &P = h->pairs;
+    if (!P.rec || !P.count) return fail (h, ICP_ESTATE, "icp_correspondences_device_ptr: the buffers are allocated by the first icp_correspondences");
+    if (pairs) *pairs = P.rec + (size_t) b * h->p.m;
+    if (count_word) *count_word = P.count + b;
     return ICP_OK;
 }
 ICP_CATCH_ALL

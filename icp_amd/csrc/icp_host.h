@@ -142,6 +142,13 @@ struct icp_context {
         icp_dist_id *nn_id = nullptr; float4 *PF = nullptr, *PM = nullptr; uint32_t *rid = nullptr;
         double *part = nullptr; uint32_t *cnt = nullptr; double *res = nullptr;
     } quality;
+    // icp_correspondences' own buffers (allocated at its first use, each on its own; freed with the others by icp_init): the block counts
+    // of k_pairs_count [batch][icp_p2pl_nblk (m)], the records [batch][m], the count words [batch].  n: the counts of the set the buffers
+    // hold as the host received them; valid: a set has been computed since icp_init.
+    struct pairs_buffers {
+        uint32_t *blk = nullptr; uint4 *rec = nullptr; uint32_t *count = nullptr;
+        std::vector<uint32_t> n; bool valid = false;
+    } pairs;
     float *dCloud = nullptr, *dCloudOut = nullptr; uint32_t cloud_cap = 0;
     std::map<uint64_t, icp_host::graph_entry> graphs;      // key: iterations << 3 | check << 2 | parity (+ fresh, + kind: see get_graph)
     uint32_t parity = 0;                         // tracking: which landmark buffers are the fixed / moving set (graphs hold pointers): frame f -> f mod 3

@@ -366,6 +366,11 @@ void icp_launch_owner_search_dense (const icp_params &p, hipStream_t s);
 // moving sets [batch][m][8]; part [batch][ICP_QUALITY_TERMS][icp_p2pl_nblk (m)], cnt [batch][2][icp_p2pl_nblk (m)], res [batch][ICP_QUALITY_RES]
 void icp_launch_quality (const float4 *PF, const float4 *PM, const float *M, uint32_t m, uint32_t batch, bool dist_on, float d2, double *part, uint32_t *cnt,
                          double *res, hipStream_t s);
+// icp_pairs.hip: k_pairs_count<source> + k_pairs_scatter<source>, the correspondence set (icp_correspondences) of the pairs in PF / PM /
+// nn_id — the evaluation's buffers with M (ICP_PAIRS_EVALUATED), or the last iteration's per-query outputs (ICP_PAIRS_LAST_ITERATION: the
+// weight is PF.w; M, dist_on and d2 are not read).  blk_cnt [batch][icp_p2pl_nblk (m)], pairs [batch][m] records of 16 bytes, count [batch]
+void icp_launch_pairs (int source, const float4 *PF, const float4 *PM, const float *M, const icp_dist_id *nn_id, uint32_t m, uint32_t batch, bool dist_on, float d2,
+                       uint32_t *blk_cnt, uint4 *pairs, uint32_t *count, hipStream_t s);
 uint32_t icp_tbox_of (const icp_params &p);
 uint32_t icp_s2_wave_of (const icp_params &p);
 void icp_search_layout_of (const icp_params &p, int *dense, int *tile, int *stage2);   // what icp_launch_search selects          // 1: the dense search scans the lists with lanes = candidates (long lists)

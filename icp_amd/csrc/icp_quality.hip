@@ -9,12 +9,12 @@
 // tests/quality_ref.py restates them.
 //
 // Pair i, with e = PM[i].xyz (the transformed moving point), f = PF[i].xyz (the returned fixed point), mv = M[i].xyz:
-//   counted = mv finite and not (0, 0, 0)                                     (n_moving counts these)
-//   geo = (gx gx + gy gy) + gz gz in fp32, g = e - f componentwise            (the rejection rule's quantity)
-//   inlier = counted, f not (0, 0, 0), geo finite, and geo <= d2 unless the distance test is off        (n_inliers counts these)
+//   counted, geo, inlier: icp_pair_counted, icp_pair_geo, icp_pair_inlier (icp_pair_rule.h; icp_correspondences' set is made of the same inliers); n_moving counts the
+//   counted pairs, n_inliers the inliers
 //   terms 0 .. 20: G about the point Q = f in double (plane_point_share: [[qq I - Q Q^T, [Q]x], [-[Q]x, I]], upper triangle, row-major);
 //   term 21: (double) geo.  A pair that is no inlier leaves exact zeros (selected: a NaN coordinate makes no NaN).
 #include "icp_plane_moments.h"          // (plane_point_share, plane_block_tree)
+#include "icp_pair_rule.h"
 
 __global__ __launch_bounds__ (256) void k_quality_pairs (const float4 *PF, const float4 *PM, const float *M, uint32_t m, uint32_t dist_on, float d2,
                                                          double *part, uint32_t *cnt, uint32_t nblk)
@@ -25,10 +25,9 @@ __global__ __launch_bounds__ (256) void k_quality_pairs (const float4 *PF, const
     const float4 f = PF[o + ic], e = PM[o + ic];
     const float4 mv = *reinterpret_cast<const float4 *> (M + (o + ic) * 8);
     __shared__ uint32_t s_cnt[2][ICP_P2PL_BLOCK / 64u];
-    const bool counted = i < m && isfinite (mv.x) && isfinite (mv.y) && isfinite (mv.z) && !(mv.x == 0.f && mv.y == 0.f && mv.z == 0.f);
-    const float gx = e.x - f.x, gy = e.y - f.y, gz = e.z - f.z;
-    const float geo = (gx * gx + gy * gy) + gz * gz;
-    const bool inlier = counted && !(f.x == 0.f && f.y == 0.f && f.z == 0.f) && isfinite (geo) && (!dist_on || geo <= d2);
+    const bool counted = icp_pair_counted (i < m, mv);
+    const float geo = icp_pair_geo (f, e);
+    const bool inlier = icp_pair_inlier (counted, f, geo, dist_on, d2);
     double v[ICP_QUALITY_TERMS];
 #pragma unroll
     for (int t = 0; t < (int) ICP_QUALITY_TERMS; ++t) v[t] = 0.0;

@@ -8,7 +8,7 @@ import time
 
 import numpy as np
 
-from . import ICP, ErrorMetric, ICPPyramid, Memory, Normals, PowerMode, PyramidReduction, ReduceMode, RobustLoss
+from . import ICP, ErrorMetric, ICPPyramid, Memory, Normals, Pairs, PowerMode, PyramidReduction, ReduceMode, RobustLoss
 from .io import load_pc8d, save_pc8d
 
 
@@ -40,6 +40,16 @@ def register_and_evaluate(fixed, moving, evaluate, **options):
     bound = inspect.signature(register_clouds).bind(fixed, moving, **options)
     bound.apply_defaults()
     return _register(0.0 if evaluate is None else evaluate, **bound.arguments)
+
+
+def register_with_pairs(fixed, moving, evaluate=None, **options):
+    """register_clouds (its options) with the registration's correspondence set at the final transform: returns (T[8], k, latency_ms,
+    transformed moving cloud, Quality record or None, pairs) — pairs the Pairs.EVALUATED set (ICPStep.correspondences: a structured
+    array of moving index, fixed landmark index, squared distance, weight) for pairs no farther apart than `evaluate` mm (None or 0:
+    no distance test); the Quality record is None when `evaluate` is None."""
+    bound = inspect.signature(register_clouds).bind(fixed, moving, **options)
+    bound.apply_defaults()
+    return _run(True, evaluate, **bound.arguments)
 
 
 def pyramid_nr(levels):
@@ -87,6 +97,14 @@ def _register(evaluate, fixed, moving, device, a, c, max_iterations, angle_thres
               max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one, normal_angle, reject_boundary,
               pyramid=None):
     """(T[8], k, latency_ms, transformed moving cloud, Quality record or None): register_clouds' options; evaluate None: no evaluation."""
+    return _run(False, **locals())[:5]
+
+
+def _run(pairs, evaluate, fixed, moving, device, a, c, max_iterations, angle_threshold, translation_threshold, reduce_mode, reject_invalid,
+         max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one, normal_angle, reject_boundary,
+         pyramid=None):
+    """_register's five values and a sixth: with `pairs` the Pairs.EVALUATED correspondence set at max_dist = evaluate (None: 0, no
+    distance test), else None."""
     options = (reduce_mode, reject_invalid, max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one,
                normal_angle, reject_boundary)
     if pyramid is not None:
@@ -110,9 +128,10 @@ def _register(evaluate, fixed, moving, device, a, c, max_iterations, angle_thres
     ms = (time.perf_counter() - t0) * 1e3
     T = result.read(Memory.T)
     quality = result.evaluate(evaluate)[0] if evaluate is not None else None
+    members = result.correspondences(Pairs.EVALUATED, evaluate or 0.0) if pairs else None
     out = result.transform_cloud(moving)
     reg.close()
-    return T, k, ms, out, quality
+    return T, k, ms, out, quality, members
 
 
 def track(frames, device=0, a=2e2, c=1e-6, warm_start=False, **kw):
@@ -230,6 +249,10 @@ def main(argv=None):
     ap.add_argument("--evaluate", type=_point_weight, default=None, metavar="MAXDIST",
                     help="after the run print the registration's fitness, inlier RMSE and inlier count at the final transform, for "
                          "pairs no farther apart than MAXDIST mm (0: no distance test)")
+    ap.add_argument("--pairs", default=None, metavar="FILE",
+                    help="after the run write the correspondence set at the final transform to FILE as .npy: one record (moving landmark "
+                         "index, fixed landmark index, squared distance in mm^2, weight) per pair no farther apart than --evaluate's "
+                         "MAXDIST (without --evaluate: no distance test), in ascending moving index; prints the count")
     ap.add_argument("--pyramid", type=_pyramid, default=None, metavar="LEVELS[:MAXDZ]",
                     help="coarse-to-fine: register on LEVELS landmark grids (128, 64, 32, .. wide; 256, 64, 64, .. representatives), "
                          "coarsest first, each level made of 2 x 2 means of the one below it (points within MAXDZ mm in z, doubling "
@@ -240,7 +263,10 @@ def main(argv=None):
                    point_to_plane=args.point_to_plane, colored=args.colored, robust=args.robust, plane_to_plane=args.plane_to_plane,
                    symmetric=args.symmetric, one_to_one=args.one_to_one, normal_angle=args.normal_angle,
                    reject_boundary=args.reject_boundary, pyramid=args.pyramid)
-    if args.evaluate is None:
+    members = None
+    if args.pairs is not None:
+        T, k, ms, out, quality, members = register_with_pairs(fixed, moving, args.evaluate, **options)
+    elif args.evaluate is None:
         (T, k, ms, out), quality = register_clouds(fixed, moving, **options), None
     else:
         T, k, ms, out, quality = register_and_evaluate(fixed, moving, args.evaluate, **options)
@@ -259,6 +285,10 @@ def main(argv=None):
         print("    Fitness               :    %.6f" % quality.fitness)
         print("    Inlier RMSE           :    %.6f mm" % quality.inlier_rmse)
         print("    Inliers               :    %d of %d" % (quality.n_inliers, quality.n_moving))
+    if members is not None:
+        with open(args.pairs, "wb") as f:                # (a file object: np.save appends no extension to it)
+            np.save(f, members)
+        print("    Correspondences       :    %d" % len(members))
     if args.output:
         save_pc8d(args.output, out)
 

@@ -668,6 +668,19 @@ namespace ICP
         void setSymmetric (bool on = true) { check (icp_set_symmetric (h, on ? 1 : 0)); }
         bool getSymmetric () { int on = 0; check (icp_get_symmetric (h, &on)); return on != 0; }
 
+        /*! \brief The correspondence set of the registration (icp_correspondences, include/icp_amd.h): one record per member pair
+         *         (moving index, fixed index, squared distance, weight) in ascending moving index, compacted on the device.
+         *         ICP_PAIRS_EVALUATED: the inliers of evaluate (max_dist); ICP_PAIRS_LAST_ITERATION: the pairs the last executed
+         *         iteration used (max_dist must be 0).  Blocking.  Open3D: RegistrationResult::correspondence_set; PCL: Correspondences. */
+        std::vector<icp_pair_t> correspondences (int source = ICP_PAIRS_EVALUATED, float max_dist = 0.f)
+        {
+            uint32_t n = 0;
+            check (icp_correspondences (h, source, max_dist, &n, 1));
+            std::vector<icp_pair_t> pairs (n);
+            check (icp_correspondences_read (h, 0, pairs.data (), n, &n));
+            return pairs;
+        }
+
         float *hPtrInF;  /*!< Staging buffer of the fixed set (reference: mapped H_IN_F). */
         float *hPtrInM;  /*!< Staging buffer of the moving set. */
         float *hPtrIOT;  /*!< Staging buffer of [q | t, s]. */
@@ -830,7 +843,8 @@ namespace ICP
      *         picks), the coarsest level run first and every finer one started from the transform of the level above it — the
      *         hand-over happens on the device.  `run` is blocking and leaves level 0's `R q t s` and every level's count in `k`
      *         (finest first); `runFixed` only enqueues.  `level (l)` is the borrowed C handle of a level for the per-level setters
-     *         (icp_set_error_metric, icp_set_normals with the level's own grid width `side >> l`, ..), icp_read and icp_evaluate;
+     *         (icp_set_error_metric, icp_set_normals with the level's own grid width `side >> l`, ..), icp_read, icp_evaluate and
+     *         icp_correspondences;
      *         it must not be initialised, destroyed or written F / M through.  The reference has no such class.
      */
     template <ICPStepConfigT CR, ICPStepConfigW CW>
@@ -890,6 +904,15 @@ namespace ICP
             }
         }
         icp_quality_t evaluate (float max_dist = 0.f) { icp_handle h = level (0); icp_quality_t r; checkLevel (h, icp_evaluate (h, max_dist, &r, 1)); return r; }
+        std::vector<icp_pair_t> correspondences (int source = ICP_PAIRS_EVALUATED, float max_dist = 0.f)
+        {
+            icp_handle h = level (0);
+            uint32_t n = 0;
+            checkLevel (h, icp_correspondences (h, source, max_dist, &n, 1));
+            std::vector<icp_pair_t> pairs (n);
+            checkLevel (h, icp_correspondences_read (h, 0, pairs.data (), n, &n));
+            return pairs;
+        }
         icp_pyramid_handle handle () { return p; }
 
         std::vector<uint32_t> k;                                             /*!< iterations every level executed in the last run, finest first */

@@ -625,6 +625,48 @@ typedef struct {
 } icp_quality_t;
 int icp_evaluate (icp_handle h, float max_dist, icp_quality_t *out, uint32_t count);
 
+/* Correspondence set (Open3D: RegistrationResult::correspondence_set; PCL: pcl::Correspondences; not reference behaviour): WHICH pairs a
+ * registration holds, as one compact list on the device.  Nothing runs unless the call is made: without it every kernel, launch, graph
+ * and bit is as before.  The rule:
+ *   - Set membership.  The set of registration b holds one 16-byte record per member pair: moving = the query index i into M, fixed =
+ *     the id into F, geo = (ex - f0)^2 + (ey - f1)^2 + (ez - f2)^2 in fp32, summed in this order, with no contraction (the rejection
+ *     rule's quantity; e = the transformed moving point, f = its fixed point), and weight, defined per source below.
+ *   - Order and layout.  Records are in ascending i.  A member's position is the number of members with a lower index: integer counts
+ *     per wave and per block of 256 consecutive pairs, then their prefix sums.  No atomics on positions; the result does not depend on
+ *     the launch shape.  Records at positions >= count are unspecified.  Each registration of a batched handle has its own set and
+ *     count; one launch set serves all of them; counts receives the counts of registrations 0 .. count - 1.
+ *   - ICP_PAIRS_EVALUATED: the member pairs are exactly the inliers of icp_evaluate's rule at the same max_dist (0 or +inf: no distance
+ *     test), from the same search at the current cumulative transform into the evaluation's own buffers: the handle's opt-in rules have
+ *     no influence, and the count equals icp_evaluate's n_inliers for the same arguments.  fixed is that search's id, weight = 1.0f.
+ *     It disturbs nothing, exactly as icp_evaluate promises: the per-query outputs, lazy outputs still to be reproduced, the state,
+ *     the partials and the cached graphs are as they were.
+ *   - ICP_PAIRS_LAST_ITERATION: the member pairs are the pairs the solver used in the last executed iteration: ICP_MEM_W[i] != 0.f (a
+ *     float comparison: a NaN weight is a member, -0 is none).  fixed = ICP_MEM_NN_ID[i].id, geo from the ICP_MEM_NN / ICP_MEM_QT xyz,
+ *     weight = ICP_MEM_W[i] (under a plane metric with a robust loss: the search's weight, as stated there).  max_dist must be 0.  The
+ *     four arrays are what icp_read would deliver at the moment of the call: lazy outputs are reproduced first, and the call returns
+ *     ICP_ESTATE exactly where icp_read (ICP_MEM_W) would — after a lazy run whose inputs have changed.  Rejection, the boundary and
+ *     normal rules, one-to-one, trimming and a point-to-point robust loss all show through W: the count equals ICP_MEM_TRIM's
+ *     accepted, ICP_MEM_UNIQUE's winners or ICP_MEM_PAIR_FILTER's accepted whenever that rule is the last one acting.
+ *   - icp_correspondences blocks: it first brings an open checked run to its end, as icp_read does, and returns after the counts have
+ *     reached the host.  The set stays readable until the next icp_correspondences, icp_init* or icp_destroy on the handle.
+ *   - icp_correspondences_read copies the `count` records of registration batch_index and writes count to *n (n may be NULL); with
+ *     capacity < count it copies nothing, writes count to *n and returns ICP_EINVAL; ICP_ESTATE when no set has been computed since
+ *     icp_init.  host_dst may be NULL when count is 0.
+ *   - icp_correspondences_device_ptr gives the device buffer of the registration's records (room for m of them) and its device count
+ *     word, for zero-copy use (either pointer may be NULL).  The pointers are valid from the first icp_correspondences until
+ *     icp_init* / icp_destroy; the buffers are allocated at that first call, each on its own, as icp_evaluate's are.  ICP_ESTATE before it.
+ * Cost: the device work behind the search (EVALUATED) or behind nothing (LAST_ITERATION) is two small passes over the pairs; a blocking
+ * call has icp_evaluate's shape — the same number of launches, a copy of the counts, the wait (INTEGRATION.md §5 has the figures).
+ * ICP_EINVAL: an unknown source, counts NULL, count 0 or above the batch, max_dist negative or NaN (LAST_ITERATION: not 0), batch_index
+ * out of range.  ICP_ESTATE: before icp_build_rbc, and on a handle that has tracked a frame since icp_init / icp_track_reset, as for
+ * icp_evaluate.  icp_batch_correspondences: one icp_correspondences on registration i's slot, then the records of registration i. */
+typedef struct { uint32_t moving, fixed; float geo, weight; } icp_pair_t;      /* 16 bytes */
+#define ICP_PAIRS_EVALUATED      0
+#define ICP_PAIRS_LAST_ITERATION 1
+int icp_correspondences (icp_handle h, int source, float max_dist, uint32_t *counts, uint32_t count);
+int icp_correspondences_read (icp_handle h, uint32_t batch_index, icp_pair_t *host_dst, uint32_t capacity, uint32_t *n);
+int icp_correspondences_device_ptr (icp_handle h, uint32_t batch_index, void **pairs, void **count_word);
+
 /* ---- adjacent steps -------------------------------------------------------------- */
 
 /* ICPLMs: getLMs — kernels/icp_kernels.cl:63-76, src/ICP/algorithms.cpp:621-785.
@@ -812,6 +854,9 @@ int icp_batch_run_fixed (icp_batch_handle b, uint32_t iterations, int from_ident
 int icp_batch_state (icp_batch_handle b, uint32_t i, icp_state_t *out);
 int icp_batch_read (icp_batch_handle b, uint32_t i, int mem, void *host_dst, size_t bytes);
 int icp_batch_evaluate (icp_batch_handle b, uint32_t i, float max_dist, icp_quality_t *out);   /* icp_evaluate: the record of registration i */
+/* icp_correspondences on registration i's slot, then icp_correspondences_read of registration i (capacity, *n and the codes as there) */
+int icp_batch_correspondences (icp_batch_handle b, uint32_t i, int source, float max_dist,
+                               icp_pair_t *host_dst, uint32_t capacity, uint32_t *n);
 int icp_batch_size (icp_batch_handle b, uint32_t *registrations, uint32_t *n_slots);
 /* wall-clock seconds of `reps` fixed-length passes (from the identity) on all slots at once = max over devices */
 int icp_batch_time_run_fixed (icp_batch_handle b, uint32_t iterations, uint32_t reps, double *seconds);
@@ -864,7 +909,7 @@ const char *icp_batch_last_error (icp_batch_handle b);   /* b may be NULL: error
  *
  * icp_pyramid_level hands out the BORROWED handle of a level.  Allowed on it: every setter and getter (modes, metric, normals,
  * rejection, trimming, robust loss, ..; they survive icp_pyramid_init as they survive icp_init), icp_read, icp_state, icp_evaluate,
- * icp_device_ptr, icp_transform_cloud, icp_sync and the diagnostics.  The grid widths of icp_set_normals and icp_set_boundary_rejection are per level
+ * icp_correspondences, icp_correspondences_read, icp_correspondences_device_ptr, icp_device_ptr, icp_transform_cloud, icp_sync and the diagnostics.  The grid widths of icp_set_normals and icp_set_boundary_rejection are per level
  * (side_l): the caller sets them level by level.  NOT allowed, because they would take the levels apart: icp_init*, icp_destroy,
  * icp_write / icp_write_cloud of F or M, icp_adopt_device_buffer and icp_track_*.
  *
