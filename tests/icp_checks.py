@@ -7,7 +7,10 @@ pytest rewrites `assert` only in the modules it collects, so every assert here c
 3. the weight-rule family (rejection, trimming, one-to-one, the pair filter, the robust loss on point-to-point): a feature's numpy rule
    names the rows that weigh nothing (`zero`), check_pieces compares the step with the oracle's pieces fed those rows zeroed;
 4. the plane family (point-to-plane, colored, plane-to-plane, symmetric, their robust forms): a `restate` callable wraps the metric's
-   float64 restatement, check_last compares the last iteration with it."""
+   float64 restatement, check_last compares the last iteration with it;
+5. the route of an iteration: every opt-in pass composed (composed_rule), the step checks against it, and the ICP_PAIRS_LAST_ITERATION
+   set against it (check_route_pairs);
+6. the scenes of the correspondence sets in every search layout (LAYOUT_CASES, layout_scene)."""
 import collections
 import functools
 
@@ -17,6 +20,8 @@ import colored_ref
 import gicp_ref
 import p2pl_ref
 import pair_filter_ref
+import pairs_ref
+import quality_ref
 import robust_ref
 import sym_ref
 import unique_ref
@@ -194,9 +199,11 @@ def oracle_search(oracle, F, M, T, nr):
     return o.nn_id, o.rid
 
 
-def pick_max_dist(oracle, F, M, T, nr, frac=0.12):
-    """A distance that rejects about `frac` of the pairs whose endpoints are both valid, at T."""
-    nn_id, _ = oracle_search(oracle, F, M, T, nr)
+def pick_max_dist(oracle, F, M, T, nr, frac=0.12, nn_id=None):
+    """A distance that rejects about `frac` of the pairs whose endpoints are both valid, at T (nn_id: the oracle's search at T, when the
+    caller has it already)."""
+    if nn_id is None:
+        nn_id, _ = oracle_search(oracle, F, M, T, nr)
     tM = oracle.transform_q(M, T)
     NN = F[nn_id["id"]]
     ok = ~((M[:, :3] == 0).all(axis=1) | (NN[:, :3] == 0).all(axis=1))
@@ -880,3 +887,86 @@ def check_route_plane_step(engine, g, F, M, NF, NM, T0, R0, k0, want, o, restate
     assert_bits(g.read(Mem.W, b), r.W_before_loss, "ICP_MEM_W (%s)" % what)
     check_last(engine, g, restate, T0, R0, k0, b, weights=r.W_before_loss)
     return r
+
+
+def last_stage_count(r, o, plane):
+    """(what decides, the number of pairs the iteration used) by include/icp_amd.h: the word of the last acting stage of o —
+    ICP_MEM_TRIM's accepted, else ICP_MEM_UNIQUE's winners, else ICP_MEM_PAIR_FILTER's accepted, with no stage on the pairs the search
+    left a weight —; a point-to-point loss acts behind all of them and may zero further weights: the pairs it leaves one."""
+    if not plane and o.loss is not None:
+        return "W'", int(np.count_nonzero(r.W))
+    if o.keep is not None:
+        return "TRIM", int(r.words["TRIM"][3])
+    if o.unique:
+        return "UNIQUE", int(r.words["UNIQUE"][1])
+    if o.gw or o.min_cos is not None:
+        return "PAIR_FILTER", int(r.words["PAIR_FILTER"][3])
+    return "W0", int(np.count_nonzero(r.W0))
+
+
+def check_route_pairs(engine, g, ids, PF, PM, r, plane, o, b, what):
+    """The ICP_PAIRS_LAST_ITERATION set of registration b behind a step with the passes of o on, against an expectation nothing of which
+    is read from the handle: ids = the oracle's nn_id at the step's T, PF = F[ids], PM = the oracle's transformed moving set, r = the
+    RouteResult of the step (a plane metric keeps the search's weight: W_before_loss; point-to-point shows the loss: W).  The count,
+    then the raw bytes; the count is the last acting stage's word (last_stage_count; the device's own word as well); `moving` ascends
+    strictly and every weight is ICP_MEM_W[moving] by its bits.  Returns the device's set."""
+    Mem = engine.Memory
+    want = pairs_ref.last_iteration(ids, r.W_before_loss if plane else r.W, PF[:, :4], PM[:, :4])
+    got = g.correspondences(engine.Pairs.LAST_ITERATION, batch_index=b)
+    pairs_ref.check_set(got, want, "the LAST_ITERATION set (%s)" % what)
+    name, n = last_stage_count(r, o, plane)
+    assert len(got) == n, "%s: %d records, the last acting stage (%s) leaves %d" % (what, len(got), name, n)
+    if name in ROUTE_WORDS:
+        word = int(g.read(getattr(Mem, name), b)[ROUTE_WORDS[name] - 1])
+        assert len(got) == word, "%s: %d records, ICP_MEM_%s says %d" % (what, len(got), name, word)
+    assert (np.diff(got["moving"].astype(np.int64)) > 0).all(), "%s: moving does not ascend strictly" % what
+    assert_bits(got["weight"], g.read(Mem.W, b)[got["moving"]], "the set's weights against ICP_MEM_W[moving] (%s)" % what)
+    return got
+
+
+# ---- 6. the correspondence sets in every search layout --------------------------------------------------------------------------------
+#
+# (side, |R|, batch, fused, zero_fraction of synth_pair or the name of a holes case, search_layout ()): test_stage2_lanes_as_candidates'
+# and test_holes_dense_layouts' shapes below 2^20 points.  One 256-tile with lanes = candidates; several 256-tiles with exact ties at the
+# origin, fused and in reference order; dense by batch with lanes = candidates and with the lanes of a query; the 1024-tile; the origin
+# list behind more than 1024 representatives.
+LAYOUT_CASES = [(256, 256, 1, True, 0.0, (1, 256, 1)), (256, 512, 1, True, 0.1, (1, 256, 1)), (256, 512, 1, False, 0.1, (1, 256, 1)),
+                (128, 64, 3, True, 0.0, (1, 256, 1)), (64, 64, 9, True, 0.0, (1, 256, 0)), (256, 8192, 1, True, 0.0, (1, 1024, 0)),
+                (192, 2048, 1, True, "blobs30", (1, 256, 0))]
+LAYOUT_KEEP = 0.75
+LayoutScene = collections.namedtuple("LayoutScene", "pairs T max_dist options wants PF PM rules")
+
+
+@functools.lru_cache(maxsize=None)
+def layout_scene(side, nr, batch, zero):
+    """The scene of a LAYOUT_CASES row, read-only, from the host-side generators and the oracle alone: a pair per registration (another
+    seed and rotation each, as test_stage2_lanes_as_candidates makes them — but the rotation grows with the registration, 3 + b / 2
+    degrees: with that test's 3 - 0.75 b the later frames of nine lie so close at _t0 () that max_dist rejects nothing, trimming keeps
+    3071 or 3072 pairs of every one of them and the evaluation holds all their points; here every registration has a count of its own
+    in both sets, tests/test_pairs_routes_cpu.py), T = _t0 (), max_dist by pick_max_dist on registration 0
+    (rounded to the engine's float), the options — rejection of invalid points and beyond max_dist, trimming to LAYOUT_KEEP, WEIGHTED —,
+    and per registration the oracle's (nn_id, rid) at T, PF = F[ids], PM = the transformed moving set and composed_rule's result."""
+    import icp_amd as engine
+    from oracle import oracle
+    if isinstance(zero, str):
+        pairs = [holes_pair(engine, side, 0x1C9D5EED + 11 * b, zero) for b in range(batch)]
+    else:
+        pairs = [engine.synth_pair(side, seed=0x1C9D5EED + 11 * b, rot_deg=3.0 + 0.5 * b, zero_fraction=zero) for b in range(batch)]
+    T = _t0()
+    wants = [oracle_search(oracle, F, M, T, nr) for F, M in pairs]
+    max_dist = float(np.float32(pick_max_dist(oracle, pairs[0][0], pairs[0][1], T, nr, nn_id=wants[0][0])))
+    o = RouteOptions(True, True, max_dist, None, None, False, LAYOUT_KEEP, None, None)
+    PF = [np.ascontiguousarray(F[w[0]["id"]]) for (F, _), w in zip(pairs, wants)]
+    PM = [oracle.transform_q(M, T) for _, M in pairs]
+    rules = [composed_rule(w[0], pf, pm, F, M, None, None, None, o) for (F, M), w, pf, pm in zip(pairs, wants, PF, PM)]
+    for a in [T] + [x for p in pairs for x in p] + [x for w in wants for x in w] + PF + PM:
+        a.flags.writeable = False
+    return LayoutScene(pairs, T, max_dist, o, wants, PF, PM, rules)
+
+
+def evaluated_expectation(oracle, F, M, T, nr, max_dist, want=None):
+    """(the ICP_PAIRS_EVALUATED set, quality_ref's Quality) from the oracle's search at T (want: that search, when the caller has it)."""
+    nn_id, _ = oracle_search(oracle, F, M, T, nr) if want is None else want
+    ids = nn_id["id"]
+    PF, PM = np.ascontiguousarray(F[ids][:, :4]), np.ascontiguousarray(oracle.transform_q(M, T)[:, :4])
+    return pairs_ref.evaluated(M, PF, PM, ids, max_dist), quality_ref.evaluate(M, PF, PM, max_dist)

@@ -12,6 +12,17 @@ import quality_ref
 PAIR = np.dtype([("moving", "<u4"), ("fixed", "<u4"), ("geo", "<f4"), ("weight", "<f4")])
 
 
+def check_set(got, want, what):
+    """A device's set against an expectation: the dtype, the count, then the records by their raw bytes."""
+    print(what, "device", len(got), "reference", len(want))
+    assert got.dtype == PAIR, (what, got.dtype)
+    assert len(got) == len(want), "%s: %d records, the reference has %d" % (what, len(got), len(want))
+    if got.tobytes() != want.tobytes():
+        a, b = got.view(np.uint32).reshape(-1, 4), want.view(np.uint32).reshape(-1, 4)
+        bad = np.nonzero((a != b).any(axis=1))[0]
+        raise AssertionError("%s: %d of %d records differ, first at %d: got %r want %r" % (what, bad.size, len(want), bad[0], got[bad[0]], want[bad[0]]))
+
+
 def _set(member, ids, geo, weight):
     idx = np.nonzero(member)[0]
     out = np.zeros(idx.size, PAIR)

@@ -111,6 +111,27 @@ def evaluate(M, PF, PM, max_dist):
     return Quality(sums, nm, ni, fitness, rmse, information_of(sums), counted, inlier, geo)
 
 
+def sums_of(q):
+    """The 22 device sums as the record carries them: the upper triangle of `information`, row-major, then sum_geo."""
+    A = q.information_matrix()
+    return np.array([A[a, c] for a in range(6) for c in range(a, 6)] + [q.sum_geo])
+
+
+def check_record(q, want, m, what):
+    """A device record (icp_quality_t) against evaluate's Quality: the counts exactly, the 22 sums and the information matrix by
+    their bits, fitness and the inlier RMSE within 1 ulp of the host formula."""
+    import icp_checks as K                               # (icp_checks imports this module through pairs_ref)
+    print(what, "device", q.n_moving, q.n_inliers, q.fitness, q.inlier_rmse, "reference", want.n_moving, want.n_inliers, want.fitness, want.inlier_rmse)
+    assert (q.n, q.n_moving, q.n_inliers, q.reserved) == (m, want.n_moving, want.n_inliers, 0), (what, q.n, q.n_moving, q.n_inliers)
+    K.assert_bits(sums_of(q), want.sums, "%s: the 22 sums" % what)
+    A = q.information_matrix()
+    assert np.array_equal(A, A.T) and not np.isnan(A).any(), what
+    K.assert_bits(A, want.information, "%s: information" % what)
+    fitness, rmse = host_numbers(q.sum_geo, q.n_moving, q.n_inliers)
+    assert abs(q.fitness - fitness) <= np.spacing(fitness), (what, q.fitness, fitness)
+    assert abs(q.inlier_rmse - rmse) <= np.spacing(rmse), (what, q.inlier_rmse, rmse)
+
+
 def independent(PF, inlier, geo):
     """An independent float64 statement: Open3D's three rows of G per pair, G^T G, every entry and geo summed with math.fsum.
     Returns (6 x 6 information, sum_geo)."""

@@ -13,6 +13,7 @@ import pytest
 import icp_checks as K
 import pairs_ref
 import quality_ref
+from pairs_ref import check_set
 
 pytestmark = pytest.mark.gpu
 
@@ -32,16 +33,6 @@ def expected(oracle, F, M, T, nr, max_dist):
     ids, PF, PM = search_at(oracle, F, M, T, nr)
     counted, _, _ = quality_ref.masks(M, PF, PM, max_dist)
     return pairs_ref.evaluated(M, PF, PM, ids, max_dist), int(np.count_nonzero(counted))
-
-
-def check_set(got, want, what):
-    print(what, "device", len(got), "reference", len(want))
-    assert got.dtype == pairs_ref.PAIR, (what, got.dtype)
-    assert len(got) == len(want), "%s: %d records, the reference has %d" % (what, len(got), len(want))
-    if got.tobytes() != want.tobytes():
-        a, b = got.view(np.uint32).reshape(-1, 4), want.view(np.uint32).reshape(-1, 4)
-        bad = np.nonzero((a != b).any(axis=1))[0]
-        raise AssertionError("%s: %d of %d records differ, first at %d: got %r want %r" % (what, bad.size, len(want), bad[0], got[bad[0]], want[bad[0]]))
 
 
 def plain(engine, side, nr, fused=True, batch=1, it=40):

@@ -11,6 +11,7 @@ import pytest
 import icp_checks as K
 import quality_ref
 import robust_ref
+from quality_ref import check_record
 
 pytestmark = pytest.mark.gpu
 
@@ -19,12 +20,6 @@ ESTATE, EINVAL = 4, 1
 
 def raw(q):
     return C.string_at(C.addressof(q), C.sizeof(q))
-
-
-def sums_of(q):
-    """The 22 device sums as the record carries them: the upper triangle of `information`, row-major, then sum_geo."""
-    A = q.information_matrix()
-    return np.array([A[a, c] for a in range(6) for c in range(a, 6)] + [q.sum_geo])
 
 
 def expected(oracle, F, M, T, nr, max_dist):
@@ -38,18 +33,6 @@ def expected(oracle, F, M, T, nr, max_dist):
 def non_trivial(want, what):
     share = want.n_inliers / want.n_moving
     assert 0.1 <= share <= 0.9, "%s: the reference accepts %d of %d counted points" % (what, want.n_inliers, want.n_moving)
-
-
-def check_record(q, want, m, what):
-    print(what, "device", q.n_moving, q.n_inliers, q.fitness, q.inlier_rmse, "reference", want.n_moving, want.n_inliers, want.fitness, want.inlier_rmse)
-    assert (q.n, q.n_moving, q.n_inliers, q.reserved) == (m, want.n_moving, want.n_inliers, 0), (what, q.n, q.n_moving, q.n_inliers)
-    K.assert_bits(sums_of(q), want.sums, "%s: the 22 sums" % what)
-    A = q.information_matrix()
-    assert np.array_equal(A, A.T) and not np.isnan(A).any(), what
-    K.assert_bits(A, want.information, "%s: information" % what)
-    fitness, rmse = quality_ref.host_numbers(q.sum_geo, q.n_moving, q.n_inliers)
-    assert abs(q.fitness - fitness) <= np.spacing(fitness), (what, q.fitness, fitness)
-    assert abs(q.inlier_rmse - rmse) <= np.spacing(rmse), (what, q.inlier_rmse, rmse)
 
 
 def plain(engine, side, nr, fused=True, batch=1, it=40):

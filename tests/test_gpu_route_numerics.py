@@ -13,6 +13,11 @@ candidates and keeps at least half; a first step's result words are compared wit
 on the device too.  A second step starts at the first's own T, which no proof covers (the frames lie closer, the normal rule at the
 same min_cos finds less to reject): there every pass must still remove some pair and keep half.
 
+Behind every step the ICP_PAIRS_LAST_ITERATION set of every registration is compared with the set composed_rule's weights give on the
+oracle's pairs (icp_checks.check_route_pairs: nothing of the expectation is read from the handle); with every pass on, beyond the grid,
+also ICP_PAIRS_EVALUATED and icp_evaluate at the T the step left, which the handle's options must not influence.
+tests/test_pairs_routes_cpu.py proves from the oracle alone that every expected set holds between 20 % and 90 % of the pairs.
+
 Shapes (test_route_table's): (30, 4), m = 900 — the last block of 64 / 128 / 256 pairs partly filled, the selection in one block —;
 (150, 4), m = 22500 — a side that is no multiple of 8, the three-pass selection, 352 blocks and so a k_moment_level1 tail."""
 import os
@@ -23,9 +28,11 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import p2pl_ref                                                  # noqa: E402
+import pairs_ref                                                 # noqa: E402
+import quality_ref                                               # noqa: E402
 import robust_ref as rref                                        # noqa: E402
-from icp_checks import (ROUTE_BATCH, ROUTE_METRICS, ROUTE_WORDS, assert_bits, before, check_route_plane_step, check_route_step,  # noqa: E402
-                        oracle_search, route_handle, route_proof, route_restate, route_scene, route_scene_options)
+from icp_checks import (ROUTE_BATCH, ROUTE_METRICS, ROUTE_WORDS, assert_bits, before, check_route_pairs, check_route_plane_step,  # noqa: E402
+                        check_route_step, evaluated_expectation, oracle_search, route_handle, route_proof, route_restate, route_scene, route_scene_options)
 
 pytestmark = pytest.mark.gpu
 
@@ -47,9 +54,26 @@ def _load(engine, g, scenes):
     return R0
 
 
-def _steps(engine, oracle, names, mask, metric, fused=None, loss=rref.CAUCHY, steps=2):
-    """`steps` steps of one handle over the scenes `names`, every registration of every step checked.  The first step starts at the
-    scene's T (its words are the CPU proof's), each later one at the step's own T."""
+def _check_evaluated(engine, oracle, g, scenes, Ts, wants, what):
+    """ICP_PAIRS_EVALUATED and icp_evaluate at the transforms Ts the step left, max_dist the scenes' own: every registration's set and
+    record bit for bit against the oracle's search there (wants), whatever passes and metric the handle has on."""
+    max_dist = scenes[0].max_dist
+    recs = g.evaluate(max_dist)
+    for b, (s, T, want) in enumerate(zip(scenes, Ts, wants)):
+        m = s.M.shape[0]
+        e, q = evaluated_expectation(oracle, s.F, s.M, T, s.nr, max_dist, want)
+        assert 0 < q.n_inliers < q.n_moving < m, (what, q.n_inliers, q.n_moving)
+        got = g.correspondences(engine.Pairs.EVALUATED, max_dist, batch_index=b)
+        pairs_ref.check_set(got, e, "the EVALUATED set (%s, registration %d)" % (what, b))
+        quality_ref.check_record(recs[b], q, m, "%s, registration %d" % (what, b))
+        assert len(got) == recs[b].n_inliers, (what, b, len(got), recs[b].n_inliers)
+
+
+def _steps(engine, oracle, names, mask, metric, fused=None, loss=rref.CAUCHY, steps=2, evaluated=False):
+    """`steps` steps of one handle over the scenes `names`, every registration of every step checked: the step itself, then the
+    ICP_PAIRS_LAST_ITERATION set against the oracle's pairs (check_route_pairs).  The first step starts at the scene's T (its words are
+    the CPU proof's), each later one at the step's own T.  evaluated: behind every step also the evaluation at the T it left
+    (_check_evaluated) — the oracle's search there is the next step's expectation as well.  Returns the last step's sets."""
     Mem = engine.Memory
     scenes = [route_scene(n) for n in names]
     s0 = scenes[0]
@@ -58,20 +82,32 @@ def _steps(engine, oracle, names, mask, metric, fused=None, loss=rref.CAUCHY, st
     g = route_handle(engine, s0.side, s0.nr, os_[0], metric, fused, batch=len(scenes))
     if len(scenes) > 1 and fused is not False:
         assert g.search_layout()[0] == 1, g.search_layout()       # (the dense layout by batch)
-    R0 = _load(engine, g, scenes)
+    _load(engine, g, scenes)
+    wants = [s.want for s in scenes]
     for it in range(steps):
         state = [before(engine, g, b) for b in range(len(scenes))]
         g.step()
+        sets = []
         for b, (s, o, name) in enumerate(zip(scenes, os_, names)):
             T0, Rb, k0 = state[b]
-            want = s.want if it == 0 else oracle_search(oracle, s.F, s.M, T0, s.nr)
+            want = wants[b]
             proof = route_proof(name, mask, loss)[0] if it == 0 else None
             what = "%s, scene %s, mask %d, loss %d, step %d" % (metric, name, mask, loss, it)
             if metric == "p2p":
-                check_route_step(engine, oracle, g, s.F, s.M, s.NF, s.NM, T0, Rb, want, o, fused, b, proof, what)
+                r = check_route_step(engine, oracle, g, s.F, s.M, s.NF, s.NM, T0, Rb, want, o, fused, b, proof, what)
             else:
-                check_route_plane_step(engine, g, s.F, s.M, s.NF, s.NM, T0, Rb, k0, want, o, route_restate(metric, o, s.M), b, proof, what)
+                r = check_route_plane_step(engine, g, s.F, s.M, s.NF, s.NM, T0, Rb, k0, want, o, route_restate(metric, o, s.M), b, proof, what)
+            PF, PM = (s.PF, s.PM) if it == 0 else (s.F[want[0]["id"]], oracle.transform_q(s.M, T0))
+            if it == 0:                                           # (the first step's weights from the reference's pairs too: the CPU proof's)
+                r = route_proof(name, mask, loss, metric != "p2p")[0]
+            sets.append(check_route_pairs(engine, g, want[0], PF, PM, r, metric != "p2p", o, b, what))
+        if evaluated or it + 1 < steps:
+            Ts = [g.read(Mem.T, b).copy() for b in range(len(scenes))]
+            wants = [oracle_search(oracle, s.F, s.M, T, s.nr) for s, T in zip(scenes, Ts)]
+        if evaluated:
+            _check_evaluated(engine, oracle, g, scenes, Ts, wants, "%s, mask %d, loss %d, behind step %d" % (metric, mask, loss, it))
     g.close()
+    return sets
 
 
 # ---- 1. the grid: every mask at both shapes ------------------------------------------------------------------------------------------
@@ -98,18 +134,31 @@ CASES = [("p2p", True), ("p2p", False)] + [(metric, None) for metric in ROUTE_ME
 @pytest.mark.parametrize("loss", [rref.HUBER, rref.TUKEY])
 @pytest.mark.parametrize("metric,fused", CASES)
 def test_every_pass_with_the_other_losses(engine, oracle, metric, fused, loss):
-    _steps(engine, oracle, ["30"], 15, metric, fused, loss)
+    _steps(engine, oracle, ["30"], 15, metric, fused, loss, evaluated=True)
+
+
+def test_tukey_zeroes_show_in_the_point_to_point_set_only(engine, oracle):
+    """Tukey's loss alone (mask 8) zeroes the pairs beyond its scale.  On point-to-point it acts on W, so those pairs leave the
+    LAST_ITERATION set; a plane metric carries the loss in its moments and keeps the search's weight, so they stay.  One step of a
+    point-to-plane handle and of a point-to-point one in either mode, each set against its expectation (_steps); the point-to-point
+    set is a strict subset of the plane one by `moving`.  (Under mask 15 trimming has already removed what Tukey would zero, and the
+    two sets are equal: tests/test_pairs_routes_cpu.py proves both statements from the oracle alone.)"""
+    plane = _steps(engine, oracle, ["30"], 8, "p2pl", None, rref.TUKEY, steps=1)[0]
+    for fused in MODES:
+        p2p = _steps(engine, oracle, ["30"], 8, "p2p", fused, rref.TUKEY, steps=1)[0]
+        assert 0 < len(p2p) < len(plane), (fused, len(p2p), len(plane))
+        assert np.isin(p2p["moving"], plane["moving"]).all(), fused
 
 
 @pytest.mark.parametrize("metric,fused", CASES[:3])
 def test_every_pass_in_a_batch_of_three(engine, oracle, metric, fused):
     """Three different scenes at (128, 64) in one handle, the dense layout by batch: each registration by its index."""
-    _steps(engine, oracle, list(ROUTE_BATCH), 15, metric, fused)
+    _steps(engine, oracle, list(ROUTE_BATCH), 15, metric, fused, evaluated=True)
 
 
 @pytest.mark.parametrize("metric,fused", CASES)
 def test_every_pass_at_config_A(engine, oracle, metric, fused):
-    _steps(engine, oracle, ["A"], 15, metric, fused)
+    _steps(engine, oracle, ["A"], 15, metric, fused, evaluated=True)
 
 
 # ---- 3. several iterations --------------------------------------------------------------------------------------------------------------
@@ -120,11 +169,12 @@ ANGLE, TRANSLATION, MAX_IT = 0.001, 0.01, 40                     # (icp_init's d
 
 def _snapshot(engine, g):
     Mem = engine.Memory
-    return [g.read(Mem.T).copy(), g.read(Mem.W).copy()] + [g.read(getattr(Mem, name)).copy() for name in ROUTE_WORDS]
+    return ([g.read(Mem.T).copy(), g.read(Mem.W).copy()] + [g.read(getattr(Mem, name)).copy() for name in ROUTE_WORDS]
+            + [g.correspondences(engine.Pairs.LAST_ITERATION).view(np.uint32)])
 
 
 def _same(a, b, what):
-    for x, y, name in zip(a, b, ("T", "W") + tuple(ROUTE_WORDS)):
+    for x, y, name in zip(a, b, ("T", "W") + tuple(ROUTE_WORDS) + ("the LAST_ITERATION set",)):
         assert_bits(x, y, "%s: %s" % (what, name))
 
 
