@@ -87,7 +87,7 @@ class TransformKind:             # ICPTransformConfig (include/ICP/algorithms.hp
 
 class Memory:                    # icp_mem in include/icp_amd.h
     F, M, T, TK, MEANS, S, NN_ID, W, SUM_W, REPS, RBC_N, RBC_O, RBC_PERM, RBC_OWNER, RBC_XP, RID, R, RK, NN, QT, TRIM, \
-        NORMALS_F, PLANE_SYSTEM, COLOR_GRAD_F, NORMALS_M, UNIQUE, PAIR_FILTER = range(27)
+        NORMALS_F, PLANE_SYSTEM, COLOR_GRAD_F, NORMALS_M, UNIQUE, PAIR_FILTER, RECIPROCAL, REVERSE_ID = range(29)
     # reference spellings (ICPStep::Memory, include/ICP/algorithms.hpp:2241-2267)
     D_IN_F, D_IN_M, D_IO_T, H_IO_T = F, M, T, T
 
@@ -183,6 +183,8 @@ def lib():
     sig("icp_get_trimming", i32, vp, C.POINTER(f32))
     sig("icp_set_unique", i32, vp, i32)
     sig("icp_get_unique", i32, vp, C.POINTER(i32))
+    sig("icp_set_reciprocal", i32, vp, i32, C.c_float)
+    sig("icp_get_reciprocal", i32, vp, C.POINTER(i32), C.POINTER(C.c_float))
     sig("icp_set_normal_rejection", i32, vp, i32, f32)
     sig("icp_get_normal_rejection", i32, vp, C.POINTER(i32), C.POINTER(f32))
     sig("icp_set_boundary_rejection", i32, vp, u32)
@@ -231,6 +233,7 @@ def lib():
     sig("icp_batch_set_rejection", i32, vp, i32, f32)
     sig("icp_batch_set_trimming", i32, vp, f32)
     sig("icp_batch_set_unique", i32, vp, i32)
+    sig("icp_batch_set_reciprocal", i32, vp, i32, C.c_float)
     sig("icp_batch_set_normal_rejection", i32, vp, i32, f32)
     sig("icp_batch_set_boundary_rejection", i32, vp, u32)
     sig("icp_batch_set_robust_loss", i32, vp, i32, f32)
@@ -621,6 +624,7 @@ _MEM_DTYPE = {
     Memory.NN: (np.float32, 4), Memory.QT: (np.float32, 4), Memory.TRIM: (np.uint32, None),
     Memory.NORMALS_F: (np.float32, 4), Memory.PLANE_SYSTEM: (np.float64, None), Memory.COLOR_GRAD_F: (np.float32, 4),
     Memory.NORMALS_M: (np.float32, 4), Memory.UNIQUE: (np.uint32, None), Memory.PAIR_FILTER: (np.uint32, None),
+    Memory.RECIPROCAL: (np.uint32, None), Memory.REVERSE_ID: (DIST_ID, None),
 }
 
 
@@ -756,6 +760,20 @@ class ICPStep:
         v = C.c_int32()
         self._chk(self._L.icp_get_unique(self._h, C.byref(v)))
         return bool(v.value)
+
+    def set_reciprocal(self, on=True, max_gap=0.0):
+        """Reciprocal correspondences (icp_set_reciprocal; not reference behaviour, off by default): a pair (m_i, f_j) keeps its weight
+        only if the moving point f_j finds when it searches the moving frame — a second RBC, over M, which the engine keeps up to date
+        by itself — is m_i, or lies within `max_gap` (the cloud's units) of it; every other pair gets the weight 0.  It acts after the
+        boundary and normal rules and before one-to-one correspondences, trimming and the robust loss.  read(Memory.RECIPROCAL) gives
+        the last iteration's (n, exact, near, accepted), read(Memory.REVERSE_ID) the back search's (dist, id) per fixed point."""
+        self._chk(self._L.icp_set_reciprocal(self._h, int(on), float(max_gap) if on else 0.0))
+
+    def reciprocal(self):
+        """max_gap of reciprocal correspondences, None while the rule is off."""
+        on, g = C.c_int32(), C.c_float()
+        self._chk(self._L.icp_get_reciprocal(self._h, C.byref(on), C.byref(g)))
+        return g.value if on.value else None
 
     def set_normal_rejection(self, min_cos=None):
         """Rejection by normal compatibility (icp_set_normal_rejection; not reference behaviour, off by default): a pair whose
@@ -1233,6 +1251,15 @@ class ICPBatch:
         """Whether one-to-one correspondences were last switched on for this batch."""
         return getattr(self, "_unique", False)
 
+    def set_reciprocal(self, on=True, max_gap=0.0):
+        """ICPStep.set_reciprocal on every registration (icp_batch_set_reciprocal)."""
+        self._chk(self._L.icp_batch_set_reciprocal(self._b, int(on), float(max_gap) if on else 0.0))
+        self._reciprocal = float(np.float32(max_gap)) if on else None
+
+    def reciprocal(self):
+        """max_gap of reciprocal correspondences as last set on this batch, None while the rule is off."""
+        return getattr(self, "_reciprocal", None)
+
     def set_normal_rejection(self, min_cos=None):
         """ICPStep.set_normal_rejection on every registration (icp_batch_set_normal_rejection)."""
         on = min_cos is not None
@@ -1329,6 +1356,7 @@ class ICPBatch:
         dt, cols = _MEM_DTYPE[mem]
         sizes = {Memory.T: 32, Memory.TK: 32, Memory.MEANS: 32, Memory.S: 44, Memory.NN_ID: self.m * 8, Memory.R: 36, Memory.RK: 36,
                  Memory.F: self.m * 32, Memory.M: self.m * 32, Memory.W: self.m * 4, Memory.RID: self.m * 4, Memory.TRIM: 16, Memory.UNIQUE: 8, Memory.PAIR_FILTER: 16,
+                 Memory.RECIPROCAL: 16, Memory.REVERSE_ID: self.m * 8,
                  Memory.NN: self.m * 16, Memory.QT: self.m * 16, Memory.NORMALS_F: self.m * 16, Memory.PLANE_SYSTEM: 28 * 8,
                  Memory.COLOR_GRAD_F: self.m * 16, Memory.NORMALS_M: self.m * 16}
         nbytes = sizes[mem]

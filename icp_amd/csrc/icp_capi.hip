@@ -34,6 +34,7 @@ void free_all (icp_context *h)
     h->dF = h->dM = nullptr; h->ownF = h->ownM = true;
     h->quality = icp_context::quality_buffers {};                 // (they were among dev_allocs)
     h->pairs = icp_context::pairs_buffers {};
+    h->recip = icp_reciprocal_set {};                              // (likewise; stale: the next handle's moving set is yet to be built)
     for (int k = 0; k < 2; ++k) {
         if (h->hBand[k]) (void) hipHostFree (h->hBand[k]);
         if (h->hFrame[k]) (void) hipHostFree (h->hFrame[k]);
@@ -76,8 +77,8 @@ uint32_t moving_normals_word (const icp_options &o)    // plane-to-plane and sym
 constexpr int reject_user_flags = ICP_REJECT_INVALID;    // the bits of `reject` that icp_set_rejection takes from the caller as they are
 void derive_params (const icp_options &o, icp_params &p)
 {
-    constexpr uint64_t sum = (uint64_t) ICP_REJECT_INVALID + ICP_REJECT_DIST_ON + ICP_REJECT_TRIM_ON + ICP_REJECT_ROBUST_MASK + ICP_REJECT_UNIQUE_ON + ICP_REJECT_FILTER_MASK;
-    static_assert (sum == (ICP_REJECT_INVALID | ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON | ICP_REJECT_FILTER_MASK),
+    constexpr uint64_t sum = (uint64_t) ICP_REJECT_INVALID + ICP_REJECT_DIST_ON + ICP_REJECT_TRIM_ON + ICP_REJECT_ROBUST_MASK + ICP_REJECT_UNIQUE_ON + ICP_REJECT_FILTER_MASK + ICP_REJECT_RECIPROCAL_ON;
+    static_assert (sum == (ICP_REJECT_INVALID | ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON | ICP_REJECT_FILTER_MASK | ICP_REJECT_RECIPROCAL_ON),
                    "every rule's bits in icp_params::reject are its own");
     static_assert (ICP_REJECT_INVALID == 1, "ks_epilogue tests bit 0");
     static_assert (ICP_ROBUST_TUKEY << ICP_REJECT_ROBUST_SHIFT == ICP_REJECT_ROBUST_MASK, "the loss's kind fills the mask's two bits");
@@ -87,7 +88,8 @@ void derive_params (const icp_options &o, icp_params &p)
     p.dist_scale = o.metric_scale;
     p.reject = (uint32_t) o.reject_flags | (dist ? ICP_REJECT_DIST_ON : 0u) | (trim ? ICP_REJECT_TRIM_ON : 0u)
              | ((uint32_t) o.robust << ICP_REJECT_ROBUST_SHIFT) | (o.unique ? ICP_REJECT_UNIQUE_ON : 0u)
-             | (o.boundary_gw ? ICP_REJECT_BOUNDARY_ON : 0u) | (o.normal_on ? ICP_REJECT_NORMAL_ON : 0u);
+             | (o.boundary_gw ? ICP_REJECT_BOUNDARY_ON : 0u) | (o.normal_on ? ICP_REJECT_NORMAL_ON : 0u)
+             | (o.reciprocal ? ICP_REJECT_RECIPROCAL_ON : 0u);
     p.reject_max_dist = o.reject_max_dist;
     p.reject_d2 = dist ? (float) ((double) o.reject_max_dist * (double) o.reject_max_dist) : 0.f;     // (the product of two floats is exact in double)
     p.trim_keep = trim ? o.trim_keep : 0.f;
@@ -98,7 +100,7 @@ void derive_params (const icp_options &o, icp_params &p)
 
 // The settings the kernels read from device words instead of captured arguments (a new value touches no graph): which value of the
 // record goes where.  write_words writes the chosen ones (OPT_WORDS: all) in stream order behind whatever the handle's stream holds.
-enum : unsigned { OPT_W_KAPPA = 1u, OPT_W_ROBUST = 2u, OPT_W_EPS = 4u, OPT_W_MIN_COS = 8u, OPT_W_GRID = 16u, OPT_WORDS = 31u };
+enum : unsigned { OPT_W_KAPPA = 1u, OPT_W_ROBUST = 2u, OPT_W_EPS = 4u, OPT_W_MIN_COS = 8u, OPT_W_GRID = 16u, OPT_W_GAP = 32u, OPT_WORDS = 63u };
 int write_words (icp_context *h, unsigned which)
 {
     const icp_options &o = h->opt;
@@ -110,6 +112,7 @@ int write_words (icp_context *h, unsigned which)
         { OPT_W_EPS, bits (o.gicp_eps), icp_gicp_eps (h->p) },
         { OPT_W_MIN_COS, bits (o.normal_min_cos), filter },
         { OPT_W_GRID, o.boundary_gw, filter + 1 },
+        { OPT_W_GAP, bits (o.reciprocal_gap), icp_reciprocal_gap (h->p) },
     };
     for (const auto &w : words)
         if (which & w.flag) HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (w.word), (int) w.value, 1, h->stream));
@@ -120,11 +123,12 @@ int write_words (icp_context *h, unsigned which)
 // changed (OPT_W_*), and whether the change is a parameter update (OPT_PARAMS: cached graphs are updated in place when next used), a
 // change of route (OPT_ROUTE: other kernels run, graphs are captured anew), or neither.  What follows from the parameters is found
 // by comparing them, old against new: the result area of a feature that went off is cleared (ICP_MEM_TRIM, ICP_MEM_UNIQUE,
-// ICP_MEM_PAIR_FILTER, ICP_MEM_PLANE_SYSTEM read zeros while it is off), and with grid normals a handle that now needs something its
+// ICP_MEM_PAIR_FILTER, ICP_MEM_RECIPROCAL, ICP_MEM_PLANE_SYSTEM read zeros while it is off), the moving set of reciprocal correspondences
+// is stale when the rule comes on (M may have been written while it was off), and with grid normals a handle that now needs something its
 // last buildRBC did not compute — the moving normals, the intensity gradients — needs a new buildRBC, as after a new F.
 // Device work in a fixed order: the open runs end, words, clears, then the stream is drained, so that work later enqueued on any of
 // the handle's streams sees them.  OPT_QUIESCE: the open runs end although nothing is written.
-enum : unsigned { OPT_PARAMS = 32u, OPT_ROUTE = 64u, OPT_QUIESCE = 128u };
+enum : unsigned { OPT_PARAMS = 64u, OPT_ROUTE = 128u, OPT_QUIESCE = 256u };
 int commit (icp_context *h, unsigned what)
 {
     const icp_params was = h->p;
@@ -132,8 +136,10 @@ int commit (icp_context *h, unsigned what)
     derive_params (h->opt, p);
     if (p.nrm_grid && ((icp_moving_normals (p) && !icp_moving_normals (was)) || (icp_colored (p) && !icp_colored (was)))) h->built = false;
     const bool off[] = { icp_trimming (was) && !icp_trimming (p), icp_unique (was) && !icp_unique (p),
-                         icp_pair_filter (was) && !icp_pair_filter (p), icp_p2pl (was) && !icp_p2pl (p) };
-    const bool clears = off[0] || off[1] || off[2] || off[3];
+                         icp_pair_filter (was) && !icp_pair_filter (p), icp_p2pl (was) && !icp_p2pl (p),
+                         icp_reciprocal (was) && !icp_reciprocal (p) };
+    const bool clears = off[0] || off[1] || off[2] || off[3] || off[4];
+    if (icp_reciprocal (p) && !icp_reciprocal (was)) h->recip.stale = true;
     if (h->inited && ((what & (OPT_WORDS | OPT_QUIESCE)) || clears)) {
         int rc = set_device (h); if (rc) return rc;
         if ((rc = run_close_all (h))) return rc;
@@ -141,8 +147,9 @@ int commit (icp_context *h, unsigned what)
         const struct { void *area; size_t bytes; } areas[] = {
             { icp_trim_area (p), sizeof (uint32_t) * 4u }, { icp_unique_area (p), sizeof (uint32_t) * 2u },
             { icp_pair_filter_area (p), sizeof (uint32_t) * 4u }, { icp_p2pl_area (p), sizeof (double) * ICP_P2PL_SYS },
+            { icp_reciprocal_area (p), sizeof (uint32_t) * 4u },
         };
-        for (int i = 0; i < 4; ++i) if (off[i]) HIPCHK (h, hipMemsetAsync (areas[i].area, 0, areas[i].bytes * p.batch, h->stream));
+        for (int i = 0; i < 5; ++i) if (off[i]) HIPCHK (h, hipMemsetAsync (areas[i].area, 0, areas[i].bytes * p.batch, h->stream));
         if ((what & OPT_WORDS) || clears) HIPCHK (h, hipStreamSynchronize (h->stream));
     }
     if (what & OPT_ROUTE) drop_graphs (h);
@@ -199,6 +206,27 @@ namespace icp_host {
 void normals_m_follow (icp_context *h, uint32_t b0, uint32_t nb)
 {
     if (icp_moving_normals (h->p) && h->p.nrm_grid && h->p.m % h->p.nrm_grid == 0u) icp_launch_normals_m (h->p, h->stream, b0, nb);
+    h->recip.stale = true;                           // (reciprocal correspondences: the moving set describes the old M)
+}
+
+int reciprocal_ready (icp_context *h)
+{
+    icp_reciprocal_set &rs = h->recip;
+    const icp_params &p = h->p;
+    const size_t n = (size_t) p.batch * p.m;
+    int rc = set_device (h); if (rc) return rc;
+    // (first need; each buffer on its own, zeroed: a call that ran out of memory half way leaves what it got to the next one)
+    if ((rc = icp_rbc_for_each (rs.rbc, p, [&] (const char *, void **q, size_t bytes) { return *q ? ICP_OK : dalloc (h, reinterpret_cast<char **> (q), bytes); }))) return rc;
+    if (!rs.st && (rc = dalloc (h, &rs.st, (size_t) p.batch))) return rc;
+    if (!rs.nn_id && (rc = dalloc (h, &rs.nn_id, n))) return rc;
+    if (!rs.PF && (rc = dalloc (h, &rs.PF, n))) return rc;
+    if (!rs.PM && (rc = dalloc (h, &rs.PM, n))) return rc;
+    if (!rs.rid && (rc = dalloc (h, &rs.rid, n))) return rc;
+    if (!rs.stale) return ICP_OK;
+    icp_launch_reciprocal_build (p, h->stream, rs);
+    HIPCHK (h, hipGetLastError ());
+    rs.stale = false;
+    return ICP_OK;
 }
 }  // namespace icp_host
 
@@ -428,6 +456,8 @@ static mem_desc mem_of (const icp_context *h, uint32_t b, int mem)
         case ICP_MEM_TRIM: return { icp_trim_area (p) + 4u * b, 16, nullptr };
         case ICP_MEM_UNIQUE: return { icp_unique_area (p) + 2u * b, 8, nullptr };
         case ICP_MEM_PAIR_FILTER: return { icp_pair_filter_area (p) + 4u * b, 16, nullptr };
+        case ICP_MEM_RECIPROCAL: return { icp_reciprocal_area (p) + 4u * b, 16, nullptr };
+        case ICP_MEM_REVERSE_ID: return { h->recip.nn_id ? h->recip.nn_id + b * m : nullptr, m * 8, nullptr };   // (allocated with the rule's first use)
         case ICP_MEM_NORMALS_F: return { icp_normals_f (p) + b * m, m * 16, "ICP_MEM_NORMALS_F" };
         case ICP_MEM_COLOR_GRAD_F: return { icp_color_grad_f (p) + b * m, m * 16, "ICP_MEM_COLOR_GRAD_F" };
         case ICP_MEM_NORMALS_M: return { icp_normals_m (p) + b * m, m * 16, "ICP_MEM_NORMALS_M" };
@@ -499,6 +529,7 @@ int icp_read_b (icp_handle h, uint32_t b, int mem, void *host_dst, size_t bytes)
     const mem_desc d = mem_of (h, b, mem);
     if (!d.bytes) return fail (h, ICP_EINVAL, "unknown icp_mem value");
     if (bytes > d.bytes) return fail (h, ICP_EINVAL, "icp_read: more bytes requested than the object holds");
+    if (!d.ptr) return fail (h, ICP_ESTATE, "icp_read: ICP_MEM_REVERSE_ID: no back search has run since icp_init (icp_set_reciprocal)");
     if ((rc = set_device (h))) return rc;
     const void *src = d.ptr;
     if ((rc = materialize_outputs (h, mem))) return rc;
@@ -521,6 +552,7 @@ int icp_device_ptr (icp_handle h, int mem, void **dptr) try
     if (!dptr) return fail (h, ICP_EINVAL, "null pointer");
     const mem_desc d = mem_of (h, 0, mem);
     if (!d.bytes) return fail (h, ICP_EINVAL, "unknown icp_mem value");
+    if (!d.ptr) return fail (h, ICP_ESTATE, "icp_device_ptr: ICP_MEM_REVERSE_ID: no back search has run since icp_init (icp_set_reciprocal)");
     if ((rc = set_device (h))) return rc;
     if ((rc = materialize_outputs (h, mem))) return rc;
     *dptr = const_cast<void *> (d.ptr);
@@ -534,7 +566,7 @@ int icp_adopt_device_buffer (icp_handle h, int mem, void *dptr) try
     int rc = need (h, false); if (rc) return rc;
     if (!dptr) return fail (h, ICP_EINVAL, "null pointer");
     if (mem == ICP_MEM_F) { h->dF = static_cast<float *> (dptr); h->p.F = h->dF; h->ownF = false; h->built = false; }
-    else if (mem == ICP_MEM_M) { h->dM = static_cast<float *> (dptr); h->p.M = h->dM; h->ownM = false; }
+    else if (mem == ICP_MEM_M) { h->dM = static_cast<float *> (dptr); h->p.M = h->dM; h->ownM = false; h->recip.stale = true; }
     else return fail (h, ICP_EINVAL, "only ICP_MEM_F and ICP_MEM_M can be adopted");
     note_inputs_change (h);
     drop_graphs (h);
@@ -556,6 +588,9 @@ int icp_build_rbc (icp_handle h) try
     icp_launch_build_rbc (h->p, h->stream);          // (plain launches: docs/HISTORY.md has the comparison with a cached graph)
     HIPCHK (h, hipGetLastError ());
     h->built = true; h->k_base = 0;                                 // (ICP::buildRBC resets k, :4796)
+    // (reciprocal correspondences: the moving set behind the fixed one, whatever the handle believes about M — the caller may have
+    // changed an adopted buffer)
+    if (icp_reciprocal (h->p)) { h->recip.stale = true; if ((rc = reciprocal_ready (h))) return rc; }
     return ICP_OK;
 }
 ICP_CATCH_ALL
@@ -569,7 +604,7 @@ int icp_step (icp_handle h, int config) try
     icp_params p = h->p; p.check = 0; p.hmirror = nullptr; p.hstate = nullptr;
     { const long long kb = h->k_base; note_enqueue (h); if (kb >= 0) h->k_base = kb + 1; }
     note_outputs_stored (h);
-    icp_launch_iteration (p, h->stream);
+    icp_launch_iteration (p, h->stream, &h->recip);
     HIPCHK (h, hipGetLastError ());
     return ICP_OK;
 }
@@ -780,6 +815,30 @@ int icp_get_unique (icp_handle h, int *on) try
     api_guard guard_ (h);
     if (!h || !on) return ICP_EINVAL;
     *on = h->opt.unique ? 1 : 0;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+// reciprocal correspondences (icp_reciprocal.hip).  On <-> off changes which kernels run — the REJ search, the inverse transform, the back
+// search and the test, on point-to-point the apply pass, no chained form —: a change of route.  A new max_gap while the rule stays on goes
+// to its device word alone: no graph is touched.  The moving set is built by the next call that enqueues an iteration (need).
+int icp_set_reciprocal (icp_handle h, int on, float max_gap) try
+{
+    api_guard guard_ (h);
+    if (on != 0 && on != 1) return fail (h, ICP_EINVAL, "icp_set_reciprocal: on must be 0 or 1");
+    if (!(max_gap >= 0.f && std::isfinite (max_gap))) return fail (h, ICP_EINVAL, "icp_set_reciprocal: max_gap must be finite and >= 0");
+    if (!h) return fail (h, ICP_EINVAL, "icp_set_reciprocal: null handle");
+    { int rc = outputs_before_change (h); if (rc) return rc; }
+    const bool was = h->opt.reciprocal;
+    h->opt.reciprocal = on != 0; h->opt.reciprocal_gap = on ? max_gap : 0.f;
+    return commit (h, h->opt.reciprocal != was ? OPT_ROUTE | OPT_W_GAP : on ? OPT_W_GAP : 0u);
+}
+ICP_CATCH_ALL
+int icp_get_reciprocal (icp_handle h, int *on, float *max_gap) try
+{
+    api_guard guard_ (h);
+    if (!h) return ICP_EINVAL;
+    if (on) *on = h->opt.reciprocal ? 1 : 0;
+    if (max_gap) *max_gap = h->opt.reciprocal_gap;
     return ICP_OK;
 }
 ICP_CATCH_ALL
@@ -1359,7 +1418,7 @@ int icp_time_masked (icp_handle h, uint32_t mask, uint32_t iterations, uint32_t 
     graph_entry ge;
     // (the per-query outputs follow the policy of the fixed-length graphs: stored by the last iteration only in fused mode)
     if ((rc = capture_graph (h, [&] {
-             for (uint32_t k = 0; k < iterations; ++k) { p.emit = (k + 1 == iterations) ? 1 : 0; icp_launch_masked (p, h->stream, mask); }
+             for (uint32_t k = 0; k < iterations; ++k) { p.emit = (k + 1 == iterations) ? 1 : 0; icp_launch_masked (p, h->stream, mask, &h->recip); }
          }, &ge))) return rc;
     hipError_t e = hipGraphLaunch (ge.exec, h->stream);                 // warm-up
     if (e == hipSuccess) e = hipEventRecord (h->ev0, h->stream);
@@ -1389,7 +1448,7 @@ int icp_debug_stamps (icp_handle h, unsigned long long *out, uint32_t nblocks) t
     note_enqueue (h); note_outputs_stored (h);
     if (e == hipSuccess) {
         if (icp_route_of (p).chained) icp_launch_chain (p, h->stream, 2);
-        else icp_launch_masked (p, h->stream, p.fused ? 1u | 8u : 1u);
+        else icp_launch_masked (p, h->stream, p.fused ? 1u | 8u : 1u, &h->recip);
         e = hipGetLastError ();
     }
     if (e == hipSuccess) e = hipStreamSynchronize (h->stream);
@@ -1414,9 +1473,9 @@ int icp_profile_run (icp_handle h, uint32_t iterations, float *out_ms, float *to
     // the stages as separate launches (the chained form has no stage boundaries to time), events around each
     for (uint32_t r = 0; r < iterations && e == hipSuccess; ++r) {
         hipEvent_t *x = &ev[(size_t) r * 5];
-        e = hipEventRecord (x[0], h->stream);                                             // (trimming, one-to-one, the pair filter on: their passes time with the search)
+        e = hipEventRecord (x[0], h->stream);                                             // (trimming, one-to-one, the pair filter, reciprocal correspondences on: their passes time with the search)
         for (int k = 0; k < 4; ++k) {
-            icp_launch_masked (p, h->stream, 1u << k);
+            icp_launch_masked (p, h->stream, 1u << k, &h->recip);
             if (e == hipSuccess) e = hipEventRecord (x[k + 1], h->stream);
         }
     }

@@ -83,6 +83,7 @@ struct icp_options {
     int reject_flags = 0; float reject_max_dist = 0.f;      // icp_set_rejection
     float trim_keep = 1.f;                       // icp_set_trimming (1: off)
     bool unique = false;                         // icp_set_unique
+    bool reciprocal = false; float reciprocal_gap = 0.f;    // icp_set_reciprocal (0 while off); device word icp_reciprocal_gap
     bool normal_on = false; float normal_min_cos = 0.f;     // icp_set_normal_rejection (0 while off); device word icp_pair_filter_settings [0]
     uint32_t boundary_gw = 0;                    // icp_set_boundary_rejection (0: off); device word icp_pair_filter_settings [1]
     int robust = ICP_ROBUST_NONE; float robust_scale = 0.f; // icp_set_robust_loss (0 while off); device word icp_robust_scale
@@ -149,6 +150,9 @@ struct icp_context {
         uint32_t *blk = nullptr; uint4 *rec = nullptr; uint32_t *count = nullptr;
         std::vector<uint32_t> n; bool valid = false;
     } pairs;
+    // reciprocal correspondences' own buffers (icp_rbc_set.h; allocated when the rule is first needed, each on its own; freed with the others
+    // by icp_init): the moving set, the reverse state, the back search's per-query outputs — and whether the moving set is stale
+    icp_reciprocal_set recip;
     float *dCloud = nullptr, *dCloudOut = nullptr; uint32_t cloud_cap = 0;
     std::map<uint64_t, icp_host::graph_entry> graphs;      // key: iterations << 3 | check << 2 | parity (+ fresh, + kind: see get_graph)
     uint32_t parity = 0;                         // tracking: which landmark buffers are the fixed / moving set (graphs hold pointers): frame f -> f mod 3
@@ -246,7 +250,11 @@ void note_outputs_stored (icp_context *h);
 int materialize_outputs (icp_context *h, int mem);
 // ---- icp_capi.hip ---------------------------------------------------------------------------------------------------------------
 // what every write of M does behind its copy (icp_write, icp_write_cloud, icp_pyramid_write): with ICP_NORMALS_GRID the moving normals follow
+// (and the moving set of reciprocal correspondences goes stale)
 void normals_m_follow (icp_context *h, uint32_t b0, uint32_t nb);
+// reciprocal correspondences: the rule's buffers exist and the moving set describes M — allocated at the first need, rebuilt on the handle's
+// stream when stale.  need (h, true) calls it in front of every enqueue of an iteration; icp_build_rbc behind the fixed set's construction.
+int reciprocal_ready (icp_context *h);
 
 // Captures the launches `launches ()` enqueues on the handle's stream into a graph (instantiate: also into an executable one).
 // Whatever fails, the stream has left capture mode and nothing is leaked when this returns.

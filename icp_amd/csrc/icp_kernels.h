@@ -129,6 +129,7 @@ struct icp_params {
 #define ICP_REJECT_BOUNDARY_ON 0x04000000u   // icp_params::reject: boundary rejection is on (icp_set_boundary_rejection: the REJ kernels, plus k_pair_filter: icp_launch_pair_filter)
 #define ICP_REJECT_NORMAL_ON 0x02000000u   // icp_params::reject: rejection by normal compatibility is on (icp_set_normal_rejection: likewise; the moving frame's normals are needed)
 #define ICP_REJECT_FILTER_MASK (ICP_REJECT_BOUNDARY_ON | ICP_REJECT_NORMAL_ON)
+#define ICP_REJECT_RECIPROCAL_ON 0x01000000u   // icp_params::reject: reciprocal correspondences are on (icp_set_reciprocal: the REJ kernels, plus the back search and k_reciprocal: icp_launch_reciprocal)
 static_assert (sizeof (icp_params) == 480, "icp_params grew: the hidden kernel arguments of every kernel would move");
 
 // rejection on: the sum-W formulas in every mode, and a step of nothing accepted (sum W == 0) is the identity
@@ -138,6 +139,8 @@ static __host__ __device__ __forceinline__ bool icp_trimming (const icp_params &
 static __host__ __device__ __forceinline__ bool icp_unique (const icp_params &p) { return (p.reject & ICP_REJECT_UNIQUE_ON) != 0u; }
 // the pair filter (icp_pair_filter.hip): rejection at the fixed grid's boundary and / or by normal compatibility, one pass behind the search
 static __host__ __device__ __forceinline__ bool icp_pair_filter (const icp_params &p) { return (p.reject & ICP_REJECT_FILTER_MASK) != 0u; }
+// reciprocal correspondences (icp_reciprocal.hip): a candidate keeps its weight only if its fixed point's back search into M finds it again
+static __host__ __device__ __forceinline__ bool icp_reciprocal (const icp_params &p) { return (p.reject & ICP_REJECT_RECIPROCAL_ON) != 0u; }
 // the moving frame's normals are needed: by a metric (p.gicp: plane-to-plane, symmetric) or by normal rejection, whatever the metric
 static __host__ __device__ __forceinline__ bool icp_moving_normals (const icp_params &p) { return p.gicp != 0u || (p.reject & ICP_REJECT_NORMAL_ON) != 0u; }
 // the robust loss's kind (ICP_ROBUST_HUBER 1, CAUCHY 2, TUKEY 3; 0: off).  Its scale k is a device word (icp_robust_scale).
@@ -193,6 +196,7 @@ struct icp_mom_layout {
     size_t uniq;                 // one-to-one correspondences: [batch][2] uint32 result words (icp_unique_area), [batch][m] uint64 claim table (icp_unique_claims)
     size_t filt;                 // the pair filter's uint32 words (icp_pair_filter_area): [batch][4] ICP_MEM_PAIR_FILTER, [batch][8] the blocks' running
                                  // counts and their arrival counter, then min_cos (float) and the boundary rule's grid width
+    size_t recip;                // reciprocal correspondences' uint32 words (icp_reciprocal_area): [batch][4] ICP_MEM_RECIPROCAL, then max_gap (float)
     size_t total;
 };
 static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (uint32_t batch, uint32_t m, uint32_t nb)
@@ -207,7 +211,8 @@ static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (uint32_t bat
     l.gicp = l.robust + 1u;
     l.uniq = l.gicp + 1u;
     l.filt = l.uniq + B + B * m;
-    l.total = l.filt + 6u * B + 1u;
+    l.recip = l.filt + 6u * B + 1u;
+    l.total = l.recip + 2u * B + 1u;
     return l;
 }
 static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (const icp_params &p) { return icp_mom_layout_of (p.batch, p.m, p.nb); }
@@ -230,6 +235,11 @@ static inline unsigned long long *icp_unique_claims (const icp_params &p)
 static inline uint32_t *icp_pair_filter_area (const icp_params &p) { return reinterpret_cast<uint32_t *> (p.mom + icp_mom_layout_of (p).filt); }
 static inline uint32_t *icp_pair_filter_counts (const icp_params &p) { return icp_pair_filter_area (p) + 4u * (size_t) p.batch; }
 static inline uint32_t *icp_pair_filter_settings (const icp_params &p) { return icp_pair_filter_area (p) + 12u * (size_t) p.batch; }
+// Reciprocal correspondences (icp_reciprocal.hip), uint32 words: [batch][4] the result of the last iteration (n, exact, near, accepted:
+// ICP_MEM_RECIPROCAL; k_reciprocal_state resets them, k_reciprocal's blocks add their counts), then the setting the kernel reads instead
+// of capturing it: max_gap (float; the kernel squares it in double).
+static inline uint32_t *icp_reciprocal_area (const icp_params &p) { return reinterpret_cast<uint32_t *> (p.mom + icp_mom_layout_of (p).recip); }
+static inline uint32_t *icp_reciprocal_gap (const icp_params &p) { return icp_reciprocal_area (p) + 4u * (size_t) p.batch; }
 
 // The XP allocation of one RBC set, offsets in floats: [batch][m][8] the permuted database, then [batch][m] float4 NORMALS_F and
 // [batch][m] float4 COLOR_GRAD_F ([gx gy gz C] per fixed point).  The normals and gradients belong to the fixed frame as the RBC does,
@@ -325,6 +335,7 @@ struct icp_route {
     bool stored;                 // the search stores its per-query outputs every iteration: a pass or the plane moments read them
     bool ref_search;             // the search in its reference-order form whatever p.fused (the plane metrics)
     bool filter;                 // k_pair_filter
+    bool reciprocal;             // k_reciprocal_state + the back search + k_reciprocal (icp_launch_reciprocal)
     bool unique;                 // k_unique_claim + k_unique_resolve
     uint32_t select;             // trimming's selection: 0, 1 (k_trim_select) or 3 launches (k_trim_select_pass<0 .. 2>)
     icp_apply_kind apply;        // the pass that writes the search's partials again from the weights
@@ -336,9 +347,12 @@ icp_route icp_route_of (const icp_params &p);
 // launchers (icp_kernels.hip, icp_build.hip)
 void icp_launch_build_rbc (const icp_params &p, hipStream_t s);
 void icp_launch_search (const icp_params &p, hipStream_t s);
-void icp_launch_iteration (const icp_params &p, hipStream_t s);
+// rs: what reciprocal correspondences keep outside icp_params (icp_reciprocal_set, icp_rbc_set.h: the moving set, the reverse state, the
+// back search's outputs); a route with the rule on needs it, every other ignores it
+struct icp_reciprocal_set;
+void icp_launch_iteration (const icp_params &p, hipStream_t s, const icp_reciprocal_set *rs = nullptr);
 // any subset of an iteration's stages (bit 0 the search with the passes behind it, 1 means, 2 sij, 3 finalize; 4: an empty kernel)
-void icp_launch_masked (const icp_params &p, hipStream_t s, unsigned mask);
+void icp_launch_masked (const icp_params &p, hipStream_t s, unsigned mask, const icp_reciprocal_set *rs = nullptr);
 void icp_launch_chain (const icp_params &p, hipStream_t s, uint32_t iterations, bool fresh = false);
 void icp_launch_chain_one (const icp_params &p, hipStream_t s, uint32_t j, bool fresh, bool emit);   // launch j of a chain (j = 0: reads the user-visible state)
 void icp_launch_chain_end (const icp_params &p, hipStream_t s, uint32_t launches);                  // after `launches` chained launches: the last moments -> p.st (and p.hstate)
@@ -353,6 +367,8 @@ void icp_launch_chain_one_rej (const icp_params &p, hipStream_t s, uint32_t j, b
 void icp_launch_trim_select (const icp_params &p, hipStream_t s, uint32_t launches);   // icp_trim.hip: k_trim_select (1) or k_trim_select_pass<0 .. 2> (3: icp_route::select)
 void icp_launch_trim_apply (const icp_params &p, hipStream_t s);             // icp_trim.hip: k_trim_apply<fused?>
 void icp_launch_unique (const icp_params &p, hipStream_t s);                 // icp_unique.hip: k_unique_claim + k_unique_resolve
+void icp_launch_reciprocal (const icp_params &p, hipStream_t s, const icp_reciprocal_set *rs);   // icp_reciprocal.hip: k_reciprocal_state + the back search + k_reciprocal
+void icp_launch_reciprocal_build (const icp_params &p, hipStream_t s, const icp_reciprocal_set &rs);   // icp_reciprocal.hip: buildRBC over M into the moving set
 void icp_launch_pair_filter (const icp_params &p, hipStream_t s);            // icp_pair_filter.hip: k_pair_filter (boundary and / or normal rejection), behind the search
 void icp_launch_robust_apply (const icp_params &p, hipStream_t s);            // icp_robust.hip: k_trim_apply_robust<fused?> (a point-to-point robust loss)
 void icp_launch_plane_moments_robust (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);   // icp_robust.hip: k_plane_moments_robust<colored?>

@@ -546,8 +546,10 @@ void icp_launch_search (const icp_params &p, hipStream_t s)
 //     filter, one-to-one correspondences or a robust loss on: an apply pass too — the filter and the resolve pass have zeroed weights
 //     behind the search's partials, the loss weighs every pair in its instantiation of the pass.  The plane metrics read the weights,
 //     and carry the loss, in their moments: no pass for them unless trimming is on.
-//   - The order: k_pair_filter first (a pair it rejects claims no fixed point), claim and resolve in front of trimming's selection (its
-//     candidates are the winners), the apply pass last.
+//   - Reciprocal correspondences (icp_reciprocal.hip): the state kernel, the back search and k_reciprocal, three launches; point-to-point:
+//     an apply pass too, as for one-to-one.
+//   - The order: k_pair_filter first (a pair it rejects claims no fixed point), then the reciprocal rule (its candidates are the pairs
+//     the filter leaves), claim and resolve in front of trimming's selection (its candidates are the winners), the apply pass last.
 //   - Whatever reads the per-query outputs between the search and the tail — a pass, the plane moments — has them stored every
 //     iteration and rules the chained form out (it folds the finalize into the next search).  The plane metrics (icp_p2pl.hip) take the
 //     search in its reference-order form whatever the reduce mode: the same outputs, and its prologue publishes every iteration's
@@ -563,15 +565,16 @@ icp_route icp_route_of (const icp_params &p)
     icp_route r {};
     r.launches = 1u;                                                              // the search
     r.filter = icp_pair_filter (p);                                               r.launches += r.filter ? 1u : 0u;
+    r.reciprocal = icp_reciprocal (p);                                            r.launches += r.reciprocal ? 3u : 0u;
     r.unique = icp_unique (p);                                                    r.launches += r.unique ? 2u : 0u;
     r.select = !icp_trimming (p) ? 0u : p.m <= ICP_TRIM_ONE_BLOCK_MAX ? 1u : 3u;  r.launches += r.select;
-    const bool pass = r.select || p2p_loss || (!plane && (r.filter || r.unique));
+    const bool pass = r.select || p2p_loss || (!plane && (r.filter || r.reciprocal || r.unique));
     r.apply = !pass ? ICP_APPLY_NONE : p2p_loss ? ICP_APPLY_ROBUST : ICP_APPLY_PLAIN;   r.launches += pass ? 1u : 0u;
     const bool level1 = (p.nb + 127u) / 128u > ICP_L1_MIN_GROUPS && p.ml1;        // (as k_finalize_fused decides where its first level comes from)
     r.tail = plane ? ICP_TAIL_PLANE : !p.fused ? ICP_TAIL_REFERENCE : level1 ? ICP_TAIL_FUSED_L1 : ICP_TAIL_FUSED;
     r.launches += r.tail == ICP_TAIL_REFERENCE ? 3u : r.tail == ICP_TAIL_FUSED ? 1u : 2u;
     r.ref_search = plane;
-    r.stored = plane || r.apply != ICP_APPLY_NONE;
+    r.stored = plane || r.apply != ICP_APPLY_NONE;                                // (the reciprocal rule on a plane metric: plane; on point-to-point: the pass)
     r.chained = p.fused && !r.stored && p.nb <= 4096u && p.nr <= 1024u && (p.chain == 2 || (p.chain == 1 && !icp_dense (p)));
     if (r.chained) r.launches = 1u;
     return r;
@@ -615,7 +618,7 @@ static void launch_finalize (const icp_params &p, hipStream_t s, icp_tail_kind t
 __global__ void k_nop (icp_params p) { if (p.m == 0xFFFFFFFFu) p.st->k = 0; }
 
 // the search of an iteration and the passes behind it, as the route says
-static void launch_search_stage (const icp_params &p, hipStream_t s, const icp_route &r)
+static void launch_search_stage (const icp_params &p, hipStream_t s, const icp_route &r, const icp_reciprocal_set *rs)
 {
     if (!r.stored) { icp_launch_search (p, s); return; }
     icp_params q = p;
@@ -623,6 +626,7 @@ static void launch_search_stage (const icp_params &p, hipStream_t s, const icp_r
     if (r.ref_search) q.fused = 0;
     icp_launch_search (q, s);
     if (r.filter) icp_launch_pair_filter (q, s);
+    if (r.reciprocal) icp_launch_reciprocal (q, s, rs);
     if (r.unique) icp_launch_unique (q, s);
     if (r.select) icp_launch_trim_select (q, s, r.select);
     if (r.apply == ICP_APPLY_ROBUST) icp_launch_robust_apply (q, s);
@@ -631,17 +635,17 @@ static void launch_search_stage (const icp_params &p, hipStream_t s, const icp_r
 
 // An iteration stage by stage, the only spelling of it: icp_launch_iteration is every stage, the diagnostics (icp_time_masked,
 // icp_profile_run, icp_debug_stamps) take subsets (bit 0 the search with the passes behind it, 1 means, 2 sij, 3 finalize, 4 an empty kernel)
-void icp_launch_masked (const icp_params &p, hipStream_t s, unsigned mask)
+void icp_launch_masked (const icp_params &p, hipStream_t s, unsigned mask, const icp_reciprocal_set *rs)
 {
     const icp_route r = icp_route_of (p);
-    if (mask & 1u) launch_search_stage (p, s, r);
+    if (mask & 1u) launch_search_stage (p, s, r, rs);
     if ((mask & 2u) && r.tail == ICP_TAIL_REFERENCE) launch_means (p, s);
     if ((mask & 4u) && r.tail == ICP_TAIL_REFERENCE) launch_sij (p, s);
     if (mask & 8u) launch_finalize (p, s, r.tail);
     if (mask & 16u) hipLaunchKernelGGL (k_nop, dim3 (256, p.batch), dim3 (64), 0, s, p);
 }
 
-void icp_launch_iteration (const icp_params &p, hipStream_t s) { icp_launch_masked (p, s, 15u); }
+void icp_launch_iteration (const icp_params &p, hipStream_t s, const icp_reciprocal_set *rs) { icp_launch_masked (p, s, 15u, rs); }
 
 // launch j of a chain (icp_search.h: ks_launch_chain_one)
 void icp_launch_chain_one (const icp_params &p, hipStream_t s, uint32_t j, bool fresh, bool emit)

@@ -61,3 +61,16 @@ inline icp_rbc_set icp_rbc_of (const icp_params &p)
 #undef X
     return s;
 }
+
+// What reciprocal correspondences (icp_set_reciprocal, icp_reciprocal.hip) keep per handle: the moving set — an RBC over M, built by
+// buildRBC's own launches —, the reverse state ([batch] icp_reg_state: T = the inverse transform, the rest the run's), and the back
+// search's per-query outputs ([batch][m] each; nn_id is ICP_MEM_REVERSE_ID).  icp_params has no room for the pointers: the route's
+// launchers take this record beside it.  Allocated when the rule is first needed on an initialised handle, each buffer on its own.
+// stale: the moving set does not describe M (M was written, the rule was switched on after icp_build_rbc, icp_init): the next call
+// that enqueues an iteration rebuilds it first.
+struct icp_reciprocal_set {
+    icp_rbc_set rbc;
+    icp_reg_state *st = nullptr;
+    icp_dist_id *nn_id = nullptr; float4 *PF = nullptr, *PM = nullptr; uint32_t *rid = nullptr;
+    bool stale = true;
+};

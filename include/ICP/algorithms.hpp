@@ -625,6 +625,13 @@ namespace ICP
         void setUnique (bool on) { check (icp_set_unique (h, on ? 1 : 0)); }
         bool getUnique () { int on = 0; check (icp_get_unique (h, &on)); return on != 0; }
 
+        /*! \brief Reciprocal correspondences (icp_set_reciprocal, include/icp_amd.h; not in the reference, off by default): a pair keeps
+         *         its weight only if its fixed point, searching the moving frame, finds the pair's moving point again or one within
+         *         max_gap of it; the others get weight 0.  It acts after the boundary and normal rules and before one-to-one
+         *         correspondences, trimming and the robust loss. */
+        void setReciprocal (bool on, float max_gap = 0.f) { check (icp_set_reciprocal (h, on ? 1 : 0, on ? max_gap : 0.f)); }
+        bool getReciprocal (float *max_gap = nullptr) { int on = 0; float g = 0.f; check (icp_get_reciprocal (h, &on, &g)); if (max_gap) *max_gap = g; return on != 0; }
+
         /*! \brief Rejection by normal compatibility (icp_set_normal_rejection, include/icp_amd.h; not in the reference, off by
          *         default): a pair whose two normals enclose an angle with a cosine below min_cos gets weight 0.  It needs both frames'
          *         normals (setNormals) and acts before one-to-one correspondences, trimming and the robust loss. */

@@ -92,6 +92,8 @@ typedef enum {
     ICP_MEM_NORMALS_M = 24,    /* io m x float4  normals of the moving landmarks [nx ny nz 0], indexed like M (plane-to-plane, symmetric) */
     ICP_MEM_UNIQUE = 25,       /* out uint32[2]   one-to-one correspondences, last iteration: candidates n, winners (0 when off) */
     ICP_MEM_PAIR_FILTER = 26,  /* out uint32[4]   boundary / normal rejection, last iteration: n, at_boundary, incompatible, accepted (0 when off) */
+    ICP_MEM_RECIPROCAL = 27,   /* out uint32[4]   reciprocal correspondences, last iteration: n, exact, near, accepted (0 when off) */
+    ICP_MEM_REVERSE_ID = 28,   /* out m x {dist,id}  reciprocal correspondences: the back search, fixed-point order, id = index into M */
     ICP_MEM_COUNT_
 } icp_mem;
 
@@ -304,6 +306,65 @@ int icp_get_trimming (icp_handle h, float *keep_fraction);
  * its passes into the search stage.  ICP_EINVAL: on outside {0, 1}. */
 int icp_set_unique (icp_handle h, int on);
 int icp_get_unique (icp_handle h, int *on);
+
+/* Reciprocal (forward-backward consistent) correspondences (PCL: setUseReciprocalCorrespondences,
+ * CorrespondenceEstimation::determineReciprocalCorrespondences; libpointmatcher; Rusinkiewicz & Levoy's matching taxonomy; not reference
+ * behaviour): a pair (m_i, f_j) is kept only if the moving point that f_j finds when it searches the moving frame is m_i itself, or
+ * lies next to it.  It is the usual answer to partial overlap: icp_set_unique keeps the closest of the pairs that share a fixed point,
+ * but cannot tell that f_j has a much better partner that no query happened to pick.  The rule:
+ *   - on is 0 or 1.  0 is the default and means off: the same kernels, launches, graphs and bits as without the rule; the getter then
+ *     gives (0, 0.f).  max_gap is finite and >= 0, in the cloud's units.
+ *   - The moving set is an RBC over M, per registration, built by exactly the construction icp_build_rbc runs over F: same m, nr and
+ *     alpha, the representatives picked from M by the getReps grid rule.  icp_build_rbc builds it behind the fixed set when the rule is
+ *     on.  It goes stale when M is written by any route (icp_write, icp_write_b, icp_write_cloud, icp_batch_write, icp_pyramid_write,
+ *     icp_adopt_device_buffer (ICP_MEM_M)), when the rule is switched on after icp_build_rbc, and by icp_init.  A stale set is rebuilt
+ *     on the handle's stream by the next call that enqueues an iteration, in front of it: no ICP_ESTATE, no extra call.  A caller who
+ *     changes an adopted M buffer behind the handle's back calls icp_build_rbc, as for F; after icp_set_alpha the caller rebuilds, as
+ *     for F.
+ *   - The inverse transform T' is computed per registration from the eight floats T = [x y z w | tx ty tz s] that this iteration's
+ *     forward search used, in double, every expression in the order written, with no contraction:
+ *         xx = x x, and likewise yy zz xy xz yz wx wy wz;
+ *         R00 = 1 - 2 (yy + zz), R01 = 2 (xy - wz), R02 = 2 (xz + wy);
+ *         R10 = 2 (xy + wz), R11 = 1 - 2 (xx + zz), R12 = 2 (yz - wx);
+ *         R20 = 2 (xz - wy), R21 = 2 (yz + wx), R22 = 1 - 2 (xx + yy);
+ *         si = 1.0 / (double) s;  u_a = (R0a tx + R1a ty) + R2a tz;
+ *         T' = [-x, -y, -z, w | (float) -(u_0 si), (float) -(u_1 si), (float) -(u_2 si), (float) si]  (the three sign flips are exact).
+ *     If s is not finite or not > 0, or a component of T' is not finite, T' is the identity and every candidate of that iteration is
+ *     rejected.
+ *   - The back search is the engine's own search: the queries are F of the registration, transformed by T' (the arithmetic of the
+ *     forward search's transform), the database is the moving set, alpha and the metric scale are the handle's.  It runs in the form
+ *     icp_evaluate's search uses: reference order, REGULAR, every opt-in rule off, nothing written but per-query outputs.  Its result,
+ *     in fixed-point order, is ICP_MEM_REVERSE_ID: m x {dist, id}, id an index into M.  With s != 1 the back search weighs geometry
+ *     against colour differently from the forward one, by s^2: it measures geometry in the moving frame.  Reciprocity is with respect
+ *     to the engine's one-shot RBC search, not an exact nearest neighbour.
+ *   - Candidates are the pairs that survive icp_set_rejection's rules and the boundary and normal rules and have a weight != 0 and an
+ *     ICP_MEM_NN_ID id < m.  For candidate i let j = NN_ID[i].id and i' = REVERSE_ID[j].id.
+ *         exact: i' == i.
+ *         near:  not exact, max_gap > 0, i' < m, and gap = (gx gx + gy gy) + gz gz in fp32 is finite and
+ *                <= (float) ((double) max_gap * max_gap), with g = QT[i].xyz - QT[i'].xyz componentwise, the transformed moving points
+ *                of this iteration.
+ *     Every other candidate behaves exactly like a rejected pair: its correspondence is kept, its weight is +0 (written to the W and NN
+ *     outputs), and its moment, mean and S terms — for a plane metric its plane-system terms — are exact zeros.  REGULAR mode uses the
+ *     sum-W formulas.  Nothing accepted: the sum W == 0 identity step.
+ *   - The forward search is untouched: at the same T its ids, distances and RID are bit-identical to a run with the rule off.
+ * The rule acts after the boundary and normal rules and before one-to-one correspondences, trimming and the robust loss: with
+ * icp_set_unique on, ICP_MEM_UNIQUE's n equals this rule's accepted count.  ICP_MEM_RECIPROCAL holds (n, exact, near, accepted) of the
+ * last iteration per registration, accepted = exact + near; zeros while the rule is off.  The counts are integer sums: they do not
+ * depend on the order in which the device gets to the pairs.  A converged registration of a checked run is left alone by every launch
+ * the rule adds.  With the rule on the per-query outputs are stored by every iteration, and an iteration is the separate form
+ * (icp_run_form is ICP_FORM_SEPARATE).  icp_launches_per_iteration counts what the rule adds behind the search:
+ *   - point-to-point: 4 launches — the inverse transform, the back search, the test, and the pass that writes the search's partials
+ *     again from the weights (the apply pass of trimming, one-to-one, the boundary and normal rules and a point-to-point robust loss;
+ *     with any of them on it runs anyway, and the rule adds 3);
+ *   - the plane metrics: 3 launches; their moments read the weights themselves.
+ * Switching the rule on or off captures the run graphs anew; a new max_gap while the rule stays on is a parameter update held in a
+ * device word, which captured run graphs see.  The setting applies to single, batched and icp_batch_* registrations and the level
+ * handles of a pyramid, to every error metric, both reduce modes and both rotation solvers, and survives icp_init.  Tracking is not
+ * provided: icp_track_submit / icp_track_next return ICP_ESTATE while the rule is on.  icp_evaluate and ICP_PAIRS_EVALUATED ignore the
+ * rule; ICP_PAIRS_LAST_ITERATION shows it through W.  icp_profile_run counts its launches into the search stage.  ICP_EINVAL: on
+ * outside {0, 1}, max_gap negative, NaN or infinite. */
+int icp_set_reciprocal (icp_handle h, int on, float max_gap);
+int icp_get_reciprocal (icp_handle h, int *on, float *max_gap);
 
 /* Rejection by normal compatibility (PCL: CorrespondenceRejectorSurfaceNormal) and at the fixed grid's boundary (PCL:
  * CorrespondenceRejectorBoundaryPoints; Turk & Levoy; both in Rusinkiewicz & Levoy, "Efficient Variants of ICP"; not reference
@@ -839,6 +900,7 @@ int icp_batch_set_modes (icp_batch_handle b, int reduce_mode, int power_mode);
 int icp_batch_set_rejection (icp_batch_handle b, int flags, float max_dist);                /* icp_set_rejection on every slot */
 int icp_batch_set_trimming (icp_batch_handle b, float keep_fraction);                        /* icp_set_trimming on every slot */
 int icp_batch_set_unique (icp_batch_handle b, int on);                                       /* icp_set_unique on every slot */
+int icp_batch_set_reciprocal (icp_batch_handle b, int on, float max_gap);                    /* icp_set_reciprocal on every slot */
 int icp_batch_set_normal_rejection (icp_batch_handle b, int on, float min_cos);              /* icp_set_normal_rejection on every slot */
 int icp_batch_set_boundary_rejection (icp_batch_handle b, uint32_t grid_width);              /* icp_set_boundary_rejection on every slot */
 int icp_batch_set_robust_loss (icp_batch_handle b, int loss, float scale);                   /* icp_set_robust_loss on every slot */
@@ -908,7 +970,7 @@ const char *icp_batch_last_error (icp_batch_handle b);   /* b may be NULL: error
  * icp_pyramid_write (ICP_MEM_T) gave it, or — in a second run without either — where its last run ended.
  *
  * icp_pyramid_level hands out the BORROWED handle of a level.  Allowed on it: every setter and getter (modes, metric, normals,
- * rejection, trimming, robust loss, ..; they survive icp_pyramid_init as they survive icp_init), icp_read, icp_state, icp_evaluate,
+ * rejection, trimming, robust loss, reciprocal correspondences — each level then keeps a moving set of its own —, ..; they survive icp_pyramid_init as they survive icp_init), icp_read, icp_state, icp_evaluate,
  * icp_correspondences, icp_correspondences_read, icp_correspondences_device_ptr, icp_device_ptr, icp_transform_cloud, icp_sync and the diagnostics.  The grid widths of icp_set_normals and icp_set_boundary_rejection are per level
  * (side_l): the caller sets them level by level.  NOT allowed, because they would take the levels apart: icp_init*, icp_destroy,
  * icp_write / icp_write_cloud of F or M, icp_adopt_device_buffer and icp_track_*.

@@ -78,6 +78,9 @@ public:
     /*! \brief One-to-one correspondences of the registration (ICPStep::setUnique; not in the reference's demo, off by default). */
     void setUnique (bool on) { reg.setUnique (on); }
     bool getUnique () { return reg.getUnique (); }
+    /*! \brief Reciprocal correspondences of the registration (ICPStep::setReciprocal; not in the reference's demo, off by default). */
+    void setReciprocal (bool on, float max_gap = 0.f) { reg.setReciprocal (on, max_gap); }
+    bool getReciprocal (float *max_gap = nullptr) { return reg.getReciprocal (max_gap); }
     /*! \brief Normal and boundary rejection of the registration (ICPStep::setNormalRejection, setBoundaryRejection; off by default). */
     void setNormalRejection (bool on, float min_cos = 0.f) { reg.setNormalRejection (on, min_cos); }
     void setBoundaryRejection (uint32_t grid_width) { reg.setBoundaryRejection (grid_width); }
