@@ -8,9 +8,12 @@ pytest rewrites `assert` only in the modules it collects, so every assert here c
    names the rows that weigh nothing (`zero`), check_pieces compares the step with the oracle's pieces fed those rows zeroed;
 4. the plane family (point-to-plane, colored, plane-to-plane, symmetric, their robust forms): a `restate` callable wraps the metric's
    float64 restatement, check_last compares the last iteration with it;
-5. the route of an iteration: every opt-in pass composed (composed_rule), the step checks against it, and the ICP_PAIRS_LAST_ITERATION
-   set against it (check_route_pairs);
-6. the scenes of the correspondence sets in every search layout (LAYOUT_CASES, layout_scene)."""
+5. the route of an iteration: every opt-in pass composed (composed_rule; bit 4 of a mask is the reciprocal rule, fed the oracle's back
+   search: back_at), the step checks against it, and the ICP_PAIRS_LAST_ITERATION set against it (check_route_pairs);
+6. the scenes of the correspondence sets in every search layout (LAYOUT_CASES, layout_scene), and the same scenes with the reciprocal rule
+   between their rejection and their trimming (layout_reciprocal);
+7. the reciprocal rule's own scenes: a registration that is done at once beside two that are not (converged_pairs), a moving frame with
+   non-finite rows (messy_scene)."""
 import collections
 import functools
 
@@ -22,6 +25,7 @@ import p2pl_ref
 import pair_filter_ref
 import pairs_ref
 import quality_ref
+import reciprocal_ref
 import robust_ref
 import sym_ref
 import unique_ref
@@ -645,37 +649,49 @@ def check_plane(engine, g, metric, loss, scale, T0, R0, mu=0.05, kappa=1e3, M=No
 
 # ---- 5. the route of an iteration: every opt-in pass composed, in icp_route_of's order -------------------------------------------
 #
-# The search's weights (invalid points and the maximum distance rejected), then the pair filter, one-to-one, trimming and — on
-# point-to-point — the robust loss, each fed what the stage before left.  The rules are the single ones above and in the *_ref modules.
+# The search's weights (invalid points and the maximum distance rejected), then the pair filter, the reciprocal rule, one-to-one, trimming
+# and — on point-to-point — the robust loss, each fed what the stage before left.  The rules are the single ones above and in the *_ref modules.
 
-RouteOptions = collections.namedtuple("RouteOptions", "weighted invalid max_dist gw min_cos unique keep loss scale")
+RouteOptions = collections.namedtuple("RouteOptions", "weighted invalid max_dist gw min_cos unique keep loss scale max_gap", defaults=(None,))
 RouteOptions.__doc__ = """What composed_rule needs of a handle's options.  Off is: gw None (the boundary rule), min_cos None (the
-normal rule), unique False, keep None (trimming), loss None."""
-RouteResult = collections.namedtuple("RouteResult", "W0 filter unique trim words W_before_loss W")
+normal rule), unique False, keep None (trimming), loss None, max_gap None (reciprocal correspondences; 0.0 is on: exact pairs only)."""
+RouteResult = collections.namedtuple("RouteResult", "W0 filter unique trim words W_before_loss W reciprocal", defaults=(None,))
 RouteResult.__doc__ = """W0: the weights behind the search's rejection;  filter: (at_boundary, incompatible, accepted);  unique:
-(winners, candidates);  trim: the accepted mask — a stage that is off has None there —;  words: name -> what ICP_MEM_<name> reports
-(PAIR_FILTER, UNIQUE, TRIM; None while the stage is off);  W_before_loss: the weights the plane moments read;  W: W'."""
+(winners, candidates);  trim: the accepted mask;  reciprocal: (exact, near, accepted) — a stage that is off has None there —;  words:
+name -> what ICP_MEM_<name> reports (PAIR_FILTER, RECIPROCAL, UNIQUE, TRIM; None while the stage is off);  W_before_loss: the weights the
+plane moments read;  W: W'."""
 
 
-def route_options(mask, max_dist, min_cos, side, keep=0.75, loss=robust_ref.CAUCHY, scale=None, weighted=True, invalid=True):
+def route_options(mask, max_dist, min_cos, side, keep=0.75, loss=robust_ref.CAUCHY, scale=None, weighted=True, invalid=True, max_gap=None):
     """The options of mask (bit 0 the pair filter — the boundary rule at the grid width `side` and the normal rule at min_cos —, bit 1
-    one-to-one, bit 2 trimming, bit 3 the robust loss) over rejection by invalid points and max_dist."""
+    one-to-one, bit 2 trimming, bit 3 the robust loss, bit 4 reciprocal correspondences at max_gap) over rejection by invalid points
+    and max_dist."""
+    assert not mask & 16 or max_gap is not None, "mask %d asks for the reciprocal rule and there is no max_gap" % mask
     return RouteOptions(weighted, invalid, max_dist, side if mask & 1 else None, min_cos if mask & 1 else None, bool(mask & 2),
-                        keep if mask & 4 else None, loss if mask & 8 else None, (SCALE[loss] if scale is None else scale) if mask & 8 else None)
+                        keep if mask & 4 else None, loss if mask & 8 else None, (SCALE[loss] if scale is None else scale) if mask & 8 else None,
+                        max_gap if mask & 16 else None)
 
 
-def composed_rule(nn_id, PF, PM, F, M, R0, NF, NM, o, plane=False):
+def composed_rule(nn_id, PF, PM, F, M, R0, NF, NM, o, plane=False, back=None):
     """The weights of an iteration with the passes of `o` (a RouteOptions) on, by the single rules in the route's order.  NF / NM: the
     two normal tables (read only when the normal rule is on).  plane: a plane metric — the loss is the moments' business, W is
-    W_before_loss.  A stage that is off passes its input through and reports no words."""
+    W_before_loss.  back: ((nn_id, rid) of the back search at the step's T, the inverse's ok flag) — reciprocal_ref.back_search's
+    result, read only when the reciprocal rule is on (back_at caches it per scene and T).  A stage that is off passes its input through
+    and reports no words."""
     ids = nn_id["id"]
     W0 = weights_before_trim(nn_id, M, PF, PM, o.weighted, o.invalid, o.max_dist)
-    W, words = W0.copy(), {"PAIR_FILTER": None, "UNIQUE": None, "TRIM": None}
-    flt = unq = trm = None
+    W, words = W0.copy(), {"PAIR_FILTER": None, "RECIPROCAL": None, "UNIQUE": None, "TRIM": None}
+    flt = rcp = unq = trm = None
     if o.gw or o.min_cos is not None:
         bnd, inc, acc, words["PAIR_FILTER"] = pair_filter_ref.pair_filter(ids, W, F, o.gw, NF, NM, R0, o.min_cos)
         flt = (bnd, inc, acc)
         W = np.where(acc, W, np.float32(0)).astype(np.float32)
+    if o.max_gap is not None:
+        assert back is not None, "the reciprocal rule is on and composed_rule has no back search"
+        (rev, _), ok = back
+        exact, near, zero, words["RECIPROCAL"] = reciprocal_ref.reciprocal_rule(ids, rev["id"], PM, W, o.max_gap, ok)
+        rcp = (exact, near, exact | near)
+        W = np.where(zero, np.float32(0), W).astype(np.float32)
     if o.unique:
         win, cand, words["UNIQUE"] = unique_ref.unique_rule(ids, PF, PM, W)
         unq = (win, cand)
@@ -684,7 +700,26 @@ def composed_rule(nn_id, PF, PM, F, M, R0, NF, NM, o, plane=False):
         trm, words["TRIM"] = trim_rule(PF, PM, W, o.keep)
         W = np.where(trm, W, np.float32(0)).astype(np.float32)
     Wl = W if plane or o.loss is None else robust_ref.p2p_weights(W, PF, PM, o.loss, o.scale)
-    return RouteResult(W0, flt, unq, trm, words, W, Wl)
+    return RouteResult(W0, flt, unq, trm, words, W, Wl, rcp)
+
+
+@functools.lru_cache(maxsize=64)
+def _back_at(key, T_bytes):
+    from oracle import oracle
+    F, M, nr = _BACK_SCENES[key]
+    back, ok = reciprocal_ref.back_search(oracle, F, M, np.frombuffer(T_bytes, np.float32), nr)
+    for a in back:
+        a.flags.writeable = False
+    return back, ok
+
+
+_BACK_SCENES = {}
+
+
+def back_at(key, F, M, T, nr):
+    """reciprocal_ref.back_search (oracle, F, M, T, nr), searched once per (key, T): key names the pair (F, M) with nr."""
+    _BACK_SCENES.setdefault(key, (F, M, nr))
+    return _back_at(key, np.ascontiguousarray(T, np.float32).tobytes())
 
 
 def stage_shares(r, o):
@@ -698,6 +733,9 @@ def stage_shares(r, o):
         if o.min_cos is not None:
             out["normal"] = (n, i, n - i)
         out["filter"] = (n, b + i, a)
+    if r.words["RECIPROCAL"] is not None:
+        n, a = int(r.words["RECIPROCAL"][0]), int(r.words["RECIPROCAL"][3])
+        out["reciprocal"] = (n, n - a, a)
     if r.words["UNIQUE"] is not None:
         n, w = (int(x) for x in r.words["UNIQUE"])
         out["unique"] = (n, n - w, w)
@@ -751,7 +789,8 @@ ROUTE_SCENES = {"30": (30, 4, 0x20C7E, 1.0, (4.0, -3.0, 2.0)), "150": (150, 4, 0
                 "batch1": (128, 64, 0x20C82, 1.2, (6.0, -2.0, 3.0)), "batch2": (128, 64, 0x20C83, 0.8, (3.0, -4.0, 1.0))}
 ROUTE_BATCH = ("batch0", "batch1", "batch2")                     # one handle, one set of options: batch0's, proven on each of the three
 ROUTE_KEEP = 0.75
-RouteScene = collections.namedtuple("RouteScene", "side nr F M T want R0 PF PM NF NM max_dist min_cos scale")
+ROUTE_GAP_KEEP = 0.7
+RouteScene = collections.namedtuple("RouteScene", "side nr F M T want R0 PF PM NF NM max_dist min_cos scale max_gap back")
 
 
 @functools.lru_cache(maxsize=None)
@@ -760,7 +799,10 @@ def route_scene(name):
     the oracle's (nn_id, rid) and R at T, PF = F[ids], PM = the transformed moving set, the grid normals of both frames, and the
     options chosen on the reference's pairs: max_dist rejects 12 % of the valid pairs (pick_max_dist), min_cos 10 % of the normal
     rule's candidates (pick_min_cos); the scales are SCALE's but Tukey's, which 90 % of the surviving residuals stay below
-    (pick_scale: SCALE's 30 mm is beyond most residuals of the 30 x 30 grid).  keep is ROUTE_KEEP."""
+    (pick_scale: SCALE's 30 mm is beyond most residuals of the 30 x 30 grid); max_gap accepts ROUTE_GAP_KEEP of the reciprocal rule's
+    candidates behind the search's rejection, the filter off (reciprocal_ref.pick_gap on `back`, the oracle's back search at T).  A
+    strictly reciprocal set (max_gap = 0) is one to one already and would leave one-to-one nothing to remove
+    (tests/test_route_rule_cpu.py).  keep is ROUTE_KEEP."""
     import icp_amd as engine
     from oracle import oracle
     side, nr, seed, rot_deg, t = ROUTE_SCENES[name]
@@ -769,21 +811,29 @@ def route_scene(name):
     M = engine.punch_holes(M, side, side, engine.HOLES_CONTIGUOUS, 0.10, True, seed=seed + 202)
     T = _t0()
     want = oracle_search(oracle, F, M, T, nr)
+    for a in (F, M, T):
+        a.flags.writeable = False
+    back = back_at(name, F, M, T, nr)
+    assert back[1], "_t0 () has an inverse"
+    PF, PM = np.ascontiguousarray(F[want[0]["id"]]), oracle.transform_q(M, T)
     if name in ROUTE_BATCH[1:]:
-        max_dist, min_cos, scale = route_scene(ROUTE_BATCH[0])[-3:]
+        s0 = route_scene(ROUTE_BATCH[0])
+        max_dist, min_cos, scale, max_gap = s0.max_dist, s0.min_cos, s0.scale, s0.max_gap
     else:
         max_dist, min_cos = float(np.float32(pick_max_dist(oracle, F, M, T, nr))), pick_min_cos(oracle, F, M, T, nr, side)
         scale = dict(SCALE)
         scale[robust_ref.TUKEY] = pick_scale(oracle, F, M, T, nr, max_dist)
-    s = RouteScene(side, nr, F, M, T, want, oracle.quat_to_rot(T[:4]).ravel(), np.ascontiguousarray(F[want[0]["id"]]),
-                   oracle.transform_q(M, T), p2pl_ref.grid_normals(F, side), p2pl_ref.grid_normals(M, side), max_dist, min_cos, scale)
-    for a in s[2:5] + want + s[6:11]:
+        max_gap = reciprocal_ref.pick_gap(want[0]["id"], back[0][0]["id"], PM, weights_before_trim(want[0], M, PF, PM, True, True, max_dist),
+                                          keep=ROUTE_GAP_KEEP)
+    s = RouteScene(side, nr, F, M, T, want, oracle.quat_to_rot(T[:4]).ravel(), PF, PM, p2pl_ref.grid_normals(F, side),
+                   p2pl_ref.grid_normals(M, side), max_dist, min_cos, scale, max_gap, back)
+    for a in want + s[6:11]:
         a.flags.writeable = False
     return s
 
 
 def route_scene_options(s, mask, loss=robust_ref.CAUCHY):
-    return route_options(mask, s.max_dist, s.min_cos, s.side, ROUTE_KEEP, loss, s.scale[loss])
+    return route_options(mask, s.max_dist, s.min_cos, s.side, ROUTE_KEEP, loss, s.scale[loss], max_gap=s.max_gap)
 
 
 @functools.lru_cache(maxsize=None)
@@ -791,11 +841,11 @@ def route_proof(name, mask, loss=robust_ref.CAUCHY, plane=False):
     """(RouteResult, stage shares) of composed_rule on the scene's reference pairs at _t0 (), every stage proven to bite."""
     s = route_scene(name)
     o = route_scene_options(s, mask, loss)
-    r = composed_rule(s.want[0], s.PF, s.PM, s.F, s.M, s.R0, s.NF, s.NM, o, plane)
+    r = composed_rule(s.want[0], s.PF, s.PM, s.F, s.M, s.R0, s.NF, s.NM, o, plane, s.back)
     return r, assert_every_stage_bites(r, o, "scene %s, mask %d, loss %d" % (name, mask, loss))
 
 
-ROUTE_WORDS = {"PAIR_FILTER": 4, "UNIQUE": 2, "TRIM": 4}
+ROUTE_WORDS = {"PAIR_FILTER": 4, "UNIQUE": 2, "TRIM": 4, "RECIPROCAL": 4}
 ROUTE_METRICS = ("p2pl", "colored", "gicp", "sym")
 GICP_EPS = 1e-3
 
@@ -805,9 +855,12 @@ def route_handle(engine, side, nr, o, metric="p2p", fused=None, batch=1, it=40):
     literal one; a plane metric of ROUTE_METRICS (mu = 0.05, kappa = 1000, epsilon = GICP_EPS): the handle's default modes."""
     loss = (o.loss, o.scale) if o.loss is not None else None
     if metric == "p2p":
-        return make_handle(engine, side * side, nr, fused, o.weighted, POWER, fused, batch, it, rejection=(o.invalid, o.max_dist),
-                           boundary=o.gw, normal_rejection=(side, o.min_cos) if o.min_cos is not None else None,
-                           unique=True if o.unique else None, trimming=o.keep, robust_loss=loss)
+        g = make_handle(engine, side * side, nr, fused, o.weighted, POWER, fused, batch, it, rejection=(o.invalid, o.max_dist),
+                        boundary=o.gw, normal_rejection=(side, o.min_cos) if o.min_cos is not None else None,
+                        unique=True if o.unique else None, trimming=o.keep, robust_loss=loss)
+        if o.max_gap is not None:
+            g.set_reciprocal(True, o.max_gap)
+        return g
     g = make_plane(engine, side, nr, WEIGHTED if o.weighted else REGULAR, batch=batch, max_iterations=it,
                    metric=COLORED if metric == "colored" else P2PL, plane_to_plane=GICP_EPS if metric == "gicp" else None,
                    symmetric=True if metric == "sym" else None, trimming=o.keep, robust_loss=loss)
@@ -818,6 +871,8 @@ def route_handle(engine, side, nr, o, metric="p2p", fused=None, batch=1, it=40):
         g.set_normal_rejection(o.min_cos)
     if o.unique:
         g.set_unique(True)
+    if o.max_gap is not None:
+        g.set_reciprocal(True, o.max_gap)
     return g
 
 
@@ -832,18 +887,28 @@ def route_restate(metric, o, M):
     return restate_colored(0.05, 1000.0) if metric == "colored" else restate_p2pl(0.05)
 
 
-def _route_rule(engine, g, F, M, NF, NM, R0, want, o, plane, b, proof, what):
-    """The search against the oracle's, the normal tables against the grid normals, then composed_rule on the engine's NN / QT: the
-    three result words against the rule's (zeros while a stage is off) and against `proof`'s (a RouteResult from the reference's pairs:
+def check_back_search(engine, g, back, b=0, what=""):
+    """ICP_MEM_REVERSE_ID of registration b — every fixed point's id, and the bits of dist — against the oracle's back search."""
+    got, rev = g.read(engine.Memory.REVERSE_ID, batch_index=b), back[0][0]
+    assert np.array_equal(got["id"], rev["id"]), "back search ids (%s): %d differ" % (what, np.count_nonzero(got["id"] != rev["id"]))
+    assert_bits(got["dist"], rev["dist"], "back search distances (%s)" % what)
+
+
+def _route_rule(engine, g, F, M, NF, NM, R0, want, o, plane, b, proof, what, back=None):
+    """The search against the oracle's, with the reciprocal rule on ICP_MEM_REVERSE_ID against the oracle's back search (back), the
+    normal tables against the grid normals, then composed_rule on the engine's NN / QT: the
+    four result words against the rule's (zeros while a stage is off) and against `proof`'s (a RouteResult from the reference's pairs:
     the first step's), every stage biting by the proof's conditions; without a proof every stage still removes some pair and keeps half."""
     Mem = engine.Memory
     check_search(engine, g, want, b)
+    if o.max_gap is not None:
+        check_back_search(engine, g, back, b, what)
     if plane or o.min_cos is not None:
         assert_bits(g.read(Mem.NORMALS_F, b), NF, "NORMALS_F against the grid normals (%s)" % what)
     if o.min_cos is not None:
         assert_bits(g.read(Mem.NORMALS_M, b), NM, "NORMALS_M against the grid normals (%s)" % what)
     PF, PM = g.read(Mem.NN, b), g.read(Mem.QT, b)
-    r = composed_rule(want[0], PF, PM, F, M, R0, NF, NM, o, plane)
+    r = composed_rule(want[0], PF, PM, F, M, R0, NF, NM, o, plane, back)
     for name, n in ROUTE_WORDS.items():
         words = r.words[name] if r.words[name] is not None else np.zeros(n, np.uint32)
         got = assert_words(engine, g, name, words, b)
@@ -854,19 +919,19 @@ def _route_rule(engine, g, F, M, NF, NM, R0, want, o, plane, b, proof, what):
         shares = assert_every_stage_bites(r, o, what)
     else:                                                         # (a later step, at a T no proof covers: the passes still have work)
         shares = stage_shares(r, o)
-        for name in ("filter", "unique", "trim", "loss"):
+        for name in ("filter", "reciprocal", "unique", "trim", "loss"):
             n, removed, kept = shares.get(name, (1, 1, 1))
             assert removed > 0 and 2 * kept >= n, "%s: stage %s has %d candidates, removes %d, keeps %d" % (what, name, n, removed, kept)
     print(what, "shares", shares)
     return r, PF, PM
 
 
-def check_route_step(engine, oracle, g, F, M, NF, NM, T, R0, want, o, fused, b=0, proof=None, what=""):
+def check_route_step(engine, oracle, g, F, M, NF, NM, T, R0, want, o, fused, b=0, proof=None, what="", back=None):
     """A point-to-point step from (T, R0), already taken, with the passes of o on: _route_rule, then ICP_MEM_W against W', sum W,
     means, S and Tk by check_pieces, "an accepted pair keeps its weight" (under the loss: the loss's weight of its search weight) and
     the NN output's weights.  Returns the RouteResult."""
     Mem = engine.Memory
-    r, PF, PM = _route_rule(engine, g, F, M, NF, NM, R0, want, o, False, b, proof, what)
+    r, PF, PM = _route_rule(engine, g, F, M, NF, NM, R0, want, o, False, b, proof, what, back)
     side = int(round(np.sqrt(F.shape[0])))
     check_pieces(engine, oracle, g, F, M, T, side, fused, o.weighted, POWER, fused, r.W == 0, want, b, r.W if o.loss is not None else None)
     gW = g.read(Mem.W, b)
@@ -878,11 +943,11 @@ def check_route_step(engine, oracle, g, F, M, NF, NM, T, R0, want, o, fused, b=0
     return r
 
 
-def check_route_plane_step(engine, g, F, M, NF, NM, T0, R0, k0, want, o, restate, b=0, proof=None, what=""):
+def check_route_plane_step(engine, g, F, M, NF, NM, T0, R0, k0, want, o, restate, b=0, proof=None, what="", back=None):
     """A plane metric's step from (T0, R0, k0), already taken: _route_rule, the NN output's weights and ICP_MEM_W against the composed
     weights before the loss, then check_last with the restatement fed the rule's weights.  Returns the RouteResult."""
     Mem = engine.Memory
-    r, PF, _ = _route_rule(engine, g, F, M, NF, NM, R0, want, o, True, b, proof, what)
+    r, PF, _ = _route_rule(engine, g, F, M, NF, NM, R0, want, o, True, b, proof, what, back)
     assert_bits(PF[:, 3], r.W_before_loss, "the NN output's weights (%s)" % what)
     assert_bits(g.read(Mem.W, b), r.W_before_loss, "ICP_MEM_W (%s)" % what)
     check_last(engine, g, restate, T0, R0, k0, b, weights=r.W_before_loss)
@@ -891,14 +956,16 @@ def check_route_plane_step(engine, g, F, M, NF, NM, T0, R0, k0, want, o, restate
 
 def last_stage_count(r, o, plane):
     """(what decides, the number of pairs the iteration used) by include/icp_amd.h: the word of the last acting stage of o —
-    ICP_MEM_TRIM's accepted, else ICP_MEM_UNIQUE's winners, else ICP_MEM_PAIR_FILTER's accepted, with no stage on the pairs the search
-    left a weight —; a point-to-point loss acts behind all of them and may zero further weights: the pairs it leaves one."""
+    ICP_MEM_TRIM's accepted, else ICP_MEM_UNIQUE's winners, else ICP_MEM_RECIPROCAL's accepted, else ICP_MEM_PAIR_FILTER's accepted, with no
+    stage on the pairs the search left a weight —; a point-to-point loss acts behind all of them and may zero further weights: the pairs it leaves one."""
     if not plane and o.loss is not None:
         return "W'", int(np.count_nonzero(r.W))
     if o.keep is not None:
         return "TRIM", int(r.words["TRIM"][3])
     if o.unique:
         return "UNIQUE", int(r.words["UNIQUE"][1])
+    if o.max_gap is not None:
+        return "RECIPROCAL", int(r.words["RECIPROCAL"][3])
     if o.gw or o.min_cos is not None:
         return "PAIR_FILTER", int(r.words["PAIR_FILTER"][3])
     return "W0", int(np.count_nonzero(r.W0))
@@ -970,3 +1037,103 @@ def evaluated_expectation(oracle, F, M, T, nr, max_dist, want=None):
     ids = nn_id["id"]
     PF, PM = np.ascontiguousarray(F[ids][:, :4]), np.ascontiguousarray(oracle.transform_q(M, T)[:, :4])
     return pairs_ref.evaluated(M, PF, PM, ids, max_dist), quality_ref.evaluate(M, PF, PM, max_dist)
+
+
+LAYOUT_GAP_KEEP = 0.6
+LayoutReciprocal = collections.namedtuple("LayoutReciprocal", "max_gap options backs rules")
+
+
+@functools.lru_cache(maxsize=None)
+def layout_reciprocal(side, nr, batch, zero):
+    """layout_scene with the reciprocal rule between its rejection and its trimming, from the oracle alone: max_gap accepts
+    LAYOUT_GAP_KEEP of registration 0's candidates (reciprocal_ref.pick_gap), the options, and per registration the oracle's back
+    search at _t0 () — every fixed point a query, the invalid ones at the origin included — and composed_rule's result."""
+    sc = layout_scene(side, nr, batch, zero)
+    backs = [back_at(("layout", side, nr, batch, zero, b), F, M, sc.T, nr) for b, (F, M) in enumerate(sc.pairs)]
+    max_gap = reciprocal_ref.pick_gap(sc.wants[0][0]["id"], backs[0][0][0]["id"], sc.PM[0], sc.rules[0].W0, keep=LAYOUT_GAP_KEEP)
+    o = sc.options._replace(max_gap=max_gap)
+    rules = [composed_rule(w[0], pf, pm, F, M, None, None, None, o, back=back)
+             for (F, M), w, pf, pm, back in zip(sc.pairs, sc.wants, sc.PF, sc.PM, backs)]
+    return LayoutReciprocal(max_gap, o, backs, rules)
+
+
+def origin_rows(X):
+    return (X[:, :3] == 0).all(axis=1)
+
+
+def layout_reciprocal_conditions(words, finals, counted, origin_share, what):
+    """What keeps the layout test of the reciprocal rule from passing vacuously, on the values given (the oracle's in
+    tests/test_reciprocal_cpu.py, the device's in tests/test_gpu_reciprocal.py): per registration words = ICP_MEM_RECIPROCAL's
+    (n, exact, near, accepted), finals = the size of the final set, counted = the points icp_evaluate counts; origin_share = the share
+    of back answers that name an origin row of M (None for a scene without holes).  exact and near are each at least 2 % of the
+    candidates, accepted is between 40 % and 90 % of them, the final set between 10 % and 90 % of the counted points, the accepted
+    counts of a batch are pairwise distinct, and at least 5 % of the back answers of a scene with holes are ties at the origin."""
+    for b, (w, final, c) in enumerate(zip(words, finals, counted)):
+        n, exact, near, acc = (int(x) for x in w)
+        assert n > 0 and 50 * exact >= n and 50 * near >= n, "%s, registration %d: %d candidates, %d exact, %d near" % (what, b, n, exact, near)
+        assert 0.4 * n <= acc <= 0.9 * n and acc == exact + near, "%s, registration %d: %d of %d candidates accepted" % (what, b, acc, n)
+        assert 0.1 * c <= final <= 0.9 * c, "%s, registration %d: the final set holds %d of %d counted points" % (what, b, final, c)
+    accepted = [int(w[3]) for w in words]
+    assert len(set(accepted)) == len(accepted), "%s: the accepted counts of the batch are not pairwise distinct: %r" % (what, accepted)
+    if origin_share is not None:
+        assert origin_share >= 0.05, "%s: %.3f of the back answers name an origin row of M" % (what, origin_share)
+
+
+# ---- 7. the reciprocal rule's own scenes ---------------------------------------------------------------------------------------------
+
+def converged_pairs():
+    """Three registrations for one handle at (128, 64): batch0's F as both frames — at the identity every valid point finds itself at
+    distance 0 in both directions, so a checked run is done with it at k = 1 —, then batch1 and batch2."""
+    s = [route_scene(n) for n in ROUTE_BATCH]
+    return [(s[0].F, s[0].F), (s[1].F, s[1].M), (s[2].F, s[2].M)]
+
+
+def messy_moving(engine, side, seed):
+    """(F, M, the clean M): synth_pair with M treated as messy_grid treats F — contiguous and scattered holes, ten NaN, ten +inf and ten
+    -inf coordinates, ten more points at the origin."""
+    F, clean = engine.synth_pair(side, seed=seed)
+    M = punch_cloud(engine, clean.copy(), side, seed)
+    rng = np.random.default_rng(seed)
+    idx = rng.choice(side * side, 40, replace=False)
+    M[idx[:10], 0] = np.nan
+    M[idx[10:20], 1] = np.inf
+    M[idx[20:30], 2] = -np.inf
+    M[idx[30:], :3] = 0.0
+    return F, M, clean
+
+
+MessyScene = collections.namedtuple("MessyScene", "F M clean T max_dist max_gap want back finite PF PM W0 rule")
+MESSY_SHAPES = [(50, 4), (64, 64)]
+
+
+@functools.lru_cache(maxsize=None)
+def messy_scene(side, nr):
+    """A pair whose moving frame — the back search's database — has non-finite rows, from the oracle alone: T = _t0 (), max_dist by
+    pick_max_dist on the clean pair, max_gap the 40 % quantile of the non-exact gaps, the oracle's forward and back search, the rows
+    of M that are finite, PF / PM, the weights behind the search's rejection (a non-finite row has +0 there: its geo is no number
+    <= max_dist^2) and reciprocal_rule's (exact, near, zero, words)."""
+    import icp_amd as engine
+    from oracle import oracle
+    F, M, clean = messy_moving(engine, side, 0x5EED + side)
+    T = _t0()
+    max_dist = float(np.float32(pick_max_dist(oracle, F, clean, T, nr)))
+    want = oracle_search(oracle, F, M, T, nr)
+    for a in (F, M, clean, T):
+        a.flags.writeable = False
+    back = back_at(("messy", side, nr), F, M, T, nr)
+    finite = np.isfinite(M[:, :3]).all(axis=1)
+    PF, PM = np.ascontiguousarray(F[want[0]["id"]]), oracle.transform_q(M, T)
+    with np.errstate(all="ignore"):
+        W0 = weights_before_trim(want[0], M, PF, PM, True, True, max_dist)
+        max_gap = float(np.float32(np.quantile(reciprocal_ref.gaps(want[0]["id"], back[0][0]["id"], PM, W0), 0.4)))
+        rule = reciprocal_ref.reciprocal_rule(want[0]["id"], back[0][0]["id"], PM, W0, max_gap, back[1])
+    return MessyScene(F, M, clean, T, max_dist, max_gap, want, back, finite, PF, PM, W0, rule)
+
+
+def messy_conditions(finite, W0, rev_ids, words, what):
+    """30 rows of M are not finite; none of them is a candidate; no back answer names one; the rule has exact, near and rejected pairs."""
+    m = finite.shape[0]
+    assert np.count_nonzero(~finite) == 30 and not W0[~finite].any(), "%s: a non-finite row is no candidate" % what
+    assert (rev_ids < m).all() and finite[rev_ids].all(), "%s: %d back answers name a non-finite row" % (what, np.count_nonzero(~finite[np.minimum(rev_ids, m - 1)]))
+    n, exact, near, acc = (int(x) for x in words)
+    assert n == np.count_nonzero(W0) and 50 * exact >= n and 50 * near >= n and acc == exact + near and 0.2 * n <= acc <= 0.9 * n, (what, words)

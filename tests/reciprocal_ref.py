@@ -4,7 +4,10 @@ collects nothing from it).
 inverse (T): the inverse transform T' in the rule's order, in Python floats (doubles), no contraction.
 back_search: the back search is the oracle's own search with F and M swapped and T' — icp_checks.oracle_search (oracle, M, F, T', nr).
 reciprocal_rule: (exact, near, rows that weigh nothing, [n, exact, near, accepted]) from the forward ids, the back ids, the transformed
-moving points, the weights before the rule and max_gap."""
+moving points, the weights before the rule and max_gap.
+gaps / gaps2 / pick_gap: the gaps of the candidates that are not exact (their fp32 squares as the rule computes them), and a max_gap that
+accepts a chosen share of the candidates.
+equality_gap: a max_gap whose float square is exactly a pair's squared gap — the rule's <= at its edge."""
 import math
 
 import numpy as np
@@ -91,3 +94,51 @@ def gaps(ids, rev_ids, QT, W0):
     g = (np.asarray(QT, F32)[rows, :3] - np.asarray(QT, F32)[back[rows], :3]).astype(F32)
     gap = ((g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]).astype(F32) + g[:, 2] * g[:, 2]).astype(F32)
     return np.sort(np.sqrt(gap[np.isfinite(gap)].astype(np.float64)))
+
+
+def pick_gap(ids, rev_ids, QT, W0, keep=0.7):
+    """A max_gap (a Python float that a float32 holds exactly) at which exact + near is about `keep` of the rule's candidates (the pairs
+    W0 gives a weight): the quantile of the non-exact gaps that asks for keep * n - exact near pairs."""
+    ids = np.asarray(ids, np.uint32)
+    cand = (np.asarray(W0, F32) != 0) & (ids < ids.shape[0])
+    n = int(np.count_nonzero(cand))
+    exact = int(np.count_nonzero(cand & (np.asarray(rev_ids, np.uint32)[np.minimum(ids, ids.shape[0] - 1)] == np.arange(ids.shape[0]))))
+    g = gaps(ids, rev_ids, QT, W0)
+    q = (keep * n - exact) / len(g)
+    assert 0.0 < q < 1.0, "no max_gap keeps %g of %d candidates: %d are exact, %d have a gap" % (keep, n, exact, len(g))
+    return float(F32(np.quantile(g, q)))
+
+
+def gaps2(ids, rev_ids, QT, W0):
+    """The squared gaps in fp32, as the rule computes them, of the candidates that are not exact and whose back id is a point of M
+    (unsorted; the non-finite ones included)."""
+    ids = np.asarray(ids, np.uint32)
+    m = ids.shape[0]
+    cand = (np.asarray(W0, F32) != 0) & (ids < m)
+    back = np.full(m, 0xFFFFFFFF, np.uint32)
+    back[cand] = np.asarray(rev_ids, np.uint32)[ids[cand]]
+    rows = np.flatnonzero(cand & (back != np.arange(m, dtype=np.uint32)) & (back < m))
+    with np.errstate(all="ignore"):
+        g = (np.asarray(QT, F32)[rows, :3] - np.asarray(QT, F32)[back[rows], :3]).astype(F32)
+        return ((g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]).astype(F32) + g[:, 2] * g[:, 2]).astype(F32)
+
+
+def gap_with_square(g2):
+    """The float32 max_gap with (float) ((double) max_gap * max_gap) == g2, or None when no float squares to g2."""
+    r = F32(np.sqrt(np.float64(g2)))
+    for c in (np.nextafter(r, F32(0)), r, np.nextafter(r, F32(np.inf))):
+        if F32(np.float64(c) * np.float64(c)) == F32(g2):
+            return F32(c)
+    return None
+
+
+def equality_gap(ids, rev_ids, QT, W0):
+    """(g2, max_gap, the next float below max_gap, the number of pairs whose squared gap is g2): over the distinct finite squared gaps
+    of the non-exact candidates that some float max_gap squares to exactly, the median one.  Also returns (distinct values, how many
+    of them have such a float)."""
+    g = gaps2(ids, rev_ids, QT, W0)
+    values = np.unique(g[np.isfinite(g)])
+    have = [(v, gap_with_square(v)) for v in values]
+    have = [(v, c) for v, c in have if c is not None]
+    v, c = have[len(have) // 2]
+    return v, float(c), float(np.nextafter(c, F32(0))), int(np.count_nonzero(g == v)), (len(values), len(have))

@@ -5,7 +5,12 @@ a rejected pair.  The forward search is not touched.
 The back search is restated by the CPU oracle with F and M swapped and the inverse transform of tests/reciprocal_ref.py; the rule by
 numpy from the engine's own NN_ID / NN / QT outputs and the weights before the rule; the reference values come from the oracle's
 piecewise entries with the rejected rows zeroed (icp_checks.expected_pieces).  ICP_MEM_RECIPROCAL holds (n, exact, near, accepted) of
-the last iteration, ICP_MEM_REVERSE_ID the back search's (dist, id) per fixed point.  Everything is compared bit for bit."""
+the last iteration, ICP_MEM_REVERSE_ID the back search's (dist, id) per fixed point.  Everything is compared bit for bit.
+
+Sections 13 to 15 take every expectation from the oracle's pairs alone (icp_checks.composed_rule with the rule as a stage): the rule in
+every search layout, a converged registration beside two running ones, max_gap exactly at a pair's gap, and non-finite rows in the back
+search's database.  tests/test_reciprocal_cpu.py proves what they rely on without a device; the rule composed with every other pass is
+tests/test_gpu_route_numerics.py's."""
 import os
 import sys
 
@@ -14,6 +19,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import p2pl_ref                                                 # noqa: E402
+import quality_ref                                              # noqa: E402
 import reciprocal_ref as ref                                    # noqa: E402
 import icp_checks                                               # noqa: E402
 from icp_checks import (A, C_, IDENTITY, MODES, POWER, EIGEN, REGULAR, WEIGHTED, assert_bits, assert_words, check_pieces,  # noqa: E402
@@ -48,14 +54,14 @@ def scenes_A(engine, oracle):
     return out
 
 
-def numpy_rule(engine, g, M, weighted, invalid, back, max_gap, ok=True, b=0, W0=None):
+def numpy_rule(engine, g, M, weighted, invalid, back, max_gap, ok=True, b=0, W0=None, max_dist=None):
     """(exact, near, rows that weigh nothing, counts, weights before the rule) from the engine's outputs of registration b and the
     restated back search."""
     Mem = engine.Memory
     nn_id = g.read(Mem.NN_ID, batch_index=b)
     PF, PM = g.read(Mem.NN, batch_index=b), g.read(Mem.QT, batch_index=b)
     if W0 is None:
-        W0 = weights_before_trim(nn_id, M, PF, PM, weighted, invalid)
+        W0 = weights_before_trim(nn_id, M, PF, PM, weighted, invalid, max_dist)
     exact, near, zero, counts = ref.reciprocal_rule(nn_id["id"], back[0]["id"], PM, W0, max_gap, ok)
     return exact, near, zero, counts, W0
 
@@ -66,10 +72,10 @@ def check_back_search(engine, g, back, b=0):
     assert_bits(got["dist"], back[0]["dist"], "back search distances")
 
 
-def check_step(engine, oracle, g, F, M, T, side, fused, weighted, rot, power_fast, invalid, back, max_gap, want=None, b=0):
+def check_step(engine, oracle, g, F, M, T, side, fused, weighted, rot, power_fast, invalid, back, max_gap, want=None, b=0, max_dist=None):
     """REVERSE_ID against the restated back search, ICP_MEM_RECIPROCAL, `W != 0 equals the rule`, and the pieces.  Returns the counts."""
     check_back_search(engine, g, back, b)
-    exact, near, zero, counts, W0 = numpy_rule(engine, g, M, weighted, invalid, back, max_gap, b=b)
+    exact, near, zero, counts, W0 = numpy_rule(engine, g, M, weighted, invalid, back, max_gap, b=b, max_dist=max_dist)
     got = assert_words(engine, g, "RECIPROCAL", counts, b)
     assert got[3] == got[1] + got[2], got
     check_pieces(engine, oracle, g, F, M, T, side, fused, weighted, rot, power_fast, zero, want, b)
@@ -541,3 +547,165 @@ def test_two_level_pyramid(engine):
         assert np.all(want[0][1][[0, 1, 3]] > 0), want[0][1]
     finally:
         p.close()
+
+
+# ---- 13. every search layout: the back search's database is M with its holes, its queries every fixed point
+
+@pytest.mark.parametrize("case", icp_checks.LAYOUT_CASES,
+                         ids=lambda c: "%d-%d-%d-%s-%s" % (c[0], c[1], c[2], "fused" if c[3] else "reference_order", c[4]))
+def test_every_search_layout(engine, oracle, case):
+    """icp_checks.layout_scene's pairs with its rejection and trimming, the rule between them at layout_reciprocal's max_gap; one step
+    from _t0 ().  Per registration REVERSE_ID for every fixed point — in the scenes with holes thousands of them are invalid points
+    whose answer is a tie among M's coincident origin points —, the RECIPROCAL and TRIM words, ICP_MEM_W and the LAST_ITERATION set,
+    all against the oracle's pairs alone.  tests/test_reciprocal_cpu.py proves the conditions asserted at the end from the oracle;
+    here they are asserted on the device's words and ids."""
+    side, nr, batch, fused, zero, layout = case
+    m = side * side
+    Mem = engine.Memory
+    sc, lr = icp_checks.layout_scene(side, nr, batch, zero), icp_checks.layout_reciprocal(side, nr, batch, zero)
+    g = icp_checks.make_handle(engine, m, nr, fused, WEIGHTED, POWER, fused, batch, rejection=(True, sc.max_dist), trimming=icp_checks.LAYOUT_KEEP)
+    g.set_reciprocal(True, lr.max_gap)
+    assert g.search_layout() == layout, g.search_layout()
+    if batch == 1:
+        one_step(engine, g, sc.pairs[0][0], sc.pairs[0][1], sc.T)
+    else:
+        step_batch(engine, g, sc.pairs, sc.T)
+    words, finals, counted, origin = [], [], [], 0
+    for b, ((F, M), want, back, r) in enumerate(zip(sc.pairs, sc.wants, lr.backs, lr.rules)):
+        what = "side %d, |R| %d, registration %d of %d" % (side, nr, b, batch)
+        icp_checks.check_search(engine, g, want, b)
+        icp_checks.check_back_search(engine, g, back, b, what)
+        words.append(assert_words(engine, g, "RECIPROCAL", r.words["RECIPROCAL"], b))
+        assert_words(engine, g, "TRIM", r.words["TRIM"], b)
+        gW = g.read(Mem.W, batch_index=b)
+        assert_bits(gW, r.W, "ICP_MEM_W (%s)" % what)
+        got = icp_checks.check_route_pairs(engine, g, want[0], sc.PF[b], sc.PM[b], r, False, lr.options, b, what)
+        finals.append(len(got))
+        counted.append(int(np.count_nonzero(quality_ref.masks(M, sc.PF[b], sc.PM[b], 0.0)[0])))
+        origin += int(np.count_nonzero(icp_checks.origin_rows(M)[g.read(Mem.REVERSE_ID, batch_index=b)["id"]]))
+    holes = any(icp_checks.origin_rows(M).any() for _, M in sc.pairs)
+    print(case[:5], "max_gap", lr.max_gap, [w.tolist() for w in words], finals, counted, origin)
+    icp_checks.layout_reciprocal_conditions(words, finals, counted, origin / (batch * m) if holes else None, str(case[:5]))
+    g.close()
+
+
+# ---- 14. a converged registration of a checked run is left alone by every launch the rule adds
+
+@pytest.mark.parametrize("metric,fused", [("p2p", True), ("p2p", False), ("p2pl", None)])
+def test_a_converged_registration_is_left_alone(engine, metric, fused):
+    """One handle, three registrations, dense by batch, a checked run with the rule on.  Registration 0 registers a frame with itself
+    and is done at k = 1 (tests/test_reciprocal_cpu.py); the other two go on for at least two more iterations, every one of which
+    launches the state kernel, the back search and the test over all three.  Each registration's k, T, W, words, back search and
+    LAST_ITERATION set are those of a handle that runs the same pair alone."""
+    Mem = engine.Memory
+    pairs = icp_checks.converged_pairs()
+    s0 = icp_checks.route_scene("batch0")
+    o = icp_checks.route_scene_options(s0, 16)
+    read = lambda g, b: (g.state(b).k, g.read(Mem.T, b).copy(), g.read(Mem.W, b).copy(), g.read(Mem.RECIPROCAL, b).copy(),
+                         g.read(Mem.REVERSE_ID, b).view(np.uint32).copy(), g.correspondences(engine.Pairs.LAST_ITERATION, batch_index=b).view(np.uint32).copy())
+    alone = []
+    for F, M in pairs:
+        h = icp_checks.route_handle(engine, s0.side, s0.nr, o, metric, fused)
+        icp_checks.load(engine, h, F, M)
+        h.buildRBC()
+        assert h.run() == h.state().k
+        alone.append(read(h, 0))
+        h.close()
+    assert alone[0][0] == 1 and alone[1][0] >= 3 and alone[2][0] >= 3, [a[0] for a in alone]
+    assert alone[0][3].tolist() == [14742, 14742, 0, 14742], alone[0][3]
+    g = icp_checks.route_handle(engine, s0.side, s0.nr, o, metric, fused, batch=3)
+    assert g.search_layout()[0] == 1, g.search_layout()
+    for b, (F, M) in enumerate(pairs):
+        icp_checks.load(engine, g, F, M, b)
+    g.buildRBC()
+    g.run()
+    for b in range(3):
+        got = read(g, b)
+        assert got[0] == alone[b][0], "k of registration %d: %d, alone %d" % (b, got[0], alone[b][0])
+        for x, y, name in zip(got[1:], alone[b][1:], ("T", "W", "RECIPROCAL", "REVERSE_ID", "the LAST_ITERATION set")):
+            assert_bits(x, y, "%s of registration %d against the same pair alone" % (name, b))
+        assert 0 < got[3][3] and len(got[5]) > 0
+    assert g.state(0).k == 1 and g.state(1).k >= 3 and g.state(2).k >= 3
+    g.close()
+
+
+# ---- 15. the rule's edges on the device
+
+def test_max_gap_at_a_pair_s_own_gap(engine, oracle):
+    """Scene 30 behind the search's rejection, the rule alone.  g2: a squared gap of a non-exact candidate that some float squares to
+    (reciprocal_ref.equality_gap; tests/test_reciprocal_cpu.py).  With that float as max_gap the pair is near — the device's <= against
+    (float) ((double) max_gap * max_gap) —, with the next float below it is not: `near` drops by exactly the pairs at g2."""
+    s = icp_checks.route_scene("30")
+    ids, rev = s.want[0]["id"], s.back[0][0]["id"]
+    W0 = weights_before_trim(s.want[0], s.M, s.PF, s.PM, True, True, s.max_dist)
+    g2, gap, below, pairs, (distinct, have) = ref.equality_gap(ids, rev, s.PM, W0)
+    assert have > 0 and pairs >= 1 and F32(np.float64(F32(gap)) * np.float64(F32(gap))) == g2
+    rows = np.flatnonzero(ref.reciprocal_rule(ids, rev, s.PM, W0, gap)[1] & ~ref.reciprocal_rule(ids, rev, s.PM, W0, below)[1])
+    assert len(rows) == pairs
+    g = icp_checks.make_handle(engine, s.side * s.side, s.nr, True, WEIGHTED, POWER, True, rejection=(True, s.max_dist))
+    near = []
+    for k, max_gap in enumerate((gap, below)):
+        g.set_reciprocal(True, max_gap)
+        if k == 0:
+            one_step(engine, g, s.F, s.M, s.T)
+        else:
+            g.write(engine.Memory.T, s.T, block=True)
+            g.step()
+        counts = check_step(engine, oracle, g, s.F, s.M, s.T, s.side, True, WEIGHTED, POWER, True, True, s.back[0], max_gap, s.want,
+                            max_dist=s.max_dist)
+        want = ref.reciprocal_rule(ids, rev, s.PM, W0, max_gap)
+        assert counts.tolist() == want[3].tolist(), (counts, want[3])
+        assert np.array_equal(g.read(engine.Memory.W)[rows] != 0, np.full(pairs, k == 0)), "the pairs at the gap are near at it and not below it"
+        near.append(int(g.read(engine.Memory.RECIPROCAL)[2]))
+    assert near[0] - near[1] == pairs and near[1] > 0, near
+    g.close()
+
+
+def _check_messy(engine, g, s, b, what):
+    """Registration b holds messy_scene s: the back search for every fixed point, the words and W against the rule, the forward search
+    on the finite rows."""
+    Mem = engine.Memory
+    icp_checks.check_back_search(engine, g, s.back, b, what)
+    exact, near, zero, words = s.rule
+    got = assert_words(engine, g, "RECIPROCAL", words, b)
+    assert_bits(g.read(Mem.W, batch_index=b), np.where(zero, F32(0), s.W0).astype(F32), "ICP_MEM_W (%s)" % what)
+    nn = g.read(Mem.NN_ID, batch_index=b)
+    assert np.array_equal(nn["id"][s.finite], s.want[0]["id"][s.finite]), "forward ids on the finite rows (%s)" % what
+    assert_bits(nn["dist"][s.finite], s.want[0]["dist"][s.finite], "forward distances on the finite rows (%s)" % what)
+    icp_checks.messy_conditions(s.finite, s.W0, g.read(Mem.REVERSE_ID, batch_index=b)["id"], got, what)
+
+
+def test_non_finite_moving_rows_alone(engine, oracle):
+    """(50, 4): M — the back search's database — with holes and thirty NaN / +inf / -inf coordinates; rejection by invalid points and a
+    max_dist from the clean pair, so a non-finite row is no candidate.  No back answer names such a row."""
+    side, nr = icp_checks.MESSY_SHAPES[0]
+    s = icp_checks.messy_scene(side, nr)
+    g = icp_checks.make_handle(engine, side * side, nr, True, WEIGHTED, POWER, True, rejection=(True, s.max_dist))
+    g.set_reciprocal(True, s.max_gap)
+    one_step(engine, g, s.F, s.M, s.T)
+    _check_messy(engine, g, s, 0, "(%d, %d) alone" % (side, nr))
+    g.close()
+
+
+def test_non_finite_moving_rows_in_a_batch_of_three(engine, oracle):
+    """(64, 64) x 3 — three registrations side by side in the latency layout —; only registration 1 is messy.  Its clean neighbours are bit-identical to the same batch with the
+    clean M in registration 1."""
+    side, nr = icp_checks.MESSY_SHAPES[1]
+    s = icp_checks.messy_scene(side, nr)
+    Mem = engine.Memory
+    neighbours = [engine.synth_pair(side, seed=0x5EED + side + 7 * (b + 1), rot_deg=3.0 + 0.5 * b) for b in range(2)]
+    out = []
+    for M1 in (s.M, s.clean):
+        pairs = [neighbours[0], (s.F, M1), neighbours[1]]
+        g = icp_checks.make_handle(engine, side * side, nr, True, WEIGHTED, POWER, True, 3, rejection=(True, s.max_dist))
+        g.set_reciprocal(True, s.max_gap)
+        step_batch(engine, g, pairs, s.T)
+        if M1 is s.M:
+            _check_messy(engine, g, s, 1, "(%d, %d), registration 1 of 3" % (side, nr))
+        out.append([[g.read(mem, batch_index=b).view(np.uint32).copy() for mem in (Mem.T, Mem.W, Mem.RECIPROCAL, Mem.REVERSE_ID, Mem.NN_ID)]
+                    for b in (0, 2)])
+        g.close()
+    for b, messy, clean in zip((0, 2), out[0], out[1]):
+        for x, y, name in zip(messy, clean, ("T", "W", "RECIPROCAL", "REVERSE_ID", "NN_ID")):
+            assert_bits(x, y, "%s of registration %d beside a messy registration" % (name, b))
+        assert 0 < messy[2][3] < messy[2][0], messy[2]

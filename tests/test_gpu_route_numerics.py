@@ -1,11 +1,14 @@
-"""Every combination of the per-iteration passes, numerically: the pair filter, one-to-one, trimming and the robust loss behind the
-search, in front of each tail (reference order, fused with and without k_moment_level1, the plane system).
+"""Every combination of the per-iteration passes, numerically: the pair filter, reciprocal correspondences, one-to-one, trimming and the
+robust loss behind the search, in front of each tail (reference order, fused with and without k_moment_level1, the plane system).
 
-The order is icp_route_of's (icp_amd/csrc/icp_kernels.hip): a pair the filter rejects claims no fixed point, trimming's candidates are the
+The order is icp_route_of's (icp_amd/csrc/icp_kernels.hip): the reciprocal rule's candidates are the pairs the filter leaves, a pair
+either of them rejects claims no fixed point, trimming's candidates are the
 winners, the apply pass comes last, the plane metrics read the weights — and carry the loss — in their moments.  icp_checks.composed_rule
 states it in numpy from the single rules; every comparison here is bit for bit.  Mask bits as in test_route_table: bit 0 the pair filter
-(the boundary rule at the grid width and the normal rule with GRID normals), bit 1 one-to-one, bit 2 trimming, bit 3 the robust loss.
-Rejection by invalid points and a maximum distance is on throughout.
+(the boundary rule at the grid width and the normal rule with GRID normals), bit 1 one-to-one, bit 2 trimming, bit 3 the robust loss;
+bit 4 the reciprocal rule at the scene's max_gap.  Rejection by invalid points and a maximum distance is on throughout.  With bit 4 on
+every step also compares ICP_MEM_REVERSE_ID — every fixed point's id and the bits of its distance — with the oracle's back search at the
+step's T (reciprocal_ref.back_search) and ICP_MEM_RECIPROCAL with the rule's words.
 
 The scenes, the options (max_dist, min_cos, keep, the scales) and why they are what they are: icp_checks.ROUTE_SCENES / route_scene.
 tests/test_route_rule_cpu.py proves from the oracle alone that under them every stage of every mask removes at least 2 % of its
@@ -31,7 +34,7 @@ import p2pl_ref                                                  # noqa: E402
 import pairs_ref                                                 # noqa: E402
 import quality_ref                                               # noqa: E402
 import robust_ref as rref                                        # noqa: E402
-from icp_checks import (ROUTE_BATCH, ROUTE_METRICS, ROUTE_WORDS, assert_bits, before, check_route_pairs, check_route_plane_step,  # noqa: E402
+from icp_checks import (ROUTE_BATCH, ROUTE_METRICS, ROUTE_WORDS, assert_bits, back_at, before, check_route_pairs, check_route_plane_step,  # noqa: E402
                         check_route_step, evaluated_expectation, oracle_search, route_handle, route_proof, route_restate, route_scene, route_scene_options)
 
 pytestmark = pytest.mark.gpu
@@ -73,7 +76,9 @@ def _steps(engine, oracle, names, mask, metric, fused=None, loss=rref.CAUCHY, st
     """`steps` steps of one handle over the scenes `names`, every registration of every step checked: the step itself, then the
     ICP_PAIRS_LAST_ITERATION set against the oracle's pairs (check_route_pairs).  The first step starts at the scene's T (its words are
     the CPU proof's), each later one at the step's own T.  evaluated: behind every step also the evaluation at the T it left
-    (_check_evaluated) — the oracle's search there is the next step's expectation as well.  Returns the last step's sets."""
+    (_check_evaluated) — the oracle's search there is the next step's expectation as well.  With the reciprocal rule on (mask bit 4)
+    the oracle's back search at the step's T stands beside the forward one: the scene's own at the first step, back_at's at a later
+    one.  Returns the last step's sets."""
     Mem = engine.Memory
     scenes = [route_scene(n) for n in names]
     s0 = scenes[0]
@@ -92,11 +97,12 @@ def _steps(engine, oracle, names, mask, metric, fused=None, loss=rref.CAUCHY, st
             T0, Rb, k0 = state[b]
             want = wants[b]
             proof = route_proof(name, mask, loss)[0] if it == 0 else None
+            back = None if not mask & 16 else s.back if it == 0 else back_at(name, s.F, s.M, T0, s.nr)
             what = "%s, scene %s, mask %d, loss %d, step %d" % (metric, name, mask, loss, it)
             if metric == "p2p":
-                r = check_route_step(engine, oracle, g, s.F, s.M, s.NF, s.NM, T0, Rb, want, o, fused, b, proof, what)
+                r = check_route_step(engine, oracle, g, s.F, s.M, s.NF, s.NM, T0, Rb, want, o, fused, b, proof, what, back)
             else:
-                r = check_route_plane_step(engine, g, s.F, s.M, s.NF, s.NM, T0, Rb, k0, want, o, route_restate(metric, o, s.M), b, proof, what)
+                r = check_route_plane_step(engine, g, s.F, s.M, s.NF, s.NM, T0, Rb, k0, want, o, route_restate(metric, o, s.M), b, proof, what, back)
             PF, PM = (s.PF, s.PM) if it == 0 else (s.F[want[0]["id"]], oracle.transform_q(s.M, T0))
             if it == 0:                                           # (the first step's weights from the reference's pairs too: the CPU proof's)
                 r = route_proof(name, mask, loss, metric != "p2p")[0]
@@ -112,14 +118,14 @@ def _steps(engine, oracle, names, mask, metric, fused=None, loss=rref.CAUCHY, st
 
 # ---- 1. the grid: every mask at both shapes ------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("mask", range(16))
+@pytest.mark.parametrize("mask", range(32))
 @pytest.mark.parametrize("fused", MODES)
 @pytest.mark.parametrize("name", GRID)
 def test_point_to_point(engine, oracle, name, fused, mask):
     _steps(engine, oracle, [name], mask, "p2p", fused)
 
 
-@pytest.mark.parametrize("mask", range(16))
+@pytest.mark.parametrize("mask", range(32))
 @pytest.mark.parametrize("metric", ROUTE_METRICS)
 @pytest.mark.parametrize("name", GRID)
 def test_plane_family(engine, oracle, name, metric, mask):
@@ -134,7 +140,7 @@ CASES = [("p2p", True), ("p2p", False)] + [(metric, None) for metric in ROUTE_ME
 @pytest.mark.parametrize("loss", [rref.HUBER, rref.TUKEY])
 @pytest.mark.parametrize("metric,fused", CASES)
 def test_every_pass_with_the_other_losses(engine, oracle, metric, fused, loss):
-    _steps(engine, oracle, ["30"], 15, metric, fused, loss, evaluated=True)
+    _steps(engine, oracle, ["30"], 31, metric, fused, loss, evaluated=True)
 
 
 def test_tukey_zeroes_show_in_the_point_to_point_set_only(engine, oracle):
@@ -153,12 +159,12 @@ def test_tukey_zeroes_show_in_the_point_to_point_set_only(engine, oracle):
 @pytest.mark.parametrize("metric,fused", CASES[:3])
 def test_every_pass_in_a_batch_of_three(engine, oracle, metric, fused):
     """Three different scenes at (128, 64) in one handle, the dense layout by batch: each registration by its index."""
-    _steps(engine, oracle, list(ROUTE_BATCH), 15, metric, fused, evaluated=True)
+    _steps(engine, oracle, list(ROUTE_BATCH), 31, metric, fused, evaluated=True)
 
 
 @pytest.mark.parametrize("metric,fused", CASES)
 def test_every_pass_at_config_A(engine, oracle, metric, fused):
-    _steps(engine, oracle, ["A"], 15, metric, fused, evaluated=True)
+    _steps(engine, oracle, ["A"], 31, metric, fused, evaluated=True)
 
 
 # ---- 3. several iterations --------------------------------------------------------------------------------------------------------------
@@ -169,12 +175,16 @@ ANGLE, TRANSLATION, MAX_IT = 0.001, 0.01, 40                     # (icp_init's d
 
 def _snapshot(engine, g):
     Mem = engine.Memory
-    return ([g.read(Mem.T).copy(), g.read(Mem.W).copy()] + [g.read(getattr(Mem, name)).copy() for name in ROUTE_WORDS]
-            + [g.correspondences(engine.Pairs.LAST_ITERATION).view(np.uint32)])
+    out = ([g.read(Mem.T).copy(), g.read(Mem.W).copy()] + [g.read(getattr(Mem, name)).copy() for name in ROUTE_WORDS]
+           + [g.correspondences(engine.Pairs.LAST_ITERATION).view(np.uint32)])
+    if g.reciprocal() is not None:
+        out.append(g.read(Mem.REVERSE_ID).view(np.uint32).copy())
+    return out
 
 
 def _same(a, b, what):
-    for x, y, name in zip(a, b, ("T", "W") + tuple(ROUTE_WORDS) + ("the LAST_ITERATION set",)):
+    assert len(a) == len(b), (what, len(a), len(b))
+    for x, y, name in zip(a, b, ("T", "W") + tuple(ROUTE_WORDS) + ("the LAST_ITERATION set", "REVERSE_ID")):
         assert_bits(x, y, "%s: %s" % (what, name))
 
 
@@ -186,13 +196,14 @@ def _loaded(engine, mask, metric, fused):
     return g, s
 
 
-@pytest.mark.parametrize("mask", [7, 15])
+@pytest.mark.parametrize("mask", [7, 15, 31])
 @pytest.mark.parametrize("metric,fused", RUNS)
 def test_run_fixed_equals_steps(engine, metric, fused, mask):
     g, _ = _loaded(engine, mask, metric, fused)
     g.run_fixed(4)
     fixed = _snapshot(engine, g)
     assert fixed[2][3] > 0 and fixed[3][1] > 0 and fixed[4][3] > 0, fixed[2:]
+    assert (0 < fixed[5][3] < fixed[5][0] and len(fixed) == 8) if mask & 16 else not fixed[5].any(), fixed[5]
     g.reset_transform(); g.buildRBC()
     for _ in range(4):
         g.step()
@@ -200,7 +211,7 @@ def test_run_fixed_equals_steps(engine, metric, fused, mask):
     g.close()
 
 
-@pytest.mark.parametrize("mask", [7, 15])
+@pytest.mark.parametrize("mask", [7, 15, 31])
 @pytest.mark.parametrize("metric,fused", RUNS)
 def test_run_equals_stepping_until_done(engine, metric, fused, mask):
     """Done is the header's: the step's Tk under both thresholds (p2pl_ref.check_converged) or max_iterations steps taken."""
@@ -220,7 +231,7 @@ def test_run_equals_stepping_until_done(engine, metric, fused, mask):
     g.close()
 
 
-@pytest.mark.parametrize("mask", [7, 15])
+@pytest.mark.parametrize("mask", [7, 15, 31])
 @pytest.mark.parametrize("metric,fused", RUNS)
 def test_every_pass_off_again_equals_never_on(engine, metric, fused, mask):
     g, s = _loaded(engine, mask, metric, fused)
@@ -229,7 +240,8 @@ def test_every_pass_off_again_equals_never_on(engine, metric, fused, mask):
     stats = (h.run_form(), h.launches_per_iteration())
     g.run(); g.run_fixed(3)
     assert g.read(engine.Memory.TRIM)[3] > 0
-    g.set_robust_loss(rref.NONE); g.set_trimming(1.0); g.set_unique(False)
+    assert (g.read(engine.Memory.RECIPROCAL)[3] > 0) == bool(mask & 16)
+    g.set_robust_loss(rref.NONE); g.set_trimming(1.0); g.set_unique(False); g.set_reciprocal(False)
     g.set_normal_rejection(None); g.set_boundary_rejection(None)
     for name in ROUTE_WORDS:
         assert np.all(g.read(getattr(engine.Memory, name)) == 0), name

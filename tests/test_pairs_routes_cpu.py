@@ -7,6 +7,7 @@ position pass.
    (icp_checks.last_stage_count) — the header's statement about the count, from composed_rule alone.  SHARES records the sizes.
 2. The Tukey condition: with the loss alone (mask 8) the point-to-point set is smaller than the plane set by at least 5 % of it; with
    every pass on (mask 15) the two are equal — trimming has removed what Tukey would zero —, which is why the device test uses mask 8.
+   Both hold again with the reciprocal rule on (masks 24 and 31).
 3. The layout scenes (icp_checks.LAYOUT_CASES): the LAST_ITERATION expectation at _t0 () and the EVALUATED expectation at the oracle's T
    after that step each hold between 10 % and 90 % of the points icp_evaluate counts.  LAYOUT_SHARES records them.
 
@@ -24,18 +25,24 @@ import pairs_ref                                                 # noqa: E402
 import quality_ref                                               # noqa: E402
 import robust_ref as rref                                        # noqa: E402
 from icp_checks import (LAYOUT_CASES, POWER, ROUTE_BATCH, evaluated_expectation, expected_pieces, last_stage_count, layout_scene,  # noqa: E402
-                        pick_max_dist, route_proof, route_scene, route_scene_options)
+                        pick_max_dist, route_proof, route_scene, route_scene_options, ROUTE_SCENES)
 
-# scene -> the size of the expected set per mask 0 .. 15 (Cauchy), (point-to-point, a plane metric); they differ only where the
-# point-to-point loss zeroes a weight, which Cauchy and Huber never do
-SHARES = {"30": [(706, 706), (500, 500), (505, 505), (396, 396), (530, 530), (375, 375), (379, 379), (297, 297)] * 2,
+# scene -> the size of the expected set per mask 0 .. 31 (Cauchy), (point-to-point, a plane metric); they differ only where the
+# point-to-point loss zeroes a weight, which Cauchy and Huber never do.  Masks 16 .. 31: the reciprocal rule on as well.
+SHARES = {"30": [(706, 706), (500, 500), (505, 505), (396, 396), (530, 530), (375, 375), (379, 379), (297, 297)] * 2
+                + [(494, 494), (360, 360), (449, 449), (337, 337), (371, 371), (270, 270), (337, 337), (253, 253)] * 2,
           "150": [(17642, 17642), (14199, 14199), (10821, 10821), (10158, 10158), (13232, 13232), (10650, 10650), (8116, 8116),
-                  (7619, 7619)] * 2}                             # (78.4 % of m at mask 0 down to 33.0 % and 33.9 % with every stage on)
-# (scene, loss) -> the sizes beyond the grid: every pass on
+                  (7619, 7619)] * 2                              # (78.4 % of m at mask 0 down to 33.0 % and 33.9 % with every stage on)
+                 + [(12349, 12349), (10519, 10519), (9065, 9065), (8309, 8309), (9262, 9262), (7890, 7890), (6799, 6799),
+                    (6232, 6232)] * 2}                           # (54.9 % of m at mask 16 down to 28.1 % and 27.7 % at mask 31)
+# (scene, loss) -> the sizes beyond the grid: every pass on but the reciprocal rule (mask 15), and every pass on (mask 31)
 BEYOND = {("30", rref.HUBER): (297, 297), ("30", rref.TUKEY): (297, 297), ("A", rref.CAUCHY): (5298, 5298),
           ("batch0", rref.CAUCHY): (5406, 5406), ("batch1", rref.CAUCHY): (4647, 4647), ("batch2", rref.CAUCHY): (5937, 5937)}
-# scene -> mask 8 with Tukey: (point-to-point, a plane metric)
+BEYOND_31 = {("30", rref.HUBER): (253, 253), ("30", rref.TUKEY): (253, 253), ("A", rref.CAUCHY): (4337, 4337),
+             ("batch0", rref.CAUCHY): (4430, 4430), ("batch1", rref.CAUCHY): (3702, 3702), ("batch2", rref.CAUCHY): (5057, 5057)}
+# scene -> mask 8 with Tukey: (point-to-point, a plane metric); mask 24, the reciprocal rule in front of it
 TUKEY = {"30": (635, 706), "150": (15877, 17642)}
+TUKEY_24 = {"30": (449, 494), "150": (11473, 12349)}
 
 
 def _sizes(name, mask, loss):
@@ -59,7 +66,7 @@ def _in_range(n, m, what):
     assert 0.2 * m <= n <= 0.9 * m, "%s: the expected set holds %d of %d pairs" % (what, n, m)
 
 
-@pytest.mark.parametrize("mask", range(16))
+@pytest.mark.parametrize("mask", range(32))
 @pytest.mark.parametrize("name", ["30", "150"])
 def test_member_shares_of_the_grid(engine, oracle, name, mask):
     m = route_scene(name).M.shape[0]
@@ -79,8 +86,37 @@ def test_member_shares_beyond_the_grid(engine, oracle, name, loss):
     assert got == BEYOND[(name, loss)], (got, BEYOND[(name, loss)])
 
 
+@pytest.mark.parametrize("name,loss", list(BEYOND_31))
+def test_member_shares_beyond_the_grid_with_the_reciprocal_rule(engine, oracle, name, loss):
+    """Mask 31: what tests/test_gpu_route_numerics.py runs beyond the grid."""
+    m = route_scene(name).M.shape[0]
+    got = _sizes(name, 31, loss)
+    for n in got:
+        _in_range(n, m, "scene %s, mask 31, loss %d" % (name, loss))
+    assert got == BEYOND_31[(name, loss)], (got, BEYOND_31[(name, loss)])
+
+
+def test_the_smallest_set_of_the_new_masks(engine, oracle):
+    """Every scene, mask 16 .. 31, loss and family: the smallest expected set is 22.6 % of m (batch1 with the filter, the rule, one-to-one
+    and trimming on, whatever the loss and the family): inside the band of _in_range, like every other."""
+    sizes = {}
+    for name in ROUTE_SCENES:
+        m = route_scene(name).M.shape[0]
+        for mask in range(16, 32):
+            for loss in ((rref.HUBER, rref.CAUCHY, rref.TUKEY) if mask & 8 else (rref.CAUCHY,)):
+                for plane, n in enumerate(_sizes(name, mask, loss)):
+                    _in_range(n, m, "scene %s, mask %d, loss %d" % (name, mask, loss))
+                    sizes[name, mask, loss, plane] = n / m
+    low = min(sizes, key=sizes.get)
+    assert low[0] == "batch1" and low[1] & 23 == 23 and round(1000 * sizes[low]) == 226, (low, sizes[low])
+    assert sizes["batch1", 31, rref.TUKEY, 1] == sizes[low], "(no loss changes the size there: the sets of masks 23 and 31 tie)"
+
+
 def test_the_batch_has_three_different_sets(engine, oracle):
     assert len({BEYOND[(n, rref.CAUCHY)] for n in ROUTE_BATCH}) == 3
+    assert len({BEYOND_31[(n, rref.CAUCHY)] for n in ROUTE_BATCH}) == 3
+    accepted = [int(route_proof(n, 31)[0].words["RECIPROCAL"][3]) for n in ROUTE_BATCH]
+    assert accepted == [7488, 6478, 8545], accepted
 
 
 @pytest.mark.parametrize("name", list(TUKEY))
@@ -95,6 +131,14 @@ def test_the_tukey_condition(engine, oracle, name):
     assert not (rp.W_before_loss[r8.W != 0] == 0).any(), "the point-to-point set is a subset of the plane set"
     both = _sizes(name, 15, rref.TUKEY)
     assert both[0] == both[1], "every pass on: trimming has removed what Tukey would zero (%r)" % (both,)
+    # the same two statements with the reciprocal rule in front (masks 24 and 31): re-established, not corrected — the rule removes
+    # pairs of every residual, Tukey still zeroes more than 5 % of what it leaves, and trimming still removes all of those
+    p2p, plane = _sizes(name, 24, rref.TUKEY)
+    _in_range(p2p, m, "the rule and Tukey, point-to-point"); _in_range(plane, m, "the rule and Tukey, a plane metric")
+    assert (p2p, plane) == TUKEY_24[name], (p2p, plane)
+    assert plane - p2p >= 0.05 * plane, "behind the rule Tukey zeroes %d of %d weights" % (plane - p2p, plane)
+    both = _sizes(name, 31, rref.TUKEY)
+    assert both[0] == both[1], "every pass on, the rule included: trimming has removed what Tukey would zero (%r)" % (both,)
     assert s.scale[rref.TUKEY] > 0
 
 

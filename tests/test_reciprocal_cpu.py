@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import icp_checks                                                # noqa: E402
+import quality_ref                                               # noqa: E402
 import reciprocal_ref as ref                                     # noqa: E402
 from reciprocal_ref import EXACT, NEAR_20, rotation_T            # noqa: E402
 from icp_checks import IDENTITY, _t0, oracle_search              # noqa: E402
@@ -114,3 +116,92 @@ def test_pinned_counts_of_the_oracle(engine, oracle, side, nr):
         gap = F32(np.quantile(g, 0.25))
         _, _, _, c = ref.reciprocal_rule(fwd["id"], rev["id"], QT, W0, gap)
         assert 0 < c[2] and c[3] < c[0]
+
+
+# ---- the conditions tests/test_gpu_reciprocal.py relies on in every search layout, for a converged registration and at the rule's
+# ---- edges, each from the oracle alone ------------------------------------------------------------------------------------------------
+
+# (side, |R|, batch, zero) -> max_gap to three decimals, per registration ICP_MEM_RECIPROCAL's words and the size of the trimmed set,
+# and the back answers that name an origin row of M
+LAYOUT_RECIPROCAL = {
+    (256, 256, 1, 0.0): (51.840, [([57671, 2725, 31878, 34603], 25953)], 0),
+    (256, 512, 1, 0.1): (51.579, [([51925, 2522, 28633, 31155], 23367)], 6576),
+    (128, 64, 3, 0.0): (51.756, [([14418, 1382, 7269, 8651], 6489), ([13335, 1144, 6401, 7545], 5659), ([12422, 1025, 5827, 6852], 5139)], 0),
+    (64, 64, 9, 0.0): (54.201, [([3604, 651, 1511, 2162], 1622), ([3333, 578, 1338, 1916], 1437), ([3131, 479, 1240, 1719], 1290),
+                                ([2936, 445, 1161, 1606], 1205), ([2759, 426, 1044, 1470], 1103), ([2604, 396, 958, 1354], 1016),
+                                ([2485, 379, 914, 1293], 970), ([2373, 357, 902, 1259], 945), ([2263, 335, 841, 1176], 882)], 0),
+    (256, 8192, 1, 0.0): (50.653, [([57671, 2294, 32309, 34603], 25953)], 0),
+    (192, 2048, 1, "blobs30"): (55.619, [([22324, 1072, 12322, 13394], 10046)], 12072)}
+
+
+@pytest.mark.parametrize("case", icp_checks.LAYOUT_CASES, ids=lambda c: "%d-%d-%d-%d-%s" % c[:5])
+def test_layout_scenes_with_the_rule(engine, oracle, case):
+    """icp_checks.layout_reciprocal: max_gap between 50.6 and 55.7 mm, accepted 60 % of registration 0's candidates, and the conditions
+    the device test asserts again (icp_checks.layout_reciprocal_conditions).  In the two scenes with holes every invalid fixed point
+    is a query of the back search, and its answer is one of M's thousands of coincident origin points: a tie only the search's
+    tie-break decides."""
+    side, nr, batch, fused, zero, _ = case
+    sc, lr = icp_checks.layout_scene(side, nr, batch, zero), icp_checks.layout_reciprocal(side, nr, batch, zero)
+    assert 50.6 <= lr.max_gap <= 55.7 and float(F32(lr.max_gap)) == lr.max_gap, lr.max_gap
+    words = [r.words["RECIPROCAL"] for r in lr.rules]
+    finals = [int(np.count_nonzero(r.W)) for r in lr.rules]
+    counted = [int(np.count_nonzero(quality_ref.masks(M, pf, pm, 0.0)[0])) for (_, M), pf, pm in zip(sc.pairs, sc.PF, sc.PM)]
+    origin = sum(int(np.count_nonzero(icp_checks.origin_rows(M)[back[0][0]["id"]])) for (_, M), back in zip(sc.pairs, lr.backs))
+    holes = any(icp_checks.origin_rows(M).any() for _, M in sc.pairs)
+    for (F, M), back, r, w in zip(sc.pairs, lr.backs, lr.rules, words):
+        assert back[1] and back[0][0]["id"].shape[0] == F.shape[0] and (back[0][0]["id"] < M.shape[0]).all()
+        assert r.words["TRIM"][1] == w[3] and r.words["TRIM"][3] == np.count_nonzero(r.W), "trimming's candidates are the pairs the rule accepts"
+        if holes:                                                 # (every invalid fixed point's answer is an origin row of M)
+            assert icp_checks.origin_rows(M)[back[0][0]["id"]][icp_checks.origin_rows(F)].all() and icp_checks.origin_rows(M).sum() > 1000
+    assert abs(int(words[0][3]) - 0.6 * int(words[0][0])) <= 1.0, words[0]
+    icp_checks.layout_reciprocal_conditions(words, finals, counted, origin / (batch * side * side) if holes else None, str(case[:5]))
+    gap, rows, origin_want = LAYOUT_RECIPROCAL[(side, nr, batch, zero)]
+    assert abs(lr.max_gap - gap) <= 1e-3 and origin == origin_want, (lr.max_gap, origin)
+    assert [(w.tolist(), f) for w, f in zip(words, finals)] == rows, [(w.tolist(), f) for w, f in zip(words, finals)]
+
+
+def test_a_registration_of_a_frame_with_itself_is_done_at_once(engine, oracle):
+    """icp_checks.converged_pairs' registration 0 at the identity: every one of the 14742 valid points finds itself at distance 0 in
+    both directions, the rule's words are [14742, 14742, 0, 14742], and the step's Tk is the identity — ICP::check stops at k = 1."""
+    import p2pl_ref
+    (F, M), _, _ = icp_checks.converged_pairs()
+    s = icp_checks.route_scene("batch0")
+    T = np.array(IDENTITY, F32)
+    want = oracle_search(oracle, F, M, T, s.nr)
+    (rev, _), ok = ref.back_search(oracle, F, M, T, s.nr)
+    valid = ~icp_checks.origin_rows(F)
+    rows = np.flatnonzero(valid)
+    assert ok and len(rows) == 14742
+    assert np.array_equal(want[0]["id"][valid], rows) and not want[0]["dist"][valid].any()
+    assert np.array_equal(rev["id"][valid], rows) and not rev["dist"][valid].any()
+    PF, PM = np.ascontiguousarray(F[want[0]["id"]]), oracle.transform_q(M, T)
+    W0 = icp_checks.weights_before_trim(want[0], M, PF, PM, True, True, s.max_dist)
+    _, _, zero, counts = ref.reciprocal_rule(want[0]["id"], rev["id"], PM, W0, s.max_gap, ok)
+    assert counts.tolist() == [14742, 14742, 0, 14742] and np.array_equal(~zero, valid)
+    for fused in (True, False):
+        Tk = icp_checks.expected_pieces(oracle, F, M, T, want[0], s.side, fused, True, icp_checks.POWER, fused, zero)[4]
+        # (the power method leaves 1e-24 in the quaternion's vector part: the identity to every threshold)
+        assert np.allclose(Tk, IDENTITY, rtol=0, atol=1e-12) and p2pl_ref.check_converged(Tk, 0.001, 0.01), Tk
+
+
+def test_a_max_gap_that_squares_to_a_pair_s_gap_exists(engine, oracle):
+    """Scene 30 behind the search's rejection: 142 of the 269 distinct squared gaps (fp32) of the non-exact candidates are the float
+    square of some float max_gap.  The median one belongs to one pair; at that max_gap the pair is near, at the next float below it
+    is not, and nothing else changes."""
+    s = icp_checks.route_scene("30")
+    ids, rev = s.want[0]["id"], s.back[0][0]["id"]
+    W0 = icp_checks.weights_before_trim(s.want[0], s.M, s.PF, s.PM, True, True, s.max_dist)
+    g2, gap, below, pairs, (distinct, have) = ref.equality_gap(ids, rev, s.PM, W0)
+    assert (distinct, have) == (269, 142) and pairs >= 1
+    assert F32(np.float64(F32(gap)) * np.float64(F32(gap))) == g2 and F32(np.float64(F32(below)) * np.float64(F32(below))) < g2
+    assert float(F32(gap)) == gap and float(F32(below)) == below < gap
+    at, under = ref.reciprocal_rule(ids, rev, s.PM, W0, gap), ref.reciprocal_rule(ids, rev, s.PM, W0, below)
+    assert at[3][2] - under[3][2] == pairs and at[3][1] == under[3][1] and at[3][0] == under[3][0], (at[3], under[3])
+    assert np.count_nonzero(at[1] & ~under[1]) == pairs and not (under[1] & ~at[1]).any() and 0 < under[3][2]
+
+
+@pytest.mark.parametrize("side,nr", icp_checks.MESSY_SHAPES)
+def test_non_finite_moving_rows_are_no_answer_of_the_back_search(engine, oracle, side, nr):
+    s = icp_checks.messy_scene(side, nr)
+    icp_checks.messy_conditions(s.finite, s.W0, s.back[0][0]["id"], s.rule[3], "the oracle, (%d, %d)" % (side, nr))
+    assert s.back[1] and np.isfinite(s.back[0][0]["dist"]).all()
