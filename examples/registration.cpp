@@ -7,7 +7,7 @@
 //   registration A B                      data/A.bin, data/B.bin — or A and B themselves when they name existing files
 //   ... [--out FILE] [--device N] [--reference-order] [--svd] [--reject-invalid] [--max-dist MM] [--trim FRACTION]
 //       [--point-to-plane MU] [--colored KAPPA] [--robust KIND:SCALE] [--plane-to-plane EPS] [--symmetric] [--one-to-one]
-//       [--reciprocal [GAP]] [--evaluate MAXDIST] [--pyramid LEVELS[:MAXDZ]]
+//       [--reciprocal [GAP]] [--projective [RADIUS]] [--evaluate MAXDIST] [--pyramid LEVELS[:MAXDZ]]
 //
 // --reject-invalid / --max-dist: correspondence rejection (icp_set_rejection: pairs with a pixel without depth at either end / pairs
 // farther apart than MM get weight 0).  --trim: trimmed ICP (icp_set_trimming: every iteration keeps the closest FRACTION in (0, 1] of the
@@ -22,6 +22,9 @@
 // --one-to-one: one-to-one correspondences (icp_set_unique): of the pairs that share a fixed point only the closest keeps its weight.
 // --reciprocal: reciprocal correspondences (icp_set_reciprocal): a pair keeps its weight only if its fixed point, searching the moving
 // frame, finds the pair's moving point again, or one within GAP mm of it (default 0: exactly that point).
+// --projective: projective data association (icp_set_projective): every moving landmark is paired with the closest fixed landmark of the
+// (2 RADIUS + 1)^2 window around the cell of the fixed landmark grid it projects to, instead of searching (RADIUS in [0, 8], default 1).
+// The intrinsics are those of the landmarks of a 640 x 480 frame (column 65 + 4 i, row 49 + 3 j), for files and the synthetic pair alike.
 // --evaluate: after the run, the registration's quality at the final transform (icp_evaluate): fitness, inlier RMSE and the inlier
 // count for pairs no farther apart than MAXDIST mm (0: no distance test).
 // --pyramid: coarse-to-fine registration (icp_pyramid_*): LEVELS landmark grids 128, 64, 32, .. wide with 256, 64, 64, .. representatives,
@@ -41,6 +44,8 @@
 namespace {
 
 const size_t kPoints = 640u * 480u;
+// the pinhole model of the 128 x 128 landmarks of a 640 x 480 frame, in grid units (include/icp_amd.h: icp_set_projective)
+const float kLmFx = 595.f / 4.f, kLmFy = 595.f / 3.f, kLmCx = (319.5f - 65.f) / 4.f, kLmCy = (239.5f - 49.f) / 3.f;
 
 bool exists (const std::string &p) { std::ifstream f (p, std::ios::binary); return f.good (); }
 
@@ -58,11 +63,12 @@ std::string data_path (const std::string &name) { return exists (name) ? name : 
 template <cl_algo::ICP::ICPStepConfigT RC>
 int run (int device, icp::Mode mode, const std::vector<icp_float8> &pc1, const std::vector<icp_float8> &pc2, const std::string &out,
          int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa, icp::RobustLoss robust, float gicp_eps, bool symmetric, bool one_to_one,
-         float reciprocal, float evaluate)
+         float reciprocal, int projective, float evaluate)
 {
     ICPReg<RC, cl_algo::ICP::ICPStepConfigW::WEIGHTED> app (device, mode);
     if (reject_flags || max_dist > 0.f) app.setRejection (reject_flags, max_dist);
     if (reciprocal >= 0.f) app.setReciprocal (true, reciprocal);
+    if (projective >= 0) app.setProjective (true, 128, kLmFx, kLmFy, kLmCx, kLmCy, (uint32_t) projective);
     if (one_to_one) app.setUnique (true);
     if (trim != 1.f) app.setTrimming (trim);
     if (robust.loss != icp::RobustLoss::NONE) app.setRobustLoss (robust);
@@ -97,7 +103,7 @@ void check_level (icp_handle h, int rc) { if (rc != ICP_OK) throw std::runtime_e
 template <cl_algo::ICP::ICPStepConfigT RC>
 int run_pyramid (int device, icp::Mode mode, unsigned levels, float max_dz, const std::vector<icp_float8> &pc1, const std::vector<icp_float8> &pc2, const std::string &out,
                  int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa, icp::RobustLoss robust, float gicp_eps, bool symmetric, bool one_to_one,
-                 float reciprocal, float evaluate)
+                 float reciprocal, int projective, float evaluate)
 {
     cl_algo::ICP::ICPPyramid<RC, cl_algo::ICP::ICPStepConfigW::WEIGHTED> pyr (icp::Env (device), mode);
     std::vector<uint32_t> nr (levels, 64u); nr[0] = 256u;
@@ -108,6 +114,10 @@ int run_pyramid (int device, icp::Mode mode, unsigned levels, float max_dz, cons
         const uint32_t gw = 128u >> l;
         if (reject_flags || max_dist > 0.f) check_level (h, icp_set_rejection (h, reject_flags, max_dist));
         if (reciprocal >= 0.f) check_level (h, icp_set_reciprocal (h, 1, reciprocal));
+        if (projective >= 0) {                               // (a level's cell is the mean of 2^l x 2^l finest cells: centred on finest column 2^l i + (2^l - 1) / 2)
+            const float f = (float) (1u << l), half = (f - 1.f) / 2.f;
+            check_level (h, icp_set_projective (h, 1, gw, kLmFx / f, kLmFy / f, (kLmCx - half) / f, (kLmCy - half) / f, (uint32_t) projective));
+        }
         if (one_to_one) check_level (h, icp_set_unique (h, 1));
         if (trim != 1.f) check_level (h, icp_set_trimming (h, trim));
         if (robust.loss != icp::RobustLoss::NONE) check_level (h, icp_set_robust_loss (h, robust.loss, robust.scale));
@@ -150,7 +160,7 @@ int main (int argc, char **argv)
     std::vector<std::string> names;
     std::string out;
     int device = 0; bool svd = false, symmetric = false, one_to_one = false;
-    int reject_flags = 0; float max_dist = 0.f, trim = 1.f, p2pl_mu = -1.f, kappa = -1.f, gicp_eps = 0.f, evaluate = -1.f, reciprocal = -1.f;     // (p2pl_mu < 0: point-to-point; kappa < 0: not colored; gicp_eps 0: off; evaluate < 0: no quality report; reciprocal < 0: off)
+    int reject_flags = 0; float max_dist = 0.f, trim = 1.f, p2pl_mu = -1.f, kappa = -1.f, gicp_eps = 0.f, evaluate = -1.f, reciprocal = -1.f; int projective = -1;     // (p2pl_mu < 0: point-to-point; kappa < 0: not colored; gicp_eps 0: off; evaluate < 0: no quality report; reciprocal < 0: off)
     icp::RobustLoss robust;
     unsigned pyramid_levels = 0; float pyramid_dz = 0.f;       // (0 levels: one level, no pyramid object)
     icp::Mode mode = icp::Mode::FAST;
@@ -208,6 +218,17 @@ int main (int argc, char **argv)
                 }
             }
         }
+        else if (a == "--projective") {                           // (RADIUS is optional: taken when the next argument is a number)
+            projective = 1;
+            if (i + 1 < argc) {
+                char *end = nullptr;
+                const long r = std::strtol (argv[i + 1], &end, 10);
+                if (end != argv[i + 1] && *end == 0) {
+                    if (r < 0 || r > 8) { std::fprintf (stderr, "--projective: RADIUS must be in [0, 8]\n"); return 2; }
+                    projective = (int) r; ++i;
+                }
+            }
+        }
         else if (a == "--robust" && i + 1 < argc) {
             const std::string v = argv[++i];
             const size_t c = v.find (':');
@@ -236,10 +257,10 @@ int main (int argc, char **argv)
             read_cloud (data_path (names[0]), pc1); read_cloud (data_path (names[1]), pc2);
         }
         if (pyramid_levels)
-            return svd ? run_pyramid<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pyramid_levels, pyramid_dz, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, reciprocal, evaluate)
-                       : run_pyramid<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pyramid_levels, pyramid_dz, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, reciprocal, evaluate);
-        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, reciprocal, evaluate)
-                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, reciprocal, evaluate);
+            return svd ? run_pyramid<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pyramid_levels, pyramid_dz, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, reciprocal, projective, evaluate)
+                       : run_pyramid<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pyramid_levels, pyramid_dz, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, reciprocal, projective, evaluate);
+        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, reciprocal, projective, evaluate)
+                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, reciprocal, projective, evaluate);
     }
     catch (const std::exception &e)
     {

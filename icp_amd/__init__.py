@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 __all__ = ["ICP", "ICPStep", "ICPError", "Memory", "Quality", "Pairs", "PAIR", "ErrorMetric", "Normals", "ICPStepConfigT", "ICPStepConfigW",
-           "PowerMode", "ReduceMode", "TransformKind", "ICPBatch", "batch_partition", "power_method", "KernelObject", "kernel_lms", "kernel_reps", "kernel_weights", "kernel_mean", "kernel_devs", "kernel_s", "ReduceScan", "lib", "lib_path", "reduce", "scan", "ReduceConfig", "synth_pair", "synth_cloud_vga", "punch_holes", "HOLES_SCATTERED", "HOLES_CONTIGUOUS", "synth_pair_scene", "SCENE_CURVED", "SCENE_WALL", "device_count", "DIST_ID"]
+           "PowerMode", "ReduceMode", "TransformKind", "ICPBatch", "batch_partition", "power_method", "KernelObject", "kernel_lms", "kernel_reps", "kernel_weights", "kernel_mean", "kernel_devs", "kernel_s", "ReduceScan", "lib", "lib_path", "reduce", "scan", "ReduceConfig", "synth_pair", "synth_cloud_vga", "punch_holes", "HOLES_SCATTERED", "HOLES_CONTIGUOUS", "synth_pair_scene", "SCENE_CURVED", "SCENE_WALL", "device_count", "DIST_ID", "grid_intrinsics", "landmark_intrinsics"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("ICP_AMD_LIB", os.path.join(_HERE, "libicp_amd.so"))   # override: A/B builds of the same ABI
@@ -87,7 +87,7 @@ class TransformKind:             # ICPTransformConfig (include/ICP/algorithms.hp
 
 class Memory:                    # icp_mem in include/icp_amd.h
     F, M, T, TK, MEANS, S, NN_ID, W, SUM_W, REPS, RBC_N, RBC_O, RBC_PERM, RBC_OWNER, RBC_XP, RID, R, RK, NN, QT, TRIM, \
-        NORMALS_F, PLANE_SYSTEM, COLOR_GRAD_F, NORMALS_M, UNIQUE, PAIR_FILTER, RECIPROCAL, REVERSE_ID = range(29)
+        NORMALS_F, PLANE_SYSTEM, COLOR_GRAD_F, NORMALS_M, UNIQUE, PAIR_FILTER, RECIPROCAL, REVERSE_ID, PROJECTIVE = range(30)
     # reference spellings (ICPStep::Memory, include/ICP/algorithms.hpp:2241-2267)
     D_IN_F, D_IN_M, D_IO_T, H_IO_T = F, M, T, T
 
@@ -185,6 +185,8 @@ def lib():
     sig("icp_get_unique", i32, vp, C.POINTER(i32))
     sig("icp_set_reciprocal", i32, vp, i32, C.c_float)
     sig("icp_get_reciprocal", i32, vp, C.POINTER(i32), C.POINTER(C.c_float))
+    sig("icp_set_projective", i32, vp, i32, u32, f32, f32, f32, f32, u32)
+    sig("icp_get_projective", i32, vp, C.POINTER(i32), C.POINTER(u32), C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), C.POINTER(u32))
     sig("icp_set_normal_rejection", i32, vp, i32, f32)
     sig("icp_get_normal_rejection", i32, vp, C.POINTER(i32), C.POINTER(f32))
     sig("icp_set_boundary_rejection", i32, vp, u32)
@@ -234,6 +236,7 @@ def lib():
     sig("icp_batch_set_trimming", i32, vp, f32)
     sig("icp_batch_set_unique", i32, vp, i32)
     sig("icp_batch_set_reciprocal", i32, vp, i32, C.c_float)
+    sig("icp_batch_set_projective", i32, vp, i32, u32, f32, f32, f32, f32, u32)
     sig("icp_batch_set_normal_rejection", i32, vp, i32, f32)
     sig("icp_batch_set_boundary_rejection", i32, vp, u32)
     sig("icp_batch_set_robust_loss", i32, vp, i32, f32)
@@ -624,8 +627,27 @@ _MEM_DTYPE = {
     Memory.NN: (np.float32, 4), Memory.QT: (np.float32, 4), Memory.TRIM: (np.uint32, None),
     Memory.NORMALS_F: (np.float32, 4), Memory.PLANE_SYSTEM: (np.float64, None), Memory.COLOR_GRAD_F: (np.float32, 4),
     Memory.NORMALS_M: (np.float32, 4), Memory.UNIQUE: (np.uint32, None), Memory.PAIR_FILTER: (np.uint32, None),
-    Memory.RECIPROCAL: (np.uint32, None), Memory.REVERSE_ID: (DIST_ID, None),
+    Memory.RECIPROCAL: (np.uint32, None), Memory.REVERSE_ID: (DIST_ID, None), Memory.PROJECTIVE: (np.uint32, None),
 }
+
+
+def grid_intrinsics(side):
+    """(fx, fy, cx, cy) in grid units of the side x side landmark grids synth_pair / synth_pair_scene sample from their 640 x 480 pinhole
+    image (ICPStep.set_projective): 595 side / 640, 595 side / 480, 319.5 side / 640, 239.5 side / 480."""
+    return 595.0 * side / 640.0, 595.0 * side / 480.0, 319.5 * side / 640.0, 239.5 * side / 480.0
+
+
+def landmark_intrinsics():
+    """(fx, fy, cx, cy) in grid units of the 128 x 128 landmarks write_cloud samples from a 640 x 480 frame (column 65 + 4 i, row 49 + 3 j):
+    595 / 4, 595 / 3, (319.5 - 65) / 4, (239.5 - 49) / 3 (ICPStep.set_projective)."""
+    return 595.0 / 4.0, 595.0 / 3.0, (319.5 - 65.0) / 4.0, (239.5 - 49.0) / 3.0
+
+
+def _projective_args(grid_width, fx, fy, cx, cy, radius):
+    """The arguments of icp_set_projective / icp_batch_set_projective behind the handle (grid_width None or 0: off)."""
+    if not grid_width:
+        return 0, 0, 1.0, 1.0, 0.0, 0.0, 0
+    return 1, int(grid_width), float(fx), float(fy), float(cx), float(cy), int(radius)
 
 
 class ICPStep:
@@ -789,6 +811,22 @@ class ICPStep:
         on, c = C.c_int32(), C.c_float()
         self._chk(self._L.icp_get_normal_rejection(self._h, C.byref(on), C.byref(c)))
         return c.value if on.value else None
+
+    def set_projective(self, grid_width=None, fx=1.0, fy=1.0, cx=0.0, cy=0.0, radius=0):
+        """Projective data association (icp_set_projective; not reference behaviour, off by default): instead of searching the RBC, every
+        moving point is transformed, projected through the pinhole model (fx, fy, cx, cy in grid units: grid_intrinsics,
+        landmark_intrinsics) onto F read as a row-major grid `grid_width` wide, and paired with the closest valid fixed point of the
+        (2 radius + 1)^2 window around its cell; a point that lands outside the grid or on an empty window is a rejected pair.
+        radius in [0, 8]; point-to-point needs radius >= 1.  grid_width None or 0: off.  read(Memory.PROJECTIVE) gives the last
+        iteration's (n, hits, outside, empty)."""
+        self._chk(self._L.icp_set_projective(self._h, *_projective_args(grid_width, fx, fy, cx, cy, radius)))
+
+    def projective(self):
+        """(grid_width, fx, fy, cx, cy, radius) of projective data association, None while it is off."""
+        on, gw, r = C.c_int32(), C.c_uint32(), C.c_uint32()
+        f = [C.c_float() for _ in range(4)]
+        self._chk(self._L.icp_get_projective(self._h, C.byref(on), C.byref(gw), *[C.byref(x) for x in f], C.byref(r)))
+        return (gw.value, f[0].value, f[1].value, f[2].value, f[3].value, r.value) if on.value else None
 
     def set_boundary_rejection(self, grid_width=None):
         """Rejection at the fixed grid's boundary (icp_set_boundary_rejection; not reference behaviour, off by default): F is read as
@@ -1270,6 +1308,16 @@ class ICPBatch:
         """The cosine threshold as last set on this batch (None: off)."""
         return getattr(self, "_normal_rejection", None)
 
+    def set_projective(self, grid_width=None, fx=1.0, fy=1.0, cx=0.0, cy=0.0, radius=0):
+        """ICPStep.set_projective on every registration (icp_batch_set_projective)."""
+        args = _projective_args(grid_width, fx, fy, cx, cy, radius)
+        self._chk(self._L.icp_batch_set_projective(self._b, *args))
+        self._projective = tuple(args[1:2]) + tuple(float(np.float32(x)) for x in args[2:6]) + (args[6],) if args[0] else None
+
+    def projective(self):
+        """(grid_width, fx, fy, cx, cy, radius) as last set on this batch (None: off)."""
+        return getattr(self, "_projective", None)
+
     def set_boundary_rejection(self, grid_width=None):
         """ICPStep.set_boundary_rejection on every registration (icp_batch_set_boundary_rejection)."""
         self._chk(self._L.icp_batch_set_boundary_rejection(self._b, int(grid_width or 0)))
@@ -1356,7 +1404,7 @@ class ICPBatch:
         dt, cols = _MEM_DTYPE[mem]
         sizes = {Memory.T: 32, Memory.TK: 32, Memory.MEANS: 32, Memory.S: 44, Memory.NN_ID: self.m * 8, Memory.R: 36, Memory.RK: 36,
                  Memory.F: self.m * 32, Memory.M: self.m * 32, Memory.W: self.m * 4, Memory.RID: self.m * 4, Memory.TRIM: 16, Memory.UNIQUE: 8, Memory.PAIR_FILTER: 16,
-                 Memory.RECIPROCAL: 16, Memory.REVERSE_ID: self.m * 8,
+                 Memory.RECIPROCAL: 16, Memory.REVERSE_ID: self.m * 8, Memory.PROJECTIVE: 16,
                  Memory.NN: self.m * 16, Memory.QT: self.m * 16, Memory.NORMALS_F: self.m * 16, Memory.PLANE_SYSTEM: 28 * 8,
                  Memory.COLOR_GRAD_F: self.m * 16, Memory.NORMALS_M: self.m * 16}
         nbytes = sizes[mem]

@@ -77,8 +77,8 @@ uint32_t moving_normals_word (const icp_options &o)    // plane-to-plane and sym
 constexpr int reject_user_flags = ICP_REJECT_INVALID;    // the bits of `reject` that icp_set_rejection takes from the caller as they are
 void derive_params (const icp_options &o, icp_params &p)
 {
-    constexpr uint64_t sum = (uint64_t) ICP_REJECT_INVALID + ICP_REJECT_DIST_ON + ICP_REJECT_TRIM_ON + ICP_REJECT_ROBUST_MASK + ICP_REJECT_UNIQUE_ON + ICP_REJECT_FILTER_MASK + ICP_REJECT_RECIPROCAL_ON;
-    static_assert (sum == (ICP_REJECT_INVALID | ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON | ICP_REJECT_FILTER_MASK | ICP_REJECT_RECIPROCAL_ON),
+    constexpr uint64_t sum = (uint64_t) ICP_REJECT_INVALID + ICP_REJECT_DIST_ON + ICP_REJECT_TRIM_ON + ICP_REJECT_ROBUST_MASK + ICP_REJECT_UNIQUE_ON + ICP_REJECT_FILTER_MASK + ICP_REJECT_RECIPROCAL_ON + ICP_REJECT_PROJECTIVE_ON;
+    static_assert (sum == (ICP_REJECT_INVALID | ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON | ICP_REJECT_FILTER_MASK | ICP_REJECT_RECIPROCAL_ON | ICP_REJECT_PROJECTIVE_ON),
                    "every rule's bits in icp_params::reject are its own");
     static_assert (ICP_REJECT_INVALID == 1, "ks_epilogue tests bit 0");
     static_assert (ICP_ROBUST_TUKEY << ICP_REJECT_ROBUST_SHIFT == ICP_REJECT_ROBUST_MASK, "the loss's kind fills the mask's two bits");
@@ -89,7 +89,7 @@ void derive_params (const icp_options &o, icp_params &p)
     p.reject = (uint32_t) o.reject_flags | (dist ? ICP_REJECT_DIST_ON : 0u) | (trim ? ICP_REJECT_TRIM_ON : 0u)
              | ((uint32_t) o.robust << ICP_REJECT_ROBUST_SHIFT) | (o.unique ? ICP_REJECT_UNIQUE_ON : 0u)
              | (o.boundary_gw ? ICP_REJECT_BOUNDARY_ON : 0u) | (o.normal_on ? ICP_REJECT_NORMAL_ON : 0u)
-             | (o.reciprocal ? ICP_REJECT_RECIPROCAL_ON : 0u);
+             | (o.reciprocal ? ICP_REJECT_RECIPROCAL_ON : 0u) | (o.projective ? ICP_REJECT_PROJECTIVE_ON : 0u);
     p.reject_max_dist = o.reject_max_dist;
     p.reject_d2 = dist ? (float) ((double) o.reject_max_dist * (double) o.reject_max_dist) : 0.f;     // (the product of two floats is exact in double)
     p.trim_keep = trim ? o.trim_keep : 0.f;
@@ -100,12 +100,12 @@ void derive_params (const icp_options &o, icp_params &p)
 
 // The settings the kernels read from device words instead of captured arguments (a new value touches no graph): which value of the
 // record goes where.  write_words writes the chosen ones (OPT_WORDS: all) in stream order behind whatever the handle's stream holds.
-enum : unsigned { OPT_W_KAPPA = 1u, OPT_W_ROBUST = 2u, OPT_W_EPS = 4u, OPT_W_MIN_COS = 8u, OPT_W_GRID = 16u, OPT_W_GAP = 32u, OPT_WORDS = 63u };
+enum : unsigned { OPT_W_KAPPA = 1u, OPT_W_ROBUST = 2u, OPT_W_EPS = 4u, OPT_W_MIN_COS = 8u, OPT_W_GRID = 16u, OPT_W_GAP = 32u, OPT_W_PROJ = 64u, OPT_WORDS = 127u };
 int write_words (icp_context *h, unsigned which)
 {
     const icp_options &o = h->opt;
     auto bits = [] (float f) { uint32_t u; std::memcpy (&u, &f, sizeof u); return u; };
-    uint32_t *const filter = icp_pair_filter_settings (h->p);
+    uint32_t *const filter = icp_pair_filter_settings (h->p), *const proj = icp_projective_settings (h->p);
     const struct { unsigned flag; uint32_t value; void *word; } words[] = {
         { OPT_W_KAPPA, bits (o.color_kappa), icp_color_kappa (h->p) },
         { OPT_W_ROBUST, bits (o.robust_scale), icp_robust_scale (h->p) },
@@ -113,6 +113,8 @@ int write_words (icp_context *h, unsigned which)
         { OPT_W_MIN_COS, bits (o.normal_min_cos), filter },
         { OPT_W_GRID, o.boundary_gw, filter + 1 },
         { OPT_W_GAP, bits (o.reciprocal_gap), icp_reciprocal_gap (h->p) },
+        { OPT_W_PROJ, o.proj_gw, proj }, { OPT_W_PROJ, bits (o.proj_fx), proj + 1 }, { OPT_W_PROJ, bits (o.proj_fy), proj + 2 },
+        { OPT_W_PROJ, bits (o.proj_cx), proj + 3 }, { OPT_W_PROJ, bits (o.proj_cy), proj + 4 }, { OPT_W_PROJ, o.proj_radius, proj + 5 },
     };
     for (const auto &w : words)
         if (which & w.flag) HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (w.word), (int) w.value, 1, h->stream));
@@ -123,12 +125,12 @@ int write_words (icp_context *h, unsigned which)
 // changed (OPT_W_*), and whether the change is a parameter update (OPT_PARAMS: cached graphs are updated in place when next used), a
 // change of route (OPT_ROUTE: other kernels run, graphs are captured anew), or neither.  What follows from the parameters is found
 // by comparing them, old against new: the result area of a feature that went off is cleared (ICP_MEM_TRIM, ICP_MEM_UNIQUE,
-// ICP_MEM_PAIR_FILTER, ICP_MEM_RECIPROCAL, ICP_MEM_PLANE_SYSTEM read zeros while it is off), the moving set of reciprocal correspondences
+// ICP_MEM_PAIR_FILTER, ICP_MEM_RECIPROCAL, ICP_MEM_PROJECTIVE, ICP_MEM_PLANE_SYSTEM read zeros while it is off), the moving set of reciprocal correspondences
 // is stale when the rule comes on (M may have been written while it was off), and with grid normals a handle that now needs something its
 // last buildRBC did not compute — the moving normals, the intensity gradients — needs a new buildRBC, as after a new F.
 // Device work in a fixed order: the open runs end, words, clears, then the stream is drained, so that work later enqueued on any of
 // the handle's streams sees them.  OPT_QUIESCE: the open runs end although nothing is written.
-enum : unsigned { OPT_PARAMS = 64u, OPT_ROUTE = 128u, OPT_QUIESCE = 256u };
+enum : unsigned { OPT_PARAMS = 128u, OPT_ROUTE = 256u, OPT_QUIESCE = 512u };
 int commit (icp_context *h, unsigned what)
 {
     const icp_params was = h->p;
@@ -137,8 +139,8 @@ int commit (icp_context *h, unsigned what)
     if (p.nrm_grid && ((icp_moving_normals (p) && !icp_moving_normals (was)) || (icp_colored (p) && !icp_colored (was)))) h->built = false;
     const bool off[] = { icp_trimming (was) && !icp_trimming (p), icp_unique (was) && !icp_unique (p),
                          icp_pair_filter (was) && !icp_pair_filter (p), icp_p2pl (was) && !icp_p2pl (p),
-                         icp_reciprocal (was) && !icp_reciprocal (p) };
-    const bool clears = off[0] || off[1] || off[2] || off[3] || off[4];
+                         icp_reciprocal (was) && !icp_reciprocal (p), icp_projective (was) && !icp_projective (p) };
+    const bool clears = off[0] || off[1] || off[2] || off[3] || off[4] || off[5];
     if (icp_reciprocal (p) && !icp_reciprocal (was)) h->recip.stale = true;
     if (h->inited && ((what & (OPT_WORDS | OPT_QUIESCE)) || clears)) {
         int rc = set_device (h); if (rc) return rc;
@@ -147,9 +149,9 @@ int commit (icp_context *h, unsigned what)
         const struct { void *area; size_t bytes; } areas[] = {
             { icp_trim_area (p), sizeof (uint32_t) * 4u }, { icp_unique_area (p), sizeof (uint32_t) * 2u },
             { icp_pair_filter_area (p), sizeof (uint32_t) * 4u }, { icp_p2pl_area (p), sizeof (double) * ICP_P2PL_SYS },
-            { icp_reciprocal_area (p), sizeof (uint32_t) * 4u },
+            { icp_reciprocal_area (p), sizeof (uint32_t) * 4u }, { icp_projective_area (p), sizeof (uint32_t) * 4u },
         };
-        for (int i = 0; i < 5; ++i) if (off[i]) HIPCHK (h, hipMemsetAsync (areas[i].area, 0, areas[i].bytes * p.batch, h->stream));
+        for (int i = 0; i < 6; ++i) if (off[i]) HIPCHK (h, hipMemsetAsync (areas[i].area, 0, areas[i].bytes * p.batch, h->stream));
         if ((what & OPT_WORDS) || clears) HIPCHK (h, hipStreamSynchronize (h->stream));
     }
     if (what & OPT_ROUTE) drop_graphs (h);
@@ -457,6 +459,7 @@ static mem_desc mem_of (const icp_context *h, uint32_t b, int mem)
         case ICP_MEM_UNIQUE: return { icp_unique_area (p) + 2u * b, 8, nullptr };
         case ICP_MEM_PAIR_FILTER: return { icp_pair_filter_area (p) + 4u * b, 16, nullptr };
         case ICP_MEM_RECIPROCAL: return { icp_reciprocal_area (p) + 4u * b, 16, nullptr };
+        case ICP_MEM_PROJECTIVE: return { icp_projective_area (p) + 4u * b, 16, nullptr };
         case ICP_MEM_REVERSE_ID: return { h->recip.nn_id ? h->recip.nn_id + b * m : nullptr, m * 8, nullptr };   // (allocated with the rule's first use)
         case ICP_MEM_NORMALS_F: return { icp_normals_f (p) + b * m, m * 16, "ICP_MEM_NORMALS_F" };
         case ICP_MEM_COLOR_GRAD_F: return { icp_color_grad_f (p) + b * m, m * 16, "ICP_MEM_COLOR_GRAD_F" };
@@ -583,6 +586,8 @@ int icp_build_rbc (icp_handle h) try
         return fail (h, ICP_ESTATE, "icp_build_rbc: ICP_NORMALS_GRID: m is not a multiple of the grid width");
     if (h->opt.boundary_gw && h->p.m % h->opt.boundary_gw)
         return fail (h, ICP_ESTATE, "icp_build_rbc: icp_set_boundary_rejection: m is not a multiple of the grid width");
+    if (h->opt.projective && h->p.m % h->opt.proj_gw)
+        return fail (h, ICP_ESTATE, "icp_build_rbc: icp_set_projective: m is not a multiple of the grid width");
     note_inputs_change (h);
     note_enqueue (h);
     icp_launch_build_rbc (h->p, h->stream);          // (plain launches: docs/HISTORY.md has the comparison with a cached graph)
@@ -839,6 +844,43 @@ int icp_get_reciprocal (icp_handle h, int *on, float *max_gap) try
     if (!h) return ICP_EINVAL;
     if (on) *on = h->opt.reciprocal ? 1 : 0;
     if (max_gap) *max_gap = h->opt.reciprocal_gap;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+// projective data association (icp_projective.hip).  On <-> off changes which kernels run — k_projective in place of the search, on
+// point-to-point the apply pass, no chained form —: a change of route.  New intrinsics, a new width or a new radius while the rule stays
+// on go to their device words alone: no graph is touched.
+int icp_set_projective (icp_handle h, int on, uint32_t grid_width, float fx, float fy, float cx, float cy, uint32_t radius) try
+{
+    api_guard guard_ (h);
+    if (on != 0 && on != 1) return fail (h, ICP_EINVAL, "icp_set_projective: on must be 0 or 1");
+    if (on && grid_width == 0u) return fail (h, ICP_EINVAL, "icp_set_projective: grid_width must be > 0");
+    if (!(fx > 0.f && std::isfinite (fx) && fy > 0.f && std::isfinite (fy))) return fail (h, ICP_EINVAL, "icp_set_projective: fx and fy must be finite and > 0");
+    if (!(std::isfinite (cx) && std::isfinite (cy))) return fail (h, ICP_EINVAL, "icp_set_projective: cx and cy must be finite");
+    if (radius > 8u) return fail (h, ICP_EINVAL, "icp_set_projective: radius must be in [0, 8]");
+    if (!h) return fail (h, ICP_EINVAL, "icp_set_projective: null handle");
+    if (on && h->inited && h->p.m % grid_width) return fail (h, ICP_ESTATE, "icp_set_projective: m is not a multiple of the grid width");
+    { int rc = outputs_before_change (h); if (rc) return rc; }
+    icp_options &o = h->opt;
+    const bool was = o.projective;
+    o.projective = on != 0;
+    o.proj_gw = on ? grid_width : 0u; o.proj_radius = on ? radius : 0u;
+    o.proj_fx = on ? fx : 0.f; o.proj_fy = on ? fy : 0.f; o.proj_cx = on ? cx : 0.f; o.proj_cy = on ? cy : 0.f;
+    return commit (h, o.projective != was ? OPT_ROUTE | OPT_W_PROJ : on ? OPT_W_PROJ : 0u);
+}
+ICP_CATCH_ALL
+int icp_get_projective (icp_handle h, int *on, uint32_t *grid_width, float *fx, float *fy, float *cx, float *cy, uint32_t *radius) try
+{
+    api_guard guard_ (h);
+    if (!h) return ICP_EINVAL;
+    const icp_options &o = h->opt;
+    if (on) *on = o.projective ? 1 : 0;
+    if (grid_width) *grid_width = o.proj_gw;
+    if (fx) *fx = o.proj_fx;
+    if (fy) *fy = o.proj_fy;
+    if (cx) *cx = o.proj_cx;
+    if (cy) *cy = o.proj_cy;
+    if (radius) *radius = o.proj_radius;
     return ICP_OK;
 }
 ICP_CATCH_ALL

@@ -130,6 +130,7 @@ struct icp_params {
 #define ICP_REJECT_NORMAL_ON 0x02000000u   // icp_params::reject: rejection by normal compatibility is on (icp_set_normal_rejection: likewise; the moving frame's normals are needed)
 #define ICP_REJECT_FILTER_MASK (ICP_REJECT_BOUNDARY_ON | ICP_REJECT_NORMAL_ON)
 #define ICP_REJECT_RECIPROCAL_ON 0x01000000u   // icp_params::reject: reciprocal correspondences are on (icp_set_reciprocal: the REJ kernels, plus the back search and k_reciprocal: icp_launch_reciprocal)
+#define ICP_REJECT_PROJECTIVE_ON 0x00800000u   // icp_params::reject: projective data association is on (icp_set_projective: k_projective in place of the search: icp_launch_projective)
 static_assert (sizeof (icp_params) == 480, "icp_params grew: the hidden kernel arguments of every kernel would move");
 
 // rejection on: the sum-W formulas in every mode, and a step of nothing accepted (sum W == 0) is the identity
@@ -141,6 +142,8 @@ static __host__ __device__ __forceinline__ bool icp_unique (const icp_params &p)
 static __host__ __device__ __forceinline__ bool icp_pair_filter (const icp_params &p) { return (p.reject & ICP_REJECT_FILTER_MASK) != 0u; }
 // reciprocal correspondences (icp_reciprocal.hip): a candidate keeps its weight only if its fixed point's back search into M finds it again
 static __host__ __device__ __forceinline__ bool icp_reciprocal (const icp_params &p) { return (p.reject & ICP_REJECT_RECIPROCAL_ON) != 0u; }
+// projective data association (icp_projective.hip): the pairs come from a projection onto the fixed grid instead of the RBC search
+static __host__ __device__ __forceinline__ bool icp_projective (const icp_params &p) { return (p.reject & ICP_REJECT_PROJECTIVE_ON) != 0u; }
 // the moving frame's normals are needed: by a metric (p.gicp: plane-to-plane, symmetric) or by normal rejection, whatever the metric
 static __host__ __device__ __forceinline__ bool icp_moving_normals (const icp_params &p) { return p.gicp != 0u || (p.reject & ICP_REJECT_NORMAL_ON) != 0u; }
 // the robust loss's kind (ICP_ROBUST_HUBER 1, CAUCHY 2, TUKEY 3; 0: off).  Its scale k is a device word (icp_robust_scale).
@@ -197,6 +200,8 @@ struct icp_mom_layout {
     size_t filt;                 // the pair filter's uint32 words (icp_pair_filter_area): [batch][4] ICP_MEM_PAIR_FILTER, [batch][8] the blocks' running
                                  // counts and their arrival counter, then min_cos (float) and the boundary rule's grid width
     size_t recip;                // reciprocal correspondences' uint32 words (icp_reciprocal_area): [batch][4] ICP_MEM_RECIPROCAL, then max_gap (float)
+    size_t proj;                 // projective data association's uint32 words (icp_projective_area): [batch][4] ICP_MEM_PROJECTIVE, [batch][8] the blocks'
+                                 // running counts and their ticket counter, then the six settings (grid width, fx, fy, cx, cy: float bits, radius)
     size_t total;
 };
 static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (uint32_t batch, uint32_t m, uint32_t nb)
@@ -212,7 +217,8 @@ static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (uint32_t bat
     l.uniq = l.gicp + 1u;
     l.filt = l.uniq + B + B * m;
     l.recip = l.filt + 6u * B + 1u;
-    l.total = l.recip + 2u * B + 1u;
+    l.proj = l.recip + 2u * B + 1u;
+    l.total = l.proj + 6u * B + 3u;
     return l;
 }
 static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (const icp_params &p) { return icp_mom_layout_of (p.batch, p.m, p.nb); }
@@ -240,6 +246,12 @@ static inline uint32_t *icp_pair_filter_settings (const icp_params &p) { return 
 // of capturing it: max_gap (float; the kernel squares it in double).
 static inline uint32_t *icp_reciprocal_area (const icp_params &p) { return reinterpret_cast<uint32_t *> (p.mom + icp_mom_layout_of (p).recip); }
 static inline uint32_t *icp_reciprocal_gap (const icp_params &p) { return icp_reciprocal_area (p) + 4u * (size_t) p.batch; }
+// Projective data association (icp_projective.hip), uint32 words: [batch][4] the result of the last iteration (n, hits, outside, empty:
+// ICP_MEM_PROJECTIVE); [batch][8] the running counts of an iteration's blocks and their ticket counter, zero between launches; then the
+// settings the kernel reads instead of capturing them: grid width, fx, fy, cx, cy (float bits), radius.
+static inline uint32_t *icp_projective_area (const icp_params &p) { return reinterpret_cast<uint32_t *> (p.mom + icp_mom_layout_of (p).proj); }
+static inline uint32_t *icp_projective_counts (const icp_params &p) { return icp_projective_area (p) + 4u * (size_t) p.batch; }
+static inline uint32_t *icp_projective_settings (const icp_params &p) { return icp_projective_area (p) + 12u * (size_t) p.batch; }
 
 // The XP allocation of one RBC set, offsets in floats: [batch][m][8] the permuted database, then [batch][m] float4 NORMALS_F and
 // [batch][m] float4 COLOR_GRAD_F ([gx gy gz C] per fixed point).  The normals and gradients belong to the fixed frame as the RBC does,
@@ -334,6 +346,7 @@ struct icp_route {
                                  // diagnostics that time an iteration stage by stage enqueue (icp_launch_masked)
     bool stored;                 // the search stores its per-query outputs every iteration: a pass or the plane moments read them
     bool ref_search;             // the search in its reference-order form whatever p.fused (the plane metrics)
+    bool projective;             // k_projective in place of the search (icp_launch_projective): the pairs by projection onto the fixed grid
     bool filter;                 // k_pair_filter
     bool reciprocal;             // k_reciprocal_state + the back search + k_reciprocal (icp_launch_reciprocal)
     bool unique;                 // k_unique_claim + k_unique_resolve
@@ -369,6 +382,7 @@ void icp_launch_trim_apply (const icp_params &p, hipStream_t s);             // 
 void icp_launch_unique (const icp_params &p, hipStream_t s);                 // icp_unique.hip: k_unique_claim + k_unique_resolve
 void icp_launch_reciprocal (const icp_params &p, hipStream_t s, const icp_reciprocal_set *rs);   // icp_reciprocal.hip: k_reciprocal_state + the back search + k_reciprocal
 void icp_launch_reciprocal_build (const icp_params &p, hipStream_t s, const icp_reciprocal_set &rs);   // icp_reciprocal.hip: buildRBC over M into the moving set
+void icp_launch_projective (const icp_params &p, hipStream_t s);             // icp_projective.hip: k_projective, in place of the search (icp_set_projective)
 void icp_launch_pair_filter (const icp_params &p, hipStream_t s);            // icp_pair_filter.hip: k_pair_filter (boundary and / or normal rejection), behind the search
 void icp_launch_robust_apply (const icp_params &p, hipStream_t s);            // icp_robust.hip: k_trim_apply_robust<fused?> (a point-to-point robust loss)
 void icp_launch_plane_moments_robust (const icp_params &p, hipStream_t s, double *part, uint32_t nblk);   // icp_robust.hip: k_plane_moments_robust<colored?>

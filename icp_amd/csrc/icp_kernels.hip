@@ -548,6 +548,9 @@ void icp_launch_search (const icp_params &p, hipStream_t s)
 //     and carry the loss, in their moments: no pass for them unless trimming is on.
 //   - Reciprocal correspondences (icp_reciprocal.hip): the state kernel, the back search and k_reciprocal, three launches; point-to-point:
 //     an apply pass too, as for one-to-one.
+//   - Projective data association (icp_projective.hip): k_projective in place of the search, same count.  It writes the per-query outputs
+//     and no block partials: point-to-point takes the apply pass for them (one launch more unless another rule runs it anyway), the
+//     plane metrics read the outputs in their moments (nothing more).
 //   - The order: k_pair_filter first (a pair it rejects claims no fixed point), then the reciprocal rule (its candidates are the pairs
 //     the filter leaves), claim and resolve in front of trimming's selection (its candidates are the winners), the apply pass last.
 //   - Whatever reads the per-query outputs between the search and the tail — a pass, the plane moments — has them stored every
@@ -564,11 +567,12 @@ icp_route icp_route_of (const icp_params &p)
     const bool plane = icp_p2pl (p), p2p_loss = !plane && icp_robust (p) != 0u;
     icp_route r {};
     r.launches = 1u;                                                              // the search
+    r.projective = icp_projective (p);
     r.filter = icp_pair_filter (p);                                               r.launches += r.filter ? 1u : 0u;
     r.reciprocal = icp_reciprocal (p);                                            r.launches += r.reciprocal ? 3u : 0u;
     r.unique = icp_unique (p);                                                    r.launches += r.unique ? 2u : 0u;
     r.select = !icp_trimming (p) ? 0u : p.m <= ICP_TRIM_ONE_BLOCK_MAX ? 1u : 3u;  r.launches += r.select;
-    const bool pass = r.select || p2p_loss || (!plane && (r.filter || r.reciprocal || r.unique));
+    const bool pass = r.select || p2p_loss || (!plane && (r.filter || r.reciprocal || r.unique || r.projective));
     r.apply = !pass ? ICP_APPLY_NONE : p2p_loss ? ICP_APPLY_ROBUST : ICP_APPLY_PLAIN;   r.launches += pass ? 1u : 0u;
     const bool level1 = (p.nb + 127u) / 128u > ICP_L1_MIN_GROUPS && p.ml1;        // (as k_finalize_fused decides where its first level comes from)
     r.tail = plane ? ICP_TAIL_PLANE : !p.fused ? ICP_TAIL_REFERENCE : level1 ? ICP_TAIL_FUSED_L1 : ICP_TAIL_FUSED;
@@ -624,7 +628,7 @@ static void launch_search_stage (const icp_params &p, hipStream_t s, const icp_r
     icp_params q = p;
     q.emit = 1;
     if (r.ref_search) q.fused = 0;
-    icp_launch_search (q, s);
+    if (r.projective) icp_launch_projective (q, s); else icp_launch_search (q, s);
     if (r.filter) icp_launch_pair_filter (q, s);
     if (r.reciprocal) icp_launch_reciprocal (q, s, rs);
     if (r.unique) icp_launch_unique (q, s);

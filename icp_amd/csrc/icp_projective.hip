@@ -1,0 +1,161 @@
+// icp_projective.hip — projective data association (icp_set_projective, include/icp_amd.h): a second way to FIND the pairs.  The fixed set is
+// read as a row-major grid gw wide; a moving point is transformed, projected through the fixed frame's pinhole model (fx, fy, cx, cy, in
+// grid units) onto that grid, and paired with the closest valid fixed point of the (2 r + 1)^2 window around the cell it lands on.  O (1)
+// per query, no search structure: k_projective stands where the RBC search stands in a route (icp_route::projective, icp_kernels.hip) and
+// every pass behind the search and every tail stay what they are.
+//
+// The rule per query i, T = p.st[b].T (only the tail of an iteration changes it):
+//   e = icp_transform_point (T, M[i].xyz); QT[i] = (e, d) for every i < m, d = +inf for a miss.
+//   The query counts iff M[i].xyz is finite and not (0, 0, 0) (icp_pair_counted).
+//   In double from the float inputs, every expression in the order written (the translation unit is built with -ffp-contract=off):
+//       u = (double) fx * ((double) e.x / (double) e.z) + (double) cx,  v likewise with fy, e.y, cy;  pu = floor (u + 0.5), pv = floor (v + 0.5).
+//   Inside iff it counts, e is finite, e.z > 0, 0 <= pu <= gw - 1 and 0 <= pv <= rows - 1, compared in double (a NaN fails).
+//   Candidates: the window's cells j = y gw + x (columns max (0, pu - r) .. min (gw - 1, pu + r), rows likewise) whose F[j].xyz is finite
+//   and not (0, 0, 0); d_j = icp_metric8 (e, M[i].rgb; F[j].xyz, F[j].rgb; alpha).  The winner is the minimum of the key
+//   ((uint64) bits (d_j) << 32) | j over the candidates with d_j < +inf: the smallest distance, a tie to the smallest j.  A minimum of
+//   distinct keys: it does not depend on how the lanes share the window.
+//   Hit: d = dist_scale d_j, NN_ID[i] = {d, j}, NN[i] = (F[j].xyz, w), w = weighted ? 100 / (100 + d) : 1 — and +0 where
+//   icp_set_rejection's distance test rejects the pair, which keeps its record as behind the RBC search.
+//   Miss (not counting, not inside, no winner): NN_ID[i] = {+inf, 0xFFFFFFFF}, NN[i] = (0, 0, 0, +0): exactly a rejected pair.
+// The kernel writes the per-query outputs and the count words and nothing else: the block partials (moments, or the weight partials of the
+// reference-order reductions) come from the apply pass behind it (icp_trim_apply.h), the plane metrics read the outputs in their moments.
+// ICP_MEM_RID is left as it is: a later RBC search seeds its pruning from it, any content is a valid seed (pruning is exact).
+//
+// The obligations of a separate-form search (icp_search.h, the prologue of k_search): block 0 publishes the progress word of a host-driven
+// checked run — not for a converged registration in fused mode, whose finalize has published DONE | FINAL itself —, a converged
+// registration of a checked run is left alone, batched registrations are indexed by blockIdx.y.
+//
+// Layout: one thread per query, whatever the radius (it is a device word: a new radius touches no graph, so no launch decision may depend
+// on it).  The thread walks its window in row-major order; at every step the lanes of a wave — neighbouring queries, which project to
+// neighbouring cells — read neighbouring 32-byte records of F, so a wave's loads are as contiguous with the window walked by one lane as
+// with the window spread over a lane group, and the gather lives in L2.  float4 loads of M and of the two halves of F[j].
+//
+// Counting (ICP_MEM_PROJECTIVE: n, hits, outside, empty; hits + outside + empty == n) follows the pair filter's scheme, because this
+// kernel has no launch in front of it that could reset the words: the blocks of a registration add their integer counts to running
+// words and take a ticket; the block that draws the last one moves the sums into the result words and leaves the running words and the
+// ticket zero for the next launch.  A block of 256 threads serves 1024 queries in four rounds at the sizes where the number of tickets
+// matters (a ticket's release writes its XCD's L2 back: icp_reciprocal.hip has the measurement), 256 where the grid would otherwise not
+// fill the chip.  (Measured at 2^20 points: blocks of 1024 threads and one round instead — the same number of tickets — take 188 instead
+// of 90 us per point-to-point iteration at r = 0.)  Integer sums: nothing depends on the order of arrival.
+#include "icp_search.h"                 // (icp_mirror_store)
+#include "icp_pair_rule.h"
+
+namespace {
+
+constexpr uint32_t PROJ_BLOCK = 256u;
+constexpr uint32_t PROJ_NONE = 0xFFFFFFFFu;
+
+__device__ __forceinline__ bool proj_valid (const float4 &g)
+{
+    return isfinite (g.x) && isfinite (g.y) && isfinite (g.z) && !(g.x == 0.f && g.y == 0.f && g.z == 0.f);
+}
+
+// ------------------------------------------------------------------------------------------
+// k_projective — one thread per query, 256 queries per round, `rounds` rounds per block; grid (ceil (m / (256 rounds)), batch).
+// result, counts, settings: icp_projective_area / _counts / _settings (icp_kernels.h); settings = (gw, fx, fy, cx, cy, r)
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__ (PROJ_BLOCK) void k_projective (icp_params p, uint32_t rounds, uint32_t *result, uint32_t *counts, const uint32_t *settings)
+{
+    __shared__ uint32_t s_cnt[PROJ_BLOCK / 64u][3];
+    const uint32_t b = blockIdx.y, t = threadIdx.x, m = p.m;
+    const icp_reg_state *st = p.st + b;
+    const uint32_t done = st->done;
+    if (p.hmirror && blockIdx.x == 0u && t == 0u && !(p.fused && done)) icp_mirror_store (p.hmirror + b, ICP_MIRROR_WORD (p.epoch, st->k, done));
+    if (p.check && done) return;                             // (a converged registration: its last iteration's outputs and counts stay)
+    float T[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) T[k] = st->T[k];
+    uint32_t gw = settings[0];
+    const double fx = (double) __uint_as_float (settings[1]), fy = (double) __uint_as_float (settings[2]);
+    const double cx = (double) __uint_as_float (settings[3]), cy = (double) __uint_as_float (settings[4]);
+    const uint32_t r = min (settings[5], 8u);
+    // (the host refuses a width that does not divide m; whatever the words hold, every index below stays inside the registration's m rows:
+    // a width of 0 or beyond m makes every query a miss, and rows gw <= m)
+    if (gw > m) gw = 0u;
+    const uint32_t rows = gw ? m / gw : 0u;
+    const size_t o = (size_t) b * m;
+    const float4 *F4 = reinterpret_cast<const float4 *> (p.F) + o * 2u, *M4 = reinterpret_cast<const float4 *> (p.M) + o * 2u;
+    uint32_t cn = 0u, ch = 0u, co = 0u;                      // this wave's counts over the rounds
+    for (uint32_t rd = 0; rd < rounds; ++rd) {
+        const uint32_t i = (blockIdx.x * rounds + rd) * PROJ_BLOCK + t;
+        const bool v = i < m;
+        float4 mg = make_float4 (0.f, 0.f, 0.f, 0.f), mc = mg;
+        if (v) { mg = M4[2u * (size_t) i]; mc = M4[2u * (size_t) i + 1u]; }
+        const bool counts_ = icp_pair_counted (v, mg);
+        float ex, ey, ez;
+        icp_transform_point (T, mg.x, mg.y, mg.z, ex, ey, ez);
+        const double u = fx * ((double) ex / (double) ez) + cx, w_ = fy * ((double) ey / (double) ez) + cy;
+        const double pu = floor (u + 0.5), pv = floor (w_ + 0.5);
+        const bool inside = counts_ && gw != 0u && isfinite (ex) && isfinite (ey) && isfinite (ez) && (double) ez > 0.0
+                            && pu >= 0.0 && pu <= (double) (gw - 1u) && pv >= 0.0 && pv <= (double) (rows - 1u);
+        unsigned long long key = ~0ull;
+        if (inside) {
+            // (0 <= pu <= gw - 1 and 0 <= pv <= rows - 1: the conversions are exact, and every cell (x, y) below has y gw + x < rows gw <= m)
+            const uint32_t ux = (uint32_t) pu, uy = (uint32_t) pv;
+            const uint32_t x0 = ux >= r ? ux - r : 0u, x1 = min (gw - 1u, ux + r), y0 = uy >= r ? uy - r : 0u, y1 = min (rows - 1u, uy + r);
+            for (uint32_t y = y0; y <= y1; ++y)
+                for (uint32_t x = x0; x <= x1; ++x) {
+                    const uint32_t j = y * gw + x;
+                    const float4 fg = F4[2u * (size_t) j], fc = F4[2u * (size_t) j + 1u];
+                    const float d = icp_metric8 (ex, ey, ez, mc.x, mc.y, mc.z, fg.x, fg.y, fg.z, fc.x, fc.y, fc.z, p.a);
+                    if (proj_valid (fg) && d < __builtin_inff ()) {
+                        const unsigned long long k = ((unsigned long long) __float_as_uint (d) << 32) | j;
+                        key = k < key ? k : key;
+                    }
+                }
+        }
+        const bool hit = inside && key != ~0ull;
+        if (v) {
+            icp_dist_id di; di.dist = __builtin_inff (); di.id = PROJ_NONE;
+            float4 pf = make_float4 (0.f, 0.f, 0.f, 0.f);
+            if (hit) {
+                const uint32_t j = (uint32_t) (key & 0xFFFFFFFFull);
+                const float4 fg = F4[2u * (size_t) j];       // (j < m: a cell of the window)
+                const float d = p.dist_scale * __uint_as_float ((uint32_t) (key >> 32));
+                float w = p.weighted ? 100.f / (100.f + d) : 1.f;
+                if (p.reject & ICP_REJECT_DIST_ON) {         // (icp_set_rejection's distance test, as the REJ search's epilogue applies it)
+                    const float gx = ex - fg.x, gy = ey - fg.y, gz = ez - fg.z;
+                    if (!(((gx * gx + gy * gy) + gz * gz) <= p.reject_d2)) w = 0.f;
+                }
+                di.dist = d; di.id = j;
+                pf = make_float4 (fg.x, fg.y, fg.z, w);
+            }
+            p.nn_id[o + i] = di;
+            p.PF[o + i] = pf;
+            p.PM[o + i] = make_float4 (ex, ey, ez, di.dist);
+        }
+        cn += (uint32_t) __popcll (__ballot (counts_));
+        ch += (uint32_t) __popcll (__ballot (hit));
+        co += (uint32_t) __popcll (__ballot (counts_ && !inside));
+    }
+    if ((t & 63u) == 0u) { s_cnt[t >> 6][0] = cn; s_cnt[t >> 6][1] = ch; s_cnt[t >> 6][2] = co; }
+    __syncthreads ();
+    if (t == 0u) {
+        uint32_t sn = 0u, sh = 0u, so = 0u;
+        for (uint32_t k = 0; k < PROJ_BLOCK / 64u; ++k) { sn += s_cnt[k][0]; sh += s_cnt[k][1]; so += s_cnt[k][2]; }
+        uint32_t *run = counts + 8u * b;
+        if (sn) __hip_atomic_fetch_add (run + 0, sn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (sh) __hip_atomic_fetch_add (run + 1, sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (so) __hip_atomic_fetch_add (run + 2, so, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t ticket = __hip_atomic_fetch_add (run + 4, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (ticket + 1u == gridDim.x) {                      // (the last block of the registration: every count is in)
+            const uint32_t n = __hip_atomic_exchange (run + 0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t nh = __hip_atomic_exchange (run + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t no = __hip_atomic_exchange (run + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store (run + 4, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            uint32_t *out = result + 4u * b;
+            out[0] = n; out[1] = nh; out[2] = no; out[3] = n - nh - no;
+        }
+    }
+}
+
+}  // namespace
+
+void icp_launch_projective (const icp_params &p, hipStream_t s)
+{
+    // queries per block: 1024 where a registration's tickets would be many (see the header), else one round's worth
+    const uint32_t rounds = (size_t) p.batch * p.m > 65536u ? 4u : 1u, per_block = rounds * PROJ_BLOCK;
+    const dim3 grid ((p.m + per_block - 1u) / per_block, p.batch);
+    hipLaunchKernelGGL (k_projective, grid, dim3 (PROJ_BLOCK), 0, s, p, rounds, icp_projective_area (p), icp_projective_counts (p),
+                        (const uint32_t *) icp_projective_settings (p));
+}

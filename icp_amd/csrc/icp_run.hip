@@ -28,6 +28,8 @@ int need (icp_context *h, bool built, bool keep_run)
         return fail (h, ICP_ESTATE, "icp_set_symmetric does not combine with ICP_METRIC_COLORED (icp_set_error_metric): switch one of them off");
     if (built && h->opt.symmetric && h->opt.gicp_eps > 0.f && icp_p2pl (h->p))          // (point-to-point ignores both)
         return fail (h, ICP_ESTATE, "icp_set_symmetric does not combine with icp_set_plane_to_plane: switch one of them off");
+    if (built && h->opt.projective && h->opt.reciprocal)      // (the back search is an RBC search: reciprocity with a projective forward search is not defined)
+        return fail (h, ICP_ESTATE, "icp_set_projective does not combine with icp_set_reciprocal: switch one of them off");
     if (!keep_run && (h->run.active || h->run2.active || h->stream2_dirty)) {
         if (hipSetDevice (h->device) != hipSuccess) return fail (h, ICP_EHIP, "hipSetDevice");
         int rc = run_close_all (h); if (rc) return rc;

@@ -324,6 +324,8 @@ static int track_submit (icp_context *h, const void *cloud, int warm_start, bool
         return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while normal rejection is on (icp_set_normal_rejection)");
     if (h->opt.reciprocal)
         return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while reciprocal correspondences are on (icp_set_reciprocal)");
+    if (h->opt.projective)
+        return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while projective data association is on (icp_set_projective)");
     // (point-to-plane: each frame's normals come from its own landmarks, which only buildRBC can give it — ICP_NORMALS_GRID)
     if (icp_p2pl (h->p) && !h->p.nrm_grid)
         return fail (h, ICP_ESTATE, "icp_track_submit: point-to-plane tracking needs ICP_NORMALS_GRID (icp_set_normals)");

@@ -8,14 +8,14 @@ import time
 
 import numpy as np
 
-from . import ICP, ErrorMetric, ICPPyramid, Memory, Normals, Pairs, PowerMode, PyramidReduction, ReduceMode, RobustLoss
+from . import landmark_intrinsics, ICP, ErrorMetric, ICPPyramid, Memory, Normals, Pairs, PowerMode, PyramidReduction, ReduceMode, RobustLoss
 from .io import load_pc8d, save_pc8d
 
 
 def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, angle_threshold=0.001,
                     translation_threshold=0.01, reduce_mode=ReduceMode.FUSED, reject_invalid=False, max_dist=None, trim=1.0,
                     point_to_plane=None, colored=None, robust=None, plane_to_plane=None, symmetric=False, one_to_one=False,
-                    normal_angle=None, reject_boundary=False, pyramid=None, reciprocal=None):
+                    normal_angle=None, reject_boundary=False, pyramid=None, reciprocal=None, projective=None):
     """Returns (T[8], k, latency_ms, transformed moving cloud).  reject_invalid / max_dist: correspondence rejection
     (ICPStep.set_rejection), trim: the fraction of pairs trimmed ICP keeps (ICPStep.set_trimming; 1.0: off), point_to_plane: mu of
     point-to-plane ICP with the fixed frame's normals from its 128 x 128 landmark grid (ICPStep.set_error_metric; None: off),
@@ -27,7 +27,9 @@ def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, a
     between the two normals of a pair, with both frames' grid normals (ICPStep.set_normal_rejection with its cosine; None: off),
     reject_boundary: pairs whose fixed point lies at the boundary of the 128 wide landmark grid get weight 0
     (ICPStep.set_boundary_rejection), reciprocal: max_gap in mm of reciprocal correspondences — a pair keeps its weight only if its fixed
-    point finds the pair's moving point again, or one within max_gap of it (ICPStep.set_reciprocal; 0: exact only, None: off); pyramid: (levels, max_dz) of a coarse-to-fine registration (ICPPyramid: 128, 64, 32, .. wide
+    point finds the pair's moving point again, or one within max_gap of it (ICPStep.set_reciprocal; 0: exact only, None: off), projective: the window radius in [0, 8] of projective data association — the pairs
+    come from projecting the moving landmarks onto the fixed landmark grid with the frame's pinhole model (landmark_intrinsics) instead
+    of from the RBC search (ICPStep.set_projective; None: off); pyramid: (levels, max_dz) of a coarse-to-fine registration (ICPPyramid: 128, 64, 32, .. wide
     levels with 256, 64, 64, .. representatives, 2 x 2 means within a z band of max_dz mm, 0: no band; every option above applies to
     every level with the level's own grid width; k is then the list of the levels' counts, finest first; None: one level); none is
     the reference's behaviour, all are off by default."""
@@ -58,10 +60,20 @@ def pyramid_nr(levels):
     return [256] + [64] * (levels - 1)
 
 
+def level_intrinsics(intr, factor):
+    """(fx, fy, cx, cy) of a pyramid level whose cells are `factor` x `factor` means of the finest grid's (PyramidReduction.MEAN): cell i
+    of the level is centred on finest column factor i + (factor - 1) / 2, so f / factor and (c - (factor - 1) / 2) / factor."""
+    fx, fy, cx, cy = intr
+    h = (factor - 1) / 2.0
+    return fx / factor, fy / factor, (cx - h) / factor, (cy - h) / factor
+
+
 def _apply_options(reg, side, reduce_mode, reject_invalid, max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric,
-                   one_to_one, normal_angle, reject_boundary, reciprocal=None):
+                   one_to_one, normal_angle, reject_boundary, reciprocal=None, projective=None):
     """register_clouds' options on one handle whose landmark grid is `side` wide (640 x 480 clouds -> 128 x 128 landmarks, row-major;
     a pyramid level l: 128 >> l)."""
+    if projective is not None:
+        reg.set_projective(side, *level_intrinsics(landmark_intrinsics(), 128 // side), radius=projective)
     reg.setPowerMode(PowerMode.SQUARED)
     reg.setReduceMode(reduce_mode)
     if reject_invalid or max_dist:
@@ -98,18 +110,18 @@ def _apply_options(reg, side, reduce_mode, reject_invalid, max_dist, trim, point
 
 def _register(evaluate, fixed, moving, device, a, c, max_iterations, angle_threshold, translation_threshold, reduce_mode, reject_invalid,
               max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one, normal_angle, reject_boundary,
-              pyramid=None, reciprocal=None):
+              pyramid=None, reciprocal=None, projective=None):
     """(T[8], k, latency_ms, transformed moving cloud, Quality record or None): register_clouds' options; evaluate None: no evaluation."""
     return _run(False, **locals())[:5]
 
 
 def _run(pairs, evaluate, fixed, moving, device, a, c, max_iterations, angle_threshold, translation_threshold, reduce_mode, reject_invalid,
          max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one, normal_angle, reject_boundary,
-         pyramid=None, reciprocal=None):
+         pyramid=None, reciprocal=None, projective=None):
     """_register's five values and a sixth: with `pairs` the Pairs.EVALUATED correspondence set at max_dist = evaluate (None: 0, no
     distance test), else None."""
     options = (reduce_mode, reject_invalid, max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one,
-               normal_angle, reject_boundary, reciprocal)
+               normal_angle, reject_boundary, reciprocal, projective)
     if pyramid is not None:
         levels, max_dz = pyramid
         reg = ICPPyramid(device)
@@ -186,6 +198,16 @@ def _angle(s):
     return v
 
 
+def _radius(s):
+    try:
+        v = int(s)
+    except ValueError:
+        raise argparse.ArgumentTypeError("must be an integer in [0, 8], got %s" % s)
+    if not 0 <= v <= 8:
+        raise argparse.ArgumentTypeError("must be in [0, 8], got %s" % s)
+    return v
+
+
 def _robust(s):
     """KIND:SCALE, e.g. tukey:50 -> (RobustLoss kind, scale); KIND is huber, cauchy or tukey, SCALE finite and > 0."""
     kind, sep, scale = s.partition(":")
@@ -232,6 +254,10 @@ def main(argv=None):
                     help="reciprocal correspondences: a pair keeps its weight only if its fixed point, searching the moving frame, "
                          "finds the pair's moving point again, or one within GAP mm of it (default 0: exactly that point); before "
                          "--one-to-one and --trim (not reference behaviour)")
+    ap.add_argument("--projective", type=_radius, nargs="?", const=1, default=None, metavar="RADIUS",
+                    help="projective data association: pair every moving landmark with the closest fixed landmark of the "
+                         "(2 RADIUS + 1)^2 window around the cell it projects to, instead of searching (RADIUS in [0, 8], default 1; "
+                         "0 suits --point-to-plane; not reference behaviour)")
     ap.add_argument("--normal-angle", type=_angle, default=None, metavar="DEG",
                     help="give pairs whose two surface normals differ by more than DEG degrees weight 0, normals from both landmark "
                          "grids (not reference behaviour)")
@@ -269,7 +295,7 @@ def main(argv=None):
     options = dict(device=args.device, a=args.alpha, reject_invalid=args.reject_invalid, max_dist=args.max_dist, trim=args.trim,
                    point_to_plane=args.point_to_plane, colored=args.colored, robust=args.robust, plane_to_plane=args.plane_to_plane,
                    symmetric=args.symmetric, one_to_one=args.one_to_one, normal_angle=args.normal_angle,
-                   reject_boundary=args.reject_boundary, pyramid=args.pyramid, reciprocal=args.reciprocal)
+                   reject_boundary=args.reject_boundary, pyramid=args.pyramid, reciprocal=args.reciprocal, projective=args.projective)
     members = None
     if args.pairs is not None:
         T, k, ms, out, quality, members = register_with_pairs(fixed, moving, args.evaluate, **options)

@@ -632,6 +632,19 @@ namespace ICP
         void setReciprocal (bool on, float max_gap = 0.f) { check (icp_set_reciprocal (h, on ? 1 : 0, on ? max_gap : 0.f)); }
         bool getReciprocal (float *max_gap = nullptr) { int on = 0; float g = 0.f; check (icp_get_reciprocal (h, &on, &g)); if (max_gap) *max_gap = g; return on != 0; }
 
+        /*! \brief Projective data association (icp_set_projective, include/icp_amd.h; not in the reference, off by default): the pairs
+         *         come from projecting every transformed moving point through the pinhole model (fx, fy, cx, cy in grid units) onto F
+         *         read as a row-major grid grid_width wide, and taking the closest valid point of the (2 radius + 1)^2 window around
+         *         its cell, instead of from the RBC search.  Every rule behind the search and every metric stay what they are. */
+        void setProjective (bool on, uint32_t grid_width = 0, float fx = 1.f, float fy = 1.f, float cx = 0.f, float cy = 0.f, uint32_t radius = 0)
+        {
+            check (on ? icp_set_projective (h, 1, grid_width, fx, fy, cx, cy, radius) : icp_set_projective (h, 0, 0, 1.f, 1.f, 0.f, 0.f, 0));
+        }
+        bool getProjective (uint32_t *grid_width = nullptr, float *fx = nullptr, float *fy = nullptr, float *cx = nullptr, float *cy = nullptr, uint32_t *radius = nullptr)
+        {
+            int on = 0; check (icp_get_projective (h, &on, grid_width, fx, fy, cx, cy, radius)); return on != 0;
+        }
+
         /*! \brief Rejection by normal compatibility (icp_set_normal_rejection, include/icp_amd.h; not in the reference, off by
          *         default): a pair whose two normals enclose an angle with a cosine below min_cos gets weight 0.  It needs both frames'
          *         normals (setNormals) and acts before one-to-one correspondences, trimming and the robust loss. */

@@ -94,6 +94,7 @@ typedef enum {
     ICP_MEM_PAIR_FILTER = 26,  /* out uint32[4]   boundary / normal rejection, last iteration: n, at_boundary, incompatible, accepted (0 when off) */
     ICP_MEM_RECIPROCAL = 27,   /* out uint32[4]   reciprocal correspondences, last iteration: n, exact, near, accepted (0 when off) */
     ICP_MEM_REVERSE_ID = 28,   /* out m x {dist,id}  reciprocal correspondences: the back search, fixed-point order, id = index into M */
+    ICP_MEM_PROJECTIVE = 29,   /* out uint32[4]   projective data association, last iteration: n, hits, outside, empty (0 when off) */
     ICP_MEM_COUNT_
 } icp_mem;
 
@@ -365,6 +366,62 @@ int icp_get_unique (icp_handle h, int *on);
  * outside {0, 1}, max_gap negative, NaN or infinite. */
 int icp_set_reciprocal (icp_handle h, int on, float max_gap);
 int icp_get_reciprocal (icp_handle h, int *on, float *max_gap);
+
+/* Projective data association (KinectFusion; Open3D's RGB-D odometry; "projection" in Rusinkiewicz & Levoy's matching taxonomy; not
+ * reference behaviour): a second way to FIND the pairs.  The fixed set is an organised grid sampled from a pinhole image; a moving point
+ * is transformed, projected through the fixed camera onto that grid, and paired with what it lands on, or with the closest point of a
+ * small window around it.  O (1) per query, no search structure.  Every rule behind the search (rejection, the boundary and normal
+ * rules, one-to-one, trimming, the robust loss) and every tail (point-to-point, the plane metrics) stay what they are.  The rule:
+ *   - on is 0 or 1.  0 is the default and means off: the same kernels, launches, graphs and bits as without the rule; the getter then
+ *     gives zeros.
+ *   - F is read as a row-major grid gw = grid_width wide, rows = m / gw.  m % gw == 0 is required and checked as
+ *     icp_set_boundary_rejection checks its width: ICP_ESTATE from this call on an initialised handle, and from icp_build_rbc.
+ *   - fx, fy, cx, cy are the pinhole model in grid units: grid column u and row v of a point (x, y, z) are fx x / z + cx and
+ *     fy y / z + cy.  For icp_synth_pair* with side G they are 595 G / 640, 595 G / 480, 319.5 G / 640 and 239.5 G / 480; for the
+ *     landmarks icp_write_cloud samples from a 640 x 480 frame (column 65 + 4 i, row 49 + 3 j) they are 595 / 4, 595 / 3,
+ *     (319.5 - 65) / 4 and (239.5 - 49) / 3.  radius r is in [0, 8]: the window is (2 r + 1)^2 cells, clipped at the grid's edges.
+ *     r = 0 is the KinectFusion pairing, meant for the plane metrics; a point-to-point registration needs r >= 1 to move along the
+ *     surface.
+ *   - Per query i of a registration, with T the transform this iteration's search uses:
+ *       mv = M[i].xyz.  The query counts iff mv is finite and not (0, 0, 0).
+ *       e = T (mv), the transformed point, with the arithmetic of the search's transform.  ICP_MEM_QT[i] = (e, d) is written for every
+ *       i < m; for a miss d = +inf.
+ *       In double from the float inputs, every expression in the order written, with no contraction:
+ *           u = (double) fx * ((double) e.x / (double) e.z) + (double) cx,  v = (double) fy * ((double) e.y / (double) e.z) + (double) cy,
+ *           pu = floor (u + 0.5), pv = floor (v + 0.5).
+ *       The query is inside iff it counts, e is finite, e.z > 0, 0 <= pu <= gw - 1 and 0 <= pv <= rows - 1, compared in double (a
+ *       NaN fails).
+ *       The window is columns max (0, pu - r) .. min (gw - 1, pu + r), and rows likewise.  A candidate is a window cell j = y gw + x
+ *       whose F[j].xyz is finite and not (0, 0, 0); d_j is the engine's metric between (e, M[i].rgb) and (F[j].xyz, F[j].rgb) with
+ *       the handle's alpha (alpha >= 0).
+ *       The winner is the smallest d_j with d_j < +inf, a tie going to the smallest j: the minimum of the key
+ *       ((uint64) bits (d_j) << 32) | j.  The result does not depend on the order in which the window is walked.
+ *       Hit: d = dist_scale d_j, NN_ID[i] = {d, j}, NN[i] = (F[j].xyz, w) with w = weighted ? 100 / (100 + d) : 1, W[i] = w.
+ *       icp_set_rejection's distance test applies to a hit as it does behind the search: the pair keeps its record, its weight is +0.
+ *       Miss — the query does not count, is not inside, or has no winner —: NN_ID[i] = {+inf, 0xFFFFFFFF}, NN[i] = (0, 0, 0, +0),
+ *       W[i] = +0.  A miss is exactly a rejected pair: every pass and every tail guards id < m and w != 0.
+ *   - ICP_MEM_RID is left as it is by a projective iteration.  A later RBC search on the handle seeds its pruning from whatever it
+ *     holds; pruning is exact, so that search's results do not depend on it.
+ *   - ICP_MEM_PROJECTIVE holds (n, hits, outside, empty) of the last iteration per registration: n the counting queries, outside those
+ *     that count and are not inside, empty those inside without a winner; hits + outside + empty == n.  Integer sums, independent of
+ *     the order of arrival; zeros while the rule is off; a converged registration of a checked run keeps its last words.
+ *   - As with rejection, REGULAR mode uses the sum-W formulas, and an iteration without a hit is the sum W == 0 identity step (T
+ *     unchanged, ICP::run stops).
+ * With the rule on the per-query outputs are stored by every iteration, and an iteration is the separate form (icp_run_form is
+ * ICP_FORM_SEPARATE, there is no chained launch).  The projection kernel takes the search's place in icp_launches_per_iteration;
+ * point-to-point adds 1 launch — the pass that writes the block partials from the weights (the apply pass of trimming, one-to-one, the
+ * boundary and normal rules and a point-to-point robust loss; with any of them on it runs anyway, and the rule adds 0) —, the plane
+ * metrics add none.  Switching the rule on or off captures the run graphs anew; a new width, new intrinsics or a new radius while the
+ * rule stays on are parameter updates held in device words, which captured run graphs see.  The setting applies to single, batched and
+ * icp_batch_* registrations and the level handles of a pyramid (icp_pyramid_level), to every error metric, both reduce modes and both
+ * rotation solvers, and survives icp_init.  Intrinsics are per handle: level l of a pyramid takes f / 2^l, and c / 2^l for ICP_PYRAMID_PICK
+ * (a level's cell is finest cell 2^l i), (c - (2^l - 1) / 2) / 2^l for ICP_PYRAMID_MEAN (centred on finest column 2^l i + (2^l - 1) / 2).  icp_build_rbc stays required and still builds the RBC: icp_evaluate, ICP_PAIRS_EVALUATED and the reciprocal rule's back
+ * search use it and ignore this rule; ICP_PAIRS_LAST_ITERATION shows the rule through W.  The rule does not combine with
+ * icp_set_reciprocal (runs return ICP_ESTATE while both are on).  Tracking is not provided: icp_track_submit / icp_track_next return
+ * ICP_ESTATE while the rule is on.  icp_profile_run counts the kernel as the search stage.  ICP_EINVAL: on outside {0, 1}, grid_width 0
+ * with on, fx or fy not finite or not > 0, cx or cy not finite, radius > 8. */
+int icp_set_projective (icp_handle h, int on, uint32_t grid_width, float fx, float fy, float cx, float cy, uint32_t radius);
+int icp_get_projective (icp_handle h, int *on, uint32_t *grid_width, float *fx, float *fy, float *cx, float *cy, uint32_t *radius);
 
 /* Rejection by normal compatibility (PCL: CorrespondenceRejectorSurfaceNormal) and at the fixed grid's boundary (PCL:
  * CorrespondenceRejectorBoundaryPoints; Turk & Levoy; both in Rusinkiewicz & Levoy, "Efficient Variants of ICP"; not reference
@@ -901,6 +958,7 @@ int icp_batch_set_rejection (icp_batch_handle b, int flags, float max_dist);    
 int icp_batch_set_trimming (icp_batch_handle b, float keep_fraction);                        /* icp_set_trimming on every slot */
 int icp_batch_set_unique (icp_batch_handle b, int on);                                       /* icp_set_unique on every slot */
 int icp_batch_set_reciprocal (icp_batch_handle b, int on, float max_gap);                    /* icp_set_reciprocal on every slot */
+int icp_batch_set_projective (icp_batch_handle b, int on, uint32_t grid_width, float fx, float fy, float cx, float cy, uint32_t radius);   /* icp_set_projective on every slot */
 int icp_batch_set_normal_rejection (icp_batch_handle b, int on, float min_cos);              /* icp_set_normal_rejection on every slot */
 int icp_batch_set_boundary_rejection (icp_batch_handle b, uint32_t grid_width);              /* icp_set_boundary_rejection on every slot */
 int icp_batch_set_robust_loss (icp_batch_handle b, int loss, float scale);                   /* icp_set_robust_loss on every slot */

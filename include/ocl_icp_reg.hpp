@@ -81,6 +81,9 @@ public:
     /*! \brief Reciprocal correspondences of the registration (ICPStep::setReciprocal; not in the reference's demo, off by default). */
     void setReciprocal (bool on, float max_gap = 0.f) { reg.setReciprocal (on, max_gap); }
     bool getReciprocal (float *max_gap = nullptr) { return reg.getReciprocal (max_gap); }
+    /*! \brief Projective data association of the registration (ICPStep::setProjective; not in the reference's demo, off by default). */
+    void setProjective (bool on, uint32_t grid_width = 0, float fx = 1.f, float fy = 1.f, float cx = 0.f, float cy = 0.f, uint32_t radius = 0) { reg.setProjective (on, grid_width, fx, fy, cx, cy, radius); }
+    bool getProjective (uint32_t *grid_width = nullptr, float *fx = nullptr, float *fy = nullptr, float *cx = nullptr, float *cy = nullptr, uint32_t *radius = nullptr) { return reg.getProjective (grid_width, fx, fy, cx, cy, radius); }
     /*! \brief Normal and boundary rejection of the registration (ICPStep::setNormalRejection, setBoundaryRejection; off by default). */
     void setNormalRejection (bool on, float min_cos = 0.f) { reg.setNormalRejection (on, min_cos); }
     void setBoundaryRejection (uint32_t grid_width) { reg.setBoundaryRejection (grid_width); }
