@@ -71,11 +71,19 @@ tests/cpp/rbc_set_test: tests/cpp/rbc_set_test.cpp icp_amd/csrc/icp_rbc_set.h ic
 rbc_set_test: tests/cpp/rbc_set_test
 	tests/cpp/rbc_set_test
 
+# the word areas behind the moments against offsets written out by hand (host only: icp_kernels.h, built like rbc_set_test);
+# tests/test_mom_layout_cpu.py runs it
+tests/cpp/mom_layout_test: tests/cpp/mom_layout_test.cpp icp_amd/csrc/icp_kernels.h icp_amd/csrc/icp_device.h icp_amd/csrc/icp_search_select.h
+	$(HIPCC) --cuda-host-only -O1 -g -std=c++17 -Wall -Werror -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -o $@ tests/cpp/mom_layout_test.cpp
+
+mom_layout_test: tests/cpp/mom_layout_test
+	tests/cpp/mom_layout_test
+
 asan: tests/cpp/asan_host
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=0 UBSAN_OPTIONS=print_stacktrace=1 tests/cpp/asan_host
 
 clean:
-	rm -rf build; rm -f $(LIB) examples/registration examples/step_by_step tests/cpp/facade_test tests/cpp/pyramid_facade_test tests/cpp/pairs_facade_test tests/cpp/capi_example tests/cpp/icpreg_test tests/cpp/asan_host tests/cpp/asan_oracle.o tests/cpp/search_select_test tests/cpp/rbc_set_test
+	rm -rf build; rm -f $(LIB) examples/registration examples/step_by_step tests/cpp/facade_test tests/cpp/pyramid_facade_test tests/cpp/pairs_facade_test tests/cpp/capi_example tests/cpp/icpreg_test tests/cpp/asan_host tests/cpp/asan_oracle.o tests/cpp/search_select_test tests/cpp/rbc_set_test tests/cpp/mom_layout_test
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean asan examples search_select_test rbc_set_test
+.PHONY: all oracle clean asan examples search_select_test rbc_set_test mom_layout_test

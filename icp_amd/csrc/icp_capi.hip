@@ -105,14 +105,14 @@ int write_words (icp_context *h, unsigned which)
 {
     const icp_options &o = h->opt;
     auto bits = [] (float f) { uint32_t u; std::memcpy (&u, &f, sizeof u); return u; };
-    uint32_t *const filter = icp_pair_filter_settings (h->p), *const proj = icp_projective_settings (h->p);
+    uint32_t *const filter = icp_words (h->p, ICP_AREA_FILTER).settings, *const proj = icp_words (h->p, ICP_AREA_PROJECTIVE).settings;
     const struct { unsigned flag; uint32_t value; void *word; } words[] = {
         { OPT_W_KAPPA, bits (o.color_kappa), icp_color_kappa (h->p) },
         { OPT_W_ROBUST, bits (o.robust_scale), icp_robust_scale (h->p) },
         { OPT_W_EPS, bits (o.gicp_eps), icp_gicp_eps (h->p) },
         { OPT_W_MIN_COS, bits (o.normal_min_cos), filter },
         { OPT_W_GRID, o.boundary_gw, filter + 1 },
-        { OPT_W_GAP, bits (o.reciprocal_gap), icp_reciprocal_gap (h->p) },
+        { OPT_W_GAP, bits (o.reciprocal_gap), icp_words (h->p, ICP_AREA_RECIPROCAL).settings },
         { OPT_W_PROJ, o.proj_gw, proj }, { OPT_W_PROJ, bits (o.proj_fx), proj + 1 }, { OPT_W_PROJ, bits (o.proj_fy), proj + 2 },
         { OPT_W_PROJ, bits (o.proj_cx), proj + 3 }, { OPT_W_PROJ, bits (o.proj_cy), proj + 4 }, { OPT_W_PROJ, o.proj_radius, proj + 5 },
     };
@@ -124,34 +124,34 @@ int write_words (icp_context *h, unsigned which)
 // The one route behind every setter, once it has updated the record.  `what` is what the setter alone knows: which device words it
 // changed (OPT_W_*), and whether the change is a parameter update (OPT_PARAMS: cached graphs are updated in place when next used), a
 // change of route (OPT_ROUTE: other kernels run, graphs are captured anew), or neither.  What follows from the parameters is found
-// by comparing them, old against new: the result area of a feature that went off is cleared (ICP_MEM_TRIM, ICP_MEM_UNIQUE,
-// ICP_MEM_PAIR_FILTER, ICP_MEM_RECIPROCAL, ICP_MEM_PROJECTIVE, ICP_MEM_PLANE_SYSTEM read zeros while it is off), the moving set of reciprocal correspondences
+// by comparing them, old against new: the result area of a feature that went off is cleared (area_features: its memory object reads
+// zeros while it is off), the moving set of reciprocal correspondences
 // is stale when the rule comes on (M may have been written while it was off), and with grid normals a handle that now needs something its
 // last buildRBC did not compute — the moving normals, the intensity gradients — needs a new buildRBC, as after a new F.
 // Device work in a fixed order: the open runs end, words, clears, then the stream is drained, so that work later enqueued on any of
 // the handle's streams sees them.  OPT_QUIESCE: the open runs end although nothing is written.
 enum : unsigned { OPT_PARAMS = 128u, OPT_ROUTE = 256u, OPT_QUIESCE = 512u };
+// The word areas (icp_area, icp_kernels.h) on the host, indexed by area: the memory object that reads an area's result words and the
+// test that its feature is on.  commit and mem_of go by it.
+const struct { int mem; bool (*on) (const icp_params &); } area_features[ICP_AREA_COUNT] = {
+    { ICP_MEM_TRIM, icp_trimming }, { ICP_MEM_PLANE_SYSTEM, icp_p2pl }, { ICP_MEM_UNIQUE, icp_unique },
+    { ICP_MEM_PAIR_FILTER, icp_pair_filter }, { ICP_MEM_RECIPROCAL, icp_reciprocal }, { ICP_MEM_PROJECTIVE, icp_projective },
+};
 int commit (icp_context *h, unsigned what)
 {
     const icp_params was = h->p;
     icp_params &p = h->p;
     derive_params (h->opt, p);
     if (p.nrm_grid && ((icp_moving_normals (p) && !icp_moving_normals (was)) || (icp_colored (p) && !icp_colored (was)))) h->built = false;
-    const bool off[] = { icp_trimming (was) && !icp_trimming (p), icp_unique (was) && !icp_unique (p),
-                         icp_pair_filter (was) && !icp_pair_filter (p), icp_p2pl (was) && !icp_p2pl (p),
-                         icp_reciprocal (was) && !icp_reciprocal (p), icp_projective (was) && !icp_projective (p) };
-    const bool clears = off[0] || off[1] || off[2] || off[3] || off[4] || off[5];
+    bool off[ICP_AREA_COUNT], clears = false;               // per word area: its feature went off
+    for (int a = 0; a < ICP_AREA_COUNT; ++a) { off[a] = area_features[a].on (was) && !area_features[a].on (p); clears = clears || off[a]; }
     if (icp_reciprocal (p) && !icp_reciprocal (was)) h->recip.stale = true;
     if (h->inited && ((what & (OPT_WORDS | OPT_QUIESCE)) || clears)) {
         int rc = set_device (h); if (rc) return rc;
         if ((rc = run_close_all (h))) return rc;
         if ((rc = write_words (h, what & OPT_WORDS))) return rc;
-        const struct { void *area; size_t bytes; } areas[] = {
-            { icp_trim_area (p), sizeof (uint32_t) * 4u }, { icp_unique_area (p), sizeof (uint32_t) * 2u },
-            { icp_pair_filter_area (p), sizeof (uint32_t) * 4u }, { icp_p2pl_area (p), sizeof (double) * ICP_P2PL_SYS },
-            { icp_reciprocal_area (p), sizeof (uint32_t) * 4u }, { icp_projective_area (p), sizeof (uint32_t) * 4u },
-        };
-        for (int i = 0; i < 6; ++i) if (off[i]) HIPCHK (h, hipMemsetAsync (areas[i].area, 0, areas[i].bytes * p.batch, h->stream));
+        for (int a = 0; a < ICP_AREA_COUNT; ++a)
+            if (off[a]) HIPCHK (h, hipMemsetAsync (icp_words (p, (icp_area) a).result, 0, sizeof (uint32_t) * icp_area_desc_of (a).result * p.batch, h->stream));
         if ((what & OPT_WORDS) || clears) HIPCHK (h, hipStreamSynchronize (h->stream));
     }
     if (what & OPT_ROUTE) drop_graphs (h);
@@ -455,18 +455,16 @@ static mem_desc mem_of (const icp_context *h, uint32_t b, int mem)
         case ICP_MEM_NN: return { p.PF + b * m, m * 16, nullptr };
         case ICP_MEM_QT: return { p.PM + b * m, m * 16, nullptr };
         case ICP_MEM_W: return { reinterpret_cast<const float *> (p.PF + b * m) + 3, m * 4, nullptr };    // (the .w lane of the matched points: a strided read)
-        case ICP_MEM_TRIM: return { icp_trim_area (p) + 4u * b, 16, nullptr };
-        case ICP_MEM_UNIQUE: return { icp_unique_area (p) + 2u * b, 8, nullptr };
-        case ICP_MEM_PAIR_FILTER: return { icp_pair_filter_area (p) + 4u * b, 16, nullptr };
-        case ICP_MEM_RECIPROCAL: return { icp_reciprocal_area (p) + 4u * b, 16, nullptr };
-        case ICP_MEM_PROJECTIVE: return { icp_projective_area (p) + 4u * b, 16, nullptr };
         case ICP_MEM_REVERSE_ID: return { h->recip.nn_id ? h->recip.nn_id + b * m : nullptr, m * 8, nullptr };   // (allocated with the rule's first use)
         case ICP_MEM_NORMALS_F: return { icp_normals_f (p) + b * m, m * 16, "ICP_MEM_NORMALS_F" };
         case ICP_MEM_COLOR_GRAD_F: return { icp_color_grad_f (p) + b * m, m * 16, "ICP_MEM_COLOR_GRAD_F" };
         case ICP_MEM_NORMALS_M: return { icp_normals_m (p) + b * m, m * 16, "ICP_MEM_NORMALS_M" };
-        case ICP_MEM_PLANE_SYSTEM: return { icp_p2pl_area (p) + (size_t) ICP_P2PL_SYS * b, ICP_P2PL_SYS * sizeof (double), nullptr };
-        default: return { nullptr, 0, nullptr };
+        default: break;
     }
+    // (registration b's result words of a word area)
+    for (int a = 0; a < ICP_AREA_COUNT; ++a)
+        if (area_features[a].mem == mem) return { icp_words (p, (icp_area) a).result + (size_t) icp_area_desc_of (a).result * b, icp_area_desc_of (a).result * sizeof (uint32_t), nullptr };
+    return { nullptr, 0, nullptr };
 }
 
 int icp_write_b (icp_handle h, uint32_t b, int mem, const void *host_ptr, int block) try

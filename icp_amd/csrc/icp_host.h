@@ -83,11 +83,11 @@ struct icp_options {
     int reject_flags = 0; float reject_max_dist = 0.f;      // icp_set_rejection
     float trim_keep = 1.f;                       // icp_set_trimming (1: off)
     bool unique = false;                         // icp_set_unique
-    bool reciprocal = false; float reciprocal_gap = 0.f;    // icp_set_reciprocal (0 while off); device word icp_reciprocal_gap
-    // icp_set_projective (all zero while off); device words icp_projective_settings [0 .. 5]
+    bool reciprocal = false; float reciprocal_gap = 0.f;    // icp_set_reciprocal (0 while off); device word ICP_AREA_RECIPROCAL .settings
+    // icp_set_projective (all zero while off); device words ICP_AREA_PROJECTIVE .settings [0 .. 5]
     bool projective = false; uint32_t proj_gw = 0, proj_radius = 0; float proj_fx = 0.f, proj_fy = 0.f, proj_cx = 0.f, proj_cy = 0.f;
-    bool normal_on = false; float normal_min_cos = 0.f;     // icp_set_normal_rejection (0 while off); device word icp_pair_filter_settings [0]
-    uint32_t boundary_gw = 0;                    // icp_set_boundary_rejection (0: off); device word icp_pair_filter_settings [1]
+    bool normal_on = false; float normal_min_cos = 0.f;     // icp_set_normal_rejection (0 while off); device word ICP_AREA_FILTER .settings [0]
+    uint32_t boundary_gw = 0;                    // icp_set_boundary_rejection (0: off); device word ICP_AREA_FILTER .settings [1]
     int robust = ICP_ROBUST_NONE; float robust_scale = 0.f; // icp_set_robust_loss (0 while off); device word icp_robust_scale
     int metric = ICP_METRIC_POINT_TO_POINT; float p2pl_mu = 0.f;   // icp_set_error_metric (0 on point-to-point)
     float color_kappa = 0.f;                     // icp_set_color_weight; device word icp_color_kappa

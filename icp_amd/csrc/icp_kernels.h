@@ -156,9 +156,7 @@ static __host__ __device__ __forceinline__ double icp_robust_omega (uint32_t los
     if (loss == 2u) return 1.0 / (1.0 + u);                             // Cauchy
     return u < 1.0 ? (1.0 - u) * (1.0 - u) : 0.0;                        // Tukey
 }
-// Trimming's buffers (icp_trim.hip) are uint32 words: [batch][4] the result of the last iteration (t bits, n, K, accepted: ICP_MEM_TRIM),
-// [batch][4] the state of the multi-block selection (prefix, rank left, count below, arrivals), [batch][2048] its histograms, and for
-// sets beyond one workgroup's selection [batch][m] the keys.
+// Trimming (icp_trim.hip; its words: ICP_AREA_TRIM below)
 #define ICP_TRIM_ONE_BLOCK_MAX 16384u    // up to this many pairs per registration: the selection is one workgroup's (k_trim_select)
 #define ICP_TRIM_BINS 2048u
 
@@ -186,72 +184,68 @@ static __host__ __device__ __forceinline__ uint32_t icp_p2pl_nblk (uint32_t m) {
 #define ICP_QUALITY_RES 24u
 
 // The moments' allocation p.mom, offsets in doubles.  icp_params has no room for more pointers, so everything the opt-in paths keep per
-// iteration lies behind the fused mode's moment partials: trimming's words, the plane system and its block partials, and colored ICP's
-// weight kappa, the robust loss's scale k and plane-to-plane's epsilon, device words (icp_set_color_weight, icp_set_robust_loss and
-// icp_set_plane_to_plane write them in stream order) that the run graphs read instead of capturing them.
-struct icp_mom_layout {
-    size_t trim;                 // trimming's uint32 words (icp_trim_area)
-    size_t sys;                  // [batch][ICP_P2PL_SYS] ICP_MEM_PLANE_SYSTEM (icp_p2pl_area)
-    size_t part;                 // [batch][ICP_P2PL_TERMS][icp_p2pl_nblk] the plane system's block partials (icp_p2pl_part)
-    size_t kappa;                // the float word of kappa (icp_color_kappa)
-    size_t robust;               // the float word of the robust loss's scale k (icp_robust_scale)
-    size_t gicp;                 // the float word of plane-to-plane's epsilon (icp_gicp_eps)
-    size_t uniq;                 // one-to-one correspondences: [batch][2] uint32 result words (icp_unique_area), [batch][m] uint64 claim table (icp_unique_claims)
-    size_t filt;                 // the pair filter's uint32 words (icp_pair_filter_area): [batch][4] ICP_MEM_PAIR_FILTER, [batch][8] the blocks' running
-                                 // counts and their arrival counter, then min_cos (float) and the boundary rule's grid width
-    size_t recip;                // reciprocal correspondences' uint32 words (icp_reciprocal_area): [batch][4] ICP_MEM_RECIPROCAL, then max_gap (float)
-    size_t proj;                 // projective data association's uint32 words (icp_projective_area): [batch][4] ICP_MEM_PROJECTIVE, [batch][8] the blocks'
-                                 // running counts and their ticket counter, then the six settings (grid width, fx, fy, cx, cy: float bits, radius)
-    size_t total;
-};
+// iteration lies behind the fused mode's moment partials: the passes' and the plane system's word areas, the plane system's block
+// partials, and the device words kappa, k (the robust scale) and epsilon, which the setters write in stream order and the run graphs
+// read instead of capturing them.
+// A word area, in uint32 words: [batch][result] what the feature's ICP_MEM_* object reads (zeros while the feature is off),
+// [batch][running] what an iteration's blocks keep between themselves (zero between launches), `settings` words the kernels read
+// instead of capturing them, then what a feature keeps per pair.  An area starts on a double.  As they lie — result, running, settings:
+//   trimming      4 (t bits, n, K, accepted), 4 + ICP_TRIM_BINS (the multi-block selection's state — prefix, rank left, count below,
+//                 arrivals: [batch][4] — then its histograms), 0; beyond one workgroup's selection [batch][m] the keys
+//   plane system  2 ICP_P2PL_SYS (the doubles of A's upper triangle, b, status), 0, 0; behind it [batch][ICP_P2PL_TERMS][icp_p2pl_nblk]
+//                 doubles, k_plane_moments' block partials, and the words kappa, k, epsilon, a double's room each
+//   one-to-one    2 (n, winners), 0, 0; [batch][m] uint64 the claim table (2 batch words in front: it starts on a double)
+//   pair filter   4 (n, at_boundary, incompatible, accepted), 8 (running counts, ticket), 2 (min_cos: float; grid width)
+//   reciprocal    4 (n, exact, near, accepted), 0, 1 (max_gap: float; the kernel squares it in double)
+//   projective    4 (n, hits, outside, empty), 8 (running counts, ticket), 6 (grid width; fx, fy, cx, cy: float bits; radius)
+enum icp_area { ICP_AREA_TRIM = 0, ICP_AREA_PLANE, ICP_AREA_UNIQUE, ICP_AREA_FILTER, ICP_AREA_RECIPROCAL, ICP_AREA_PROJECTIVE, ICP_AREA_COUNT };
+struct icp_area_desc { uint32_t result, running, settings; };
+static __host__ __device__ inline icp_area_desc icp_area_desc_of (int a)
+{
+    constexpr icp_area_desc d[ICP_AREA_COUNT] = { { 4u, 4u + ICP_TRIM_BINS, 0u }, { 2u * ICP_P2PL_SYS, 0u, 0u }, { 2u, 0u, 0u },     // trimming, plane system, one-to-one
+                                                  { 4u, 8u, 2u }, { 4u, 0u, 1u }, { 4u, 8u, 6u } };                                    // pair filter, reciprocal, projective
+    return d[a];
+}
+static __host__ __device__ inline size_t icp_area_size (int a, size_t B, uint32_t m)    // words, with trimming's keys and the claim table
+{
+    const icp_area_desc d = icp_area_desc_of (a);
+    const size_t per_pair = a == ICP_AREA_TRIM ? (m > ICP_TRIM_ONE_BLOCK_MAX ? B * m : 0u) : a == ICP_AREA_UNIQUE ? 2u * B * m : 0u;
+    return B * (d.result + d.running) + d.settings + per_pair;
+}
+struct icp_mom_layout { size_t area[ICP_AREA_COUNT], part, kappa, robust, gicp, total; };    // part: icp_p2pl_part; the three words: icp_color_kappa, icp_robust_scale, icp_gicp_eps
+// (the robust kernels compute `robust` on the device: the steps up to it stand in the order the compiler has always seen them)
 static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (uint32_t batch, uint32_t m, uint32_t nb)
 {
-    const size_t B = batch, trim_words = B * (8u + ICP_TRIM_BINS) + (m > ICP_TRIM_ONE_BLOCK_MAX ? B * m : 0u);
+    const size_t B = batch, trim_words = icp_area_size (ICP_AREA_TRIM, B, m);
     icp_mom_layout l;
-    l.trim = B * 2 * 18 * nb;                            // behind [batch][2][18][nb], the fused mode's moment partials
-    l.sys = l.trim + (trim_words + 1u) / 2u;
-    l.part = l.sys + B * ICP_P2PL_SYS;
+    l.area[ICP_AREA_TRIM] = B * 2 * 18 * nb;             // behind [batch][2][18][nb], the fused mode's moment partials
+    l.area[ICP_AREA_PLANE] = l.area[ICP_AREA_TRIM] + (trim_words + 1u) / 2u;
+    l.part = l.area[ICP_AREA_PLANE] + icp_area_size (ICP_AREA_PLANE, B, m) / 2u;
     l.kappa = l.part + B * ICP_P2PL_TERMS * icp_p2pl_nblk (m);
     l.robust = l.kappa + 1u;
     l.gicp = l.robust + 1u;
-    l.uniq = l.gicp + 1u;
-    l.filt = l.uniq + B + B * m;
-    l.recip = l.filt + 6u * B + 1u;
-    l.proj = l.recip + 2u * B + 1u;
-    l.total = l.proj + 6u * B + 3u;
+    size_t at = l.gicp + 1u;
+    for (int a = ICP_AREA_UNIQUE; a < ICP_AREA_COUNT; ++a) { l.area[a] = at; at += (icp_area_size (a, B, m) + 1u) / 2u; }
+    l.total = at;
     return l;
 }
 static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (const icp_params &p) { return icp_mom_layout_of (p.batch, p.m, p.nb); }
-static inline uint32_t *icp_trim_area (const icp_params &p) { return reinterpret_cast<uint32_t *> (p.mom + icp_mom_layout_of (p).trim); }
-static inline double *icp_p2pl_area (const icp_params &p) { return p.mom + icp_mom_layout_of (p).sys; }
+// an area's three runs of words (.result + result-words * b is registration b's; behind .settings lies what the area keeps per pair)
+struct icp_area_words { uint32_t *result, *running, *settings; };
+static inline icp_area_words icp_words (const icp_params &p, icp_area a)
+{
+    const icp_area_desc d = icp_area_desc_of (a);
+    uint32_t *w = reinterpret_cast<uint32_t *> (p.mom + icp_mom_layout_of (p).area[a]);
+    return { w, w + (size_t) d.result * p.batch, w + (size_t) (d.result + d.running) * p.batch };
+}
+static inline double *icp_p2pl_area (const icp_params &p) { return reinterpret_cast<double *> (icp_words (p, ICP_AREA_PLANE).result); }
 static inline double *icp_p2pl_part (const icp_params &p) { return p.mom + icp_mom_layout_of (p).part; }
 static inline float *icp_color_kappa (const icp_params &p) { return reinterpret_cast<float *> (p.mom + icp_mom_layout_of (p).kappa); }
 // (also on the device: the robust kernels find the word from their icp_params, the loss-off kernels take no argument for it)
 static __host__ __device__ inline float *icp_robust_scale (const icp_params &p) { return reinterpret_cast<float *> (p.mom + icp_mom_layout_of (p).robust); }
 static __host__ __device__ inline float *icp_gicp_eps (const icp_params &p) { return reinterpret_cast<float *> (p.mom + icp_mom_layout_of (p).gicp); }
-// One-to-one correspondences (icp_unique.hip): the result words of a registration are (n, winners), ICP_MEM_UNIQUE as it is read.
-static inline uint32_t *icp_unique_area (const icp_params &p) { return reinterpret_cast<uint32_t *> (p.mom + icp_mom_layout_of (p).uniq); }
-static inline unsigned long long *icp_unique_claims (const icp_params &p)
-{
-    return reinterpret_cast<unsigned long long *> (p.mom + icp_mom_layout_of (p).uniq + (size_t) p.batch);
-}
-// The pair filter (icp_pair_filter.hip), uint32 words: [batch][4] the result of the last iteration (n, at_boundary, incompatible, accepted:
-// ICP_MEM_PAIR_FILTER); [batch][8] the running counts of an iteration's blocks and their arrival counter, zero between launches; then
-// the two settings the kernel reads instead of capturing them: min_cos (float) and the grid width.
-static inline uint32_t *icp_pair_filter_area (const icp_params &p) { return reinterpret_cast<uint32_t *> (p.mom + icp_mom_layout_of (p).filt); }
-static inline uint32_t *icp_pair_filter_counts (const icp_params &p) { return icp_pair_filter_area (p) + 4u * (size_t) p.batch; }
-static inline uint32_t *icp_pair_filter_settings (const icp_params &p) { return icp_pair_filter_area (p) + 12u * (size_t) p.batch; }
-// Reciprocal correspondences (icp_reciprocal.hip), uint32 words: [batch][4] the result of the last iteration (n, exact, near, accepted:
-// ICP_MEM_RECIPROCAL; k_reciprocal_state resets them, k_reciprocal's blocks add their counts), then the setting the kernel reads instead
-// of capturing it: max_gap (float; the kernel squares it in double).
-static inline uint32_t *icp_reciprocal_area (const icp_params &p) { return reinterpret_cast<uint32_t *> (p.mom + icp_mom_layout_of (p).recip); }
-static inline uint32_t *icp_reciprocal_gap (const icp_params &p) { return icp_reciprocal_area (p) + 4u * (size_t) p.batch; }
-// Projective data association (icp_projective.hip), uint32 words: [batch][4] the result of the last iteration (n, hits, outside, empty:
-// ICP_MEM_PROJECTIVE); [batch][8] the running counts of an iteration's blocks and their ticket counter, zero between launches; then the
-// settings the kernel reads instead of capturing them: grid width, fx, fy, cx, cy (float bits), radius.
-static inline uint32_t *icp_projective_area (const icp_params &p) { return reinterpret_cast<uint32_t *> (p.mom + icp_mom_layout_of (p).proj); }
-static inline uint32_t *icp_projective_counts (const icp_params &p) { return icp_projective_area (p) + 4u * (size_t) p.batch; }
-static inline uint32_t *icp_projective_settings (const icp_params &p) { return icp_projective_area (p) + 12u * (size_t) p.batch; }
+// (one-to-one's claim table)
+static inline unsigned long long *icp_unique_claims (const icp_params &p) { return reinterpret_cast<unsigned long long *> (icp_words (p, ICP_AREA_UNIQUE).settings); }
 
 // The XP allocation of one RBC set, offsets in floats: [batch][m][8] the permuted database, then [batch][m] float4 NORMALS_F and
 // [batch][m] float4 COLOR_GRAD_F ([gx gy gz C] per fixed point).  The normals and gradients belong to the fixed frame as the RBC does,

@@ -11,23 +11,17 @@
 // icp_symmetric.hip's, also NORMALS_M from M), and with the colored metric k_color_grad_grid computes COLOR_GRAD_F behind it.  None of the
 // point-to-point kernels carries any of this code; the translation unit is built with -ffp-contract=off like every other, so each
 // expression below is evaluated exactly in the order it is written.
-#include "icp_plane_moments.h"          // (plane_moments, intensity)
+#include "icp_plane_moments.h"          // (plane_moments, intensity; icp_pair_rule.h)
 
 namespace {
 
-// a grid point takes part in a difference or a gradient when its xyz is finite and not the origin (a Kinect pixel without depth)
-__device__ __forceinline__ bool grid_valid (float x, float y, float z)
-{
-    return isfinite (x) && isfinite (y) && isfinite (z) && !(x == 0.f && y == 0.f && z == 0.f);
-}
-
-
+// (a grid point takes part in a difference or a gradient when it is valid — icp_point_valid: a Kinect pixel without depth is not)
 __device__ __forceinline__ float3 nrm_sub (float3 a, float3 b) { return make_float3 (a.x - b.x, a.y - b.y, a.z - b.z); }
 
 // the difference along one grid axis: central if both neighbours are valid, else one-sided against the centre (the next neighbour first)
 __device__ __forceinline__ bool nrm_diff (float3 prev, bool has_prev, float3 c, float3 next, bool has_next, float3 &d)
 {
-    const bool vp = has_prev && grid_valid (prev.x, prev.y, prev.z), vn = has_next && grid_valid (next.x, next.y, next.z);
+    const bool vp = has_prev && icp_point_valid (prev.x, prev.y, prev.z), vn = has_next && icp_point_valid (next.x, next.y, next.z);
     if (vp && vn) d = nrm_sub (next, prev);
     else if (vn) d = nrm_sub (next, c);
     else if (vp) d = nrm_sub (c, prev);
@@ -95,7 +89,7 @@ __global__ __launch_bounds__ (256) void k_normals_grid (icp_params p, const floa
     const float3 zero = dh;
     // (i + 1 < m, y + 1 < H: no read beyond the set even if the width did not divide m — the host refuses that, ICP_ESTATE)
     const bool hasl = x > 0u, hasr = x + 1u < W && i + 1u < p.m, hasu = y > 0u, hasd = y + 1u < H;
-    if (grid_valid (c.x, c.y, c.z) &&
+    if (icp_point_valid (c.x, c.y, c.z) &&
         nrm_diff (hasl ? at (i - 1u) : zero, hasl, c, hasr ? at (i + 1u) : zero, hasr, dh) &&
         nrm_diff (hasu ? at (i - W) : zero, hasu, c, hasd ? at (i + W) : zero, hasd, dv)) {
         const float cx = dh.y * dv.z - dh.z * dv.y, cy = dh.z * dv.x - dh.x * dv.z, cz = dh.x * dv.y - dh.y * dv.x;
@@ -126,7 +120,7 @@ __global__ __launch_bounds__ (256) void k_color_grad_grid (icp_params p, const f
     const float cx = c[0], cy = c[1], cz = c[2], Cc = intensity (c[4], c[5], c[6]);
     const float4 n = nrm[(size_t) b * p.m + i];
     float4 out = make_float4 (0.f, 0.f, 0.f, Cc);
-    if (grid_valid (cx, cy, cz) && !(n.x == 0.f && n.y == 0.f && n.z == 0.f)) {
+    if (icp_point_valid (cx, cy, cz) && !(n.x == 0.f && n.y == 0.f && n.z == 0.f)) {
         const double nx = (double) n.x, ny = (double) n.y, nz = (double) n.z;
         const double px = (double) cx, py = (double) cy, pz = (double) cz, pc = (double) Cc;
         double A00 = 0.0, A01 = 0.0, A02 = 0.0, A11 = 0.0, A12 = 0.0, A22 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0;
@@ -142,7 +136,7 @@ __global__ __launch_bounds__ (256) void k_color_grad_grid (icp_params p, const f
                 if (j >= p.m) continue;                      // (no read beyond the set even if the width did not divide m)
                 const float *q = F + (size_t) j * 8;
                 const float qx = q[0], qy = q[1], qz = q[2];
-                if (!grid_valid (qx, qy, qz)) continue;
+                if (!icp_point_valid (qx, qy, qz)) continue;
                 const double vx = (double) qx - px, vy = (double) qy - py, vz = (double) qz - pz;
                 const double vn = (vx * nx + vy * ny) + vz * nz;
                 const double ux = vx - vn * nx, uy = vy - vn * ny, uz = vz - vn * nz;

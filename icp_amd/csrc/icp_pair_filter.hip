@@ -16,23 +16,15 @@
 // (plane_rot_normal), qq = (qx qx + qy qy) + qz qz, pp likewise, o = (qx px + qy py) + qz pz; the pair is compatible iff
 // qq > 0 && pp > 0 && o >= (double) min_cos * sqrt (qq * pp).  min_cos is a device word: a new threshold touches no graph.
 //
-// Counting: the boundary test comes first, a pair is counted once, n = at_boundary + incompatible + accepted.  The blocks of a
-// registration add their integer counts to four running words and then take a ticket; the block that draws the last ticket — every
-// other block's counts are in by then (release / acquire on the ticket, agent scope) — moves the sums into the result words
-// (n, at_boundary, incompatible, accepted: ICP_MEM_PAIR_FILTER), and leaves the running words and the ticket counter zero for the
-// next launch.  Integer sums: nothing depends on the order in which the device gets to the pairs.  Nothing else reads the words: the
-// apply pass behind the filter accepts every pair that still has a weight (icp_trim_apply.h).
-#include "icp_plane_moments.h"          // (plane_finite_or_zero, plane_rot_normal)
+// Counting: the boundary test comes first, a pair is counted once, n = at_boundary + incompatible + accepted: the result words are
+// (n, at_boundary, incompatible, accepted: ICP_MEM_PAIR_FILTER).  No launch stands in front of the pass that could reset them, so
+// its blocks count by ticket (pair_counts_ticket, icp_pair_rule.h).  Nothing else reads the words: the apply pass behind the filter
+// accepts every pair that still has a weight (icp_trim_apply.h).
+#include "icp_plane_moments.h"          // (plane_finite_or_zero, plane_rot_normal; icp_pair_rule.h)
 
 namespace {
 
 constexpr uint32_t FILTER_BLOCK = 256u;
-
-__device__ __forceinline__ bool filter_valid (const float *r)
-{
-    const float x = r[0], y = r[1], z = r[2];
-    return isfinite (x) && isfinite (y) && isfinite (z) && !(x == 0.f && y == 0.f && z == 0.f);
-}
 
 // fixed point id of a grid gw wide and `rows` high: on the rim, invalid, or beside an invalid point
 __device__ __forceinline__ bool filter_at_boundary (const float *F, uint32_t id, uint32_t gw, uint32_t rows)
@@ -45,20 +37,19 @@ __device__ __forceinline__ bool filter_at_boundary (const float *F, uint32_t id,
     for (int dy = -1; dy <= 1; ++dy)
 #pragma unroll
         for (int dx = -1; dx <= 1; ++dx)
-            ok = ok && filter_valid (F + (size_t) ((y + dy) * gw + (x + dx)) * 8u);
+            ok = ok && icp_point_valid (F + (size_t) ((y + dy) * gw + (x + dx)) * 8u);
     return !ok;
 }
 
 // ------------------------------------------------------------------------------------------
-// k_pair_filter — one thread per pair, grid (ceil (m / 256), batch).  result, counts, settings: icp_pair_filter_area / _counts /
-// _settings (icp_kernels.h)
+// k_pair_filter — one thread per pair, grid (ceil (m / 256), batch).  result, counts, settings: icp_words (p, ICP_AREA_FILTER)
+// (icp_kernels.h)
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__ (FILTER_BLOCK) void k_pair_filter (icp_params p, const float4 *nrm, const float4 *nrm_m, uint32_t *result, uint32_t *counts,
                                                                 const uint32_t *settings)
 {
-    __shared__ uint32_t s_cnt[FILTER_BLOCK / 64u][4];
     const uint32_t b = blockIdx.y, t = threadIdx.x, i = blockIdx.x * FILTER_BLOCK + t;
-    if (p.check && p.st[b].done) return;                     // (a converged registration: its last iteration's outputs and counts stay)
+    if (icp_pass_leaves (p, b)) return;
     const float min_cos = __uint_as_float (settings[0]);
     const uint32_t gw = settings[1];
     const bool by_boundary = (p.reject & ICP_REJECT_BOUNDARY_ON) != 0u && gw != 0u, by_normal = (p.reject & ICP_REJECT_NORMAL_ON) != 0u;
@@ -67,7 +58,7 @@ __global__ __launch_bounds__ (FILTER_BLOCK) void k_pair_filter (icp_params p, co
         const size_t o = (size_t) b * p.m, e = o + i;
         const float4 f = p.PF[e];
         const uint32_t id = p.nn_id[e].id;
-        cand = f.w != 0.f && id < p.m;
+        cand = icp_pair_candidate (f.w, id, p.m);
         if (cand) {
             if (by_boundary) bnd = filter_at_boundary (p.F + o * 8u, id, gw, p.m / gw);
             if (by_normal && !bnd) {
@@ -82,30 +73,12 @@ __global__ __launch_bounds__ (FILTER_BLOCK) void k_pair_filter (icp_params p, co
                 const double dot = (qx * np[0] + qy * np[1]) + qz * np[2];
                 inc = !(qq > 0.0 && pp > 0.0 && dot >= (double) min_cos * sqrt (qq * pp));
             }
-            if (bnd || inc) reinterpret_cast<float *> (p.PF + e)[3] = 0.f;
+            if (bnd || inc) icp_pair_reject (p.PF + e);
         }
     }
-    const uint32_t wn = (uint32_t) __popcll (__ballot (cand)), wb = (uint32_t) __popcll (__ballot (bnd)), wi = (uint32_t) __popcll (__ballot (inc));
-    if ((t & 63u) == 0u) { s_cnt[t >> 6][0] = wn; s_cnt[t >> 6][1] = wb; s_cnt[t >> 6][2] = wi; }
-    __syncthreads ();
-    if (t == 0u) {
-        uint32_t sn = 0u, sb = 0u, si = 0u;
-#pragma unroll
-        for (uint32_t v = 0; v < FILTER_BLOCK / 64u; ++v) { sn += s_cnt[v][0]; sb += s_cnt[v][1]; si += s_cnt[v][2]; }
-        uint32_t *run = counts + 8u * b;
-        if (sn) __hip_atomic_fetch_add (run + 0, sn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (sb) __hip_atomic_fetch_add (run + 1, sb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (si) __hip_atomic_fetch_add (run + 2, si, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t ticket = __hip_atomic_fetch_add (run + 4, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (ticket + 1u == gridDim.x) {                      // (the last block of the registration: every count is in)
-            const uint32_t n = __hip_atomic_exchange (run + 0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t nb = __hip_atomic_exchange (run + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t ni = __hip_atomic_exchange (run + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store (run + 4, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            uint32_t *out = result + 4u * b;
-            out[0] = n; out[1] = nb; out[2] = ni; out[3] = n - nb - ni;
-        }
-    }
+    const uint32_t wave[3] = { (uint32_t) __popcll (__ballot (cand)), (uint32_t) __popcll (__ballot (bnd)), (uint32_t) __popcll (__ballot (inc)) };
+    uint32_t sum[3];
+    if (pair_block_counts<3, FILTER_BLOCK> (wave, sum)) pair_counts_ticket (counts + 8u * b, result + 4u * b, sum[0], sum[1], sum[2], gridDim.x);
 }
 
 }  // namespace
@@ -113,6 +86,7 @@ __global__ __launch_bounds__ (FILTER_BLOCK) void k_pair_filter (icp_params p, co
 void icp_launch_pair_filter (const icp_params &p, hipStream_t s)
 {
     const dim3 grid ((p.m + FILTER_BLOCK - 1u) / FILTER_BLOCK, p.batch);
+    const icp_area_words w = icp_words (p, ICP_AREA_FILTER);
     hipLaunchKernelGGL (k_pair_filter, grid, dim3 (FILTER_BLOCK), 0, s, p, (const float4 *) icp_normals_f (p), (const float4 *) icp_normals_m (p),
-                        icp_pair_filter_area (p), icp_pair_filter_counts (p), icp_pair_filter_settings (p));
+                        w.result, w.running, (const uint32_t *) w.settings);
 }

@@ -33,7 +33,7 @@
 //   qc of J_C and r_C as q of J and r,  kc = kappa;   with a loss sC2 = kappa (r_C r_C),  wC = omega (sC2 / k2),  kc = kappa wC
 #pragma once
 #include <type_traits>
-#include "icp_kernels.h"
+#include "icp_pair_rule.h"              // (icp_pass_leaves; icp_kernels.h)
 
 namespace {
 
@@ -160,7 +160,7 @@ __device__ __forceinline__ void plane_moments (icp_params p, const float4 *nrm, 
     const float4 mc = COLORED ? *reinterpret_cast<const float4 *> (p.M + (o + ic) * 8 + 4) : make_float4 (0.f, 0.f, 0.f, 0.f);
     const float kap = COLORED ? *kappa_word : 0.f;
     // (a converged registration: asked behind the pair's loads — in front of them the flag's round trip would come first)
-    if (p.check && p.st[b].done) return;                 // (block-uniform)
+    if (icp_pass_leaves (p, b)) return;                  // (block-uniform)
     double v[ICP_P2PL_TERMS];
 #pragma unroll
     for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) v[t] = 0.0;

@@ -30,13 +30,10 @@
 // neighbouring cells — read neighbouring 32-byte records of F, so a wave's loads are as contiguous with the window walked by one lane as
 // with the window spread over a lane group, and the gather lives in L2.  float4 loads of M and of the two halves of F[j].
 //
-// Counting (ICP_MEM_PROJECTIVE: n, hits, outside, empty; hits + outside + empty == n) follows the pair filter's scheme, because this
-// kernel has no launch in front of it that could reset the words: the blocks of a registration add their integer counts to running
-// words and take a ticket; the block that draws the last one moves the sums into the result words and leaves the running words and the
-// ticket zero for the next launch.  A block of 256 threads serves 1024 queries in four rounds at the sizes where the number of tickets
-// matters (a ticket's release writes its XCD's L2 back: icp_reciprocal.hip has the measurement), 256 where the grid would otherwise not
-// fill the chip.  (Measured at 2^20 points: blocks of 1024 threads and one round instead — the same number of tickets — take 188 instead
-// of 90 us per point-to-point iteration at r = 0.)  Integer sums: nothing depends on the order of arrival.
+// Counting (ICP_MEM_PROJECTIVE: n, hits, outside, empty; hits + outside + empty == n): this kernel has no launch in front of it that
+// could reset the words, so its blocks count by ticket (pair_counts_ticket, icp_pair_rule.h, which has the measurements).  A block of
+// 256 threads serves 1024 queries in four rounds at the sizes where the number of tickets matters, 256 where the grid would otherwise
+// not fill the chip; a wave accumulates its counts over the rounds.
 #include "icp_search.h"                 // (icp_mirror_store)
 #include "icp_pair_rule.h"
 
@@ -45,23 +42,17 @@ namespace {
 constexpr uint32_t PROJ_BLOCK = 256u;
 constexpr uint32_t PROJ_NONE = 0xFFFFFFFFu;
 
-__device__ __forceinline__ bool proj_valid (const float4 &g)
-{
-    return isfinite (g.x) && isfinite (g.y) && isfinite (g.z) && !(g.x == 0.f && g.y == 0.f && g.z == 0.f);
-}
-
 // ------------------------------------------------------------------------------------------
 // k_projective — one thread per query, 256 queries per round, `rounds` rounds per block; grid (ceil (m / (256 rounds)), batch).
-// result, counts, settings: icp_projective_area / _counts / _settings (icp_kernels.h); settings = (gw, fx, fy, cx, cy, r)
+// result, counts, settings: icp_words (p, ICP_AREA_PROJECTIVE) (icp_kernels.h); settings = (gw, fx, fy, cx, cy, r)
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__ (PROJ_BLOCK) void k_projective (icp_params p, uint32_t rounds, uint32_t *result, uint32_t *counts, const uint32_t *settings)
 {
-    __shared__ uint32_t s_cnt[PROJ_BLOCK / 64u][3];
     const uint32_t b = blockIdx.y, t = threadIdx.x, m = p.m;
     const icp_reg_state *st = p.st + b;
     const uint32_t done = st->done;
     if (p.hmirror && blockIdx.x == 0u && t == 0u && !(p.fused && done)) icp_mirror_store (p.hmirror + b, ICP_MIRROR_WORD (p.epoch, st->k, done));
-    if (p.check && done) return;                             // (a converged registration: its last iteration's outputs and counts stay)
+    if (p.check && done) return;                             // (icp_pass_leaves, with the one load of `done` above)
     float T[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) T[k] = st->T[k];
@@ -98,7 +89,7 @@ __global__ __launch_bounds__ (PROJ_BLOCK) void k_projective (icp_params p, uint3
                     const uint32_t j = y * gw + x;
                     const float4 fg = F4[2u * (size_t) j], fc = F4[2u * (size_t) j + 1u];
                     const float d = icp_metric8 (ex, ey, ez, mc.x, mc.y, mc.z, fg.x, fg.y, fg.z, fc.x, fc.y, fc.z, p.a);
-                    if (proj_valid (fg) && d < __builtin_inff ()) {
+                    if (icp_point_valid (fg) && d < __builtin_inff ()) {
                         const unsigned long long k = ((unsigned long long) __float_as_uint (d) << 32) | j;
                         key = k < key ? k : key;
                     }
@@ -113,7 +104,8 @@ __global__ __launch_bounds__ (PROJ_BLOCK) void k_projective (icp_params p, uint3
                 const float4 fg = F4[2u * (size_t) j];       // (j < m: a cell of the window)
                 const float d = p.dist_scale * __uint_as_float ((uint32_t) (key >> 32));
                 float w = p.weighted ? 100.f / (100.f + d) : 1.f;
-                if (p.reject & ICP_REJECT_DIST_ON) {         // (icp_set_rejection's distance test, as the REJ search's epilogue applies it)
+                if (p.reject & ICP_REJECT_DIST_ON) {         // (icp_set_rejection's distance test, as the REJ search's epilogue applies it:
+                    // icp_pair_geo of e - fg, written out — through the helper the compiler branches where it selects here: profiles/pair_pass_isa_diff.txt)
                     const float gx = ex - fg.x, gy = ey - fg.y, gz = ez - fg.z;
                     if (!(((gx * gx + gy * gy) + gz * gz) <= p.reject_d2)) w = 0.f;
                 }
@@ -128,25 +120,9 @@ __global__ __launch_bounds__ (PROJ_BLOCK) void k_projective (icp_params p, uint3
         ch += (uint32_t) __popcll (__ballot (hit));
         co += (uint32_t) __popcll (__ballot (counts_ && !inside));
     }
-    if ((t & 63u) == 0u) { s_cnt[t >> 6][0] = cn; s_cnt[t >> 6][1] = ch; s_cnt[t >> 6][2] = co; }
-    __syncthreads ();
-    if (t == 0u) {
-        uint32_t sn = 0u, sh = 0u, so = 0u;
-        for (uint32_t k = 0; k < PROJ_BLOCK / 64u; ++k) { sn += s_cnt[k][0]; sh += s_cnt[k][1]; so += s_cnt[k][2]; }
-        uint32_t *run = counts + 8u * b;
-        if (sn) __hip_atomic_fetch_add (run + 0, sn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (sh) __hip_atomic_fetch_add (run + 1, sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (so) __hip_atomic_fetch_add (run + 2, so, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t ticket = __hip_atomic_fetch_add (run + 4, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (ticket + 1u == gridDim.x) {                      // (the last block of the registration: every count is in)
-            const uint32_t n = __hip_atomic_exchange (run + 0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t nh = __hip_atomic_exchange (run + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t no = __hip_atomic_exchange (run + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store (run + 4, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            uint32_t *out = result + 4u * b;
-            out[0] = n; out[1] = nh; out[2] = no; out[3] = n - nh - no;
-        }
-    }
+    const uint32_t wave[3] = { cn, ch, co };
+    uint32_t sum[3];
+    if (pair_block_counts<3, PROJ_BLOCK> (wave, sum)) pair_counts_ticket (counts + 8u * b, result + 4u * b, sum[0], sum[1], sum[2], gridDim.x);
 }
 
 }  // namespace
@@ -156,6 +132,6 @@ void icp_launch_projective (const icp_params &p, hipStream_t s)
     // queries per block: 1024 where a registration's tickets would be many (see the header), else one round's worth
     const uint32_t rounds = (size_t) p.batch * p.m > 65536u ? 4u : 1u, per_block = rounds * PROJ_BLOCK;
     const dim3 grid ((p.m + per_block - 1u) / per_block, p.batch);
-    hipLaunchKernelGGL (k_projective, grid, dim3 (PROJ_BLOCK), 0, s, p, rounds, icp_projective_area (p), icp_projective_counts (p),
-                        (const uint32_t *) icp_projective_settings (p));
+    const icp_area_words w = icp_words (p, ICP_AREA_PROJECTIVE);
+    hipLaunchKernelGGL (k_projective, grid, dim3 (PROJ_BLOCK), 0, s, p, rounds, w.result, w.running, (const uint32_t *) w.settings);
 }

@@ -3,6 +3,7 @@
 // (k_set_T reading the coarser handle's state, the streams ordered by an event).  The rule is in include/icp_amd.h.
 // No reference counterpart (one resolution: src/ICP/algorithms.cpp:4403-4582); Open3D: multi_scale_icp, KinectFusion's three-level pyramid.
 #include "icp_host.h"
+#include "icp_pair_rule.h"              // (icp_point_valid)
 
 using namespace icp_host;
 
@@ -21,11 +22,6 @@ struct icp_pyramid_args {
     float max_dz;
 };
 
-static __device__ __forceinline__ bool pyr_valid (const float4 &g)
-{
-    return isfinite (g.x) && isfinite (g.y) && isfinite (g.z) && !(g.x == 0.f && g.y == 0.f && g.z == 0.f);
-}
-
 // one point of a block joins the running sums (s = the first included value as it is — a lone -0 stays -0 —, then s = s + next)
 static __device__ __forceinline__ void pyr_add (bool inc, const float4 &g, const float4 &c, uint32_t &n, float4 &sg, float4 &sc)
 {
@@ -43,7 +39,7 @@ static __device__ __forceinline__ void pyr_reduce (const float4 &g0, const float
 {
     og = g0; oc = c0;                                                // PICK, and a block without a valid point: element 0, bit for bit
     if (kind == ICP_PYRAMID_PICK) return;
-    const bool v0 = pyr_valid (g0), v1 = pyr_valid (g1), v2 = pyr_valid (g2), v3 = pyr_valid (g3);
+    const bool v0 = icp_point_valid (g0), v1 = icp_point_valid (g1), v2 = icp_point_valid (g2), v3 = icp_point_valid (g3);
     if (!(v0 || v1 || v2 || v3)) return;
     const float zref = v0 ? g0.z : v1 ? g1.z : v2 ? g2.z : g3.z;
     float4 sg = make_float4 (0.f, 0.f, 0.f, 0.f), sc = sg;

@@ -19,12 +19,10 @@
 // registration again — the same words: T has not changed since.)
 //
 // Counting follows one-to-one's passes: the state kernel's first lane resets the registration's result words (n, exact, near, accepted:
-// ICP_MEM_RECIPROCAL), k_reciprocal's blocks add their integer counts to them with relaxed atomics — no ticket, no fence: a block's
-// release at agent scope would write its XCD's L2 back, fresh weights and all (measured with the pair filter's ticket scheme: 64 batched
-// registrations of 16384 pairs took 388 instead of 294 us per iteration).  The two kernels are launched together and test the same flag, which only
-// the tail behind them changes: a reset without its counts does not exist, and a converged registration's words stay.  Integer sums:
-// nothing depends on the order of arrival.
+// ICP_MEM_RECIPROCAL), k_reciprocal's blocks add their integer counts to them (pair_counts_add, icp_pair_rule.h, which says why no
+// ticket).  The two kernels are launched together and test the same flag, which only the tail behind them changes.
 #include "icp_rbc_set.h"
+#include "icp_pair_rule.h"
 #include <cstdio>
 #include <cstdlib>
 
@@ -50,7 +48,7 @@ __global__ __launch_bounds__ (64) void k_reciprocal_state (icp_params p, icp_reg
     if (t < sizeof (icp_reg_state) / 4u && !(t >= T0 && t < T0 + 8u) && t != G0)
         reinterpret_cast<uint32_t *> (out)[t] = reinterpret_cast<const uint32_t *> (st)[t];
     if (t != 0u) return;
-    if (!(p.check && st->done)) { uint32_t *w = result + 4u * b; w[0] = 0u; w[1] = 0u; w[2] = 0u; w[3] = 0u; }     // (a converged registration: its last iteration's counts stay)
+    if (!icp_pass_leaves (p, b)) { uint32_t *w = result + 4u * b; w[0] = 0u; w[1] = 0u; w[2] = 0u; w[3] = 0u; }     // (a converged registration: its last iteration's counts stay)
     const double x = (double) st->T[0], y = (double) st->T[1], z = (double) st->T[2], w = (double) st->T[3];
     const double tx = (double) st->T[4], ty = (double) st->T[5], tz = (double) st->T[6];
     const float s = st->T[7];
@@ -72,14 +70,13 @@ __global__ __launch_bounds__ (64) void k_reciprocal_state (icp_params p, icp_reg
 
 // ------------------------------------------------------------------------------------------
 // k_reciprocal — one thread per pair, grid (ceil (m / 256), batch).  rev: the back search's (dist, id) per fixed point; result, gap:
-// icp_reciprocal_area / _gap (icp_kernels.h)
+// icp_words (p, ICP_AREA_RECIPROCAL) (icp_kernels.h)
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__ (RECIPROCAL_BLOCK) void k_reciprocal (icp_params p, const icp_dist_id *rev, const icp_reg_state *rst, uint32_t *result,
                                                                    const uint32_t *gap)
 {
-    __shared__ uint32_t s_cnt[RECIPROCAL_BLOCK / 64u][3];
-    const uint32_t b = blockIdx.y, t = threadIdx.x, i = blockIdx.x * RECIPROCAL_BLOCK + t;
-    if (p.check && p.st[b].done) return;                     // (a converged registration: its last iteration's outputs and counts stay)
+    const uint32_t b = blockIdx.y, i = blockIdx.x * RECIPROCAL_BLOCK + threadIdx.x;
+    if (icp_pass_leaves (p, b)) return;
     const float max_gap = __uint_as_float (gap[0]);
     const float gap2 = (float) ((double) max_gap * (double) max_gap);
     const bool guard = rst[b].RECIPROCAL_GUARD != 0u;
@@ -87,33 +84,25 @@ __global__ __launch_bounds__ (RECIPROCAL_BLOCK) void k_reciprocal (icp_params p,
     if (i < p.m) {
         const size_t o = (size_t) b * p.m, e = o + i;
         const uint32_t j = p.nn_id[e].id;
-        cand = p.PF[e].w != 0.f && j < p.m;
+        cand = icp_pair_candidate (p.PF[e].w, j, p.m);
         if (cand) {
             if (!guard) {
                 const uint32_t i2 = rev[o + j].id;           // (j < m: inside the registration's rows)
                 exact = i2 == i;
                 if (!exact && max_gap > 0.f && i2 < p.m) {
                     const float4 a = p.PM[e], c = p.PM[o + i2];
-                    const float gx = a.x - c.x, gy = a.y - c.y, gz = a.z - c.z;
-                    const float g = (gx * gx + gy * gy) + gz * gz;
+                    const float g = icp_pair_geo (c, a);     // (of a - c)
                     near = isfinite (g) && g <= gap2;
                 }
             }
-            if (!exact && !near) reinterpret_cast<float *> (p.PF + e)[3] = 0.f;
+            if (!exact && !near) icp_pair_reject (p.PF + e);
         }
     }
-    const uint32_t wn = (uint32_t) __popcll (__ballot (cand)), we = (uint32_t) __popcll (__ballot (exact)), wr = (uint32_t) __popcll (__ballot (near));
-    if ((t & 63u) == 0u) { s_cnt[t >> 6][0] = wn; s_cnt[t >> 6][1] = we; s_cnt[t >> 6][2] = wr; }
-    __syncthreads ();
-    if (t == 0u) {
-        uint32_t sn = 0u, se = 0u, sr = 0u;
-#pragma unroll
-        for (uint32_t v = 0; v < RECIPROCAL_BLOCK / 64u; ++v) { sn += s_cnt[v][0]; se += s_cnt[v][1]; sr += s_cnt[v][2]; }
-        uint32_t *out = result + 4u * b;
-        if (sn) __hip_atomic_fetch_add (out + 0, sn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (se) __hip_atomic_fetch_add (out + 1, se, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (sr) __hip_atomic_fetch_add (out + 2, sr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (se + sr) __hip_atomic_fetch_add (out + 3, se + sr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t wave[3] = { (uint32_t) __popcll (__ballot (cand)), (uint32_t) __popcll (__ballot (exact)), (uint32_t) __popcll (__ballot (near)) };
+    uint32_t sum[3];
+    if (pair_block_counts<3, RECIPROCAL_BLOCK> (wave, sum)) {
+        const uint32_t words[4] = { sum[0], sum[1], sum[2], sum[1] + sum[2] };       // (n, exact, near, accepted)
+        pair_counts_add (result + 4u * b, words);
     }
 }
 
@@ -147,11 +136,12 @@ void icp_launch_reciprocal (const icp_params &p, hipStream_t s, const icp_recipr
         std::fprintf (stderr, "icp_amd: reciprocal correspondences are on and the launch has no moving set\n");
         std::abort ();
     }
-    hipLaunchKernelGGL (k_reciprocal_state, dim3 (p.batch), dim3 (64), 0, s, p, rs->st, icp_reciprocal_area (p));
+    const icp_area_words w = icp_words (p, ICP_AREA_RECIPROCAL);
+    hipLaunchKernelGGL (k_reciprocal_state, dim3 (p.batch), dim3 (64), 0, s, p, rs->st, w.result);
     // (the back search's first search of a registration — k == 0, copied — seeds its pruning from the query's own grid cell, like the forward
     // one; later ones from the rule's own rid buffer, any content of which is a valid seed: pruning is exact)
     icp_launch_search (reciprocal_params (p, *rs), s);
     const dim3 grid ((p.m + RECIPROCAL_BLOCK - 1u) / RECIPROCAL_BLOCK, p.batch);
     hipLaunchKernelGGL (k_reciprocal, grid, dim3 (RECIPROCAL_BLOCK), 0, s, p, (const icp_dist_id *) rs->nn_id, (const icp_reg_state *) rs->st,
-                        icp_reciprocal_area (p), (const uint32_t *) icp_reciprocal_gap (p));
+                        w.result, (const uint32_t *) w.settings);
 }

@@ -28,7 +28,7 @@ __global__ __launch_bounds__ (256) void k_plane_moments_robust (icp_params p, co
 
 void icp_launch_robust_apply (const icp_params &p, hipStream_t s)
 {
-    const uint32_t *area = icp_trim_area (p);
+    const uint32_t *area = icp_words (p, ICP_AREA_TRIM).result;
     if (p.fused) hipLaunchKernelGGL (k_trim_apply_robust<true>, dim3 (p.nb, p.batch), dim3 (64), 0, s, p, area, icp_tpr_magic (p.side));
     else hipLaunchKernelGGL (k_trim_apply_robust<false>, dim3 (2 * p.nwg, p.batch), dim3 (64), 0, s, p, area, icp_tpr_magic (p.side));
 }

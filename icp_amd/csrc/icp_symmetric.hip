@@ -27,7 +27,7 @@ __global__ __launch_bounds__ (256) void k_sym_moments (icp_params p, const float
 #pragma unroll
     for (int k = 0; k < 9; ++k) Rf[k] = p.st[b].R[k];
     // (a converged registration: asked behind the pair's loads — in front of them the flag's round trip would come first)
-    if (p.check && p.st[b].done) return;                 // (block-uniform)
+    if (icp_pass_leaves (p, b)) return;                  // (block-uniform)
     double v[ICP_P2PL_TERMS];
 #pragma unroll
     for (int t = 0; t < (int) ICP_P2PL_TERMS; ++t) v[t] = 0.0;

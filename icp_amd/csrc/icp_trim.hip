@@ -87,7 +87,7 @@ __global__ __launch_bounds__ (1024) void k_trim_select (icp_params p, uint32_t *
     constexpr int NT = 1024, KPT = (int) ICP_TRIM_ONE_BLOCK_MAX / NT;
     __shared__ uint32_t s_hist[ICP_TRIM_BINS], s_wsum[NT / 64], s_pick[3];
     const uint32_t b = blockIdx.y, t = threadIdx.x, m = p.m;
-    if (p.check && p.st[b].done) return;                     // (a converged registration: its last iteration's outputs stay)
+    if (icp_pass_leaves (p, b)) return;
     const float4 *PF = p.PF + (size_t) b * m, *PM = p.PM + (size_t) b * m;
     uint32_t key[KPT], cnt = 0u;
 #pragma unroll
@@ -132,7 +132,7 @@ __global__ __launch_bounds__ (256) void k_trim_select_pass (icp_params p, uint32
     __shared__ uint32_t s_hist[ICP_TRIM_BINS], s_wsum[NT / 64], s_pick[3];
     __shared__ uint32_t s_last;
     const uint32_t b = blockIdx.y, t = threadIdx.x, m = p.m, B = p.batch;
-    if (p.check && p.st[b].done) return;
+    if (icp_pass_leaves (p, b)) return;
     uint32_t *out = area + 4u * b, *sel = area + 4u * B + 4u * b, *hist = area + 8u * B + (size_t) ICP_TRIM_BINS * b;
     uint32_t *keys = area + (8u + ICP_TRIM_BINS) * (size_t) B + (size_t) b * m;
     if (D > 0 && out[1] == 0u) return;                       // (no candidate: pass 0 has said so)
@@ -198,7 +198,7 @@ __global__ __launch_bounds__ (64) void k_trim_apply (icp_params p, const uint32_
 // the selection: one workgroup's up to ICP_TRIM_ONE_BLOCK_MAX pairs per registration, three multi-workgroup passes beyond (launches: icp_route::select)
 void icp_launch_trim_select (const icp_params &p, hipStream_t s, uint32_t launches)
 {
-    uint32_t *area = icp_trim_area (p);
+    uint32_t *area = icp_words (p, ICP_AREA_TRIM).result;
     if (launches == 1u) { hipLaunchKernelGGL (k_trim_select, dim3 (1, p.batch), dim3 (1024), 0, s, p, area); return; }
     const dim3 grid ((p.m + 2047u) / 2048u, p.batch);
     hipLaunchKernelGGL (k_trim_select_pass<0>, grid, dim3 (256), 0, s, p, area);
@@ -208,7 +208,7 @@ void icp_launch_trim_select (const icp_params &p, hipStream_t s, uint32_t launch
 
 void icp_launch_trim_apply (const icp_params &p, hipStream_t s)
 {
-    const uint32_t *area = icp_trim_area (p);
+    const uint32_t *area = icp_words (p, ICP_AREA_TRIM).result;
     if (p.fused) hipLaunchKernelGGL (k_trim_apply<true>, dim3 (p.nb, p.batch), dim3 (64), 0, s, p, area, icp_tpr_magic (p.side));
     else hipLaunchKernelGGL (k_trim_apply<false>, dim3 (2 * p.nwg, p.batch), dim3 (64), 0, s, p, area, icp_tpr_magic (p.side));
 }

@@ -4,14 +4,14 @@
 // point-to-point robust loss), so that each translation unit keeps its own kernel list.
 //
 // One acceptance rule for both: a pair is accepted iff it is a candidate and, with trimming on, among the K closest (key <= t, K != 0).
-// icp_trimming (p) is a uniform test of the kernel argument p.reject; trimming's words (area = icp_trim_area (p), always) are read under
+// icp_trimming (p) is a uniform test of the kernel argument p.reject; trimming's words (area = ICP_AREA_TRIM's, always) are read under
 // it only.  With trimming off the pass accepts every candidate the passes in front of it left: nobody forges words for it.
 //
-// The key of a pair is the bit pattern of its geo = (ex - f0)^2 + (ey - f1)^2 + (ez - f2)^2 in fp32, summed in that order (the
-// translation units are built with -ffp-contract=off): a non-negative float orders as its bits do as uint32.  A pair that is no
-// candidate — weight 0, geo not finite, no query — gets the key ~0u, above every candidate's.
+// The key of a pair is the bit pattern of its geo (icp_pair_geo, icp_pair_rule.h) in fp32: a non-negative float orders as its bits
+// do as uint32.  A pair that is no candidate — weight 0, geo not finite, no query — gets the key ~0u, above every candidate's.
 #pragma once
 #include "icp_search.h"
+#include "icp_pair_rule.h"
 
 namespace {
 
@@ -20,8 +20,7 @@ constexpr uint32_t TRIM_NONE = 0xFFFFFFFFu;     // the key of a pair that is no 
 __device__ __forceinline__ uint32_t trim_key (float4 f, float4 q)
 {
     if (f.w == 0.f) return TRIM_NONE;
-    const float gx = q.x - f.x, gy = q.y - f.y, gz = q.z - f.z;
-    const float geo = (gx * gx + gy * gy) + gz * gz;
+    const float geo = icp_pair_geo (f, q);
     return geo < __builtin_inff () ? __float_as_uint (geo) : TRIM_NONE;      // (NaN and +inf: no candidate)
 }
 
@@ -40,7 +39,7 @@ __device__ __forceinline__ void trim_apply (icp_params p, const uint32_t *area, 
     __shared__ double s_mom[FUSED ? ICP_NMOM : 1][64];
     __shared__ float s_w[64];
     const uint32_t b = blockIdx.y, lane = threadIdx.x, m = p.m;
-    if (p.check && p.st[b].done) return;
+    if (icp_pass_leaves (p, b)) return;
     const uint32_t i = FUSED ? fused_query_index (m, p.side, tpr_magic, blockIdx.x, lane) : (blockIdx.x >> 1) * 128u + 2u * lane + (blockIdx.x & 1u);
     const bool v = i < m;
     float4 f = make_float4 (0.f, 0.f, 0.f, 0.f), q = f;
@@ -56,7 +55,7 @@ __device__ __forceinline__ void trim_apply (icp_params p, const uint32_t *area, 
         acc = wr != 0.f;
         f.w = wr;
     } else {
-        if (v && f.w != 0.f && !acc) reinterpret_cast<float *> (p.PF + (size_t) b * m + i)[3] = 0.f;
+        if (v && f.w != 0.f && !acc) icp_pair_reject (p.PF + (size_t) b * m + i);
     }
     if constexpr (FUSED) {
         // (ks_epilogue's products, term for term)

@@ -21,10 +21,10 @@
 // icp_init (which fills the table with 0xFF), buildRBC, reset_transform or a new graph finds it as the last resolve pass left it.  No
 // memset, no extra launch, no second table.
 //
-// The result words of a registration, [batch][2] uint32 (icp_unique_area): (n, winners), ICP_MEM_UNIQUE as it is read.  k_unique_claim's
-// first thread resets them, k_unique_resolve's blocks add their counts.  Nothing else reads them: the apply pass behind the rule
-// accepts every pair that still has a weight (icp_trim_apply.h).
-#include "icp_trim_apply.h"             // (TRIM_NONE, trim_key)
+// The result words of a registration, [batch][2] uint32 (ICP_AREA_UNIQUE): (n, winners), ICP_MEM_UNIQUE as it is read.  k_unique_claim's
+// first thread resets them, k_unique_resolve's blocks add their counts (pair_counts_add, icp_pair_rule.h).  Nothing else reads them:
+// the apply pass behind the rule accepts every pair that still has a weight (icp_trim_apply.h).
+#include "icp_trim_apply.h"             // (TRIM_NONE, trim_key; icp_pair_rule.h)
 
 namespace {
 
@@ -37,7 +37,7 @@ __device__ __forceinline__ unsigned long long unique_key (const icp_params &p, u
     const size_t e = (size_t) b * p.m + i;
     const uint32_t k = trim_key (p.PF[e], p.PM[e]);
     *id = p.nn_id[e].id;
-    // (an id is an index into F; a word that is not would be no claim, never a store outside the table)
+    // (icp_pair_candidate, with a finite geo: an id is an index into F; a word that is not would be no claim, never a store outside the table)
     return (k != TRIM_NONE && *id < p.m) ? ((unsigned long long) k << 32) | i : UNIQUE_FREE;
 }
 
@@ -47,7 +47,7 @@ __device__ __forceinline__ unsigned long long unique_key (const icp_params &p, u
 __global__ __launch_bounds__ (UNIQUE_BLOCK) void k_unique_claim (icp_params p, unsigned long long *claims, uint32_t *area)
 {
     const uint32_t b = blockIdx.y, i = blockIdx.x * UNIQUE_BLOCK + threadIdx.x;
-    if (p.check && p.st[b].done) return;                     // (a converged registration: its last iteration's outputs stay)
+    if (icp_pass_leaves (p, b)) return;
     if (i == 0u) { uint32_t *out = area + 2u * b; out[0] = 0u; out[1] = 0u; }
     if (i >= p.m) return;
     uint32_t id;
@@ -60,9 +60,8 @@ __global__ __launch_bounds__ (UNIQUE_BLOCK) void k_unique_claim (icp_params p, u
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__ (UNIQUE_BLOCK) void k_unique_resolve (icp_params p, unsigned long long *claims, uint32_t *area)
 {
-    __shared__ uint32_t s_n[UNIQUE_BLOCK / 64u], s_win[UNIQUE_BLOCK / 64u];
-    const uint32_t b = blockIdx.y, t = threadIdx.x, i = blockIdx.x * UNIQUE_BLOCK + t;
-    if (p.check && p.st[b].done) return;
+    const uint32_t b = blockIdx.y, i = blockIdx.x * UNIQUE_BLOCK + threadIdx.x;
+    if (icp_pass_leaves (p, b)) return;
     bool cand = false, win = false;
     if (i < p.m) {
         uint32_t id;
@@ -72,20 +71,12 @@ __global__ __launch_bounds__ (UNIQUE_BLOCK) void k_unique_resolve (icp_params p,
             unsigned long long *slot = claims + (size_t) b * p.m + id;
             win = __hip_atomic_load (slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == key;
             if (win) __hip_atomic_store (slot, UNIQUE_FREE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // (clean for the next iteration)
-            else reinterpret_cast<float *> (p.PF + (size_t) b * p.m + i)[3] = 0.f;
+            else icp_pair_reject (p.PF + (size_t) b * p.m + i);
         }
     }
-    const uint32_t n = (uint32_t) __popcll (__ballot (cand)), w = (uint32_t) __popcll (__ballot (win));
-    if ((t & 63u) == 0u) { s_n[t >> 6] = n; s_win[t >> 6] = w; }
-    __syncthreads ();
-    if (t == 0u) {
-        uint32_t sn = 0u, sw = 0u;
-#pragma unroll
-        for (uint32_t v = 0; v < UNIQUE_BLOCK / 64u; ++v) { sn += s_n[v]; sw += s_win[v]; }
-        uint32_t *out = area + 2u * b;
-        if (sn) __hip_atomic_fetch_add (out + 0, sn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (sw) __hip_atomic_fetch_add (out + 1, sw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    const uint32_t wave[2] = { (uint32_t) __popcll (__ballot (cand)), (uint32_t) __popcll (__ballot (win)) };
+    uint32_t sum[2];
+    if (pair_block_counts<2, UNIQUE_BLOCK> (wave, sum)) pair_counts_add (area + 2u * b, sum);
 }
 
 }  // namespace
@@ -94,7 +85,7 @@ void icp_launch_unique (const icp_params &p, hipStream_t s)
 {
     const dim3 grid ((p.m + UNIQUE_BLOCK - 1u) / UNIQUE_BLOCK, p.batch);
     unsigned long long *claims = icp_unique_claims (p);
-    uint32_t *area = icp_unique_area (p);
+    uint32_t *area = icp_words (p, ICP_AREA_UNIQUE).result;
     hipLaunchKernelGGL (k_unique_claim, grid, dim3 (UNIQUE_BLOCK), 0, s, p, claims, area);
     hipLaunchKernelGGL (k_unique_resolve, grid, dim3 (UNIQUE_BLOCK), 0, s, p, claims, area);
 }

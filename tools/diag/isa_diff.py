@@ -6,6 +6,7 @@ listed too.  Whole instruction lists are compared (only the function's number in
 it follows the order of instantiation) — what a refactor that must not change generated code is checked with.  Needs only the compiler,
 no GPU.
     python tools/diag/isa_diff.py OTHER_TREE [sources..] [-D...]      # exit status 1 when anything differs
+Without sources: every .hip unit of the Makefile's SRC.
 """
 import difflib
 import os
@@ -16,7 +17,12 @@ from concurrent.futures import ThreadPoolExecutor
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from kernel_resources import ROOT, demangle, kernel_isa  # noqa: E402
 
-SOURCES = ["icp_amd/csrc/icp_kernels.hip", "icp_amd/csrc/icp_search_dense.hip", "icp_amd/csrc/icp_search_rej.hip", "icp_amd/csrc/icp_build.hip"]
+
+def makefile_sources():
+    """The .hip translation units of the Makefile's SRC, in its order."""
+    with open(os.path.join(ROOT, "Makefile")) as f:
+        src = re.search(r"^SRC\s*:=\s*(.*)$", f.read(), re.M).group(1)
+    return [s for s in src.split() if s.endswith(".hip")]
 
 
 def normalise(lines):
@@ -62,7 +68,7 @@ def main(argv):
     if not pos:
         print(__doc__)
         return 2
-    other, sources = os.path.abspath(pos[0]), pos[1:] or SOURCES
+    other, sources = os.path.abspath(pos[0]), pos[1:] or makefile_sources()
     bad = 0
     for src in sources:
         rows = compare(src, other, flags)
