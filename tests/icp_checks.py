@@ -9,7 +9,8 @@ pytest rewrites `assert` only in the modules it collects, so every assert here c
 4. the plane family (point-to-plane, colored, plane-to-plane, symmetric, their robust forms): a `restate` callable wraps the metric's
    float64 restatement, check_last compares the last iteration with it;
 5. the route of an iteration: every opt-in pass composed (composed_rule; bit 4 of a mask is the reciprocal rule, fed the oracle's back
-   search: back_at), the step checks against it, and the ICP_PAIRS_LAST_ITERATION set against it (check_route_pairs);
+   search: back_at), the step checks against it, and the ICP_PAIRS_LAST_ITERATION set against it (check_route_pairs); the same route
+   headed by the projection in the search's place (PROJ_ROUTE_SCENES, ProjectiveWant: projective_ref.project is the expectation);
 6. the scenes of the correspondence sets in every search layout (LAYOUT_CASES, layout_scene), and the same scenes with the reciprocal rule
    between their rejection and their trimming (layout_reciprocal);
 7. the reciprocal rule's own scenes: a registration that is done at once beside two that are not (converged_pairs), a moving frame with
@@ -374,8 +375,14 @@ def expected_pieces(oracle, F, M, T, nn_id, side, fused, weighted, rot, power_fa
 
 
 def check_search(engine, g, want, b=0):
-    """The engine's correspondences, distances and nearest representatives against the oracle's (nn_id, rid)."""
+    """The engine's correspondences, distances and nearest representatives against the oracle's (nn_id, rid).  want a ProjectiveWant
+    (the projection heads the route): ICP_MEM_NN_ID — the misses' 0xFFFFFFFF included —, the matched fixed points of ICP_MEM_NN,
+    ICP_MEM_QT and the words of ICP_MEM_PROJECTIVE against projective_ref.project's."""
     Mem = engine.Memory
+    if isinstance(want, ProjectiveWant):
+        got = check_projective_outputs(engine, g, want.res, b)
+        assert got[1] > 0, "ICP_MEM_PROJECTIVE %r: no hit" % (got,)
+        return
     nn_id, rid = want
     gn = g.read(Mem.NN_ID, batch_index=b)
     assert np.array_equal(gn["id"], nn_id["id"]), "correspondence ids: %d differ" % np.count_nonzero(gn["id"] != nn_id["id"])
@@ -602,6 +609,10 @@ def check_last(engine, g, restate, T0, R0, k0, b=0, steps=1, weights=None):
     the device's own weight column.  Returns the system."""
     Mem = engine.Memory
     PF, PM, ids = g.read(Mem.NN, b), g.read(Mem.QT, b), g.read(Mem.NN_ID, b)["id"]
+    miss = ids >= PF.shape[0]                                     # (a miss of the projection: id 0xFFFFFFFF, the record of a rejected pair)
+    if miss.any():
+        assert not PF[miss].any(), "a pair without a fixed point has the record (0, 0, 0, +0) (registration %d)" % b
+        ids = np.where(miss, np.uint32(0), ids)                   # (the restatements index their tables with it; its weight is +0)
     if weights is not None:
         PF = PF.copy()
         PF[:, 3] = weights
@@ -790,7 +801,126 @@ ROUTE_SCENES = {"30": (30, 4, 0x20C7E, 1.0, (4.0, -3.0, 2.0)), "150": (150, 4, 0
 ROUTE_BATCH = ("batch0", "batch1", "batch2")                     # one handle, one set of options: batch0's, proven on each of the three
 ROUTE_KEEP = 0.75
 ROUTE_GAP_KEEP = 0.7
-RouteScene = collections.namedtuple("RouteScene", "side nr F M T want R0 PF PM NF NM max_dist min_cos scale max_gap back")
+RouteScene = collections.namedtuple("RouteScene", "side nr F M T want R0 PF PM NF NM max_dist min_cos scale max_gap back projective",
+                                    defaults=(None,))
+
+# The projection at the head of a route (icp_set_projective in the RBC search's place): the same pairs of frames, the expectation of a
+# step projective_ref.project at the step's T.  name -> the scene of ROUTE_SCENES it shares its frames with, or a pair of its own (two
+# more at side 150 for the batch of three: 3 x 22500 points is also a shape the kernel serves in four rounds per block).
+PROJ_ROUTE_SCENES = {"p30": "30", "p150": "150", "p150b1": (150, 4, 0x20C84, 1.2, (6.0, -2.0, 3.0)), "p150b2": (150, 4, 0x20C85, 0.8, (3.0, -4.0, 1.0))}
+PROJ_ROUTE_BATCH = ("p150", "p150b1", "p150b2")                  # one handle, one set of options: p150's, proven on each of the three
+PROJ_ROUTE_RADIUS = 1                                            # (r = 0 leaves one-to-one nothing to remove: a cell has one query or two)
+ProjectiveWant = collections.namedtuple("ProjectiveWant", "nn_id res")
+ProjectiveWant.__doc__ = """The expectation of a step behind the projection, in the place of the oracle's (nn_id, rid): nn_id = the rule's
+pairs with the misses clipped (id 0, dist +inf: what every rule and the oracle's pieces index F with; a miss weighs nothing), res =
+projective_ref.project's Result."""
+
+
+def projective_want(F, M, T, side, r=PROJ_ROUTE_RADIUS):
+    """projective_ref.project at T with the grid's own intrinsics, WEIGHTED, as a ProjectiveWant."""
+    import icp_amd as engine
+    import projective_ref
+    from oracle import oracle
+    res = projective_ref.project(oracle, F, M, T, side, engine.grid_intrinsics(side), r, True)
+    nn_id = projective_ref.clipped(res.nn_id, res.miss)
+    for a in (nn_id,) + tuple(res):
+        a.flags.writeable = False
+    return ProjectiveWant(nn_id, res)
+
+
+def projective_handle(engine, m, nr, fused, weighted, rot, power_fast, gw, intr, r, batch=1, **options):
+    """make_handle, then the projection (grid width gw, intrinsics intr, radius r) on the handle."""
+    g = make_handle(engine, m, nr, fused, weighted, rot, power_fast, batch, **options)
+    g.set_projective(gw, *intr, radius=r)
+    return g
+
+
+def check_projective_outputs(engine, g, res, b=0):
+    """NN_ID (ids — a miss's 0xFFFFFFFF included —, distance bits), the matched fixed points, QT and ICP_MEM_PROJECTIVE of registration b
+    against the restatement (res: projective_ref.project's Result).  Returns the words."""
+    Mem = engine.Memory
+    gn = g.read(Mem.NN_ID, batch_index=b)
+    assert np.array_equal(gn["id"], res.nn_id["id"]), "projective ids: %d differ" % np.count_nonzero(gn["id"] != res.nn_id["id"])
+    assert_bits(gn["dist"], res.nn_id["dist"], "projective distances")
+    assert_bits(g.read(Mem.NN, batch_index=b)[:, :3], res.NN[:, :3], "matched fixed points")
+    assert_bits_nan(g.read(Mem.QT, batch_index=b), res.QT, "transformed moving points and distances")
+    got = assert_words(engine, g, "PROJECTIVE", res.counts, b)
+    assert got[0] == got[1] + got[2] + got[3], "ICP_MEM_PROJECTIVE %r: hits + outside + empty is not n" % (got,)
+    return got
+
+
+def check_projective_step(engine, oracle, g, res, F, M, T, side, fused, weighted, rot, power_fast, b=0, zero=None, pieces=None):
+    """check_projective_outputs, then W, NN.w, sum W, means, S and Tk against the oracle's pieces fed the rule's pairs.  zero: further
+    rows that weigh nothing (icp_set_rejection's distance test); pieces: projective_ref.pieces of these arguments where the caller
+    has them already."""
+    import projective_ref
+    Mem = engine.Memory
+    got = check_projective_outputs(engine, g, res, b)
+    W, sw, means, S, Tk = pieces or projective_ref.pieces(oracle, res, F, M, T, side, fused, weighted, rot, power_fast, zero)
+    gW = g.read(Mem.W, batch_index=b)
+    assert_bits(gW, W, "weights")
+    nonzero = np.count_nonzero(np.ascontiguousarray(gW[res.miss]).view(np.uint32))
+    assert nonzero == 0, "a miss has the weight +0: %d have not" % nonzero
+    assert_bits(g.read(Mem.NN, batch_index=b)[:, 3], W, "the NN output's weights")
+    assert_bits(g.read(Mem.SUM_W, batch_index=b), np.array([sw]), "sum of weights")
+    assert_bits(g.read(Mem.MEANS, batch_index=b), means, "means")
+    assert_bits(g.read(Mem.S, batch_index=b), S, "S")
+    assert_bits_nan(g.read(Mem.TK, batch_index=b), Tk, "Tk")
+    return got
+
+
+def route_want(oracle, s, T):
+    """The expectation of a step of the scene s from T: the oracle's search, or the projection's rule where it heads the route."""
+    if s.projective is not None:
+        return projective_want(s.F, s.M, T, s.side, s.projective[5])
+    return oracle_search(oracle, s.F, s.M, T, s.nr)
+
+
+def route_pairs_of(oracle, s, want, T):
+    """(PF, PM) of the expectation `want` at T: the matched fixed points and the transformed moving set."""
+    if s.projective is not None:
+        return want.res.NN, want.res.QT
+    return s.F[want[0]["id"]], oracle.transform_q(s.M, T)
+
+
+def _route_frames(side, seed, rot_deg, t):
+    import icp_amd as engine
+    F, M = engine.synth_pair(side, seed=seed, rot_deg=rot_deg, t=t)
+    F = engine.punch_holes(F, side, side, engine.HOLES_CONTIGUOUS, 0.10, True, seed=seed + 101)
+    M = engine.punch_holes(M, side, side, engine.HOLES_CONTIGUOUS, 0.10, True, seed=seed + 202)
+    return F, M
+
+
+def _projective_route_scene(name):
+    """The scene `name` of PROJ_ROUTE_SCENES: T = _t0 (), the rule's pairs at r = PROJ_ROUTE_RADIUS, and the options: max_dist the 0.88
+    quantile of the hits' own geometric distances (the RBC scene's max_dist rejects more than half of "150" at r <= 1), min_cos and
+    the scales those of the scene it shares its frames with.  tests/test_route_rule_cpu.py proves that every stage bites under them."""
+    import icp_amd as engine
+    from oracle import oracle
+    spec = PROJ_ROUTE_SCENES[name]
+    if isinstance(spec, str):
+        base = route_scene(spec)
+        side, nr, F, M = base.side, base.nr, base.F, base.M
+    else:
+        side, nr = spec[:2]
+        F, M = _route_frames(side, *spec[2:])
+    T = _t0()
+    for a in (F, M, T):
+        a.flags.writeable = False
+    want = projective_want(F, M, T, side)
+    PF, PM = want.res.NN, want.res.QT
+    if name in PROJ_ROUTE_BATCH[1:]:
+        s0 = route_scene(PROJ_ROUTE_BATCH[0])
+        max_dist, min_cos, scale = s0.max_dist, s0.min_cos, s0.scale
+    else:
+        geo = geo_of(PF, PM)[~want.res.miss]
+        max_dist, min_cos, scale = float(np.float32(np.sqrt(np.quantile(geo.astype(np.float64), 0.88)))), base.min_cos, base.scale
+    s = RouteScene(side, nr, F, M, T, want, oracle.quat_to_rot(T[:4]).ravel(), PF, PM, p2pl_ref.grid_normals(F, side),
+                   p2pl_ref.grid_normals(M, side), max_dist, min_cos, scale, None, None,
+                   (side,) + tuple(engine.grid_intrinsics(side)) + (PROJ_ROUTE_RADIUS,))
+    for a in (s.R0, s.NF, s.NM):
+        a.flags.writeable = False
+    return s
 
 
 @functools.lru_cache(maxsize=None)
@@ -803,12 +933,11 @@ def route_scene(name):
     candidates behind the search's rejection, the filter off (reciprocal_ref.pick_gap on `back`, the oracle's back search at T).  A
     strictly reciprocal set (max_gap = 0) is one to one already and would leave one-to-one nothing to remove
     (tests/test_route_rule_cpu.py).  keep is ROUTE_KEEP."""
-    import icp_amd as engine
     from oracle import oracle
+    if name in PROJ_ROUTE_SCENES:
+        return _projective_route_scene(name)
     side, nr, seed, rot_deg, t = ROUTE_SCENES[name]
-    F, M = engine.synth_pair(side, seed=seed, rot_deg=rot_deg, t=t)
-    F = engine.punch_holes(F, side, side, engine.HOLES_CONTIGUOUS, 0.10, True, seed=seed + 101)
-    M = engine.punch_holes(M, side, side, engine.HOLES_CONTIGUOUS, 0.10, True, seed=seed + 202)
+    F, M = _route_frames(side, seed, rot_deg, t)
     T = _t0()
     want = oracle_search(oracle, F, M, T, nr)
     for a in (F, M, T):
@@ -850,9 +979,17 @@ ROUTE_METRICS = ("p2pl", "colored", "gicp", "sym")
 GICP_EPS = 1e-3
 
 
-def route_handle(engine, side, nr, o, metric="p2p", fused=None, batch=1, it=40):
+def route_handle(engine, side, nr, o, metric="p2p", fused=None, batch=1, it=40, projective=None):
     """A handle with the options o on.  metric "p2p": explicit modes, fused + the squared power start or reference order + the
-    literal one; a plane metric of ROUTE_METRICS (mu = 0.05, kappa = 1000, epsilon = GICP_EPS): the handle's default modes."""
+    literal one; a plane metric of ROUTE_METRICS (mu = 0.05, kappa = 1000, epsilon = GICP_EPS): the handle's default modes.
+    projective: (grid width, fx, fy, cx, cy, radius) — a RouteScene's — puts the projection in the search's place."""
+    g = _route_handle(engine, side, nr, o, metric, fused, batch, it)
+    if projective is not None:
+        g.set_projective(*projective[:5], radius=projective[5])
+    return g
+
+
+def _route_handle(engine, side, nr, o, metric, fused, batch, it):
     loss = (o.loss, o.scale) if o.loss is not None else None
     if metric == "p2p":
         g = make_handle(engine, side * side, nr, fused, o.weighted, POWER, fused, batch, it, rejection=(o.invalid, o.max_dist),

@@ -26,40 +26,7 @@ F32 = np.float32
 EINVAL, ESTATE = 1, 4
 
 
-def make_handle(engine, m, nr, fused, weighted, rot, power_fast, gw, intr, r, batch=1, **options):
-    """icp_checks.make_handle, then the rule on the handle."""
-    g = icp_checks.make_handle(engine, m, nr, fused, weighted, rot, power_fast, batch, **options)
-    g.set_projective(gw, *intr, radius=r)
-    return g
-
-
-def check_outputs(engine, g, res, b=0):
-    """NN_ID (ids, distance bits), the matched fixed points, QT and ICP_MEM_PROJECTIVE against the restatement."""
-    Mem = engine.Memory
-    gn = g.read(Mem.NN_ID, batch_index=b)
-    assert np.array_equal(gn["id"], res.nn_id["id"]), "ids: %d differ" % np.count_nonzero(gn["id"] != res.nn_id["id"])
-    assert_bits(gn["dist"], res.nn_id["dist"], "distances")
-    assert_bits(g.read(Mem.NN, batch_index=b)[:, :3], res.NN[:, :3], "matched fixed points")
-    assert_bits_nan(g.read(Mem.QT, batch_index=b), res.QT, "transformed moving points and distances")
-    got = assert_words(engine, g, "PROJECTIVE", res.counts, b)
-    assert got[0] == got[1] + got[2] + got[3], got
-    return got
-
-
-def check_step(engine, oracle, g, res, F, M, T, side, fused, weighted, rot, power_fast, b=0):
-    """The outputs, then W, NN.w, sum W, means, S and Tk against the oracle's pieces fed the rule's pairs."""
-    Mem = engine.Memory
-    got = check_outputs(engine, g, res, b)
-    W, sw, means, S, Tk = ref.pieces(oracle, res, F, M, T, side, fused, weighted, rot, power_fast)
-    gW = g.read(Mem.W, batch_index=b)
-    assert_bits(gW, W, "weights")
-    assert np.count_nonzero(np.ascontiguousarray(gW[res.miss]).view(np.uint32)) == 0, "a miss has the weight +0"
-    assert_bits(g.read(Mem.NN, batch_index=b)[:, 3], W, "the NN output's weights")
-    assert_bits(g.read(Mem.SUM_W, batch_index=b), np.array([sw]), "sum of weights")
-    assert_bits(g.read(Mem.MEANS, batch_index=b), means, "means")
-    assert_bits(g.read(Mem.S, batch_index=b), S, "S")
-    assert_bits_nan(g.read(Mem.TK, batch_index=b), Tk, "Tk")
-    return got
+make_handle, check_outputs, check_step = icp_checks.projective_handle, icp_checks.check_projective_outputs, icp_checks.check_projective_step
 
 
 # ---- 1. arguments

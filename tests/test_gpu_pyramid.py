@@ -290,17 +290,26 @@ def _opt_symmetric(engine, h, side_l):
     h.set_symmetric(True)
 
 
-@pytest.mark.parametrize("case", ["point_to_plane_rejection_trimming", "symmetric"])
+def _opt_projective(engine, h, side_l):
+    """Point-to-point behind the projection, r = 1, the level's own intrinsics under the MEAN reduction."""
+    from icp_amd import register
+    h.set_projective(side_l, *register.level_intrinsics(engine.grid_intrinsics(128), 128 // side_l), radius=1)
+
+
+@pytest.mark.parametrize("case", ["point_to_plane_rejection_trimming", "symmetric", "projective"])
 def test_options_per_level_match_a_chain_made_by_hand(engine, case):
-    """Every level's own options (grid widths per level) take part: T, the plane system and the moving normals of every level equal
-    those of separate plain handles fed pyramid_ref's clouds, T handed on through the host.  The moving set is written a second time
-    after buildRBC: with grid normals the levels' moving normals must follow the device-side write as they follow icp_write."""
-    opt = _opt_point_to_plane if case.startswith("point") else _opt_symmetric
+    """Every level's own options (grid widths per level, the projection's intrinsics per level) take part: T, the plane system, the
+    moving normals, the pairs and the projection's words of every level equal those of separate plain handles fed pyramid_ref's clouds,
+    T handed on through the host.  The moving set is written a second time after buildRBC: with grid normals the levels' moving normals
+    must follow the device-side write as they follow icp_write."""
+    opt = {"point": _opt_point_to_plane, "symme": _opt_symmetric, "proje": _opt_projective}[case[:5]]
     F, M = _clouds(engine, 128, "blobs30")
     M0 = _clouds(engine, 128, "clean")[1]
     nr, its = (256, 64, 64), [3, 3, 3]
     Fs, Ms, M0s = PR.build(F, 128, 3), PR.build(M, 128, 3), PR.build(M0, 128, 3)
-    mems = (engine.Memory.T, engine.Memory.PLANE_SYSTEM, engine.Memory.NORMALS_M)
+    mems = (engine.Memory.T, engine.Memory.NN_ID, engine.Memory.QT, engine.Memory.PROJECTIVE)
+    if case != "projective":
+        mems += (engine.Memory.PLANE_SYSTEM, engine.Memory.NORMALS_M)
     want = [None] * 3
     T = np.array([0, 0, 0, 1, 0, 0, 0, 1], F32)
     for l in (2, 1, 0):
@@ -333,9 +342,51 @@ def test_options_per_level_match_a_chain_made_by_hand(engine, case):
             for mem in mems:
                 got = p.level(l).read(mem)
                 assert np.array_equal(got.view(np.uint8), want[l][mem].view(np.uint8)), "%s level %d mem %d" % (case, l, mem)
-        assert np.any(want[0][engine.Memory.PLANE_SYSTEM] != 0)
+        if case == "projective":
+            for l in range(3):
+                n, hits, outside, empty = (int(x) for x in want[l][engine.Memory.PROJECTIVE])
+                assert n == hits + outside + empty and 2 * hits >= n and outside > 0 and empty > 0, (l, n, hits, outside, empty)
+        else:
+            assert np.any(want[0][engine.Memory.PLANE_SYSTEM] != 0)
+            assert all(not want[l][engine.Memory.PROJECTIVE].any() for l in range(3))
         if case == "symmetric":
             assert np.any(want[2][engine.Memory.NORMALS_M] != 0)
+    finally:
+        p.close()
+
+
+@pytest.mark.parametrize("kind", ["mean", "pick"])
+def test_projective_levels_match_the_restatement(engine, oracle, kind):
+    """One projective iteration per level (r = 1, a level's intrinsics by include/icp_amd.h: f / 2^l, and (c - (2^l - 1) / 2) / 2^l
+    under MEAN, c / 2^l under PICK): every level's pairs, words and pieces against projective_ref.project on pyramid_ref's level
+    clouds at the T the level started from — the identity at the coarsest level, the T of the level above at a finer one —, and the T
+    it leaves.  projective_ref.pyramid_chain computes all of it on the CPU; tests/test_projective_cpu.py proves that every level has
+    hits, outside queries and empty cells and no pixel at a rounding boundary."""
+    import projective_ref as ref
+    check_step = K.check_projective_step
+    k = ref.PYRAMID_MEAN if kind == "mean" else ref.PYRAMID_PICK
+    chain = ref.pyramid_chain(k)
+    p = engine.ICPPyramid(0)
+    try:
+        p.init(ref.PYRAMID_SIDE ** 2, ref.PYRAMID_NR, 2e2, 1e-6)
+        p.set_reduction(k, 0.0)
+        for l, lv in enumerate(chain):
+            p.level(l).set_projective(lv.side, *lv.intr, radius=1)
+        p.write(engine.Memory.F, chain[0].F)
+        p.write(engine.Memory.M, chain[0].M)
+        p.buildRBC()
+        p.run_fixed([1, 1, 1])
+        p.sync()
+        for l in (2, 1, 0):
+            lv, h = chain[l], p.level(l)
+            if l < 2:
+                _same_bits(p.level(l + 1).read(engine.Memory.T), lv.T, "the T level %d started from" % l)
+            _same_bits(h.read(engine.Memory.F), lv.F, "level %d F" % l)
+            _same_bits(h.read(engine.Memory.M), lv.M, "level %d M" % l)
+            got = check_step(engine, oracle, h, lv.res, lv.F, lv.M, lv.T, lv.side, True, K.WEIGHTED, K.POWER, True, pieces=lv.pieces)
+            assert got[1] > 0 and got[2] > 0 and got[3] > 0, (l, got)
+            _same_bits(h.read(engine.Memory.T), lv.T_next, "level %d T" % l)
+            assert h.k == 1
     finally:
         p.close()
 

@@ -21,6 +21,8 @@ oracle's pairs (icp_checks.check_route_pairs: nothing of the expectation is read
 also ICP_PAIRS_EVALUATED and icp_evaluate at the T the step left, which the handle's options must not influence.
 tests/test_pairs_routes_cpu.py proves from the oracle alone that every expected set holds between 20 % and 90 % of the pairs.
 
+Section 2b runs the grid once more with the projection (icp_set_projective) at the head of the route instead of the RBC search.
+
 Shapes (test_route_table's): (30, 4), m = 900 — the last block of 64 / 128 / 256 pairs partly filled, the selection in one block —;
 (150, 4), m = 22500 — a side that is no multiple of 8, the three-pass selection, 352 blocks and so a k_moment_level1 tail."""
 import os
@@ -34,8 +36,9 @@ import p2pl_ref                                                  # noqa: E402
 import pairs_ref                                                 # noqa: E402
 import quality_ref                                               # noqa: E402
 import robust_ref as rref                                        # noqa: E402
-from icp_checks import (ROUTE_BATCH, ROUTE_METRICS, ROUTE_WORDS, assert_bits, back_at, before, check_route_pairs, check_route_plane_step,  # noqa: E402
-                        check_route_step, evaluated_expectation, oracle_search, route_handle, route_proof, route_restate, route_scene, route_scene_options)
+from icp_checks import (PROJ_ROUTE_BATCH, ROUTE_BATCH, ROUTE_METRICS, ROUTE_WORDS, assert_bits, back_at, before, check_route_pairs,  # noqa: E402
+                        check_route_plane_step, check_route_step, evaluated_expectation, oracle_search, route_handle, route_pairs_of, route_proof,
+                        route_restate, route_scene, route_scene_options, route_want)
 
 pytestmark = pytest.mark.gpu
 
@@ -84,8 +87,10 @@ def _steps(engine, oracle, names, mask, metric, fused=None, loss=rref.CAUCHY, st
     s0 = scenes[0]
     os_ = [route_scene_options(s, mask, loss) for s in scenes]
     assert all(o == os_[0] for o in os_), "a handle has one set of options"
-    g = route_handle(engine, s0.side, s0.nr, os_[0], metric, fused, batch=len(scenes))
-    if len(scenes) > 1 and fused is not False:
+    assert all(s.projective == s0.projective for s in scenes), "a handle has one way to find its pairs"
+    assert not (evaluated and s0.projective), "the evaluation is the RBC search's: its expectation is no projective one"
+    g = route_handle(engine, s0.side, s0.nr, os_[0], metric, fused, batch=len(scenes), projective=s0.projective)
+    if len(scenes) > 1 and fused is not False and s0.projective is None:
         assert g.search_layout()[0] == 1, g.search_layout()       # (the dense layout by batch)
     _load(engine, g, scenes)
     wants = [s.want for s in scenes]
@@ -103,13 +108,13 @@ def _steps(engine, oracle, names, mask, metric, fused=None, loss=rref.CAUCHY, st
                 r = check_route_step(engine, oracle, g, s.F, s.M, s.NF, s.NM, T0, Rb, want, o, fused, b, proof, what, back)
             else:
                 r = check_route_plane_step(engine, g, s.F, s.M, s.NF, s.NM, T0, Rb, k0, want, o, route_restate(metric, o, s.M), b, proof, what, back)
-            PF, PM = (s.PF, s.PM) if it == 0 else (s.F[want[0]["id"]], oracle.transform_q(s.M, T0))
+            PF, PM = (s.PF, s.PM) if it == 0 else route_pairs_of(oracle, s, want, T0)
             if it == 0:                                           # (the first step's weights from the reference's pairs too: the CPU proof's)
                 r = route_proof(name, mask, loss, metric != "p2p")[0]
             sets.append(check_route_pairs(engine, g, want[0], PF, PM, r, metric != "p2p", o, b, what))
         if evaluated or it + 1 < steps:
             Ts = [g.read(Mem.T, b).copy() for b in range(len(scenes))]
-            wants = [oracle_search(oracle, s.F, s.M, T, s.nr) for s, T in zip(scenes, Ts)]
+            wants = [route_want(oracle, s, T) for s, T in zip(scenes, Ts)]
         if evaluated:
             _check_evaluated(engine, oracle, g, scenes, Ts, wants, "%s, mask %d, loss %d, behind step %d" % (metric, mask, loss, it))
     g.close()
@@ -167,6 +172,59 @@ def test_every_pass_at_config_A(engine, oracle, metric, fused):
     _steps(engine, oracle, ["A"], 31, metric, fused, evaluated=True)
 
 
+# ---- 2b. the projection at the head of the route ------------------------------------------------------------------------------------------
+#
+# icp_set_projective in the RBC search's place (scenes "p30", "p150": the frames of "30" and "150", icp_checks.PROJ_ROUTE_SCENES): the
+# expectation of a step is projective_ref.project at the step's T — check_search then compares ICP_MEM_NN_ID, NN, QT and
+# ICP_MEM_PROJECTIVE with it —, everything behind it is what it is behind the search.  The reciprocal rule (bit 4) does not combine with
+# the projection: masks 0 .. 15.  r = 1 and a max_dist of the projective pairs' own: icp_checks._projective_route_scene.
+
+PGRID = ["p30", "p150"]
+
+
+@pytest.mark.parametrize("mask", range(16))
+@pytest.mark.parametrize("fused", MODES)
+@pytest.mark.parametrize("name", PGRID)
+def test_point_to_point_behind_the_projection(engine, oracle, name, fused, mask):
+    _steps(engine, oracle, [name], mask, "p2p", fused)
+
+
+@pytest.mark.parametrize("mask", range(16))
+@pytest.mark.parametrize("metric", ROUTE_METRICS)
+@pytest.mark.parametrize("name", PGRID)
+def test_plane_family_behind_the_projection(engine, oracle, name, metric, mask):
+    _steps(engine, oracle, [name], mask, metric)
+
+
+@pytest.mark.parametrize("loss", [rref.HUBER, rref.TUKEY])
+@pytest.mark.parametrize("metric,fused", CASES)
+def test_every_pass_with_the_other_losses_behind_the_projection(engine, oracle, metric, fused, loss):
+    _steps(engine, oracle, ["p30"], 15, metric, fused, loss)
+
+
+@pytest.mark.parametrize("metric,fused", CASES[:3])
+def test_every_pass_in_a_batch_of_three_behind_the_projection(engine, oracle, metric, fused):
+    """Three different scenes at (150, 4) in one handle: 3 x 22500 points, which the projection serves in four rounds per block."""
+    _steps(engine, oracle, list(PROJ_ROUTE_BATCH), 15, metric, fused)
+
+
+def test_the_reciprocal_rule_does_not_combine_with_the_projection(engine):
+    """Both on: every run returns ICP_ESTATE (include/icp_amd.h); the reciprocal rule off again, the handle steps."""
+    s = route_scene("p30")
+    g = route_handle(engine, s.side, s.nr, route_scene_options(s, 15), "p2p", True, projective=s.projective)
+    g.write(engine.Memory.F, s.F); g.write(engine.Memory.M, s.M)
+    g.buildRBC()
+    g.set_reciprocal(True, route_scene("30").max_gap)
+    for call in (g.step, g.run, lambda: g.run_fixed(2)):
+        with pytest.raises(engine.ICPError) as e:
+            call()
+        assert e.value.code == 4
+    g.set_reciprocal(False)
+    g.step()
+    assert g.read(engine.Memory.PROJECTIVE)[1] > 0
+    g.close()
+
+
 # ---- 3. several iterations --------------------------------------------------------------------------------------------------------------
 
 RUNS = [("p2p", True), ("p2p", False), ("p2pl", None)]
@@ -188,9 +246,9 @@ def _same(a, b, what):
         assert_bits(x, y, "%s: %s" % (what, name))
 
 
-def _loaded(engine, mask, metric, fused):
-    s = route_scene("30")
-    g = route_handle(engine, s.side, s.nr, route_scene_options(s, mask), metric, fused)
+def _loaded(engine, mask, metric, fused, name="30"):
+    s = route_scene(name)
+    g = route_handle(engine, s.side, s.nr, route_scene_options(s, mask), metric, fused, projective=s.projective)
     g.write(engine.Memory.F, s.F); g.write(engine.Memory.M, s.M)
     g.buildRBC()
     return g, s
@@ -199,7 +257,17 @@ def _loaded(engine, mask, metric, fused):
 @pytest.mark.parametrize("mask", [7, 15, 31])
 @pytest.mark.parametrize("metric,fused", RUNS)
 def test_run_fixed_equals_steps(engine, metric, fused, mask):
-    g, _ = _loaded(engine, mask, metric, fused)
+    _run_fixed_equals_steps(engine, metric, fused, mask)
+
+
+@pytest.mark.parametrize("mask", [7, 15])
+@pytest.mark.parametrize("metric,fused", RUNS)
+def test_run_fixed_equals_steps_behind_the_projection(engine, metric, fused, mask):
+    _run_fixed_equals_steps(engine, metric, fused, mask, "p30")
+
+
+def _run_fixed_equals_steps(engine, metric, fused, mask, name="30"):
+    g, _ = _loaded(engine, mask, metric, fused, name)
     g.run_fixed(4)
     fixed = _snapshot(engine, g)
     assert fixed[2][3] > 0 and fixed[3][1] > 0 and fixed[4][3] > 0, fixed[2:]
@@ -214,8 +282,18 @@ def test_run_fixed_equals_steps(engine, metric, fused, mask):
 @pytest.mark.parametrize("mask", [7, 15, 31])
 @pytest.mark.parametrize("metric,fused", RUNS)
 def test_run_equals_stepping_until_done(engine, metric, fused, mask):
+    _run_equals_stepping_until_done(engine, metric, fused, mask)
+
+
+@pytest.mark.parametrize("mask", [7, 15])
+@pytest.mark.parametrize("metric,fused", RUNS)
+def test_run_equals_stepping_until_done_behind_the_projection(engine, metric, fused, mask):
+    _run_equals_stepping_until_done(engine, metric, fused, mask, "p30")
+
+
+def _run_equals_stepping_until_done(engine, metric, fused, mask, name="30"):
     """Done is the header's: the step's Tk under both thresholds (p2pl_ref.check_converged) or max_iterations steps taken."""
-    g, _ = _loaded(engine, mask, metric, fused)
+    g, _ = _loaded(engine, mask, metric, fused, name)
     k = g.run()
     assert 1 < k <= MAX_IT, k
     run = _snapshot(engine, g)
@@ -234,8 +312,18 @@ def test_run_equals_stepping_until_done(engine, metric, fused, mask):
 @pytest.mark.parametrize("mask", [7, 15, 31])
 @pytest.mark.parametrize("metric,fused", RUNS)
 def test_every_pass_off_again_equals_never_on(engine, metric, fused, mask):
-    g, s = _loaded(engine, mask, metric, fused)
-    h = route_handle(engine, s.side, s.nr, route_scene_options(s, 0), metric, fused)
+    _every_pass_off_again_equals_never_on(engine, metric, fused, mask)
+
+
+@pytest.mark.parametrize("mask", [7, 15])
+@pytest.mark.parametrize("metric,fused", RUNS)
+def test_every_pass_off_again_equals_never_on_behind_the_projection(engine, metric, fused, mask):
+    _every_pass_off_again_equals_never_on(engine, metric, fused, mask, "p30")
+
+
+def _every_pass_off_again_equals_never_on(engine, metric, fused, mask, name="30"):
+    g, s = _loaded(engine, mask, metric, fused, name)
+    h = route_handle(engine, s.side, s.nr, route_scene_options(s, 0), metric, fused, projective=s.projective)
     h.write(engine.Memory.F, s.F); h.write(engine.Memory.M, s.M)
     stats = (h.run_form(), h.launches_per_iteration())
     g.run(); g.run_fixed(3)

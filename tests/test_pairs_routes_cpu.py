@@ -192,3 +192,34 @@ def test_layout_scenes_have_members_and_non_members(engine, oracle, case):
     if batch > 1:
         assert len({r[1] for r in rows}) == batch and len({r[3] for r in rows}) == batch, "the counts of a batch are pairwise distinct: %r" % (rows,)
     assert rows == LAYOUT_SHARES[case[:5]], rows
+
+
+# ---- the projection at the head of the route (tests/test_gpu_route_numerics.py section 2b) ------------------------------------------------
+
+# scene -> the size of the expected set per mask 0 .. 15 (Cauchy), (point-to-point, a plane metric)
+PROJ_SHARES = {"p30": [(640, 640), (471, 471), (467, 467), (377, 377), (480, 480), (354, 354), (351, 351), (283, 283)] * 2,
+               "p150": [(15136, 15136), (12700, 12700), (11960, 11960), (10717, 10717), (11352, 11352), (9525, 9525), (8970, 8970),
+                        (8038, 8038)] * 2}
+PROJ_BEYOND = {("p30", rref.HUBER): (283, 283), ("p30", rref.TUKEY): (283, 283), ("p150", rref.CAUCHY): (8038, 8038),
+               ("p150b1", rref.CAUCHY): (7281, 7281), ("p150b2", rref.CAUCHY): (8934, 8934)}
+
+
+@pytest.mark.parametrize("mask", range(16))
+@pytest.mark.parametrize("name", list(PROJ_SHARES))
+def test_member_shares_behind_the_projection(engine, oracle, name, mask):
+    """The expectation is projective_ref.project's pairs under composed_rule: the set holds between 20 % and 90 % of the m pairs."""
+    m = route_scene(name).M.shape[0]
+    got = _sizes(name, mask, rref.CAUCHY)
+    print(name, mask, got, [round(100.0 * n / m, 1) for n in got])
+    for n in got:
+        _in_range(n, m, "scene %s, mask %d" % (name, mask))
+    assert got == PROJ_SHARES[name][mask], (got, PROJ_SHARES[name][mask])
+
+
+@pytest.mark.parametrize("name,loss", list(PROJ_BEYOND))
+def test_member_shares_behind_the_projection_beyond_the_grid(engine, oracle, name, loss):
+    m = route_scene(name).M.shape[0]
+    got = _sizes(name, 15, loss)
+    for n in got:
+        _in_range(n, m, "scene %s, mask 15, loss %d" % (name, loss))
+    assert got == PROJ_BEYOND[(name, loss)], (got, PROJ_BEYOND[(name, loss)])

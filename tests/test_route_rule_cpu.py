@@ -408,3 +408,78 @@ def test_against_the_plain_restatement(mask, seed):
         assert rt.words["TRIM"].tolist() == wt["TRIM"] and same(rt.trim, mt["trimmed to"]) and same(rt.W != 0, mt["final"])
         assert rt.words["TRIM"][2] == K and rt.words["TRIM"][3] > K, "pairs that tie at the threshold are all accepted"
     assert not r.W0[40] and 0 < np.count_nonzero(r.W) < np.count_nonzero(r.W0) + (0 if mask & 23 else 1)
+
+
+# ---- 4. the projection at the head of the route ---------------------------------------------------------------------------------------
+#
+# tests/test_gpu_route_numerics.py section 2b: the pairs are projective_ref.project's at r = 1 (icp_checks.PROJ_ROUTE_SCENES), max_dist
+# is the 0.88 quantile of the hits' own distances, min_cos and the scales are those of the scene the frames come from.
+
+# scene -> (max_dist, min_cos, Tukey's scale), to three decimals
+PROJ_CHOSEN = {"p30": (67.823, 0.485, 65.574), "p150": (120.935, 0.157, 55.019), "p150b1": (120.935, 0.157, 55.019), "p150b2": (120.935, 0.157, 55.019)}
+# scene -> ICP_MEM_PROJECTIVE at _t0 (), and with every pass on ICP_MEM_PAIR_FILTER, ICP_MEM_UNIQUE and ICP_MEM_TRIM's (n, K, accepted)
+PROJ_COUNTS = {"p30": ([803, 728, 60, 15], [640, 110, 59, 471], [471, 377], [377, 283, 283]),
+               "p150": ([20048, 17200, 1363, 1485], [15136, 554, 1882, 12700], [12700, 10717], [10717, 8038, 8038]),
+               "p150b1": ([19797, 17331, 1312, 1154], [14467, 626, 2076, 11765], [11765, 9707], [9707, 7281, 7281]),
+               "p150b2": ([20196, 17408, 1031, 1757], [16502, 888, 1576, 14038], [14038, 11912], [11912, 8934, 8934])}
+
+
+@pytest.mark.parametrize("name", list(PROJ_COUNTS))
+def test_the_projective_choices_are_the_recorded_ones(engine, oracle, name):
+    from icp_checks import PROJ_ROUTE_BATCH, PROJ_ROUTE_RADIUS, PROJ_ROUTE_SCENES, ProjectiveWant, geo_of
+    import projective_ref
+    assert list(PROJ_ROUTE_SCENES) == list(PROJ_COUNTS) and PROJ_ROUTE_RADIUS == 1
+    s = route_scene(name)
+    assert isinstance(s.want, ProjectiveWant) and s.max_gap is None and s.back is None
+    assert s.projective == (s.side,) + tuple(engine.grid_intrinsics(s.side)) + (1,)
+    got = (s.max_dist, s.min_cos, s.scale[rref.TUKEY])
+    assert np.allclose(got, PROJ_CHOSEN[name], rtol=0, atol=1e-3), (got, PROJ_CHOSEN[name])
+    assert float(F32(s.max_dist)) == s.max_dist and float(F32(s.min_cos)) == s.min_cos
+    res = s.want.res
+    # the expectation: the rule's pairs, the misses clipped to a row of F and weighing nothing; the tables the rules read are the rule's
+    assert np.array_equal(s.want[0]["id"][~res.miss], res.nn_id["id"][~res.miss]) and not s.want[0]["id"][res.miss].any()
+    assert np.isinf(s.want[0]["dist"][res.miss]).all() and s.PF is res.NN and s.PM is res.QT and not s.PF[res.miss].any()
+    W0 = weights_before_trim(s.want[0], s.M, s.PF, s.PM, True, True, s.max_dist)
+    assert not W0[res.miss].any() and np.array_equal(s.T, route_scene(name[1:4].rstrip("b")).T)
+    if name in PROJ_ROUTE_BATCH[:1] + ("p30",):                   # (max_dist is the 0.88 quantile of the hits' own distances)
+        hits = int(res.counts[1])
+        beyond = np.count_nonzero(~(geo_of(s.PF, s.PM)[~res.miss] <= F32(s.max_dist) * F32(s.max_dist)))
+        assert abs(beyond - 0.12 * hits) <= 1.0, (beyond, hits)
+    r, _ = route_proof(name, 15)
+    t = r.words["TRIM"]
+    assert (res.counts.tolist(), r.words["PAIR_FILTER"].tolist(), r.words["UNIQUE"].tolist(), [int(t[1]), int(t[2]), int(t[3])]) == PROJ_COUNTS[name]
+    if name == "p150":                                            # (the figures the choice was made on)
+        assert np.count_nonzero(r.W0 == 0) == 7364 and s.M.shape[0] == 22500
+    if isinstance(PROJ_ROUTE_SCENES[name], str):                  # the two choices that do not work
+        base = route_scene(PROJ_ROUTE_SCENES[name])
+        assert s.F is base.F and s.M is base.M
+        far = np.count_nonzero(W0) - np.count_nonzero(weights_before_trim(s.want[0], s.M, s.PF, s.PM, True, True, base.max_dist))
+        if name == "p150":
+            assert np.count_nonzero(weights_before_trim(s.want[0], s.M, s.PF, s.PM, True, True, base.max_dist)) < s.M.shape[0] // 2, far
+        else:                                                     # (r = 0: a cell has one query, seldom two: one-to-one has nothing to remove)
+            r0 = projective_ref.project(oracle, s.F, s.M, s.T, s.side, engine.grid_intrinsics(s.side), 0, True)
+            nn0 = projective_ref.clipped(r0.nn_id, r0.miss)
+            o = route_scene_options(s, 2)
+            u = composed_rule(nn0, r0.NN, r0.QT, s.F, s.M, s.R0, s.NF, s.NM, o).words["UNIQUE"]
+            assert u[0] - u[1] <= 1, u
+
+
+@pytest.mark.parametrize("mask", range(16))
+@pytest.mark.parametrize("name", list(PROJ_COUNTS))
+def test_every_stage_bites_behind_the_projection(engine, oracle, name, mask):
+    """As test_every_stage_bites, on the projection's pairs: every scene, mask, loss and family the device grid runs (and more: every
+    loss and both families on every scene)."""
+    for loss in (LOSSES if mask & 8 else LOSSES[:1]):
+        for plane in (False, True):
+            r, shares = route_proof(name, mask, loss, plane)
+            want = [n for bit, names in ((1, ("boundary", "normal", "filter")), (2, ("unique",)), (4, ("trim",))) if mask & bit for n in names]
+            assert sorted(shares) == sorted(want + (["loss"] if mask & 8 and not plane else [])), shares
+            for n, removed, kept in shares.values():
+                assert 50 * removed >= n and 2 * kept >= n
+    w = r.words
+    if mask & 2:
+        assert not mask & 1 or w["UNIQUE"][0] == w["PAIR_FILTER"][3]
+    if mask & 4:
+        front = w["UNIQUE"][1] if mask & 2 else w["PAIR_FILTER"][3] if mask & 1 else None
+        assert front is None or w["TRIM"][1] == front
+    assert w["RECIPROCAL"] is None and r.reciprocal is None
