@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — ICP iterations/sec at |F|=|M|=16384, |R|=256 (BASELINE.json metric) on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config A|B|C] [--batch B] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--full] [--config A|B|C] [--batch B] [--dump-outputs DIR]
+
+A plain run does what its headline figure needs and nothing else: it sets up, warms up, times the K steps, writes the outputs of the
+last one if --dump-outputs says so, and prints the result line.  `--full` adds everything else this file measures or checks — the
+latency of a whole registration, `roofline` (per-kernel times from runs of their own), the other BASELINE configs, tracking, the
+invalid-point cases, the mode comparison with its float64 check, `cpu_baseline` — after the timed steps and the dump, so `value`,
+`ms_per_step` and the dumped arrays are the same with and without it.
 
 A "step" is one fixed-length registration pass of the hot path: starting from the identity transform,
 `iterations_per_step` (40 = the length of the reference's profiling run, include/ICP/algorithms.hpp:2482-2494; 10 at
@@ -14,7 +20,7 @@ Workloads (icp_amd/workloads.py):  A = BASELINE configs[1] (|F|=|M|=16384, |R|=2
 B = configs[2] (65536 / 1024), C = configs[4] (2^20 / 4096); `--batch B` = B independent registrations sharing every
 launch (configs[3] runs 64 per GPU).
 
---gpus 1 (default): batch 1 — the headline metric.  The line also carries `other_configs`: the same measurement at
+--gpus 1 (default): batch 1 — the headline metric.  With --full the record also carries `other_configs`: the same measurement at
 A x 64 registrations, B and C (fewer steps) and frame-to-frame tracking.
 --gpus N > 1: a frame pair does not shard — "replicas only": every GPU registers its own 64 independent
 pairs (config 4) unless --batch says otherwise, no data-path collective, no RCCL.  Two ways to get there, same numbers:
@@ -23,14 +29,15 @@ pairs (config 4) unless --batch says otherwise, no data-path collective, no RCCL
   * plain `python bench.py --gpus N`: devices 0..N-1 are driven in-process through the library's own icp_batch_* (one host
     thread + one stream per device).
 `--gpus` must equal the ranks / devices actually used, or the run fails.  value = iterations of all GPUs / max-over-GPUs
-time ("scaling": "weak").  EVERY line carries `config4_per_gpu_value` — iterations/s of one GPU at config 4's per-GPU share
-(64 registrations per launch) — so that N = 1 -> 8 reads off ONE field; the N = 1 `value` itself is the batch-1 headline.
+time ("scaling": "weak").  `config4_per_gpu_value` — iterations/s of one GPU at config 4's per-GPU share (64 registrations per
+launch) — is in every line whose own work is that share and, with --full, in the N = 1 headline line too (measured beside it), so
+that N = 1 -> 8 reads off ONE field; the N = 1 `value` itself is the batch-1 headline.
 
-Prints ONE JSON line (rank 0) as the LAST line of stdout, shorter than 4 KB (`compact_line`): the contract's fields, `roofline`,
-`cpu_baseline` and flat scalars for the other BASELINE configs.  Everything else that is measured (per-kernel times, tracking
-distributions, the invalid-point cases, the mode comparison, the thread sweep) goes to bench_extra.json beside this file (stderr gets one
-line that says so; ICP_BENCH_STDERR_RECORD=1: the whole record).
-Objects of the line:
+Prints ONE JSON line (rank 0) as the LAST line of stdout, shorter than 4 KB (`compact_line`): the contract's fields and, with --full,
+`roofline`, `cpu_baseline` and flat scalars for the other BASELINE configs.  Everything else that --full measures (per-kernel times,
+tracking distributions, the invalid-point cases, the mode comparison, the thread sweep) goes to bench_extra.json beside this file
+(stderr gets one line that says so; ICP_BENCH_STDERR_RECORD=1: the whole record).
+Objects of the --full line:
   roofline      dominant kernel (k_search): algorithmic bytes per launch ((72 m + 32 |R| + 64) x registrations per launch,
                 SURVEY.md §8d) / its average launch-to-launch time, measured with HIP events on the engine's own stream.
                 In the default (fused, chained) form an iteration IS one k_search launch (it first turns the previous
@@ -885,8 +892,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the B / C / tracking / mode measurements of the N = 1 line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps (and the dump), also measure and check everything beside the headline figure: registration latency, "
+                         "roofline with per-kernel times, the other configs, tracking, invalid points, the mode comparison, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the B / C / tracking / mode measurements of the N = 1 line")
     ap.add_argument("--power-mode", choices=["literal", "squared"], default="squared")
     ap.add_argument("--reduce-mode", choices=["reference", "fused"], default="fused")
     ap.add_argument("--config", choices=["A", "B", "C"], default="A",
@@ -967,12 +977,14 @@ def main():
     if launch == "inprocess":
         total_t, total_iters, per_gpu, devices_used = run_inprocess(icp_amd, args, world, batch, iters, steps, warmup)
         device = devices_used[0]
-        # the dominant kernel's launch time, live, on the first device: a handle of its own with the same per-GPU work
+        # a handle of its own with the same per-GPU work on the first device: it says what form an iteration takes there and, with
+        # --full, times the dominant kernel's launches live
         g, m, nr, (F, M) = setup(icp_amd, device, args.config, batch, 0, args.power_mode, args.reduce_mode)
-        rsteps = max(2, min(steps, 10))
-        g.run_fixed_fresh(iters)
-        g.sync()
-        ev_ms, ev_steps = g.time_run_fixed_tail(iters, rsteps, from_identity=True)
+        if args.full:
+            rsteps = max(2, min(steps, 10))
+            g.run_fixed_fresh(iters)
+            g.sync()
+            ev_ms, ev_steps = g.time_run_fixed_tail(iters, rsteps, from_identity=True)
     else:
         g, m, nr, (F, M) = setup(icp_amd, device, args.config, batch, rank * batch, args.power_mode, args.reduce_mode)
 
@@ -987,7 +999,9 @@ def main():
                 torch.cuda.synchronize()
 
         # what a freshly started process sees (reported beside the metric, never as it): the same W warm-up + K timed steps BEFORE the
-        # device has been kept busy for SETUP_MS — an MI355X that was idle runs its first ~10 ms of work below its steady clocks
+        # device has been kept busy for SETUP_MS — an MI355X that was idle runs its first ~10 ms of work below its steady clocks.
+        # (Not behind --full: these passes come BEFORE the timed steps, so the clocks those start at depend on them — they are part of
+        # what the headline figure is; they cost W + K steps.)
         unsettled = None
         if dist is None:
             for _ in range(warmup):
@@ -1012,10 +1026,11 @@ def main():
         if args.dump_outputs and rank == 0:
             dump_outputs(args.dump_outputs, outputs_of(icp_amd, lambda i, mem: g.read(mem, batch_index=i), g.state, batch, m))
 
-    # beside the metric (never part of `value`): latency of one whole registration = RBC construction + the iterations,
+    # The headline figure is complete here and the outputs are written: everything below, down to the line, runs only with --full.
+    # Beside the metric (never part of `value`): latency of one whole registration = RBC construction + the iterations,
     # inputs resident, and the same with the two clouds uploaded from host memory first
     e2e = None
-    if rank == 0 and batch == 1 and launch == "single":
+    if args.full and rank == 0 and batch == 1 and launch == "single":
         reps = 20 if m <= 65536 else 3
         g.buildRBC(); g.sync()
         t1 = time.perf_counter()
@@ -1044,11 +1059,11 @@ def main():
     # `iters` k_search launches (+ one end kernel per graph); otherwise a graph holding only that kernel.
     tkey = "k_search_hbm_bytes_per_launch" if (args.config == "A" and batch == 1) else \
            "k_search_hbm_bytes_per_launch_%s" % (args.config if batch == 1 else "%s_x%d" % (args.config, batch))
-    roofline = roofline_of(g, m, nr, batch, iters, ev_steps, ev_ms, fused, tkey) if rank == 0 else None
+    roofline = roofline_of(g, m, nr, batch, iters, ev_steps, ev_ms, fused, tkey) if args.full and rank == 0 else None
     launches = g.launches_per_iteration()
     headline = launch == "single" and args.config == "A" and batch == 1
     modes = None
-    if rank == 0 and headline and fused and args.power_mode == "squared" and not args.no_other_configs:
+    if args.full and rank == 0 and headline and fused and args.power_mode == "squared" and not args.no_other_configs:
         try:
             modes = measure_modes(icp_amd, device, g, args.power_mode, args.reduce_mode)
         except Exception as e:                       # noqa: BLE001 — beside the metric: reported, never fatal
@@ -1109,8 +1124,8 @@ def main():
                                                    "N = 1 batch-1 headline `value`" % batch)
         if e2e is not None:
             line["registration_latency"] = e2e
-        if headline:
-            # config 4's per-GPU share on this GPU (always: the field every line carries), then the other BASELINE configs, same step
+        if args.full and headline:
+            # config 4's per-GPU share on this GPU (the field every --full line carries), then the other BASELINE configs, same step
             # definition, fewer steps (C: 3 steps of 10 iterations), tracking, and what the benchmarked mode is against the other one
             # (everything beside the metric is guarded: a failure there is reported in its place and never costs the line its `value`)
             def guarded(fn, *a, **kw):
@@ -1129,7 +1144,7 @@ def main():
             line["other_configs"] = oc
             if modes is not None:
                 line.update(modes)
-        if world == 1 and not args.no_cpu_baseline and m <= 65536:
+        if args.full and world == 1 and not args.no_cpu_baseline and m <= 65536:
             line["cpu_baseline"] = cpu_baseline(F, M, m, nr, fused)
         line["git_head"] = git_head()
         emit(line)

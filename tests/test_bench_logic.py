@@ -103,6 +103,25 @@ def test_result_line_is_short_and_last_on_stdout(tmp_path):
         assert "other_configs" not in line and "mode_note" not in line
 
 
+def test_result_line_of_a_plain_run_carries_the_headline_alone():
+    """Without --full nothing beside the headline figure is measured: the record has no `roofline`, `cpu_baseline`, `other_configs`,
+    latency or mode comparison, and the line is the contract's fields and what describes the run — no empty stand-ins for the rest."""
+    import json
+    full = _canned_full()
+    for k in ("roofline", "cpu_baseline", "other_configs", "registration_latency", "mode_note", "reference_order_us_per_iteration",
+              "reference_order_squared_us_per_iteration"):
+        del full[k]
+    full["config4_per_gpu_value"] = None
+    line = json.loads(bench.compact_line(full))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert k in line, k
+    assert abs(line["value"] - full["value"]) < 1e-2 and abs(line["ms_per_step"] - full["ms_per_step"]) < 1e-6 and line["higher_is_better"] is True
+    assert set(line) - {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+                        "data", "config"} == {"us_per_iteration", "per_gpu_iterations_per_s", "single_gpu_same_work_key", "config4_per_gpu_value",
+                                              "git_head", "extra", "value_right_after_start"}
+    assert line["config4_per_gpu_value"] is None
+
+
 def test_result_line_drops_optional_scalars_before_it_grows(monkeypatch):
     """Whatever a run adds beside the metric, the line stays under the limit and keeps the contract's fields."""
     import json

@@ -370,7 +370,7 @@ def test_bench_two_ranks_on_one_gpu():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, ICP_BENCH_DEVICE="0", ICP_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -397,7 +397,7 @@ def test_bench_gpus_2_plain_python_in_process():
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["ICP_BENCH_DEVICES"] = "0,0"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"]      # (--full: the roofline)
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -419,17 +419,25 @@ def test_bench_gpus_2_plain_python_in_process():
 def test_bench_dump_outputs_are_the_timed_passes_results(engine, tmp_path):
     """`bench.py --dump-outputs DIR` writes what the last timed step computed: T, R, the correspondences and the weights of the benchmark
     pair after one fresh 40-iteration pass, bit for bit what a handle of its own gives for that pass — and the same files again from a
-    second run with the same arguments."""
+    second run with the same arguments.  These are plain runs (no --full): their line carries the headline figure and what describes
+    it, and nothing that takes measurements of its own."""
+    import json
     import sys
     from icp_amd import workloads as W
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     got = []
     for run in range(2):
         d = tmp_path / ("run%d" % run)
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                              "--no-other-configs", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
         assert out.returncode == 0, out.stderr[-3000:]
         got.append({p.stem: np.load(p) for p in d.iterdir()})
+        line = json.loads(out.stdout.splitlines()[-1])
+        assert line["metric"] == "ICP iterations/sec at |F|=|M|=16384, |R|=256" and line["unit"] == "iterations/s" and line["dtype"] == "f32"
+        assert line["higher_is_better"] is True and line["n_gpus"] == 1 and line["steps"] == 3 and line["warmup"] == 1
+        assert line["value"] == pytest.approx(3 * 40 / (line["ms_per_step"] * 3 * 1e-3), rel=1e-6) and line["config"]["launches_per_iteration"] == 1
+        beside = [k for k in line if k in ("roofline", "cpu_baseline", "build_rbc_ms", "config4_per_gpu_value") or k.startswith(("A_", "B_", "C_", "track_", "reference_order"))]
+        assert beside == ["config4_per_gpu_value"] and line["config4_per_gpu_value"] is None, beside
     assert sorted(got[0]) == ["R", "T", "nn_dist", "nn_id", "w"]
     for name, a in got[0].items():
         assert a.dtype in (np.float32, np.float64) and np.array_equal(a.view(np.uint8), got[1][name].view(np.uint8)), name

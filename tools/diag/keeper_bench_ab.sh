@@ -2,7 +2,7 @@
 # Diagnostic (not a test): the tracking lines of bench.py itself (a process that has imported torch) with / without the keeper thread, alternating.
 for i in 1 2 3; do
     for k in 1 0; do
-        ICP_AMD_TRACK_KEEPER=$k python3 bench.py --no-cpu-baseline --steps 20 --warmup 5 > /tmp/kb.txt 2>/dev/null
+        ICP_AMD_TRACK_KEEPER=$k python3 bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > /dev/null 2>&1
         python3 - "$k" <<'P'
 import json, sys
 d = json.load(open("bench_extra.json")); t = d["other_configs"]["track"]
