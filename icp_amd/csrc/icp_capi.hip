@@ -330,6 +330,7 @@ int icp_init_batched (icp_handle h, uint32_t batch, uint32_t m, uint32_t nr, flo
     if (m == 0) return fail (h, ICP_EINVAL, "The sets of landmarks cannot have zero points");
     if (nr == 0) return fail (h, ICP_EINVAL, "The sets of representatives cannot have zero points");
     if (a == 0.f) return fail (h, ICP_EINVAL, "The alpha parameter cannot be equal to zero");
+    if (!std::isfinite (a)) return fail (h, ICP_EINVAL, "The alpha parameter cannot be NaN or infinite");
     if (m % 2) return fail (h, ICP_EINVAL, "The number of points in the array must be a multiple of 2");
     if (batch == 0 || batch > 65535u) return fail (h, ICP_EINVAL, "batch must be in [1, 65535]");
     if (max_iterations == 0) return fail (h, ICP_EINVAL, "max_iterations must be positive");
@@ -741,6 +742,7 @@ int icp_set_alpha (icp_handle h, float a) try
     api_guard guard_ (h);
     if (!h) return ICP_EINVAL;
     if (a == 0.f) return fail (h, ICP_EINVAL, "The alpha parameter cannot be equal to zero");
+    if (!std::isfinite (a)) return fail (h, ICP_EINVAL, "The alpha parameter cannot be NaN or infinite");
     { int rc = outputs_before_change (h); if (rc) return rc; }
     h->p.a = a; ++h->param_gen; return ICP_OK;
 }

@@ -11,9 +11,9 @@
 //       u = (double) fx * ((double) e.x / (double) e.z) + (double) cx,  v likewise with fy, e.y, cy;  pu = floor (u + 0.5), pv = floor (v + 0.5).
 //   Inside iff it counts, e is finite, e.z > 0, 0 <= pu <= gw - 1 and 0 <= pv <= rows - 1, compared in double (a NaN fails).
 //   Candidates: the window's cells j = y gw + x (columns max (0, pu - r) .. min (gw - 1, pu + r), rows likewise) whose F[j].xyz is finite
-//   and not (0, 0, 0); d_j = icp_metric8 (e, M[i].rgb; F[j].xyz, F[j].rgb; alpha).  The winner is the minimum of the key
-//   ((uint64) bits (d_j) << 32) | j over the candidates with d_j < +inf: the smallest distance, a tie to the smallest j.  A minimum of
-//   distinct keys: it does not depend on how the lanes share the window.
+//   and not (0, 0, 0); d_j = icp_metric8 (e, M[i].rgb; F[j].xyz, F[j].rgb; alpha).  The winner is the candidate with the smallest
+//   d_j < +inf, compared as floats (a negative alpha makes negative distances; a NaN or +inf never wins), a tie to the smallest j: what a
+//   scan of the window in ascending j that starts from +inf and updates on a strict '<' keeps.
 //   Hit: d = dist_scale d_j, NN_ID[i] = {d, j}, NN[i] = (F[j].xyz, w), w = weighted ? 100 / (100 + d) : 1 — and +0 where
 //   icp_set_rejection's distance test rejects the pair, which keeps its record as behind the RBC search.
 //   Miss (not counting, not inside, no winner): NN_ID[i] = {+inf, 0xFFFFFFFF}, NN[i] = (0, 0, 0, +0): exactly a rejected pair.
@@ -79,7 +79,7 @@ __global__ __launch_bounds__ (PROJ_BLOCK) void k_projective (icp_params p, uint3
         const double pu = floor (u + 0.5), pv = floor (w_ + 0.5);
         const bool inside = counts_ && gw != 0u && isfinite (ex) && isfinite (ey) && isfinite (ez) && (double) ez > 0.0
                             && pu >= 0.0 && pu <= (double) (gw - 1u) && pv >= 0.0 && pv <= (double) (rows - 1u);
-        unsigned long long key = ~0ull;
+        float best = __builtin_inff (); uint32_t bj = PROJ_NONE;
         if (inside) {
             // (0 <= pu <= gw - 1 and 0 <= pv <= rows - 1: the conversions are exact, and every cell (x, y) below has y gw + x < rows gw <= m)
             const uint32_t ux = (uint32_t) pu, uy = (uint32_t) pv;
@@ -89,20 +89,18 @@ __global__ __launch_bounds__ (PROJ_BLOCK) void k_projective (icp_params p, uint3
                     const uint32_t j = y * gw + x;
                     const float4 fg = F4[2u * (size_t) j], fc = F4[2u * (size_t) j + 1u];
                     const float d = icp_metric8 (ex, ey, ez, mc.x, mc.y, mc.z, fg.x, fg.y, fg.z, fc.x, fc.y, fc.z, p.a);
-                    if (icp_point_valid (fg) && d < __builtin_inff ()) {
-                        const unsigned long long k = ((unsigned long long) __float_as_uint (d) << 32) | j;
-                        key = k < key ? k : key;
-                    }
+                    // (the thread's cells ascend: a strict '<' from +inf keeps the smallest j among equal distances, and a NaN or +inf never wins)
+                    if (icp_point_valid (fg) && d < best) { best = d; bj = j; }
                 }
         }
-        const bool hit = inside && key != ~0ull;
+        const bool hit = inside && bj != PROJ_NONE;
         if (v) {
             icp_dist_id di; di.dist = __builtin_inff (); di.id = PROJ_NONE;
             float4 pf = make_float4 (0.f, 0.f, 0.f, 0.f);
             if (hit) {
-                const uint32_t j = (uint32_t) (key & 0xFFFFFFFFull);
+                const uint32_t j = bj;
                 const float4 fg = F4[2u * (size_t) j];       // (j < m: a cell of the window)
-                const float d = p.dist_scale * __uint_as_float ((uint32_t) (key >> 32));
+                const float d = p.dist_scale * best;
                 float w = p.weighted ? 100.f / (100.f + d) : 1.f;
                 if (p.reject & ICP_REJECT_DIST_ON) {         // (icp_set_rejection's distance test, as the REJ search's epilogue applies it:
                     // icp_pair_geo of e - fg, written out — through the helper the compiler branches where it selects here: profiles/pair_pass_isa_diff.txt)

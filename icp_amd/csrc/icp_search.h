@@ -143,6 +143,12 @@ template <int LPQ> static __device__ __forceinline__ uint32_t ks_grp_min_u (uint
     return v;
 }
 
+// The bits of a float as 32 bits whose UNSIGNED order is the order of the values, for every float that is not a NaN (-inf lowest, +inf
+// highest; -0 below +0): a non-negative float gets its sign bit set, a negative one all bits flipped.  Distances are negative only with
+// a < 0 (d = fma (a, pho, geo)); among non-negative ones the plain bits order the same.  ks_ordered_bits_inv: the inverse.
+static __device__ __forceinline__ uint32_t ks_ordered_bits (uint32_t u) { return u ^ ((uint32_t) ((int32_t) u >> 31) | 0x80000000u); }
+static __device__ __forceinline__ uint32_t ks_ordered_bits_inv (uint32_t k) { return k ^ ((uint32_t) ((int32_t) ~k >> 31) | 0x80000000u); }
+
 // Invalid points (a Kinect frame's pixels without depth: x = y = z = 0, the colour kept — reference src/kinect_frame_grabber.cpp:246-262,
 // kernels/icp_kernels.cl:49-50) among the members of a pruning box would stretch it from the scene to the origin: a box every query is
 // near, i.e. no pruning at all in a frame with holes.  The boxes are therefore built over the representatives that are NOT at the
@@ -727,8 +733,9 @@ static __device__ __forceinline__ void ks_stage2_wave (const char *XQb, uint32_t
     // positions l, l + 64, .. — and every lane evaluates its candidate against each query of the wave that has this list,
     // the query's six coordinates in SGPRs.  Distinct lists of the wave are served one after the other.  Per lane and
     // query: best (distance, trip); at the end one butterfly over the 64 lanes that halves the number of queries a lane
-    // holds while it doubles the lanes reduced ((distance bits, position) as one 64-bit key: distances are >= +0, so
-    // the unsigned order of the bits is the order of the values; smallest distance, ties -> lowest position).
+    // holds while it doubles the lanes reduced ((distance bits, position) as one 64-bit key: with a > 0 distances are
+    // >= +0, so the unsigned order of the bits is the order of the values; with a < 0 they can be negative, and the
+    // key's high word is ks_ordered_bits of them; smallest distance, ties -> lowest position).
     const uint32_t je = valid ? o + n : o;
     unsigned long long todo = __ballot (je != o);                // lanes of the queries with a list to scan
     float sx[8], sy[8], sz[8], sr[8], sg[8], sb[8];
@@ -782,17 +789,26 @@ static __device__ __forceinline__ void ks_stage2_wave (const char *XQb, uint32_t
         }
     }
 #undef KS_WCAND
-    // the wave's winner per query: (distance bits, position) as one 64-bit key (distances are >= +0: the unsigned order of
-    // the bits is the order of the values), and a butterfly over the 64 lanes that halves the queries a lane holds while it
+    // the wave's winner per query: (distance bits, position) as one 64-bit key (distances are >= +0 with a > 0: the unsigned order of
+    // the bits is the order of the values; a < 0 — a scalar branch no default search takes — makes negative ones: ks_ordered_bits of
+    // them in front of the butterfly, the inverse behind it), and a butterfly over the 64 lanes that halves the queries a lane holds while it
     // doubles the lanes reduced — after three steps lane l holds query l & 7 over its group of 8 lanes, after six over the wave.
     // (Measured against it and slower, 283 -> 292 us at C: the distances alone through the butterfly and the winner's
     // position looked up with ballots / readlanes in scalars.)
     unsigned long long key[8];
+    uint32_t kd[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) kd[q] = __float_as_uint (bd[q]);
+    const bool signed_d = alpha < 0.f;                           // (wave-uniform: a kernel argument)
+    if (__builtin_expect (signed_d, 0)) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { kd[q] = ks_ordered_bits (kd[q]); asm volatile ("" : "+v"(kd[q])); }      // (opaque: stays a branch, not eight selects)
+    }
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const uint32_t oq = (uint32_t) __builtin_amdgcn_readlane ((int) o, 8 * q), jeq = (uint32_t) __builtin_amdgcn_readlane ((int) je, 8 * q);
         const uint32_t pos = (btr[q] == 0xFFFFFFFFu) ? 0xFFFFFFFFu : min (oq + lane + 64u * btr[q], jeq - 1u);
-        key[q] = ((unsigned long long) __float_as_uint (bd[q]) << 32) | pos;
+        key[q] = ((unsigned long long) kd[q] << 32) | pos;
     }
     auto xchg_dpp = [] (unsigned long long v, auto ctrl) -> unsigned long long {
         const uint32_t lo = (uint32_t) __builtin_amdgcn_update_dpp (0, (int) (uint32_t) v, decltype (ctrl)::value, 0xF, 0xF, true);
@@ -827,7 +843,9 @@ static __device__ __forceinline__ void ks_stage2_wave (const char *XQb, uint32_t
     k1 = min64 (k1, xchg_lane (k1, lane ^ 16u));
     k1 = min64 (k1, xchg_lane (k1, lane ^ 32u));
     k1 = xchg_lane (k1, (lane & 56u) | (lane >> 3));            // to the lanes of query lane >> 3
-    dmin = __uint_as_float ((uint32_t) (k1 >> 32)); jmin = (uint32_t) k1;
+    uint32_t dbits = (uint32_t) (k1 >> 32);
+    if (__builtin_expect (signed_d, 0)) { dbits = ks_ordered_bits_inv (dbits); asm volatile ("" : "+v"(dbits)); }
+    dmin = __uint_as_float (dbits); jmin = (uint32_t) k1;
     // ---- long lists (beyond ICP_S2W_UNCOND positions: no clean scene has one; a frame's invalid points with their colours zeroed are ONE
     // point, and the list that holds them all is scanned by every query that is such a point — |F| = 65536, |R| = 256, 30 % of them: 377 us
     // per iteration instead of 23): the rest of such a list is scanned by the query's own 8 lanes behind chunk-box tests (ks_list_tail),

@@ -119,7 +119,7 @@ int icp_destroy (icp_handle h);
 
 /* ICP<CR,CW>::init (m, nr, a, c, max_iterations, angle_threshold, translation_threshold, staging)
  * — include/ICP/algorithms.hpp:2437-2440, src/ICP/algorithms.cpp:4777-4786 and ICPStep::init
- * :4403-4582.  Rejects m == 0, nr == 0, a == 0 (reference :4413-4420), odd m (:1573),
+ * :4403-4582.  Rejects m == 0, nr == 0, a == 0 (reference :4413-4420), a NaN or infinite a, odd m (:1573),
  * nr not a power of two or not tiling the sqrt(m) landmark grid (:842-854).
  * `batch` >= 1 independent registrations share the launch set (SURVEY §8e "replicas only"). */
 int icp_init (icp_handle h, uint32_t m, uint32_t nr, float a, float c,
@@ -218,7 +218,10 @@ int icp_sync (icp_handle h);
 
 /* ---- parameters ---------------------------------------------------------------------------- */
 /* getAlpha/setAlpha/getScaling/setScaling — include/ICP/algorithms.hpp:2279-2295;
- * get/setMaxIterations, AngleThreshold, TranslationThreshold — :2447-2460. */
+ * get/setMaxIterations, AngleThreshold, TranslationThreshold — :2447-2460.
+ * Alpha: every finite float but 0 is accepted (0, NaN and +-inf: ICP_EINVAL) — negative, denormal and huge ones included; the search gives
+ * the serial scan's answer (strict '<' from +inf, a tie to the lowest index) for all of them, in every layout.  Its exact pruning rests on
+ * d >= geo and is on for a > 0 only: with a < 0 every representative and every list member is scanned. */
 int icp_get_alpha (icp_handle h, float *a);
 int icp_set_alpha (icp_handle h, float a);
 int icp_get_scaling (icp_handle h, float *c);
@@ -393,9 +396,9 @@ int icp_get_reciprocal (icp_handle h, int *on, float *max_gap);
  *       NaN fails).
  *       The window is columns max (0, pu - r) .. min (gw - 1, pu + r), and rows likewise.  A candidate is a window cell j = y gw + x
  *       whose F[j].xyz is finite and not (0, 0, 0); d_j is the engine's metric between (e, M[i].rgb) and (F[j].xyz, F[j].rgb) with
- *       the handle's alpha (alpha >= 0).
- *       The winner is the smallest d_j with d_j < +inf, a tie going to the smallest j: the minimum of the key
- *       ((uint64) bits (d_j) << 32) | j.  The result does not depend on the order in which the window is walked.
+ *       the handle's alpha (any alpha icp_set_alpha accepts: a negative one makes negative distances).
+ *       The winner is the smallest d_j with d_j < +inf, compared as floats — a NaN or +inf never wins —, a tie going to the smallest
+ *       j.  The result does not depend on the order in which the window is walked.
  *       Hit: d = dist_scale d_j, NN_ID[i] = {d, j}, NN[i] = (F[j].xyz, w) with w = weighted ? 100 / (100 + d) : 1, W[i] = w.
  *       icp_set_rejection's distance test applies to a hit as it does behind the search: the pair keeps its record, its weight is +0.
  *       Miss — the query does not count, is not inside, or has no winner —: NN_ID[i] = {+inf, 0xFFFFFFFF}, NN[i] = (0, 0, 0, +0),

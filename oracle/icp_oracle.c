@@ -985,6 +985,7 @@ int orc_icp_init (orc_icp *h, uint32_t m, uint32_t nr, float a, float c, uint32_
 {
     uint32_t nrx, nry, g;
     if (m == 0 || nr == 0 || a == 0.f) return -1;             /* algorithms.cpp:4413-4420 */
+    if (!isfinite (a)) return -1;                              /* (the engine's own refusal: a NaN or infinite alpha orders nothing) */
     if (m % 2) return -1;                                      /* :1573 (means need even n) */
     if (orc_reps_grid (m, nr, &nrx, &nry, &g)) return -1;
     free_bufs (h);

@@ -197,8 +197,8 @@ def weights_before_trim(nn_id, M, PF, PM, weighted, invalid, max_dist=None):
     return W0
 
 
-def oracle_search(oracle, F, M, T, nr):
-    o = oracle.OracleICP(F.shape[0], nr, A, C_, threads=8)
+def oracle_search(oracle, F, M, T, nr, a=A):
+    o = oracle.OracleICP(F.shape[0], nr, a, C_, threads=8)
     o.write_f(F); o.write_m(M); o.build_rbc(); o.write_t(T)
     o.step()
     return o.nn_id, o.rid

@@ -9,7 +9,8 @@ The rule per query i at the transform T:
   inside iff it counts, e is finite, e.z > 0, 0 <= pu <= gw - 1 and 0 <= pv <= rows - 1 (a NaN fails every comparison);
   candidates: the cells j = y gw + x of the window [pu - r, pu + r] x [pv - r, pv + r] clipped to the grid whose F[j].xyz is finite and
   not (0, 0, 0); d_j = oracle.metric8 (e | M[i].rgb, F[j], alpha), one call per candidate;
-  the winner: the smallest d_j < +inf, a tie to the smallest j — the minimum of (bits (d_j), j);
+  the winner: the smallest d_j < +inf as floats compare (a negative alpha makes negative distances), a tie to the smallest j — the
+  minimum of (d_j, j);
   hit: d = dist_scale * d_j in fp32, NN_ID = {d, j}, NN = (F[j].xyz, w), w = weighted ? 100 / (100 + d) : 1;
   miss (does not count, not inside, no winner): NN_ID = {+inf, 0xFFFFFFFF}, NN = (0, 0, 0, +0), W = +0; QT = (e, d) for every row.
 Counts (ICP_MEM_PROJECTIVE): n = counting queries, hits, outside = counting and not inside, empty = inside without a winner.
@@ -92,7 +93,7 @@ def project(oracle, F, M, T, gw, intr, r, weighted, alpha=2e2, dist_scale=1.0):
         ys, xs = np.arange(max(0, y - r), min(rows - 1, y + r) + 1), np.arange(max(0, x - r), min(gw - 1, x + r) + 1)
         js = (ys[:, None] * gw + xs[None, :]).ravel()
         js = js[fvalid[js]]
-        if js.size > 9:
+        if js.size > 9 and alpha >= 0:
             # A large window: only the candidates that can win get the exact call.  The metric is a sum of non-negative terms (alpha
             # >= 0), so its fp32 value lies within a few 2^-24 of the float64 value of the same expression, relatively: a candidate
             # more than 1e-5 above the smallest float64 value cannot be the fp32 minimum.  Non-finite values take the exact call.
@@ -107,11 +108,11 @@ def project(oracle, F, M, T, gw, intr, r, weighted, alpha=2e2, dist_scale=1.0):
             d = F32(oracle.metric8(q, F[j], alpha))
             if not d < np.inf:
                 continue
-            key = (int(d.view(np.uint32)), int(j))
+            key = (d, int(j))                                    # (float32 compares: -0 and +0 tie)
             if best is None or key < best:
                 best = key
         if best is not None:
-            d = F32(F32(dist_scale) * np.uint32(best[0]).view(F32))
+            d = F32(F32(dist_scale) * best[0])
             nn_id[i] = (d, best[1])
             NN[i, :3] = F[best[1], :3]
     miss = nn_id["id"] == NONE

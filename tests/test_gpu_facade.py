@@ -185,6 +185,32 @@ def test_error_paths(engine):
     assert (g.getAlpha(), g.getMaxIterations(), g.getAngleThreshold(), g.getTranslationThreshold()) == (50.0, 7, 0.5, 2.0)
     with pytest.raises(engine.ICPError):
         g.setAlpha(0.0)
+    # a NaN or infinite alpha orders no distances: refused like zero (ICP_EINVAL = 1) by every entry point that takes alpha, and the
+    # handle keeps the alpha it had; every finite one — negative, denormal, huge — is accepted
+    for bad in (float("nan"), float("inf"), float("-inf")):
+        with pytest.raises(engine.ICPError, match="alpha parameter cannot be NaN or infinite") as e:
+            g.setAlpha(bad)
+        assert e.value.code == 1 and g.getAlpha() == 50.0
+        h = engine.ICP(0)
+        with pytest.raises(engine.ICPError, match="alpha parameter cannot be NaN or infinite") as e:
+            h.init(16, 4, bad)
+        assert e.value.code == 1
+        with pytest.raises(engine.ICPError):
+            h.init(16, 4, bad, batch=3)
+        h.close()
+        B = engine.ICPBatch([0])
+        with pytest.raises(engine.ICPError) as e:
+            B.init(2, 16, 4, bad)
+        assert e.value.code == 1
+        B.close()
+        P = engine.ICPPyramid(0)
+        with pytest.raises(engine.ICPError, match="alpha parameter cannot be NaN or infinite") as e:
+            P.init(64, [4, 4], bad)
+        assert e.value.code == 1
+        P.close()
+    for fine in (-1e5, -1e-3, 1e-30, 1e-40, 1e38):
+        g.setAlpha(fine)
+        assert g.getAlpha() == float(np.float32(fine))
     g.close()
 
 
