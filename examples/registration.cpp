@@ -7,7 +7,7 @@
 //   registration A B                      data/A.bin, data/B.bin — or A and B themselves when they name existing files
 //   ... [--out FILE] [--device N] [--reference-order] [--svd] [--reject-invalid] [--max-dist MM] [--trim FRACTION]
 //       [--point-to-plane MU] [--colored KAPPA] [--robust KIND:SCALE] [--plane-to-plane EPS] [--symmetric] [--one-to-one]
-//       [--reciprocal [GAP]] [--projective [RADIUS]] [--evaluate MAXDIST] [--pyramid LEVELS[:MAXDZ]]
+//       [--median-factor F] [--reciprocal [GAP]] [--projective [RADIUS]] [--evaluate MAXDIST] [--pyramid LEVELS[:MAXDZ]]
 //
 // --reject-invalid / --max-dist: correspondence rejection (icp_set_rejection: pairs with a pixel without depth at either end / pairs
 // farther apart than MM get weight 0).  --trim: trimmed ICP (icp_set_trimming: every iteration keeps the closest FRACTION in (0, 1] of the
@@ -20,6 +20,8 @@
 // --symmetric: symmetric ICP (icp_set_symmetric; Rusinkiewicz 2019): point-to-plane along the mean of both frames' grid normals, the
 // rotation split between the frames; implies --point-to-plane 0 when no MU is given.
 // --one-to-one: one-to-one correspondences (icp_set_unique): of the pairs that share a fixed point only the closest keeps its weight.
+// --median-factor: median-distance rejection (icp_set_median_rejection): every iteration gives the pairs farther apart than F (> 0)
+// times that iteration's median pair distance weight 0.
 // --reciprocal: reciprocal correspondences (icp_set_reciprocal): a pair keeps its weight only if its fixed point, searching the moving
 // frame, finds the pair's moving point again, or one within GAP mm of it (default 0: exactly that point).
 // --projective: projective data association (icp_set_projective): every moving landmark is paired with the closest fixed landmark of the
@@ -62,7 +64,7 @@ std::string data_path (const std::string &name) { return exists (name) ? name : 
 
 template <cl_algo::ICP::ICPStepConfigT RC>
 int run (int device, icp::Mode mode, const std::vector<icp_float8> &pc1, const std::vector<icp_float8> &pc2, const std::string &out,
-         int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa, icp::RobustLoss robust, float gicp_eps, bool symmetric, bool one_to_one,
+         int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa, icp::RobustLoss robust, float gicp_eps, bool symmetric, bool one_to_one, float median_factor,
          float reciprocal, int projective, float evaluate)
 {
     ICPReg<RC, cl_algo::ICP::ICPStepConfigW::WEIGHTED> app (device, mode);
@@ -70,6 +72,7 @@ int run (int device, icp::Mode mode, const std::vector<icp_float8> &pc1, const s
     if (reciprocal >= 0.f) app.setReciprocal (true, reciprocal);
     if (projective >= 0) app.setProjective (true, 128, kLmFx, kLmFy, kLmCx, kLmCy, (uint32_t) projective);
     if (one_to_one) app.setUnique (true);
+    if (median_factor > 0.f) app.setMedianRejection (median_factor);
     if (trim != 1.f) app.setTrimming (trim);
     if (robust.loss != icp::RobustLoss::NONE) app.setRobustLoss (robust);
     if (gicp_eps > 0.f) app.setPlaneToPlane (gicp_eps);
@@ -102,7 +105,7 @@ void check_level (icp_handle h, int rc) { if (rc != ICP_OK) throw std::runtime_e
 // the same registration through cl_algo::ICP::ICPPyramid: the options on every level's handle, the level's own grid width
 template <cl_algo::ICP::ICPStepConfigT RC>
 int run_pyramid (int device, icp::Mode mode, unsigned levels, float max_dz, const std::vector<icp_float8> &pc1, const std::vector<icp_float8> &pc2, const std::string &out,
-                 int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa, icp::RobustLoss robust, float gicp_eps, bool symmetric, bool one_to_one,
+                 int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa, icp::RobustLoss robust, float gicp_eps, bool symmetric, bool one_to_one, float median_factor,
                  float reciprocal, int projective, float evaluate)
 {
     cl_algo::ICP::ICPPyramid<RC, cl_algo::ICP::ICPStepConfigW::WEIGHTED> pyr (icp::Env (device), mode);
@@ -119,6 +122,7 @@ int run_pyramid (int device, icp::Mode mode, unsigned levels, float max_dz, cons
             check_level (h, icp_set_projective (h, 1, gw, kLmFx / f, kLmFy / f, (kLmCx - half) / f, (kLmCy - half) / f, (uint32_t) projective));
         }
         if (one_to_one) check_level (h, icp_set_unique (h, 1));
+        if (median_factor > 0.f) check_level (h, icp_set_median_rejection (h, median_factor));
         if (trim != 1.f) check_level (h, icp_set_trimming (h, trim));
         if (robust.loss != icp::RobustLoss::NONE) check_level (h, icp_set_robust_loss (h, robust.loss, robust.scale));
         if (gicp_eps > 0.f) check_level (h, icp_set_plane_to_plane (h, gicp_eps));
@@ -160,7 +164,7 @@ int main (int argc, char **argv)
     std::vector<std::string> names;
     std::string out;
     int device = 0; bool svd = false, symmetric = false, one_to_one = false;
-    int reject_flags = 0; float max_dist = 0.f, trim = 1.f, p2pl_mu = -1.f, kappa = -1.f, gicp_eps = 0.f, evaluate = -1.f, reciprocal = -1.f; int projective = -1;     // (p2pl_mu < 0: point-to-point; kappa < 0: not colored; gicp_eps 0: off; evaluate < 0: no quality report; reciprocal < 0: off)
+    int reject_flags = 0; float max_dist = 0.f, trim = 1.f, p2pl_mu = -1.f, kappa = -1.f, gicp_eps = 0.f, evaluate = -1.f, reciprocal = -1.f, median_factor = 0.f; int projective = -1;     // (p2pl_mu < 0: point-to-point; kappa < 0: not colored; gicp_eps 0: off; evaluate < 0: no quality report; reciprocal < 0: off)
     icp::RobustLoss robust;
     unsigned pyramid_levels = 0; float pyramid_dz = 0.f;       // (0 levels: one level, no pyramid object)
     icp::Mode mode = icp::Mode::FAST;
@@ -207,6 +211,10 @@ int main (int argc, char **argv)
         }
         else if (a == "--symmetric") symmetric = true;
         else if (a == "--one-to-one") one_to_one = true;
+        else if (a == "--median-factor" && i + 1 < argc) {
+            median_factor = std::strtof (argv[++i], nullptr);
+            if (!(median_factor > 0.f && std::isfinite (median_factor))) { std::fprintf (stderr, "--median-factor: F must be finite and > 0\n"); return 2; }
+        }
         else if (a == "--reciprocal") {                           // (GAP is optional: taken when the next argument is a number)
             reciprocal = 0.f;
             if (i + 1 < argc) {
@@ -257,10 +265,10 @@ int main (int argc, char **argv)
             read_cloud (data_path (names[0]), pc1); read_cloud (data_path (names[1]), pc2);
         }
         if (pyramid_levels)
-            return svd ? run_pyramid<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pyramid_levels, pyramid_dz, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, reciprocal, projective, evaluate)
-                       : run_pyramid<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pyramid_levels, pyramid_dz, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, reciprocal, projective, evaluate);
-        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, reciprocal, projective, evaluate)
-                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, reciprocal, projective, evaluate);
+            return svd ? run_pyramid<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pyramid_levels, pyramid_dz, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, median_factor, reciprocal, projective, evaluate)
+                       : run_pyramid<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pyramid_levels, pyramid_dz, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, median_factor, reciprocal, projective, evaluate);
+        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, median_factor, reciprocal, projective, evaluate)
+                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, median_factor, reciprocal, projective, evaluate);
     }
     catch (const std::exception &e)
     {

@@ -87,7 +87,7 @@ class TransformKind:             # ICPTransformConfig (include/ICP/algorithms.hp
 
 class Memory:                    # icp_mem in include/icp_amd.h
     F, M, T, TK, MEANS, S, NN_ID, W, SUM_W, REPS, RBC_N, RBC_O, RBC_PERM, RBC_OWNER, RBC_XP, RID, R, RK, NN, QT, TRIM, \
-        NORMALS_F, PLANE_SYSTEM, COLOR_GRAD_F, NORMALS_M, UNIQUE, PAIR_FILTER, RECIPROCAL, REVERSE_ID, PROJECTIVE = range(30)
+        NORMALS_F, PLANE_SYSTEM, COLOR_GRAD_F, NORMALS_M, UNIQUE, PAIR_FILTER, RECIPROCAL, REVERSE_ID, PROJECTIVE, MEDIAN = range(31)
     # reference spellings (ICPStep::Memory, include/ICP/algorithms.hpp:2241-2267)
     D_IN_F, D_IN_M, D_IO_T, H_IO_T = F, M, T, T
 
@@ -182,6 +182,8 @@ def lib():
     sig("icp_set_trimming", i32, vp, f32)
     sig("icp_get_trimming", i32, vp, C.POINTER(f32))
     sig("icp_set_unique", i32, vp, i32)
+    sig("icp_set_median_rejection", i32, vp, f32)
+    sig("icp_get_median_rejection", i32, vp, C.POINTER(f32))
     sig("icp_get_unique", i32, vp, C.POINTER(i32))
     sig("icp_set_reciprocal", i32, vp, i32, C.c_float)
     sig("icp_get_reciprocal", i32, vp, C.POINTER(i32), C.POINTER(C.c_float))
@@ -235,6 +237,7 @@ def lib():
     sig("icp_batch_set_rejection", i32, vp, i32, f32)
     sig("icp_batch_set_trimming", i32, vp, f32)
     sig("icp_batch_set_unique", i32, vp, i32)
+    sig("icp_batch_set_median_rejection", i32, vp, f32)
     sig("icp_batch_set_reciprocal", i32, vp, i32, C.c_float)
     sig("icp_batch_set_projective", i32, vp, i32, u32, f32, f32, f32, f32, u32)
     sig("icp_batch_set_normal_rejection", i32, vp, i32, f32)
@@ -628,6 +631,7 @@ _MEM_DTYPE = {
     Memory.NORMALS_F: (np.float32, 4), Memory.PLANE_SYSTEM: (np.float64, None), Memory.COLOR_GRAD_F: (np.float32, 4),
     Memory.NORMALS_M: (np.float32, 4), Memory.UNIQUE: (np.uint32, None), Memory.PAIR_FILTER: (np.uint32, None),
     Memory.RECIPROCAL: (np.uint32, None), Memory.REVERSE_ID: (DIST_ID, None), Memory.PROJECTIVE: (np.uint32, None),
+    Memory.MEDIAN: (np.uint32, None),
 }
 
 
@@ -782,6 +786,19 @@ class ICPStep:
         v = C.c_int32()
         self._chk(self._L.icp_get_unique(self._h, C.byref(v)))
         return bool(v.value)
+
+    def set_median_rejection(self, factor):
+        """Median-distance rejection (icp_set_median_rejection; not reference behaviour, 0 = off, the default): every iteration rejects
+        the pairs farther apart than factor times the median pair distance of that iteration (geo > factor^2 * the lower median of
+        geo).  It acts behind one-to-one and in front of trimming and the robust loss.  read(Memory.MEDIAN) gives the last
+        iteration's (t_med bits, n, thr bits, accepted)."""
+        self._chk(self._L.icp_set_median_rejection(self._h, float(factor)))
+
+    def median_rejection(self):
+        """The factor of median-distance rejection (0: off)."""
+        v = C.c_float()
+        self._chk(self._L.icp_get_median_rejection(self._h, C.byref(v)))
+        return v.value
 
     def set_reciprocal(self, on=True, max_gap=0.0):
         """Reciprocal correspondences (icp_set_reciprocal; not reference behaviour, off by default): a pair (m_i, f_j) keeps its weight
@@ -1289,6 +1306,10 @@ class ICPBatch:
         """Whether one-to-one correspondences were last switched on for this batch."""
         return getattr(self, "_unique", False)
 
+    def set_median_rejection(self, factor):
+        """ICPStep.set_median_rejection on every registration (icp_batch_set_median_rejection)."""
+        self._chk(self._L.icp_batch_set_median_rejection(self._b, float(factor)))
+
     def set_reciprocal(self, on=True, max_gap=0.0):
         """ICPStep.set_reciprocal on every registration (icp_batch_set_reciprocal)."""
         self._chk(self._L.icp_batch_set_reciprocal(self._b, int(on), float(max_gap) if on else 0.0))
@@ -1404,7 +1425,7 @@ class ICPBatch:
         dt, cols = _MEM_DTYPE[mem]
         sizes = {Memory.T: 32, Memory.TK: 32, Memory.MEANS: 32, Memory.S: 44, Memory.NN_ID: self.m * 8, Memory.R: 36, Memory.RK: 36,
                  Memory.F: self.m * 32, Memory.M: self.m * 32, Memory.W: self.m * 4, Memory.RID: self.m * 4, Memory.TRIM: 16, Memory.UNIQUE: 8, Memory.PAIR_FILTER: 16,
-                 Memory.RECIPROCAL: 16, Memory.REVERSE_ID: self.m * 8, Memory.PROJECTIVE: 16,
+                 Memory.RECIPROCAL: 16, Memory.REVERSE_ID: self.m * 8, Memory.PROJECTIVE: 16, Memory.MEDIAN: 16,
                  Memory.NN: self.m * 16, Memory.QT: self.m * 16, Memory.NORMALS_F: self.m * 16, Memory.PLANE_SYSTEM: 28 * 8,
                  Memory.COLOR_GRAD_F: self.m * 16, Memory.NORMALS_M: self.m * 16}
         nbytes = sizes[mem]

@@ -35,6 +35,7 @@ void free_all (icp_context *h)
     h->quality = icp_context::quality_buffers {};                 // (they were among dev_allocs)
     h->pairs = icp_context::pairs_buffers {};
     h->recip = icp_reciprocal_set {};                              // (likewise; stale: the next handle's moving set is yet to be built)
+    h->median = nullptr;                                           // (likewise: median-distance rejection's words)
     for (int k = 0; k < 2; ++k) {
         if (h->hBand[k]) (void) hipHostFree (h->hBand[k]);
         if (h->hFrame[k]) (void) hipHostFree (h->hFrame[k]);
@@ -77,8 +78,8 @@ uint32_t moving_normals_word (const icp_options &o)    // plane-to-plane and sym
 constexpr int reject_user_flags = ICP_REJECT_INVALID;    // the bits of `reject` that icp_set_rejection takes from the caller as they are
 void derive_params (const icp_options &o, icp_params &p)
 {
-    constexpr uint64_t sum = (uint64_t) ICP_REJECT_INVALID + ICP_REJECT_DIST_ON + ICP_REJECT_TRIM_ON + ICP_REJECT_ROBUST_MASK + ICP_REJECT_UNIQUE_ON + ICP_REJECT_FILTER_MASK + ICP_REJECT_RECIPROCAL_ON + ICP_REJECT_PROJECTIVE_ON;
-    static_assert (sum == (ICP_REJECT_INVALID | ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON | ICP_REJECT_FILTER_MASK | ICP_REJECT_RECIPROCAL_ON | ICP_REJECT_PROJECTIVE_ON),
+    constexpr uint64_t sum = (uint64_t) ICP_REJECT_INVALID + ICP_REJECT_DIST_ON + ICP_REJECT_TRIM_ON + ICP_REJECT_ROBUST_MASK + ICP_REJECT_UNIQUE_ON + ICP_REJECT_FILTER_MASK + ICP_REJECT_RECIPROCAL_ON + ICP_REJECT_PROJECTIVE_ON + ICP_REJECT_MEDIAN_ON;
+    static_assert (sum == (ICP_REJECT_INVALID | ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON | ICP_REJECT_FILTER_MASK | ICP_REJECT_RECIPROCAL_ON | ICP_REJECT_PROJECTIVE_ON | ICP_REJECT_MEDIAN_ON),
                    "every rule's bits in icp_params::reject are its own");
     static_assert (ICP_REJECT_INVALID == 1, "ks_epilogue tests bit 0");
     static_assert (ICP_ROBUST_TUKEY << ICP_REJECT_ROBUST_SHIFT == ICP_REJECT_ROBUST_MASK, "the loss's kind fills the mask's two bits");
@@ -89,7 +90,8 @@ void derive_params (const icp_options &o, icp_params &p)
     p.reject = (uint32_t) o.reject_flags | (dist ? ICP_REJECT_DIST_ON : 0u) | (trim ? ICP_REJECT_TRIM_ON : 0u)
              | ((uint32_t) o.robust << ICP_REJECT_ROBUST_SHIFT) | (o.unique ? ICP_REJECT_UNIQUE_ON : 0u)
              | (o.boundary_gw ? ICP_REJECT_BOUNDARY_ON : 0u) | (o.normal_on ? ICP_REJECT_NORMAL_ON : 0u)
-             | (o.reciprocal ? ICP_REJECT_RECIPROCAL_ON : 0u) | (o.projective ? ICP_REJECT_PROJECTIVE_ON : 0u);
+             | (o.reciprocal ? ICP_REJECT_RECIPROCAL_ON : 0u) | (o.projective ? ICP_REJECT_PROJECTIVE_ON : 0u)
+             | (o.median_factor > 0.f ? ICP_REJECT_MEDIAN_ON : 0u);
     p.reject_max_dist = o.reject_max_dist;
     p.reject_d2 = dist ? (float) ((double) o.reject_max_dist * (double) o.reject_max_dist) : 0.f;     // (the product of two floats is exact in double)
     p.trim_keep = trim ? o.trim_keep : 0.f;
@@ -100,7 +102,7 @@ void derive_params (const icp_options &o, icp_params &p)
 
 // The settings the kernels read from device words instead of captured arguments (a new value touches no graph): which value of the
 // record goes where.  write_words writes the chosen ones (OPT_WORDS: all) in stream order behind whatever the handle's stream holds.
-enum : unsigned { OPT_W_KAPPA = 1u, OPT_W_ROBUST = 2u, OPT_W_EPS = 4u, OPT_W_MIN_COS = 8u, OPT_W_GRID = 16u, OPT_W_GAP = 32u, OPT_W_PROJ = 64u, OPT_WORDS = 127u };
+enum : unsigned { OPT_W_KAPPA = 1u, OPT_W_ROBUST = 2u, OPT_W_EPS = 4u, OPT_W_MIN_COS = 8u, OPT_W_GRID = 16u, OPT_W_GAP = 32u, OPT_W_PROJ = 64u, OPT_W_MEDIAN = 128u, OPT_WORDS = 255u };
 int write_words (icp_context *h, unsigned which)
 {
     const icp_options &o = h->opt;
@@ -116,6 +118,9 @@ int write_words (icp_context *h, unsigned which)
         { OPT_W_PROJ, o.proj_gw, proj }, { OPT_W_PROJ, bits (o.proj_fx), proj + 1 }, { OPT_W_PROJ, bits (o.proj_fy), proj + 2 },
         { OPT_W_PROJ, bits (o.proj_cx), proj + 3 }, { OPT_W_PROJ, bits (o.proj_cy), proj + 4 }, { OPT_W_PROJ, o.proj_radius, proj + 5 },
     };
+    // (median-distance rejection's factor lives in the rule's own allocation: nothing to write before median_ready has made it)
+    if ((which & OPT_W_MEDIAN) && h->median)
+        HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (h->median + icp_median_layout_of (h->p.batch, h->p.m).factor), (int) bits (o.median_factor), 1, h->stream));
     for (const auto &w : words)
         if (which & w.flag) HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (w.word), (int) w.value, 1, h->stream));
     return ICP_OK;
@@ -130,7 +135,7 @@ int write_words (icp_context *h, unsigned which)
 // last buildRBC did not compute — the moving normals, the intensity gradients — needs a new buildRBC, as after a new F.
 // Device work in a fixed order: the open runs end, words, clears, then the stream is drained, so that work later enqueued on any of
 // the handle's streams sees them.  OPT_QUIESCE: the open runs end although nothing is written.
-enum : unsigned { OPT_PARAMS = 128u, OPT_ROUTE = 256u, OPT_QUIESCE = 512u };
+enum : unsigned { OPT_PARAMS = 256u, OPT_ROUTE = 512u, OPT_QUIESCE = 1024u };
 // The word areas (icp_area, icp_kernels.h) on the host, indexed by area: the memory object that reads an area's result words and the
 // test that its feature is on.  commit and mem_of go by it.
 const struct { int mem; bool (*on) (const icp_params &); } area_features[ICP_AREA_COUNT] = {
@@ -146,12 +151,15 @@ int commit (icp_context *h, unsigned what)
     bool off[ICP_AREA_COUNT], clears = false;               // per word area: its feature went off
     for (int a = 0; a < ICP_AREA_COUNT; ++a) { off[a] = area_features[a].on (was) && !area_features[a].on (p); clears = clears || off[a]; }
     if (icp_reciprocal (p) && !icp_reciprocal (was)) h->recip.stale = true;
+    const bool median_off = icp_median (was) && !icp_median (p) && h->median;    // (its result words are its own allocation's: ICP_MEM_MEDIAN reads zeros while it is off)
+    clears = clears || median_off;
     if (h->inited && ((what & (OPT_WORDS | OPT_QUIESCE)) || clears)) {
         int rc = set_device (h); if (rc) return rc;
         if ((rc = run_close_all (h))) return rc;
         if ((rc = write_words (h, what & OPT_WORDS))) return rc;
         for (int a = 0; a < ICP_AREA_COUNT; ++a)
             if (off[a]) HIPCHK (h, hipMemsetAsync (icp_words (p, (icp_area) a).result, 0, sizeof (uint32_t) * icp_area_desc_of (a).result * p.batch, h->stream));
+        if (median_off) HIPCHK (h, hipMemsetAsync (h->median, 0, sizeof (uint32_t) * 4u * p.batch, h->stream));
         if ((what & OPT_WORDS) || clears) HIPCHK (h, hipStreamSynchronize (h->stream));
     }
     if (what & OPT_ROUTE) drop_graphs (h);
@@ -228,6 +236,17 @@ int reciprocal_ready (icp_context *h)
     icp_launch_reciprocal_build (p, h->stream, rs);
     HIPCHK (h, hipGetLastError ());
     rs.stale = false;
+    return ICP_OK;
+}
+
+int median_ready (icp_context *h)
+{
+    if (h->median) return ICP_OK;
+    const icp_median_layout l = icp_median_layout_of (h->p.batch, h->p.m);
+    int rc = set_device (h); if (rc) return rc;
+    if ((rc = dalloc (h, &h->median, l.total))) return rc;                   // (zeroed: the histograms and the arrival counters start clean)
+    float f = h->opt.median_factor; uint32_t u; std::memcpy (&u, &f, sizeof u);
+    HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (h->median + l.factor), (int) u, 1, h->stream));
     return ICP_OK;
 }
 }  // namespace icp_host
@@ -457,6 +476,7 @@ static mem_desc mem_of (const icp_context *h, uint32_t b, int mem)
         case ICP_MEM_QT: return { p.PM + b * m, m * 16, nullptr };
         case ICP_MEM_W: return { reinterpret_cast<const float *> (p.PF + b * m) + 3, m * 4, nullptr };    // (the .w lane of the matched points: a strided read)
         case ICP_MEM_REVERSE_ID: return { h->recip.nn_id ? h->recip.nn_id + b * m : nullptr, m * 8, nullptr };   // (allocated with the rule's first use)
+        case ICP_MEM_MEDIAN: return { h->median ? h->median + 4u * b : nullptr, 16, nullptr };                  // (likewise; before that it reads zeros)
         case ICP_MEM_NORMALS_F: return { icp_normals_f (p) + b * m, m * 16, "ICP_MEM_NORMALS_F" };
         case ICP_MEM_COLOR_GRAD_F: return { icp_color_grad_f (p) + b * m, m * 16, "ICP_MEM_COLOR_GRAD_F" };
         case ICP_MEM_NORMALS_M: return { icp_normals_m (p) + b * m, m * 16, "ICP_MEM_NORMALS_M" };
@@ -531,6 +551,7 @@ int icp_read_b (icp_handle h, uint32_t b, int mem, void *host_dst, size_t bytes)
     const mem_desc d = mem_of (h, b, mem);
     if (!d.bytes) return fail (h, ICP_EINVAL, "unknown icp_mem value");
     if (bytes > d.bytes) return fail (h, ICP_EINVAL, "icp_read: more bytes requested than the object holds");
+    if (!d.ptr && mem == ICP_MEM_MEDIAN) { std::memset (host_dst, 0, bytes); return ICP_OK; }     // (the rule has not run since icp_init: its words are yet to be allocated)
     if (!d.ptr) return fail (h, ICP_ESTATE, "icp_read: ICP_MEM_REVERSE_ID: no back search has run since icp_init (icp_set_reciprocal)");
     if ((rc = set_device (h))) return rc;
     const void *src = d.ptr;
@@ -554,6 +575,7 @@ int icp_device_ptr (icp_handle h, int mem, void **dptr) try
     if (!dptr) return fail (h, ICP_EINVAL, "null pointer");
     const mem_desc d = mem_of (h, 0, mem);
     if (!d.bytes) return fail (h, ICP_EINVAL, "unknown icp_mem value");
+    if (!d.ptr && mem == ICP_MEM_MEDIAN) return fail (h, ICP_ESTATE, "icp_device_ptr: ICP_MEM_MEDIAN: the rule has not run since icp_init (icp_set_median_rejection)");
     if (!d.ptr) return fail (h, ICP_ESTATE, "icp_device_ptr: ICP_MEM_REVERSE_ID: no back search has run since icp_init (icp_set_reciprocal)");
     if ((rc = set_device (h))) return rc;
     if ((rc = materialize_outputs (h, mem))) return rc;
@@ -608,7 +630,7 @@ int icp_step (icp_handle h, int config) try
     icp_params p = h->p; p.check = 0; p.hmirror = nullptr; p.hstate = nullptr;
     { const long long kb = h->k_base; note_enqueue (h); if (kb >= 0) h->k_base = kb + 1; }
     note_outputs_stored (h);
-    icp_launch_iteration (p, h->stream, &h->recip);
+    icp_launch_iteration (p, h->stream, &h->recip, h->median);
     HIPCHK (h, hipGetLastError ());
     return ICP_OK;
 }
@@ -820,6 +842,28 @@ int icp_get_unique (icp_handle h, int *on) try
     api_guard guard_ (h);
     if (!h || !on) return ICP_EINVAL;
     *on = h->opt.unique ? 1 : 0;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+// median-distance rejection (icp_median.hip).  On <-> off changes which kernels run — the REJ search, the rule's launches, on point-to-point
+// the apply pass, no chained form —: a change of route.  A new factor while the rule stays on goes to its device word alone: no graph
+// is touched.  The rule's words are allocated by the next call that enqueues an iteration (need: median_ready).
+int icp_set_median_rejection (icp_handle h, float factor) try
+{
+    api_guard guard_ (h);
+    if (!(factor >= 0.f && std::isfinite (factor))) return fail (h, ICP_EINVAL, "icp_set_median_rejection: factor must be finite and >= 0");
+    if (!h) return fail (h, ICP_EINVAL, "icp_set_median_rejection: null handle");
+    { int rc = outputs_before_change (h); if (rc) return rc; }
+    const bool was = h->opt.median_factor > 0.f, on = factor > 0.f;
+    h->opt.median_factor = factor;
+    return commit (h, on != was ? OPT_ROUTE | OPT_W_MEDIAN : on ? OPT_W_MEDIAN : 0u);
+}
+ICP_CATCH_ALL
+int icp_get_median_rejection (icp_handle h, float *factor) try
+{
+    api_guard guard_ (h);
+    if (!h || !factor) return ICP_EINVAL;
+    *factor = h->opt.median_factor;
     return ICP_OK;
 }
 ICP_CATCH_ALL
@@ -1460,7 +1504,7 @@ int icp_time_masked (icp_handle h, uint32_t mask, uint32_t iterations, uint32_t 
     graph_entry ge;
     // (the per-query outputs follow the policy of the fixed-length graphs: stored by the last iteration only in fused mode)
     if ((rc = capture_graph (h, [&] {
-             for (uint32_t k = 0; k < iterations; ++k) { p.emit = (k + 1 == iterations) ? 1 : 0; icp_launch_masked (p, h->stream, mask, &h->recip); }
+             for (uint32_t k = 0; k < iterations; ++k) { p.emit = (k + 1 == iterations) ? 1 : 0; icp_launch_masked (p, h->stream, mask, &h->recip, h->median); }
          }, &ge))) return rc;
     hipError_t e = hipGraphLaunch (ge.exec, h->stream);                 // warm-up
     if (e == hipSuccess) e = hipEventRecord (h->ev0, h->stream);
@@ -1490,7 +1534,7 @@ int icp_debug_stamps (icp_handle h, unsigned long long *out, uint32_t nblocks) t
     note_enqueue (h); note_outputs_stored (h);
     if (e == hipSuccess) {
         if (icp_route_of (p).chained) icp_launch_chain (p, h->stream, 2);
-        else icp_launch_masked (p, h->stream, p.fused ? 1u | 8u : 1u, &h->recip);
+        else icp_launch_masked (p, h->stream, p.fused ? 1u | 8u : 1u, &h->recip, h->median);
         e = hipGetLastError ();
     }
     if (e == hipSuccess) e = hipStreamSynchronize (h->stream);
@@ -1517,7 +1561,7 @@ int icp_profile_run (icp_handle h, uint32_t iterations, float *out_ms, float *to
         hipEvent_t *x = &ev[(size_t) r * 5];
         e = hipEventRecord (x[0], h->stream);                                             // (trimming, one-to-one, the pair filter, reciprocal correspondences on: their passes time with the search)
         for (int k = 0; k < 4; ++k) {
-            icp_launch_masked (p, h->stream, 1u << k, &h->recip);
+            icp_launch_masked (p, h->stream, 1u << k, &h->recip, h->median);
             if (e == hipSuccess) e = hipEventRecord (x[k + 1], h->stream);
         }
     }

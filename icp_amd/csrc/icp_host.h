@@ -83,6 +83,7 @@ struct icp_options {
     int reject_flags = 0; float reject_max_dist = 0.f;      // icp_set_rejection
     float trim_keep = 1.f;                       // icp_set_trimming (1: off)
     bool unique = false;                         // icp_set_unique
+    float median_factor = 0.f;                   // icp_set_median_rejection (0: off); device word icp_median_layout::factor of the rule's own allocation
     bool reciprocal = false; float reciprocal_gap = 0.f;    // icp_set_reciprocal (0 while off); device word ICP_AREA_RECIPROCAL .settings
     // icp_set_projective (all zero while off); device words ICP_AREA_PROJECTIVE .settings [0 .. 5]
     bool projective = false; uint32_t proj_gw = 0, proj_radius = 0; float proj_fx = 0.f, proj_fy = 0.f, proj_cx = 0.f, proj_cy = 0.f;
@@ -155,6 +156,9 @@ struct icp_context {
     // reciprocal correspondences' own buffers (icp_rbc_set.h; allocated when the rule is first needed, each on its own; freed with the others
     // by icp_init): the moving set, the reverse state, the back search's per-query outputs — and whether the moving set is stale
     icp_reciprocal_set recip;
+    // median-distance rejection's words (icp_median_layout, icp_kernels.h; allocated zeroed when the rule is first needed on an initialised
+    // handle, freed with the others by icp_init): the result words ICP_MEM_MEDIAN reads, the selection's state, the factor
+    uint32_t *median = nullptr;
     float *dCloud = nullptr, *dCloudOut = nullptr; uint32_t cloud_cap = 0;
     std::map<uint64_t, icp_host::graph_entry> graphs;      // key: iterations << 3 | check << 2 | parity (+ fresh, + kind: see get_graph)
     uint32_t parity = 0;                         // tracking: which landmark buffers are the fixed / moving set (graphs hold pointers): frame f -> f mod 3
@@ -257,6 +261,9 @@ void normals_m_follow (icp_context *h, uint32_t b0, uint32_t nb);
 // reciprocal correspondences: the rule's buffers exist and the moving set describes M — allocated at the first need, rebuilt on the handle's
 // stream when stale.  need (h, true) calls it in front of every enqueue of an iteration; icp_build_rbc behind the fixed set's construction.
 int reciprocal_ready (icp_context *h);
+// median-distance rejection: the rule's words exist and hold the factor — allocated at the first need.  need (h, true) calls it in front of
+// every enqueue of an iteration while the rule is on.
+int median_ready (icp_context *h);
 
 // Captures the launches `launches ()` enqueues on the handle's stream into a graph (instantiate: also into an executable one).
 // Whatever fails, the stream has left capture mode and nothing is leaked when this returns.

@@ -131,6 +131,7 @@ struct icp_params {
 #define ICP_REJECT_FILTER_MASK (ICP_REJECT_BOUNDARY_ON | ICP_REJECT_NORMAL_ON)
 #define ICP_REJECT_RECIPROCAL_ON 0x01000000u   // icp_params::reject: reciprocal correspondences are on (icp_set_reciprocal: the REJ kernels, plus the back search and k_reciprocal: icp_launch_reciprocal)
 #define ICP_REJECT_PROJECTIVE_ON 0x00800000u   // icp_params::reject: projective data association is on (icp_set_projective: k_projective in place of the search: icp_launch_projective)
+#define ICP_REJECT_MEDIAN_ON 0x00400000u   // icp_params::reject: median-distance rejection is on (icp_set_median_rejection: the REJ kernels, plus the rule's launches: icp_launch_median)
 static_assert (sizeof (icp_params) == 480, "icp_params grew: the hidden kernel arguments of every kernel would move");
 
 // rejection on: the sum-W formulas in every mode, and a step of nothing accepted (sum W == 0) is the identity
@@ -144,6 +145,8 @@ static __host__ __device__ __forceinline__ bool icp_pair_filter (const icp_param
 static __host__ __device__ __forceinline__ bool icp_reciprocal (const icp_params &p) { return (p.reject & ICP_REJECT_RECIPROCAL_ON) != 0u; }
 // projective data association (icp_projective.hip): the pairs come from a projection onto the fixed grid instead of the RBC search
 static __host__ __device__ __forceinline__ bool icp_projective (const icp_params &p) { return (p.reject & ICP_REJECT_PROJECTIVE_ON) != 0u; }
+// median-distance rejection (icp_median.hip): a candidate farther than factor times the iteration's median pair distance loses its weight
+static __host__ __device__ __forceinline__ bool icp_median (const icp_params &p) { return (p.reject & ICP_REJECT_MEDIAN_ON) != 0u; }
 // the moving frame's normals are needed: by a metric (p.gicp: plane-to-plane, symmetric) or by normal rejection, whatever the metric
 static __host__ __device__ __forceinline__ bool icp_moving_normals (const icp_params &p) { return p.gicp != 0u || (p.reject & ICP_REJECT_NORMAL_ON) != 0u; }
 // the robust loss's kind (ICP_ROBUST_HUBER 1, CAUCHY 2, TUKEY 3; 0: off).  Its scale k is a device word (icp_robust_scale).
@@ -159,6 +162,18 @@ static __host__ __device__ __forceinline__ double icp_robust_omega (uint32_t los
 // Trimming (icp_trim.hip; its words: ICP_AREA_TRIM below)
 #define ICP_TRIM_ONE_BLOCK_MAX 16384u    // up to this many pairs per registration: the selection is one workgroup's (k_trim_select)
 #define ICP_TRIM_BINS 2048u
+
+// Median-distance rejection (icp_median.hip): its words are an allocation of their own on the handle (icp_context::median, made at the
+// first need, freed by icp_init) and reach the kernels as an argument.  Offsets in uint32 words: [batch][4] the result words
+// (t_med bits, n, thr bits, accepted: ICP_MEM_MEDIAN), [batch][4] the multi-workgroup selection's state, [batch][ICP_TRIM_BINS] its
+// histograms, the factor (float bits: a new factor touches no graph) and a word of padding, then [batch][m] the keys where the
+// selection is not one workgroup's (m > ICP_TRIM_ONE_BLOCK_MAX).
+struct icp_median_layout { size_t result, state, hist, factor, keys, total; };
+static __host__ __device__ inline icp_median_layout icp_median_layout_of (uint32_t batch, uint32_t m)
+{
+    const size_t B = batch, fixed = (8u + ICP_TRIM_BINS) * B;
+    return { 0u, 4u * B, 8u * B, fixed, fixed + 2u, fixed + 2u + (m > ICP_TRIM_ONE_BLOCK_MAX ? B * m : 0u) };
+}
 
 // The plane system (icp_set_error_metric, icp_p2pl.hip): point-to-plane ICP and colored ICP (ICP_METRIC_COLORED), the point-to-plane
 // system with a photometric term.  [batch][28] ICP_MEM_PLANE_SYSTEM (A's upper triangle, b, status), [batch][27][icp_p2pl_nblk] the
@@ -344,6 +359,7 @@ struct icp_route {
     bool filter;                 // k_pair_filter
     bool reciprocal;             // k_reciprocal_state + the back search + k_reciprocal (icp_launch_reciprocal)
     bool unique;                 // k_unique_claim + k_unique_resolve
+    uint32_t median;             // median-distance rejection: 0, 1 (k_median) or 4 launches (k_median_select_pass<0 .. 2>, k_median_reject)
     uint32_t select;             // trimming's selection: 0, 1 (k_trim_select) or 3 launches (k_trim_select_pass<0 .. 2>)
     icp_apply_kind apply;        // the pass that writes the search's partials again from the weights
     icp_tail_kind tail;          // k_finalize_fused / k_moment_level1 + k_finalize_fused / k_means, k_sij, k_finalize / k_plane_moments, k_p2pl_finalize
@@ -356,10 +372,11 @@ void icp_launch_build_rbc (const icp_params &p, hipStream_t s);
 void icp_launch_search (const icp_params &p, hipStream_t s);
 // rs: what reciprocal correspondences keep outside icp_params (icp_reciprocal_set, icp_rbc_set.h: the moving set, the reverse state, the
 // back search's outputs); a route with the rule on needs it, every other ignores it
+// median: the words of median-distance rejection (icp_median_layout), which live outside icp_params likewise
 struct icp_reciprocal_set;
-void icp_launch_iteration (const icp_params &p, hipStream_t s, const icp_reciprocal_set *rs = nullptr);
+void icp_launch_iteration (const icp_params &p, hipStream_t s, const icp_reciprocal_set *rs = nullptr, uint32_t *median = nullptr);
 // any subset of an iteration's stages (bit 0 the search with the passes behind it, 1 means, 2 sij, 3 finalize; 4: an empty kernel)
-void icp_launch_masked (const icp_params &p, hipStream_t s, unsigned mask, const icp_reciprocal_set *rs = nullptr);
+void icp_launch_masked (const icp_params &p, hipStream_t s, unsigned mask, const icp_reciprocal_set *rs = nullptr, uint32_t *median = nullptr);
 void icp_launch_chain (const icp_params &p, hipStream_t s, uint32_t iterations, bool fresh = false);
 void icp_launch_chain_one (const icp_params &p, hipStream_t s, uint32_t j, bool fresh, bool emit);   // launch j of a chain (j = 0: reads the user-visible state)
 void icp_launch_chain_end (const icp_params &p, hipStream_t s, uint32_t launches);                  // after `launches` chained launches: the last moments -> p.st (and p.hstate)
@@ -374,6 +391,7 @@ void icp_launch_chain_one_rej (const icp_params &p, hipStream_t s, uint32_t j, b
 void icp_launch_trim_select (const icp_params &p, hipStream_t s, uint32_t launches);   // icp_trim.hip: k_trim_select (1) or k_trim_select_pass<0 .. 2> (3: icp_route::select)
 void icp_launch_trim_apply (const icp_params &p, hipStream_t s);             // icp_trim.hip: k_trim_apply<fused?>
 void icp_launch_unique (const icp_params &p, hipStream_t s);                 // icp_unique.hip: k_unique_claim + k_unique_resolve
+void icp_launch_median (const icp_params &p, hipStream_t s, uint32_t *words, uint32_t launches);   // icp_median.hip: k_median (1) or k_median_select_pass<0 .. 2> + k_median_reject (4: icp_route::median)
 void icp_launch_reciprocal (const icp_params &p, hipStream_t s, const icp_reciprocal_set *rs);   // icp_reciprocal.hip: k_reciprocal_state + the back search + k_reciprocal
 void icp_launch_reciprocal_build (const icp_params &p, hipStream_t s, const icp_reciprocal_set &rs);   // icp_reciprocal.hip: buildRBC over M into the moving set
 void icp_launch_projective (const icp_params &p, hipStream_t s);             // icp_projective.hip: k_projective, in place of the search (icp_set_projective)

@@ -324,6 +324,8 @@ static int track_submit (icp_context *h, const void *cloud, int warm_start, bool
         return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while normal rejection is on (icp_set_normal_rejection)");
     if (h->opt.reciprocal)
         return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while reciprocal correspondences are on (icp_set_reciprocal)");
+    if (h->opt.median_factor > 0.f)       // (the rule's words and launches stay out of the gated tracking path)
+        return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while median-distance rejection is on (icp_set_median_rejection)");
     if (h->opt.projective)
         return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while projective data association is on (icp_set_projective)");
     // (point-to-plane: each frame's normals come from its own landmarks, which only buildRBC can give it — ICP_NORMALS_GRID)

@@ -15,7 +15,7 @@ from .io import load_pc8d, save_pc8d
 def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, angle_threshold=0.001,
                     translation_threshold=0.01, reduce_mode=ReduceMode.FUSED, reject_invalid=False, max_dist=None, trim=1.0,
                     point_to_plane=None, colored=None, robust=None, plane_to_plane=None, symmetric=False, one_to_one=False,
-                    normal_angle=None, reject_boundary=False, pyramid=None, reciprocal=None, projective=None):
+                    normal_angle=None, reject_boundary=False, pyramid=None, reciprocal=None, projective=None, median_factor=None):
     """Returns (T[8], k, latency_ms, transformed moving cloud).  reject_invalid / max_dist: correspondence rejection
     (ICPStep.set_rejection), trim: the fraction of pairs trimmed ICP keeps (ICPStep.set_trimming; 1.0: off), point_to_plane: mu of
     point-to-plane ICP with the fixed frame's normals from its 128 x 128 landmark grid (ICPStep.set_error_metric; None: off),
@@ -29,7 +29,8 @@ def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, a
     (ICPStep.set_boundary_rejection), reciprocal: max_gap in mm of reciprocal correspondences — a pair keeps its weight only if its fixed
     point finds the pair's moving point again, or one within max_gap of it (ICPStep.set_reciprocal; 0: exact only, None: off), projective: the window radius in [0, 8] of projective data association — the pairs
     come from projecting the moving landmarks onto the fixed landmark grid with the frame's pinhole model (landmark_intrinsics) instead
-    of from the RBC search (ICPStep.set_projective; None: off); pyramid: (levels, max_dz) of a coarse-to-fine registration (ICPPyramid: 128, 64, 32, .. wide
+    of from the RBC search (ICPStep.set_projective; None: off), median_factor: every iteration rejects the pairs farther apart than
+    median_factor times that iteration's median pair distance (ICPStep.set_median_rejection; None: off); pyramid: (levels, max_dz) of a coarse-to-fine registration (ICPPyramid: 128, 64, 32, .. wide
     levels with 256, 64, 64, .. representatives, 2 x 2 means within a z band of max_dz mm, 0: no band; every option above applies to
     every level with the level's own grid width; k is then the list of the levels' counts, finest first; None: one level); none is
     the reference's behaviour, all are off by default."""
@@ -69,7 +70,7 @@ def level_intrinsics(intr, factor):
 
 
 def _apply_options(reg, side, reduce_mode, reject_invalid, max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric,
-                   one_to_one, normal_angle, reject_boundary, reciprocal=None, projective=None):
+                   one_to_one, normal_angle, reject_boundary, reciprocal=None, projective=None, median_factor=None):
     """register_clouds' options on one handle whose landmark grid is `side` wide (640 x 480 clouds -> 128 x 128 landmarks, row-major;
     a pyramid level l: 128 >> l)."""
     if projective is not None:
@@ -87,6 +88,8 @@ def _apply_options(reg, side, reduce_mode, reject_invalid, max_dist, trim, point
         reg.set_reciprocal(True, reciprocal)
     if one_to_one:
         reg.set_unique(True)
+    if median_factor is not None:
+        reg.set_median_rejection(median_factor)
     if trim != 1.0:
         reg.set_trimming(trim)
     if robust is not None:
@@ -110,18 +113,18 @@ def _apply_options(reg, side, reduce_mode, reject_invalid, max_dist, trim, point
 
 def _register(evaluate, fixed, moving, device, a, c, max_iterations, angle_threshold, translation_threshold, reduce_mode, reject_invalid,
               max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one, normal_angle, reject_boundary,
-              pyramid=None, reciprocal=None, projective=None):
+              pyramid=None, reciprocal=None, projective=None, median_factor=None):
     """(T[8], k, latency_ms, transformed moving cloud, Quality record or None): register_clouds' options; evaluate None: no evaluation."""
     return _run(False, **locals())[:5]
 
 
 def _run(pairs, evaluate, fixed, moving, device, a, c, max_iterations, angle_threshold, translation_threshold, reduce_mode, reject_invalid,
          max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one, normal_angle, reject_boundary,
-         pyramid=None, reciprocal=None, projective=None):
+         pyramid=None, reciprocal=None, projective=None, median_factor=None):
     """_register's five values and a sixth: with `pairs` the Pairs.EVALUATED correspondence set at max_dist = evaluate (None: 0, no
     distance test), else None."""
     options = (reduce_mode, reject_invalid, max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one,
-               normal_angle, reject_boundary, reciprocal, projective)
+               normal_angle, reject_boundary, reciprocal, projective, median_factor)
     if pyramid is not None:
         levels, max_dz = pyramid
         reg = ICPPyramid(device)
@@ -222,6 +225,14 @@ def _robust(s):
     return RobustLoss.NAMES[kind.lower()], v
 
 
+def _median_factor(s):
+    """a finite factor > 0"""
+    v = float(s)
+    if not (v > 0.0 and math.isfinite(v)):
+        raise argparse.ArgumentTypeError("must be finite and > 0, got %s" % s)
+    return v
+
+
 def _pyramid(s):
     """LEVELS[:MAXDZ], e.g. 3 or 3:24 -> (levels, max_dz); LEVELS in [1, 5], MAXDZ finite and >= 0 (mm; 0: no band)."""
     levels, sep, dz = s.partition(":")
@@ -250,6 +261,9 @@ def main(argv=None):
     ap.add_argument("--one-to-one", action="store_true",
                     help="one-to-one correspondences: of the pairs that share a fixed point only the closest keeps its weight, "
                          "before trimming (not reference behaviour)")
+    ap.add_argument("--median-factor", type=_median_factor, default=None, metavar="F",
+                    help="median-distance rejection: in every iteration give the pairs farther apart than F times that iteration's "
+                         "median pair distance weight 0, e.g. 2; behind --one-to-one, before --trim (not reference behaviour)")
     ap.add_argument("--reciprocal", type=_point_weight, nargs="?", const=0.0, default=None, metavar="GAP",
                     help="reciprocal correspondences: a pair keeps its weight only if its fixed point, searching the moving frame, "
                          "finds the pair's moving point again, or one within GAP mm of it (default 0: exactly that point); before "
@@ -295,7 +309,8 @@ def main(argv=None):
     options = dict(device=args.device, a=args.alpha, reject_invalid=args.reject_invalid, max_dist=args.max_dist, trim=args.trim,
                    point_to_plane=args.point_to_plane, colored=args.colored, robust=args.robust, plane_to_plane=args.plane_to_plane,
                    symmetric=args.symmetric, one_to_one=args.one_to_one, normal_angle=args.normal_angle,
-                   reject_boundary=args.reject_boundary, pyramid=args.pyramid, reciprocal=args.reciprocal, projective=args.projective)
+                   reject_boundary=args.reject_boundary, pyramid=args.pyramid, reciprocal=args.reciprocal, projective=args.projective,
+                   median_factor=args.median_factor)
     members = None
     if args.pairs is not None:
         T, k, ms, out, quality, members = register_with_pairs(fixed, moving, args.evaluate, **options)

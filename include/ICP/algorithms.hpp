@@ -625,6 +625,12 @@ namespace ICP
         void setUnique (bool on) { check (icp_set_unique (h, on ? 1 : 0)); }
         bool getUnique () { int on = 0; check (icp_get_unique (h, &on)); return on != 0; }
 
+        /*! \brief Median-distance rejection (icp_set_median_rejection, include/icp_amd.h; not in the reference, 0 = off, the default):
+         *         every iteration rejects the pairs farther apart than factor times the median pair distance of that iteration.  It
+         *         acts behind one-to-one and in front of trimming and the robust loss. */
+        void setMedianRejection (float factor) { check (icp_set_median_rejection (h, factor)); }
+        float getMedianRejection () { float f = 0.f; check (icp_get_median_rejection (h, &f)); return f; }
+
         /*! \brief Reciprocal correspondences (icp_set_reciprocal, include/icp_amd.h; not in the reference, off by default): a pair keeps
          *         its weight only if its fixed point, searching the moving frame, finds the pair's moving point again or one within
          *         max_gap of it; the others get weight 0.  It acts after the boundary and normal rules and before one-to-one

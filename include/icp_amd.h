@@ -95,6 +95,7 @@ typedef enum {
     ICP_MEM_RECIPROCAL = 27,   /* out uint32[4]   reciprocal correspondences, last iteration: n, exact, near, accepted (0 when off) */
     ICP_MEM_REVERSE_ID = 28,   /* out m x {dist,id}  reciprocal correspondences: the back search, fixed-point order, id = index into M */
     ICP_MEM_PROJECTIVE = 29,   /* out uint32[4]   projective data association, last iteration: n, hits, outside, empty (0 when off) */
+    ICP_MEM_MEDIAN = 30,       /* out uint32[4]   median-distance rejection, last iteration: t_med (float bits), n, thr (float bits), accepted (0 when off) */
     ICP_MEM_COUNT_
 } icp_mem;
 
@@ -310,6 +311,44 @@ int icp_get_trimming (icp_handle h, float *keep_fraction);
  * its passes into the search stage.  ICP_EINVAL: on outside {0, 1}. */
 int icp_set_unique (icp_handle h, int on);
 int icp_get_unique (icp_handle h, int *on);
+
+/* Median-distance rejection (PCL: CorrespondenceRejectorMedianDistance; libpointmatcher: MedianDistOutlierFilter; not reference
+ * behaviour): a pair is rejected when it is farther apart than `factor` times the median pair distance of the same iteration.  The
+ * threshold shrinks as the registration converges and scales with the level of a pyramid; its one parameter has no unit.  The rule:
+ *   - factor == 0 is the default and means off: the same kernels, launches, graphs and bits as without it, for every metric.
+ *     factor > 0 and finite turns the rule on; values below 1 are allowed.
+ *   - Candidates are the pairs that the passes in front have left — icp_set_rejection's rules, boundary and normal rejection,
+ *     reciprocal correspondences, one-to-one —, with a weight != 0 and a finite geo.  geo is the quantity the rejection rule defines:
+ *     (ex - f0)^2 + (ey - f1)^2 + (ez - f2)^2 in fp32, summed in that order, with no contraction.  Let n be their number.
+ *   - K = (n + 1) / 2 in integer division, and t_med is the K-th smallest geo among the candidates, counting from 1: the lower median,
+ *     an element of the set — what trimming selects at keep_fraction 0.5.
+ *   - thr = (float) (((double) factor * (double) factor) * (double) t_med), in the order written.  A thr that rounds to +inf accepts
+ *     every candidate; t_med == 0 gives thr == 0.
+ *   - Accepted are the candidates with geo <= thr, an fp32 compare (geo is never negative: the same as a compare of the bit patterns).
+ *   - Every other candidate behaves exactly like a rejected pair: its correspondence is kept, its weight is +0 (written to the W and
+ *     NN outputs), and its moment, mean and S terms — for a plane metric its plane-system terms — are exact zeros.  As with
+ *     rejection, REGULAR mode uses the sum-W formulas with w in {0, 1}.
+ *   - n == 0, or nothing accepted: the sum W == 0 identity step (T unchanged, ICP::run stops).
+ *   - Each registration of a batched handle (icp_init_batched) computes its own n, t_med and thr.  A converged registration of a
+ *     checked run is left alone: its words stay.
+ * The rule runs behind one-to-one and in front of trimming and the robust loss: trimming's candidates, and its n, are the pairs this
+ * rule accepts.  The search is untouched: at the same T the ids, distances and RID are bit-identical to a run with the rule off.  The
+ * median is one number and the counts are integer sums: nothing depends on the order in which the device gets to the pairs.
+ * ICP_MEM_MEDIAN holds (t_med bits, n, thr bits, accepted) of the last iteration per registration; zeros while the rule is off.  With
+ * the rule on the per-query outputs are stored by every iteration, and an iteration is the separate form (icp_run_form is
+ * ICP_FORM_SEPARATE, there is no chained launch).  icp_launches_per_iteration counts what the rule adds behind the search: 1 launch
+ * up to 16384 pairs per registration (one workgroup selects the median, rejects and counts), 4 beyond (three selection passes and
+ * the pass that rejects and counts); on point-to-point also the pass that writes the search's partials again from the weights, unless
+ * another rule runs it anyway.  The plane metrics add nothing more: their moments read the weights.  icp_profile_run counts the
+ * rule's passes into the search stage.
+ * Turning the rule on or off captures the graphs anew; a new factor while it stays on is a parameter update that takes effect in
+ * already captured graphs.  The setting survives icp_init.  It applies to single, batched and icp_batch_* registrations and the level
+ * handles of a pyramid (icp_pyramid_level), to every error metric, both reduce modes, both rotation solvers, the search and
+ * projective association.  Tracking is not provided: icp_track_submit / icp_track_next return ICP_ESTATE while the rule is on, as
+ * with plane-to-plane.
+ * ICP_EINVAL: a null handle, or a negative, NaN or infinite factor. */
+int icp_set_median_rejection (icp_handle h, float factor);
+int icp_get_median_rejection (icp_handle h, float *factor);
 
 /* Reciprocal (forward-backward consistent) correspondences (PCL: setUseReciprocalCorrespondences,
  * CorrespondenceEstimation::determineReciprocalCorrespondences; libpointmatcher; Rusinkiewicz & Levoy's matching taxonomy; not reference
@@ -960,6 +999,7 @@ int icp_batch_set_modes (icp_batch_handle b, int reduce_mode, int power_mode);
 int icp_batch_set_rejection (icp_batch_handle b, int flags, float max_dist);                /* icp_set_rejection on every slot */
 int icp_batch_set_trimming (icp_batch_handle b, float keep_fraction);                        /* icp_set_trimming on every slot */
 int icp_batch_set_unique (icp_batch_handle b, int on);                                       /* icp_set_unique on every slot */
+int icp_batch_set_median_rejection (icp_batch_handle b, float factor);                        /* icp_set_median_rejection on every slot */
 int icp_batch_set_reciprocal (icp_batch_handle b, int on, float max_gap);                    /* icp_set_reciprocal on every slot */
 int icp_batch_set_projective (icp_batch_handle b, int on, uint32_t grid_width, float fx, float fy, float cx, float cy, uint32_t radius);   /* icp_set_projective on every slot */
 int icp_batch_set_normal_rejection (icp_batch_handle b, int on, float min_cos);              /* icp_set_normal_rejection on every slot */

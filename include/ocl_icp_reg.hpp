@@ -78,6 +78,9 @@ public:
     /*! \brief One-to-one correspondences of the registration (ICPStep::setUnique; not in the reference's demo, off by default). */
     void setUnique (bool on) { reg.setUnique (on); }
     bool getUnique () { return reg.getUnique (); }
+    /*! \brief Median-distance rejection of the registration (ICPStep::setMedianRejection; not in the reference's demo, 0 = off, the default). */
+    void setMedianRejection (float factor) { reg.setMedianRejection (factor); }
+    float getMedianRejection () { return reg.getMedianRejection (); }
     /*! \brief Reciprocal correspondences of the registration (ICPStep::setReciprocal; not in the reference's demo, off by default). */
     void setReciprocal (bool on, float max_gap = 0.f) { reg.setReciprocal (on, max_gap); }
     bool getReciprocal (float *max_gap = nullptr) { return reg.getReciprocal (max_gap); }

@@ -71,6 +71,9 @@ def main(argv):
     other, sources = os.path.abspath(pos[0]), pos[1:] or makefile_sources()
     bad = 0
     for src in sources:
+        if not os.path.exists(os.path.join(other, src)):           # (a unit the other tree does not have: nothing existed before)
+            print("%-36s only here" % src)
+            continue
         rows = compare(src, other, flags)
         names = demangle([r[0] for r in rows])
         for (sym, what, detail), name in zip(rows, names):
