@@ -120,7 +120,7 @@ int write_words (icp_context *h, unsigned which)
     };
     // (median-distance rejection's factor lives in the rule's own allocation: nothing to write before median_ready has made it)
     if ((which & OPT_W_MEDIAN) && h->median)
-        HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (h->median + icp_median_layout_of (h->p.batch, h->p.m).factor), (int) bits (o.median_factor), 1, h->stream));
+        HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (icp_words (h->median, icp_median_desc (), h->p.batch).settings), (int) bits (o.median_factor), 1, h->stream));
     for (const auto &w : words)
         if (which & w.flag) HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (w.word), (int) w.value, 1, h->stream));
     return ICP_OK;
@@ -159,7 +159,7 @@ int commit (icp_context *h, unsigned what)
         if ((rc = write_words (h, what & OPT_WORDS))) return rc;
         for (int a = 0; a < ICP_AREA_COUNT; ++a)
             if (off[a]) HIPCHK (h, hipMemsetAsync (icp_words (p, (icp_area) a).result, 0, sizeof (uint32_t) * icp_area_desc_of (a).result * p.batch, h->stream));
-        if (median_off) HIPCHK (h, hipMemsetAsync (h->median, 0, sizeof (uint32_t) * 4u * p.batch, h->stream));
+        if (median_off) HIPCHK (h, hipMemsetAsync (h->median, 0, sizeof (uint32_t) * icp_median_desc ().result * p.batch, h->stream));
         if ((what & OPT_WORDS) || clears) HIPCHK (h, hipStreamSynchronize (h->stream));
     }
     if (what & OPT_ROUTE) drop_graphs (h);
@@ -242,11 +242,10 @@ int reciprocal_ready (icp_context *h)
 int median_ready (icp_context *h)
 {
     if (h->median) return ICP_OK;
-    const icp_median_layout l = icp_median_layout_of (h->p.batch, h->p.m);
     int rc = set_device (h); if (rc) return rc;
-    if ((rc = dalloc (h, &h->median, l.total))) return rc;                   // (zeroed: the histograms and the arrival counters start clean)
+    if ((rc = dalloc (h, &h->median, icp_area_size (icp_median_desc (), h->p.batch, icp_select_keys (h->p.batch, h->p.m))))) return rc;                  // (zeroed: the histograms and the arrival counters start clean)
     float f = h->opt.median_factor; uint32_t u; std::memcpy (&u, &f, sizeof u);
-    HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (h->median + l.factor), (int) u, 1, h->stream));
+    HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (icp_words (h->median, icp_median_desc (), h->p.batch).settings), (int) u, 1, h->stream));
     return ICP_OK;
 }
 }  // namespace icp_host
@@ -476,7 +475,7 @@ static mem_desc mem_of (const icp_context *h, uint32_t b, int mem)
         case ICP_MEM_QT: return { p.PM + b * m, m * 16, nullptr };
         case ICP_MEM_W: return { reinterpret_cast<const float *> (p.PF + b * m) + 3, m * 4, nullptr };    // (the .w lane of the matched points: a strided read)
         case ICP_MEM_REVERSE_ID: return { h->recip.nn_id ? h->recip.nn_id + b * m : nullptr, m * 8, nullptr };   // (allocated with the rule's first use)
-        case ICP_MEM_MEDIAN: return { h->median ? h->median + 4u * b : nullptr, 16, nullptr };                  // (likewise; before that it reads zeros)
+        case ICP_MEM_MEDIAN: return { h->median ? h->median + icp_median_desc ().result * b : nullptr, icp_median_desc ().result * sizeof (uint32_t), nullptr };                  // (likewise; before that it reads zeros)
         case ICP_MEM_NORMALS_F: return { icp_normals_f (p) + b * m, m * 16, "ICP_MEM_NORMALS_F" };
         case ICP_MEM_COLOR_GRAD_F: return { icp_color_grad_f (p) + b * m, m * 16, "ICP_MEM_COLOR_GRAD_F" };
         case ICP_MEM_NORMALS_M: return { icp_normals_m (p) + b * m, m * 16, "ICP_MEM_NORMALS_M" };

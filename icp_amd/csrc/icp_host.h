@@ -83,7 +83,7 @@ struct icp_options {
     int reject_flags = 0; float reject_max_dist = 0.f;      // icp_set_rejection
     float trim_keep = 1.f;                       // icp_set_trimming (1: off)
     bool unique = false;                         // icp_set_unique
-    float median_factor = 0.f;                   // icp_set_median_rejection (0: off); device word icp_median_layout::factor of the rule's own allocation
+    float median_factor = 0.f;                   // icp_set_median_rejection (0: off); device word: the first setting of the rule's own words (icp_median_desc)
     bool reciprocal = false; float reciprocal_gap = 0.f;    // icp_set_reciprocal (0 while off); device word ICP_AREA_RECIPROCAL .settings
     // icp_set_projective (all zero while off); device words ICP_AREA_PROJECTIVE .settings [0 .. 5]
     bool projective = false; uint32_t proj_gw = 0, proj_radius = 0; float proj_fx = 0.f, proj_fy = 0.f, proj_cx = 0.f, proj_cy = 0.f;
@@ -156,7 +156,7 @@ struct icp_context {
     // reciprocal correspondences' own buffers (icp_rbc_set.h; allocated when the rule is first needed, each on its own; freed with the others
     // by icp_init): the moving set, the reverse state, the back search's per-query outputs — and whether the moving set is stale
     icp_reciprocal_set recip;
-    // median-distance rejection's words (icp_median_layout, icp_kernels.h; allocated zeroed when the rule is first needed on an initialised
+    // median-distance rejection's words (icp_median_desc, icp_kernels.h; allocated zeroed when the rule is first needed on an initialised
     // handle, freed with the others by icp_init): the result words ICP_MEM_MEDIAN reads, the selection's state, the factor
     uint32_t *median = nullptr;
     float *dCloud = nullptr, *dCloudOut = nullptr; uint32_t cloud_cap = 0;

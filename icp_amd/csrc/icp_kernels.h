@@ -163,18 +163,6 @@ static __host__ __device__ __forceinline__ double icp_robust_omega (uint32_t los
 #define ICP_TRIM_ONE_BLOCK_MAX 16384u    // up to this many pairs per registration: the selection is one workgroup's (k_trim_select)
 #define ICP_TRIM_BINS 2048u
 
-// Median-distance rejection (icp_median.hip): its words are an allocation of their own on the handle (icp_context::median, made at the
-// first need, freed by icp_init) and reach the kernels as an argument.  Offsets in uint32 words: [batch][4] the result words
-// (t_med bits, n, thr bits, accepted: ICP_MEM_MEDIAN), [batch][4] the multi-workgroup selection's state, [batch][ICP_TRIM_BINS] its
-// histograms, the factor (float bits: a new factor touches no graph) and a word of padding, then [batch][m] the keys where the
-// selection is not one workgroup's (m > ICP_TRIM_ONE_BLOCK_MAX).
-struct icp_median_layout { size_t result, state, hist, factor, keys, total; };
-static __host__ __device__ inline icp_median_layout icp_median_layout_of (uint32_t batch, uint32_t m)
-{
-    const size_t B = batch, fixed = (8u + ICP_TRIM_BINS) * B;
-    return { 0u, 4u * B, 8u * B, fixed, fixed + 2u, fixed + 2u + (m > ICP_TRIM_ONE_BLOCK_MAX ? B * m : 0u) };
-}
-
 // The plane system (icp_set_error_metric, icp_p2pl.hip): point-to-plane ICP and colored ICP (ICP_METRIC_COLORED), the point-to-plane
 // system with a photometric term.  [batch][28] ICP_MEM_PLANE_SYSTEM (A's upper triangle, b, status), [batch][27][icp_p2pl_nblk] the
 // block partials of k_plane_moments.
@@ -205,8 +193,8 @@ static __host__ __device__ __forceinline__ uint32_t icp_p2pl_nblk (uint32_t m) {
 // A word area, in uint32 words: [batch][result] what the feature's ICP_MEM_* object reads (zeros while the feature is off),
 // [batch][running] what an iteration's blocks keep between themselves (zero between launches), `settings` words the kernels read
 // instead of capturing them, then what a feature keeps per pair.  An area starts on a double.  As they lie — result, running, settings:
-//   trimming      4 (t bits, n, K, accepted), 4 + ICP_TRIM_BINS (the multi-block selection's state — prefix, rank left, count below,
-//                 arrivals: [batch][4] — then its histograms), 0; beyond one workgroup's selection [batch][m] the keys
+//   trimming      4 (t bits, n, K, accepted), 4 + ICP_TRIM_BINS, 0: a selection's words (icp_select_words_of below, which says what
+//                 the running words and the words per pair are)
 //   plane system  2 ICP_P2PL_SYS (the doubles of A's upper triangle, b, status), 0, 0; behind it [batch][ICP_P2PL_TERMS][icp_p2pl_nblk]
 //                 doubles, k_plane_moments' block partials, and the words kappa, k, epsilon, a double's room each
 //   one-to-one    2 (n, winners), 0, 0; [batch][m] uint64 the claim table (2 batch words in front: it starts on a double)
@@ -221,11 +209,12 @@ static __host__ __device__ inline icp_area_desc icp_area_desc_of (int a)
                                                   { 4u, 8u, 2u }, { 4u, 0u, 1u }, { 4u, 8u, 6u } };                                    // pair filter, reciprocal, projective
     return d[a];
 }
+// a selection keeps its keys where it is not one workgroup's
+static __host__ __device__ inline size_t icp_select_keys (size_t B, uint32_t m) { return m > ICP_TRIM_ONE_BLOCK_MAX ? B * m : 0u; }
+static __host__ __device__ inline size_t icp_area_size (icp_area_desc d, size_t B, size_t per_pair) { return B * (d.result + d.running) + d.settings + per_pair; }
 static __host__ __device__ inline size_t icp_area_size (int a, size_t B, uint32_t m)    // words, with trimming's keys and the claim table
 {
-    const icp_area_desc d = icp_area_desc_of (a);
-    const size_t per_pair = a == ICP_AREA_TRIM ? (m > ICP_TRIM_ONE_BLOCK_MAX ? B * m : 0u) : a == ICP_AREA_UNIQUE ? 2u * B * m : 0u;
-    return B * (d.result + d.running) + d.settings + per_pair;
+    return icp_area_size (icp_area_desc_of (a), B, a == ICP_AREA_TRIM ? icp_select_keys (B, m) : a == ICP_AREA_UNIQUE ? 2u * B * m : 0u);
 }
 struct icp_mom_layout { size_t area[ICP_AREA_COUNT], part, kappa, robust, gicp, total; };    // part: icp_p2pl_part; the three words: icp_color_kappa, icp_robust_scale, icp_gicp_eps
 // (the robust kernels compute `robust` on the device: the steps up to it stand in the order the compiler has always seen them)
@@ -247,12 +236,30 @@ static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (uint32_t bat
 static __host__ __device__ inline icp_mom_layout icp_mom_layout_of (const icp_params &p) { return icp_mom_layout_of (p.batch, p.m, p.nb); }
 // an area's three runs of words (.result + result-words * b is registration b's; behind .settings lies what the area keeps per pair)
 struct icp_area_words { uint32_t *result, *running, *settings; };
+static __host__ __device__ inline icp_area_words icp_words (uint32_t *w, icp_area_desc d, size_t B)
+{
+    return { w, w + d.result * B, w + (d.result + d.running) * B };
+}
 static inline icp_area_words icp_words (const icp_params &p, icp_area a)
 {
-    const icp_area_desc d = icp_area_desc_of (a);
-    uint32_t *w = reinterpret_cast<uint32_t *> (p.mom + icp_mom_layout_of (p).area[a]);
-    return { w, w + (size_t) d.result * p.batch, w + (size_t) (d.result + d.running) * p.batch };
+    return icp_words (reinterpret_cast<uint32_t *> (p.mom + icp_mom_layout_of (p).area[a]), icp_area_desc_of (a), p.batch);
 }
+// A selection's words (icp_select.h), the shape of trimming's area and of median-distance rejection's words: registration b's result
+// words out [4]; the running words, [batch][4] the state between the multi-workgroup passes (sel: prefix, rank left, count below,
+// arrivals), then [batch][ICP_TRIM_BINS] their histograms (hist); behind the settings [batch][m] the keys, where the selection is not
+// one workgroup's (icp_select_keys).  base: the area's first word.
+struct icp_select_words { uint32_t *out, *sel, *hist, *keys; };
+static __host__ __device__ inline icp_select_words icp_select_words_of (uint32_t *base, icp_area_desc d, uint32_t B, uint32_t b, uint32_t m)
+{
+    // (icp_words' three runs; the first two steps in 32 bits, as the pass kernels have always taken them: mom_layout_test.cpp pins the places)
+    return { base + d.result * b, base + d.result * B + 4u * b, base + (d.result + 4u) * B + (size_t) ICP_TRIM_BINS * b,
+             base + (d.result + d.running) * (size_t) B + d.settings + (size_t) b * m };
+}
+// Median-distance rejection (icp_median.hip): its words are an allocation of their own on the handle (icp_context::median, made at the
+// first need, freed by icp_init) and reach the kernels as an argument.  They are a selection's words with the result words (t_med bits,
+// n, thr bits, accepted: ICP_MEM_MEDIAN) and two settings: the factor (float bits: a new factor touches no graph) and a word of
+// padding.  Their size: icp_area_size (icp_median_desc (), batch, icp_select_keys (batch, m)).
+static __host__ __device__ inline icp_area_desc icp_median_desc () { return { 4u, 4u + ICP_TRIM_BINS, 2u }; }
 static inline double *icp_p2pl_area (const icp_params &p) { return reinterpret_cast<double *> (icp_words (p, ICP_AREA_PLANE).result); }
 static inline double *icp_p2pl_part (const icp_params &p) { return p.mom + icp_mom_layout_of (p).part; }
 static inline float *icp_color_kappa (const icp_params &p) { return reinterpret_cast<float *> (p.mom + icp_mom_layout_of (p).kappa); }
@@ -372,7 +379,7 @@ void icp_launch_build_rbc (const icp_params &p, hipStream_t s);
 void icp_launch_search (const icp_params &p, hipStream_t s);
 // rs: what reciprocal correspondences keep outside icp_params (icp_reciprocal_set, icp_rbc_set.h: the moving set, the reverse state, the
 // back search's outputs); a route with the rule on needs it, every other ignores it
-// median: the words of median-distance rejection (icp_median_layout), which live outside icp_params likewise
+// median: the words of median-distance rejection (icp_median_desc), which live outside icp_params likewise
 struct icp_reciprocal_set;
 void icp_launch_iteration (const icp_params &p, hipStream_t s, const icp_reciprocal_set *rs = nullptr, uint32_t *median = nullptr);
 // any subset of an iteration's stages (bit 0 the search with the passes behind it, 1 means, 2 sij, 3 finalize; 4: an empty kernel)

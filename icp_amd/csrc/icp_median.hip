@@ -17,8 +17,8 @@
 // Nothing depends on the order of arrival.
 //
 // The rule's words are no part of icp_params or of the moments' allocation: they are an allocation of their own on the handle
-// (icp_median_layout, icp_kernels.h) and reach the kernels as an argument.  Result words of a registration: (t_med bits, n, thr bits,
-// accepted), ICP_MEM_MEDIAN as it is read.
+// (a selection's words with two settings, the factor and a word of padding: icp_median_desc, icp_kernels.h) and reach the kernels as an
+// argument.  Result words of a registration: (t_med bits, n, thr bits, accepted), ICP_MEM_MEDIAN as it is read.
 #include "icp_select.h"                 // (select_digits, select_pass; TRIM_NONE, trim_key; icp_pair_rule.h)
 
 namespace {
@@ -62,14 +62,14 @@ __global__ __launch_bounds__ (1024) void k_median (icp_params p, uint32_t *words
         cnt += key[k] != TRIM_NONE ? 1u : 0u;
     }
     const uint32_t n = block_sum<NT> (cnt, s_wsum);
-    uint32_t *out = words + icp_median_layout_of (p.batch, m).result + 4u * b;
+    uint32_t *out = words + 4u * b;
     if (n == 0u) {                                           // no candidate: nothing to reject
         if (t == 0u) { out[0] = 0u; out[1] = 0u; out[2] = 0u; out[3] = 0u; }
         return;
     }
     uint32_t t_med, below, at;
     select_digits<NT, KPT> (key, median_rank (n), t, s_hist, s_wsum, s_pick, t_med, below, at);
-    const uint32_t thr = median_threshold (words[icp_median_layout_of (p.batch, m).factor], t_med);
+    const uint32_t thr = median_threshold (*icp_words (words, icp_median_desc (), p.batch).settings, t_med);
     uint32_t acc = 0u;
 #pragma unroll
     for (int k = 0; k < KPT; ++k) {
@@ -87,11 +87,9 @@ __global__ __launch_bounds__ (1024) void k_median (icp_params p, uint32_t *words
 template <int D>
 __global__ __launch_bounds__ (256) void k_median_select_pass (icp_params p, uint32_t *words)
 {
-    const uint32_t b = blockIdx.y, t = threadIdx.x, m = p.m;
+    const uint32_t b = blockIdx.y, t = threadIdx.x;
     if (icp_pass_leaves (p, b)) return;
-    const icp_median_layout l = icp_median_layout_of (p.batch, m);
-    const select_words w = { words + l.result + 4u * b, words + l.state + 4u * b, words + l.hist + (size_t) ICP_TRIM_BINS * b, words + l.keys + (size_t) b * m };
-    select_pass<D> (p, b, t, w, median_rule { words + l.factor });
+    select_pass<D> (p, b, t, icp_select_words_of (words, icp_median_desc (), p.batch, b, p.m), median_rule { icp_words (words, icp_median_desc (), p.batch).settings });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -101,13 +99,13 @@ __global__ __launch_bounds__ (MEDIAN_BLOCK) void k_median_reject (icp_params p, 
 {
     const uint32_t b = blockIdx.y, i = blockIdx.x * MEDIAN_BLOCK + threadIdx.x, m = p.m;
     if (icp_pass_leaves (p, b)) return;
-    const icp_median_layout l = icp_median_layout_of (p.batch, m);
-    uint32_t *out = words + l.result + 4u * b;
+    const icp_select_words w = icp_select_words_of (words, icp_median_desc (), p.batch, b, m);
+    uint32_t *out = w.out;
     if (out[1] == 0u) return;                                // (no candidate: pass 0 has written the four zeros)
     const uint32_t thr = out[2];
     bool acc = false;
     if (i < m) {
-        const uint32_t key = words[l.keys + (size_t) b * m + i];
+        const uint32_t key = w.keys[i];
         acc = key != TRIM_NONE && key <= thr;
         if (key != TRIM_NONE && !acc) icp_pair_reject (p.PF + (size_t) b * m + i);
     }
@@ -119,7 +117,7 @@ __global__ __launch_bounds__ (MEDIAN_BLOCK) void k_median_reject (icp_params p, 
 }  // namespace
 
 // the rule: one workgroup's launch up to ICP_TRIM_ONE_BLOCK_MAX pairs per registration, three select passes and the reject pass beyond
-// (launches: icp_route::median); words: the rule's allocation (icp_median_layout)
+// (launches: icp_route::median); words: the rule's allocation (icp_median_desc)
 void icp_launch_median (const icp_params &p, hipStream_t s, uint32_t *words, uint32_t launches)
 {
     if (launches == 1u) { hipLaunchKernelGGL (k_median, dim3 (1, p.batch), dim3 (1024), 0, s, p, words); return; }

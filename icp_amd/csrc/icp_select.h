@@ -1,16 +1,19 @@
-// icp_select.h — the deterministic radix select over the keys of a registration's pairs (trim_key, icp_trim_apply.h), parametrised by
-// the rank rule and the words it works in: the K-th smallest key among the candidates.  Median-distance rejection instantiates it
-// (icp_median.hip: K = (n + 1) / 2, the words of the rule's own allocation).  It is trimming's selection (icp_trim.hip: K = ceil (ξ n),
-// the words of ICP_AREA_TRIM), statement for statement; icp_trim.hip keeps its own spelling, because instantiating this one there
-// changes the instructions of k_trim_select and k_trim_select_pass<0> (register reuse and scheduling: tools/diag/isa_diff.py), and no
-// existing kernel may change with a rule that is off by default.  A change to either spelling belongs in both.
+// icp_select.h — the deterministic radix select over the keys of a registration's pairs (trim_key, icp_trim_apply.h): the K-th smallest
+// key among the candidates, parametrised by the rank rule and the words it works in.  Two rules instantiate it: trimming (icp_trim.hip:
+// K = ceil (ξ n), the words of ICP_AREA_TRIM) and median-distance rejection (icp_median.hip: K = (n + 1) / 2, the words of the rule's
+// own allocation).  The words of both have one shape (icp_select_words_of, icp_kernels.h).
 //
 // The selection works on 11 / 11 / 10-bit digits: a histogram of the digit over the keys that match the digits picked so far, then the
-// bin that holds the remaining rank.  One workgroup with its keys in registers runs select_digits; beyond ICP_TRIM_ONE_BLOCK_MAX pairs
-// every digit is a launch of many workgroups (select_pass<D>) whose LDS histograms are merged by device atomics, and the workgroup that
-// arrives last picks the bin.  Both take the same t: the K-th smallest key is one number, and every count is an integer sum.
+// bin that holds the remaining rank.  One workgroup with its keys in registers runs the three digits in one launch (select_digits);
+// beyond ICP_TRIM_ONE_BLOCK_MAX pairs every digit is a launch of many workgroups (select_pass<D>) whose LDS histograms are merged by
+// device atomics, and the workgroup that arrives last picks the bin.  Both take the same t: the K-th smallest key is one number, and
+// every count is an integer sum.
 //
-// What a rule brings to select_pass (RULE, a struct of three members; the kernel hands its words in as select_words):
+// One exception, measured: k_trim_select writes select_digits' loop out in its own body, from the helpers here.  Calling select_digits
+// there changes the kernel's instructions, and trimming's iteration at 16384 pairs then takes 0.1 - 0.2 us longer than the parent's
+// range (profiles/select_ab.txt).  tests/test_gpu_select.py holds the two rules against each other.
+//
+// What a rule brings to select_pass (RULE, a struct of three members; the kernel hands its words in as icp_select_words):
 //   uint32_t rank (uint32_t n)                                the rank K in 1 .. n of n >= 1 candidates
 //   void first (uint32_t *out, uint32_t n, uint32_t K)        pass 0's last workgroup, thread 0: n and K are known
 //   void last (uint32_t *out, uint32_t t, uint32_t below, uint32_t at)    pass 2's last workgroup, thread 0: t, how many keys are < t and == t
@@ -98,10 +101,6 @@ __device__ __forceinline__ void select_digits (uint32_t (&key)[KPT], uint32_t K,
     }
 }
 
-// the words of registration b a multi-workgroup selection works in: out [4] the rule's result words, sel [4] the state between the
-// passes (prefix, rank left, count below, arrivals), hist [ICP_TRIM_BINS], keys [m]
-struct select_words { uint32_t *out, *sel, *hist, *keys; };
-
 // ------------------------------------------------------------------------------------------
 // select_pass<D> — pass D of the selection of large sets: 2048 pairs per workgroup of 256 threads, grid (ceil (m / 2048), batch).  Pass 0
 // computes the keys and leaves them for passes 1 and 2 (and for whoever reads them behind the selection).  The workgroups merge their
@@ -109,7 +108,7 @@ struct select_words { uint32_t *out, *sel, *hist, *keys; };
 // and clears the histogram and the counter.
 // ------------------------------------------------------------------------------------------
 template <int D, class RULE>
-__device__ __forceinline__ void select_pass (const icp_params &p, uint32_t b, uint32_t t, const select_words w, const RULE &rule)
+__device__ __forceinline__ void select_pass (const icp_params &p, uint32_t b, uint32_t t, const icp_select_words w, const RULE &rule)
 {
     constexpr int NT = 256, KPT = 8;
     __shared__ uint32_t s_hist[ICP_TRIM_BINS], s_wsum[NT / 64], s_pick[3];

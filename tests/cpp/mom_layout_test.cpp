@@ -1,5 +1,6 @@
 // mom_layout_test.cpp — the word areas behind the moments (icp_amd/csrc/icp_kernels.h: icp_mom_layout_of, icp_words and the accessors)
-// against offsets written out by hand: host only, no HIP call.  `make mom_layout_test` builds and runs it; tests/test_mom_layout_cpu.py
+// and the words of a selection under both its rules (icp_median_desc, icp_select_words_of) against offsets written out by hand: host
+// only, no HIP call.  `make mom_layout_test` builds and runs it; tests/test_mom_layout_cpu.py
 // does too.  The offsets are an ABI between the kernels, the C-ABI's icp_read and the graphs that have captured them: they must not move.
 #include <cstdint>
 #include <cstdio>
@@ -77,6 +78,30 @@ int main ()
         check (s, "projective's result words", at (j.result), 8 * proj);
         check (s, "projective's running words", at (j.running), 8 * proj + 4 * (4 * B));
         check (s, "projective's settings", at (j.settings), 8 * proj + 4 * (12 * B));
+
+        // median-distance rejection's words, an allocation of their own, as uint32 offsets from its first word: result 0, the
+        // selection's state 4 B, its histograms 8 B, the factor (8 + 2048) B, the keys two words behind it
+        uint32_t *const mbase = reinterpret_cast<uint32_t *> (base);
+        auto word = [&] (const uint32_t *q) { return (size_t) (q - mbase); };
+        const size_t fixed = (8 + 2048) * B;
+        const icp_area_words mw = icp_words (mbase, icp_median_desc (), B);
+        check (s, "median's result words", word (mw.result), 0);
+        check (s, "median's selection state", word (mw.running), 4 * B);
+        check (s, "median's factor", word (mw.settings), fixed);
+        check (s, "median's total", icp_area_size (icp_median_desc (), B, icp_select_keys (B, s.m)), fixed + 2 + keys);
+        // a registration's words in the multi-workgroup selection, under both rules: trimming's area has no settings in front of the keys
+        const struct { const char *rule; uint32_t *first; icp_area_desc d; size_t settings; } RULES[] = {
+            { "median", mbase, icp_median_desc (), 2 }, { "trimming", t.result, icp_area_desc_of (ICP_AREA_TRIM), 0 },
+        };
+        for (const auto &r : RULES)
+            for (const size_t b : { (size_t) 0, B - 1 }) {
+                const icp_select_words w = icp_select_words_of (r.first, r.d, s.batch, (uint32_t) b, s.m);
+                const size_t first = word (r.first);
+                check (s, r.rule, word (w.out), first + 4 * b);
+                check (s, r.rule, word (w.sel), first + 4 * B + 4 * b);
+                check (s, r.rule, word (w.hist), first + 8 * B + 2048 * b);
+                check (s, r.rule, word (w.keys), first + fixed + r.settings + b * m);
+            }
 
         // consecutive areas do not overlap: each one's bytes, by hand, end where the next begins or before
         const struct { const char *name; size_t begin, bytes; } AREAS[] = {
