@@ -6,7 +6,7 @@ ARCH     ?= gfx950
 EXTRA    ?=
 BUILD    ?= build
 HIPFLAGS ?= $(EXTRA) -O3 -std=c++17 -fPIC -fvisibility=hidden --offload-arch=$(ARCH) -ffp-contract=off -fno-fast-math -Wall -Wno-unused-result -pthread -mllvm -amdgpu-kernarg-preload-count=14
-SRC      := icp_amd/csrc/icp_kernels.hip icp_amd/csrc/icp_search_dense.hip icp_amd/csrc/icp_search_rej.hip icp_amd/csrc/icp_trim.hip icp_amd/csrc/icp_p2pl.hip icp_amd/csrc/icp_robust.hip icp_amd/csrc/icp_gicp.hip icp_amd/csrc/icp_symmetric.hip icp_amd/csrc/icp_unique.hip icp_amd/csrc/icp_median.hip icp_amd/csrc/icp_pair_filter.hip icp_amd/csrc/icp_reciprocal.hip icp_amd/csrc/icp_projective.hip icp_amd/csrc/icp_quality.hip icp_amd/csrc/icp_pairs.hip icp_amd/csrc/icp_build.hip icp_amd/csrc/icp_capi.hip icp_amd/csrc/icp_run.hip icp_amd/csrc/icp_track.hip icp_amd/csrc/icp_reduce_scan.hip icp_amd/csrc/icp_standalone.hip icp_amd/csrc/icp_synth.cpp icp_amd/csrc/icp_batch.cpp icp_amd/csrc/icp_pyramid.hip
+SRC      := icp_amd/csrc/icp_kernels.hip icp_amd/csrc/icp_search_dense.hip icp_amd/csrc/icp_search_rej.hip icp_amd/csrc/icp_trim.hip icp_amd/csrc/icp_p2pl.hip icp_amd/csrc/icp_robust.hip icp_amd/csrc/icp_gicp.hip icp_amd/csrc/icp_symmetric.hip icp_amd/csrc/icp_unique.hip icp_amd/csrc/icp_median.hip icp_amd/csrc/icp_adaptive_trim.hip icp_amd/csrc/icp_pair_filter.hip icp_amd/csrc/icp_reciprocal.hip icp_amd/csrc/icp_projective.hip icp_amd/csrc/icp_quality.hip icp_amd/csrc/icp_pairs.hip icp_amd/csrc/icp_build.hip icp_amd/csrc/icp_capi.hip icp_amd/csrc/icp_run.hip icp_amd/csrc/icp_track.hip icp_amd/csrc/icp_reduce_scan.hip icp_amd/csrc/icp_standalone.hip icp_amd/csrc/icp_synth.cpp icp_amd/csrc/icp_batch.cpp icp_amd/csrc/icp_pyramid.hip
 HDR      := icp_amd/csrc/icp_device.h icp_amd/csrc/icp_kernels.h icp_amd/csrc/icp_rbc_set.h icp_amd/csrc/icp_search.h icp_amd/csrc/icp_search_select.h icp_amd/csrc/icp_host.h icp_amd/csrc/icp_cguard.h icp_amd/csrc/icp_trim_apply.h icp_amd/csrc/icp_select.h icp_amd/csrc/icp_plane_moments.h icp_amd/csrc/icp_pair_rule.h include/icp_amd.h
 LIB      ?= icp_amd/libicp_amd.so
 OBJ      := $(patsubst icp_amd/csrc/%,$(BUILD)/%.o,$(SRC))

@@ -7,7 +7,7 @@
 //   registration A B                      data/A.bin, data/B.bin — or A and B themselves when they name existing files
 //   ... [--out FILE] [--device N] [--reference-order] [--svd] [--reject-invalid] [--max-dist MM] [--trim FRACTION]
 //       [--point-to-plane MU] [--colored KAPPA] [--robust KIND:SCALE] [--plane-to-plane EPS] [--symmetric] [--one-to-one]
-//       [--median-factor F] [--reciprocal [GAP]] [--projective [RADIUS]] [--evaluate MAXDIST] [--pyramid LEVELS[:MAXDZ]]
+//       [--median-factor F] [--adaptive-trim [MIN:MAX[:Q]]] [--reciprocal [GAP]] [--projective [RADIUS]] [--evaluate MAXDIST] [--pyramid LEVELS[:MAXDZ]]
 //
 // --reject-invalid / --max-dist: correspondence rejection (icp_set_rejection: pairs with a pixel without depth at either end / pairs
 // farther apart than MM get weight 0).  --trim: trimmed ICP (icp_set_trimming: every iteration keeps the closest FRACTION in (0, 1] of the
@@ -22,6 +22,8 @@
 // --one-to-one: one-to-one correspondences (icp_set_unique): of the pairs that share a fixed point only the closest keeps its weight.
 // --median-factor: median-distance rejection (icp_set_median_rejection): every iteration gives the pairs farther apart than F (> 0)
 // times that iteration's median pair distance weight 0.
+// --adaptive-trim: adaptive trimming (icp_set_adaptive_trimming): every iteration chooses the kept fraction itself, between MIN and MAX,
+// by minimising the fractional RMSD with lambda = (Q - 1) / 2, Q in 2 .. 8 (default 0.05:0.95:4); in --trim's place, not together with it.
 // --reciprocal: reciprocal correspondences (icp_set_reciprocal): a pair keeps its weight only if its fixed point, searching the moving
 // frame, finds the pair's moving point again, or one within GAP mm of it (default 0: exactly that point).
 // --projective: projective data association (icp_set_projective): every moving landmark is paired with the closest fixed landmark of the
@@ -46,6 +48,7 @@
 namespace {
 
 const size_t kPoints = 640u * 480u;
+struct AdaptiveTrim { float lo = 0.f, hi = 0.f; uint32_t q = 0; };      // --adaptive-trim (q 0: off)
 // the pinhole model of the 128 x 128 landmarks of a 640 x 480 frame, in grid units (include/icp_amd.h: icp_set_projective)
 const float kLmFx = 595.f / 4.f, kLmFy = 595.f / 3.f, kLmCx = (319.5f - 65.f) / 4.f, kLmCy = (239.5f - 49.f) / 3.f;
 
@@ -64,7 +67,7 @@ std::string data_path (const std::string &name) { return exists (name) ? name : 
 
 template <cl_algo::ICP::ICPStepConfigT RC>
 int run (int device, icp::Mode mode, const std::vector<icp_float8> &pc1, const std::vector<icp_float8> &pc2, const std::string &out,
-         int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa, icp::RobustLoss robust, float gicp_eps, bool symmetric, bool one_to_one, float median_factor,
+         int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa, icp::RobustLoss robust, float gicp_eps, bool symmetric, bool one_to_one, float median_factor, AdaptiveTrim adaptive,
          float reciprocal, int projective, float evaluate)
 {
     ICPReg<RC, cl_algo::ICP::ICPStepConfigW::WEIGHTED> app (device, mode);
@@ -74,6 +77,7 @@ int run (int device, icp::Mode mode, const std::vector<icp_float8> &pc1, const s
     if (one_to_one) app.setUnique (true);
     if (median_factor > 0.f) app.setMedianRejection (median_factor);
     if (trim != 1.f) app.setTrimming (trim);
+    if (adaptive.q) app.setAdaptiveTrimming (adaptive.lo, adaptive.hi, adaptive.q);
     if (robust.loss != icp::RobustLoss::NONE) app.setRobustLoss (robust);
     if (gicp_eps > 0.f) app.setPlaneToPlane (gicp_eps);
     if (symmetric) app.setSymmetric (true);
@@ -105,7 +109,7 @@ void check_level (icp_handle h, int rc) { if (rc != ICP_OK) throw std::runtime_e
 // the same registration through cl_algo::ICP::ICPPyramid: the options on every level's handle, the level's own grid width
 template <cl_algo::ICP::ICPStepConfigT RC>
 int run_pyramid (int device, icp::Mode mode, unsigned levels, float max_dz, const std::vector<icp_float8> &pc1, const std::vector<icp_float8> &pc2, const std::string &out,
-                 int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa, icp::RobustLoss robust, float gicp_eps, bool symmetric, bool one_to_one, float median_factor,
+                 int reject_flags, float max_dist, float trim, float p2pl_mu, float kappa, icp::RobustLoss robust, float gicp_eps, bool symmetric, bool one_to_one, float median_factor, AdaptiveTrim adaptive,
                  float reciprocal, int projective, float evaluate)
 {
     cl_algo::ICP::ICPPyramid<RC, cl_algo::ICP::ICPStepConfigW::WEIGHTED> pyr (icp::Env (device), mode);
@@ -124,6 +128,7 @@ int run_pyramid (int device, icp::Mode mode, unsigned levels, float max_dz, cons
         if (one_to_one) check_level (h, icp_set_unique (h, 1));
         if (median_factor > 0.f) check_level (h, icp_set_median_rejection (h, median_factor));
         if (trim != 1.f) check_level (h, icp_set_trimming (h, trim));
+        if (adaptive.q) check_level (h, icp_set_adaptive_trimming (h, adaptive.lo, adaptive.hi, adaptive.q));
         if (robust.loss != icp::RobustLoss::NONE) check_level (h, icp_set_robust_loss (h, robust.loss, robust.scale));
         if (gicp_eps > 0.f) check_level (h, icp_set_plane_to_plane (h, gicp_eps));
         if (symmetric) check_level (h, icp_set_symmetric (h, 1));
@@ -166,6 +171,7 @@ int main (int argc, char **argv)
     int device = 0; bool svd = false, symmetric = false, one_to_one = false;
     int reject_flags = 0; float max_dist = 0.f, trim = 1.f, p2pl_mu = -1.f, kappa = -1.f, gicp_eps = 0.f, evaluate = -1.f, reciprocal = -1.f, median_factor = 0.f; int projective = -1;     // (p2pl_mu < 0: point-to-point; kappa < 0: not colored; gicp_eps 0: off; evaluate < 0: no quality report; reciprocal < 0: off)
     icp::RobustLoss robust;
+    AdaptiveTrim adaptive;
     unsigned pyramid_levels = 0; float pyramid_dz = 0.f;       // (0 levels: one level, no pyramid object)
     icp::Mode mode = icp::Mode::FAST;
     for (int i = 1; i < argc; ++i) {
@@ -215,6 +221,24 @@ int main (int argc, char **argv)
             median_factor = std::strtof (argv[++i], nullptr);
             if (!(median_factor > 0.f && std::isfinite (median_factor))) { std::fprintf (stderr, "--median-factor: F must be finite and > 0\n"); return 2; }
         }
+        else if (a == "--adaptive-trim") {                        // (MIN:MAX[:Q] is optional: taken when the next argument is no option and holds a colon)
+            adaptive.lo = 0.05f; adaptive.hi = 0.95f; adaptive.q = 4u;
+            if (i + 1 < argc && argv[i + 1][0] != '-' && std::strchr (argv[i + 1], ':')) {
+                const char *v = argv[++i];
+                char *e1 = nullptr, *e2 = nullptr, *e3 = nullptr;
+                long q = 4;
+                adaptive.lo = std::strtof (v, &e1);
+                const bool lo_ok = e1 != v && *e1 == ':';
+                if (lo_ok) adaptive.hi = std::strtof (e1 + 1, &e2);
+                const bool hi_ok = lo_ok && e2 != e1 + 1 && (*e2 == 0 || *e2 == ':');
+                if (hi_ok && *e2 == ':') q = std::strtol (e2 + 1, &e3, 10);
+                const bool q_ok = hi_ok && (*e2 == 0 || (e3 != e2 + 1 && *e3 == 0));
+                if (!q_ok || !(adaptive.lo > 0.f && adaptive.lo <= adaptive.hi && adaptive.hi <= 1.f) || q < 2 || q > 8) {
+                    std::fprintf (stderr, "--adaptive-trim: MIN:MAX[:Q] with 0 < MIN <= MAX <= 1 and Q in 2 .. 8\n"); return 2;
+                }
+                adaptive.q = (uint32_t) q;
+            }
+        }
         else if (a == "--reciprocal") {                           // (GAP is optional: taken when the next argument is a number)
             reciprocal = 0.f;
             if (i + 1 < argc) {
@@ -251,6 +275,7 @@ int main (int argc, char **argv)
         else if (a.rfind ("--", 0) == 0) { std::fprintf (stderr, "unknown option %s\n", a.c_str ()); return 2; }
         else names.push_back (a);
     }
+    if (adaptive.q && trim != 1.f) { std::fprintf (stderr, "--adaptive-trim and --trim exclude each other\n"); return 2; }
     if ((gicp_eps > 0.f || symmetric) && p2pl_mu < 0.f) p2pl_mu = 0.f;   // (plane-to-plane and symmetric act in the point-to-plane metric)
     try
     {
@@ -265,10 +290,10 @@ int main (int argc, char **argv)
             read_cloud (data_path (names[0]), pc1); read_cloud (data_path (names[1]), pc2);
         }
         if (pyramid_levels)
-            return svd ? run_pyramid<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pyramid_levels, pyramid_dz, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, median_factor, reciprocal, projective, evaluate)
-                       : run_pyramid<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pyramid_levels, pyramid_dz, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, median_factor, reciprocal, projective, evaluate);
-        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, median_factor, reciprocal, projective, evaluate)
-                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, median_factor, reciprocal, projective, evaluate);
+            return svd ? run_pyramid<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pyramid_levels, pyramid_dz, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, median_factor, adaptive, reciprocal, projective, evaluate)
+                       : run_pyramid<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pyramid_levels, pyramid_dz, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, median_factor, adaptive, reciprocal, projective, evaluate);
+        return svd ? run<cl_algo::ICP::ICPStepConfigT::EIGEN> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, median_factor, adaptive, reciprocal, projective, evaluate)
+                   : run<cl_algo::ICP::ICPStepConfigT::POWER_METHOD> (device, mode, pc1, pc2, out, reject_flags, max_dist, trim, p2pl_mu, kappa, robust, gicp_eps, symmetric, one_to_one, median_factor, adaptive, reciprocal, projective, evaluate);
     }
     catch (const std::exception &e)
     {

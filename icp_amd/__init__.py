@@ -87,7 +87,7 @@ class TransformKind:             # ICPTransformConfig (include/ICP/algorithms.hp
 
 class Memory:                    # icp_mem in include/icp_amd.h
     F, M, T, TK, MEANS, S, NN_ID, W, SUM_W, REPS, RBC_N, RBC_O, RBC_PERM, RBC_OWNER, RBC_XP, RID, R, RK, NN, QT, TRIM, \
-        NORMALS_F, PLANE_SYSTEM, COLOR_GRAD_F, NORMALS_M, UNIQUE, PAIR_FILTER, RECIPROCAL, REVERSE_ID, PROJECTIVE, MEDIAN = range(31)
+        NORMALS_F, PLANE_SYSTEM, COLOR_GRAD_F, NORMALS_M, UNIQUE, PAIR_FILTER, RECIPROCAL, REVERSE_ID, PROJECTIVE, MEDIAN, TRIM_ADAPTIVE = range(32)
     # reference spellings (ICPStep::Memory, include/ICP/algorithms.hpp:2241-2267)
     D_IN_F, D_IN_M, D_IO_T, H_IO_T = F, M, T, T
 
@@ -184,6 +184,8 @@ def lib():
     sig("icp_set_unique", i32, vp, i32)
     sig("icp_set_median_rejection", i32, vp, f32)
     sig("icp_get_median_rejection", i32, vp, C.POINTER(f32))
+    sig("icp_set_adaptive_trimming", i32, vp, f32, f32, u32)
+    sig("icp_get_adaptive_trimming", i32, vp, C.POINTER(f32), C.POINTER(f32), C.POINTER(u32))
     sig("icp_get_unique", i32, vp, C.POINTER(i32))
     sig("icp_set_reciprocal", i32, vp, i32, C.c_float)
     sig("icp_get_reciprocal", i32, vp, C.POINTER(i32), C.POINTER(C.c_float))
@@ -238,6 +240,7 @@ def lib():
     sig("icp_batch_set_trimming", i32, vp, f32)
     sig("icp_batch_set_unique", i32, vp, i32)
     sig("icp_batch_set_median_rejection", i32, vp, f32)
+    sig("icp_batch_set_adaptive_trimming", i32, vp, f32, f32, u32)
     sig("icp_batch_set_reciprocal", i32, vp, i32, C.c_float)
     sig("icp_batch_set_projective", i32, vp, i32, u32, f32, f32, f32, f32, u32)
     sig("icp_batch_set_normal_rejection", i32, vp, i32, f32)
@@ -632,6 +635,7 @@ _MEM_DTYPE = {
     Memory.NORMALS_M: (np.float32, 4), Memory.UNIQUE: (np.uint32, None), Memory.PAIR_FILTER: (np.uint32, None),
     Memory.RECIPROCAL: (np.uint32, None), Memory.REVERSE_ID: (DIST_ID, None), Memory.PROJECTIVE: (np.uint32, None),
     Memory.MEDIAN: (np.uint32, None),
+    Memory.TRIM_ADAPTIVE: (np.uint32, None),
 }
 
 
@@ -799,6 +803,21 @@ class ICPStep:
         v = C.c_float()
         self._chk(self._L.icp_get_median_rejection(self._h, C.byref(v)))
         return v.value
+
+    def set_adaptive_trimming(self, min_fraction=0.05, max_fraction=0.95, power=4):
+        """Adaptive trimming (icp_set_adaptive_trimming; not reference behaviour, power 0 = off, the default): trimming whose kept
+        fraction every iteration chooses itself, between min_fraction and max_fraction, by minimising (sum of the closest geo) /
+        (their number)^power over a table of thresholds — the fractional RMSD of Fractional ICP with lambda = (power - 1) / 2.
+        power is 2 .. 8.  It excludes set_trimming(keep < 1) and stands in its place, behind median-distance rejection and in front of
+        the robust loss.  read(Memory.TRIM) gives the last iteration's (t bits, n, K, accepted) — K / n is the kept fraction —,
+        read(Memory.TRIM_ADAPTIVE) its (winning bin, r_lo, r_hi, candidate bins)."""
+        self._chk(self._L.icp_set_adaptive_trimming(self._h, float(min_fraction), float(max_fraction), int(power)))
+
+    def adaptive_trimming(self):
+        """(min_fraction, max_fraction, power) of adaptive trimming ((0, 0, 0): off)."""
+        lo, hi, q = C.c_float(), C.c_float(), C.c_uint32()
+        self._chk(self._L.icp_get_adaptive_trimming(self._h, C.byref(lo), C.byref(hi), C.byref(q)))
+        return lo.value, hi.value, q.value
 
     def set_reciprocal(self, on=True, max_gap=0.0):
         """Reciprocal correspondences (icp_set_reciprocal; not reference behaviour, off by default): a pair (m_i, f_j) keeps its weight
@@ -1310,6 +1329,10 @@ class ICPBatch:
         """ICPStep.set_median_rejection on every registration (icp_batch_set_median_rejection)."""
         self._chk(self._L.icp_batch_set_median_rejection(self._b, float(factor)))
 
+    def set_adaptive_trimming(self, min_fraction=0.05, max_fraction=0.95, power=4):
+        """ICPStep.set_adaptive_trimming on every registration (icp_batch_set_adaptive_trimming)."""
+        self._chk(self._L.icp_batch_set_adaptive_trimming(self._b, float(min_fraction), float(max_fraction), int(power)))
+
     def set_reciprocal(self, on=True, max_gap=0.0):
         """ICPStep.set_reciprocal on every registration (icp_batch_set_reciprocal)."""
         self._chk(self._L.icp_batch_set_reciprocal(self._b, int(on), float(max_gap) if on else 0.0))
@@ -1425,7 +1448,7 @@ class ICPBatch:
         dt, cols = _MEM_DTYPE[mem]
         sizes = {Memory.T: 32, Memory.TK: 32, Memory.MEANS: 32, Memory.S: 44, Memory.NN_ID: self.m * 8, Memory.R: 36, Memory.RK: 36,
                  Memory.F: self.m * 32, Memory.M: self.m * 32, Memory.W: self.m * 4, Memory.RID: self.m * 4, Memory.TRIM: 16, Memory.UNIQUE: 8, Memory.PAIR_FILTER: 16,
-                 Memory.RECIPROCAL: 16, Memory.REVERSE_ID: self.m * 8, Memory.PROJECTIVE: 16, Memory.MEDIAN: 16,
+                 Memory.RECIPROCAL: 16, Memory.REVERSE_ID: self.m * 8, Memory.PROJECTIVE: 16, Memory.MEDIAN: 16, Memory.TRIM_ADAPTIVE: 16,
                  Memory.NN: self.m * 16, Memory.QT: self.m * 16, Memory.NORMALS_F: self.m * 16, Memory.PLANE_SYSTEM: 28 * 8,
                  Memory.COLOR_GRAD_F: self.m * 16, Memory.NORMALS_M: self.m * 16}
         nbytes = sizes[mem]

@@ -385,6 +385,7 @@ int icp_batch_set_rejection (icp_batch_handle b, int flags, float max_dist) try 
 int icp_batch_set_trimming (icp_batch_handle b, float keep_fraction) try { return set_all (b, icp_set_trimming, keep_fraction); } ICP_CATCH_ALL
 int icp_batch_set_unique (icp_batch_handle b, int on) try { return set_all (b, icp_set_unique, on); } ICP_CATCH_ALL
 int icp_batch_set_median_rejection (icp_batch_handle b, float factor) try { return set_all (b, icp_set_median_rejection, factor); } ICP_CATCH_ALL
+int icp_batch_set_adaptive_trimming (icp_batch_handle b, float min_fraction, float max_fraction, uint32_t power) try { return set_all (b, icp_set_adaptive_trimming, min_fraction, max_fraction, power); } ICP_CATCH_ALL
 int icp_batch_set_reciprocal (icp_batch_handle b, int on, float max_gap) try { return set_all (b, icp_set_reciprocal, on, max_gap); } ICP_CATCH_ALL
 int icp_batch_set_projective (icp_batch_handle b, int on, uint32_t grid_width, float fx, float fy, float cx, float cy, uint32_t radius) try { return set_all (b, icp_set_projective, on, grid_width, fx, fy, cx, cy, radius); } ICP_CATCH_ALL
 int icp_batch_set_normal_rejection (icp_batch_handle b, int on, float min_cos) try { return set_all (b, icp_set_normal_rejection, on, min_cos); } ICP_CATCH_ALL

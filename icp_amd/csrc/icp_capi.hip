@@ -36,6 +36,7 @@ void free_all (icp_context *h)
     h->pairs = icp_context::pairs_buffers {};
     h->recip = icp_reciprocal_set {};                              // (likewise; stale: the next handle's moving set is yet to be built)
     h->median = nullptr;                                           // (likewise: median-distance rejection's words)
+    h->adaptive = nullptr;                                         // (likewise: adaptive trimming's words)
     for (int k = 0; k < 2; ++k) {
         if (h->hBand[k]) (void) hipHostFree (h->hBand[k]);
         if (h->hFrame[k]) (void) hipHostFree (h->hFrame[k]);
@@ -78,20 +79,20 @@ uint32_t moving_normals_word (const icp_options &o)    // plane-to-plane and sym
 constexpr int reject_user_flags = ICP_REJECT_INVALID;    // the bits of `reject` that icp_set_rejection takes from the caller as they are
 void derive_params (const icp_options &o, icp_params &p)
 {
-    constexpr uint64_t sum = (uint64_t) ICP_REJECT_INVALID + ICP_REJECT_DIST_ON + ICP_REJECT_TRIM_ON + ICP_REJECT_ROBUST_MASK + ICP_REJECT_UNIQUE_ON + ICP_REJECT_FILTER_MASK + ICP_REJECT_RECIPROCAL_ON + ICP_REJECT_PROJECTIVE_ON + ICP_REJECT_MEDIAN_ON;
-    static_assert (sum == (ICP_REJECT_INVALID | ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON | ICP_REJECT_FILTER_MASK | ICP_REJECT_RECIPROCAL_ON | ICP_REJECT_PROJECTIVE_ON | ICP_REJECT_MEDIAN_ON),
+    constexpr uint64_t sum = (uint64_t) ICP_REJECT_INVALID + ICP_REJECT_DIST_ON + ICP_REJECT_TRIM_ON + ICP_REJECT_ROBUST_MASK + ICP_REJECT_UNIQUE_ON + ICP_REJECT_FILTER_MASK + ICP_REJECT_RECIPROCAL_ON + ICP_REJECT_PROJECTIVE_ON + ICP_REJECT_MEDIAN_ON + ICP_REJECT_TRIM_ADAPTIVE;
+    static_assert (sum == (ICP_REJECT_INVALID | ICP_REJECT_DIST_ON | ICP_REJECT_TRIM_ON | ICP_REJECT_ROBUST_MASK | ICP_REJECT_UNIQUE_ON | ICP_REJECT_FILTER_MASK | ICP_REJECT_RECIPROCAL_ON | ICP_REJECT_PROJECTIVE_ON | ICP_REJECT_MEDIAN_ON | ICP_REJECT_TRIM_ADAPTIVE),
                    "every rule's bits in icp_params::reject are its own");
     static_assert (ICP_REJECT_INVALID == 1, "ks_epilogue tests bit 0");
     static_assert (ICP_ROBUST_TUKEY << ICP_REJECT_ROBUST_SHIFT == ICP_REJECT_ROBUST_MASK, "the loss's kind fills the mask's two bits");
     static_assert (ICP_REJECT_BOUNDARY_ON + ICP_REJECT_NORMAL_ON == ICP_REJECT_FILTER_MASK, "the pair filter's two rules, a bit each");
-    const bool dist = o.reject_max_dist > 0.f && !std::isinf (o.reject_max_dist), trim = o.trim_keep < 1.f;
+    const bool dist = o.reject_max_dist > 0.f && !std::isinf (o.reject_max_dist), trim = o.trim_keep < 1.f, adaptive = o.adaptive_power != 0u;
     p.rot = o.rot; p.weighted = o.weighted; p.power_mode = o.power_mode; p.fused = o.reduce_mode; p.chain = o.chain;
     p.dist_scale = o.metric_scale;
-    p.reject = (uint32_t) o.reject_flags | (dist ? ICP_REJECT_DIST_ON : 0u) | (trim ? ICP_REJECT_TRIM_ON : 0u)
+    p.reject = (uint32_t) o.reject_flags | (dist ? ICP_REJECT_DIST_ON : 0u) | (trim || adaptive ? ICP_REJECT_TRIM_ON : 0u)
              | ((uint32_t) o.robust << ICP_REJECT_ROBUST_SHIFT) | (o.unique ? ICP_REJECT_UNIQUE_ON : 0u)
              | (o.boundary_gw ? ICP_REJECT_BOUNDARY_ON : 0u) | (o.normal_on ? ICP_REJECT_NORMAL_ON : 0u)
              | (o.reciprocal ? ICP_REJECT_RECIPROCAL_ON : 0u) | (o.projective ? ICP_REJECT_PROJECTIVE_ON : 0u)
-             | (o.median_factor > 0.f ? ICP_REJECT_MEDIAN_ON : 0u);
+             | (o.median_factor > 0.f ? ICP_REJECT_MEDIAN_ON : 0u) | (adaptive ? ICP_REJECT_TRIM_ADAPTIVE : 0u);     // (the setters keep trim and adaptive apart)
     p.reject_max_dist = o.reject_max_dist;
     p.reject_d2 = dist ? (float) ((double) o.reject_max_dist * (double) o.reject_max_dist) : 0.f;     // (the product of two floats is exact in double)
     p.trim_keep = trim ? o.trim_keep : 0.f;
@@ -102,7 +103,7 @@ void derive_params (const icp_options &o, icp_params &p)
 
 // The settings the kernels read from device words instead of captured arguments (a new value touches no graph): which value of the
 // record goes where.  write_words writes the chosen ones (OPT_WORDS: all) in stream order behind whatever the handle's stream holds.
-enum : unsigned { OPT_W_KAPPA = 1u, OPT_W_ROBUST = 2u, OPT_W_EPS = 4u, OPT_W_MIN_COS = 8u, OPT_W_GRID = 16u, OPT_W_GAP = 32u, OPT_W_PROJ = 64u, OPT_W_MEDIAN = 128u, OPT_WORDS = 255u };
+enum : unsigned { OPT_W_KAPPA = 1u, OPT_W_ROBUST = 2u, OPT_W_EPS = 4u, OPT_W_MIN_COS = 8u, OPT_W_GRID = 16u, OPT_W_GAP = 32u, OPT_W_PROJ = 64u, OPT_W_MEDIAN = 128u, OPT_W_ADAPTIVE = 2048u, OPT_WORDS = 255u | OPT_W_ADAPTIVE };
 int write_words (icp_context *h, unsigned which)
 {
     const icp_options &o = h->opt;
@@ -121,6 +122,12 @@ int write_words (icp_context *h, unsigned which)
     // (median-distance rejection's factor lives in the rule's own allocation: nothing to write before median_ready has made it)
     if ((which & OPT_W_MEDIAN) && h->median)
         HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (icp_words (h->median, icp_median_desc (), h->p.batch).settings), (int) bits (o.median_factor), 1, h->stream));
+    // (adaptive trimming's fractions and power: likewise, once adaptive_ready has made the rule's words)
+    if ((which & OPT_W_ADAPTIVE) && h->adaptive) {
+        uint32_t *set = icp_words (h->adaptive, icp_adaptive_desc (), h->p.batch).settings;
+        const uint32_t v[3] = { bits (o.adaptive_min), bits (o.adaptive_max), o.adaptive_power };
+        for (int k = 0; k < 3; ++k) HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (set + k), (int) v[k], 1, h->stream));
+    }
     for (const auto &w : words)
         if (which & w.flag) HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (w.word), (int) w.value, 1, h->stream));
     return ICP_OK;
@@ -152,7 +159,8 @@ int commit (icp_context *h, unsigned what)
     for (int a = 0; a < ICP_AREA_COUNT; ++a) { off[a] = area_features[a].on (was) && !area_features[a].on (p); clears = clears || off[a]; }
     if (icp_reciprocal (p) && !icp_reciprocal (was)) h->recip.stale = true;
     const bool median_off = icp_median (was) && !icp_median (p) && h->median;    // (its result words are its own allocation's: ICP_MEM_MEDIAN reads zeros while it is off)
-    clears = clears || median_off;
+    const bool adaptive_off = icp_adaptive_trim (was) && !icp_adaptive_trim (p) && h->adaptive;    // (likewise: ICP_MEM_TRIM_ADAPTIVE; trimming's words go with ICP_AREA_TRIM)
+    clears = clears || median_off || adaptive_off;
     if (h->inited && ((what & (OPT_WORDS | OPT_QUIESCE)) || clears)) {
         int rc = set_device (h); if (rc) return rc;
         if ((rc = run_close_all (h))) return rc;
@@ -160,6 +168,7 @@ int commit (icp_context *h, unsigned what)
         for (int a = 0; a < ICP_AREA_COUNT; ++a)
             if (off[a]) HIPCHK (h, hipMemsetAsync (icp_words (p, (icp_area) a).result, 0, sizeof (uint32_t) * icp_area_desc_of (a).result * p.batch, h->stream));
         if (median_off) HIPCHK (h, hipMemsetAsync (h->median, 0, sizeof (uint32_t) * icp_median_desc ().result * p.batch, h->stream));
+        if (adaptive_off) HIPCHK (h, hipMemsetAsync (h->adaptive, 0, sizeof (uint32_t) * icp_adaptive_desc ().result * p.batch, h->stream));
         if ((what & OPT_WORDS) || clears) HIPCHK (h, hipStreamSynchronize (h->stream));
     }
     if (what & OPT_ROUTE) drop_graphs (h);
@@ -247,6 +256,14 @@ int median_ready (icp_context *h)
     float f = h->opt.median_factor; uint32_t u; std::memcpy (&u, &f, sizeof u);
     HIPCHK (h, hipMemsetD32Async (reinterpret_cast<hipDeviceptr_t> (icp_words (h->median, icp_median_desc (), h->p.batch).settings), (int) u, 1, h->stream));
     return ICP_OK;
+}
+
+int adaptive_ready (icp_context *h)
+{
+    if (h->adaptive) return ICP_OK;
+    int rc = set_device (h); if (rc) return rc;
+    if ((rc = dalloc (h, &h->adaptive, icp_area_size (icp_adaptive_desc (), h->p.batch, 0u)))) return rc;      // (zeroed: the tables and the arrival words start clean)
+    return write_words (h, OPT_W_ADAPTIVE);
 }
 }  // namespace icp_host
 
@@ -476,6 +493,7 @@ static mem_desc mem_of (const icp_context *h, uint32_t b, int mem)
         case ICP_MEM_W: return { reinterpret_cast<const float *> (p.PF + b * m) + 3, m * 4, nullptr };    // (the .w lane of the matched points: a strided read)
         case ICP_MEM_REVERSE_ID: return { h->recip.nn_id ? h->recip.nn_id + b * m : nullptr, m * 8, nullptr };   // (allocated with the rule's first use)
         case ICP_MEM_MEDIAN: return { h->median ? h->median + icp_median_desc ().result * b : nullptr, icp_median_desc ().result * sizeof (uint32_t), nullptr };                  // (likewise; before that it reads zeros)
+        case ICP_MEM_TRIM_ADAPTIVE: return { h->adaptive ? h->adaptive + icp_adaptive_desc ().result * b : nullptr, icp_adaptive_desc ().result * sizeof (uint32_t), nullptr };    // (likewise)
         case ICP_MEM_NORMALS_F: return { icp_normals_f (p) + b * m, m * 16, "ICP_MEM_NORMALS_F" };
         case ICP_MEM_COLOR_GRAD_F: return { icp_color_grad_f (p) + b * m, m * 16, "ICP_MEM_COLOR_GRAD_F" };
         case ICP_MEM_NORMALS_M: return { icp_normals_m (p) + b * m, m * 16, "ICP_MEM_NORMALS_M" };
@@ -550,7 +568,7 @@ int icp_read_b (icp_handle h, uint32_t b, int mem, void *host_dst, size_t bytes)
     const mem_desc d = mem_of (h, b, mem);
     if (!d.bytes) return fail (h, ICP_EINVAL, "unknown icp_mem value");
     if (bytes > d.bytes) return fail (h, ICP_EINVAL, "icp_read: more bytes requested than the object holds");
-    if (!d.ptr && mem == ICP_MEM_MEDIAN) { std::memset (host_dst, 0, bytes); return ICP_OK; }     // (the rule has not run since icp_init: its words are yet to be allocated)
+    if (!d.ptr && (mem == ICP_MEM_MEDIAN || mem == ICP_MEM_TRIM_ADAPTIVE)) { std::memset (host_dst, 0, bytes); return ICP_OK; }     // (the rule has not run since icp_init: its words are yet to be allocated)
     if (!d.ptr) return fail (h, ICP_ESTATE, "icp_read: ICP_MEM_REVERSE_ID: no back search has run since icp_init (icp_set_reciprocal)");
     if ((rc = set_device (h))) return rc;
     const void *src = d.ptr;
@@ -575,6 +593,7 @@ int icp_device_ptr (icp_handle h, int mem, void **dptr) try
     const mem_desc d = mem_of (h, 0, mem);
     if (!d.bytes) return fail (h, ICP_EINVAL, "unknown icp_mem value");
     if (!d.ptr && mem == ICP_MEM_MEDIAN) return fail (h, ICP_ESTATE, "icp_device_ptr: ICP_MEM_MEDIAN: the rule has not run since icp_init (icp_set_median_rejection)");
+    if (!d.ptr && mem == ICP_MEM_TRIM_ADAPTIVE) return fail (h, ICP_ESTATE, "icp_device_ptr: ICP_MEM_TRIM_ADAPTIVE: the rule has not run since icp_init (icp_set_adaptive_trimming)");
     if (!d.ptr) return fail (h, ICP_ESTATE, "icp_device_ptr: ICP_MEM_REVERSE_ID: no back search has run since icp_init (icp_set_reciprocal)");
     if ((rc = set_device (h))) return rc;
     if ((rc = materialize_outputs (h, mem))) return rc;
@@ -629,7 +648,7 @@ int icp_step (icp_handle h, int config) try
     icp_params p = h->p; p.check = 0; p.hmirror = nullptr; p.hstate = nullptr;
     { const long long kb = h->k_base; note_enqueue (h); if (kb >= 0) h->k_base = kb + 1; }
     note_outputs_stored (h);
-    icp_launch_iteration (p, h->stream, &h->recip, h->median);
+    icp_launch_iteration (p, h->stream, &h->recip, h->median, h->adaptive);
     HIPCHK (h, hipGetLastError ());
     return ICP_OK;
 }
@@ -810,6 +829,8 @@ int icp_set_trimming (icp_handle h, float keep_fraction) try
     if (!(keep_fraction > 0.f && keep_fraction <= 1.f)) return fail (h, ICP_EINVAL, "icp_set_trimming: keep_fraction must be in (0, 1] (1: off)");
     if (!h) return fail (h, ICP_EINVAL, "icp_set_trimming: null handle");
     { int rc = outputs_before_change (h); if (rc) return rc; }
+    if (keep_fraction < 1.f && h->opt.adaptive_power != 0u)
+        return fail (h, ICP_ESTATE, "icp_set_trimming: adaptive trimming is on (icp_set_adaptive_trimming): switch it off first");
     const bool was = h->opt.trim_keep < 1.f, on = keep_fraction < 1.f;
     h->opt.trim_keep = keep_fraction;
     return commit (h, on != was ? OPT_ROUTE : on ? OPT_PARAMS : 0u);
@@ -820,6 +841,33 @@ int icp_get_trimming (icp_handle h, float *keep_fraction) try
     api_guard guard_ (h);
     if (!h || !keep_fraction) return ICP_EINVAL;
     *keep_fraction = h->opt.trim_keep;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+// adaptive trimming (icp_adaptive_trim.hip).  On <-> off changes which kernels run — the REJ search, the rule's selection and the apply
+// pass, no chained form —: a change of route.  New fractions or a new power while the rule stays on go to its device words alone: no
+// graph is touched.  The rule's words are allocated by the next call that enqueues an iteration (need: adaptive_ready).
+int icp_set_adaptive_trimming (icp_handle h, float min_fraction, float max_fraction, uint32_t power) try
+{
+    api_guard guard_ (h);
+    if (power != 0u && !(power >= 2u && power <= 8u && min_fraction > 0.f && min_fraction <= max_fraction && max_fraction <= 1.f))
+        return fail (h, ICP_EINVAL, "icp_set_adaptive_trimming: power must be 0 (off) or in 2 .. 8 with 0 < min_fraction <= max_fraction <= 1");
+    if (!h) return fail (h, ICP_EINVAL, "icp_set_adaptive_trimming: null handle");
+    if (power != 0u && h->opt.trim_keep < 1.f)
+        return fail (h, ICP_ESTATE, "icp_set_adaptive_trimming: trimming is on (icp_set_trimming): switch it off first (keep_fraction 1)");
+    { int rc = outputs_before_change (h); if (rc) return rc; }
+    const bool was = h->opt.adaptive_power != 0u, on = power != 0u;
+    h->opt.adaptive_min = on ? min_fraction : 0.f; h->opt.adaptive_max = on ? max_fraction : 0.f; h->opt.adaptive_power = power;
+    return commit (h, on != was ? OPT_ROUTE | OPT_W_ADAPTIVE : on ? OPT_W_ADAPTIVE : 0u);
+}
+ICP_CATCH_ALL
+int icp_get_adaptive_trimming (icp_handle h, float *min_fraction, float *max_fraction, uint32_t *power) try
+{
+    api_guard guard_ (h);
+    if (!h) return ICP_EINVAL;
+    if (min_fraction) *min_fraction = h->opt.adaptive_min;
+    if (max_fraction) *max_fraction = h->opt.adaptive_max;
+    if (power) *power = h->opt.adaptive_power;
     return ICP_OK;
 }
 ICP_CATCH_ALL
@@ -1503,7 +1551,7 @@ int icp_time_masked (icp_handle h, uint32_t mask, uint32_t iterations, uint32_t 
     graph_entry ge;
     // (the per-query outputs follow the policy of the fixed-length graphs: stored by the last iteration only in fused mode)
     if ((rc = capture_graph (h, [&] {
-             for (uint32_t k = 0; k < iterations; ++k) { p.emit = (k + 1 == iterations) ? 1 : 0; icp_launch_masked (p, h->stream, mask, &h->recip, h->median); }
+             for (uint32_t k = 0; k < iterations; ++k) { p.emit = (k + 1 == iterations) ? 1 : 0; icp_launch_masked (p, h->stream, mask, &h->recip, h->median, h->adaptive); }
          }, &ge))) return rc;
     hipError_t e = hipGraphLaunch (ge.exec, h->stream);                 // warm-up
     if (e == hipSuccess) e = hipEventRecord (h->ev0, h->stream);
@@ -1533,7 +1581,7 @@ int icp_debug_stamps (icp_handle h, unsigned long long *out, uint32_t nblocks) t
     note_enqueue (h); note_outputs_stored (h);
     if (e == hipSuccess) {
         if (icp_route_of (p).chained) icp_launch_chain (p, h->stream, 2);
-        else icp_launch_masked (p, h->stream, p.fused ? 1u | 8u : 1u, &h->recip, h->median);
+        else icp_launch_masked (p, h->stream, p.fused ? 1u | 8u : 1u, &h->recip, h->median, h->adaptive);
         e = hipGetLastError ();
     }
     if (e == hipSuccess) e = hipStreamSynchronize (h->stream);
@@ -1558,9 +1606,9 @@ int icp_profile_run (icp_handle h, uint32_t iterations, float *out_ms, float *to
     // the stages as separate launches (the chained form has no stage boundaries to time), events around each
     for (uint32_t r = 0; r < iterations && e == hipSuccess; ++r) {
         hipEvent_t *x = &ev[(size_t) r * 5];
-        e = hipEventRecord (x[0], h->stream);                                             // (trimming, one-to-one, the pair filter, reciprocal correspondences on: their passes time with the search)
+        e = hipEventRecord (x[0], h->stream);                                             // (trimming, adaptive trimming, one-to-one, the pair filter, reciprocal correspondences on: their passes time with the search)
         for (int k = 0; k < 4; ++k) {
-            icp_launch_masked (p, h->stream, 1u << k, &h->recip, h->median);
+            icp_launch_masked (p, h->stream, 1u << k, &h->recip, h->median, h->adaptive);
             if (e == hipSuccess) e = hipEventRecord (x[k + 1], h->stream);
         }
     }

@@ -82,6 +82,8 @@ struct icp_options {
     float metric_scale = 1.f;                    // icp_set_metric_scale
     int reject_flags = 0; float reject_max_dist = 0.f;      // icp_set_rejection
     float trim_keep = 1.f;                       // icp_set_trimming (1: off)
+    // icp_set_adaptive_trimming (power 0: off, the fractions 0 then); device words: the settings of the rule's own words (icp_adaptive_desc)
+    float adaptive_min = 0.f, adaptive_max = 0.f; uint32_t adaptive_power = 0;
     bool unique = false;                         // icp_set_unique
     float median_factor = 0.f;                   // icp_set_median_rejection (0: off); device word: the first setting of the rule's own words (icp_median_desc)
     bool reciprocal = false; float reciprocal_gap = 0.f;    // icp_set_reciprocal (0 while off); device word ICP_AREA_RECIPROCAL .settings
@@ -159,6 +161,9 @@ struct icp_context {
     // median-distance rejection's words (icp_median_desc, icp_kernels.h; allocated zeroed when the rule is first needed on an initialised
     // handle, freed with the others by icp_init): the result words ICP_MEM_MEDIAN reads, the selection's state, the factor
     uint32_t *median = nullptr;
+    // adaptive trimming's words (icp_adaptive_desc; allocated and freed likewise): the result words ICP_MEM_TRIM_ADAPTIVE reads, the
+    // arrival words and the tables, the fractions and the power
+    uint32_t *adaptive = nullptr;
     float *dCloud = nullptr, *dCloudOut = nullptr; uint32_t cloud_cap = 0;
     std::map<uint64_t, icp_host::graph_entry> graphs;      // key: iterations << 3 | check << 2 | parity (+ fresh, + kind: see get_graph)
     uint32_t parity = 0;                         // tracking: which landmark buffers are the fixed / moving set (graphs hold pointers): frame f -> f mod 3
@@ -264,6 +269,8 @@ int reciprocal_ready (icp_context *h);
 // median-distance rejection: the rule's words exist and hold the factor — allocated at the first need.  need (h, true) calls it in front of
 // every enqueue of an iteration while the rule is on.
 int median_ready (icp_context *h);
+// adaptive trimming: likewise (the rule's words exist and hold the fractions and the power)
+int adaptive_ready (icp_context *h);
 
 // Captures the launches `launches ()` enqueues on the handle's stream into a graph (instantiate: also into an executable one).
 // Whatever fails, the stream has left capture mode and nothing is leaked when this returns.

@@ -132,6 +132,7 @@ struct icp_params {
 #define ICP_REJECT_RECIPROCAL_ON 0x01000000u   // icp_params::reject: reciprocal correspondences are on (icp_set_reciprocal: the REJ kernels, plus the back search and k_reciprocal: icp_launch_reciprocal)
 #define ICP_REJECT_PROJECTIVE_ON 0x00800000u   // icp_params::reject: projective data association is on (icp_set_projective: k_projective in place of the search: icp_launch_projective)
 #define ICP_REJECT_MEDIAN_ON 0x00400000u   // icp_params::reject: median-distance rejection is on (icp_set_median_rejection: the REJ kernels, plus the rule's launches: icp_launch_median)
+#define ICP_REJECT_TRIM_ADAPTIVE 0x00200000u   // icp_params::reject, beside ICP_REJECT_TRIM_ON: adaptive trimming's selection fills trimming's words (icp_set_adaptive_trimming: icp_launch_adaptive_trim in icp_launch_trim_select's place)
 static_assert (sizeof (icp_params) == 480, "icp_params grew: the hidden kernel arguments of every kernel would move");
 
 // rejection on: the sum-W formulas in every mode, and a step of nothing accepted (sum W == 0) is the identity
@@ -147,6 +148,8 @@ static __host__ __device__ __forceinline__ bool icp_reciprocal (const icp_params
 static __host__ __device__ __forceinline__ bool icp_projective (const icp_params &p) { return (p.reject & ICP_REJECT_PROJECTIVE_ON) != 0u; }
 // median-distance rejection (icp_median.hip): a candidate farther than factor times the iteration's median pair distance loses its weight
 static __host__ __device__ __forceinline__ bool icp_median (const icp_params &p) { return (p.reject & ICP_REJECT_MEDIAN_ON) != 0u; }
+// adaptive trimming (icp_adaptive_trim.hip): trimming (icp_trimming holds too) whose kept fraction the selection chooses per iteration
+static __host__ __device__ __forceinline__ bool icp_adaptive_trim (const icp_params &p) { return (p.reject & ICP_REJECT_TRIM_ADAPTIVE) != 0u; }
 // the moving frame's normals are needed: by a metric (p.gicp: plane-to-plane, symmetric) or by normal rejection, whatever the metric
 static __host__ __device__ __forceinline__ bool icp_moving_normals (const icp_params &p) { return p.gicp != 0u || (p.reject & ICP_REJECT_NORMAL_ON) != 0u; }
 // the robust loss's kind (ICP_ROBUST_HUBER 1, CAUCHY 2, TUKEY 3; 0: off).  Its scale k is a device word (icp_robust_scale).
@@ -260,6 +263,20 @@ static __host__ __device__ inline icp_select_words icp_select_words_of (uint32_t
 // n, thr bits, accepted: ICP_MEM_MEDIAN) and two settings: the factor (float bits: a new factor touches no graph) and a word of
 // padding.  Their size: icp_area_size (icp_median_desc (), batch, icp_select_keys (batch, m)).
 static __host__ __device__ inline icp_area_desc icp_median_desc () { return { 4u, 4u + ICP_TRIM_BINS, 2u }; }
+// Adaptive trimming (icp_adaptive_trim.hip): its words are an allocation of their own on the handle likewise (icp_context::adaptive).
+// Result words (j*, r_lo, r_hi, candidate bins: ICP_MEM_TRIM_ADAPTIVE); running words per registration: the arrival word and three of
+// padding, then the table — [ICP_ADAPTIVE_BINS] uint64 the sums of the keys' low 19 bits, [ICP_ADAPTIVE_BINS] uint32 the counts —, zero
+// between launches; four settings: min_fraction, max_fraction (float bits), the power q, a word of padding (new values touch no graph).
+// Every run starts on a double.  Its size: icp_area_size (icp_adaptive_desc (), batch, 0).
+#define ICP_ADAPTIVE_BINS 4096u
+static __host__ __device__ inline icp_area_desc icp_adaptive_desc () { return { 4u, 4u + 3u * ICP_ADAPTIVE_BINS, 4u }; }
+struct icp_adaptive_words { uint32_t *out, *arrivals; unsigned long long *sum; uint32_t *cnt; const uint32_t *settings; };
+static __host__ __device__ inline icp_adaptive_words icp_adaptive_words_of (uint32_t *base, uint32_t B, uint32_t b)
+{
+    const icp_area_desc d = icp_adaptive_desc ();
+    uint32_t *run = base + (size_t) d.result * B + (size_t) d.running * b;
+    return { base + d.result * b, run, reinterpret_cast<unsigned long long *> (run + 4), run + 4u + 2u * ICP_ADAPTIVE_BINS, base + (size_t) (d.result + d.running) * B };
+}
 static inline double *icp_p2pl_area (const icp_params &p) { return reinterpret_cast<double *> (icp_words (p, ICP_AREA_PLANE).result); }
 static inline double *icp_p2pl_part (const icp_params &p) { return p.mom + icp_mom_layout_of (p).part; }
 static inline float *icp_color_kappa (const icp_params &p) { return reinterpret_cast<float *> (p.mom + icp_mom_layout_of (p).kappa); }
@@ -367,7 +384,8 @@ struct icp_route {
     bool reciprocal;             // k_reciprocal_state + the back search + k_reciprocal (icp_launch_reciprocal)
     bool unique;                 // k_unique_claim + k_unique_resolve
     uint32_t median;             // median-distance rejection: 0, 1 (k_median) or 4 launches (k_median_select_pass<0 .. 2>, k_median_reject)
-    uint32_t select;             // trimming's selection: 0, 1 (k_trim_select) or 3 launches (k_trim_select_pass<0 .. 2>)
+    uint32_t select;             // trimming's selection: 0, 1 (k_trim_select, or k_adaptive_trim at any size) or 3 launches (k_trim_select_pass<0 .. 2>)
+    bool adaptive;               // the selection is adaptive trimming's (icp_launch_adaptive_trim)
     icp_apply_kind apply;        // the pass that writes the search's partials again from the weights
     icp_tail_kind tail;          // k_finalize_fused / k_moment_level1 + k_finalize_fused / k_means, k_sij, k_finalize / k_plane_moments, k_p2pl_finalize
     uint32_t launches;           // what icp_launches_per_iteration reports
@@ -380,10 +398,11 @@ void icp_launch_search (const icp_params &p, hipStream_t s);
 // rs: what reciprocal correspondences keep outside icp_params (icp_reciprocal_set, icp_rbc_set.h: the moving set, the reverse state, the
 // back search's outputs); a route with the rule on needs it, every other ignores it
 // median: the words of median-distance rejection (icp_median_desc), which live outside icp_params likewise
+// adaptive: the words of adaptive trimming (icp_adaptive_desc), likewise
 struct icp_reciprocal_set;
-void icp_launch_iteration (const icp_params &p, hipStream_t s, const icp_reciprocal_set *rs = nullptr, uint32_t *median = nullptr);
+void icp_launch_iteration (const icp_params &p, hipStream_t s, const icp_reciprocal_set *rs = nullptr, uint32_t *median = nullptr, uint32_t *adaptive = nullptr);
 // any subset of an iteration's stages (bit 0 the search with the passes behind it, 1 means, 2 sij, 3 finalize; 4: an empty kernel)
-void icp_launch_masked (const icp_params &p, hipStream_t s, unsigned mask, const icp_reciprocal_set *rs = nullptr, uint32_t *median = nullptr);
+void icp_launch_masked (const icp_params &p, hipStream_t s, unsigned mask, const icp_reciprocal_set *rs = nullptr, uint32_t *median = nullptr, uint32_t *adaptive = nullptr);
 void icp_launch_chain (const icp_params &p, hipStream_t s, uint32_t iterations, bool fresh = false);
 void icp_launch_chain_one (const icp_params &p, hipStream_t s, uint32_t j, bool fresh, bool emit);   // launch j of a chain (j = 0: reads the user-visible state)
 void icp_launch_chain_end (const icp_params &p, hipStream_t s, uint32_t launches);                  // after `launches` chained launches: the last moments -> p.st (and p.hstate)
@@ -399,6 +418,7 @@ void icp_launch_trim_select (const icp_params &p, hipStream_t s, uint32_t launch
 void icp_launch_trim_apply (const icp_params &p, hipStream_t s);             // icp_trim.hip: k_trim_apply<fused?>
 void icp_launch_unique (const icp_params &p, hipStream_t s);                 // icp_unique.hip: k_unique_claim + k_unique_resolve
 void icp_launch_median (const icp_params &p, hipStream_t s, uint32_t *words, uint32_t launches);   // icp_median.hip: k_median (1) or k_median_select_pass<0 .. 2> + k_median_reject (4: icp_route::median)
+void icp_launch_adaptive_trim (const icp_params &p, hipStream_t s, uint32_t *words);   // icp_adaptive_trim.hip: k_adaptive_trim, in the selection's place (icp_route::adaptive)
 void icp_launch_reciprocal (const icp_params &p, hipStream_t s, const icp_reciprocal_set *rs);   // icp_reciprocal.hip: k_reciprocal_state + the back search + k_reciprocal
 void icp_launch_reciprocal_build (const icp_params &p, hipStream_t s, const icp_reciprocal_set &rs);   // icp_reciprocal.hip: buildRBC over M into the moving set
 void icp_launch_projective (const icp_params &p, hipStream_t s);             // icp_projective.hip: k_projective, in place of the search (icp_set_projective)

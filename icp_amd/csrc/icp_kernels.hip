@@ -551,6 +551,8 @@ void icp_launch_search (const icp_params &p, hipStream_t s)
 //   - Median-distance rejection (icp_median.hip): one launch up to ICP_TRIM_ONE_BLOCK_MAX pairs, four beyond; point-to-point: an apply
 //     pass too, as for one-to-one.  Behind one-to-one (its candidates are the winners), in front of trimming's selection (whose
 //     candidates are the pairs it accepts).
+//   - Adaptive trimming (icp_adaptive_trim.hip): trimming with its own selection in the radix select's place, one launch at every
+//     size; the apply pass as for trimming.
 //   - Projective data association (icp_projective.hip): k_projective in place of the search, same count.  It writes the per-query outputs
 //     and no block partials: point-to-point takes the apply pass for them (one launch more unless another rule runs it anyway), the
 //     plane metrics read the outputs in their moments (nothing more).
@@ -575,7 +577,8 @@ icp_route icp_route_of (const icp_params &p)
     r.reciprocal = icp_reciprocal (p);                                            r.launches += r.reciprocal ? 3u : 0u;
     r.unique = icp_unique (p);                                                    r.launches += r.unique ? 2u : 0u;
     r.median = !icp_median (p) ? 0u : p.m <= ICP_TRIM_ONE_BLOCK_MAX ? 1u : 4u;    r.launches += r.median;
-    r.select = !icp_trimming (p) ? 0u : p.m <= ICP_TRIM_ONE_BLOCK_MAX ? 1u : 3u;  r.launches += r.select;
+    r.adaptive = icp_adaptive_trim (p);                                           // (one launch at every size: icp_adaptive_trim.hip)
+    r.select = !icp_trimming (p) ? 0u : r.adaptive || p.m <= ICP_TRIM_ONE_BLOCK_MAX ? 1u : 3u;  r.launches += r.select;
     const bool pass = r.select || p2p_loss || (!plane && (r.filter || r.reciprocal || r.unique || r.median || r.projective));
     r.apply = !pass ? ICP_APPLY_NONE : p2p_loss ? ICP_APPLY_ROBUST : ICP_APPLY_PLAIN;   r.launches += pass ? 1u : 0u;
     const bool level1 = (p.nb + 127u) / 128u > ICP_L1_MIN_GROUPS && p.ml1;        // (as k_finalize_fused decides where its first level comes from)
@@ -626,7 +629,7 @@ static void launch_finalize (const icp_params &p, hipStream_t s, icp_tail_kind t
 __global__ void k_nop (icp_params p) { if (p.m == 0xFFFFFFFFu) p.st->k = 0; }
 
 // the search of an iteration and the passes behind it, as the route says
-static void launch_search_stage (const icp_params &p, hipStream_t s, const icp_route &r, const icp_reciprocal_set *rs, uint32_t *median)
+static void launch_search_stage (const icp_params &p, hipStream_t s, const icp_route &r, const icp_reciprocal_set *rs, uint32_t *median, uint32_t *adaptive)
 {
     if (!r.stored) { icp_launch_search (p, s); return; }
     icp_params q = p;
@@ -637,24 +640,25 @@ static void launch_search_stage (const icp_params &p, hipStream_t s, const icp_r
     if (r.reciprocal) icp_launch_reciprocal (q, s, rs);
     if (r.unique) icp_launch_unique (q, s);
     if (r.median) icp_launch_median (q, s, median, r.median);
-    if (r.select) icp_launch_trim_select (q, s, r.select);
+    if (r.adaptive) icp_launch_adaptive_trim (q, s, adaptive);
+    else if (r.select) icp_launch_trim_select (q, s, r.select);
     if (r.apply == ICP_APPLY_ROBUST) icp_launch_robust_apply (q, s);
     else if (r.apply == ICP_APPLY_PLAIN) icp_launch_trim_apply (q, s);
 }
 
 // An iteration stage by stage, the only spelling of it: icp_launch_iteration is every stage, the diagnostics (icp_time_masked,
 // icp_profile_run, icp_debug_stamps) take subsets (bit 0 the search with the passes behind it, 1 means, 2 sij, 3 finalize, 4 an empty kernel)
-void icp_launch_masked (const icp_params &p, hipStream_t s, unsigned mask, const icp_reciprocal_set *rs, uint32_t *median)
+void icp_launch_masked (const icp_params &p, hipStream_t s, unsigned mask, const icp_reciprocal_set *rs, uint32_t *median, uint32_t *adaptive)
 {
     const icp_route r = icp_route_of (p);
-    if (mask & 1u) launch_search_stage (p, s, r, rs, median);
+    if (mask & 1u) launch_search_stage (p, s, r, rs, median, adaptive);
     if ((mask & 2u) && r.tail == ICP_TAIL_REFERENCE) launch_means (p, s);
     if ((mask & 4u) && r.tail == ICP_TAIL_REFERENCE) launch_sij (p, s);
     if (mask & 8u) launch_finalize (p, s, r.tail);
     if (mask & 16u) hipLaunchKernelGGL (k_nop, dim3 (256, p.batch), dim3 (64), 0, s, p);
 }
 
-void icp_launch_iteration (const icp_params &p, hipStream_t s, const icp_reciprocal_set *rs, uint32_t *median) { icp_launch_masked (p, s, 15u, rs, median); }
+void icp_launch_iteration (const icp_params &p, hipStream_t s, const icp_reciprocal_set *rs, uint32_t *median, uint32_t *adaptive) { icp_launch_masked (p, s, 15u, rs, median, adaptive); }
 
 // launch j of a chain (icp_search.h: ks_launch_chain_one)
 void icp_launch_chain_one (const icp_params &p, hipStream_t s, uint32_t j, bool fresh, bool emit)

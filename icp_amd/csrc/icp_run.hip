@@ -37,7 +37,8 @@ int need (icp_context *h, bool built, bool keep_run)
     // (reciprocal correspondences: whatever the caller enqueues next may be an iteration — a stale moving set is rebuilt in front of it)
     if (built && !keep_run && icp_reciprocal (h->p)) { int rc = reciprocal_ready (h); if (rc) return rc; }
     // (median-distance rejection: its words exist before an iteration with the rule on is enqueued)
-    if (built && !keep_run && icp_median (h->p)) return median_ready (h);
+    if (built && !keep_run && icp_median (h->p)) { int rc = median_ready (h); if (rc) return rc; }
+    if (built && !keep_run && icp_adaptive_trim (h->p)) return adaptive_ready (h);      // (adaptive trimming: likewise)
     return ICP_OK;
 }
 
@@ -68,7 +69,7 @@ static hipError_t enqueue_fixed_run (icp_context *h, uint32_t iterations, int ch
         if (fresh) icp_launch_reset_state (p, h->stream, 1);
         for (uint32_t k = 0; k < iterations; ++k) {
             p.emit = (check || k + 1 == iterations) ? 1 : 0;
-            icp_launch_iteration (p, h->stream, &h->recip, h->median);
+            icp_launch_iteration (p, h->stream, &h->recip, h->median, h->adaptive);
         }
     }
     return check ? hipMemcpyAsync (h->hState, p.st, sizeof (icp_reg_state) * p.batch, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
@@ -124,7 +125,7 @@ void run_launch_one (icp_context *h, run_ctl &r)
 {
     const double t0 = now_s ();
     if (r.chained) icp_launch_chain_one (r.p, r.stream, r.enq, r.fresh, r.p.emit != 0);
-    else icp_launch_iteration (r.p, r.stream, &h->recip, h->median);
+    else icp_launch_iteration (r.p, r.stream, &h->recip, h->median, h->adaptive);
     const double us = (now_s () - t0) * 1e6;
     if (us > r.launch_max_us) r.launch_max_us = us;
     if (us > 10.0) ++r.launch_slow;
@@ -298,7 +299,7 @@ int materialize_outputs (icp_context *h, int mem)
     // (a route that stores the outputs — icp_route::stored — never leaves them to this: run_begin stores them every iteration, and the
     // setters materialise before they switch.  The whole search stage here is defensive, so that the weights read back are the applied
     // ones whatever path gets here)
-    icp_launch_masked (q, h->stream, 1u, &h->recip, h->median);
+    icp_launch_masked (q, h->stream, 1u, &h->recip, h->median, h->adaptive);
     HIPCHK (h, hipGetLastError ());
     h->outputs_stale = false;
     return ICP_OK;

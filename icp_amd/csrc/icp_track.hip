@@ -326,6 +326,8 @@ static int track_submit (icp_context *h, const void *cloud, int warm_start, bool
         return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while reciprocal correspondences are on (icp_set_reciprocal)");
     if (h->opt.median_factor > 0.f)       // (the rule's words and launches stay out of the gated tracking path)
         return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while median-distance rejection is on (icp_set_median_rejection)");
+    if (h->opt.adaptive_power != 0u)      // (likewise)
+        return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while adaptive trimming is on (icp_set_adaptive_trimming)");
     if (h->opt.projective)
         return fail (h, ICP_ESTATE, "icp_track_submit: tracking is not provided while projective data association is on (icp_set_projective)");
     // (point-to-plane: each frame's normals come from its own landmarks, which only buildRBC can give it — ICP_NORMALS_GRID)

@@ -15,7 +15,8 @@ from .io import load_pc8d, save_pc8d
 def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, angle_threshold=0.001,
                     translation_threshold=0.01, reduce_mode=ReduceMode.FUSED, reject_invalid=False, max_dist=None, trim=1.0,
                     point_to_plane=None, colored=None, robust=None, plane_to_plane=None, symmetric=False, one_to_one=False,
-                    normal_angle=None, reject_boundary=False, pyramid=None, reciprocal=None, projective=None, median_factor=None):
+                    normal_angle=None, reject_boundary=False, pyramid=None, reciprocal=None, projective=None, median_factor=None,
+                    adaptive_trim=None):
     """Returns (T[8], k, latency_ms, transformed moving cloud).  reject_invalid / max_dist: correspondence rejection
     (ICPStep.set_rejection), trim: the fraction of pairs trimmed ICP keeps (ICPStep.set_trimming; 1.0: off), point_to_plane: mu of
     point-to-plane ICP with the fixed frame's normals from its 128 x 128 landmark grid (ICPStep.set_error_metric; None: off),
@@ -30,7 +31,9 @@ def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, a
     point finds the pair's moving point again, or one within max_gap of it (ICPStep.set_reciprocal; 0: exact only, None: off), projective: the window radius in [0, 8] of projective data association — the pairs
     come from projecting the moving landmarks onto the fixed landmark grid with the frame's pinhole model (landmark_intrinsics) instead
     of from the RBC search (ICPStep.set_projective; None: off), median_factor: every iteration rejects the pairs farther apart than
-    median_factor times that iteration's median pair distance (ICPStep.set_median_rejection; None: off); pyramid: (levels, max_dz) of a coarse-to-fine registration (ICPPyramid: 128, 64, 32, .. wide
+    median_factor times that iteration's median pair distance (ICPStep.set_median_rejection; None: off), adaptive_trim: (min_fraction,
+    max_fraction, power) of adaptive trimming — every iteration chooses the kept fraction itself (ICPStep.set_adaptive_trimming; None:
+    off; not together with trim < 1); pyramid: (levels, max_dz) of a coarse-to-fine registration (ICPPyramid: 128, 64, 32, .. wide
     levels with 256, 64, 64, .. representatives, 2 x 2 means within a z band of max_dz mm, 0: no band; every option above applies to
     every level with the level's own grid width; k is then the list of the levels' counts, finest first; None: one level); none is
     the reference's behaviour, all are off by default."""
@@ -70,7 +73,7 @@ def level_intrinsics(intr, factor):
 
 
 def _apply_options(reg, side, reduce_mode, reject_invalid, max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric,
-                   one_to_one, normal_angle, reject_boundary, reciprocal=None, projective=None, median_factor=None):
+                   one_to_one, normal_angle, reject_boundary, reciprocal=None, projective=None, median_factor=None, adaptive_trim=None):
     """register_clouds' options on one handle whose landmark grid is `side` wide (640 x 480 clouds -> 128 x 128 landmarks, row-major;
     a pyramid level l: 128 >> l)."""
     if projective is not None:
@@ -92,6 +95,8 @@ def _apply_options(reg, side, reduce_mode, reject_invalid, max_dist, trim, point
         reg.set_median_rejection(median_factor)
     if trim != 1.0:
         reg.set_trimming(trim)
+    if adaptive_trim is not None:
+        reg.set_adaptive_trimming(*adaptive_trim)
     if robust is not None:
         reg.set_robust_loss(*robust)
     if plane_to_plane is not None:
@@ -113,18 +118,18 @@ def _apply_options(reg, side, reduce_mode, reject_invalid, max_dist, trim, point
 
 def _register(evaluate, fixed, moving, device, a, c, max_iterations, angle_threshold, translation_threshold, reduce_mode, reject_invalid,
               max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one, normal_angle, reject_boundary,
-              pyramid=None, reciprocal=None, projective=None, median_factor=None):
+              pyramid=None, reciprocal=None, projective=None, median_factor=None, adaptive_trim=None):
     """(T[8], k, latency_ms, transformed moving cloud, Quality record or None): register_clouds' options; evaluate None: no evaluation."""
     return _run(False, **locals())[:5]
 
 
 def _run(pairs, evaluate, fixed, moving, device, a, c, max_iterations, angle_threshold, translation_threshold, reduce_mode, reject_invalid,
          max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one, normal_angle, reject_boundary,
-         pyramid=None, reciprocal=None, projective=None, median_factor=None):
+         pyramid=None, reciprocal=None, projective=None, median_factor=None, adaptive_trim=None):
     """_register's five values and a sixth: with `pairs` the Pairs.EVALUATED correspondence set at max_dist = evaluate (None: 0, no
     distance test), else None."""
     options = (reduce_mode, reject_invalid, max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one,
-               normal_angle, reject_boundary, reciprocal, projective, median_factor)
+               normal_angle, reject_boundary, reciprocal, projective, median_factor, adaptive_trim)
     if pyramid is not None:
         levels, max_dz = pyramid
         reg = ICPPyramid(device)
@@ -233,6 +238,18 @@ def _median_factor(s):
     return v
 
 
+def _adaptive_trim(s):
+    """MIN:MAX[:Q], e.g. 0.05:0.95 or 0.4:1:3 -> (min_fraction, max_fraction, power); 0 < MIN <= MAX <= 1, Q in 2 .. 8 (default 4)."""
+    parts = s.split(":")
+    try:
+        lo, hi, q = float(parts[0]), float(parts[1]), int(parts[2]) if len(parts) == 3 else 4
+    except (ValueError, IndexError):
+        raise argparse.ArgumentTypeError("must be MIN:MAX[:Q], got %s" % s)
+    if len(parts) > 3 or not (0.0 < lo <= hi <= 1.0) or not 2 <= q <= 8:
+        raise argparse.ArgumentTypeError("must be MIN:MAX[:Q] with 0 < MIN <= MAX <= 1 and Q in 2 .. 8, got %s" % s)
+    return lo, hi, q
+
+
 def _pyramid(s):
     """LEVELS[:MAXDZ], e.g. 3 or 3:24 -> (levels, max_dz); LEVELS in [1, 5], MAXDZ finite and >= 0 (mm; 0: no band)."""
     levels, sep, dz = s.partition(":")
@@ -264,6 +281,10 @@ def main(argv=None):
     ap.add_argument("--median-factor", type=_median_factor, default=None, metavar="F",
                     help="median-distance rejection: in every iteration give the pairs farther apart than F times that iteration's "
                          "median pair distance weight 0, e.g. 2; behind --one-to-one, before --trim (not reference behaviour)")
+    ap.add_argument("--adaptive-trim", type=_adaptive_trim, nargs="?", const=(0.05, 0.95, 4), default=None, metavar="MIN:MAX[:Q]",
+                    help="adaptive trimming: every iteration chooses the kept fraction itself, between MIN and MAX, by minimising the "
+                         "fractional RMSD with lambda = (Q - 1) / 2, Q in 2 .. 8 (default 0.05:0.95:4); in --trim's place, not together "
+                         "with it (not reference behaviour)")
     ap.add_argument("--reciprocal", type=_point_weight, nargs="?", const=0.0, default=None, metavar="GAP",
                     help="reciprocal correspondences: a pair keeps its weight only if its fixed point, searching the moving frame, "
                          "finds the pair's moving point again, or one within GAP mm of it (default 0: exactly that point); before "
@@ -305,12 +326,14 @@ def main(argv=None):
                          "coarsest first, each level made of 2 x 2 means of the one below it (points within MAXDZ mm in z, doubling "
                          "per level; default 0: no band); the other options apply to every level (not reference behaviour)")
     args = ap.parse_args(argv)
+    if args.adaptive_trim is not None and args.trim != 1.0:
+        ap.error("--adaptive-trim and --trim exclude each other")
     fixed, moving = load_pc8d(args.fixed), load_pc8d(args.moving)
     options = dict(device=args.device, a=args.alpha, reject_invalid=args.reject_invalid, max_dist=args.max_dist, trim=args.trim,
                    point_to_plane=args.point_to_plane, colored=args.colored, robust=args.robust, plane_to_plane=args.plane_to_plane,
                    symmetric=args.symmetric, one_to_one=args.one_to_one, normal_angle=args.normal_angle,
                    reject_boundary=args.reject_boundary, pyramid=args.pyramid, reciprocal=args.reciprocal, projective=args.projective,
-                   median_factor=args.median_factor)
+                   median_factor=args.median_factor, adaptive_trim=args.adaptive_trim)
     members = None
     if args.pairs is not None:
         T, k, ms, out, quality, members = register_with_pairs(fixed, moving, args.evaluate, **options)

@@ -630,6 +630,11 @@ namespace ICP
          *         acts behind one-to-one and in front of trimming and the robust loss. */
         void setMedianRejection (float factor) { check (icp_set_median_rejection (h, factor)); }
         float getMedianRejection () { float f = 0.f; check (icp_get_median_rejection (h, &f)); return f; }
+        /*! \brief Adaptive trimming (icp_set_adaptive_trimming, include/icp_amd.h; not in the reference, power 0 = off, the default):
+         *         trimming whose kept fraction every iteration chooses itself, in [min_fraction, max_fraction], by minimising the
+         *         fractional RMSD with lambda = (power - 1) / 2; power is 2 .. 8.  It excludes setTrimming (keep < 1). */
+        void setAdaptiveTrimming (float min_fraction, float max_fraction, uint32_t power) { check (icp_set_adaptive_trimming (h, min_fraction, max_fraction, power)); }
+        void getAdaptiveTrimming (float *min_fraction, float *max_fraction, uint32_t *power) { check (icp_get_adaptive_trimming (h, min_fraction, max_fraction, power)); }
 
         /*! \brief Reciprocal correspondences (icp_set_reciprocal, include/icp_amd.h; not in the reference, off by default): a pair keeps
          *         its weight only if its fixed point, searching the moving frame, finds the pair's moving point again or one within

@@ -96,6 +96,7 @@ typedef enum {
     ICP_MEM_REVERSE_ID = 28,   /* out m x {dist,id}  reciprocal correspondences: the back search, fixed-point order, id = index into M */
     ICP_MEM_PROJECTIVE = 29,   /* out uint32[4]   projective data association, last iteration: n, hits, outside, empty (0 when off) */
     ICP_MEM_MEDIAN = 30,       /* out uint32[4]   median-distance rejection, last iteration: t_med (float bits), n, thr (float bits), accepted (0 when off) */
+    ICP_MEM_TRIM_ADAPTIVE = 31, /* out uint32[4]  adaptive trimming, last iteration: the winning bin j*, r_lo, r_hi, candidate bins (0 when off) */
     ICP_MEM_COUNT_
 } icp_mem;
 
@@ -349,6 +350,52 @@ int icp_get_unique (icp_handle h, int *on);
  * ICP_EINVAL: a null handle, or a negative, NaN or infinite factor. */
 int icp_set_median_rejection (icp_handle h, float factor);
 int icp_get_median_rejection (icp_handle h, float *factor);
+
+/* Adaptive trimming (Fractional ICP: Phillips, Liu & Tomasi; the automatic overlap search of Trimmed ICP: Chetverikov et al.; PCL:
+ * CorrespondenceRejectorVarTrimmed; libpointmatcher: VarTrimmedDistOutlierFilter; not reference behaviour): trimming whose kept
+ * fraction every iteration chooses itself, so that the overlap need not be known beforehand.  The choice minimises the fractional
+ * root mean squared distance FRMSD (f) = RMSD of the closest fraction f, divided by f^lambda, over a fixed table of thresholds; the
+ * power q below is 2 lambda + 1 (FRMSD^2 = mean of the closest geo / f^(2 lambda) = their sum / f^q, up to a constant).  The rule:
+ *   - power == 0 is the default and means off: the fractions are ignored and read back as 0, and the same kernels, launches, graphs
+ *     and bits run as without the rule.  On requires power q in 2 .. 8 and 0 < min_fraction <= max_fraction <= 1.
+ *   - Fixed and adaptive trimming exclude each other: turning the rule on while icp_set_trimming's keep_fraction is < 1, and
+ *     icp_set_trimming (keep_fraction < 1) while the rule is on, return ICP_ESTATE.  icp_set_trimming (1) always passes.
+ *   - Candidates are exactly trimming's: the pairs that the passes in front have left — icp_set_rejection's rules, boundary and
+ *     normal rejection, reciprocal correspondences, one-to-one, median-distance rejection —, with a weight != 0 and a finite geo.
+ *     The key of a candidate is the bit pattern of its geo in fp32; n is the number of candidates.
+ *   - Bin j of a key is key >> 19, j in 0 .. 4095: the 8 exponent bits and the top 4 mantissa bits — sixteen thresholds per octave
+ *     of squared distance, at most 3.1 % apart in distance.  c_j is the number of candidates in bin j, B_j the sum of their geo in
+ *     double.  B_j is exact in any order: a bin's members share an exponent, so the sum of their 24-bit significands is an integer
+ *     below 2^44.
+ *   - r_j = c_0 + .. + c_j.  S_j is the cumulative sum of B in double, in this fixed order: the 4096 bins are 64 runs of 64
+ *     consecutive bins; within run u, s_{u,0} = B_{64u} and s_{u,i} = s_{u,i-1} + B_{64u+i}; Base_0 = 0 and Base_u = Base_{u-1} +
+ *     s_{u-1,63}; S_{64u+i} = Base_u + s_{u,i}.  No contraction, no other order.
+ *   - r_lo = min (ceil ((double) min_fraction * n), n), r_hi the same with max_fraction.  j_lo is the first bin with r_j >= r_lo,
+ *     j_hi the first with r_j >= r_hi; both exist and are non-empty.  Candidate bins are the non-empty bins in [j_lo, j_hi].
+ *   - cost_j = S_j / P_j, P_j = r_j^q in double by q - 1 successive multiplications ((r r) r ..).  The winner j* is the candidate
+ *     bin with the smallest cost; among equal costs the lowest j.  Costs are non-negative doubles: the minimum over the pair (cost
+ *     bits, j) as integers is one number, whatever the order in which the device gets to the bins.
+ *   - t = ((j* + 1) << 19) - 1, the largest key of bin j*.  Accepted are the candidates with key <= t, exactly r_{j*} of them; ties
+ *     at t are all kept.  Every other candidate behaves exactly like a trimmed pair: its correspondence is kept, its weight is +0
+ *     (written to the W and NN outputs), and its moment, mean and S terms — for a plane metric its plane-system terms — are exact
+ *     zeros.  REGULAR mode uses the sum-W formulas with w in {0, 1}.
+ *   - n == 0: eight zero words and the sum W == 0 identity step (T unchanged, ICP::run stops).
+ *   - Each registration of a batched handle (icp_init_batched) computes its own words.  A converged registration of a checked run is
+ *     left alone: its words stay.
+ * ICP_MEM_TRIM holds (t, n, K = r_{j*}, accepted = r_{j*}) of the last iteration per registration — the kept fraction is K / n —,
+ * ICP_MEM_TRIM_ADAPTIVE (j*, r_lo, r_hi, the number of candidate bins); both read zeros while the rule is off or before an iteration.
+ * The rule stands where trimming stands: behind median-distance rejection, in front of the robust loss.  The search is untouched.
+ * With the rule on the per-query outputs are stored by every iteration, and an iteration is the separate form (icp_run_form is
+ * ICP_FORM_SEPARATE).  icp_launches_per_iteration counts what the rule adds behind the search: one selection launch at every size,
+ * and the pass that applies the weights, as for trimming.  icp_profile_run counts both into the search stage.
+ * Turning the rule on or off captures the graphs anew; new fractions or a new power while it stays on are parameter updates that
+ * take effect in already captured graphs.  The setting survives icp_init.  It applies to single, batched and icp_batch_*
+ * registrations and the level handles of a pyramid (icp_pyramid_level), to every error metric, both reduce modes, both rotation
+ * solvers, the search and projective association.  Tracking is not provided: icp_track_submit / icp_track_next return ICP_ESTATE
+ * while the rule is on, as with median-distance rejection.
+ * ICP_EINVAL: a null handle; a power of 1 or above 8; with a power in 2 .. 8, fractions that are NaN or not 0 < min <= max <= 1. */
+int icp_set_adaptive_trimming (icp_handle h, float min_fraction, float max_fraction, uint32_t power);
+int icp_get_adaptive_trimming (icp_handle h, float *min_fraction, float *max_fraction, uint32_t *power);
 
 /* Reciprocal (forward-backward consistent) correspondences (PCL: setUseReciprocalCorrespondences,
  * CorrespondenceEstimation::determineReciprocalCorrespondences; libpointmatcher; Rusinkiewicz & Levoy's matching taxonomy; not reference
@@ -1000,6 +1047,7 @@ int icp_batch_set_rejection (icp_batch_handle b, int flags, float max_dist);    
 int icp_batch_set_trimming (icp_batch_handle b, float keep_fraction);                        /* icp_set_trimming on every slot */
 int icp_batch_set_unique (icp_batch_handle b, int on);                                       /* icp_set_unique on every slot */
 int icp_batch_set_median_rejection (icp_batch_handle b, float factor);                        /* icp_set_median_rejection on every slot */
+int icp_batch_set_adaptive_trimming (icp_batch_handle b, float min_fraction, float max_fraction, uint32_t power);   /* icp_set_adaptive_trimming on every slot */
 int icp_batch_set_reciprocal (icp_batch_handle b, int on, float max_gap);                    /* icp_set_reciprocal on every slot */
 int icp_batch_set_projective (icp_batch_handle b, int on, uint32_t grid_width, float fx, float fy, float cx, float cy, uint32_t radius);   /* icp_set_projective on every slot */
 int icp_batch_set_normal_rejection (icp_batch_handle b, int on, float min_cos);              /* icp_set_normal_rejection on every slot */

@@ -81,6 +81,9 @@ public:
     /*! \brief Median-distance rejection of the registration (ICPStep::setMedianRejection; not in the reference's demo, 0 = off, the default). */
     void setMedianRejection (float factor) { reg.setMedianRejection (factor); }
     float getMedianRejection () { return reg.getMedianRejection (); }
+    /*! \brief Adaptive trimming of the registration (ICPStep::setAdaptiveTrimming; not in the reference's demo, power 0 = off, the default). */
+    void setAdaptiveTrimming (float min_fraction, float max_fraction, uint32_t power) { reg.setAdaptiveTrimming (min_fraction, max_fraction, power); }
+    void getAdaptiveTrimming (float *min_fraction, float *max_fraction, uint32_t *power) { reg.getAdaptiveTrimming (min_fraction, max_fraction, power); }
     /*! \brief Reciprocal correspondences of the registration (ICPStep::setReciprocal; not in the reference's demo, off by default). */
     void setReciprocal (bool on, float max_gap = 0.f) { reg.setReciprocal (on, max_gap); }
     bool getReciprocal (float *max_gap = nullptr) { return reg.getReciprocal (max_gap); }
