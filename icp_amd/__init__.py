@@ -59,9 +59,28 @@ class Normals:                    # icp_set_normals: where the fixed frame's poi
     GRID = 1                      # computed by buildRBC from F read as a row-major grid
 
 
-def _write_floats(mem, m):
-    """Floats a write of `mem` takes: T 8, NORMALS_F / COLOR_GRAD_F / NORMALS_M m x 4, F / M m x 8."""
-    return 8 if mem == Memory.T else m * 4 if mem in (Memory.NORMALS_F, Memory.COLOR_GRAD_F, Memory.NORMALS_M) else m * 8
+_i32, _u32, _f32 = C.c_int, C.c_uint32, C.c_float
+
+# The per-registration options, by the stem n of their C names (include/icp_amd.h): the argument types behind the handle of icp_set_<n>
+# and icp_batch_set_<n> — icp_get_<n> takes pointers to the same, in the same order —, and the values a fresh handle holds (icp_options'
+# initialisers, icp_amd/csrc/icp_host.h).  lib() declares the three entry points of every row; _Options holds the setter and the getter.
+_OPTIONS = {
+    "rejection": ((_i32, _f32), (0, 0.0)),
+    "trimming": ((_f32,), (1.0,)),
+    "unique": ((_i32,), (0,)),
+    "median_rejection": ((_f32,), (0.0,)),
+    "adaptive_trimming": ((_f32, _f32, _u32), (0.0, 0.0, 0)),
+    "reciprocal": ((_i32, _f32), (0, 0.0)),
+    "projective": ((_i32, _u32, _f32, _f32, _f32, _f32, _u32), (0, 0, 0.0, 0.0, 0.0, 0.0, 0)),
+    "normal_rejection": ((_i32, _f32), (0, 0.0)),
+    "boundary_rejection": ((_u32,), (0,)),
+    "robust_loss": ((_i32, _f32), (0, 0.0)),
+    "error_metric": ((_i32, _f32), (0, 0.0)),
+    "normals": ((_i32, _u32), (0, 0)),
+    "color_weight": ((_f32,), (0.0,)),
+    "plane_to_plane": ((_f32,), (0.0,)),
+    "symmetric": ((_i32,), (0,)),
+}
 
 
 def _max_dist_arg(max_dist):
@@ -177,36 +196,10 @@ def lib():
     sig("icp_set_scaling", i32, vp, f32)
     sig("icp_set_metric_scale", i32, vp, f32)
     sig("icp_get_metric_scale", i32, vp, C.POINTER(f32))
-    sig("icp_set_rejection", i32, vp, i32, f32)
-    sig("icp_get_rejection", i32, vp, C.POINTER(i32), C.POINTER(f32))
-    sig("icp_set_trimming", i32, vp, f32)
-    sig("icp_get_trimming", i32, vp, C.POINTER(f32))
-    sig("icp_set_unique", i32, vp, i32)
-    sig("icp_set_median_rejection", i32, vp, f32)
-    sig("icp_get_median_rejection", i32, vp, C.POINTER(f32))
-    sig("icp_set_adaptive_trimming", i32, vp, f32, f32, u32)
-    sig("icp_get_adaptive_trimming", i32, vp, C.POINTER(f32), C.POINTER(f32), C.POINTER(u32))
-    sig("icp_get_unique", i32, vp, C.POINTER(i32))
-    sig("icp_set_reciprocal", i32, vp, i32, C.c_float)
-    sig("icp_get_reciprocal", i32, vp, C.POINTER(i32), C.POINTER(C.c_float))
-    sig("icp_set_projective", i32, vp, i32, u32, f32, f32, f32, f32, u32)
-    sig("icp_get_projective", i32, vp, C.POINTER(i32), C.POINTER(u32), C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), C.POINTER(u32))
-    sig("icp_set_normal_rejection", i32, vp, i32, f32)
-    sig("icp_get_normal_rejection", i32, vp, C.POINTER(i32), C.POINTER(f32))
-    sig("icp_set_boundary_rejection", i32, vp, u32)
-    sig("icp_get_boundary_rejection", i32, vp, C.POINTER(u32))
-    sig("icp_set_robust_loss", i32, vp, i32, f32)
-    sig("icp_get_robust_loss", i32, vp, C.POINTER(i32), C.POINTER(f32))
-    sig("icp_set_error_metric", i32, vp, i32, f32)
-    sig("icp_get_error_metric", i32, vp, C.POINTER(i32), C.POINTER(f32))
-    sig("icp_set_normals", i32, vp, i32, u32)
-    sig("icp_get_normals", i32, vp, C.POINTER(i32), C.POINTER(u32))
-    sig("icp_set_color_weight", i32, vp, f32)
-    sig("icp_get_color_weight", i32, vp, C.POINTER(f32))
-    sig("icp_set_plane_to_plane", i32, vp, f32)
-    sig("icp_get_plane_to_plane", i32, vp, C.POINTER(f32))
-    sig("icp_set_symmetric", i32, vp, i32)
-    sig("icp_get_symmetric", i32, vp, C.POINTER(i32))
+    for name, (types, _) in _OPTIONS.items():
+        sig("icp_set_" + name, i32, vp, *types)
+        sig("icp_get_" + name, i32, vp, *[C.POINTER(t) for t in types])
+        sig("icp_batch_set_" + name, i32, vp, *types)
     sig("icp_get_max_iterations", i32, vp, C.POINTER(u32))
     sig("icp_set_max_iterations", i32, vp, u32)
     sig("icp_get_angle_threshold", i32, vp, C.POINTER(f64))
@@ -236,21 +229,6 @@ def lib():
     sig("icp_batch_destroy", i32, vp)
     sig("icp_batch_init", i32, vp, u32, u32, u32, f32, f32, u32, f64, f64)
     sig("icp_batch_set_modes", i32, vp, i32, i32)
-    sig("icp_batch_set_rejection", i32, vp, i32, f32)
-    sig("icp_batch_set_trimming", i32, vp, f32)
-    sig("icp_batch_set_unique", i32, vp, i32)
-    sig("icp_batch_set_median_rejection", i32, vp, f32)
-    sig("icp_batch_set_adaptive_trimming", i32, vp, f32, f32, u32)
-    sig("icp_batch_set_reciprocal", i32, vp, i32, C.c_float)
-    sig("icp_batch_set_projective", i32, vp, i32, u32, f32, f32, f32, f32, u32)
-    sig("icp_batch_set_normal_rejection", i32, vp, i32, f32)
-    sig("icp_batch_set_boundary_rejection", i32, vp, u32)
-    sig("icp_batch_set_robust_loss", i32, vp, i32, f32)
-    sig("icp_batch_set_error_metric", i32, vp, i32, f32)
-    sig("icp_batch_set_normals", i32, vp, i32, u32)
-    sig("icp_batch_set_color_weight", i32, vp, f32)
-    sig("icp_batch_set_plane_to_plane", i32, vp, f32)
-    sig("icp_batch_set_symmetric", i32, vp, i32)
     sig("icp_batch_write", i32, vp, u32, i32, vp)
     sig("icp_batch_build_rbc", i32, vp)
     sig("icp_batch_run", i32, vp)
@@ -623,20 +601,39 @@ def punch_holes(cloud, width, height, pattern=HOLES_SCATTERED, fraction=0.1, kee
     return out
 
 
-_MEM_DTYPE = {
-    Memory.F: (np.float32, 8), Memory.M: (np.float32, 8), Memory.RBC_XP: (np.float32, 8),
-    Memory.T: (np.float32, None), Memory.TK: (np.float32, None), Memory.MEANS: (np.float32, None),
-    Memory.S: (np.float32, None), Memory.NN_ID: (DIST_ID, None), Memory.W: (np.float32, None),
-    Memory.SUM_W: (np.float64, None), Memory.REPS: (np.float32, 8), Memory.RBC_N: (np.uint32, None),
-    Memory.RBC_O: (np.uint32, None), Memory.RBC_PERM: (np.uint32, None), Memory.RBC_OWNER: (np.uint32, None),
-    Memory.RID: (np.uint32, None), Memory.R: (np.float32, 3), Memory.RK: (np.float32, 3),
-    Memory.NN: (np.float32, 4), Memory.QT: (np.float32, 4), Memory.TRIM: (np.uint32, None),
-    Memory.NORMALS_F: (np.float32, 4), Memory.PLANE_SYSTEM: (np.float64, None), Memory.COLOR_GRAD_F: (np.float32, 4),
-    Memory.NORMALS_M: (np.float32, 4), Memory.UNIQUE: (np.uint32, None), Memory.PAIR_FILTER: (np.uint32, None),
-    Memory.RECIPROCAL: (np.uint32, None), Memory.REVERSE_ID: (DIST_ID, None), Memory.PROJECTIVE: (np.uint32, None),
-    Memory.MEDIAN: (np.uint32, None),
-    Memory.TRIM_ADAPTIVE: (np.uint32, None),
+# The memory objects (icp_mem, include/icp_amd.h): the dtype and the columns of the array a read returns (None: flat), and the object's
+# elements of that dtype per registration, fixed + per_point * m.  (None, None): only a handle sizes it (icp_mem_size): ICPBatch.read does
+# not serve it.
+_MEM = {                          # mem: (dtype, columns, fixed, per_point)
+    Memory.F: (np.float32, 8, 0, 8), Memory.M: (np.float32, 8, 0, 8), Memory.RBC_XP: (np.float32, 8, None, None),
+    Memory.T: (np.float32, None, 8, 0), Memory.TK: (np.float32, None, 8, 0), Memory.MEANS: (np.float32, None, 8, 0),
+    Memory.S: (np.float32, None, 11, 0), Memory.NN_ID: (DIST_ID, None, 0, 1), Memory.W: (np.float32, None, 0, 1),
+    Memory.SUM_W: (np.float64, None, None, None), Memory.REPS: (np.float32, 8, None, None), Memory.RBC_N: (np.uint32, None, None, None),
+    Memory.RBC_O: (np.uint32, None, None, None), Memory.RBC_PERM: (np.uint32, None, None, None), Memory.RBC_OWNER: (np.uint32, None, None, None),
+    Memory.RID: (np.uint32, None, 0, 1), Memory.R: (np.float32, 3, 9, 0), Memory.RK: (np.float32, 3, 9, 0),
+    Memory.NN: (np.float32, 4, 0, 4), Memory.QT: (np.float32, 4, 0, 4), Memory.TRIM: (np.uint32, None, 4, 0),
+    Memory.NORMALS_F: (np.float32, 4, 0, 4), Memory.PLANE_SYSTEM: (np.float64, None, 28, 0), Memory.COLOR_GRAD_F: (np.float32, 4, 0, 4),
+    Memory.NORMALS_M: (np.float32, 4, 0, 4), Memory.UNIQUE: (np.uint32, None, 2, 0), Memory.PAIR_FILTER: (np.uint32, None, 4, 0),
+    Memory.RECIPROCAL: (np.uint32, None, 4, 0), Memory.REVERSE_ID: (DIST_ID, None, 0, 1), Memory.PROJECTIVE: (np.uint32, None, 4, 0),
+    Memory.MEDIAN: (np.uint32, None, 4, 0),
+    Memory.TRIM_ADAPTIVE: (np.uint32, None, 4, 0),
 }
+_MEM_DTYPE = {mem: row[:2] for mem, row in _MEM.items()}           # (dtype, columns) alone
+_MEM_WRITTEN = (Memory.T, Memory.F, Memory.M, Memory.NORMALS_F, Memory.COLOR_GRAD_F, Memory.NORMALS_M)      # what icp_write takes
+
+
+def _mem_elements(mem, m):
+    """Elements of its dtype that `mem` holds per registration of m points; KeyError for an object the table does not size."""
+    fixed, per_point = _MEM[mem][2:]
+    if fixed is None:
+        raise KeyError(mem)
+    return fixed + per_point * m
+
+
+def _write_floats(mem, m):
+    """Floats a write of `mem` takes: T 8, NORMALS_F / COLOR_GRAD_F / NORMALS_M m x 4, F / M m x 8 (and m x 8 for an object the library
+    takes no writes of: it says so itself)."""
+    return _mem_elements(mem, m) if mem in _MEM_WRITTEN else m * 8
 
 
 def grid_intrinsics(side):
@@ -658,7 +655,180 @@ def _projective_args(grid_width, fx, fy, cx, cy, radius):
     return 1, int(grid_width), float(fx), float(fy), float(cx), float(cy), int(radius)
 
 
-class ICPStep:
+class _Options:
+    """The per-registration options of _OPTIONS, once for every class that holds them: a setter turns its arguments into the C arguments
+    and hands them to _set (name, *cargs), a getter decodes the C values _get (name) returns.  ICPStep sets and asks the library's handle;
+    ICPBatch sets every registration and answers with what was last set on the batch."""
+
+    def set_rejection(self, invalid=False, max_dist=None):
+        """Correspondence rejection (icp_set_rejection; not reference behaviour, off by default): pairs with an invalid endpoint (a
+        point at the origin) and / or pairs farther apart than `max_dist` (geometric, the cloud's units; None: no distance test) get
+        the weight 0.  The search itself is unchanged."""
+        self._set("rejection", REJECT_INVALID if invalid else 0, _max_dist_arg(max_dist))
+
+    def rejection(self):
+        """(invalid, max_dist) as set: max_dist None when there is no distance test."""
+        fl, md = self._get("rejection")
+        return bool(fl & REJECT_INVALID), (None if md == 0.0 or md == float("inf") else md)
+
+    def set_trimming(self, keep=1.0):
+        """Trimmed ICP (icp_set_trimming; not reference behaviour, off by default): every iteration keeps the closest fraction
+        `keep` in (0, 1] of the pairs rejection leaves and gives the rest the weight 0; 1.0 switches it off.  read(Memory.TRIM) gives
+        the last iteration's (t bits, n, K, accepted).  Kinect data needs set_rejection(invalid=True) alongside it."""
+        self._set("trimming", float(keep))
+
+    def trimming(self):
+        """The keep fraction as set (1.0: off)."""
+        return self._get("trimming")[0]
+
+    def set_unique(self, on=True):
+        """One-to-one correspondences (icp_set_unique; not reference behaviour, off by default): of the pairs that share a fixed
+        point only the closest keeps its weight (ties: the lowest query index), the others get the weight 0.  It acts after
+        rejection and before trimming and the robust loss.  read(Memory.UNIQUE) gives the last iteration's (candidates, winners)."""
+        self._set("unique", int(on))
+
+    def unique(self):
+        """Whether one-to-one correspondences are on."""
+        return bool(self._get("unique")[0])
+
+    def set_median_rejection(self, factor):
+        """Median-distance rejection (icp_set_median_rejection; not reference behaviour, 0 = off, the default): every iteration rejects
+        the pairs farther apart than factor times the median pair distance of that iteration (geo > factor^2 * the lower median of
+        geo).  It acts behind one-to-one and in front of trimming and the robust loss.  read(Memory.MEDIAN) gives the last
+        iteration's (t_med bits, n, thr bits, accepted)."""
+        self._set("median_rejection", float(factor))
+
+    def median_rejection(self):
+        """The factor of median-distance rejection (0: off)."""
+        return self._get("median_rejection")[0]
+
+    def set_adaptive_trimming(self, min_fraction=0.05, max_fraction=0.95, power=4):
+        """Adaptive trimming (icp_set_adaptive_trimming; not reference behaviour, power 0 = off, the default): trimming whose kept
+        fraction every iteration chooses itself, between min_fraction and max_fraction, by minimising (sum of the closest geo) /
+        (their number)^power over a table of thresholds — the fractional RMSD of Fractional ICP with lambda = (power - 1) / 2.
+        power is 2 .. 8.  It excludes set_trimming(keep < 1) and stands in its place, behind median-distance rejection and in front of
+        the robust loss.  read(Memory.TRIM) gives the last iteration's (t bits, n, K, accepted) — K / n is the kept fraction —,
+        read(Memory.TRIM_ADAPTIVE) its (winning bin, r_lo, r_hi, candidate bins)."""
+        self._set("adaptive_trimming", float(min_fraction), float(max_fraction), int(power))
+
+    def adaptive_trimming(self):
+        """(min_fraction, max_fraction, power) of adaptive trimming ((0, 0, 0): off)."""
+        return self._get("adaptive_trimming")
+
+    def set_reciprocal(self, on=True, max_gap=0.0):
+        """Reciprocal correspondences (icp_set_reciprocal; not reference behaviour, off by default): a pair (m_i, f_j) keeps its weight
+        only if the moving point f_j finds when it searches the moving frame — a second RBC, over M, which the engine keeps up to date
+        by itself — is m_i, or lies within `max_gap` (the cloud's units) of it; every other pair gets the weight 0.  It acts after the
+        boundary and normal rules and before one-to-one correspondences, trimming and the robust loss.  read(Memory.RECIPROCAL) gives
+        the last iteration's (n, exact, near, accepted), read(Memory.REVERSE_ID) the back search's (dist, id) per fixed point."""
+        self._set("reciprocal", int(on), float(max_gap) if on else 0.0)
+
+    def reciprocal(self):
+        """max_gap of reciprocal correspondences, None while the rule is off."""
+        on, gap = self._get("reciprocal")
+        return gap if on else None
+
+    def set_normal_rejection(self, min_cos=None):
+        """Rejection by normal compatibility (icp_set_normal_rejection; not reference behaviour, off by default): a pair whose
+        fixed normal and rotated moving normal enclose an angle with a cosine below `min_cos` (in [-1, 1]) gets the weight 0; a pair
+        without both normals too.  None: off.  It needs NORMALS_F and NORMALS_M (set_normals), under every metric, and acts before
+        one-to-one correspondences, trimming and the robust loss.  read(Memory.PAIR_FILTER) gives the last iteration's
+        (n, at_boundary, incompatible, accepted)."""
+        on = min_cos is not None
+        self._set("normal_rejection", int(on), float(min_cos) if on else 0.0)
+
+    def normal_rejection(self):
+        """The cosine threshold of normal rejection, None while it is off."""
+        on, min_cos = self._get("normal_rejection")
+        return min_cos if on else None
+
+    def set_projective(self, grid_width=None, fx=1.0, fy=1.0, cx=0.0, cy=0.0, radius=0):
+        """Projective data association (icp_set_projective; not reference behaviour, off by default): instead of searching the RBC, every
+        moving point is transformed, projected through the pinhole model (fx, fy, cx, cy in grid units: grid_intrinsics,
+        landmark_intrinsics) onto F read as a row-major grid `grid_width` wide, and paired with the closest valid fixed point of the
+        (2 radius + 1)^2 window around its cell; a point that lands outside the grid or on an empty window is a rejected pair.
+        radius in [0, 8]; point-to-point needs radius >= 1.  grid_width None or 0: off.  read(Memory.PROJECTIVE) gives the last
+        iteration's (n, hits, outside, empty)."""
+        self._set("projective", *_projective_args(grid_width, fx, fy, cx, cy, radius))
+
+    def projective(self):
+        """(grid_width, fx, fy, cx, cy, radius) of projective data association, None while it is off."""
+        on, *values = self._get("projective")
+        return tuple(values) if on else None
+
+    def set_boundary_rejection(self, grid_width=None):
+        """Rejection at the fixed grid's boundary (icp_set_boundary_rejection; not reference behaviour, off by default): F is read as
+        a row-major grid `grid_width` wide, and a pair whose fixed point lies on the grid's rim, is invalid or has an invalid grid
+        neighbour gets the weight 0.  None or 0: off."""
+        self._set("boundary_rejection", int(grid_width or 0))
+
+    def boundary_rejection(self):
+        """The grid width of boundary rejection, None while it is off."""
+        return self._get("boundary_rejection")[0] or None
+
+    def set_robust_loss(self, loss=RobustLoss.NONE, scale=0.0):
+        """Robust loss (icp_set_robust_loss; not reference behaviour, off by default): every pair's weight is multiplied by the
+        loss's IRLS weight omega (s^2 / scale^2) of its own residual s, for every error metric.  `scale` k (finite, > 0, the cloud's
+        units) is ignored with RobustLoss.NONE.  Point-to-point: read(Memory.W) gives the weights after it."""
+        self._set("robust_loss", int(loss), float(scale))
+
+    def robust_loss(self):
+        """(loss, scale) as set ((0, 0.0): off)."""
+        return self._get("robust_loss")
+
+    def set_error_metric(self, metric=ErrorMetric.POINT_TO_POINT, point_weight=0.0):
+        """Point-to-plane ICP (icp_set_error_metric; not reference behaviour, off by default): each iteration minimises the
+        point-to-plane error plus `point_weight` (mu >= 0) times the point-to-point error, linearised, solved by LDL^T on the device.
+        The normals of the fixed frame come from set_normals.  read(Memory.PLANE_SYSTEM) gives the last system and its status."""
+        self._set("error_metric", int(metric), float(point_weight))
+
+    def error_metric(self):
+        """(metric, point_weight) as set."""
+        return self._get("error_metric")
+
+    def set_normals(self, source=Normals.GIVEN, grid_width=0):
+        """Where the fixed frame's normals come from: Normals.GIVEN (write(Memory.NORMALS_F, m x 4 floats)) or Normals.GRID (buildRBC
+        computes them from F read as a row-major grid `grid_width` wide; m must be a multiple of it)."""
+        self._set("normals", int(source), int(grid_width))
+
+    def normals(self):
+        """(source, grid_width) as set."""
+        return self._get("normals")
+
+    def set_color_weight(self, kappa):
+        """Colored ICP's photometric weight kappa (icp_set_color_weight; finite, >= 0, default 0, mm^2 per intensity^2): used with
+        set_error_metric(ErrorMetric.COLORED, mu).  The fixed frame's intensity gradients are Memory.COLOR_GRAD_F (m x 4 floats
+        [gx gy gz C]): computed by buildRBC with Normals.GRID, written by the user with Normals.GIVEN."""
+        self._set("color_weight", float(kappa))
+
+    def color_weight(self):
+        """kappa as set."""
+        return self._get("color_weight")[0]
+
+    def set_plane_to_plane(self, epsilon):
+        """Generalized ICP (icp_set_plane_to_plane; not reference behaviour): with ErrorMetric.POINT_TO_PLANE every pair's residual is
+        weighed by (C_Q + C_P)^-1, the covariances R diag(epsilon, 1, 1) R^T of the two frames' normals.  epsilon in (0, 1]; 0 (the
+        default) is off.  The moving frame's normals are Memory.NORMALS_M (m x 4 floats): computed from M with Normals.GRID (by
+        buildRBC and every later write of M), written by the user with Normals.GIVEN."""
+        self._set("plane_to_plane", float(epsilon))
+
+    def plane_to_plane(self):
+        """epsilon as set (0: off)."""
+        return self._get("plane_to_plane")[0]
+
+    def set_symmetric(self, on=True):
+        """Symmetric ICP (icp_set_symmetric; Rusinkiewicz 2019; not reference behaviour): with ErrorMetric.POINT_TO_PLANE every pair's
+        residual is taken along the mean of the two frames' normals and the rotation is split evenly between the frames.  The moving
+        frame's normals are Memory.NORMALS_M, as for set_plane_to_plane (with which, as with ErrorMetric.COLORED, it does not
+        combine): computed from M with Normals.GRID (by buildRBC and every later write of M), written by the user with Normals.GIVEN."""
+        self._set("symmetric", int(bool(on)))
+
+    def symmetric(self):
+        """Whether the symmetric objective is switched on."""
+        return bool(self._get("symmetric")[0])
+
+
+class ICPStep(_Options):
     """One ICP iteration engine — mirror of cl_algo::ICP::ICPStep<CR,CW>.
 
     Reference                                   here
@@ -699,6 +869,19 @@ class ICPStep:
         if rc:
             raise ICPError(rc, self._L.icp_last_error(self._h).decode())
 
+    def _out(self, fn, *args):
+        """fn (handle, *args) with every ctypes type among `args` replaced by a pointer to a fresh object of it: the tuple of what the
+        library wrote into them."""
+        out = [a() if isinstance(a, type) else a for a in args]
+        self._chk(fn(self._h, *[C.byref(o) if isinstance(a, type) else o for a, o in zip(args, out)]))
+        return tuple(o.value for a, o in zip(args, out) if isinstance(a, type))
+
+    def _set(self, name, *cargs):
+        self._chk(getattr(self._L, "icp_set_" + name)(self._h, *cargs))
+
+    def _get(self, name):
+        return self._out(getattr(self._L, "icp_get_" + name), *_OPTIONS[name][0])
+
     # -- reference API ---------------------------------------------------------------------
     def init(self, m, nr, a=1e2, c=1e-6, batch=1):
         self._chk(self._L.icp_init_batched(self._h, batch, m, nr, a, c, self._max_it, self._ang, self._tra))
@@ -731,17 +914,13 @@ class ICPStep:
         self._chk(self._L.icp_step(self._h, int(config)))
 
     def getAlpha(self):
-        v = C.c_float()
-        self._chk(self._L.icp_get_alpha(self._h, C.byref(v)))
-        return v.value
+        return self._out(self._L.icp_get_alpha, C.c_float)[0]
 
     def setAlpha(self, a):
         self._chk(self._L.icp_set_alpha(self._h, a))
 
     def getScaling(self):
-        v = C.c_float()
-        self._chk(self._L.icp_get_scaling(self._h, C.byref(v)))
-        return v.value
+        return self._out(self._L.icp_get_scaling, C.c_float)[0]
 
     def setScaling(self, c):
         self._chk(self._L.icp_set_scaling(self._h, c))
@@ -751,203 +930,7 @@ class ICPStep:
         self._chk(self._L.icp_set_metric_scale(self._h, f_g))
 
     def getMetricScale(self):
-        v = C.c_float()
-        self._chk(self._L.icp_get_metric_scale(self._h, C.byref(v)))
-        return v.value
-
-    def set_rejection(self, invalid=False, max_dist=None):
-        """Correspondence rejection (icp_set_rejection; not reference behaviour, off by default): pairs with an invalid endpoint (a
-        point at the origin) and / or pairs farther apart than `max_dist` (geometric, the cloud's units; None: no distance test) get
-        the weight 0.  The search itself is unchanged."""
-        self._chk(self._L.icp_set_rejection(self._h, REJECT_INVALID if invalid else 0, _max_dist_arg(max_dist)))
-
-    def rejection(self):
-        """(invalid, max_dist) as set: max_dist None when there is no distance test."""
-        fl, md = C.c_int32(), C.c_float()
-        self._chk(self._L.icp_get_rejection(self._h, C.byref(fl), C.byref(md)))
-        return bool(fl.value & REJECT_INVALID), (None if md.value == 0.0 or md.value == float("inf") else md.value)
-
-    def set_trimming(self, keep=1.0):
-        """Trimmed ICP (icp_set_trimming; not reference behaviour, off by default): every iteration keeps the closest fraction
-        `keep` in (0, 1] of the pairs rejection leaves and gives the rest the weight 0; 1.0 switches it off.  read(Memory.TRIM) gives
-        the last iteration's (t bits, n, K, accepted).  Kinect data needs set_rejection(invalid=True) alongside it."""
-        self._chk(self._L.icp_set_trimming(self._h, float(keep)))
-
-    def trimming(self):
-        """The keep fraction as set (1.0: off)."""
-        v = C.c_float()
-        self._chk(self._L.icp_get_trimming(self._h, C.byref(v)))
-        return v.value
-
-    def set_unique(self, on=True):
-        """One-to-one correspondences (icp_set_unique; not reference behaviour, off by default): of the pairs that share a fixed
-        point only the closest keeps its weight (ties: the lowest query index), the others get the weight 0.  It acts after
-        rejection and before trimming and the robust loss.  read(Memory.UNIQUE) gives the last iteration's (candidates, winners)."""
-        self._chk(self._L.icp_set_unique(self._h, int(on)))
-
-    def unique(self):
-        """Whether one-to-one correspondences are on."""
-        v = C.c_int32()
-        self._chk(self._L.icp_get_unique(self._h, C.byref(v)))
-        return bool(v.value)
-
-    def set_median_rejection(self, factor):
-        """Median-distance rejection (icp_set_median_rejection; not reference behaviour, 0 = off, the default): every iteration rejects
-        the pairs farther apart than factor times the median pair distance of that iteration (geo > factor^2 * the lower median of
-        geo).  It acts behind one-to-one and in front of trimming and the robust loss.  read(Memory.MEDIAN) gives the last
-        iteration's (t_med bits, n, thr bits, accepted)."""
-        self._chk(self._L.icp_set_median_rejection(self._h, float(factor)))
-
-    def median_rejection(self):
-        """The factor of median-distance rejection (0: off)."""
-        v = C.c_float()
-        self._chk(self._L.icp_get_median_rejection(self._h, C.byref(v)))
-        return v.value
-
-    def set_adaptive_trimming(self, min_fraction=0.05, max_fraction=0.95, power=4):
-        """Adaptive trimming (icp_set_adaptive_trimming; not reference behaviour, power 0 = off, the default): trimming whose kept
-        fraction every iteration chooses itself, between min_fraction and max_fraction, by minimising (sum of the closest geo) /
-        (their number)^power over a table of thresholds — the fractional RMSD of Fractional ICP with lambda = (power - 1) / 2.
-        power is 2 .. 8.  It excludes set_trimming(keep < 1) and stands in its place, behind median-distance rejection and in front of
-        the robust loss.  read(Memory.TRIM) gives the last iteration's (t bits, n, K, accepted) — K / n is the kept fraction —,
-        read(Memory.TRIM_ADAPTIVE) its (winning bin, r_lo, r_hi, candidate bins)."""
-        self._chk(self._L.icp_set_adaptive_trimming(self._h, float(min_fraction), float(max_fraction), int(power)))
-
-    def adaptive_trimming(self):
-        """(min_fraction, max_fraction, power) of adaptive trimming ((0, 0, 0): off)."""
-        lo, hi, q = C.c_float(), C.c_float(), C.c_uint32()
-        self._chk(self._L.icp_get_adaptive_trimming(self._h, C.byref(lo), C.byref(hi), C.byref(q)))
-        return lo.value, hi.value, q.value
-
-    def set_reciprocal(self, on=True, max_gap=0.0):
-        """Reciprocal correspondences (icp_set_reciprocal; not reference behaviour, off by default): a pair (m_i, f_j) keeps its weight
-        only if the moving point f_j finds when it searches the moving frame — a second RBC, over M, which the engine keeps up to date
-        by itself — is m_i, or lies within `max_gap` (the cloud's units) of it; every other pair gets the weight 0.  It acts after the
-        boundary and normal rules and before one-to-one correspondences, trimming and the robust loss.  read(Memory.RECIPROCAL) gives
-        the last iteration's (n, exact, near, accepted), read(Memory.REVERSE_ID) the back search's (dist, id) per fixed point."""
-        self._chk(self._L.icp_set_reciprocal(self._h, int(on), float(max_gap) if on else 0.0))
-
-    def reciprocal(self):
-        """max_gap of reciprocal correspondences, None while the rule is off."""
-        on, g = C.c_int32(), C.c_float()
-        self._chk(self._L.icp_get_reciprocal(self._h, C.byref(on), C.byref(g)))
-        return g.value if on.value else None
-
-    def set_normal_rejection(self, min_cos=None):
-        """Rejection by normal compatibility (icp_set_normal_rejection; not reference behaviour, off by default): a pair whose
-        fixed normal and rotated moving normal enclose an angle with a cosine below `min_cos` (in [-1, 1]) gets the weight 0; a pair
-        without both normals too.  None: off.  It needs NORMALS_F and NORMALS_M (set_normals), under every metric, and acts before
-        one-to-one correspondences, trimming and the robust loss.  read(Memory.PAIR_FILTER) gives the last iteration's
-        (n, at_boundary, incompatible, accepted)."""
-        on = min_cos is not None
-        self._chk(self._L.icp_set_normal_rejection(self._h, int(on), float(min_cos) if on else 0.0))
-
-    def normal_rejection(self):
-        """The cosine threshold of normal rejection, None while it is off."""
-        on, c = C.c_int32(), C.c_float()
-        self._chk(self._L.icp_get_normal_rejection(self._h, C.byref(on), C.byref(c)))
-        return c.value if on.value else None
-
-    def set_projective(self, grid_width=None, fx=1.0, fy=1.0, cx=0.0, cy=0.0, radius=0):
-        """Projective data association (icp_set_projective; not reference behaviour, off by default): instead of searching the RBC, every
-        moving point is transformed, projected through the pinhole model (fx, fy, cx, cy in grid units: grid_intrinsics,
-        landmark_intrinsics) onto F read as a row-major grid `grid_width` wide, and paired with the closest valid fixed point of the
-        (2 radius + 1)^2 window around its cell; a point that lands outside the grid or on an empty window is a rejected pair.
-        radius in [0, 8]; point-to-point needs radius >= 1.  grid_width None or 0: off.  read(Memory.PROJECTIVE) gives the last
-        iteration's (n, hits, outside, empty)."""
-        self._chk(self._L.icp_set_projective(self._h, *_projective_args(grid_width, fx, fy, cx, cy, radius)))
-
-    def projective(self):
-        """(grid_width, fx, fy, cx, cy, radius) of projective data association, None while it is off."""
-        on, gw, r = C.c_int32(), C.c_uint32(), C.c_uint32()
-        f = [C.c_float() for _ in range(4)]
-        self._chk(self._L.icp_get_projective(self._h, C.byref(on), C.byref(gw), *[C.byref(x) for x in f], C.byref(r)))
-        return (gw.value, f[0].value, f[1].value, f[2].value, f[3].value, r.value) if on.value else None
-
-    def set_boundary_rejection(self, grid_width=None):
-        """Rejection at the fixed grid's boundary (icp_set_boundary_rejection; not reference behaviour, off by default): F is read as
-        a row-major grid `grid_width` wide, and a pair whose fixed point lies on the grid's rim, is invalid or has an invalid grid
-        neighbour gets the weight 0.  None or 0: off."""
-        self._chk(self._L.icp_set_boundary_rejection(self._h, int(grid_width or 0)))
-
-    def boundary_rejection(self):
-        """The grid width of boundary rejection, None while it is off."""
-        w = C.c_uint32()
-        self._chk(self._L.icp_get_boundary_rejection(self._h, C.byref(w)))
-        return w.value or None
-
-    def set_robust_loss(self, loss=RobustLoss.NONE, scale=0.0):
-        """Robust loss (icp_set_robust_loss; not reference behaviour, off by default): every pair's weight is multiplied by the
-        loss's IRLS weight omega (s^2 / scale^2) of its own residual s, for every error metric.  `scale` k (finite, > 0, the cloud's
-        units) is ignored with RobustLoss.NONE.  Point-to-point: read(Memory.W) gives the weights after it."""
-        self._chk(self._L.icp_set_robust_loss(self._h, int(loss), float(scale)))
-
-    def robust_loss(self):
-        """(loss, scale) as set ((0, 0.0): off)."""
-        l, k = C.c_int32(), C.c_float()
-        self._chk(self._L.icp_get_robust_loss(self._h, C.byref(l), C.byref(k)))
-        return l.value, k.value
-
-    def set_error_metric(self, metric=ErrorMetric.POINT_TO_POINT, point_weight=0.0):
-        """Point-to-plane ICP (icp_set_error_metric; not reference behaviour, off by default): each iteration minimises the
-        point-to-plane error plus `point_weight` (mu >= 0) times the point-to-point error, linearised, solved by LDL^T on the device.
-        The normals of the fixed frame come from set_normals.  read(Memory.PLANE_SYSTEM) gives the last system and its status."""
-        self._chk(self._L.icp_set_error_metric(self._h, int(metric), float(point_weight)))
-
-    def error_metric(self):
-        """(metric, point_weight) as set."""
-        m, w = C.c_int32(), C.c_float()
-        self._chk(self._L.icp_get_error_metric(self._h, C.byref(m), C.byref(w)))
-        return m.value, w.value
-
-    def set_normals(self, source=Normals.GIVEN, grid_width=0):
-        """Where the fixed frame's normals come from: Normals.GIVEN (write(Memory.NORMALS_F, m x 4 floats)) or Normals.GRID (buildRBC
-        computes them from F read as a row-major grid `grid_width` wide; m must be a multiple of it)."""
-        self._chk(self._L.icp_set_normals(self._h, int(source), int(grid_width)))
-
-    def normals(self):
-        """(source, grid_width) as set."""
-        s, w = C.c_int32(), C.c_uint32()
-        self._chk(self._L.icp_get_normals(self._h, C.byref(s), C.byref(w)))
-        return s.value, w.value
-
-    def set_color_weight(self, kappa):
-        """Colored ICP's photometric weight kappa (icp_set_color_weight; finite, >= 0, default 0, mm^2 per intensity^2): used with
-        set_error_metric(ErrorMetric.COLORED, mu).  The fixed frame's intensity gradients are Memory.COLOR_GRAD_F (m x 4 floats
-        [gx gy gz C]): computed by buildRBC with Normals.GRID, written by the user with Normals.GIVEN."""
-        self._chk(self._L.icp_set_color_weight(self._h, float(kappa)))
-
-    def color_weight(self):
-        """kappa as set."""
-        v = C.c_float()
-        self._chk(self._L.icp_get_color_weight(self._h, C.byref(v)))
-        return v.value
-
-    def set_plane_to_plane(self, epsilon):
-        """Generalized ICP (icp_set_plane_to_plane; not reference behaviour): with ErrorMetric.POINT_TO_PLANE every pair's residual is
-        weighed by (C_Q + C_P)^-1, the covariances R diag(epsilon, 1, 1) R^T of the two frames' normals.  epsilon in (0, 1]; 0 (the
-        default) is off.  The moving frame's normals are Memory.NORMALS_M (m x 4 floats): computed from M with Normals.GRID (by
-        buildRBC and every later write of M), written by the user with Normals.GIVEN."""
-        self._chk(self._L.icp_set_plane_to_plane(self._h, float(epsilon)))
-
-    def plane_to_plane(self):
-        """epsilon as set (0: off)."""
-        v = C.c_float()
-        self._chk(self._L.icp_get_plane_to_plane(self._h, C.byref(v)))
-        return v.value
-
-    def set_symmetric(self, on=True):
-        """Symmetric ICP (icp_set_symmetric; Rusinkiewicz 2019; not reference behaviour): with ErrorMetric.POINT_TO_PLANE every pair's
-        residual is taken along the mean of the two frames' normals and the rotation is split evenly between the frames.  The moving
-        frame's normals are Memory.NORMALS_M, as for set_plane_to_plane (with which, as with ErrorMetric.COLORED, it does not
-        combine): computed from M with Normals.GRID (by buildRBC and every later write of M), written by the user with Normals.GIVEN."""
-        self._chk(self._L.icp_set_symmetric(self._h, int(bool(on))))
-
-    def symmetric(self):
-        """Whether the symmetric objective is switched on."""
-        v = C.c_int32()
-        self._chk(self._L.icp_get_symmetric(self._h, C.byref(v)))
-        return bool(v.value)
+        return self._out(self._L.icp_get_metric_scale, C.c_float)[0]
 
     # -- extensions ------------------------------------------------------------------------
     def setPowerMode(self, mode):
@@ -979,15 +962,12 @@ class ICPStep:
         cloud = np.ascontiguousarray(cloud, np.float32)
         if cloud.size != 640 * 480 * 8:
             raise ValueError("expected a 640x480 float8 cloud")
-        k, reg = C.c_uint32(), C.c_int()
-        self._chk(self._L.icp_track_next(self._h, _p(cloud), int(warm_start), C.byref(k), C.byref(reg)))
-        return k.value if reg.value else None
+        k, registered = self._out(self._L.icp_track_next, _p(cloud), int(warm_start), C.c_uint32, C.c_int)
+        return k if registered else None
 
     def track_form(self):
         """1: tracked frames alternate between two streams behind device-side gates; 0: one stream, host-ordered (icp_track_form)."""
-        g = C.c_int()
-        self._chk(self._L.icp_track_form(self._h, C.byref(g)))
-        return g.value
+        return self._out(self._L.icp_track_form, C.c_int)[0]
 
     def track_reset(self):
         self._chk(self._L.icp_track_reset(self._h))
@@ -1007,9 +987,9 @@ class ICPStep:
 
     def track_collect(self):
         """Result of the oldest frame in flight (blocking): (k, T[8]) or None for the first frame of a sequence."""
-        k, reg, T = C.c_uint32(), C.c_int(), np.empty(8, np.float32)
-        self._chk(self._L.icp_track_collect(self._h, C.byref(k), _p(T), C.byref(reg)))
-        return (k.value, T) if reg.value else None
+        T = np.empty(8, np.float32)
+        k, registered = self._out(self._L.icp_track_collect, C.c_uint32, _p(T), C.c_int)
+        return (k, T) if registered else None
 
     def track_staging(self, slot):
         """Pinned host buffer `slot` (0 / 1) for a whole frame, as a (307200, 8) float32 array: fill it, then track_submit(slot)."""
@@ -1066,15 +1046,11 @@ class ICPStep:
         return out
 
     def time_run_fixed(self, iterations, reps, from_identity=False):
-        ms = C.c_float()
-        self._chk(self._L.icp_time_run_fixed(self._h, iterations, reps, int(from_identity), C.byref(ms)))
-        return ms.value
+        return self._out(self._L.icp_time_run_fixed, iterations, reps, int(from_identity), C.c_float)[0]
 
     def time_run_fixed_tail(self, iterations, reps, from_identity=False):
         """`reps` passes, HIP events around all but the first: (ms over the timed passes, number of timed passes)."""
-        ms, n = C.c_float(), C.c_uint32()
-        self._chk(self._L.icp_time_run_fixed_tail(self._h, iterations, reps, int(from_identity), C.byref(ms), C.byref(n)))
-        return ms.value, n.value
+        return self._out(self._L.icp_time_run_fixed_tail, iterations, reps, int(from_identity), C.c_float, C.c_uint32)
 
     def reset_transform(self):
         """T <- identity, k <- 0 (enqueue only)."""
@@ -1082,27 +1058,19 @@ class ICPStep:
 
     def launches_per_iteration(self):
         """Kernel launches per iteration of run() / run_fixed(): 4 (reference order), 2 (fused) or 1 (fused, chained)."""
-        n = C.c_uint32()
-        self._chk(self._L.icp_launches_per_iteration(self._h, C.byref(n)))
-        return n.value
+        return self._out(self._L.icp_launches_per_iteration, C.c_uint32)[0]
 
     def run_form(self):
         """0 separate launches per stage, 1 chained (one launch per iteration)."""
-        f = C.c_int()
-        self._chk(self._L.icp_run_form(self._h, C.byref(f)))
-        return f.value
+        return self._out(self._L.icp_run_form, C.c_int)[0]
 
     def search_layout(self):
         """(dense, representatives per LDS tile, stage-2 form) of the search kernel in use (diagnostic, see icp_search_layout)."""
-        d, t, s2 = C.c_int(), C.c_int(), C.c_int()
-        self._chk(self._L.icp_search_layout(self._h, C.byref(d), C.byref(t), C.byref(s2)))
-        return d.value, t.value, s2.value
+        return self._out(self._L.icp_search_layout, C.c_int, C.c_int, C.c_int)
 
     def time_masked(self, mask, iterations=40, reps=20):
         """us per iteration of a graph holding only the kernels in `mask` (diagnostic)."""
-        ms = C.c_float()
-        self._chk(self._L.icp_time_masked(self._h, mask, iterations, reps, C.byref(ms)))
-        return ms.value * 1e3 / (iterations * reps)
+        return self._out(self._L.icp_time_masked, mask, iterations, reps, C.c_float)[0] * 1e3 / (iterations * reps)
 
     def profile_run(self, iterations=40, print_table=False):
         """ICP::run(timer) (include/ICP/algorithms.hpp:2482-2494): `iterations` steps with per-step, per-stage times.
@@ -1185,18 +1153,14 @@ class ICP(ICPStep):
 
     def run(self):
         """ICP::run — iterate until check() stops (blocking); returns k."""
-        k = C.c_uint32()
-        self._chk(self._L.icp_run(self._h, C.byref(k)))
-        return k.value
+        return self._out(self._L.icp_run, C.c_uint32)[0]
 
     def step(self, config=False):
         ICPStep.run(self, config)
 
     def run_stats(self):
         """(iteration launches enqueued, final k, launches past the last live iteration) of the last finished checked run."""
-        n, k, d = C.c_uint32(), C.c_uint32(), C.c_uint32()
-        self._chk(self._L.icp_run_stats(self._h, C.byref(n), C.byref(k), C.byref(d)))
-        return n.value, k.value, d.value
+        return self._out(self._L.icp_run_stats, C.c_uint32, C.c_uint32, C.c_uint32)
 
     def run_timeline(self):
         """Host timeline of the last run() in us: [0, launches enqueued, first progress seen, decided, end enqueued, FINAL seen]."""
@@ -1206,9 +1170,7 @@ class ICP(ICPStep):
 
     def launch_stats(self, reset=False):
         """(longest launch call in us, calls slower than 10 us, calls) of the checked runs since init / the last reset."""
-        mx, slow, tot = C.c_double(), C.c_uint64(), C.c_uint64()
-        self._chk(self._L.icp_launch_stats(self._h, C.byref(mx), C.byref(slow), C.byref(tot), int(reset)))
-        return mx.value, slow.value, tot.value
+        return self._out(self._L.icp_launch_stats, C.c_double, C.c_uint64, C.c_uint64, int(reset))
 
     def set_output_mode(self, every_iteration=False):
         """Per-query outputs of checked runs: stored by every iteration, or (default) reproduced on the first read (icp_set_output_mode)."""
@@ -1219,27 +1181,21 @@ class ICP(ICPStep):
         self._chk(self._L.icp_set_run_depth(self._h, depth, int(adaptive)))
 
     def getMaxIterations(self):
-        v = C.c_uint32()
-        self._chk(self._L.icp_get_max_iterations(self._h, C.byref(v)))
-        return v.value
+        return self._out(self._L.icp_get_max_iterations, C.c_uint32)[0]
 
     def setMaxIterations(self, n):
         self._chk(self._L.icp_set_max_iterations(self._h, n))
         self._max_it = n
 
     def getAngleThreshold(self):
-        v = C.c_double()
-        self._chk(self._L.icp_get_angle_threshold(self._h, C.byref(v)))
-        return v.value
+        return self._out(self._L.icp_get_angle_threshold, C.c_double)[0]
 
     def setAngleThreshold(self, deg):
         self._chk(self._L.icp_set_angle_threshold(self._h, deg))
         self._ang = deg
 
     def getTranslationThreshold(self):
-        v = C.c_double()
-        self._chk(self._L.icp_get_translation_threshold(self._h, C.byref(v)))
-        return v.value
+        return self._out(self._L.icp_get_translation_threshold, C.c_double)[0]
 
     def setTranslationThreshold(self, mm):
         self._chk(self._L.icp_set_translation_threshold(self._h, mm))
@@ -1255,7 +1211,7 @@ def batch_partition(registrations, n_slots, i):
     return slot.value, idx.value, cnt.value
 
 
-class ICPBatch:
+class ICPBatch(_Options):
     """B independent registrations over a list of devices inside the library (icp_batch_*, include/icp_amd.h):
     registration i -> device slot i mod n, one host thread and one stream per slot, no collective."""
 
@@ -1298,102 +1254,13 @@ class ICPBatch:
     def set_modes(self, reduce_mode, power_mode):
         self._chk(self._L.icp_batch_set_modes(self._b, reduce_mode, power_mode))
 
-    def set_rejection(self, invalid=False, max_dist=None):
-        """ICPStep.set_rejection on every registration (icp_batch_set_rejection)."""
-        self._chk(self._L.icp_batch_set_rejection(self._b, REJECT_INVALID if invalid else 0, _max_dist_arg(max_dist)))
-        self._rejection = (bool(invalid), None if max_dist in (None, 0, float("inf")) else float(np.float32(max_dist)))
+    def _set(self, name, *cargs):
+        self._chk(getattr(self._L, "icp_batch_set_" + name)(self._b, *cargs))
+        # (the library has no icp_batch_get_*: the batch answers with what it last set, as the C types hold it)
+        self.__dict__.setdefault("_options", {})[name] = tuple(t(v).value for t, v in zip(_OPTIONS[name][0], cargs))
 
-    def rejection(self):
-        """(invalid, max_dist) as last set on this batch."""
-        return getattr(self, "_rejection", (False, None))
-
-    def set_trimming(self, keep=1.0):
-        """ICPStep.set_trimming on every registration (icp_batch_set_trimming)."""
-        self._chk(self._L.icp_batch_set_trimming(self._b, float(keep)))
-        self._trimming = float(np.float32(keep))
-
-    def trimming(self):
-        """The keep fraction as last set on this batch (1.0: off)."""
-        return getattr(self, "_trimming", 1.0)
-
-    def set_unique(self, on=True):
-        """ICPStep.set_unique on every registration (icp_batch_set_unique)."""
-        self._chk(self._L.icp_batch_set_unique(self._b, int(on)))
-        self._unique = bool(on)
-
-    def unique(self):
-        """Whether one-to-one correspondences were last switched on for this batch."""
-        return getattr(self, "_unique", False)
-
-    def set_median_rejection(self, factor):
-        """ICPStep.set_median_rejection on every registration (icp_batch_set_median_rejection)."""
-        self._chk(self._L.icp_batch_set_median_rejection(self._b, float(factor)))
-
-    def set_adaptive_trimming(self, min_fraction=0.05, max_fraction=0.95, power=4):
-        """ICPStep.set_adaptive_trimming on every registration (icp_batch_set_adaptive_trimming)."""
-        self._chk(self._L.icp_batch_set_adaptive_trimming(self._b, float(min_fraction), float(max_fraction), int(power)))
-
-    def set_reciprocal(self, on=True, max_gap=0.0):
-        """ICPStep.set_reciprocal on every registration (icp_batch_set_reciprocal)."""
-        self._chk(self._L.icp_batch_set_reciprocal(self._b, int(on), float(max_gap) if on else 0.0))
-        self._reciprocal = float(np.float32(max_gap)) if on else None
-
-    def reciprocal(self):
-        """max_gap of reciprocal correspondences as last set on this batch, None while the rule is off."""
-        return getattr(self, "_reciprocal", None)
-
-    def set_normal_rejection(self, min_cos=None):
-        """ICPStep.set_normal_rejection on every registration (icp_batch_set_normal_rejection)."""
-        on = min_cos is not None
-        self._chk(self._L.icp_batch_set_normal_rejection(self._b, int(on), float(min_cos) if on else 0.0))
-        self._normal_rejection = float(min_cos) if on else None
-
-    def normal_rejection(self):
-        """The cosine threshold as last set on this batch (None: off)."""
-        return getattr(self, "_normal_rejection", None)
-
-    def set_projective(self, grid_width=None, fx=1.0, fy=1.0, cx=0.0, cy=0.0, radius=0):
-        """ICPStep.set_projective on every registration (icp_batch_set_projective)."""
-        args = _projective_args(grid_width, fx, fy, cx, cy, radius)
-        self._chk(self._L.icp_batch_set_projective(self._b, *args))
-        self._projective = tuple(args[1:2]) + tuple(float(np.float32(x)) for x in args[2:6]) + (args[6],) if args[0] else None
-
-    def projective(self):
-        """(grid_width, fx, fy, cx, cy, radius) as last set on this batch (None: off)."""
-        return getattr(self, "_projective", None)
-
-    def set_boundary_rejection(self, grid_width=None):
-        """ICPStep.set_boundary_rejection on every registration (icp_batch_set_boundary_rejection)."""
-        self._chk(self._L.icp_batch_set_boundary_rejection(self._b, int(grid_width or 0)))
-        self._boundary_rejection = int(grid_width or 0) or None
-
-    def boundary_rejection(self):
-        """The grid width as last set on this batch (None: off)."""
-        return getattr(self, "_boundary_rejection", None)
-
-    def set_robust_loss(self, loss=RobustLoss.NONE, scale=0.0):
-        """ICPStep.set_robust_loss on every registration (icp_batch_set_robust_loss)."""
-        self._chk(self._L.icp_batch_set_robust_loss(self._b, int(loss), float(scale)))
-
-    def set_error_metric(self, metric=ErrorMetric.POINT_TO_POINT, point_weight=0.0):
-        """ICPStep.set_error_metric on every registration (icp_batch_set_error_metric)."""
-        self._chk(self._L.icp_batch_set_error_metric(self._b, int(metric), float(point_weight)))
-
-    def set_normals(self, source=Normals.GIVEN, grid_width=0):
-        """ICPStep.set_normals on every registration (icp_batch_set_normals)."""
-        self._chk(self._L.icp_batch_set_normals(self._b, int(source), int(grid_width)))
-
-    def set_color_weight(self, kappa):
-        """ICPStep.set_color_weight on every registration (icp_batch_set_color_weight)."""
-        self._chk(self._L.icp_batch_set_color_weight(self._b, float(kappa)))
-
-    def set_plane_to_plane(self, epsilon):
-        """ICPStep.set_plane_to_plane on every registration (icp_batch_set_plane_to_plane)."""
-        self._chk(self._L.icp_batch_set_plane_to_plane(self._b, float(epsilon)))
-
-    def set_symmetric(self, on=True):
-        """ICPStep.set_symmetric on every registration (icp_batch_set_symmetric)."""
-        self._chk(self._L.icp_batch_set_symmetric(self._b, int(bool(on))))
+    def _get(self, name):
+        return self.__dict__.get("_options", {}).get(name, _OPTIONS[name][1])
 
     def write(self, i, mem, ptr):
         arr = np.ascontiguousarray(ptr, dtype=np.float32)
@@ -1446,14 +1313,9 @@ class ICPBatch:
 
     def read(self, i, mem):
         dt, cols = _MEM_DTYPE[mem]
-        sizes = {Memory.T: 32, Memory.TK: 32, Memory.MEANS: 32, Memory.S: 44, Memory.NN_ID: self.m * 8, Memory.R: 36, Memory.RK: 36,
-                 Memory.F: self.m * 32, Memory.M: self.m * 32, Memory.W: self.m * 4, Memory.RID: self.m * 4, Memory.TRIM: 16, Memory.UNIQUE: 8, Memory.PAIR_FILTER: 16,
-                 Memory.RECIPROCAL: 16, Memory.REVERSE_ID: self.m * 8, Memory.PROJECTIVE: 16, Memory.MEDIAN: 16, Memory.TRIM_ADAPTIVE: 16,
-                 Memory.NN: self.m * 16, Memory.QT: self.m * 16, Memory.NORMALS_F: self.m * 16, Memory.PLANE_SYSTEM: 28 * 8,
-                 Memory.COLOR_GRAD_F: self.m * 16, Memory.NORMALS_M: self.m * 16}
-        nbytes = sizes[mem]
-        out = np.empty(nbytes // np.dtype(dt).itemsize, dt)
-        self._chk(self._L.icp_batch_read(self._b, i, mem, _p(out), nbytes))
+        n = _mem_elements(mem, self.m)
+        out = np.empty(n, dt)
+        self._chk(self._L.icp_batch_read(self._b, i, mem, _p(out), out.nbytes))
         return out.reshape(-1, cols) if cols else out
 
 

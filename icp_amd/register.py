@@ -5,6 +5,7 @@ import argparse
 import inspect
 import math
 import time
+import types
 
 import numpy as np
 
@@ -37,16 +38,14 @@ def register_clouds(fixed, moving, device=0, a=2e2, c=1e-6, max_iterations=40, a
     levels with 256, 64, 64, .. representatives, 2 x 2 means within a z band of max_dz mm, 0: no band; every option above applies to
     every level with the level's own grid width; k is then the list of the levels' counts, finest first; None: one level); none is
     the reference's behaviour, all are off by default."""
-    return _register(None, **locals())[:4]
+    return _run(False, None, types.SimpleNamespace(**locals()))[:4]
 
 
 def register_and_evaluate(fixed, moving, evaluate, **options):
     """register_clouds (its options) with the registration's quality at the final transform: returns (T[8], k, latency_ms,
     transformed moving cloud, Quality record) — fitness, inlier RMSE, information matrix and counts for pairs no farther apart than
     `evaluate` mm (ICPStep.evaluate; 0 or None: no distance test)."""
-    bound = inspect.signature(register_clouds).bind(fixed, moving, **options)
-    bound.apply_defaults()
-    return _register(0.0 if evaluate is None else evaluate, **bound.arguments)
+    return _run(False, 0.0 if evaluate is None else evaluate, _bind(fixed, moving, options))[:5]
 
 
 def register_with_pairs(fixed, moving, evaluate=None, **options):
@@ -54,9 +53,15 @@ def register_with_pairs(fixed, moving, evaluate=None, **options):
     transformed moving cloud, Quality record or None, pairs) — pairs the Pairs.EVALUATED set (ICPStep.correspondences: a structured
     array of moving index, fixed landmark index, squared distance, weight) for pairs no farther apart than `evaluate` mm (None or 0:
     no distance test); the Quality record is None when `evaluate` is None."""
+    return _run(True, evaluate, _bind(fixed, moving, options))
+
+
+def _bind(fixed, moving, options):
+    """The record register_clouds makes of its arguments — one field per parameter, its defaults filled in —, for the functions that
+    take its options by name; TypeError for a name it does not have."""
     bound = inspect.signature(register_clouds).bind(fixed, moving, **options)
     bound.apply_defaults()
-    return _run(True, evaluate, **bound.arguments)
+    return types.SimpleNamespace(**bound.arguments)
 
 
 def pyramid_nr(levels):
@@ -72,78 +77,68 @@ def level_intrinsics(intr, factor):
     return fx / factor, fy / factor, (cx - h) / factor, (cy - h) / factor
 
 
-def _apply_options(reg, side, reduce_mode, reject_invalid, max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric,
-                   one_to_one, normal_angle, reject_boundary, reciprocal=None, projective=None, median_factor=None, adaptive_trim=None):
-    """register_clouds' options on one handle whose landmark grid is `side` wide (640 x 480 clouds -> 128 x 128 landmarks, row-major;
-    a pyramid level l: 128 >> l)."""
-    if projective is not None:
-        reg.set_projective(side, *level_intrinsics(landmark_intrinsics(), 128 // side), radius=projective)
+def _apply_options(reg, side, o):
+    """The options of register_clouds' record `o` on one handle whose landmark grid is `side` wide (640 x 480 clouds -> 128 x 128
+    landmarks, row-major; a pyramid level l: 128 >> l)."""
+    if o.projective is not None:
+        reg.set_projective(side, *level_intrinsics(landmark_intrinsics(), 128 // side), radius=o.projective)
     reg.setPowerMode(PowerMode.SQUARED)
-    reg.setReduceMode(reduce_mode)
-    if reject_invalid or max_dist:
-        reg.set_rejection(reject_invalid, max_dist)
-    if reject_boundary:
+    reg.setReduceMode(o.reduce_mode)
+    if o.reject_invalid or o.max_dist:
+        reg.set_rejection(o.reject_invalid, o.max_dist)
+    if o.reject_boundary:
         reg.set_boundary_rejection(side)
-    if normal_angle is not None:
+    if o.normal_angle is not None:
         reg.set_normals(Normals.GRID, side)
-        reg.set_normal_rejection(normal_cosine(normal_angle))
-    if reciprocal is not None:
-        reg.set_reciprocal(True, reciprocal)
-    if one_to_one:
+        reg.set_normal_rejection(normal_cosine(o.normal_angle))
+    if o.reciprocal is not None:
+        reg.set_reciprocal(True, o.reciprocal)
+    if o.one_to_one:
         reg.set_unique(True)
-    if median_factor is not None:
-        reg.set_median_rejection(median_factor)
-    if trim != 1.0:
-        reg.set_trimming(trim)
-    if adaptive_trim is not None:
-        reg.set_adaptive_trimming(*adaptive_trim)
-    if robust is not None:
-        reg.set_robust_loss(*robust)
-    if plane_to_plane is not None:
-        reg.set_plane_to_plane(plane_to_plane)
+    if o.median_factor is not None:
+        reg.set_median_rejection(o.median_factor)
+    if o.trim != 1.0:
+        reg.set_trimming(o.trim)
+    if o.adaptive_trim is not None:
+        reg.set_adaptive_trimming(*o.adaptive_trim)
+    if o.robust is not None:
+        reg.set_robust_loss(*o.robust)
+    point_to_plane = o.point_to_plane
+    if o.plane_to_plane is not None:
+        reg.set_plane_to_plane(o.plane_to_plane)
         if point_to_plane is None:
             point_to_plane = 0.0                               # (plane-to-plane acts in the point-to-plane metric)
-    if symmetric:
+    if o.symmetric:
         reg.set_symmetric(True)
         if point_to_plane is None:
             point_to_plane = 0.0                               # (the symmetric objective acts in the point-to-plane metric)
-    if colored is not None:
+    if o.colored is not None:
         reg.set_normals(Normals.GRID, side)
-        reg.set_color_weight(colored)
+        reg.set_color_weight(o.colored)
         reg.set_error_metric(ErrorMetric.COLORED, 0.0 if point_to_plane is None else point_to_plane)
     elif point_to_plane is not None:
         reg.set_normals(Normals.GRID, side)
         reg.set_error_metric(ErrorMetric.POINT_TO_PLANE, point_to_plane)
 
 
-def _register(evaluate, fixed, moving, device, a, c, max_iterations, angle_threshold, translation_threshold, reduce_mode, reject_invalid,
-              max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one, normal_angle, reject_boundary,
-              pyramid=None, reciprocal=None, projective=None, median_factor=None, adaptive_trim=None):
-    """(T[8], k, latency_ms, transformed moving cloud, Quality record or None): register_clouds' options; evaluate None: no evaluation."""
-    return _run(False, **locals())[:5]
-
-
-def _run(pairs, evaluate, fixed, moving, device, a, c, max_iterations, angle_threshold, translation_threshold, reduce_mode, reject_invalid,
-         max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one, normal_angle, reject_boundary,
-         pyramid=None, reciprocal=None, projective=None, median_factor=None, adaptive_trim=None):
-    """_register's five values and a sixth: with `pairs` the Pairs.EVALUATED correspondence set at max_dist = evaluate (None: 0, no
-    distance test), else None."""
-    options = (reduce_mode, reject_invalid, max_dist, trim, point_to_plane, colored, robust, plane_to_plane, symmetric, one_to_one,
-               normal_angle, reject_boundary, reciprocal, projective, median_factor, adaptive_trim)
-    if pyramid is not None:
-        levels, max_dz = pyramid
-        reg = ICPPyramid(device)
-        reg.init(16384, pyramid_nr(levels), a, c, max_iterations, angle_threshold, translation_threshold)
+def _run(pairs, evaluate, o):
+    """(T[8], k, latency_ms, transformed moving cloud, Quality record or None, pairs or None) for register_clouds' record `o`: the
+    quality at max_dist = evaluate (None: no evaluation), with `pairs` the Pairs.EVALUATED correspondence set at the same max_dist (None:
+    0, no distance test).  `o` has one field per parameter of register_clouds."""
+    if o.pyramid is not None:
+        levels, max_dz = o.pyramid
+        reg = ICPPyramid(o.device)
+        reg.init(16384, pyramid_nr(levels), o.a, o.c, o.max_iterations, o.angle_threshold, o.translation_threshold)
         reg.set_reduction(PyramidReduction.MEAN, max_dz)
         for l in range(levels):
-            _apply_options(reg.level(l), 128 >> l, *options)
+            _apply_options(reg.level(l), 128 >> l, o)
         result = reg.level(0)
     else:
-        reg = result = ICP(device)
-        reg.init(16384, 256, a, c, max_iterations, angle_threshold, translation_threshold)   # src/ocl_icp_reg.cpp:81-88
-        _apply_options(reg, 128, *options)
-    reg.write_cloud(Memory.F, fixed)
-    reg.write_cloud(Memory.M, moving)
+        reg = result = ICP(o.device)
+        reg.init(16384, 256, o.a, o.c, o.max_iterations, o.angle_threshold, o.translation_threshold)   # src/ocl_icp_reg.cpp:81-88
+        _apply_options(reg, 128, o)
+    reg.write_cloud(Memory.F, o.fixed)
+    reg.write_cloud(Memory.M, o.moving)
     reg.buildRBC()
     reg.sync()
     t0 = time.perf_counter()
@@ -152,7 +147,7 @@ def _run(pairs, evaluate, fixed, moving, device, a, c, max_iterations, angle_thr
     T = result.read(Memory.T)
     quality = result.evaluate(evaluate)[0] if evaluate is not None else None
     members = result.correspondences(Pairs.EVALUATED, evaluate or 0.0) if pairs else None
-    out = result.transform_cloud(moving)
+    out = result.transform_cloud(o.moving)
     reg.close()
     return T, k, ms, out, quality, members
 
@@ -184,13 +179,6 @@ def _point_weight(s):
     v = float(s)
     if not (v >= 0.0 and math.isfinite(v)):
         raise argparse.ArgumentTypeError("must be finite and >= 0, got %s" % s)
-    return v
-
-
-def _epsilon(s):
-    v = float(s)
-    if not 0.0 < v <= 1.0:
-        raise argparse.ArgumentTypeError("must be in (0, 1], got %s" % s)
     return v
 
 
@@ -268,7 +256,7 @@ def main(argv=None):
     ap.add_argument("moving")
     ap.add_argument("-o", "--output", help="write the transformed moving cloud (raw 640x480 float8)")
     ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("-a", "--alpha", type=float, default=2e2)
+    ap.add_argument("-a", "--alpha", dest="a", metavar="ALPHA", type=float, default=2e2)
     ap.add_argument("--reject-invalid", action="store_true",
                     help="give pairs with an invalid endpoint (a pixel without depth) weight 0 (not reference behaviour)")
     ap.add_argument("--max-dist", type=float, default=None,
@@ -308,7 +296,7 @@ def main(argv=None):
     ap.add_argument("--robust", type=_robust, default=None, metavar="KIND:SCALE",
                     help="robust loss: huber, cauchy or tukey with the scale SCALE (> 0, mm), e.g. tukey:50; every pair is "
                          "down-weighted by its own residual (not reference behaviour)")
-    ap.add_argument("--plane-to-plane", type=_epsilon, default=None, metavar="EPS",
+    ap.add_argument("--plane-to-plane", type=_fraction, default=None, metavar="EPS",
                     help="Generalized ICP: point-to-plane with every pair weighed by both frames' grid normals, covariance parameter "
                          "EPS in (0, 1], e.g. 0.001; implies --point-to-plane 0 when no MU is given (not reference behaviour)")
     ap.add_argument("--symmetric", action="store_true",
@@ -329,18 +317,10 @@ def main(argv=None):
     if args.adaptive_trim is not None and args.trim != 1.0:
         ap.error("--adaptive-trim and --trim exclude each other")
     fixed, moving = load_pc8d(args.fixed), load_pc8d(args.moving)
-    options = dict(device=args.device, a=args.alpha, reject_invalid=args.reject_invalid, max_dist=args.max_dist, trim=args.trim,
-                   point_to_plane=args.point_to_plane, colored=args.colored, robust=args.robust, plane_to_plane=args.plane_to_plane,
-                   symmetric=args.symmetric, one_to_one=args.one_to_one, normal_angle=args.normal_angle,
-                   reject_boundary=args.reject_boundary, pyramid=args.pyramid, reciprocal=args.reciprocal, projective=args.projective,
-                   median_factor=args.median_factor, adaptive_trim=args.adaptive_trim)
-    members = None
-    if args.pairs is not None:
-        T, k, ms, out, quality, members = register_with_pairs(fixed, moving, args.evaluate, **options)
-    elif args.evaluate is None:
-        (T, k, ms, out), quality = register_clouds(fixed, moving, **options), None
-    else:
-        T, k, ms, out, quality = register_and_evaluate(fixed, moving, args.evaluate, **options)
+    # (every option's flag is stored under register_clouds' name for it)
+    names = list(inspect.signature(register_clouds).parameters)[2:]
+    o = _bind(fixed, moving, {name: getattr(args, name) for name in names if hasattr(args, name)})
+    T, k, ms, out, quality, members = _run(args.pairs is not None, args.evaluate, o)
     q, t, s = T[:4], T[4:7], T[7]
     sinth_2 = float(np.linalg.norm(q[:3]))
     angle = 180.0 / math.pi * 2 * math.atan2(sinth_2, float(q[3]))

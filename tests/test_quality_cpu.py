@@ -110,6 +110,21 @@ def test_register_functions_keep_one_shape_each():
     from icp_amd import register
     opts = inspect.signature(register.register_clouds).parameters
     assert "evaluate" not in opts and opts["max_dist"].default is None
-    inner = inspect.signature(register._register).parameters
-    assert list(inner) == ["evaluate"] + list(opts)
-    assert list(inspect.signature(register.register_and_evaluate).parameters)[:3] == ["fixed", "moving", "evaluate"]
+    # the two functions around it take exactly register_clouds' options, by name and with its defaults, behind fixed, moving, evaluate
+    import facade_record
+    import pytest
+    names = list(opts)[2:]
+    for f in (register.register_and_evaluate, register.register_with_pairs):
+        assert list(inspect.signature(f).parameters)[:3] == ["fixed", "moving", "evaluate"]
+        with facade_record.stand_ins(register) as (log, _):
+            plain = f("F", "M", 1.0)
+            assert len(plain) == (5 if f is register.register_and_evaluate else 6) and len(register.register_clouds("F", "M")) == 4
+            for name in names:
+                with pytest.raises(TypeError):
+                    f("F", "M", 1.0, **{name + "_": opts[name].default})
+                del log[:]
+                assert len(f("F", "M", 1.0, **{name: opts[name].default})) == len(plain)
+                explicit = list(log)
+                del log[:]
+                f("F", "M", 1.0)
+                assert explicit == log, name                   # (the default, given by name, is what is taken without it)
