@@ -30,6 +30,15 @@ void free_all (icp_context *h)
     h->run = run_ctl {}; h->track_k_hist[0] = h->track_k_hist[1] = 0; h->track_hist_frame = 0;
     if (h->dCloud) (void) hipFree (h->dCloud);
     if (h->dCloudOut) (void) hipFree (h->dCloudOut);
+    if (h->dRgbdDepth) (void) hipFree (h->dRgbdDepth);
+    if (h->dRgbdColour) (void) hipFree (h->dRgbdColour);
+    h->dRgbdDepth = nullptr; h->dRgbdColour = nullptr; h->rgbd_depth_cap = h->rgbd_colour_cap = 0;
+    for (int k = 0; k < 2; ++k) {
+        if (h->hRgbd[k]) (void) hipHostFree (h->hRgbd[k]);
+        if (h->dRgbd[k]) (void) hipFree (h->dRgbd[k]);
+        h->hRgbd[k] = h->dRgbd[k] = nullptr;
+    }
+    h->rgbd_track_cap = 0;
     h->hF = h->hM = h->hT = nullptr; h->dCloud = h->dCloudOut = nullptr; h->cloud_cap = 0;
     h->dF = h->dM = nullptr; h->ownF = h->ownM = true;
     h->quality = icp_context::quality_buffers {};                 // (they were among dev_allocs)
@@ -1394,6 +1403,108 @@ int icp_write_cloud (icp_handle h, int which, const void *cloud, int block) try
     HIPCHK (h, hipGetLastError ());
     HIPCHK (h, hipStreamSynchronize (h->stream));   // the source is pageable host memory
     (void) block;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
+int icp_set_rgbd (icp_handle h, const icp_rgbd_t *cfg) try
+{
+    api_guard guard_ (h);
+    if (!h) return ICP_EINVAL;
+    const icp_rgbd_t c = cfg ? *cfg : icp_rgbd_default ();
+    if (const char *why = icp_rgbd_refusal (c)) return fail (h, ICP_EINVAL, std::string ("icp_set_rgbd: ") + why);
+    if (h->inited && !icp_rgbd_lattice_fits (c, h->p.side)) return fail (h, ICP_EINVAL, "icp_set_rgbd: the lattice of sqrt (m) x sqrt (m) landmarks leaves the image");
+    if (h->track_submitted != h->track_collected) return fail (h, ICP_ESTATE, "icp_set_rgbd: tracked frames are in flight: collect them first (icp_track_collect)");
+    h->rgbd = c;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
+int icp_get_rgbd (icp_handle h, icp_rgbd_t *cfg) try
+{
+    api_guard guard_ (h);
+    if (!h || !cfg) return ICP_EINVAL;
+    *cfg = h->rgbd;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
+// the device copy of `bytes` of image rows: *q holds at least that much
+static int rgbd_reserve (icp_context *h, void **q, size_t *cap, size_t bytes)
+{
+    if (*cap >= bytes) return ICP_OK;
+    if (*q) { HIPCHK (h, hipStreamSynchronize (h->stream)); (void) hipFree (*q); }
+    *q = nullptr; *cap = 0;
+    HIPCHK (h, hipMalloc (q, bytes));
+    *cap = bytes;
+    return ICP_OK;
+}
+
+int icp_write_rgbd (icp_handle h, int which, const uint16_t *depth, const uint8_t *rgb, int normals, int block) try
+{
+    api_guard guard_ (h);
+    int rc = need (h, false); if (rc) return rc;
+    if (which != ICP_MEM_F && which != ICP_MEM_M) return fail (h, ICP_EINVAL, "which must be ICP_MEM_F or ICP_MEM_M");
+    if (!depth) return fail (h, ICP_EINVAL, "null pointer");
+    const icp_rgbd_t &c = h->rgbd;
+    const uint32_t side = h->p.side;
+    if ((uint64_t) side * side != h->p.m || !icp_rgbd_lattice_fits (c, side))
+        return fail (h, ICP_EINVAL, "icp_write_rgbd: the lattice of sqrt (m) x sqrt (m) landmarks does not fit the image (icp_set_rgbd)");
+    if ((rc = set_device (h))) return rc;
+    // (whole image rows: contiguous in the caller's images, so each goes up by one copy)
+    const icp_rgbd_region g = icp_rgbd_region_of (c, side, normals != 0);
+    const uint32_t d0 = g.dy0, c0 = c.y0, c1 = c.y0 + c.step_y * (side - 1u) + 1u;
+    const size_t dbytes = g.depth_bytes (false, c.width), cbytes = (size_t) (c1 - c0) * c.width * 3u;
+    if ((rc = rgbd_reserve (h, (void **) &h->dRgbdDepth, &h->rgbd_depth_cap, dbytes))) return rc;
+    if (rgb && (rc = rgbd_reserve (h, (void **) &h->dRgbdColour, &h->rgbd_colour_cap, cbytes))) return rc;
+    note_inputs_change (h);
+    HIPCHK (h, hipMemcpyAsync (h->dRgbdDepth, depth + (size_t) d0 * c.width, dbytes, hipMemcpyHostToDevice, h->stream));
+    if (rgb) HIPCHK (h, hipMemcpyAsync (h->dRgbdColour, rgb + (size_t) c0 * c.width * 3u, cbytes, hipMemcpyHostToDevice, h->stream));
+    icp_rgbd_args a {};
+    a.c = c; a.depth = h->dRgbdDepth; a.rgb = rgb ? h->dRgbdColour : nullptr;
+    a.dx0 = 0u; a.dy0 = d0; a.dpitch = c.width; a.cx0 = 0u; a.cy0 = c0; a.cpitch = c.width; a.cstep = 1u; a.side = side;
+    a.out = reinterpret_cast<float4 *> (which == ICP_MEM_F ? h->dF : h->dM);
+    // (the normals as icp_write of the object places them: registration 0's, behind whatever the stream holds)
+    a.nrm = normals ? const_cast<float4 *> (static_cast<const float4 *> (mem_of (h, 0u, which == ICP_MEM_F ? ICP_MEM_NORMALS_F : ICP_MEM_NORMALS_M).ptr)) : nullptr;
+    icp_launch_rgbd_lattice (a, h->stream);
+    if (which == ICP_MEM_M) normals_m_follow (h, 0u, 1u);
+    HIPCHK (h, hipGetLastError ());
+    HIPCHK (h, hipStreamSynchronize (h->stream));   // the sources are pageable host memory
+    (void) block;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
+// Diagnostic: one form of the front end alone — whole images uploaded once, `reps` launches between two events on the handle's stream, into
+// the cloud scratch (F, M and the normals stay as they are).
+int icp_time_rgbd (icp_handle h, int dense, int normals, const uint16_t *depth, const uint8_t *rgb, uint32_t reps, float *us_per_launch) try
+{
+    api_guard guard_ (h);
+    int rc = need (h, false); if (rc) return rc;
+    if (!depth || !us_per_launch || reps == 0u) return fail (h, ICP_EINVAL, "icp_time_rgbd: bad arguments");
+    const icp_rgbd_t &c = h->rgbd;
+    const uint32_t side = h->p.side, n = c.width * c.height;
+    if (!dense && !icp_rgbd_lattice_fits (c, side)) return fail (h, ICP_EINVAL, "icp_time_rgbd: the lattice does not fit the image (icp_set_rgbd)");
+    if ((rc = set_device (h))) return rc;
+    if ((rc = rgbd_reserve (h, (void **) &h->dRgbdDepth, &h->rgbd_depth_cap, (size_t) n * 2u))) return rc;
+    if (rgb && (rc = rgbd_reserve (h, (void **) &h->dRgbdColour, &h->rgbd_colour_cap, (size_t) n * 3u))) return rc;
+    if ((rc = cloud_reserve (h, n))) return rc;                          // (n >= side^2: the lattice lies inside the image)
+    HIPCHK (h, hipMemcpyAsync (h->dRgbdDepth, depth, (size_t) n * 2u, hipMemcpyHostToDevice, h->stream));
+    if (rgb) HIPCHK (h, hipMemcpyAsync (h->dRgbdColour, rgb, (size_t) n * 3u, hipMemcpyHostToDevice, h->stream));
+    icp_rgbd_args a {};
+    a.c = c; a.depth = h->dRgbdDepth; a.rgb = rgb ? h->dRgbdColour : nullptr;
+    a.dpitch = a.cpitch = c.width; a.cstep = 1u; a.side = side;
+    a.out = reinterpret_cast<float4 *> (h->dCloud); a.nrm = normals ? reinterpret_cast<float4 *> (h->dCloudOut) : nullptr;
+    auto launch = [&] () { if (dense) icp_launch_rgbd_dense (a, h->stream); else icp_launch_rgbd_lattice (a, h->stream); };
+    launch ();                                                           // (untimed: the code object is loaded)
+    HIPCHK (h, hipEventRecord (h->ev0, h->stream));
+    for (uint32_t i = 0; i < reps; ++i) launch ();
+    HIPCHK (h, hipEventRecord (h->ev1, h->stream));
+    HIPCHK (h, hipGetLastError ());
+    HIPCHK (h, hipEventSynchronize (h->ev1));
+    float ms = 0.f;
+    HIPCHK (h, hipEventElapsedTime (&ms, h->ev0, h->ev1));
+    *us_per_launch = ms * 1e3f / (float) reps;
     return ICP_OK;
 }
 ICP_CATCH_ALL

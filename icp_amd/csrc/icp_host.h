@@ -7,6 +7,7 @@
 #include "../../include/icp_amd.h"
 #include "icp_kernels.h"
 #include "icp_rbc_set.h"
+#include "icp_rgbd.h"
 #include "icp_cguard.h"
 
 #include <atomic>
@@ -165,6 +166,13 @@ struct icp_context {
     // arrival words and the tables, the fractions and the power
     uint32_t *adaptive = nullptr;
     float *dCloud = nullptr, *dCloudOut = nullptr; uint32_t cloud_cap = 0;
+    // the RGB-D front end (icp_set_rgbd; survives icp_init) and the device copies of the image rows icp_write_rgbd reads (allocated at its
+    // first use, grown when a call needs more, freed by icp_init)
+    icp_rgbd_t rgbd = icp_rgbd_default ();
+    uint16_t *dRgbdDepth = nullptr; uint8_t *dRgbdColour = nullptr; size_t rgbd_depth_cap = 0, rgbd_colour_cap = 0;
+    // tracking from images (icp_track_submit_rgbd): per staging slot the packed region of a frame — its depth box, then its colour rows —
+    // pinned / device; sized by track_prepare for the configuration in force
+    char *hRgbd[2] = { nullptr, nullptr }, *dRgbd[2] = { nullptr, nullptr }; size_t rgbd_track_cap = 0;
     std::map<uint64_t, icp_host::graph_entry> graphs;      // key: iterations << 3 | check << 2 | parity (+ fresh, + kind: see get_graph)
     uint32_t parity = 0;                         // tracking: which landmark buffers are the fixed / moving set (graphs hold pointers): frame f -> f mod 3
     // frame-to-frame tracking (icp_track_*): three landmark buffers in rotation, band staging, a copy stream

@@ -12,21 +12,9 @@
 // point-to-point kernels carries any of this code; the translation unit is built with -ffp-contract=off like every other, so each
 // expression below is evaluated exactly in the order it is written.
 #include "icp_plane_moments.h"          // (plane_moments, intensity; icp_pair_rule.h)
+#include "icp_normal_rule.h"            // (icp_grid_normal)
 
 namespace {
-
-// (a grid point takes part in a difference or a gradient when it is valid — icp_point_valid: a Kinect pixel without depth is not)
-__device__ __forceinline__ float3 nrm_sub (float3 a, float3 b) { return make_float3 (a.x - b.x, a.y - b.y, a.z - b.z); }
-
-// the difference along one grid axis: central if both neighbours are valid, else one-sided against the centre (the next neighbour first)
-__device__ __forceinline__ bool nrm_diff (float3 prev, bool has_prev, float3 c, float3 next, bool has_next, float3 &d)
-{
-    const bool vp = has_prev && icp_point_valid (prev.x, prev.y, prev.z), vn = has_next && icp_point_valid (next.x, next.y, next.z);
-    if (vp && vn) d = nrm_sub (next, prev);
-    else if (vn) d = nrm_sub (next, c);
-    else if (vp) d = nrm_sub (c, prev);
-    return vp || vn;
-}
 
 // A x = bb for a symmetric N x N A by LDL^T, column by column:  e_jk = L_jk d_k;  d_j = A_jj - e_j0 L_j0 - .. - e_j(j-1) L_j(j-1)
 // (subtracted in order k = 0, 1, ..);  L_ij = (A_ij - L_i0 e_j0 - .. - L_i(j-1) e_j(j-1)) / d_j for i > j.  Then L y = bb (y_i = bb_i -
@@ -73,9 +61,7 @@ __device__ __forceinline__ void ldlt_solve (const double (&A)[N][N], const doubl
 
 // NORMALS_F of the fixed set (src = F), read as a row-major grid p.nrm_grid wide (m % width == 0: icp_build_rbc checks it); with
 // plane-to-plane or the symmetric objective on also NORMALS_M of the moving set (src = M).  One thread per point, grid.y = registration counted from src and nrm.
-// fp32, no contraction:
-//   c = dh x dv,  n = c / sqrtf ((c.x^2 + c.y^2) + c.z^2),  n = -n if (n.x C.x + n.y C.y) + n.z C.z > 0 (faces the sensor at the origin),
-//   n = 0 when the centre is invalid, a difference is missing, or the length is not > 0 and finite.
+// The rule: icp_grid_normal (icp_normal_rule.h).
 __global__ __launch_bounds__ (256) void k_normals_grid (icp_params p, const float *src, float4 *nrm)
 {
     const uint32_t b = blockIdx.y, i = blockIdx.x * 256u + threadIdx.x;
@@ -83,23 +69,11 @@ __global__ __launch_bounds__ (256) void k_normals_grid (icp_params p, const floa
     const uint32_t W = p.nrm_grid, x = i % W, y = i / W, H = p.m / W;
     const float *F = src + (size_t) b * p.m * 8;
     auto at = [&] (uint32_t j) { const float *r = F + (size_t) j * 8; return make_float3 (r[0], r[1], r[2]); };
-    const float3 c = at (i);
-    float4 n = make_float4 (0.f, 0.f, 0.f, 0.f);
-    float3 dh = make_float3 (0.f, 0.f, 0.f), dv = dh;
-    const float3 zero = dh;
+    const float3 zero = make_float3 (0.f, 0.f, 0.f);
     // (i + 1 < m, y + 1 < H: no read beyond the set even if the width did not divide m — the host refuses that, ICP_ESTATE)
     const bool hasl = x > 0u, hasr = x + 1u < W && i + 1u < p.m, hasu = y > 0u, hasd = y + 1u < H;
-    if (icp_point_valid (c.x, c.y, c.z) &&
-        nrm_diff (hasl ? at (i - 1u) : zero, hasl, c, hasr ? at (i + 1u) : zero, hasr, dh) &&
-        nrm_diff (hasu ? at (i - W) : zero, hasu, c, hasd ? at (i + W) : zero, hasd, dv)) {
-        const float cx = dh.y * dv.z - dh.z * dv.y, cy = dh.z * dv.x - dh.x * dv.z, cz = dh.x * dv.y - dh.y * dv.x;
-        const float len = sqrtf ((cx * cx + cy * cy) + cz * cz);
-        if (len > 0.f && len < __builtin_inff ()) {
-            float nx = cx / len, ny = cy / len, nz = cz / len;
-            if ((nx * c.x + ny * c.y) + nz * c.z > 0.f) { nx = -nx; ny = -ny; nz = -nz; }
-            n = make_float4 (nx, ny, nz, 0.f);
-        }
-    }
+    const float4 n = icp_grid_normal (at (i), hasl ? at (i - 1u) : zero, hasl, hasr ? at (i + 1u) : zero, hasr,
+                                      hasu ? at (i - W) : zero, hasu, hasd ? at (i + W) : zero, hasd);
     nrm[(size_t) b * p.m + i] = n;
 }
 

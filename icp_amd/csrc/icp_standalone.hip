@@ -10,6 +10,7 @@
 #include "../../include/icp_amd.h"
 #include "icp_cguard.h"
 #include "icp_kernels.h"
+#include "icp_rgbd.h"
 
 #include <cmath>
 #include <cstring>
@@ -484,6 +485,46 @@ int icp_kernel_s (int device, int weighted, const float *DM, const float *DF, co
     if ((rc = icp_ko_create (&g.k, device, weighted ? ICP_KO_S_WEIGHTED : ICP_KO_S, m, 0, c))) return rc;
     if ((rc = icp_ko_write (g.k, 0, DM)) || (rc = icp_ko_write (g.k, 1, DF)) || (weighted && (rc = icp_ko_write (g.k, 2, W))) || (rc = icp_ko_run (g.k))) return rc;
     return icp_ko_read (g.k, 3, S11);
+}
+ICP_CATCH_ALL
+
+// The RGB-D front end's dense form (icp_rgbd.hip: k_rgbd_dense): whole images up, every pixel's point (and normal) down
+namespace {
+struct sa_buffers {
+    std::vector<void *> q;
+    ~sa_buffers () { for (void *b : q) (void) hipFree (b); }
+    int get (void **out, size_t bytes)
+    {
+        void *b = nullptr;
+        const hipError_t e = hipMalloc (&b, bytes ? bytes : 1);
+        if (e != hipSuccess) return sa_fail (ICP_ENOMEM, std::string ("hipMalloc: ") + hipGetErrorString (e));
+        q.push_back (b); *out = b;
+        return ICP_OK;
+    }
+};
+}
+
+int icp_kernel_rgbd (int device, const icp_rgbd_t *cfg, const uint16_t *depth, const uint8_t *rgb, void *cloud_out, float *normals_out) try
+{
+    if (!depth || !cloud_out) return sa_fail (ICP_EINVAL, "null pointer");
+    const icp_rgbd_t c = cfg ? *cfg : icp_rgbd_default ();
+    if (const char *why = icp_rgbd_refusal (c)) return sa_fail (ICP_EINVAL, std::string ("icp_kernel_rgbd: ") + why);
+    int rc = sa_device (device); if (rc) return rc;
+    const size_t n = (size_t) c.width * c.height;
+    sa_buffers B;
+    uint16_t *dD = nullptr; uint8_t *dC = nullptr; float4 *dO = nullptr, *dN = nullptr;
+    if ((rc = B.get ((void **) &dD, n * 2)) || (rgb && (rc = B.get ((void **) &dC, n * 3))) || (rc = B.get ((void **) &dO, n * 32)) ||
+        (normals_out && (rc = B.get ((void **) &dN, n * 16)))) return rc;
+    auto chk = [] (hipError_t e, const char *what) { return e == hipSuccess ? ICP_OK : sa_fail (ICP_EHIP, std::string (what) + ": " + hipGetErrorString (e)); };
+    if ((rc = chk (hipMemcpy (dD, depth, n * 2, hipMemcpyHostToDevice), "hipMemcpy"))) return rc;
+    if (rgb && (rc = chk (hipMemcpy (dC, rgb, n * 3, hipMemcpyHostToDevice), "hipMemcpy"))) return rc;
+    icp_rgbd_args a {};
+    a.c = c; a.depth = dD; a.rgb = dC; a.dpitch = a.cpitch = c.width; a.cstep = 1u; a.out = dO; a.nrm = dN;
+    icp_launch_rgbd_dense (a, 0);
+    if ((rc = chk (hipGetLastError (), "icp_kernel_rgbd"))) return rc;
+    if ((rc = chk (hipMemcpy (cloud_out, dO, n * 32, hipMemcpyDeviceToHost), "hipMemcpy"))) return rc;     // (blocking: behind the kernel on the null stream)
+    if (normals_out && (rc = chk (hipMemcpy (normals_out, dN, n * 16, hipMemcpyDeviceToHost), "hipMemcpy"))) return rc;
+    return ICP_OK;
 }
 ICP_CATCH_ALL
 

@@ -15,9 +15,12 @@ extern "C" {
 // run (icp_run.hip) whose final state the device stores into the frame's slot of a pinned ring (hTrack, words in hTrackMirror);
 // consecutive registrations alternate between two streams, each behind a one-wave gate kernel that waits for its predecessor's release
 // of the sequence word (track_submit).  ICP_AMD_RUN_ADAPTIVE=0 keeps rounds 1 - 3's form: one graph per frame on one stream.
+// A frame given as images (icp_track_submit_rgbd) differs in the source of its landmarks alone: the packed region of the image pair that the
+// lattice form of the RGB-D front end reads goes through staging of its own, and k_rgbd_lattice runs in k_get_lms_band's place.
 #define ICP_TRACK_RING 4u
 
-static int track_prepare (icp_context *h)
+// rgbd: the frame comes as images (icp_track_submit_rgbd) — the staging of the packed region exists and holds the configuration in force
+static int track_prepare (icp_context *h, bool rgbd = false)
 {
     if (h->p.m != 16384u || h->p.batch != 1u) return fail (h, ICP_EINVAL, "tracking needs m == 16384 (getLMs) and a single registration");
     if (!h->ownF || !h->ownM) return fail (h, ICP_ESTATE, "tracking rotates the handle's own landmark buffers: not available with adopted F / M buffers");
@@ -30,6 +33,25 @@ static int track_prepare (icp_context *h)
     if (!h->hTrackMirror) {
         HIPCHK (h, hipHostMalloc ((void **) &h->hTrackMirror, ICP_TRACK_RING * sizeof (unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
         std::memset (h->hTrackMirror, 0, ICP_TRACK_RING * sizeof (unsigned long long));
+    }
+    if (rgbd) {
+        const icp_rgbd_region g = icp_rgbd_region_of (h->rgbd, h->p.side, false);
+        const size_t bytes = g.depth_bytes (true, h->rgbd.width) + (size_t) h->p.side * (g.cx1 - h->rgbd.x0) * 3u;
+        if (h->rgbd_track_cap < bytes) {
+            // (a configuration changes only with nothing in flight — icp_set_rgbd —: no upload out of the old buffers is queued)
+            HIPCHK (h, hipStreamSynchronize (h->copy_stream));
+            for (int k = 0; k < 2; ++k) {
+                if (h->hRgbd[k]) (void) hipHostFree (h->hRgbd[k]);
+                if (h->dRgbd[k]) (void) hipFree (h->dRgbd[k]);
+                h->hRgbd[k] = h->dRgbd[k] = nullptr;
+            }
+            h->rgbd_track_cap = 0;
+            for (int k = 0; k < 2; ++k) {
+                HIPCHK (h, hipHostMalloc ((void **) &h->hRgbd[k], bytes, hipHostMallocDefault));
+                HIPCHK (h, hipMalloc ((void **) &h->dRgbd[k], bytes));
+            }
+            h->rgbd_track_cap = bytes;
+        }
     }
     if (h->run_adaptive && h->track_gate && !h->rbc2_ready) {
         // frames gated on the device: a second stream, the sequence word and the run flags, a second set of RBC buffers (frame f builds its
@@ -312,7 +334,8 @@ static uint32_t track_blind (const icp_context *h)
     return k ? k + 1u : h->run_depth + 1u;
 }
 
-static int track_submit (icp_context *h, const void *cloud, int warm_start, bool blocking)
+// rgb_frame: the frame is an image pair — `cloud` its depth image, *rgb_frame its colour image or null — in place of a float8 cloud
+static int track_submit (icp_context *h, const void *cloud, int warm_start, bool blocking, const uint8_t *const *rgb_frame = nullptr)
 {
     double tp_last = g_tp.on ? now_s () : 0.0; const double tp_first = tp_last;
     int rc = need (h, false, true); if (rc) return rc;
@@ -339,7 +362,9 @@ static int track_submit (icp_context *h, const void *cloud, int warm_start, bool
     if (h->opt.boundary_gw && h->p.m % h->opt.boundary_gw)
         return fail (h, ICP_ESTATE, "icp_track_submit: icp_set_boundary_rejection: m is not a multiple of the grid width");
     if ((rc = set_device (h))) return rc;
-    if ((rc = track_prepare (h))) return rc;                            // (everything that can fail for lack of memory comes first)
+    if (rgb_frame && !icp_rgbd_lattice_fits (h->rgbd, h->p.side))
+        return fail (h, ICP_EINVAL, "icp_track_submit_rgbd: the lattice of sqrt (m) x sqrt (m) landmarks does not fit the image (icp_set_rgbd)");
+    if ((rc = track_prepare (h, rgb_frame != nullptr))) return rc;     // (everything that can fail for lack of memory comes first)
     if (h->track_submitted - h->track_collected >= ICP_TRACK_RING)
         return fail (h, ICP_ESTATE, "icp_track_submit: four frames are in flight: collect a result first (icp_track_collect)");
     const uint64_t f = h->track_submitted;
@@ -381,37 +406,65 @@ static int track_submit (icp_context *h, const void *cloud, int warm_start, bool
     }
     tend ();
     TP (1);
-    const bool staged = cloud == h->hFrame[0] || cloud == h->hFrame[1];
-    bool pinned = staged;
-    for (const auto &r : h->sources)                                    // a frame in one of the caller's registered (page-locked) buffers
-        if (static_cast<const char *> (cloud) >= r.base && static_cast<const char *> (cloud) + (size_t) 640 * 480 * 32 <= r.base + r.bytes) pinned = true;
-    if (pinned) {
-        // the caller filled one of the engine's pinned frame buffers (icp_track_staging): the band goes by DMA straight from there
-        HIPCHK (h, hipMemcpy2DAsync (h->dBand[s], ICP_BAND_ROW_BYTES, src, spitch, ICP_BAND_ROW_BYTES, ICP_BAND_ROWS, hipMemcpyHostToDevice, h->copy_stream));
-        if (staged) HIPCHK (h, hipEventRecord (h->evFrame[cloud == h->hFrame[0] ? 0 : 1], h->copy_stream));
-        tend ();
-    } else {
-        // pageable source: the band's 128 row segments into the slot's pinned staging (free once the upload of frame f - 2 is through)
+    if (rgb_frame) {
+        // an image pair: the depth rows of the lattice's bounding box (grown by the radius) and the colour rows of the lattice into the slot's
+        // pinned staging (free once the upload of frame f - 2 is through), one upload, the lattice kernel in k_get_lms_band's place
+        const icp_rgbd_t &c = h->rgbd;
+        const icp_rgbd_region g = icp_rgbd_region_of (c, h->p.side, false);
+        const uint16_t *depth = static_cast<const uint16_t *> (cloud);
+        const uint8_t *rgb = *rgb_frame;
+        const size_t drow = (size_t) (g.dx1 - g.dx0) * sizeof (uint16_t), dbytes = g.depth_bytes (true, c.width), crow = (size_t) (g.cx1 - c.x0) * 3u;
         if (f >= 2u) HIPCHK (h, hipEventSynchronize (h->evUp[s]));
-        // in two pieces, each uploaded as soon as it is staged: the DMA of the first runs under the host copy of the second (a blocking
-        // icp_track_next waits for 60 us of copy + 45 us of upload otherwise; every copy command costs ~12 us by itself, so more pieces
-        // give the gain back: 1 / 2 / 4 pieces = 393 / 371 / 393 us per blocking cold frame; ICP_AMD_BAND_PIECES for the comparison)
-        static const uint32_t npieces = [] { const char *e = std::getenv ("ICP_AMD_BAND_PIECES"); const int v = e ? std::atoi (e) : 2; return (v == 1 || v == 2 || v == 4 || v == 8) ? (uint32_t) v : 2u; } ();
-        const uint32_t piece = ICP_BAND_ROWS / npieces;
-        for (uint32_t j = 0; j < ICP_BAND_ROWS; ++j) {
-            std::memcpy (reinterpret_cast<char *> (h->hBand[s]) + (size_t) j * ICP_BAND_ROW_BYTES, src + (size_t) j * spitch, ICP_BAND_ROW_BYTES);
-            // (the copy takes ~60 us: the previous frame's open registration is looked after on the way — a word read, a launch if it needs one)
-            if ((j & 7u) == 7u && P->active) (void) run_pump (h, *P);
-            if ((j + 1u) % piece == 0u) {
-                const size_t off = (size_t) (j + 1u - piece) * ICP_BAND_ROW_BYTES;
-                HIPCHK (h, hipMemcpyAsync (reinterpret_cast<char *> (h->dBand[s]) + off, reinterpret_cast<char *> (h->hBand[s]) + off, (size_t) piece * ICP_BAND_ROW_BYTES,
-                                           hipMemcpyHostToDevice, h->copy_stream));
-                tend ();
+        for (uint32_t v = g.dy0; v < g.dy1; ++v) {
+            std::memcpy (h->hRgbd[s] + (size_t) (v - g.dy0) * drow, depth + (size_t) v * c.width + g.dx0, drow);
+            if ((v & 15u) == 15u && P->active) (void) run_pump (h, *P);
+        }
+        if (rgb)
+            for (uint32_t j = 0; j < h->p.side; ++j) {
+                std::memcpy (h->hRgbd[s] + dbytes + (size_t) j * crow, rgb + ((size_t) (c.y0 + c.step_y * j) * c.width + c.x0) * 3u, crow);
+                if ((j & 15u) == 15u && P->active) (void) run_pump (h, *P);
+            }
+        HIPCHK (h, hipMemcpyAsync (h->dRgbd[s], h->hRgbd[s], dbytes + (rgb ? (size_t) h->p.side * crow : 0u), hipMemcpyHostToDevice, h->copy_stream));
+        tend ();
+        TP (2);
+        icp_rgbd_args a {};
+        a.c = c; a.depth = reinterpret_cast<const uint16_t *> (h->dRgbd[s]); a.rgb = rgb ? reinterpret_cast<const uint8_t *> (h->dRgbd[s] + dbytes) : nullptr;
+        a.dx0 = g.dx0; a.dy0 = g.dy0; a.dpitch = g.dx1 - g.dx0; a.cx0 = c.x0; a.cy0 = c.y0; a.cpitch = g.cx1 - c.x0; a.cstep = c.step_y;
+        a.side = h->p.side; a.out = reinterpret_cast<float4 *> (h->lm[buf]); a.nrm = nullptr;
+        icp_launch_rgbd_lattice (a, h->copy_stream);
+    } else {
+        const bool staged = cloud == h->hFrame[0] || cloud == h->hFrame[1];
+        bool pinned = staged;
+        for (const auto &r : h->sources)                                    // a frame in one of the caller's registered (page-locked) buffers
+            if (static_cast<const char *> (cloud) >= r.base && static_cast<const char *> (cloud) + (size_t) 640 * 480 * 32 <= r.base + r.bytes) pinned = true;
+        if (pinned) {
+            // the caller filled one of the engine's pinned frame buffers (icp_track_staging): the band goes by DMA straight from there
+            HIPCHK (h, hipMemcpy2DAsync (h->dBand[s], ICP_BAND_ROW_BYTES, src, spitch, ICP_BAND_ROW_BYTES, ICP_BAND_ROWS, hipMemcpyHostToDevice, h->copy_stream));
+            if (staged) HIPCHK (h, hipEventRecord (h->evFrame[cloud == h->hFrame[0] ? 0 : 1], h->copy_stream));
+            tend ();
+        } else {
+            // pageable source: the band's 128 row segments into the slot's pinned staging (free once the upload of frame f - 2 is through)
+            if (f >= 2u) HIPCHK (h, hipEventSynchronize (h->evUp[s]));
+            // in two pieces, each uploaded as soon as it is staged: the DMA of the first runs under the host copy of the second (a blocking
+            // icp_track_next waits for 60 us of copy + 45 us of upload otherwise; every copy command costs ~12 us by itself, so more pieces
+            // give the gain back: 1 / 2 / 4 pieces = 393 / 371 / 393 us per blocking cold frame; ICP_AMD_BAND_PIECES for the comparison)
+            static const uint32_t npieces = [] { const char *e = std::getenv ("ICP_AMD_BAND_PIECES"); const int v = e ? std::atoi (e) : 2; return (v == 1 || v == 2 || v == 4 || v == 8) ? (uint32_t) v : 2u; } ();
+            const uint32_t piece = ICP_BAND_ROWS / npieces;
+            for (uint32_t j = 0; j < ICP_BAND_ROWS; ++j) {
+                std::memcpy (reinterpret_cast<char *> (h->hBand[s]) + (size_t) j * ICP_BAND_ROW_BYTES, src + (size_t) j * spitch, ICP_BAND_ROW_BYTES);
+                // (the copy takes ~60 us: the previous frame's open registration is looked after on the way — a word read, a launch if it needs one)
+                if ((j & 7u) == 7u && P->active) (void) run_pump (h, *P);
+                if ((j + 1u) % piece == 0u) {
+                    const size_t off = (size_t) (j + 1u - piece) * ICP_BAND_ROW_BYTES;
+                    HIPCHK (h, hipMemcpyAsync (reinterpret_cast<char *> (h->dBand[s]) + off, reinterpret_cast<char *> (h->hBand[s]) + off, (size_t) piece * ICP_BAND_ROW_BYTES,
+                                               hipMemcpyHostToDevice, h->copy_stream));
+                    tend ();
+                }
             }
         }
+        TP (2);
+        icp_launch_get_lms_band (h->dBand[s], h->lm[buf], h->copy_stream);
     }
-    TP (2);
-    icp_launch_get_lms_band (h->dBand[s], h->lm[buf], h->copy_stream);
     HIPCHK (h, hipGetLastError ());
     tend ();
     HIPCHK (h, hipEventRecord (h->evUp[s], h->copy_stream));
@@ -514,6 +567,8 @@ static int track_submit (icp_context *h, const void *cloud, int warm_start, bool
 
 int icp_track_submit (icp_handle h, const void *cloud, int warm_start) try { api_guard guard_ (h); return track_submit (h, cloud, warm_start, false); } ICP_CATCH_ALL
 
+int icp_track_submit_rgbd (icp_handle h, const uint16_t *depth, const uint8_t *rgb, int warm_start) try { api_guard guard_ (h); return track_submit (h, depth, warm_start, false, &rgb); } ICP_CATCH_ALL
+
 int icp_track_form (icp_handle h, int *gated) try
 {
     api_guard guard_ (h);
@@ -565,18 +620,30 @@ int icp_track_collect (icp_handle h, uint32_t *k, float *T8, int *registered) tr
 }
 ICP_CATCH_ALL
 
-int icp_track_next (icp_handle h, const void *cloud, int warm_start, uint32_t *k, int *registered) try
+static int track_next (icp_context *h, const void *cloud, const uint8_t *const *rgb_frame, int warm_start, uint32_t *k, int *registered)
 {
-    api_guard guard_ (h);
     if (k) *k = 0;
     if (registered) *registered = 0;
     int rc = need (h, false, true); if (rc) return rc;
     while (h->track_collected < h->track_submitted)                     // (results of an earlier pipelined use nobody collected)
         if ((rc = icp_track_collect (h, nullptr, nullptr, nullptr))) return rc;
-    if ((rc = track_submit (h, cloud, warm_start, true))) return rc;
+    if ((rc = track_submit (h, cloud, warm_start, true, rgb_frame))) return rc;
     if ((rc = icp_track_collect (h, k, nullptr, registered))) return rc;
     if (!h->run_adaptive) return settle (h);
     return ICP_OK;
+}
+
+int icp_track_next (icp_handle h, const void *cloud, int warm_start, uint32_t *k, int *registered) try
+{
+    api_guard guard_ (h);
+    return track_next (h, cloud, nullptr, warm_start, k, registered);
+}
+ICP_CATCH_ALL
+
+int icp_track_next_rgbd (icp_handle h, const uint16_t *depth, const uint8_t *rgb, int warm_start, uint32_t *k, int *registered) try
+{
+    api_guard guard_ (h);
+    return track_next (h, depth, &rgb, warm_start, k, registered);
 }
 ICP_CATCH_ALL
 

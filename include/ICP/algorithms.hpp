@@ -312,6 +312,28 @@ namespace ICP
         std::vector<float> in, out;
     };
 
+    /*! \brief The RGB-D front end's dense form as a one-call operation (icp_kernel_rgbd, include/icp_amd.h): a depth image and a colour
+     *         image (or none) become the float8 cloud of every pixel and, where asked for, the normals of the vertex map.  The reference
+     *         makes this cloud on the host (src/kinect_frame_grabber.cpp:246-262); it has no such class. */
+    class RGBDTo8D
+    {
+    public:
+        explicit RGBDTo8D (icp::Env _env) : env (_env) { defaults_ (); }
+        icp_rgbd_t cfg;                       /*!< the header's defaults until changed */
+        /*! cloud: width x height x 8 floats; normals: width x height x 4 floats, or nullptr */
+        void run (const uint16_t *depth, const uint8_t *rgb, float *cloud, float *normals = nullptr)
+        {
+            if (icp_kernel_rgbd (env.device, &cfg, depth, rgb, cloud, normals) != ICP_OK) throw std::runtime_error (std::string ("RGBDTo8D: ") + icp_kernel_last_error ());
+        }
+    private:
+        void defaults_ ()
+        {
+            cfg.width = 640; cfg.height = 480; cfg.fx = cfg.fy = 595.f; cfg.cx = 319.5f; cfg.cy = 239.5f; cfg.depth_scale = 1.f;
+            cfg.d_min = 1; cfg.d_max = 65535; cfg.x0 = 65; cfg.y0 = 49; cfg.step_x = 4; cfg.step_y = 3; cfg.radius = 0; cfg.range = 30;
+        }
+        icp::Env env;
+    };
+
     /*! \brief Representatives — mirrors `ICPReps` (reference :397-468, kernel `getReps` kernels/icp_kernels.cl:97-114, grid rule
      *         src/ICP/algorithms.cpp:842-854): `init (nr)` for the reference's 128 x 128 landmarks, `init (nr, m)` for any square set. */
     class ICPReps : public KernelClass
@@ -712,6 +734,14 @@ namespace ICP
             return pairs;
         }
 
+        /*! \brief The RGB-D front end (icp_set_rgbd / icp_write_rgbd, include/icp_amd.h): `writeRGBD` turns a 16-bit depth image and an
+         *         8-bit colour image (or none) into the landmarks of `which` (ICP_MEM_F / ICP_MEM_M) on the device — filtered,
+         *         back-projected and picked on the lattice of the configuration —, with `normals` also into NORMALS_F / NORMALS_M. */
+        void setRGBD (const icp_rgbd_t &cfg) { check (icp_set_rgbd (h, &cfg)); }
+        icp_rgbd_t getRGBD () { icp_rgbd_t cfg; check (icp_get_rgbd (h, &cfg)); return cfg; }
+        void writeRGBD (int which, const uint16_t *depth, const uint8_t *rgb = nullptr, bool normals = false, bool block = false)
+        { check (icp_write_rgbd (h, which, depth, rgb, normals ? 1 : 0, block ? 1 : 0)); }
+
         float *hPtrInF;  /*!< Staging buffer of the fixed set (reference: mapped H_IN_F). */
         float *hPtrInM;  /*!< Staging buffer of the moving set. */
         float *hPtrIOT;  /*!< Staging buffer of [q | t, s]. */
@@ -864,6 +894,17 @@ namespace ICP
             return registered;
         }
         bool next (const void *cloud) { submit (cloud); return collect (); }
+        /*! \brief A frame as the sensor delivers it (icp_track_submit_rgbd / icp_track_next_rgbd): the handle's RGB-D configuration
+         *         (setRGBD) makes its landmarks on the device; `collect` collects both kinds of frame, which may alternate. */
+        void submitRGBD (const uint16_t *depth, const uint8_t *rgb = nullptr) { this->check (icp_track_submit_rgbd (this->h, depth, rgb, warm_start ? 1 : 0)); }
+        bool nextRGBD (const uint16_t *depth, const uint8_t *rgb = nullptr)
+        {
+            uint32_t kk = 0; int reg = 0;
+            this->check (icp_track_next_rgbd (this->h, depth, rgb, warm_start ? 1 : 0, &kk, &reg));
+            registered = reg != 0;
+            if (registered) { this->pull (); this->k = kk; }
+            return registered;
+        }
         void reset () { this->check (icp_track_reset (this->h)); }
         bool warm_start;   /*!< start every registration from the previous hop's transform instead of the identity */
         bool registered;   /*!< the last collected frame had a predecessor */

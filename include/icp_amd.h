@@ -942,6 +942,76 @@ int icp_track_reset (icp_handle h);
  * a runtime that serves the two streams from one hardware queue: probed once per handle).  Same results either way. */
 int icp_track_form (icp_handle h, int *gated);
 
+/* ---- RGB-D front end: depth and colour images to landmarks on the device --------------------------------------------------------
+ * A sensor delivers a 16-bit depth image and an 8-bit colour image, not a float8 cloud; the reference makes the cloud in its grabber
+ * (src/kinect_frame_grabber.cpp:246-262) and can first pass the images through an edge-preserving filter (:179-243).  Here the
+ * device filters the depth (optionally), back-projects it with the caller's intrinsics, picks the landmarks on a configurable lattice
+ * and can compute normals from the full-resolution filtered vertex map.  With no RGB-D call made, none of this code runs.
+ *
+ * A fresh handle, and cfg == NULL, hold: width, height = 640, 480; fx, fy = 595, 595; cx, cy = 319.5, 239.5; depth_scale = 1;
+ * d_min, d_max = 1, 65535; x0, y0 = 65, 49; step_x, step_y = 4, 3; radius = 0, range = 30 — the reference's unfiltered writer followed
+ * by getLMs (icp_write_cloud).
+ *
+ * Depth at pixel p = (u, v) with count c0.  If c0 is invalid, z = 0: holes are not filled.  Otherwise the neighbours q = p + (dx, dy)
+ * count when |dx|, |dy| <= r, q lies inside the image and its count c_q is valid:
+ *   w_s = max (0, (r + 1)^2 - dx^2 - dy^2),   w_r = max (0, S^2 - (c_q - c0)^2),
+ *   N = sum w_s w_r c_q  and  D = sum w_s w_r,  both as exact integers,
+ *   z = (float) ((double) N / (double) D) * depth_scale:  one correctly rounded double division, one rounding to float, one float
+ *   multiplication.
+ * Both kernels are Epanechnikov kernels in place of KinectFusion's two Gaussians; a pixel across a depth step of S or more counts has
+ * weight 0; the result contains no transcendental function and does not depend on summation order.  D > 0 always (the centre weighs
+ * (r + 1)^2 S^2); N < 2^53 at r <= 6 and S <= 4095 (sum w_s = 3765 at r = 6, and 3765 * 4095^2 * 65535 = 4.14e15), so the conversion
+ * to double is exact; any exact integer evaluation is allowed.  With r = 0, z = (float) c0 * depth_scale.
+ *
+ * Point:  X = ((float) u - cx) * z / fx,  Y = ((float) v - cy) * z / fy,  Z = z,  lane 3 = 1;  the colour lanes are (float) channel /
+ * 255.f, or 0 if no colour image is given;  lane 7 = 1.  Each operation is rounded on its own.  An invalid pixel gets the same formulas
+ * from z = 0: xyz = +-0 is the engine's invalid point with its colour kept, exactly as the reference's writer produces it.
+ *
+ * Normals (optional): ICP_NORMALS_GRID's rule (icp_set_normals) applied to the whole width x height vertex map as a `width`-wide grid —
+ * one-pixel neighbours, central differences where both neighbours are valid, one-sided ones otherwise, oriented toward the camera, zero
+ * where the rule has no answer.
+ *
+ * Landmarks: side = sqrt (m); landmark j * side + i is pixel (x0 + step_x i, y0 + step_y j), its normal that pixel's normal.  The
+ * lattice must lie inside the image. */
+typedef struct {
+    uint32_t width, height;                 /* image size, 1 .. 4096 each; both images row-major, colour interleaved R G B */
+    float    fx, fy, cx, cy;                /* pinhole model: fx, fy finite and > 0, cx, cy finite */
+    float    depth_scale;                   /* engine units per depth count, finite and > 0 (1: the reference's millimetres) */
+    uint32_t d_min, d_max;                  /* a count c is valid iff c != 0 and d_min <= c <= d_max <= 65535 */
+    uint32_t x0, y0, step_x, step_y;        /* landmark (i, j) = pixel (x0 + step_x i, y0 + step_y j); steps >= 1 */
+    uint32_t radius;                        /* filter radius r, 0 .. 6; 0: no filter */
+    uint32_t range;                         /* range cut-off S in counts, 1 .. 4095 (unused when r = 0) */
+} icp_rgbd_t;
+/* The handle's configuration (it survives icp_init as the other settings do).  ICP_EINVAL for every value outside the ranges above, and,
+ * on an initialised handle, for a lattice that does not fit sqrt (m) landmarks into the image; ICP_ESTATE while tracked frames are in
+ * flight.  A refused call leaves the configuration as it was. */
+int icp_set_rgbd (icp_handle h, const icp_rgbd_t *cfg);
+int icp_get_rgbd (icp_handle h, icp_rgbd_t *cfg);
+/* The landmarks of an image pair into F or M (which = ICP_MEM_F or ICP_MEM_M), as icp_write of the same values would: the lattice form
+ * of the front end reads only the rows of the lattice's bounding box grown by r (+ 1 with normals).  The input-change bookkeeping, the
+ * lazy outputs and the restriction to registration 0 are icp_write_cloud's.  normals != 0: also ICP_MEM_NORMALS_F / ICP_MEM_NORMALS_M, as
+ * icp_write of that object would (for a registration with ICP_NORMALS_GIVEN; with ICP_NORMALS_GRID buildRBC replaces them).  rgb may be
+ * NULL.  ICP_EINVAL if m is not a square number or the lattice does not fit sqrt (m) landmarks into the image.  Blocking (the images may
+ * be pageable host memory). */
+int icp_write_rgbd (icp_handle h, int which, const uint16_t *depth, const uint8_t *rgb, int normals, int block);
+/* Tracking from images: icp_track_submit / icp_track_next with an image pair in place of the float8 frame; icp_track_collect collects both
+ * kinds, which may alternate within one sequence.  The calling thread copies the depth rows of the lattice's bounding box (grown by r) and
+ * the colour rows of the lattice into pinned staging — at the defaults 0.58 MB of the images' 1.54 MB, beside the 2.08 MB of a float8
+ * frame's band —, one upload on the copy stream follows, and the lattice form runs there in getLMs' place.  m must be 16384: any image
+ * size and lattice that give 128 x 128 landmarks are accepted (ICP_EINVAL otherwise).  Tracked frames get no front-end normals:
+ * point-to-plane tracking keeps ICP_NORMALS_GRID.  icp_track_register_source stays what it is: zero-copy submission of RGB-D frames is
+ * out of scope.  rgb may be NULL. */
+int icp_track_submit_rgbd (icp_handle h, const uint16_t *depth, const uint8_t *rgb, int warm_start);
+int icp_track_next_rgbd (icp_handle h, const uint16_t *depth, const uint8_t *rgb, int warm_start, uint32_t *k, int *registered);
+/* The dense form as a one-call operation beside the other icp_kernel_* entries (host in, host out, blocking, no icp_init; errors through
+ * icp_kernel_last_error): every pixel of the image, the lattice fields of cfg ignored.  cfg == NULL: the defaults.  cloud_out: width x
+ * height x 8 floats; normals_out: width x height x 4 floats, or NULL; rgb may be NULL. */
+int icp_kernel_rgbd (int device, const icp_rgbd_t *cfg, const uint16_t *depth, const uint8_t *rgb, void *cloud_out, float *normals_out);
+/* Diagnostic (tools/diag/rgbd_time.py): one form of the front end alone with the handle's configuration — dense != 0: every pixel, else the
+ * sqrt (m) x sqrt (m) landmarks —, whole images uploaded once, `reps` launches between two events on the handle's stream, the results into
+ * scratch (F, M and the normals stay as they are).  Microseconds per launch. */
+int icp_time_rgbd (icp_handle h, int dense, int normals, const uint16_t *depth, const uint8_t *rgb, uint32_t reps, float *us_per_launch);
+
 /* ICPTransform<QUATERNION> / ICPTransform<MATRIX> with an explicit transformation — include/ICP/algorithms.hpp:1189-1211,
  * 1240, 1348; src/ICP/algorithms.cpp:2554-2753 (quaternion), :2760-2960 (matrix); kernels/icp_kernels.cl:772-802
  * (icpTransform_Quaternion), :842-879 (icpTransform_Quaternion_2: the same mapping through two 4x4 products),
