@@ -10,6 +10,7 @@
 //
 // There is NO CPU fallback: without a gfx950 device icp_create fails with ICP_ENODEVICE.
 #include "icp_host.h"
+#include "icp_tsdf.h"
 
 using namespace icp_host;
 
@@ -1505,6 +1506,39 @@ int icp_time_rgbd (icp_handle h, int dense, int normals, const uint16_t *depth, 
     float ms = 0.f;
     HIPCHK (h, hipEventElapsedTime (&ms, h->ev0, h->ev1));
     *us_per_launch = ms * 1e3f / (float) reps;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
+// The view of a TSDF volume (icp_tsdf.hip) as the landmarks of F or M: the volume's ray cast writes the handle's buffers itself, on the
+// volume's stream, between two synchronisations — the handle's stream has drained before and the cast has finished after.
+int icp_tsdf_raycast_to (icp_tsdf_handle t, icp_handle h, int which, const icp_rgbd_t *cam, const float *pose12, float z_near, float z_far, int normals) try
+{
+    if (!t) return ICP_EINVAL;
+    if (!h) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_raycast_to: null handle");
+    api_guard guard_ (h);
+    if (!h->inited) return tsdf_fail (t, ICP_ESTATE, "icp_tsdf_raycast_to: icp_init has not been called on the handle");
+    if (h->device != t->device) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_raycast_to: the handle lives on another device than the volume");
+    if (which != ICP_MEM_F && which != ICP_MEM_M) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_raycast_to: which must be ICP_MEM_F or ICP_MEM_M");
+    if (h->track_submitted != h->track_collected) return tsdf_fail (t, ICP_ESTATE, "icp_tsdf_raycast_to: tracked frames are in flight: collect them first (icp_track_collect)");
+    const uint32_t side = h->p.side;
+    if ((uint64_t) side * side != h->p.m) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_raycast_to: m is not a square number");
+    icp_tsdf_cast_args a;
+    int rc = tsdf_cast_prepare (t, "icp_tsdf_raycast_to", cam ? cam : &h->rgbd, pose12, z_near, z_far, side, &a); if (rc) return rc;
+    if ((rc = need (h, false)) || (rc = set_device (h))) return tsdf_fail (t, rc, "icp_tsdf_raycast_to: " + h->err);
+    a.out = reinterpret_cast<float4 *> (which == ICP_MEM_F ? h->dF : h->dM);
+    a.nrm = normals ? const_cast<float4 *> (static_cast<const float4 *> (mem_of (h, 0u, which == ICP_MEM_F ? ICP_MEM_NORMALS_F : ICP_MEM_NORMALS_M).ptr)) : nullptr;
+    auto chk = [&] (hipError_t e, const char *what) { return e == hipSuccess ? ICP_OK : tsdf_fail (t, ICP_EHIP, std::string (what) + ": " + hipGetErrorString (e)); };
+    note_inputs_change (h);
+    if ((rc = chk (hipStreamSynchronize (h->stream), "hipStreamSynchronize"))) return rc;
+    tsdf_launch_raycast (a, t->stream);
+    if ((rc = chk (hipGetLastError (), "icp_tsdf_raycast_to"))) return rc;
+    if ((rc = chk (hipStreamSynchronize (t->stream), "hipStreamSynchronize"))) return rc;
+    if (which == ICP_MEM_M) {
+        normals_m_follow (h, 0u, 1u);
+        if ((rc = chk (hipGetLastError (), "icp_tsdf_raycast_to"))) return rc;
+        if ((rc = chk (hipStreamSynchronize (h->stream), "hipStreamSynchronize"))) return rc;
+    }
     return ICP_OK;
 }
 ICP_CATCH_ALL

@@ -1,0 +1,45 @@
+// icp_tsdf.h — what icp_tsdf.hip (the volume, its two kernels and its C entries) shares with icp_capi.hip, which owns the one entry
+// that needs the inside of an icp_context (icp_tsdf_raycast_to): the volume's handle, the arguments of a ray cast and its launcher.
+#pragma once
+#include "../../include/icp_amd.h"
+#include "icp_rgbd.h"
+
+#include <string>
+
+// The device's view of a volume.  Voxel (i, j, k) lives at dw[(k ny + j) nx + i] = {D, W} and, with colour, col[(k ny + j) nx + i] =
+// {C_0, C_1, C_2, -}: a wave's 64 consecutive i are one coalesced 8- or 16-byte access, and the march of the ray cast never touches col.
+struct icp_tsdf_dev {
+    uint32_t nx, ny, nz;
+    float voxel, ox, oy, oz, mu, w_max;
+    float2 *dw; float4 *col;                     // col: null without colour
+};
+
+// a camera at a pose: R row-major, camera -> world
+struct icp_tsdf_view { icp_rgbd_t c; float R[9], t[3]; };
+
+struct icp_tsdf_cast_args {
+    icp_tsdf_dev v; icp_tsdf_view cam;
+    float z_near, delta; uint32_t N;             // the march: lambda_n = z_near + n delta, n = 0 .. N
+    uint32_t side;                               // 0: every pixel of the image, else the side x side landmarks of the lattice
+    float4 *out, *nrm;                           // [pixels or landmarks][2] float4, [pixels or landmarks] float4 (may be null)
+};
+
+struct icp_tsdf_context {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    icp_tsdf_t cfg {};
+    icp_tsdf_dev v {};
+    // device copies of the images of an integration and the results of a ray cast to the host (grown when a call needs more)
+    void *dDepth = nullptr, *dRgb = nullptr, *dOut = nullptr, *dNrm = nullptr;
+    size_t depth_cap = 0, rgb_cap = 0, out_cap = 0, nrm_cap = 0;
+    std::string err;
+};
+
+namespace icp_host __attribute__ ((visibility ("hidden"))) {
+int tsdf_fail (icp_tsdf_context *t, int code, const std::string &msg);
+// The checks of a ray cast that need no device — camera, pose, z range, lattice (side != 0) — and its arguments but for out / nrm.
+// ICP_OK, or the status with the volume's error text set.
+int tsdf_cast_prepare (icp_tsdf_context *t, const char *who, const icp_rgbd_t *cam, const float *pose12, float z_near, float z_far, uint32_t side, icp_tsdf_cast_args *a);
+void tsdf_launch_raycast (const icp_tsdf_cast_args &a, hipStream_t s);
+}

@@ -1,0 +1,206 @@
+"""Frame-to-model: a TSDF volume fused and ray-cast on the device (include/icp_amd.h: icp_tsdf_t, icp_tsdf_integrate, icp_tsdf_raycast,
+icp_tsdf_raycast_to, icp_tsdf_compose_pose).
+
+    vol = TSDFVolume(TSDFConfig(256, 256, 256, voxel=8.0, origin=(-1024, -1024, 0), mu=24.0))
+    for pose, k, scale in track_to_model(icp, vol, frames, pose0, 300.0, 4000.0):
+        ...
+
+A pose is 12 floats, row-major [R | t], camera -> world.  A camera is an icp_amd.rgbd.RGBDConfig."""
+import ctypes as C
+
+import numpy as np
+
+import icp_amd
+from icp_amd import rgbd
+from icp_amd.rgbd import _images, _ptr
+
+
+class icp_tsdf_t(C.Structure):
+    _fields_ = [("nx", C.c_uint32), ("ny", C.c_uint32), ("nz", C.c_uint32), ("voxel", C.c_float), ("origin", C.c_float * 3),
+                ("mu", C.c_float), ("w_max", C.c_float), ("colour", C.c_uint32)]
+
+
+class TSDFConfig:
+    """icp_tsdf_t: nx x ny x nz voxels of edge `voxel`, voxel (0, 0, 0) centred at `origin`, truncation distance mu, weight cap w_max,
+    and whether the volume keeps colour."""
+    FIELDS = ("nx", "ny", "nz", "voxel", "origin", "mu", "w_max", "colour")
+
+    def __init__(self, nx, ny, nz, voxel, origin, mu, w_max=64.0, colour=False):
+        self.nx, self.ny, self.nz = nx, ny, nz
+        self.voxel, self.origin, self.mu, self.w_max, self.colour = voxel, tuple(origin), mu, w_max, int(colour)
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f in self.FIELDS}
+
+    def __repr__(self):
+        return "TSDFConfig(%s)" % ", ".join("%s=%r" % kv for kv in self.as_dict().items())
+
+    def _c(self):
+        return icp_tsdf_t(self.nx, self.ny, self.nz, self.voxel, (C.c_float * 3)(*self.origin), self.mu, self.w_max, self.colour)
+
+    @classmethod
+    def _from_c(cls, c):
+        return cls(c.nx, c.ny, c.nz, c.voxel, tuple(c.origin), c.mu, c.w_max, c.colour)
+
+
+_declared = None
+
+
+def _lib():
+    """The engine's library with the volume's entry points declared."""
+    global _declared
+    L = icp_amd.lib()
+    if _declared is not L:
+        vp, i32, u32, f32, cfg, cam = C.c_void_p, C.c_int, C.c_uint32, C.c_float, C.POINTER(icp_tsdf_t), C.POINTER(rgbd.icp_rgbd_t)
+        for name, args in (("icp_tsdf_create", (C.POINTER(vp), i32, cfg)), ("icp_tsdf_destroy", (vp,)), ("icp_tsdf_reset", (vp,)),
+                           ("icp_tsdf_get_config", (vp, cfg)),
+                           ("icp_tsdf_integrate", (vp, cam, vp, vp, vp)),
+                           ("icp_tsdf_raycast", (vp, cam, vp, f32, f32, u32, vp, vp)),
+                           ("icp_tsdf_raycast_to", (vp, vp, i32, cam, vp, f32, f32, i32)),
+                           ("icp_tsdf_read", (vp, vp, vp)), ("icp_tsdf_write", (vp, vp, vp)),
+                           ("icp_tsdf_compose_pose", (vp, vp, vp, C.POINTER(f32))),
+                           ("icp_tsdf_time", (vp, i32, cam, vp, vp, vp, f32, f32, u32, u32, C.POINTER(f32)))):
+            f = getattr(L, name)
+            f.restype, f.argtypes = i32, list(args)
+        L.icp_tsdf_last_error.restype, L.icp_tsdf_last_error.argtypes = C.c_char_p, [vp]
+        _declared = L
+    return L
+
+
+def _pose(pose12):
+    p = np.ascontiguousarray(pose12, np.float32).reshape(-1)
+    if p.size != 12:
+        raise ValueError("expected a pose of 12 floats, row-major [R | t]")
+    return p
+
+
+def compose_pose(pose12, T8):
+    """icp_tsdf_compose_pose: (pose12 o (R (q), t) of the engine's T8 as 12 float32, T8's scale) — computed in double, rounded once."""
+    p, T = _pose(pose12), np.ascontiguousarray(T8, np.float32).reshape(-1)
+    if T.size != 8:
+        raise ValueError("expected a transform of 8 floats [q | t, s]")
+    out, s = np.empty(12, np.float32), C.c_float()
+    rc = _lib().icp_tsdf_compose_pose(_ptr(p), _ptr(T), _ptr(out), C.byref(s))
+    if rc:
+        raise icp_amd.ICPError(rc, "icp_tsdf_compose_pose: the quaternion must be finite and non-zero")
+    return out, s.value
+
+
+class TSDFVolume:
+    """A volume on device `device` (icp_tsdf_create).  Every call is blocking."""
+
+    def __init__(self, cfg, device=0):
+        self._L = _lib()
+        self._t = C.c_void_p()
+        c = cfg._c()
+        rc = self._L.icp_tsdf_create(C.byref(self._t), device, C.byref(c))
+        if rc:
+            self._t = None
+            raise icp_amd.ICPError(rc, self._L.icp_tsdf_last_error(None).decode())
+        self.cfg = cfg
+        self.device = device
+
+    def close(self):
+        if self._t:
+            self._L.icp_tsdf_destroy(self._t)
+            self._t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _chk(self, rc):
+        if rc:
+            raise icp_amd.ICPError(rc, self._L.icp_tsdf_last_error(self._t).decode())
+
+    @property
+    def shape(self):
+        return (self.cfg.nz, self.cfg.ny, self.cfg.nx)
+
+    def get_config(self):
+        c = icp_tsdf_t()
+        self._chk(self._L.icp_tsdf_get_config(self._t, C.byref(c)))
+        return TSDFConfig._from_c(c)
+
+    def reset(self):
+        self._chk(self._L.icp_tsdf_reset(self._t))
+
+    def integrate(self, cam, pose12, depth, rgb=None):
+        """icp_tsdf_integrate: one frame (a uint16 depth image, a uint8 colour image or None) seen from pose12 into the volume."""
+        depth, rgb = _images(depth, rgb, cam.width, cam.height)
+        c = cam._c()
+        self._chk(self._L.icp_tsdf_integrate(self._t, C.byref(c), _ptr(_pose(pose12)), _ptr(depth), _ptr(rgb)))
+
+    def raycast(self, cam, pose12, z_near, z_far, side=0, normals=True):
+        """icp_tsdf_raycast: the view from pose12 as (cloud (n, 8), normals (n, 4) or None) — every pixel (side = 0, n = width * height) or
+        the side x side landmarks of the camera's lattice."""
+        n = side * side if side else cam.width * cam.height
+        cloud = np.empty((n, 8), np.float32)
+        nrm = np.empty((n, 4), np.float32) if normals else None
+        c = cam._c()
+        self._chk(self._L.icp_tsdf_raycast(self._t, C.byref(c), _ptr(_pose(pose12)), z_near, z_far, side, _ptr(cloud), _ptr(nrm)))
+        return cloud, nrm
+
+    def raycast_to(self, icp, which, pose12, z_near, z_far, cam=None, normals=False):
+        """icp_tsdf_raycast_to: the sqrt (m) x sqrt (m) landmarks of the view into F or M of `icp` (which = Memory.F / Memory.M), device to
+        device; with normals also into NORMALS_F / NORMALS_M.  cam = None: the handle's RGB-D configuration."""
+        rgbd._handle(icp, "a ray cast into a level")
+        c = cam._c() if cam is not None else None
+        self._chk(self._L.icp_tsdf_raycast_to(self._t, icp._h, which, C.byref(c) if c is not None else None, _ptr(_pose(pose12)),
+                                              z_near, z_far, int(bool(normals))))
+
+    def read(self):
+        """icp_tsdf_read: (dw (nz, ny, nx, 2), rgb (nz, ny, nx, 3) or None without colour)."""
+        dw = np.empty(self.shape + (2,), np.float32)
+        col = np.empty(self.shape + (3,), np.float32) if self.cfg.colour else None
+        self._chk(self._L.icp_tsdf_read(self._t, _ptr(dw), _ptr(col)))
+        return dw, col
+
+    def write(self, dw, rgb=None):
+        """icp_tsdf_write: the whole volume from the layout read () returns."""
+        dw = np.ascontiguousarray(dw, np.float32)
+        if dw.size != 2 * np.prod(self.shape):
+            raise ValueError("expected nz x ny x nx x 2 floats")
+        if rgb is not None:
+            rgb = np.ascontiguousarray(rgb, np.float32)
+            if rgb.size != 3 * np.prod(self.shape):
+                raise ValueError("expected nz x ny x nx x 3 floats")
+        self._chk(self._L.icp_tsdf_write(self._t, _ptr(dw), _ptr(rgb)))
+
+    def time_kernel(self, what, cam, pose12, depth=None, rgb=None, z_near=0.0, z_far=0.0, side=0, reps=20):
+        """icp_tsdf_time (diagnostic): microseconds per launch of k_tsdf_integrate (what = 0; the volume changes) or k_tsdf_raycast (1)."""
+        if depth is not None:
+            depth, rgb = _images(depth, rgb, cam.width, cam.height)
+        c, us = cam._c(), C.c_float()
+        self._chk(self._L.icp_tsdf_time(self._t, what, C.byref(c), _ptr(_pose(pose12)), _ptr(depth), _ptr(rgb), z_near, z_far, side, reps, C.byref(us)))
+        return us.value
+
+
+def track_to_model(icp, volume, frames, pose0, z_near, z_far, normals=False):
+    """Frame-to-model tracking as a generator over `frames`, an iterable of (depth, rgb or None) image pairs of the handle's RGB-D
+    configuration.  The first frame is integrated at pose0.  Every later frame: the volume's view from the current pose goes into F
+    (raycast_to; with `normals` also into NORMALS_F) and buildRBC follows; the front end writes the frame into M; reset_transform and run;
+    pose = compose_pose (pose, T); the frame is integrated at the new pose.  Yields (pose, k, scale) per frame, (pose0, None, 1.0) first."""
+    cam = rgbd.get_config(icp)
+    pose = _pose(pose0).copy()
+    first = True
+    for depth, colour in frames:
+        if first:
+            first, k, scale = False, None, 1.0
+        else:
+            volume.raycast_to(icp, icp_amd.Memory.F, pose, z_near, z_far, normals=normals)
+            icp.buildRBC()
+            rgbd.write(icp, icp_amd.Memory.M, depth, colour)
+            icp.reset_transform()
+            k = icp.run()
+            pose, scale = compose_pose(pose, icp.read(icp_amd.Memory.T))
+        volume.integrate(cam, pose, depth, colour)
+        yield pose.copy(), k, scale

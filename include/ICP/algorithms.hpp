@@ -334,6 +334,47 @@ namespace ICP
         icp::Env env;
     };
 
+    /*! \brief Frame-to-model (icp_tsdf_*, include/icp_amd.h): a truncated signed distance volume on the device that registered frames
+     *         are fused into (`integrate`) and whose view from a pose (`raycast`, `raycastTo`) is the fixed frame of the next
+     *         registration — an organised grid with normals.  A pose is 12 floats, row-major [R | t], camera -> world.  The reference has
+     *         no model and no such class. */
+    class TSDFVolume
+    {
+    public:
+        TSDFVolume (icp::Env _env, const icp_tsdf_t &_cfg) : env (_env), t (nullptr)
+        {
+            if (icp_tsdf_create (&t, env.device, &_cfg) != ICP_OK) throw std::runtime_error (std::string ("TSDFVolume: ") + icp_tsdf_last_error (nullptr));
+        }
+        ~TSDFVolume () { if (t) icp_tsdf_destroy (t); }
+        TSDFVolume (const TSDFVolume &) = delete;
+        TSDFVolume &operator= (const TSDFVolume &) = delete;
+        icp_tsdf_handle handle () const { return t; }
+        icp_tsdf_t config () { icp_tsdf_t c; check (icp_tsdf_get_config (t, &c)); return c; }
+        size_t voxels () { const icp_tsdf_t c = config (); return (size_t) c.nx * c.ny * c.nz; }
+        void reset () { check (icp_tsdf_reset (t)); }
+        void integrate (const icp_rgbd_t &cam, const float *pose12, const uint16_t *depth, const uint8_t *rgb = nullptr) { check (icp_tsdf_integrate (t, &cam, pose12, depth, rgb)); }
+        /*! side == 0: every pixel (cloud: width x height x 8 floats, normals: x 4 or nullptr); else the side x side landmarks of cam's lattice */
+        void raycast (const icp_rgbd_t &cam, const float *pose12, float z_near, float z_far, float *cloud, float *normals = nullptr, uint32_t side = 0)
+        { check (icp_tsdf_raycast (t, &cam, pose12, z_near, z_far, side, cloud, normals)); }
+        /*! the landmarks of the view into F or M of an initialised handle (which = ICP_MEM_F / ICP_MEM_M), device to device; cam == nullptr: the handle's configuration */
+        void raycastTo (icp_handle h, int which, const float *pose12, float z_near, float z_far, bool normals = false, const icp_rgbd_t *cam = nullptr)
+        { check (icp_tsdf_raycast_to (t, h, which, cam, pose12, z_near, z_far, normals ? 1 : 0)); }
+        /*! dw: voxels x 2 floats; rgb: voxels x 3 floats, nullptr for a volume without colour */
+        void read (float *dw, float *rgb = nullptr) { check (icp_tsdf_read (t, dw, rgb)); }
+        void write (const float *dw, const float *rgb = nullptr) { check (icp_tsdf_write (t, dw, rgb)); }
+        /*! out12 = pose12 o (R (q), t) of the engine's T8; returns T8's scale */
+        static float composePose (const float *pose12, const float *T8, float *out12)
+        {
+            float s = 1.f;
+            if (icp_tsdf_compose_pose (pose12, T8, out12, &s) != ICP_OK) throw std::runtime_error ("TSDFVolume::composePose: bad arguments");
+            return s;
+        }
+    private:
+        void check (int rc) { if (rc != ICP_OK) throw std::runtime_error (std::string ("TSDFVolume: ") + icp_tsdf_last_error (t)); }
+        icp::Env env;
+        icp_tsdf_handle t;
+    };
+
     /*! \brief Representatives — mirrors `ICPReps` (reference :397-468, kernel `getReps` kernels/icp_kernels.cl:97-114, grid rule
      *         src/ICP/algorithms.cpp:842-854): `init (nr)` for the reference's 128 x 128 landmarks, `init (nr, m)` for any square set. */
     class ICPReps : public KernelClass

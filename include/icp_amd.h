@@ -1012,6 +1012,87 @@ int icp_kernel_rgbd (int device, const icp_rgbd_t *cfg, const uint16_t *depth, c
  * scratch (F, M and the normals stay as they are).  Microseconds per launch. */
 int icp_time_rgbd (icp_handle h, int dense, int normals, const uint16_t *depth, const uint8_t *rgb, uint32_t reps, float *us_per_launch);
 
+/* ---- Frame-to-model: a TSDF volume fused and ray-cast on the device -----------------------------------------------------------------
+ * Registered frames are fused into a truncated signed distance volume (KinectFusion, Newcombe et al. 2011; Curless & Levoy 1996); the
+ * next frame is registered against a view of that volume ray-cast from the last pose: an organised grid sampled from a pinhole image, with
+ * normals, as projective association and the plane metrics want their fixed set.  A volume is a handle of its own with a stream of its
+ * own; it touches nothing an iteration reads or writes, and with no icp_tsdf_* call made, none of this code runs.  The reference has no
+ * model.  Arithmetic: fp32, each operation rounded on its own, IEEE divide and sqrt, dots as (a0 b0 + a1 b1) + a2 b2;
+ * tests/tsdf_ref.py restates every value bit for bit.
+ *
+ * Volume.  Voxel (i, j, k), i < nx, j < ny, k < nz, has the centre origin + voxel * (i, j, k) and the state (D, W) and, with `colour`,
+ * C[3]; all 0 after create and reset.  icp_tsdf_read / icp_tsdf_write exchange the logical layout, x fastest:
+ * dw[((k ny + j) nx + i) 2 + {0, 1}] = D, W and rgb[((k ny + j) nx + i) 3 + ch].
+ *
+ * Pose.  pose12: 12 floats, row-major [R | t], camera -> world: x_w = R x_c + t, R_ab = pose12[4 a + b], t_a = pose12[4 a + 3]; checked
+ * for finiteness only.  Camera.  An icp_rgbd_t gives the image size, the intrinsics, depth_scale, d_min / d_max and the lattice; radius
+ * and range are ignored: the raw counts are fused, as KinectFusion does.
+ *
+ * Integrate, per voxel:
+ *    p_a = origin_a + (float) idx_a * voxel;   d = p - t;   q_a = (R_0a d_0 + R_1a d_1) + R_2a d_2;       unchanged unless q_z > 0
+ *    u = (fx * (q_x / q_z) + cx) + 0.5f, v likewise;   unchanged unless 0 <= u < width and 0 <= v < height (float comparisons, made before
+ *    any conversion: NaN fails); the pixel is (floor u, floor v);   unchanged unless its count c is valid by the front end's rule
+ *    z = (float) c * depth_scale;   s = z - q_z;   unchanged unless s >= -mu;   e = min (1.f, s / mu)
+ *    D' = (D * W + e) / (W + 1.f);   with `colour` and a colour image C'_ch = (C_ch * W + (float) ch / 255.f) / (W + 1.f), else C stays;
+ *    W' = min (W + 1.f, w_max)
+ *
+ * Ray cast, per output pixel (u, v):  a_x = ((float) u - cx) / fx, a_y likewise;  delta = 0.5f * mu;  N = floorf ((z_far - z_near) / delta);
+ * lambda_n = z_near + (float) n * delta for n = 0 .. N (no running sum); the sample point is x_c = (a_x lambda, a_y lambda, lambda),
+ * w_a = ((R_a0 x + R_a1 y) + R_a2 z) + t_a.
+ *    The sample S (w):  g_a = (w_a - origin_a) / voxel, i_a = floorf (g_a);  it is KNOWN iff 0 <= i_a <= n_a - 2 on every axis (float
+ *    comparisons) and all eight corners of the cell have W > 0;  f_a = g_a - i_a;  lerp (a, b, t) = a + t * (b - a) along x, then y, then z.
+ *    n* = the first n whose sample is known and <= 0.  The pixel is a HIT iff n* exists, n* >= 1, sample n* - 1 is known and S_{n*-1} > 0;
+ *    then lambda* = lambda_{n*-1} + delta * (S_{n*-1} / (S_{n*-1} - S_{n*})), and the vertex is the front end's back-projection of the depth
+ *    lambda*:  X = ((float) u - cx) * lambda* / fx, Y likewise, Z = lambda*.  Its world point h comes from the formula above, and the hit
+ *    stands only if S (h) is known (the hit's own cell).  The colour is the same trilinear form of C in that cell (0 without `colour`).
+ *    Normal:  G_a = S (h + voxel e_a) - S (h - voxel e_a); all six samples known and len = sqrt ((G_0^2 + G_1^2) + G_2^2) > 0, otherwise the
+ *    normal is 0;  n_w = G / len;  n_c,a = (R_0a n_0 + R_1a n_1) + R_2a n_2, negated if (n_c . vertex) > 0: toward the camera, as
+ *    ICP_NORMALS_GRID orients its normals.
+ *    A hit gives the point [X Y Z 1 r g b 1] and the normal [n_c 0]; every other pixel the engine's invalid point [0 0 0 1 0 0 0 1] and a
+ *    zero normal.
+ * Any shortcut that leaves every bit as the rule gives it is allowed. */
+typedef struct icp_tsdf_context *icp_tsdf_handle;
+typedef struct {
+    uint32_t nx, ny, nz;                    /* voxels per axis, 2 .. 1024 each */
+    float    voxel;                         /* edge of a voxel in engine units, finite and > 0 */
+    float    origin[3];                     /* centre of voxel (0, 0, 0), finite */
+    float    mu;                            /* truncation distance, finite and > 0 */
+    float    w_max;                         /* weight cap, integer-valued, 1 .. 65536 */
+    uint32_t colour;                        /* 0 or 1: the volume keeps C */
+} icp_tsdf_t;
+/* Life cycle.  ICP_EINVAL for every field outside its range, ICP_ENOMEM if the device cannot hold the volume (8 bytes a voxel, 24 with
+ * colour).  icp_tsdf_last_error (NULL): why the last icp_tsdf_create of this thread failed.  A refused call of any entry below leaves the
+ * volume (and the handle of icp_tsdf_raycast_to) as it was.  All calls are blocking. */
+int icp_tsdf_create (icp_tsdf_handle *out, int device, const icp_tsdf_t *cfg);
+int icp_tsdf_destroy (icp_tsdf_handle t);
+int icp_tsdf_reset (icp_tsdf_handle t);
+int icp_tsdf_get_config (icp_tsdf_handle t, icp_tsdf_t *cfg);
+const char *icp_tsdf_last_error (icp_tsdf_handle t);
+/* One frame into the volume: depth is cam->width x cam->height counts, rgb the interleaved colour image or NULL (host pointers). */
+int icp_tsdf_integrate (icp_tsdf_handle t, const icp_rgbd_t *cam, const float *pose12, const uint16_t *depth, const uint8_t *rgb);
+/* The view from pose12, host pointers out.  side == 0: every pixel, cloud_out width x height x 8 floats, normals_out width x height x 4
+ * floats or NULL; otherwise the side x side landmarks of cam's lattice, landmark j side + i = pixel (x0 + step_x i, y0 + step_y j)
+ * (ICP_EINVAL if the lattice leaves the image).  ICP_EINVAL unless 0 < z_near < z_far are finite and N <= 4095. */
+int icp_tsdf_raycast (icp_tsdf_handle t, const icp_rgbd_t *cam, const float *pose12, float z_near, float z_far, uint32_t side, void *cloud_out, float *normals_out);
+/* The sqrt (m) x sqrt (m) landmarks of the view, device to device, into F or M of handle h (which = ICP_MEM_F or ICP_MEM_M) and, with
+ * normals != 0, into ICP_MEM_NORMALS_F / ICP_MEM_NORMALS_M: as icp_write of the same values would leave them, with icp_write_rgbd's
+ * bookkeeping.  cam == NULL: the handle's configuration (icp_set_rgbd).  Registration 0 only.  ICP_EINVAL for a handle on another device,
+ * a non-square m or a lattice that does not fit; ICP_ESTATE while tracked frames are in flight.  An error is left in the volume's
+ * icp_tsdf_last_error. */
+int icp_tsdf_raycast_to (icp_tsdf_handle t, icp_handle h, int which, const icp_rgbd_t *cam, const float *pose12, float z_near, float z_far, int normals);
+/* The whole volume in the logical layout, host pointers: dw nx ny nz x 2 floats; rgb nx ny nz x 3 floats, NULL for (and only for) a volume
+ * without colour. */
+int icp_tsdf_read (icp_tsdf_handle t, float *dw, float *rgb);
+int icp_tsdf_write (icp_tsdf_handle t, const float *dw, const float *rgb);
+/* Host only, computed in double and rounded once: out12 = pose12 o (R (q / |q|), t) of the engine's T8 = [q | t, s], the pose of the moving
+ * frame of a registration whose fixed frame was ray-cast from pose12.  T's scale s is returned through `scale` (may be NULL), not applied. */
+int icp_tsdf_compose_pose (const float *pose12, const float *T8, float *out12, float *scale);
+/* Diagnostic (tools/diag/tsdf_time.py): `reps` launches of one kernel between two events on the volume's stream, after one untimed launch.
+ * what = 0: k_tsdf_integrate of (depth, rgb) at pose12 — the volume is left as reps + 1 integrations leave it;  what = 1: k_tsdf_raycast as
+ * icp_tsdf_raycast (cam, pose12, z_near, z_far, side) runs it, into scratch (depth, rgb unused).  Microseconds per launch. */
+int icp_tsdf_time (icp_tsdf_handle t, int what, const icp_rgbd_t *cam, const float *pose12, const uint16_t *depth, const uint8_t *rgb, float z_near, float z_far,
+                   uint32_t side, uint32_t reps, float *us_per_launch);
+
 /* ICPTransform<QUATERNION> / ICPTransform<MATRIX> with an explicit transformation — include/ICP/algorithms.hpp:1189-1211,
  * 1240, 1348; src/ICP/algorithms.cpp:2554-2753 (quaternion), :2760-2960 (matrix); kernels/icp_kernels.cl:772-802
  * (icpTransform_Quaternion), :842-879 (icpTransform_Quaternion_2: the same mapping through two 4x4 products),
