@@ -1,5 +1,6 @@
 // icp_tsdf.h — what icp_tsdf.hip (the volume, its two kernels and its C entries) shares with icp_capi.hip, which owns the one entry
-// that needs the inside of an icp_context (icp_tsdf_raycast_to): the volume's handle, the arguments of a ray cast and its launcher.
+// that needs the inside of an icp_context (icp_tsdf_raycast_to), and with icp_tsdf_surface.hip (icp_tsdf_extract_surface): the volume's
+// handle, the arguments of a ray cast and its launcher, the scratch of a call.
 #pragma once
 #include "../../include/icp_amd.h"
 #include "icp_rgbd.h"
@@ -33,6 +34,10 @@ struct icp_tsdf_context {
     // device copies of the images of an integration and the results of a ray cast to the host (grown when a call needs more)
     void *dDepth = nullptr, *dRgb = nullptr, *dOut = nullptr, *dNrm = nullptr;
     size_t depth_cap = 0, rgb_cap = 0, out_cap = 0, nrm_cap = 0;
+    // the words of a surface extraction (icp_tsdf_surface.hip: block counts, their offsets, tile sums, tile offsets, the count)
+    // and the edges of its members in order
+    void *dSurf = nullptr, *dEdge = nullptr;
+    size_t surf_cap = 0, edge_cap = 0;
     std::string err;
 };
 
@@ -42,4 +47,16 @@ int tsdf_fail (icp_tsdf_context *t, int code, const std::string &msg);
 // ICP_OK, or the status with the volume's error text set.
 int tsdf_cast_prepare (icp_tsdf_context *t, const char *who, const icp_rgbd_t *cam, const float *pose12, float z_near, float z_far, uint32_t side, icp_tsdf_cast_args *a);
 void tsdf_launch_raycast (const icp_tsdf_cast_args &a, hipStream_t s);
+// *q holds at least `bytes` on the device (grown on demand; ICP_ENOMEM with the volume's error text set)
+int tsdf_reserve (icp_tsdf_context *t, void **q, size_t *cap, size_t bytes);
+// icp_tsdf_time, what = 2 .. 4: `reps` extractions' launches (normals on, min_weight 1) between the volume's two events, after an untimed
+// extraction — part 0: all of them, 1: the two scan launches alone, 2: the scatter and the points alone
+int tsdf_time_surface (icp_tsdf_context *t, int part, uint32_t reps, float *us_per_group);
 }
+
+#define TSDFCHK(t, expr)                                                                                       \
+    do {                                                                                                       \
+        hipError_t e_ = (expr);                                                                                \
+        if (e_ != hipSuccess)                                                                                  \
+            return icp_host::tsdf_fail ((t), ICP_EHIP, std::string (#expr) + ": " + hipGetErrorString (e_));   \
+    } while (0)

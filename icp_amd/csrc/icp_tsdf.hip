@@ -1,5 +1,5 @@
 // icp_tsdf.hip — frame-to-model: a truncated signed distance volume fused and ray-cast on the device (the rule: include/icp_amd.h,
-// "Frame-to-model"; tests/tsdf_ref.py restates it).  The reference has no model: each of its frames is registered against the previous one.
+// "Frame-to-model"; tests/tsdf_ref.py restates it).  The volume's surface as a point cloud: icp_tsdf_surface.hip.  The reference has no model: each of its frames is registered against the previous one.
 //
 //   k_tsdf_integrate  one lane per voxel, lanes along i: a block of 256 owns 64 i x 4 j of one k, so every access to the volume is a
 //                     wave-wide coalesced 8-byte {D, W} (16-byte colour) vector access.  A voxel the frame does not change is not stored.
@@ -249,6 +249,16 @@ int tsdf_cast_prepare (icp_tsdf_context *t, const char *who, const icp_rgbd_t *c
     return ICP_OK;
 }
 
+int tsdf_reserve (icp_tsdf_context *t, void **q, size_t *cap, size_t bytes)
+{
+    if (*cap >= bytes) return ICP_OK;
+    if (*q) (void) hipFree (*q);                    // (every public call is blocking: nothing in flight reads it)
+    *q = nullptr; *cap = 0;
+    if (hipMalloc (q, bytes) != hipSuccess) { (void) hipGetLastError (); *q = nullptr; return tsdf_fail (t, ICP_ENOMEM, "hipMalloc: out of device memory"); }
+    *cap = bytes;
+    return ICP_OK;
+}
+
 void tsdf_launch_raycast (const icp_tsdf_cast_args &a, hipStream_t s)
 {
     const uint32_t gw = a.side ? a.side : a.cam.c.width, gh = a.side ? a.side : a.cam.c.height, bw = TILE * TILES_X;
@@ -259,29 +269,11 @@ void tsdf_launch_raycast (const icp_tsdf_cast_args &a, hipStream_t s)
 
 using namespace icp_host;
 
-#define TSDFCHK(t, expr)                                                                            \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess)                                                                       \
-            return tsdf_fail ((t), ICP_EHIP, std::string (#expr) + ": " + hipGetErrorString (e_));  \
-    } while (0)
-
 namespace {
 
 void launch_integrate (const tsdf_integrate_args &a, hipStream_t s)
 {
     hipLaunchKernelGGL (k_tsdf_integrate, dim3 ((a.v.nx + INT_I - 1u) / INT_I, (a.v.ny + INT_J - 1u) / INT_J, a.v.nz), dim3 (256), 0, s, a);
-}
-
-// *q holds at least `bytes` on the device
-int reserve (icp_tsdf_context *t, void **q, size_t *cap, size_t bytes)
-{
-    if (*cap >= bytes) return ICP_OK;
-    if (*q) (void) hipFree (*q);                    // (every public call is blocking: nothing in flight reads it)
-    *q = nullptr; *cap = 0;
-    if (hipMalloc (q, bytes) != hipSuccess) { (void) hipGetLastError (); *q = nullptr; return tsdf_fail (t, ICP_ENOMEM, "hipMalloc: out of device memory"); }
-    *cap = bytes;
-    return ICP_OK;
 }
 
 int zero_volume (icp_tsdf_context *t)
@@ -303,8 +295,8 @@ int integrate_prepare (icp_tsdf_context *t, const char *who, const icp_rgbd_t *c
     TSDFCHK (t, hipSetDevice (t->device));
     const size_t n = (size_t) cam->width * cam->height;
     int rc;
-    if ((rc = reserve (t, &t->dDepth, &t->depth_cap, n * 2u))) return rc;
-    if (rgb && (rc = reserve (t, &t->dRgb, &t->rgb_cap, n * 3u))) return rc;
+    if ((rc = tsdf_reserve (t, &t->dDepth, &t->depth_cap, n * 2u))) return rc;
+    if (rgb && (rc = tsdf_reserve (t, &t->dRgb, &t->rgb_cap, n * 3u))) return rc;
     TSDFCHK (t, hipMemcpyAsync (t->dDepth, depth, n * 2u, hipMemcpyHostToDevice, t->stream));
     if (rgb) TSDFCHK (t, hipMemcpyAsync (t->dRgb, rgb, n * 3u, hipMemcpyHostToDevice, t->stream));
     a->v = t->v; a->cam = view_of (*cam, pose12);
@@ -323,7 +315,7 @@ int icp_tsdf_destroy (icp_tsdf_handle t) try
     if (!t) return ICP_EINVAL;
     (void) hipSetDevice (t->device);
     if (t->stream) (void) hipStreamSynchronize (t->stream);
-    for (void *q : { (void *) t->v.dw, (void *) t->v.col, t->dDepth, t->dRgb, t->dOut, t->dNrm }) if (q) (void) hipFree (q);
+    for (void *q : { (void *) t->v.dw, (void *) t->v.col, t->dDepth, t->dRgb, t->dOut, t->dNrm, t->dSurf, t->dEdge }) if (q) (void) hipFree (q);
     if (t->ev0) (void) hipEventDestroy (t->ev0);
     if (t->ev1) (void) hipEventDestroy (t->ev1);
     if (t->stream) (void) hipStreamDestroy (t->stream);
@@ -397,8 +389,8 @@ int icp_tsdf_raycast (icp_tsdf_handle t, const icp_rgbd_t *cam, const float *pos
     int rc = tsdf_cast_prepare (t, "icp_tsdf_raycast", cam, pose12, z_near, z_far, side, &a); if (rc) return rc;
     TSDFCHK (t, hipSetDevice (t->device));
     const size_t n = side ? (size_t) side * side : (size_t) cam->width * cam->height;
-    if ((rc = reserve (t, &t->dOut, &t->out_cap, n * 32u))) return rc;
-    if (normals_out && (rc = reserve (t, &t->dNrm, &t->nrm_cap, n * 16u))) return rc;
+    if ((rc = tsdf_reserve (t, &t->dOut, &t->out_cap, n * 32u))) return rc;
+    if (normals_out && (rc = tsdf_reserve (t, &t->dNrm, &t->nrm_cap, n * 16u))) return rc;
     a.out = static_cast<float4 *> (t->dOut); a.nrm = normals_out ? static_cast<float4 *> (t->dNrm) : nullptr;
     tsdf_launch_raycast (a, t->stream);
     TSDFCHK (t, hipGetLastError ());
@@ -464,7 +456,8 @@ int icp_tsdf_time (icp_tsdf_handle t, int what, const icp_rgbd_t *cam, const flo
                            uint32_t side, uint32_t reps, float *us_per_launch) try
 {
     if (!t) return ICP_EINVAL;
-    if (!us_per_launch || reps == 0u || (what != 0 && what != 1)) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_time: bad arguments");
+    if (!us_per_launch || reps == 0u || what < 0 || what > 4) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_time: bad arguments");
+    if (what >= 2) return tsdf_time_surface (t, what - 2, reps, us_per_launch);
     tsdf_integrate_args ia {};
     icp_tsdf_cast_args ca {};
     int rc;
@@ -473,7 +466,7 @@ int icp_tsdf_time (icp_tsdf_handle t, int what, const icp_rgbd_t *cam, const flo
         if ((rc = tsdf_cast_prepare (t, "icp_tsdf_time", cam, pose12, z_near, z_far, side, &ca))) return rc;
         TSDFCHK (t, hipSetDevice (t->device));
         const size_t n = side ? (size_t) side * side : (size_t) cam->width * cam->height;
-        if ((rc = reserve (t, &t->dOut, &t->out_cap, n * 32u)) || (rc = reserve (t, &t->dNrm, &t->nrm_cap, n * 16u))) return rc;
+        if ((rc = tsdf_reserve (t, &t->dOut, &t->out_cap, n * 32u)) || (rc = tsdf_reserve (t, &t->dNrm, &t->nrm_cap, n * 16u))) return rc;
         ca.out = static_cast<float4 *> (t->dOut); ca.nrm = static_cast<float4 *> (t->dNrm);
     }
     auto launch = [&] () { if (what == 0) launch_integrate (ia, t->stream); else tsdf_launch_raycast (ca, t->stream); };

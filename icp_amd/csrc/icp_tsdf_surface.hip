@@ -1,0 +1,345 @@
+// icp_tsdf_surface.hip — the surface of a TSDF volume as a point cloud, extracted on the device (icp_tsdf_extract_surface; the rule:
+// include/icp_amd.h, "Surface extraction"; tests/tsdf_surface_ref.py restates it).  The points are the zero crossings of D on the edges
+// between neighbouring usable voxels, in ascending 3 * (linear voxel index) + axis: an ordered stream compaction of a sweep over the
+// volume, in the form of icp_pairs.hip carried to a volume's 2^20 blocks.
+//
+// A block owns RUN = 1024 consecutive linear voxel indices, as STEPS = 4 sub-runs of 256: lane l of wave w judges voxel
+// RUN blk + 256 s + 64 w + l in step s, so a wave's {D, W} access is one coalesced 8-byte vector access whether or not a row ends inside
+// it, and the order of the output is the order of (blk, s, w, lane, axis).
+//
+//   k_tsdf_surface_count    the sweep.  A voxel that is not usable is the low end of no member: its +x, +y, +z neighbours (plain loads at
+//                           offsets 1, nx, nx ny; the z neighbour comes back one slice later) are fetched, and its indices divided out,
+//                           only where the voxel itself is usable — a wave of free or unseen space makes one load.  Every lane has 0 to 3
+//                           members: three ballots a step.  A wave stores its four steps' counts as four bytes (at most 192 a step) and,
+//                           for a step with members, the three ballots themselves (24 bytes for 512 bytes of {D, W}); the block stores
+//                           the sum of its counts.
+//   k_tsdf_scan_tiles       exclusive scan of SCAN_TILE = 1024 words per block, four per lane: the offsets inside the tile and the tile's
+//                           sum.  Launched twice: over the block counts (at most 2^20: 1024 tiles), then as one block over the tile sums,
+//                           whose sum is the number of members.
+//   k_tsdf_surface_scatter  one block per block of the sweep, which judges nothing again: a wave reads its block's sixteen counts, its
+//                           offsets and its own ballots in one round trip, leaves if it has no member, and member (lane, axis) goes to
+//                               (tile offset + offset inside the tile) + (members of the steps and waves in front: sums of those bytes) +
+//                               (members below the lane: mbcnt of the three ballots) + (the lane's own members on lower axes)
+//                           as the word 3 * (linear voxel index) + axis.  No LDS, no barrier.  Positions past the capacity are not written.
+//   k_tsdf_surface_points   a lane per written member: D0, D1, the colour and the twelve gradient samples are fetched for members only,
+//                           all in one round trip, and the record is three 16-byte stores.  (A wall across the x axis has one member in
+//                           every row, so one in a wave of 64 i: gathered from the scatter's lanes, the members' loads were instructions
+//                           with one lane in use, and that pass was measured at 165 us for 465 000 members, 78 us without the gradients;
+//                           here 64 members share an instruction.)
+// Nothing waits for another workgroup inside a launch: the order between the passes is the stream's.  The counts are integer sums and a
+// position is a function of the predicate alone: no atomics, and the result does not depend on the launch shape.
+//
+// -ffp-contract=off keeps every operation on its own; `/` and sqrtf are the correctly rounded ones.
+#include "icp_tsdf.h"
+#include "icp_cguard.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace {
+
+constexpr uint32_t BLOCK = 256u, WAVES = BLOCK / 64u;
+constexpr uint32_t STEPS = 4u, RUN = BLOCK * STEPS;        // voxels of a block
+constexpr uint32_t SCAN_TILE = BLOCK * 4u;                 // words of a block of k_tsdf_scan_tiles
+constexpr uint32_t MASKS = STEPS * 3u;                     // ballots a wave of the sweep may store: [step][axis]
+
+typedef unsigned long long mask64;
+
+struct tsdf_surface_args {
+    icp_tsdf_dev v;
+    float min_weight;
+    uint32_t n_vox;                                        // nx ny nz <= 2^30
+    // what the sweep leaves: [nblk][WAVES] words, byte s of word w = the members of wave w in step s;  [nblk][WAVES][STEPS][3] ballots,
+    // written for the steps whose byte is not 0;  [nblk] sums
+    uint32_t *wave_cnt; mask64 *masks; uint32_t *blk_cnt;
+    const uint32_t *blk_off, *tile_off;                    // the scan: a block's offset inside its tile, a tile's offset
+    uint32_t limit;                                        // min (count, capacity): positions below it are written
+    uint32_t *edge;                                        // [limit]: member p is edge 3 * (linear voxel index) + axis
+    float4 *out, *nrm;                                     // [limit][2], [limit] or null
+};
+
+__device__ __forceinline__ bool usable (float2 dw, float min_weight) { return dw.y >= min_weight && fabsf (dw.x) < 1.f; }
+
+__device__ __forceinline__ uint32_t below_lane (mask64 bal, uint32_t add)
+{
+    return __builtin_amdgcn_mbcnt_hi ((uint32_t) (bal >> 32), __builtin_amdgcn_mbcnt_lo ((uint32_t) bal, add));
+}
+
+__global__ __launch_bounds__ (BLOCK) void k_tsdf_surface_count (tsdf_surface_args a)
+{
+    __shared__ uint32_t s_wave[WAVES];
+    const icp_tsdf_dev &v = a.v;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, g0 = blockIdx.x * RUN + tid;
+    float2 own[STEPS];                                     // all steps in flight together (a lane past the volume reads the last voxel)
+#pragma unroll
+    for (uint32_t s = 0; s < STEPS; ++s) own[s] = v.dw[min (g0 + s * BLOCK, a.n_vox - 1u)];
+    const uint32_t off[3] = { 1u, v.nx, v.nx * v.ny };
+    uint32_t c = 0u, steps = 0u;
+#pragma unroll
+    for (uint32_t s = 0; s < STEPS; ++s) {
+        const uint32_t g = g0 + s * BLOCK;
+        bool m[3] = { false, false, false };
+        if (g < a.n_vox && usable (own[s], a.min_weight)) {
+            const uint32_t row = g / v.nx, i = g - row * v.nx, k = row / v.ny, j = row - k * v.ny;
+            const bool inside[3] = { i + 1u < v.nx, j + 1u < v.ny, k + 1u < v.nz };
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                if (!inside[ax]) continue;                 // (g + off <= n_vox - 1 where the neighbour exists)
+                const float2 e = v.dw[g + off[ax]];
+                m[ax] = usable (e, a.min_weight) && ((own[s].x > 0.f) != (e.x > 0.f));
+            }
+        }
+        const mask64 b0 = __ballot (m[0]), b1 = __ballot (m[1]), b2 = __ballot (m[2]);
+        const uint32_t n = (uint32_t) (__popcll (b0) + __popcll (b1) + __popcll (b2));
+        c += n; steps |= n << (8u * s);
+        if (n && lane < 3u) a.masks[((size_t) (blockIdx.x * WAVES + wave) * STEPS + s) * 3u + lane] = lane == 0u ? b0 : lane == 1u ? b1 : b2;
+    }
+    if (lane == 0u) { s_wave[wave] = c; a.wave_cnt[blockIdx.x * WAVES + wave] = steps; }
+    __syncthreads ();
+    if (tid == 0u) a.blk_cnt[blockIdx.x] = (s_wave[0] + s_wave[1]) + (s_wave[2] + s_wave[3]);
+}
+
+// out[i] = in[first word of the tile] + .. + in[i - 1] for the n words in tiles of SCAN_TILE, sums[tile] = the tile's sum
+__global__ __launch_bounds__ (BLOCK) void k_tsdf_scan_tiles (const uint32_t *in, uint32_t n, uint32_t *out, uint32_t *sums)
+{
+    __shared__ uint32_t s_wave[WAVES];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, at = blockIdx.x * SCAN_TILE + tid * 4u;
+    uint32_t x[4];
+#pragma unroll
+    for (uint32_t e = 0; e < 4u; ++e) x[e] = at + e < n ? in[at + e] : 0u;
+    const uint32_t mine = (x[0] + x[1]) + (x[2] + x[3]);
+    uint32_t incl = mine;                                  // inclusive scan over the wave's lanes
+#pragma unroll
+    for (uint32_t d = 1u; d < 64u; d <<= 1) {
+        const uint32_t up = __shfl_up (incl, d, 64);
+        if (lane >= d) incl += up;
+    }
+    if (lane == 63u) s_wave[wave] = incl;
+    __syncthreads ();
+    uint32_t front = incl - mine;
+    for (uint32_t w = 0; w < wave; ++w) front += s_wave[w];
+#pragma unroll
+    for (uint32_t e = 0; e < 4u; ++e) {
+        if (at + e < n) out[at + e] = front;
+        front += x[e];
+    }
+    if (tid == BLOCK - 1u) sums[blockIdx.x] = front;
+}
+
+// the six neighbours of voxel u = (i, j, k) at linear index g, which has all of them inside the volume
+struct six { float2 xp, xm, yp, ym, zp, zm; };
+
+__device__ __forceinline__ six neighbours (const icp_tsdf_dev &v, uint32_t g)
+{
+    const uint32_t sy = v.nx, sz = v.nx * v.ny;
+    return six { v.dw[g + 1u], v.dw[g - 1u], v.dw[g + sy], v.dw[g - sy], v.dw[g + sz], v.dw[g - sz] };
+}
+
+__device__ __forceinline__ bool known (const six &n) { return n.xp.y > 0.f && n.xm.y > 0.f && n.yp.y > 0.f && n.ym.y > 0.f && n.zp.y > 0.f && n.zm.y > 0.f; }
+
+// the record of member (v, AX), v = (i, j, k) at linear index g, at position pos: every load first, then the arithmetic of the rule
+template <int AX>
+__device__ __forceinline__ void emit (const tsdf_surface_args &a, uint32_t g, uint32_t i, uint32_t j, uint32_t k, uint32_t pos)
+{
+    const icp_tsdf_dev &v = a.v;
+    const uint32_t off = AX == 0 ? 1u : AX == 1 ? v.nx : v.nx * v.ny;
+    const uint32_t hi = i + (AX == 0), hj = j + (AX == 1), hk = k + (AX == 2);                // v + e_a
+    // G is known at neither end unless both have their six neighbours inside
+    const bool inside = a.nrm && i >= 1u && hi + 1u < v.nx && j >= 1u && hj + 1u < v.ny && k >= 1u && hk + 1u < v.nz;
+    const float d0 = v.dw[g].x, d1 = v.dw[g + off].x;
+    float4 c0 = make_float4 (0.f, 0.f, 0.f, 0.f), c1 = c0;
+    if (v.col) { c0 = v.col[g]; c1 = v.col[g + off]; }
+    six n0 {}, n1 {};
+    if (inside) { n0 = neighbours (v, g); n1 = neighbours (v, g + off); }
+    const float t = d0 / (d0 - d1);
+    const float fi = (float) i, fj = (float) j, fk = (float) k;
+    const float px = v.ox + (AX == 0 ? fi + t : fi) * v.voxel, py = v.oy + (AX == 1 ? fj + t : fj) * v.voxel, pz = v.oz + (AX == 2 ? fk + t : fk) * v.voxel;
+    a.out[2 * (size_t) pos] = make_float4 (px, py, pz, 1.f);
+    a.out[2 * (size_t) pos + 1] = make_float4 (c0.x + t * (c1.x - c0.x), c0.y + t * (c1.y - c0.y), c0.z + t * (c1.z - c0.z), 1.f);
+    if (!a.nrm) return;
+    float4 n = make_float4 (0.f, 0.f, 0.f, 0.f);
+    if (inside && known (n0) && known (n1)) {
+        const float g0x = n0.xp.x - n0.xm.x, g0y = n0.yp.x - n0.ym.x, g0z = n0.zp.x - n0.zm.x;
+        const float g1x = n1.xp.x - n1.xm.x, g1y = n1.yp.x - n1.ym.x, g1z = n1.zp.x - n1.zm.x;
+        const float gx = g0x + t * (g1x - g0x), gy = g0y + t * (g1y - g0y), gz = g0z + t * (g1z - g0z);
+        const float len = sqrtf ((gx * gx + gy * gy) + gz * gz);
+        if (len > 0.f) n = make_float4 (gx / len, gy / len, gz / len, 0.f);
+    }
+    a.nrm[pos] = n;
+}
+
+__global__ __launch_bounds__ (BLOCK) void k_tsdf_surface_scatter (tsdf_surface_args a)
+{
+    const uint32_t blk = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    // one round trip: the block's counts, its offsets, the wave's ballots (those of a step without members were never written, and are not used)
+    const uint4 wc = reinterpret_cast<const uint4 *> (a.wave_cnt)[blk];
+    uint32_t front = a.tile_off[blk / SCAN_TILE] + a.blk_off[blk];                          // the position of the first member of step s
+    const mask64 *mk = a.masks + (size_t) (blk * WAVES + wave) * MASKS;
+    mask64 bal[MASKS];
+#pragma unroll
+    for (uint32_t e = 0; e < MASKS; ++e) bal[e] = mk[e];
+    const uint32_t mine = wave == 0u ? wc.x : wave == 1u ? wc.y : wave == 2u ? wc.z : wc.w;
+    if (mine == 0u || front >= a.limit) return;            // (wave-uniform)
+#pragma unroll
+    for (uint32_t s = 0; s < STEPS; ++s) {
+        const uint32_t c0 = (wc.x >> (8u * s)) & 255u, c1 = (wc.y >> (8u * s)) & 255u, c2 = (wc.z >> (8u * s)) & 255u, c3 = (wc.w >> (8u * s)) & 255u;
+        const uint32_t first = front + (wave > 0u ? c0 : 0u) + (wave > 1u ? c1 : 0u) + (wave > 2u ? c2 : 0u);
+        front += (c0 + c1) + (c2 + c3);
+        if (((mine >> (8u * s)) & 255u) == 0u) continue;
+        if (first >= a.limit) break;                       // (the wave's later steps lie further back; the block's other waves may not)
+        const mask64 b0 = bal[3u * s], b1 = bal[3u * s + 1u], b2 = bal[3u * s + 2u];
+        const bool m0 = (b0 >> lane) & 1ull, m1 = (b1 >> lane) & 1ull, m2 = (b2 >> lane) & 1ull;
+        if (!(m0 || m1 || m2)) continue;
+        uint32_t pos = first + below_lane (b2, below_lane (b1, below_lane (b0, 0u)));
+        const uint32_t e = 3u * (blk * RUN + s * BLOCK + wave * 64u + lane);               // (< 3 * 2^30)
+        if (m0) { if (pos < a.limit) a.edge[pos] = e; ++pos; }
+        if (m1) { if (pos < a.limit) a.edge[pos] = e + 1u; ++pos; }
+        if (m2) { if (pos < a.limit) a.edge[pos] = e + 2u; }
+    }
+}
+
+// a lane per written member: the gathers of 64 members are one wave's instructions
+__global__ __launch_bounds__ (BLOCK) void k_tsdf_surface_points (tsdf_surface_args a)
+{
+    const icp_tsdf_dev &v = a.v;
+    const uint32_t pos = blockIdx.x * BLOCK + threadIdx.x;
+    if (pos >= a.limit) return;
+    const uint32_t e = a.edge[pos], g = e / 3u, ax = e - 3u * g;
+    if (g + (ax == 0u ? 1u : ax == 1u ? v.nx : v.nx * v.ny) >= a.n_vox) return;            // (never: a member's high end is inside the volume)
+    const uint32_t row = g / v.nx, i = g - row * v.nx, k = row / v.ny, j = row - k * v.ny;
+    if (ax == 0u) emit<0> (a, g, i, j, k, pos);
+    else if (ax == 1u) emit<1> (a, g, i, j, k, pos);
+    else emit<2> (a, g, i, j, k, pos);
+}
+
+// The words of an extraction in the volume's scratch: the sweep's ballots (384 bytes a block of 8 KiB of {D, W}), its wave counts, its block
+// counts; the blocks' offsets inside their tiles, the tile sums, the tile offsets, the count.  (The members' edges, like their records, are
+// scratch of their own, sized by the count.)
+struct surface_plan {
+    uint32_t n_vox, nblk, ntile;
+    mask64 *masks;
+    uint32_t *wave_cnt, *blk_cnt, *blk_off, *tile_sum, *tile_off, *count;
+};
+
+int plan_surface (icp_tsdf_context *t, surface_plan *p)
+{
+    p->n_vox = t->cfg.nx * t->cfg.ny * t->cfg.nz;           // (<= 2^30: every axis <= 1024)
+    p->nblk = (p->n_vox + RUN - 1u) / RUN;
+    p->ntile = (p->nblk + SCAN_TILE - 1u) / SCAN_TILE;      // (<= 1024: the second scan is one block)
+    const size_t units = (size_t) p->nblk * WAVES, words = units + 2u * (size_t) p->nblk + 2u * p->ntile + 1u;
+    int rc = icp_host::tsdf_reserve (t, &t->dSurf, &t->surf_cap, units * MASKS * sizeof (mask64) + words * sizeof (uint32_t)); if (rc) return rc;
+    p->masks = static_cast<mask64 *> (t->dSurf);
+    p->wave_cnt = reinterpret_cast<uint32_t *> (p->masks + units * MASKS);                  // (16-byte aligned: a unit's ballots are 96 bytes)
+    p->blk_cnt = p->wave_cnt + units; p->blk_off = p->blk_cnt + p->nblk;
+    p->tile_sum = p->blk_off + p->nblk; p->tile_off = p->tile_sum + p->ntile; p->count = p->tile_off + p->ntile;
+    return ICP_OK;
+}
+
+tsdf_surface_args args_of (const icp_tsdf_context *t, const surface_plan &p, float min_weight)
+{
+    tsdf_surface_args a {};
+    a.v = t->v; a.min_weight = min_weight; a.n_vox = p.n_vox;
+    a.wave_cnt = p.wave_cnt; a.masks = p.masks; a.blk_cnt = p.blk_cnt; a.blk_off = p.blk_off; a.tile_off = p.tile_off;
+    return a;
+}
+
+void launch_scan (const surface_plan &p, hipStream_t s)
+{
+    hipLaunchKernelGGL (k_tsdf_scan_tiles, dim3 (p.ntile), dim3 (BLOCK), 0, s, (const uint32_t *) p.blk_cnt, p.nblk, p.blk_off, p.tile_sum);
+    hipLaunchKernelGGL (k_tsdf_scan_tiles, dim3 (1), dim3 (BLOCK), 0, s, (const uint32_t *) p.tile_sum, p.ntile, p.tile_off, p.count);
+}
+
+// the count and the position of every block's first member
+void launch_count_and_scan (const tsdf_surface_args &a, const surface_plan &p, hipStream_t s)
+{
+    hipLaunchKernelGGL (k_tsdf_surface_count, dim3 (p.nblk), dim3 (BLOCK), 0, s, a);
+    launch_scan (p, s);
+}
+
+// the first a.limit > 0 members: their edges in order, then their records
+void launch_scatter (const tsdf_surface_args &a, const surface_plan &p, hipStream_t s)
+{
+    hipLaunchKernelGGL (k_tsdf_surface_scatter, dim3 (p.nblk), dim3 (BLOCK), 0, s, a);
+    hipLaunchKernelGGL (k_tsdf_surface_points, dim3 ((a.limit + BLOCK - 1u) / BLOCK), dim3 (BLOCK), 0, s, a);
+}
+
+// the count of the volume's members on the host, and the output scratch for the first min (count, capacity) of them
+int count_and_reserve (icp_tsdf_context *t, tsdf_surface_args &a, const surface_plan &p, uint32_t capacity, bool normals, uint32_t *total)
+{
+    launch_count_and_scan (a, p, t->stream);
+    TSDFCHK (t, hipGetLastError ());
+    TSDFCHK (t, hipMemcpyAsync (total, p.count, sizeof (uint32_t), hipMemcpyDeviceToHost, t->stream));
+    TSDFCHK (t, hipStreamSynchronize (t->stream));
+    a.limit = std::min (*total, capacity);
+    if (a.limit == 0u) return ICP_OK;
+    int rc;
+    if ((rc = icp_host::tsdf_reserve (t, &t->dEdge, &t->edge_cap, (size_t) a.limit * 4u))) return rc;
+    if ((rc = icp_host::tsdf_reserve (t, &t->dOut, &t->out_cap, (size_t) a.limit * 32u))) return rc;
+    if (normals && (rc = icp_host::tsdf_reserve (t, &t->dNrm, &t->nrm_cap, (size_t) a.limit * 16u))) return rc;
+    a.edge = static_cast<uint32_t *> (t->dEdge); a.out = static_cast<float4 *> (t->dOut); a.nrm = normals ? static_cast<float4 *> (t->dNrm) : nullptr;
+    return ICP_OK;
+}
+
+}  // namespace
+
+namespace icp_host {
+
+int tsdf_time_surface (icp_tsdf_context *t, int part, uint32_t reps, float *us_per_group)
+{
+    TSDFCHK (t, hipSetDevice (t->device));
+    surface_plan p;
+    int rc = plan_surface (t, &p); if (rc) return rc;
+    tsdf_surface_args a = args_of (t, p, 1.f);
+    uint32_t total = 0u;
+    if ((rc = count_and_reserve (t, a, p, UINT32_MAX, true, &total))) return rc;      // (untimed: the code objects are loaded, the scratch holds every member)
+    auto group = [&] () {
+        if (part == 1) { launch_scan (p, t->stream); return; }
+        if (part != 2) launch_count_and_scan (a, p, t->stream);
+        if (a.limit) launch_scatter (a, p, t->stream);
+    };
+    group ();
+    TSDFCHK (t, hipEventRecord (t->ev0, t->stream));
+    for (uint32_t i = 0; i < reps; ++i) group ();
+    TSDFCHK (t, hipEventRecord (t->ev1, t->stream));
+    TSDFCHK (t, hipGetLastError ());
+    TSDFCHK (t, hipEventSynchronize (t->ev1));
+    float ms = 0.f;
+    TSDFCHK (t, hipEventElapsedTime (&ms, t->ev0, t->ev1));
+    *us_per_group = ms * 1e3f / (float) reps;
+    return ICP_OK;
+}
+
+}  // namespace icp_host
+
+using namespace icp_host;
+
+extern "C" {
+
+int icp_tsdf_extract_surface (icp_tsdf_handle t, const icp_tsdf_surface_t *opt, uint32_t capacity, void *cloud_out, float *normals_out, uint32_t *count) try
+{
+    if (!t) return ICP_EINVAL;
+    if (!count) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_extract_surface: count is required");
+    const icp_tsdf_surface_t o = opt ? *opt : icp_tsdf_surface_t { 1.f, 0u };
+    if (!(std::isfinite (o.min_weight) && o.min_weight >= 1.f)) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_extract_surface: min_weight must be finite and >= 1");
+    if (o.normals > 1u) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_extract_surface: normals must be 0 or 1");
+    if (capacity && (!cloud_out || (o.normals && !normals_out)))
+        return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_extract_surface: with a capacity, cloud_out is required, and normals_out if normals are wanted");
+    TSDFCHK (t, hipSetDevice (t->device));
+    surface_plan p;
+    int rc = plan_surface (t, &p); if (rc) return rc;
+    tsdf_surface_args a = args_of (t, p, o.min_weight);
+    uint32_t total = 0u;
+    if ((rc = count_and_reserve (t, a, p, capacity, o.normals != 0u, &total))) return rc;
+    if (a.limit) {
+        launch_scatter (a, p, t->stream);
+        TSDFCHK (t, hipGetLastError ());
+        TSDFCHK (t, hipMemcpyAsync (cloud_out, t->dOut, (size_t) a.limit * 32u, hipMemcpyDeviceToHost, t->stream));
+        if (a.nrm) TSDFCHK (t, hipMemcpyAsync (normals_out, t->dNrm, (size_t) a.limit * 16u, hipMemcpyDeviceToHost, t->stream));
+        TSDFCHK (t, hipStreamSynchronize (t->stream));
+    }
+    *count = total;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
+}  // extern "C"

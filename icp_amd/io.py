@@ -1,6 +1,7 @@
-"""Point-cloud files of the reference's demos: raw little-endian 640x480 float8 `[x y z 1 r g b 1]`
+"""Point-cloud files.  The reference's demos: raw little-endian 640x480 float8 `[x y z 1 r g b 1]`
 (`data/kg_pc8d_{1,2}.bin`, 9 830 400 bytes; reader examples/registration.cpp:285-337, writer
-src/kinect_frame_grabber.cpp:252-272)."""
+src/kinect_frame_grabber.cpp:252-272).  Any viewer: binary little-endian PLY (save_ply / load_ply), for clouds of any size — the
+surface of a TSDF volume (icp_amd.tsdf.TSDFVolume.extract_surface).  Host code only."""
 import numpy as np
 
 VGA_POINTS = 640 * 480
@@ -18,3 +19,79 @@ def save_pc8d(path, cloud):
     if cloud.size != VGA_POINTS * 8:
         raise ValueError("expected a 640x480 float8 cloud")
     cloud.tofile(path)
+
+
+_PLY_XYZ, _PLY_NORMAL, _PLY_RGB = ("x", "y", "z"), ("nx", "ny", "nz"), ("red", "green", "blue")
+
+
+def _ply_dtype(normals):
+    return np.dtype([(n, "<f4") for n in _PLY_XYZ + (_PLY_NORMAL if normals else ())] + [(n, "u1") for n in _PLY_RGB])
+
+
+def save_ply(path, cloud, normals=None):
+    """An (n, 8) cloud `[x y z 1 r g b 1]`, and its (n, 4) normals if given, as a binary little-endian PLY: float x y z, float nx ny nz
+    with normals, uchar red green blue = rint (255 c) clipped to 0 .. 255."""
+    cloud = np.asarray(cloud, np.float32).reshape(-1, 8)
+    n = cloud.shape[0]
+    rec = np.empty(n, _ply_dtype(normals is not None))
+    for a, name in enumerate(_PLY_XYZ):
+        rec[name] = cloud[:, a]
+    if normals is not None:
+        normals = np.asarray(normals, np.float32).reshape(-1, 4)
+        if normals.shape[0] != n:
+            raise ValueError("expected one normal per point")
+        for a, name in enumerate(_PLY_NORMAL):
+            rec[name] = normals[:, a]
+    with np.errstate(invalid="ignore"):
+        byte = np.clip(np.rint(np.nan_to_num(cloud[:, 4:7]) * np.float32(255)), 0, 255).astype(np.uint8)
+    for a, name in enumerate(_PLY_RGB):
+        rec[name] = byte[:, a]
+    head = ["ply", "format binary_little_endian 1.0", "comment icp_amd", "element vertex %d" % n]
+    head += ["property %s %s" % ("uchar" if rec.dtype[name] == np.uint8 else "float", name) for name in rec.dtype.names]
+    with open(path, "wb") as f:
+        f.write(("\n".join(head + ["end_header"]) + "\n").encode("ascii"))
+        f.write(rec.tobytes())
+
+
+def load_ply(path):
+    """A file save_ply wrote: (cloud (n, 8) with the colour as byte / 255, normals (n, 4) or None)."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError("%s: not a PLY file" % path)
+        n, props, fmt = None, [], None
+        for line in iter(f.readline, b""):
+            w = line.decode("ascii").split()
+            if w[:1] == ["end_header"]:
+                break
+            if w[:1] == ["format"]:
+                fmt = w[1]
+            elif w[:2] == ["element", "vertex"]:
+                n = int(w[2])
+            elif w[:1] == ["element"]:
+                raise ValueError("%s: only a vertex element is supported" % path)
+            elif w[:1] == ["property"]:
+                props.append((w[2], w[1]))
+        else:
+            raise ValueError("%s: no end_header" % path)
+        if fmt != "binary_little_endian" or n is None:
+            raise ValueError("%s: expected a binary_little_endian PLY with a vertex element" % path)
+        normals = any(name == "nx" for name, _ in props)
+        want = _ply_dtype(normals)
+        if [(name, {"float": "<f4", "uchar": "u1"}.get(kind)) for name, kind in props] != [(name, want[name].str.replace("|", "")) for name in want.names]:
+            raise ValueError("%s: expected the properties save_ply writes, got %r" % (path, props))
+        data = f.read()
+    if len(data) != n * want.itemsize:
+        raise ValueError("%s: expected %d bytes of vertices, got %d" % (path, n * want.itemsize, len(data)))
+    rec = np.frombuffer(data, want)
+    cloud = np.zeros((n, 8), np.float32)
+    cloud[:, 3] = cloud[:, 7] = 1
+    for a, name in enumerate(_PLY_XYZ):
+        cloud[:, a] = rec[name]
+    for a, name in enumerate(_PLY_RGB):
+        cloud[:, 4 + a] = rec[name].astype(np.float32) / np.float32(255)
+    nrm = None
+    if normals:
+        nrm = np.zeros((n, 4), np.float32)
+        for a, name in enumerate(_PLY_NORMAL):
+            nrm[:, a] = rec[name]
+    return cloud, nrm

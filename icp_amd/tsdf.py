@@ -1,9 +1,11 @@
 """Frame-to-model: a TSDF volume fused and ray-cast on the device (include/icp_amd.h: icp_tsdf_t, icp_tsdf_integrate, icp_tsdf_raycast,
-icp_tsdf_raycast_to, icp_tsdf_compose_pose).
+icp_tsdf_raycast_to, icp_tsdf_compose_pose), and its surface as a point cloud (icp_tsdf_extract_surface).
 
     vol = TSDFVolume(TSDFConfig(256, 256, 256, voxel=8.0, origin=(-1024, -1024, 0), mu=24.0))
     for pose, k, scale in track_to_model(icp, vol, frames, pose0, 300.0, 4000.0):
         ...
+    cloud, normals = vol.extract_surface()
+    icp_amd.io.save_ply("model.ply", cloud, normals)
 
 A pose is 12 floats, row-major [R | t], camera -> world.  A camera is an icp_amd.rgbd.RGBDConfig."""
 import ctypes as C
@@ -18,6 +20,10 @@ from icp_amd.rgbd import _images, _ptr
 class icp_tsdf_t(C.Structure):
     _fields_ = [("nx", C.c_uint32), ("ny", C.c_uint32), ("nz", C.c_uint32), ("voxel", C.c_float), ("origin", C.c_float * 3),
                 ("mu", C.c_float), ("w_max", C.c_float), ("colour", C.c_uint32)]
+
+
+class icp_tsdf_surface_t(C.Structure):
+    _fields_ = [("min_weight", C.c_float), ("normals", C.c_uint32)]
 
 
 class TSDFConfig:
@@ -59,6 +65,7 @@ def _lib():
                            ("icp_tsdf_raycast_to", (vp, vp, i32, cam, vp, f32, f32, i32)),
                            ("icp_tsdf_read", (vp, vp, vp)), ("icp_tsdf_write", (vp, vp, vp)),
                            ("icp_tsdf_compose_pose", (vp, vp, vp, C.POINTER(f32))),
+                           ("icp_tsdf_extract_surface", (vp, C.POINTER(icp_tsdf_surface_t), u32, vp, vp, C.POINTER(u32))),
                            ("icp_tsdf_time", (vp, i32, cam, vp, vp, vp, f32, f32, u32, u32, C.POINTER(f32)))):
             f = getattr(L, name)
             f.restype, f.argtypes = i32, list(args)
@@ -175,12 +182,32 @@ class TSDFVolume:
                 raise ValueError("expected nz x ny x nx x 3 floats")
         self._chk(self._L.icp_tsdf_write(self._t, _ptr(dw), _ptr(rgb)))
 
-    def time_kernel(self, what, cam, pose12, depth=None, rgb=None, z_near=0.0, z_far=0.0, side=0, reps=20):
-        """icp_tsdf_time (diagnostic): microseconds per launch of k_tsdf_integrate (what = 0; the volume changes) or k_tsdf_raycast (1)."""
+    def extract_surface(self, min_weight=1.0, normals=True, capacity=None):
+        """icp_tsdf_extract_surface: the volume's surface as (cloud (n, 8), normals (n, 4) or None), the zero crossings of D on the edges
+        between usable voxels in ascending 3 * (linear voxel index) + axis.  capacity = None: a counting call first, then every member.
+        With a capacity: (cloud, normals, count) — the first min (count, capacity) members and the number there are."""
+        opt, count = icp_tsdf_surface_t(min_weight, int(bool(normals))), C.c_uint32()
+        if capacity is None:
+            self._chk(self._L.icp_tsdf_extract_surface(self._t, C.byref(opt), 0, None, None, C.byref(count)))
+            room = count.value
+        else:
+            room = int(capacity)
+        cloud = np.empty((room, 8), np.float32)
+        nrm = np.empty((room, 4), np.float32) if normals else None
+        self._chk(self._L.icp_tsdf_extract_surface(self._t, C.byref(opt), room, _ptr(cloud) if room else None, _ptr(nrm) if room else None, C.byref(count)))
+        n = min(count.value, room)
+        if capacity is None:
+            return cloud[:n], (nrm[:n] if normals else None)
+        return cloud[:n], (nrm[:n] if normals else None), count.value
+
+    def time_kernel(self, what, cam=None, pose12=None, depth=None, rgb=None, z_near=0.0, z_far=0.0, side=0, reps=20):
+        """icp_tsdf_time (diagnostic): microseconds per launch of k_tsdf_integrate (what = 0; the volume changes) or k_tsdf_raycast (1), or
+        per group of the launches of one extract_surface with normals (2; 3: its two scan launches alone, 4: its scatter and points launches alone — nothing but reps is used)."""
         if depth is not None:
             depth, rgb = _images(depth, rgb, cam.width, cam.height)
-        c, us = cam._c(), C.c_float()
-        self._chk(self._L.icp_tsdf_time(self._t, what, C.byref(c), _ptr(_pose(pose12)), _ptr(depth), _ptr(rgb), z_near, z_far, side, reps, C.byref(us)))
+        c, us = cam._c() if cam is not None else None, C.c_float()
+        self._chk(self._L.icp_tsdf_time(self._t, what, C.byref(c) if c is not None else None, _ptr(_pose(pose12)) if pose12 is not None else None,
+                                        _ptr(depth), _ptr(rgb), z_near, z_far, side, reps, C.byref(us)))
         return us.value
 
 

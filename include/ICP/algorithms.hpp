@@ -336,8 +336,8 @@ namespace ICP
 
     /*! \brief Frame-to-model (icp_tsdf_*, include/icp_amd.h): a truncated signed distance volume on the device that registered frames
      *         are fused into (`integrate`) and whose view from a pose (`raycast`, `raycastTo`) is the fixed frame of the next
-     *         registration — an organised grid with normals.  A pose is 12 floats, row-major [R | t], camera -> world.  The reference has
-     *         no model and no such class. */
+     *         registration — an organised grid with normals.  `extractSurface` gives the model itself as a point cloud.  A pose is 12
+     *         floats, row-major [R | t], camera -> world.  The reference has no model and no such class. */
     class TSDFVolume
     {
     public:
@@ -362,6 +362,18 @@ namespace ICP
         /*! dw: voxels x 2 floats; rgb: voxels x 3 floats, nullptr for a volume without colour */
         void read (float *dw, float *rgb = nullptr) { check (icp_tsdf_read (t, dw, rgb)); }
         void write (const float *dw, const float *rgb = nullptr) { check (icp_tsdf_write (t, dw, rgb)); }
+        /*! the volume's surface as a point cloud (icp_tsdf_extract_surface): a counting call, then every member — `cloud` receives 8 floats
+         *  a point, `normals` (if given) 4 floats a point; returns the number of points */
+        uint32_t extractSurface (std::vector<float> &cloud, std::vector<float> *normals = nullptr, float min_weight = 1.f)
+        {
+            const icp_tsdf_surface_t o = { min_weight, normals ? 1u : 0u };
+            uint32_t n = 0;
+            check (icp_tsdf_extract_surface (t, &o, 0, nullptr, nullptr, &n));
+            cloud.resize ((size_t) n * 8);
+            if (normals) normals->resize ((size_t) n * 4);
+            if (n) check (icp_tsdf_extract_surface (t, &o, n, cloud.data (), normals ? normals->data () : nullptr, &n));
+            return n;
+        }
         /*! out12 = pose12 o (R (q), t) of the engine's T8; returns T8's scale */
         static float composePose (const float *pose12, const float *T8, float *out12)
         {

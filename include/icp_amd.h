@@ -1087,9 +1087,44 @@ int icp_tsdf_write (icp_tsdf_handle t, const float *dw, const float *rgb);
 /* Host only, computed in double and rounded once: out12 = pose12 o (R (q / |q|), t) of the engine's T8 = [q | t, s], the pose of the moving
  * frame of a registration whose fixed frame was ray-cast from pose12.  T's scale s is returned through `scale` (may be NULL), not applied. */
 int icp_tsdf_compose_pose (const float *pose12, const float *T8, float *out12, float *scale);
+/* Surface extraction: the model itself as a point cloud — the zero crossings of D on the edges of the voxel lattice (what Open3D's
+ * extract_point_cloud and KinFu's fetchCloudHost / fetchNormals give), compacted in order on the device.  The arithmetic is the volume's:
+ * fp32, each operation rounded on its own, IEEE divide and sqrt, dots as (a0 b0 + a1 b1) + a2 b2; tests/tsdf_surface_ref.py restates
+ * every value bit for bit.  The volume is never modified.
+ *    Usable.  Voxel v is USABLE iff W (v) >= min_weight and fabsf (D (v)) < 1.f (float comparisons: a NaN in either fails).  The second
+ *    test drops the crossings between a truncated free-space value and the back of another surface (Open3D's 0.98).  A fused D reaches
+ *    +-1 where the distance along the ray reaches mu, so both ends of a member lie within mu of the surface: choose mu well above the
+ *    voxel edge.  Where neighbouring voxels differ by 2 mu or more along the rays — a surface seen along an axis of a volume whose mu
+ *    is at most half its voxel edge — no edge has two usable ends and the volume yields nothing.
+ *    Edges.  Edge (v, a), a in {x, y, z} = {0, 1, 2}, joins voxel v = (i, j, k) to v + e_a; it exists only where v + e_a is inside the
+ *    volume.  With D0 = D (v), D1 = D (v + e_a) the edge is a MEMBER iff both ends are usable and (D0 > 0.f) != (D1 > 0.f): -0 and +0 both
+ *    count as "not positive".
+ *    Order.  Members are output in ascending 3 * ((k ny + j) nx + i) + a: a function of the volume alone.
+ *    Point.  t = D0 / (D0 - D1), in [0, 1] (-0 or +0 where D0 is a zero);  p_a = origin_a + ((float) idx_a + t) * voxel and
+ *    p_b = origin_b + (float) idx_b * voxel on the two other axes;  the record is [p_x p_y p_z 1 r g b 1] with the colour
+ *    C_ch (v) + t * (C_ch (v + e_a) - C_ch (v)), 0 without `colour`.
+ *    Normal (if wanted).  For a voxel u, G_b (u) = D (u + e_b) - D (u - e_b); it is KNOWN iff all six neighbours are inside the volume and
+ *    have W > 0 (nothing else is asked of a neighbour: truncated ones count).  G = G (v) + t * (G (v + e_a) - G (v)) per component,
+ *    len = sqrtf ((G_0^2 + G_1^2) + G_2^2).  The normal is [G / len, 0] iff both ends' gradients are known and len > 0 (NaN fails),
+ *    otherwise [0 0 0 0].  It points from inside to free space, where the ray cast's normals point.
+ *    A voxel with D exactly 0 and positive neighbours on both sides of an axis is the end of two members, whose points coincide
+ *    (t = 1 on one edge, t = -0 on the next): that is the rule, not a defect.
+ * opt == NULL: min_weight 1, no normals.  The call stores the number of members in *count (at most 3 * 2^30) and writes the first
+ * min (count, capacity) of them: cloud_out holds capacity x 8 floats, normals_out capacity x 4 floats (host pointers; normals_out is
+ * required iff opt->normals).  capacity 0 with NULL outputs is the counting call.  ICP_EINVAL for a NULL count, a min_weight that is not
+ * finite and >= 1, normals outside {0, 1}, a NULL output with capacity > 0; ICP_ENOMEM if the device cannot hold the scratch. */
+typedef struct {
+    float    min_weight;                    /* finite, >= 1 */
+    uint32_t normals;                       /* 0 or 1 */
+} icp_tsdf_surface_t;
+int icp_tsdf_extract_surface (icp_tsdf_handle t, const icp_tsdf_surface_t *opt, uint32_t capacity, void *cloud_out, float *normals_out, uint32_t *count);
 /* Diagnostic (tools/diag/tsdf_time.py): `reps` launches of one kernel between two events on the volume's stream, after one untimed launch.
  * what = 0: k_tsdf_integrate of (depth, rgb) at pose12 — the volume is left as reps + 1 integrations leave it;  what = 1: k_tsdf_raycast as
- * icp_tsdf_raycast (cam, pose12, z_near, z_far, side) runs it, into scratch (depth, rgb unused).  Microseconds per launch. */
+ * icp_tsdf_raycast (cam, pose12, z_near, z_far, side) runs it, into scratch (depth, rgb unused);  what = 2: the launches of one
+ * icp_tsdf_extract_surface with normals and min_weight 1 as a group, every member into scratch;  what = 3: the two scan launches of
+ * that group alone;  what = 4: its last two launches (the members' edges, their records) alone (for 2 .. 4 every argument but reps is unused, cam and
+ * pose12 may be NULL).
+ * Microseconds per launch (per group). */
 int icp_tsdf_time (icp_tsdf_handle t, int what, const icp_rgbd_t *cam, const float *pose12, const uint16_t *depth, const uint8_t *rgb, float z_near, float z_far,
                    uint32_t side, uint32_t reps, float *us_per_launch);
 

@@ -5,8 +5,14 @@
     (6.29 TB/s measured with a float4 copy; 8.0 TB/s is the specification);
   - k_tsdf_raycast dense at 640 x 480 and on the 128 x 128 lattice, with normals, on the 256^3 volume; beside the lattice form a blocking
     icp_write_rgbd (what makes the same landmarks of a frame) and the search stage of an iteration (icp_time_kernels) from the same run;
-  - the end-to-end errors of tests/test_gpu_tsdf.py::test_frame_to_model_end_to_end (frame-to-model against its frame-to-frame twin).
-    python tools/diag/tsdf_time.py [--reps N] [--skip-512]"""
+  - the end-to-end errors of tests/test_gpu_tsdf.py::test_frame_to_model_end_to_end (frame-to-model against its frame-to-frame twin);
+  - with --surface (and nothing else then): the surface extraction of the corner scene of tests/tsdf_ref.py — six 640 x 480 frames fused
+    into 256^3 and 512^3 voxels over the scene's 1.02 m cube, mu = 3 voxel edges —: the launches of one extraction as a group
+    (icp_tsdf_time, what = 2) against one read of the volume's {D, W} at the HBM rate, the two scan launches (what = 3) and the
+    scatter and points launches (what = 4) alone, the
+    blocking calls with the copy to the host, and what they replace: a blocking icp_tsdf_read plus the numpy restatement on the host
+    (the restatement at 256^3 only: at 512^3 its temporaries do not fit a workstation's memory).
+    python tools/diag/tsdf_time.py [--reps N] [--skip-512] [--surface]"""
 import argparse
 import os
 import statistics
@@ -38,11 +44,63 @@ def median(call, reps):
     return statistics.median(call() for _ in range(reps))
 
 
+def blocking(call, reps):
+    call(); call()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter(); call(); t.append((time.perf_counter() - t0) * 1e6)
+    return statistics.median(t)
+
+
+def surface(a):
+    sys.path[:0] = [os.path.join(ROOT, "tests")]
+    import tsdf_ref as T                # noqa: E402
+    import tsdf_surface_ref as S        # noqa: E402
+    d = T.corner_camera(width=640, height=480, fx=600.0, cx=319.5, cy=239.5)
+    cam = rgbd.RGBDConfig(**d)
+    frames = [(T.look_at(eye).reshape(12).astype(np.float32),) + T.render_corner(T.look_at(eye), d)[:2] for eye in T.EYES]
+    for n in (256,) if a.skip_512 else (256, 512):
+        voxel = 1024.0 / n
+        v = tsdf.TSDFVolume(tsdf.TSDFConfig(n, n, n, voxel, (-64.0, -64.0, -64.0), 3.0 * voxel, 64.0, 1))
+        for pose, depth, colour in frames:
+            v.integrate(cam, pose, depth, colour)
+        floor = n ** 3 * 8 / HBM_MEASURED * 1e6
+        cloud, nrm, count = v.extract_surface(capacity=0)
+        group = median(lambda: v.time_kernel(2, reps=20), a.reps)
+        scan = median(lambda: v.time_kernel(3, reps=20), a.reps)
+        scatter = median(lambda: v.time_kernel(4, reps=20), a.reps)
+        print("surface %d^3: %d points (%.2f %% of %d edges), %d blocks of the sweep" % (n, count, 100.0 * count / (3 * n * n * (n - 1)), 3 * n * n * (n - 1), n ** 3 // 1024), flush=True)
+        print("surface %d^3 launches of one extraction %9.2f us   one read of {D, W} at 6.29 TB/s %7.2f us: ratio %.2f" % (n, group, floor, group / floor), flush=True)
+        print("surface %d^3 the two scan launches      %9.2f us   %.1f %% of the extraction" % (n, scan, 100.0 * scan / group), flush=True)
+        print("surface %d^3 scatter and points alone   %9.2f us   (the sweep: the rest, %.2f us = %.2f of the read)" % (n, scatter, group - scan - scatter, (group - scan - scatter) / floor), flush=True)
+        one = blocking(lambda: v.extract_surface(capacity=count), a.reps)
+        two = blocking(lambda: v.extract_surface(), a.reps)
+        cnt = blocking(lambda: v.extract_surface(capacity=0), a.reps)
+        print("surface %d^3 blocking extract_surface   %9.2f us with the capacity given, %9.2f us with the counting call first, %9.2f us the counting call alone  (%.1f MB to the host)"
+              % (n, one, two, cnt, count * 48 / 1e6), flush=True)
+        t0 = time.perf_counter(); dw, col = v.read(); t_read = time.perf_counter() - t0
+        print("surface %d^3 blocking icp_tsdf_read     %9.2f ms  (%.0f MB of {D, W}, %.0f MB of colour)" % (n, t_read * 1e3, dw.nbytes / 1e6, col.nbytes / 1e6), flush=True)
+        if n == 256:
+            ref = T.Volume(v.get_config().as_dict())
+            ref.dw, ref.rgb = dw, col
+            t0 = time.perf_counter(); want = S.extract(ref); t_host = time.perf_counter() - t0
+            got = v.extract_surface()
+            same = all(np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(got, want))
+            print("surface %d^3 the numpy restatement on the host %9.2f ms  (%d points, %s the device's bit for bit)" % (n, t_host * 1e3, want[0].shape[0], "equal to" if same else "DIFFERENT FROM"), flush=True)
+        else:
+            print("surface %d^3 the numpy restatement on the host: not measured" % n, flush=True)
+        del dw, col
+        v.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--skip-512", action="store_true")
+    ap.add_argument("--surface", action="store_true")
     a = ap.parse_args()
+    if a.surface:
+        return surface(a)
     depth, colour = frame()
     cam = rgbd.RGBDConfig()
     print("frame: %d of %d pixels valid, depth %d .. %d" % ((depth != 0).sum(), depth.size, depth[depth != 0].min(), depth.max()), flush=True)
