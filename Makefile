@@ -42,6 +42,9 @@ tsdf_facade_test: $(LIB) tests/cpp/tsdf_facade_test.cpp include/ICP/algorithms.h
 tsdf_surface_facade_test: $(LIB) tests/cpp/tsdf_surface_facade_test.cpp include/ICP/algorithms.hpp
 	g++ -O2 -std=c++17 -Wall -ffp-contract=off -Iinclude -o tests/cpp/tsdf_surface_facade_test tests/cpp/tsdf_surface_facade_test.cpp -Licp_amd -licp_amd -Wl,-rpath,'$$ORIGIN/../../icp_amd'
 
+tsdf_mesh_facade_test: $(LIB) tests/cpp/tsdf_mesh_facade_test.cpp include/ICP/algorithms.hpp
+	g++ -O2 -std=c++17 -Wall -ffp-contract=off -Iinclude -o tests/cpp/tsdf_mesh_facade_test tests/cpp/tsdf_mesh_facade_test.cpp -Licp_amd -licp_amd -Wl,-rpath,'$$ORIGIN/../../icp_amd'
+
 icpreg_test: $(LIB) tests/cpp/icpreg_test.cpp include/ocl_icp_reg.hpp include/ocl_icp_sbs.hpp include/ICP/algorithms.hpp
 	g++ -O2 -std=c++17 -Iinclude -o tests/cpp/icpreg_test tests/cpp/icpreg_test.cpp -Licp_amd -licp_amd -Wl,-rpath,'$$ORIGIN/../../icp_amd'
 
@@ -92,7 +95,7 @@ asan: tests/cpp/asan_host
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=0 UBSAN_OPTIONS=print_stacktrace=1 tests/cpp/asan_host
 
 clean:
-	rm -rf build; rm -f $(LIB) examples/registration examples/step_by_step tests/cpp/facade_test tests/cpp/pyramid_facade_test tests/cpp/pairs_facade_test tests/cpp/rgbd_facade_test tests/cpp/tsdf_facade_test tests/cpp/tsdf_surface_facade_test tests/cpp/capi_example tests/cpp/icpreg_test tests/cpp/asan_host tests/cpp/asan_oracle.o tests/cpp/search_select_test tests/cpp/rbc_set_test tests/cpp/mom_layout_test
+	rm -rf build; rm -f $(LIB) examples/registration examples/step_by_step tests/cpp/facade_test tests/cpp/pyramid_facade_test tests/cpp/pairs_facade_test tests/cpp/rgbd_facade_test tests/cpp/tsdf_facade_test tests/cpp/tsdf_surface_facade_test tests/cpp/tsdf_mesh_facade_test tests/cpp/capi_example tests/cpp/icpreg_test tests/cpp/asan_host tests/cpp/asan_oracle.o tests/cpp/search_select_test tests/cpp/rbc_set_test tests/cpp/mom_layout_test
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean asan examples search_select_test rbc_set_test mom_layout_test

@@ -1,6 +1,6 @@
 // icp_tsdf.h — what icp_tsdf.hip (the volume, its two kernels and its C entries) shares with icp_capi.hip, which owns the one entry
-// that needs the inside of an icp_context (icp_tsdf_raycast_to), and with icp_tsdf_surface.hip (icp_tsdf_extract_surface): the volume's
-// handle, the arguments of a ray cast and its launcher, the scratch of a call.
+// that needs the inside of an icp_context (icp_tsdf_raycast_to), and with icp_tsdf_surface.hip (icp_tsdf_extract_surface,
+// icp_tsdf_extract_mesh): the volume's handle, the arguments of a ray cast and its launcher, the scratch of a call.
 #pragma once
 #include "../../include/icp_amd.h"
 #include "icp_rgbd.h"
@@ -38,6 +38,10 @@ struct icp_tsdf_context {
     // and the edges of its members in order
     void *dSurf = nullptr, *dEdge = nullptr;
     size_t surf_cap = 0, edge_cap = 0;
+    // the words of a mesh extraction's cell sweep (case bytes, wave counts, block counts and their scan), its triangles, and the case
+    // table (256 words, uploaded by the first mesh extraction)
+    void *dMesh = nullptr, *dTri = nullptr, *dMeshTab = nullptr;
+    size_t mesh_cap = 0, tri_cap = 0;
     std::string err;
 };
 
@@ -52,6 +56,8 @@ int tsdf_reserve (icp_tsdf_context *t, void **q, size_t *cap, size_t bytes);
 // icp_tsdf_time, what = 2 .. 4: `reps` extractions' launches (normals on, min_weight 1) between the volume's two events, after an untimed
 // extraction — part 0: all of them, 1: the two scan launches alone, 2: the scatter and the points alone
 int tsdf_time_surface (icp_tsdf_context *t, int part, uint32_t reps, float *us_per_group);
+// icp_tsdf_time, what = 5 .. 7: the same for a mesh extraction — part 0: all of its launches, 1: the cell sweep alone, 2: the triangle pass alone
+int tsdf_time_mesh (icp_tsdf_context *t, int part, uint32_t reps, float *us_per_group);
 }
 
 #define TSDFCHK(t, expr)                                                                                       \

@@ -315,7 +315,7 @@ int icp_tsdf_destroy (icp_tsdf_handle t) try
     if (!t) return ICP_EINVAL;
     (void) hipSetDevice (t->device);
     if (t->stream) (void) hipStreamSynchronize (t->stream);
-    for (void *q : { (void *) t->v.dw, (void *) t->v.col, t->dDepth, t->dRgb, t->dOut, t->dNrm, t->dSurf, t->dEdge }) if (q) (void) hipFree (q);
+    for (void *q : { (void *) t->v.dw, (void *) t->v.col, t->dDepth, t->dRgb, t->dOut, t->dNrm, t->dSurf, t->dEdge, t->dMesh, t->dTri, t->dMeshTab }) if (q) (void) hipFree (q);
     if (t->ev0) (void) hipEventDestroy (t->ev0);
     if (t->ev1) (void) hipEventDestroy (t->ev1);
     if (t->stream) (void) hipStreamDestroy (t->stream);
@@ -456,7 +456,8 @@ int icp_tsdf_time (icp_tsdf_handle t, int what, const icp_rgbd_t *cam, const flo
                            uint32_t side, uint32_t reps, float *us_per_launch) try
 {
     if (!t) return ICP_EINVAL;
-    if (!us_per_launch || reps == 0u || what < 0 || what > 4) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_time: bad arguments");
+    if (!us_per_launch || reps == 0u || what < 0 || what > 7) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_time: bad arguments");
+    if (what >= 5) return tsdf_time_mesh (t, what - 5, reps, us_per_launch);
     if (what >= 2) return tsdf_time_surface (t, what - 2, reps, us_per_launch);
     tsdf_integrate_args ia {};
     icp_tsdf_cast_args ca {};

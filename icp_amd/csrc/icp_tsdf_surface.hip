@@ -29,6 +29,15 @@
 // Nothing waits for another workgroup inside a launch: the order between the passes is the stream's.  The counts are integer sums and a
 // position is a function of the predicate alone: no atomics, and the result does not depend on the launch shape.
 //
+// The mesh (icp_tsdf_extract_mesh; the rule: include/icp_amd.h, "Mesh extraction"; tests/tsdf_mesh_ref.py restates it) has the members as its
+// vertices and adds a second compaction of the same form, of up to five triangles per cell, queued after the member sweep and its scan:
+//   k_tsdf_mesh_count       the sweep over cells, lane = voxel = the cell's corner 0.  It stores 16 bits a wave and step (up to 320
+//                           triangles) and, for a step with triangles, the lanes' case bytes; the block stores its sum (at most 5120).
+//   k_tsdf_scan_tiles       as above, over the triangle block counts.  One synchronisation then reads both counts.
+//   k_tsdf_mesh_triangles   a lane per cell: a cell's local edge becomes its vertex index by the scatter's formula read from the member
+//                           sweep's tables (no dense edge-to-index volume), and the triples are stored in order.
+// The case table (256 words: a 4-bit count, fifteen 4-bit edge ids) is generated on the host by its rule and read from device memory.
+//
 // -ffp-contract=off keeps every operation on its own; `/` and sqrtf are the correctly rounded ones.
 #include "icp_tsdf.h"
 #include "icp_cguard.h"
@@ -212,6 +221,144 @@ __global__ __launch_bounds__ (BLOCK) void k_tsdf_surface_points (tsdf_surface_ar
     else emit<2> (a, g, i, j, k, pos);
 }
 
+// ---- the mesh: a second ordered compaction, of triangles per cell ---------------------------------------------------------------------------
+
+constexpr uint32_t CELL_OK = 0x100u;                       // beside a lane's four sign bits: its corners 0, 2, 4, 6 are all usable
+
+struct tsdf_mesh_args {
+    tsdf_surface_args m;                                   // the volume and what the member sweep and its scan left
+    const mask64 *table;                                   // [256]: a 4-bit triangle count, then fifteen 4-bit local edge ids
+    // what the cell sweep leaves: [nblk][WAVES] pairs of words, 16 bits a step = the triangles of wave w in step s (at most 320);
+    // [nblk][WAVES][STEPS][64] case bytes (0 for an inactive cell), written for the steps whose count is not 0;  [nblk] sums
+    uint2 *wave_cnt; uint8_t *cases; uint32_t *blk_cnt;
+    const uint32_t *blk_off, *tile_off;                    // the scan of the sums
+    uint32_t limit;                                        // min (count, capacity): triangles below it are written
+    uint32_t *tri;                                         // [limit][3]
+};
+
+// The sweep over cells in the member sweep's layout: lane = the cell's corner 0.  A lane fetches corners 2, 4 and 6 (+y, +z, +y +z) only
+// where its own voxel is usable, and takes corners 1, 3, 5, 7 from the next lane, which fetched them as its own 0, 2, 4, 6 (the next
+// lane is in the same row wherever the cell exists); only the wave's last lane loads them.  A lane's triangle count has three bits: three
+// ballots give the wave's sum.
+__global__ __launch_bounds__ (BLOCK) void k_tsdf_mesh_count (tsdf_mesh_args a)
+{
+    __shared__ uint32_t s_wave[WAVES];
+    const icp_tsdf_dev &v = a.m.v;
+    const float min_weight = a.m.min_weight;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, g0 = blockIdx.x * RUN + tid, n_vox = a.m.n_vox;
+    float2 own[STEPS];
+#pragma unroll
+    for (uint32_t s = 0; s < STEPS; ++s) own[s] = v.dw[min (g0 + s * BLOCK, n_vox - 1u)];
+    const uint32_t sy = v.nx, sz = v.nx * v.ny;
+    uint32_t c = 0u, lo = 0u, hi = 0u;
+#pragma unroll
+    for (uint32_t s = 0; s < STEPS; ++s) {
+        const uint32_t g = g0 + s * BLOCK;
+        uint32_t mine = 0u;                                // CELL_OK | the signs of corners 0, 2, 4, 6 at their bits
+        bool has_x = false;
+        if (g < n_vox && usable (own[s], min_weight)) {
+            const uint32_t row = g / v.nx, i = g - row * v.nx, k = row / v.ny, j = row - k * v.ny;
+            has_x = i + 1u < v.nx;
+            if (j + 1u < v.ny && k + 1u < v.nz) {          // (g + sz + sy <= n_vox - 1)
+                const float2 e2 = v.dw[g + sy], e4 = v.dw[g + sz], e6 = v.dw[g + sz + sy];
+                if (usable (e2, min_weight) && usable (e4, min_weight) && usable (e6, min_weight))
+                    mine = CELL_OK | (uint32_t) (own[s].x > 0.f) | (uint32_t) (e2.x > 0.f) << 2 | (uint32_t) (e4.x > 0.f) << 4 | (uint32_t) (e6.x > 0.f) << 6;
+            }
+        }
+        uint32_t next = __shfl_down (mine, 1u, 64);
+        if (lane == 63u) {
+            next = 0u;
+            if (mine && has_x) {                           // (g + 1 + sz + sy <= n_vox - 1: the cell exists)
+                const float2 e1 = v.dw[g + 1u], e3 = v.dw[g + 1u + sy], e5 = v.dw[g + 1u + sz], e7 = v.dw[g + 1u + sz + sy];
+                if (usable (e1, min_weight) && usable (e3, min_weight) && usable (e5, min_weight) && usable (e7, min_weight))
+                    next = CELL_OK | (uint32_t) (e1.x > 0.f) | (uint32_t) (e3.x > 0.f) << 2 | (uint32_t) (e5.x > 0.f) << 4 | (uint32_t) (e7.x > 0.f) << 6;
+            }
+        }
+        const bool active = mine && has_x && next;
+        const uint32_t cs = active ? (mine & 0x55u) | (next & 0x55u) << 1 : 0u;
+        const uint32_t n = active ? (uint32_t) (a.table[cs] & 15ull) : 0u;
+        const mask64 b0 = __ballot (n & 1u), b1 = __ballot (n & 2u), b2 = __ballot (n & 4u);
+        const uint32_t tot = (uint32_t) (__popcll (b0) + 2 * __popcll (b1) + 4 * __popcll (b2));
+        c += tot;
+        if (s < 2u) lo |= tot << (16u * s); else hi |= tot << (16u * (s - 2u));
+        if (tot) a.cases[((size_t) (blockIdx.x * WAVES + wave) * STEPS + s) * 64u + lane] = (uint8_t) cs;
+    }
+    if (lane == 0u) { s_wave[wave] = c; a.wave_cnt[blockIdx.x * WAVES + wave] = make_uint2 (lo, hi); }
+    __syncthreads ();
+    if (tid == 0u) a.blk_cnt[blockIdx.x] = (s_wave[0] + s_wave[1]) + (s_wave[2] + s_wave[3]);
+}
+
+__device__ __forceinline__ uint32_t step16 (uint2 w, uint32_t s) { return ((s < 2u ? w.x : w.y) >> (16u * (s & 1u))) & 0xFFFFu; }
+
+// the position of the first member of voxel gv in the member order, by the scatter's formula, and whether (gv, x) and (gv, y) are members
+__device__ __forceinline__ uint32_t first_member (const tsdf_surface_args &m, uint32_t gv, bool *m0, bool *m1)
+{
+    const uint32_t blk = gv / RUN, s = (gv / BLOCK) & (STEPS - 1u), w = (gv >> 6) & (WAVES - 1u), l = gv & 63u;
+    const uint4 wc = reinterpret_cast<const uint4 *> (m.wave_cnt)[blk];
+    uint32_t pos = m.tile_off[blk / SCAN_TILE] + m.blk_off[blk];
+    const mask64 *mk = m.masks + ((size_t) (blk * WAVES + w) * STEPS + s) * 3u;
+    const mask64 b0 = mk[0], b1 = mk[1], b2 = mk[2];       // (written: the voxel has a member in this step)
+#pragma unroll
+    for (uint32_t q = 0; q < STEPS; ++q) {
+        const uint32_t c0 = (wc.x >> (8u * q)) & 255u, c1 = (wc.y >> (8u * q)) & 255u, c2 = (wc.z >> (8u * q)) & 255u, c3 = (wc.w >> (8u * q)) & 255u;
+        if (q < s) pos += (c0 + c1) + (c2 + c3);
+        else if (q == s) pos += (w > 0u ? c0 : 0u) + (w > 1u ? c1 : 0u) + (w > 2u ? c2 : 0u);
+    }
+    const mask64 below = (1ull << l) - 1ull;
+    pos += (uint32_t) (__popcll (b0 & below) + __popcll (b1 & below) + __popcll (b2 & below));
+    *m0 = (b0 >> l) & 1ull; *m1 = (b1 >> l) & 1ull;
+    return pos;
+}
+
+// One block per block of the cell sweep, which judges nothing again: lane = cell.  The triangles of a cell go to
+//     (tile offset + offset inside the tile) + (triangles of the steps and waves in front) + (triangles below the lane: three mbcnt)
+// in table order.  A local edge 4 a + m is the lattice edge (corner voxel, a): its vertex index is that member's position, taken from the
+// member sweep's own tables.  A lane keeps its up to twelve indices in LDS words of its own (no barrier), so that a triangle's edge id can
+// index them.
+__global__ __launch_bounds__ (BLOCK) void k_tsdf_mesh_triangles (tsdf_mesh_args a)
+{
+    __shared__ uint32_t s_idx[12][BLOCK];
+    const uint32_t blk = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint4 wa = reinterpret_cast<const uint4 *> (a.wave_cnt)[2u * blk], wb = reinterpret_cast<const uint4 *> (a.wave_cnt)[2u * blk + 1u];
+    uint32_t front = a.tile_off[blk / SCAN_TILE] + a.blk_off[blk];
+    const uint2 w0 = make_uint2 (wa.x, wa.y), w1 = make_uint2 (wa.z, wa.w), w2 = make_uint2 (wb.x, wb.y), w3 = make_uint2 (wb.z, wb.w);
+    const uint2 mine = wave == 0u ? w0 : wave == 1u ? w1 : wave == 2u ? w2 : w3;
+    if ((mine.x | mine.y) == 0u || front >= a.limit) return;                                // (wave-uniform)
+    const uint32_t sy = a.m.v.nx, sz = a.m.v.nx * a.m.v.ny;
+#pragma unroll
+    for (uint32_t s = 0; s < STEPS; ++s) {
+        const uint32_t c0 = step16 (w0, s), c1 = step16 (w1, s), c2 = step16 (w2, s), c3 = step16 (w3, s);
+        const uint32_t first = front + (wave > 0u ? c0 : 0u) + (wave > 1u ? c1 : 0u) + (wave > 2u ? c2 : 0u);
+        front += (c0 + c1) + (c2 + c3);
+        if (step16 (mine, s) == 0u) continue;
+        if (first >= a.limit) break;
+        const uint32_t cs = a.cases[((size_t) (blk * WAVES + wave) * STEPS + s) * 64u + lane];
+        const mask64 word = a.table[cs];
+        const uint32_t n = (uint32_t) (word & 15ull);
+        const mask64 b0 = __ballot (n & 1u), b1 = __ballot (n & 2u), b2 = __ballot (n & 4u);
+        const uint32_t pos = first + below_lane (b0, 0u) + 2u * below_lane (b1, 0u) + 4u * below_lane (b2, 0u);
+        if (n == 0u || pos >= a.limit) continue;
+        const uint32_t g = blk * RUN + s * BLOCK + wave * 64u + lane;
+#pragma unroll
+        for (uint32_t c = 0; c < 7u; ++c) {                // the corners that are the low end of a cell edge
+            const uint32_t ends = (cs >> c) & 1u;
+            const bool x0 = !(c & 1u) && ((cs >> (c | 1u)) & 1u) != ends, x1 = !(c & 2u) && ((cs >> (c | 2u)) & 1u) != ends, x2 = !(c & 4u) && ((cs >> (c | 4u)) & 1u) != ends;
+            if (!(x0 || x1 || x2)) continue;
+            bool m0, m1;
+            const uint32_t at = first_member (a.m, g + (c & 1u) + ((c >> 1) & 1u) * sy + (c >> 2) * sz, &m0, &m1);
+            // local edge 4 a + m, m = bit_b1 + 2 bit_b2 of the corner
+            if (!(c & 1u)) s_idx[((c >> 1) & 1u) + 2u * (c >> 2)][tid] = at;
+            if (!(c & 2u)) s_idx[4u + (c & 1u) + 2u * (c >> 2)][tid] = at + (m0 ? 1u : 0u);
+            if (!(c & 4u)) s_idx[8u + (c & 1u) + 2u * ((c >> 1) & 1u)][tid] = at + (m0 ? 1u : 0u) + (m1 ? 1u : 0u);
+        }
+        for (uint32_t t = 0; t < n && pos + t < a.limit; ++t) {
+            uint32_t *out = a.tri + 3u * (size_t) (pos + t);
+#pragma unroll
+            for (uint32_t q = 0; q < 3u; ++q) out[q] = s_idx[(uint32_t) (word >> (4u + 4u * (3u * t + q))) & 15u][tid];
+        }
+    }
+}
+
 // The words of an extraction in the volume's scratch: the sweep's ballots (384 bytes a block of 8 KiB of {D, W}), its wave counts, its block
 // counts; the blocks' offsets inside their tiles, the tile sums, the tile offsets, the count.  (The members' edges, like their records, are
 // scratch of their own, sized by the count.)
@@ -263,6 +410,18 @@ void launch_scatter (const tsdf_surface_args &a, const surface_plan &p, hipStrea
     hipLaunchKernelGGL (k_tsdf_surface_points, dim3 ((a.limit + BLOCK - 1u) / BLOCK), dim3 (BLOCK), 0, s, a);
 }
 
+// the output scratch of the first a.limit members
+int reserve_records (icp_tsdf_context *t, tsdf_surface_args &a, bool normals)
+{
+    if (a.limit == 0u) return ICP_OK;
+    int rc;
+    if ((rc = icp_host::tsdf_reserve (t, &t->dEdge, &t->edge_cap, (size_t) a.limit * 4u))) return rc;
+    if ((rc = icp_host::tsdf_reserve (t, &t->dOut, &t->out_cap, (size_t) a.limit * 32u))) return rc;
+    if (normals && (rc = icp_host::tsdf_reserve (t, &t->dNrm, &t->nrm_cap, (size_t) a.limit * 16u))) return rc;
+    a.edge = static_cast<uint32_t *> (t->dEdge); a.out = static_cast<float4 *> (t->dOut); a.nrm = normals ? static_cast<float4 *> (t->dNrm) : nullptr;
+    return ICP_OK;
+}
+
 // the count of the volume's members on the host, and the output scratch for the first min (count, capacity) of them
 int count_and_reserve (icp_tsdf_context *t, tsdf_surface_args &a, const surface_plan &p, uint32_t capacity, bool normals, uint32_t *total)
 {
@@ -271,12 +430,176 @@ int count_and_reserve (icp_tsdf_context *t, tsdf_surface_args &a, const surface_
     TSDFCHK (t, hipMemcpyAsync (total, p.count, sizeof (uint32_t), hipMemcpyDeviceToHost, t->stream));
     TSDFCHK (t, hipStreamSynchronize (t->stream));
     a.limit = std::min (*total, capacity);
+    return reserve_records (t, a, normals);
+}
+
+// ---- the mesh's host side --------------------------------------------------------------------------------------------------------------------
+
+// The case table by its rule (include/icp_amd.h, "Mesh extraction": the case table; tests/tsdf_mesh_ref.py generates it again).
+struct mesh_table { mask64 word[256]; };
+
+void edge_ends (int e, int *c0, int *c1)
+{
+    const int a = e >> 2, m = e & 3, b1 = a == 0 ? 1 : 0, b2 = a == 2 ? 1 : 2;
+    *c0 = ((m & 1) << b1) | ((m >> 1) << b2); *c1 = *c0 | (1 << a);
+}
+
+// the two faces 2 f + side of an edge as a mask of six bits
+int edge_faces (int e)
+{
+    const int a = e >> 2, m = e & 3, b1 = a == 0 ? 1 : 0, b2 = a == 2 ? 1 : 2;
+    return 1 << (2 * b1 + (m & 1)) | 1 << (2 * b2 + (m >> 1));
+}
+
+mesh_table make_mesh_table ()
+{
+    mesh_table T {};
+    for (int cs = 0; cs < 256; ++cs) {
+        int nb[12][2], nnb[12] = {}, c0, c1;
+        bool cross[12];
+        for (int e = 0; e < 12; ++e) { edge_ends (e, &c0, &c1); cross[e] = ((cs >> c0) ^ (cs >> c1)) & 1; }
+        auto join = [&] (int x, int y) { nb[x][nnb[x]++] = y; nb[y][nnb[y]++] = x; };
+        for (int face = 0; face < 6; ++face) {            // rule 2: the segments of a face
+            int on[4], n_on = 0;
+            for (int e = 0; e < 12; ++e) if (cross[e] && (edge_faces (e) >> face & 1)) on[n_on++] = e;
+            if (n_on == 2) join (on[0], on[1]);
+            if (n_on != 4) continue;
+            for (int c = 0; c < 8; ++c) {                  // a positive corner of the face is cut off singly
+                if (((c >> (face >> 1)) & 1) != (face & 1) || !((cs >> c) & 1)) continue;
+                int pair[2], n_pair = 0;
+                for (int q = 0; q < 4; ++q) { edge_ends (on[q], &c0, &c1); if (c0 == c || c1 == c) pair[n_pair++] = on[q]; }
+                join (pair[0], pair[1]);
+            }
+        }
+        mask64 word = 0ull;
+        uint32_t n_tri = 0u;
+        bool used[12] = {};
+        for (int e0 = 0; e0 < 12; ++e0) {                  // rule 3: loops in ascending order of their smallest edge
+            if (!cross[e0] || used[e0]) continue;
+            int r[12], n = 0, prev = -1, cur = e0;
+            r[n++] = e0;
+            for (;;) {
+                const int nxt = prev >= 0 && nb[cur][0] == prev ? nb[cur][1] : nb[cur][0];
+                if (nxt == e0) break;
+                prev = cur; cur = nxt; r[n++] = nxt;
+            }
+            // rule 4, in doubled coordinates: sum of P_i x P_i+1 against the sum of the edges' directions toward the positive end
+            int area[3] = {}, up[3] = {}, P[12][3];
+            for (int i = 0; i < n; ++i) {
+                used[r[i]] = true;
+                edge_ends (r[i], &c0, &c1);
+                for (int b = 0; b < 3; ++b) P[i][b] = 2 * ((c0 >> b) & 1);
+                P[i][r[i] >> 2] = 1;
+                up[r[i] >> 2] += (cs >> c0) & 1 ? -1 : 1;
+            }
+            for (int i = 0; i < n; ++i) {
+                const int *p = P[i], *q = P[(i + 1) % n];
+                area[0] += p[1] * q[2] - p[2] * q[1]; area[1] += p[2] * q[0] - p[0] * q[2]; area[2] += p[0] * q[1] - p[1] * q[0];
+            }
+            if (area[0] * up[0] + area[1] * up[1] + area[2] * up[2] < 0) std::reverse (r + 1, r + n);
+            int s = 0;                                     // rule 5: the first apex none of whose fan diagonals lies in a face
+            for (; s < n; ++s) {
+                bool ok = true;
+                for (int i = 2; i + 1 < n; ++i) ok = ok && !(edge_faces (r[s]) & edge_faces (r[(s + i) % n]));
+                if (ok) break;
+            }
+            for (int i = 1; i + 1 < n; ++i) {
+                const int tri[3] = { r[s % n], r[(s + i) % n], r[(s + i + 1) % n] };
+                for (int q = 0; q < 3; ++q) word |= (mask64) tri[q] << (4u + 4u * (3u * n_tri + q));
+                ++n_tri;
+            }
+        }
+        T.word[cs] = word | n_tri;
+    }
+    return T;
+}
+
+const mesh_table &mesh_cases () { static const mesh_table T = make_mesh_table (); return T; }
+
+// The words of a mesh extraction's cell sweep in scratch of their own: a case byte per voxel, the wave counts, the block counts; their
+// offsets inside their tiles, the tile sums, the tile offsets, the count.
+struct mesh_plan {
+    uint8_t *cases; uint2 *wave_cnt;
+    uint32_t *blk_cnt, *blk_off, *tile_sum, *tile_off, *count;
+};
+
+int plan_mesh (icp_tsdf_context *t, const surface_plan &p, mesh_plan *q)
+{
+    if (!t->dMeshTab) {
+        void *tab = nullptr;
+        if (hipMalloc (&tab, sizeof (mesh_table)) != hipSuccess) { (void) hipGetLastError (); return icp_host::tsdf_fail (t, ICP_ENOMEM, "icp_tsdf_extract_mesh: the device cannot hold the case table"); }
+        const hipError_t e = hipMemcpy (tab, mesh_cases ().word, sizeof (mesh_table), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void) hipFree (tab); return icp_host::tsdf_fail (t, ICP_EHIP, std::string ("icp_tsdf_extract_mesh: the case table: ") + hipGetErrorString (e)); }
+        t->dMeshTab = tab;
+    }
+    const size_t units = (size_t) p.nblk * WAVES, words = 2u * (size_t) p.nblk + 2u * p.ntile + 1u;
+    int rc = icp_host::tsdf_reserve (t, &t->dMesh, &t->mesh_cap, units * STEPS * 64u + units * sizeof (uint2) + words * sizeof (uint32_t)); if (rc) return rc;
+    q->cases = static_cast<uint8_t *> (t->dMesh);
+    q->wave_cnt = reinterpret_cast<uint2 *> (q->cases + units * STEPS * 64u);                 // (16-byte aligned: a block's case bytes are 1024)
+    q->blk_cnt = reinterpret_cast<uint32_t *> (q->wave_cnt + units); q->blk_off = q->blk_cnt + p.nblk;
+    q->tile_sum = q->blk_off + p.nblk; q->tile_off = q->tile_sum + p.ntile; q->count = q->tile_off + p.ntile;
+    return ICP_OK;
+}
+
+tsdf_mesh_args mesh_args_of (const icp_tsdf_context *t, const tsdf_surface_args &m, const mesh_plan &q)
+{
+    tsdf_mesh_args a {};
+    a.m = m; a.table = static_cast<const mask64 *> (t->dMeshTab);
+    a.wave_cnt = q.wave_cnt; a.cases = q.cases; a.blk_cnt = q.blk_cnt; a.blk_off = q.blk_off; a.tile_off = q.tile_off;
+    return a;
+}
+
+// the triangle count and the position of every block's first triangle
+void launch_cells (const tsdf_mesh_args &a, const surface_plan &p, hipStream_t s)
+{
+    hipLaunchKernelGGL (k_tsdf_mesh_count, dim3 (p.nblk), dim3 (BLOCK), 0, s, a);
+}
+
+void launch_mesh_scan (const surface_plan &p, const mesh_plan &q, hipStream_t s)
+{
+    hipLaunchKernelGGL (k_tsdf_scan_tiles, dim3 (p.ntile), dim3 (BLOCK), 0, s, (const uint32_t *) q.blk_cnt, p.nblk, q.blk_off, q.tile_sum);
+    hipLaunchKernelGGL (k_tsdf_scan_tiles, dim3 (1), dim3 (BLOCK), 0, s, (const uint32_t *) q.tile_sum, p.ntile, q.tile_off, q.count);
+}
+
+void launch_triangles (const tsdf_mesh_args &a, const surface_plan &p, hipStream_t s)
+{
+    hipLaunchKernelGGL (k_tsdf_mesh_triangles, dim3 (p.nblk), dim3 (BLOCK), 0, s, a);
+}
+
+// Both sweeps and their scans, both counts on the host in one round trip, and the output scratch for the first min (count, capacity) of
+// each kind.  a.m.limit and a.limit are set.
+int count_mesh_and_reserve (icp_tsdf_context *t, tsdf_mesh_args &a, const surface_plan &p, const mesh_plan &q, uint32_t vertex_capacity, bool normals,
+                            uint32_t triangle_capacity, uint32_t *vertices, uint32_t *triangles)
+{
+    launch_count_and_scan (a.m, p, t->stream);
+    launch_cells (a, p, t->stream);
+    launch_mesh_scan (p, q, t->stream);
+    TSDFCHK (t, hipGetLastError ());
+    TSDFCHK (t, hipMemcpyAsync (vertices, p.count, sizeof (uint32_t), hipMemcpyDeviceToHost, t->stream));
+    TSDFCHK (t, hipMemcpyAsync (triangles, q.count, sizeof (uint32_t), hipMemcpyDeviceToHost, t->stream));
+    TSDFCHK (t, hipStreamSynchronize (t->stream));
+    a.m.limit = std::min (*vertices, vertex_capacity);
+    a.limit = std::min (*triangles, triangle_capacity);
+    int rc = reserve_records (t, a.m, normals); if (rc) return rc;
     if (a.limit == 0u) return ICP_OK;
-    int rc;
-    if ((rc = icp_host::tsdf_reserve (t, &t->dEdge, &t->edge_cap, (size_t) a.limit * 4u))) return rc;
-    if ((rc = icp_host::tsdf_reserve (t, &t->dOut, &t->out_cap, (size_t) a.limit * 32u))) return rc;
-    if (normals && (rc = icp_host::tsdf_reserve (t, &t->dNrm, &t->nrm_cap, (size_t) a.limit * 16u))) return rc;
-    a.edge = static_cast<uint32_t *> (t->dEdge); a.out = static_cast<float4 *> (t->dOut); a.nrm = normals ? static_cast<float4 *> (t->dNrm) : nullptr;
+    if ((rc = icp_host::tsdf_reserve (t, &t->dTri, &t->tri_cap, (size_t) a.limit * 12u))) return rc;
+    a.tri = static_cast<uint32_t *> (t->dTri);
+    return ICP_OK;
+}
+
+// `reps` groups of launches between the volume's two events, after an untimed group
+template <class G>
+int time_groups (icp_tsdf_context *t, uint32_t reps, G group, float *us_per_group)
+{
+    group ();
+    TSDFCHK (t, hipEventRecord (t->ev0, t->stream));
+    for (uint32_t i = 0; i < reps; ++i) group ();
+    TSDFCHK (t, hipEventRecord (t->ev1, t->stream));
+    TSDFCHK (t, hipGetLastError ());
+    TSDFCHK (t, hipEventSynchronize (t->ev1));
+    float ms = 0.f;
+    TSDFCHK (t, hipEventElapsedTime (&ms, t->ev0, t->ev1));
+    *us_per_group = ms * 1e3f / (float) reps;
     return ICP_OK;
 }
 
@@ -292,21 +615,32 @@ int tsdf_time_surface (icp_tsdf_context *t, int part, uint32_t reps, float *us_p
     tsdf_surface_args a = args_of (t, p, 1.f);
     uint32_t total = 0u;
     if ((rc = count_and_reserve (t, a, p, UINT32_MAX, true, &total))) return rc;      // (untimed: the code objects are loaded, the scratch holds every member)
-    auto group = [&] () {
+    return time_groups (t, reps, [&] () {
         if (part == 1) { launch_scan (p, t->stream); return; }
         if (part != 2) launch_count_and_scan (a, p, t->stream);
         if (a.limit) launch_scatter (a, p, t->stream);
-    };
-    group ();
-    TSDFCHK (t, hipEventRecord (t->ev0, t->stream));
-    for (uint32_t i = 0; i < reps; ++i) group ();
-    TSDFCHK (t, hipEventRecord (t->ev1, t->stream));
-    TSDFCHK (t, hipGetLastError ());
-    TSDFCHK (t, hipEventSynchronize (t->ev1));
-    float ms = 0.f;
-    TSDFCHK (t, hipEventElapsedTime (&ms, t->ev0, t->ev1));
-    *us_per_group = ms * 1e3f / (float) reps;
-    return ICP_OK;
+    }, us_per_group);
+}
+
+int tsdf_time_mesh (icp_tsdf_context *t, int part, uint32_t reps, float *us_per_group)
+{
+    TSDFCHK (t, hipSetDevice (t->device));
+    surface_plan p;
+    mesh_plan q;
+    int rc;
+    if ((rc = plan_surface (t, &p)) || (rc = plan_mesh (t, p, &q))) return rc;
+    tsdf_mesh_args a = mesh_args_of (t, args_of (t, p, 1.f), q);
+    uint32_t vertices = 0u, triangles = 0u;
+    if ((rc = count_mesh_and_reserve (t, a, p, q, UINT32_MAX, true, UINT32_MAX, &vertices, &triangles))) return rc;      // (untimed, as above)
+    return time_groups (t, reps, [&] () {
+        if (part == 0) launch_count_and_scan (a.m, p, t->stream);
+        if (part != 2) launch_cells (a, p, t->stream);
+        if (part == 0) {
+            launch_mesh_scan (p, q, t->stream);
+            if (a.m.limit) launch_scatter (a.m, p, t->stream);
+        }
+        if (part != 1 && a.limit) launch_triangles (a, p, t->stream);
+    }, us_per_group);
 }
 
 }  // namespace icp_host
@@ -338,6 +672,53 @@ int icp_tsdf_extract_surface (icp_tsdf_handle t, const icp_tsdf_surface_t *opt, 
         TSDFCHK (t, hipStreamSynchronize (t->stream));
     }
     *count = total;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
+int icp_tsdf_extract_mesh (icp_tsdf_handle t, const icp_tsdf_surface_t *opt, uint32_t vertex_capacity, void *cloud_out, float *normals_out, uint32_t *vertex_count,
+                           uint32_t triangle_capacity, uint32_t *triangles_out, uint32_t *triangle_count) try
+{
+    if (!t) return ICP_EINVAL;
+    if (!vertex_count || !triangle_count) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_extract_mesh: vertex_count and triangle_count are required");
+    const icp_tsdf_surface_t o = opt ? *opt : icp_tsdf_surface_t { 1.f, 0u };
+    if (!(std::isfinite (o.min_weight) && o.min_weight >= 1.f)) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_extract_mesh: min_weight must be finite and >= 1");
+    if (o.normals > 1u) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_extract_mesh: normals must be 0 or 1");
+    if (vertex_capacity && (!cloud_out || (o.normals && !normals_out)))
+        return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_extract_mesh: with a vertex capacity, cloud_out is required, and normals_out if normals are wanted");
+    if (triangle_capacity && !triangles_out) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_extract_mesh: with a triangle capacity, triangles_out is required");
+    if (5ull * (t->cfg.nx - 1u) * (t->cfg.ny - 1u) * (t->cfg.nz - 1u) > 0xFFFFFFFFull)
+        return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_extract_mesh: five triangles a cell of this volume do not count in 32 bits");
+    TSDFCHK (t, hipSetDevice (t->device));
+    surface_plan p;
+    mesh_plan q;
+    int rc;
+    if ((rc = plan_surface (t, &p)) || (rc = plan_mesh (t, p, &q))) return rc;
+    tsdf_mesh_args a = mesh_args_of (t, args_of (t, p, o.min_weight), q);
+    uint32_t vertices = 0u, triangles = 0u;
+    if ((rc = count_mesh_and_reserve (t, a, p, q, vertex_capacity, o.normals != 0u, triangle_capacity, &vertices, &triangles))) return rc;
+    if (a.m.limit || a.limit) {
+        if (a.m.limit) launch_scatter (a.m, p, t->stream);
+        if (a.limit) launch_triangles (a, p, t->stream);
+        TSDFCHK (t, hipGetLastError ());
+        if (a.m.limit) {
+            TSDFCHK (t, hipMemcpyAsync (cloud_out, t->dOut, (size_t) a.m.limit * 32u, hipMemcpyDeviceToHost, t->stream));
+            if (a.m.nrm) TSDFCHK (t, hipMemcpyAsync (normals_out, t->dNrm, (size_t) a.m.limit * 16u, hipMemcpyDeviceToHost, t->stream));
+        }
+        if (a.limit) TSDFCHK (t, hipMemcpyAsync (triangles_out, t->dTri, (size_t) a.limit * 12u, hipMemcpyDeviceToHost, t->stream));
+        TSDFCHK (t, hipStreamSynchronize (t->stream));
+    }
+    *vertex_count = vertices; *triangle_count = triangles;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
+int icp_tsdf_mesh_case (uint32_t case_index, uint32_t *n_triangles, uint8_t edges[15]) try
+{
+    if (case_index > 255u || !n_triangles || !edges) return ICP_EINVAL;
+    const mask64 word = mesh_cases ().word[case_index];
+    *n_triangles = (uint32_t) (word & 15ull);
+    for (uint32_t q = 0; q < 15u; ++q) edges[q] = (uint8_t) ((word >> (4u + 4u * q)) & 15ull);      // (0 past the case's triangles)
     return ICP_OK;
 }
 ICP_CATCH_ALL

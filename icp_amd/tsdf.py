@@ -1,11 +1,14 @@
 """Frame-to-model: a TSDF volume fused and ray-cast on the device (include/icp_amd.h: icp_tsdf_t, icp_tsdf_integrate, icp_tsdf_raycast,
-icp_tsdf_raycast_to, icp_tsdf_compose_pose), and its surface as a point cloud (icp_tsdf_extract_surface).
+icp_tsdf_raycast_to, icp_tsdf_compose_pose), and its surface as a point cloud (icp_tsdf_extract_surface) or a triangle mesh
+(icp_tsdf_extract_mesh).
 
     vol = TSDFVolume(TSDFConfig(256, 256, 256, voxel=8.0, origin=(-1024, -1024, 0), mu=24.0))
     for pose, k, scale in track_to_model(icp, vol, frames, pose0, 300.0, 4000.0):
         ...
     cloud, normals = vol.extract_surface()
     icp_amd.io.save_ply("model.ply", cloud, normals)
+    cloud, normals, triangles = vol.extract_mesh()
+    icp_amd.io.save_ply("mesh.ply", cloud, normals, triangles)
 
 A pose is 12 floats, row-major [R | t], camera -> world.  A camera is an icp_amd.rgbd.RGBDConfig."""
 import ctypes as C
@@ -66,6 +69,8 @@ def _lib():
                            ("icp_tsdf_read", (vp, vp, vp)), ("icp_tsdf_write", (vp, vp, vp)),
                            ("icp_tsdf_compose_pose", (vp, vp, vp, C.POINTER(f32))),
                            ("icp_tsdf_extract_surface", (vp, C.POINTER(icp_tsdf_surface_t), u32, vp, vp, C.POINTER(u32))),
+                           ("icp_tsdf_extract_mesh", (vp, C.POINTER(icp_tsdf_surface_t), u32, vp, vp, C.POINTER(u32), u32, vp, C.POINTER(u32))),
+                           ("icp_tsdf_mesh_case", (u32, C.POINTER(u32), C.POINTER(C.c_uint8))),
                            ("icp_tsdf_time", (vp, i32, cam, vp, vp, vp, f32, f32, u32, u32, C.POINTER(f32)))):
             f = getattr(L, name)
             f.restype, f.argtypes = i32, list(args)
@@ -91,6 +96,15 @@ def compose_pose(pose12, T8):
     if rc:
         raise icp_amd.ICPError(rc, "icp_tsdf_compose_pose: the quaternion must be finite and non-zero")
     return out, s.value
+
+
+def mesh_case(case_index):
+    """icp_tsdf_mesh_case (host only): the case table's entry as a list of triangles, each a triple of local edge ids 4 a + m."""
+    n, edges = C.c_uint32(), (C.c_uint8 * 15)()
+    rc = _lib().icp_tsdf_mesh_case(case_index, C.byref(n), edges)
+    if rc:
+        raise icp_amd.ICPError(rc, "icp_tsdf_mesh_case: the case index must be at most 255")
+    return [tuple(edges[3 * t:3 * t + 3]) for t in range(n.value)]
 
 
 class TSDFVolume:
@@ -200,9 +214,33 @@ class TSDFVolume:
             return cloud[:n], (nrm[:n] if normals else None)
         return cloud[:n], (nrm[:n] if normals else None), count.value
 
+    def extract_mesh(self, min_weight=1.0, normals=True, vertex_capacity=None, triangle_capacity=None):
+        """icp_tsdf_extract_mesh: the volume's surface as (cloud (n, 8), normals (n, 4) or None, triangles (m, 3) uint32): the vertices
+        are extract_surface's members, a triangle is three member positions, in ascending cell index and table order.  Without capacities:
+        one counting call for both counts, then everything.  When a capacity is given: (cloud, normals, triangles, vertex count, triangle
+        count), the first min (count, capacity) records of each kind (a capacity left None is 0) and the numbers there are; the indices
+        always refer to the full member order."""
+        opt, nv, nt = icp_tsdf_surface_t(min_weight, int(bool(normals))), C.c_uint32(), C.c_uint32()
+        counting = vertex_capacity is None and triangle_capacity is None
+        if counting:
+            self._chk(self._L.icp_tsdf_extract_mesh(self._t, C.byref(opt), 0, None, None, C.byref(nv), 0, None, C.byref(nt)))
+            vroom, troom = nv.value, nt.value
+        else:
+            vroom, troom = int(vertex_capacity or 0), int(triangle_capacity or 0)
+        cloud = np.empty((vroom, 8), np.float32)
+        nrm = np.empty((vroom, 4), np.float32) if normals else None
+        tri = np.empty((troom, 3), np.uint32)
+        self._chk(self._L.icp_tsdf_extract_mesh(self._t, C.byref(opt), vroom, _ptr(cloud) if vroom else None, _ptr(nrm) if vroom else None, C.byref(nv),
+                                                troom, _ptr(tri) if troom else None, C.byref(nt)))
+        n, m = min(nv.value, vroom), min(nt.value, troom)
+        out = (cloud[:n], (nrm[:n] if normals else None), tri[:m])
+        return out if counting else out + (nv.value, nt.value)
+
     def time_kernel(self, what, cam=None, pose12=None, depth=None, rgb=None, z_near=0.0, z_far=0.0, side=0, reps=20):
         """icp_tsdf_time (diagnostic): microseconds per launch of k_tsdf_integrate (what = 0; the volume changes) or k_tsdf_raycast (1), or
-        per group of the launches of one extract_surface with normals (2; 3: its two scan launches alone, 4: its scatter and points launches alone — nothing but reps is used)."""
+        per group of the launches of one extract_surface with normals (2; 3: its two scan launches alone, 4: its scatter and points launches alone), or
+        per group of the launches of one extract_mesh with normals (5; 6: its cell sweep alone, 7: its triangle pass alone) — for 2 .. 7
+        nothing but reps is used."""
         if depth is not None:
             depth, rgb = _images(depth, rgb, cam.width, cam.height)
         c, us = cam._c() if cam is not None else None, C.c_float()

@@ -336,7 +336,7 @@ namespace ICP
 
     /*! \brief Frame-to-model (icp_tsdf_*, include/icp_amd.h): a truncated signed distance volume on the device that registered frames
      *         are fused into (`integrate`) and whose view from a pose (`raycast`, `raycastTo`) is the fixed frame of the next
-     *         registration — an organised grid with normals.  `extractSurface` gives the model itself as a point cloud.  A pose is 12
+     *         registration — an organised grid with normals.  `extractSurface` gives the model itself as a point cloud, `extractMesh` as a triangle mesh.  A pose is 12
      *         floats, row-major [R | t], camera -> world.  The reference has no model and no such class. */
     class TSDFVolume
     {
@@ -373,6 +373,19 @@ namespace ICP
             if (normals) normals->resize ((size_t) n * 4);
             if (n) check (icp_tsdf_extract_surface (t, &o, n, cloud.data (), normals ? normals->data () : nullptr, &n));
             return n;
+        }
+        /*! the volume's surface as a triangle mesh (icp_tsdf_extract_mesh): one counting call for both counts, then everything — `cloud` and
+         *  `normals` receive extractSurface's points, `triangles` three vertex indices a triangle; returns the number of triangles */
+        uint32_t extractMesh (std::vector<float> &cloud, std::vector<uint32_t> &triangles, std::vector<float> *normals = nullptr, float min_weight = 1.f)
+        {
+            const icp_tsdf_surface_t o = { min_weight, normals ? 1u : 0u };
+            uint32_t n = 0, m = 0;
+            check (icp_tsdf_extract_mesh (t, &o, 0, nullptr, nullptr, &n, 0, nullptr, &m));
+            cloud.resize ((size_t) n * 8);
+            triangles.resize ((size_t) m * 3);
+            if (normals) normals->resize ((size_t) n * 4);
+            if (n || m) check (icp_tsdf_extract_mesh (t, &o, n, cloud.data (), normals ? normals->data () : nullptr, &n, m, triangles.data (), &m));
+            return m;
         }
         /*! out12 = pose12 o (R (q), t) of the engine's T8; returns T8's scale */
         static float composePose (const float *pose12, const float *T8, float *out12)

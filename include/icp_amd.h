@@ -1118,12 +1118,51 @@ typedef struct {
     uint32_t normals;                       /* 0 or 1 */
 } icp_tsdf_surface_t;
 int icp_tsdf_extract_surface (icp_tsdf_handle t, const icp_tsdf_surface_t *opt, uint32_t capacity, void *cloud_out, float *normals_out, uint32_t *count);
+/* Mesh extraction: the model as a triangle mesh (what Open3D's extract_triangle_mesh and KinFu's marching cubes give), compacted in order
+ * on the device; tests/tsdf_mesh_ref.py restates it.  The volume is never modified.
+ *    Vertices.  The vertices are the members of icp_tsdf_extract_surface for the same min_weight and normals: the same records in the
+ *    same order, bit for bit.  A vertex index is a member's position.
+ *    Cells.  Cell v = (i, j, k) exists where i + 1 < nx, j + 1 < ny and k + 1 < nz.  Its corner c = bx + 2 by + 4 bz is voxel
+ *    v + (bx, by, bz).  It is ACTIVE iff all eight corners are usable (W >= min_weight && fabsf (D) < 1.f); its case is the sum of
+ *    (D (corner c) > 0.f) << c.  An inactive cell yields nothing: the mesh ends where the usable volume ends.
+ *    Cell edges.  Local edge e = 4 a + m: a is its axis, b1 < b2 are the two other axes, m = bit_b1 + 2 bit_b2 of its low corner.  It is
+ *    the lattice edge (v + bits, a).  In an active cell it is a member iff its ends differ in sign, and its vertex index is that member's
+ *    position.
+ *    The case table: 256 entries of at most five triangles, each a triple of local edge ids, generated by this rule (icp_tsdf_mesh_case
+ *    returns an entry):
+ *      1. The crossing edges are those whose ends differ in sign.
+ *      2. Each of the six faces has 0, 2 or 4 crossing edges.  Two give one segment.  Four give two segments, each joining the two face
+ *         edges that meet at a POSITIVE corner: positive corners are cut off singly, the two non-positive corners stay joined.  The
+ *         choice depends on the face's four signs alone, so the two cells that share a face draw the same segments.
+ *      3. Every crossing edge lies on two faces, so the segments close into loops; loops are taken in ascending order of their smallest
+ *         edge id.
+ *      4. With the vertices at the edge midpoints P_i, a loop is traversed in the direction for which sum P_i x P_i+1 has a positive dot
+ *         product with the sum over the loop's edges of the unit vector from the non-positive end to the positive end (never 0).  Triangle
+ *         normals (v1 - v0) x (v2 - v0) then point into free space, where the ray cast's and the surface's normals point.
+ *      5. Let r be the loop in that direction from its smallest edge id.  The fan (r_s, r_s+i, r_s+i+1), i = 1 .. n - 2, takes as apex
+ *         the first r_s in that order none of whose fan diagonals joins two edges of one cube face (a diagonal in a face could be drawn
+ *         by the neighbouring cell too, and the edge would carry four triangles).  18 loops move the apex off their smallest edge.
+ *      The table has 820 triangles; no case has more than five.
+ *    Triangles.  Output in ascending cell index (k ny + j) nx + i and, inside a cell, in table order; a record is three uint32_t vertex
+ *    indices, which always refer to the full member order, whatever the vertex capacity is.  A voxel with D exactly 0 gives coincident
+ *    vertices and so zero-area triangles: that is the rule, as it is for the points, and keeps the index topology closed.
+ * opt, cloud_out, normals_out and vertex_capacity are icp_tsdf_extract_surface's, with its refusals.  Both counts are required;
+ * triangles_out (triangle_capacity x 3 words, a host pointer) is required iff triangle_capacity > 0.  The first min (count, capacity)
+ * records of each kind are written and nothing past them is touched; both capacities 0 is the counting call, which makes one host round
+ * trip for both counts.  ICP_EINVAL, before any launch, also if 5 (nx - 1) (ny - 1) (nz - 1) > 2^32 - 1 (1024 x 1024 x 821 passes,
+ * 1024 x 1024 x 822 is refused): the triangle count stays in 32 bits; lifting this limit is later work. */
+int icp_tsdf_extract_mesh (icp_tsdf_handle t, const icp_tsdf_surface_t *opt, uint32_t vertex_capacity, void *cloud_out, float *normals_out, uint32_t *vertex_count,
+                           uint32_t triangle_capacity, uint32_t *triangles_out, uint32_t *triangle_count);
+/* Host only, no device needed: entry case_index of the case table — the number of triangles (0 .. 5) and their local edge ids, three a
+ * triangle, 0 past them.  ICP_EINVAL for case_index > 255 or a NULL output. */
+int icp_tsdf_mesh_case (uint32_t case_index, uint32_t *n_triangles, uint8_t edges[15]);
 /* Diagnostic (tools/diag/tsdf_time.py): `reps` launches of one kernel between two events on the volume's stream, after one untimed launch.
  * what = 0: k_tsdf_integrate of (depth, rgb) at pose12 — the volume is left as reps + 1 integrations leave it;  what = 1: k_tsdf_raycast as
  * icp_tsdf_raycast (cam, pose12, z_near, z_far, side) runs it, into scratch (depth, rgb unused);  what = 2: the launches of one
  * icp_tsdf_extract_surface with normals and min_weight 1 as a group, every member into scratch;  what = 3: the two scan launches of
- * that group alone;  what = 4: its last two launches (the members' edges, their records) alone (for 2 .. 4 every argument but reps is unused, cam and
- * pose12 may be NULL).
+ * that group alone;  what = 4: its last two launches (the members' edges, their records) alone (for 2 .. 7 every argument but reps is unused, cam and
+ * pose12 may be NULL);  what = 5: the launches of one icp_tsdf_extract_mesh with normals and min_weight 1 as a group, every vertex and
+ * triangle into scratch;  what = 6: its cell sweep alone;  what = 7: its triangle pass alone.
  * Microseconds per launch (per group). */
 int icp_tsdf_time (icp_tsdf_handle t, int what, const icp_rgbd_t *cam, const float *pose12, const uint16_t *depth, const uint8_t *rgb, float z_near, float z_far,
                    uint32_t side, uint32_t reps, float *us_per_launch);

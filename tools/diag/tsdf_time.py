@@ -12,7 +12,11 @@
     scatter and points launches (what = 4) alone, the
     blocking calls with the copy to the host, and what they replace: a blocking icp_tsdf_read plus the numpy restatement on the host
     (the restatement at 256^3 only: at 512^3 its temporaries do not fit a workstation's memory).
-    python tools/diag/tsdf_time.py [--reps N] [--skip-512] [--surface]"""
+  - with --mesh (and nothing else then): the mesh extraction of the same scene and volumes: the launches of one extract_mesh as a group
+    (what = 5) beside those of extract_surface with normals (what = 2) from the same run, the cell sweep (what = 6) and the triangle
+    pass (what = 7) alone, each against one read of {D, W} at the HBM rate; the blocking call with both capacities given and with the
+    counting call first; the vertex and triangle counts.
+    python tools/diag/tsdf_time.py [--reps N] [--skip-512] [--surface | --mesh]"""
 import argparse
 import os
 import statistics
@@ -52,10 +56,10 @@ def blocking(call, reps):
     return statistics.median(t)
 
 
-def surface(a):
+def corner_volumes(a):
+    """The corner scene of tests/tsdf_ref.py fused from six 640 x 480 frames into 256^3 and 512^3 voxels over its 1.02 m cube, mu = 3 voxel edges."""
     sys.path[:0] = [os.path.join(ROOT, "tests")]
     import tsdf_ref as T                # noqa: E402
-    import tsdf_surface_ref as S        # noqa: E402
     d = T.corner_camera(width=640, height=480, fx=600.0, cx=319.5, cy=239.5)
     cam = rgbd.RGBDConfig(**d)
     frames = [(T.look_at(eye).reshape(12).astype(np.float32),) + T.render_corner(T.look_at(eye), d)[:2] for eye in T.EYES]
@@ -64,6 +68,15 @@ def surface(a):
         v = tsdf.TSDFVolume(tsdf.TSDFConfig(n, n, n, voxel, (-64.0, -64.0, -64.0), 3.0 * voxel, 64.0, 1))
         for pose, depth, colour in frames:
             v.integrate(cam, pose, depth, colour)
+        yield n, v
+        v.close()
+
+
+def surface(a):
+    sys.path[:0] = [os.path.join(ROOT, "tests")]
+    import tsdf_ref as T                # noqa: E402
+    import tsdf_surface_ref as S        # noqa: E402
+    for n, v in corner_volumes(a):
         floor = n ** 3 * 8 / HBM_MEASURED * 1e6
         cloud, nrm, count = v.extract_surface(capacity=0)
         group = median(lambda: v.time_kernel(2, reps=20), a.reps)
@@ -90,7 +103,26 @@ def surface(a):
         else:
             print("surface %d^3 the numpy restatement on the host: not measured" % n, flush=True)
         del dw, col
-        v.close()
+
+
+def mesh(a):
+    for n, v in corner_volumes(a):
+        floor = n ** 3 * 8 / HBM_MEASURED * 1e6
+        _, _, _, nv, nt = v.extract_mesh(vertex_capacity=0, triangle_capacity=0)
+        points = median(lambda: v.time_kernel(2, reps=20), a.reps)
+        group = median(lambda: v.time_kernel(5, reps=20), a.reps)
+        cells = median(lambda: v.time_kernel(6, reps=20), a.reps)
+        tris = median(lambda: v.time_kernel(7, reps=20), a.reps)
+        print("mesh %d^3: %d vertices, %d triangles (%.2f a vertex)" % (n, nv, nt, nt / max(nv, 1)), flush=True)
+        print("mesh %d^3 launches of one extract_mesh     %9.2f us = %.2f of one read of {D, W} at 6.29 TB/s (%.2f us)" % (n, group, group / floor, floor), flush=True)
+        print("mesh %d^3 launches of one extract_surface  %9.2f us = %.2f of the read: the mesh costs %.2f us more" % (n, points, points / floor, group - points), flush=True)
+        print("mesh %d^3 the cell sweep alone             %9.2f us = %.2f of the read" % (n, cells, cells / floor), flush=True)
+        print("mesh %d^3 the triangle pass alone          %9.2f us = %.2f of the read  (the second scan: the rest, %.2f us)" % (n, tris, tris / floor, group - points - cells - tris), flush=True)
+        one = blocking(lambda: v.extract_mesh(vertex_capacity=nv, triangle_capacity=nt), a.reps)
+        two = blocking(lambda: v.extract_mesh(), a.reps)
+        cnt = blocking(lambda: v.extract_mesh(vertex_capacity=0, triangle_capacity=0), a.reps)
+        print("mesh %d^3 blocking extract_mesh            %9.2f us with both capacities given, %9.2f us with the counting call first, %9.2f us the counting call alone  (%.1f MB to the host)"
+              % (n, one, two, cnt, (nv * 48 + nt * 12) / 1e6), flush=True)
 
 
 def main():
@@ -98,9 +130,12 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--skip-512", action="store_true")
     ap.add_argument("--surface", action="store_true")
+    ap.add_argument("--mesh", action="store_true")
     a = ap.parse_args()
     if a.surface:
         return surface(a)
+    if a.mesh:
+        return mesh(a)
     depth, colour = frame()
     cam = rgbd.RGBDConfig()
     print("frame: %d of %d pixels valid, depth %d .. %d" % ((depth != 0).sum(), depth.size, depth[depth != 0].min(), depth.max()), flush=True)
