@@ -9,7 +9,9 @@
 //
 // Map of this file (what a phase needs from the others is in its parameter list):
 //   helpers                      sums, group minima (DPP), KS_CAND / KS_CAND_IF (one list candidate against the lane's query), KS_PAIR (one pair of
-//                                representatives in LDS against it: the unpruned stage-1 scan), ks_tile_of_block, fused_query_index, cell_rep_of
+//                                representatives in LDS against it: the unpruned stage-1 scan of the dense variants), ks_group_min_first (the
+//                                same scan of the one-block-per-CU variants: a group's minimum first, the index afterwards), ks_tile_of_block,
+//                                fused_query_index, cell_rep_of
 //   ks_seed_against_invalid, ks_origin_list, ks_origin_section    a frame's invalid points (representatives at the origin): the seed of a
 //                                query whose cell's representative is of the other kind; their list, scanned behind the tiles
 //   fused_moment_* / fused_finalize_block / fin_result_to_state      the finalize of a block: 18 double moments -> T (shared with icp_kernels.hip)
@@ -330,6 +332,50 @@ static __device__ __forceinline__ void ks_origin_section (float4 *s_pair, uint32
         if (d.x < best) { best = d.x; bid = r0; }                                                                                         \
         if (d.y < best) { best = d.y; bid = r0 + 1u; }                                                                                    \
     }
+
+// The unpruned stage-1 scan of the one-block-per-CU variants (MINW == 2: ks_latency, ks_chained, the owner search with lists), minimum
+// first and the index afterwards.  A lane takes a GROUP of up to 8 of its pairs (P0, P0 + LPQ, ..), keeps the group's 16 distances in
+// registers — the d.x, d.y of KS_PAIR, the same operations — and folds them into the group's minimum with one v_min3_f32 per pair; only
+// where that minimum is strictly below the lane's best so far it looks for the LOWEST position of the group whose distance EQUALS the
+// minimum (one compare and one select per position, scanned descending so that the lowest is written last).  KS_PAIR spent two compares,
+// four selects and two index adds per pair on the same answer, a dependent chain each.
+// Same bits as KS_PAIR over ascending pairs:
+//   - KS_PAIR's strict '<' over ascending positions keeps a lane's lowest index among equal distances: that is the lowest position whose
+//     distance equals the lane's minimum.  Groups ascend, and a later group replaces (best, bid) on a strict '<' only.
+//   - a NaN distance (a NaN representative, the odd tile's pad slot, inf - inf) never equals anything, and v_min3_f32 returns the operand
+//     that is not a NaN, as the '<' that is false for a NaN did.
+//   - a lane whose distances are all +inf or NaN has a group minimum of +inf, which is not below best = +inf: it keeps bid = 0xFFFFFFFF.
+//     A minimum of +inf never names a position.
+//   - no -0: d = fma (a, pho, geo) with geo, pho sums of squares is -0 for no input (+0 + -0 = +0), so "equal" is "the same bits".
+// PARTIAL: the tile's last group, where a lane may have fewer than 8 pairs — a pair it does not have is read at a clamped address and its
+// distances are replaced by NaN: it never matches.  r0 = the index of the first representative of pair P0.
+static __device__ __forceinline__ float ks_min3_f (float a, float b, float c) { return __builtin_fminf (__builtin_fminf (a, b), c); }
+template <int LPQ, bool PARTIAL>
+static __device__ __forceinline__ void ks_group_min_first (const float4 *s_pair, uint32_t P0, uint32_t npair, uint32_t r0, float2v vqx, float2v vqy, float2v vqz, float2v vqr,
+                                                           float2v vqg, float2v vqb, float2v va, float &best, uint32_t &bid)
+{
+    float dd[16];
+    float gmin = __builtin_inff ();
+#pragma unroll
+    for (uint32_t k = 0; k < 8u; ++k) {
+        const uint32_t P = P0 + k * (uint32_t) LPQ, P3 = 3u * (PARTIAL ? min (P, npair - 1u) : P);
+        float4 A = s_pair[P3], B = s_pair[P3 + 1], C = s_pair[P3 + 2];
+        float2v x = { A.x, A.y }, y = { A.z, A.w }, z = { B.x, B.y }, r = { B.z, B.w }, g = { C.x, C.y }, bb = { C.z, C.w };
+        float2v dx = vqx - x, dy = vqy - y, dz = vqz - z, dr = vqr - r, dg = vqg - g, db = vqb - bb;
+        float2v geo = __builtin_elementwise_fma (dz, dz, __builtin_elementwise_fma (dy, dy, dx * dx));
+        float2v pho = __builtin_elementwise_fma (db, db, __builtin_elementwise_fma (dg, dg, dr * dr));
+        float2v d = __builtin_elementwise_fma (va, pho, geo);
+        if (PARTIAL && P >= npair) d = float2v { __builtin_nanf (""), __builtin_nanf ("") };
+        dd[2u * k] = d.x; dd[2u * k + 1u] = d.y;
+        gmin = ks_min3_f (gmin, d.x, d.y);
+    }
+    if (gmin < best) {                               // (the lanes that improved; a group in which no lane of the wave did is skipped: execz)
+        uint32_t pos = 0u;                           // (gmin < best <= +inf is one of the 16 distances: some position matches)
+#pragma unroll
+        for (int k = 15; k >= 0; --k) pos = (dd[k] == gmin) ? 2u * (uint32_t) (k >> 1) * (uint32_t) LPQ + (uint32_t) (k & 1) : pos;
+        best = gmin; bid = r0 + pos;
+    }
+}
 
 #define ICP_NMOM 18
 
@@ -1668,6 +1714,14 @@ __global__ __launch_bounds__ (64 * LPQ, TILE == 256 ? 8 : MINW) void k_search (c
             if (t0 == 0 && __ballot (tile_near (lim))) cmask = ks_coarse_pass<LPQ, TILE> (s_box, 0u, qx, qy, qz, ss, tn, lim);
             ks_fine_pass<LPQ> (s_pair, 0u, qx, qy, qz, qr, qg, qb, alpha, gt_lg1, ss, t0, npair, cmask, best, bid);
             s1_lim = fminf (lim, ks_grp_min_f<KS_SPLIT> (best));
+        } else if constexpr (MINW == 2) {
+            // one-block-per-CU variants: groups of 8 pairs per lane, minimum first (ks_group_min_first) — |R| = 256 is one full group
+            constexpr uint32_t GP = 8u * KS_SPLIT;   // pairs of the tile one group of every lane covers
+            const uint32_t nfull = npair / GP;
+            for (uint32_t gi = 0; gi < nfull; ++gi)
+                ks_group_min_first<LPQ, false> (s_pair, gi * GP + ss, npair, t0 + 2u * (gi * GP + ss), vqx, vqy, vqz, vqr, vqg, vqb, va, best, bid);
+            if (npair != nfull * GP)
+                ks_group_min_first<LPQ, true> (s_pair, nfull * GP + ss, npair, t0 + 2u * (nfull * GP + ss), vqx, vqy, vqz, vqr, vqg, vqb, va, best, bid);
         } else {
 #pragma unroll 8
             for (uint32_t P = ss; P < npair; P += KS_SPLIT) KS_PAIR (3 * P, t0 + 2u * P)
