@@ -1543,6 +1543,25 @@ int icp_tsdf_raycast_to (icp_tsdf_handle t, icp_handle h, int which, const icp_r
 }
 ICP_CATCH_ALL
 
+// F or M of registration 0 registered against a TSDF volume (icp_tsdf_register.hip), device to device: the volume's kernels read the
+// handle's buffer on the volume's stream, behind everything the handle's stream holds.  Nothing in the handle changes.
+int icp_tsdf_register_from (icp_tsdf_handle t, const icp_tsdf_register_t *opt, icp_handle h, int which, const float *pose12, icp_tsdf_registration_t *out) try
+{
+    if (!t) return ICP_EINVAL;
+    if (!h) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_register_from: null handle");
+    api_guard guard_ (h);
+    if (!h->inited) return tsdf_fail (t, ICP_ESTATE, "icp_tsdf_register_from: icp_init has not been called on the handle");
+    if (h->device != t->device) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_register_from: the handle lives on another device than the volume");
+    if (which != ICP_MEM_F && which != ICP_MEM_M) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_register_from: which must be ICP_MEM_F or ICP_MEM_M");
+    if (h->track_submitted != h->track_collected) return tsdf_fail (t, ICP_ESTATE, "icp_tsdf_register_from: tracked frames are in flight: collect them first (icp_track_collect)");
+    const void *cloud = which == ICP_MEM_F ? h->dF : h->dM;
+    int rc = tsdf_register_check (t, "icp_tsdf_register_from", opt, cloud, h->p.m, pose12, out); if (rc) return rc;
+    if ((rc = need (h, false)) || (rc = set_device (h))) return tsdf_fail (t, rc, "icp_tsdf_register_from: " + h->err);
+    if (hipError_t e = hipStreamSynchronize (h->stream); e != hipSuccess) return tsdf_fail (t, ICP_EHIP, std::string ("hipStreamSynchronize: ") + hipGetErrorString (e));
+    return tsdf_register_run (t, opt, cloud, h->p.m, pose12, out);
+}
+ICP_CATCH_ALL
+
 int icp_transform_cloud (icp_handle h, const void *host_in, void *host_out, uint32_t n) try
 {
     api_guard guard_ (h);

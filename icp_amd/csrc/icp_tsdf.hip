@@ -28,8 +28,6 @@ constexpr uint32_t AHEAD = 4u;                             // steps of the march
 
 struct tsdf_integrate_args { icp_tsdf_dev v; icp_tsdf_view cam; const uint16_t *depth; const uint8_t *rgb; };
 
-__device__ __forceinline__ float dot3 (float a0, float b0, float a1, float b1, float a2, float b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
-
 __global__ __launch_bounds__ (256) void k_tsdf_integrate (tsdf_integrate_args a)
 {
     const icp_tsdf_dev &v = a.v;
@@ -62,49 +60,6 @@ __global__ __launch_bounds__ (256) void k_tsdf_integrate (tsdf_integrate_args a)
     v.dw[at] = make_float2 ((dw.x * dw.y + e) / w1, fminf (w1, v.w_max));
 }
 
-// The cell of the world point w: false unless 0 <= floor (g_a) <= n_a - 2 on every axis (NaN fails; no conversion before the check).
-// at: the cell's corner (i, j, k); f: the fractions.
-__device__ __forceinline__ bool tsdf_cell (const icp_tsdf_dev &v, float wx, float wy, float wz, size_t &at, float3 &f)
-{
-    const float gx = (wx - v.ox) / v.voxel, gy = (wy - v.oy) / v.voxel, gz = (wz - v.oz) / v.voxel;
-    const float ix = floorf (gx), iy = floorf (gy), iz = floorf (gz);
-    if (!(ix >= 0.f && ix <= (float) (v.nx - 2u) && iy >= 0.f && iy <= (float) (v.ny - 2u) && iz >= 0.f && iz <= (float) (v.nz - 2u))) return false;
-    at = ((size_t) (uint32_t) iz * v.ny + (uint32_t) iy) * v.nx + (uint32_t) ix;
-    f = make_float3 (gx - ix, gy - iy, gz - iz);
-    return true;
-}
-
-__device__ __forceinline__ float lerp1 (float a, float b, float t) { return a + t * (b - a); }
-
-// along x, then y, then z; c[dz][dy][dx]
-__device__ __forceinline__ float tsdf_trilinear (float c000, float c001, float c010, float c011, float c100, float c101, float c110, float c111, const float3 &f)
-{
-    const float y00 = lerp1 (c000, c001, f.x), y01 = lerp1 (c010, c011, f.x), y10 = lerp1 (c100, c101, f.x), y11 = lerp1 (c110, c111, f.x);
-    return lerp1 (lerp1 (y00, y01, f.y), lerp1 (y10, y11, f.y), f.z);
-}
-
-// The eight {D, W} of the cell of a world point — of cell (0, 0, 0) where the point has none, so that a fetch is unconditional and the
-// loads of several samples can be in flight together — and what decides the sample from them.
-struct tsdf_corners { float2 c[8]; float3 f; size_t at; bool cell; };
-
-__device__ __forceinline__ void tsdf_fetch (const icp_tsdf_dev &v, float wx, float wy, float wz, tsdf_corners &q)
-{
-    q.at = 0;
-    q.cell = tsdf_cell (v, wx, wy, wz, q.at, q.f);
-    const size_t sy = v.nx, sz = (size_t) v.nx * v.ny;
-    const float2 *p = v.dw + q.at;
-    q.c[0] = p[0]; q.c[1] = p[1]; q.c[2] = p[sy]; q.c[3] = p[sy + 1]; q.c[4] = p[sz]; q.c[5] = p[sz + 1]; q.c[6] = p[sz + sy]; q.c[7] = p[sz + sy + 1];
-}
-
-// S (w): known, and its value
-__device__ __forceinline__ bool tsdf_value (const tsdf_corners &q, float &S)
-{
-    const float2 *c = q.c;
-    if (!(q.cell && c[0].y > 0.f && c[1].y > 0.f && c[2].y > 0.f && c[3].y > 0.f && c[4].y > 0.f && c[5].y > 0.f && c[6].y > 0.f && c[7].y > 0.f)) return false;
-    S = tsdf_trilinear (c[0].x, c[1].x, c[2].x, c[3].x, c[4].x, c[5].x, c[6].x, c[7].x, q.f);
-    return true;
-}
-
 __device__ __forceinline__ bool tsdf_sample (const icp_tsdf_dev &v, float wx, float wy, float wz, float &S, size_t *cell = nullptr, float3 *frac = nullptr)
 {
     tsdf_corners q;
@@ -112,12 +67,6 @@ __device__ __forceinline__ bool tsdf_sample (const icp_tsdf_dev &v, float wx, fl
     if (!tsdf_value (q, S)) return false;
     if (cell) { *cell = q.at; *frac = q.f; }
     return true;
-}
-
-__device__ __forceinline__ float3 tsdf_world (const icp_tsdf_view &cam, float x, float y, float z)
-{
-    const float *R = cam.R, *t = cam.t;
-    return make_float3 (dot3 (R[0], x, R[1], y, R[2], z) + t[0], dot3 (R[3], x, R[4], y, R[5], z) + t[1], dot3 (R[6], x, R[7], y, R[8], z) + t[2]);
 }
 
 __global__ __launch_bounds__ (256) void k_tsdf_raycast (icp_tsdf_cast_args a)
@@ -315,7 +264,7 @@ int icp_tsdf_destroy (icp_tsdf_handle t) try
     if (!t) return ICP_EINVAL;
     (void) hipSetDevice (t->device);
     if (t->stream) (void) hipStreamSynchronize (t->stream);
-    for (void *q : { (void *) t->v.dw, (void *) t->v.col, t->dDepth, t->dRgb, t->dOut, t->dNrm, t->dSurf, t->dEdge, t->dMesh, t->dTri, t->dMeshTab }) if (q) (void) hipFree (q);
+    for (void *q : { (void *) t->v.dw, (void *) t->v.col, t->dDepth, t->dRgb, t->dOut, t->dNrm, t->dSurf, t->dEdge, t->dMesh, t->dTri, t->dMeshTab, t->dRegCloud, t->dRegWork }) if (q) (void) hipFree (q);
     if (t->ev0) (void) hipEventDestroy (t->ev0);
     if (t->ev1) (void) hipEventDestroy (t->ev1);
     if (t->stream) (void) hipStreamDestroy (t->stream);
@@ -456,7 +405,8 @@ int icp_tsdf_time (icp_tsdf_handle t, int what, const icp_rgbd_t *cam, const flo
                            uint32_t side, uint32_t reps, float *us_per_launch) try
 {
     if (!t) return ICP_EINVAL;
-    if (!us_per_launch || reps == 0u || what < 0 || what > 7) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_time: bad arguments");
+    if (!us_per_launch || reps == 0u || what < 0 || what > 9) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_time: bad arguments");
+    if (what >= 8) return tsdf_time_register (t, what - 8, depth, side, pose12, reps, us_per_launch);
     if (what >= 5) return tsdf_time_mesh (t, what - 5, reps, us_per_launch);
     if (what >= 2) return tsdf_time_surface (t, what - 2, reps, us_per_launch);
     tsdf_integrate_args ia {};

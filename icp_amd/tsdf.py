@@ -1,6 +1,6 @@
 """Frame-to-model: a TSDF volume fused and ray-cast on the device (include/icp_amd.h: icp_tsdf_t, icp_tsdf_integrate, icp_tsdf_raycast,
 icp_tsdf_raycast_to, icp_tsdf_compose_pose), and its surface as a point cloud (icp_tsdf_extract_surface) or a triangle mesh
-(icp_tsdf_extract_mesh).
+(icp_tsdf_extract_mesh), and a cloud registered against the volume itself (icp_tsdf_register, icp_tsdf_register_from, track_to_volume).
 
     vol = TSDFVolume(TSDFConfig(256, 256, 256, voxel=8.0, origin=(-1024, -1024, 0), mu=24.0))
     for pose, k, scale in track_to_model(icp, vol, frames, pose0, 300.0, 4000.0):
@@ -27,6 +27,36 @@ class icp_tsdf_t(C.Structure):
 
 class icp_tsdf_surface_t(C.Structure):
     _fields_ = [("min_weight", C.c_float), ("normals", C.c_uint32)]
+
+
+class icp_tsdf_register_t(C.Structure):
+    _fields_ = [("max_iterations", C.c_uint32), ("angle_threshold", C.c_double), ("translation_threshold", C.c_double)]
+
+
+class icp_tsdf_registration_t(C.Structure):
+    _fields_ = [("pose12", C.c_float * 12), ("iterations", C.c_uint32), ("converged", C.c_uint32), ("singular", C.c_uint32),
+                ("members", C.c_uint32), ("rmse", C.c_double), ("sys", C.c_double * 27)]
+
+
+class Registration:
+    """icp_tsdf_registration_t: pose (12 float32), iterations, converged, singular, and of the last iteration evaluated members, rmse and
+    sys (27 float64: the information matrix's upper triangle, then J^T r)."""
+
+    def __init__(self, c):
+        self.pose = np.array(c.pose12, np.float32)
+        self.iterations, self.converged, self.singular, self.members = c.iterations, bool(c.converged), bool(c.singular), c.members
+        self.rmse, self.sys = c.rmse, np.array(c.sys, np.float64)
+
+    def __repr__(self):
+        return "Registration(iterations=%d, converged=%s, singular=%s, members=%d, rmse=%r)" % (self.iterations, self.converged, self.singular, self.members, self.rmse)
+
+
+ANGLE_THRESHOLD, TRANSLATION_THRESHOLD = 0.001, 0.01          # icp_tsdf_register's defaults: those of ICP.init
+
+
+def _register_options(max_iterations, angle_threshold, translation_threshold):
+    return icp_tsdf_register_t(max_iterations, ANGLE_THRESHOLD if angle_threshold is None else angle_threshold,
+                               TRANSLATION_THRESHOLD if translation_threshold is None else translation_threshold)
 
 
 class TSDFConfig:
@@ -71,6 +101,8 @@ def _lib():
                            ("icp_tsdf_extract_surface", (vp, C.POINTER(icp_tsdf_surface_t), u32, vp, vp, C.POINTER(u32))),
                            ("icp_tsdf_extract_mesh", (vp, C.POINTER(icp_tsdf_surface_t), u32, vp, vp, C.POINTER(u32), u32, vp, C.POINTER(u32))),
                            ("icp_tsdf_mesh_case", (u32, C.POINTER(u32), C.POINTER(C.c_uint8))),
+                           ("icp_tsdf_register", (vp, C.POINTER(icp_tsdf_register_t), vp, u32, vp, C.POINTER(icp_tsdf_registration_t))),
+                           ("icp_tsdf_register_from", (vp, C.POINTER(icp_tsdf_register_t), vp, i32, vp, C.POINTER(icp_tsdf_registration_t))),
                            ("icp_tsdf_time", (vp, i32, cam, vp, vp, vp, f32, f32, u32, u32, C.POINTER(f32)))):
             f = getattr(L, name)
             f.restype, f.argtypes = i32, list(args)
@@ -236,6 +268,29 @@ class TSDFVolume:
         out = (cloud[:n], (nrm[:n] if normals else None), tri[:m])
         return out if counting else out + (nv.value, nt.value)
 
+    def register(self, cloud, pose12, max_iterations=20, angle_threshold=None, translation_threshold=None):
+        """icp_tsdf_register: the cloud (n, 8) of the camera's frame registered against the volume itself from pose12: a Registration."""
+        cloud = np.ascontiguousarray(cloud, np.float32)
+        if cloud.ndim != 2 or cloud.shape[1] != 8:
+            raise ValueError("expected a cloud of n x 8 floats")
+        opt, out = _register_options(max_iterations, angle_threshold, translation_threshold), icp_tsdf_registration_t()
+        self._chk(self._L.icp_tsdf_register(self._t, C.byref(opt), _ptr(cloud), cloud.shape[0], _ptr(_pose(pose12)), C.byref(out)))
+        return Registration(out)
+
+    def register_from(self, icp, which, pose12, max_iterations=20, angle_threshold=None, translation_threshold=None):
+        """icp_tsdf_register_from: F or M (which = Memory.F / Memory.M) of registration 0 of `icp`, device to device: a Registration."""
+        rgbd._handle(icp, "a registration of a level's landmarks")
+        opt, out = _register_options(max_iterations, angle_threshold, translation_threshold), icp_tsdf_registration_t()
+        self._chk(self._L.icp_tsdf_register_from(self._t, C.byref(opt), icp._h, which, _ptr(_pose(pose12)), C.byref(out)))
+        return Registration(out)
+
+    def time_register(self, what, cloud, pose12, reps=20):
+        """icp_tsdf_time (diagnostic), what = 8: microseconds per iteration (both launches) of a registration of `cloud` held at pose12;
+        9: of k_tsdf_reg_moments alone."""
+        cloud, us = np.ascontiguousarray(cloud, np.float32), C.c_float()
+        self._chk(self._L.icp_tsdf_time(self._t, what, None, _ptr(_pose(pose12)), _ptr(cloud), None, 0.0, 0.0, cloud.shape[0], reps, C.byref(us)))
+        return us.value
+
     def time_kernel(self, what, cam=None, pose12=None, depth=None, rgb=None, z_near=0.0, z_far=0.0, side=0, reps=20):
         """icp_tsdf_time (diagnostic): microseconds per launch of k_tsdf_integrate (what = 0; the volume changes) or k_tsdf_raycast (1), or
         per group of the launches of one extract_surface with normals (2; 3: its two scan launches alone, 4: its scatter and points launches alone), or
@@ -269,3 +324,22 @@ def track_to_model(icp, volume, frames, pose0, z_near, z_far, normals=False):
             pose, scale = compose_pose(pose, icp.read(icp_amd.Memory.T))
         volume.integrate(cam, pose, depth, colour)
         yield pose.copy(), k, scale
+
+
+def track_to_volume(icp, volume, frames, pose0, max_iterations=20):
+    """track_to_model without the view, as a generator over `frames`.  The first frame is integrated at pose0.  Every later frame: the front
+    end writes it into M (rgbd.write), register_from registers M against the volume starting at the last pose, and the frame is integrated
+    at the new pose.  Yields (pose, Registration) per frame, (pose0, None) first."""
+    cam = rgbd.get_config(icp)
+    pose = _pose(pose0).copy()
+    first = True
+    for depth, colour in frames:
+        reg = None
+        if first:
+            first = False
+        else:
+            rgbd.write(icp, icp_amd.Memory.M, depth, colour)
+            reg = volume.register_from(icp, icp_amd.Memory.M, pose, max_iterations)
+            pose = reg.pose.copy()
+        volume.integrate(cam, pose, depth, colour)
+        yield pose.copy(), reg

@@ -387,6 +387,13 @@ namespace ICP
             if (n || m) check (icp_tsdf_extract_mesh (t, &o, n, cloud.data (), normals ? normals->data () : nullptr, &n, m, triangles.data (), &m));
             return m;
         }
+        /*! n float8 points of the camera's frame registered against the volume itself from pose12 (icp_tsdf_register); opt == nullptr: 20
+         *  iterations and the engine's default thresholds */
+        icp_tsdf_registration_t registerCloud (const float *cloud, uint32_t n, const float *pose12, const icp_tsdf_register_t *opt = nullptr)
+        { icp_tsdf_registration_t r; check (icp_tsdf_register (t, opt, cloud, n, pose12, &r)); return r; }
+        /*! the same of F or M (which = ICP_MEM_F / ICP_MEM_M) of an initialised handle, device to device (icp_tsdf_register_from) */
+        icp_tsdf_registration_t registerFrom (icp_handle h, int which, const float *pose12, const icp_tsdf_register_t *opt = nullptr)
+        { icp_tsdf_registration_t r; check (icp_tsdf_register_from (t, opt, h, which, pose12, &r)); return r; }
         /*! out12 = pose12 o (R (q), t) of the engine's T8; returns T8's scale */
         static float composePose (const float *pose12, const float *T8, float *out12)
         {

@@ -1156,13 +1156,67 @@ int icp_tsdf_extract_mesh (icp_tsdf_handle t, const icp_tsdf_surface_t *opt, uin
 /* Host only, no device needed: entry case_index of the case table — the number of triangles (0 .. 5) and their local edge ids, three a
  * triangle, 0 past them.  ICP_EINVAL for case_index > 255 or a NULL output. */
 int icp_tsdf_mesh_case (uint32_t case_index, uint32_t *n_triangles, uint8_t edges[15]);
+/* Registration against the volume itself (the SDF tracker of Bylow, Sturm, Kerl, Kahl and Cremers, RSS 2013; Canelhas et al. 2013): the
+ * residual of a moving point is the volume's own value at that point, the Jacobian the volume's own gradient there.  No view, no search
+ * structure, no correspondence, no normals.  tests/tsdf_register_ref.py restates it bit for bit.  The volume is never modified.
+ *    Inputs.  n moving points, float8 records [x y z 1 r g b 1] in the camera's frame, and pose12 (camera -> world, checked for finiteness
+ *    only).  State: R[9], t[3] in fp32 (from pose12), the iteration count k = 0, the flags done = singular = converged = 0.
+ *    Per point i, at the state's R, t:
+ *      1. It is VALID iff not (x == 0 && y == 0 && z == 0): the engine's invalid point.
+ *      2. w_a = ((R_a0 x + R_a1 y) + R_a2 z) + t_a in fp32: the ray cast's world point.
+ *      3. S = S (w) and G_a = S (w + voxel e_a) - S (w - voxel e_a) are the ray cast's sample and gradient: each of the seven samples has
+ *         its own cell and fractions, its own KNOWN test and its fp32 lerps along x, then y, then z; w_a + voxel and w_a - voxel in fp32.
+ *      4. It is a MEMBER iff it is valid, all seven samples are known and fabsf (S) < 1.f (NaN fails; a truncated value carries no distance).
+ *      5. In double, each operation on its own, converted from float first:  r = -((double) mu * S);
+ *         kg = (double) mu / ((double) voxel + (double) voxel);  g_a = G_a * kg;
+ *         c = w x g = (wy gz - wz gy, wz gx - wx gz, wx gy - wy gx);  J = (c, g).
+ *      6. Its 29 terms: J_a J_b for a <= b, row-major (21); J_a r (6); 1.0; r r.  A non-member contributes 29 exact zeros, selected and never
+ *         multiplied: a NaN coordinate makes no NaN.
+ *    Sums.  The plane system's two trees: the halving tree over blocks of 256 points, x[i] += x[i + h] for h = 128 .. 1 (points past n are
+ *    non-members), then the halving tree over the block partials zero-padded to the next power of two.  n <= 2^20.
+ *    Solve and step.  A from the first 21 sums (its upper triangle), b from the next six; x = (omega, tau) by the plane system's LDL^T under
+ *    its singularity rule (a pivot not finite or d_j <= 1e-12 A_jj), members == 0 being singular too.  Singular: the pose stays bit for
+ *    bit, singular = 1, done = 1.  Otherwise x is a world-frame increment, w' = w + omega x w + tau:
+ *      h = omega / 2 (omega_a * 0.5);  inv = 1.0 / sqrt (((hx hx + hy hy) + hz hz) + 1.0);  q = (x, y, z, w) = (hx inv, hy inv, hz inv, inv), as
+ *      the point-to-plane step forms it;  dR = the rotation matrix of q by icp_tsdf_compose_pose's formula (1 - 2 (y y + z z), 2 (x y - z w),
+ *      ..), q not normalised again;  R'_ab = (float) ((dR_a0 R_0b + dR_a1 R_1b) + dR_a2 R_2b);  t'_a = (float) (((dR_a0 t_0 + dR_a1 t_1) +
+ *      dR_a2 t_2) + tau_a), all in double and rounded once;  k = k + 1.
+ *      converged = done = 1 when the engine's two convergence tests hold for Tk = [(float) q | (float) tau, 1]:  |q_xyz| < q_w tan
+ *      (angle_threshold pi / 360) with q_w > 0, and |tau| < translation_threshold, norms in fp32 as (a a + b b) + c c and sqrtf.
+ *    A done state is left as it is by every later iteration.
+ * The record: pose12 from R, t; iterations = k; converged; singular; and of the last iteration evaluated, at the pose before its step:
+ * members, rmse = sqrt (sum r r / members) (0 without members), and sys = the 27 sums — the first 21 are the information matrix of the
+ * pose (J^T J, rotation first, then translation), in the order icp_quality_t uses, the last six J^T r.
+ * opt == NULL: max_iterations 20, angle_threshold 0.001 degrees, translation_threshold 0.01 — the defaults of the facades' icp_init.
+ * icp_tsdf_register takes the cloud from the host; icp_tsdf_register_from reads F or M (which = ICP_MEM_F / ICP_MEM_M) of registration 0
+ * of an initialised handle on the volume's device, device to device, after the handle's stream has drained, and changes nothing in the
+ * handle.  A call enqueues max_iterations pairs of launches (k_tsdf_reg_moments, k_tsdf_reg_finalize) on the volume's stream, synchronises
+ * once and reads the record: no host round trip between iterations.  Both are blocking; a refused call leaves the volume and the handle
+ * as they were, the reason in icp_tsdf_last_error.  ICP_EINVAL for a null pointer, n == 0 or n > 2^20 (for _from: the handle's m), a
+ * non-finite pose, options out of range, `which` other than F / M, a handle on another device; ICP_ESTATE for an uninitialised handle or
+ * tracked frames in flight. */
+typedef struct {
+    uint32_t max_iterations;                /* 1 .. 256 */
+    double   angle_threshold;               /* degrees, finite, >= 0 */
+    double   translation_threshold;         /* engine units, finite, >= 0 */
+} icp_tsdf_register_t;
+typedef struct {
+    float    pose12[12];
+    uint32_t iterations, converged, singular, members;
+    double   rmse;
+    double   sys[27];
+} icp_tsdf_registration_t;
+int icp_tsdf_register (icp_tsdf_handle t, const icp_tsdf_register_t *opt, const void *cloud_nx8, uint32_t n, const float *pose12, icp_tsdf_registration_t *out);
+int icp_tsdf_register_from (icp_tsdf_handle t, const icp_tsdf_register_t *opt, icp_handle h, int which, const float *pose12, icp_tsdf_registration_t *out);
 /* Diagnostic (tools/diag/tsdf_time.py): `reps` launches of one kernel between two events on the volume's stream, after one untimed launch.
  * what = 0: k_tsdf_integrate of (depth, rgb) at pose12 — the volume is left as reps + 1 integrations leave it;  what = 1: k_tsdf_raycast as
  * icp_tsdf_raycast (cam, pose12, z_near, z_far, side) runs it, into scratch (depth, rgb unused);  what = 2: the launches of one
  * icp_tsdf_extract_surface with normals and min_weight 1 as a group, every member into scratch;  what = 3: the two scan launches of
  * that group alone;  what = 4: its last two launches (the members' edges, their records) alone (for 2 .. 7 every argument but reps is unused, cam and
  * pose12 may be NULL);  what = 5: the launches of one icp_tsdf_extract_mesh with normals and min_weight 1 as a group, every vertex and
- * triangle into scratch;  what = 6: its cell sweep alone;  what = 7: its triangle pass alone.
+ * triangle into scratch;  what = 6: its cell sweep alone;  what = 7: its triangle pass alone;  what = 8: the two launches of one iteration of
+ * icp_tsdf_register as a group, over the host cloud `depth` points to (side records of 8 floats, 1 .. 2^20) from pose12, the state held at
+ * that pose with `done` clear (every group does the same work; the record goes to scratch);  what = 9: k_tsdf_reg_moments of that group alone.
  * Microseconds per launch (per group). */
 int icp_tsdf_time (icp_tsdf_handle t, int what, const icp_rgbd_t *cam, const float *pose12, const uint16_t *depth, const uint8_t *rgb, float z_near, float z_far,
                    uint32_t side, uint32_t reps, float *us_per_launch);

@@ -16,7 +16,13 @@
     (what = 5) beside those of extract_surface with normals (what = 2) from the same run, the cell sweep (what = 6) and the triangle
     pass (what = 7) alone, each against one read of {D, W} at the HBM rate; the blocking call with both capacities given and with the
     counting call first; the vertex and triangle counts.
-    python tools/diag/tsdf_time.py [--reps N] [--skip-512] [--surface | --mesh]"""
+  - with --register (and nothing else then): a cloud registered against the volume itself (icp_tsdf_register) on the same scene at 256^3:
+    the two launches of one iteration as a group (what = 8) and k_tsdf_reg_moments alone (what = 9) over the 16 384 lattice landmarks
+    and over the dense 307 200 pixels of a frame 1 degree / 9.9 mm from the start pose; a blocking register of 10 iterations; the
+    end-to-end error of that registration; and in the same run, on the same volume, the route it replaces: a blocking raycast_to with
+    normals, buildRBC, a point-to-plane iteration, and a blocking track_to_model step beside a blocking register_from of 10 iterations,
+    each with its end-to-end error.  Written to profiles/tsdf_register_time.txt as well.
+    python tools/diag/tsdf_time.py [--reps N] [--skip-512] [--surface | --mesh | --register]"""
 import argparse
 import os
 import statistics
@@ -125,17 +131,107 @@ def mesh(a):
               % (n, one, two, cnt, (nv * 48 + nt * 12) / 1e6), flush=True)
 
 
+def register(a):
+    sys.path[:0] = [os.path.join(ROOT, "tests")]
+    import rgbd_ref as R                # noqa: E402
+    import tsdf_ref as T                # noqa: E402
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    a.skip_512 = True
+    d = T.corner_camera(width=640, height=480, fx=600.0, cx=319.5, cy=239.5, x0=2, y0=3, step_x=5, step_y=3)
+    start = T.look_at(T.EYE_CAST)
+    true = T.rotate_pose(start, (0.3, 1.0, 0.2), 1.0, (8, -5, 3))
+    depth, colour = T.render_corner(true, d)[:2]
+    dense = R.cloud(depth, colour, d)
+    pose = start.reshape(12).astype(np.float32)
+
+    def errors(p):
+        P = np.asarray(p, np.float64).reshape(3, 4)
+        c = (np.trace(P[:, :3].T @ true[:, :3]) - 1.0) / 2.0
+        return np.degrees(np.arccos(np.clip(c, -1.0, 1.0))), np.linalg.norm(P[:, 3] - true[:, 3])
+
+    for n, v in corner_volumes(a):
+        for name, cloud in (("16 384 lattice landmarks", R.landmarks(depth, colour, d, 128)[0]), ("307 200 dense pixels", dense)):
+            group = median(lambda: v.time_register(8, cloud, pose, reps=20), a.reps)
+            moments = median(lambda: v.time_register(9, cloud, pose, reps=20), a.reps)
+            call = blocking(lambda: v.register(cloud, pose, 10, 0.0, 0.0), a.reps)
+            rec = v.register(cloud, pose, 10, 0.0, 0.0)
+            say("register %d^3 %-26s one iteration (two launches) %8.2f us   k_tsdf_reg_moments alone %8.2f us   (%d blocks, %d members)"
+                % (n, name, group, moments, -(-cloud.shape[0] // 256), rec.members))
+            say("register %d^3 %-26s blocking register of 10 iterations, host cloud %9.2f us   ends %.4f degrees / %.3f mm from the truth (start %.4f / %.3f), rmse %.3f"
+                % ((n, name, call) + errors(rec.pose) + errors(pose) + (rec.rmse,)))
+        # the route this replaces, in the same run on the same volume: the view of the volume into F with normals, buildRBC, point-to-plane
+        # iterations with a search (the handle of tests/test_gpu_tsdf.py: 128 x 128 landmarks here, 256 representatives, point weight 0.05)
+        import icp_checks as K              # noqa: E402
+        Mem = icp_amd.Memory
+        g = icp_amd.ICP(0)
+        g.init(16384, 256, 2e2, 1e-6)
+        rgbd.set_config(g, rgbd.RGBDConfig(**d))
+        g.set_normals(K.GIVEN, 0)
+        g.set_error_metric(K.P2PL, 0.05)
+        g.set_rejection(invalid=True)
+        z_near, z_far = 200.0, 1600.0
+        cast = blocking(lambda: v.raycast_to(g, Mem.F, pose, z_near, z_far, normals=True), a.reps)
+        cast_kernel = median(lambda: v.time_kernel(1, rgbd.RGBDConfig(**d), pose, z_near=z_near, z_far=z_far, side=128, reps=20), a.reps)
+        build = blocking(lambda: (g.buildRBC(), g.sync()), a.reps)
+        rgbd.write(g, Mem.M, depth, colour)
+
+        def twenty_steps():
+            for _ in range(20):
+                g.step()
+            g.sync()
+
+        g.reset_transform()
+        step20 = blocking(twenty_steps, a.reps) / 20.0
+        step1 = blocking(lambda: (g.step(), g.sync()), a.reps)
+        say("route    %d^3 blocking raycast_to F with normals %8.2f us (k_tsdf_raycast on the lattice alone %8.2f us)   buildRBC + sync %8.2f us   one point-to-plane iteration: %8.2f us blocking, %8.2f us each of 20 enqueued"
+            % (n, cast, cast_kernel, build, step1, step20))
+
+        def model_step():
+            v.raycast_to(g, Mem.F, pose, z_near, z_far, normals=True)
+            g.buildRBC()
+            rgbd.write(g, Mem.M, depth, colour)
+            g.reset_transform()
+            k = g.run()
+            return tsdf.compose_pose(pose, g.read(Mem.T))[0], k
+
+        def volume_step():
+            rgbd.write(g, Mem.M, depth, colour)
+            return v.register_from(g, Mem.M, pose, 10, 0.0, 0.0)
+
+        t_model = blocking(model_step, a.reps)
+        p_model, k_model = model_step()
+        t_volume = blocking(volume_step, a.reps)
+        t_from = blocking(lambda: v.register_from(g, Mem.M, pose, 10, 0.0, 0.0), a.reps)
+        rec = volume_step()
+        say("step     %d^3 blocking track_to_model step without integrate (raycast_to, buildRBC, write M, run: k = %d, compose) %9.2f us   ends %.4f degrees / %.3f mm from the truth"
+            % ((n, k_model, t_model) + errors(p_model)))
+        say("step     %d^3 blocking track_to_volume step without integrate (write M, register_from of 10 iterations)          %9.2f us   ends %.4f degrees / %.3f mm from the truth   (register_from alone %9.2f us, %d members)"
+            % ((n, t_volume) + errors(rec.pose) + (t_from, rec.members)))
+        g.close()
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "tsdf_register_time.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--skip-512", action="store_true")
     ap.add_argument("--surface", action="store_true")
     ap.add_argument("--mesh", action="store_true")
+    ap.add_argument("--register", action="store_true")
     a = ap.parse_args()
     if a.surface:
         return surface(a)
     if a.mesh:
         return mesh(a)
+    if a.register:
+        return register(a)
     depth, colour = frame()
     cam = rgbd.RGBDConfig()
     print("frame: %d of %d pixels valid, depth %d .. %d" % ((depth != 0).sum(), depth.size, depth[depth != 0].min(), depth.max()), flush=True)
