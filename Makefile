@@ -6,7 +6,7 @@ ARCH     ?= gfx950
 EXTRA    ?=
 BUILD    ?= build
 HIPFLAGS ?= $(EXTRA) -O3 -std=c++17 -fPIC -fvisibility=hidden --offload-arch=$(ARCH) -ffp-contract=off -fno-fast-math -Wall -Wno-unused-result -pthread -mllvm -amdgpu-kernarg-preload-count=14
-SRC      := icp_amd/csrc/icp_kernels.hip icp_amd/csrc/icp_search_dense.hip icp_amd/csrc/icp_search_rej.hip icp_amd/csrc/icp_trim.hip icp_amd/csrc/icp_p2pl.hip icp_amd/csrc/icp_robust.hip icp_amd/csrc/icp_gicp.hip icp_amd/csrc/icp_symmetric.hip icp_amd/csrc/icp_unique.hip icp_amd/csrc/icp_median.hip icp_amd/csrc/icp_adaptive_trim.hip icp_amd/csrc/icp_pair_filter.hip icp_amd/csrc/icp_reciprocal.hip icp_amd/csrc/icp_projective.hip icp_amd/csrc/icp_quality.hip icp_amd/csrc/icp_pairs.hip icp_amd/csrc/icp_build.hip icp_amd/csrc/icp_capi.hip icp_amd/csrc/icp_run.hip icp_amd/csrc/icp_track.hip icp_amd/csrc/icp_reduce_scan.hip icp_amd/csrc/icp_standalone.hip icp_amd/csrc/icp_synth.cpp icp_amd/csrc/icp_batch.cpp icp_amd/csrc/icp_pyramid.hip icp_amd/csrc/icp_rgbd.hip icp_amd/csrc/icp_tsdf.hip icp_amd/csrc/icp_tsdf_surface.hip icp_amd/csrc/icp_tsdf_register.hip
+SRC      := icp_amd/csrc/icp_kernels.hip icp_amd/csrc/icp_search_dense.hip icp_amd/csrc/icp_search_rej.hip icp_amd/csrc/icp_trim.hip icp_amd/csrc/icp_p2pl.hip icp_amd/csrc/icp_robust.hip icp_amd/csrc/icp_gicp.hip icp_amd/csrc/icp_symmetric.hip icp_amd/csrc/icp_unique.hip icp_amd/csrc/icp_median.hip icp_amd/csrc/icp_adaptive_trim.hip icp_amd/csrc/icp_pair_filter.hip icp_amd/csrc/icp_reciprocal.hip icp_amd/csrc/icp_projective.hip icp_amd/csrc/icp_quality.hip icp_amd/csrc/icp_pairs.hip icp_amd/csrc/icp_build.hip icp_amd/csrc/icp_capi.hip icp_amd/csrc/icp_run.hip icp_amd/csrc/icp_track.hip icp_amd/csrc/icp_reduce_scan.hip icp_amd/csrc/icp_standalone.hip icp_amd/csrc/icp_synth.cpp icp_amd/csrc/icp_batch.cpp icp_amd/csrc/icp_pyramid.hip icp_amd/csrc/icp_rgbd.hip icp_amd/csrc/icp_tsdf.hip icp_amd/csrc/icp_tsdf_surface.hip icp_amd/csrc/icp_tsdf_register.hip icp_amd/csrc/icp_tsdf_shift.hip
 HDR      := icp_amd/csrc/icp_device.h icp_amd/csrc/icp_kernels.h icp_amd/csrc/icp_rbc_set.h icp_amd/csrc/icp_search.h icp_amd/csrc/icp_search_select.h icp_amd/csrc/icp_host.h icp_amd/csrc/icp_cguard.h icp_amd/csrc/icp_trim_apply.h icp_amd/csrc/icp_select.h icp_amd/csrc/icp_plane_moments.h icp_amd/csrc/icp_pair_rule.h icp_amd/csrc/icp_normal_rule.h icp_amd/csrc/icp_rgbd.h icp_amd/csrc/icp_tsdf.h icp_amd/csrc/icp_ldlt.h include/icp_amd.h
 LIB      ?= icp_amd/libicp_amd.so
 OBJ      := $(patsubst icp_amd/csrc/%,$(BUILD)/%.o,$(SRC))
@@ -47,6 +47,9 @@ tsdf_mesh_facade_test: $(LIB) tests/cpp/tsdf_mesh_facade_test.cpp include/ICP/al
 
 tsdf_register_facade_test: $(LIB) tests/cpp/tsdf_register_facade_test.cpp include/ICP/algorithms.hpp
 	g++ -O2 -std=c++17 -Wall -ffp-contract=off -Iinclude -o tests/cpp/tsdf_register_facade_test tests/cpp/tsdf_register_facade_test.cpp -Licp_amd -licp_amd -Wl,-rpath,'$$ORIGIN/../../icp_amd'
+
+tsdf_shift_facade_test: $(LIB) tests/cpp/tsdf_shift_facade_test.cpp include/ICP/algorithms.hpp
+	g++ -O2 -std=c++17 -Wall -ffp-contract=off -Iinclude -o tests/cpp/tsdf_shift_facade_test tests/cpp/tsdf_shift_facade_test.cpp -Licp_amd -licp_amd -Wl,-rpath,'$$ORIGIN/../../icp_amd'
 
 icpreg_test: $(LIB) tests/cpp/icpreg_test.cpp include/ocl_icp_reg.hpp include/ocl_icp_sbs.hpp include/ICP/algorithms.hpp
 	g++ -O2 -std=c++17 -Iinclude -o tests/cpp/icpreg_test tests/cpp/icpreg_test.cpp -Licp_amd -licp_amd -Wl,-rpath,'$$ORIGIN/../../icp_amd'
@@ -98,7 +101,7 @@ asan: tests/cpp/asan_host
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=0 UBSAN_OPTIONS=print_stacktrace=1 tests/cpp/asan_host
 
 clean:
-	rm -rf build; rm -f $(LIB) examples/registration examples/step_by_step tests/cpp/facade_test tests/cpp/pyramid_facade_test tests/cpp/pairs_facade_test tests/cpp/rgbd_facade_test tests/cpp/tsdf_facade_test tests/cpp/tsdf_surface_facade_test tests/cpp/tsdf_mesh_facade_test tests/cpp/tsdf_register_facade_test tests/cpp/capi_example tests/cpp/icpreg_test tests/cpp/asan_host tests/cpp/asan_oracle.o tests/cpp/search_select_test tests/cpp/rbc_set_test tests/cpp/mom_layout_test
+	rm -rf build; rm -f $(LIB) examples/registration examples/step_by_step tests/cpp/facade_test tests/cpp/pyramid_facade_test tests/cpp/pairs_facade_test tests/cpp/rgbd_facade_test tests/cpp/tsdf_facade_test tests/cpp/tsdf_surface_facade_test tests/cpp/tsdf_mesh_facade_test tests/cpp/tsdf_register_facade_test tests/cpp/tsdf_shift_facade_test tests/cpp/capi_example tests/cpp/icpreg_test tests/cpp/asan_host tests/cpp/asan_oracle.o tests/cpp/search_select_test tests/cpp/rbc_set_test tests/cpp/mom_layout_test
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean asan examples search_select_test rbc_set_test mom_layout_test

@@ -83,8 +83,13 @@ struct icp_tsdf_context {
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    icp_tsdf_t cfg {};
+    icp_tsdf_t cfg {};                           // (origin: the window's current one)
     icp_tsdf_dev v {};
+    // the moving window (icp_tsdf_shift.hip): the origin given at create, the cumulative shift in voxels, and the second buffer of the
+    // volume's size a shift writes into before v.dw / v.col swap with it (allocated by the first shift, kept until destroy)
+    float base[3] = { 0.f, 0.f, 0.f };
+    int32_t win[3] = { 0, 0, 0 };
+    float2 *dw2 = nullptr; float4 *col2 = nullptr;
     // device copies of the images of an integration and the results of a ray cast to the host (grown when a call needs more)
     void *dDepth = nullptr, *dRgb = nullptr, *dOut = nullptr, *dNrm = nullptr;
     size_t depth_cap = 0, rgb_cap = 0, out_cap = 0, nrm_cap = 0;
@@ -123,6 +128,11 @@ int tsdf_register_run (icp_tsdf_context *t, const icp_tsdf_register_t *opt, cons
 // icp_tsdf_time, what = 8, 9: `reps` iterations' launches over the host cloud of n records (part 0: both launches, 1: k_tsdf_reg_moments alone)
 // with the state held at pose12
 int tsdf_time_register (icp_tsdf_context *t, int part, const void *cloud, uint32_t n, const float *pose12, uint32_t reps, float *us_per_group);
+// icp_tsdf_time, what = 10: `reps` launches of k_tsdf_shift by +s, -s, +s, .. from the live buffers into the second ones, which never swap in:
+// the volume stays as it is
+int tsdf_time_shift (icp_tsdf_context *t, const int32_t *s, uint32_t reps, float *us_per_launch);
+// icp_tsdf_time, what = 11: `reps` groups of the launches of one icp_tsdf_extract_surface_region (normals on, min_weight 1) for the kept box of s, OUTSIDE
+int tsdf_time_region (icp_tsdf_context *t, const int32_t *s, uint32_t reps, float *us_per_group);
 }
 
 #define TSDFCHK(t, expr)                                                                                       \

@@ -1,5 +1,5 @@
 // icp_tsdf.hip — frame-to-model: a truncated signed distance volume fused and ray-cast on the device (the rule: include/icp_amd.h,
-// "Frame-to-model"; tests/tsdf_ref.py restates it).  The volume's surface as a point cloud: icp_tsdf_surface.hip.  The reference has no model: each of its frames is registered against the previous one.
+// "Frame-to-model"; tests/tsdf_ref.py restates it).  The volume's surface as a point cloud: icp_tsdf_surface.hip.  The moving window: icp_tsdf_shift.hip.  The reference has no model: each of its frames is registered against the previous one.
 //
 //   k_tsdf_integrate  one lane per voxel, lanes along i: a block of 256 owns 64 i x 4 j of one k, so every access to the volume is a
 //                     wave-wide coalesced 8-byte {D, W} (16-byte colour) vector access.  A voxel the frame does not change is not stored.
@@ -264,7 +264,7 @@ int icp_tsdf_destroy (icp_tsdf_handle t) try
     if (!t) return ICP_EINVAL;
     (void) hipSetDevice (t->device);
     if (t->stream) (void) hipStreamSynchronize (t->stream);
-    for (void *q : { (void *) t->v.dw, (void *) t->v.col, t->dDepth, t->dRgb, t->dOut, t->dNrm, t->dSurf, t->dEdge, t->dMesh, t->dTri, t->dMeshTab, t->dRegCloud, t->dRegWork }) if (q) (void) hipFree (q);
+    for (void *q : { (void *) t->v.dw, (void *) t->v.col, (void *) t->dw2, (void *) t->col2, t->dDepth, t->dRgb, t->dOut, t->dNrm, t->dSurf, t->dEdge, t->dMesh, t->dTri, t->dMeshTab, t->dRegCloud, t->dRegWork }) if (q) (void) hipFree (q);
     if (t->ev0) (void) hipEventDestroy (t->ev0);
     if (t->ev1) (void) hipEventDestroy (t->ev1);
     if (t->stream) (void) hipStreamDestroy (t->stream);
@@ -288,6 +288,7 @@ int icp_tsdf_create (icp_tsdf_handle *out, int device, const icp_tsdf_t *cfg) tr
         return tsdf_fail (nullptr, ICP_ENODEVICE, std::string ("icp_tsdf_create: device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
     icp_tsdf_context *t = new icp_tsdf_context ();
     t->device = device; t->cfg = *cfg;
+    for (int a = 0; a < 3; ++a) t->base[a] = cfg->origin[a];
     auto give_up = [&] (int code, const std::string &msg) { (void) hipGetLastError (); icp_tsdf_destroy (t); return tsdf_fail (nullptr, code, msg); };
     if (hipSetDevice (device) != hipSuccess || hipStreamCreateWithFlags (&t->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate (&t->ev0) != hipSuccess || hipEventCreate (&t->ev1) != hipSuccess) return give_up (ICP_EHIP, "icp_tsdf_create: stream and events");
@@ -306,7 +307,7 @@ int icp_tsdf_reset (icp_tsdf_handle t) try
 {
     if (!t) return ICP_EINVAL;
     TSDFCHK (t, hipSetDevice (t->device));
-    return zero_volume (t);
+    return zero_volume (t);                         // (the live buffers; the window of icp_tsdf_shift stays where it is)
 }
 ICP_CATCH_ALL
 
@@ -405,7 +406,9 @@ int icp_tsdf_time (icp_tsdf_handle t, int what, const icp_rgbd_t *cam, const flo
                            uint32_t side, uint32_t reps, float *us_per_launch) try
 {
     if (!t) return ICP_EINVAL;
-    if (!us_per_launch || reps == 0u || what < 0 || what > 9) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_time: bad arguments");
+    if (!us_per_launch || reps == 0u || what < 0 || what > 11) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_time: bad arguments");
+    if (what == 11) return tsdf_time_region (t, reinterpret_cast<const int32_t *> (depth), reps, us_per_launch);
+    if (what == 10) return tsdf_time_shift (t, reinterpret_cast<const int32_t *> (depth), reps, us_per_launch);
     if (what >= 8) return tsdf_time_register (t, what - 8, depth, side, pose12, reps, us_per_launch);
     if (what >= 5) return tsdf_time_mesh (t, what - 5, reps, us_per_launch);
     if (what >= 2) return tsdf_time_surface (t, what - 2, reps, us_per_launch);

@@ -26,6 +26,9 @@
 //                           every row, so one in a wave of 64 i: gathered from the scatter's lanes, the members' loads were instructions
 //                           with one lane in use, and that pass was measured at 165 us for 465 000 members, 78 us without the gradients;
 //                           here 64 members share an instruction.)
+// A region (icp_tsdf_extract_surface_region; the rule: include/icp_amd.h, "Moving volume") is the same four passes with the box test in the
+// sweep's member predicate (k_tsdf_surface_count_region), launched over the blocks that can hold a member of the wanted kind alone; the
+// counts of the other blocks are cleared, so the scan, the scatter and the points are the full extraction's launches as they are.
 // Nothing waits for another workgroup inside a launch: the order between the passes is the stream's.  The counts are integer sums and a
 // position is a function of the predicate alone: no atomics, and the result does not depend on the launch shape.
 //
@@ -106,6 +109,64 @@ __global__ __launch_bounds__ (BLOCK) void k_tsdf_surface_count (tsdf_surface_arg
     if (lane == 0u) { s_wave[wave] = c; a.wave_cnt[blockIdx.x * WAVES + wave] = steps; }
     __syncthreads ();
     if (tid == 0u) a.blk_cnt[blockIdx.x] = (s_wave[0] + s_wave[1]) + (s_wave[2] + s_wave[3]);
+}
+
+// A region of icp_tsdf_extract_surface_region: the box lo_a <= idx_a < hi_a and the first block of the sweep's launch (the blocks in
+// front of it can hold no member of the wanted kind).
+struct tsdf_region_dev { uint32_t lo[3], hi[3], first_blk; };
+struct tsdf_region_args { tsdf_surface_args a; tsdf_region_dev r; };
+
+// The sweep of a region: k_tsdf_surface_count with the box test in the member predicate, the wanted kind as a template parameter.  Member
+// (v, ax) is INSIDE iff v and v + e_ax both lie in the box, and is kept iff that is the kind wanted.  A voxel that can be the low end of no
+// member of the wanted kind — for INSIDE one with no edge that ends in the box; for OUTSIDE one in the box whose every edge ends in the
+// box — is not loaded: a wave of such voxels makes no load at all.  (A kernel of its own, not a switch in k_tsdf_surface_count's body: with
+// the body shared, the compiler reassociates the full extraction's integer sums differently, and that kernel is to stay the code it is.)
+template <bool OUTSIDE>
+__global__ __launch_bounds__ (BLOCK) void k_tsdf_surface_count_region (tsdf_region_args q)
+{
+    __shared__ uint32_t s_wave[WAVES];
+    const tsdf_surface_args &a = q.a;
+    const tsdf_region_dev &r = q.r;
+    const icp_tsdf_dev &v = a.v;
+    const uint32_t blk = blockIdx.x + r.first_blk;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, g0 = blk * RUN + tid;
+    float2 own[STEPS];                                     // all steps in flight together
+    bool in[STEPS][3];                                     // edge (v, ax) would be INSIDE
+#pragma unroll
+    for (uint32_t s = 0; s < STEPS; ++s) {
+        const uint32_t g = min (g0 + s * BLOCK, a.n_vox - 1u);
+        const uint32_t row = g / v.nx, i = g - row * v.nx, k = row / v.ny, j = row - k * v.ny;
+        const bool vin = i >= r.lo[0] && i < r.hi[0] && j >= r.lo[1] && j < r.hi[1] && k >= r.lo[2] && k < r.hi[2];
+        in[s][0] = vin && i + 1u < r.hi[0]; in[s][1] = vin && j + 1u < r.hi[1]; in[s][2] = vin && k + 1u < r.hi[2];
+        const bool can = OUTSIDE ? !(vin && (in[s][0] || i + 1u >= v.nx) && (in[s][1] || j + 1u >= v.ny) && (in[s][2] || k + 1u >= v.nz))
+                                 : (in[s][0] || in[s][1] || in[s][2]);
+        own[s] = make_float2 (0.f, 0.f);                   // (W = 0: not usable)
+        if (can) own[s] = v.dw[g];
+    }
+    const uint32_t off[3] = { 1u, v.nx, v.nx * v.ny };
+    uint32_t c = 0u, steps = 0u;
+#pragma unroll
+    for (uint32_t s = 0; s < STEPS; ++s) {
+        const uint32_t g = g0 + s * BLOCK;
+        bool m[3] = { false, false, false };
+        if (g < a.n_vox && usable (own[s], a.min_weight)) {
+            const uint32_t row = g / v.nx, i = g - row * v.nx, k = row / v.ny, j = row - k * v.ny;
+            const bool inside[3] = { i + 1u < v.nx, j + 1u < v.ny, k + 1u < v.nz };
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                if (!inside[ax] || in[s][ax] == OUTSIDE) continue;      // (no such edge, or not of the wanted kind)
+                const float2 e = v.dw[g + off[ax]];
+                m[ax] = usable (e, a.min_weight) && ((own[s].x > 0.f) != (e.x > 0.f));
+            }
+        }
+        const mask64 b0 = __ballot (m[0]), b1 = __ballot (m[1]), b2 = __ballot (m[2]);
+        const uint32_t n = (uint32_t) (__popcll (b0) + __popcll (b1) + __popcll (b2));
+        c += n; steps |= n << (8u * s);
+        if (n && lane < 3u) a.masks[((size_t) (blk * WAVES + wave) * STEPS + s) * 3u + lane] = lane == 0u ? b0 : lane == 1u ? b1 : b2;
+    }
+    if (lane == 0u) { s_wave[wave] = c; a.wave_cnt[blk * WAVES + wave] = steps; }
+    __syncthreads ();
+    if (tid == 0u) a.blk_cnt[blk] = (s_wave[0] + s_wave[1]) + (s_wave[2] + s_wave[3]);
 }
 
 // out[i] = in[first word of the tile] + .. + in[i - 1] for the n words in tiles of SCAN_TILE, sums[tile] = the tile's sum
@@ -433,6 +494,72 @@ int count_and_reserve (icp_tsdf_context *t, tsdf_surface_args &a, const surface_
     return reserve_records (t, a, normals);
 }
 
+// ---- a region's host side ---------------------------------------------------------------------------------------------------------------------
+
+// the box on the device and the blocks [first_blk, first_blk + nb) of the sweep that can hold a member of the wanted kind
+struct region_plan { tsdf_region_dev r; bool outside; uint32_t nb; };
+
+// INSIDE: a member's low end lies in the box, so between the box's first and last voxel in linear order.  OUTSIDE: where the box spans x
+// and y, the slices lo_z <= k < hi_z - 1 (and k = nz - 1 with them if hi_z = nz) hold INSIDE members only; if what is left is one run of
+// slices at either end of the volume — what the kept box of a shift along z leaves — the sweep covers that run alone.
+region_plan plan_region (const icp_tsdf_t &c, const icp_tsdf_region_t &g, const surface_plan &p)
+{
+    region_plan q {};
+    for (int a = 0; a < 3; ++a) { q.r.lo[a] = g.lo[a]; q.r.hi[a] = g.hi[a]; }
+    q.outside = g.mode == ICP_TSDF_REGION_OUTSIDE;
+    const bool empty = g.lo[0] == g.hi[0] || g.lo[1] == g.hi[1] || g.lo[2] == g.hi[2];
+    const uint32_t slice = c.nx * c.ny;
+    uint32_t b0 = 0u, b1 = p.nblk;
+    if (!q.outside) {
+        if (empty) b1 = 0u;
+        else {
+            b0 = ((g.lo[2] * c.ny + g.lo[1]) * c.nx + g.lo[0]) / RUN;
+            b1 = (((g.hi[2] - 1u) * c.ny + (g.hi[1] - 1u)) * c.nx + (g.hi[0] - 1u)) / RUN + 1u;
+        }
+    } else if (!empty && g.lo[0] == 0u && g.hi[0] == c.nx && g.lo[1] == 0u && g.hi[1] == c.ny) {
+        const uint32_t in_end = g.hi[2] == c.nz ? c.nz : g.hi[2] - 1u;                // slices lo_z <= k < in_end hold no OUTSIDE member
+        if (g.lo[2] == 0u && in_end == c.nz) b1 = 0u;                                // (the full box)
+        else if (g.lo[2] == 0u) b0 = in_end * slice / RUN;
+        else if (in_end == c.nz) b1 = (g.lo[2] * slice - 1u) / RUN + 1u;
+    }
+    q.r.first_blk = b0; q.nb = b1 - b0;
+    return q;
+}
+
+// the count of the region's members and the position of every block's first one: the blocks the sweep leaves out count 0
+hipError_t launch_region_count_and_scan (const tsdf_surface_args &a, const region_plan &q, const surface_plan &p, hipStream_t s)
+{
+    if (q.nb != p.nblk) {                           // (the wave counts and the block counts lie side by side: plan_surface)
+        const hipError_t e = hipMemsetAsync (p.wave_cnt, 0, ((size_t) p.nblk * WAVES + p.nblk) * sizeof (uint32_t), s);
+        if (e != hipSuccess) return e;
+    }
+    if (q.nb && q.outside) hipLaunchKernelGGL (k_tsdf_surface_count_region<true>, dim3 (q.nb), dim3 (BLOCK), 0, s, tsdf_region_args { a, q.r });
+    else if (q.nb) hipLaunchKernelGGL (k_tsdf_surface_count_region<false>, dim3 (q.nb), dim3 (BLOCK), 0, s, tsdf_region_args { a, q.r });
+    launch_scan (p, s);
+    return hipSuccess;
+}
+
+int count_region_and_reserve (icp_tsdf_context *t, tsdf_surface_args &a, const region_plan &q, const surface_plan &p, uint32_t capacity, bool normals, uint32_t *total)
+{
+    TSDFCHK (t, launch_region_count_and_scan (a, q, p, t->stream));
+    TSDFCHK (t, hipGetLastError ());
+    TSDFCHK (t, hipMemcpyAsync (total, p.count, sizeof (uint32_t), hipMemcpyDeviceToHost, t->stream));
+    TSDFCHK (t, hipStreamSynchronize (t->stream));
+    a.limit = std::min (*total, capacity);
+    return reserve_records (t, a, normals);
+}
+
+const char *region_refusal (const icp_tsdf_t &c, const icp_tsdf_region_t &g)
+{
+    const uint32_t n[3] = { c.nx, c.ny, c.nz };
+    for (int a = 0; a < 3; ++a) {
+        if (g.lo[a] > g.hi[a]) return "lo must not exceed hi";
+        if (g.hi[a] > n[a]) return "hi must not exceed the volume's size";
+    }
+    if (g.mode > 1u) return "mode must be ICP_TSDF_REGION_INSIDE or ICP_TSDF_REGION_OUTSIDE";
+    return nullptr;
+}
+
 // ---- the mesh's host side --------------------------------------------------------------------------------------------------------------------
 
 // The case table by its rule (include/icp_amd.h, "Mesh extraction": the case table; tests/tsdf_mesh_ref.py generates it again).
@@ -622,6 +749,24 @@ int tsdf_time_surface (icp_tsdf_context *t, int part, uint32_t reps, float *us_p
     }, us_per_group);
 }
 
+int tsdf_time_region (icp_tsdf_context *t, const int32_t *s, uint32_t reps, float *us_per_group)
+{
+    if (!s) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_time: what = 11 takes the three int32 of the shift through `depth`");
+    icp_tsdf_region_t box;
+    if (icp_tsdf_kept_box (&t->cfg, s, &box) != ICP_OK) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_time: the kept box");
+    TSDFCHK (t, hipSetDevice (t->device));
+    surface_plan p;
+    int rc = plan_surface (t, &p); if (rc) return rc;
+    const region_plan q = plan_region (t->cfg, box, p);
+    tsdf_surface_args a = args_of (t, p, 1.f);
+    uint32_t total = 0u;
+    if ((rc = count_region_and_reserve (t, a, q, p, UINT32_MAX, true, &total))) return rc;      // (untimed, as above)
+    return time_groups (t, reps, [&] () {
+        (void) launch_region_count_and_scan (a, q, p, t->stream);
+        if (a.limit) launch_scatter (a, p, t->stream);
+    }, us_per_group);
+}
+
 int tsdf_time_mesh (icp_tsdf_context *t, int part, uint32_t reps, float *us_per_group)
 {
     TSDFCHK (t, hipSetDevice (t->device));
@@ -664,6 +809,37 @@ int icp_tsdf_extract_surface (icp_tsdf_handle t, const icp_tsdf_surface_t *opt, 
     tsdf_surface_args a = args_of (t, p, o.min_weight);
     uint32_t total = 0u;
     if ((rc = count_and_reserve (t, a, p, capacity, o.normals != 0u, &total))) return rc;
+    if (a.limit) {
+        launch_scatter (a, p, t->stream);
+        TSDFCHK (t, hipGetLastError ());
+        TSDFCHK (t, hipMemcpyAsync (cloud_out, t->dOut, (size_t) a.limit * 32u, hipMemcpyDeviceToHost, t->stream));
+        if (a.nrm) TSDFCHK (t, hipMemcpyAsync (normals_out, t->dNrm, (size_t) a.limit * 16u, hipMemcpyDeviceToHost, t->stream));
+        TSDFCHK (t, hipStreamSynchronize (t->stream));
+    }
+    *count = total;
+    return ICP_OK;
+}
+ICP_CATCH_ALL
+
+int icp_tsdf_extract_surface_region (icp_tsdf_handle t, const icp_tsdf_surface_t *opt, const icp_tsdf_region_t *region, uint32_t capacity, void *cloud_out,
+                                     float *normals_out, uint32_t *count) try
+{
+    if (!t) return ICP_EINVAL;
+    if (!count) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_extract_surface_region: count is required");
+    if (!region) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_extract_surface_region: region is required");
+    const icp_tsdf_surface_t o = opt ? *opt : icp_tsdf_surface_t { 1.f, 0u };
+    if (!(std::isfinite (o.min_weight) && o.min_weight >= 1.f)) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_extract_surface_region: min_weight must be finite and >= 1");
+    if (o.normals > 1u) return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_extract_surface_region: normals must be 0 or 1");
+    if (capacity && (!cloud_out || (o.normals && !normals_out)))
+        return tsdf_fail (t, ICP_EINVAL, "icp_tsdf_extract_surface_region: with a capacity, cloud_out is required, and normals_out if normals are wanted");
+    if (const char *why = region_refusal (t->cfg, *region)) return tsdf_fail (t, ICP_EINVAL, std::string ("icp_tsdf_extract_surface_region: ") + why);
+    TSDFCHK (t, hipSetDevice (t->device));
+    surface_plan p;
+    int rc = plan_surface (t, &p); if (rc) return rc;
+    const region_plan q = plan_region (t->cfg, *region, p);
+    tsdf_surface_args a = args_of (t, p, o.min_weight);
+    uint32_t total = 0u;
+    if ((rc = count_region_and_reserve (t, a, q, p, capacity, o.normals != 0u, &total))) return rc;
     if (a.limit) {
         launch_scatter (a, p, t->stream);
         TSDFCHK (t, hipGetLastError ());

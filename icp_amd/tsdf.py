@@ -1,6 +1,8 @@
 """Frame-to-model: a TSDF volume fused and ray-cast on the device (include/icp_amd.h: icp_tsdf_t, icp_tsdf_integrate, icp_tsdf_raycast,
 icp_tsdf_raycast_to, icp_tsdf_compose_pose), and its surface as a point cloud (icp_tsdf_extract_surface) or a triangle mesh
-(icp_tsdf_extract_mesh), and a cloud registered against the volume itself (icp_tsdf_register, icp_tsdf_register_from, track_to_volume).
+(icp_tsdf_extract_mesh), and a cloud registered against the volume itself (icp_tsdf_register, icp_tsdf_register_from, track_to_volume),
+and the moving volume: the window shifted by whole voxels on the device (icp_tsdf_shift), the surface that leaves it
+(icp_tsdf_extract_surface_region, kept_box) and the rule that decides when to shift (follow).
 
     vol = TSDFVolume(TSDFConfig(256, 256, 256, voxel=8.0, origin=(-1024, -1024, 0), mu=24.0))
     for pose, k, scale in track_to_model(icp, vol, frames, pose0, 300.0, 4000.0):
@@ -27,6 +29,13 @@ class icp_tsdf_t(C.Structure):
 
 class icp_tsdf_surface_t(C.Structure):
     _fields_ = [("min_weight", C.c_float), ("normals", C.c_uint32)]
+
+
+class icp_tsdf_region_t(C.Structure):
+    _fields_ = [("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("mode", C.c_uint32)]
+
+
+REGION_INSIDE, REGION_OUTSIDE = 0, 1
 
 
 class icp_tsdf_register_t(C.Structure):
@@ -103,6 +112,10 @@ def _lib():
                            ("icp_tsdf_mesh_case", (u32, C.POINTER(u32), C.POINTER(C.c_uint8))),
                            ("icp_tsdf_register", (vp, C.POINTER(icp_tsdf_register_t), vp, u32, vp, C.POINTER(icp_tsdf_registration_t))),
                            ("icp_tsdf_register_from", (vp, C.POINTER(icp_tsdf_register_t), vp, i32, vp, C.POINTER(icp_tsdf_registration_t))),
+                           ("icp_tsdf_shift", (vp, C.POINTER(C.c_int32))), ("icp_tsdf_get_window", (vp, C.POINTER(C.c_int32))),
+                           ("icp_tsdf_extract_surface_region", (vp, C.POINTER(icp_tsdf_surface_t), C.POINTER(icp_tsdf_region_t), u32, vp, vp, C.POINTER(u32))),
+                           ("icp_tsdf_kept_box", (cfg, C.POINTER(C.c_int32), C.POINTER(icp_tsdf_region_t))),
+                           ("icp_tsdf_follow", (cfg, C.POINTER(f32), u32, C.POINTER(C.c_int32))),
                            ("icp_tsdf_time", (vp, i32, cam, vp, vp, vp, f32, f32, u32, u32, C.POINTER(f32)))):
             f = getattr(L, name)
             f.restype, f.argtypes = i32, list(args)
@@ -137,6 +150,36 @@ def mesh_case(case_index):
     if rc:
         raise icp_amd.ICPError(rc, "icp_tsdf_mesh_case: the case index must be at most 255")
     return [tuple(edges[3 * t:3 * t + 3]) for t in range(n.value)]
+
+
+def _shift3(s):
+    s = [int(x) for x in s]
+    if len(s) != 3 or any(not -2 ** 31 <= x < 2 ** 31 for x in s):
+        raise ValueError("expected a shift of three int32")
+    return (C.c_int32 * 3)(*s)
+
+
+def kept_box(cfg, s):
+    """icp_tsdf_kept_box (host only): (lo, hi) of the box of voxels a shift by s keeps, lo_a = max (0, s_a), hi_a = max (lo_a, min (n_a,
+    n_a + s_a)); the members of extract_surface_region (lo, hi, outside=True) are what the shift drops."""
+    c, box = cfg._c(), icp_tsdf_region_t()
+    rc = _lib().icp_tsdf_kept_box(C.byref(c), _shift3(s), C.byref(box))
+    if rc:
+        raise icp_amd.ICPError(rc, "icp_tsdf_kept_box: bad arguments")
+    return tuple(box.lo), tuple(box.hi)
+
+
+def follow(cfg, point, threshold):
+    """icp_tsdf_follow (host only): the shift (three ints) that centres the window of cfg on `point` again, or (0, 0, 0) while the point
+    is at most `threshold` voxels from the centre on every axis."""
+    c, out = cfg._c(), (C.c_int32 * 3)()
+    pt = np.ascontiguousarray(point, np.float32).reshape(-1)
+    if pt.size != 3:
+        raise ValueError("expected a point of 3 floats")
+    rc = _lib().icp_tsdf_follow(C.byref(c), pt.ctypes.data_as(C.POINTER(C.c_float)), int(threshold), out)
+    if rc:
+        raise icp_amd.ICPError(rc, "icp_tsdf_follow: the point must be finite and within int32 voxels of the centre")
+    return tuple(out)
 
 
 class TSDFVolume:
@@ -246,6 +289,51 @@ class TSDFVolume:
             return cloud[:n], (nrm[:n] if normals else None)
         return cloud[:n], (nrm[:n] if normals else None), count.value
 
+    def extract_surface_region(self, lo, hi, outside=False, min_weight=1.0, normals=True, capacity=None):
+        """icp_tsdf_extract_surface_region: extract_surface's members with both ends in the box of voxels lo_a <= idx_a < hi_a (or, with
+        `outside`, every other member), the same records in the same relative order; the capacity convention is extract_surface's."""
+        opt, count = icp_tsdf_surface_t(min_weight, int(bool(normals))), C.c_uint32()
+        box = icp_tsdf_region_t((C.c_uint32 * 3)(*lo), (C.c_uint32 * 3)(*hi), REGION_OUTSIDE if outside else REGION_INSIDE)
+        if capacity is None:
+            self._chk(self._L.icp_tsdf_extract_surface_region(self._t, C.byref(opt), C.byref(box), 0, None, None, C.byref(count)))
+            room = count.value
+        else:
+            room = int(capacity)
+        cloud = np.empty((room, 8), np.float32)
+        nrm = np.empty((room, 4), np.float32) if normals else None
+        self._chk(self._L.icp_tsdf_extract_surface_region(self._t, C.byref(opt), C.byref(box), room, _ptr(cloud) if room else None,
+                                                          _ptr(nrm) if room else None, C.byref(count)))
+        n = min(count.value, room)
+        if capacity is None:
+            return cloud[:n], (nrm[:n] if normals else None)
+        return cloud[:n], (nrm[:n] if normals else None), count.value
+
+    def window(self):
+        """icp_tsdf_get_window: the cumulative shift of the window in voxels, three ints."""
+        c = (C.c_int32 * 3)()
+        self._chk(self._L.icp_tsdf_get_window(self._t, c))
+        return tuple(c)
+
+    def shift(self, s, extract=False, min_weight=1.0, normals=True):
+        """icp_tsdf_shift: the window moves by s voxels; the new voxel v holds the old voxel v + s, what enters is empty.  With `extract`
+        the surface the shift drops (extract_surface_region outside kept_box) is taken first and returned as (cloud, normals); else None.
+        self.cfg follows the window's origin."""
+        s3 = _shift3(s)
+        leaving = None
+        if extract:
+            lo, hi = kept_box(self.cfg, s)
+            leaving = self.extract_surface_region(lo, hi, True, min_weight, normals)
+        self._chk(self._L.icp_tsdf_shift(self._t, s3))
+        self.cfg = self.get_config()
+        return leaving
+
+    def time_shift(self, what, s, reps=20):
+        """icp_tsdf_time (diagnostic), what = 10: microseconds per launch of k_tsdf_shift by +s and -s in turn (the volume stays as it is);
+        11: per group of the launches of one extract_surface_region outside kept_box (s)."""
+        us = C.c_float()
+        self._chk(self._L.icp_tsdf_time(self._t, what, None, None, C.cast(_shift3(s), C.c_void_p), None, 0.0, 0.0, 0, reps, C.byref(us)))
+        return us.value
+
     def extract_mesh(self, min_weight=1.0, normals=True, vertex_capacity=None, triangle_capacity=None):
         """icp_tsdf_extract_mesh: the volume's surface as (cloud (n, 8), normals (n, 4) or None, triangles (m, 3) uint32): the vertices
         are extract_surface's members, a triangle is three member positions, in ascending cell index and table order.  Without capacities:
@@ -304,11 +392,25 @@ class TSDFVolume:
         return us.value
 
 
-def track_to_model(icp, volume, frames, pose0, z_near, z_far, normals=False):
+def _follow_camera(volume, pose, follow_, on_shift):
+    """After a frame: hand pose . (0, 0, distance) to follow (); a non-zero shift extracts what leaves, shifts, and calls on_shift."""
+    distance, threshold = follow_
+    P = np.asarray(pose, np.float64).reshape(3, 4)
+    point = (P[:, 2] * float(distance) + P[:, 3]).astype(np.float32)
+    s = follow(volume.cfg, point, threshold)
+    if any(s):
+        cloud, nrm = volume.shift(s, extract=True)
+        if on_shift is not None:
+            on_shift(s, cloud, nrm)
+
+
+def track_to_model(icp, volume, frames, pose0, z_near, z_far, normals=False, follow=None, on_shift=None):
     """Frame-to-model tracking as a generator over `frames`, an iterable of (depth, rgb or None) image pairs of the handle's RGB-D
     configuration.  The first frame is integrated at pose0.  Every later frame: the volume's view from the current pose goes into F
     (raycast_to; with `normals` also into NORMALS_F) and buildRBC follows; the front end writes the frame into M; reset_transform and run;
-    pose = compose_pose (pose, T); the frame is integrated at the new pose.  Yields (pose, k, scale) per frame, (pose0, None, 1.0) first."""
+    pose = compose_pose (pose, T); the frame is integrated at the new pose.  Yields (pose, k, scale) per frame, (pose0, None, 1.0) first.
+    follow = (distance, threshold): the volume follows the camera — after a frame is integrated the point pose . (0, 0, distance) goes to
+    follow (); a non-zero shift s runs volume.shift (s, extract=True) and on_shift (s, cloud, normals) receives the surface that left."""
     cam = rgbd.get_config(icp)
     pose = _pose(pose0).copy()
     first = True
@@ -323,13 +425,15 @@ def track_to_model(icp, volume, frames, pose0, z_near, z_far, normals=False):
             k = icp.run()
             pose, scale = compose_pose(pose, icp.read(icp_amd.Memory.T))
         volume.integrate(cam, pose, depth, colour)
+        if follow is not None:
+            _follow_camera(volume, pose, follow, on_shift)
         yield pose.copy(), k, scale
 
 
-def track_to_volume(icp, volume, frames, pose0, max_iterations=20):
+def track_to_volume(icp, volume, frames, pose0, max_iterations=20, follow=None, on_shift=None):
     """track_to_model without the view, as a generator over `frames`.  The first frame is integrated at pose0.  Every later frame: the front
     end writes it into M (rgbd.write), register_from registers M against the volume starting at the last pose, and the frame is integrated
-    at the new pose.  Yields (pose, Registration) per frame, (pose0, None) first."""
+    at the new pose.  Yields (pose, Registration) per frame, (pose0, None) first.  follow, on_shift: as in track_to_model."""
     cam = rgbd.get_config(icp)
     pose = _pose(pose0).copy()
     first = True
@@ -342,4 +446,6 @@ def track_to_volume(icp, volume, frames, pose0, max_iterations=20):
             reg = volume.register_from(icp, icp_amd.Memory.M, pose, max_iterations)
             pose = reg.pose.copy()
         volume.integrate(cam, pose, depth, colour)
+        if follow is not None:
+            _follow_camera(volume, pose, follow, on_shift)
         yield pose.copy(), reg

@@ -20,6 +20,7 @@
 #ifndef ICP_ALGORITHMS_HPP
 #define ICP_ALGORITHMS_HPP
 
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -336,7 +337,7 @@ namespace ICP
 
     /*! \brief Frame-to-model (icp_tsdf_*, include/icp_amd.h): a truncated signed distance volume on the device that registered frames
      *         are fused into (`integrate`) and whose view from a pose (`raycast`, `raycastTo`) is the fixed frame of the next
-     *         registration — an organised grid with normals.  `extractSurface` gives the model itself as a point cloud, `extractMesh` as a triangle mesh.  A pose is 12
+     *         registration — an organised grid with normals.  `extractSurface` gives the model itself as a point cloud, `extractMesh` as a triangle mesh; `shift` moves the volume's window by whole voxels and `shiftAndExtract` keeps the surface that leaves it.  A pose is 12
      *         floats, row-major [R | t], camera -> world.  The reference has no model and no such class. */
     class TSDFVolume
     {
@@ -394,6 +395,38 @@ namespace ICP
         /*! the same of F or M (which = ICP_MEM_F / ICP_MEM_M) of an initialised handle, device to device (icp_tsdf_register_from) */
         icp_tsdf_registration_t registerFrom (icp_handle h, int which, const float *pose12, const icp_tsdf_register_t *opt = nullptr)
         { icp_tsdf_registration_t r; check (icp_tsdf_register_from (t, opt, h, which, pose12, &r)); return r; }
+        /*! the moving volume (icp_tsdf_shift): the window moves by s voxels — the new voxel v holds the old voxel v + s, what enters is
+         *  empty; config () gives the window's origin afterwards */
+        void shift (const int32_t s[3]) { check (icp_tsdf_shift (t, s)); }
+        /*! the cumulative shift of the window in voxels (icp_tsdf_get_window) */
+        std::array<int32_t, 3> window () { std::array<int32_t, 3> c; check (icp_tsdf_get_window (t, c.data ())); return c; }
+        /*! extractSurface's members with both ends inside the region's box, or every other one (icp_tsdf_extract_surface_region): the
+         *  same records in the same relative order; returns their number */
+        uint32_t extractSurfaceRegion (const icp_tsdf_region_t &region, std::vector<float> &cloud, std::vector<float> *normals = nullptr, float min_weight = 1.f)
+        {
+            const icp_tsdf_surface_t o = { min_weight, normals ? 1u : 0u };
+            uint32_t n = 0;
+            check (icp_tsdf_extract_surface_region (t, &o, &region, 0, nullptr, nullptr, &n));
+            cloud.resize ((size_t) n * 8);
+            if (normals) normals->resize ((size_t) n * 4);
+            if (n) check (icp_tsdf_extract_surface_region (t, &o, &region, n, cloud.data (), normals ? normals->data () : nullptr, &n));
+            return n;
+        }
+        /*! the box of voxels a shift by s keeps, mode OUTSIDE: the region of what the shift drops (icp_tsdf_kept_box, host only) */
+        static icp_tsdf_region_t keptBox (const icp_tsdf_t &cfg, const int32_t s[3])
+        {
+            icp_tsdf_region_t box;
+            if (icp_tsdf_kept_box (&cfg, s, &box) != ICP_OK) throw std::runtime_error ("TSDFVolume::keptBox: bad arguments");
+            return box;
+        }
+        /*! the surface a shift by s drops into `cloud` (and `normals`), then the shift: no member of the surface is lost; returns the
+         *  number of points that left */
+        uint32_t shiftAndExtract (const int32_t s[3], std::vector<float> &cloud, std::vector<float> *normals = nullptr, float min_weight = 1.f)
+        {
+            const uint32_t n = extractSurfaceRegion (keptBox (config (), s), cloud, normals, min_weight);
+            shift (s);
+            return n;
+        }
         /*! out12 = pose12 o (R (q), t) of the engine's T8; returns T8's scale */
         static float composePose (const float *pose12, const float *T8, float *out12)
         {

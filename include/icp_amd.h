@@ -1061,7 +1061,10 @@ typedef struct {
     uint32_t colour;                        /* 0 or 1: the volume keeps C */
 } icp_tsdf_t;
 /* Life cycle.  ICP_EINVAL for every field outside its range, ICP_ENOMEM if the device cannot hold the volume (8 bytes a voxel, 24 with
- * colour).  icp_tsdf_last_error (NULL): why the last icp_tsdf_create of this thread failed.  A refused call of any entry below leaves the
+ * colour; the first icp_tsdf_shift allocates a second buffer of the same size and keeps it until destroy: 16 bytes a voxel from then on,
+ * 48 with colour).  icp_tsdf_reset clears the voxels and keeps the window where icp_tsdf_shift has moved it: the origin and the cumulative
+ * shift stay (for a volume that was never shifted, the state after create).  icp_tsdf_get_config returns the window's current origin.
+ * icp_tsdf_last_error (NULL): why the last icp_tsdf_create of this thread failed.  A refused call of any entry below leaves the
  * volume (and the handle of icp_tsdf_raycast_to) as it was.  All calls are blocking. */
 int icp_tsdf_create (icp_tsdf_handle *out, int device, const icp_tsdf_t *cfg);
 int icp_tsdf_destroy (icp_tsdf_handle t);
@@ -1208,6 +1211,41 @@ typedef struct {
 } icp_tsdf_registration_t;
 int icp_tsdf_register (icp_tsdf_handle t, const icp_tsdf_register_t *opt, const void *cloud_nx8, uint32_t n, const float *pose12, icp_tsdf_registration_t *out);
 int icp_tsdf_register_from (icp_tsdf_handle t, const icp_tsdf_register_t *opt, icp_handle h, int which, const float *pose12, icp_tsdf_registration_t *out);
+/* Moving volume: the window of the volume follows the camera by whole voxels, on the device (KinFu large-scale, Kintinuous, Open3D's
+ * scalable volume), and the part of the surface that a shift drops can be extracted first.  tests/tsdf_shift_ref.py restates it.
+ *    State.  The handle keeps base, the origin given at create, and c, the cumulative shift per axis in voxels, 0 at create.
+ *    Shift by s.  c'_a = c_a + s_a;  origin_a = base_a + (float) c'_a * voxel in fp32, one multiplication and one addition, each rounded
+ *    on its own: recomputed from c', never accumulated, so a thousand shifts round once.  The new voxel (i, j, k) holds the old voxel
+ *    (i + s_x, j + s_y, k + s_z) where that lies inside the volume — D, W and C as bit patterns: a NaN, its payload and a -0 survive —;
+ *    every other voxel becomes all-zero bits, the state after create.  |s_a| >= n_a on any axis empties the volume and still moves the
+ *    window.  s = 0: no launch, nothing changes, ICP_OK.  World points keep their values: old voxel v + s and new voxel v have the same
+ *    centre up to the rounding of the origin.
+ *    Refusals, the volume untouched: ICP_EINVAL for a NULL pointer, a new |c_a| > 2^24 (so that (float) c_a stays exact), a new origin
+ *    that is not finite;  ICP_ENOMEM if the device cannot hold the second buffer.
+ *    Every other entry — integrate, both ray casts, read and write, both extractions, both registrations — sees the new origin and the
+ *    new contents after a shift, with no other change.
+ * icp_tsdf_get_window returns c. */
+int icp_tsdf_shift (icp_tsdf_handle t, const int32_t shift[3]);
+int icp_tsdf_get_window (icp_tsdf_handle t, int32_t cumulative[3]);
+/* The part of the surface inside or outside a box of voxels.  A member (v, a) of icp_tsdf_extract_surface is INSIDE iff both its ends, v and
+ * v + e_a, lie in the box lo_b <= idx_b < hi_b; it is OUTSIDE otherwise.  The call returns exactly the full extraction's records for the
+ * members of the chosen kind: the same bits and the same normals (gradients look at neighbours wherever they lie), in the same relative
+ * order.  For any box INSIDE and OUTSIDE partition the full extraction; an empty box (lo == hi on some axis) makes every member OUTSIDE,
+ * the full box every member INSIDE.  The counting call, the capacity prefix and the refusals are icp_tsdf_extract_surface's; in addition
+ * ICP_EINVAL for a NULL region, lo > hi, hi > n, a mode other than 0 or 1.  The volume is never modified.  The mesh of a region is not
+ * offered: stitching vertex indices across slabs is later work.
+ * icp_tsdf_kept_box (host only) gives the box a shift by s keeps: lo_a = max (0, s_a) (at most n_a), hi_a = max (lo_a, min (n_a, n_a + s_a)),
+ * mode OUTSIDE.  Extracting with that region and then shifting by s loses no member, whatever the signs of s: a member whose low end stays
+ * but whose high end leaves is OUTSIDE (a rule that looked at v alone would drop it from both sets).  ICP_EINVAL for a NULL pointer. */
+typedef struct { uint32_t lo[3], hi[3]; uint32_t mode; } icp_tsdf_region_t;   /* voxels lo_a <= idx_a < hi_a, hi_a <= n_a, lo_a <= hi_a */
+enum { ICP_TSDF_REGION_INSIDE = 0, ICP_TSDF_REGION_OUTSIDE = 1 };
+int icp_tsdf_extract_surface_region (icp_tsdf_handle t, const icp_tsdf_surface_t *opt, const icp_tsdf_region_t *region,
+                                     uint32_t capacity, void *cloud_out, float *normals_out, uint32_t *count);
+int icp_tsdf_kept_box (const icp_tsdf_t *cfg, const int32_t shift[3], icp_tsdf_region_t *out);
+/* When to shift (host only; KinFu large-scale's rule), in double:  centre_a = origin_a + 0.5 (n_a - 1) voxel,  d_a = (point_a - centre_a) /
+ * voxel.  The shift is 0 on every axis if max |d_a| <= threshold, otherwise shift_a = lrint (d_a) on every axis (ties to even): the window
+ * is centred on the point again.  ICP_EINVAL for a NULL pointer, a NaN d_a or one past the range of int32_t. */
+int icp_tsdf_follow (const icp_tsdf_t *cfg, const float point[3], uint32_t threshold, int32_t shift_out[3]);
 /* Diagnostic (tools/diag/tsdf_time.py): `reps` launches of one kernel between two events on the volume's stream, after one untimed launch.
  * what = 0: k_tsdf_integrate of (depth, rgb) at pose12 — the volume is left as reps + 1 integrations leave it;  what = 1: k_tsdf_raycast as
  * icp_tsdf_raycast (cam, pose12, z_near, z_far, side) runs it, into scratch (depth, rgb unused);  what = 2: the launches of one
@@ -1216,7 +1254,10 @@ int icp_tsdf_register_from (icp_tsdf_handle t, const icp_tsdf_register_t *opt, i
  * pose12 may be NULL);  what = 5: the launches of one icp_tsdf_extract_mesh with normals and min_weight 1 as a group, every vertex and
  * triangle into scratch;  what = 6: its cell sweep alone;  what = 7: its triangle pass alone;  what = 8: the two launches of one iteration of
  * icp_tsdf_register as a group, over the host cloud `depth` points to (side records of 8 floats, 1 .. 2^20) from pose12, the state held at
- * that pose with `done` clear (every group does the same work; the record goes to scratch);  what = 9: k_tsdf_reg_moments of that group alone.
+ * that pose with `done` clear (every group does the same work; the record goes to scratch);  what = 9: k_tsdf_reg_moments of that group alone;
+ * what = 10: k_tsdf_shift alone for the shift of three int32_t that `depth` points to, by +s and -s in turn, from the live buffers into the
+ * second ones, which are not swapped in: the volume stays as it is;  what = 11: the launches of one icp_tsdf_extract_surface_region with
+ * normals and min_weight 1 as a group, for icp_tsdf_kept_box of that shift (for 10 and 11 nothing else but reps is used).
  * Microseconds per launch (per group). */
 int icp_tsdf_time (icp_tsdf_handle t, int what, const icp_rgbd_t *cam, const float *pose12, const uint16_t *depth, const uint8_t *rgb, float z_near, float z_far,
                    uint32_t side, uint32_t reps, float *us_per_launch);

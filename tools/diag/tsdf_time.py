@@ -22,7 +22,13 @@
     end-to-end error of that registration; and in the same run, on the same volume, the route it replaces: a blocking raycast_to with
     normals, buildRBC, a point-to-plane iteration, and a blocking track_to_model step beside a blocking register_from of 10 iterations,
     each with its end-to-end error.  Written to profiles/tsdf_register_time.txt as well.
-    python tools/diag/tsdf_time.py [--reps N] [--skip-512] [--surface | --mesh | --register]"""
+  - with --shift (and nothing else then): the moving volume on the same scene at 256^3 and 512^3, without and with colour: k_tsdf_shift
+    alone (what = 10) for a shift of n / 8 voxels along x, y and z against two passes over the volume's bytes at the HBM rate; the launches
+    of one region extraction (what = 11) for the kept box of each of those shifts — the n / 8 slab that leaves — beside the full
+    extraction (what = 2) and a blocking icp_tsdf_reset of the same run; a blocking shift (extract=True) along z (the volume written
+    again before each sample) against the route it replaces: icp_tsdf_read, a numpy roll, icp_tsdf_write.  Written to
+    profiles/tsdf_shift_time.txt as well.
+    python tools/diag/tsdf_time.py [--reps N] [--skip-512] [--surface | --mesh | --register | --shift]"""
 import argparse
 import os
 import statistics
@@ -62,7 +68,7 @@ def blocking(call, reps):
     return statistics.median(t)
 
 
-def corner_volumes(a):
+def corner_volumes(a, colour=1):
     """The corner scene of tests/tsdf_ref.py fused from six 640 x 480 frames into 256^3 and 512^3 voxels over its 1.02 m cube, mu = 3 voxel edges."""
     sys.path[:0] = [os.path.join(ROOT, "tests")]
     import tsdf_ref as T                # noqa: E402
@@ -71,9 +77,9 @@ def corner_volumes(a):
     frames = [(T.look_at(eye).reshape(12).astype(np.float32),) + T.render_corner(T.look_at(eye), d)[:2] for eye in T.EYES]
     for n in (256,) if a.skip_512 else (256, 512):
         voxel = 1024.0 / n
-        v = tsdf.TSDFVolume(tsdf.TSDFConfig(n, n, n, voxel, (-64.0, -64.0, -64.0), 3.0 * voxel, 64.0, 1))
-        for pose, depth, colour in frames:
-            v.integrate(cam, pose, depth, colour)
+        v = tsdf.TSDFVolume(tsdf.TSDFConfig(n, n, n, voxel, (-64.0, -64.0, -64.0), 3.0 * voxel, 64.0, colour))
+        for pose, depth, rgb in frames:
+            v.integrate(cam, pose, depth, rgb if colour else None)
         yield n, v
         v.close()
 
@@ -218,6 +224,58 @@ def register(a):
         f.write("\n".join(lines) + "\n")
 
 
+def shift(a):
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    for colour in (0, 1):
+        for n, v in corner_volumes(a, colour):
+            name = "shift %d^3 %-14s" % (n, "with colour" if colour else "without colour")
+            nbytes = n ** 3 * (24 if colour else 8)
+            floor = 2.0 * nbytes / HBM_MEASURED * 1e6
+            full = median(lambda: v.time_kernel(2, reps=20), a.reps)
+            reset_us = None
+            _, _, count = v.extract_surface(capacity=0)
+            say("%s the full extraction's launches %9.2f us (%d points)   two passes over %.0f MB at 6.29 TB/s %8.2f us" % (name, full, count, nbytes / 1e6, floor))
+            for axis, s in (("x", (n // 8, 0, 0)), ("y", (0, n // 8, 0)), ("z", (0, 0, n // 8)), ("-z", (0, 0, -(n // 8)))):
+                us = median(lambda: v.time_shift(10, s, reps=20), a.reps)
+                reg = median(lambda: v.time_shift(11, s, reps=20), a.reps)
+                lo, hi = tsdf.kept_box(v.cfg, s)
+                _, _, leaving = v.extract_surface_region(lo, hi, True, capacity=0)
+                say("%s n / 8 along %-2s  k_tsdf_shift %9.2f us = %.2f of the two passes (%.2f TB/s)   the leaving slab's extraction %9.2f us = %.2f of the full one (%d points)"
+                    % (name, axis, us, us / floor, 2.0 * nbytes / (us * 1e-6) / 1e12, reg, reg / full, leaving))
+            dw, col = v.read()
+            reps = a.reps if n <= 256 else min(a.reps, 5)
+            s = (0, 0, n // 8)
+            t = []
+            for _ in range(reps):
+                v.write(dw, col)
+                t0 = time.perf_counter(); cloud, nrm = v.shift(s, extract=True); t.append((time.perf_counter() - t0) * 1e3)
+            v.write(dw, col)
+            t0 = time.perf_counter(); v.shift(s); t_plain = (time.perf_counter() - t0) * 1e3
+            host = []
+            for _ in range(3 if n <= 256 else 1):
+                v.write(dw, col)
+                t0 = time.perf_counter()
+                d2, c2 = v.read()
+                d3 = np.zeros_like(d2); d3[:n - s[2]] = d2[s[2]:]
+                c3 = None
+                if c2 is not None:
+                    c3 = np.zeros_like(c2); c3[:n - s[2]] = c2[s[2]:]
+                v.write(d3, c3)
+                host.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter(); v.reset(); reset_us = (time.perf_counter() - t0) * 1e6
+            say("%s blocking shift (extract=True) along z %9.3f ms (%d points to the host), shift alone %9.3f ms   read + numpy + write %9.1f ms   blocking icp_tsdf_reset %9.2f us"
+                % (name, statistics.median(t), cloud.shape[0], t_plain, statistics.median(host), reset_us))
+            del dw, col
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "tsdf_shift_time.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--reps", type=int, default=20)
@@ -225,6 +283,7 @@ def main():
     ap.add_argument("--surface", action="store_true")
     ap.add_argument("--mesh", action="store_true")
     ap.add_argument("--register", action="store_true")
+    ap.add_argument("--shift", action="store_true")
     a = ap.parse_args()
     if a.surface:
         return surface(a)
@@ -232,6 +291,8 @@ def main():
         return mesh(a)
     if a.register:
         return register(a)
+    if a.shift:
+        return shift(a)
     depth, colour = frame()
     cam = rgbd.RGBDConfig()
     print("frame: %d of %d pixels valid, depth %d .. %d" % ((depth != 0).sum(), depth.size, depth[depth != 0].min(), depth.max()), flush=True)
